@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- VMP iterations/sec of the sparse-GP node's sweep on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload T|C2|C3|N1M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload T|C2|C3|N1M] [--blocks B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,11 @@ K_uf, the summed :v messages (Psi2, b), q(v) incl. Sigma_v and Uv, the summed :w
 average energy.  Inputs are resident in HBM before the timed region.  With N > 1 the points are sharded
 over the ranks (strong scaling: the data set is fixed) and the packed statistics are summed by one RCCL
 all-reduce per sweep.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, runs W warm-up sweeps, times exactly K sweeps (in B back-to-back blocks of K / B, default one block;
+the median block is reported), writes the last sweep's outputs if --dump-outputs is given and prints the line.
+--full adds everything else after the timed region: per-phase durations and rooflines (kernels timed alone), parity
+against the CPU oracle, the CPU baselines, the other BASELINE.json configurations and, at N > 1, the N1M scaling leg.
 """
 from __future__ import annotations
 
@@ -188,16 +193,50 @@ def scaling_leg(world, rank, local_rank, barrier):
             "collective": {"backend": sw.backend, "payload_doubles": int(eng.stats.numel())}}
 
 
+def dump_outputs(dev, path):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last sweep, as float64 .npy files -- q(v)
+    (mu_v, Sigma_v, Uv), the summed statistics the sweep worked from (Psi2, B, s_yy, s_w, n_points) and the sweep's scalars
+    (energy, sum_I1, sum_I2, logdet_kuu, logdet_lambda).  About 6 MB at M = 512."""
+    from gaussianprocessnode_amd import _lib
+    mu, Sig, Uv = dev.posterior()
+    Psi2, B, sc = dev.stats()
+    s = dev.scalars()
+    arrays = {"mu_v": mu, "Sigma_v": Sig, "Uv": Uv, "Psi2": Psi2, "B": B,
+              "s_yy": sc[_lib.SGP_S_YY:_lib.SGP_S_YY + 1], "s_w": sc[_lib.SGP_S_W:_lib.SGP_S_W + 1],
+              "n_points": sc[_lib.SGP_S_N:_lib.SGP_S_N + 1]}
+    for name in ("energy", "sum_I1", "sum_I2", "logdet_kuu", "logdet_lambda"):
+        arrays[name] = np.array([getattr(s, name)])
+    total = sum(np.asarray(a).nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the 64 MB limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", default="T", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--blocks", type=int, default=None,
-                    help="back-to-back timed blocks of --steps sweeps each (default 15, 5 at N > 1e5); the MEDIAN block is reported")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the timed CPU baselines")
+    ap.add_argument("--blocks", type=int, default=1,
+                    help="split the --steps timed sweeps into this many back-to-back blocks (it must divide --steps); the MEDIAN "
+                         "block is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed sweep's outputs to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-phase durations, rooflines, parity, CPU baselines, other configurations and sizes")
     args = ap.parse_args()
+    N, M, D = WORKLOADS[args.workload]
+    if args.steps is None:
+        args.steps = 300 if N <= 100000 else 20
+    if args.warmup is None:
+        args.warmup = 30 if N <= 100000 else 3
+    if args.blocks < 1 or args.steps % args.blocks:
+        ap.error(f"--blocks {args.blocks} must be positive and divide --steps {args.steps}")
+    per_block = args.steps // args.blocks
 
     # Host side of this rank on the CPUs of the GPU's NUMA node, before torch or HIP create a thread (what numactl --cpunodebind
     # does; gaussianprocessnode_amd/hostbind.py says why: an unconfined process on a two-socket host runs its short blocks 6 % slower
@@ -245,11 +284,6 @@ def main():
         else:
             dist.init_process_group(backend="nccl", device_id=torch.device(f"cuda:{local_rank}"))
 
-    N, M, D = WORKLOADS[args.workload]
-    if args.steps is None:
-        args.steps = 300 if N <= 100000 else 20
-    if args.warmup is None:
-        args.warmup = 30 if N <= 100000 else 3
     X, Xu, y, Xt, yt = synthetic(N, M, D)
     lo, hi = shard_bounds(N, world, rank)
 
@@ -272,20 +306,19 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Timed region: R back-to-back blocks, each EXACTLY --steps full sweeps bracketed by barrier + synchronize on both sides (max
-    # over ranks per block); the MEDIAN block is the reported one.  One block of 20 sweeps is 5 ms of timing -- a single hiccup of
-    # the host thread moved round 3's driver line by 3 % against the same process' 200-sweep figure.
-    if args.blocks is None:
-        args.blocks = 15 if N <= 100000 else 5
+    # Timed region: EXACTLY --steps full sweeps, in --blocks back-to-back blocks (default one) each bracketed by barrier +
+    # synchronize on both sides (max over ranks per block); the MEDIAN block is the reported one.  One block of 20 sweeps is 5 ms
+    # of timing -- a single hiccup of the host thread moved round 3's 20-sweep line by 3 % -- so short runs want more steps.
     for _ in range(args.warmup):
         sweep.sweep()
     barrier()
-    dev.phase_totals(reset=True)
+    if args.full:
+        dev.phase_totals(reset=True)
     block_s = []
-    for _ in range(max(1, args.blocks)):
+    for _ in range(args.blocks):
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(per_block):
             sweep.sweep()
         barrier()
         block_s.append(time.perf_counter() - t0)
@@ -294,8 +327,60 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         block_s = [float(v) for v in t.cpu()]
     elapsed = float(np.median(block_s))
+    n_loc = hi - lo
+    plan = dev.overlap_plan()            # (hooked sweeps too: one all-reduce per statistics group, include/sgp_hip.h)
+    Qp = (M + 63) // 64 * 64
+    pack_doubles = (Qp // 64) * (Qp // 64 + 1) // 2 * 4096 + Qp + 8 + 1      # [lower 64 x 64 tiles | B | scalars | Ryy]
 
-    # ---- live per-kernel numbers (this rank's shard) ------------------------------------------------
+    out = {
+        "metric": "VMP iterations/sec (sparse-GP node sweep, kin40k-shaped synthetic)",
+        "value": per_block / elapsed,
+        "unit": "iterations/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / per_block,
+        "blocks": {"count": len(block_s), "steps_per_block": per_block, "reported": "median block",
+                   "ms_per_step_min": 1e3 * min(block_s) / per_block, "ms_per_step_median": 1e3 * elapsed / per_block,
+                   "ms_per_step_max": 1e3 * max(block_s) / per_block,
+                   "iterations_per_s_over_all_blocks": args.steps / sum(block_s)},
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"{args.workload}: N={N} M={M} D={D} UniSGP regression, ARD-SE kernel at the trained kin40k "
+                               f"hyper-parameters, w=1e4, prior N(0,50I), jitter 0",
+                   "points_per_gpu": n_loc,
+                   "parallelism": f"data-sharded x{world}, " + (f"{len(plan)} all-reduces per sweep (one per statistics group) of the packed "
+                                                                f"exchange buffer, {pack_doubles} f64 in all" if (plan and sweep.hooked) else
+                                                                f"1 all-reduce of the packed exchange buffer ({pack_doubles} f64)"),
+                   "variant": "W' trace form (SURVEY.md Appendix A): sum I1 / sum I2 from the reduced statistics, no per-point "
+                              "TRSM / TRMM (their 2 n M^2 flop are not part of the timed sweep)",
+                   "collective": {"backend": sweep.backend, "world_size_seen": sweep.world,
+                                  "where": "inside sgp_sweep (C ABI all-reduce hook) on the sweep's stream" if sweep.hooked
+                                           else "none (single rank)"}},
+        "host_binding": host_binding,
+        "sweep_order": ({"kind": "overlapped", "groups": plan,
+                         "note": "statistics in tile-row groups (first on all CUs, the others on a CU-masked queue) while the Lambda "
+                                 "chain factors the tile columns it has; `local` and `finish1_lambda_chain` overlap in time"}
+                        if plan else {"kind": "plain", "note": "statistics, then the Lambda chain"}),
+    }
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(dev, args.dump_outputs)
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
+    # ---- --full: live per-kernel numbers (this rank's shard) -----------------------------------------
     # (1) averages over the K timed sweeps, from in-kernel first-block-in / last-block-out stamps (100 MHz clock)
     #     accumulated on the device inside the timed sweeps -- no host interaction in the timed region;
     # (2) HIP events around eager launches of the same kernel on the same stream, right after the timed region (the
@@ -303,13 +388,11 @@ def main():
     phase_us, n_counted = dev.phase_totals()
     tick_us = lambda i: float(phase_us[i])
     stream = eng.stream.cuda_stream
-    n_loc = hi - lo
     syrk_flops = float(n_loc) * M * (M + 1)                     # SYRK lower half n M (M+1)
     # The SYRK of the timed sweeps.  Plain order: ONE launch over all lower tiles.  Overlapped sweep (sgp_overlap_plan): one launch
     # per statistics group, the first on all CUs, the others on the CU-masked stream -- each is timed alone with HIP events on
     # the stream (and the CUs) it uses inside the sweep; `achieved` = the sweep's SYRK flops / the sum of its launches =
     # (flops per launch) / (average launch duration), the quantity rocprofv3 --kernel-trace --stats shows for k_syrk_direct.
-    plan = dev.overlap_plan()            # (hooked sweeps too: one all-reduce per statistics group, include/sgp_hip.h)
     ntiles_all = (M + 63) // 64 * ((M + 63) // 64 + 1) // 2
     # (SGP_BENCH_SKIP_ALONE: the rocprofv3 --pmc passes of tools/measure_round.sh -- every k_syrk_direct launch in their output is
     # then one of the timed sweeps' own; the stand-alone timings are skipped and the roofline block is not meaningful)
@@ -342,39 +425,9 @@ def main():
     sclk_mfma, mfma_probe_tflops, n_cus = clocks[0], clocks[1], int(clocks[3])
     peak_at_clock = n_cus * 4 * 32.0 * sclk_mfma * 1e6 / 1e12     # 4 SIMDs x (2048 flop / 64 cycles) per CU at the measured clock
     f1_us = tick_us(_lib.SGP_T_FINISH1)
-    Qp = (M + 63) // 64 * 64
-    pack_doubles = (Qp // 64) * (Qp // 64 + 1) // 2 * 4096 + Qp + 8 + 1      # [lower 64 x 64 tiles | B | scalars | Ryy]
     chain_floor_us = Qp * PIVOT_CYCLES / sclk.value              # the pivots of one factorisation, nothing else
 
-    out = {
-        "metric": "VMP iterations/sec (sparse-GP node sweep, kin40k-shaped synthetic)",
-        "value": args.steps / elapsed,
-        "unit": "iterations/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "blocks": {"count": len(block_s), "steps_per_block": args.steps, "reported": "median block",
-                   "ms_per_step_min": 1e3 * min(block_s) / args.steps, "ms_per_step_median": 1e3 * elapsed / args.steps,
-                   "ms_per_step_max": 1e3 * max(block_s) / args.steps,
-                   "iterations_per_s_over_all_blocks": len(block_s) * args.steps / sum(block_s)},
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"{args.workload}: N={N} M={M} D={D} UniSGP regression, ARD-SE kernel at the trained kin40k "
-                               f"hyper-parameters, w=1e4, prior N(0,50I), jitter 0",
-                   "points_per_gpu": n_loc,
-                   "parallelism": f"data-sharded x{world}, " + (f"{len(plan)} all-reduces per sweep (one per statistics group) of the packed "
-                                                                f"exchange buffer, {pack_doubles} f64 in all" if (plan and sweep.hooked) else
-                                                                f"1 all-reduce of the packed exchange buffer ({pack_doubles} f64)"),
-                   "variant": "W' trace form (SURVEY.md Appendix A): sum I1 / sum I2 from the reduced statistics, no per-point "
-                              "TRSM / TRMM (their 2 n M^2 flop are not part of the timed sweep)",
-                   "collective": {"backend": sweep.backend, "world_size_seen": sweep.world,
-                                  "where": "inside sgp_sweep (C ABI all-reduce hook) on the sweep's stream" if sweep.hooked
-                                           else "none (single rank)"}},
-        "host_binding": host_binding,
+    out.update({
         "sclk_mhz": sclk.value,
         "sclk_mhz_under_mfma_f64": sclk_mfma,
         "roofline": {"kernel": "k_syrk_direct (Psi2 = K_uf K_uf^T, v_mfma_f64_16x16x4_f64, operands straight from global memory; k_syrk_stream where the SYRK does not fill the chip)", "bound": "mfma",
@@ -413,17 +466,14 @@ def main():
                           "algorithmic_bytes_per_launch": 8.0 * n_loc * dev.stats_layout()[2],
                           "note": "41 MB at T; PMC WRITE_SIZE 41.6 MB.  Not store-bound: the same store pattern alone sustains 6.7 TB/s "
                                   "(tools/store_bw_probe.hip); the kernel's phases add up, profiles/r04_ab_log.txt [19]"},
-        "sweep_order": ({"kind": "overlapped", "groups": plan,
-                         "note": "statistics in tile-row groups (first on all CUs, the others on a CU-masked queue) while the Lambda "
-                                 "chain factors the tile columns it has; `local` and `finish1_lambda_chain` overlap in time"}
-                        if plan else {"kind": "plain", "note": "statistics, then the Lambda chain"}),
         "phases_us": {"sweep_device": tick_us(_lib.SGP_T_SWEEP), "gram_uf": tick_us(_lib.SGP_T_GRAM),
                       "gram_uf_alone_hip_events": gram_us_alone, "syrk": syrk_us,
                       "local": tick_us(_lib.SGP_T_LOCAL), "gap_local_to_finish": tick_us(_lib.SGP_T_GAP_LOCAL_FINISH),
                       "finish1_lambda_chain": tick_us(_lib.SGP_T_FINISH1), "finish2_traces": tick_us(_lib.SGP_T_FINISH2)},
-    }
+    })
 
-    # N > 1: the scaling regime of the design, measured in the same run (all ranks take part; after the headline's timed region)
+    # N > 1 (--full): the scaling regime of the design, measured in the same run (all ranks take part; after the headline's timed
+    # region)
     if args.workload == "T" and (world > 1 or os.environ.get("SGP_BENCH_SCALING") is not None):
         try:
             out.setdefault("extra", {})["scaling_workload"] = scaling_leg(world, rank, local_rank, barrier)
@@ -528,10 +578,7 @@ def main():
                     out.setdefault("extra", {})["error"] = repr(e)
         if ctx:
             ctx.__exit__(None, None, None)
-        print(json.dumps(out))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@ D=gaussianprocessnode_amd/csrc
 for i in $(seq $R); do
   for v in $A $B; do
     cp $D/libsgp_hip_$v.so $D/libsgp_hip.so
-    SGP_BENCH_SKIP_ALONE=1 timeout -k 10 300 python bench.py --no-cpu-baseline --steps 1000 "$@" 2>/dev/null | python -c "
+    SGP_BENCH_SKIP_ALONE=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 1000 "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', round(d['value'],1), 'chain', round(d['phases_us']['finish1_lambda_chain'],1))"
   done

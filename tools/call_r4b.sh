@@ -6,7 +6,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -q > $O/pytest.txt 2>&1; rc=$?
 tail -15 $O/pytest.txt
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "pytest was killed: stopping"; exit 1; fi
 bash tools/ab_multi.sh 2 "base|base|" "new|new|" 2>&1 | tee $O/ab.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_T.json 2> $O/bench_T.err; echo "bench rc $?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_T.json 2> $O/bench_T.err; echo "bench rc $?"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r4b/bench_T.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "pytest was killed: stopping"; 
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 300 python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 tools/rehearse_two_ranks.py 2>&1 | grep -E "rank [01]\]|Error|error" > $O/rehearse_small.txt; tail -6 $O/rehearse_small.txt
 RH_N=20000 RH_M=512 timeout -k 10 300 python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 tools/rehearse_two_ranks.py 2>&1 | grep -E "rank [01]\]|Error|error" > $O/rehearse_T.txt; tail -6 $O/rehearse_T.txt
-SGP_BENCH_REHEARSAL=1 timeout -k 10 600 python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29514 bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_2rank_rehearsal.json 2> $O/bench_2rank_rehearsal.err; echo "2-rank bench rehearsal rc $?"
+SGP_BENCH_REHEARSAL=1 timeout -k 10 600 python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29514 bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_2rank_rehearsal.json 2> $O/bench_2rank_rehearsal.err; echo "2-rank bench rehearsal rc $?"
 python - <<'PY'
 import json
 try:

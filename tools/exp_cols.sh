@@ -5,7 +5,7 @@ W=$1; shift
 for cols in "$@"; do
   if [ "$cols" = "0" ]; then export SGP_OVERLAP=0; unset SGP_OVERLAP_COLS; else export SGP_OVERLAP=1; export SGP_OVERLAP_COLS=$cols; fi
   [ -z "$cols" ] && { unset SGP_OVERLAP; unset SGP_OVERLAP_COLS; }
-  SGP_BENCH_SKIP_ALONE=1 timeout -k 10 300 python bench.py --no-cpu-baseline --workload $W --steps 300 2>/dev/null | python -c "
+  SGP_BENCH_SKIP_ALONE=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload $W --steps 300 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cols=[$cols]', round(d['value'],1), 'sweep_us', round(d['phases_us']['sweep_device'],1))"
 done

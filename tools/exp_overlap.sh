@@ -5,7 +5,7 @@ for cfg in "$@"; do
   set -- $cfg
   echo "== overlap=$1 g1_after=$2 cols=$3"
   SGP_OVERLAP=$1 SGP_G1_AFTER=$2 SGP_OVERLAP_COLS=$3 timeout -k 10 60 python tools/sweep_trace.py 2>&1 | grep -v amdgpu.ids | tail -52
-  SGP_OVERLAP=$1 SGP_G1_AFTER=$2 SGP_OVERLAP_COLS=$3 timeout -k 10 100 python bench.py --steps 200 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
+  SGP_OVERLAP=$1 SGP_G1_AFTER=$2 SGP_OVERLAP_COLS=$3 timeout -k 10 100 python bench.py --full --steps 200 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 l=sys.stdin.read().strip().splitlines()
 if l:

@@ -31,9 +31,9 @@ g=$(find /tmp/kh -name "*kernel_stats.csv" | head -1); python3 $R/tools/kstats.p
 fi
 if [ "$1" = "rest" ]; then
 cd $R
-timeout -k 10 300 python bench.py > $O/bench_T.json 2> $O/bench_T.err; tail -c 400 $O/bench_T.json; echo
-SGP_OVERLAP=0 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_T_plain_order.json 2> /dev/null
-timeout -k 10 300 python bench.py --workload N1M --no-cpu-baseline > $O/bench_N1M.json 2> $O/bench_N1M.err; tail -c 300 $O/bench_N1M.json; echo
+timeout -k 10 300 python bench.py --full > $O/bench_T.json 2> $O/bench_T.err; tail -c 400 $O/bench_T.json; echo
+SGP_OVERLAP=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_T_plain_order.json 2> /dev/null
+timeout -k 10 300 python bench.py --full --workload N1M --no-cpu-baseline > $O/bench_N1M.json 2> $O/bench_N1M.err; tail -c 300 $O/bench_N1M.json; echo
 SGP_TRACE_WGS=1 timeout -k 10 60 python tools/sweep_trace.py > $O/sweep_timeline_T.txt 2>&1
 timeout -k 10 60 python tools/step_trace.py > $O/step_trace_T.txt 2>&1
 SGP_OVERLAP=0 timeout -k 10 60 python tools/sweep_trace.py > $O/sweep_timeline_T_plain_order.txt 2>&1
@@ -46,7 +46,7 @@ timeout -k 10 200 python tools/soak.py > $O/soak.txt 2>&1; tail -3 $O/soak.txt
 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout -k 10 300 python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 tools/rehearse_two_ranks.py 2>&1 | grep -E "rank [01]\]" > $O/rehearse_two_ranks.txt; tail -3 $O/rehearse_two_ranks.txt
 RH_N=20000 RH_M=512 RH_D=8 RH_JIT=1e-6 RH_GTOL=1e-5 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout -k 10 300 python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 tools/rehearse_two_ranks.py 2>&1 | grep -E "rank [01]\]" > $O/rehearse_two_ranks_overlapped.txt; tail -3 $O/rehearse_two_ranks_overlapped.txt
 timeout -k 10 200 python tools/wstats_time.py 2>&1 | grep -v amdgpu > $O/wstats_time.txt; cat $O/wstats_time.txt
-SGP_SYRK_WIDE=0 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_T_syrk_256_threads.json 2> /dev/null
+SGP_SYRK_WIDE=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_T_syrk_256_threads.json 2> /dev/null
 # same-box A/B of library builds (tools/ab_multi.sh): round 3's (commit 0f7549a), the first half of round 4 (8dfa5c6: LDS-staged 16-wave SYRK,
 # one cut) and this one.  The old libraries are built by hand from `git show <commit>:...`; a library that lacks an
 # export bench.py now calls prints no line.

@@ -12,13 +12,11 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libsgp_hip.so")
-# variant libraries (same ABI, extra compile-time options): "chain" = with the round-2 persistent factorisation launch
-# (csrc/sgp_chain.hip.h; correct, measured slower, kept out of the default library)
-VARIANTS = {"chain": ("libsgp_hip_chain.so", ["-DSGP_WITH_PERSISTENT_CHAIN"]),
-            # diagnostics: in-kernel begin / end stamps of every kernel of a sweep (tools/sweep_trace.py)
-            "trace": ("libsgp_hip_trace.so", ["-DSGP_SWEEP_TRACE", "-DSGP_STEP_TRACE"])}
+# variant libraries (same ABI, extra compile-time options)
+# "trace": diagnostics, in-kernel begin / end stamps of every kernel of a sweep (tools/sweep_trace.py)
+VARIANTS = {"trace": ("libsgp_hip_trace.so", ["-DSGP_SWEEP_TRACE", "-DSGP_STEP_TRACE"])}
 SOURCES = [os.path.join(CSRC, "sgp_api.hip")]
-HEADERS = [os.path.join(CSRC, "sgp_kernels.hip.h"), os.path.join(CSRC, "sgp_chain.hip.h"), os.path.join(os.path.dirname(HERE), "include", "sgp_hip.h")]
+HEADERS = [os.path.join(CSRC, "sgp_kernels.hip.h"), os.path.join(os.path.dirname(HERE), "include", "sgp_hip.h")]
 
 
 def _hipcc() -> str:

@@ -8,9 +8,6 @@
 // Per-sweep scalars travel through a pinned Params block that each sequence's first kernel mirrors on the device.
 #include "../../include/sgp_hip.h"
 #include "sgp_kernels.hip.h"
-#ifdef SGP_WITH_PERSISTENT_CHAIN          // the round-2 experiment (one persistent launch per factorisation): correct, slower,
-#include "sgp_chain.hip.h"                // and therefore only in the variant library (`_build.build(variant="chain")`)
-#endif
 
 #include <algorithm>
 #include <atomic>
@@ -66,12 +63,6 @@ bool unregister_handle(sgp_handle* h) {          // false: not (or no longer) a 
     return true;
 }
 
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-// The persistent factorisation launches need ALL their workgroups resident at once (they wait for each other).  Two handles
-// sweeping at the same time could each hold part of the chip: a handle that starts a sweep while another one's may still
-// be running waits for the device first.
-sgp_handle* g_chain_owner = nullptr;
-#endif
 
 struct Graph {
     hipGraph_t graph = nullptr;
@@ -96,7 +87,7 @@ enum { WORD_JOIN = 0,      // the K_uu chain of the sweep has finished (k_join_s
        WORD_GATE = 2,      // the streaming SYRK's resident round is on the CUs               -> K_uu chain's first kernel
        WORD_GRAD = 3,      // the K_uu half of the theta gradient is complete                -> k_theta_grad_finish
        WORD_ASM0 = 4,      // group 0's assembly of overlapped sweep number (value) has started     -> the masked statistics stream
-       WORD_GROUP0 = 8,    // + g: statistics group g of overlapped sweep number (value) is assembled -> Lambda chain, statM
+       WORD_GROUP0 = 8,    // + g: statistics group g of overlapped sweep number (value) is assembled -> Lambda chain
        WORD_COUNT = 8 + LAM_MAX_GROUPS };
 constexpr int RESERVED_CUS_PER_SE = 2;      // of 8: the masked statistics stream runs on 6 CUs per shader engine (192 of 256)
 
@@ -134,25 +125,7 @@ struct sgp_handle {
     double *dPa = nullptr, *dPb = nullptr, *dKmu = nullptr, *dUvT = nullptr, *dScratch = nullptr, *dOut2 = nullptr, *dUvWork = nullptr;
     double *dGradM = nullptr, *dGradPart = nullptr, *dGrad = nullptr;   // theta-gradient scratch (allocated on first use)
     double* dSaccK = nullptr;      // K_uu chain: Sigma-style accumulator of K_uu^-1 = W_K^T W_K (see sigma_row_tile)
-    bool use_chain = false;        // (always false without SGP_WITH_PERSISTENT_CHAIN)
     long long gate_epoch = 0;      // value the sweep's SYRK stores into the gate word
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    // persistent factorisation launch (sgp_chain.hip.h), one set per chain: [0] K_uu, [1] Lambda
-    long long* dChainFlags[2] = {nullptr, nullptr};
-    long long chain_epoch[2] = {0, 0};
-    bool gate_kuu = false;         // the K_uu chain of the sweep being enqueued waits behind the gate (see k_chain_gate)
-    double* dKuuAlt = nullptr;     // the other parity of dKuu / dLam: the launches alternate (see sgp_chain.hip.h, hand-offs)
-    double* dLamAlt = nullptr;
-    double* dChainFar[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};     // [chain][parity] mailbox matrices
-    double* dChainShip[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    double* dChainRinv[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    long long* dChainTrace[2] = {nullptr, nullptr};   // diagnostics, allocated when SGP_CHAIN_TRACE is set
-    ChainArgs* dChainArgs[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [chain][parity]: the launches' argument structs
-    ChainArgs chain_args_shadow[2][2];                // what the device copies hold (rewritten only when something changes)
-    bool chain_args_valid[2][2] = {{false, false}, {false, false}};
-#endif
-    // environment switches (diagnostics / A-B), read once in sgp_create
-    bool env_no_gate = false, env_join_event = false, env_grad_one_stream = false;
     int spin_limit = JOIN_SPIN_LIMIT;   // polls before a bounded device-word wait gives up (SGP_SPIN_LIMIT: tests shorten it)
     double* dCall = nullptr;       // scratch of the per-call outputs (sgp_predict, sgp_w_stats): grows, never shrinks
     size_t call_capacity = 0;
@@ -199,16 +172,12 @@ struct sgp_handle {
     StatGroup grp[LAM_MAX_GROUPS];
     long long stat_epoch = 0;      // number of the last overlapped sweep: what its groups' words dJoin[WORD_GROUP0 + g] receive
     int env_overlap = -1;          // SGP_OVERLAP: 0 off, 1 on wherever it is possible; default: where the planner's model says it pays
-    int env_g1_mode = 2;           // SGP_G1_AFTER (see enqueue_stats_overlapped)
-    int env_syrk_wt = 0;           // SGP_SYRK_WT (see plan_overlap)
-    bool env_syrk_wide = true;     // SGP_SYRK_WIDE=0: the 256-thread SYRK everywhere (A/B switch)
     bool defer_request = false, kuu_deferred = false;   // the K_uu chain's steps enqueued alternately with the Lambda chain's (sgp_sweep, see enqueue_finish1)
     bool env_interleave = true;     // the K_uu chain's and the Lambda chain's launches enqueued alternately (SGP_INTERLEAVE=0: chain after chain).  A sweep
                                     // that starts on an idle device -- the first of a block, every sweep of a caller that fetches something in between --
                                     // otherwise has its Lambda chain wait for the host to get through the other chain's 14 launches; once the host is a
                                     // sweep ahead the order makes no difference (profiles/r04_ab_log.txt [30], [37], [38])
-    bool env_no_zero_copy = false; // SGP_NO_ZERO_COPY=1: sgp_w_stats copies its results back instead of writing them to pinned memory (A/B switch)
-    int64_t gate_min = 10000;      // points x lower tiles from which the SYRK is taken to fill the chip (SGP_GATE_MIN: A/B switch; see set_point_count)
+    bool env_no_zero_copy = false; // SGP_NO_ZERO_COPY=1: sgp_w_stats copies its results back instead of writing them to pinned memory
     bool syrk_wide = false;        // the resident problem's SYRK launches are k_syrk_direct (set_point_count)
     std::vector<int> env_overlap_cols;   // SGP_OVERLAP_COLS: group boundaries (tile columns of P Lambda P), e.g. "3" or "2,4"
     int nblk = 0, ntiles = 0, num_cus = 256;
@@ -274,16 +243,13 @@ static int call_scratch(sgp_handle* h, size_t count, double** out) {
 // interrupt arrives (the runtime's choice of wait mode): tens of microseconds of wake-up latency behind a 230 us sweep, paid by
 // every "sweep, fetch something, next sweep" iteration of a host-paced caller (measured with tools/wstats_time.py: a sweep +
 // sgp_get_scalars took 300-350 us of wall time for 223 us of device time).  The waits below first POLL hipStreamQuery for up to ~2 ms
-// -- several sweeps' worth -- and only then fall back to the blocking call.  SGP_SPIN_WAIT=0 restores the plain blocking waits.
-static bool g_spin_wait = [] { const char* e = getenv("SGP_SPIN_WAIT"); return !(e && atoi(e) == 0); }();
+// -- several sweeps' worth -- and only then fall back to the blocking call.
 static hipError_t wait_stream(hipStream_t s) {
-    if (g_spin_wait) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int it = 0;; ++it) {
-            const hipError_t e = hipStreamQuery(s);
-            if (e != hipErrorNotReady) return e;
-            if ((it & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-        }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int it = 0;; ++it) {
+        const hipError_t e = hipStreamQuery(s);
+        if (e != hipErrorNotReady) return e;
+        if ((it & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
     }
     return hipStreamSynchronize(s);
 }
@@ -314,12 +280,8 @@ static int quiesce(sgp_handle* h) {
 // CU: SYRK_RESERVED_CUS are left out of the slot count for it unless the chain is gated behind this launch (set_point_count).
 // Measured at T with the round-1 grid (sweeps/s, SYRK us): 40 reserved 3312 / 66.5, 24 the same, 8: 3355 / 62.6, 0: 3202 /
 // 76.7 (a second round).
-#ifndef SYRK_BLOCKS_PER_CU
-#define SYRK_BLOCKS_PER_CU 4
-#endif
-#ifndef SYRK_RESERVED_CUS
-#define SYRK_RESERVED_CUS 8
-#endif
+constexpr int SYRK_BLOCKS_PER_CU = 4;
+constexpr int SYRK_RESERVED_CUS = 8;
 // wide (round 4): the launch is k_syrk_direct -- ONE 512-thread workgroup per CU, whose eight waves take the item's k-steps (4 points)
 // round-robin, each with the whole tile in its accumulators, and add their partial tiles up in LDS: one slab per CU.  Any item count
 // works there (its block map pads to a multiple of 8); a chunk is a multiple of 4 SYRK_WAVES points (whole rounds of k-steps).
@@ -331,7 +293,6 @@ static SyrkGeom syrk_geometry(int row_lo, int nrows, int cus, int64_t n, bool wi
     g.ntiles = (row_lo + nrows) * (row_lo + nrows + 1) / 2 - g.tile0;
     g.chunk = wide ? 4 * SYRK_WAVES : KB;
     g.nchunks = 0;
-    g.write_through = 0;
     g.wide = wide ? 1 : 0;
     if (n <= 0) return g;
     if (wide) {
@@ -439,49 +400,6 @@ static void launch_ata(const double* W, double* C, int ld, int Tn, hipStream_t s
                        Kinv, trace_part, uv ? *uv : UvArgs{}, Sacc);
 }
 
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-// The same factorisation (and ride-along roles) as launch_potrf, with the Cholesky itself as ONE persistent launch
-// (sgp_chain.hip.h).  `which`: 0 = K_uu chain (the matrix is evaluated from the scaled inducing inputs), 1 = Lambda chain
-// (evaluated from the statistics through `form`).  A receives L; Winv / Sacc / tv_* as in launch_potrf.
-static int launch_chain(sgp_handle* h, int which, double* A, double* A_next, int ld, int Tn, int* info, int n_valid, hipStream_t s,
-                         double* Winv, const LamForm* form, double* Sacc, const double* tv_xi, double* tv_t, const double* Xus,
-                         const Params* P, int M, int D) {
-    ChainArgs g;
-    memset(&g, 0, sizeof g);
-    const int par = (int)(++h->chain_epoch[which] & 1);
-    g.A = A; g.A_next = A_next; g.ld = ld; g.Tn = Tn; g.info = info; g.n_valid = n_valid;
-    g.Far = h->dChainFar[which][par]; g.Far_next = h->dChainFar[which][par ^ 1];
-    g.Ship = h->dChainShip[which][par]; g.Ship_next = h->dChainShip[which][par ^ 1];
-    g.rinv_all = h->dChainRinv[which][par]; g.rinv_next = h->dChainRinv[which][par ^ 1];
-    g.Winv = Winv;
-    g.abortw = h->dChainFlags[which] + CH_F_ABORT + par;
-    g.abortw_next = h->dChainFlags[which] + CH_F_ABORT + (par ^ 1);
-    g.trace = h->dChainTrace[which];
-    if (form) g.form = *form;
-    g.Xus = Xus; g.P = P; g.M = M; g.D = D;
-    // the device copy of the arguments changes rarely (statistics buffer rebound, prior form): rewritten only then, after
-    // waiting for whatever may still be reading it
-    if (!h->chain_args_valid[which][par] || memcmp(&g, &h->chain_args_shadow[which][par], sizeof g) != 0) {
-        HIPCHK(h, hipDeviceSynchronize());
-        HIPCHK(h, hipMemcpy(h->dChainArgs[which][par], &g, sizeof g, hipMemcpyHostToDevice));
-        h->chain_args_shadow[which][par] = g;
-        h->chain_args_valid[which][par] = true;
-    }
-    hipLaunchKernelGGL(k_chol_chain, dim3(chain_blocks(Tn, Winv != nullptr)), dim3(CH_THREADS), 0, s,
-                       (const ChainArgs*)h->dChainArgs[which][par]);
-    if (!Winv) return 0;
-    for (int j = 1; j <= Tn; ++j) {
-        int e = 0;
-        if (j >= 2) {
-            e += 2 * (j - 1) * (j < Tn ? 2 : 1);
-            if (Sacc && j < Tn) e += (j - 1) * j / 2;
-        }
-        if (tv_t) e += 1;
-        if (e > 0) hipLaunchKernelGGL(k_chain_extras, dim3(e), dim3(256), 0, s, A, ld, j, Tn, Winv, Sacc, tv_xi, tv_t);
-    }
-    return 0;
-}
-#endif
 
 // ------------------------------------------------------------------------------------------------
 extern "C" int sgp_abi_version(void) { return SGP_ABI_VERSION; }
@@ -511,6 +429,8 @@ extern "C" int sgp_create(const sgp_config* cfg, sgp_handle** out) {
     HIPCHK((sgp_handle*)nullptr, hipGetDeviceProperties(&prop, cfg->device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(nullptr, SGP_ERR_NODEVICE, "sgp_create: device is not gfx950 (MI355X); this library is built for gfx950 only");
+    if (cfg->flags & SGP_FLAG_PERSISTENT_CHAIN)
+        return fail(nullptr, SGP_ERR_ARG, "sgp_create: the persistent factorisation launch is not part of this library (reserved flag)");
 
     sgp_handle* h = new sgp_handle();
     register_handle(h);
@@ -587,16 +507,11 @@ extern "C" int sgp_create(const sgp_config* cfg, sgp_handle** out) {
     ALLOC(h->dParamsK, 1);
     ALLOC(h->dXusK, Mp * h->D);
     {
-        // diagnostic switches of the environment, read once (not per sweep)
-        h->env_no_gate = getenv("SGP_NO_GATE") != nullptr;
-        h->env_join_event = getenv("SGP_JOIN_EVENT") != nullptr;
-        h->env_grad_one_stream = getenv("SGP_GRAD_ONE_STREAM") != nullptr;
+        // Test hooks, read once (not per sweep).  Each forces a path the product already takes in some configuration, so that the
+        // tests can compare it with the others: SGP_OVERLAP / SGP_OVERLAP_COLS (the overlapped sweep and its groups), SGP_SPIN_LIMIT
+        // (a short bounded wait), SGP_INTERLEAVE (the chain-after-chain host order), SGP_NO_ZERO_COPY (results copied back).
         if (const char* lim = getenv("SGP_SPIN_LIMIT")) h->spin_limit = std::max(1, atoi(lim));
         if (const char* ov = getenv("SGP_OVERLAP")) h->env_overlap = atoi(ov);
-        if (const char* g1 = getenv("SGP_G1_AFTER")) h->env_g1_mode = atoi(g1);
-        if (const char* wt = getenv("SGP_SYRK_WT")) h->env_syrk_wt = atoi(wt);
-        if (const char* sw = getenv("SGP_SYRK_WIDE")) h->env_syrk_wide = atoi(sw) != 0;
-        if (const char* gm = getenv("SGP_GATE_MIN")) h->gate_min = atoll(gm);
         if (const char* zc = getenv("SGP_NO_ZERO_COPY")) h->env_no_zero_copy = atoi(zc) != 0;
         if (const char* ni = getenv("SGP_INTERLEAVE")) h->env_interleave = atoi(ni) != 0;
         if (const char* oc = getenv("SGP_OVERLAP_COLS"))
@@ -606,56 +521,6 @@ extern "C" int sgp_create(const sgp_config* cfg, sgp_handle** out) {
                 if (*q == ',') ++q;
             }
     }
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    {
-        // opt-in: one persistent launch per factorisation (sgp_chain.hip.h) instead of one launch per 64-column step
-        const char* env = getenv("SGP_CHAIN");
-        const bool persistent = (env && strcmp(env, "persistent") == 0) || (cfg->flags & SGP_FLAG_PERSISTENT_CHAIN);
-        h->use_chain = persistent && !(cfg->flags & SGP_FLAG_GRAPH) && h->TQ <= CH_TMAX && h->T <= CH_TMAX;
-        if (h->use_chain) {
-            ALLOC(h->dChainFlags[0], CH_F_COUNT);
-            ALLOC(h->dChainFlags[1], CH_F_COUNT);
-            ALLOC(h->dKuuAlt, Mp * Mp);
-            ALLOC(h->dLamAlt, Qp * Qp);
-            for (int par = 0; par < 2; ++par) {
-                ALLOC(h->dChainFar[0][par], Mp * Mp);
-                ALLOC(h->dChainFar[1][par], Qp * Qp);
-                ALLOC(h->dChainShip[0][par], Mp * Mp);
-                ALLOC(h->dChainShip[1][par], Qp * Qp);
-                ALLOC(h->dChainRinv[0][par], Mp);
-                ALLOC(h->dChainRinv[1][par], Qp);
-                ALLOC(h->dChainArgs[0][par], 1);
-                ALLOC(h->dChainArgs[1][par], 1);
-            }
-            if (getenv("SGP_CHAIN_TRACE")) {
-                ALLOC(h->dChainTrace[0], CH_TMAX * 32);
-                ALLOC(h->dChainTrace[1], CH_TMAX * 32);
-                hipMemset(h->dChainTrace[0], 0, sizeof(long long) * CH_TMAX * 32);
-                hipMemset(h->dChainTrace[1], 0, sizeof(long long) * CH_TMAX * 32);
-            }
-            hipMemset(h->dChainFlags[0], 0, sizeof(long long) * CH_F_COUNT);
-            hipMemset(h->dChainFlags[1], 0, sizeof(long long) * CH_F_COUNT);
-            // every mailbox starts out full of sentinels; from then on each launch refills the other parity's
-            auto fill = [&](double* p, size_t n) {
-                hipLaunchKernelGGL(k_chain_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, p, n);
-            };
-            fill(h->dKuu, Mp * Mp); fill(h->dKuuAlt, Mp * Mp); fill(h->dLam, Qp * Qp); fill(h->dLamAlt, Qp * Qp);
-            for (int par = 0; par < 2; ++par) {
-                fill(h->dChainFar[0][par], Mp * Mp); fill(h->dChainFar[1][par], Qp * Qp);
-                fill(h->dChainShip[0][par], Mp * Mp); fill(h->dChainShip[1][par], Qp * Qp);
-                fill(h->dChainRinv[0][par], Mp); fill(h->dChainRinv[1][par], Qp);
-            }
-            hipDeviceSynchronize();
-        }
-    }
-#else
-    if ((cfg->flags & SGP_FLAG_PERSISTENT_CHAIN) || (getenv("SGP_CHAIN") && strcmp(getenv("SGP_CHAIN"), "persistent") == 0)) {
-        g_create_error = "sgp_create: this build does not contain the persistent factorisation launch (build the variant library "
-                         "with -DSGP_WITH_PERSISTENT_CHAIN: gaussianprocessnode_amd._build.build(variant=\"chain\"))";
-        sgp_destroy(h);
-        return SGP_ERR_ARG;
-    }
-#endif
     if (cfg->flags & SGP_FLAG_KEEP_KUF) {
         // per-point partials of k_quadform_fused: [2 T] rows of each quadratic form, then [4] rows of k_n . mu (one allocation)
         ALLOC(h->dPa, (4 * (size_t)h->T + 4) * nmax);
@@ -708,10 +573,8 @@ extern "C" int sgp_create(const sgp_config* cfg, sgp_handle** out) {
     // is CU (i / 8 / 4) of shader engine (i / 8) % 4 of XCD i % 8 (measured with tools/cu_mask_probe.hip), so the first
     // 32 k bits are k CUs on every shader engine of every XCD -- a symmetric mask: an uneven one (e.g. 216 bits) leaves some
     // engines with fewer CUs than their equal share of the workgroups and costs a second round.
-    int reserved_per_se = RESERVED_CUS_PER_SE;
-    if (const char* r = getenv("SGP_RESERVED_PER_SE")) reserved_per_se = std::max(1, atoi(r));     // (A/B switch)
-    if (h->env_overlap != 0 && !(cfg->flags & SGP_FLAG_GRAPH) && h->dout == 1 && h->num_cus % 32 == 0 && h->num_cus / 32 > reserved_per_se) {
-        const int keep = h->num_cus - 32 * reserved_per_se;
+    if (h->env_overlap != 0 && !(cfg->flags & SGP_FLAG_GRAPH) && h->dout == 1 && h->num_cus % 32 == 0 && h->num_cus / 32 > RESERVED_CUS_PER_SE) {
+        const int keep = h->num_cus - 32 * RESERVED_CUS_PER_SE;
         uint32_t mask[16] = {0};
         for (int i = 0; i < keep && i < 512; ++i) mask[i / 32] |= 1u << (i % 32);
         // (Confining the K_uu chain's stream to the complement, the reserved CUs, was measured and dropped: an unmasked launch
@@ -749,9 +612,6 @@ extern "C" int sgp_destroy(sgp_handle* h) {
         delete h;
         return 0;
     }
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    if (g_chain_owner == h) g_chain_owner = nullptr;
-#endif
     h->gLocal.reset();
     h->gFinish.reset();
     h->gFinish2.reset();
@@ -763,15 +623,6 @@ extern "C" int sgp_destroy(sgp_handle* h) {
                     h->dGradM, h->dGradPart, h->dGrad, h->dCall, h->dSaccK,
                     h->dTrainX, h->dTrainY, h->dTrain, h->dTrainParams, h->dJoin, h->dPack, h->dBred};
     for (void* b : bufs) if (b) hipFree(b);
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    void* cbufs[] = {h->dChainFlags[0], h->dChainFlags[1],
-                     h->dChainFar[0][0], h->dChainFar[0][1], h->dChainFar[1][0], h->dChainFar[1][1],
-                     h->dChainShip[0][0], h->dChainShip[0][1], h->dChainShip[1][0], h->dChainShip[1][1],
-                     h->dChainRinv[0][0], h->dChainRinv[0][1], h->dChainRinv[1][0], h->dChainRinv[1][1],
-                     h->dChainTrace[0], h->dChainTrace[1], h->dKuuAlt, h->dLamAlt,
-                     h->dChainArgs[0][0], h->dChainArgs[0][1], h->dChainArgs[1][0], h->dChainArgs[1][1]};
-    for (void* b : cbufs) if (b) hipFree(b);
-#endif
     if (h->hParams) hipHostFree(h->hParams);
     if (h->hStage) hipHostFree(h->hStage);
     if (h->hMirror) hipHostFree(h->hMirror);
@@ -854,7 +705,7 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
     h->overlap = false;
     h->ngroups = 0;
     const int T = h->T;
-    if (!h->statM || h->env_overlap == 0 || h->dout != 1 || T < 3 || T > LAM_MAX_COLS || h->use_chain || h->training ||
+    if (!h->statM || h->env_overlap == 0 || h->dout != 1 || T < 3 || T > LAM_MAX_COLS || h->training ||
         (h->cfg.flags & SGP_FLAG_GRAPH) || n < 1 || (!h->gate_side && h->env_overlap != 1))
         return;
     std::vector<int> cuts;                                   // group boundaries, ascending, in (0, T)
@@ -904,8 +755,6 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
         G.form_step = G.c0;
         // (the 16-wave kernel for the masked groups as well: with the 256-thread kernel there the sweep was 1 % slower, profiles/r04_ab_log.txt [9])
         G.geom = syrk_geometry(G.row_lo, G.nrows, G.masked ? h->stat_cus_masked : h->num_cus, n, h->syrk_wide);
-        // SGP_SYRK_WT (A/B, see k_syrk_stream): 0 plain slab stores (default), 1 write-through in the masked groups, 2 in all
-        G.geom.write_through = (h->env_syrk_wt == 2 || (h->env_syrk_wt == 1 && G.masked)) ? 1 : 0;
         G.ntiles = G.geom.ntiles;
         G.slab_off = off;
         off += syrk_items(G.geom) * TB * TB;
@@ -923,6 +772,8 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
     h->overlap = true;
 }
 
+constexpr int64_t GATE_MIN = 10000;         // points x lower tiles from which the SYRK is taken to fill the chip (set_point_count)
+
 // the launch geometry of the data-sized kernels for n points
 static int set_point_count(sgp_handle* h, int64_t n) {
     h->n = n;
@@ -935,13 +786,12 @@ static int set_point_count(sgp_handle* h, int64_t n) {
     // The threshold (points x lower tiles) was 200 000 through the first half of round 4 -- what the LDS-staged SYRK needed to fill
     // the chip; k_syrk_direct has one workgroup per CU and splits the point axis down to 32 points, so far smaller problems gain
     // from it, from the gate and, from ~50 000 on, from the overlapped order (sweeps/s at the old / new threshold, one box,
-    // tools/gate_sweep.py, profiles/r04_ab_log.txt [22]): N = 5 000, M = 512: 4 534 -> 4 970; C2 (N = 10 000, M = 256): 7 333 -> 7 640;
+    // profiles/r04_ab_log.txt [22]): N = 5 000, M = 512: 4 534 -> 4 970; C2 (N = 10 000, M = 256): 7 333 -> 7 640;
     // 3 000 x 512: 4 819 -> 5 057; 10 000 x 128: 10 523 -> 11 836; C4 (4 000 x 128): 11 205 -> 13 032; C5 (1 500 x 48, one tile:
     // 1 500) loses 2 % if gated and C1 15 %: the threshold is 10 000.
-    h->gate_side = n * (int64_t)h->ntiles >= h->gate_min && h->dJoin && !(h->cfg.flags & SGP_FLAG_GRAPH) && !h->use_chain &&
-                   !h->env_no_gate;
+    h->gate_side = n * (int64_t)h->ntiles >= GATE_MIN && h->dJoin && !(h->cfg.flags & SGP_FLAG_GRAPH);
     // (the in-CU split needs the whole LDS of a CU: only where the K_uu chain is gated behind this launch, i.e. the SYRK fills the chip)
-    h->syrk_wide = h->gate_side && h->env_syrk_wide;
+    h->syrk_wide = h->gate_side;
     h->geom = syrk_geometry(0, h->T, h->num_cus - (h->gate_side ? 0 : SYRK_RESERVED_CUS), n, h->syrk_wide);
     if (syrk_items(h->geom) * TB * TB > h->slab_capacity)
         return fail(h, SGP_ERR_ARG, "sgp_set_data: internal slab capacity exceeded");
@@ -1192,17 +1042,6 @@ static void enqueue_kuu_head(sgp_handle* h, hipStream_t s, bool steps_too) {
                        words ? (const long long*)(h->dJoin + WORD_DONE) : (const long long*)nullptr, h->done_epoch,
                        gate ? (const long long*)(h->dJoin + WORD_GATE) : (const long long*)nullptr,
                        h->gate_epoch, h->spin_limit, h->dInfo + 3);
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    if (h->use_chain) {
-        if (h->gate_kuu)
-            hipLaunchKernelGGL(k_chain_gate, dim3(1), dim3(64), 0, s, (const long long*)(h->dChainFlags[0] + CH_F_GATE), h->gate_epoch);
-        std::swap(h->dKuu, h->dKuuAlt);         // this launch's factor goes to the buffer the last one refilled with sentinels
-        launch_chain(h, 0, h->dKuu, h->dKuuAlt, Mp, T, h->dInfo + 0, M, s, h->dWk, nullptr, h->dSaccK, nullptr, nullptr, h->dXusK,
-                     h->dParamsK, M, D);
-        kuu_tail(h, s);
-        return;
-    }
-#endif
     kuu_gram(h, s, gate);
     if (steps_too) {
         launch_potrf(h->dKuu, Mp, T, h->dInfo + 0, M, h->dScratch, s, h->dWk, nullptr, h->dSaccK);
@@ -1236,9 +1075,6 @@ static void enqueue_local(sgp_handle* h, hipStream_t s) {
     if (h->n > 0) {
         launch_gram(h, s, true);
         long long* gate = h->gate_side ? h->dJoin + WORD_GATE : nullptr;
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-        if (h->use_chain) gate = h->dChainFlags[0] + CH_F_GATE;
-#endif
         launch_syrk(h->geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs, Mp, h->n, h->dStamps + STAMP_STRIDE * SGP_T_SYRK,
                     gate, h->gate_epoch);
     }
@@ -1279,14 +1115,12 @@ static int enqueue_stats_overlapped(sgp_handle* h, hipStream_t own) {
         h->main_prep_gen = h->params_gen;
     }
     launch_gram(h, own, true);
-    // When the masked groups may start (A/B switch SGP_G1_AFTER, read in sgp_create): 2 (default) = when group 0's assembly
-    // starts, i.e. its SYRK has drained; 0 = as soon as group 0's SYRK has its round on the CUs (the masked SYRK then fills the
-    // CUs as they drain, but group 0's assembly shares them with it: 12.7 instead of 8.7 us on the critical path);
-    // 1 = when group 0 is assembled (the chains' whole-CU workgroups settle on the idle masked CUs meanwhile and the masked
-    // SYRK no longer fits its single round).  Sweeps/s at T on one box: 3978 / 3975 / 3865.
-    const int g1_mode = sharded ? 2 : h->env_g1_mode;
-    const long long* g1_word = h->dJoin + (g1_mode == 0 ? WORD_GATE : (g1_mode == 1 ? WORD_GROUP0 : WORD_ASM0));
-    hipLaunchKernelGGL(k_join_wait, dim3(1), dim3(64), 0, h->statM, g1_word, g1_mode == 0 ? h->gate_epoch : h->stat_epoch,
+    // The masked groups start when group 0's assembly starts, i.e. its SYRK has drained.  Measured against starting them as soon
+    // as group 0's SYRK has its round on the CUs (the masked SYRK then fills the CUs as they drain, but group 0's assembly shares
+    // them with it: 12.7 instead of 8.7 us on the critical path) and once group 0 is assembled (the chains' whole-CU workgroups
+    // settle on the idle masked CUs meanwhile and the masked SYRK no longer fits its single round).  Sweeps/s at T on one box:
+    // 3978 / 3975 / 3865.
+    hipLaunchKernelGGL(k_join_wait, dim3(1), dim3(64), 0, h->statM, (const long long*)(h->dJoin + WORD_ASM0), h->stat_epoch,
                        h->spin_limit, h->dInfo + 3, (int)SYNC_LATE_COLUMN, 8);
     for (int g = 0; g < h->ngroups; ++g) {
         const StatGroup& G = h->grp[g];
@@ -1301,7 +1135,7 @@ static int enqueue_stats_overlapped(sgp_handle* h, hipStream_t own) {
         if (sharded) {
             if (int xrc = exchange_stats(h, s, G.geom.tile0, G.geom.ntiles, g == 0)) return xrc;
             if (G.masked && hipEventRecord(h->evGroup[g], s) != hipSuccess) return fail(h, SGP_ERR_HIP, "hipEventRecord failed (statistics group)");
-        } else if (G.masked || g1_mode == 1)
+        } else if (G.masked)
             hipLaunchKernelGGL(k_join_set, dim3(1), dim3(64), 0, s, h->dJoin + WORD_GROUP0 + g, h->stat_epoch);
     }
     return 0;
@@ -1341,31 +1175,23 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s) {
         }
     }
     double* uvt0 = h->dUvWork + 2 * (size_t)Qp;     // t = W' P xi, advanced block by block during the factorisation
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    if (h->use_chain) {
-        std::swap(h->dLam, h->dLamAlt);
-        launch_chain(h, 1, h->dLam, h->dLamAlt, Qp, TQ, h->dInfo + 1, Qp, s, h->dWl, &form, h->dTmp, h->dXi, uvt0, nullptr, nullptr, 0, 0);
-    } else
-#endif
-    {
-        PotrfSeq lam(h->dLam, Qp, TQ, h->dInfo + 1, Qp, h->dScratch + POTRF_SCRATCH, s, h->dWl, &form, h->dTmp, h->dXi, uvt0,
-                     any_wait ? step_wait : nullptr);
-        if (h->kuu_deferred) {
-            // (SGP_INTERLEAVE=1, off by default.)  The K_uu chain's Cholesky steps were held back (sweep_local_impl): its launches and the
-            // Lambda chain's go out ALTERNATELY, so that on a GPU that is idle when the sweep arrives neither chain waits for the host to
-            // get through the other's ten launches (the Lambda chain's first step arrives ~25 us after the GPU is ready for it).  Same
-            // launches, same order on each stream.  Measured: the first A/B gained 1.3 % on 20-sweep blocks and 5 % on the sweep; w_stats
-            // loop, two repeats on other boxes were neutral to -1 % -- switching streams between launches costs the host ~20 us per
-            // sweep (120 instead of 100 us), which on a busy host is exactly what a short block lacks (profiles/r04_ab_log.txt [30]).
-            PotrfSeq kuu(h->dKuu, h->Mp, h->T, h->dInfo + 0, h->M, h->dScratch, h->side, h->dWk, nullptr, h->dSaccK);
-            while (!lam.done() || !kuu.done()) {
-                if (!lam.done()) lam.next();
-                if (!kuu.done()) kuu.next();
-            }
-            kuu_tail(h, h->side);
-        } else {
-            while (!lam.done()) lam.next();
+    PotrfSeq lam(h->dLam, Qp, TQ, h->dInfo + 1, Qp, h->dScratch + POTRF_SCRATCH, s, h->dWl, &form, h->dTmp, h->dXi, uvt0,
+                 any_wait ? step_wait : nullptr);
+    if (h->kuu_deferred) {
+        // (The default; SGP_INTERLEAVE=0 turns it off.)  The K_uu chain's Cholesky steps were held back (sweep_local_impl): its launches and the
+        // Lambda chain's go out ALTERNATELY, so that on a GPU that is idle when the sweep arrives neither chain waits for the host to
+        // get through the other's ten launches (the Lambda chain's first step arrives ~25 us after the GPU is ready for it).  Same
+        // launches, same order on each stream.  Measured: the first A/B gained 1.3 % on 20-sweep blocks and 5 % on the sweep; w_stats
+        // loop, two repeats on other boxes were neutral to -1 % -- switching streams between launches costs the host ~20 us per
+        // sweep (120 instead of 100 us), which on a busy host is exactly what a short block lacks (profiles/r04_ab_log.txt [30]).
+        PotrfSeq kuu(h->dKuu, h->Mp, h->T, h->dInfo + 0, h->M, h->dScratch, h->side, h->dWk, nullptr, h->dSaccK);
+        while (!lam.done() || !kuu.done()) {
+            if (!lam.done()) lam.next();
+            if (!kuu.done()) kuu.next();
         }
+        kuu_tail(h, h->side);
+    } else {
+        while (!lam.done()) lam.next();
     }
     // mu = Sigma xi = P W'^T W' P xi as two triangular mat-vecs; their intermediate t IS p = V^-T mu up to the reversal,
     // so the closed-form Uv needs no further solve and nothing here waits for Sigma itself
@@ -1418,8 +1244,7 @@ static void enqueue_finish2(sgp_handle* h, hipStream_t s) {
                        h->dLam, h->dInfo, h->dParams, h->dOut, h->dWishart, M, Mp, h->dout, Q, Qp, Qp - Q,
                        h->dStamps + STAMP_STRIDE * SGP_T_FINISH2, h->dStamps, h->dStampTotals,
                        (h->cfg.flags & SGP_FLAG_GRAPH) ? (long long*)nullptr : h->dJoin + WORD_DONE, h->done_epoch,
-                       h->use_chain ? (const double*)nullptr : (const double*)(h->dScratch + POTRF_LOGDET), h->T,
-                       h->use_chain ? (const double*)nullptr : (const double*)(h->dScratch + POTRF_SCRATCH + POTRF_LOGDET), TQ,
+                       (const double*)(h->dScratch + POTRF_LOGDET), h->T, (const double*)(h->dScratch + POTRF_SCRATCH + POTRF_LOGDET), TQ,
                        mirror_for(h));
 }
 
@@ -1485,12 +1310,6 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped) {
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    if (h->use_chain) {
-        if (g_chain_owner && g_chain_owner != h) HIPCHK(h, hipDeviceSynchronize());
-        g_chain_owner = h;
-    }
-#endif
     if (h->sync_reported) {
         // (the getter that reported the word had drained the device: nothing is in flight)
         HIPCHK(h, hipMemset(h->dInfo + 3, 0, sizeof(int)));
@@ -1519,15 +1338,11 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped) {
     // second handle's sweep may hold CUs too --, and not inside captured graphs.
     {
         const int grid = h->TQ * (h->TQ + 1) / 2 * 4 + h->TQ * h->TQ;
-        h->join_by_flag = h->dJoin && h->dout == 1 && !h->use_events && grid <= h->num_cus - 40 && !h->env_join_event &&
-                          g_live_handles.load() <= 1;
+        h->join_by_flag = h->dJoin && h->dout == 1 && !h->use_events && grid <= h->num_cus - 40 && g_live_handles.load() <= 1;
         ++h->join_epoch;
     }
     ++h->gate_epoch;
     if (overlapped) ++h->stat_epoch;                            // (what the words of this sweep's statistics groups receive)
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    h->gate_kuu = h->use_chain && h->n > 0;                    // (a SYRK launch follows on the main stream and opens the gate)
-#endif
     // Host order of the enqueues.  The K_uu chain is 14 launches (~50 us of host time).  Where it is gated behind the SYRK anyway
     // (gate_side) the data-sized kernels go out FIRST: a sweep that starts on an idle GPU -- the drop-in's pattern: sweep, fetch
     // something, next sweep -- otherwise has its Gram kernel wait ~50 us for the host to get through launches the GPU cannot run
@@ -1546,16 +1361,13 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped) {
         if (int src = enqueue_stats()) return src;
     // (one-shot sgp_sweep on the library's streams: only the K_uu chain's first two kernels go out here, its steps are enqueued
     // alternately with the Lambda chain's by sgp_sweep_finish -- see enqueue_finish1)
-    h->kuu_deferred = h->defer_request && stats_first && !h->use_events && !h->use_chain && s == h->own;
+    h->kuu_deferred = h->defer_request && stats_first && !h->use_events && s == h->own;
     if (h->kuu_deferred) {
         enqueue_kuu_head(h, h->side, false);
         HIPCHK(h, hipGetLastError());
         rc = 0;
     } else
         rc = run_sequence(h, h->gKuu, enqueue_kuu, h->side);
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    h->gate_kuu = false;
-#endif
     if (rc) return rc;
     if (!h->kuu_deferred) HIPCHK(h, hipEventRecord(h->evSide, h->side));
     if (!stats_first)
@@ -1910,15 +1722,7 @@ extern "C" int sgp_get_timestamps(sgp_handle* h, int64_t* out) {
 
 extern "C" int sgp_get_chain_trace(sgp_handle* h, int32_t which, int64_t* out) {
     if (!h || !out || which < 0 || which > 1) return SGP_ERR_ARG;
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    if (!h->dChainTrace[which]) return fail(h, SGP_ERR_ARG, "sgp_get_chain_trace: create the handle with SGP_CHAIN_TRACE set in the environment");
-    int rc = sync_all(h);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpy(out, h->dChainTrace[which], sizeof(long long) * CH_TMAX * 32, hipMemcpyDeviceToHost));
-    return 0;
-#else
-    return fail(h, SGP_ERR_ARG, "sgp_get_chain_trace: this build does not contain the persistent factorisation launch");
-#endif
+    return fail(h, SGP_ERR_ARG, "sgp_get_chain_trace: the persistent factorisation launch is not part of this library");
 }
 
 extern "C" int sgp_get_step_trace(int64_t* out) {
@@ -2154,7 +1958,7 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
     // derivatives) and the K_uu half (H = K_uu^-1 Psi2 K_uu^-1 against dK_uu).  On the library's own streams they run side
     // by side -- the K_uu half on the side stream, which idles between two sweeps -- and meet in the finishing kernel through
     // a device word (an event would cost the main stream ~6 us, see sgp_sweep_finish).
-    const bool split = s == h->own && h->dJoin && !(h->cfg.flags & SGP_FLAG_GRAPH) && !h->env_grad_one_stream;
+    const bool split = s == h->own && h->dJoin && !(h->cfg.flags & SGP_FLAG_GRAPH);
     h->mirror_epoch = -1;                      // (the gradient's hand-offs report into the same status word)
     hipStream_t su = split ? h->side : s;
     if (split)
@@ -2497,7 +2301,7 @@ static int dense_common(int32_t device, const double* A, int32_t n, double* out,
         else tmp[(size_t)j * np + j] = 1.0;
     }
     const size_t mat = sizeof(double) * np * np;
-    DevBuf bA, bInfo, bScr, bW, bC, bL, bFar, bShip, bRinv, bFlags, bArgs;
+    DevBuf bA, bInfo, bScr, bW, bC;
     HIPCHK(h, bA.alloc(mat));
     HIPCHK(h, bInfo.alloc(sizeof(int)));
     HIPCHK(h, hipMemset(bInfo.p, 0, sizeof(int)));
@@ -2506,48 +2310,10 @@ static int dense_common(int32_t device, const double* A, int32_t n, double* out,
         HIPCHK(h, bW.alloc(mat));
         HIPCHK(h, bC.alloc(mat));
     }
-    const double* factor = bA.as<double>();
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    const char* env = getenv("SGP_CHAIN");
-    const bool chain = env && strcmp(env, "persistent") == 0 && Tn <= CH_TMAX;
-    if (chain) {
-        // one persistent launch (sgp_chain.hip.h); the factor goes to a buffer of its own (see ChainArgs::Ain)
-        if (g_chain_owner) HIPCHK(h, hipDeviceSynchronize());
-        HIPCHK(h, bL.alloc(mat));
-        HIPCHK(h, bFar.alloc(mat));
-        HIPCHK(h, bShip.alloc(mat));
-        HIPCHK(h, bRinv.alloc(sizeof(double) * np));
-        HIPCHK(h, bFlags.alloc(sizeof(long long) * CH_F_COUNT));
-        HIPCHK(h, hipMemset(bFlags.p, 0, sizeof(long long) * CH_F_COUNT));
-        const unsigned nb = (unsigned)(((size_t)np * np + 255) / 256);
-        hipLaunchKernelGGL(k_chain_fill, dim3(nb), dim3(256), 0, 0, bL.as<double>(), (size_t)np * np);
-        hipLaunchKernelGGL(k_chain_fill, dim3(nb), dim3(256), 0, 0, bFar.as<double>(), (size_t)np * np);
-        hipLaunchKernelGGL(k_chain_fill, dim3(nb), dim3(256), 0, 0, bShip.as<double>(), (size_t)np * np);
-        hipLaunchKernelGGL(k_chain_fill, dim3((np + 255) / 256), dim3(256), 0, 0, bRinv.as<double>(), (size_t)np);
-        ChainArgs g;
-        memset(&g, 0, sizeof g);
-        g.A = bL.as<double>(); g.Ain = bA.as<double>(); g.ld = np; g.Tn = Tn; g.info = bInfo.as<int>(); g.n_valid = n;
-        g.Winv = inverse ? bW.as<double>() : nullptr; g.Far = bFar.as<double>(); g.Ship = bShip.as<double>();
-        g.rinv_all = bRinv.as<double>();
-        g.abortw = bFlags.as<long long>() + CH_F_ABORT;
-        HIPCHK(h, bArgs.alloc(sizeof(ChainArgs)));
-        HIPCHK(h, hipMemcpy(bArgs.p, &g, sizeof g, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_chol_chain, dim3(chain_blocks(Tn, inverse)), dim3(CH_THREADS), 0, 0, (const ChainArgs*)bArgs.as<ChainArgs>());
-        if (inverse)
-            for (int j = 2; j <= Tn; ++j)
-                hipLaunchKernelGGL(k_chain_extras, dim3(2 * (j - 1) * (j < Tn ? 2 : 1)), dim3(256), 0, 0, bL.as<double>(), np, j, Tn,
-                                   bW.as<double>(), (double*)nullptr, (const double*)nullptr, (double*)nullptr);
-        factor = bL.as<double>();
-    } else
-#else
-    const bool chain = false;
-#endif
-    {
-        HIPCHK(h, bScr.alloc(sizeof(double) * POTRF_SCRATCH));
-        HIPCHK(h, hipMemset(bScr.p, 0, sizeof(double) * POTRF_SCRATCH));
-        launch_potrf(bA.as<double>(), np, Tn, bInfo.as<int>(), n, bScr.as<double>(), 0, bW.as<double>());
-    }
-    const double* result = factor;
+    HIPCHK(h, bScr.alloc(sizeof(double) * POTRF_SCRATCH));
+    HIPCHK(h, hipMemset(bScr.p, 0, sizeof(double) * POTRF_SCRATCH));
+    launch_potrf(bA.as<double>(), np, Tn, bInfo.as<int>(), n, bScr.as<double>(), 0, bW.as<double>());
+    const double* result = bA.as<double>();
     if (inverse) {
         launch_ata(bW.as<double>(), bC.as<double>(), np, Tn, 0);
         result = bC.as<double>();
@@ -2556,23 +2322,7 @@ static int dense_common(int32_t device, const double* A, int32_t n, double* out,
     HIPCHK(h, hipGetLastError());
     int info = 0;
     HIPCHK(h, hipMemcpy(&info, bInfo.p, sizeof(int), hipMemcpyDeviceToHost));
-#ifdef SGP_WITH_PERSISTENT_CHAIN
-    if (chain && getenv("SGP_CHAIN_DUMP")) {              // debugging aid: the mailbox matrices of this call, raw
-        std::vector<double> hb((size_t)np * np);
-        FILE* f = fopen(getenv("SGP_CHAIN_DUMP"), "wb");
-        if (f) {
-            int hdr[2] = {np, Tn};
-            fwrite(hdr, sizeof(int), 2, f);
-            for (void* src : {bL.p, bShip.p, bFar.p}) {
-                hipMemcpy(hb.data(), src, mat, hipMemcpyDeviceToHost);
-                fwrite(hb.data(), sizeof(double), hb.size(), f);
-            }
-            fclose(f);
-        }
-    }
-#endif
-    (void)chain;
-    if (info < 0) return fail(nullptr, SGP_ERR_HIP, "the persistent factorisation launch gave up waiting (deadlock guard)");
+    if (info < 0) return fail(nullptr, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
     HIPCHK(h, hipMemcpy2D(out, sizeof(double) * n, result, sizeof(double) * np, sizeof(double) * n, n, hipMemcpyDeviceToHost));
     if (!inverse)
         for (int j = 0; j < n; ++j)

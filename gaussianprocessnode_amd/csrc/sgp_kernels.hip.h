@@ -442,40 +442,6 @@ __device__ __forceinline__ void tile_mma_bk(Acc4& acc, const double* As, const d
     }
 }
 
-// The same for a DIAGONAL tile of a symmetric product (As and Bs hold the same rows, Bs weighted): only the 10 sub-tiles (R, C),
-// R >= C, of the 4 x 4 grid of 16 x 16 blocks are formed, dealt 3 : 2 : 2 : 3 over the waves --
-//   wave 0: (0,0) (1,0) (1,1)   wave 1: (2,0) (2,1)   wave 2: (3,0) (3,1)   wave 3: (2,2) (3,2) (3,3)
-// (accumulators t[0][0], t[1][0], t[1][1] for waves 0 / 3, t[0][0], t[0][1] for waves 1 / 2): 3 instead of 4 MFMAs per wave and
-// k-step, and no flop on the upper halves, which the algorithm does not contain.
-__device__ __forceinline__ void tile_mma_diag(Acc4& acc, const double* As, const double* Bs, int kcount, int lane, int wave) {
-    const int li = lane & 15, lk = lane >> 4;
-    if (wave == 0 || wave == 3) {
-        const int base = (wave == 3) ? 32 : 0;
-        const double* ap = As + lk * PS + base + li;
-        const double* bp = Bs + lk * PS + base + li;
-#pragma unroll 4
-        for (int k = 0; k < kcount; k += 4) {
-            const double a0 = ap[0], a1 = ap[16], b0 = bp[0], b1 = bp[16];
-            acc.t[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc.t[0][0], 0, 0, 0);
-            acc.t[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc.t[1][0], 0, 0, 0);
-            acc.t[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc.t[1][1], 0, 0, 0);
-            ap += 4 * PS;
-            bp += 4 * PS;
-        }
-    } else {
-        const double* ap = As + lk * PS + 16 * (wave + 1) + li;
-        const double* bp = Bs + lk * PS + li;
-#pragma unroll 4
-        for (int k = 0; k < kcount; k += 4) {
-            const double a0 = ap[0], b0 = bp[0], b1 = bp[16];
-            acc.t[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc.t[0][0], 0, 0, 0);
-            acc.t[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc.t[0][1], 0, 0, 0);
-            ap += 4 * PS;
-            bp += 4 * PS;
-        }
-    }
-}
-
 // element (i, j) of the 64 x 64 tile owned by (lane, wave, ti, tj, r)
 __device__ __forceinline__ int acc_row(int lane, int wr, int ti, int r) { return wr * 32 + ti * 16 + (lane >> 4) + 4 * r; }
 __device__ __forceinline__ int acc_col(int lane, int wc, int tj) { return wc * 32 + tj * 16 + (lane & 15); }
@@ -560,9 +526,8 @@ __device__ __forceinline__ void tile_from_index(int t, int& I, int& J) {
 
 // One work item of the streaming SYRK: the 64 x 64 tile (I, J) summed over the points of chunk `chunk_id`, into `out` ([i][j]
 // row-major; a diagonal tile as the full symmetric tile).
-template <bool DIAG>
 __device__ __forceinline__ void syrk_item(const double* __restrict__ Kuf, const double* __restrict__ omega, double* __restrict__ out,
-                                          double* lds, int Mp, int64_t N, int I, int J, int chunk_id, int chunk, bool write_through) {
+                                          double* lds, int Mp, int64_t N, int I, int J, int chunk_id, int chunk) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
     const int64_t nbeg = (int64_t)chunk_id * chunk;
     int64_t nend = nbeg + chunk;
@@ -577,7 +542,7 @@ __device__ __forceinline__ void syrk_item(const double* __restrict__ Kuf, const 
     // memory latency before its products)
     double2 ra[2], rb[2];
     double rw = 1.0;
-    const bool offdiag = DIAG ? false : (I != J);         // (a diagonal tile reads its rows once)
+    const bool offdiag = I != J;                          // (a diagonal tile reads its rows once)
     auto gload = [&](int s) {
         int64_t n = nbeg + (int64_t)s * KB + p;
         ra[0] = ra[1] = rb[0] = rb[1] = make_double2(0.0, 0.0);
@@ -612,63 +577,29 @@ __device__ __forceinline__ void syrk_item(const double* __restrict__ Kuf, const 
         const int buf = s & 1;
         if (s + 1 < stages) gload(s + 1);
         const double* A = lds + buf * (2 * KB * PS);
-        if constexpr (DIAG) tile_mma_diag(acc, A, A + KB * PS, KB, lane, wave);
-        else tile_mma(acc, A, A + KB * PS, KB, lane, wr, wc);
+        tile_mma(acc, A, A + KB * PS, KB, lane, wr, wc);
         if (s + 1 < stages) lstore(buf ^ 1);
         __syncthreads();
     }
-#ifdef SGP_EXP_QUARTER_SLABS      // timing experiment only (results are wrong): what would a quarter of the slab traffic buy?
-    if (chunk_id & 3) return;
-#endif
-    if constexpr (!DIAG) {
 #pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
+    for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    // write_through (A/B switch SGP_SYRK_WT, default off): agent-scope stores, past this XCD's write-back L2, so
-                    // that the chain steps running beside this launch do not flush its slab lines at their kernel boundaries.
-                    // Measured at T, 4 alternations x 1000 sweeps on one box: 4118-4135 sweeps/s in all three modes -- no effect
-                    // on the overlapped sweep; alone, the single plain-order launch is slower with it (63.6 vs 59.5 us).
-                    double* dst = out + acc_row(lane, wr, ti, r) * TB + acc_col(lane, wc, tj);
-                    if (write_through)
-                        __hip_atomic_store((__attribute__((address_space(1))) double*)dst, acc.t[ti][tj][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else
-                        *dst = acc.t[ti][tj][r];
-                }
-    } else {
-        // the wave's sub-tiles (tile_mma_diag), each also at its mirror position: the slab is the full symmetric tile.
-        // Accumulator slot s of the wave holds sub-tile (R0 + (s > 0), C0 + (s > 1)) for waves 0 / 3, (wave + 1, s) for waves 1 / 2
-        const int row = lane >> 4, col = lane & 15;
-        const bool corner = (wave == 0 || wave == 3);
-        const int b = (wave == 3) ? 2 : 0;
-#pragma unroll
-        for (int slot = 0; slot < 3; ++slot) {
-            if (!corner && slot == 2) break;
-            const d4 v = corner ? (slot == 0 ? acc.t[0][0] : (slot == 1 ? acc.t[1][0] : acc.t[1][1])) : (slot == 0 ? acc.t[0][0] : acc.t[0][1]);
-            const int R = corner ? b + (slot > 0) : wave + 1, C = corner ? b + (slot > 1) : slot;
+        for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                out[(16 * R + row + 4 * r) * TB + 16 * C + col] = v[r];
-                if (R != C) out[(16 * C + col) * TB + 16 * R + row + 4 * r] = v[r];
+                double* dst = out + acc_row(lane, wr, ti, r) * TB + acc_col(lane, wc, tj);
+                *dst = acc.t[ti][tj][r];
             }
-        }
-    }
 }
 
 // One launch covers the lower tiles of the tile rows [row_lo, row_lo + nrows) of Psi2 (a whole matrix: row_lo = 0, nrows = T; the
 // overlapped sweep launches the rows in groups, last rows first, see sgp_api.hip): tiles [tile0, tile0 + ntiles) of the row-major
 // triangle, the point axis split into `nchunks` chunks of `chunk` points.  `slabs` is the launch's own slab area
-// [nchunks][ntiles] of 64 x 64.  Diagonal tiles form 10 of their 16 sub-tiles (tile_mma_diag): no flop on the halves the
-// algorithm does not contain.  (Their workgroups finish a quarter earlier; giving them 4/3 longer chunks to rebalance the round
-// was measured -- 30 x 336 points off the diagonal, 23 x 448 on it -- and lost, 69 vs 61 us: the items of one point range then
-// no longer sit next to each other in the XCD map below, and the diagonal items' K_uf reads miss the L2 their chunk-mates filled.)
+// [nchunks][ntiles] of 64 x 64.
 struct SyrkGeom {
     int row_lo, nrows;              // tile rows
     int tile0, ntiles;              // their lower tiles
     int chunk, nchunks;             // split of the point axis
-    int write_through;              // slabs stored past the L2 (launches that run beside the factorisation chains)
     int wide;                       // 1: launched as k_syrk_direct (one 512-thread workgroup per CU, no LDS staging; `chunk` a multiple of 4 points)
 };
 __global__ void __launch_bounds__(256) k_syrk_stream(const double* __restrict__ Kuf, const double* __restrict__ omega,
@@ -694,14 +625,7 @@ __global__ void __launch_bounds__(256) k_syrk_stream(const double* __restrict__ 
     const int chunk = g.chunk;
     const size_t slab = (size_t)chunk_id * g.ntiles + tile_id;
     double* out = slabs + slab * (TB * TB);
-#ifdef SGP_SYRK_DIAG_SKIP
-    // two specialisations of the whole stage loop: with the choice inside the loop the kernel needed 148 VGPRs (2 waves per
-    // SIMD, i.e. two workgroups per CU and a second round: 95 instead of 58 us)
-    if (I == J) syrk_item<true>(Kuf, omega, out, lds, Mp, N, I, J, chunk_id, chunk, g.write_through != 0);
-    else syrk_item<false>(Kuf, omega, out, lds, Mp, N, I, J, chunk_id, chunk, g.write_through != 0);
-#else
-    syrk_item<false>(Kuf, omega, out, lds, Mp, N, I, J, chunk_id, chunk, g.write_through != 0);
-#endif
+    syrk_item(Kuf, omega, out, lds, Mp, N, I, J, chunk_id, chunk);
     stamp_exit(stamps);
 }
 
@@ -979,13 +903,8 @@ __global__ void __launch_bounds__(256) k_assemble(const double* __restrict__ sla
         const int zr = 4 * z + (tid >> 6), j = tid & 63;
         const int t = I * (I + 1) / 2 + J - g.tile0;
         const double* base = slabs + (size_t)t * (TB * TB) + (size_t)(4 * zr) * TB + j;
-#ifdef SGP_EXP_QUARTER_SLABS
-        const size_t cstride = (size_t)g.ntiles * (TB * TB) * 4;
-        const int nchunks = (g.nchunks + 3) / 4;
-#else
         const size_t cstride = (size_t)g.ntiles * (TB * TB);
         const int nchunks = g.nchunks;
-#endif
         double s[4] = {0.0, 0.0, 0.0, 0.0};
         int c = 0;
         for (; c + 12 <= nchunks; c += 12) {                 // 48 loads in flight; fixed summation order: chunk 0, 1, 2, ...
@@ -1202,11 +1121,6 @@ __device__ __forceinline__ void solve16(double (&x)[4], const double* Dp, const 
 // The four column blocks are a RUNTIME loop (one copy of the 16 unrolled pivots, not four): the step kernel's code was 210 KB
 // with everything unrolled, several times the instruction cache, and the pivot chain -- one instruction every few cycles, no
 // reuse -- then runs at the rate instructions arrive from the L2, which a streaming SYRK on the other CUs keeps busy.
-#ifdef SGP_POTF2_LEFT_LOOKING          // A/B switch: the diagonal blocks updated left-looking, in front of their pivot runs
-constexpr int POTF2_LEFT = 1;
-#else
-constexpr int POTF2_LEFT = 0;
-#endif
 // acc += A[16 x 16 K] B^T for K = 16 chunks: rows of A at ap, of B at bp (both LDS, [row][k], stride LT, already offset by the
 // lane's row and k), operands of all chunks first, four independent accumulators
 template <int CHUNKS>
@@ -1234,7 +1148,7 @@ __device__ __forceinline__ void potf2_tile(double* S, double* Dp, double* rinv, 
     const int rr = lane >> 2, q = lane & 3;
 #pragma unroll 1
     for (int cb = 0; cb < 4; ++cb) {
-        if (cb > 0 && wave > cb - POTF2_LEFT) {                          // (the pivot wave's own block is already up to date, see (3))
+        if (cb > 0 && wave > cb) {                          // (the pivot wave's own block is already up to date, see (3))
             d4 acc[4];
             mma_left_n(acc, S + (r0 + li) * LT + lk /* A[i][k] = L[r0 + i][k] */, S + (16 * cb + li) * LT + lk /* B[k][j] = L[16 cb + j][k] */, cb);
 #pragma unroll
@@ -1321,19 +1235,17 @@ __device__ __forceinline__ void potf2_tile(double* S, double* Dp, double* rinv, 
             // so that a wave that becomes the pivot wave starts its 16 pivots with nothing left to subtract: the
             // left-looking form put 4 cb dependent MFMAs (~200 cycles each) in front of every pivot run.
             __builtin_amdgcn_wave_barrier();
-            if constexpr (!POTF2_LEFT) {
-                const double* dp = S + (r0 + li) * LT + 16 * cb + lk;    // A[i][k] = L[r0 + i][16 cb + k] = B[k][i]
-                double dv[4];
+            const double* dp = S + (r0 + li) * LT + 16 * cb + lk;    // A[i][k] = L[r0 + i][16 cb + k] = B[k][i]
+            double dv[4];
 #pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) dv[s4] = dp[4 * s4];
-                d4 g[4];
+            for (int s4 = 0; s4 < 4; ++s4) dv[s4] = dp[4 * s4];
+            d4 g[4];
 #pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4)
-                    g[s4] = __builtin_amdgcn_mfma_f64_16x16x4f64(dv[s4], dv[s4], (d4){0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
+            for (int s4 = 0; s4 < 4; ++s4)
+                g[s4] = __builtin_amdgcn_mfma_f64_16x16x4f64(dv[s4], dv[s4], (d4){0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    S[(r0 + lk + 4 * r) * LT + r0 + li] -= (g[0][r] + g[1][r]) + (g[2][r] + g[3][r]);
-            }
+            for (int r = 0; r < 4; ++r)
+                S[(r0 + lk + 4 * r) * LT + r0 + li] -= (g[0][r] + g[1][r]) + (g[2][r] + g[3][r]);
         } else {
             if (wave < cb) {
                 // rows of finished waves: the strict upper part of this block column is zero
@@ -1989,9 +1901,7 @@ constexpr int PSTEP_THREADS = 512;
 // that can only start once column blocks of X are final, i.e. in the last three barrier intervals) and was the last to leave
 // in every step (in-kernel exit stamps: +1.6 us after the other panel blocks, and the next step waits for the launch).
 // POTRF_TWINS further workgroups solve the same tile redundantly and share the ten lower 16 x 16 tiles of X X^T with it.
-#ifndef POTRF_TWINS
-#define POTRF_TWINS 2
-#endif
+constexpr int POTRF_TWINS = 2;
 __host__ __device__ constexpr int potrf_twins(int Tn, int j) { return (Tn - j >= 2) ? POTRF_TWINS : 0; }
 // A twin reads tile (j + 1, j) of the matrix at its start; the owner overwrites that tile with L at its end -- and nothing orders
 // the start of one workgroup against the end of another (a twin may wait for a free CU).  So a twin counts itself into a word

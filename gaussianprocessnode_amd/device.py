@@ -52,8 +52,9 @@ class SGPDevice:
 
     def __init__(self, n_max: int, m: int, d: int, d_out: int = 1, device: int = 0, use_graph: bool = False,
                  keep_kuf: bool = False, persistent_chain: bool = False):
-        # (the round-2 persistent factorisation launch lives in a variant library of the same ABI, see _build.VARIANTS)
-        self._lib = _lib.load(variant="chain" if persistent_chain else None)
+        # persistent_chain sets the reserved SGP_FLAG_PERSISTENT_CHAIN (a removed experiment): the library
+        # refuses it, so True raises SGPError; the keyword stays so that existing callers passing False keep working
+        self._lib = _lib.load()
         self._h = C.c_void_p()
         flags = ((_lib.SGP_FLAG_GRAPH if use_graph else 0) | (_lib.SGP_FLAG_KEEP_KUF if keep_kuf else 0)
                  | (_lib.SGP_FLAG_PERSISTENT_CHAIN if persistent_chain else 0))
@@ -341,9 +342,9 @@ def kernelmatrix(A, B, sigma2: float, ell, device: int = 0):
     return K.T.copy()
 
 
-def potrf(A, device: int = 0, variant=None):
+def potrf(A, device: int = 0):
     """Lower Cholesky factor on the device (fastcholesky(A).L)."""
-    lib = _lib.load(variant=variant)
+    lib = _lib.load()
     A = as_f64(A)
     n = A.shape[0]
     L = np.empty((n, n))
@@ -351,9 +352,9 @@ def potrf(A, device: int = 0, variant=None):
     return L.T.copy()
 
 
-def potri(A, device: int = 0, variant=None):
+def potri(A, device: int = 0):
     """Inverse of an SPD matrix through its Cholesky factor on the device (cholinv(A))."""
-    lib = _lib.load(variant=variant)
+    lib = _lib.load()
     A = as_f64(A)
     n = A.shape[0]
     out = np.empty((n, n))

@@ -38,12 +38,7 @@ extern "C" {
                                  * than hipGraph replay at every size (tools/graph_vs_eager.py); kept as a no-op */
 #define SGP_FLAG_KEEP_KUF   2   /* keep K_uf resident for the per-point outputs (sgp_w_stats per_point) */
 #define SGP_FLAG_GRAPH      4   /* replay the launch sequences as captured hipGraphs (opt-in; bitwise the same results) */
-#define SGP_FLAG_PERSISTENT_CHAIN 8   /* EXPERIMENTAL, only in the variant library built with -DSGP_WITH_PERSISTENT_CHAIN
-                                 * (libsgp_hip_chain.so; the default library returns SGP_ERR_ARG from sgp_create): factor K_uu and
-                                 * Lambda with one persistent launch per factorisation (csrc/sgp_chain.hip.h) instead of one launch
-                                 * per 64-column step.  Correct and deterministic (it differs from the default by rounding: right- vs
-                                 * left-looking) but measured SLOWER on MI355X (24 vs 19.5 us per step at M = 512);
-                                 * ignored with SGP_FLAG_GRAPH and for matrices of more than 12 tile rows (d_out * M > 768). */
+#define SGP_FLAG_PERSISTENT_CHAIN 8   /* reserved (a removed experiment): sgp_create returns SGP_ERR_ARG */
 
 typedef struct sgp_handle sgp_handle;
 
@@ -270,14 +265,6 @@ int sgp_get_timestamps(sgp_handle* h, int64_t* out /* 2*SGP_T_COUNT */);
 /* Running totals of the per-sweep phase durations (same slots, 100 MHz ticks) over all sweeps since the last reset, and
  * the number of sweeps counted: the per-launch averages of the kernels INSIDE the timed sweeps. */
 int sgp_get_phase_totals(sgp_handle* h, int64_t* totals /* SGP_T_COUNT */, int64_t* count, int32_t reset);
-/* Diagnostics of the persistent factorisation launch (csrc/sgp_chain.hip.h), recorded when the handle was created with the
- * environment variable SGP_CHAIN_TRACE set: 12 steps x 32 ticks (100 MHz) during the last sweep.  Critical workgroup: [0] step
- * begins, [1] last pivot run of the diagonal tile done, [5] lower tile awaited, [2] lower tile arrived, [3] its last block
- * solved, [4] its share of the next diagonal tile's update applied, [6] / [7] waves 0 / 1 done with theirs, [8] far part of
- * the next diagonal tile received.  Feeder whose shipment this step consumes: [13] accumulation done, [9] last block solved,
- * [14] last product slice awaited, [10] ... done, [11] / [12] shipment stored by waves 0 / 4.
- * [16 + 4 cb ..]: that feeder's wave 0 at column block cb: block in registers, solved, published, updates applied.
- * which: 0 = K_uu chain, 1 = Lambda chain. */
 /* diagnostics of the Cholesky step kernel (all zeros unless the library was built with -DSGP_STEP_TRACE): out[512],
  * 100 MHz stamps of one panel workgroup of the Lambda chain (the owner of tile (j + 1, j), or the block chosen with
  * -DSGP_STEP_TRACE_A=a); slot 64 j + 32 g + e = event e of wave group g (0 factoring, 1 solve) in step j < 8.  Events: see
@@ -288,6 +275,7 @@ int sgp_get_step_trace(int64_t* out /* 512 */);
  * Lambda chain, 40 + j of the K_uu chain, 64 + first tile of a SYRK launch (k_syrk_direct / k_syrk_stream), 128 + first tile row of a k_assemble launch,
  * 200 + j the moment step j had its statistics, ... (csrc/sgp_kernels.hip.h, g_sweep_trace; tools/sweep_trace.py prints them). */
 int sgp_get_sweep_trace(int64_t* out /* 256 * 65 */);
+/* reserved (the removed persistent factorisation launch, see SGP_FLAG_PERSISTENT_CHAIN): returns SGP_ERR_ARG */
 int sgp_get_chain_trace(sgp_handle* h, int32_t which, int64_t* out /* 384 */);
 /* HIP-event timing of one data-sized kernel (which = SGP_T_GRAM or SGP_T_SYRK) launched eagerly `iters` times on
  * `stream` with the resident data of the last sweep; returns the average launch duration in microseconds. */
@@ -308,8 +296,8 @@ int sgp_time_kernel(sgp_handle* h, int32_t which, int32_t iters, void* stream, d
  * of groups with, per group, info[8 g ..] = {first, past-the-last tile column of P Lambda P, lower tiles, point chunks, points
  * per chunk, masked (0/1), CUs available, the Lambda-chain step that forms the group}.  Environment: SGP_OVERLAP=0 turns it
  * off, SGP_OVERLAP=1 forces it wherever it is possible, SGP_OVERLAP_COLS="3" / "2,4" sets the group boundaries.
- * "Fills the chip" = points x lower tiles >= 10 000 (SGP_GATE_MIN overrides): from there on the SYRK is k_syrk_direct (one
- * workgroup per CU, no LDS staging; SGP_SYRK_WIDE=0: the LDS-staged k_syrk_stream everywhere) and the K_uu chain is held back
+ * "Fills the chip" = points x lower tiles >= 10 000: from there on the SYRK is k_syrk_direct (one workgroup per CU, no LDS
+ * staging; below it the LDS-staged k_syrk_stream) and the K_uu chain is held back
  * until its single round is resident.  The planner places one cut, or two from six tile columns on while the masked launches
  * are short; a data-sharded sweep (hook installed) keeps one cut -- every group is a collective.
  * Host order of the launches: sgp_sweep on the library's streams enqueues the launches of the K_uu chain and of the Lambda chain

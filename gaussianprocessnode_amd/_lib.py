@@ -12,9 +12,9 @@ import numpy as np
 
 from . import _build
 
-SGP_FLAG_NO_GRAPH = 1
+SGP_FLAG_NO_GRAPH = 1          # no-op: launches are always eager
 SGP_FLAG_KEEP_KUF = 2
-SGP_FLAG_GRAPH = 4
+SGP_FLAG_GRAPH = 4             # no-op: graph replay was measured slower and removed (DESIGN.md "Launch mode")
 SGP_FLAG_PERSISTENT_CHAIN = 8
 SGP_S_YY, SGP_S_W, SGP_S_N, SGP_S_COUNT = 0, 1, 2, 8
 (SGP_R_SUM_I1, SGP_R_SUM_I2, SGP_R_ENERGY, SGP_R_INFO_KUU, SGP_R_INFO_LAMBDA, SGP_R_INFO_PRIOR,

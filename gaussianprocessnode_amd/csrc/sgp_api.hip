@@ -3,9 +3,9 @@
 // The handle owns every device buffer of one rank's shard; a sweep is two launch sequences
 // (sgp_sweep_local, sgp_sweep_finish) with the packed statistics buffer as the only hand-off, so that a
 // multi-GPU caller can sum-all-reduce that buffer in between (RCCL through torch.distributed).  Launches
-// are eager by default (~45 kernels per sweep, enqueued well ahead of the GPU); SGP_FLAG_GRAPH captures each
-// sequence once into a hipGraph and replays it -- bitwise the same results, measured ~20 us per sweep slower.
-// Per-sweep scalars travel through a pinned Params block that each sequence's first kernel mirrors on the device.
+// are eager (~45 kernels per sweep, enqueued well ahead of the GPU; replaying captured graphs measured ~20 us
+// per sweep slower, DESIGN.md "Launch mode").  Per-sweep scalars travel through a pinned Params block that each
+// sequence's first kernel mirrors on the device.
 #include "../../include/sgp_hip.h"
 #include "sgp_kernels.hip.h"
 
@@ -63,22 +63,6 @@ bool unregister_handle(sgp_handle* h) {          // false: not (or no longer) a 
     return true;
 }
 
-
-struct Graph {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int64_t key_n = -1;
-    int key_prior = -1;
-    int key_omega = -1;
-    void* key_stats = nullptr;
-    bool valid = false;
-    void reset() {
-        if (exec) hipGraphExecDestroy(exec);
-        if (graph) hipGraphDestroy(graph);
-        exec = nullptr; graph = nullptr; valid = false;
-    }
-};
-
 }  // namespace
 
 // words of sgp_handle::dJoin
@@ -100,6 +84,17 @@ struct StatGroup {
     int form_step;
     bool masked;           // runs on statM
     size_t slab_off;       // doubles into dSlabs
+};
+
+// How one sweep's launches meet, decided once by sweep_local_impl.  It is kept on the handle because sgp_sweep_local and
+// sgp_sweep_finish are separate calls, and a caller may run its own collective between them.
+struct SweepPlan {
+    hipStream_t stream = nullptr;  // the stream the statistics are enqueued on
+    bool overlapped = false;       // statistics in tile-row groups beside the Lambda chain (enqueue_stats_overlapped)
+    bool pack = false;             // the statistics go to dPack (exchange_stats follows)
+    bool events = false;           // the streams meet through events as well (all-reduce hook, caller's stream)
+    bool join_word = false;        // F2 waits on dJoin[WORD_JOIN] inside k_gemm32 instead of on evSide
+    bool kuu_interleaved = false;  // the K_uu chain's steps go out alternately with the Lambda chain's (enqueue_finish1)
 };
 
 struct sgp_handle {
@@ -143,10 +138,7 @@ struct sgp_handle {
     Params* dParamsK = nullptr;    // the K_uu chain's own copy (it runs on the side stream)
     long long* dJoin = nullptr;    // device-side join word of the two streams (see UvArgs::join)
     long long join_epoch = 0;
-    bool dev_words = false;        // this sweep's streams meet through device words (eager launches)
-    bool use_events = false;       // ... and (captured graphs, sweeps with an all-reduce hook) through events
-    bool overlap_now = false;      // the sweep being enqueued is an overlapped one (sweep_overlapped)
-    bool join_by_flag = false;     // this sweep's F2 waits on dJoin inside k_gemm32 instead of on evSide
+    SweepPlan plan;                // of the last sweep (sweep_local_impl), read by sgp_sweep_finish
     bool gate_side = false;        // the K_uu chain waits for the SYRK's resident round (dJoin[2]); the SYRK grid then uses all CUs
     long long grad_epoch = 0;      // dJoin[3]: the K_uu half of the theta gradient is complete (enqueue_theta_grad)
     long long done_epoch = 0;      // dJoin[1]: the last value a sweep's final kernel was told to write (see k_scalars)
@@ -172,7 +164,6 @@ struct sgp_handle {
     StatGroup grp[LAM_MAX_GROUPS];
     long long stat_epoch = 0;      // number of the last overlapped sweep: what its groups' words dJoin[WORD_GROUP0 + g] receive
     int env_overlap = -1;          // SGP_OVERLAP: 0 off, 1 on wherever it is possible; default: where the planner's model says it pays
-    bool defer_request = false, kuu_deferred = false;   // the K_uu chain's steps enqueued alternately with the Lambda chain's (sgp_sweep, see enqueue_finish1)
     bool env_interleave = true;     // the K_uu chain's and the Lambda chain's launches enqueued alternately (SGP_INTERLEAVE=0: chain after chain).  A sweep
                                     // that starts on an idle device -- the first of a block, every sweep of a caller that fetches something in between --
                                     // otherwise has its Lambda chain wait for the host to get through the other chain's 14 launches; once the host is a
@@ -184,11 +175,9 @@ struct sgp_handle {
     SyrkGeom geom{};               // the plain sweep's single SYRK launch over all tile rows (set_point_count)
     int64_t stats_count = 0;
     size_t slab_capacity = 0;
-    Graph gLocal, gFinish, gFinish2, gKuu;
     double* dBred = nullptr;
     double* dPack = nullptr;       // exchange buffer of data-sharded sweeps: [lower tiles | B | scalars] (allocated with the hook)
     int64_t pack_count = 0;
-    bool pack_now = false;         // the statistics being enqueued go to dPack (exchange_stats follows)
     sgp_allreduce_fn allreduce = nullptr;   // the multi-GPU exchange step of sgp_sweep (see include/sgp_hip.h)
     void* allreduce_ctx = nullptr;
     void* rccl_comm = nullptr;
@@ -573,7 +562,7 @@ extern "C" int sgp_create(const sgp_config* cfg, sgp_handle** out) {
     // is CU (i / 8 / 4) of shader engine (i / 8) % 4 of XCD i % 8 (measured with tools/cu_mask_probe.hip), so the first
     // 32 k bits are k CUs on every shader engine of every XCD -- a symmetric mask: an uneven one (e.g. 216 bits) leaves some
     // engines with fewer CUs than their equal share of the workgroups and costs a second round.
-    if (h->env_overlap != 0 && !(cfg->flags & SGP_FLAG_GRAPH) && h->dout == 1 && h->num_cus % 32 == 0 && h->num_cus / 32 > RESERVED_CUS_PER_SE) {
+    if (h->env_overlap != 0 && h->dout == 1 && h->num_cus % 32 == 0 && h->num_cus / 32 > RESERVED_CUS_PER_SE) {
         const int keep = h->num_cus - 32 * RESERVED_CUS_PER_SE;
         uint32_t mask[16] = {0};
         for (int i = 0; i < keep && i < 512; ++i) mask[i / 32] |= 1u << (i % 32);
@@ -612,10 +601,6 @@ extern "C" int sgp_destroy(sgp_handle* h) {
         delete h;
         return 0;
     }
-    h->gLocal.reset();
-    h->gFinish.reset();
-    h->gFinish2.reset();
-    h->gKuu.reset();
     void* bufs[] = {h->dXu, h->dXus, h->dX, h->dYw, h->dY, h->dYv, h->dOmega, h->dKuf, h->dBpart, h->dSlabs, h->dStatsOwn,
                     h->dDataScal, h->dKuu, h->dWk, h->dKinv, h->dLam, h->dWl, h->dSigma, h->dR, h->dTmp, h->dLambda0,
                     h->dXi, h->dMu, h->dXi0, h->dOut, h->dWishart, h->dTrace, h->dInfo, h->dStamps, h->dParams, h->dPa,
@@ -705,8 +690,8 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
     h->overlap = false;
     h->ngroups = 0;
     const int T = h->T;
-    if (!h->statM || h->env_overlap == 0 || h->dout != 1 || T < 3 || T > LAM_MAX_COLS || h->training ||
-        (h->cfg.flags & SGP_FLAG_GRAPH) || n < 1 || (!h->gate_side && h->env_overlap != 1))
+    if (!h->statM || h->env_overlap == 0 || h->dout != 1 || T < 3 || T > LAM_MAX_COLS || h->training || n < 1 ||
+        (!h->gate_side && h->env_overlap != 1))
         return;
     std::vector<int> cuts;                                   // group boundaries, ascending, in (0, T)
     for (int c : h->env_overlap_cols) if (c > 0 && c < T && (cuts.empty() || c > cuts.back())) cuts.push_back(c);
@@ -789,7 +774,7 @@ static int set_point_count(sgp_handle* h, int64_t n) {
     // profiles/r04_ab_log.txt [22]): N = 5 000, M = 512: 4 534 -> 4 970; C2 (N = 10 000, M = 256): 7 333 -> 7 640;
     // 3 000 x 512: 4 819 -> 5 057; 10 000 x 128: 10 523 -> 11 836; C4 (4 000 x 128): 11 205 -> 13 032; C5 (1 500 x 48, one tile:
     // 1 500) loses 2 % if gated and C1 15 %: the threshold is 10 000.
-    h->gate_side = n * (int64_t)h->ntiles >= GATE_MIN && h->dJoin && !(h->cfg.flags & SGP_FLAG_GRAPH);
+    h->gate_side = n * (int64_t)h->ntiles >= GATE_MIN;
     // (the in-CU split needs the whole LDS of a CU: only where the K_uu chain is gated behind this launch, i.e. the SYRK fills the chip)
     h->syrk_wide = h->gate_side;
     h->geom = syrk_geometry(0, h->T, h->num_cus - (h->gate_side ? 0 : SYRK_RESERVED_CUS), n, h->syrk_wide);
@@ -999,9 +984,6 @@ extern "C" int sgp_bind_stats(sgp_handle* h, void* stats_dev) {
     if (!h) return SGP_ERR_ARG;
     if (int qrc = quiesce(h)) return qrc;
     h->dStats = stats_dev ? static_cast<double*>(stats_dev) : h->dStatsOwn;
-    h->gLocal.valid = false;
-    h->gFinish.valid = false;
-    h->gFinish2.valid = false;
     return 0;
 }
 
@@ -1015,20 +997,21 @@ extern "C" int sgp_bind_stats(sgp_handle* h, void* stats_dev) {
 //   F1 (main stream) : Lambda chain -- Lambda formed in step 0, Cholesky + inverse factor, mu, p, scan, Uv pass 1
 //   F2 (main stream) : Sigma, R, both traces, Uv pass 2, scalars                               [sgp_sweep_finish]
 // The two chains are latency-bound pivot sequences that use a handful of CUs each; they overlap only when they sit on
-// different streams (parallel branches inside ONE captured graph were observed to execute back to back).
+// different streams.
 // the K_uu chain in three pieces -- [k_prep_xu, Gram] [Cholesky steps + inverse factor] [K_uu^-1, join word] -- so that a sweep can
 // enqueue its two chains' steps alternately (enqueue_chains_interleaved)
 static void kuu_gram(sgp_handle* h, hipStream_t s, bool gate) {
     if (gate) hipLaunchKernelGGL(k_gram_uu_lds, dim3(h->T, h->T), dim3(256), 0, s, h->dXusK, h->dKuu, h->dParamsK, h->M, h->Mp, h->D);
     else hipLaunchKernelGGL(k_gram_uu, dim3(h->T, h->T), dim3(256), 0, s, h->dXusK, h->dKuu, h->dParamsK, h->M, h->Mp, h->D);
 }
-static void kuu_tail(sgp_handle* h, hipStream_t s) {
+static void kuu_tail(sgp_handle* h, hipStream_t s, bool join_word) {
     launch_ata(h->dWk, h->dKinv, h->Mp, h->T, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->dSaccK);
-    if (h->join_by_flag) hipLaunchKernelGGL(k_join_set, dim3(1), dim3(64), 0, s, h->dJoin + WORD_JOIN, h->join_epoch);
+    if (join_word) hipLaunchKernelGGL(k_join_set, dim3(1), dim3(64), 0, s, h->dJoin + WORD_JOIN, h->join_epoch);
 }
-static void enqueue_kuu_head(sgp_handle* h, hipStream_t s, bool steps_too) {
-    const int M = h->M, Mp = h->Mp, D = h->D, T = h->T;
-    const bool words = h->dev_words && s == h->side;
+// (on the side stream the chain waits for the previous sweep's done word first; on the main stream, stream order covers it)
+static void enqueue_kuu_head(sgp_handle* h, hipStream_t s) {
+    const int M = h->M, Mp = h->Mp, D = h->D;
+    const bool words = s == h->side;
     // The gate (the chain's whole-CU workgroups stay off the chip until the SYRK's resident round is on it) sits inside k_prep_xu, in
     // front of K_uu's Gram: k_gram_uu_lds then starts together with the SYRK, gets a CU only as SYRK workgroups leave (it needs LDS, the
     // SYRK holds all of it) and the chain's first step begins a few microseconds after the SYRK has drained.  Round 4 tried to start
@@ -1043,12 +1026,12 @@ static void enqueue_kuu_head(sgp_handle* h, hipStream_t s, bool steps_too) {
                        gate ? (const long long*)(h->dJoin + WORD_GATE) : (const long long*)nullptr,
                        h->gate_epoch, h->spin_limit, h->dInfo + 3);
     kuu_gram(h, s, gate);
-    if (steps_too) {
-        launch_potrf(h->dKuu, Mp, T, h->dInfo + 0, M, h->dScratch, s, h->dWk, nullptr, h->dSaccK);
-        kuu_tail(h, s);
-    }
 }
-static void enqueue_kuu(sgp_handle* h, hipStream_t s) { enqueue_kuu_head(h, s, true); }
+static void enqueue_kuu(sgp_handle* h, hipStream_t s, bool join_word) {
+    enqueue_kuu_head(h, s);
+    launch_potrf(h->dKuu, h->Mp, h->T, h->dInfo + 0, h->M, h->dScratch, s, h->dWk, nullptr, h->dSaccK);
+    kuu_tail(h, s, join_word);
+}
 
 static void launch_gram(sgp_handle* h, hipStream_t s, bool opens_sweep) {
     int64_t* sweep_begin = opens_sweep ? h->dStamps : nullptr;
@@ -1060,18 +1043,21 @@ static void launch_gram(sgp_handle* h, hipStream_t s, bool opens_sweep) {
                            h->dParams, h->M, h->Mp, h->D, h->n, h->dout, h->dStamps + STAMP_STRIDE * SGP_T_GRAM, sweep_begin);
 }
 
-static void enqueue_local(sgp_handle* h, hipStream_t s) {
-    const int M = h->M, Mp = h->Mp, D = h->D, T = h->T;
-    // The scaled inducing inputs and the parameter mirror only change when a setter ran: a sweep at unchanged parameters
-    // (VMP iterations at fixed theta) starts with the Gram kernel.  (Always in graph mode -- the captured sequence is fixed
-    // -- and without data, where no Gram kernel exists to open the sweep's stamps.)
-    const bool prep = h->main_prep_gen != h->params_gen || (h->cfg.flags & SGP_FLAG_GRAPH) || h->n <= 0;
-    if (prep) {
-        hipLaunchKernelGGL(k_prep_xu, dim3((Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXus, h->params_src,
-                           h->dParams, (int*)nullptr, M, Mp, D, h->dStamps, (int)SGP_T_COUNT, (int)SGP_T_SWEEP,
-                           (const long long*)nullptr, 0LL, (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
-        h->main_prep_gen = h->params_gen;
-    }
+// The scaled inducing inputs and the parameter mirror of the main stream (dXus, dParams) only change when a setter ran: a sweep
+// at unchanged parameters (VMP iterations at fixed theta) starts with the Gram kernel.  `always`: a sweep without data has no
+// Gram kernel to open its phase stamps, so k_prep_xu, which opens them too, runs regardless.
+static void prep_main(sgp_handle* h, hipStream_t s, bool always) {
+    if (!always && h->main_prep_gen == h->params_gen) return;
+    hipLaunchKernelGGL(k_prep_xu, dim3((h->Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXus, h->params_src,
+                       h->dParams, (int*)nullptr, h->M, h->Mp, h->D, h->dStamps, (int)SGP_T_COUNT, (int)SGP_T_SWEEP,
+                       (const long long*)nullptr, 0LL, (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
+    h->main_prep_gen = h->params_gen;
+}
+
+// `pack`: the statistics go to the exchange buffer (exchange_stats follows)
+static void enqueue_local(sgp_handle* h, hipStream_t s, bool pack) {
+    const int Mp = h->Mp, T = h->T;
+    prep_main(h, s, h->n <= 0);
     if (h->n > 0) {
         launch_gram(h, s, true);
         long long* gate = h->gate_side ? h->dJoin + WORD_GATE : nullptr;
@@ -1082,9 +1068,9 @@ static void enqueue_local(sgp_handle* h, hipStream_t s) {
     if (h->n <= 0) { ga = syrk_geometry(0, T, h->num_cus, 0); }       // no data: zero chunks, the statistics are zero
     // (data-sharded sweeps write the exchange buffer instead: lower tiles only, see exchange_stats)
     hipLaunchKernelGGL(k_assemble, dim3(T, T + 1, assemble_z(ga)), dim3(256), 0, s, h->dSlabs, h->dBpart, h->dDataScal,
-                       h->pack_now ? h->dPack : h->dStats, Mp, T, ga, h->n > 0 ? h->nblk : 0, h->dout,
+                       pack ? h->dPack : h->dStats, Mp, T, ga, h->n > 0 ? h->nblk : 0, h->dout,
                        SGP_S_COUNT + h->dout * h->dout, 1, h->dStamps + STAMP_STRIDE * SGP_T_LOCAL, h->dInfo + 1, (long long*)nullptr, 0LL,
-                       h->pack_now ? 1 : 0, h->dBred);
+                       pack ? 1 : 0, h->dBred);
 }
 
 // The statistics of an overlapped sweep (see plan_overlap): the same kernels, the SYRK and the assembly once per tile-row group.
@@ -1103,17 +1089,11 @@ static int exchange_stats(sgp_handle* h, hipStream_t s, int tile0, int ntile, bo
 // word: words are waited for with a bounded spin, and a collective that builds its rings or waits for a straggler rank may take
 // longer than that.  The chain therefore starts after (statistics of group 0 -> reduce of 0.6 MB) instead of (all statistics ->
 // reduce of 1.18 MB), and the second reduce runs beside it.  Every rank calls the hook in the same order (group 0, 1, ...).
-static int enqueue_stats_overlapped(sgp_handle* h, hipStream_t own) {
-    const int M = h->M, Mp = h->Mp, D = h->D, T = h->T;
-    const bool sharded = h->allreduce != nullptr;
-    // (as in enqueue_local: a sweep at unchanged parameters starts with the Gram kernel)
-    const bool prep = h->main_prep_gen != h->params_gen;
-    if (prep) {
-        hipLaunchKernelGGL(k_prep_xu, dim3((Mp + 255) / 256), dim3(256), 0, own, h->dXu, h->dXus, h->params_src,
-                           h->dParams, (int*)nullptr, M, Mp, D, h->dStamps, (int)SGP_T_COUNT, (int)SGP_T_SWEEP,
-                           (const long long*)nullptr, 0LL, (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
-        h->main_prep_gen = h->params_gen;
-    }
+static int enqueue_stats_overlapped(sgp_handle* h, const SweepPlan& p) {
+    const int Mp = h->Mp, T = h->T;
+    hipStream_t own = p.stream;
+    const bool sharded = p.pack;
+    prep_main(h, own, false);
     launch_gram(h, own, true);
     // The masked groups start when group 0's assembly starts, i.e. its SYRK has drained.  Measured against starting them as soon
     // as group 0's SYRK has its round on the CUs (the masked SYRK then fills the CUs as they drain, but group 0's assembly shares
@@ -1141,7 +1121,7 @@ static int enqueue_stats_overlapped(sgp_handle* h, hipStream_t own) {
     return 0;
 }
 
-static void enqueue_finish1(sgp_handle* h, hipStream_t s) {
+static void enqueue_finish1(sgp_handle* h, hipStream_t s, const SweepPlan& p) {
     const int M = h->M, Mp = h->Mp, Q = h->Q, Qp = h->Qp, TQ = h->TQ;
     // Lambda is factored in index-reversed order (P Lambda P = L' L'^T): its inverse factor W' = L'^-1 then IS the upper
     // Cholesky factor of Sigma_v up to the reversal, and Uv follows by a rank-1 update instead of a third potrf.
@@ -1157,7 +1137,7 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s) {
     form.trace_chain = 1;
     hipEvent_t step_wait[LAM_MAX_COLS] = {nullptr};
     bool any_wait = false;
-    if (h->overlap_now) {
+    if (p.overlapped) {
         // the statistics arrive group by group while the chain runs (enqueue_stats_overlapped): step G.form_step forms group G.
         // Group 0 was summed on this very stream: nothing to wait for.  (A step 0 resident from the start of the sweep and
         // waiting for its statistics itself was measured too: on T + 1 CUs it keeps group 0's SYRK from its full single round,
@@ -1169,15 +1149,15 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s) {
         for (int g = 0; g < h->ngroups; ++g) {
             for (int c = h->grp[g].c0; c < h->grp[g].c1; ++c) {
                 form.form_step[c] = (unsigned char)h->grp[g].form_step;
-                form.col_group[c] = (h->grp[g].masked && !h->allreduce) ? (unsigned char)g : (unsigned char)0xff;
+                form.col_group[c] = (h->grp[g].masked && !p.pack) ? (unsigned char)g : (unsigned char)0xff;
             }
-            if (h->grp[g].masked && h->allreduce) { step_wait[h->grp[g].form_step] = h->evGroup[g]; any_wait = true; }
+            if (h->grp[g].masked && p.pack) { step_wait[h->grp[g].form_step] = h->evGroup[g]; any_wait = true; }
         }
     }
     double* uvt0 = h->dUvWork + 2 * (size_t)Qp;     // t = W' P xi, advanced block by block during the factorisation
     PotrfSeq lam(h->dLam, Qp, TQ, h->dInfo + 1, Qp, h->dScratch + POTRF_SCRATCH, s, h->dWl, &form, h->dTmp, h->dXi, uvt0,
                  any_wait ? step_wait : nullptr);
-    if (h->kuu_deferred) {
+    if (p.kuu_interleaved) {
         // (The default; SGP_INTERLEAVE=0 turns it off.)  The K_uu chain's Cholesky steps were held back (sweep_local_impl): its launches and the
         // Lambda chain's go out ALTERNATELY, so that on a GPU that is idle when the sweep arrives neither chain waits for the host to
         // get through the other's ten launches (the Lambda chain's first step arrives ~25 us after the GPU is ready for it).  Same
@@ -1189,7 +1169,7 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s) {
             if (!lam.done()) lam.next();
             if (!kuu.done()) kuu.next();
         }
-        kuu_tail(h, h->side);
+        kuu_tail(h, h->side, p.join_word);
     } else {
         while (!lam.done()) lam.next();
     }
@@ -1206,12 +1186,12 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s) {
 }
 
 // after the join with the side stream (K_uu chain): Sigma, R, the traces, Uv pass 2 and the scalars
-// k_scalars' pinned mirror (see there): on for eager sweeps outside a device-paced training run (whose loop reads nothing back)
+// k_scalars' pinned mirror (see there): on for sweeps outside a device-paced training run (whose loop reads nothing back)
 static double* mirror_for(const sgp_handle* h) {
-    return (h->hMirror && !(h->cfg.flags & SGP_FLAG_GRAPH) && !h->env_no_zero_copy && !h->training) ? h->hMirror : nullptr;
+    return (h->hMirror && !h->env_no_zero_copy && !h->training) ? h->hMirror : nullptr;
 }
 
-static void enqueue_finish2(sgp_handle* h, hipStream_t s) {
+static void enqueue_finish2(sgp_handle* h, hipStream_t s, bool join_word) {
     const int M = h->M, Mp = h->Mp, Q = h->Q, Qp = h->Qp, TQ = h->TQ;
     double* uvp = h->dXi;
     double* uvck = h->dUvWork;
@@ -1226,7 +1206,7 @@ static void enqueue_finish2(sgp_handle* h, hipStream_t s) {
     UvArgs uv;
     uv.Wp = h->dWl; uv.p = uvp; uv.ck = uvck; uv.ak = uvak; uv.partial = uvpart; uv.LR = h->dUvT;
     uv.stamps = h->dStamps + STAMP_STRIDE * SGP_T_FINISH1;
-    uv.join = h->join_by_flag ? h->dJoin + WORD_JOIN : nullptr;
+    uv.join = join_word ? h->dJoin + WORD_JOIN : nullptr;
     uv.join_need = h->join_epoch;
     uv.spin_limit = h->spin_limit;
     uv.sync_status = h->dInfo + 3;
@@ -1243,7 +1223,7 @@ static void enqueue_finish2(sgp_handle* h, hipStream_t s) {
     hipLaunchKernelGGL(k_scalars, dim3(1), dim3(256), 0, s, h->dStats, partK, nK, (const double*)traceR, nR, h->dMu, h->dKuu,
                        h->dLam, h->dInfo, h->dParams, h->dOut, h->dWishart, M, Mp, h->dout, Q, Qp, Qp - Q,
                        h->dStamps + STAMP_STRIDE * SGP_T_FINISH2, h->dStamps, h->dStampTotals,
-                       (h->cfg.flags & SGP_FLAG_GRAPH) ? (long long*)nullptr : h->dJoin + WORD_DONE, h->done_epoch,
+                       h->dJoin + WORD_DONE, h->done_epoch,
                        (const double*)(h->dScratch + POTRF_LOGDET), h->T, (const double*)(h->dScratch + POTRF_SCRATCH + POTRF_LOGDET), TQ,
                        mirror_for(h));
 }
@@ -1272,29 +1252,6 @@ struct DevBuf {
 }  // namespace
 
 
-typedef void (*enqueue_fn)(sgp_handle*, hipStream_t);
-
-static int run_sequence(sgp_handle* h, Graph& g, enqueue_fn fn, hipStream_t s) {
-    if (!(h->cfg.flags & SGP_FLAG_GRAPH)) {
-        fn(h, s);
-        HIPCHK(h, hipGetLastError());
-        return 0;
-    }
-    if (!g.valid || g.key_n != h->n || g.key_prior != h->prior_form || g.key_stats != (void*)h->dStats ||
-        g.key_omega != (int)h->has_omega) {
-        g.reset();
-        // capture on the library's own stream (the caller's stream may be the legacy default stream)
-        HIPCHK(h, hipStreamBeginCapture(h->own, hipStreamCaptureModeThreadLocal));
-        fn(h, h->own);
-        hipError_t e = hipStreamEndCapture(h->own, &g.graph);
-        if (e != hipSuccess) { h->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return SGP_ERR_HIP; }
-        HIPCHK(h, hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-        g.key_n = h->n; g.key_prior = h->prior_form; g.key_stats = h->dStats; g.key_omega = (int)h->has_omega; g.valid = true;
-    }
-    HIPCHK(h, hipGraphLaunch(g.exec, s));
-    return 0;
-}
-
 static int check_ready(sgp_handle* h) {
     if (!h) return SGP_ERR_ARG;
     if (!h->have_inducing || !h->have_data || !h->have_kernel)
@@ -1303,42 +1260,41 @@ static int check_ready(sgp_handle* h) {
 }
 
 // `overlapped`: the statistics go to the handle's own statistics streams in tile-row groups and the Lambda chain (sgp_sweep_finish
-// on the library's stream) starts on the first group while the others are still being summed (plan_overlap); only from
-// sgp_sweep, which owns both halves.
-static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped) {
+// on the library's stream) starts on the first group while the others are still being summed (plan_overlap); `interleave`: the
+// K_uu chain's steps may go out alternately with the Lambda chain's; `pack`: the statistics go to the exchange buffer.  All three
+// only from sgp_sweep, which owns both halves.
+static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool interleave, bool pack) {
     int rc = check_ready(h);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
+    SweepPlan p;
+    p.stream = stream ? static_cast<hipStream_t>(stream) : h->own;
+    p.overlapped = overlapped;
+    p.pack = pack;
     if (h->sync_reported) {
         // (the getter that reported the word had drained the device: nothing is in flight)
         HIPCHK(h, hipMemset(h->dInfo + 3, 0, sizeof(int)));
         h->sync_reported = false;
     }
     h->in_flight = true;
-    h->overlap_now = overlapped;
     // The K_uu chain depends on theta and Xu only: it starts on the (low-priority) side stream as soon as the previous
     // sweep has finished with its outputs, runs beside the data-sized kernels, the all-reduce and the Lambda chain, and is
-    // joined just before the Sigma launch.  Eager launches meet through device words (the chain's first kernel waits for the
-    // previous sweep's done word itself, see enqueue_kuu): an event record or wait between two kernels of a stream was
-    // measured at ~6 us of idle time.  Captured graphs use events -- and so does a sweep with an all-reduce hook, in addition:
-    // the words are waited for with a BOUNDED spin (~1 s), and a collective that builds its rings or waits for a straggler
-    // rank may take longer than that.
-    const bool graph = (h->cfg.flags & SGP_FLAG_GRAPH) != 0;
-    const bool hooked = h->allreduce != nullptr;
-    h->dev_words = !graph;
+    // joined just before the Sigma launch.  The streams meet through device words (the chain's first kernel waits for the
+    // previous sweep's done word itself, see enqueue_kuu_head): an event record or wait between two kernels of a stream was
+    // measured at ~6 us of idle time.  A sweep with an all-reduce hook uses events in addition: the words are waited for with
+    // a BOUNDED spin (~1 s), and a collective that builds its rings or waits for a straggler rank may take longer than that.
     // (a caller's stream as well: two-phase callers -- sgp_sweep_local, their own reduce, sgp_sweep_finish -- may sit in a collective
     // between the halves for longer than the bounded words wait, exactly like the hook)
-    h->use_events = graph || hooked || s != h->own;
-    if (h->use_events) HIPCHK(h, hipStreamWaitEvent(h->side, h->evDone, 0));
+    p.events = h->allreduce != nullptr || p.stream != h->own;
+    if (p.events) HIPCHK(h, hipStreamWaitEvent(h->side, h->evDone, 0));
     // How F2 will join the K_uu chain: an event wait between two kernels of the main stream costs it ~5 us of idle time even
     // when the event fired long ago, so the UniSGP path lets the Sigma launch's product workgroups poll a device word in
     // front of their epilogue instead (k_join_set behind the chain's last kernel).  Only while that launch leaves enough
     // CUs free for a late chain's workgroups (each needs a whole CU's LDS) -- which nobody can promise when a collective or a
-    // second handle's sweep may hold CUs too --, and not inside captured graphs.
+    // second handle's sweep may hold CUs too.
     {
         const int grid = h->TQ * (h->TQ + 1) / 2 * 4 + h->TQ * h->TQ;
-        h->join_by_flag = h->dJoin && h->dout == 1 && !h->use_events && grid <= h->num_cus - 40 && g_live_handles.load() <= 1;
+        p.join_word = h->dout == 1 && !p.events && grid <= h->num_cus - 40 && g_live_handles.load() <= 1;
         ++h->join_epoch;
     }
     ++h->gate_epoch;
@@ -1348,28 +1304,27 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped) {
     // something, next sweep -- otherwise has its Gram kernel wait ~50 us for the host to get through launches the GPU cannot run
     // yet.  (Back-to-back sweeps are enqueued a sweep ahead either way.)  Small problems keep the chain first: there the two chains
     // are the sweep.  With an all-reduce hook too: the hook is a host callback that may block (gloo), the chain should be queued by then.
-    const bool stats_first = h->gate_side && h->n > 0 && !graph && !h->allreduce;
+    const bool stats_first = h->gate_side && h->n > 0 && !h->allreduce;
+    // (one-shot sgp_sweep on the library's streams: only the K_uu chain's first two kernels go out here, its steps are enqueued
+    // alternately with the Lambda chain's by sgp_sweep_finish -- see enqueue_finish1)
+    p.kuu_interleaved = interleave && stats_first && !p.events;
+    h->plan = p;
     auto enqueue_stats = [&]() -> int {
         if (overlapped) {
-            if (int orc = enqueue_stats_overlapped(h, s)) return orc;
-            HIPCHK(h, hipGetLastError());
-            return 0;
-        }
-        return run_sequence(h, h->gLocal, enqueue_local, s);
+            if (int orc = enqueue_stats_overlapped(h, p)) return orc;
+        } else
+            enqueue_local(h, p.stream, p.pack);
+        HIPCHK(h, hipGetLastError());
+        return 0;
     };
     if (stats_first)
         if (int src = enqueue_stats()) return src;
-    // (one-shot sgp_sweep on the library's streams: only the K_uu chain's first two kernels go out here, its steps are enqueued
-    // alternately with the Lambda chain's by sgp_sweep_finish -- see enqueue_finish1)
-    h->kuu_deferred = h->defer_request && stats_first && !h->use_events && s == h->own;
-    if (h->kuu_deferred) {
-        enqueue_kuu_head(h, h->side, false);
-        HIPCHK(h, hipGetLastError());
-        rc = 0;
-    } else
-        rc = run_sequence(h, h->gKuu, enqueue_kuu, h->side);
-    if (rc) return rc;
-    if (!h->kuu_deferred) HIPCHK(h, hipEventRecord(h->evSide, h->side));
+    if (p.kuu_interleaved)
+        enqueue_kuu_head(h, h->side);
+    else
+        enqueue_kuu(h, h->side, p.join_word);
+    HIPCHK(h, hipGetLastError());
+    if (!p.kuu_interleaved) HIPCHK(h, hipEventRecord(h->evSide, h->side));
     if (!stats_first)
         if (int src = enqueue_stats()) return src;
     h->stats_dirty = false;
@@ -1379,28 +1334,27 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped) {
     return 0;
 }
 
-extern "C" int sgp_sweep_local(sgp_handle* h, void* stream) { return sweep_local_impl(h, stream, false); }
+extern "C" int sgp_sweep_local(sgp_handle* h, void* stream) { return sweep_local_impl(h, stream, false, false, false); }
 
 extern "C" int sgp_sweep_finish(sgp_handle* h, void* stream) {
     if (!h) return SGP_ERR_ARG;
     if (!h->swept_local) return fail(h, SGP_ERR_ARG, "sgp_sweep_finish: call sgp_sweep_local first");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
+    const SweepPlan p = h->plan;
+    // (a repeated sgp_sweep_finish runs F1 and F2 alone: the statistics are complete and the K_uu chain has gone out)
+    h->plan.overlapped = h->plan.kuu_interleaved = false;
     h->in_flight = true;
-    int rc = run_sequence(h, h->gFinish, enqueue_finish1, s);
-    if (rc) return rc;
-    if (h->kuu_deferred) {                                   // (the K_uu chain's steps and tail went out inside enqueue_finish1)
-        HIPCHK(h, hipEventRecord(h->evSide, h->side));
-        h->kuu_deferred = false;
-    }
-    if (!h->join_by_flag) HIPCHK(h, hipStreamWaitEvent(s, h->evSide, 0));          // join with the K_uu chain
+    enqueue_finish1(h, s, p);
+    HIPCHK(h, hipGetLastError());
+    if (p.kuu_interleaved) HIPCHK(h, hipEventRecord(h->evSide, h->side));   // (the K_uu chain's steps and tail went out inside enqueue_finish1)
+    if (!p.join_word) HIPCHK(h, hipStreamWaitEvent(s, h->evSide, 0));          // join with the K_uu chain
     ++h->done_epoch;                                         // what this sweep's k_scalars writes when it is through
-    rc = run_sequence(h, h->gFinish2, enqueue_finish2, s);
-    if (rc) return rc;
+    enqueue_finish2(h, s, p.join_word);
+    HIPCHK(h, hipGetLastError());
     h->mirror_epoch = mirror_for(h) ? h->done_epoch : -1;
     // the next sweep's K_uu chain may overwrite K_uu^-1 after this
-    if (h->use_events) HIPCHK(h, hipEventRecord(h->evDone, s));
-    h->overlap_now = false;
+    if (p.events) HIPCHK(h, hipEventRecord(h->evDone, s));
     h->swept = true;
     h->last_stream = s;
     return 0;
@@ -1430,11 +1384,7 @@ extern "C" int sgp_sweep(sgp_handle* h, void* stream) {
     // single GPU, the library's own streams, a problem that qualifies: statistics and Lambda chain overlapped
     // (with an all-reduce hook as well: one reduce per statistics group, see enqueue_stats_overlapped)
     const bool overlapped = h->overlap && !stream && h->n > 0 && !h->training;
-    h->pack_now = h->allreduce != nullptr;
-    h->defer_request = h->env_interleave;
-    int rc = sweep_local_impl(h, stream, overlapped);
-    h->defer_request = false;
-    h->pack_now = false;
+    int rc = sweep_local_impl(h, stream, overlapped, h->env_interleave, h->allreduce != nullptr);
     if (rc) return rc;
     if (h->allreduce && !overlapped) {
         rc = exchange_stats(h, stream ? static_cast<hipStream_t>(stream) : h->own);
@@ -1958,7 +1908,7 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
     // derivatives) and the K_uu half (H = K_uu^-1 Psi2 K_uu^-1 against dK_uu).  On the library's own streams they run side
     // by side -- the K_uu half on the side stream, which idles between two sweeps -- and meet in the finishing kernel through
     // a device word (an event would cost the main stream ~6 us, see sgp_sweep_finish).
-    const bool split = s == h->own && h->dJoin && !(h->cfg.flags & SGP_FLAG_GRAPH);
+    const bool split = s == h->own;
     h->mirror_epoch = -1;                      // (the gradient's hand-offs report into the same status word)
     hipStream_t su = split ? h->side : s;
     if (split)
@@ -1994,10 +1944,8 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
 }
 
 static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value) {
-    enqueue_kuu(h, s);
-    h->pack_now = h->allreduce != nullptr;
-    enqueue_local(h, s);
-    h->pack_now = false;
+    enqueue_kuu(h, s, false);
+    enqueue_local(h, s, h->allreduce != nullptr);
     // (data-sharded run: the statistics re-formed at the new theta are this rank's -- sum them like a sweep's)
     if (h->allreduce)
         if (int xrc = exchange_stats(h, s)) return xrc;
@@ -2075,7 +2023,6 @@ extern "C" int sgp_train_begin(sgp_handle* h, const double* X, const double* y, 
     if (!h || !X || !y || !theta_raw) return fail(h, SGP_ERR_ARG, "sgp_train_begin: null argument");
     if (int qrc = quiesce(h)) return qrc;
     if (h->dout != 1) return fail(h, SGP_ERR_ARG, "sgp_train_begin: the theta objective is defined for UniSGP (d_out = 1)");
-    if (h->cfg.flags & SGP_FLAG_GRAPH) return fail(h, SGP_ERR_ARG, "sgp_train_begin: not with SGP_FLAG_GRAPH (the window moves every step)");
     // (a caller-bound statistics buffer is fine here: inside sgp_train_step nobody but the library -- through the all-reduce hook,
     // if one is installed -- touches the statistics between the two halves of the sweep)
     if (!h->have_inducing) return fail(h, SGP_ERR_ARG, "sgp_train_begin: call sgp_set_inducing first");
@@ -2187,10 +2134,7 @@ extern "C" int sgp_train_step(sgp_handle* h, int64_t offset, int64_t n, int32_t 
     int rc = set_point_count(h, n);
     if (!rc && h->train_probit) {
         // q(f) of the window: forward message from the carried posterior mean at the current theta, then the Probit moments
-        hipLaunchKernelGGL(k_prep_xu, dim3((h->Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXus, h->params_src, h->dParams, (int*)nullptr,
-                           h->M, h->Mp, h->D, h->dStamps, (int)SGP_T_COUNT, (int)SGP_T_SWEEP, (const long long*)nullptr, 0LL,
-                           (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
-        h->main_prep_gen = h->params_gen;                      // (the sweep below starts with its Gram kernel)
+        prep_main(h, s, false);                                // (theta moved, so it runs; the sweep below starts with its Gram kernel)
         double* mz = h->dCall;
         if (n > 0) {
             switch (h->D) {
@@ -2220,7 +2164,7 @@ extern "C" int sgp_train_step(sgp_handle* h, int64_t offset, int64_t n, int32_t 
                                (const double*)(h->dStats + (size_t)h->Mp * h->Mp + (size_t)h->Mp * h->dout + SGP_S_N));
         // the next K_uu chain (side stream) reads the parameters this step wrote and overwrites the K_uu^-1 its gradient read
         if (!rc) hipLaunchKernelGGL(k_join_set, dim3(1), dim3(64), 0, s, h->dJoin + WORD_DONE, ++h->done_epoch);
-        if (!rc && h->use_events) HIPCHK(h, hipEventRecord(h->evDone, s));   // (hooked run: the next K_uu chain waits on this, see sweep_local_impl)
+        if (!rc && h->plan.events) HIPCHK(h, hipEventRecord(h->evDone, s));   // (hooked run: the next K_uu chain waits on this, see sweep_local_impl)
     }
     h->dX = ownX; h->dYw = ownYw; h->dY = ownY;
     h->has_yv = false;

@@ -29,8 +29,8 @@ constexpr int LT = TB + 1;      // row stride of a 64 x 64 LDS tile
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-// Parameters that change from sweep to sweep (theta, w): kept in device memory so that a captured
-// hipGraph replays with fresh values (the graph's first node copies them from pinned host memory).
+// Parameters that change from sweep to sweep (theta, w): kept in device memory, where the first kernel of a
+// launch sequence (k_prep_xu) copies them from the pinned host block.
 struct Params {
     double sigma2;
     double jitter;

@@ -53,7 +53,9 @@ class SGPDevice:
     def __init__(self, n_max: int, m: int, d: int, d_out: int = 1, device: int = 0, use_graph: bool = False,
                  keep_kuf: bool = False, persistent_chain: bool = False):
         # persistent_chain sets the reserved SGP_FLAG_PERSISTENT_CHAIN (a removed experiment): the library
-        # refuses it, so True raises SGPError; the keyword stays so that existing callers passing False keep working
+        # refuses it, so True raises SGPError; the keyword stays so that existing callers passing False keep working.
+        # use_graph sets SGP_FLAG_GRAPH, which the library ignores (graph replay was removed, DESIGN.md "Launch mode"): kept for
+        # existing callers, launches are eager either way
         self._lib = _lib.load()
         self._h = C.c_void_p()
         flags = ((_lib.SGP_FLAG_GRAPH if use_graph else 0) | (_lib.SGP_FLAG_KEEP_KUF if keep_kuf else 0)

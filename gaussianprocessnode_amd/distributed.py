@@ -81,7 +81,8 @@ def device_tensor(ptr: int, count: int, device="cuda"):
 
 
 class HipEngine:
-    """This rank's shard on its MI355X: local statistics and the replicated tail through the C ABI."""
+    """This rank's shard on its MI355X: local statistics and the replicated tail through the C ABI.  `use_graph` is accepted
+    and ignored (see SGPDevice)."""
 
     def __init__(self, n_max: int, m: int, d: int, d_out: int = 1, device: int = 0, use_graph: bool = False):
         import torch

@@ -34,10 +34,10 @@ extern "C" {
 #define SGP_ERR_NOMEM    (-4)
 
 /* flags for sgp_config.flags */
-#define SGP_FLAG_NO_GRAPH   1   /* launch kernels eagerly -- the default since eager launches measured ~20 us per sweep faster
-                                 * than hipGraph replay at every size (tools/graph_vs_eager.py); kept as a no-op */
+#define SGP_FLAG_NO_GRAPH   1   /* launch kernels eagerly -- what every handle does; kept as a no-op */
 #define SGP_FLAG_KEEP_KUF   2   /* keep K_uf resident for the per-point outputs (sgp_w_stats per_point) */
-#define SGP_FLAG_GRAPH      4   /* replay the launch sequences as captured hipGraphs (opt-in; bitwise the same results) */
+#define SGP_FLAG_GRAPH      4   /* replayed the launch sequences as captured hipGraphs, measured ~20 us per sweep slower than
+                                 * eager launches at every size and removed (DESIGN.md "Launch mode"); kept as a no-op */
 #define SGP_FLAG_PERSISTENT_CHAIN 8   /* reserved (a removed experiment): sgp_create returns SGP_ERR_ARG */
 
 typedef struct sgp_handle sgp_handle;
@@ -212,7 +212,7 @@ int sgp_theta_objective(sgp_handle* h, double* value, double* grad);
  * kernel parameters from where the optimiser kernel wrote them, so the host only enqueues and never waits in the loop.
  *   sgp_train_begin  X is n_total x D point-major (row i = point i), y n_total; theta_raw[1 + n_ell] the raw
  *                    (pre-softplus) parameters (sigma2 first); noise, prior and inducing inputs as the setters left them;
- *                    AdaMax(eta, (beta1, beta2), eps) starts from zero state.  UniSGP handles without SGP_FLAG_GRAPH.  With an
+ *                    AdaMax(eta, (beta1, beta2), eps) starts from zero state.  UniSGP handles only.  With an
  *                    all-reduce hook installed (sgp_set_allreduce / sgp_use_rccl) the run is data-sharded: every rank
  *                    passes ITS slice of each minibatch to sgp_train_step (possibly empty), statistics and the data half
  *                    of the gradient are summed through the hook, AdaMax runs replicated on identical gradients and every

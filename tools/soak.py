@@ -12,8 +12,8 @@ n_sweeps = int(sys.argv[1]) if len(sys.argv) > 1 else 5000
 d = np.load(os.path.join(ROOT, "tests", "golden", "kin40k_data.npz")); f = np.load(os.path.join(ROOT, "tests", "golden", "kin40k_fixture.npz"))
 p = softplus(f["theta_opt"])
 bad = 0
-for M, use_graph in ((512, False), (600, False), (512, True)):
-    with G.SGPDevice(10000, M, 8, use_graph=use_graph) as dev:
+for M in (512, 600):
+    with G.SGPDevice(10000, M, 8) as dev:
         dev.set_inducing(f["Xu"][:M]); dev.set_data(d["xtrain"], d["ytrain"]); dev.set_kernel(float(p[0]), p[1:], 0.0)
         dev.set_prior_isotropic(50.0); dev.set_noise([[1e4]])
         dev.sweep(); ref = dev.posterior(); ref_sc = dev.scalars()
@@ -26,5 +26,5 @@ for M, use_graph in ((512, False), (600, False), (512, True)):
                 bad += (not same)
                 for _ in range(7): dev.sweep()   # ... bursts without any host synchronisation in between
         dt = time.perf_counter() - t0
-    print(f"M={M} graph={use_graph}: {n_sweeps} sweeps, {bad} mismatches so far, {dt:.1f} s", flush=True)
+    print(f"M={M}: {n_sweeps} sweeps, {bad} mismatches so far, {dt:.1f} s", flush=True)
 sys.exit(1 if bad else 0)

@@ -16,6 +16,8 @@ SGP_FLAG_NO_GRAPH = 1          # no-op: launches are always eager
 SGP_FLAG_KEEP_KUF = 2
 SGP_FLAG_GRAPH = 4             # no-op: graph replay was measured slower and removed (DESIGN.md "Launch mode")
 SGP_FLAG_PERSISTENT_CHAIN = 8
+SGP_FLAG_REUSE_STATS = 16      # sgp_sweep reuses the resident statistics where the setters left them valid (sgp_sweep_kind)
+SGP_SWEEP_FULL, SGP_SWEEP_TARGETS, SGP_SWEEP_REUSED = 0, 1, 2
 SGP_S_YY, SGP_S_W, SGP_S_N, SGP_S_COUNT = 0, 1, 2, 8
 (SGP_R_SUM_I1, SGP_R_SUM_I2, SGP_R_ENERGY, SGP_R_INFO_KUU, SGP_R_INFO_LAMBDA, SGP_R_INFO_PRIOR,
  SGP_R_LOGDET_KUU, SGP_R_LOGDET_LAMBDA, SGP_R_COUNT) = range(9)
@@ -29,7 +31,7 @@ EXPORTS = [
     "sgp_get_kuu_chol", "sgp_get_wishart_invscale", "sgp_w_stats", "sgp_predict", "sgp_theta_objective", "sgp_carry_posterior", "sgp_set_posterior",
     "sgp_kernelmatrix", "sgp_potrf", "sgp_potri", "sgp_get_timestamps", "sgp_get_phase_totals", "sgp_time_kernel", "sgp_get_chain_trace", "sgp_set_allreduce", "sgp_use_rccl", "sgp_measure_sclk_mhz",
     "sgp_train_begin", "sgp_train_step", "sgp_train_end", "sgp_get_step_trace", "sgp_measure_clocks", "sgp_overlap_plan",
-    "sgp_get_sweep_trace", "sgp_train_likelihood", "sgp_train_get_gamma", "sgp_wait",
+    "sgp_get_sweep_trace", "sgp_train_likelihood", "sgp_train_get_gamma", "sgp_wait", "sgp_set_targets", "sgp_sweep_kind",
 ]
 SGP_TIME_GROUP0 = 100
 SGP_TIME_QUADFORM = 120
@@ -130,6 +132,8 @@ def load(build_if_missing: bool = True, variant=None):
     lib.sgp_train_likelihood.argtypes = [vp, C.c_int32, C.c_double, C.c_double]
     lib.sgp_train_get_gamma.argtypes = [vp, dp]
     lib.sgp_wait.argtypes = [vp]
+    lib.sgp_set_targets.argtypes = [vp, dp, dp]
+    lib.sgp_sweep_kind.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name != "sgp_last_error":

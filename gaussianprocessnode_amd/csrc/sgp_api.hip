@@ -95,6 +95,7 @@ struct SweepPlan {
     bool events = false;           // the streams meet through events as well (all-reduce hook, caller's stream)
     bool join_word = false;        // F2 waits on dJoin[WORD_JOIN] inside k_gemm32 instead of on evSide
     bool kuu_interleaved = false;  // the K_uu chain's steps go out alternately with the Lambda chain's (enqueue_finish1)
+    bool resident = false;         // the statistics are resident (sweep_resident): an overlapped sweep's column layout, nothing to wait for
 };
 
 struct sgp_handle {
@@ -182,6 +183,16 @@ struct sgp_handle {
     void* allreduce_ctx = nullptr;
     void* rccl_comm = nullptr;
     double ryy_data[MAXO * MAXO] = {0};   // sum omega y y' of the current data (without the output-covariance term)
+    // SGP_FLAG_REUSE_STATS: the resident statistics -- K_uf, the Psi2 / B partials and the assembled statistics (dKuf, dBpart,
+    // dSlabs, dStats), the K_uu chain's outputs (dKuu, dWk, dKinv, dSaccK, the log-det in dScratch + POTRF_LOGDET) -- of the last
+    // full sweep: valid until a path that writes them or changes what they depend on (inputs, inducing points, kernel values)
+    // runs; `checked`: that sweep was seen to end with K_uu factored and no bounded wait given up; `targets`: new targets since
+    // (B and the data scalars are to be formed again)
+    struct ResidentStats {
+        bool valid = false, checked = false, targets = false;
+        double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};
+    } rec;
+    int32_t last_kind = SGP_SWEEP_FULL;   // what the last completed sgp_sweep did (sgp_sweep_kind)
     std::string err;
 };
 
@@ -626,6 +637,7 @@ extern "C" int sgp_set_inducing(sgp_handle* h, const double* Xu) {
     if (!h || !Xu) return fail(h, SGP_ERR_ARG, "sgp_set_inducing: null argument");
     if (int qrc = quiesce(h)) return qrc;
     h->data_gen++;
+    h->rec.valid = false;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpy(h->dXu, Xu, sizeof(double) * h->M * h->D, hipMemcpyHostToDevice));
     h->have_inducing = true;
@@ -784,17 +796,13 @@ static int set_point_count(sgp_handle* h, int64_t n) {
     return 0;
 }
 
-extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean, const double* y_var,
-                            const double* pt_weight, int64_t n, double n_nodes) {
-    if (!h || !X || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_set_data: null argument");
-    if (int qrc = quiesce(h)) return qrc;
-    h->data_gen++;
-    if (n < 0 || n > h->n_max) return fail(h, SGP_ERR_ARG, "sgp_set_data: n outside [0, n_max]");
-    if (y_var && h->dout != 1) return fail(h, SGP_ERR_ARG, "sgp_set_data: y_var is only defined for d_out = 1");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
+// The targets' share of the data, on the host, for sgp_set_data and sgp_set_targets alike: the weighted targets Yw = omega .* y
+// (n x d_out), the data scalars (SGP_S_YY, SGP_S_W, SGP_S_N, then Ryy) and ryy_data.
+static void form_targets(sgp_handle* h, const double* y_mean, const double* y_var, const double* pt_weight, int64_t n,
+                         double n_nodes, std::vector<double>& yw, std::vector<double>& scal) {
     const int dout = h->dout;
-    std::vector<double> yw((size_t)std::max<int64_t>(n, 1) * dout);
-    std::vector<double> scal(SGP_S_COUNT + (size_t)dout * dout, 0.0);
+    yw.assign((size_t)std::max<int64_t>(n, 1) * dout, 0.0);
+    scal.assign(SGP_S_COUNT + (size_t)dout * dout, 0.0);
     double s_w = 0.0;
     for (int64_t i = 0; i < n; ++i) s_w += pt_weight ? pt_weight[i] : 1.0;
     for (int o = 0; o < dout; ++o)
@@ -814,19 +822,17 @@ extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean
     scal[SGP_S_W] = s_w;
     scal[SGP_S_N] = (n_nodes > 0) ? n_nodes : (double)n;
     for (int i = 0; i < dout * dout; ++i) h->ryy_data[i] = scal[SGP_S_COUNT + i];
-    const size_t need = (size_t)n * ((size_t)h->D + 2 * (size_t)dout + 2) + scal.size();
+}
+
+// host -> device copies of a setter: through the pinned staging block when `need` doubles fit (asynchronous copies, ONE
+// synchronisation: the six blocking copies from pageable memory were ~70 us per minibatch of the host-paced streaming loop, a
+// quarter of the sweep behind them), else one blocking copy per piece.  Empty pieces are skipped.
+struct HostPiece { double* dst; const double* src; size_t count; };
+static int upload_pieces(sgp_handle* h, const HostPiece* pieces, int npieces, size_t need) {
     if (h->hStage && need <= h->stage_doubles) {
-        // a minibatch: everything through the pinned staging block, asynchronous copies, ONE synchronisation (the six blocking
-        // copies from pageable memory were ~70 us per minibatch of the host-paced streaming loop, a quarter of the sweep behind them)
         double* st = h->hStage;
-        struct Piece { double* dst; const double* src; size_t count; };
-        const Piece pieces[] = {{h->dX, X, (size_t)n * h->D},
-                                {h->dYw, yw.data(), (size_t)n * dout},
-                                {h->dY, y_mean, (size_t)n * dout},
-                                {h->dYv, y_var, y_var ? (size_t)n : 0},
-                                {h->dOmega, pt_weight, pt_weight ? (size_t)n : 0},
-                                {h->dDataScal, scal.data(), scal.size()}};
-        for (const Piece& pc : pieces) {
+        for (int i = 0; i < npieces; ++i) {
+            const HostPiece& pc = pieces[i];
             if (!pc.count) continue;
             memcpy(st, pc.src, sizeof(double) * pc.count);
             HIPCHK(h, hipMemcpyAsync(pc.dst, st, sizeof(double) * pc.count, hipMemcpyHostToDevice, h->own));
@@ -834,15 +840,32 @@ extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean
         }
         HIPCHK(h, hipStreamSynchronize(h->own));
     } else {
-        if (n > 0) {
-            HIPCHK(h, hipMemcpy(h->dX, X, sizeof(double) * n * h->D, hipMemcpyHostToDevice));
-            HIPCHK(h, hipMemcpy(h->dYw, yw.data(), sizeof(double) * n * dout, hipMemcpyHostToDevice));
-            HIPCHK(h, hipMemcpy(h->dY, y_mean, sizeof(double) * n * dout, hipMemcpyHostToDevice));
-            if (y_var) HIPCHK(h, hipMemcpy(h->dYv, y_var, sizeof(double) * n, hipMemcpyHostToDevice));
-            if (pt_weight) HIPCHK(h, hipMemcpy(h->dOmega, pt_weight, sizeof(double) * n, hipMemcpyHostToDevice));
-        }
-        HIPCHK(h, hipMemcpy(h->dDataScal, scal.data(), sizeof(double) * scal.size(), hipMemcpyHostToDevice));
+        for (int i = 0; i < npieces; ++i)
+            if (pieces[i].count)
+                HIPCHK(h, hipMemcpy(pieces[i].dst, pieces[i].src, sizeof(double) * pieces[i].count, hipMemcpyHostToDevice));
     }
+    return 0;
+}
+
+extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean, const double* y_var,
+                            const double* pt_weight, int64_t n, double n_nodes) {
+    if (!h || !X || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_set_data: null argument");
+    if (int qrc = quiesce(h)) return qrc;
+    h->data_gen++;
+    h->rec.valid = false;
+    if (n < 0 || n > h->n_max) return fail(h, SGP_ERR_ARG, "sgp_set_data: n outside [0, n_max]");
+    if (y_var && h->dout != 1) return fail(h, SGP_ERR_ARG, "sgp_set_data: y_var is only defined for d_out = 1");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int dout = h->dout;
+    std::vector<double> yw, scal;
+    form_targets(h, y_mean, y_var, pt_weight, n, n_nodes, yw, scal);
+    const HostPiece pieces[] = {{h->dX, X, (size_t)n * h->D},
+                                {h->dYw, yw.data(), (size_t)n * dout},
+                                {h->dY, y_mean, (size_t)n * dout},
+                                {h->dYv, y_var, y_var ? (size_t)n : 0},
+                                {h->dOmega, pt_weight, pt_weight ? (size_t)n : 0},
+                                {h->dDataScal, scal.data(), scal.size()}};
+    if (int urc = upload_pieces(h, pieces, 6, (size_t)n * ((size_t)h->D + 2 * (size_t)dout + 2) + scal.size())) return urc;
     h->n = n;
     h->n_nodes = scal[SGP_S_N];
     h->has_omega = pt_weight != nullptr;
@@ -850,6 +873,34 @@ extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean
     h->have_data = true;
     if (int rc = set_point_count(h, n)) return rc;
     h->swept = h->swept_local = false;
+    return 0;
+}
+
+// new targets at the resident inputs: what a VMP iteration of a classification model changes (q(f)); the weights and n_nodes are
+// those of sgp_set_data, the weights are read back from the device
+extern "C" int sgp_set_targets(sgp_handle* h, const double* y_mean, const double* y_var) {
+    if (!h || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_set_targets: null argument");
+    if (int qrc = quiesce(h)) return qrc;
+    if (!h->have_data) return fail(h, SGP_ERR_ARG, "sgp_set_targets: call sgp_set_data first");
+    if (y_var && h->dout != 1) return fail(h, SGP_ERR_ARG, "sgp_set_targets: y_var is only defined for d_out = 1");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int64_t n = h->n;
+    const int dout = h->dout;
+    std::vector<double> omega;
+    if (h->has_omega && n > 0) {
+        omega.resize((size_t)n);
+        HIPCHK(h, hipMemcpy(omega.data(), h->dOmega, sizeof(double) * n, hipMemcpyDeviceToHost));
+    }
+    std::vector<double> yw, scal;
+    form_targets(h, y_mean, y_var, h->has_omega ? omega.data() : nullptr, n, h->n_nodes, yw, scal);
+    const HostPiece pieces[] = {{h->dYw, yw.data(), (size_t)n * dout},
+                                {h->dY, y_mean, (size_t)n * dout},
+                                {h->dYv, y_var, y_var ? (size_t)n : 0},
+                                {h->dDataScal, scal.data(), scal.size()}};
+    if (int urc = upload_pieces(h, pieces, 4, (size_t)n * (2 * (size_t)dout + 1) + scal.size())) return urc;
+    h->has_yv = y_var != nullptr;
+    h->data_gen++;                             // (the statistics no longer belong to the data: sgp_theta_objective re-forms them)
+    h->rec.targets = true;
     return 0;
 }
 
@@ -867,6 +918,7 @@ extern "C" int sgp_set_output_cov_sum(sgp_handle* h, const double* S) {
         double syy = h->ryy_data[0] + S[0];
         HIPCHK(h, hipMemcpy(h->dDataScal + SGP_S_YY, &syy, sizeof(double), hipMemcpyHostToDevice));
     }
+    h->rec.targets = true;                     // (the data scalars of the statistics are to be formed again)
     return 0;
 }
 
@@ -984,6 +1036,7 @@ extern "C" int sgp_bind_stats(sgp_handle* h, void* stats_dev) {
     if (!h) return SGP_ERR_ARG;
     if (int qrc = quiesce(h)) return qrc;
     h->dStats = stats_dev ? static_cast<double*>(stats_dev) : h->dStatsOwn;
+    h->rec.valid = false;                      // (the buffer now bound holds no statistics of this handle's)
     return 0;
 }
 
@@ -1046,10 +1099,11 @@ static void launch_gram(sgp_handle* h, hipStream_t s, bool opens_sweep) {
 // The scaled inducing inputs and the parameter mirror of the main stream (dXus, dParams) only change when a setter ran: a sweep
 // at unchanged parameters (VMP iterations at fixed theta) starts with the Gram kernel.  `always`: a sweep without data has no
 // Gram kernel to open its phase stamps, so k_prep_xu, which opens them too, runs regardless.
-static void prep_main(sgp_handle* h, hipStream_t s, bool always) {
+// `info_reset`: a status word to clear as well (a sweep over resident statistics: the Lambda chain's, which k_assemble clears otherwise).
+static void prep_main(sgp_handle* h, hipStream_t s, bool always, int* info_reset = nullptr) {
     if (!always && h->main_prep_gen == h->params_gen) return;
     hipLaunchKernelGGL(k_prep_xu, dim3((h->Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXus, h->params_src,
-                       h->dParams, (int*)nullptr, h->M, h->Mp, h->D, h->dStamps, (int)SGP_T_COUNT, (int)SGP_T_SWEEP,
+                       h->dParams, info_reset, h->M, h->Mp, h->D, h->dStamps, (int)SGP_T_COUNT, (int)SGP_T_SWEEP,
                        (const long long*)nullptr, 0LL, (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
     h->main_prep_gen = h->params_gen;
 }
@@ -1149,9 +1203,9 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s, const SweepPlan& p) {
         for (int g = 0; g < h->ngroups; ++g) {
             for (int c = h->grp[g].c0; c < h->grp[g].c1; ++c) {
                 form.form_step[c] = (unsigned char)h->grp[g].form_step;
-                form.col_group[c] = (h->grp[g].masked && !p.pack) ? (unsigned char)g : (unsigned char)0xff;
+                form.col_group[c] = (h->grp[g].masked && !p.pack && !p.resident) ? (unsigned char)g : (unsigned char)0xff;
             }
-            if (h->grp[g].masked && p.pack) { step_wait[h->grp[g].form_step] = h->evGroup[g]; any_wait = true; }
+            if (h->grp[g].masked && p.pack && !p.resident) { step_wait[h->grp[g].form_step] = h->evGroup[g]; any_wait = true; }
         }
     }
     double* uvt0 = h->dUvWork + 2 * (size_t)Qp;     // t = W' P xi, advanced block by block during the factorisation
@@ -1334,7 +1388,12 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool i
     return 0;
 }
 
-extern "C" int sgp_sweep_local(sgp_handle* h, void* stream) { return sweep_local_impl(h, stream, false, false, false); }
+// (a caller that runs the halves itself may change the statistics between them: what they hold is not the library's to reuse)
+extern "C" int sgp_sweep_local(sgp_handle* h, void* stream) {
+    const int rc = sweep_local_impl(h, stream, false, false, false);
+    if (h) h->rec.valid = false;
+    return rc;
+}
 
 extern "C" int sgp_sweep_finish(sgp_handle* h, void* stream) {
     if (!h) return SGP_ERR_ARG;
@@ -1379,8 +1438,100 @@ static int exchange_stats(sgp_handle* h, hipStream_t s, int tile0, int ntile, bo
 }
 static int exchange_stats(sgp_handle* h, hipStream_t s) { return exchange_stats(h, s, 0, h->ntiles, true); }
 
+// ---- SGP_FLAG_REUSE_STATS: sweeps over the resident statistics (see sgp_sweep_kind in include/sgp_hip.h) ----
+static int sync_all(sgp_handle* h);
+// what the host state allows the next sgp_sweep to skip
+static int32_t planned_kind(const sgp_handle* h) {
+    if (!(h->cfg.flags & SGP_FLAG_REUSE_STATS) || !h->rec.valid || h->training) return SGP_SWEEP_FULL;
+    if (h->dStats != h->dStatsOwn && !h->allreduce) return SGP_SWEEP_FULL;
+    // kernel values compared as sgp_theta_objective's freshness test does: set_kernel at the same theta keeps the statistics
+    const Params& P = *h->hParams;
+    if (P.sigma2 != h->rec.sigma2 || P.jitter != h->rec.jitter) return SGP_SWEEP_FULL;
+    for (int d = 0; d < h->D; ++d)
+        if (P.inv_ell[d] != h->rec.inv_ell[d]) return SGP_SWEEP_FULL;
+    return h->rec.targets ? SGP_SWEEP_TARGETS : SGP_SWEEP_REUSED;
+}
+// ... and what it will do: the full sweep that formed the statistics must have ended with K_uu factored and without a bounded
+// wait giving up (the K_uu chain and the masked statistics stream meet the sweep through such waits) -- looked at once, before the
+// first sweep that relies on it, after waiting for that sweep
+static int next_kind(sgp_handle* h, int32_t* kind) {
+    *kind = planned_kind(h);
+    if (*kind == SGP_SWEEP_FULL || h->rec.checked) return 0;
+    if (int rc = sync_all(h)) return rc;
+    int info[4];
+    HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
+    if (info[0] != 0 || info[3] != 0) {
+        h->rec.valid = false;
+        *kind = SGP_SWEEP_FULL;
+    } else
+        h->rec.checked = true;
+    return 0;
+}
+
+// A sweep over the resident statistics: k_prep_xu (the new W and prior into dParams; it opens the phase stamps and clears the
+// Lambda chain's status word), with new targets B and the data scalars from the resident K_uf (k_bpart_kuf, k_assemble_b; with
+// an all-reduce hook ONE reduce of the exchange buffer's tail), then phase 2 in plain stream order.  No K_uu chain, no join.
+static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    SweepPlan p;
+    p.stream = stream ? static_cast<hipStream_t>(stream) : h->own;
+    p.events = h->allreduce != nullptr || p.stream != h->own;
+    // The Lambda chain forms its tile columns at the steps a full sweep of this call would (sgp_sweep's overlapped order: a column
+    // formed at a later step has collected its rank-64 updates first, i.e. in another order), so that the results are bitwise
+    // that sweep's -- every column in stream order, nothing waited for.
+    p.overlapped = h->overlap && !stream && h->n > 0 && !h->training;
+    p.pack = h->allreduce != nullptr;
+    p.resident = true;
+    hipStream_t s = p.stream;
+    if (h->sync_reported) {
+        HIPCHK(h, hipMemset(h->dInfo + 3, 0, sizeof(int)));
+        h->sync_reported = false;
+    }
+    h->in_flight = true;
+    h->plan = p;
+    h->plan.overlapped = false;                              // (as after sgp_sweep_finish: a repeated finish runs F1 and F2 alone)
+    prep_main(h, s, true, h->dInfo + 1);
+    if (targets) {
+        const int Mp = h->Mp, T = h->T;
+        const bool pack = h->allreduce != nullptr;
+        if (h->n > 0)
+            hipLaunchKernelGGL(k_bpart_kuf, dim3(h->nblk, (Mp + BPK_ROWS - 1) / BPK_ROWS), dim3(64), 0, s, (const double*)h->dKuf,
+                               (const double*)h->dYw, h->dBpart, Mp, h->n, h->dout);
+        double* B = pack ? h->dPack + (size_t)h->ntiles * TB * TB : h->dStats + (size_t)Mp * Mp;
+        hipLaunchKernelGGL(k_assemble_b, dim3(T * h->dout), dim3(256), 0, s, (const double*)h->dBpart, (const double*)h->dDataScal, B,
+                           Mp, T, h->n > 0 ? h->nblk : 0, h->dout, SGP_S_COUNT + h->dout * h->dout,
+                           h->dStamps + STAMP_STRIDE * SGP_T_LOCAL, h->dBred);
+        HIPCHK(h, hipGetLastError());
+        if (pack)
+            if (int xrc = exchange_stats(h, s, h->ntiles, 0, true)) return xrc;
+    }
+    HIPCHK(h, hipGetLastError());
+    h->stats_dirty = false;
+    h->swept_params = *h->hParams;
+    h->swept_data_gen = h->data_gen;
+    h->swept_local = true;
+    enqueue_finish1(h, s, p);
+    HIPCHK(h, hipGetLastError());
+    ++h->done_epoch;                                         // what this sweep's k_scalars writes when it is through
+    enqueue_finish2(h, s, false);
+    HIPCHK(h, hipGetLastError());
+    h->mirror_epoch = mirror_for(h) ? h->done_epoch : -1;
+    if (p.events) HIPCHK(h, hipEventRecord(h->evDone, s));
+    h->swept = true;
+    h->last_stream = s;
+    h->rec.targets = false;
+    h->last_kind = targets ? SGP_SWEEP_TARGETS : SGP_SWEEP_REUSED;
+    return 0;
+}
+
 extern "C" int sgp_sweep(sgp_handle* h, void* stream) {
     if (!h) return SGP_ERR_ARG;
+    if (h->cfg.flags & SGP_FLAG_REUSE_STATS) {
+        if (int rc = check_ready(h)) return rc;
+        int32_t kind = SGP_SWEEP_FULL;
+        if (int rc = next_kind(h, &kind)) return rc;
+        if (kind != SGP_SWEEP_FULL) return sweep_resident(h, stream, kind == SGP_SWEEP_TARGETS);
+    }
     // single GPU, the library's own streams, a problem that qualifies: statistics and Lambda chain overlapped
     // (with an all-reduce hook as well: one reduce per statistics group, see enqueue_stats_overlapped)
     const bool overlapped = h->overlap && !stream && h->n > 0 && !h->training;
@@ -1390,7 +1541,29 @@ extern "C" int sgp_sweep(sgp_handle* h, void* stream) {
         rc = exchange_stats(h, stream ? static_cast<hipStream_t>(stream) : h->own);
         if (rc) return rc;
     }
-    return sgp_sweep_finish(h, stream);
+    rc = sgp_sweep_finish(h, stream);
+    if (rc) return rc;
+    h->last_kind = SGP_SWEEP_FULL;
+    if ((h->cfg.flags & SGP_FLAG_REUSE_STATS) && !h->training) {   // this sweep formed the statistics of the resident inputs
+        h->rec.valid = true;
+        h->rec.checked = h->rec.targets = false;
+        h->rec.sigma2 = h->hParams->sigma2;
+        h->rec.jitter = h->hParams->jitter;
+        for (int d = 0; d < MAXD; ++d) h->rec.inv_ell[d] = h->hParams->inv_ell[d];
+    }
+    return 0;
+}
+
+extern "C" int sgp_sweep_kind(const sgp_handle* hc, int32_t* next, int32_t* last) {
+    if (!hc) return SGP_ERR_ARG;
+    sgp_handle* h = const_cast<sgp_handle*>(hc);      // (the one-time status check of the resident statistics is kept on the handle)
+    if (next) {
+        int32_t kind = SGP_SWEEP_FULL;
+        if (int rc = next_kind(h, &kind)) return rc;
+        *next = kind;
+    }
+    if (last) *last = h->last_kind;
+    return 0;
 }
 
 static int ensure_pack(sgp_handle* h) {
@@ -1407,6 +1580,7 @@ extern "C" int sgp_set_allreduce(sgp_handle* h, sgp_allreduce_fn fn, void* ctx) 
     if (int prc = ensure_pack(h)) return prc;
     h->allreduce = fn;
     h->allreduce_ctx = ctx;
+    h->rec.valid = false;                      // (the resident statistics are this rank's, or the sum over other ranks)
     if (h->n > 0) plan_overlap(h, h->n);         // (a data-sharded sweep pays one collective per statistics group: one cut)
     return 0;
 }
@@ -1427,6 +1601,7 @@ extern "C" int sgp_use_rccl(sgp_handle* h, void* nccl_comm) {
     h->rccl_comm = nccl_comm;
     h->allreduce = rccl_hook;
     h->allreduce_ctx = h;
+    h->rec.valid = false;
     if (h->n > 0) plan_overlap(h, h->n);
     return 0;
 }
@@ -1717,6 +1892,7 @@ extern "C" int sgp_time_kernel(sgp_handle* h, int32_t which, int32_t iters, void
     if (!h || !avg_us || iters < 1) return fail(h, SGP_ERR_ARG, "sgp_time_kernel: bad argument");
     if (!h->swept_local || h->n == 0) return fail(h, SGP_ERR_ARG, "sgp_time_kernel: run a sweep on non-empty data first");
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->rec.valid = false;                      // (the timed launches rewrite K_uf, the partials and the slabs)
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
     // which = SGP_TIME_GROUP0 + g: the SYRK launch of statistics group g of the overlapped sweep, on the stream (and CUs) it runs on
     const StatGroup* G = nullptr;
@@ -1999,6 +2175,7 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
         if (!grad) return 0;
     } else {
         h->stats_dirty = true;                   // the statistics now belong to the NEW theta, not to q(v)'s sweep
+        h->rec.valid = false;
         rc = theta_objective_eval(h, s, value);
         if (rc || !grad) { h->swept_local = true; return rc; }
     }
@@ -2026,6 +2203,7 @@ extern "C" int sgp_train_begin(sgp_handle* h, const double* X, const double* y, 
     // (a caller-bound statistics buffer is fine here: inside sgp_train_step nobody but the library -- through the all-reduce hook,
     // if one is installed -- touches the statistics between the two halves of the sweep)
     if (!h->have_inducing) return fail(h, SGP_ERR_ARG, "sgp_train_begin: call sgp_set_inducing first");
+    h->rec.valid = false;                      // (every step rewrites the statistics of its window)
     if (n_total < 1) return fail(h, SGP_ERR_ARG, "sgp_train_begin: empty training set");
     if (n_ell != 1 && n_ell != h->D) return fail(h, SGP_ERR_ARG, "sgp_train_begin: n_ell must be 1 or D");
     if (!(jitter >= 0.0) || !(eta > 0.0)) return fail(h, SGP_ERR_ARG, "sgp_train_begin: jitter >= 0 and eta > 0 required");
@@ -2196,6 +2374,7 @@ extern "C" int sgp_train_end(sgp_handle* h, double* theta_raw, int64_t* counts) 
     h->train_probit = false;
     h->params_gen++;
     h->stats_dirty = true;                                     // the resident statistics belong to the previous theta
+    h->rec.valid = false;
     h->swept_local = false;
     if (theta_raw) for (int i = 0; i <= h->n_ell; ++i) theta_raw[i] = st.theta[i];
     if (counts) { counts[0] = (int64_t)st.steps; counts[1] = (int64_t)st.rejected; }

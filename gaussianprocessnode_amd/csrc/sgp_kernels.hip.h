@@ -147,7 +147,8 @@ __device__ __forceinline__ void stamp_fold_finish(StampFold f, int64_t* stamps, 
     long long b = f.b, e = f.e;
     if (slot == SWEEP || slot == FINISH2) e = now;        // this kernel is the end of both (its own exit atomic may be in flight)
     const long long local_end = __shfl(e, LOCAL), finish1_begin = __shfl(b, FINISH1);
-    if (slot == GAP) { b = local_end; e = (finish1_begin != UNSET) ? finish1_begin : local_end; }
+    // (a sweep over resident statistics has no LOCAL phase to close -- its end was never stamped: no gap either)
+    if (slot == GAP) { b = local_end > 0 ? local_end : UNSET; e = (finish1_begin != UNSET) ? finish1_begin : local_end; }
     if (lane < NSLOTS) {
         int64_t* last = totals + NSLOTS + 1;                  // this sweep's (begin, end) pairs, for sgp_get_timestamps
         last[2 * slot] = b;
@@ -296,6 +297,31 @@ __global__ void __launch_bounds__(256) k_gram_uu(const double* __restrict__ Xus,
 }
 
 // ------------------------------------------------------------------------------------------------
+// The summation order of a B partial -- one row of K_uf against one output's weighted targets over a 64-point block: a 4-term
+// fma chain per group of 4 consecutive points (bpart_group), the 16 groups added in order to a sum that starts at 0.0
+// (bpart_sum; `group(g, part)` delivers group g's partials of R rows at once).  k_gram_uf and k_bpart_kuf both go through
+// these two, so B formed from the resident K_uf is bitwise the full sweep's.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double bpart_group(const double (&k)[4], const double (&y)[4]) {
+    double s = 0.0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) s = fma(k[b], y[b], s);
+    return s;
+}
+template <int R, int UNROLL = 16, class Group>
+__device__ __forceinline__ void bpart_sum(double (&s)[R], Group group) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) s[r] = 0.0;
+#pragma unroll UNROLL
+    for (int g = 0; g < 16; ++g) {
+        double part[R];
+        group(g, part);
+#pragma unroll
+        for (int r = 0; r < R; ++r) s[r] += part[r];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K_uf tile 64 (m) x 64 (n) per block; each thread a 4 x 4 micro-tile.  Also the per-block partial of
 // B = K_uf * Yw  (Yw = omega .* y, n x d_out), reduced deterministically later by k_assemble.
 //   X   : D x N AoS (one point per column), unscaled;  Yw : N x d_out column-major
@@ -367,25 +393,66 @@ __global__ void __launch_bounds__(256) k_gram_uf(const double* __restrict__ Xus,
             *reinterpret_cast<double2*>(dst + 2) = make_double2(acc[2][b], acc[3][b]);
         }
     }
-    // partial B for this block's 64 points: reduce the 16 n-groups through LDS in a fixed order
+    // partial B for this block's 64 points: reduce the 16 n-groups through LDS in a fixed order (bpart_group / bpart_sum)
     for (int o = 0; o < d_out; ++o) {
         __syncthreads();
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            double s = 0.0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) s = fma(acc[a][b], ys[o * TB + tn * 4 + b], s);
-            red[tn * TB + tm * 4 + a] = s;
+            const double k[4] = {acc[a][0], acc[a][1], acc[a][2], acc[a][3]};
+            const double y[4] = {ys[o * TB + tn * 4], ys[o * TB + tn * 4 + 1], ys[o * TB + tn * 4 + 2], ys[o * TB + tn * 4 + 3]};
+            red[tn * TB + tm * 4 + a] = bpart_group(k, y);
         }
         __syncthreads();
         if (threadIdx.x < TB) {
-            double s = 0.0;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) s += red[g * TB + threadIdx.x];
-            bpart[((size_t)blockIdx.x * d_out + o) * Mp + I + threadIdx.x] = s;
+            double s[1];
+            bpart_sum(s, [&](int g, double* part) { part[0] = red[g * TB + threadIdx.x]; });
+            bpart[((size_t)blockIdx.x * d_out + o) * Mp + I + threadIdx.x] = s[0];
         }
     }
     stamp_exit(stamps);
+}
+
+// ------------------------------------------------------------------------------------------------
+// B partials from the RESIDENT K_uf (a sweep after sgp_set_targets: same inputs and kernel, new targets), in k_gram_uf's
+// partition and order, so that the B they sum to is bitwise the one a full sweep forms: bpart[blk][o][m] over the 64 points
+// of block blk.  A GEMV that streams K_uf once (8 n Mp bytes: 41 MB at N = 10 000, M = 512): one wave per (point block, 128
+// rows), lane = two adjacent rows, so every load is a 16-byte piece of a 1 KB run down one K_uf column; no LDS (nothing is
+// shared between lanes), the targets are wave-uniform, K_uf is read with non-temporal loads (touched once per sweep).
+// ------------------------------------------------------------------------------------------------
+constexpr int BPK_ROWS = 128;                 // rows of K_uf per wave
+constexpr int BPK_UNROLL = 4;                 // point groups (16 loads of 16 bytes) per unrolled step: 4 waves per SIMD, no spills
+typedef double d2v __attribute__((ext_vector_type(2)));
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) k_bpart_kuf(const double* __restrict__ Kuf, const double* __restrict__ Yw,
+                                                  double* __restrict__ bpart, int Mp, int64_t N, int d_out) {
+    const int m = blockIdx.y * BPK_ROWS + 2 * (int)threadIdx.x;
+    if (m >= Mp) return;                                      // (Mp is a multiple of 64: m + 1 < Mp as well)
+    const int64_t n0 = (int64_t)blockIdx.x * TB;
+    const bool whole = n0 + TB <= N;                          // (the last block: points past N count as zeros, as in k_gram_uf)
+    const d2v* col = reinterpret_cast<const d2v*>(Kuf + (size_t)n0 * Mp + m);
+    const size_t cstride = (size_t)Mp / 2;                    // one K_uf column, in d2v
+    double s[2 * MAXO];                                       // [o][row]
+    bpart_sum<2 * MAXO, BPK_UNROLL>(s, [&](int g, double* part) {
+        d2v k[4];
+        double y[MAXO][4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int64_t n = n0 + 4 * g + b;
+            const bool in = whole || n < N;
+            k[b] = in ? __builtin_nontemporal_load(col + (size_t)(4 * g + b) * cstride) : (d2v){0.0, 0.0};
+#pragma unroll
+            for (int o = 0; o < MAXO; ++o) y[o][b] = (o < d_out && in) ? Yw[(size_t)o * N + n] : 0.0;
+        }
+        const double k0[4] = {k[0].x, k[1].x, k[2].x, k[3].x}, k1[4] = {k[0].y, k[1].y, k[2].y, k[3].y};
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o) {
+            part[2 * o] = bpart_group(k0, y[o]);
+            part[2 * o + 1] = bpart_group(k1, y[o]);
+        }
+    });
+#pragma unroll
+    for (int o = 0; o < MAXO; ++o)
+        if (o < d_out)
+            *reinterpret_cast<d2v*>(bpart + ((size_t)blockIdx.x * d_out + o) * Mp + m) = (d2v){s[2 * o], s[2 * o + 1]};
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -951,6 +1018,18 @@ __global__ void __launch_bounds__(256) k_assemble(const double* __restrict__ sla
             for (int e = tid; e < nscal; e += 256) B[(size_t)Mp * d_out + e] = data_scalars[e];
     }
     if (info_reset && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *info_reset = 0;
+    stamp_exit(stamps);
+}
+
+// B and the data scalars alone, for a sweep whose Psi2 is resident (new targets): k_assemble's extra grid row (sum_b_pairs, then
+// the scalars) as a launch of its own -- grid T * d_out, one (row block, output) pair per workgroup.  `B` points at B in the
+// statistics buffer or in the exchange buffer's tail; Psi2 is not touched.
+__global__ void __launch_bounds__(256) k_assemble_b(const double* __restrict__ bpart, const double* __restrict__ data_scalars,
+                                                    double* __restrict__ B, int Mp, int T, int nblk, int d_out, int nscal,
+                                                    int64_t* stamps, double* __restrict__ bscratch) {
+    sum_b_pairs(bpart, B, bscratch, Mp, T, nblk, d_out, blockIdx.x, gridDim.x);
+    if (blockIdx.x == 0)
+        for (int e = threadIdx.x; e < nscal; e += 256) B[(size_t)Mp * d_out + e] = data_scalars[e];
     stamp_exit(stamps);
 }
 

@@ -51,20 +51,23 @@ class SGPDevice:
     """Owns the device buffers for (n_max points, M inducing points, D dims, d_out outputs)."""
 
     def __init__(self, n_max: int, m: int, d: int, d_out: int = 1, device: int = 0, use_graph: bool = False,
-                 keep_kuf: bool = False, persistent_chain: bool = False):
+                 keep_kuf: bool = False, persistent_chain: bool = False, reuse_stats: bool = False):
         # persistent_chain sets the reserved SGP_FLAG_PERSISTENT_CHAIN (a removed experiment, DESIGN.md section 8): the library
         # refuses it, so True raises SGPError; the keyword stays so that existing callers passing False keep working.
         # use_graph sets SGP_FLAG_GRAPH, which the library ignores (graph replay was removed, DESIGN.md "Launch mode"): kept for
         # existing callers, launches are eager either way
+        # reuse_stats sets SGP_FLAG_REUSE_STATS: `sweep` then skips the work the setters since the last sweep left valid
+        # (VMP iterations at fixed kernel and inputs; `sweep_kind` says what the next sweep does)
         self._lib = _lib.load()
         self._h = C.c_void_p()
         flags = ((_lib.SGP_FLAG_GRAPH if use_graph else 0) | (_lib.SGP_FLAG_KEEP_KUF if keep_kuf else 0)
-                 | (_lib.SGP_FLAG_PERSISTENT_CHAIN if persistent_chain else 0))
+                 | (_lib.SGP_FLAG_PERSISTENT_CHAIN if persistent_chain else 0) | (_lib.SGP_FLAG_REUSE_STATS if reuse_stats else 0))
         cfg = _lib.Config(n_max=int(n_max), m=int(m), d=int(d), d_out=int(d_out), device=int(device), flags=flags)
         check(self._lib.sgp_create(C.byref(cfg), C.byref(self._h)), None, "sgp_create", lib=self._lib)
         self.n_max, self.M, self.D, self.d_out, self.device = int(n_max), int(m), int(d), int(d_out), int(device)
         self.Q = self.M * self.d_out
         self.n = 0
+        self.reuse_stats = bool(reuse_stats)
         self._allreduce_cb = None
         _live.add(self)
 
@@ -115,6 +118,15 @@ class SGPDevice:
         self._check(self._lib.sgp_set_data(self._h, ptr(X), ptr(y_cm), ptr(yv), ptr(w), n,
                                      float(-1.0 if n_nodes is None else n_nodes)), "sgp_set_data")
         self.n = n
+
+    def set_targets(self, y_mean, y_var=None):
+        """New targets for the resident inputs (sgp_set_targets): X, weights and n_nodes stay those of the last `set_data`."""
+        y = np.asarray(y_mean, dtype=np.float64).reshape(-1, self.d_out)
+        if self.n and len(y) != self.n:
+            raise ValueError(f"set_targets: {len(y)} targets for {self.n} resident points")
+        y_cm = as_f64(y.T)
+        yv = None if y_var is None else as_f64(np.reshape(y_var, (len(y),)))
+        self._check(self._lib.sgp_set_targets(self._h, ptr(y_cm), ptr(yv)), "sgp_set_targets")
 
     def set_output_cov_sum(self, S):
         S = as_f64(np.reshape(S, (self.d_out, self.d_out)))
@@ -177,6 +189,13 @@ class SGPDevice:
 
     def sweep(self, stream: int = 0):
         self._check(self._lib.sgp_sweep(self._h, C.c_void_p(stream)), "sgp_sweep")
+
+    def sweep_kind(self):
+        """(next, last): what the next `sweep` will do and what the last one did -- SGP_SWEEP_FULL (0), SGP_SWEEP_TARGETS (1) or
+        SGP_SWEEP_REUSED (2) (sgp_sweep_kind; always FULL without reuse_stats)."""
+        nxt, last = C.c_int32(), C.c_int32()
+        self._check(self._lib.sgp_sweep_kind(self._h, C.byref(nxt), C.byref(last)), "sgp_sweep_kind")
+        return nxt.value, last.value
 
     def wait(self):
         """Returns when everything this handle has enqueued has finished (polled, then blocking: sgp_wait)."""

@@ -84,14 +84,18 @@ class HipEngine:
     """This rank's shard on its MI355X: local statistics and the replicated tail through the C ABI.  `use_graph` is accepted
     and ignored (see SGPDevice)."""
 
-    def __init__(self, n_max: int, m: int, d: int, d_out: int = 1, device: int = 0, use_graph: bool = False):
+    def __init__(self, n_max: int, m: int, d: int, d_out: int = 1, device: int = 0, use_graph: bool = False,
+                 reuse_stats: bool = False):
         import torch
         from .device import SGPDevice
         if not torch.cuda.is_available():
             raise RuntimeError("HipEngine needs a gfx950 GPU (the product path has no CPU fallback)")
         torch.cuda.set_device(device)
         self.torch = torch
-        self.dev = SGPDevice(n_max, m, d, d_out, device=device, use_graph=use_graph)
+        # (reuse_stats: SGPDevice's flag; the statistics tensor bound below is the library's to reuse only while the all-reduce
+        # hook -- install_allreduce -- fills it)
+        self.dev = SGPDevice(n_max, m, d, d_out, device=device, use_graph=use_graph, reuse_stats=reuse_stats)
+        self.reuse_stats = self.dev.reuse_stats
         self.stats = torch.zeros(stats_count(m, d_out), dtype=torch.float64, device=f"cuda:{device}")
         self.dev.bind_stats(self.stats.data_ptr())
         # One explicit (non-default) torch stream carries the sweep AND the collective: the C ABI treats a NULL stream as
@@ -251,6 +255,11 @@ class ShardedDevice:
         cut = lambda a: None if a is None else np.asarray(a)[lo:hi]
         nn = None if n_nodes is None else float(n_nodes) * (hi - lo) / max(n, 1)
         self.dev.set_data(X.reshape(n, -1)[lo:hi], cut(y_mean), cut(y_var), cut(weights), nn)
+        self._n = n
+
+    def set_targets(self, y_mean, y_var=None):
+        lo, hi = self._slice(self._n)
+        self.dev.set_targets(np.asarray(y_mean)[lo:hi], None if y_var is None else np.asarray(y_var)[lo:hi])
 
     def train_step(self, offset, n, learn=True, reset_prior=False):
         lo, hi = self._slice(n)

@@ -25,6 +25,7 @@ import numpy as np
 from .distributions import (MvNormalMeanCovariance, MvNormalMeanPrecision, MvNormalWeightedMeanPrecision, PointMass,
                             WishartFast)
 from .meta import MultiSGPMeta
+from .unisgp import load_batch
 
 
 class MultiSGP:
@@ -49,7 +50,7 @@ def _engine(meta: MultiSGPMeta, n_points: int, d_out: int):
         from .device import SGPDevice
         if eng is not None:
             eng.close()
-        eng = SGPDevice(max(n_points, 1), M, D, d_out, device=meta.device)
+        eng = SGPDevice(max(n_points, 1), M, D, d_out, device=meta.device, reuse_stats=True)
         eng.set_inducing(Xu)
         meta.engine = eng
     return eng
@@ -83,7 +84,7 @@ def sweep(meta: MultiSGPMeta, q_outs: Sequence, q_ins: Sequence, q_w, q_theta: P
     d_out = W.shape[0]
     eng = _engine(meta, len(wts), d_out)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    eng.set_data(pts, ys, None, wts, n_nodes=len(q_ins))
+    load_batch(eng, pts, ys, None, wts, n_nodes=len(q_ins))
     if cov_sum is not None:
         eng.set_output_cov_sum(cov_sum)
     eng.set_kernel(sigma2, ell, meta.jitter)
@@ -140,7 +141,7 @@ def rule_v(q_out, q_in, q_w, q_theta: PointMass, meta: MultiSGPMeta) -> MvNormal
     d_out = W.shape[0]
     eng = _engine(meta, len(wts), d_out)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    eng.set_data(pts, np.ones((len(wts), d_out)), None, wts, n_nodes=1)
+    load_batch(eng, pts, np.ones((len(wts), d_out)), None, wts, n_nodes=1)
     eng.set_kernel(sigma2, ell, meta.jitter)
     eng.sweep_local()
     Psi2, B, _ = eng.stats()

@@ -157,10 +157,14 @@ def vmp_classification(p, xtrain, ytrain, Xu, engine, *, iterations=30, prior_va
     engine.set_inducing(Xu)
     engine.set_kernel(float(p[0]), p[1:], jitter)
     engine.set_prior_isotropic(prior_var)
-    for _ in range(iterations):
+    reuse = getattr(engine, "reuse_stats", False)
+    for it in range(iterations):
         w = a / b
         mf, vf = probit_marginal(ytrain, engine.predict(xtrain, mu), 1.0 / w)
-        engine.set_data(xtrain, mf, vf)
+        if it > 0 and reuse:
+            engine.set_targets(mf, vf)         # x is fixed: only q(f) moves (the sweep then reuses K_uf, Psi2 and the K_uu chain)
+        else:
+            engine.set_data(xtrain, mf, vf)
         engine.set_noise([[w]])
         engine.sweep()
         sc = engine.scalars()

@@ -74,13 +74,29 @@ def _engine(meta: UniSGPMeta, n: int):
         from .device import SGPDevice
         if eng is not None:
             eng.close()
-        eng = SGPDevice(max(n, meta.N, 1), M, D, 1, device=meta.device, keep_kuf=True)
+        eng = SGPDevice(max(n, meta.N, 1), M, D, 1, device=meta.device, keep_kuf=True, reuse_stats=True)
         meta.engine = eng
         meta._batch.pop("inducing_set", None)
     if not meta._batch.get("inducing_set"):
         eng.set_inducing(meta.Xu)
         meta._batch["inducing_set"] = True
     return eng
+
+
+def load_batch(eng, X, y, y_var=None, weights=None, n_nodes=None):
+    """Put one VMP iteration's batch on a node mirror's engine.  Between the iterations of one `infer` call only the targets
+    move (q_out; the inputs do not): when X, the weights and n_nodes equal what is resident on an engine that reuses its
+    statistics (`SGPDevice(reuse_stats=True)`), only the targets go over (`set_targets`) and the next sweep keeps K_uf, Psi2
+    and the K_uu chain; otherwise -- and always for engines without `reuse_stats` -- `set_data`."""
+    res = getattr(eng, "_resident_inputs", None)
+    if (getattr(eng, "reuse_stats", False) and res is not None and res[2] == n_nodes and np.array_equal(res[0], X)
+            and (res[1] is None) == (weights is None) and (weights is None or np.array_equal(res[1], weights))):
+        eng.set_targets(y, y_var)
+        return
+    eng._resident_inputs = None
+    eng.set_data(X, y, y_var, weights, n_nodes=n_nodes)
+    eng._resident_inputs = (np.array(X, dtype=np.float64), None if weights is None else np.array(weights, dtype=np.float64),
+                            n_nodes)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -149,7 +165,7 @@ def prod(left, right: BufferUniSGP):
         wts = None
     eng = _engine(meta, len(y))
     sigma2, ell = meta.kernel(meta._batch["theta"])
-    eng.set_data(X, y, vy, wts, n_nodes=meta.N)
+    load_batch(eng, X, y, vy, wts, n_nodes=meta.N)
     eng.set_kernel(sigma2, ell, meta.jitter)
     eng.set_noise([[meta._batch["w"]]], meta._batch["E_logw"])
     prior = meta._prior

@@ -39,6 +39,10 @@ extern "C" {
 #define SGP_FLAG_GRAPH      4   /* replayed the launch sequences as captured hipGraphs, measured ~20 us per sweep slower than
                                  * eager launches at every size and removed (DESIGN.md "Launch mode"); kept as a no-op */
 #define SGP_FLAG_PERSISTENT_CHAIN 8   /* reserved (a removed experiment): sgp_create returns SGP_ERR_ARG */
+#define SGP_FLAG_REUSE_STATS 16  /* sgp_sweep does only the work the setters since the last completed sweep have invalidated: the
+                                 * statistics of the resident inputs at the resident kernel values -- K_uf, Psi2, B, the data scalars, K_uu,
+                                 * its factor, inverse factor and inverse -- are kept between sweeps (VMP iterations at fixed theta and
+                                 * inputs, see sgp_sweep_kind).  Without it every sgp_sweep is a full sweep. */
 
 typedef struct sgp_handle sgp_handle;
 
@@ -89,6 +93,13 @@ int sgp_set_inducing(sgp_handle* h, const double* Xu);
  * GPnode/MultiSGPnode.jl:11-35); n_nodes = number of factor nodes the n points belong to (n if no cubature). */
 int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean, const double* y_var,
                  const double* pt_weight, int64_t n, double n_nodes);
+/* sgp_set_targets: new targets for the RESIDENT inputs -- the :out messages of the next VMP iteration at the same x
+ * (experiments/GPT_classification.ipynb: q(f) moves, x does not).  n, X, pt_weight and n_nodes stay those of the last
+ * sgp_set_data; y_mean is n x d_out, y_var (may be NULL; d_out = 1 only) as in sgp_set_data, and the weighted targets and
+ * data scalars are formed by the same host code.  Resets the output-covariance sum.  SGP_ERR_ARG before a sgp_set_data.
+ * With SGP_FLAG_REUSE_STATS the next sgp_sweep forms only B and the data scalars (from the resident K_uf); without it, a full
+ * sweep. */
+int sgp_set_targets(sgp_handle* h, const double* y_mean, const double* y_var);
 /* sgp_set_output_cov_sum: MultiSGP with Gaussian (not PointMass) q_out: sum over the nodes of cov(q_out)
  * (d_out x d_out), the Sigma_y term of `Ry = Sigma_y + mu_y mu_y'` (GPnode/MultiSGPnode.jl:398-401,566).  Call after
  * sgp_set_data (which resets it to zero). */
@@ -117,6 +128,22 @@ int sgp_set_noise(sgp_handle* h, const double* W, double E_log_w);
 int sgp_sweep_local(sgp_handle* h, void* stream);
 int sgp_sweep_finish(sgp_handle* h, void* stream);
 int sgp_sweep(sgp_handle* h, void* stream);                 /* local + [all-reduce hook] + finish */
+/* What a sgp_sweep does on a handle created with SGP_FLAG_REUSE_STATS (both FULL, always, without the flag):
+ *   SGP_SWEEP_FULL     the whole sweep above: after sgp_set_data, sgp_set_inducing, a changed kernel value (sigma2, a lengthscale,
+ *                      the jitter), sgp_theta_objective at another theta, sgp_train_*, sgp_time_kernel, sgp_bind_stats,
+ *                      sgp_set_allreduce / sgp_use_rccl, a direct sgp_sweep_local, or a full sweep whose K_uu factorisation failed or
+ *                      whose stream hand-off gave up;
+ *   SGP_SWEEP_TARGETS  after sgp_set_targets or sgp_set_output_cov_sum: B and the data scalars from the resident K_uf (with an
+ *                      all-reduce hook: ONE call, of the exchange buffer's tail [B | scalars], count = Mp d_out + SGP_S_COUNT +
+ *                      d_out^2 on every rank), then phase 2;
+ *   SGP_SWEEP_REUSED   otherwise (sgp_set_noise, sgp_set_prior, sgp_carry_posterior, sgp_set_posterior, sgp_w_stats, sgp_predict):
+ *                      phase 2 alone over the resident statistics; no K_uu chain, no hook call.
+ * The results of TARGETS and REUSED sweeps are bitwise those of a full sweep.  sgp_sweep_local / sgp_sweep_finish keep their
+ * meaning (a full local phase, phase 2).
+ * sgp_sweep_kind: next = what the next sgp_sweep will do (it may wait, once, for the last full sweep to finish and checks its
+ * status), last = what the last completed sgp_sweep did.  Either pointer may be NULL. */
+enum { SGP_SWEEP_FULL = 0, SGP_SWEEP_TARGETS = 1, SGP_SWEEP_REUSED = 2 };
+int sgp_sweep_kind(const sgp_handle* h, int32_t* next, int32_t* last);
 
 /* ---- multi-GPU: the one exchange step of a sweep --------------------------------------------
  * Points are sharded over the ranks (one process = one GPU = one handle); Xu, theta and the prior are replicated.  The

@@ -44,6 +44,8 @@ struct SGPConfig
     n_max::Int64; m::Int32; d::Int32; d_out::Int32; device::Int32; flags::Int32; reserved::Int32
 end
 const SGP_FLAG_KEEP_KUF = Int32(2)
+const SGP_FLAG_REUSE_STATS = Int32(16)
+const SGP_SWEEP_FULL, SGP_SWEEP_TARGETS, SGP_SWEEP_REUSED = 0, 1, 2
 const SGP_S_COUNT = 8
 const SGP_R_COUNT = 8
 
@@ -80,7 +82,17 @@ set_noise!(h::Handle, W::Matrix{Float64}, ElogW) =
     check(ccall((:sgp_set_noise, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64), h.ptr, W, ElogW), h.ptr)
 set_prior!(h::Handle, vec, mat::Matrix{Float64}, form) =
     check(ccall((:sgp_set_prior, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32), h.ptr, vec, mat, form), h.ptr)
+# new targets for the resident inputs (X, weights and n_nodes of the last set_data!): with SGP_FLAG_REUSE_STATS the next sweep!
+# forms only B and the data scalars
+set_targets!(h::Handle, y, yv) =
+    check(ccall((:sgp_set_targets, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h.ptr, y, yv === nothing ? C_NULL : yv), h.ptr)
 sweep!(h::Handle) = check(ccall((:sgp_sweep, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), h.ptr, C_NULL), h.ptr)
+# (next, last) kind of sweep: SGP_SWEEP_FULL, SGP_SWEEP_TARGETS or SGP_SWEEP_REUSED (include/sgp_hip.h, sgp_sweep_kind)
+function sweep_kind(h::Handle)
+    nxt = Ref{Int32}(0); last = Ref{Int32}(0)
+    check(ccall((:sgp_sweep_kind, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), h.ptr, nxt, last), h.ptr)
+    return (Int(nxt[]), Int(last[]))
+end
 sweep_local!(h::Handle) = check(ccall((:sgp_sweep_local, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), h.ptr, C_NULL), h.ptr)
 wait!(h::Handle) = check(ccall((:sgp_wait, LIB), Cint, (Ptr{Cvoid},), h.ptr), h.ptr)      # polled drain of the handle's streams
 
@@ -169,9 +181,11 @@ mutable struct HipSGPMeta{R<:UniSGPMeta}
     μ_last::Vector{Float64}           # mean of the last swept q(v): the per-point pass belongs to it
 end
 
-function HipSGPMeta(ref::UniSGPMeta; kernel_params, jitter = 0.0, device = 0, cubature_points = 21)
+function HipSGPMeta(ref::UniSGPMeta; kernel_params, jitter = 0.0, device = 0, cubature_points = 21, reuse_stats = false)
     # (uncertain inputs enter the sweep as `cubature_points` weighted points per node: size the handle for them)
-    h = Handle(ref.N * max(1, cubature_points), inducing_matrix(ref.Xu), 1; device = device)
+    # reuse_stats: SGP_FLAG_REUSE_STATS -- sweeps at unchanged kernel and inputs reuse K_uf, Psi2 and the K_uu factor
+    flags = SGP_FLAG_KEEP_KUF | (reuse_stats ? SGP_FLAG_REUSE_STATS : 0)
+    h = Handle(ref.N * max(1, cubature_points), inducing_matrix(ref.Xu), 1; device = device, flags = flags)
     return HipSGPMeta(ref, h, kernel_params, Float64(jitter), Vector{Float64}[], Float64[], Float64[], nothing, 1.0, 0.0,
                       Float64[], Dict{Vector{Float64},Int}(), Float64[], Float64[], Float64[], false, nothing, device, Float64[])
 end

@@ -170,6 +170,8 @@ struct sgp_handle {
                                     // otherwise has its Lambda chain wait for the host to get through the other chain's 14 launches; once the host is a
                                     // sweep ahead the order makes no difference (profiles/r04_ab_log.txt [30], [37], [38])
     bool env_no_zero_copy = false; // SGP_NO_ZERO_COPY=1: sgp_w_stats copies its results back instead of writing them to pinned memory
+    int64_t env_predict_chunk = 0; // SGP_PREDICT_CHUNK: test points per chunk of sgp_predict_var (default: sized to a scratch budget)
+    bool posterior_set = false;    // sgp_set_posterior installed mu_v and Uv only: dSigma is not that q(v)'s covariance until the next sweep
     bool syrk_wide = false;        // the resident problem's SYRK launches are k_syrk_direct (set_point_count)
     std::vector<int> env_overlap_cols;   // SGP_OVERLAP_COLS: group boundaries (tile columns of P Lambda P), e.g. "3" or "2,4"
     int nblk = 0, ntiles = 0, num_cus = 256;
@@ -509,11 +511,13 @@ extern "C" int sgp_create(const sgp_config* cfg, sgp_handle** out) {
     {
         // Test hooks, read once (not per sweep).  Each forces a path the product already takes in some configuration, so that the
         // tests can compare it with the others: SGP_OVERLAP / SGP_OVERLAP_COLS (the overlapped sweep and its groups), SGP_SPIN_LIMIT
-        // (a short bounded wait), SGP_INTERLEAVE (the chain-after-chain host order), SGP_NO_ZERO_COPY (results copied back).
+        // (a short bounded wait), SGP_INTERLEAVE (the chain-after-chain host order), SGP_NO_ZERO_COPY (results copied back),
+        // SGP_PREDICT_CHUNK (sgp_predict_var in small chunks).
         if (const char* lim = getenv("SGP_SPIN_LIMIT")) h->spin_limit = std::max(1, atoi(lim));
         if (const char* ov = getenv("SGP_OVERLAP")) h->env_overlap = atoi(ov);
         if (const char* zc = getenv("SGP_NO_ZERO_COPY")) h->env_no_zero_copy = atoi(zc) != 0;
         if (const char* ni = getenv("SGP_INTERLEAVE")) h->env_interleave = atoi(ni) != 0;
+        if (const char* pc = getenv("SGP_PREDICT_CHUNK")) h->env_predict_chunk = std::max(1LL, atoll(pc));
         if (const char* oc = getenv("SGP_OVERLAP_COLS"))
             for (const char* q = oc; *q;) {
                 h->env_overlap_cols.push_back(atoi(q));
@@ -1415,6 +1419,7 @@ extern "C" int sgp_sweep_finish(sgp_handle* h, void* stream) {
     // the next sweep's K_uu chain may overwrite K_uu^-1 after this
     if (p.events) HIPCHK(h, hipEventRecord(h->evDone, s));
     h->swept = true;
+    h->posterior_set = false;
     h->last_stream = s;
     return 0;
 }
@@ -1518,6 +1523,7 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     h->mirror_epoch = mirror_for(h) ? h->done_epoch : -1;
     if (p.events) HIPCHK(h, hipEventRecord(h->evDone, s));
     h->swept = true;
+    h->posterior_set = false;
     h->last_stream = s;
     h->rec.targets = false;
     h->last_kind = targets ? SGP_SWEEP_TARGETS : SGP_SWEEP_REUSED;
@@ -1744,6 +1750,7 @@ extern "C" int sgp_set_posterior(sgp_handle* h, const double* mu_v, const double
     HIPCHK(h, hipMemcpy(h->dUvT, ut.data(), Qp * Qp * sizeof(double), hipMemcpyHostToDevice));
     h->swept = true;
     h->stats_dirty = true;                     // q(v) no longer belongs to the statistics on the device
+    h->posterior_set = true;                   // (no Sigma_v came with it: sgp_predict_var needs one passed in)
     return 0;
 }
 
@@ -2051,6 +2058,164 @@ extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy(mean, dMean, sizeof(double) * ns * h->dout, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Predictive mean and (co)variance of the latent f at test inputs (include/sgp_hip.h).  Everything is formed at the CURRENT kernel
+// parameters in call scratch -- K_uu, W_K = L_K^-1, the factor of Sigma_v -- and nothing the sweep keeps is written (dKuu, dWk, dKinv,
+// dSaccK, dWl, the log-det slot and dInfo stay what SGP_FLAG_REUSE_STATS and sgp_theta_objective expect); only the parameter mirror
+// dXusK / dParamsK is rewritten, as sgp_predict does.  The test points go through in chunks, so that the scratch stays bounded.
+constexpr int64_t PREDICT_CHUNK_DOUBLES = int64_t(1) << 25;     // scratch of one chunk: 256 MB
+template <int DT>
+static void launch_gram_star(sgp_handle* h, const double* dXs, double* dK, int64_t nc, hipStream_t s) {
+    // (d_out = 0: no targets, no B partial -- k_gram_uf's K tile alone, in its summation order)
+    hipLaunchKernelGGL(k_gram_uf<DT>, dim3((unsigned)((nc + TB - 1) / TB), h->T), dim3(256), 0, s, h->dXusK, dXs, (const double*)nullptr,
+                       dK, (double*)nullptr, h->dParamsK, h->M, h->Mp, h->D, nc, 0, (int64_t*)nullptr, (int64_t*)nullptr);
+}
+
+extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
+                               int32_t flags, double* mean, double* var) {
+    if (!h || ns < 0 || (ns > 0 && (!Xstar || !mean || !var))) return fail(h, SGP_ERR_ARG, "sgp_predict_var: bad argument");
+    if (flags & ~SGP_PREDICT_NOISE) return fail(h, SGP_ERR_ARG, "sgp_predict_var: unknown flags");
+    if (!mu_v != !Sigma_v) return fail(h, SGP_ERR_ARG, "sgp_predict_var: pass both mu_v and Sigma_v, or neither");
+    if (!h->have_inducing || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_predict_var: set_inducing and set_kernel first");
+    if (h->training) return fail(h, SGP_ERR_ARG, "sgp_predict_var: a device-paced training run is open (sgp_train_end first)");
+    if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_predict_var: no posterior in the handle and mu_v / Sigma_v are NULL");
+    if (!mu_v && h->posterior_set)
+        return fail(h, SGP_ERR_ARG, "sgp_predict_var: sgp_set_posterior gave no Sigma_v: pass mu_v and Sigma_v, or sweep first");
+    if (ns == 0) return 0;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, drain_device(h));
+    h->in_flight = false;
+    if (!mu_v) {
+        // the last sweep's q(v), refused exactly when sgp_get_posterior refuses it
+        if (int src = check_sync_status(h)) return src;
+        int info[2];
+        HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
+        if (info[0] < 0 || info[1] < 0) return fail(h, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
+        if (info[0] > 0) { h->err = "K_uu is not positive definite (last sweep)"; return info[0]; }
+        if (info[1] > 0) { h->err = "Lambda is not positive definite (last sweep)"; return std::max(1, h->Qp - info[1] + 1); }
+    }
+    hipStream_t s = h->own;
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T, TQ = h->TQ;
+    // chunk of test points: a multiple of 64, sized to the scratch budget (or SGP_PREDICT_CHUNK)
+    const int64_t per_point = (int64_t)Mp + 4 * T + 4 + D + dout + dout * dout;
+    int64_t chunk = h->env_predict_chunk > 0 ? h->env_predict_chunk : std::max<int64_t>(TB, PREDICT_CHUNK_DOUBLES / per_point);
+    chunk = std::min<int64_t>((chunk + TB - 1) / TB * TB, (ns + TB - 1) / TB * TB);
+    // scratch (doubles; every piece a multiple of 64, so that the 16-byte loads of the tiles stay aligned):
+    //   K_uu | W_K (Mp^2 each) | L_S (Qp^2) | chunk: K(Xu, X*) (Mp), pa, pb (2 T each), kmu (4), X* (D), mean (d_out), var (d_out^2)
+    //   | mu_v (Qp) | two factorisations' scratch | status words
+    const size_t fixed = 2 * (size_t)Mp * Mp + (size_t)Qp * Qp;
+    const size_t total = fixed + (size_t)(chunk * per_point) + Qp + 2 * POTRF_SCRATCH + 64;
+    double* base = nullptr;
+    if (int crc = call_scratch(h, total, &base)) return crc;
+    double* dKuuS = base;
+    double* dWkS = dKuuS + (size_t)Mp * Mp;
+    double* dLS = dWkS + (size_t)Mp * Mp;
+    double* dKc = dLS + (size_t)Qp * Qp;
+    double* dPa = dKc + (size_t)chunk * Mp;
+    double* dPb = dPa + (size_t)chunk * 2 * T;
+    double* dKmu = dPb + (size_t)chunk * 2 * T;
+    double* dXs = dKmu + (size_t)chunk * 4;
+    double* dMeanC = dXs + (size_t)chunk * D;
+    double* dVarC = dMeanC + (size_t)chunk * dout;
+    double* dMuX = dVarC + (size_t)chunk * dout * dout;
+    double* dPscr = dMuX + Qp;
+    int* dInfoS = reinterpret_cast<int*>(dPscr + 2 * POTRF_SCRATCH);
+    // q(v): the explicit one uploaded (Sigma_v padded with the identity), or the last sweep's mean in place and its Sigma_v
+    // (dSigma, what sgp_get_posterior returns -- not dWl, which sgp_set_prior(form 0) reuses) copied
+    const double* dMu = h->dMu;
+    if (mu_v) {
+        std::vector<double> m(Qp, 0.0);
+        memcpy(m.data(), mu_v, sizeof(double) * Q);
+        HIPCHK(h, hipMemcpy(dMuX, m.data(), sizeof(double) * Qp, hipMemcpyHostToDevice));
+        if (int rc = upload_padded(h, Sigma_v, dLS)) return rc;
+        dMu = dMuX;
+    } else {
+        hipLaunchKernelGGL(k_pad_square, dim3((unsigned)(((size_t)Qp * Qp + 255) / 256)), dim3(256), 0, s, (const double*)h->dSigma, Qp,
+                           dLS, Q, Qp);
+    }
+    HIPCHK(h, hipMemsetAsync(dPscr, 0, sizeof(double) * (2 * POTRF_SCRATCH + 64), s));
+    // the current parameters into the K_uu chain's mirror (as sgp_predict), K_uu at them and its inverse factor, Sigma_v's factor
+    hipLaunchKernelGGL(k_prep_xu, dim3((Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXusK, (const Params*)h->hParams,
+                       h->dParamsK, (int*)nullptr, M, Mp, D, (int64_t*)nullptr, 0, 0, (const long long*)nullptr, 0LL,
+                       (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
+    hipLaunchKernelGGL(k_gram_uu, dim3(T, T), dim3(256), 0, s, h->dXusK, dKuuS, h->dParamsK, M, Mp, D);
+    launch_potrf(dKuuS, Mp, T, dInfoS + 0, M, dPscr, s, dWkS);
+    launch_potrf(dLS, Qp, TQ, dInfoS + 1, Q, dPscr + POTRF_SCRATCH, s);
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    int info[2];
+    HIPCHK(h, hipMemcpy(info, dInfoS, sizeof info, hipMemcpyDeviceToHost));
+    if (info[0] < 0 || info[1] < 0) return fail(h, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
+    if (info[0] > 0) { h->err = "K_uu is not positive definite (current kernel)"; return info[0]; }
+    if (info[1] > 0) { h->err = "Sigma_v is not positive definite"; return info[1]; }
+    // the observation noise W^-1 (of the last sgp_set_noise), added in the finishing kernel: 0 without the flag
+    OutMat noise;
+    memset(&noise, 0, sizeof noise);
+    if (flags & SGP_PREDICT_NOISE) {
+        if (dout == 1) noise.v[0] = 1.0 / h->hParams->W[0];
+        else {
+            // Gauss-Jordan with partial pivoting on the d_out x d_out mean of q(W) (column-major, as sgp_set_noise stores it)
+            double a[MAXO][2 * MAXO];
+            for (int i = 0; i < dout; ++i)
+                for (int j = 0; j < dout; ++j) { a[i][j] = h->hParams->W[j * dout + i]; a[i][dout + j] = (i == j) ? 1.0 : 0.0; }
+            for (int c = 0; c < dout; ++c) {
+                int piv = c;
+                for (int r = c + 1; r < dout; ++r) if (fabs(a[r][c]) > fabs(a[piv][c])) piv = r;
+                if (!(a[piv][c] != 0.0)) return fail(h, SGP_ERR_ARG, "sgp_predict_var: the noise matrix of sgp_set_noise is singular");
+                for (int j = 0; j < 2 * dout; ++j) std::swap(a[c][j], a[piv][j]);
+                const double inv = 1.0 / a[c][c];
+                for (int j = 0; j < 2 * dout; ++j) a[c][j] *= inv;
+                for (int r = 0; r < dout; ++r)
+                    if (r != c && a[r][c] != 0.0) {
+                        const double f = a[r][c];
+                        for (int j = 0; j < 2 * dout; ++j) a[r][j] -= f * a[c][j];
+                    }
+            }
+            for (int i = 0; i < dout; ++i)
+                for (int j = 0; j < dout; ++j) noise.v[j * dout + i] = 0.5 * (a[i][dout + j] + a[j][dout + i]);
+        }
+    }
+    for (int64_t s0 = 0; s0 < ns; s0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, ns - s0);
+        const unsigned nblk = (unsigned)((nc + TB - 1) / TB);
+        HIPCHK(h, hipMemcpyAsync(dXs, Xstar + (size_t)s0 * D, sizeof(double) * nc * D, hipMemcpyHostToDevice, s));
+        // the mean: sgp_predict's kernel on the same mirror, so it is bitwise sgp_predict's
+        switch (D) {
+            case 1: launch_predict<1>(h, dXs, dMu, dMeanC, nc, s); break;
+            case 2: launch_predict<2>(h, dXs, dMu, dMeanC, nc, s); break;
+            case 3: launch_predict<3>(h, dXs, dMu, dMeanC, nc, s); break;
+            case 4: launch_predict<4>(h, dXs, dMu, dMeanC, nc, s); break;
+            case 8: launch_predict<8>(h, dXs, dMu, dMeanC, nc, s); break;
+            default: launch_predict<0>(h, dXs, dMu, dMeanC, nc, s); break;
+        }
+        if (D <= 8) launch_gram_star<8>(h, dXs, dKc, nc, s);
+        else launch_gram_star<MAXD>(h, dXs, dKc, nc, s);
+        // |W_K k*|^2 -> pa and, for d_out = 1, |L_S' k*|^2 -> pb: k_quadform_fused as sgp_w_stats runs it, with L_S where that
+        // passes Uv' (its k . mu rows go to kmu, unused).  MultiSGP needs cross terms instead of the second form: the launch then
+        // repeats W_K there (its pb is not read) and k_predvar_multi forms them.
+        hipLaunchKernelGGL(k_quadform_fused, dim3(nblk, 2 * T), dim3(256), 0, s, (const double*)dWkS, dout == 1 ? (const double*)dLS : dWkS,
+                           (const double*)dKc, dMu, dPa, dPb, dKmu, Mp, T, nc);
+        switch (dout) {
+            case 1:
+                hipLaunchKernelGGL(k_predvar_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)dPa,
+                                   (const double*)dPb, dVarC, (const Params*)h->dParamsK, noise.v[0], T, nc);
+                break;
+            case 2: hipLaunchKernelGGL(k_predvar_multi<2>, dim3(nblk), dim3(256), 0, s, (const double*)dLS, (const double*)dKc,
+                                       (const double*)dPa, dVarC, (const Params*)h->dParamsK, noise, M, Mp, Q, Qp, T, nc); break;
+            case 3: hipLaunchKernelGGL(k_predvar_multi<3>, dim3(nblk), dim3(256), 0, s, (const double*)dLS, (const double*)dKc,
+                                       (const double*)dPa, dVarC, (const Params*)h->dParamsK, noise, M, Mp, Q, Qp, T, nc); break;
+            default: hipLaunchKernelGGL(k_predvar_multi<4>, dim3(nblk), dim3(256), 0, s, (const double*)dLS, (const double*)dKc,
+                                        (const double*)dPa, dVarC, (const Params*)h->dParamsK, noise, M, Mp, Q, Qp, T, nc); break;
+        }
+        HIPCHK(h, hipGetLastError());
+        // mean chunk: [d_out][nc] on the device -> rows s0 .. of the ns x d_out column-major output; var chunk: contiguous
+        HIPCHK(h, hipMemcpy2DAsync(mean + s0, sizeof(double) * ns, dMeanC, sizeof(double) * nc, sizeof(double) * nc, dout,
+                                   hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(var + (size_t)s0 * dout * dout, dVarC, sizeof(double) * nc * dout * dout, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));             // (the next chunk's upload reuses the scratch; pageable host memory)
+    }
     return 0;
 }
 

@@ -3044,6 +3044,114 @@ __global__ void __launch_bounds__(256) k_w_point_finish(const double* __restrict
     I2[n] = yy * yy + v - 2.0 * yy * km + b;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Predictive variances (sgp_predict_var).  For a test point with k* = k(Xu, x*) and q(v) = N(mu_v, Sigma_v):
+//   C_f[i][j] = delta_ij (sigma2 - |L_K^-1 k*|^2) + k*' Sigma_v^(ij) k*   (+ W^-1 with the noise flag)
+// |L_K^-1 k*|^2 and, for d_out = 1, k*' Sigma_v k* = |L_S' k*|^2 (Sigma_v = L_S L_S') are k_quadform_fused's two forms over a
+// chunk of K(Xu, X*); the kernels below finish them.
+// ------------------------------------------------------------------------------------------------
+// var[n] = ((sigma2 - sum_r pa[r][n]) + sum_r pb[r][n]) + noise     (fixed summation order, rows as k_w_point_finish sums them)
+__global__ void __launch_bounds__(256) k_predvar_finish(const double* __restrict__ pa, const double* __restrict__ pb,
+                                                        double* __restrict__ var, const Params* __restrict__ P, double noise,
+                                                        int T, int64_t N) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    double a = 0.0, b = 0.0;
+    for (int r = 0; r < 2 * T; ++r) { a += pa[(size_t)r * N + n]; b += pb[(size_t)r * N + n]; }
+    var[n] = ((P->sigma2 - a) + b) + noise;
+}
+
+// dst (np x np, column-major) = src (n x n, leading dimension lds) padded with the identity
+__global__ void __launch_bounds__(256) k_pad_square(const double* __restrict__ src, int lds, double* __restrict__ dst, int n, int np) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)np * np) return;
+    const int i = (int)(e % np), j = (int)(e / np);
+    dst[e] = (i < n && j < n) ? src[(size_t)j * lds + i] : (i == j ? 1.0 : 0.0);
+}
+
+// MultiSGP: the cross terms k*' Sigma_v^(ij) k* = z_i . z_j with z_i = (L_S[iM:(i+1)M, :])' k* (a Q-vector; L_S lower, Q = d_out M),
+// and the finished d_out x d_out blocks.  One workgroup per 64 test points: thread (point p = tid & 63, wave g) holds z_i for the
+// 16 columns g*16 .. g*16+15 of every 64-column tile of L_S; K_uf and L_S tiles are staged in LDS (the L_S reads are wave-uniform
+// broadcasts), the products z_i . z_j accumulate per thread and the four waves' partials are added in a fixed order at the end.
+// Entries of L_S above its diagonal (what the factorisation leaves of the input there) are masked on the way into LDS.
+struct OutMat { double v[MAXO * MAXO]; };     // d_out x d_out, column-major
+template <int DO>
+__global__ void __launch_bounds__(256) k_predvar_multi(const double* __restrict__ L, const double* __restrict__ Kc,
+                                                       const double* __restrict__ pa, double* __restrict__ var,
+                                                       const Params* __restrict__ P, OutMat noise, int M, int Mp, int Q, int Qp,
+                                                       int T, int64_t N) {
+    constexpr int NP = DO * (DO + 1) / 2;
+    __shared__ double ks[TB * LT];            // [m][point]
+    __shared__ double ls[TB * LT];            // [m][column of L_S]
+    __shared__ double red[4 * NP * TB];
+    const int tid = threadIdx.x, p = tid & 63;
+    const int g = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const int64_t n0 = (int64_t)blockIdx.x * TB;
+    double c[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) c[k] = 0.0;
+    const int TQ = (Q + TB - 1) / TB;
+    for (int ct = 0; ct < TQ; ++ct) {
+        const int c0 = ct * TB;
+        double z[DO][16];
+#pragma unroll
+        for (int i = 0; i < DO; ++i)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) z[i][q] = 0.0;
+        for (int m0 = 0; m0 < M; m0 += TB) {
+            __syncthreads();                                  // the previous tiles have been consumed
+            for (int e = tid; e < TB * TB; e += 256) {
+                const int r = e & 63, pt = e >> 6;
+                const int64_t n = n0 + pt;
+                ks[r * LT + pt] = (n < N) ? Kc[(size_t)n * Mp + m0 + r] : 0.0;
+            }
+#pragma unroll
+            for (int i = 0; i < DO; ++i) {
+                const int rb = i * M + m0;                    // first row of L_S in this tile
+                if (c0 > rb + TB - 1) continue;               // tile above the diagonal (uniform)
+                __syncthreads();
+                for (int e = tid; e < TB * TB; e += 256) {
+                    const int r = e & 63, cc = e >> 6, row = rb + r, col = c0 + cc;
+                    ls[r * LT + cc] = (m0 + r < M && col <= row) ? L[(size_t)col * Qp + row] : 0.0;
+                }
+                __syncthreads();
+                for (int r = 0; r < TB; ++r) {
+                    const double kv = ks[r * LT + p];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) z[i][q] = fma(ls[r * LT + g * 16 + q], kv, z[i][q]);
+                }
+            }
+        }
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < DO; ++i)
+#pragma unroll
+            for (int j = i; j < DO; ++j, ++k)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) c[k] = fma(z[i][q], z[j][q], c[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) red[(g * NP + k) * TB + p] = c[k];
+    __syncthreads();
+    const int64_t n = n0 + tid;
+    if (tid >= TB || n >= N) return;
+    double a = 0.0;
+    for (int r = 0; r < 2 * T; ++r) a += pa[(size_t)r * N + n];
+    const double qff = P->sigma2 - a;
+    double* out = var + (size_t)n * DO * DO;
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < DO; ++i)
+#pragma unroll
+        for (int j = i; j < DO; ++j, ++k) {
+            const double s = (red[(0 * NP + k) * TB + tid] + red[(1 * NP + k) * TB + tid]) +
+                             (red[(2 * NP + k) * TB + tid] + red[(3 * NP + k) * TB + tid]);
+            const double v = ((i == j ? qff : 0.0) + s) + noise.v[j * DO + i];
+            out[j * DO + i] = v;
+            out[i * DO + j] = v;
+        }
+}
+
 // transpose-copy of a square column-major matrix (Uv = L_R^T on the way out)
 __global__ void __launch_bounds__(256) k_transpose(const double* __restrict__ A, double* __restrict__ At, int ld) {
     __shared__ double tile[TB * (TB + 1)];

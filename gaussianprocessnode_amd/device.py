@@ -253,6 +253,22 @@ class SGPDevice:
         self._check(self._lib.sgp_predict(self._h, ptr(Xs), ns, ptr(mu), ptr(out)), "sgp_predict")
         return out[0] if self.d_out == 1 else out.T.copy()
 
+    def predict_var(self, Xstar, mu_v=None, Sigma_v=None, noise: bool = False):
+        """Predictive mean and (co)variance of the latent f at Xstar (sgp_predict_var), at the current kernel: (mean, var) with
+        mean (ns,) and var (ns,) for d_out = 1, mean (ns, d_out) and var (ns, d_out, d_out) otherwise.  q(v) is the last sweep's
+        (mu_v = Sigma_v = None) or the one given; noise=True adds W^-1 of the last `set_noise`."""
+        Xs = as_f64(np.reshape(Xstar, (-1, self.D)))
+        ns = Xs.shape[0]
+        if (mu_v is None) != (Sigma_v is None):
+            raise ValueError("predict_var: pass both mu_v and Sigma_v, or neither")
+        mu = None if mu_v is None else as_f64(np.reshape(mu_v, (self.Q,)))
+        S = None if Sigma_v is None else as_f64(np.asarray(Sigma_v, dtype=np.float64).reshape(self.Q, self.Q).T)   # column-major
+        mean = np.empty((self.d_out, ns))
+        var = np.empty(ns) if self.d_out == 1 else np.empty((ns, self.d_out, self.d_out))
+        flags = _lib.SGP_PREDICT_NOISE if noise else 0
+        self._check(self._lib.sgp_predict_var(self._h, ptr(Xs), ns, ptr(mu), ptr(S), flags, ptr(mean), ptr(var)), "sgp_predict_var")
+        return (mean[0], var) if self.d_out == 1 else (mean.T.copy(), var)
+
     def set_posterior(self, mu_v, Uv):
         """Install an external q(v) (mean and Uv = chol(Sigma_v + mu mu').U) for the per-point outputs (`w_stats`)."""
         mu = as_f64(np.reshape(mu_v, (self.Q,)))

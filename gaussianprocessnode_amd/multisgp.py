@@ -133,6 +133,31 @@ def rule_out(q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta) -> MvNormal
     return MvNormalMeanPrecision(w @ f, W)
 
 
+def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, noise: bool = True):
+    """Predictive means and covariances of the d_out latent outputs (noise=False) or of the observation (noise=True: +
+    mean(q_w)^-1) at kernel(q_theta) and the explicit q_v (sgp_predict_var).  Test inputs (ns, D) give means (ns, d_out) and
+    covariances (ns, d_out, d_out); a PointMass or an uncertain input q(x*) gives one mean (d_out,) and covariance (d_out,
+    d_out) -- the latter by one device call over meta.method's cubature points and the law of total variance in matrix form."""
+    from .unisgp import _test_points, combine_total_variance
+    W = _mean_W(q_w)
+    d_out = W.shape[0]
+    D = np.asarray(meta.Xu).shape[1]
+    X, wts = _test_points(Xstar_or_q_in, meta.method, D)
+    eng = _engine(meta, 1, d_out)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    eng.set_kernel(sigma2, ell, meta.jitter)
+    if noise:
+        eng.set_noise(W)
+    mu_v, Sigma_v = q_v.mean_cov()
+    m, C = eng.predict_var(X, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64), noise=noise)
+    m, C = np.asarray(m, dtype=np.float64).reshape(-1, d_out), np.asarray(C, dtype=np.float64).reshape(-1, d_out, d_out)
+    if wts is not None:
+        return combine_total_variance(wts, m, C)
+    if isinstance(Xstar_or_q_in, PointMass):
+        return m[0], C[0]
+    return m, C
+
+
 def rule_v(q_out, q_in, q_w, q_theta: PointMass, meta: MultiSGPMeta) -> MvNormalWeightedMeanPrecision:
     """@rule MultiSGP(:v) for ONE step (GPnode/MultiSGPnode.jl:290-328): the message itself, xi = vcat(Psi1 (mu_y' W)_d),
     Lambda = kron(W, Psi2), with Psi1 / Psi2 from the device statistics of that step."""

@@ -312,6 +312,63 @@ def predict(Xstar, q_v, q_theta, meta: UniSGPMeta) -> np.ndarray:
     return eng.predict(Xstar, np.asarray(q_v.mean(), dtype=np.float64))
 
 
+def _test_points(x, method, D: int):
+    """(points (S, D), cubature weights or None) of an array of test inputs, a PointMass, or an uncertain input q(x*) (by
+    meta.method's cubature, as `rule_out` takes them)."""
+    if _is_pointmass(x):
+        return np.atleast_1d(np.asarray(x.mean(), dtype=np.float64)).reshape(1, D), None
+    if not isinstance(x, (np.ndarray, list, tuple, float, int)) and hasattr(x, "mean"):
+        if method is None:
+            raise ValueError("an uncertain test input needs meta.method (a cubature rule)")
+        m, P = x.mean_cov() if hasattr(x, "mean_cov") else (x.mean(), x.var())
+        pts, wts = method.points_weights(m, P)
+        return np.asarray(pts, dtype=np.float64).reshape(-1, D), np.asarray(wts, dtype=np.float64)
+    X = np.asarray(x, dtype=np.float64)
+    return X.reshape(-1, D), None
+
+
+def combine_total_variance(wts, m, var):
+    """Law of total variance over cubature points s: mean = sum w_s m_s, var = sum w_s (var_s + m_s^2) - mean^2.  Scalar
+    outputs: m, var (S,); matrix outputs: m (S, d), var (S, d, d) -> (d,), (d, d) with m_s m_s' in place of m_s^2."""
+    wts, m, var = np.asarray(wts, dtype=np.float64), np.asarray(m, dtype=np.float64), np.asarray(var, dtype=np.float64)
+    mean = wts @ m
+    if m.ndim == 1:
+        return float(mean), float(wts @ (var + m * m) - mean * mean)
+    second = np.einsum("s,sij->ij", wts, var + m[:, :, None] * m[:, None, :])
+    return mean, second - np.outer(mean, mean)
+
+
+def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool = True):
+    """Predictive mean and variance of the latent f (noise=False) or of the observation y (noise=True: + 1 / mean(q_w)) at
+    kernel(q_theta) and the explicit q_v (`q_v.mean_cov()` goes to the device, sgp_predict_var).  Test inputs (ns, D) give
+    per-point arrays (ns,), (ns,); a PointMass or an uncertain input q(x*) gives two floats -- the latter by one device call over
+    meta.method's cubature points and the law of total variance on the host.  `rule_out` is unchanged (the reference's
+    message carries precision mean(q_w) only)."""
+    D = meta.Xu.shape[1]
+    X, wts = _test_points(Xstar_or_q_in, meta.method, D)
+    eng = _engine(meta, 1)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    eng.set_kernel(sigma2, ell, meta.jitter)
+    if noise:
+        eng.set_noise([[_mean_w(q_w)]], _elog_w(q_w))
+    mu_v, Sigma_v = q_v.mean_cov()
+    m, v = eng.predict_var(X, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64), noise=noise)
+    if wts is not None:
+        return combine_total_variance(wts, m, v)
+    if _is_pointmass(Xstar_or_q_in):
+        return float(m[0]), float(v[0])
+    return m, v
+
+
+def probit_predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta):
+    """P(y = 1) of the classification model (`f ~ UniSGP(x, v, w, theta); y ~ Probit(f)`, experiments/classification_banana.ipynb):
+    Phi(m / sqrt(1 + var_f + 1 / mean(q_w))), with (m, var_f + 1 / mean(q_w)) from `predictive(..., noise=True)`."""
+    from scipy.special import ndtr
+    m, v = predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta, noise=True)
+    p = ndtr(np.asarray(m, dtype=np.float64) / np.sqrt(1.0 + np.asarray(v, dtype=np.float64)))
+    return float(p) if np.ndim(p) == 0 else p
+
+
 # ------------------------------------------------------------------------------------------------
 # @average_energy  (GPnode/UniSGPnode.jl:337-359 Gamma w; :363-387 classification; :411-436 PointMass w)
 # ------------------------------------------------------------------------------------------------

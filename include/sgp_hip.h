@@ -136,7 +136,8 @@ int sgp_sweep(sgp_handle* h, void* stream);                 /* local + [all-redu
  *   SGP_SWEEP_TARGETS  after sgp_set_targets or sgp_set_output_cov_sum: B and the data scalars from the resident K_uf (with an
  *                      all-reduce hook: ONE call, of the exchange buffer's tail [B | scalars], count = Mp d_out + SGP_S_COUNT +
  *                      d_out^2 on every rank), then phase 2;
- *   SGP_SWEEP_REUSED   otherwise (sgp_set_noise, sgp_set_prior, sgp_carry_posterior, sgp_set_posterior, sgp_w_stats, sgp_predict):
+ *   SGP_SWEEP_REUSED   otherwise (sgp_set_noise, sgp_set_prior, sgp_carry_posterior, sgp_set_posterior, sgp_w_stats, sgp_predict,
+ *                      sgp_predict_var):
  *                      phase 2 alone over the resident statistics; no K_uu chain, no hook call.
  * The results of TARGETS and REUSED sweeps are bitwise those of a full sweep.  sgp_sweep_local / sgp_sweep_finish keep their
  * meaning (a full local phase, phase 2).
@@ -218,6 +219,25 @@ int sgp_w_stats(sgp_handle* h, double* I1 /* n */, double* I2 /* n */, void* str
  * experiments/regression_kin40k.ipynb:288-304): mean[s] = K(x*_s, Xu) mu_v^(d).  Xstar is D x ns (host),
  * mu_v (host, d_out*M) or NULL to use the handle's current posterior; mean is ns x d_out. */
 int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, double* mean);
+
+/* sgp_predict_var: predictive mean and (co)variance of the latent f at test inputs.  With k* = k(Xu, x*), k** = sigma2 and
+ * q(v) = N(mu_v, Sigma_v) (Q = d_out*M entries, output-major; block (i, j) of Sigma_v is Sigma_v^(ij), M x M):
+ *     mean_o     = k*' mu_v^(o)                                         (bitwise what sgp_predict returns)
+ *     C_f[i][j]  = delta_ij (sigma2 - |L_K^-1 k*|^2) + k*' Sigma_v^(ij) k*,   L_K = chol(K_uu + jitter I)
+ * at the CURRENT kernel parameters (the last sgp_set_kernel, as sgp_predict).  flags & SGP_PREDICT_NOISE adds W^-1 of the last
+ * sgp_set_noise: 1 / w_bar for d_out = 1, the inverse of the d_out x d_out mean of q(W) otherwise (the precision the :out rules
+ * attach, GPnode/UniSGPnode.jl:103, GPnode/MultiSGPnode.jl:90-120).
+ * Layout: Xstar and mean as sgp_predict (D x ns, ns x d_out); var is [ns] for d_out = 1 and [ns][d_out][d_out] otherwise, every
+ * block a full, exactly symmetric matrix.
+ * Posterior: mu_v = Sigma_v = NULL uses the last finished sweep's q(v) (what sgp_get_posterior returns); both given: that q(v),
+ * Sigma_v dense Q x Q column-major.  Refused with SGP_ERR_ARG: only one of the two given; NULL after sgp_set_posterior (which
+ * installs no Sigma_v) until the next sweep; NULL before any sweep; an open sgp_train_* run; unknown flags.  A K_uu (at the
+ * current kernel) or Sigma_v that is not positive definite returns its failing leading minor k > 0.
+ * Blocking.  K_uu, its factor and the factor of Sigma_v are formed in call scratch: nothing the sweep keeps is written, so the
+ * kind of the next sgp_sweep (sgp_sweep_kind) and the theta gradient are unaffected.  Test points are processed in chunks. */
+#define SGP_PREDICT_NOISE 1   /* add the observation noise W^-1 */
+int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
+                    int32_t flags, double* mean, double* var);
 
 /* sgp_wait: returns when everything this handle has enqueued -- on its own streams or the caller's -- has finished: what a caller
  * does between `infer` calls when it wants the sweep to be over but none of its results yet.  The library's streams are polled

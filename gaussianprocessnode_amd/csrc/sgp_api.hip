@@ -661,7 +661,7 @@ extern "C" int sgp_set_inducing(sgp_handle* h, const double* Xu) {
 //     (N = 10 000, M = 512; sweeps/s on one box): plain order 3750; cuts {3} 3896, {2} 3832-3950, {2,4} 3925, {1,3} 3656,
 //     {2,3,5} 3790, {1,2,4} 3528 -- the model ranks them the same way.  When no plan beats the plain order by 5 us the plain
 //     order stays (huge N: the masked groups' lost CUs cost more than the chain's early start saves).
-static double model_overlap_end(const sgp_handle* h, int64_t n, const int* cuts, int ncuts, double* classic_end) {
+static double model_overlap_end(const sgp_handle* h, int64_t n, bool wide, const int* cuts, int ncuts, double* classic_end) {
     const int T = h->T;
     // one SYRK launch = one resident round: its duration follows the points per chunk (k_syrk_stream: 0.18 us per point at four
     // workgroups per CU, + ~5 us of launch ramp and tail; k_syrk_direct: 0.029 us per point -- eight waves share the chunk, two to a
@@ -669,7 +669,7 @@ static double model_overlap_end(const sgp_handle* h, int64_t n, const int* cuts,
     // tiles' meeting in LDS and the slab store), whatever the number of tiles -- fewer CUs or an awkward tile count show up as
     // fewer, longer chunks (syrk_geometry)
     auto syrk_us = [&](int row_lo, int nrows, int cus) {
-        const SyrkGeom g = syrk_geometry(row_lo, nrows, cus, n, h->syrk_wide);
+        const SyrkGeom g = syrk_geometry(row_lo, nrows, cus, n, wide);
         return g.wide ? 13.0 + 0.029 * g.chunk : 5.0 + 0.18 * g.chunk;
     };
     // The schedule's constants.  k_syrk_stream launches (small problems never overlap; kept as fitted in round 3): ~8 / ~11 us of
@@ -680,7 +680,7 @@ static double model_overlap_end(const sgp_handle* h, int64_t n, const int* cuts,
     // +-1.3 us): in the kernel's own duration (7.5 + 0.029 us per point; syrk_us above is what HIP events see) group 0's assembly
     // and its two boundaries are 11.5 us, the masked stream's first SYRK starts 8 us behind group 0's, a masked group is usable
     // 5 us behind its SYRK, and a step that forms a group costs 5 us more than one that does not.
-    const bool dk = h->syrk_wide;
+    const bool dk = wide;
     const double asm0 = dk ? 11.5 : 8.0, asmm = dk ? 5.0 : 11.0, step = 17.0, margin = dk ? 0.0 : 4.0, forming = dk ? 5.0 : 2.5;
     const double mstart = dk ? 8.0 : 2.0, launch = dk ? 5.5 : 0.0;   // (launch: what syrk_us counts beyond the kernel's own duration)
     if (classic_end) *classic_end = syrk_us(0, T, h->num_cus) - launch + asm0 + step * T;
@@ -702,12 +702,20 @@ static double model_overlap_end(const sgp_handle* h, int64_t n, const int* cuts,
     return end;
 }
 
+constexpr int64_t GATE_MIN = 10000;         // points x lower tiles from which the SYRK is taken to fill the chip (set_point_count)
+
+// Data-sharded (an all-reduce hook is installed): every group of the plan is one collective, so the ranks of a run must agree on
+// it while their shards differ by a point (shard_bounds) or are empty.  The plan -- whether to overlap, and the cuts -- is then
+// chosen from n_max, which the ranks of one run share (include/sgp_hip.h: the largest shard), never from the resident n; only
+// each group's SYRK geometry follows the resident n.  Without a hook the resident n decides, as before.
 static void plan_overlap(sgp_handle* h, int64_t n) {
     h->overlap = false;
     h->ngroups = 0;
     const int T = h->T;
-    if (!h->statM || h->env_overlap == 0 || h->dout != 1 || T < 3 || T > LAM_MAX_COLS || h->training || n < 1 ||
-        (!h->gate_side && h->env_overlap != 1))
+    const int64_t np = h->allreduce ? h->n_max : n;                 // the point count the plan is chosen for
+    const bool wide = h->allreduce ? np * (int64_t)h->ntiles >= GATE_MIN : h->syrk_wide;   // (syrk_wide = gate_side)
+    if (!h->statM || h->env_overlap == 0 || h->dout != 1 || T < 3 || T > LAM_MAX_COLS || h->training || np < 1 ||
+        (!wide && h->env_overlap != 1))
         return;
     std::vector<int> cuts;                                   // group boundaries, ascending, in (0, T)
     for (int c : h->env_overlap_cols) if (c > 0 && c < T && (cuts.empty() || c > cuts.back())) cuts.push_back(c);
@@ -719,9 +727,9 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
         // Among plans the model cannot tell apart (< 0.3 us) the later second cut wins: the measured order at T.
         for (int a = 1; a < T; ++a) {
             cand[0] = a; cand[1] = a;
-            const double e = model_overlap_end(h, n, cand, 1, &classic);
+            const double e = model_overlap_end(h, np, wide, cand, 1, &classic);
             if (e < best - 0.3) { best = e; cuts.assign(cand, cand + 1); }
-            if (!h->syrk_wide || h->allreduce) continue;     // (data-sharded: every further group is another collective)
+            if (!wide || h->allreduce) continue;     // (data-sharded: every further group is another collective)
             // (three groups were fitted and validated at eight tile columns; with four -- M = 256 -- the planner's {1,2} lost 8 % against the
             // plain order at N = 20 000 where {1} gains: fewer than six columns keep one cut)
             if (T < 6) continue;
@@ -732,16 +740,16 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
                 // group late polls and then reads the statistics past the L2, the masked SYRK beside it slows down (0.038 instead of
                 // 0.029 us per point in the timeline), and the next group is later still -- a model that knows no feedback must stay
                 // out of that regime (profiles/r04_ab_log.txt [17]).
-                const double m1 = 13.0 + 0.029 * syrk_geometry(T - b, b - a, h->stat_cus_masked, n, true).chunk;
-                const double m2 = 13.0 + 0.029 * syrk_geometry(0, T - b, h->stat_cus_masked, n, true).chunk;
+                const double m1 = 13.0 + 0.029 * syrk_geometry(T - b, b - a, h->stat_cus_masked, np, true).chunk;
+                const double m2 = 13.0 + 0.029 * syrk_geometry(0, T - b, h->stat_cus_masked, np, true).chunk;
                 if (m1 > 45.0 || m2 > 45.0) continue;
-                const double e2 = model_overlap_end(h, n, cand, 2, &classic);
+                const double e2 = model_overlap_end(h, np, wide, cand, 2, &classic);
                 if (e2 < best - 0.3) { best = e2; cuts.assign(cand, cand + 2); }
             }
         }
         // (the plain order stays unless the model sees a gain: 5 us with the LDS-staged SYRK's constants; 1 us with k_syrk_direct's --
         // at C2 (M = 256, four tile columns) the model sees 1.1 us for the cut {1} and the sweep gains 4.5, 129.2 -> 124.8 us)
-        if (h->env_overlap != 1 && best > classic - (h->syrk_wide ? 1.0 : 5.0)) return;
+        if (h->env_overlap != 1 && best > classic - (wide ? 1.0 : 5.0)) return;
     }
     if ((int)cuts.size() + 1 > LAM_MAX_GROUPS) return;
     size_t off = 0;
@@ -772,8 +780,6 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
     h->ngroups = (int)cuts.size() + 1;
     h->overlap = true;
 }
-
-constexpr int64_t GATE_MIN = 10000;         // points x lower tiles from which the SYRK is taken to fill the chip (set_point_count)
 
 // the launch geometry of the data-sized kernels for n points
 static int set_point_count(sgp_handle* h, int64_t n) {
@@ -1151,8 +1157,9 @@ static int enqueue_stats_overlapped(sgp_handle* h, const SweepPlan& p) {
     const int Mp = h->Mp, T = h->T;
     hipStream_t own = p.stream;
     const bool sharded = p.pack;
-    prep_main(h, own, false);
-    launch_gram(h, own, true);
+    // (a data-sharded rank with an empty shard follows the plan as well: no Gram kernel, no SYRK, zero pieces -- plan_overlap)
+    prep_main(h, own, h->n <= 0);
+    if (h->n > 0) launch_gram(h, own, true);
     // The masked groups start when group 0's assembly starts, i.e. its SYRK has drained.  Measured against starting them as soon
     // as group 0's SYRK has its round on the CUs (the masked SYRK then fills the CUs as they drain, but group 0's assembly shares
     // them with it: 12.7 instead of 8.7 us on the critical path) and once group 0 is assembled (the chains' whole-CU workgroups
@@ -1163,8 +1170,9 @@ static int enqueue_stats_overlapped(sgp_handle* h, const SweepPlan& p) {
     for (int g = 0; g < h->ngroups; ++g) {
         const StatGroup& G = h->grp[g];
         hipStream_t s = G.masked ? h->statM : own;
-        launch_syrk(G.geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs + G.slab_off, Mp, h->n,
-                    h->dStamps + STAMP_STRIDE * SGP_T_SYRK, g == 0 ? h->dJoin + WORD_GATE : (long long*)nullptr, h->gate_epoch);
+        if (h->n > 0)
+            launch_syrk(G.geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs + G.slab_off, Mp, h->n,
+                        h->dStamps + STAMP_STRIDE * SGP_T_SYRK, g == 0 ? h->dJoin + WORD_GATE : (long long*)nullptr, h->gate_epoch);
         hipLaunchKernelGGL(k_assemble, dim3(G.nrows, T + (g == 0 ? 1 : 0), assemble_z(G.geom)), dim3(256), 0, s, h->dSlabs + G.slab_off, h->dBpart,
                            h->dDataScal, sharded ? h->dPack : h->dStats, Mp, T, G.geom, h->nblk, h->dout,
                            SGP_S_COUNT + h->dout * h->dout, g == 0 ? 1 : 0, h->dStamps + STAMP_STRIDE * SGP_T_LOCAL,
@@ -1484,7 +1492,7 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     // The Lambda chain forms its tile columns at the steps a full sweep of this call would (sgp_sweep's overlapped order: a column
     // formed at a later step has collected its rank-64 updates first, i.e. in another order), so that the results are bitwise
     // that sweep's -- every column in stream order, nothing waited for.
-    p.overlapped = h->overlap && !stream && h->n > 0 && !h->training;
+    p.overlapped = h->overlap && !stream && (h->n > 0 || h->allreduce) && !h->training;
     p.pack = h->allreduce != nullptr;
     p.resident = true;
     hipStream_t s = p.stream;
@@ -1539,8 +1547,9 @@ extern "C" int sgp_sweep(sgp_handle* h, void* stream) {
         if (kind != SGP_SWEEP_FULL) return sweep_resident(h, stream, kind == SGP_SWEEP_TARGETS);
     }
     // single GPU, the library's own streams, a problem that qualifies: statistics and Lambda chain overlapped
-    // (with an all-reduce hook as well: one reduce per statistics group, see enqueue_stats_overlapped)
-    const bool overlapped = h->overlap && !stream && h->n > 0 && !h->training;
+    // (with an all-reduce hook as well: one reduce per statistics group, see enqueue_stats_overlapped -- an empty shard included,
+    // whose rank must issue the same collectives as the others)
+    const bool overlapped = h->overlap && !stream && (h->n > 0 || h->allreduce) && !h->training;
     int rc = sweep_local_impl(h, stream, overlapped, h->env_interleave, h->allreduce != nullptr);
     if (rc) return rc;
     if (h->allreduce && !overlapped) {
@@ -1587,7 +1596,7 @@ extern "C" int sgp_set_allreduce(sgp_handle* h, sgp_allreduce_fn fn, void* ctx) 
     h->allreduce = fn;
     h->allreduce_ctx = ctx;
     h->rec.valid = false;                      // (the resident statistics are this rank's, or the sum over other ranks)
-    if (h->n > 0) plan_overlap(h, h->n);         // (a data-sharded sweep pays one collective per statistics group: one cut)
+    plan_overlap(h, h->n);         // (a data-sharded sweep pays one collective per statistics group: one cut, chosen from n_max)
     return 0;
 }
 
@@ -1608,7 +1617,7 @@ extern "C" int sgp_use_rccl(sgp_handle* h, void* nccl_comm) {
     h->allreduce = rccl_hook;
     h->allreduce_ctx = h;
     h->rec.valid = false;
-    if (h->n > 0) plan_overlap(h, h->n);
+    plan_overlap(h, h->n);
     return 0;
 }
 

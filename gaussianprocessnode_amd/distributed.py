@@ -81,8 +81,9 @@ def device_tensor(ptr: int, count: int, device="cuda"):
 
 
 class HipEngine:
-    """This rank's shard on its MI355X: local statistics and the replicated tail through the C ABI.  `use_graph` is accepted
-    and ignored (see SGPDevice)."""
+    """This rank's shard on its MI355X: local statistics and the replicated tail through the C ABI.  `n_max`: the same on every
+    rank of a run, the largest shard (`-(-N // world)`; include/sgp_hip.h, sgp_config.n_max).  `use_graph` is accepted and
+    ignored (see SGPDevice)."""
 
     def __init__(self, n_max: int, m: int, d: int, d_out: int = 1, device: int = 0, use_graph: bool = False,
                  reuse_stats: bool = False):
@@ -235,7 +236,9 @@ class ShardedDevice:
     same q(v) and the same theta.  The reference has no counterpart (single process); the additivity it relies on is the
     N-fold product of GPnode/UniSGPnode.jl:62-63 and the sum over points of helper_functions/derivative_helper.jl:29-38.
 
-    `dev`: the rank's device (an `SGPDevice`, or a test double with the same methods); `rank`, `world`: the partition.
+    `dev`: the rank's device (an `SGPDevice`, or a test double with the same methods); `rank`, `world`: the partition.  Every
+    rank's device has the same `n_max` (at least the largest shard of the largest minibatch): with the hook installed the
+    library chooses the order of a sweep's collectives from it (include/sgp_hip.h, sgp_config.n_max).
     The hook is the caller's business (`HipEngine.install_allreduce` / `ShardedSweep` for torch.distributed, `sgp_use_rccl`
     for a bare communicator, a test double)."""
 

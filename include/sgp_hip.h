@@ -49,7 +49,10 @@ typedef struct sgp_handle sgp_handle;
 /* Limits of this build (sgp_create returns SGP_ERR_ARG beyond them): 1 <= d <= 32 (LDS coordinate panels),
  * 1 <= d_out <= 4 (register tiles of the MultiSGP reductions), d_out * m <= 4032 (LDS copy of the forward-solve vector). */
 typedef struct sgp_config {
-    int64_t n_max;    /* capacity in points of this handle (this rank's shard) */
+    int64_t n_max;    /* capacity in points of this handle (this rank's shard).  Data-sharded runs (sgp_set_allreduce /
+                       * sgp_use_rccl): every rank of one run creates its handle with the SAME n_max, the largest shard --
+                       * ceil(N / world) for a block partition -- because the order of the sweep's collectives is chosen from
+                       * it (sgp_overlap_plan) */
     int32_t m;        /* inducing points M                 */
     int32_t d;        /* input dimension D (1..32)         */
     int32_t d_out;    /* outputs: 1 = UniSGP, 2..4 = MultiSGP (shared kernel) */
@@ -346,7 +349,9 @@ int sgp_time_kernel(sgp_handle* h, int32_t which, int32_t iters, void* stream, d
  * "Fills the chip" = points x lower tiles >= 10 000: from there on the SYRK is k_syrk_direct (one workgroup per CU, no LDS
  * staging; below it the LDS-staged k_syrk_stream) and the K_uu chain is held back
  * until its single round is resident.  The planner places one cut, or two from six tile columns on while the masked launches
- * are short; a data-sharded sweep (hook installed) keeps one cut -- every group is a collective.
+ * are short; a data-sharded sweep (hook installed) keeps one cut -- every group is a collective -- and chooses the order and the
+ * cut from n_max, not from the resident point count: ranks whose shards differ by a point, or that hold none, then issue the
+ * same collectives (an empty shard sends zero pieces); only the point chunks of each group follow the rank's own shard.
  * Host order of the launches: sgp_sweep on the library's streams enqueues the launches of the K_uu chain and of the Lambda chain
  * alternately -- a sweep that starts on an idle device (the first of a block, every sweep of a caller that fetches something in
  * between) then does not have its Lambda chain wait for the host to get through the other chain's 14 launches; once the host is a

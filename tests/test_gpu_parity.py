@@ -897,7 +897,7 @@ def test_overlapped_sweep_with_one_reduce_per_statistics_group(G):
     cut = N // 2
 
     def make(sl):
-        d = G.SGPDevice(N, M, D)
+        d = G.SGPDevice(N - cut, M, D)           # (n_max: the largest shard, the same on every rank -- include/sgp_hip.h)
         d.set_inducing(Xu); d.set_data(X[sl], y[sl]); d.set_kernel(s2, ell, 0.0)
         d.set_prior_isotropic(50.0); d.set_noise([[w]])
         return d

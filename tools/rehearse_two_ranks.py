@@ -26,7 +26,7 @@ X = rng.uniform(-1.7, 1.7, (N, D)); Xu = X[:M].copy(); y = np.sin(X.sum(1))
 lo, hi = shard_bounds(N, world, rank)
 say(f"engine for points [{lo}, {hi})")
 
-eng = HipEngine(hi - lo, M, D, 1, device=0)
+eng = HipEngine(-(-N // world), M, D, 1, device=0)          # every rank: n_max = the largest shard (include/sgp_hip.h)
 dev = eng.dev
 dev.set_inducing(Xu); dev.set_data(X[lo:hi], y[lo:hi]); dev.set_kernel(0.9, np.full(D, 1.5), JIT)
 dev.set_prior_isotropic(50.0); dev.set_noise([[100.0]])

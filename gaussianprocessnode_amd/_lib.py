@@ -32,8 +32,23 @@ EXPORTS = [
     "sgp_kernelmatrix", "sgp_potrf", "sgp_potri", "sgp_get_timestamps", "sgp_get_phase_totals", "sgp_time_kernel", "sgp_get_chain_trace", "sgp_set_allreduce", "sgp_use_rccl", "sgp_measure_sclk_mhz",
     "sgp_train_begin", "sgp_train_step", "sgp_train_end", "sgp_get_step_trace", "sgp_measure_clocks", "sgp_overlap_plan",
     "sgp_get_sweep_trace", "sgp_train_likelihood", "sgp_train_get_gamma", "sgp_wait", "sgp_set_targets", "sgp_sweep_kind",
-    "sgp_predict_var",
+    "sgp_predict_var", "sgp_set_kernel_family", "sgp_kernelmatrix_family",
 ]
+# kernel families (SGP_KERNEL_* of include/sgp_hip.h), by the names the Python layer accepts
+SGP_KERNEL_SE, SGP_KERNEL_MATERN12, SGP_KERNEL_MATERN32, SGP_KERNEL_MATERN52 = 0, 1, 2, 3
+KERNEL_FAMILIES = {"se": SGP_KERNEL_SE, "matern12": SGP_KERNEL_MATERN12, "matern32": SGP_KERNEL_MATERN32,
+                   "matern52": SGP_KERNEL_MATERN52}
+
+
+def family_id(family) -> int:
+    """SGP_KERNEL_* id of a family name ("se", "matern12", "matern32", "matern52"); None is SE."""
+    if family is None:
+        return SGP_KERNEL_SE
+    try:
+        return KERNEL_FAMILIES[str(family).lower()]
+    except KeyError:
+        raise ValueError(f"unknown kernel family {family!r}: expected one of {sorted(KERNEL_FAMILIES)}") from None
+
 SGP_TIME_GROUP0 = 100
 SGP_TIME_QUADFORM = 120
 SGP_PREDICT_NOISE = 1         # sgp_predict_var: add the observation noise W^-1
@@ -116,6 +131,9 @@ def load(build_if_missing: bool = True, variant=None):
     lib.sgp_predict_var.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int32, dp, dp]
     lib.sgp_theta_objective.argtypes = [vp, dp, dp]
     lib.sgp_kernelmatrix.argtypes = [C.c_int32, dp, C.c_int64, dp, C.c_int64, C.c_int32, C.c_double, dp, C.c_int32, dp]
+    lib.sgp_kernelmatrix_family.argtypes = [C.c_int32, C.c_int32, dp, C.c_int64, dp, C.c_int64, C.c_int32, C.c_double, dp,
+                                            C.c_int32, dp]
+    lib.sgp_set_kernel_family.argtypes = [vp, C.c_int32]
     lib.sgp_potrf.argtypes = [C.c_int32, dp, C.c_int32, dp]
     lib.sgp_potri.argtypes = [C.c_int32, dp, C.c_int32, dp]
     lib.sgp_get_timestamps.argtypes = [vp, C.POINTER(C.c_int64)]

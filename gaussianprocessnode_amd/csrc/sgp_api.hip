@@ -20,6 +20,7 @@
 #include <limits>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace sgp;
@@ -111,6 +112,7 @@ struct sgp_handle {
     hipStream_t last_stream = nullptr;   // the stream the last sweep's tail was enqueued on (sgp_sweep_finish): what stream order covers
     uint64_t data_gen = 0, swept_data_gen = ~0ull;   // bumped by set_data / set_inducing; recorded by the sweep
     Params swept_params{};                            // kernel / noise parameters the last sweep ran with
+    int32_t family = SGP_KERNEL_SE, swept_family = SGP_KERNEL_SE;   // kernel family (sgp_set_kernel_family) / that of the last sweep
     int n_ell = 1;
     // device buffers
     double *dXu = nullptr, *dXus = nullptr, *dX = nullptr, *dYw = nullptr, *dY = nullptr, *dYv = nullptr, *dOmega = nullptr;
@@ -193,10 +195,23 @@ struct sgp_handle {
     struct ResidentStats {
         bool valid = false, checked = false, targets = false;
         double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};
+        int32_t family = SGP_KERNEL_SE;
     } rec;
     int32_t last_kind = SGP_SWEEP_FULL;   // what the last completed sgp_sweep did (sgp_sweep_kind)
     std::string err;
 };
+
+// the kernel family as a compile-time constant: f(std::integral_constant<int, FAM>{}) -- every kernel that evaluates k is
+// instantiated per family (sgp_kernels.hip.h, fam_kappa), and the launch sites of a handle dispatch on h->family through this
+template <class F>
+static void by_family(int32_t family, F&& f) {
+    switch (family) {
+        case SGP_KERNEL_MATERN12: f(std::integral_constant<int, SGP_KERNEL_MATERN12>{}); break;
+        case SGP_KERNEL_MATERN32: f(std::integral_constant<int, SGP_KERNEL_MATERN32>{}); break;
+        case SGP_KERNEL_MATERN52: f(std::integral_constant<int, SGP_KERNEL_MATERN52>{}); break;
+        default: f(std::integral_constant<int, SGP_KERNEL_SE>{}); break;
+    }
+}
 
 #define HIPCHK(h, call)                                                                                   \
     do {                                                                                                  \
@@ -950,6 +965,14 @@ extern "C" int sgp_set_kernel(sgp_handle* h, double sigma2, const double* ell, i
     return 0;
 }
 
+extern "C" int sgp_set_kernel_family(sgp_handle* h, int32_t family) {
+    if (!h) return fail(h, SGP_ERR_ARG, "sgp_set_kernel_family: null handle");
+    if (int qrc = quiesce(h)) return qrc;                 // (also refuses a change inside a device-paced training run)
+    if (family < SGP_KERNEL_SE || family > SGP_KERNEL_MATERN52) return fail(h, SGP_ERR_ARG, "sgp_set_kernel_family: unknown family");
+    h->family = family;
+    return 0;
+}
+
 extern "C" int sgp_set_noise(sgp_handle* h, const double* W, double E_log_w) {
     if (!h || !W) return fail(h, SGP_ERR_ARG, "sgp_set_noise: null argument");
     if (int qrc = quiesce(h)) return qrc;
@@ -1064,8 +1087,11 @@ extern "C" int sgp_bind_stats(sgp_handle* h, void* stats_dev) {
 // the K_uu chain in three pieces -- [k_prep_xu, Gram] [Cholesky steps + inverse factor] [K_uu^-1, join word] -- so that a sweep can
 // enqueue its two chains' steps alternately (enqueue_chains_interleaved)
 static void kuu_gram(sgp_handle* h, hipStream_t s, bool gate) {
-    if (gate) hipLaunchKernelGGL(k_gram_uu_lds, dim3(h->T, h->T), dim3(256), 0, s, h->dXusK, h->dKuu, h->dParamsK, h->M, h->Mp, h->D);
-    else hipLaunchKernelGGL(k_gram_uu, dim3(h->T, h->T), dim3(256), 0, s, h->dXusK, h->dKuu, h->dParamsK, h->M, h->Mp, h->D);
+    by_family(h->family, [&](auto F) {
+        constexpr int FAM = decltype(F)::value;
+        if (gate) hipLaunchKernelGGL(k_gram_uu_lds<FAM>, dim3(h->T, h->T), dim3(256), 0, s, h->dXusK, h->dKuu, h->dParamsK, h->M, h->Mp, h->D);
+        else hipLaunchKernelGGL(k_gram_uu<FAM>, dim3(h->T, h->T), dim3(256), 0, s, h->dXusK, h->dKuu, h->dParamsK, h->M, h->Mp, h->D);
+    });
 }
 static void kuu_tail(sgp_handle* h, hipStream_t s, bool join_word) {
     launch_ata(h->dWk, h->dKinv, h->Mp, h->T, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->dSaccK);
@@ -1098,12 +1124,15 @@ static void enqueue_kuu(sgp_handle* h, hipStream_t s, bool join_word) {
 
 static void launch_gram(sgp_handle* h, hipStream_t s, bool opens_sweep) {
     int64_t* sweep_begin = opens_sweep ? h->dStamps : nullptr;
-    if (h->D <= 8)
-        hipLaunchKernelGGL(k_gram_uf<8>, dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw, h->dKuf, h->dBpart,
-                           h->dParams, h->M, h->Mp, h->D, h->n, h->dout, h->dStamps + STAMP_STRIDE * SGP_T_GRAM, sweep_begin);
-    else
-        hipLaunchKernelGGL(k_gram_uf<MAXD>, dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw, h->dKuf, h->dBpart,
-                           h->dParams, h->M, h->Mp, h->D, h->n, h->dout, h->dStamps + STAMP_STRIDE * SGP_T_GRAM, sweep_begin);
+    by_family(h->family, [&](auto F) {
+        constexpr int FAM = decltype(F)::value;
+        if (h->D <= 8)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<8, FAM>), dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw, h->dKuf,
+                               h->dBpart, h->dParams, h->M, h->Mp, h->D, h->n, h->dout, h->dStamps + STAMP_STRIDE * SGP_T_GRAM, sweep_begin);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<MAXD, FAM>), dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw, h->dKuf,
+                               h->dBpart, h->dParams, h->M, h->Mp, h->D, h->n, h->dout, h->dStamps + STAMP_STRIDE * SGP_T_GRAM, sweep_begin);
+    });
 }
 
 // The scaled inducing inputs and the parameter mirror of the main stream (dXus, dParams) only change when a setter ran: a sweep
@@ -1395,6 +1424,7 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool i
         if (int src = enqueue_stats()) return src;
     h->stats_dirty = false;
     h->swept_params = *h->hParams;
+    h->swept_family = h->family;
     h->swept_data_gen = h->data_gen;
     h->swept_local = true;
     return 0;
@@ -1459,7 +1489,7 @@ static int32_t planned_kind(const sgp_handle* h) {
     if (h->dStats != h->dStatsOwn && !h->allreduce) return SGP_SWEEP_FULL;
     // kernel values compared as sgp_theta_objective's freshness test does: set_kernel at the same theta keeps the statistics
     const Params& P = *h->hParams;
-    if (P.sigma2 != h->rec.sigma2 || P.jitter != h->rec.jitter) return SGP_SWEEP_FULL;
+    if (P.sigma2 != h->rec.sigma2 || P.jitter != h->rec.jitter || h->family != h->rec.family) return SGP_SWEEP_FULL;
     for (int d = 0; d < h->D; ++d)
         if (P.inv_ell[d] != h->rec.inv_ell[d]) return SGP_SWEEP_FULL;
     return h->rec.targets ? SGP_SWEEP_TARGETS : SGP_SWEEP_REUSED;
@@ -1521,6 +1551,7 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     HIPCHK(h, hipGetLastError());
     h->stats_dirty = false;
     h->swept_params = *h->hParams;
+    h->swept_family = h->family;
     h->swept_data_gen = h->data_gen;
     h->swept_local = true;
     enqueue_finish1(h, s, p);
@@ -1565,6 +1596,7 @@ extern "C" int sgp_sweep(sgp_handle* h, void* stream) {
         h->rec.sigma2 = h->hParams->sigma2;
         h->rec.jitter = h->hParams->jitter;
         for (int d = 0; d < MAXD; ++d) h->rec.inv_ell[d] = h->hParams->inv_ell[d];
+        h->rec.family = h->family;
     }
     return 0;
 }
@@ -1931,12 +1963,16 @@ extern "C" int sgp_time_kernel(sgp_handle* h, int32_t which, int32_t iters, void
         else if (G)
             launch_syrk(G->geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs + G->slab_off, h->Mp, h->n, (int64_t*)nullptr,
                         (long long*)nullptr, 0LL);
-        else if (which == SGP_T_GRAM && h->D <= 8)
-            hipLaunchKernelGGL(k_gram_uf<8>, dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw, h->dKuf, h->dBpart,
-                               h->dParams, h->M, h->Mp, h->D, h->n, h->dout, (int64_t*)nullptr, (int64_t*)nullptr);
         else if (which == SGP_T_GRAM)
-            hipLaunchKernelGGL(k_gram_uf<MAXD>, dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw, h->dKuf, h->dBpart,
-                               h->dParams, h->M, h->Mp, h->D, h->n, h->dout, (int64_t*)nullptr, (int64_t*)nullptr);
+            by_family(h->family, [&](auto F) {
+                constexpr int FAM = decltype(F)::value;
+                if (h->D <= 8)
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<8, FAM>), dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw,
+                                       h->dKuf, h->dBpart, h->dParams, h->M, h->Mp, h->D, h->n, h->dout, (int64_t*)nullptr, (int64_t*)nullptr);
+                else
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<MAXD, FAM>), dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw,
+                                       h->dKuf, h->dBpart, h->dParams, h->M, h->Mp, h->D, h->n, h->dout, (int64_t*)nullptr, (int64_t*)nullptr);
+            });
         else
             launch_syrk(h->geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs, h->Mp, h->n, (int64_t*)nullptr,
                         (long long*)nullptr, 0LL);
@@ -2016,17 +2052,24 @@ extern "C" int sgp_w_stats(sgp_handle* h, double* I1, double* I2, void* stream) 
 // ------------------------------------------------------------------------------------------------
 // prediction
 // ------------------------------------------------------------------------------------------------
+// (the SE family has forms for D = 1, 2, 3, 4 and 8; the others only the generic one: DT = 0)
 template <int DT>
 static void launch_predict(sgp_handle* h, const double* dXs, const double* dMu, double* dMean, int64_t ns, hipStream_t s) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<DT>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, h->dXusK, dXs, dMu,
-                       dMean, h->dParamsK, h->M, h->Mp, h->D, ns, h->dout);
+    by_family(h->family, [&](auto F) {
+        constexpr int FAM = decltype(F)::value, DTF = FAM == SGP_KERNEL_SE ? DT : 0;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<DTF, FAM>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, h->dXusK, dXs,
+                           dMu, dMean, h->dParamsK, h->M, h->Mp, h->D, ns, h->dout);
+    });
 }
 
 // (the same on the MAIN stream's copies of the scaled inducing inputs / parameters: the classification training step's forward message)
 template <int DT>
 static void launch_predict_main(sgp_handle* h, const double* dXs, const double* dMu, double* dMean, int64_t ns, hipStream_t s) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<DT>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, h->dXus, dXs, dMu,
-                       dMean, h->dParams, h->M, h->Mp, h->D, ns, h->dout);
+    by_family(h->family, [&](auto F) {
+        constexpr int FAM = decltype(F)::value, DTF = FAM == SGP_KERNEL_SE ? DT : 0;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<DTF, FAM>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, h->dXus, dXs,
+                           dMu, dMean, h->dParams, h->M, h->Mp, h->D, ns, h->dout);
+    });
 }
 
 extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, double* mean) {
@@ -2078,8 +2121,12 @@ constexpr int64_t PREDICT_CHUNK_DOUBLES = int64_t(1) << 25;     // scratch of on
 template <int DT>
 static void launch_gram_star(sgp_handle* h, const double* dXs, double* dK, int64_t nc, hipStream_t s) {
     // (d_out = 0: no targets, no B partial -- k_gram_uf's K tile alone, in its summation order)
-    hipLaunchKernelGGL(k_gram_uf<DT>, dim3((unsigned)((nc + TB - 1) / TB), h->T), dim3(256), 0, s, h->dXusK, dXs, (const double*)nullptr,
-                       dK, (double*)nullptr, h->dParamsK, h->M, h->Mp, h->D, nc, 0, (int64_t*)nullptr, (int64_t*)nullptr);
+    by_family(h->family, [&](auto F) {
+        constexpr int FAM = decltype(F)::value;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<DT, FAM>), dim3((unsigned)((nc + TB - 1) / TB), h->T), dim3(256), 0, s, h->dXusK,
+                           dXs, (const double*)nullptr, dK, (double*)nullptr, h->dParamsK, h->M, h->Mp, h->D, nc, 0, (int64_t*)nullptr,
+                           (int64_t*)nullptr);
+    });
 }
 
 extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
@@ -2149,7 +2196,9 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
     hipLaunchKernelGGL(k_prep_xu, dim3((Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXusK, (const Params*)h->hParams,
                        h->dParamsK, (int*)nullptr, M, Mp, D, (int64_t*)nullptr, 0, 0, (const long long*)nullptr, 0LL,
                        (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
-    hipLaunchKernelGGL(k_gram_uu, dim3(T, T), dim3(256), 0, s, h->dXusK, dKuuS, h->dParamsK, M, Mp, D);
+    by_family(h->family, [&](auto F) {
+        hipLaunchKernelGGL(k_gram_uu<decltype(F)::value>, dim3(T, T), dim3(256), 0, s, h->dXusK, dKuuS, h->dParamsK, M, Mp, D);
+    });
     launch_potrf(dKuuS, Mp, T, dInfoS + 0, M, dPscr, s, dWkS);
     launch_potrf(dLS, Qp, TQ, dInfoS + 1, Q, dPscr + POTRF_SCRATCH, s);
     HIPCHK(h, hipStreamSynchronize(s));
@@ -2268,12 +2317,17 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
                        Mp, T, 3, 0, 0, (const double*)nullptr, (double*)nullptr, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, UvArgs{}, (const double*)nullptr);
     hipLaunchKernelGGL(k_gemm32, dim3(T * T * 4), dim3(256), 0, su, (const double*)dT1, (const double*)h->dKinv, dH, Mp, T,
                        3, 0, 0, (const double*)nullptr, (double*)nullptr, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, UvArgs{}, (const double*)nullptr);
-    hipLaunchKernelGGL(k_theta_grad_uu, dim3(T, T), dim3(256), 0, su, dH, h->dXus, h->dParams, part_uu, h->M, Mp, h->D);
+    by_family(h->family, [&](auto F) {
+        hipLaunchKernelGGL(k_theta_grad_uu<decltype(F)::value>, dim3(T, T), dim3(256), 0, su, dH, h->dXus, h->dParams, part_uu, h->M,
+                           Mp, h->D);
+    });
     if (split) hipLaunchKernelGGL(k_join_set, dim3(1), dim3(64), 0, su, h->dJoin + WORD_GRAD, ++h->grad_epoch);
     hipLaunchKernelGGL(k_form_G, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, h->dR, h->dKinv, dG, cnt);
     if (h->n > 0)
-        hipLaunchKernelGGL(k_theta_grad_uf, dim3(h->nblk, T, KS), dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus, h->dYw,
-                           h->has_omega ? h->dOmega : nullptr, h->dMu, h->dParams, part_uf, Mp, T, h->D, h->n);
+        by_family(h->family, [&](auto F) {
+            hipLaunchKernelGGL(k_theta_grad_uf<decltype(F)::value>, dim3(h->nblk, T, KS), dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus,
+                               h->dYw, h->has_omega ? h->dOmega : nullptr, h->dMu, h->dParams, part_uf, Mp, T, h->D, h->n);
+        });
     // Data-sharded run (an all-reduce hook is installed; the statistics in dStats are the reduced ones): the data half above used
     // this rank's K_uf, X and y -- its fixed-order total (1 + D doubles) is summed over the ranks through the same hook; the
     // K_uu half and the s_w term come from the reduced statistics and are replicated.  Every rank ends with the whole gradient.
@@ -2335,7 +2389,8 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
     // hook).  A caller-bound buffer WITHOUT a hook may have been reduced outside the library: then the statistics are
     // re-formed locally, as before.
     bool fresh = !h->stats_dirty && h->swept_data_gen == h->data_gen && (h->dStats == h->dStatsOwn || h->allreduce) &&
-                 h->swept_params.sigma2 == h->hParams->sigma2 && h->swept_params.jitter == h->hParams->jitter;
+                 h->swept_params.sigma2 == h->hParams->sigma2 && h->swept_params.jitter == h->hParams->jitter &&
+                 h->swept_family == h->family;
     // the objective is linear in w: a new mean(q_w) (classification_banana.ipynb passes the UPDATED q(w)) only rescales it
     const double wscale = fresh ? h->hParams->W[0] / h->swept_params.W[0] : 1.0;
     for (int d = 0; d < h->D && fresh; ++d) fresh = h->swept_params.inv_ell[d] == h->hParams->inv_ell[d];
@@ -2560,8 +2615,14 @@ extern "C" int sgp_train_end(sgp_handle* h, double* theta_raw, int64_t* counts) 
 // ------------------------------------------------------------------------------------------------
 extern "C" int sgp_kernelmatrix(int32_t device, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
                                 double sigma2, const double* ell, int32_t n_ell, double* K) {
+    return sgp_kernelmatrix_family(device, SGP_KERNEL_SE, A, na, B, nb, d, sigma2, ell, n_ell, K);
+}
+
+extern "C" int sgp_kernelmatrix_family(int32_t device, int32_t family, const double* A, int64_t na, const double* B, int64_t nb,
+                                       int32_t d, double sigma2, const double* ell, int32_t n_ell, double* K) {
     if (!A || !B || !K || !ell || d < 1 || d > MAXD || (n_ell != 1 && n_ell != d) || na < 0 || nb < 0)
         return fail(nullptr, SGP_ERR_ARG, "sgp_kernelmatrix: bad argument");
+    if (family < SGP_KERNEL_SE || family > SGP_KERNEL_MATERN52) return fail(nullptr, SGP_ERR_ARG, "sgp_kernelmatrix_family: unknown family");
     int rc = set_device_checked(device);
     if (rc) return rc;
     if (na == 0 || nb == 0) return 0;
@@ -2578,8 +2639,10 @@ extern "C" int sgp_kernelmatrix(int32_t device, const double* A, int64_t na, con
     HIPCHK(h, hipMemcpy(bA.p, A, sizeof(double) * na * d, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(bB.p, B, sizeof(double) * nb * d, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(bP.p, &P, sizeof(Params), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_kernelmatrix, dim3((unsigned)((na * nb + 255) / 256)), dim3(256), 0, 0, bA.as<double>(), bB.as<double>(),
-                       bK.as<double>(), bP.as<Params>(), na, nb, d);
+    by_family(family, [&](auto F) {
+        hipLaunchKernelGGL(k_kernelmatrix<decltype(F)::value>, dim3((unsigned)((na * nb + 255) / 256)), dim3(256), 0, 0, bA.as<double>(),
+                           bB.as<double>(), bK.as<double>(), bP.as<Params>(), na, nb, d);
+    });
     HIPCHK(h, hipDeviceSynchronize());
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy(K, bK.p, sizeof(double) * na * nb, hipMemcpyDeviceToHost));

@@ -236,6 +236,38 @@ __global__ void k_prep_xu(const double* __restrict__ Xu, double* __restrict__ Xu
 }
 
 // ------------------------------------------------------------------------------------------------
+// Kernel families (SGP_KERNEL_* in include/sgp_hip.h; KernelFunctions.jl definitions with `with_lengthscale`): k = sigma2 kappa(r),
+// r = sqrt(s), s = sum_d ((a_d - b_d) / ell_d)^2 -- always the direct-difference sum, so s >= 0 and sqrt is safe -- and
+// dk/dell_d = sigma2 phi(r) (a_d - b_d)^2 / ell_d^3.  FAM is a template parameter of every kernel that evaluates k: the SE
+// instantiations are the kernels as they were before the other families existed.
+//   SE  : kappa = exp(-s/2)                              phi = kappa
+//   M12 : kappa = exp(-r)                                phi = exp(-r) / r   (0 at r = 0, where every difference is 0)
+//   M32 : kappa = (1 + sqrt3 r) exp(-sqrt3 r)            phi = 3 exp(-sqrt3 r)
+//   M52 : kappa = (1 + sqrt5 r + 5 s / 3) exp(-sqrt5 r)  phi = 5/3 (1 + sqrt5 r) exp(-sqrt5 r)
+// ------------------------------------------------------------------------------------------------
+constexpr double FAM_SQRT3 = 1.7320508075688772935;
+constexpr double FAM_SQRT5 = 2.2360679774997896964;
+template <int FAM>
+__device__ __forceinline__ double fam_kappa(double s) {
+    if constexpr (FAM == 0) return exp(-0.5 * s);
+    else if constexpr (FAM == 1) return exp(-sqrt(s));
+    else if constexpr (FAM == 2) { const double a = FAM_SQRT3 * sqrt(s); return (1.0 + a) * exp(-a); }
+    else { const double a = FAM_SQRT5 * sqrt(s); return fma(5.0 / 3.0, s, 1.0 + a) * exp(-a); }
+}
+// kappa and phi at once (one exp)
+template <int FAM>
+__device__ __forceinline__ void fam_kappa_phi(double s, double& kappa, double& phi) {
+    if constexpr (FAM == 0) { kappa = exp(-0.5 * s); phi = kappa; }
+    else if constexpr (FAM == 1) { const double r = sqrt(s), e = exp(-r); kappa = e; phi = r > 0.0 ? e / r : 0.0; }
+    else if constexpr (FAM == 2) { const double a = FAM_SQRT3 * sqrt(s), e = exp(-a); kappa = (1.0 + a) * e; phi = 3.0 * e; }
+    else {
+        const double a = FAM_SQRT5 * sqrt(s), e = exp(-a);
+        kappa = fma(5.0 / 3.0, s, 1.0 + a) * e;
+        phi = (5.0 / 3.0) * (1.0 + a) * e;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K_uu (+ jitter I), padded with the identity.  One 64 x 64 tile per block, 16 entries per thread.
 // ------------------------------------------------------------------------------------------------
 // Two forms.  k_gram_uu_lds (coordinate panels in 32 KB of LDS) is what a sweep whose SYRK fills the chip launches: it is queued
@@ -244,6 +276,7 @@ __global__ void k_prep_xu(const double* __restrict__ Xu, double* __restrict__ Xu
 // (round 4, profiles/r04_ab_log.txt [9]: the LDS-free form beside it, 51 instead of 42 us for group 0's launch).  k_gram_uu (no
 // LDS; thread = row i with its D coordinates in registers, a column's coordinates wave-uniform scalar loads) is for the small
 // problems, where the K_uu chain starts with the sweep and nothing is there to wait for (C1: 20 300 instead of 17 500 sweeps/s).
+template <int FAM>
 __global__ void __launch_bounds__(256) k_gram_uu_lds(const double* __restrict__ Xus, double* __restrict__ Kuu,
                                                  const Params* __restrict__ P, int M, int Mp, int D) {
     __shared__ double ui[MAXD * TB];
@@ -265,12 +298,13 @@ __global__ void __launch_bounds__(256) k_gram_uu_lds(const double* __restrict__ 
         for (int d = 0; d < D; ++d) { double t = ui[d * TB + i] - uj[d * TB + j]; d2 = fma(t, t, d2); }
         int gi = I + i, gj = J + j;
         double v;
-        if (gi < M && gj < M) v = s2 * exp(-0.5 * d2) + (gi == gj ? jit : 0.0);
+        if (gi < M && gj < M) v = s2 * fam_kappa<FAM>(d2) + (gi == gj ? jit : 0.0);
         else v = (gi == gj) ? 1.0 : 0.0;
         Kuu[(size_t)gj * Mp + gi] = v;
     }
 }
 
+template <int FAM>
 __global__ void __launch_bounds__(256) k_gram_uu(const double* __restrict__ Xus, double* __restrict__ Kuu,
                                                  const Params* __restrict__ P, int M, int Mp, int D) {
     TraceScope trace(3);
@@ -290,7 +324,7 @@ __global__ void __launch_bounds__(256) k_gram_uu(const double* __restrict__ Xus,
         for (int d = 0; d < MAXD; ++d)
             if (d < D) { const double t = ui[d] - uj[(size_t)d * Mp]; d2 = fma(t, t, d2); }
         double v;
-        if (gi < M && gj < M) v = s2 * exp(-0.5 * d2) + (gi == gj ? jit : 0.0);
+        if (gi < M && gj < M) v = s2 * fam_kappa<FAM>(d2) + (gi == gj ? jit : 0.0);
         else v = (gi == gj) ? 1.0 : 0.0;
         Kuu[(size_t)gj * Mp + gi] = v;
     }
@@ -329,7 +363,7 @@ __device__ __forceinline__ void bpart_sum(double (&s)[R], Group group) {
 // ------------------------------------------------------------------------------------------------
 // DCAP: capacity of the LDS coordinate panels (8 for D <= 8 -- 18 KB of LDS per workgroup instead of 42 KB, i.e. 8
 // instead of 3 resident workgroups per CU for this store-bound kernel -- else MAXD)
-template <int DCAP>
+template <int DCAP, int FAM>
 __global__ void __launch_bounds__(256) k_gram_uf(const double* __restrict__ Xus, const double* __restrict__ X,
                                                  const double* __restrict__ Yw, double* __restrict__ Kuf,
                                                  double* __restrict__ bpart, const Params* __restrict__ P,
@@ -384,7 +418,7 @@ __global__ void __launch_bounds__(256) k_gram_uf(const double* __restrict__ Xus,
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             int m = I + tm * 4 + a;
-            double v = (m < M && n < N) ? s2 * exp(-0.5 * acc[a][b]) : 0.0;
+            double v = (m < M && n < N) ? s2 * fam_kappa<FAM>(acc[a][b]) : 0.0;
             acc[a][b] = v;
         }
         if (n < N) {
@@ -2811,7 +2845,7 @@ __global__ void __launch_bounds__(256) k_scalars(const double* __restrict__ stat
 // Prediction: mean[s, o] = sum_m K(x*_s, u_m) mu[o*M + m]   (GPnode/UniSGPnode.jl:96-104 batched).
 // One thread per test point, Xus tile and mu staged in LDS.
 // ------------------------------------------------------------------------------------------------
-template <int DT>   // DT > 0: input dimension known at compile time (x stays in registers); DT = 0: runtime D <= MAXD
+template <int DT, int FAM>   // DT > 0: input dimension known at compile time (x stays in registers); DT = 0: runtime D <= MAXD
 __global__ void __launch_bounds__(256) k_predict(const double* __restrict__ Xus, const double* __restrict__ Xs,
                                                  const double* __restrict__ mu, double* __restrict__ mean,
                                                  const Params* __restrict__ P, int M, int Mp, int Drt, int64_t NS, int d_out) {
@@ -2840,7 +2874,7 @@ __global__ void __launch_bounds__(256) k_predict(const double* __restrict__ Xus,
 #pragma unroll
             for (int d = 0; d < DA; ++d)
                 if (d < D) { double t = x[d] - us[d * TB + m]; d2 = fma(t, t, d2); }
-            double k = exp(-0.5 * d2);
+            double k = fam_kappa<FAM>(d2);
 #pragma unroll
             for (int o = 0; o < MAXO; ++o)
                 if (o < d_out) acc[o] = fma(k, ms[o * TB + m], acc[o]);
@@ -2851,6 +2885,7 @@ __global__ void __launch_bounds__(256) k_predict(const double* __restrict__ Xus,
 }
 
 // generic K(A, B): na x nb column-major
+template <int FAM>
 __global__ void __launch_bounds__(256) k_kernelmatrix(const double* __restrict__ A, const double* __restrict__ B,
                                                       double* __restrict__ K, const Params* __restrict__ P,
                                                       int64_t na, int64_t nb, int D) {
@@ -2862,7 +2897,7 @@ __global__ void __launch_bounds__(256) k_kernelmatrix(const double* __restrict__
         double t = (A[(size_t)i * D + d] - B[(size_t)j * D + d]) * P->inv_ell[d];
         d2 = fma(t, t, d2);
     }
-    K[e] = P->sigma2 * exp(-0.5 * d2);
+    K[e] = P->sigma2 * fam_kappa<FAM>(d2);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3178,6 +3213,8 @@ __global__ void __launch_bounds__(256) k_transpose(const double* __restrict__ A,
 // k_theta_grad_uf: one 64 x 64 tile of G K_uf per block on the matrix cores, the contraction with the kernel
 //   derivatives in the epilogue, block partial sums [slot 0: sum Z ; slot 1 + d: sum Z ((x_d - u_d) / ell_d)^2].
 // k_theta_grad_uu: the same contraction of H with the K_uu derivatives.
+// Other families (FAM > 0, see fam_kappa_phi): dk/dell_d = sigma2 phi (x_d - u_d)^2 / ell_d^3, so the slots 1 + d contract
+//   Z' = 2 (omega_n (G k_n)_m - omega_n y_n mu_m) sigma2 phi_mn instead of Z (slot 0 keeps Z: dk/dsigma2 = k / sigma2 holds for all).
 // k_theta_grad_finish: fixed-order sum of the partials (bitwise reproducible) and the chain-rule factors.
 // ------------------------------------------------------------------------------------------------
 constexpr int GRAD_SLOTS = MAXD + 1;
@@ -3188,6 +3225,7 @@ __global__ void __launch_bounds__(256) k_form_G(const double* __restrict__ R, co
     if (e < count) G[e] = R[e] - Kinv[e];
 }
 
+template <int FAM>
 __global__ void __launch_bounds__(256) k_theta_grad_uf(const double* __restrict__ G, const double* __restrict__ Kuf,
                                                        const double* __restrict__ X, const double* __restrict__ Xus,
                                                        const double* __restrict__ Yw, const double* __restrict__ omega,
@@ -3259,9 +3297,20 @@ __global__ void __launch_bounds__(256) k_theta_grad_uf(const double* __restrict_
             for (int r = 0; r < 4; ++r) {
                 const int row = acc_row(lane, wr, ti, r);
                 const double kv = (n < N) ? Kuf[(size_t)n * Mp + I * TB + row] : 0.0;
-                const double v = 2.0 * (om[col] * acc.t[ti][tj][r] - (ks == 0 ? ys[col] * mus[row] : 0.0)) * kv;
-                z[ti][tj][r] = v;
+                const double c = 2.0 * (om[col] * acc.t[ti][tj][r] - (ks == 0 ? ys[col] * mus[row] : 0.0));
+                const double v = c * kv;
                 e0 += v;
+                if constexpr (FAM == 0) {
+                    z[ti][tj][r] = v;
+                } else {
+                    double s = 0.0;                                 // (the direct-difference sum of k_gram_uf)
+                    for (int d = 0; d < D; ++d) { const double t = xs[d * TB + col] - us[d * TB + row]; s = fma(t, t, s); }
+                    double kap, phi;
+                    fam_kappa_phi<FAM>(s, kap, phi);
+                    // K_uf is exactly zero at padded inducing rows and past N, and Z' is to be zero there too; elsewhere
+                    // K_uf = 0 means sigma2 kappa underflowed, and phi with it up to a term below the underflow threshold
+                    z[ti][tj][r] = kv != 0.0 ? c * (P->sigma2 * phi) : 0.0;
+                }
             }
         }
     for (int o = 32; o > 0; o >>= 1) e0 += __shfl_xor(e0, o);
@@ -3291,6 +3340,7 @@ __global__ void __launch_bounds__(256) k_theta_grad_uf(const double* __restrict_
 // one 64 x 64 tile of H o dK_uu per workgroup (grid T x T): the kernel value is computed once per entry, 16 entries per
 // thread stay in registers across the D + 1 contractions.  (A first version re-evaluated the kernel in every pass with
 // 64 workgroups striding over the matrix: 280 us at M = 600 -- a quarter of a training step.)
+template <int FAM>
 __global__ void __launch_bounds__(256) k_theta_grad_uu(const double* __restrict__ H, const double* __restrict__ Xus,
                                                        const Params* __restrict__ P, double* __restrict__ partial,
                                                        int M, int Mp, int D) {
@@ -3308,6 +3358,7 @@ __global__ void __launch_bounds__(256) k_theta_grad_uu(const double* __restrict_
     const int r = tid & 63, c0 = (tid >> 6) * 16;
     const double s2 = P->sigma2;
     double hk[16];
+    double hp[FAM == 0 ? 1 : 16];     // (FAM > 0: h sigma2 phi for the lengthscale slots; SE contracts h k there)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
         double d2 = 0.0;
@@ -3317,7 +3368,14 @@ __global__ void __launch_bounds__(256) k_theta_grad_uu(const double* __restrict_
         }
         const bool in = (I + r < M) && (J + c0 + e < M);
         const double h = H[(size_t)(J + c0 + e) * Mp + I + r];
-        hk[e] = in ? h * (s2 * exp(-0.5 * d2)) : 0.0;
+        if constexpr (FAM == 0) {
+            hk[e] = in ? h * (s2 * exp(-0.5 * d2)) : 0.0;
+        } else {
+            double kap, phi;
+            fam_kappa_phi<FAM>(d2, kap, phi);
+            hk[e] = in ? h * (s2 * kap) : 0.0;
+            hp[e] = in ? h * (s2 * phi) : 0.0;
+        }
     }
     double* out = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * GRAD_SLOTS;
     {
@@ -3333,7 +3391,8 @@ __global__ void __launch_bounds__(256) k_theta_grad_uu(const double* __restrict_
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const double t = a - uj[d * TB + c0 + e];
-            v = fma(hk[e], t * t, v);
+            if constexpr (FAM == 0) v = fma(hk[e], t * t, v);
+            else v = fma(hp[e], t * t, v);
         }
         v = block_sum(v, red);
         if (tid == 0) out[1 + d] = v;

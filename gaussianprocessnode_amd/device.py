@@ -132,10 +132,21 @@ class SGPDevice:
         S = as_f64(np.reshape(S, (self.d_out, self.d_out)))
         self._check(self._lib.sgp_set_output_cov_sum(self._h, ptr(as_f64(S.T))), "sgp_set_output_cov_sum")
 
-    def set_kernel(self, sigma2: float, ell, jitter: float = 0.0):
+    def set_kernel(self, sigma2: float, ell, jitter: float = 0.0, family: Optional[str] = None):
+        """sigma2 * kappa(|(x - x') / ell|); `family` ("se", "matern12", "matern32", "matern52") also sets the kernel family
+        (set_kernel_family), None leaves it as it is (SE on a new handle)."""
+        fam = None if family is None else _lib.family_id(family)
         ell = as_f64(np.atleast_1d(ell))
         self._check(self._lib.sgp_set_kernel(self._h, float(sigma2), ptr(ell), int(ell.size), float(jitter)), "sgp_set_kernel")
         self._n_ell = int(ell.size)          # the C side writes 1 + n_ell gradient entries (sgp_theta_objective)
+        if fam is not None:
+            self._check(self._lib.sgp_set_kernel_family(self._h, fam), "sgp_set_kernel_family")
+
+    def set_kernel_family(self, family) -> None:
+        """Kernel family of every later sweep, prediction and theta objective: a name ("se", "matern12", "matern32",
+        "matern52") or an SGP_KERNEL_* id.  Ids outside 0..3 and a change inside a training run raise SGPError."""
+        fam = family if isinstance(family, (int, np.integer)) else _lib.family_id(family)
+        self._check(self._lib.sgp_set_kernel_family(self._h, int(fam)), "sgp_set_kernel_family")
 
     def set_prior_meancov(self, mu0, Sigma0):
         mu0 = as_f64(np.reshape(mu0, (self.Q,)))
@@ -367,15 +378,21 @@ class SGPDevice:
 
 
 # ---- stand-alone building blocks -------------------------------------------------------------
-def kernelmatrix(A, B, sigma2: float, ell, device: int = 0):
-    """K(A, B) on the device: sigma2 * exp(-0.5 |(a-b)/ell|^2); A (na, D), B (nb, D) -> (na, nb)."""
+def kernelmatrix(A, B, sigma2: float, ell, device: int = 0, family: str = "se"):
+    """K(A, B) on the device: sigma2 * kappa(|(a-b)/ell|) (SE: sigma2 * exp(-0.5 |(a-b)/ell|^2)); A (na, D), B (nb, D) -> (na, nb).
+    `family`: "se", "matern12", "matern32" or "matern52" (or an SGP_KERNEL_* id)."""
+    fam = family if isinstance(family, (int, np.integer)) else _lib.family_id(family)
     lib = _lib.load()
     A = as_f64(np.atleast_2d(A))
     B = as_f64(np.atleast_2d(B))
     ell = as_f64(np.atleast_1d(ell))
     K = np.empty((B.shape[0], A.shape[0]))            # column-major na x nb
-    check(lib.sgp_kernelmatrix(device, ptr(A), A.shape[0], ptr(B), B.shape[0], A.shape[1], float(sigma2), ptr(ell),
-                               int(ell.size), ptr(K)), None, "sgp_kernelmatrix")
+    if int(fam) == _lib.SGP_KERNEL_SE:
+        check(lib.sgp_kernelmatrix(device, ptr(A), A.shape[0], ptr(B), B.shape[0], A.shape[1], float(sigma2), ptr(ell),
+                                   int(ell.size), ptr(K)), None, "sgp_kernelmatrix")
+    else:
+        check(lib.sgp_kernelmatrix_family(device, int(fam), ptr(A), A.shape[0], ptr(B), B.shape[0], A.shape[1], float(sigma2),
+                                          ptr(ell), int(ell.size), ptr(K)), None, "sgp_kernelmatrix_family")
     return K.T.copy()
 
 

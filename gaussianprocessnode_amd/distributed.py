@@ -108,6 +108,13 @@ class HipEngine:
     def stream_context(self):
         return self.torch.cuda.stream(self.stream)
 
+    def set_kernel(self, sigma2, ell, jitter=0.0, family=None):
+        self.dev.set_kernel(sigma2, ell, jitter, family=family)
+
+    def set_kernel_family(self, family):
+        # (every rank of a run sets the same family: the statistics the hook sums are formed with it)
+        self.dev.set_kernel_family(family)
+
     def sweep_local(self):
         self.dev.sweep_local(self.stream.cuda_stream)
 

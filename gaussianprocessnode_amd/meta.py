@@ -7,6 +7,7 @@ compatibility but are not used: the batched device path never materialises per-p
 """
 from __future__ import annotations
 
+import inspect
 import math
 from dataclasses import dataclass, field
 from typing import Callable, Optional
@@ -33,6 +34,43 @@ class SEARDKernel:
         if self.softplus_params:
             theta = softplus(theta)
         return float(theta[0]), theta[1:].copy()
+
+    family = "se"
+
+
+class MaternARDKernel(SEARDKernel):
+    """theta -> (sigma2, lengthscales) for `theta[1] * with_lengthscale(MaternKernel(nu = nu), theta[2:end])`, nu = 1/2
+    (Matern12Kernel = ExponentialKernel), 3/2 (Matern32Kernel) or 5/2 (Matern52Kernel); theta is mapped exactly as
+    SEARDKernel maps it.  `family` names the kernel the device evaluates ("matern12", "matern32", "matern52")."""
+
+    _FAMILIES = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
+
+    def __init__(self, nu: float, softplus_params: bool = False):
+        super().__init__(softplus_params)
+        nu = float(nu)
+        if nu not in self._FAMILIES:
+            raise ValueError(f"MaternARDKernel: nu must be 0.5, 1.5 or 2.5, not {nu}")
+        self.nu = nu
+        self.family = self._FAMILIES[nu]
+
+
+def kernel_family(kernel) -> str:
+    """The family name a kernel callable carries ("se" for a plain callable without a `family` attribute)."""
+    return getattr(kernel, "family", "se")
+
+
+def set_engine_kernel(eng, sigma2, ell, jitter, family: str = "se"):
+    """eng.set_kernel(sigma2, ell, jitter) with the kernel family.  An engine whose set_kernel takes no `family` (an SE-only
+    double) is called as before for SE and refuses the other families (TypeError) rather than evaluating SE."""
+    try:
+        params = inspect.signature(eng.set_kernel).parameters
+    except (TypeError, ValueError):
+        params = {}
+    takes = "family" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+    if takes or family != "se":
+        eng.set_kernel(sigma2, ell, jitter, family=family)
+    else:
+        eng.set_kernel(sigma2, ell, jitter)
 
 
 # ---- GPCache (helper_functions/gp_helperfunction.jl:16-20,78-123) ------------------------------

@@ -24,7 +24,7 @@ import numpy as np
 
 from .distributions import (MvNormalMeanCovariance, MvNormalMeanPrecision, MvNormalWeightedMeanPrecision, PointMass,
                             WishartFast)
-from .meta import MultiSGPMeta
+from .meta import MultiSGPMeta, kernel_family, set_engine_kernel
 from .unisgp import load_batch
 
 
@@ -87,7 +87,7 @@ def sweep(meta: MultiSGPMeta, q_outs: Sequence, q_ins: Sequence, q_w, q_theta: P
     load_batch(eng, pts, ys, None, wts, n_nodes=len(q_ins))
     if cov_sum is not None:
         eng.set_output_cov_sum(cov_sum)
-    eng.set_kernel(sigma2, ell, meta.jitter)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     if E_logdet_W is None:
         E_logdet_W = q_w.mean_logdet() if hasattr(q_w, "mean_logdet") else float(np.linalg.slogdet(W)[1])
     eng.set_noise(W, E_logdet_W)
@@ -126,7 +126,7 @@ def rule_out(q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta) -> MvNormal
         p, w = meta.method.points_weights(*q_in.mean_cov())
     eng = _engine(meta, len(w), d_out)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    eng.set_kernel(sigma2, ell, meta.jitter)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     f = np.atleast_2d(eng.predict(p, np.asarray(q_v.mean(), dtype=np.float64)))      # (S, d_out)
     if f.shape[0] != len(w):
         f = f.T
@@ -145,7 +145,7 @@ def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, 
     X, wts = _test_points(Xstar_or_q_in, meta.method, D)
     eng = _engine(meta, 1, d_out)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    eng.set_kernel(sigma2, ell, meta.jitter)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     if noise:
         eng.set_noise(W)
     mu_v, Sigma_v = q_v.mean_cov()
@@ -167,7 +167,7 @@ def rule_v(q_out, q_in, q_w, q_theta: PointMass, meta: MultiSGPMeta) -> MvNormal
     eng = _engine(meta, len(wts), d_out)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
     load_batch(eng, pts, np.ones((len(wts), d_out)), None, wts, n_nodes=1)
-    eng.set_kernel(sigma2, ell, meta.jitter)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     eng.sweep_local()
     Psi2, B, _ = eng.stats()
     Psi1 = B[:, 0]
@@ -218,7 +218,7 @@ def rule_in(q_out, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, q_in=None):
         X = np.asarray(x, dtype=np.float64).reshape(-1, D_in)
         eng = _aux_engine(meta, len(X))
         eng.set_data(X, np.ones(len(X)), None)
-        eng.set_kernel(sigma2, ell, meta.jitter)
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
         eng.sweep_local()
         eng.set_posterior(s_vec, US)
         I1, I2 = eng.w_stats()
@@ -295,10 +295,11 @@ def rule_theta(q_out, q_in, q_v, q_w, meta: MultiSGPMeta):
         sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(theta, dtype=np.float64)))
         eng = _aux_engine(meta, len(pts))
         eng.set_data(pts, np.ones(len(pts)), None)
-        eng.set_kernel(sigma2, ell, 0.0)
+        set_engine_kernel(eng, sigma2, ell, 0.0, kernel_family(meta.kernel))
         eng.sweep_local()
         eng.set_posterior(s_vec, US)
         I1, I2 = eng.w_stats()
-        tr_kinv = float(np.trace(potri(kernelmatrix(Xu, Xu, sigma2, ell, meta.device), meta.device)))
+        Kuu = kernelmatrix(Xu, Xu, sigma2, ell, meta.device, family=kernel_family(meta.kernel))
+        tr_kinv = float(np.trace(potri(Kuu, meta.device)))
         return float(wts @ (-0.5 * trW * I1 - 0.5 * (I2 - 1.0)) + 0.5e-7 * (trW * tr_kinv - trS))
     return LogPdfClosure(log_backwardmess, multivariate=True)

@@ -11,7 +11,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .distributions import MvNormalMeanCovariance
-from .meta import softplus, split2batch
+from .meta import set_engine_kernel, softplus, split2batch
 
 
 @dataclass
@@ -36,8 +36,16 @@ def sigmoid(x):
     return 1.0 / (1.0 + np.exp(-np.asarray(x, dtype=np.float64)))
 
 
+def _set_family(engine, family):
+    """The kernel family of a device-paced run (its sweeps set no kernel from the host); an engine without families is SE only."""
+    if hasattr(engine, "set_kernel_family"):
+        engine.set_kernel_family(family)
+    elif family != "se":
+        raise TypeError(f"the engine has no kernel families: cannot train with {family!r}")
+
+
 def perform_inference(theta, xtrain, ytrain, Xu, engine, *, batch_size=500, epochs=1, w_val=1e4, prior_var=50.0,
-                      jitter=0.0, optimizer=None, learn_theta=True, device_paced=None):
+                      jitter=0.0, optimizer=None, learn_theta=True, device_paced=None, family="se"):
     """Returns (q_v of the last minibatch, theta) like `PerformInference` (:196-230).  `theta` is the raw
     (pre-softplus) parameter vector of `kernel_gp` (:108); `engine` an SGPDevice sized for `batch_size` points.
 
@@ -45,7 +53,8 @@ def perform_inference(theta, xtrain, ytrain, Xu, engine, *, batch_size=500, epoc
     the optimiser state stay on the device and the loop below only enqueues (sgp_train_* in include/sgp_hip.h); otherwise
     every minibatch goes through the setters, `theta_objective` and the host-side `AdaMax` (the same arithmetic,
     host-paced).  Device-paced, a minibatch whose K_uu or Lambda is not positive definite is skipped and counted; the
-    LinAlgError is raised after the run, not at the failing minibatch."""
+    LinAlgError is raised after the run, not at the failing minibatch.  `family`: the kernel family ("se", "matern12",
+    "matern32", "matern52"; `meta.kernel_family(kernel)`), with theta mapped as for SE."""
     theta = np.array(theta, dtype=np.float64)
     xtrain = np.asarray(xtrain, dtype=np.float64).reshape(len(ytrain), -1)
     Xu = np.asarray(Xu, dtype=np.float64).reshape(-1, xtrain.shape[1])
@@ -57,7 +66,7 @@ def perform_inference(theta, xtrain, ytrain, Xu, engine, *, batch_size=500, epoc
         device_paced = hasattr(engine, "train_begin") and not optimizer._state
     if device_paced:
         return _perform_inference_device(theta, xtrain, ytrain, Xu, engine, batch_size, epochs, w_val, prior_var, jitter,
-                                         optimizer, learn_theta)
+                                         optimizer, learn_theta, family)
     xb, yb = split2batch((xtrain, np.asarray(ytrain, dtype=np.float64)), batch_size)
     engine.set_inducing(Xu)
     engine.set_noise([[w_val]])
@@ -73,7 +82,7 @@ def perform_inference(theta, xtrain, ytrain, Xu, engine, *, batch_size=500, epoc
             if not device_carry:
                 engine.set_prior_meancov(mu, Sigma)
             engine.set_data(xi, yi)
-            engine.set_kernel(float(p[0]), p[1:], jitter)                  # :183-184 (no jitter in training)
+            set_engine_kernel(engine, float(p[0]), p[1:], jitter, family)  # :183-184 (no jitter in training)
             engine.sweep()                                                 # :185-192  infer(iterations = 1)
             if device_carry:
                 engine.carry_posterior()                                   # :212 without leaving the device
@@ -88,7 +97,7 @@ def perform_inference(theta, xtrain, ytrain, Xu, engine, *, batch_size=500, epoc
 
 
 def _perform_inference_device(theta, xtrain, ytrain, Xu, engine, batch_size, epochs, w_val, prior_var, jitter, optimizer,
-                              learn_theta):
+                              learn_theta, family="se"):
     """The same loop with the device pacing itself: one `train_step` per minibatch, an isotropic-prior reset per epoch
     (:203-204); the host waits once, at the end."""
     N = len(ytrain)
@@ -97,6 +106,7 @@ def _perform_inference_device(theta, xtrain, ytrain, Xu, engine, batch_size, epo
     engine.set_inducing(Xu)
     engine.set_noise([[w_val]])
     engine.set_prior_isotropic(prior_var)                                  # :203-204, put back by reset_prior every epoch
+    _set_family(engine, family)
     engine.train_begin(xtrain, ytrain, theta, jitter=jitter, eta=optimizer.eta, beta=optimizer.beta, eps=optimizer.eps)
     for _ in range(epochs):
         for o in range(0, N, batch_size):
@@ -120,7 +130,8 @@ def probit_marginal(y, mz, vz):
     return mz + s * vz * r / np.sqrt(1.0 + vz), vz - vz * vz / (1.0 + vz) * r * (g + r)
 
 
-def vmp_regression(p, xtrain, ytrain, Xu, engine, *, iterations=7, prior_var=50.0, shape=1e-2, rate=1e-2, jitter=1e-8):
+def vmp_regression(p, xtrain, ytrain, Xu, engine, *, iterations=7, prior_var=50.0, shape=1e-2, rate=1e-2, jitter=1e-8,
+                   family="se"):
     """The inner `infer(...)` of experiments/GPT_regression.ipynb's `my_free_energy` (cell 9; model cell 6:
     `v ~ MvNormal(0, 50 I); w ~ Gamma(1e-2, 1e-2); y[i] ~ UniSGP(x[i], v, w, theta)`, mean field q(v) q(w), q(w) initialised
     at its prior, 7 iterations) at the kernel parameters p = (sigma2, lengthscale...) -- BASELINE config 1.  Per iteration:
@@ -131,7 +142,7 @@ def vmp_regression(p, xtrain, ytrain, Xu, engine, *, iterations=7, prior_var=50.
     p = np.asarray(p, dtype=np.float64)
     a, b = float(shape), float(rate)
     engine.set_inducing(Xu)
-    engine.set_kernel(float(p[0]), p[1:], jitter)
+    set_engine_kernel(engine, float(p[0]), p[1:], jitter, family)
     engine.set_prior_isotropic(prior_var)
     engine.set_data(xtrain, np.asarray(ytrain, dtype=np.float64))
     for _ in range(iterations):
@@ -143,7 +154,8 @@ def vmp_regression(p, xtrain, ytrain, Xu, engine, *, iterations=7, prior_var=50.
     return MvNormalMeanCovariance(mu, Sigma), (a, b)
 
 
-def vmp_classification(p, xtrain, ytrain, Xu, engine, *, iterations=30, prior_var=50.0, shape=1e-2, rate=1e-2, jitter=0.0):
+def vmp_classification(p, xtrain, ytrain, Xu, engine, *, iterations=30, prior_var=50.0, shape=1e-2, rate=1e-2, jitter=0.0,
+                       family="se"):
     """The inner `infer(...)` of experiments/GPT_classification.ipynb's `my_free_energy` (cell 9; model cell 7:
     `f[i] ~ UniSGP(x[i], v, w, theta); y[i] ~ Probit(f[i])`, mean field q(f) q(v) q(w), q(v) and q(w) initialised at their
     priors, 30 iterations, K_uu without jitter).  Per iteration: q(f_i) from the :out message N(k_i' mu_v, 1 / mean(q_w))
@@ -155,7 +167,7 @@ def vmp_classification(p, xtrain, ytrain, Xu, engine, *, iterations=30, prior_va
     a, b = float(shape), float(rate)
     mu = np.zeros(Xu.shape[0])
     engine.set_inducing(Xu)
-    engine.set_kernel(float(p[0]), p[1:], jitter)
+    set_engine_kernel(engine, float(p[0]), p[1:], jitter, family)
     engine.set_prior_isotropic(prior_var)
     reuse = getattr(engine, "reuse_stats", False)
     for it in range(iterations):
@@ -175,7 +187,7 @@ def vmp_classification(p, xtrain, ytrain, Xu, engine, *, iterations=30, prior_va
 
 
 def perform_inference_classification(theta, xtrain, ytrain, Xu, engine, *, batch_size=200, epochs=1, prior_var=50.0,
-                                     shape=0.01, rate=0.01, jitter=1e-8, optimizer=None, device_paced=None):
+                                     shape=0.01, rate=0.01, jitter=1e-8, optimizer=None, device_paced=None, family="se"):
     """`PerformInference` of experiments/classification_banana.ipynb (model `f[i] ~ UniSGP(x[i], v, w, theta);
     y[i] ~ Probit(f[i])`, mean-field q(f) q(v) q(w), one VMP iteration per minibatch, q(v) and q(w) carried over every
     minibatch and never reset).  Per minibatch:
@@ -203,7 +215,7 @@ def perform_inference_classification(theta, xtrain, ytrain, Xu, engine, *, batch
         device_paced = hasattr(engine, "train_begin") and not optimizer._state
     if device_paced:
         return _perform_inference_classification_device(theta, xtrain, ytrain, Xu, engine, batch_size, epochs, prior_var, shape,
-                                                        rate, jitter, optimizer)
+                                                        rate, jitter, optimizer, family)
     xb, yb = split2batch((xtrain, ytrain), batch_size)
     a, b = float(shape), float(rate)
     engine.set_inducing(Xu)
@@ -214,7 +226,7 @@ def perform_inference_classification(theta, xtrain, ytrain, Xu, engine, *, batch
         for xi, yi in zip(xb, yb):
             p = softplus(theta)
             w0 = a / b
-            engine.set_kernel(float(p[0]), p[1:], jitter)
+            set_engine_kernel(engine, float(p[0]), p[1:], jitter, family)
             mz = engine.predict(xi, mu if first else None)             # k_i' mu_v with the carried posterior mean
             mf, vf = probit_marginal(yi, mz, 1.0 / w0)
             engine.set_data(xi, mf, vf)
@@ -232,12 +244,13 @@ def perform_inference_classification(theta, xtrain, ytrain, Xu, engine, *, batch
 
 
 def _perform_inference_classification_device(theta, xtrain, ytrain, Xu, engine, batch_size, epochs, prior_var, shape, rate, jitter,
-                                             optimizer):
+                                             optimizer, family="se"):
     """The same loop paced by the device: one `train_step` per minibatch (window of the resident set; the forward message, the
     Probit moments, the Gamma update and AdaMax are kernels between the sweep's own), the host waits once, at the end."""
     N = len(ytrain)
     engine.set_inducing(Xu)
     engine.set_prior_isotropic(prior_var)                                  # q(v) starts at its prior and is never reset
+    _set_family(engine, family)
     engine.train_begin(xtrain, ytrain, theta, jitter=jitter, eta=optimizer.eta, beta=optimizer.beta, eps=optimizer.eps,
                        likelihood="probit", gamma=(shape, rate))
     for _ in range(epochs):

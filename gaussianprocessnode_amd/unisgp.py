@@ -25,7 +25,7 @@ import numpy as np
 
 from .distributions import (GammaShapeRate, MvNormalMeanCovariance, MvNormalMeanPrecision,
                             MvNormalWeightedMeanPrecision, NormalMeanPrecision, NormalMeanVariance, PointMass)
-from .meta import UniSGPMeta
+from .meta import UniSGPMeta, kernel_family, set_engine_kernel
 
 LOG2PI = math.log(2.0 * math.pi)
 
@@ -166,7 +166,7 @@ def prod(left, right: BufferUniSGP):
     eng = _engine(meta, len(y))
     sigma2, ell = meta.kernel(meta._batch["theta"])
     load_batch(eng, X, y, vy, wts, n_nodes=meta.N)
-    eng.set_kernel(sigma2, ell, meta.jitter)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     eng.set_noise([[meta._batch["w"]]], meta._batch["E_logw"])
     prior = meta._prior
     if extra_precision:
@@ -218,7 +218,7 @@ def _stats_at(meta: UniSGPMeta, theta, X, y, vy, mu_v, Uv):
     eng = _aux_engine(meta, len(y))
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(theta, dtype=np.float64)))
     eng.set_data(X, y, vy)
-    eng.set_kernel(sigma2, ell, meta.jitter)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     eng.sweep_local()
     eng.set_posterior(mu_v, Uv)
     return eng.w_stats()
@@ -308,7 +308,7 @@ def predict(Xstar, q_v, q_theta, meta: UniSGPMeta) -> np.ndarray:
         Xstar = Xstar[:, None]
     eng = _engine(meta, 1)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    eng.set_kernel(sigma2, ell, meta.jitter)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     return eng.predict(Xstar, np.asarray(q_v.mean(), dtype=np.float64))
 
 
@@ -348,7 +348,7 @@ def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool =
     X, wts = _test_points(Xstar_or_q_in, meta.method, D)
     eng = _engine(meta, 1)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    eng.set_kernel(sigma2, ell, meta.jitter)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     if noise:
         eng.set_noise([[_mean_w(q_w)]], _elog_w(q_w))
     mu_v, Sigma_v = q_v.mean_cov()

@@ -107,10 +107,28 @@ int sgp_set_targets(sgp_handle* h, const double* y_mean, const double* y_var);
  * (d_out x d_out), the Sigma_y term of `Ry = Sigma_y + mu_y mu_y'` (GPnode/MultiSGPnode.jl:398-401,566).  Call after
  * sgp_set_data (which resets it to zero). */
 int sgp_set_output_cov_sum(sgp_handle* h, const double* S);
-/* sgp_set_kernel: kernel(theta) = sigma2 * with_lengthscale(SEKernel(), ell)
+/* sgp_set_kernel: kernel(theta) = sigma2 * with_lengthscale(SEKernel(), ell) -- or another family, sgp_set_kernel_family
  * (GPtest.jl:21; experiments/regression_kin40k.ipynb:108).  n_ell = 1 (isotropic) or D (ARD).
  * jitter is added to diag(K_uu) (0 in kin40k training :183, 1e-8 at prediction :297 and in banana). */
 int sgp_set_kernel(sgp_handle* h, double sigma2, const double* ell, int32_t n_ell, double jitter);
+/* Kernel families (KernelFunctions.jl, `with_lengthscale` divides the inputs by ell):  with s = sum_d ((a_d - b_d) / ell_d)^2
+ * and r = sqrt(s),  k = sigma2 kappa(r)  with
+ *   SGP_KERNEL_SE        kappa = exp(-s / 2)                                  (SEKernel)
+ *   SGP_KERNEL_MATERN12  kappa = exp(-r)                                      (Matern12Kernel = ExponentialKernel)
+ *   SGP_KERNEL_MATERN32  kappa = (1 + sqrt(3) r) exp(-sqrt(3) r)              (Matern32Kernel)
+ *   SGP_KERNEL_MATERN52  kappa = (1 + sqrt(5) r + 5 s / 3) exp(-sqrt(5) r)    (Matern52Kernel)
+ * k(x, x) = sigma2 for all four. */
+#define SGP_KERNEL_SE       0
+#define SGP_KERNEL_MATERN12 1
+#define SGP_KERNEL_MATERN32 2
+#define SGP_KERNEL_MATERN52 3
+/* sgp_set_kernel_family: the family every later sweep, prediction and theta objective of this handle evaluates, with the
+ * parameters of sgp_set_kernel (sigma2, ell and jitter mean the same for every family).  The default is SGP_KERNEL_SE: a
+ * handle that never calls this evaluates exactly what it did before the families existed.  Waits for work in flight like
+ * sgp_set_kernel.  SGP_ERR_ARG for an unknown id, and between sgp_train_begin and sgp_train_end.  A change of family
+ * invalidates the statistics SGP_FLAG_REUSE_STATS keeps and sgp_theta_objective's reuse of the last sweep.  In a data-sharded
+ * run every rank sets the same family. */
+int sgp_set_kernel_family(sgp_handle* h, int32_t family);
 /* sgp_set_prior: `v ~ MvNormalMeanCovariance(mu_v, Sigma_v)` (experiments/regression_kin40k.ipynb:148).
  * form: 0 = mean + covariance, 1 = weighted mean xi0 + precision Lambda0, 2 = isotropic N(0, s I) with
  * s = mat[0] (the notebook's per-epoch reset 50 I, :203-204).  Vectors have d_out*M entries. */
@@ -133,7 +151,7 @@ int sgp_sweep_finish(sgp_handle* h, void* stream);
 int sgp_sweep(sgp_handle* h, void* stream);                 /* local + [all-reduce hook] + finish */
 /* What a sgp_sweep does on a handle created with SGP_FLAG_REUSE_STATS (both FULL, always, without the flag):
  *   SGP_SWEEP_FULL     the whole sweep above: after sgp_set_data, sgp_set_inducing, a changed kernel value (sigma2, a lengthscale,
- *                      the jitter), sgp_theta_objective at another theta, sgp_train_*, sgp_time_kernel, sgp_bind_stats,
+ *                      the jitter, the kernel family), sgp_theta_objective at another theta, sgp_train_*, sgp_time_kernel, sgp_bind_stats,
  *                      sgp_set_allreduce / sgp_use_rccl, a direct sgp_sweep_local, or a full sweep whose K_uu factorisation failed or
  *                      whose stream hand-off gave up;
  *   SGP_SWEEP_TARGETS  after sgp_set_targets or sgp_set_output_cov_sum: B and the data scalars from the resident K_uf (with an
@@ -299,6 +317,9 @@ int sgp_train_end(sgp_handle* h, double* theta_raw, int64_t* counts /* 2 */);
  * GPnode/UniSGPnode.jl:102,153; A is D x na, B is D x nb, K is na x nb column-major. */
 int sgp_kernelmatrix(int32_t device, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
                      double sigma2, const double* ell, int32_t n_ell, double* K);
+/* the same for any kernel family (SGP_KERNEL_*): K = sigma2 kappa(|(a - b) / ell|) */
+int sgp_kernelmatrix_family(int32_t device, int32_t family, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
+                            double sigma2, const double* ell, int32_t n_ell, double* K);
 /* dense FP64 factorisations on the device (fastcholesky / cholinv call sites: GPnode/UniSGPnode.jl:68,
  * experiments/regression_kin40k.ipynb:184): A is n x n column-major symmetric; L lower; Ainv full. */
 int sgp_potrf(int32_t device, const double* A, int32_t n, double* L);

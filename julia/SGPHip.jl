@@ -25,6 +25,7 @@
 module SGPHip
 
 using ReactiveMP, LinearAlgebra
+import KernelFunctions                         # (the kernel family of a kernel object, kernel_family_id)
 import Optim                                   # (the reference's MultiSGP(:in) Laplace rule uses it, GPnode/MultiSGPnode.jl:229)
 import ReactiveMP: @rule, @average_energy, @call_rule, GenericProd, PointMass, MvNormalMeanCovariance,
                    MvNormalMeanPrecision, MvNormalWeightedMeanPrecision, NormalMeanPrecision, GammaShapeRate, Wishart,
@@ -46,6 +47,19 @@ end
 const SGP_FLAG_KEEP_KUF = Int32(2)
 const SGP_FLAG_REUSE_STATS = Int32(16)
 const SGP_SWEEP_FULL, SGP_SWEEP_TARGETS, SGP_SWEEP_REUSED = 0, 1, 2
+const SGP_KERNEL_SE, SGP_KERNEL_MATERN12, SGP_KERNEL_MATERN32, SGP_KERNEL_MATERN52 = Int32(0), Int32(1), Int32(2), Int32(3)
+
+# the kernel family (include/sgp_hip.h, SGP_KERNEL_*) of a `kernel_family` argument: a name (:se, :matern12, :matern32,
+# :matern52), an id, or the kernel object kernel(θ) returns (σ² * with_lengthscale(base, ℓ): the base kernel decides)
+kernel_family_id(i::Integer) = Int32(i)
+kernel_family_id(s::Symbol) = Dict(:se => SGP_KERNEL_SE, :matern12 => SGP_KERNEL_MATERN12, :matern32 => SGP_KERNEL_MATERN32,
+                                   :matern52 => SGP_KERNEL_MATERN52)[s]
+kernel_family_id(k::KernelFunctions.ScaledKernel) = kernel_family_id(k.kernel)
+kernel_family_id(k::KernelFunctions.TransformedKernel) = kernel_family_id(k.kernel)
+kernel_family_id(::KernelFunctions.SqExponentialKernel) = SGP_KERNEL_SE             # SEKernel
+kernel_family_id(::KernelFunctions.ExponentialKernel) = SGP_KERNEL_MATERN12         # Matern12Kernel
+kernel_family_id(::KernelFunctions.Matern32Kernel) = SGP_KERNEL_MATERN32
+kernel_family_id(::KernelFunctions.Matern52Kernel) = SGP_KERNEL_MATERN52
 const SGP_S_COUNT = 8
 const SGP_R_COUNT = 8
 
@@ -58,16 +72,18 @@ end
 mutable struct Handle
     ptr::Ptr{Cvoid}
     m::Int; d::Int; d_out::Int; n_max::Int
+    family::Int32                     # kernel family (sgp_set_kernel_family), set once at creation
 end
 
-function Handle(n_max, Xu::Matrix{Float64}, d_out; device = 0, flags = SGP_FLAG_KEEP_KUF)
+function Handle(n_max, Xu::Matrix{Float64}, d_out; device = 0, flags = SGP_FLAG_KEEP_KUF, family = SGP_KERNEL_SE)
     D, M = size(Xu)                                            # D × M column-major = M points of D doubles: the ABI layout
     cfg = Ref(SGPConfig(n_max, M, D, d_out, device, flags, 0))
     p = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:sgp_create, LIB), Cint, (Ref{SGPConfig}, Ref{Ptr{Cvoid}}), cfg, p), C_NULL)
-    h = Handle(p[], M, D, d_out, n_max)
-    check(ccall((:sgp_set_inducing, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, Xu), h.ptr)
+    h = Handle(p[], M, D, d_out, n_max, Int32(family))
     finalizer(x -> ccall((:sgp_destroy, LIB), Cint, (Ptr{Cvoid},), x.ptr), h)
+    check(ccall((:sgp_set_inducing, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, Xu), h.ptr)
+    check(ccall((:sgp_set_kernel_family, LIB), Cint, (Ptr{Cvoid}, Int32), h.ptr, h.family), h.ptr)
     return h
 end
 
@@ -161,11 +177,12 @@ function potri(A::Matrix{Float64}; device = 0)
     check(ccall((:sgp_potri, LIB), Cint, (Int32, Ptr{Float64}, Int32, Ptr{Float64}), device, A, n, Ai), C_NULL)
     return Ai
 end
-function kernelmatrix_dev(A::Matrix{Float64}, B::Matrix{Float64}, σ², ℓ::Vector{Float64}; device = 0)      # A: D × na, B: D × nb
+function kernelmatrix_dev(A::Matrix{Float64}, B::Matrix{Float64}, σ², ℓ::Vector{Float64}; device = 0,
+                          kernel_family = SGP_KERNEL_SE)                                     # A: D × na, B: D × nb
     K = zeros(size(A, 2), size(B, 2))
-    check(ccall((:sgp_kernelmatrix, LIB), Cint,
-                (Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Int32, Ptr{Float64}),
-                device, A, size(A, 2), B, size(B, 2), size(A, 1), σ², ℓ, length(ℓ), K), C_NULL)
+    check(ccall((:sgp_kernelmatrix_family, LIB), Cint,
+                (Int32, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Int32, Ptr{Float64}),
+                device, kernel_family_id(kernel_family), A, size(A, 2), B, size(B, 2), size(A, 1), σ², ℓ, length(ℓ), K), C_NULL)
     return K
 end
 
@@ -194,11 +211,15 @@ mutable struct HipSGPMeta{R<:UniSGPMeta}
     μ_last::Vector{Float64}           # mean of the last swept q(v): the per-point pass belongs to it
 end
 
-function HipSGPMeta(ref::UniSGPMeta; kernel_params, jitter = 0.0, device = 0, cubature_points = 21, reuse_stats = false)
+function HipSGPMeta(ref::UniSGPMeta; kernel_params, jitter = 0.0, device = 0, cubature_points = 21, reuse_stats = false,
+                    kernel_family = :se)
     # (uncertain inputs enter the sweep as `cubature_points` weighted points per node: size the handle for them)
     # reuse_stats: SGP_FLAG_REUSE_STATS -- sweeps at unchanged kernel and inputs reuse K_uf, Psi2 and the K_uu factor
+    # kernel_family: the base kernel of ref.kernel(θ) (:se, :matern12, :matern32, :matern52, or a kernel object such as
+    # ref.kernel(θ0)); kernel_params maps θ exactly as for SE
     flags = SGP_FLAG_KEEP_KUF | (reuse_stats ? SGP_FLAG_REUSE_STATS : 0)
-    h = Handle(ref.N * max(1, cubature_points), inducing_matrix(ref.Xu), 1; device = device, flags = flags)
+    h = Handle(ref.N * max(1, cubature_points), inducing_matrix(ref.Xu), 1; device = device, flags = flags,
+               family = kernel_family_id(kernel_family))
     return HipSGPMeta(ref, h, kernel_params, Float64(jitter), Vector{Float64}[], Float64[], Float64[], nothing, 1.0, 0.0,
                       Float64[], Dict{Vector{Float64},Int}(), Float64[], Float64[], Float64[], false, nothing, device, Float64[])
 end
@@ -323,7 +344,7 @@ end
 # auxiliary handle: the main one holds the last swept batch.
 function aux_handle!(meta::HipSGPMeta, n::Int)
     if meta.aux === nothing || meta.aux.n_max < n
-        meta.aux = Handle(max(n, 64), inducing_matrix(meta.ref.Xu), 1; device = meta.device)
+        meta.aux = Handle(max(n, 64), inducing_matrix(meta.ref.Xu), 1; device = meta.device, family = meta.handle.family)
     end
     return meta.aux
 end
@@ -481,11 +502,12 @@ mutable struct HipMultiSGPMeta{R<:MultiSGPMeta}
     device::Int
 end
 
-function HipMultiSGPMeta(ref::MultiSGPMeta, d_out::Int; kernel_params, n_steps, jitter = 0.0, device = 0)
+function HipMultiSGPMeta(ref::MultiSGPMeta, d_out::Int; kernel_params, n_steps, jitter = 0.0, device = 0, kernel_family = :se)
     Xu = inducing_matrix(ref.Xu)
     npts = 2 * size(Xu, 1) + 1                                 # srcubature: 2 d_in + 1 points per step
-    return HipMultiSGPMeta(ref, d_out, Handle(n_steps * npts, Xu, d_out; device = device), Handle(npts, Xu, 1; device = device),
-                           kernel_params, Float64(jitter), nothing, device)
+    fam = kernel_family_id(kernel_family)                      # (as HipSGPMeta)
+    return HipMultiSGPMeta(ref, d_out, Handle(n_steps * npts, Xu, d_out; device = device, family = fam),
+                           Handle(npts, Xu, 1; device = device, family = fam), kernel_params, Float64(jitter), nothing, device)
 end
 
 # cubature points / weights of q_in as the reference's approximate_kernel_expectation! walks them (GPnode/MultiSGPnode.jl:11-35)
@@ -565,7 +587,7 @@ function second_moment_contraction(q_out, q_v, W, M)
 end
 function aux_handle!(meta::HipMultiSGPMeta, n::Int)
     if meta.aux === nothing || meta.aux.n_max < n
-        meta.aux = Handle(max(n, 64), inducing_matrix(meta.ref.Xu), 1; device = meta.device)
+        meta.aux = Handle(max(n, 64), inducing_matrix(meta.ref.Xu), 1; device = meta.device, family = meta.handle.family)
     end
     return meta.aux
 end
@@ -618,7 +640,8 @@ end
     log_backwardmess = (θ) -> begin
         σ², ℓ = meta.kernel_params(θ)
         I1, I2 = pseudo_stats(meta, X, σ², ℓ, 0.0, s, US)
-        tr_kinv = tr(potri(kernelmatrix_dev(Xu, Xu, σ², collect(Float64, ℓ); device = meta.device); device = meta.device))
+        tr_kinv = tr(potri(kernelmatrix_dev(Xu, Xu, σ², collect(Float64, ℓ); device = meta.device,
+                                                 kernel_family = meta.handle.family); device = meta.device))
         dot(ω, -0.5 * trW .* I1 .- 0.5 .* (I2 .- 1.0)) + 0.5e-7 * (trW * tr_kinv - trS)
     end
     return ContinuousMultivariateLogPdf(UnspecifiedDomain(), log_backwardmess)

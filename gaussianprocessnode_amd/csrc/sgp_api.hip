@@ -122,6 +122,7 @@ struct sgp_handle {
     double *dLambda0 = nullptr, *dXi0 = nullptr, *dOut = nullptr, *dWishart = nullptr, *dTrace = nullptr, *dTmp = nullptr;
     double *dPa = nullptr, *dPb = nullptr, *dKmu = nullptr, *dUvT = nullptr, *dScratch = nullptr, *dOut2 = nullptr, *dUvWork = nullptr;
     double *dGradM = nullptr, *dGradPart = nullptr, *dGrad = nullptr;   // theta-gradient scratch (allocated on first use)
+    double* dThetaMulti = nullptr; // MultiSGP theta objective scratch (first use): R from Uv, omega W y, padded mu, G column shares
     double* dSaccK = nullptr;      // K_uu chain: Sigma-style accumulator of K_uu^-1 = W_K^T W_K (see sigma_row_tile)
     long long gate_epoch = 0;      // value the sweep's SYRK stores into the gate word
     int spin_limit = JOIN_SPIN_LIMIT;   // polls before a bounded device-word wait gives up (SGP_SPIN_LIMIT: tests shorten it)
@@ -635,7 +636,7 @@ extern "C" int sgp_destroy(sgp_handle* h) {
                     h->dDataScal, h->dKuu, h->dWk, h->dKinv, h->dLam, h->dWl, h->dSigma, h->dR, h->dTmp, h->dLambda0,
                     h->dXi, h->dMu, h->dXi0, h->dOut, h->dWishart, h->dTrace, h->dInfo, h->dStamps, h->dParams, h->dPa,
                     h->dUvT, h->dScratch, h->dParamsK, h->dXusK, h->dOut2, h->dStampTotals, h->dUvWork,
-                    h->dGradM, h->dGradPart, h->dGrad, h->dCall, h->dSaccK,
+                    h->dGradM, h->dGradPart, h->dGrad, h->dCall, h->dSaccK, h->dThetaMulti,
                     h->dTrainX, h->dTrainY, h->dTrain, h->dTrainParams, h->dJoin, h->dPack, h->dBred};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->hParams) hipHostFree(h->hParams);
@@ -2285,7 +2286,7 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
 // analytic gradient w.r.t. (sigma2, ell_1 .. ell_n_ell) of the objective at the resident K_uf, Psi2, K_uu^-1, R and mu, into
 // h->dGrad: one G K_uf GEMM contracted with the kernel derivatives in its
 // epilogue, plus the K_uu term through H = Kinv Psi2 Kinv (see k_theta_grad_* in sgp_kernels.hip.h)
-static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
+static int alloc_theta_grad(sgp_handle* h) {
     const int Mp = h->Mp, T = h->T;
     const int nblk_max = (int)((h->n_max + TB - 1) / TB);
     if (!h->dGradM) {
@@ -2294,6 +2295,24 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
                             sizeof(double) * ((size_t)std::max(std::max(nblk_max, 1) * T, 512 + T) + (size_t)T * T) * GRAD_SLOTS));
         HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dGrad), sizeof(double) * 2 * GRAD_SLOTS));
     }
+    return 0;
+}
+
+// MultiSGP scratch: [R: Qp x Qp | Uv: Qp x Qp | omega W y: d_out x n_max | padded mu: d_out x Mp | G column shares: Mp]
+static size_t theta_multi_doubles(const sgp_handle* h) {
+    return 2 * (size_t)h->Qp * h->Qp + (size_t)h->dout * (size_t)std::max<int64_t>(h->n_max, 1) + (size_t)h->dout * h->Mp + h->Mp;
+}
+
+// tr(W) of the current mean(q_W), summed in the same order wherever it is used
+static double theta_trace_W(const sgp_handle* h) {
+    double t = 0.0;
+    for (int d = 0; d < h->dout; ++d) t += h->hParams->W[d + d * h->dout];
+    return t;
+}
+
+static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
+    const int Mp = h->Mp, T = h->T;
+    if (int arc = alloc_theta_grad(h)) return arc;
     double* dG = h->dGradM;
     double* dT1 = dG + (size_t)Mp * Mp;
     double* dH = dT1 + (size_t)Mp * Mp;
@@ -2322,12 +2341,30 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
                            Mp, h->D);
     });
     if (split) hipLaunchKernelGGL(k_join_set, dim3(1), dim3(64), 0, su, h->dJoin + WORD_GRAD, ++h->grad_epoch);
-    hipLaunchKernelGGL(k_form_G, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, h->dR, h->dKinv, dG, cnt);
-    if (h->n > 0)
+    if (h->dout == 1) {
+        hipLaunchKernelGGL(k_form_G, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, h->dR, h->dKinv, dG, cnt);
+        if (h->n > 0)
+            by_family(h->family, [&](auto F) {
+                hipLaunchKernelGGL(k_theta_grad_uf<decltype(F)::value>, dim3(h->nblk, T, KS), dim3(256), 0, s, dG, h->dKuf, h->dX,
+                                   h->dXus, h->dYw, h->has_omega ? h->dOmega : nullptr, h->dMu, h->dParams, part_uf, Mp, T, h->D, h->n);
+            });
+    } else if (h->n > 0) {
+        // MultiSGP: G (= S - tr(W) K_uu^-1), omega W y and the padded mean columns were formed by enqueue_theta_multi_value
+        const double* cw = h->dThetaMulti + 2 * (size_t)h->Qp * h->Qp;
+        const double* mup = cw + (size_t)h->dout * (size_t)std::max<int64_t>(h->n_max, 1);
         by_family(h->family, [&](auto F) {
-            hipLaunchKernelGGL(k_theta_grad_uf<decltype(F)::value>, dim3(h->nblk, T, KS), dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus,
-                               h->dYw, h->has_omega ? h->dOmega : nullptr, h->dMu, h->dParams, part_uf, Mp, T, h->D, h->n);
+            constexpr int FAM = decltype(F)::value;
+            const dim3 grid(h->nblk, T, KS);
+            switch (h->dout) {
+                case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_theta_grad_uf<FAM, 2>), grid, dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus, cw,
+                                           h->has_omega ? h->dOmega : nullptr, mup, h->dParams, part_uf, Mp, T, h->D, h->n); break;
+                case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_theta_grad_uf<FAM, 3>), grid, dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus, cw,
+                                           h->has_omega ? h->dOmega : nullptr, mup, h->dParams, part_uf, Mp, T, h->D, h->n); break;
+                default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_theta_grad_uf<FAM, 4>), grid, dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus, cw,
+                                            h->has_omega ? h->dOmega : nullptr, mup, h->dParams, part_uf, Mp, T, h->D, h->n); break;
+            }
         });
+    }
     // Data-sharded run (an all-reduce hook is installed; the statistics in dStats are the reduced ones): the data half above used
     // this rank's K_uf, X and y -- its fixed-order total (1 + D doubles) is summed over the ranks through the same hook; the
     // K_uu half and the s_w term come from the reduced statistics and are replicated.  Every rank ends with the whole gradient.
@@ -2340,10 +2377,88 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
         uf_src = tot;
         uf_blocks = 1;
     }
-    hipLaunchKernelGGL(k_theta_grad_finish, dim3(1), dim3(256), 0, s, uf_src, uf_blocks, part_uu, T * T,
-                       h->dStats + (size_t)Mp * Mp + (size_t)Mp * h->dout, h->dParams, h->dGrad, h->D, h->n_ell,
-                       split ? (const long long*)(h->dJoin + WORD_GRAD) : (const long long*)nullptr, h->grad_epoch, h->spin_limit,
-                       h->dInfo + 3);
+    if (h->dout == 1)
+        hipLaunchKernelGGL(k_theta_grad_finish<false>, dim3(1), dim3(256), 0, s, uf_src, uf_blocks, part_uu, T * T,
+                           h->dStats + (size_t)Mp * Mp + (size_t)Mp * h->dout, h->dParams, h->dGrad, h->D, h->n_ell,
+                           split ? (const long long*)(h->dJoin + WORD_GRAD) : (const long long*)nullptr, h->grad_epoch, h->spin_limit,
+                           h->dInfo + 3, 0.0);
+    else
+        hipLaunchKernelGGL(k_theta_grad_finish<true>, dim3(1), dim3(256), 0, s, uf_src, uf_blocks, part_uu, T * T,
+                           h->dStats + (size_t)Mp * Mp + (size_t)Mp * h->dout, h->dParams, h->dGrad, h->D, h->n_ell,
+                           split ? (const long long*)(h->dJoin + WORD_GRAD) : (const long long*)nullptr, h->grad_epoch, h->spin_limit,
+                           h->dInfo + 3, theta_trace_W(h));
+    return 0;
+}
+
+// ---- MultiSGP (d_out = 2..4): neg_log_backwardmess_multi (helper_functions/derivative_helper.jl:92-106) and its gradient ----
+// the value on `s`, into dGrad[GRAD_SLOTS]: R_v (the last sweep's dR, or Uv^T Uv of sgp_set_posterior in call scratch), then
+// omega W y and the padded mean columns, G = S - tr(W) K_uu^-1 with the column shares of tr(G Psi2), and the fixed-order value.
+// W is the CURRENT mean(q_W) (a sgp_set_noise since the sweep is honoured), passed by value; sigma2 and ell are read from the
+// main stream's mirror, which holds the current values on both paths (fresh: the sweep's, equal to them; re-evaluated: mirrored).
+static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s) {
+    if (int arc = alloc_theta_grad(h)) return arc;
+    if (!h->dThetaMulti)
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dThetaMulti), sizeof(double) * theta_multi_doubles(h)));
+    const int M = h->M, Mp = h->Mp, Qp = h->Qp, TQ = h->TQ, dout = h->dout;
+    const size_t nmax = (size_t)std::max<int64_t>(h->n_max, 1);
+    double* dRs = h->dThetaMulti;
+    double* dUv = dRs + (size_t)Qp * Qp;
+    double* cw = dUv + (size_t)Qp * Qp;
+    double* mup = cw + (size_t)dout * nmax;
+    double* part = mup + (size_t)dout * Mp;
+    OutMat W{};
+    for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
+    const double* R = h->dR;
+    if (h->posterior_set) {     // R_v = Uv^T Uv: dUvT holds Uv^T (identity-padded); the pad rows / columns are not read
+        hipLaunchKernelGGL(k_transpose, dim3(TQ, TQ), dim3(256), 0, s, (const double*)h->dUvT, dUv, Qp);
+        hipLaunchKernelGGL(k_gemm32, dim3(TQ * TQ * 4), dim3(256), 0, s, (const double*)h->dUvT, (const double*)dUv, dRs, Qp, TQ,
+                           3, 0, 0, (const double*)nullptr, (double*)nullptr, (const double*)nullptr, (const double*)nullptr,
+                           (double*)nullptr, UvArgs{}, (const double*)nullptr);
+        R = dRs;
+    }
+    const int64_t nprep = std::max<int64_t>(h->n, Mp);
+    hipLaunchKernelGGL(k_theta_multi_prep, dim3((unsigned)((nprep + 255) / 256)), dim3(256), 0, s, (const double*)h->dYw,
+                       (const double*)h->dMu, W, cw, mup, h->n, M, Mp, dout);
+    const double trW = theta_trace_W(h);
+    hipLaunchKernelGGL(k_form_G_multi, dim3(Mp), dim3(256), 0, s, R, Qp, (const double*)h->dKinv, (const double*)h->dStats,
+                       W, trW, h->dGradM, part, M, Mp, dout);
+    hipLaunchKernelGGL(k_theta_value_multi, dim3(1), dim3(256), 0, s, (const double*)part, (const double*)h->dStats,
+                       (const double*)mup, (const Params*)h->dParams, W, trW, h->dGrad + GRAD_SLOTS, Mp, dout);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// MultiSGP objective: fresh (the statistics, K_uu^-1 and q(v) of the last sweep at the current kernel) or re-evaluated (K_uu
+// chain and local statistics at the current theta, as theta_objective_eval); then value and, with grad, the gradient
+static int theta_objective_multi(sgp_handle* h, hipStream_t s, bool fresh, double* value, double* grad) {
+    if (fresh) {
+        double out[SGP_R_COUNT];
+        HIPCHK(h, hipMemcpy(out, h->dOut, sizeof out, hipMemcpyDeviceToHost));
+        if (out[SGP_R_INFO_KUU] > 0) { h->err = "K_uu is not positive definite"; return (int)out[SGP_R_INFO_KUU]; }
+    } else {
+        h->stats_dirty = true;                   // the statistics now belong to the NEW theta, not to q(v)'s sweep
+        h->rec.valid = false;
+        h->swept_local = true;
+        enqueue_kuu(h, s, false);
+        enqueue_local(h, s, false);
+        h->main_prep_gen = 0;
+        HIPCHK(h, hipStreamSynchronize(s));
+        HIPCHK(h, hipGetLastError());
+        int info = 0;
+        HIPCHK(h, hipMemcpy(&info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
+        if (info < 0) return fail(h, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
+        if (info > 0) { h->err = "K_uu is not positive definite"; return info; }
+    }
+    if (int vrc = enqueue_theta_multi_value(h, s)) return vrc;
+    if (grad)
+        if (int grc = enqueue_theta_grad(h, s)) return grc;
+    HIPCHK(h, wait_stream(s));
+    HIPCHK(h, hipGetLastError());
+    double res[GRAD_SLOTS + 1];
+    HIPCHK(h, hipMemcpy(res, h->dGrad, sizeof res, hipMemcpyDeviceToHost));
+    *value = res[GRAD_SLOTS];
+    if (grad)
+        for (int i = 0; i <= h->n_ell; ++i) grad[i] = res[i];
     return 0;
 }
 
@@ -2374,9 +2489,11 @@ static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value) {
 
 extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
     if (!h || !value) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: null argument");
-    if (!h->swept || h->dout != 1) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: needs a finished UniSGP sweep (q(v))");
+    if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: needs a finished sweep or sgp_set_posterior (q(v))");
     if (!h->have_data || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: data and kernel must be set");
     if (h->training) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: a device-paced training run is open (sgp_train_end first)");
+    if (h->dout > 1 && h->allreduce)
+        return fail(h, SGP_ERR_ARG, "sgp_theta_objective: data-sharded MultiSGP theta objectives are not supported (remove the hook)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, drain_device(h));
     h->in_flight = false;
@@ -2394,6 +2511,7 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
     // the objective is linear in w: a new mean(q_w) (classification_banana.ipynb passes the UPDATED q(w)) only rescales it
     const double wscale = fresh ? h->hParams->W[0] / h->swept_params.W[0] : 1.0;
     for (int d = 0; d < h->D && fresh; ++d) fresh = h->swept_params.inv_ell[d] == h->hParams->inv_ell[d];
+    if (h->dout > 1) return theta_objective_multi(h, s, fresh, value, grad);
     int rc = 0;
     if (fresh) {
         double out[SGP_R_COUNT], sc[SGP_S_COUNT];

@@ -3225,7 +3225,94 @@ __global__ void __launch_bounds__(256) k_form_G(const double* __restrict__ R, co
     if (e < count) G[e] = R[e] - Kinv[e];
 }
 
-template <int FAM>
+// ---- MultiSGP (d_out = 2..4) -------------------------------------------------------------------
+// neg_log_backwardmess_multi (helper_functions/derivative_helper.jl:92-106) with q(v) (mu_v = [mu^(1); ..], R_v = Sigma_v +
+// mu_v mu_v^T, blocks R^(ij)) and W = mean(q_W) fixed, S = sum_ij W_ij R^(ij), c_n = W y_n:
+//   f  = 1/2 tr(W) (sigma2 s_w - tr(K_uu^-1 Psi2)) + 1/2 tr(S Psi2) - sum_de W_de mu^(d)' B_e
+//      = 1/2 [ tr(W) sigma2 s_w + tr(G Psi2) ] - sum_de W_de mu^(d)' B_e ,          G = S - tr(W) K_uu^-1
+//   df = 1/2 [ tr(W) s_w dsigma2 + sum_mn Z_mn dKuf_mn / Kuf_mn + tr(W) sum_mm' H_mm' dKuu_mm' ],
+//   Z_mn = 2 (omega_n (G k_n)_m - sum_d mu^(d)_m (omega_n W y_n)_d) Kuf_mn ,       H = K_uu^-1 Psi2 K_uu^-1
+// -- the UniSGP formula above with w R -> S, w K_uu^-1 -> tr(W) K_uu^-1 and w y_n mu -> the rank-d_out term.
+// W is passed by value (the current mean(q_W)): the parameter mirror dParams keeps the last sweep's W, which
+// sgp_carry_posterior reads.
+// k_theta_multi_prep: the DO x N columns omega W y (from Yw = omega y, [d][n]) and the zero-padded mean columns [d][Mp]
+__global__ void __launch_bounds__(256) k_theta_multi_prep(const double* __restrict__ Yw, const double* __restrict__ mu,
+                                                          OutMat W, double* __restrict__ cw,
+                                                          double* __restrict__ mup, int64_t N, int M, int Mp, int dout) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < N)
+        for (int d = 0; d < dout; ++d) {
+            double v = 0.0;
+            for (int e = 0; e < dout; ++e) v = fma(W.v[d + e * dout], Yw[(size_t)e * N + t], v);
+            cw[(size_t)d * N + t] = v;
+        }
+    if (t < Mp)
+        for (int d = 0; d < dout; ++d) mup[(size_t)d * Mp + t] = (t < M) ? mu[(size_t)d * M + t] : 0.0;
+}
+
+// G = S - tr(W) K_uu^-1 (Mp x Mp, zero outside M x M), S = sum_ij W_ij R^(ij) read from R (Qp x Qp, block (i, j) at rows i M,
+// columns j M).  Grid Mp (one column each); part[j] = column j's share of tr(G Psi2), summed in a fixed order.
+__global__ void __launch_bounds__(256) k_form_G_multi(const double* __restrict__ R, int Qp, const double* __restrict__ Kinv,
+                                                      const double* __restrict__ Psi2, OutMat W, double trW,
+                                                      double* __restrict__ G, double* __restrict__ part, int M, int Mp, int dout) {
+    __shared__ double red[4];
+    const int j = blockIdx.x;
+    double t = 0.0;
+    for (int i = threadIdx.x; i < Mp; i += 256) {
+        double g = 0.0;
+        if (i < M && j < M) {
+            double s = 0.0;
+            for (int b = 0; b < dout; ++b)
+                for (int a = 0; a < dout; ++a) s = fma(W.v[a + b * dout], R[(size_t)(b * M + j) * Qp + a * M + i], s);
+            g = s - trW * Kinv[(size_t)j * Mp + i];
+        }
+        G[(size_t)j * Mp + i] = g;
+        t = fma(g, Psi2[(size_t)j * Mp + i], t);
+    }
+    t = block_sum(t, red);
+    if (threadIdx.x == 0) part[j] = t;
+}
+
+// out[0] = f: the Mp column shares of tr(G Psi2) and the linear term sum_m sum_d mu^(d)_m (B W)_md, each in a fixed order
+__global__ void __launch_bounds__(256) k_theta_value_multi(const double* __restrict__ part, const double* __restrict__ stats,
+                                                           const double* __restrict__ mup, const Params* __restrict__ P,
+                                                           OutMat W, double trW, double* __restrict__ out, int Mp, int dout) {
+    __shared__ double red[4];
+    const double* B = stats + (size_t)Mp * Mp;
+    double tg = 0.0, lin = 0.0;
+    for (int m = threadIdx.x; m < Mp; m += 256) {
+        tg += part[m];
+        for (int d = 0; d < dout; ++d) {
+            double bw = 0.0;
+            for (int e = 0; e < dout; ++e) bw = fma(B[(size_t)e * Mp + m], W.v[d + e * dout], bw);
+            lin = fma(mup[(size_t)d * Mp + m], bw, lin);
+        }
+    }
+    tg = block_sum(tg, red);
+    lin = block_sum(lin, red);
+    if (threadIdx.x == 0) {
+        const double s_w = stats[(size_t)Mp * Mp + (size_t)Mp * dout + 1];
+        out[0] = 0.5 * (trW * P->sigma2 * s_w + tg) - lin;
+    }
+}
+
+// the linear term of one (inducing row, point) entry: y_n mu_m (UniSGP: Yw = omega y, mu = mu_v) or, for DO > 1 outputs,
+// sum_d (omega W y_n)_d mu_m^(d) from the per-output columns k_theta_multi_prep formed (cws: [d][point], mum: [d][row])
+template <int DO>
+__device__ __forceinline__ double grad_lin(const double* ys, const double* mus, const double* cws, const double* mum, int col, int row) {
+    if constexpr (DO == 1) {
+        return ys[col] * mus[row];
+    } else {
+        double v = 0.0;
+#pragma unroll
+        for (int d = 0; d < DO; ++d) v = fma(cws[d * TB + col], mum[d * TB + row], v);
+        return v;
+    }
+}
+
+// DO = d_out: 1 = UniSGP; 2..4 = MultiSGP, where Yw is the DO x N matrix omega W y (k_theta_multi_prep) and mu the DO x Mp
+// zero-padded mean columns -- G is then S - tr(W) K_uu^-1 (k_form_G_multi)
+template <int FAM, int DO = 1>
 __global__ void __launch_bounds__(256) k_theta_grad_uf(const double* __restrict__ G, const double* __restrict__ Kuf,
                                                        const double* __restrict__ X, const double* __restrict__ Xus,
                                                        const double* __restrict__ Yw, const double* __restrict__ omega,
@@ -3236,6 +3323,7 @@ __global__ void __launch_bounds__(256) k_theta_grad_uf(const double* __restrict_
     // with split 0)
     __shared__ __attribute__((aligned(16))) double lds[2 * TB * PS];
     __shared__ double ys[TB], om[TB], mus[TB];
+    __shared__ double cws[DO > 1 ? DO * TB : 1], mum[DO > 1 ? DO * TB : 1];
     __shared__ double wsum[4][GRAD_SLOTS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
     const int I = blockIdx.y;
@@ -3284,6 +3372,16 @@ __global__ void __launch_bounds__(256) k_theta_grad_uf(const double* __restrict_
         om[tid] = (n < N) ? (omega ? omega[n] : 1.0) : 0.0;
         mus[tid] = mu[I * TB + tid];
     }
+    if constexpr (DO > 1) {
+        if (tid < TB) {
+            const int64_t n = n0 + tid;
+#pragma unroll
+            for (int d = 0; d < DO; ++d) {
+                cws[d * TB + tid] = (n < N) ? Yw[(size_t)d * N + n] : 0.0;
+                mum[d * TB + tid] = mu[(size_t)d * Mp + I * TB + tid];
+            }
+        }
+    }
     __syncthreads();
     double z[2][2][4];
     double e0 = 0.0;
@@ -3297,7 +3395,7 @@ __global__ void __launch_bounds__(256) k_theta_grad_uf(const double* __restrict_
             for (int r = 0; r < 4; ++r) {
                 const int row = acc_row(lane, wr, ti, r);
                 const double kv = (n < N) ? Kuf[(size_t)n * Mp + I * TB + row] : 0.0;
-                const double c = 2.0 * (om[col] * acc.t[ti][tj][r] - (ks == 0 ? ys[col] * mus[row] : 0.0));
+                const double c = 2.0 * (om[col] * acc.t[ti][tj][r] - (ks == 0 ? grad_lin<DO>(ys, mus, cws, mum, col, row) : 0.0));
                 const double v = c * kv;
                 e0 += v;
                 if constexpr (FAM == 0) {
@@ -3422,12 +3520,15 @@ __global__ void __launch_bounds__(256) k_theta_grad_fold(const double* __restric
 }
 
 // grad[0] = df/dsigma2, grad[1 ..] = df/dell (n_ell = 1: one shared lengthscale, else one per dimension)
+// MULTI (d_out > 1): the data half is scaled by 1/2, the K_uu half and the s_w term by tr(W) / 2 (trW; unused otherwise),
+// so the two halves are summed apart
+template <bool MULTI = false>
 __global__ void __launch_bounds__(256) k_theta_grad_finish(const double* __restrict__ part_uf, int n_uf,
                                                            const double* __restrict__ part_uu, int n_uu,
                                                            const double* __restrict__ stats_scal, const Params* __restrict__ P,
                                                            double* __restrict__ grad, int D, int n_ell,
                                                            const long long* wait_word, long long wait_need, int spin_limit,
-                                                           int* sync_status) {
+                                                           int* sync_status, double trW) {
     // wait_word (may be nullptr): the K_uu half of the gradient (part_uu) was formed on the other stream; it is complete when
     // the word reaches wait_need (bounded wait, SYNC_LATE_GRAD_JOIN if it gives up; the partials are then read past this XCD's L2)
     if (wait_word) {
@@ -3438,10 +3539,16 @@ __global__ void __launch_bounds__(256) k_theta_grad_finish(const double* __restr
     // blocks slot by slot with one wave: 31 us of load latency), then one workgroup reduction per slot -- fixed order
     __shared__ double red[4];
     __shared__ double tot[GRAD_SLOTS];
+    __shared__ double totK[MULTI ? GRAD_SLOTS : 1];
     const int tid = threadIdx.x;
     double acc[GRAD_SLOTS];
+    double accK[MULTI ? GRAD_SLOTS : 1];
 #pragma unroll
     for (int sl = 0; sl < GRAD_SLOTS; ++sl) acc[sl] = 0.0;
+    if constexpr (MULTI) {
+#pragma unroll
+        for (int sl = 0; sl < GRAD_SLOTS; ++sl) accK[sl] = 0.0;
+    }
     for (int b = tid; b < n_uf; b += 256) {
 #pragma unroll
         for (int sl = 0; sl < GRAD_SLOTS; ++sl)
@@ -3450,19 +3557,40 @@ __global__ void __launch_bounds__(256) k_theta_grad_finish(const double* __restr
     for (int b = tid; b < n_uu; b += 256) {
 #pragma unroll
         for (int sl = 0; sl < GRAD_SLOTS; ++sl)
-            if (sl <= D)
-                acc[sl] += wait_word ? __hip_atomic_load((const __attribute__((address_space(1))) double*)(part_uu + (size_t)b * GRAD_SLOTS + sl),
-                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                     : part_uu[(size_t)b * GRAD_SLOTS + sl];
+            if (sl <= D) {
+                const double v = wait_word ? __hip_atomic_load((const __attribute__((address_space(1))) double*)(part_uu + (size_t)b * GRAD_SLOTS + sl),
+                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                           : part_uu[(size_t)b * GRAD_SLOTS + sl];
+                if constexpr (MULTI) accK[sl] += v;
+                else acc[sl] += v;
+            }
     }
 #pragma unroll
     for (int sl = 0; sl < GRAD_SLOTS; ++sl) {
         if (sl <= D) {                                   // uniform
             const double v = block_sum(acc[sl], red);
             if (tid == 0) tot[sl] = v;
+            if constexpr (MULTI) {
+                const double vk = block_sum(accK[sl], red);
+                if (tid == 0) totK[sl] = vk;
+            }
         }
     }
     __syncthreads();
+    if constexpr (MULTI) {
+        if (tid == 0) {
+            // f = 1/2 [ tr(W) s_w sigma2 + sum Z + tr(W) sum H o K_uu ] differentiated (see k_form_G_multi)
+            grad[0] = 0.5 * (trW * stats_scal[1] + (tot[0] + trW * totK[0]) / P->sigma2);
+            if (n_ell == 1) {
+                double g = 0.0;
+                for (int d = 0; d < D; ++d) g += tot[1 + d] + trW * totK[1 + d];
+                grad[1] = 0.5 * g * P->inv_ell[0];
+            } else {
+                for (int d = 0; d < D; ++d) grad[1 + d] = 0.5 * (tot[1 + d] + trW * totK[1 + d]) * P->inv_ell[d];
+            }
+        }
+        return;
+    }
     if (tid == 0) {
         const double hw = 0.5 * P->W[0];
         grad[0] = hw * (stats_scal[1] + tot[0] / P->sigma2);

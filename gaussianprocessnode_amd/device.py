@@ -291,8 +291,9 @@ class SGPDevice:
         self._check(self._lib.sgp_carry_posterior(self._h, C.c_void_p(stream)), "sgp_carry_posterior")
 
     def theta_objective(self, want_grad: bool = False, n_ell: Optional[int] = None):
-        """neg_log_backwardmess_fast at the current kernel with q(v) fixed at the last sweep; optionally its gradient
-        w.r.t. (sigma2, ell...)."""
+        """The hyper-parameter objective at the current kernel with q(v) fixed at the last sweep (or at sgp_set_posterior's
+        q(v) for d_out > 1); optionally its gradient w.r.t. (sigma2, ell...).  d_out = 1: neg_log_backwardmess_fast; d_out =
+        2..4: neg_log_backwardmess_multi with W = the last set_noise (helper_functions/derivative_helper.jl:23-39, :92-106)."""
         v = C.c_double()
         have = getattr(self, "_n_ell", None)
         if want_grad and have is None:

@@ -303,3 +303,68 @@ def rule_theta(q_out, q_in, q_v, q_w, meta: MultiSGPMeta):
         tr_kinv = float(np.trace(potri(Kuu, meta.device)))
         return float(wts @ (-0.5 * trW * I1 - 0.5 * (I2 - 1.0)) + 0.5e-7 * (trW * tr_kinv - trS))
     return LogPdfClosure(log_backwardmess, multivariate=True)
+
+
+# ------------------------------------------------------------------------------------------------
+# the hyper-parameter objective: neg_log_backwardmess_multi / grad_llh_multi! (helper_functions/derivative_helper.jl:92-115)
+# ------------------------------------------------------------------------------------------------
+def theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta):
+    """Load the objective's inputs on `meta.engine` once and return `evaluate(theta) -> (value, grad)`, value and gradient of
+    neg_log_backwardmess_multi at the raw theta that `meta.kernel` maps (derivative_helper.jl:92-106).
+
+    The points are meta.method's cubature points of every q_in (a PointMass input is its own point), each node's target
+    y_data[i] repeated over its points (the reference passes y_data = mean.(qx)); W = mean(q_w); q(v) is installed with
+    `set_posterior` (mu_v and chol(Sigma_v + mu mu').U, factored on the device), so the device forms S = sum_ij W_ij Rv[i][j]
+    and the linear term itself.  K_uu^-1 is taken at meta.jitter (the reference adds 1e-12 I).  Each call of `evaluate` is one
+    `set_kernel` and one `sgp_theta_objective`: value and analytic gradient w.r.t. (sigma2, ell...), then the chain rule
+    through softplus (d softplus / dx = sigmoid) when meta.kernel has softplus_params set.  A kernel callable without
+    `softplus_params` is taken to map theta to (theta[0], theta[1:]) unchanged."""
+    from .device import potrf
+    W = _mean_W(q_w)
+    d_out = W.shape[0]
+    if d_out < 2:
+        raise ValueError("theta_objective_multi: MultiSGP needs d_out >= 2 (a d_out x d_out mean(q_w)); use the UniSGP objective")
+    q_ins = list(q_ins)
+    Y = np.asarray(y_data, dtype=np.float64)
+    if Y.ndim == 1 and len(q_ins) == 1:
+        Y = Y[None, :]
+    if Y.ndim != 2 or Y.shape != (len(q_ins), d_out):
+        raise ValueError(f"theta_objective_multi: y_data must be {len(q_ins)} x {d_out} (one target per node), got {Y.shape}")
+    if meta.method is None and not all(isinstance(q, PointMass) for q in q_ins):
+        raise ValueError("theta_objective_multi: uncertain inputs need meta.method (a cubature rule)")
+    pts, wts, ys, _ = _expand(meta, q_ins, [PointMass(y) for y in Y])
+    M, D_in = np.asarray(meta.Xu).shape
+    mu_v, Sigma_v = q_v.mean_cov()
+    mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
+    if mu_v.shape != (d_out * M,):
+        raise ValueError(f"theta_objective_multi: q_v must have d_out * M = {d_out * M} entries, got {mu_v.size}")
+    Uv = potrf(np.asarray(Sigma_v, dtype=np.float64) + np.outer(mu_v, mu_v), meta.device).T
+    eng = _engine(meta, len(wts), d_out)
+    load_batch(eng, pts, ys, None, wts, n_nodes=len(q_ins))
+    sign, logdet = np.linalg.slogdet(W)
+    eng.set_noise(W, float(logdet))
+    eng.set_posterior(mu_v, Uv)
+    softplus_params = bool(getattr(meta.kernel, "softplus_params", False))
+    family = kernel_family(meta.kernel)
+
+    def evaluate(theta):
+        th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
+        sigma2, ell = meta.kernel(th)
+        ell = np.atleast_1d(np.asarray(ell, dtype=np.float64))
+        if th.size != 1 + ell.size or ell.size not in (1, D_in):
+            raise ValueError(f"theta_objective_multi: theta must be (sigma2, 1 or {D_in} lengthscales), got {th.size} entries")
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, family)
+        value, grad = eng.theta_objective(want_grad=True, n_ell=ell.size)
+        grad = np.asarray(grad, dtype=np.float64)
+        if softplus_params:
+            grad = grad / (1.0 + np.exp(-th))                                       # d softplus(x) / dx = sigmoid(x)
+        return float(value), grad
+    return evaluate
+
+
+def grad_llh_multi(theta, y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta):
+    """grad_llh_multi! (helper_functions/derivative_helper.jl:108-115) on the device: (value, gradient) of
+    neg_log_backwardmess_multi at the raw theta of meta.kernel, with y_data (n_nodes x d_out), the inputs q_ins, q(v) and
+    mean(q_w) held fixed.  See `theta_objective_multi` for what is loaded; the reference's sumRv_Wbar, tr_W and v are formed
+    from q_v and q_w on the device."""
+    return theta_objective_multi(y_data, q_ins, q_v, q_w, meta)(theta)

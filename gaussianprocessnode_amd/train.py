@@ -262,3 +262,19 @@ def _perform_inference_classification_device(theta, xtrain, ytrain, Xu, engine, 
     a, b = engine.train_gamma()
     mu, Sigma, _ = engine.posterior(want_uv=False)
     return MvNormalMeanCovariance(mu, Sigma), (a, b), np.asarray(theta)
+
+
+def optimize_theta_multi(theta, y_data, q_ins, q_v, q_w, meta, *, steps: int = 100, optimizer=None, grad_fn=None):
+    """The inner loop of the pendulum's `PerformInference` (experiments/Pendulum_Wishart_2d.ipynb, cell 16): `steps` times
+    grad_llh_multi! at the current theta with q(x), q(v) and q(W) held, then Flux.Optimise.update!(AdaMax, theta, grad).
+    theta (raw, as meta.kernel maps it) is updated in place and returned.  The objective's inputs go to the device once; each
+    step is one set_kernel and one sgp_theta_objective (multisgp.theta_objective_multi).  `grad_fn(theta) -> (value, grad)`
+    replaces the device objective (a host restatement, for comparisons).  The optimiser runs on the host."""
+    from .multisgp import theta_objective_multi
+    theta = np.asarray(theta, dtype=np.float64)
+    opt = optimizer if optimizer is not None else AdaMax()
+    evaluate = grad_fn if grad_fn is not None else theta_objective_multi(y_data, q_ins, q_v, q_w, meta)
+    for _ in range(int(steps)):
+        _, g = evaluate(theta)
+        opt.update(theta, np.asarray(g, dtype=np.float64))
+    return theta

@@ -266,10 +266,21 @@ int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double
  * interrupt, tens of microseconds behind a 0.22 ms sweep.  The getters wait the same way. */
 int sgp_wait(sgp_handle* h);
 
-/* sgp_theta_objective: neg_log_backwardmess_fast (helper_functions/derivative_helper.jl:23-39) evaluated at the CURRENT
- * kernel parameters (sgp_set_kernel) with q(v) -- mu_v and Uv'Uv -- held at the last finished sweep, as the notebooks use
- * it (experiments/regression_kin40k.ipynb:212-221).  grad (may be NULL): d/d(sigma2, ell_1..ell_n_ell), 1 + n_ell
- * entries (grad_llh_new!, derivative_helper.jl:59-63 uses ForwardDiff; here the analytic kernel-derivative contraction). */
+/* sgp_theta_objective: the hyper-parameter objective evaluated at the CURRENT kernel parameters (sgp_set_kernel, family) with
+ * q(v) held fixed.  grad (may be NULL): d/d(sigma2, ell_1..ell_n_ell), 1 + n_ell entries (the reference differentiates with
+ * ForwardDiff; here the analytic kernel-derivative contraction).  With k_p = K(Xu, x_p), Kinv = (K_uu + jitter I)^-1, the
+ * point weights omega_p of sgp_set_data, Psi2 = sum_p omega_p k_p k_p', B = sum_p omega_p k_p y_p', s_w = sum_p omega_p:
+ *   d_out = 1 (UniSGP): neg_log_backwardmess_fast (helper_functions/derivative_helper.jl:23-39; grad_llh_new! :59-63)
+ *       f = w/2 [ sigma2 s_w - tr(Kinv Psi2) + tr(R_v Psi2) ] - w mu_v' B,     q(v) = the last finished sweep's, as the
+ *       notebooks use it (experiments/regression_kin40k.ipynb:212-221), w = the last sgp_set_noise;
+ *   d_out = 2..4 (MultiSGP): neg_log_backwardmess_multi (derivative_helper.jl:92-106; grad_llh_multi! :108-115)
+ *       f = 1/2 tr(W) (sigma2 s_w - tr(Kinv Psi2)) + 1/2 tr(S Psi2) - sum_de W_de mu^(d)' B_e,   S = sum_ij W_ij R_v^(ij),
+ *       with W = the last sgp_set_noise (a mean(q_W) set after the sweep is used), mu_v = [mu^(1); ..] and R_v = Sigma_v +
+ *       mu_v mu_v' from the last finished sweep -- or mu_v and Uv'Uv of sgp_set_posterior when that came later.  There is no
+ *       theta-free term.  SGP_ERR_ARG with an all-reduce hook installed (no data-sharded MultiSGP objective).
+ * Both: at the sweep's own data and kernel values nothing is recomputed; at another theta the K_uu chain, K_uf, Psi2 and B are
+ * re-evaluated (the next sgp_sweep is then a full one).  q(v) is not changed.  SGP_ERR_ARG without a finished sweep or
+ * sgp_set_posterior, and while a sgp_train_* run is open.  Sums are in a fixed order: repeated calls agree bitwise. */
 int sgp_theta_objective(sgp_handle* h, double* value, double* grad);
 
 /* ---- device-paced minibatch training: `PerformInference` of experiments/regression_kin40k.ipynb:196-230 ---------------

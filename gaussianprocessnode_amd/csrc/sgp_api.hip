@@ -2788,8 +2788,11 @@ static int dense_common(int32_t device, const double* A, int32_t n, double* out,
         HIPCHK(h, bW.alloc(mat));
         HIPCHK(h, bC.alloc(mat));
     }
-    HIPCHK(h, bScr.alloc(sizeof(double) * POTRF_SCRATCH));
-    HIPCHK(h, hipMemset(bScr.p, 0, sizeof(double) * POTRF_SCRATCH));
+    // every step j writes its log-det slot scratch[POTRF_LOGDET + j]: POTRF_SCRATCH holds 64 of them (a handle's chains have
+    // Tn <= 63), a stand-alone factorisation has Tn = ceil(n / 64) steps
+    const size_t scr = (size_t)POTRF_LOGDET + std::max(64, Tn);
+    HIPCHK(h, bScr.alloc(sizeof(double) * scr));
+    HIPCHK(h, hipMemset(bScr.p, 0, sizeof(double) * scr));
     launch_potrf(bA.as<double>(), np, Tn, bInfo.as<int>(), n, bScr.as<double>(), 0, bW.as<double>());
     const double* result = bA.as<double>();
     if (inverse) {

@@ -332,7 +332,9 @@ int sgp_kernelmatrix(int32_t device, const double* A, int64_t na, const double* 
 int sgp_kernelmatrix_family(int32_t device, int32_t family, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
                             double sigma2, const double* ell, int32_t n_ell, double* K);
 /* dense FP64 factorisations on the device (fastcholesky / cholinv call sites: GPnode/UniSGPnode.jl:68,
- * experiments/regression_kin40k.ipynb:184): A is n x n column-major symmetric; L lower; Ainv full. */
+ * experiments/regression_kin40k.ipynb:184): A is n x n column-major symmetric; L lower; Ainv full.  Any n >= 1: unlike a
+ * handle (d_out * m <= 4032) they are not bound by the LDS vector, and their scratch is sized by the ceil(n / 64)
+ * factorisation steps.  Device memory 8 n'^2 bytes for sgp_potrf and 24 n'^2 for sgp_potri, n' = n rounded up to 64. */
 int sgp_potrf(int32_t device, const double* A, int32_t n, double* L);
 int sgp_potri(int32_t device, const double* A, int32_t n, double* Ainv);
 

@@ -99,6 +99,32 @@ struct SweepPlan {
     bool resident = false;         // the statistics are resident (sweep_resident): an overlapped sweep's column layout, nothing to wait for
 };
 
+// What the statistics now on the device belong to: K_uf, the Psi2 / B partials and the assembled statistics (dKuf, dBpart, dSlabs,
+// dStats), the K_uu chain's outputs (dKuu, dWk, dKinv, dSaccK, the log-det in dScratch + POTRF_LOGDET) and q(v).  Written only by the
+// stats_* helpers, read by sgp_theta_objective's fresh path and planned_kind (kernel_matches + what is theirs).  Entry point -> effect:
+//   sgp_set_inducing, sgp_set_data              drop reuse; data_gen++ (new inputs: the objective re-forms the statistics too)
+//   sgp_set_targets / sgp_set_output_cov_sum    targets pending; data_gen++ / data_gen stays as it always has (not settled here)
+//   sgp_set_kernel, sgp_set_kernel_family       nothing: kernel_matches compares values, the same theta set again keeps the statistics
+//   sgp_bind_stats, sgp_set_allreduce/use_rccl  drop reuse (another buffer; this rank's share or the ranks' sum)
+//   sgp_sweep_local                             fills the record, drops reuse (the caller may change the statistics between the halves)
+//   sgp_sweep, full / over resident statistics  fills the record; reusable unless a training run is open / targets formed
+//   sgp_time_kernel, sgp_train_begin            drop reuse (they rewrite K_uf, the partials and the slabs; q(v) is untouched)
+//   sgp_set_posterior                           drops q(v) (a foreign one; the statistics are untouched)
+//   sgp_theta_objective at another theta/data   drops reuse and q(v); swept_local (the statistics are the NEW theta's)
+//   sgp_train_end                               drops reuse and q(v); swept_local = false (theta moved on the device)
+//   next_kind (once per record)                 checked, or drops reuse: its sweep ended without K_uu factored / with a wait given up
+struct StatsRecord {
+    double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};   // the kernel values they were formed at ...
+    int32_t family = SGP_KERNEL_SE;                           // ... and the family
+    uint64_t data_gen = ~0ull;     // the handle's data_gen they were formed from
+    double w0 = 1.0;               // W[0] of the sweep that produced q(v) (the UniSGP objective is linear in w)
+    bool qv = false;               // q(v) on the device is that sweep's
+    bool reusable = false;         // formed by a whole sgp_sweep outside a training run, and nothing has touched them since
+    bool checked = false;          // ... and that sweep was seen to end with K_uu factored and no bounded wait given up
+    bool targets = false;          // new targets since (B and the data scalars are to be formed again)
+};
+enum : unsigned { STATS_REUSE = 1u, STATS_QV = 2u };          // what stats_drop drops
+
 struct sgp_handle {
     sgp_config cfg{};
     int M = 0, Mp = 0, D = 0, dout = 1, Q = 0, Qp = 0, T = 0, TQ = 0;
@@ -106,13 +132,12 @@ struct sgp_handle {
     double n_nodes = 0;
     bool has_omega = false, has_yv = false, have_data = false, have_kernel = false, have_inducing = false;
     int prior_form = 2;            // 1 dense precision, 2 isotropic
-    bool swept_local = false, swept = false, stats_dirty = false;
+    bool swept_local = false, swept = false;
     bool in_flight = false;        // a sweep may still be executing (its streams are non-blocking)
     bool sync_reported = false;    // a getter has reported dInfo[3] (check_sync_status): the next sweep clears it
     hipStream_t last_stream = nullptr;   // the stream the last sweep's tail was enqueued on (sgp_sweep_finish): what stream order covers
-    uint64_t data_gen = 0, swept_data_gen = ~0ull;   // bumped by set_data / set_inducing; recorded by the sweep
-    Params swept_params{};                            // kernel / noise parameters the last sweep ran with
-    int32_t family = SGP_KERNEL_SE, swept_family = SGP_KERNEL_SE;   // kernel family (sgp_set_kernel_family) / that of the last sweep
+    uint64_t data_gen = 0;         // bumped by set_data / set_inducing / set_targets; recorded by the sweep (stats.data_gen)
+    int32_t family = SGP_KERNEL_SE;   // kernel family (sgp_set_kernel_family)
     int n_ell = 1;
     // device buffers
     double *dXu = nullptr, *dXus = nullptr, *dX = nullptr, *dYw = nullptr, *dY = nullptr, *dYv = nullptr, *dOmega = nullptr;
@@ -188,16 +213,7 @@ struct sgp_handle {
     void* allreduce_ctx = nullptr;
     void* rccl_comm = nullptr;
     double ryy_data[MAXO * MAXO] = {0};   // sum omega y y' of the current data (without the output-covariance term)
-    // SGP_FLAG_REUSE_STATS: the resident statistics -- K_uf, the Psi2 / B partials and the assembled statistics (dKuf, dBpart,
-    // dSlabs, dStats), the K_uu chain's outputs (dKuu, dWk, dKinv, dSaccK, the log-det in dScratch + POTRF_LOGDET) -- of the last
-    // full sweep: valid until a path that writes them or changes what they depend on (inputs, inducing points, kernel values)
-    // runs; `checked`: that sweep was seen to end with K_uu factored and no bounded wait given up; `targets`: new targets since
-    // (B and the data scalars are to be formed again)
-    struct ResidentStats {
-        bool valid = false, checked = false, targets = false;
-        double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};
-        int32_t family = SGP_KERNEL_SE;
-    } rec;
+    StatsRecord stats;             // what the statistics, the K_uu chain's outputs and q(v) on the device belong to
     int32_t last_kind = SGP_SWEEP_FULL;   // what the last completed sgp_sweep did (sgp_sweep_kind)
     std::string err;
 };
@@ -212,6 +228,35 @@ static void by_family(int32_t family, F&& f) {
         case SGP_KERNEL_MATERN52: f(std::integral_constant<int, SGP_KERNEL_MATERN52>{}); break;
         default: f(std::integral_constant<int, SGP_KERNEL_SE>{}); break;
     }
+}
+
+// The only writers of sgp_handle::stats (see the table above StatsRecord).  stats_formed: a sweep has enqueued the statistics (or
+// relies on the resident ones) at the handle's current kernel values, data and W
+static void stats_formed(sgp_handle* h) {
+    const Params& P = *h->hParams;
+    StatsRecord& r = h->stats;
+    r.sigma2 = P.sigma2; r.jitter = P.jitter; r.family = h->family; r.data_gen = h->data_gen; r.w0 = P.W[0];
+    for (int d = 0; d < MAXD; ++d) r.inv_ell[d] = P.inv_ell[d];
+    r.qv = h->swept_local = true;
+}
+// ... and that sweep was a whole sgp_sweep: the next one may skip what these statistics make unnecessary
+static void stats_reusable(sgp_handle* h) { h->stats.reusable = true; h->stats.checked = h->stats.targets = false; }
+static void stats_drop(sgp_handle* h, unsigned what) {
+    if (what & STATS_REUSE) h->stats.reusable = false;
+    if (what & STATS_QV) h->stats.qv = false;
+}
+static void stats_targets(sgp_handle* h, bool pending) { h->stats.targets = pending; }
+static void stats_checked(sgp_handle* h, bool ok) { if (ok) h->stats.checked = true; else h->stats.reusable = false; }
+// are the handle's current kernel values and family those of the record?  (values: sgp_set_kernel at the same theta keeps them.)
+// Both readers also need the library's own buffer or a hook: a caller-bound buffer without one may have been reduced outside.
+static bool kernel_matches(const sgp_handle* h) {
+    const Params& P = *h->hParams;
+    const StatsRecord& r = h->stats;
+    if (h->dStats != h->dStatsOwn && !h->allreduce) return false;
+    if (P.sigma2 != r.sigma2 || P.jitter != r.jitter || h->family != r.family) return false;
+    for (int d = 0; d < h->D; ++d)
+        if (P.inv_ell[d] != r.inv_ell[d]) return false;
+    return true;
 }
 
 #define HIPCHK(h, call)                                                                                   \
@@ -278,14 +323,16 @@ static hipError_t drain_device(sgp_handle* h) {
     return hipDeviceSynchronize();
 }
 
+static int sync_all(sgp_handle* h) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, drain_device(h));
+    h->in_flight = false;
+    return 0;
+}
+
 static int quiesce(sgp_handle* h) {
     if (h->training) return fail(h, SGP_ERR_ARG, "a device-paced training run is open on this handle: call sgp_train_end first");
-    if (h->in_flight) {
-        HIPCHK(h, hipSetDevice(h->cfg.device));
-        HIPCHK(h, drain_device(h));
-        h->in_flight = false;
-    }
-    return 0;
+    return h->in_flight ? sync_all(h) : 0;
 }
 
 // streaming-SYRK grid: tiles x point-chunks, sized to ONE resident round: the kernel's 40 KB of LDS let 4 workgroups
@@ -657,7 +704,7 @@ extern "C" int sgp_set_inducing(sgp_handle* h, const double* Xu) {
     if (!h || !Xu) return fail(h, SGP_ERR_ARG, "sgp_set_inducing: null argument");
     if (int qrc = quiesce(h)) return qrc;
     h->data_gen++;
-    h->rec.valid = false;
+    stats_drop(h, STATS_REUSE);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpy(h->dXu, Xu, sizeof(double) * h->M * h->D, hipMemcpyHostToDevice));
     h->have_inducing = true;
@@ -878,7 +925,7 @@ extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean
     if (!h || !X || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_set_data: null argument");
     if (int qrc = quiesce(h)) return qrc;
     h->data_gen++;
-    h->rec.valid = false;
+    stats_drop(h, STATS_REUSE);
     if (n < 0 || n > h->n_max) return fail(h, SGP_ERR_ARG, "sgp_set_data: n outside [0, n_max]");
     if (y_var && h->dout != 1) return fail(h, SGP_ERR_ARG, "sgp_set_data: y_var is only defined for d_out = 1");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -925,8 +972,8 @@ extern "C" int sgp_set_targets(sgp_handle* h, const double* y_mean, const double
                                 {h->dDataScal, scal.data(), scal.size()}};
     if (int urc = upload_pieces(h, pieces, 4, (size_t)n * (2 * (size_t)dout + 1) + scal.size())) return urc;
     h->has_yv = y_var != nullptr;
-    h->data_gen++;                             // (the statistics no longer belong to the data: sgp_theta_objective re-forms them)
-    h->rec.targets = true;
+    h->data_gen++;
+    stats_targets(h, true);
     return 0;
 }
 
@@ -944,7 +991,7 @@ extern "C" int sgp_set_output_cov_sum(sgp_handle* h, const double* S) {
         double syy = h->ryy_data[0] + S[0];
         HIPCHK(h, hipMemcpy(h->dDataScal + SGP_S_YY, &syy, sizeof(double), hipMemcpyHostToDevice));
     }
-    h->rec.targets = true;                     // (the data scalars of the statistics are to be formed again)
+    stats_targets(h, true);                    // (and no data_gen++: see the table above StatsRecord)
     return 0;
 }
 
@@ -1044,7 +1091,7 @@ extern "C" int sgp_set_prior(sgp_handle* h, const double* vec, const double* mat
 // inverting Sigma_v again on the next sweep.
 extern "C" int sgp_carry_posterior(sgp_handle* h, void* stream) {
     if (!h) return SGP_ERR_ARG;
-    if (!h->swept || h->stats_dirty)
+    if (!h->swept || !h->stats.qv)
         return fail(h, SGP_ERR_ARG, "sgp_carry_posterior: call it right after a finished sweep (before sgp_theta_objective)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
@@ -1070,7 +1117,7 @@ extern "C" int sgp_bind_stats(sgp_handle* h, void* stats_dev) {
     if (!h) return SGP_ERR_ARG;
     if (int qrc = quiesce(h)) return qrc;
     h->dStats = stats_dev ? static_cast<double*>(stats_dev) : h->dStatsOwn;
-    h->rec.valid = false;                      // (the buffer now bound holds no statistics of this handle's)
+    stats_drop(h, STATS_REUSE);
     return 0;
 }
 
@@ -1147,6 +1194,7 @@ static void prep_main(sgp_handle* h, hipStream_t s, bool always, int* info_reset
                        (const long long*)nullptr, 0LL, (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
     h->main_prep_gen = h->params_gen;
 }
+static void force_prep_main(sgp_handle* h) { h->main_prep_gen = 0; }   // (phase stamps were opened that no closing kernel folds)
 
 // `pack`: the statistics go to the exchange buffer (exchange_stats follows)
 static void enqueue_local(sgp_handle* h, hipStream_t s, bool pack) {
@@ -1355,6 +1403,31 @@ static int check_ready(sgp_handle* h) {
     return 0;
 }
 
+// Every sweep's host state (sweep_local_impl + sgp_sweep_finish, sweep_resident).  (1) A sweep starts: clear a status word some getter
+// has reported (it had drained the device); the scalars mirror stops speaking for the device until (3), getters read dInfo[3] itself
+static int sweep_begin(sgp_handle* h) {
+    if (h->sync_reported) {
+        HIPCHK(h, hipMemset(h->dInfo + 3, 0, sizeof(int)));
+        h->sync_reported = false;
+    }
+    h->in_flight = true;
+    h->mirror_epoch = -1;
+    return 0;
+}
+// (2) its statistics are enqueued: stats_formed.  (3) F2 with the sweep's closing kernel: k_scalars writes the new done epoch (and
+// the mirror, which speaks for the device again); with events, the next sweep's K_uu chain may overwrite K_uu^-1 after evDone
+static int sweep_close(sgp_handle* h, hipStream_t s, const SweepPlan& p, bool join_word) {
+    ++h->done_epoch;                                         // what this sweep's k_scalars writes when it is through
+    enqueue_finish2(h, s, join_word);
+    HIPCHK(h, hipGetLastError());
+    h->mirror_epoch = mirror_for(h) ? h->done_epoch : -1;
+    if (p.events) HIPCHK(h, hipEventRecord(h->evDone, s));
+    h->swept = true;
+    h->posterior_set = false;
+    h->last_stream = s;
+    return 0;
+}
+
 // `overlapped`: the statistics go to the handle's own statistics streams in tile-row groups and the Lambda chain (sgp_sweep_finish
 // on the library's stream) starts on the first group while the others are still being summed (plan_overlap); `interleave`: the
 // K_uu chain's steps may go out alternately with the Lambda chain's; `pack`: the statistics go to the exchange buffer.  All three
@@ -1367,12 +1440,7 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool i
     p.stream = stream ? static_cast<hipStream_t>(stream) : h->own;
     p.overlapped = overlapped;
     p.pack = pack;
-    if (h->sync_reported) {
-        // (the getter that reported the word had drained the device: nothing is in flight)
-        HIPCHK(h, hipMemset(h->dInfo + 3, 0, sizeof(int)));
-        h->sync_reported = false;
-    }
-    h->in_flight = true;
+    if (int brc = sweep_begin(h)) return brc;
     // The K_uu chain depends on theta and Xu only: it starts on the (low-priority) side stream as soon as the previous
     // sweep has finished with its outputs, runs beside the data-sized kernels, the all-reduce and the Lambda chain, and is
     // joined just before the Sigma launch.  The streams meet through device words (the chain's first kernel waits for the
@@ -1423,18 +1491,13 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool i
     if (!p.kuu_interleaved) HIPCHK(h, hipEventRecord(h->evSide, h->side));
     if (!stats_first)
         if (int src = enqueue_stats()) return src;
-    h->stats_dirty = false;
-    h->swept_params = *h->hParams;
-    h->swept_family = h->family;
-    h->swept_data_gen = h->data_gen;
-    h->swept_local = true;
+    stats_formed(h);
     return 0;
 }
 
-// (a caller that runs the halves itself may change the statistics between them: what they hold is not the library's to reuse)
 extern "C" int sgp_sweep_local(sgp_handle* h, void* stream) {
     const int rc = sweep_local_impl(h, stream, false, false, false);
-    if (h) h->rec.valid = false;
+    if (h) stats_drop(h, STATS_REUSE);
     return rc;
 }
 
@@ -1451,16 +1514,7 @@ extern "C" int sgp_sweep_finish(sgp_handle* h, void* stream) {
     HIPCHK(h, hipGetLastError());
     if (p.kuu_interleaved) HIPCHK(h, hipEventRecord(h->evSide, h->side));   // (the K_uu chain's steps and tail went out inside enqueue_finish1)
     if (!p.join_word) HIPCHK(h, hipStreamWaitEvent(s, h->evSide, 0));          // join with the K_uu chain
-    ++h->done_epoch;                                         // what this sweep's k_scalars writes when it is through
-    enqueue_finish2(h, s, p.join_word);
-    HIPCHK(h, hipGetLastError());
-    h->mirror_epoch = mirror_for(h) ? h->done_epoch : -1;
-    // the next sweep's K_uu chain may overwrite K_uu^-1 after this
-    if (p.events) HIPCHK(h, hipEventRecord(h->evDone, s));
-    h->swept = true;
-    h->posterior_set = false;
-    h->last_stream = s;
-    return 0;
+    return sweep_close(h, s, p, p.join_word);
 }
 
 // The one exchange step of a data-sharded sweep: the ranks sum the exchange buffer k_assemble just wrote -- the LOWER tiles of
@@ -1483,32 +1537,23 @@ static int exchange_stats(sgp_handle* h, hipStream_t s, int tile0, int ntile, bo
 static int exchange_stats(sgp_handle* h, hipStream_t s) { return exchange_stats(h, s, 0, h->ntiles, true); }
 
 // ---- SGP_FLAG_REUSE_STATS: sweeps over the resident statistics (see sgp_sweep_kind in include/sgp_hip.h) ----
-static int sync_all(sgp_handle* h);
 // what the host state allows the next sgp_sweep to skip
 static int32_t planned_kind(const sgp_handle* h) {
-    if (!(h->cfg.flags & SGP_FLAG_REUSE_STATS) || !h->rec.valid || h->training) return SGP_SWEEP_FULL;
-    if (h->dStats != h->dStatsOwn && !h->allreduce) return SGP_SWEEP_FULL;
-    // kernel values compared as sgp_theta_objective's freshness test does: set_kernel at the same theta keeps the statistics
-    const Params& P = *h->hParams;
-    if (P.sigma2 != h->rec.sigma2 || P.jitter != h->rec.jitter || h->family != h->rec.family) return SGP_SWEEP_FULL;
-    for (int d = 0; d < h->D; ++d)
-        if (P.inv_ell[d] != h->rec.inv_ell[d]) return SGP_SWEEP_FULL;
-    return h->rec.targets ? SGP_SWEEP_TARGETS : SGP_SWEEP_REUSED;
+    if (!(h->cfg.flags & SGP_FLAG_REUSE_STATS) || !h->stats.reusable || h->training || !kernel_matches(h)) return SGP_SWEEP_FULL;
+    return h->stats.targets ? SGP_SWEEP_TARGETS : SGP_SWEEP_REUSED;
 }
 // ... and what it will do: the full sweep that formed the statistics must have ended with K_uu factored and without a bounded
 // wait giving up (the K_uu chain and the masked statistics stream meet the sweep through such waits) -- looked at once, before the
 // first sweep that relies on it, after waiting for that sweep
 static int next_kind(sgp_handle* h, int32_t* kind) {
     *kind = planned_kind(h);
-    if (*kind == SGP_SWEEP_FULL || h->rec.checked) return 0;
+    if (*kind == SGP_SWEEP_FULL || h->stats.checked) return 0;
     if (int rc = sync_all(h)) return rc;
     int info[4];
     HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
-    if (info[0] != 0 || info[3] != 0) {
-        h->rec.valid = false;
-        *kind = SGP_SWEEP_FULL;
-    } else
-        h->rec.checked = true;
+    const bool ok = info[0] == 0 && info[3] == 0;
+    stats_checked(h, ok);
+    if (!ok) *kind = SGP_SWEEP_FULL;
     return 0;
 }
 
@@ -1527,11 +1572,7 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     p.pack = h->allreduce != nullptr;
     p.resident = true;
     hipStream_t s = p.stream;
-    if (h->sync_reported) {
-        HIPCHK(h, hipMemset(h->dInfo + 3, 0, sizeof(int)));
-        h->sync_reported = false;
-    }
-    h->in_flight = true;
+    if (int brc = sweep_begin(h)) return brc;
     h->plan = p;
     h->plan.overlapped = false;                              // (as after sgp_sweep_finish: a repeated finish runs F1 and F2 alone)
     prep_main(h, s, true, h->dInfo + 1);
@@ -1550,22 +1591,11 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
             if (int xrc = exchange_stats(h, s, h->ntiles, 0, true)) return xrc;
     }
     HIPCHK(h, hipGetLastError());
-    h->stats_dirty = false;
-    h->swept_params = *h->hParams;
-    h->swept_family = h->family;
-    h->swept_data_gen = h->data_gen;
-    h->swept_local = true;
+    stats_formed(h);
     enqueue_finish1(h, s, p);
     HIPCHK(h, hipGetLastError());
-    ++h->done_epoch;                                         // what this sweep's k_scalars writes when it is through
-    enqueue_finish2(h, s, false);
-    HIPCHK(h, hipGetLastError());
-    h->mirror_epoch = mirror_for(h) ? h->done_epoch : -1;
-    if (p.events) HIPCHK(h, hipEventRecord(h->evDone, s));
-    h->swept = true;
-    h->posterior_set = false;
-    h->last_stream = s;
-    h->rec.targets = false;
+    if (int crc = sweep_close(h, s, p, false)) return crc;
+    stats_targets(h, false);
     h->last_kind = targets ? SGP_SWEEP_TARGETS : SGP_SWEEP_REUSED;
     return 0;
 }
@@ -1591,26 +1621,19 @@ extern "C" int sgp_sweep(sgp_handle* h, void* stream) {
     rc = sgp_sweep_finish(h, stream);
     if (rc) return rc;
     h->last_kind = SGP_SWEEP_FULL;
-    if ((h->cfg.flags & SGP_FLAG_REUSE_STATS) && !h->training) {   // this sweep formed the statistics of the resident inputs
-        h->rec.valid = true;
-        h->rec.checked = h->rec.targets = false;
-        h->rec.sigma2 = h->hParams->sigma2;
-        h->rec.jitter = h->hParams->jitter;
-        for (int d = 0; d < MAXD; ++d) h->rec.inv_ell[d] = h->hParams->inv_ell[d];
-        h->rec.family = h->family;
-    }
+    if ((h->cfg.flags & SGP_FLAG_REUSE_STATS) && !h->training) stats_reusable(h);   // this sweep formed the statistics of the resident inputs
     return 0;
 }
 
 extern "C" int sgp_sweep_kind(const sgp_handle* hc, int32_t* next, int32_t* last) {
     if (!hc) return SGP_ERR_ARG;
-    sgp_handle* h = const_cast<sgp_handle*>(hc);      // (the one-time status check of the resident statistics is kept on the handle)
     if (next) {
         int32_t kind = SGP_SWEEP_FULL;
-        if (int rc = next_kind(h, &kind)) return rc;
+        // (the ABI's handle is const; the one-time status check of the resident statistics is kept on it: the only cast)
+        if (int rc = next_kind(const_cast<sgp_handle*>(hc), &kind)) return rc;
         *next = kind;
     }
-    if (last) *last = h->last_kind;
+    if (last) *last = hc->last_kind;
     return 0;
 }
 
@@ -1628,7 +1651,7 @@ extern "C" int sgp_set_allreduce(sgp_handle* h, sgp_allreduce_fn fn, void* ctx) 
     if (int prc = ensure_pack(h)) return prc;
     h->allreduce = fn;
     h->allreduce_ctx = ctx;
-    h->rec.valid = false;                      // (the resident statistics are this rank's, or the sum over other ranks)
+    stats_drop(h, STATS_REUSE);
     plan_overlap(h, h->n);         // (a data-sharded sweep pays one collective per statistics group: one cut, chosen from n_max)
     return 0;
 }
@@ -1644,14 +1667,9 @@ extern "C" int sgp_use_rccl(sgp_handle* h, void* nccl_comm) {
     if (!h || !nccl_comm) return fail(h, SGP_ERR_ARG, "sgp_use_rccl: null argument");
     if (!g_nccl_allreduce) g_nccl_allreduce = reinterpret_cast<nccl_allreduce_t>(dlsym(RTLD_DEFAULT, "ncclAllReduce"));
     if (!g_nccl_allreduce) return fail(h, SGP_ERR_ARG, "sgp_use_rccl: no ncclAllReduce in this process (load librccl first)");
-    if (int qrc = quiesce(h)) return qrc;
-    if (int prc = ensure_pack(h)) return prc;
-    h->rccl_comm = nccl_comm;
-    h->allreduce = rccl_hook;
-    h->allreduce_ctx = h;
-    h->rec.valid = false;
-    plan_overlap(h, h->n);
-    return 0;
+    const int rc = sgp_set_allreduce(h, rccl_hook, h);
+    if (!rc) h->rccl_comm = nccl_comm;
+    return rc;
 }
 
 __global__ void k_clock_probe(long long* out, int iters) {
@@ -1730,16 +1748,9 @@ extern "C" int sgp_measure_clocks(int32_t device, double* out) {
 // ------------------------------------------------------------------------------------------------
 // results
 // ------------------------------------------------------------------------------------------------
-static int sync_all(sgp_handle* h) {
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, drain_device(h));
-    h->in_flight = false;
-    return 0;
-}
-
 // A bounded wait on a device word gave up somewhere since the last check (dInfo[3], see SYNC_LATE_* in sgp_kernels.hip.h): what
 // the wait protected -- the buffers the two streams hand each other -- cannot be trusted, so the results are refused by EVERY
-// getter, until the next sweep is enqueued (sweep_local_impl clears the word then).  Call after a device synchronisation.
+// getter, until the next sweep is enqueued (sweep_begin clears the word then).  Call after a device synchronisation.
 extern "C" int sgp_wait(sgp_handle* h) {
     if (!h) return SGP_ERR_ARG;
     return sync_all(h);
@@ -1769,6 +1780,12 @@ static int check_sync_status(sgp_handle* h) {
     return SGP_ERR_HIP;
 }
 
+// the getters' wait: everything the handle has enqueued is through, and no stream hand-off gave up
+static int sync_checked(sgp_handle* h) {
+    if (int rc = sync_all(h)) return rc;
+    return check_sync_status(h);
+}
+
 static int download_square(sgp_handle* h, const double* dsrc, int ld, int n, double* dst) {
     HIPCHK(h, hipMemcpy2D(dst, sizeof(double) * n, dsrc, sizeof(double) * ld, sizeof(double) * n, n, hipMemcpyDeviceToHost));
     return 0;
@@ -1791,7 +1808,7 @@ extern "C" int sgp_set_posterior(sgp_handle* h, const double* mu_v, const double
     HIPCHK(h, hipMemcpy(h->dMu, m.data(), Qp * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->dUvT, ut.data(), Qp * Qp * sizeof(double), hipMemcpyHostToDevice));
     h->swept = true;
-    h->stats_dirty = true;                     // q(v) no longer belongs to the statistics on the device
+    stats_drop(h, STATS_QV);                   // q(v) no longer belongs to the statistics on the device
     h->posterior_set = true;                   // (no Sigma_v came with it: sgp_predict_var needs one passed in)
     return 0;
 }
@@ -1799,9 +1816,7 @@ extern "C" int sgp_set_posterior(sgp_handle* h, const double* mu_v, const double
 extern "C" int sgp_get_scalars(sgp_handle* h, double* out) {
     if (!h || !out) return fail(h, SGP_ERR_ARG, "sgp_get_scalars: null argument");
     if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_get_scalars: no finished sweep");
-    int rc = sync_all(h);
-    if (rc) return rc;
-    if (int src = check_sync_status(h)) return src;
+    if (int rc = sync_checked(h)) return rc;
     if (mirror_fresh(h)) memcpy(out, h->hMirror, SGP_R_COUNT * sizeof(double));
     else HIPCHK(h, hipMemcpy(out, h->dOut, SGP_R_COUNT * sizeof(double), hipMemcpyDeviceToHost));
     if (out[SGP_R_INFO_KUU] < 0 || out[SGP_R_INFO_LAMBDA] < 0)
@@ -1819,9 +1834,8 @@ extern "C" int sgp_get_scalars(sgp_handle* h, double* out) {
 extern "C" int sgp_get_posterior(sgp_handle* h, double* mu_v, double* Sigma_v, double* Uv) {
     if (!h) return SGP_ERR_ARG;
     if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_get_posterior: no finished sweep");
-    int rc = sync_all(h);
+    int rc = sync_checked(h);
     if (rc) return rc;
-    if (int src = check_sync_status(h)) return src;
     int info[4];
     HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
     if (info[0] < 0 || info[1] < 0)
@@ -1845,9 +1859,8 @@ extern "C" int sgp_get_posterior(sgp_handle* h, double* mu_v, double* Sigma_v, d
 extern "C" int sgp_get_stats(sgp_handle* h, double* Psi2, double* B, double* scalars) {
     if (!h) return SGP_ERR_ARG;
     if (!h->swept_local) return fail(h, SGP_ERR_ARG, "sgp_get_stats: no sweep yet");
-    int rc = sync_all(h);
+    int rc = sync_checked(h);
     if (rc) return rc;
-    if (int src = check_sync_status(h)) return src;
     const int M = h->M, Mp = h->Mp;
     if (Psi2) { rc = download_square(h, h->dStats, Mp, M, Psi2); if (rc) return rc; }
     if (B)
@@ -1862,9 +1875,8 @@ extern "C" int sgp_get_stats(sgp_handle* h, double* Psi2, double* B, double* sca
 extern "C" int sgp_get_kuu_chol(sgp_handle* h, double* KuuL) {
     if (!h || !KuuL) return fail(h, SGP_ERR_ARG, "sgp_get_kuu_chol: null argument");
     if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_get_kuu_chol: no finished sweep");
-    int rc = sync_all(h);
+    int rc = sync_checked(h);
     if (rc) return rc;
-    if (int src = check_sync_status(h)) return src;
     rc = download_square(h, h->dKuu, h->Mp, h->M, KuuL);
     if (rc) return rc;
     for (int j = 0; j < h->M; ++j)
@@ -1876,9 +1888,7 @@ extern "C" int sgp_get_wishart_invscale(sgp_handle* h, double* S) {
     if (!h || !S) return fail(h, SGP_ERR_ARG, "sgp_get_wishart_invscale: null argument");
     if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_get_wishart_invscale: no finished sweep");
     if (h->dout == 1) return fail(h, SGP_ERR_ARG, "sgp_get_wishart_invscale: d_out = 1 (use sgp_get_scalars)");
-    int rc = sync_all(h);
-    if (rc) return rc;
-    if (int src = check_sync_status(h)) return src;
+    if (int rc = sync_checked(h)) return rc;
     std::vector<double> tmp(MAXO * MAXO);
     HIPCHK(h, hipMemcpy(tmp.data(), h->dWishart, sizeof(double) * MAXO * MAXO, hipMemcpyDeviceToHost));
     for (int i = 0; i < h->dout * h->dout; ++i) S[i] = tmp[i];
@@ -1941,7 +1951,7 @@ extern "C" int sgp_time_kernel(sgp_handle* h, int32_t which, int32_t iters, void
     if (!h || !avg_us || iters < 1) return fail(h, SGP_ERR_ARG, "sgp_time_kernel: bad argument");
     if (!h->swept_local || h->n == 0) return fail(h, SGP_ERR_ARG, "sgp_time_kernel: run a sweep on non-empty data first");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->rec.valid = false;                      // (the timed launches rewrite K_uf, the partials and the slabs)
+    stats_drop(h, STATS_REUSE);
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
     // which = SGP_TIME_GROUP0 + g: the SYRK launch of statistics group g of the overlapped sweep, on the stream (and CUs) it runs on
     const StatGroup* G = nullptr;
@@ -2079,9 +2089,7 @@ extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const
     if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_predict: no posterior in the handle and mu_v is NULL");
     if (h->training) return fail(h, SGP_ERR_ARG, "sgp_predict: a device-paced training run is open (sgp_train_end first)");
     if (ns == 0) return 0;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, drain_device(h));
-    h->in_flight = false;
+    if (int wrc = sync_all(h)) return wrc;
     hipStream_t s = h->own;
     double *dXs = nullptr, *dMean = nullptr, *dMuTmp = nullptr;
     if (int crc = call_scratch(h, (size_t)ns * (h->D + h->dout) + (mu_v ? (size_t)h->Q : 0), &dXs)) return crc;
@@ -2141,9 +2149,7 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
     if (!mu_v && h->posterior_set)
         return fail(h, SGP_ERR_ARG, "sgp_predict_var: sgp_set_posterior gave no Sigma_v: pass mu_v and Sigma_v, or sweep first");
     if (ns == 0) return 0;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, drain_device(h));
-    h->in_flight = false;
+    if (int wrc = sync_all(h)) return wrc;
     if (!mu_v) {
         // the last sweep's q(v), refused exactly when sgp_get_posterior refuses it
         if (int src = check_sync_status(h)) return src;
@@ -2430,18 +2436,26 @@ static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s) {
 
 // MultiSGP objective: fresh (the statistics, K_uu^-1 and q(v) of the last sweep at the current kernel) or re-evaluated (K_uu
 // chain and local statistics at the current theta, as theta_objective_eval); then value and, with grad, the gradient
+// Both re-evaluation paths of sgp_theta_objective: the K_uu chain and the local statistics at the CURRENT theta on `s` (data-sharded:
+// this rank's, summed like a sweep's).  The statistics are that theta's now, not those of q(v)'s sweep.
+static int enqueue_restats(sgp_handle* h, hipStream_t s) {
+    stats_drop(h, STATS_REUSE | STATS_QV);
+    h->swept_local = true;                                     // (a local sweep's worth of statistics: sgp_get_stats, sgp_sweep_finish)
+    enqueue_kuu(h, s, false);
+    enqueue_local(h, s, h->allreduce != nullptr);
+    if (h->allreduce)
+        if (int xrc = exchange_stats(h, s)) return xrc;
+    force_prep_main(h);
+    return 0;
+}
+
 static int theta_objective_multi(sgp_handle* h, hipStream_t s, bool fresh, double* value, double* grad) {
     if (fresh) {
         double out[SGP_R_COUNT];
         HIPCHK(h, hipMemcpy(out, h->dOut, sizeof out, hipMemcpyDeviceToHost));
         if (out[SGP_R_INFO_KUU] > 0) { h->err = "K_uu is not positive definite"; return (int)out[SGP_R_INFO_KUU]; }
     } else {
-        h->stats_dirty = true;                   // the statistics now belong to the NEW theta, not to q(v)'s sweep
-        h->rec.valid = false;
-        h->swept_local = true;
-        enqueue_kuu(h, s, false);
-        enqueue_local(h, s, false);
-        h->main_prep_gen = 0;
+        if (int erc = enqueue_restats(h, s)) return erc;     // (no hook here: sgp_theta_objective refuses d_out > 1 with one)
         HIPCHK(h, hipStreamSynchronize(s));
         HIPCHK(h, hipGetLastError());
         int info = 0;
@@ -2463,12 +2477,7 @@ static int theta_objective_multi(sgp_handle* h, hipStream_t s, bool fresh, doubl
 }
 
 static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value) {
-    enqueue_kuu(h, s, false);
-    enqueue_local(h, s, h->allreduce != nullptr);
-    // (data-sharded run: the statistics re-formed at the new theta are this rank's -- sum them like a sweep's)
-    if (h->allreduce)
-        if (int xrc = exchange_stats(h, s)) return xrc;
-    h->main_prep_gen = 0;       // this evaluation opens phase stamps that no closing kernel folds: let the next sweep's k_prep_xu reset them
+    if (int erc = enqueue_restats(h, s)) return erc;
     const int M = h->M, Mp = h->Mp, Q = h->Q, Qp = h->Qp;
     hipLaunchKernelGGL(k_trace_kinv, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dKinv, h->dTrace, M, Mp);
     hipLaunchKernelGGL(k_trace_R, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dR, h->dTrace + TRACE_BLOCKS, M, Mp, h->dout,
@@ -2494,10 +2503,7 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
     if (h->training) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: a device-paced training run is open (sgp_train_end first)");
     if (h->dout > 1 && h->allreduce)
         return fail(h, SGP_ERR_ARG, "sgp_theta_objective: data-sharded MultiSGP theta objectives are not supported (remove the hook)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, drain_device(h));
-    h->in_flight = false;
-    if (int src = check_sync_status(h)) return src;
+    if (int wrc = sync_checked(h)) return wrc;
     hipStream_t s = h->own;
     // Same theta, data and noise as the sweep that produced q(v) -- the notebooks' call pattern
     // (experiments/regression_kin40k.ipynb:205-221 evaluates the gradient at the theta the sweep just used): K_uf, Psi2, b,
@@ -2505,12 +2511,9 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
     // are the reduced ones and value and gradient are those of ALL shards (enqueue_theta_grad sums the data half through the
     // hook).  A caller-bound buffer WITHOUT a hook may have been reduced outside the library: then the statistics are
     // re-formed locally, as before.
-    bool fresh = !h->stats_dirty && h->swept_data_gen == h->data_gen && (h->dStats == h->dStatsOwn || h->allreduce) &&
-                 h->swept_params.sigma2 == h->hParams->sigma2 && h->swept_params.jitter == h->hParams->jitter &&
-                 h->swept_family == h->family;
+    const bool fresh = h->stats.qv && h->stats.data_gen == h->data_gen && kernel_matches(h);
     // the objective is linear in w: a new mean(q_w) (classification_banana.ipynb passes the UPDATED q(w)) only rescales it
-    const double wscale = fresh ? h->hParams->W[0] / h->swept_params.W[0] : 1.0;
-    for (int d = 0; d < h->D && fresh; ++d) fresh = h->swept_params.inv_ell[d] == h->hParams->inv_ell[d];
+    const double wscale = fresh ? h->hParams->W[0] / h->stats.w0 : 1.0;
     if (h->dout > 1) return theta_objective_multi(h, s, fresh, value, grad);
     int rc = 0;
     if (fresh) {
@@ -2521,17 +2524,14 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
         *value = 0.5 * h->hParams->W[0] * (out[SGP_R_SUM_I1] + out[SGP_R_SUM_I2] - sc[SGP_S_YY]);
         if (!grad) return 0;
     } else {
-        h->stats_dirty = true;                   // the statistics now belong to the NEW theta, not to q(v)'s sweep
-        h->rec.valid = false;
         rc = theta_objective_eval(h, s, value);
-        if (rc || !grad) { h->swept_local = true; return rc; }
+        if (rc || !grad) return rc;
     }
     if (int grc = enqueue_theta_grad(h, s)) return grc;
     HIPCHK(h, wait_stream(s));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy(grad, h->dGrad, sizeof(double) * (1 + h->n_ell), hipMemcpyDeviceToHost));
     for (int i = 0; i <= h->n_ell; ++i) grad[i] *= wscale;
-    if (!fresh) h->swept_local = true;
     return 0;
 }
 
@@ -2550,7 +2550,7 @@ extern "C" int sgp_train_begin(sgp_handle* h, const double* X, const double* y, 
     // (a caller-bound statistics buffer is fine here: inside sgp_train_step nobody but the library -- through the all-reduce hook,
     // if one is installed -- touches the statistics between the two halves of the sweep)
     if (!h->have_inducing) return fail(h, SGP_ERR_ARG, "sgp_train_begin: call sgp_set_inducing first");
-    h->rec.valid = false;                      // (every step rewrites the statistics of its window)
+    stats_drop(h, STATS_REUSE);
     if (n_total < 1) return fail(h, SGP_ERR_ARG, "sgp_train_begin: empty training set");
     if (n_ell != 1 && n_ell != h->D) return fail(h, SGP_ERR_ARG, "sgp_train_begin: n_ell must be 1 or D");
     if (!(jitter >= 0.0) || !(eta > 0.0)) return fail(h, SGP_ERR_ARG, "sgp_train_begin: jitter >= 0 and eta > 0 required");
@@ -2720,8 +2720,7 @@ extern "C" int sgp_train_end(sgp_handle* h, double* theta_raw, int64_t* counts) 
     if (h->train_probit) { h->hParams->W[0] = P.W[0]; h->hParams->E_logw = P.E_logw; }      // mean(q_w) after the last minibatch
     h->train_probit = false;
     h->params_gen++;
-    h->stats_dirty = true;                                     // the resident statistics belong to the previous theta
-    h->rec.valid = false;
+    stats_drop(h, STATS_REUSE | STATS_QV);                     // the resident statistics belong to the previous theta
     h->swept_local = false;
     if (theta_raw) for (int i = 0; i <= h->n_ell; ++i) theta_raw[i] = st.theta[i];
     if (counts) { counts[0] = (int64_t)st.steps; counts[1] = (int64_t)st.rejected; }

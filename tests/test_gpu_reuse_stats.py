@@ -190,6 +190,49 @@ def test_reuse_is_dropped_where_the_statistics_stop_being_valid(G):
         assert a.sweep_kind()[0] == FULL
         a.sweep()
         assert_bitwise(snapshot(a), snapshot(b), "after bind_stats")
+        # predictive variances read the K_uu chain's outputs and q(v), they do not change them
+        a.predict_var(X[:50])
+        assert a.sweep_kind()[0] == REUSED
+
+        # every other path that overwrites the statistics or changes what they depend on: the next sweep is a full one
+        def two_phase(dev):
+            dev.sweep_local()
+            dev.sweep_finish()
+
+        def passthrough(buf, count, stream):                  # one rank: the sum is the identity
+            pass
+
+        steps = [("set_inducing", lambda d: d.set_inducing(Xu)),
+                 ("sweep_local + sweep_finish", two_phase),
+                 ("time_kernel", lambda d: d.time_kernel(G._lib.SGP_T_GRAM, 2)),
+                 ("set_allreduce", lambda d: d.set_allreduce(passthrough)),
+                 ("set_allreduce(None)", lambda d: d.set_allreduce(None))]
+        for name, step in steps:
+            for dev in (a, b):
+                step(dev)
+            assert a.sweep_kind()[0] == FULL, name
+            assert b.sweep_kind() == (FULL, FULL), name
+            for dev in (a, b):
+                dev.sweep()
+            assert a.sweep_kind() == (REUSED, FULL), name
+            assert_bitwise(snapshot(a), snapshot(b), f"after {name}")
+        # a device-paced training run rewrites the statistics of its windows and moves theta
+        for dev in (a, b):
+            dev.train_begin(X, y, np.zeros(1 + D), jitter=1e-6)
+            assert dev.sweep_kind()[0] == FULL
+            dev.train_step(0, 1000)
+            assert dev.sweep_kind()[0] == FULL
+            dev.train_end()
+        assert a.sweep_kind()[0] == FULL
+        assert b.sweep_kind()[0] == FULL
+        for dev in (a, b):
+            dev.set_data(X, y)                                # (the run leaves the handle without data)
+            dev.set_kernel(0.8, ell, 1e-8)
+            dev.set_prior_isotropic(50.0)
+            dev.set_noise([[25.0]])
+            dev.sweep()
+        assert a.sweep_kind() == (REUSED, FULL)
+        assert_bitwise(snapshot(a), snapshot(b), "after a training run")
 
 
 def test_hook_is_called_once_for_new_targets_and_never_for_reused_statistics(G):

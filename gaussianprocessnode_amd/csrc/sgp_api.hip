@@ -87,8 +87,8 @@ struct StatGroup {
     size_t slab_off;       // doubles into dSlabs
 };
 
-// How one sweep's launches meet, decided once by sweep_local_impl.  It is kept on the handle because sgp_sweep_local and
-// sgp_sweep_finish are separate calls, and a caller may run its own collective between them.
+// How one sweep's launches meet, decided once by sweep_plan and sweep_local_impl (or sweep_resident).  It is kept on the handle
+// because sgp_sweep_local and sgp_sweep_finish are separate calls, and a caller may run its own collective between them.
 struct SweepPlan {
     hipStream_t stream = nullptr;  // the stream the statistics are enqueued on
     bool overlapped = false;       // statistics in tile-row groups beside the Lambda chain (enqueue_stats_overlapped)
@@ -229,6 +229,18 @@ static void by_family(int32_t family, F&& f) {
         default: f(std::integral_constant<int, SGP_KERNEL_SE>{}); break;
     }
 }
+// d_out as a compile-time constant for the MultiSGP kernels (d_out >= 2): 2, 3, and 4 for everything else
+template <class F>
+static void by_dout(int dout, F&& f) {
+    switch (dout) {
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+
+// the point weights omega of the resident data (nullptr: all ones)
+static const double* omega_of(const sgp_handle* h) { return h->has_omega ? h->dOmega : nullptr; }
 
 // The only writers of sgp_handle::stats (see the table above StatsRecord).  stats_formed: a sweep has enqueued the statistics (or
 // relies on the resident ones) at the handle's current kernel values, data and W
@@ -273,6 +285,20 @@ static bool kernel_matches(const sgp_handle* h) {
 static int fail(sgp_handle* h, int code, const char* msg) {
     if (h) h->err = msg; else g_create_error = msg;
     return code;
+}
+
+// The status words of up to two factorisations as the ABI reports them: 0 when both are 0; SGP_ERR_HIP when either is negative
+// (a bounded wait for a twin workgroup gave up); else the failing leading minor of the first failed matrix, with the message
+// naming it.  `reversed`: the second matrix is Lambda, factored from its last row upwards -- its minor is reported in natural
+// order (needs the handle).
+static int factor_status(sgp_handle* h, int info_a, const char* name_a, int info_b = 0, const char* name_b = nullptr,
+                         bool reversed = false) {
+    if (info_a < 0 || info_b < 0)
+        return fail(h, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
+    if (info_a > 0) return fail(h, info_a, (std::string(name_a) + " is not positive definite").c_str());
+    if (info_b > 0)
+        return fail(h, reversed ? std::max(1, h->Qp - info_b + 1) : info_b, (std::string(name_b) + " is not positive definite").c_str());
+    return 0;
 }
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -463,6 +489,11 @@ static void launch_ata(const double* W, double* C, int ld, int Tn, hipStream_t s
     const int extra = uv ? Tn * Tn : 0;                  // pass 2 of Uv rides in the same launch (uv_cols_role)
     hipLaunchKernelGGL(k_gemm32, dim3(Tn * (Tn + 1) / 2 * 4 + extra), dim3(256), 0, s, W, W, C, ld, Tn, 0, 0, rev, mu, R, Psi2,
                        Kinv, trace_part, uv ? *uv : UvArgs{}, Sacc);
+}
+// C = A B, every tile (k_gemm32's plain product: mode 3, no epilogue)
+static void launch_gemm(const double* A, const double* B, double* C, int ld, int Tn, hipStream_t s) {
+    hipLaunchKernelGGL(k_gemm32, dim3(Tn * Tn * 4), dim3(256), 0, s, A, B, C, ld, Tn, 3, 0, 0, (const double*)nullptr, (double*)nullptr,
+                       (const double*)nullptr, (const double*)nullptr, (double*)nullptr, UvArgs{}, (const double*)nullptr);
 }
 
 
@@ -1082,8 +1113,7 @@ extern "C" int sgp_set_prior(sgp_handle* h, const double* vec, const double* mat
     int info = 0;
     HIPCHK(h, hipMemcpy(&info, h->dInfo + 2, sizeof(int), hipMemcpyDeviceToHost));
     h->prior_form = 1;
-    if (info > 0) { h->err = "sgp_set_prior: prior covariance is not positive definite"; return info; }
-    return 0;
+    return factor_status(h, info, "sgp_set_prior: prior covariance");
 }
 
 // prior <- posterior in natural form: Lambda0 += W (x) Psi2, xi0 += vec(B W).  The minibatch carry of
@@ -1132,6 +1162,22 @@ extern "C" int sgp_bind_stats(sgp_handle* h, void* stats_dev) {
 //   F2 (main stream) : Sigma, R, both traces, Uv pass 2, scalars                               [sgp_sweep_finish]
 // The two chains are latency-bound pivot sequences that use a handful of CUs each; they overlap only when they sit on
 // different streams.
+// k_prep_xu: the scaled inducing inputs Xus and the parameter mirror dP from `src`.  Optional roles (nullptr: not used): a status
+// word to clear, the phase stamps to open (all slots, the sweep's among them), a word to wait for, a gate word, and the status
+// word a wait that gives up reports into.
+static void launch_prep_xu(sgp_handle* h, hipStream_t s, double* Xus, const Params* src, Params* dP, int* info_reset = nullptr,
+                           int64_t* stamps = nullptr, const long long* wait_word = nullptr, long long wait_need = 0,
+                           const long long* gate_word = nullptr, long long gate_need = 0, int* sync_status = nullptr) {
+    hipLaunchKernelGGL(k_prep_xu, dim3((h->Mp + 255) / 256), dim3(256), 0, s, h->dXu, Xus, src, dP, info_reset, h->M, h->Mp, h->D, stamps,
+                       stamps ? (int)SGP_T_COUNT : 0, stamps ? (int)SGP_T_SWEEP : 0, wait_word, wait_need, gate_word, gate_need,
+                       h->spin_limit, sync_status);
+}
+// The CURRENT kernel parameters into the K_uu chain's mirror (dParamsK / dXusK: every sweep rewrites it first thing) for the
+// prediction entry points, not into dParams / dXus: those must keep the values of the last sweep, which sgp_carry_posterior and
+// the gradient of sgp_theta_objective at unchanged theta still read (a predict between set_noise and theta_objective
+// scaled the gradient by w_new / w_old twice).
+static void mirror_current_params(sgp_handle* h, hipStream_t s) { launch_prep_xu(h, s, h->dXusK, h->hParams, h->dParamsK); }
+
 // the K_uu chain in three pieces -- [k_prep_xu, Gram] [Cholesky steps + inverse factor] [K_uu^-1, join word] -- so that a sweep can
 // enqueue its two chains' steps alternately (enqueue_chains_interleaved)
 static void kuu_gram(sgp_handle* h, hipStream_t s, bool gate) {
@@ -1147,7 +1193,6 @@ static void kuu_tail(sgp_handle* h, hipStream_t s, bool join_word) {
 }
 // (on the side stream the chain waits for the previous sweep's done word first; on the main stream, stream order covers it)
 static void enqueue_kuu_head(sgp_handle* h, hipStream_t s) {
-    const int M = h->M, Mp = h->Mp, D = h->D;
     const bool words = s == h->side;
     // The gate (the chain's whole-CU workgroups stay off the chip until the SYRK's resident round is on it) sits inside k_prep_xu, in
     // front of K_uu's Gram: k_gram_uu_lds then starts together with the SYRK, gets a CU only as SYRK workgroups leave (it needs LDS, the
@@ -1157,11 +1202,8 @@ static void enqueue_kuu_head(sgp_handle* h, hipStream_t s) {
     // group 0's SYRK, or whole-CU workgroups in its tail, lengthens that SYRK, which is on the critical path, by more than the
     // K_uu chain gains (profiles/r04_ab_log.txt [1], [9]).
     const bool gate = words && h->gate_side;
-    hipLaunchKernelGGL(k_prep_xu, dim3((Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXusK, h->params_src,
-                       h->dParamsK, h->dInfo + 0, M, Mp, D, (int64_t*)nullptr, 0, 0,
-                       words ? (const long long*)(h->dJoin + WORD_DONE) : (const long long*)nullptr, h->done_epoch,
-                       gate ? (const long long*)(h->dJoin + WORD_GATE) : (const long long*)nullptr,
-                       h->gate_epoch, h->spin_limit, h->dInfo + 3);
+    launch_prep_xu(h, s, h->dXusK, h->params_src, h->dParamsK, h->dInfo + 0, nullptr, words ? h->dJoin + WORD_DONE : nullptr,
+                   h->done_epoch, gate ? h->dJoin + WORD_GATE : nullptr, h->gate_epoch, h->dInfo + 3);
     kuu_gram(h, s, gate);
 }
 static void enqueue_kuu(sgp_handle* h, hipStream_t s, bool join_word) {
@@ -1170,17 +1212,25 @@ static void enqueue_kuu(sgp_handle* h, hipStream_t s, bool join_word) {
     kuu_tail(h, s, join_word);
 }
 
-static void launch_gram(sgp_handle* h, hipStream_t s, bool opens_sweep) {
-    int64_t* sweep_begin = opens_sweep ? h->dStamps : nullptr;
+// K(Xu, X) of N points (and, d_out > 0, the B partials of Yw): k_gram_uf with the LDS panels sized to D (DCAP) and the handle's
+// family, one workgroup per tile row and 64-point block.  `stamps`, `sweep_begin`: the phase stamps it opens (nullptr: none).
+static void launch_gram_uf(const sgp_handle* h, hipStream_t s, const double* Xus, const double* X, const double* Yw, double* Kuf,
+                           double* bpart, const Params* P, int64_t N, int d_out, int64_t* stamps, int64_t* sweep_begin) {
+    const dim3 grid((unsigned)((N + TB - 1) / TB), h->T);
     by_family(h->family, [&](auto F) {
-        constexpr int FAM = decltype(F)::value;
-        if (h->D <= 8)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<8, FAM>), dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw, h->dKuf,
-                               h->dBpart, h->dParams, h->M, h->Mp, h->D, h->n, h->dout, h->dStamps + STAMP_STRIDE * SGP_T_GRAM, sweep_begin);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<MAXD, FAM>), dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw, h->dKuf,
-                               h->dBpart, h->dParams, h->M, h->Mp, h->D, h->n, h->dout, h->dStamps + STAMP_STRIDE * SGP_T_GRAM, sweep_begin);
+        auto launch = [&](auto DCAP) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<decltype(DCAP)::value, decltype(F)::value>), grid, dim3(256), 0, s, Xus, X, Yw,
+                               Kuf, bpart, P, h->M, h->Mp, h->D, N, d_out, stamps, sweep_begin);
+        };
+        if (h->D <= 8) launch(std::integral_constant<int, 8>{});
+        else launch(std::integral_constant<int, MAXD>{});
     });
+}
+// K_uf and the B partials of the resident data at the main stream's mirror; `stamped`: it opens the sweep's phase stamps
+// (sgp_time_kernel's launches open none)
+static void launch_gram(sgp_handle* h, hipStream_t s, bool stamped) {
+    launch_gram_uf(h, s, h->dXus, h->dX, h->dYw, h->dKuf, h->dBpart, h->dParams, h->n, h->dout,
+                   stamped ? h->dStamps + STAMP_STRIDE * SGP_T_GRAM : nullptr, stamped ? h->dStamps : nullptr);
 }
 
 // The scaled inducing inputs and the parameter mirror of the main stream (dXus, dParams) only change when a setter ran: a sweep
@@ -1189,9 +1239,7 @@ static void launch_gram(sgp_handle* h, hipStream_t s, bool opens_sweep) {
 // `info_reset`: a status word to clear as well (a sweep over resident statistics: the Lambda chain's, which k_assemble clears otherwise).
 static void prep_main(sgp_handle* h, hipStream_t s, bool always, int* info_reset = nullptr) {
     if (!always && h->main_prep_gen == h->params_gen) return;
-    hipLaunchKernelGGL(k_prep_xu, dim3((h->Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXus, h->params_src,
-                       h->dParams, info_reset, h->M, h->Mp, h->D, h->dStamps, (int)SGP_T_COUNT, (int)SGP_T_SWEEP,
-                       (const long long*)nullptr, 0LL, (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
+    launch_prep_xu(h, s, h->dXus, h->params_src, h->dParams, info_reset, h->dStamps);
     h->main_prep_gen = h->params_gen;
 }
 static void force_prep_main(sgp_handle* h) { h->main_prep_gen = 0; }   // (phase stamps were opened that no closing kernel folds)
@@ -1203,8 +1251,7 @@ static void enqueue_local(sgp_handle* h, hipStream_t s, bool pack) {
     if (h->n > 0) {
         launch_gram(h, s, true);
         long long* gate = h->gate_side ? h->dJoin + WORD_GATE : nullptr;
-        launch_syrk(h->geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs, Mp, h->n, h->dStamps + STAMP_STRIDE * SGP_T_SYRK,
-                    gate, h->gate_epoch);
+        launch_syrk(h->geom, s, h->dKuf, omega_of(h), h->dSlabs, Mp, h->n, h->dStamps + STAMP_STRIDE * SGP_T_SYRK, gate, h->gate_epoch);
     }
     SyrkGeom ga = h->geom;
     if (h->n <= 0) { ga = syrk_geometry(0, T, h->num_cus, 0); }       // no data: zero chunks, the statistics are zero
@@ -1249,7 +1296,7 @@ static int enqueue_stats_overlapped(sgp_handle* h, const SweepPlan& p) {
         const StatGroup& G = h->grp[g];
         hipStream_t s = G.masked ? h->statM : own;
         if (h->n > 0)
-            launch_syrk(G.geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs + G.slab_off, Mp, h->n,
+            launch_syrk(G.geom, s, h->dKuf, omega_of(h), h->dSlabs + G.slab_off, Mp, h->n,
                         h->dStamps + STAMP_STRIDE * SGP_T_SYRK, g == 0 ? h->dJoin + WORD_GATE : (long long*)nullptr, h->gate_epoch);
         hipLaunchKernelGGL(k_assemble, dim3(G.nrows, T + (g == 0 ? 1 : 0), assemble_z(G.geom)), dim3(256), 0, s, h->dSlabs + G.slab_off, h->dBpart,
                            h->dDataScal, sharded ? h->dPack : h->dStats, Mp, T, G.geom, h->nblk, h->dout,
@@ -1335,6 +1382,14 @@ static double* mirror_for(const sgp_handle* h) {
     return (h->hMirror && !h->env_no_zero_copy && !h->training) ? h->hMirror : nullptr;
 }
 
+// the TRACE_BLOCKS shares of tr(K_uu^-1 Psi2) into dTrace and of tr(R Psi2) behind them, in their own launches (MultiSGP's sweep, the
+// objective at a new theta; the UniSGP sweep takes both from the Sigma launch's epilogue)
+static void launch_traces(sgp_handle* h, hipStream_t s) {
+    hipLaunchKernelGGL(k_trace_kinv, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dKinv, h->dTrace, h->M, h->Mp);
+    hipLaunchKernelGGL(k_trace_R, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dR, h->dTrace + TRACE_BLOCKS, h->M, h->Mp, h->dout,
+                       h->Qp, (int64_t*)nullptr);
+}
+
 static void enqueue_finish2(sgp_handle* h, hipStream_t s, bool join_word) {
     const int M = h->M, Mp = h->Mp, Q = h->Q, Qp = h->Qp, TQ = h->TQ;
     double* uvp = h->dXi;
@@ -1360,9 +1415,7 @@ static void enqueue_finish2(sgp_handle* h, hipStream_t s, bool join_word) {
         nK = nR = nata;
     } else {
         launch_ata(h->dWl, h->dSigma, Qp, TQ, s, 1, h->dMu, h->dR, nullptr, nullptr, nullptr, &uv, h->dTmp);
-        hipLaunchKernelGGL(k_trace_kinv, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dKinv, h->dTrace, M, Mp);
-        hipLaunchKernelGGL(k_trace_R, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dR, traceR, M, Mp, h->dout, Qp,
-                           (int64_t*)nullptr);
+        launch_traces(h, s);
     }
     hipLaunchKernelGGL(k_scalars, dim3(1), dim3(256), 0, s, h->dStats, partK, nK, (const double*)traceR, nR, h->dMu, h->dKuu,
                        h->dLam, h->dInfo, h->dParams, h->dOut, h->dWishart, M, Mp, h->dout, Q, Qp, Qp - Q,
@@ -1428,28 +1481,40 @@ static int sweep_close(sgp_handle* h, hipStream_t s, const SweepPlan& p, bool jo
     return 0;
 }
 
-// `overlapped`: the statistics go to the handle's own statistics streams in tile-row groups and the Lambda chain (sgp_sweep_finish
-// on the library's stream) starts on the first group while the others are still being summed (plan_overlap); `interleave`: the
-// K_uu chain's steps may go out alternately with the Lambda chain's; `pack`: the statistics go to the exchange buffer.  All three
-// only from sgp_sweep, which owns both halves.
-static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool interleave, bool pack) {
+// Where a sweep's statistics go and how its streams meet, for the full sweep (sweep_local_impl) and the sweep over the resident
+// statistics (sweep_resident) alike.  `whole`: sgp_sweep, which owns both halves -- only it overlaps or packs.
+//   overlapped: single GPU or data-sharded, the library's own streams, a problem that qualifies (plan_overlap): the statistics go to
+//     the handle's statistics streams in tile-row groups, and the Lambda chain starts on the first group while the others are still
+//     being summed (an empty shard included, whose rank must issue the same collectives as the others).  The resident sweep forms
+//     its tile columns at the same steps (a column formed at a later step has collected its rank-64 updates first, i.e. in another
+//     order), so that its results are bitwise those of the full sweep.
+//   pack: the statistics go to the exchange buffer (an all-reduce hook is installed).
+//   events: the streams meet through events as well as device words.  The words are waited for with a BOUNDED spin (~1 s), and a
+//     collective that builds its rings or waits for a straggler rank may take longer than that: with an all-reduce hook, and on a
+//     caller's stream (two-phase callers -- sgp_sweep_local, their own reduce, sgp_sweep_finish -- may sit in a collective between
+//     the halves for as long).
+static SweepPlan sweep_plan(const sgp_handle* h, void* stream, bool whole) {
+    SweepPlan p;
+    p.stream = stream ? static_cast<hipStream_t>(stream) : h->own;
+    p.events = h->allreduce != nullptr || p.stream != h->own;
+    p.overlapped = whole && h->overlap && !stream && (h->n > 0 || h->allreduce) && !h->training;
+    p.pack = whole && h->allreduce != nullptr;
+    return p;
+}
+
+// the first half of a full sweep; `whole`: of sgp_sweep (sweep_plan), whose K_uu chain's steps may also go out alternately with the
+// Lambda chain's
+static int sweep_local_impl(sgp_handle* h, void* stream, bool whole) {
     int rc = check_ready(h);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    SweepPlan p;
-    p.stream = stream ? static_cast<hipStream_t>(stream) : h->own;
-    p.overlapped = overlapped;
-    p.pack = pack;
+    SweepPlan p = sweep_plan(h, stream, whole);
     if (int brc = sweep_begin(h)) return brc;
     // The K_uu chain depends on theta and Xu only: it starts on the (low-priority) side stream as soon as the previous
     // sweep has finished with its outputs, runs beside the data-sized kernels, the all-reduce and the Lambda chain, and is
     // joined just before the Sigma launch.  The streams meet through device words (the chain's first kernel waits for the
     // previous sweep's done word itself, see enqueue_kuu_head): an event record or wait between two kernels of a stream was
-    // measured at ~6 us of idle time.  A sweep with an all-reduce hook uses events in addition: the words are waited for with
-    // a BOUNDED spin (~1 s), and a collective that builds its rings or waits for a straggler rank may take longer than that.
-    // (a caller's stream as well: two-phase callers -- sgp_sweep_local, their own reduce, sgp_sweep_finish -- may sit in a collective
-    // between the halves for longer than the bounded words wait, exactly like the hook)
-    p.events = h->allreduce != nullptr || p.stream != h->own;
+    // measured at ~6 us of idle time -- and through events as well where the plan says so (sweep_plan).
     if (p.events) HIPCHK(h, hipStreamWaitEvent(h->side, h->evDone, 0));
     // How F2 will join the K_uu chain: an event wait between two kernels of the main stream costs it ~5 us of idle time even
     // when the event fired long ago, so the UniSGP path lets the Sigma launch's product workgroups poll a device word in
@@ -1462,7 +1527,7 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool i
         ++h->join_epoch;
     }
     ++h->gate_epoch;
-    if (overlapped) ++h->stat_epoch;                            // (what the words of this sweep's statistics groups receive)
+    if (p.overlapped) ++h->stat_epoch;                           // (what the words of this sweep's statistics groups receive)
     // Host order of the enqueues.  The K_uu chain is 14 launches (~50 us of host time).  Where it is gated behind the SYRK anyway
     // (gate_side) the data-sized kernels go out FIRST: a sweep that starts on an idle GPU -- the drop-in's pattern: sweep, fetch
     // something, next sweep -- otherwise has its Gram kernel wait ~50 us for the host to get through launches the GPU cannot run
@@ -1471,10 +1536,10 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool i
     const bool stats_first = h->gate_side && h->n > 0 && !h->allreduce;
     // (one-shot sgp_sweep on the library's streams: only the K_uu chain's first two kernels go out here, its steps are enqueued
     // alternately with the Lambda chain's by sgp_sweep_finish -- see enqueue_finish1)
-    p.kuu_interleaved = interleave && stats_first && !p.events;
+    p.kuu_interleaved = whole && h->env_interleave && stats_first && !p.events;
     h->plan = p;
     auto enqueue_stats = [&]() -> int {
-        if (overlapped) {
+        if (p.overlapped) {
             if (int orc = enqueue_stats_overlapped(h, p)) return orc;
         } else
             enqueue_local(h, p.stream, p.pack);
@@ -1496,7 +1561,7 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool overlapped, bool i
 }
 
 extern "C" int sgp_sweep_local(sgp_handle* h, void* stream) {
-    const int rc = sweep_local_impl(h, stream, false, false, false);
+    const int rc = sweep_local_impl(h, stream, false);
     if (h) stats_drop(h, STATS_REUSE);
     return rc;
 }
@@ -1562,14 +1627,9 @@ static int next_kind(sgp_handle* h, int32_t* kind) {
 // an all-reduce hook ONE reduce of the exchange buffer's tail), then phase 2 in plain stream order.  No K_uu chain, no join.
 static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    SweepPlan p;
-    p.stream = stream ? static_cast<hipStream_t>(stream) : h->own;
-    p.events = h->allreduce != nullptr || p.stream != h->own;
-    // The Lambda chain forms its tile columns at the steps a full sweep of this call would (sgp_sweep's overlapped order: a column
-    // formed at a later step has collected its rank-64 updates first, i.e. in another order), so that the results are bitwise
-    // that sweep's -- every column in stream order, nothing waited for.
-    p.overlapped = h->overlap && !stream && (h->n > 0 || h->allreduce) && !h->training;
-    p.pack = h->allreduce != nullptr;
+    // (the Lambda chain forms its tile columns at the steps the full sweep of this call would -- every column in stream order,
+    // nothing waited for)
+    SweepPlan p = sweep_plan(h, stream, true);
     p.resident = true;
     hipStream_t s = p.stream;
     if (int brc = sweep_begin(h)) return brc;
@@ -1578,16 +1638,15 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     prep_main(h, s, true, h->dInfo + 1);
     if (targets) {
         const int Mp = h->Mp, T = h->T;
-        const bool pack = h->allreduce != nullptr;
         if (h->n > 0)
             hipLaunchKernelGGL(k_bpart_kuf, dim3(h->nblk, (Mp + BPK_ROWS - 1) / BPK_ROWS), dim3(64), 0, s, (const double*)h->dKuf,
                                (const double*)h->dYw, h->dBpart, Mp, h->n, h->dout);
-        double* B = pack ? h->dPack + (size_t)h->ntiles * TB * TB : h->dStats + (size_t)Mp * Mp;
+        double* B = p.pack ? h->dPack + (size_t)h->ntiles * TB * TB : h->dStats + (size_t)Mp * Mp;
         hipLaunchKernelGGL(k_assemble_b, dim3(T * h->dout), dim3(256), 0, s, (const double*)h->dBpart, (const double*)h->dDataScal, B,
                            Mp, T, h->n > 0 ? h->nblk : 0, h->dout, SGP_S_COUNT + h->dout * h->dout,
                            h->dStamps + STAMP_STRIDE * SGP_T_LOCAL, h->dBred);
         HIPCHK(h, hipGetLastError());
-        if (pack)
+        if (p.pack)
             if (int xrc = exchange_stats(h, s, h->ntiles, 0, true)) return xrc;
     }
     HIPCHK(h, hipGetLastError());
@@ -1608,14 +1667,10 @@ extern "C" int sgp_sweep(sgp_handle* h, void* stream) {
         if (int rc = next_kind(h, &kind)) return rc;
         if (kind != SGP_SWEEP_FULL) return sweep_resident(h, stream, kind == SGP_SWEEP_TARGETS);
     }
-    // single GPU, the library's own streams, a problem that qualifies: statistics and Lambda chain overlapped
-    // (with an all-reduce hook as well: one reduce per statistics group, see enqueue_stats_overlapped -- an empty shard included,
-    // whose rank must issue the same collectives as the others)
-    const bool overlapped = h->overlap && !stream && (h->n > 0 || h->allreduce) && !h->training;
-    int rc = sweep_local_impl(h, stream, overlapped, h->env_interleave, h->allreduce != nullptr);
+    int rc = sweep_local_impl(h, stream, true);
     if (rc) return rc;
-    if (h->allreduce && !overlapped) {
-        rc = exchange_stats(h, stream ? static_cast<hipStream_t>(stream) : h->own);
+    if (h->plan.pack && !h->plan.overlapped) {              // (overlapped: one reduce per statistics group, enqueue_stats_overlapped)
+        rc = exchange_stats(h, h->plan.stream);
         if (rc) return rc;
     }
     rc = sgp_sweep_finish(h, stream);
@@ -1819,16 +1874,10 @@ extern "C" int sgp_get_scalars(sgp_handle* h, double* out) {
     if (int rc = sync_checked(h)) return rc;
     if (mirror_fresh(h)) memcpy(out, h->hMirror, SGP_R_COUNT * sizeof(double));
     else HIPCHK(h, hipMemcpy(out, h->dOut, SGP_R_COUNT * sizeof(double), hipMemcpyDeviceToHost));
-    if (out[SGP_R_INFO_KUU] < 0 || out[SGP_R_INFO_LAMBDA] < 0)
-        return fail(h, SGP_ERR_HIP, "the persistent factorisation launch gave up waiting (deadlock guard): its workgroups were not all resident");
-    if (out[SGP_R_INFO_KUU] > 0) { h->err = "K_uu is not positive definite"; return (int)out[SGP_R_INFO_KUU]; }
-    if (out[SGP_R_INFO_LAMBDA] > 0) {
-        // Lambda is factored from its last row upwards: report the natural index of the failing pivot
-        out[SGP_R_INFO_LAMBDA] = (double)(h->Qp - (int)out[SGP_R_INFO_LAMBDA] + 1);
-        h->err = "Lambda is not positive definite";
-        return (int)std::max(1.0, out[SGP_R_INFO_LAMBDA]);
-    }
-    return 0;
+    const int rc = factor_status(h, (int)out[SGP_R_INFO_KUU], "K_uu", (int)out[SGP_R_INFO_LAMBDA], "Lambda", true);
+    // (Lambda's failing pivot in natural order in the output as well)
+    if (out[SGP_R_INFO_KUU] == 0 && out[SGP_R_INFO_LAMBDA] > 0) out[SGP_R_INFO_LAMBDA] = (double)(h->Qp - (int)out[SGP_R_INFO_LAMBDA] + 1);
+    return rc;
 }
 
 extern "C" int sgp_get_posterior(sgp_handle* h, double* mu_v, double* Sigma_v, double* Uv) {
@@ -1838,10 +1887,7 @@ extern "C" int sgp_get_posterior(sgp_handle* h, double* mu_v, double* Sigma_v, d
     if (rc) return rc;
     int info[4];
     HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
-    if (info[0] < 0 || info[1] < 0)
-        return fail(h, SGP_ERR_HIP, "the persistent factorisation launch gave up waiting (deadlock guard): its workgroups were not all resident");
-    if (info[0] > 0) { h->err = "K_uu is not positive definite"; return info[0]; }
-    if (info[1] > 0) { h->err = "Lambda is not positive definite"; return std::max(1, h->Qp - info[1] + 1); }
+    if (int frc = factor_status(h, info[0], "K_uu", info[1], "Lambda", true)) return frc;
     const int Q = h->Q, Qp = h->Qp;
     if (mu_v) HIPCHK(h, hipMemcpy(mu_v, h->dMu, sizeof(double) * Q, hipMemcpyDeviceToHost));
     if (Sigma_v) { rc = download_square(h, h->dSigma, Qp, Q, Sigma_v); if (rc) return rc; }
@@ -1972,21 +2018,11 @@ extern "C" int sgp_time_kernel(sgp_handle* h, int32_t which, int32_t iters, void
         if (qmode >= 0)
             launch_quadform(h, s);
         else if (G)
-            launch_syrk(G->geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs + G->slab_off, h->Mp, h->n, (int64_t*)nullptr,
-                        (long long*)nullptr, 0LL);
+            launch_syrk(G->geom, s, h->dKuf, omega_of(h), h->dSlabs + G->slab_off, h->Mp, h->n, (int64_t*)nullptr, (long long*)nullptr, 0LL);
         else if (which == SGP_T_GRAM)
-            by_family(h->family, [&](auto F) {
-                constexpr int FAM = decltype(F)::value;
-                if (h->D <= 8)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<8, FAM>), dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw,
-                                       h->dKuf, h->dBpart, h->dParams, h->M, h->Mp, h->D, h->n, h->dout, (int64_t*)nullptr, (int64_t*)nullptr);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<MAXD, FAM>), dim3(h->nblk, h->T), dim3(256), 0, s, h->dXus, h->dX, h->dYw,
-                                       h->dKuf, h->dBpart, h->dParams, h->M, h->Mp, h->D, h->n, h->dout, (int64_t*)nullptr, (int64_t*)nullptr);
-            });
+            launch_gram(h, s, false);
         else
-            launch_syrk(h->geom, s, h->dKuf, h->has_omega ? h->dOmega : nullptr, h->dSlabs, h->Mp, h->n, (int64_t*)nullptr,
-                        (long long*)nullptr, 0LL);
+            launch_syrk(h->geom, s, h->dKuf, omega_of(h), h->dSlabs, h->Mp, h->n, (int64_t*)nullptr, (long long*)nullptr, 0LL);
     };
     if (!G && qmode < 0 && which != SGP_T_GRAM && which != SGP_T_SYRK)
         return fail(h, SGP_ERR_ARG, "sgp_time_kernel: which must be SGP_T_GRAM, SGP_T_SYRK or SGP_TIME_GROUP0 + g");
@@ -2063,24 +2099,26 @@ extern "C" int sgp_w_stats(sgp_handle* h, double* I1, double* I2, void* stream) 
 // ------------------------------------------------------------------------------------------------
 // prediction
 // ------------------------------------------------------------------------------------------------
-// (the SE family has forms for D = 1, 2, 3, 4 and 8; the others only the generic one: DT = 0)
-template <int DT>
-static void launch_predict(sgp_handle* h, const double* dXs, const double* dMu, double* dMean, int64_t ns, hipStream_t s) {
-    by_family(h->family, [&](auto F) {
-        constexpr int FAM = decltype(F)::value, DTF = FAM == SGP_KERNEL_SE ? DT : 0;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<DTF, FAM>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, h->dXusK, dXs,
-                           dMu, dMean, h->dParamsK, h->M, h->Mp, h->D, ns, h->dout);
-    });
-}
-
-// (the same on the MAIN stream's copies of the scaled inducing inputs / parameters: the classification training step's forward message)
-template <int DT>
-static void launch_predict_main(sgp_handle* h, const double* dXs, const double* dMu, double* dMean, int64_t ns, hipStream_t s) {
-    by_family(h->family, [&](auto F) {
-        constexpr int FAM = decltype(F)::value, DTF = FAM == SGP_KERNEL_SE ? DT : 0;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<DTF, FAM>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, h->dXus, dXs,
-                           dMu, dMean, h->dParams, h->M, h->Mp, h->D, ns, h->dout);
-    });
+// the predictive mean k(X*, Xu) mu of ns points at the scaled inducing inputs Xus and parameter mirror P (the K_uu chain's for
+// sgp_predict / sgp_predict_var, the main stream's for the classification training step's forward message).  The SE family has
+// forms for D = 1, 2, 3, 4 and 8; the others only the generic one: DT = 0.
+static void launch_predict(const sgp_handle* h, hipStream_t s, const double* Xus, const Params* P, const double* dXs, const double* dMu,
+                           double* dMean, int64_t ns) {
+    auto launch = [&](auto DT) {
+        by_family(h->family, [&](auto F) {
+            constexpr int FAM = decltype(F)::value, DTF = FAM == SGP_KERNEL_SE ? decltype(DT)::value : 0;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<DTF, FAM>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, Xus, dXs, dMu,
+                               dMean, P, h->M, h->Mp, h->D, ns, h->dout);
+        });
+    };
+    switch (h->D) {
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        case 3: launch(std::integral_constant<int, 3>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        case 8: launch(std::integral_constant<int, 8>{}); break;
+        default: launch(std::integral_constant<int, 0>{}); break;
+    }
 }
 
 extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, double* mean) {
@@ -2101,21 +2139,8 @@ extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const
         HIPCHK(h, hipMemcpy(dMuTmp, mu_v, sizeof(double) * h->Q, hipMemcpyHostToDevice));
         dMu = dMuTmp;
     }
-    // The CURRENT kernel parameters go into the K_uu chain's mirror (dParamsK / dXusK: every sweep rewrites it first thing), not
-    // into dParams / dXus: those must keep the values of the last sweep, which sgp_carry_posterior and the gradient of
-    // sgp_theta_objective at unchanged theta still read (a predict between set_noise and theta_objective scaled
-    // the gradient by w_new / w_old twice).
-    hipLaunchKernelGGL(k_prep_xu, dim3((h->Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXusK, (const Params*)h->hParams,
-                       h->dParamsK, (int*)nullptr, h->M, h->Mp, h->D, (int64_t*)nullptr, 0, 0, (const long long*)nullptr, 0LL,
-                       (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
-    switch (h->D) {
-        case 1: launch_predict<1>(h, dXs, dMu, dMean, ns, s); break;
-        case 2: launch_predict<2>(h, dXs, dMu, dMean, ns, s); break;
-        case 3: launch_predict<3>(h, dXs, dMu, dMean, ns, s); break;
-        case 4: launch_predict<4>(h, dXs, dMu, dMean, ns, s); break;
-        case 8: launch_predict<8>(h, dXs, dMu, dMean, ns, s); break;
-        default: launch_predict<0>(h, dXs, dMu, dMean, ns, s); break;
-    }
+    mirror_current_params(h, s);
+    launch_predict(h, s, h->dXusK, h->dParamsK, dXs, dMu, dMean, ns);
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy(mean, dMean, sizeof(double) * ns * h->dout, hipMemcpyDeviceToHost));
@@ -2127,16 +2152,6 @@ extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const
 // dSaccK, dWl, the log-det slot and dInfo stay what SGP_FLAG_REUSE_STATS and sgp_theta_objective expect); only the parameter mirror
 // dXusK / dParamsK is rewritten, as sgp_predict does.  The test points go through in chunks, so that the scratch stays bounded.
 constexpr int64_t PREDICT_CHUNK_DOUBLES = int64_t(1) << 25;     // scratch of one chunk: 256 MB
-template <int DT>
-static void launch_gram_star(sgp_handle* h, const double* dXs, double* dK, int64_t nc, hipStream_t s) {
-    // (d_out = 0: no targets, no B partial -- k_gram_uf's K tile alone, in its summation order)
-    by_family(h->family, [&](auto F) {
-        constexpr int FAM = decltype(F)::value;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_uf<DT, FAM>), dim3((unsigned)((nc + TB - 1) / TB), h->T), dim3(256), 0, s, h->dXusK,
-                           dXs, (const double*)nullptr, dK, (double*)nullptr, h->dParamsK, h->M, h->Mp, h->D, nc, 0, (int64_t*)nullptr,
-                           (int64_t*)nullptr);
-    });
-}
 
 extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
                                int32_t flags, double* mean, double* var) {
@@ -2155,9 +2170,7 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
         if (int src = check_sync_status(h)) return src;
         int info[2];
         HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
-        if (info[0] < 0 || info[1] < 0) return fail(h, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
-        if (info[0] > 0) { h->err = "K_uu is not positive definite (last sweep)"; return info[0]; }
-        if (info[1] > 0) { h->err = "Lambda is not positive definite (last sweep)"; return std::max(1, h->Qp - info[1] + 1); }
+        if (int frc = factor_status(h, info[0], "K_uu (last sweep)", info[1], "Lambda (last sweep)", true)) return frc;
     }
     hipStream_t s = h->own;
     const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T, TQ = h->TQ;
@@ -2200,9 +2213,7 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
     }
     HIPCHK(h, hipMemsetAsync(dPscr, 0, sizeof(double) * (2 * POTRF_SCRATCH + 64), s));
     // the current parameters into the K_uu chain's mirror (as sgp_predict), K_uu at them and its inverse factor, Sigma_v's factor
-    hipLaunchKernelGGL(k_prep_xu, dim3((Mp + 255) / 256), dim3(256), 0, s, h->dXu, h->dXusK, (const Params*)h->hParams,
-                       h->dParamsK, (int*)nullptr, M, Mp, D, (int64_t*)nullptr, 0, 0, (const long long*)nullptr, 0LL,
-                       (const long long*)nullptr, 0LL, h->spin_limit, (int*)nullptr);
+    mirror_current_params(h, s);
     by_family(h->family, [&](auto F) {
         hipLaunchKernelGGL(k_gram_uu<decltype(F)::value>, dim3(T, T), dim3(256), 0, s, h->dXusK, dKuuS, h->dParamsK, M, Mp, D);
     });
@@ -2212,9 +2223,7 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
     HIPCHK(h, hipGetLastError());
     int info[2];
     HIPCHK(h, hipMemcpy(info, dInfoS, sizeof info, hipMemcpyDeviceToHost));
-    if (info[0] < 0 || info[1] < 0) return fail(h, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
-    if (info[0] > 0) { h->err = "K_uu is not positive definite (current kernel)"; return info[0]; }
-    if (info[1] > 0) { h->err = "Sigma_v is not positive definite"; return info[1]; }
+    if (int frc = factor_status(h, info[0], "K_uu (current kernel)", info[1], "Sigma_v")) return frc;
     // the observation noise W^-1 (of the last sgp_set_noise), added in the finishing kernel: 0 without the flag
     OutMat noise;
     memset(&noise, 0, sizeof noise);
@@ -2247,33 +2256,22 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
         const unsigned nblk = (unsigned)((nc + TB - 1) / TB);
         HIPCHK(h, hipMemcpyAsync(dXs, Xstar + (size_t)s0 * D, sizeof(double) * nc * D, hipMemcpyHostToDevice, s));
         // the mean: sgp_predict's kernel on the same mirror, so it is bitwise sgp_predict's
-        switch (D) {
-            case 1: launch_predict<1>(h, dXs, dMu, dMeanC, nc, s); break;
-            case 2: launch_predict<2>(h, dXs, dMu, dMeanC, nc, s); break;
-            case 3: launch_predict<3>(h, dXs, dMu, dMeanC, nc, s); break;
-            case 4: launch_predict<4>(h, dXs, dMu, dMeanC, nc, s); break;
-            case 8: launch_predict<8>(h, dXs, dMu, dMeanC, nc, s); break;
-            default: launch_predict<0>(h, dXs, dMu, dMeanC, nc, s); break;
-        }
-        if (D <= 8) launch_gram_star<8>(h, dXs, dKc, nc, s);
-        else launch_gram_star<MAXD>(h, dXs, dKc, nc, s);
+        launch_predict(h, s, h->dXusK, h->dParamsK, dXs, dMu, dMeanC, nc);
+        // K(Xu, X*) (d_out = 0: no targets, no B partial -- k_gram_uf's K tile alone, in its summation order)
+        launch_gram_uf(h, s, h->dXusK, dXs, nullptr, dKc, nullptr, h->dParamsK, nc, 0, nullptr, nullptr);
         // |W_K k*|^2 -> pa and, for d_out = 1, |L_S' k*|^2 -> pb: k_quadform_fused as sgp_w_stats runs it, with L_S where that
         // passes Uv' (its k . mu rows go to kmu, unused).  MultiSGP needs cross terms instead of the second form: the launch then
         // repeats W_K there (its pb is not read) and k_predvar_multi forms them.
         hipLaunchKernelGGL(k_quadform_fused, dim3(nblk, 2 * T), dim3(256), 0, s, (const double*)dWkS, dout == 1 ? (const double*)dLS : dWkS,
                            (const double*)dKc, dMu, dPa, dPb, dKmu, Mp, T, nc);
-        switch (dout) {
-            case 1:
-                hipLaunchKernelGGL(k_predvar_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)dPa,
-                                   (const double*)dPb, dVarC, (const Params*)h->dParamsK, noise.v[0], T, nc);
-                break;
-            case 2: hipLaunchKernelGGL(k_predvar_multi<2>, dim3(nblk), dim3(256), 0, s, (const double*)dLS, (const double*)dKc,
-                                       (const double*)dPa, dVarC, (const Params*)h->dParamsK, noise, M, Mp, Q, Qp, T, nc); break;
-            case 3: hipLaunchKernelGGL(k_predvar_multi<3>, dim3(nblk), dim3(256), 0, s, (const double*)dLS, (const double*)dKc,
-                                       (const double*)dPa, dVarC, (const Params*)h->dParamsK, noise, M, Mp, Q, Qp, T, nc); break;
-            default: hipLaunchKernelGGL(k_predvar_multi<4>, dim3(nblk), dim3(256), 0, s, (const double*)dLS, (const double*)dKc,
-                                        (const double*)dPa, dVarC, (const Params*)h->dParamsK, noise, M, Mp, Q, Qp, T, nc); break;
-        }
+        if (dout == 1)
+            hipLaunchKernelGGL(k_predvar_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)dPa,
+                               (const double*)dPb, dVarC, (const Params*)h->dParamsK, noise.v[0], T, nc);
+        else
+            by_dout(dout, [&](auto DO) {
+                hipLaunchKernelGGL(k_predvar_multi<decltype(DO)::value>, dim3(nblk), dim3(256), 0, s, (const double*)dLS, (const double*)dKc,
+                                   (const double*)dPa, dVarC, (const Params*)h->dParamsK, noise, M, Mp, Q, Qp, T, nc);
+            });
         HIPCHK(h, hipGetLastError());
         // mean chunk: [d_out][nc] on the device -> rows s0 .. of the ns x d_out column-major output; var chunk: contiguous
         HIPCHK(h, hipMemcpy2DAsync(mean + s0, sizeof(double) * ns, dMeanC, sizeof(double) * nc, sizeof(double) * nc, dout,
@@ -2338,38 +2336,31 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
     if (split)
         hipLaunchKernelGGL(k_join_wait, dim3(1), dim3(64), 0, su, (const long long*)(h->dJoin + WORD_DONE), h->done_epoch,
                            h->spin_limit, h->dInfo + 3, (int)SYNC_LATE_GRAD_START, 8);
-    hipLaunchKernelGGL(k_gemm32, dim3(T * T * 4), dim3(256), 0, su, (const double*)h->dKinv, (const double*)h->dStats, dT1,
-                       Mp, T, 3, 0, 0, (const double*)nullptr, (double*)nullptr, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, UvArgs{}, (const double*)nullptr);
-    hipLaunchKernelGGL(k_gemm32, dim3(T * T * 4), dim3(256), 0, su, (const double*)dT1, (const double*)h->dKinv, dH, Mp, T,
-                       3, 0, 0, (const double*)nullptr, (double*)nullptr, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, UvArgs{}, (const double*)nullptr);
+    launch_gemm(h->dKinv, h->dStats, dT1, Mp, T, su);
+    launch_gemm(dT1, h->dKinv, dH, Mp, T, su);
     by_family(h->family, [&](auto F) {
         hipLaunchKernelGGL(k_theta_grad_uu<decltype(F)::value>, dim3(T, T), dim3(256), 0, su, dH, h->dXus, h->dParams, part_uu, h->M,
                            Mp, h->D);
     });
     if (split) hipLaunchKernelGGL(k_join_set, dim3(1), dim3(64), 0, su, h->dJoin + WORD_GRAD, ++h->grad_epoch);
-    if (h->dout == 1) {
-        hipLaunchKernelGGL(k_form_G, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, h->dR, h->dKinv, dG, cnt);
-        if (h->n > 0)
+    const bool multi = h->dout > 1;
+    if (!multi) hipLaunchKernelGGL(k_form_G, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, h->dR, h->dKinv, dG, cnt);
+    if (h->n > 0) {
+        // (MultiSGP: G (= S - tr(W) K_uu^-1), omega W y and the padded mean columns were formed by enqueue_theta_multi_value)
+        const double* yw = h->dYw;
+        const double* mu = h->dMu;
+        if (multi) {
+            yw = h->dThetaMulti + 2 * (size_t)h->Qp * h->Qp;
+            mu = yw + (size_t)h->dout * (size_t)std::max<int64_t>(h->n_max, 1);
+        }
+        auto launch = [&](auto DO) {
             by_family(h->family, [&](auto F) {
-                hipLaunchKernelGGL(k_theta_grad_uf<decltype(F)::value>, dim3(h->nblk, T, KS), dim3(256), 0, s, dG, h->dKuf, h->dX,
-                                   h->dXus, h->dYw, h->has_omega ? h->dOmega : nullptr, h->dMu, h->dParams, part_uf, Mp, T, h->D, h->n);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_theta_grad_uf<decltype(F)::value, decltype(DO)::value>), dim3(h->nblk, T, KS), dim3(256),
+                                   0, s, dG, h->dKuf, h->dX, h->dXus, yw, omega_of(h), mu, h->dParams, part_uf, Mp, T, h->D, h->n);
             });
-    } else if (h->n > 0) {
-        // MultiSGP: G (= S - tr(W) K_uu^-1), omega W y and the padded mean columns were formed by enqueue_theta_multi_value
-        const double* cw = h->dThetaMulti + 2 * (size_t)h->Qp * h->Qp;
-        const double* mup = cw + (size_t)h->dout * (size_t)std::max<int64_t>(h->n_max, 1);
-        by_family(h->family, [&](auto F) {
-            constexpr int FAM = decltype(F)::value;
-            const dim3 grid(h->nblk, T, KS);
-            switch (h->dout) {
-                case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_theta_grad_uf<FAM, 2>), grid, dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus, cw,
-                                           h->has_omega ? h->dOmega : nullptr, mup, h->dParams, part_uf, Mp, T, h->D, h->n); break;
-                case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_theta_grad_uf<FAM, 3>), grid, dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus, cw,
-                                           h->has_omega ? h->dOmega : nullptr, mup, h->dParams, part_uf, Mp, T, h->D, h->n); break;
-                default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_theta_grad_uf<FAM, 4>), grid, dim3(256), 0, s, dG, h->dKuf, h->dX, h->dXus, cw,
-                                            h->has_omega ? h->dOmega : nullptr, mup, h->dParams, part_uf, Mp, T, h->D, h->n); break;
-            }
-        });
+        };
+        if (multi) by_dout(h->dout, launch);
+        else launch(std::integral_constant<int, 1>{});
     }
     // Data-sharded run (an all-reduce hook is installed; the statistics in dStats are the reduced ones): the data half above used
     // this rank's K_uf, X and y -- its fixed-order total (1 + D doubles) is summed over the ranks through the same hook; the
@@ -2383,16 +2374,14 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
         uf_src = tot;
         uf_blocks = 1;
     }
-    if (h->dout == 1)
-        hipLaunchKernelGGL(k_theta_grad_finish<false>, dim3(1), dim3(256), 0, s, uf_src, uf_blocks, part_uu, T * T,
+    auto finish = [&](auto MULTI) {
+        hipLaunchKernelGGL(k_theta_grad_finish<decltype(MULTI)::value>, dim3(1), dim3(256), 0, s, uf_src, uf_blocks, part_uu, T * T,
                            h->dStats + (size_t)Mp * Mp + (size_t)Mp * h->dout, h->dParams, h->dGrad, h->D, h->n_ell,
                            split ? (const long long*)(h->dJoin + WORD_GRAD) : (const long long*)nullptr, h->grad_epoch, h->spin_limit,
-                           h->dInfo + 3, 0.0);
-    else
-        hipLaunchKernelGGL(k_theta_grad_finish<true>, dim3(1), dim3(256), 0, s, uf_src, uf_blocks, part_uu, T * T,
-                           h->dStats + (size_t)Mp * Mp + (size_t)Mp * h->dout, h->dParams, h->dGrad, h->D, h->n_ell,
-                           split ? (const long long*)(h->dJoin + WORD_GRAD) : (const long long*)nullptr, h->grad_epoch, h->spin_limit,
-                           h->dInfo + 3, theta_trace_W(h));
+                           h->dInfo + 3, multi ? theta_trace_W(h) : 0.0);
+    };
+    if (multi) finish(std::true_type{});
+    else finish(std::false_type{});
     return 0;
 }
 
@@ -2417,9 +2406,7 @@ static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s) {
     const double* R = h->dR;
     if (h->posterior_set) {     // R_v = Uv^T Uv: dUvT holds Uv^T (identity-padded); the pad rows / columns are not read
         hipLaunchKernelGGL(k_transpose, dim3(TQ, TQ), dim3(256), 0, s, (const double*)h->dUvT, dUv, Qp);
-        hipLaunchKernelGGL(k_gemm32, dim3(TQ * TQ * 4), dim3(256), 0, s, (const double*)h->dUvT, (const double*)dUv, dRs, Qp, TQ,
-                           3, 0, 0, (const double*)nullptr, (double*)nullptr, (const double*)nullptr, (const double*)nullptr,
-                           (double*)nullptr, UvArgs{}, (const double*)nullptr);
+        launch_gemm(h->dUvT, dUv, dRs, Qp, TQ, s);
         R = dRs;
     }
     const int64_t nprep = std::max<int64_t>(h->n, Mp);
@@ -2453,15 +2440,14 @@ static int theta_objective_multi(sgp_handle* h, hipStream_t s, bool fresh, doubl
     if (fresh) {
         double out[SGP_R_COUNT];
         HIPCHK(h, hipMemcpy(out, h->dOut, sizeof out, hipMemcpyDeviceToHost));
-        if (out[SGP_R_INFO_KUU] > 0) { h->err = "K_uu is not positive definite"; return (int)out[SGP_R_INFO_KUU]; }
+        if (int frc = factor_status(h, (int)out[SGP_R_INFO_KUU], "K_uu")) return frc;
     } else {
         if (int erc = enqueue_restats(h, s)) return erc;     // (no hook here: sgp_theta_objective refuses d_out > 1 with one)
         HIPCHK(h, hipStreamSynchronize(s));
         HIPCHK(h, hipGetLastError());
         int info = 0;
         HIPCHK(h, hipMemcpy(&info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
-        if (info < 0) return fail(h, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
-        if (info > 0) { h->err = "K_uu is not positive definite"; return info; }
+        if (int frc = factor_status(h, info, "K_uu")) return frc;
     }
     if (int vrc = enqueue_theta_multi_value(h, s)) return vrc;
     if (grad)
@@ -2479,9 +2465,7 @@ static int theta_objective_multi(sgp_handle* h, hipStream_t s, bool fresh, doubl
 static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value) {
     if (int erc = enqueue_restats(h, s)) return erc;
     const int M = h->M, Mp = h->Mp, Q = h->Q, Qp = h->Qp;
-    hipLaunchKernelGGL(k_trace_kinv, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dKinv, h->dTrace, M, Mp);
-    hipLaunchKernelGGL(k_trace_R, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dR, h->dTrace + TRACE_BLOCKS, M, Mp, h->dout,
-                       Qp, (int64_t*)nullptr);
+    launch_traces(h, s);
     hipLaunchKernelGGL(k_scalars, dim3(1), dim3(256), 0, s, h->dStats, (const double*)h->dTrace, (int)TRACE_BLOCKS,
                        (const double*)(h->dTrace + TRACE_BLOCKS), (int)TRACE_BLOCKS, h->dMu, h->dKuu, h->dLam, h->dInfo, h->dParams,
                        h->dOut2, h->dWishart, M, Mp, h->dout, Q, Qp, Qp - Q, (int64_t*)nullptr, (int64_t*)nullptr,
@@ -2491,7 +2475,7 @@ static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value) {
     double out[SGP_R_COUNT], sc[SGP_S_COUNT];
     HIPCHK(h, hipMemcpy(out, h->dOut2, sizeof out, hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(sc, h->dStats + (size_t)Mp * Mp + (size_t)Mp * h->dout, sizeof sc, hipMemcpyDeviceToHost));
-    if (out[SGP_R_INFO_KUU] > 0) { h->err = "K_uu is not positive definite"; return (int)out[SGP_R_INFO_KUU]; }
+    if (int frc = factor_status(h, (int)out[SGP_R_INFO_KUU], "K_uu")) return frc;
     *value = 0.5 * h->hParams->W[0] * (out[SGP_R_SUM_I1] + out[SGP_R_SUM_I2] - sc[SGP_S_YY]);
     return 0;
 }
@@ -2520,7 +2504,7 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
         double out[SGP_R_COUNT], sc[SGP_S_COUNT];
         HIPCHK(h, hipMemcpy(out, h->dOut, sizeof out, hipMemcpyDeviceToHost));
         HIPCHK(h, hipMemcpy(sc, h->dStats + (size_t)h->Mp * h->Mp + (size_t)h->Mp * h->dout, sizeof sc, hipMemcpyDeviceToHost));
-        if (out[SGP_R_INFO_KUU] > 0) { h->err = "K_uu is not positive definite"; return (int)out[SGP_R_INFO_KUU]; }
+        if (int frc = factor_status(h, (int)out[SGP_R_INFO_KUU], "K_uu")) return frc;
         *value = 0.5 * h->hParams->W[0] * (out[SGP_R_SUM_I1] + out[SGP_R_SUM_I2] - sc[SGP_S_YY]);
         if (!grad) return 0;
     } else {
@@ -2661,16 +2645,7 @@ extern "C" int sgp_train_step(sgp_handle* h, int64_t offset, int64_t n, int32_t 
         // q(f) of the window: forward message from the carried posterior mean at the current theta, then the Probit moments
         prep_main(h, s, false);                                // (theta moved, so it runs; the sweep below starts with its Gram kernel)
         double* mz = h->dCall;
-        if (n > 0) {
-            switch (h->D) {
-                case 1: launch_predict_main<1>(h, h->dX, h->dMu, mz, n, s); break;
-                case 2: launch_predict_main<2>(h, h->dX, h->dMu, mz, n, s); break;
-                case 3: launch_predict_main<3>(h, h->dX, h->dMu, mz, n, s); break;
-                case 4: launch_predict_main<4>(h, h->dX, h->dMu, mz, n, s); break;
-                case 8: launch_predict_main<8>(h, h->dX, h->dMu, mz, n, s); break;
-                default: launch_predict_main<0>(h, h->dX, h->dMu, mz, n, s); break;
-            }
-        }
+        if (n > 0) launch_predict(h, s, h->dXus, h->dParams, h->dX, h->dMu, mz, n);
         hipLaunchKernelGGL(k_probit_window, dim3(1), dim3(256), 0, s, (const double*)(h->dTrainY + offset), (const double*)mz, n,
                            (const TrainState*)h->dTrain, h->dY, h->dYw, h->dYv, h->dDataScal, (int)SGP_S_COUNT + 1);
     }
@@ -2802,13 +2777,13 @@ static int dense_common(int32_t device, const double* A, int32_t n, double* out,
     HIPCHK(h, hipGetLastError());
     int info = 0;
     HIPCHK(h, hipMemcpy(&info, bInfo.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (info < 0) return fail(nullptr, SGP_ERR_HIP, "the factorisation gave up waiting for a twin workgroup (deadlock guard)");
+    const int status = factor_status(h, info, "matrix");
+    if (status < 0) return status;                 // (a factorisation that gave up has no result to copy)
     HIPCHK(h, hipMemcpy2D(out, sizeof(double) * n, result, sizeof(double) * np, sizeof(double) * n, n, hipMemcpyDeviceToHost));
     if (!inverse)
         for (int j = 0; j < n; ++j)
             for (int i = 0; i < j; ++i) out[(size_t)j * n + i] = 0.0;
-    if (info > 0) { g_create_error = "matrix is not positive definite"; return info; }
-    return 0;
+    return status;
 }
 
 extern "C" int sgp_potrf(int32_t device, const double* A, int32_t n, double* L) { return dense_common(device, A, n, L, false); }

@@ -172,7 +172,7 @@ def test_theta_gradient_matches_oracle(G, D, iso, weighted):
 
 
 # ------------------------------------------------------------------------------------------------
-# prediction: sgp_predict (k_predict<0> for D = 5, 6, 7, 9..32) and sgp_predict_var (launch_gram_star<MAXD> for D > 8) against the
+# prediction: sgp_predict (k_predict<0> for D = 5, 6, 7, 9..32) and sgp_predict_var (k_gram_uf<MAXD> for D > 8) against the
 # reference of test_gpu_predict_var.py; k_kernelmatrix
 
 @gpu

@@ -437,6 +437,8 @@ static void launch_syrk(const SyrkGeom& g, hipStream_t s, const double* Kuf, con
 struct PotrfSeq {
     double* A; int ld, Tn; int* info; int n_valid; double* scratch; hipStream_t s;
     double* Winv; LamForm form; bool has_form; double* Sacc; const double* tv_xi; double* tv_t; const hipEvent_t* step_wait;
+    double* mu_acc = nullptr;       // (needs tv_t) the running mu = P W^T t, collected block row by block row (mu_row_tile) ...
+    double* uv_part = nullptr;      // ... and the same terms as pass 1 of Uv
     int j = 0;
     PotrfSeq(double* A_, int ld_, int Tn_, int* info_, int n_valid_, double* scratch_, hipStream_t s_, double* Winv_ = nullptr,
              const LamForm* form_ = nullptr, double* Sacc_ = nullptr, const double* tv_xi_ = nullptr, double* tv_t_ = nullptr,
@@ -448,7 +450,8 @@ struct PotrfSeq {
     }
     // extra workgroups of launch j: (j >= 2) finish block row j - 1 of W, pre-accumulate block row j (not in the last,
     // potrf-free launch j = Tn), with Sacc add block row j - 2's contribution to Sigma = W^T W; (j >= 1, with tv_t) one
-    // workgroup computes block j - 1 of the forward solve t = W (P xi)
+    // workgroup computes block j - 1 of the forward solve t = W (P xi); (j >= 2, with mu_acc) j - 1 short workgroups add block row
+    // j - 2's term of mu = P W^T t
     int extras(int jj) const {
         if (!Winv) return 0;
         int e = 0;
@@ -457,6 +460,7 @@ struct PotrfSeq {
             if (Sacc && jj < Tn) e += (jj - 1) * jj / 2;           // (row Tn - 2 of Sigma: left to the product launch, see k_potrf_step)
         }
         if (tv_t && jj >= 1) e += 1;
+        if (tv_t && mu_acc && jj >= 2) e += jj - 1;
         return e;
     }
     bool done() const { return j > Tn; }
@@ -468,10 +472,10 @@ struct PotrfSeq {
             const int nt = Tn - j;
             if (step_wait && step_wait[j]) (void)hipStreamWaitEvent(s, step_wait[j], 0);
             hipLaunchKernelGGL(k_potrf_step, dim3(nt * (nt + 1) / 2 + potrf_twins(Tn, j) + extras(j)), dim3(PSTEP_THREADS), 0, s, A, ld, j, Tn, info,
-                               n_valid, scratch, Winv, Sacc, tv_xi, tv_t, has_form ? form : none);   // (every step: a tile column may be formed later than step 0)
+                               n_valid, scratch, Winv, Sacc, tv_xi, tv_t, mu_acc, uv_part, has_form ? form : none);   // (every step: a tile column may be formed later than step 0)
         } else if (j == Tn && Winv && extras(Tn) > 0) {
             hipLaunchKernelGGL(k_potrf_step, dim3(extras(Tn)), dim3(PSTEP_THREADS), 0, s, A, ld, Tn, Tn, info, n_valid, scratch, Winv, Sacc,
-                               tv_xi, tv_t, none);
+                               tv_xi, tv_t, mu_acc, uv_part, none);
         }
         ++j;
     }
@@ -483,16 +487,17 @@ static void launch_potrf(double* A, int ld, int Tn, int* info, int n_valid, doub
     while (!q.done()) q.next();
 }
 
-static void launch_ata(const double* W, double* C, int ld, int Tn, hipStream_t s, int rev = 0, const double* mu = nullptr,
+static void launch_ata(const double* W, double* C, int ld, int Tn, hipStream_t s, int rev = 0, double* mu = nullptr,
                        double* R = nullptr, const double* Psi2 = nullptr, const double* Kinv = nullptr,
                        double* trace_part = nullptr, const UvArgs* uv = nullptr, const double* Sacc = nullptr) {
-    const int extra = uv ? Tn * Tn : 0;                  // pass 2 of Uv rides in the same launch (uv_cols_role)
+    // mu (with uv): an OUTPUT, finished from uv->muacc and the last block row of W; pass 2 of Uv rides in the same launch (uv_cols_role)
+    const int extra = uv ? Tn * Tn : 0;
     hipLaunchKernelGGL(k_gemm32, dim3(Tn * (Tn + 1) / 2 * 4 + extra), dim3(256), 0, s, W, W, C, ld, Tn, 0, 0, rev, mu, R, Psi2,
                        Kinv, trace_part, uv ? *uv : UvArgs{}, Sacc);
 }
 // C = A B, every tile (k_gemm32's plain product: mode 3, no epilogue)
 static void launch_gemm(const double* A, const double* B, double* C, int ld, int Tn, hipStream_t s) {
-    hipLaunchKernelGGL(k_gemm32, dim3(Tn * Tn * 4), dim3(256), 0, s, A, B, C, ld, Tn, 3, 0, 0, (const double*)nullptr, (double*)nullptr,
+    hipLaunchKernelGGL(k_gemm32, dim3(Tn * Tn * 4), dim3(256), 0, s, A, B, C, ld, Tn, 3, 0, 0, (double*)nullptr, (double*)nullptr,
                        (const double*)nullptr, (const double*)nullptr, (double*)nullptr, UvArgs{}, (const double*)nullptr);
 }
 
@@ -1345,9 +1350,14 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s, const SweepPlan& p) {
             if (h->grp[g].masked && p.pack && !p.resident) { step_wait[h->grp[g].form_step] = h->evGroup[g]; any_wait = true; }
         }
     }
-    double* uvt0 = h->dUvWork + 2 * (size_t)Qp;     // t = W' P xi, advanced block by block during the factorisation
+    // mu = Sigma xi = P W'^T W' P xi as two triangular mat-vecs, both riding along with the factorisation: t = W' P xi block by
+    // block (tvec_role), and mu = P W'^T t block row by block row (mu_row_tile), whose terms are pass 1 of the closed-form Uv as
+    // well (t IS p = V^-T mu up to the reversal).  Only the last block row's term is left: the Sigma launch (enqueue_finish2) adds it.
+    double* uvt0 = h->dUvWork + 2 * (size_t)Qp;     // t
     PotrfSeq lam(h->dLam, Qp, TQ, h->dInfo + 1, Qp, h->dScratch + POTRF_SCRATCH, s, h->dWl, &form, h->dTmp, h->dXi, uvt0,
                  any_wait ? step_wait : nullptr);
+    lam.mu_acc = h->dUvWork;                        // the running mu (in the factor's reversed order)
+    lam.uv_part = uvt0 + (size_t)TQ * Qp;           // TQ x Qp tile partial sums
     if (p.kuu_interleaved) {
         // (The default; SGP_INTERLEAVE=0 turns it off.)  The K_uu chain's Cholesky steps were held back (sweep_local_impl): its launches and the
         // Lambda chain's go out ALTERNATELY, so that on a GPU that is idle when the sweep arrives neither chain waits for the host to
@@ -1364,16 +1374,6 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s, const SweepPlan& p) {
     } else {
         while (!lam.done()) lam.next();
     }
-    // mu = Sigma xi = P W'^T W' P xi as two triangular mat-vecs; their intermediate t IS p = V^-T mu up to the reversal,
-    // so the closed-form Uv needs no further solve and nothing here waits for Sigma itself
-    double* uvp = h->dXi;                    // xi is consumed by the forward solve; p lands in the same vector afterwards
-    double* uvck = h->dUvWork;               // C_kk
-    double* uvak = h->dUvWork + Qp;          // p_k / sqrt(alpha_k alpha_{k+1})
-    double* uvt = uvt0;
-    double* uvpart = uvt + (size_t)TQ * Qp;         // TQ x Qp tile partial sums
-    // mu, p, the alpha scan and (extra workgroups) pass 1 of Uv in one launch
-    hipLaunchKernelGGL(k_trmv_mu_scan, dim3(Qp / 4 + 1 + TQ * (TQ + 1) / 2), dim3(256), 0, s, (const double*)h->dWl,
-                       (const double*)uvt, h->dMu, uvp, uvck, uvak, uvpart, Qp);
 }
 
 // after the join with the side stream (K_uu chain): Sigma, R, the traces, Uv pass 2 and the scalars
@@ -1392,10 +1392,8 @@ static void launch_traces(sgp_handle* h, hipStream_t s) {
 
 static void enqueue_finish2(sgp_handle* h, hipStream_t s, bool join_word) {
     const int M = h->M, Mp = h->Mp, Q = h->Q, Qp = h->Qp, TQ = h->TQ;
-    double* uvp = h->dXi;
-    double* uvck = h->dUvWork;
-    double* uvak = h->dUvWork + Qp;
-    double* uvpart = h->dUvWork + 2 * (size_t)Qp + (size_t)TQ * Qp;
+    double* uvt = h->dUvWork + 2 * (size_t)Qp;
+    double* uvpart = uvt + (size_t)TQ * Qp;
     // Sigma = W'^T W' (index-reversed back), R = Sigma + mu mu^T, -- UniSGP -- the shares of tr(R Psi2) and tr(Kuu^-1 Psi2),
     // and (extra workgroups) pass 2 of Uv = chol(Sigma_v + mu mu^T).U (GPnode/UniSGPnode.jl:67-69): one launch
     const int nata = TQ * (TQ + 1) / 2 * 4;
@@ -1403,7 +1401,7 @@ static void enqueue_finish2(sgp_handle* h, hipStream_t s, bool join_word) {
     const double* partK = h->dTrace;
     int nK = TRACE_BLOCKS, nR = TRACE_BLOCKS;
     UvArgs uv;
-    uv.Wp = h->dWl; uv.p = uvp; uv.ck = uvck; uv.ak = uvak; uv.partial = uvpart; uv.LR = h->dUvT;
+    uv.Wp = h->dWl; uv.t = uvt; uv.muacc = h->dUvWork; uv.partial = uvpart; uv.LR = h->dUvT;
     uv.stamps = h->dStamps + STAMP_STRIDE * SGP_T_FINISH1;
     uv.join = join_word ? h->dJoin + WORD_JOIN : nullptr;
     uv.join_need = h->join_epoch;

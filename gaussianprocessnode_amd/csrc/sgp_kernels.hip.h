@@ -47,7 +47,7 @@ __device__ __forceinline__ int64_t realtime_ticks() { return (int64_t)__builtin_
 // Diagnostics (variant library built with -DSGP_SWEEP_TRACE, tools/sweep_trace.py): 100 MHz begin / end stamps of the kernels of
 // the LAST sweep, taken inside the kernels -- rocprofv3's kernel trace slows the host's launches down until the GPU starves,
 // so it cannot show how the streams of an overlapped sweep really interleave.  Slot map: 0 k_prep_xu (statistics), 1 k_prep_xu
-// (K_uu chain), 2 k_gram_uf, 3 k_gram_uu, 4 k_trmv_mu_scan, 5 / 6 k_gemm32 (Sigma launch / K_uu^-1), 7 k_scalars, 8 k_join_wait,
+// (K_uu chain), 2 k_gram_uf, 3 k_gram_uu, 4 (retired: was k_trmv_mu_scan), 5 / 6 k_gemm32 (Sigma launch / K_uu^-1), 7 k_scalars, 8 k_join_wait,
 // 16 + j Lambda-chain step j, 40 + j K_uu-chain step j, 64 + tile0 k_syrk_stream, 128 + row_lo k_assemble, 200 + j: the
 // moment step j of the Lambda chain had its statistics (end of its wait).
 constexpr int TRACE_SLOTS_N = 256;
@@ -1960,6 +1960,38 @@ __device__ __forceinline__ void tvec_role(const double* __restrict__ L, const do
     if (part == 0) t[i * TB + r] = tree(r);
 }
 
+// ------------------------------------------------------------------------------------------------
+// And so does mu = P W^T t = sum_i W(i,.)^T t_i, a sum over block rows like Sigma: block row i of W and t_i are both final after
+// launch i + 1, so launch i + 2 carries i + 1 short workgroups (all eight waves), one per tile (i, I), I <= i:
+//   c_i[k] = sum_kk W(64 i + kk, k) t(64 i + kk),   k = 64 I .. 64 I + 63,
+// added into the running sum muacc[k] (first contribution of a column block: plain store; one workgroup per column block and
+// launch, the launches in stream order: a fixed order, no atomics).  The very same number is pass 1 of Uv (see uv_cols_role):
+// partial[Tn-1-i][ld-1-k] = sum_m p_m V[m][ld-1-k] over tile row Tn-1-i of V.  Only the last block row's term is left
+// for the Sigma launch (k_gemm32 mode 0), whose workgroups add it from the operands they hold anyway.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void mu_row_tile(const double* __restrict__ W, const double* __restrict__ t, double* __restrict__ muacc,
+                                            double* __restrict__ partial, int ld, int Tn, int i, int I, double* red) {
+    const int c = threadIdx.x & 63, part = threadIdx.x >> 6, k = I * TB + c;      // wave `part`: rows 8 part .. 8 part + 7 of the tile
+    const double2* src = reinterpret_cast<const double2*>(W + (size_t)k * ld + i * TB + 8 * part);
+    const double* tp = t + i * TB + 8 * part;
+    const double prev = (part == 0 && I != i) ? muacc[k] : 0.0;
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const double2 w = src[u];
+        s = fma(w.y, tp[2 * u + 1], fma(w.x, tp[2 * u], s));
+    }
+    red[part * TB + c] = s;
+    __syncthreads();
+    if (part != 0) return;
+    double a[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) a[q] = red[q * TB + c];
+    const double ci = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));   // fixed order over the waves
+    partial[(size_t)(Tn - 1 - i) * ld + ld - 1 - k] = ci;
+    muacc[k] = prev + ci;
+}
+
 // xi = xi0 + vec(B W) of the Lambda chain's step 0 (one workgroup, 256 threads)
 __device__ __forceinline__ void form_xi(const LamForm& form, int ld, int tid, bool bypass = false) {
     const double* B = form.stats + (size_t)form.Mp * form.Mp;
@@ -2029,7 +2061,8 @@ constexpr int POTRF_LOGDET = 3 * TB * TB + 64;
 __global__ void __launch_bounds__(PSTEP_THREADS) k_potrf_step(double* __restrict__ A, int ld, int j, int Tn, int* __restrict__ info,
                                                     int n_valid, double* __restrict__ scratch, double* __restrict__ Winv,
                                                     double* __restrict__ Sacc, const double* __restrict__ tv_xi,
-                                                    double* __restrict__ tv_t, LamForm form) {
+                                                    double* __restrict__ tv_t, double* __restrict__ mu_acc,
+                                                    double* __restrict__ uv_part, LamForm form) {
     // LDS: two MFMA operand panels (2 x 64 x PS) and two 64 x 64 tiles.  The panels stay valid while the diagonal tile is
     // factored: the waves that idle during the pivot runs use them for the block's own rank-64 update.
     __shared__ __attribute__((aligned(16))) double lds[2 * TB * PS];
@@ -2051,7 +2084,9 @@ __global__ void __launch_bounds__(PSTEP_THREADS) k_potrf_step(double* __restrict
             // the inverse factor's; the product launch behind it, whose workgroups are a quarter of the size, adds the last TWO
             // block rows instead)
             const int nsig = (Sacc && j >= 2 && j < Tn) ? (j - 1) * j / 2 : 0;
-            if (e >= nfin + npre + nsig) { tvec_role<8>(A, Winv, tv_xi, tv_t, ld, j - 1, lds); return; }     // (all eight waves)
+            if (e == nfin + npre + nsig) { tvec_role<8>(A, Winv, tv_xi, tv_t, ld, j - 1, lds); return; }     // (all eight waves)
+            // behind it (with mu_acc, j >= 2): block row j - 2's share of mu = P W^T t and of pass 1 of Uv, see mu_row_tile
+            if (e > nfin + npre + nsig) { mu_row_tile(Winv, tv_t, mu_acc, uv_part, ld, Tn, j - 2, e - (nfin + npre + nsig) - 1, lds); return; }
             if (xgroup) return;
             if (e < nfin) winv_row_tile(A, Winv, ld, j - 1, e >> 1, e & 1, lds, 2, tiles);
             else if (e < nfin + npre) { e -= nfin; winv_row_tile(A, Winv, ld, j, e >> 1, e & 1, lds, 1); }
@@ -2324,10 +2359,9 @@ __device__ __forceinline__ void load_v_column(double (&v)[64], const double* __r
 // kb > jb).  Runs as the extra workgroups of the Sigma = W'^T W' launch (k_gemm32 mode 0): neither needs the other.
 struct UvArgs {
     const double* Wp;        // nullptr: no Uv role in this launch
-    const double* p;
-    const double* ck;
-    const double* ak;
-    const double* partial;
+    const double* t;         // t = W' (P xi) (tvec_role): p = P t
+    const double* muacc;     // mu = P W'^T t without the last block row's term (mu_row_tile), in the factor's order
+    const double* partial;   // pass 1 (mu_row_tile): per 64-row tile b >= 1 of V and column j, sum_m p_m V[m][j]
     double* LR;
     int64_t* stamps;
     // device-side join with the K_uu chain (side stream): the product workgroups read K_uu^-1 only in their epilogue and
@@ -2371,9 +2405,29 @@ __device__ __forceinline__ void uv_cols_role(const UvArgs& u, int Qp, int kb, in
 #pragma unroll
         for (int e = 0; e < 8; ++e) T += pv[e];
     }
-    // the tile's 64 coefficients: one coalesced load each (lane kk holds row 64 kb + kk's), handed out with v_readlane --
-    // as uniform loads inside the loop they were 192 scalar loads whose latencies this single wave sat out one after another
-    const double ckl = u.ck[64 * kb + lane], akl = u.ak[64 * kb + lane], pl = u.p[64 * kb + lane];
+    // the tile's 64 coefficients (lane kk holds row 64 kb + kk's), handed out with v_readlane -- as uniform loads inside the
+    // loop they were 192 scalar loads whose latencies this single wave sat out one after another.  The alpha scan over p = P t
+    // is recomputed here (a wave sum over the tiles above, a wave scan inside the tile) instead of being waited for: every
+    // tile of a tile row takes the same steps, so the rows of Uv are consistent across the tiles.
+    const double pl = u.t[Qp - 1 - (64 * kb + lane)];
+    double above = 0.0;                                   // lane's share of sum_{e < 64 kb} p_e^2, eight loads in flight
+    for (int b0 = 0; b0 < kb; b0 += 8) {
+        double x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = u.t[Qp - 1 - (64 * min(b0 + e, kb - 1) + lane)] * ((b0 + e < kb) ? 1.0 : 0.0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) above = fma(x[e], x[e], above);
+    }
+    for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o);      // (the same bits in every lane)
+    double inc = pl * pl;
+    for (int o = 1; o < 64; o <<= 1) {
+        const double up = __shfl_up(inc, o);
+        if (lane >= o) inc += up;
+    }
+    const double before = __shfl_up(inc, 1);
+    const double alpha = (1.0 + above) + (lane > 0 ? before : 0.0), an = fma(pl, pl, alpha);
+    const double ir = 1.0 / sqrt(alpha * an);
+    const double ckl = an * ir, akl = pl * ir;            // C_kk and p_k / sqrt(alpha_k alpha_{k+1})
     auto lane_value = [](double x, int src) {
         return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), src), __builtin_amdgcn_readlane(__double2loint(x), src));
     };
@@ -2392,17 +2446,21 @@ __device__ __forceinline__ void uv_cols_role(const UvArgs& u, int Qp, int kb, in
 //   mode 3  C = A B                                 every tile                                     (theta gradient)
 // (I, J, k are 64-tile indices; W lower triangular, so the k range skips the structural zeros.)
 // ------------------------------------------------------------------------------------------------
-// mode 0 extras (all nullable): with `mu` the kernel also writes R = C + mu mu^T (Sigma_v + mu mu^T, GPnode/UniSGPnode.jl:67)
+// mode 0 extras (all nullable): with `mu` (needs uv.t, uv.muacc) the kernel finishes mu = P W^T t -- every product workgroup forms
+// the 2 x 32 entries of its rows and columns as uv.muacc + the last block row's term, a 64-deep dot product with the operand panels
+// of its last product; the same steps everywhere, so the same bits; the diagonal quadrants write theirs to `mu` --
+// and writes R = C + mu mu^T (Sigma_v + mu mu^T, GPnode/UniSGPnode.jl:67)
 // and, with `Psi2` (d_out = 1), the block's shares of the two traces of the :w rule / average energy (:196-238, :337-359):
 // tr(R Psi2) into trace_part[blockIdx.x] and tr(Kuu^-1 Psi2) into trace_part[n + blockIdx.x], n = the launch's Tn (Tn + 1) / 2 * 4 product workgroups.
 __global__ void __launch_bounds__(256) k_gemm32(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ C,
-                                                int ld, int Tn, int mode, int s, int rev, const double* __restrict__ mu,
+                                                int ld, int Tn, int mode, int s, int rev, double* __restrict__ mu,
                                                 double* __restrict__ R, const double* __restrict__ Psi2,
                                                 const double* __restrict__ Kinv, double* __restrict__ trace_part, UvArgs uv,
                                                 const double* __restrict__ Sacc) {
     __shared__ double As[64 * PS32];
     __shared__ double Bs[64 * PS32];
     __shared__ double tred[4];
+    __shared__ double mup[4 * 64], mus[64];                              // mu of rows r0 .. r0 + 31 and columns c0 .. c0 + 31
     TraceScope trace(mode == 0 ? (mu ? 5 : 6) : 255);
     if (mode == 0 && uv.Wp) {                                            // extra workgroups: pass 2 of Uv (uv_cols_role)
         const int ngemm = Tn * (Tn + 1) / 2 * 4;
@@ -2439,14 +2497,15 @@ __global__ void __launch_bounds__(256) k_gemm32(const double* __restrict__ A, co
     const size_t offA = (size_t)gcA * ld + grA, offB = (size_t)gcB * ld + grB;
     double2 p0 = make_double2(0.0, 0.0), p1 = p0, q0 = p0, q1 = p0;
     double muA[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, muB[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int me = tid & 63;                                             // mu: entry me of the 64, wave `wave` rows 16 wave .. + 15 of the last block row
+    double mt[16], mbase = 0.0;
     // K_uu^-1 comes from the side stream's chain.  Normally that finished long ago: one poll, and the operands are fetched
     // now like the others.  If not, the product goes first and the workgroup waits in front of its epilogue.
     bool kinv_late = false;
     if (mode == 0 && mu) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { muA[e] = mu[grA + e]; muB[e] = mu[grB + e]; }
-        muA[4] = mu[gcA];
-        muB[4] = mu[gcB];
+        for (int u = 0; u < 16; ++u) mt[u] = uv.t[(Tn - 1) * TB + 16 * wave + u];
+        if (wave == 0 && ((me < 32) ? I : J) < Tn - 1) mbase = uv.muacc[(me < 32) ? r0 + me : c0 + me - 32];   // (the last block column has no earlier term)
         if (Psi2) {
             p0 = *reinterpret_cast<const double2*>(Psi2 + offA); p1 = *reinterpret_cast<const double2*>(Psi2 + offA + 2);
             kinv_late = uv.join && !join_ready(uv.join, uv.join_need);
@@ -2464,6 +2523,13 @@ __global__ void __launch_bounds__(256) k_gemm32(const double* __restrict__ A, co
 #pragma unroll
         for (int k4 = 0; k4 < 16; ++k4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[k4 * 4 * PS32], bp[k4 * 4 * PS32], acc, 0, 0, 0);
     }
+    if (mode == 0 && mu) {                                               // As, Bs: block row Tn - 1 of W, columns r0 .. and c0 ..
+        const double* pan = ((me < 32) ? As + me : Bs + me - 32) + 16 * wave * PS32;
+        double sdot = 0.0;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) sdot = fma(pan[u * PS32], mt[u], sdot);
+        mup[wave * 64 + me] = sdot;
+    }
     double tsum = 0.0, tsumK = 0.0;
     if (mode != 0) {
 #pragma unroll
@@ -2479,7 +2545,18 @@ __global__ void __launch_bounds__(256) k_gemm32(const double* __restrict__ A, co
     double* Qd = As;                                                     // Qd[c][r], stride 33
 #pragma unroll
     for (int r = 0; r < 4; ++r) Qd[(wc * 16 + li) * 33 + wr * 16 + lk + 4 * r] = acc[r];
+    if (mu && tid < 64) {
+        const double m = mbase + ((mup[tid] + mup[64 + tid]) + (mup[128 + tid] + mup[192 + tid]));   // fixed order over the waves
+        mus[tid] = m;
+        if (I == J && qi == qj && tid < 32) mu[rev ? ld - 1 - (r0 + tid) : r0 + tid] = m;
+    }
     __syncthreads();
+    if (mu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { muA[e] = mus[o4 + (rev ? 3 - e : e)]; muB[e] = mus[32 + o4 + (rev ? 3 - e : e)]; }
+        muA[4] = mus[32 + oc];
+        muB[4] = mus[oc];
+    }
     {   // the quadrant: column c0 + oc, rows r0 + o4 .. + 3 (index-reversed: a descending, still contiguous run)
         double v[4];
 #pragma unroll
@@ -2561,84 +2638,17 @@ __global__ void __launch_bounds__(256) k_symv(const double* __restrict__ S, cons
 // it is accumulated directly, not as x_j minus a prefix).
 // p costs nothing extra: mu = Sigma xi = P W'^T W' P xi, so with t = W' (P xi) one has mu = P W'^T t and
 // p = P L'^T P mu = P L'^T W'^T t = P t.
-//   tvec_role      : t = W' (P xi), block by block during the factorisation
-//   k_trmv_mu_scan : mu = P W'^T t, p = P t, alpha scan -> C_kk and p_k / sqrt(alpha_k alpha_{k+1})
-//   k_uv_partial : per 64-row tile and column, sum_m p_m V[m][j]   (so that tiles can start their suffix sums independently)
-//   k_uv_cols    : one wave per 64 x 64 tile, 64 rows in registers, writes the rows of Uv
+//   tvec_role    : t = W' (P xi), block by block during the factorisation
+//   mu_row_tile  : mu = P W'^T t, block row by block row during the factorisation; its terms are pass 1 of Uv: per 64-row tile
+//                  and column, sum_m p_m V[m][j]   (so that tiles can start their suffix sums independently)
+//   k_gemm32     : (mode 0) adds the last block row's term of mu; its extra workgroups (uv_cols_role) are pass 2: one wave per
+//                  64 x 64 tile, 64 rows in registers, the alpha scan -> C_kk and p_k / sqrt(alpha_k alpha_{k+1}) recomputed per
+//                  tile, writes the rows of Uv
+// No launch of its own is left between the factorisation and the Sigma launch, and no workgroup waits for another.
 // V[k][j] = W'[Qp-1-k][Qp-1-j] is read straight from the inverse factor (load_v_column).
 // Output LR = Uv^T (lower, column-major: column k = row k of Uv), the layout potrf(R) would have produced.
 // ------------------------------------------------------------------------------------------------
 constexpr int CU_MAXQ = 4096;
-
-// mu = P W'^T t (one wave per column of W'), p = P t, and -- in the extra last workgroup -- the alpha scan of p:
-// ck[k] = C_kk, ak[k] = p_k / sqrt(alpha_k alpha_{k+1}).
-__global__ void __launch_bounds__(256) k_trmv_mu_scan(const double* __restrict__ W, const double* __restrict__ tpart /* t */,
-                                                      double* __restrict__ mu, double* __restrict__ p,
-                                                      double* __restrict__ ck, double* __restrict__ ak,
-                                                      double* __restrict__ uvpart, int Qp) {
-    __shared__ double ts[CU_MAXQ];
-    TraceScope trace(4);
-    const int lane = threadIdx.x & 63;
-    // mat-vec workgroups: the first eight entries of the wave's column of W' are requested before the LDS copy of t is
-    // waited for -- one memory round trip for both instead of two (this launch sits alone on the critical path)
-    const bool matvec = (int)blockIdx.x < Qp / 4;
-    const int kcol = blockIdx.x * 4 + (threadIdx.x >> 6);
-    double wv[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (matvec) {
-        const double* col = W + (size_t)kcol * Qp;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = kcol + lane + 64 * u;
-            wv[u] = col[min(i, Qp - 1)] * ((i < Qp) ? 1.0 : 0.0);
-        }
-    }
-    for (int i = threadIdx.x; i < Qp; i += 256) ts[i] = tpart[i];     // t = W' (P xi), advanced block by block by tvec_role
-    __syncthreads();
-    if ((int)blockIdx.x > Qp / 4) {
-        // workgroups beyond the mat-vec and the scan: pass 1 of Uv, one wave per 64 x 64 tile (kb <= jb) of V:
-        //   partial[kb][j] = sum_kk p_{64 kb + kk} V[64 kb + kk][j],  p = P t straight from the LDS copy of t
-        if (threadIdx.x >= 64) return;
-        int jb, kb;
-        tile_from_index(blockIdx.x - Qp / 4 - 1, jb, kb);            // jb >= kb
-        const int j = 64 * jb + lane;
-        double v[64];
-        load_v_column(v, W, Qp, kb, j);
-        double sacc = 0.0;
-#pragma unroll
-        for (int kk = 0; kk < 64; ++kk) sacc = fma(ts[Qp - 1 - (64 * kb + kk)], v[kk], sacc);
-        uvpart[(size_t)kb * Qp + j] = sacc;
-        return;
-    }
-    if ((int)blockIdx.x == Qp / 4) {
-        if (threadIdx.x >= 64) return;
-        const int per = (Qp + 63) / 64;
-        const int e0 = lane * per, e1 = min((lane + 1) * per, Qp);
-        double loc = 0.0;
-        for (int e = e0; e < e1; ++e) { double v = ts[Qp - 1 - e]; p[e] = v; loc = fma(v, v, loc); }
-        double inc = loc;
-        for (int o = 1; o < 64; o <<= 1) {
-            double u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
-        double alpha = 1.0 + (inc - loc);
-        for (int e = e0; e < e1; ++e) {
-            const double pe = ts[Qp - 1 - e], an = fma(pe, pe, alpha);
-            const double ir = 1.0 / sqrt(alpha * an);
-            ck[e] = an * ir;
-            ak[e] = pe * ir;
-            alpha = an;
-        }
-        return;
-    }
-    const int k = kcol;
-    const double* col = W + (size_t)k * Qp;
-    double s = 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s = fma(wv[u], ts[min(k + lane + 64 * u, Qp - 1)], s);
-    for (int i = k + lane + 512; i < Qp; i += 64) s = fma(col[i], ts[i], s);
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) mu[Qp - 1 - k] = s;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Scalars of the sweep.  Two passes, fixed summation order (bitwise reproducible):

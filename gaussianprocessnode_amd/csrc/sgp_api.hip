@@ -2280,6 +2280,156 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
     return 0;
 }
 
+// The :in log-messages of many nodes and their moment-matched marginals (include/sgp_hip.h).  Modelled on sgp_predict_var: blocking,
+// K_uu, W_K = L_K^-1, S and its factor formed at the CURRENT kernel parameters in call scratch, nothing the sweep keeps written, the
+// M-wide panel K(Xu, X) chunked under the same knob.  Launches: [pad Sigma_v] k_form_S_in, k_prep_xu, k_gram_uu, the two
+// factorisations; per chunk k_predict, k_gram_uf, k_quadform_fused, k_in_point_finish; k_in_moments once behind the last chunk,
+// over the logpdf and the points of ALL chunks (a node may straddle chunks).
+extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes,
+                              const double* y_mean, const double* weights, const double* mu_v, const double* Sigma_v,
+                              double* logpdf, double* log_norm, double* mean, double* cov) {
+    if (!h || n < 0 || n_nodes < 0) return fail(h, SGP_ERR_ARG, "sgp_in_message: bad argument");
+    if (n == 0) return 0;
+    if (!X || !node_start || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_in_message: null X, node_start or y_mean");
+    if (weights && (!log_norm || !mean || !cov))
+        return fail(h, SGP_ERR_ARG, "sgp_in_message: weights given without log_norm, mean and cov");
+    if (!mu_v != !Sigma_v) return fail(h, SGP_ERR_ARG, "sgp_in_message: pass both mu_v and Sigma_v, or neither");
+    if (!h->have_inducing || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_in_message: set_inducing and set_kernel first");
+    if (h->training) return fail(h, SGP_ERR_ARG, "sgp_in_message: a device-paced training run is open (sgp_train_end first)");
+    if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_in_message: no posterior in the handle and mu_v / Sigma_v are NULL");
+    if (!mu_v && h->posterior_set)
+        return fail(h, SGP_ERR_ARG, "sgp_in_message: sgp_set_posterior gave no Sigma_v: pass mu_v and Sigma_v, or sweep first");
+    if (n_nodes < 1 || n_nodes > n || node_start[0] != 0 || node_start[n_nodes] != n)
+        return fail(h, SGP_ERR_ARG, "sgp_in_message: node_start must run from 0 to n");
+    for (int64_t t = 0; t < n_nodes; ++t)
+        if (node_start[t + 1] <= node_start[t]) return fail(h, SGP_ERR_ARG, "sgp_in_message: node_start must increase (no empty node)");
+    if (weights)
+        for (int64_t p = 0; p < n; ++p)
+            if (!(weights[p] >= 0.0) || !std::isfinite(weights[p]))
+                return fail(h, SGP_ERR_ARG, "sgp_in_message: weights must be finite and non-negative");
+    if (int wrc = sync_all(h)) return wrc;
+    if (!mu_v) {
+        // the last sweep's q(v), refused exactly when sgp_get_posterior refuses it
+        if (int src = check_sync_status(h)) return src;
+        int info[2];
+        HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
+        if (int frc = factor_status(h, info[0], "K_uu (last sweep)", info[1], "Lambda (last sweep)", true)) return frc;
+    }
+    hipStream_t s = h->own;
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T;
+    // W = mean(q_W) of the last sgp_set_noise ([w_bar] for d_out = 1), tr(W) and the nodes' rows y_t' W
+    OutMat W;
+    memset(&W, 0, sizeof W);
+    double trW = 0.0;
+    for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
+    for (int i = 0; i < dout; ++i) trW += W.v[i * dout + i];
+    std::vector<double> yw((size_t)n_nodes * dout);
+    std::vector<int64_t> node_of((size_t)n);
+    for (int64_t t = 0; t < n_nodes; ++t) {
+        for (int d = 0; d < dout; ++d) {
+            double v = 0.0;
+            for (int e = 0; e < dout; ++e) v = fma(y_mean[t + e * n_nodes], W.v[e + d * dout], v);
+            yw[(size_t)t * dout + d] = v;
+        }
+        for (int64_t p = node_start[t]; p < node_start[t + 1]; ++p) node_of[(size_t)p] = t;
+    }
+    // chunk of points: a multiple of 64, sized to the scratch budget (or SGP_PREDICT_CHUNK), as sgp_predict_var
+    const int64_t per_point = (int64_t)Mp + 4 * T + 4 + dout;
+    int64_t chunk = h->env_predict_chunk > 0 ? h->env_predict_chunk : std::max<int64_t>(TB, PREDICT_CHUNK_DOUBLES / per_point);
+    chunk = std::min<int64_t>((chunk + TB - 1) / TB * TB, (n + TB - 1) / TB * TB);
+    // scratch (doubles; the pieces the tiles' 16-byte loads read come first, every one a multiple of 64):
+    //   K_uu | W_K | S -> L_S (Mp^2 each) | Sigma_v padded (Qp^2) | chunk: K(Xu, X) (Mp), pa, pb (2 T each), kmu (4), means (d_out)
+    //   | mu_v (Qp) | two factorisations' scratch | status words | all points: X (D), logpdf, weights, g, node (1 each)
+    //   | rows y' W (n_nodes d_out) | node_start (n_nodes + 1) | log_norm, mean, cov (n_nodes (1 + D + D^2))
+    const size_t nn = (size_t)n_nodes;
+    const size_t fixed = 3 * (size_t)Mp * Mp + (size_t)Qp * Qp;
+    const size_t total = fixed + (size_t)(chunk * per_point) + Qp + 2 * POTRF_SCRATCH + 64 + (size_t)n * (D + 4) + nn * dout + (nn + 1) +
+                         nn * (1 + (size_t)D + (size_t)D * D);
+    double* base = nullptr;
+    if (int crc = call_scratch(h, total, &base)) return crc;
+    double* dKuuS = base;
+    double* dWkS = dKuuS + (size_t)Mp * Mp;
+    double* dSS = dWkS + (size_t)Mp * Mp;
+    double* dSigP = dSS + (size_t)Mp * Mp;
+    double* dKc = dSigP + (size_t)Qp * Qp;
+    double* dPa = dKc + (size_t)chunk * Mp;
+    double* dPb = dPa + (size_t)chunk * 2 * T;
+    double* dKmu = dPb + (size_t)chunk * 2 * T;
+    double* dMeanC = dKmu + (size_t)chunk * 4;
+    double* dMuX = dMeanC + (size_t)chunk * dout;
+    double* dPscr = dMuX + Qp;
+    int* dInfoS = reinterpret_cast<int*>(dPscr + 2 * POTRF_SCRATCH);
+    double* dXall = dPscr + 2 * POTRF_SCRATCH + 64;
+    double* dLp = dXall + (size_t)n * D;
+    double* dWt = dLp + n;
+    double* dG = dWt + n;
+    int64_t* dNode = reinterpret_cast<int64_t*>(dG + n);
+    double* dYw = dG + 2 * (size_t)n;
+    int64_t* dStart = reinterpret_cast<int64_t*>(dYw + nn * dout);
+    double* dLogNorm = dYw + nn * dout + (nn + 1);
+    double* dMeanN = dLogNorm + nn;
+    double* dCovN = dMeanN + nn * D;
+    // q(v): the explicit one uploaded (Sigma_v padded with the identity), or the last sweep's in place (dSigma: what
+    // sgp_get_posterior returns; leading dimension Qp either way)
+    const double* dMu = h->dMu;
+    const double* dSig = h->dSigma;
+    if (mu_v) {
+        std::vector<double> m(Qp, 0.0);
+        memcpy(m.data(), mu_v, sizeof(double) * Q);
+        HIPCHK(h, hipMemcpy(dMuX, m.data(), sizeof(double) * Qp, hipMemcpyHostToDevice));
+        if (int rc = upload_padded(h, Sigma_v, dSigP)) return rc;
+        dMu = dMuX;
+        dSig = dSigP;
+    }
+    HIPCHK(h, hipMemcpy(dXall, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(dNode, node_of.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(dYw, yw.data(), sizeof(double) * nn * dout, hipMemcpyHostToDevice));
+    if (weights) {
+        HIPCHK(h, hipMemcpy(dWt, weights, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(dStart, node_start, sizeof(int64_t) * (nn + 1), hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, hipMemsetAsync(dPscr, 0, sizeof(double) * (2 * POTRF_SCRATCH + 64), s));
+    // the current parameters into the K_uu chain's mirror (as sgp_predict), K_uu at them and its inverse factor; S and its factor
+    mirror_current_params(h, s);
+    by_family(h->family, [&](auto F) {
+        hipLaunchKernelGGL(k_gram_uu<decltype(F)::value>, dim3(T, T), dim3(256), 0, s, h->dXusK, dKuuS, h->dParamsK, M, Mp, D);
+    });
+    hipLaunchKernelGGL(k_form_S_in, dim3((unsigned)(((size_t)Mp * Mp + 255) / 256)), dim3(256), 0, s, dSig, Qp, dMu, W, dSS, M, Mp, dout);
+    launch_potrf(dKuuS, Mp, T, dInfoS + 0, M, dPscr, s, dWkS);
+    launch_potrf(dSS, Mp, T, dInfoS + 1, M, dPscr + POTRF_SCRATCH, s);
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    int info[2];
+    HIPCHK(h, hipMemcpy(info, dInfoS, sizeof info, hipMemcpyDeviceToHost));
+    if (int frc = factor_status(h, info[0], "K_uu (current kernel)", info[1], "S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)')")) return frc;
+    for (int64_t s0 = 0; s0 < n; s0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, n - s0);
+        const unsigned nblk = (unsigned)((nc + TB - 1) / TB);
+        const double* dXs = dXall + (size_t)s0 * D;
+        // the d_out means k' mu^(d) (sgp_predict's kernel), K(Xu, X) of the chunk, |W_K k|^2 -> pa and |L_S' k|^2 -> pb
+        launch_predict(h, s, h->dXusK, h->dParamsK, dXs, dMu, dMeanC, nc);
+        launch_gram_uf(h, s, h->dXusK, dXs, nullptr, dKc, nullptr, h->dParamsK, nc, 0, nullptr, nullptr);
+        hipLaunchKernelGGL(k_quadform_fused, dim3(nblk, 2 * T), dim3(256), 0, s, (const double*)dWkS, (const double*)dSS,
+                           (const double*)dKc, dMu, dPa, dPb, dKmu, Mp, T, nc);
+        hipLaunchKernelGGL(k_in_point_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)dPa, (const double*)dPb,
+                           (const double*)dMeanC, (const double*)dYw, (const int64_t*)(dNode + s0), dLp + s0,
+                           (const Params*)h->dParamsK, 0.5 * trW, T, nc, dout);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (weights)
+        hipLaunchKernelGGL(k_in_moments, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, s, (const double*)dLp, (const double*)dXall,
+                           (const double*)dWt, (const int64_t*)dStart, dG, dLogNorm, dMeanN, dCovN, D, n_nodes);
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    if (logpdf) HIPCHK(h, hipMemcpy(logpdf, dLp, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (weights) {
+        HIPCHK(h, hipMemcpy(log_norm, dLogNorm, sizeof(double) * nn, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(mean, dMeanN, sizeof(double) * nn * D, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(cov, dCovN, sizeof(double) * nn * D * D, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
 // F(theta) = -sum_n [ -w/2 k_nn + w/2 |L^-1 k_n|^2 - w/2 |Uv k_n|^2 + w y_n mu_v'k_n ]  (derivative_helper.jl:23-39)
 //          = w/2 [ s_kk - tr(Kuu^-1 Psi2) + tr(R Psi2) ] - w b'mu_v
 // evaluated at the CURRENT kernel parameters with q(v) (mu_v, R = Sigma_v + mu mu') held fixed at the last finished

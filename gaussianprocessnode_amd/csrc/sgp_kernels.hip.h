@@ -3197,6 +3197,102 @@ __global__ void __launch_bounds__(256) k_predvar_multi(const double* __restrict_
         }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Input messages (sgp_in_message): the :in closure of GPnode/MultiSGPnode.jl:162-208 / UniSGPnode.jl:107-122 at many points of
+// many nodes, and the moment match of the Gaussian x log-pdf products (MultiSGPnode.jl:37-44, UniSGPnode.jl:39-54).  For point p
+// of node t, k = K(Xu, x_p):
+//   logpdf_p = -1/2 tr(W) (sigma2 - |L_K^-1 k|^2) + sum_d (y_t' W)_d k' mu^(d) - 1/2 |L_S' k|^2,   S = L_S L_S'
+// |L_K^-1 k|^2 and |L_S' k|^2 are k_quadform_fused's two forms, the d_out means are k_predict's; the kernels below form S,
+// finish the points and take the moments.
+// ------------------------------------------------------------------------------------------------
+// S = sum_ab W_ab (Sigma_v^(ab) + mu^(a) mu^(b)') (Mp x Mp, the identity on the padding) from Sigma_v (leading dimension lds,
+// block (a, b) at rows a M, columns b M) and mu_v.  Entry (i, j) is the mean of the sum taken at (i, j) and at (j, i), the same
+// two numbers for both: S is exactly symmetric whatever the rounding of Sigma_v.  The sibling of k_form_G_multi.
+__global__ void __launch_bounds__(256) k_form_S_in(const double* __restrict__ Sig, int lds, const double* __restrict__ mu, OutMat W,
+                                                   double* __restrict__ S, int M, int Mp, int dout) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)Mp * Mp) return;
+    const int i = (int)(e % Mp), j = (int)(e / Mp);
+    if (i >= M || j >= M) { S[e] = (i == j) ? 1.0 : 0.0; return; }
+    auto term = [&](int r, int c) {
+        double s = 0.0;
+        for (int b = 0; b < dout; ++b)
+            for (int a = 0; a < dout; ++a)
+                s = fma(W.v[a + b * dout], fma(mu[a * M + r], mu[b * M + c], Sig[(size_t)(b * M + c) * lds + a * M + r]), s);
+        return s;
+    };
+    S[e] = 0.5 * (term(i, j) + term(j, i));
+}
+
+// logpdf[n] = (-1/2 tr(W) (sigma2 - sum_r pa[r][n]) + sum_d yw[node[n]][d] means[d][n]) - 1/2 sum_r pb[r][n]   (fixed order, rows
+// as k_w_point_finish sums them); yw: [node][d] rows y_t' W, node: the node of every point of this chunk
+__global__ void __launch_bounds__(256) k_in_point_finish(const double* __restrict__ pa, const double* __restrict__ pb,
+                                                         const double* __restrict__ means, const double* __restrict__ yw,
+                                                         const int64_t* __restrict__ node, double* __restrict__ logpdf,
+                                                         const Params* __restrict__ P, double half_trW, int T, int64_t N, int dout) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    double a = 0.0, b = 0.0;
+    for (int r = 0; r < 2 * T; ++r) { a += pa[(size_t)r * N + n]; b += pb[(size_t)r * N + n]; }
+    const double* row = yw + (size_t)node[n] * dout;
+    double lin = 0.0;
+    for (int d = 0; d < dout; ++d) lin = fma(row[d], means[(size_t)d * N + n], lin);
+    logpdf[n] = (lin - half_trW * (P->sigma2 - a)) - 0.5 * b;
+}
+
+// Moments of one node's weighted points under exp(logpdf), shifted by the node's largest logpdf a:  g_s = w_s exp(logpdf_s - a),
+//   log_norm = a + log sum g,  mean = sum g x / sum g,  cov = sum g (x - mean)(x - mean)' / sum g  (about the new mean).
+// One wavefront per node (four nodes per workgroup): lane l sums the points l, l + 64, .. of its node in order, the 64 partial
+// sums meet in an xor butterfly -- every lane ends with the same bits, and a repeated call with them again.  No atomics.
+// g: n doubles of scratch (a lane reads back only what it wrote).  cov is written from its lower triangle: exactly symmetric.
+__global__ void __launch_bounds__(256) k_in_moments(const double* __restrict__ lp, const double* __restrict__ X,
+                                                    const double* __restrict__ w, const int64_t* __restrict__ node_start,
+                                                    double* __restrict__ g, double* __restrict__ log_norm, double* __restrict__ mean,
+                                                    double* __restrict__ cov, int D, int64_t n_nodes) {
+    __shared__ double ms[4][MAXD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t t = (int64_t)blockIdx.x * 4 + wave;
+    const bool live = t < n_nodes;
+    const int64_t s0 = live ? node_start[t] : 0, s1 = live ? node_start[t + 1] : 0;
+    auto wave_sum = [](double v) {
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        return v;
+    };
+    double a = -__builtin_inf();
+    for (int64_t s = s0 + lane; s < s1; s += 64) a = fmax(a, lp[s]);
+    for (int o = 32; o > 0; o >>= 1) a = fmax(a, __shfl_xor(a, o));
+    double z = 0.0;
+    for (int64_t s = s0 + lane; s < s1; s += 64) {
+        const double gs = w[s] * exp(lp[s] - a);
+        g[s] = gs;
+        z += gs;
+    }
+    z = wave_sum(z);
+    if (live && lane == 0) log_norm[t] = a + log(z);
+    for (int d = 0; d < D; ++d) {
+        double m = 0.0;
+        for (int64_t s = s0 + lane; s < s1; s += 64) m = fma(g[s], X[(size_t)s * D + d], m);
+        m = wave_sum(m) / z;
+        if (lane == 0) {
+            ms[wave][d] = m;
+            if (live) mean[(size_t)t * D + d] = m;
+        }
+    }
+    __syncthreads();
+    for (int j = 0; j < D; ++j)
+        for (int i = j; i < D; ++i) {
+            const double mi = ms[wave][i], mj = ms[wave][j];
+            double c = 0.0;
+            for (int64_t s = s0 + lane; s < s1; s += 64)
+                c = fma(g[s] * (X[(size_t)s * D + i] - mi), X[(size_t)s * D + j] - mj, c);
+            c = wave_sum(c) / z;
+            if (live && lane == 0) {
+                cov[((size_t)t * D + j) * D + i] = c;
+                cov[((size_t)t * D + i) * D + j] = c;
+            }
+        }
+}
+
 // transpose-copy of a square column-major matrix (Uv = L_R^T on the way out)
 __global__ void __launch_bounds__(256) k_transpose(const double* __restrict__ A, double* __restrict__ At, int ld) {
     __shared__ double tile[TB * (TB + 1)];

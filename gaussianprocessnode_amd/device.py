@@ -280,6 +280,33 @@ class SGPDevice:
         self._check(self._lib.sgp_predict_var(self._h, ptr(Xs), ns, ptr(mu), ptr(S), flags, ptr(mean), ptr(var)), "sgp_predict_var")
         return (mean[0], var) if self.d_out == 1 else (mean.T.copy(), var)
 
+    def in_message(self, X, node_start, y_mean, weights=None, mu_v=None, Sigma_v=None):
+        """The :in log-messages of many nodes in one call (sgp_in_message), at the current kernel and the last `set_noise`.
+        X (n, D): the points of all nodes; node t owns X[node_start[t]:node_start[t + 1]] (n_nodes + 1 entries, 0 .. n);
+        y_mean (n_nodes, d_out): mean(q_out) per node.  q(v) is the last sweep's (mu_v = Sigma_v = None) or the one given.
+        Returns logpdf (n,) without `weights`; with the n cubature weights (logpdf, log_norm (n_nodes,), mean (n_nodes, D),
+        cov (n_nodes, D, D)): per node the moments of N(x) exp(logpdf(x)), shifted by the node's largest logpdf."""
+        Xs = as_f64(np.reshape(X, (-1, self.D)))
+        n = Xs.shape[0]
+        start = np.ascontiguousarray(np.asarray(node_start, dtype=np.int64).reshape(-1))
+        n_nodes = start.size - 1
+        if n_nodes < 0:
+            raise ValueError("in_message: node_start needs n_nodes + 1 entries")
+        if (mu_v is None) != (Sigma_v is None):
+            raise ValueError("in_message: pass both mu_v and Sigma_v, or neither")
+        y_cm = as_f64(np.asarray(y_mean, dtype=np.float64).reshape(n_nodes, self.d_out).T)      # column-major n_nodes x d_out
+        mu = None if mu_v is None else as_f64(np.reshape(mu_v, (self.Q,)))
+        S = None if Sigma_v is None else as_f64(np.asarray(Sigma_v, dtype=np.float64).reshape(self.Q, self.Q).T)   # column-major
+        logpdf = np.empty(n)
+        w = log_norm = mean = cov = None
+        if weights is not None:
+            w = as_f64(np.reshape(weights, (n,)))
+            log_norm, mean, cov = np.empty(n_nodes), np.empty((n_nodes, self.D)), np.empty((n_nodes, self.D, self.D))
+        self._check(self._lib.sgp_in_message(self._h, ptr(Xs), n, start.ctypes.data_as(C.POINTER(C.c_int64)), n_nodes, ptr(y_cm),
+                                             ptr(w), ptr(mu), ptr(S), ptr(logpdf), ptr(log_norm), ptr(mean), ptr(cov)),
+                    "sgp_in_message")
+        return logpdf if weights is None else (logpdf, log_norm, mean, cov)
+
     def set_posterior(self, mu_v, Uv):
         """Install an external q(v) (mean and Uv = chol(Sigma_v + mu mu').U) for the per-point outputs (`w_stats`)."""
         mu = as_f64(np.reshape(mu_v, (self.Q,)))

@@ -224,7 +224,66 @@ def rule_in(q_out, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, q_in=None):
         I1, I2 = eng.w_stats()
         val = -0.5 * trW * I1 - 0.5 * (I2 - 1.0)                                        # :181
         return float(val[0]) if np.ndim(x) == 1 else val
-    return LogPdfClosure(log_backwardmess, multivariate=True)
+    closure = LogPdfClosure(log_backwardmess, multivariate=True)
+    closure.in_node = (q_out, q_v, q_w, q_theta, meta)          # what `prod_logpdf` hands to the batched device path
+    return closure
+
+
+def marginal_in_batch(q_outs, lefts, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, reference_fallback: bool = True):
+    """q(x_t) of T MultiSGP nodes in ONE device call: `prod_logpdf(lefts[t], rule_in(q_outs[t], q_v, q_w, q_theta, meta))` for
+    every t (GPnode/MultiSGPnode.jl:37-44 over :162-208) -- the loop a GP-SSM runs over its time steps in every VMP iteration.
+    The srcubature points of every left message go to `SGPDevice.in_message` with the explicit q_v and mean(q_w); the device
+    returns the closure values and, per node, the moments of N(x) exp(logpdf(x)) shifted by the node's largest closure value.
+    reference_fallback (default): a node whose unshifted moments are NaN in the reference (`reference_moments_are_nan`,
+    decided on the host from the returned closure values) gets its left message back, as the reference returns it; False
+    returns the shifted moments there too.  Returns a list of MvNormalMeanCovariance (or left messages)."""
+    from .cubature import srcubature
+    from .unisgp import reference_moments_are_nan
+    q_outs, lefts = list(q_outs), list(lefts)
+    if len(q_outs) != len(lefts):
+        raise ValueError("marginal_in_batch: one left message per node")
+    if not lefts:
+        return []
+    W = _mean_W(q_w)
+    d_out = W.shape[0]
+    rule = srcubature()
+    pw = [rule.points_weights(*left.mean_cov()) for left in lefts]
+    X = np.concatenate([np.atleast_2d(np.asarray(p, dtype=np.float64)) for p, _ in pw])
+    wts = np.concatenate([np.asarray(w, dtype=np.float64) for _, w in pw])
+    start = np.concatenate([[0], np.cumsum([len(w) for _, w in pw])]).astype(np.int64)
+    Y = np.stack([np.asarray(q.mean(), dtype=np.float64).ravel() for q in q_outs])
+    eng = _engine(meta, 1, d_out)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    eng.set_noise(W)
+    mu_v, Sigma_v = q_v.mean_cov()
+    lp, _, mean, cov = eng.in_message(X, start, Y, wts, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64))
+    out = []
+    for t, left in enumerate(lefts):
+        if reference_fallback and reference_moments_are_nan(lp[start[t]:start[t + 1]]):
+            out.append(left)
+        else:
+            out.append(MvNormalMeanCovariance(np.array(mean[t], dtype=np.float64), np.array(cov[t], dtype=np.float64)))
+    return out
+
+
+def prod_logpdf(left, right, reference_fallback: bool = True):
+    """ReactiveMP.prod(GenericProd, MultivariateGaussian, ContinuousMultivariateLogPdf) (GPnode/MultiSGPnode.jl:37-44): the
+    moments of N(x) exp(logpdf(x)) over srcubature's points; NaN moments return the Gaussian unchanged.  A closure that came
+    from `rule_in` is a one-node call of `marginal_in_batch` (the device evaluates the closure and takes the moments); any other
+    closure is evaluated point by point and the same shifted moments are taken on the host."""
+    node = getattr(right, "in_node", None)
+    if node is not None:
+        q_out, q_v, q_w, q_theta, meta = node
+        return marginal_in_batch([q_out], [left], q_v, q_w, q_theta, meta, reference_fallback)[0]
+    from .cubature import srcubature
+    from .unisgp import reference_moments_are_nan, shifted_moments
+    pts, wts = srcubature().points_weights(*left.mean_cov())
+    lp = np.array([float(right.logpdf(p)) for p in pts])
+    if reference_fallback and reference_moments_are_nan(lp):
+        return left
+    _, mean, cov = shifted_moments(pts, wts, lp)
+    return MvNormalMeanCovariance(mean, cov)
 
 
 def rule_in_laplace(q_out, q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, iterations: int = 20):

@@ -458,3 +458,64 @@ def prod_logpdf(left, right):
     if math.isnan(m) or math.isnan(v):
         return gauss
     return NormalMeanVariance(m, v + pad)
+
+
+# ------------------------------------------------------------------------------------------------
+# batched :in messages and their moment-matched marginals (sgp_in_message)
+# ------------------------------------------------------------------------------------------------
+def reference_moments_are_nan(logpdf) -> bool:
+    """Whether the reference's products (GPnode/UniSGPnode.jl:39-54, GPnode/MultiSGPnode.jl:37-44) return their Gaussian
+    argument for a node with these closure values: they exponentiate unshifted, so the moments are NaN when some exp overflows
+    (logpdf > log(DBL_MAX): Inf / Inf) or every exp underflows (0 / 0)."""
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        e = np.exp(np.asarray(logpdf, dtype=np.float64))
+    return bool(np.any(np.isinf(e)) or np.any(np.isnan(e)) or not np.any(e > 0.0))
+
+
+def shifted_moments(pts, wts, logpdf):
+    """(log_norm, mean, cov) of the weighted points under exp(logpdf), shifted by the largest logpdf (what sgp_in_message
+    computes on the device): g = w exp(logpdf - a), mean = sum g x / sum g, cov about that mean."""
+    pts = np.asarray(pts, dtype=np.float64).reshape(len(wts), -1)
+    lp = np.asarray(logpdf, dtype=np.float64)
+    a = float(lp.max())
+    g = np.asarray(wts, dtype=np.float64) * np.exp(lp - a)
+    Z = float(g.sum())
+    mean = (g @ pts) / Z
+    d = pts - mean
+    return a + math.log(Z), mean, (d * g[:, None]).T @ d / Z
+
+
+def marginal_in_batch(q_outs, lefts, q_v, q_w, q_theta, meta: UniSGPMeta, reference_fallback: bool = True):
+    """q(x_t) of T UniSGP nodes in ONE device call: `prod_logpdf(lefts[t], rule_in(q_outs[t], ...))` for every t
+    (GPnode/UniSGPnode.jl:39-46 over :107-122).  The ghcubature(21) points of every left message go to `SGPDevice.in_message`
+    with the explicit q_v; the device returns the closure values and the shifted moments, and `v + 1e-6` is added as
+    `prod_logpdf` adds it for a Gaussian on the left.  reference_fallback (default): a node whose unshifted moments are NaN
+    in the reference (`reference_moments_are_nan`, decided from the returned closure values) gets its left message back;
+    False returns the shifted moments there too.  Returns a list of NormalMeanVariance (or left messages)."""
+    from .cubature import ghcubature
+    if meta.Xu.shape[1] != 1:
+        raise ValueError("unisgp.marginal_in_batch: the Gauss-Hermite product needs a one-dimensional input")
+    q_outs, lefts = list(q_outs), list(lefts)
+    if len(q_outs) != len(lefts):
+        raise ValueError("marginal_in_batch: one left message per node")
+    if not lefts:
+        return []
+    rule = ghcubature(21)
+    pw = [rule.points_weights(left.mean(), left.var()) for left in lefts]
+    X = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1, 1) for p, _ in pw])
+    wts = np.concatenate([np.asarray(w, dtype=np.float64) for _, w in pw])
+    start = np.concatenate([[0], np.cumsum([len(w) for _, w in pw])]).astype(np.int64)
+    y = np.array([[float(q.mean())] for q in q_outs])
+    eng = _engine(meta, 1)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    eng.set_noise([[_mean_w(q_w)]], _elog_w(q_w))
+    mu_v, Sigma_v = q_v.mean_cov()
+    lp, _, mean, cov = eng.in_message(X, start, y, wts, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64))
+    out = []
+    for t, left in enumerate(lefts):
+        if reference_fallback and reference_moments_are_nan(lp[start[t]:start[t + 1]]):
+            out.append(left)
+        else:
+            out.append(NormalMeanVariance(float(np.ravel(mean[t])[0]), float(np.ravel(cov[t])[0]) + 1e-6))
+    return out

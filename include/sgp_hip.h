@@ -158,7 +158,7 @@ int sgp_sweep(sgp_handle* h, void* stream);                 /* local + [all-redu
  *                      all-reduce hook: ONE call, of the exchange buffer's tail [B | scalars], count = Mp d_out + SGP_S_COUNT +
  *                      d_out^2 on every rank), then phase 2;
  *   SGP_SWEEP_REUSED   otherwise (sgp_set_noise, sgp_set_prior, sgp_carry_posterior, sgp_set_posterior, sgp_w_stats, sgp_predict,
- *                      sgp_predict_var):
+ *                      sgp_predict_var, sgp_in_message):
  *                      phase 2 alone over the resident statistics; no K_uu chain, no hook call.
  * The results of TARGETS and REUSED sweeps are bitwise those of a full sweep.  sgp_sweep_local / sgp_sweep_finish keep their
  * meaning (a full local phase, phase 2).
@@ -259,6 +259,32 @@ int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu
 #define SGP_PREDICT_NOISE 1   /* add the observation noise W^-1 */
 int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
                     int32_t flags, double* mean, double* var);
+
+/* sgp_in_message: the :in log-messages of many nodes in one call and, with cubature weights, the moment-matched marginals of the
+ * Gaussian x log-pdf products -- @rule MultiSGP(:in) (GPnode/MultiSGPnode.jl:162-208) / UniSGP(:in) (GPnode/UniSGPnode.jl:107-122)
+ * and ReactiveMP.prod(GenericProd, Gaussian, Continuous*LogPdf) (GPnode/MultiSGPnode.jl:37-44, GPnode/UniSGPnode.jl:39-54).
+ * X is D x n as in sgp_predict; node t owns the points [node_start[t], node_start[t + 1]) (n_nodes + 1 entries, 0 = node_start[0]
+ * < ... < node_start[n_nodes] = n); y_mean is n_nodes x d_out column-major, mean(q_out) of every node.  For point p of node t,
+ * with k = K(Xu, x_p) at the CURRENT kernel (the last sgp_set_kernel, its family and jitter), W = the last sgp_set_noise ([w_bar]
+ * for d_out = 1), L_K = chol(K_uu + jitter I) and q(v) = N(mu_v, Sigma_v):
+ *     logpdf_p = -1/2 tr(W) (sigma2 - |L_K^-1 k|^2) + sum_d (y_t' W)_d k' mu_v^(d) - 1/2 k' S k,
+ *     S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)'),   k' S k = |L_S' k|^2 with S = L_S L_S'
+ * (both quadratic forms through factors, as sgp_w_stats and sgp_predict_var take them).  weights (n cubature weights; NULL: no
+ * moments) turns every node's points into the moments of N(x) exp(logpdf(x)), shifted by a = max_s logpdf_s of the node:
+ *     g_s = w_s exp(logpdf_s - a),  log_norm = a + log sum g,  mean = sum g x / sum g,  cov = sum g (x - mean)(x - mean)' / sum g
+ * -- approximate_meancov of the reference's products, which exponentiates unshifted and returns NaN where exp overflows or
+ * every term underflows; the shifted sums are finite there.  Outputs: logpdf [n] (may be NULL), log_norm [n_nodes], mean
+ * D x n_nodes, cov D x D x n_nodes (every block exactly symmetric); the last three are required exactly when weights is given.
+ * Posterior: mu_v and Sigma_v both given, or both NULL for the last finished sweep's q(v) -- the rules of sgp_predict_var.
+ * SGP_ERR_ARG: node_start not as above (an empty node included), negative or non-finite weights, weights without the three moment
+ * outputs, the posterior cases sgp_predict_var refuses, an open sgp_train_* run.  A K_uu (at the current kernel) or S that is not
+ * positive definite returns its failing leading minor k > 0.  n = 0 returns 0, nothing done.
+ * Blocking.  Everything is formed in call scratch and the points go through in chunks, as in sgp_predict_var: nothing the sweep
+ * keeps is written (sgp_sweep_kind and the theta objective are unaffected).  All sums are in a fixed order, one wavefront per
+ * node, no atomics: repeated calls agree bitwise, and so do calls that differ in the chunk size. */
+int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes, const double* y_mean,
+                   const double* weights, const double* mu_v, const double* Sigma_v, double* logpdf, double* log_norm,
+                   double* mean, double* cov);
 
 /* sgp_wait: returns when everything this handle has enqueued -- on its own streams or the caller's -- has finished: what a caller
  * does between `infer` calls when it wants the sweep to be over but none of its results yet.  The library's streams are polled

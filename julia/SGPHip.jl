@@ -157,6 +157,27 @@ function predict_var(h::Handle, Xstar::Matrix{Float64}, μ_v = nothing, Σ_v = n
     return mean, var
 end
 
+# the :in log-messages of many nodes and their moment-matched marginals in one call (include/sgp_hip.h, sgp_in_message): X is
+# D × n, node t owns the columns node_start[t] + 1 : node_start[t + 1] (0-based offsets, n_nodes + 1 entries), y_mean is
+# n_nodes × d_out; weights === nothing returns the closure values alone, else (logpdf, log_norm, mean D × n_nodes,
+# cov D × D × n_nodes).  Like the rest of this file it has never been executed: only the ccall signature is stated here, no
+# rule dispatches on it yet.
+function in_message(h::Handle, X::Matrix{Float64}, node_start::Vector{Int64}, y_mean::Matrix{Float64}, weights = nothing,
+                    μ_v = nothing, Σ_v = nothing)
+    n = size(X, 2); n_nodes = length(node_start) - 1
+    logpdf = zeros(n)
+    log_norm = zeros(n_nodes); m = zeros(h.d, n_nodes); C = zeros(h.d, h.d, n_nodes)
+    moments = weights !== nothing
+    μp = μ_v === nothing ? C_NULL : Vector{Float64}(μ_v)
+    Σp = Σ_v === nothing ? C_NULL : Matrix{Float64}(Σ_v)
+    check(ccall((:sgp_in_message, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, X, n, node_start, n_nodes, y_mean, moments ? Vector{Float64}(weights) : C_NULL, μp, Σp, logpdf,
+                moments ? log_norm : C_NULL, moments ? m : C_NULL, moments ? C : C_NULL), h.ptr)
+    return moments ? (logpdf, log_norm, m, C) : logpdf
+end
+
 # q(v) installed from outside for the per-point outputs (include/sgp_hip.h, sgp_set_posterior): mean and the upper factor
 # Uv = chol(Σ_v + μ μ').U, column-major Q × Q -- a Julia Matrix as it is
 set_posterior!(h::Handle, μ_v::Vector{Float64}, Uv::Matrix{Float64}) =

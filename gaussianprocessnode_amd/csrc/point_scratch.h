@@ -1,0 +1,96 @@
+// Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message).  Plain C++, no HIP: the
+// layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+// Hands out consecutive pieces of one allocation.  Every layout function runs twice over the same code: with a null base to sum
+// the sizes (`used` is then the total to allocate), and over the allocation to get the pointers.  Each piece is rounded up to
+// ALIGN doubles, so every piece starts a multiple of 512 bytes from the base whatever its neighbours hold (the tiles' 16-byte
+// loads need 16).
+struct Carver {
+    static constexpr size_t ALIGN = 64;     // doubles
+    double* base = nullptr;
+    size_t used = 0;                        // doubles handed out so far
+    template <typename T>
+    T* take(size_t count) {
+        const size_t doubles = (count * sizeof(T) + sizeof(double) - 1) / sizeof(double);
+        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += (doubles + ALIGN - 1) / ALIGN * ALIGN;
+        return p;
+    }
+};
+
+struct PointShape {
+    int Mp, Qp, T, D, dout;
+    int potrf_scratch;              // POTRF_SCRATCH
+    int64_t chunk, n, n_nodes;      // points per chunk (a multiple of 64), points and nodes of the call
+};
+
+// what sgp_predict_var and sgp_in_message share: the factors at the current kernel and one chunk of the M-wide panel
+struct PanelScratch {
+    double *Kuu, *Wk;               // K_uu -> L_K, and W_K = L_K^-1
+    double *Kc, *Pa, *Pb, *Kmu;     // per chunk: K(Xu, X), the two quadratic forms' partials, k . mu rows
+    double* MeanC;                  // per chunk: the d_out means, [d_out][nc]
+    double* MuX;                    // an explicit mu_v, zero-padded
+    double* Pscr;                   // two factorisations' scratch ...
+    int* Info;                      // ... and their status words directly behind it: one memset clears both
+};
+static inline void layout_panel(Carver& c, const PointShape& p, PanelScratch* b) {
+    b->Kuu = c.take<double>((size_t)p.Mp * p.Mp);
+    b->Wk = c.take<double>((size_t)p.Mp * p.Mp);
+    b->Kc = c.take<double>((size_t)p.chunk * p.Mp);
+    b->Pa = c.take<double>((size_t)p.chunk * 2 * p.T);
+    b->Pb = c.take<double>((size_t)p.chunk * 2 * p.T);
+    b->Kmu = c.take<double>((size_t)p.chunk * 4);
+    b->MeanC = c.take<double>((size_t)p.chunk * p.dout);
+    b->MuX = c.take<double>((size_t)p.Qp);
+    b->Pscr = c.take<double>(2 * (size_t)p.potrf_scratch);
+    b->Info = c.take<int>(2);
+}
+
+struct PredictVarScratch : PanelScratch {
+    double* LS;                     // Sigma_v padded with the identity -> its factor L_S
+    double *Xs, *VarC;              // per chunk: X* and the d_out x d_out (co)variances
+};
+static inline void layout_predict_var(Carver& c, const PointShape& p, PredictVarScratch* b) {
+    layout_panel(c, p, b);
+    b->LS = c.take<double>((size_t)p.Qp * p.Qp);
+    b->Xs = c.take<double>((size_t)p.chunk * p.D);
+    b->VarC = c.take<double>((size_t)p.chunk * p.dout * p.dout);
+}
+
+struct InMessageScratch : PanelScratch {
+    double* SS;                     // S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)') -> its factor
+    double* SigP;                   // an explicit Sigma_v padded with the identity
+    double *Xall, *Lp, *Wt, *G;     // all points: X, logpdf, cubature weights, k_in_moments' shifted weights
+    int64_t* Node;                  // all points: the node of each
+    double* Yw;                     // per node: the row y_t' W
+    int64_t* Start;                 // node_start (n_nodes + 1)
+    double *LogNorm, *MeanN, *CovN; // per node: the moments
+};
+static inline void layout_in_message(Carver& c, const PointShape& p, InMessageScratch* b) {
+    const size_t n = (size_t)p.n, nn = (size_t)p.n_nodes, D = (size_t)p.D;
+    layout_panel(c, p, b);
+    b->SS = c.take<double>((size_t)p.Mp * p.Mp);
+    b->SigP = c.take<double>((size_t)p.Qp * p.Qp);
+    b->Xall = c.take<double>(n * D);
+    b->Lp = c.take<double>(n);
+    b->Wt = c.take<double>(n);
+    b->G = c.take<double>(n);
+    b->Node = c.take<int64_t>(n);
+    b->Yw = c.take<double>(nn * p.dout);
+    b->Start = c.take<int64_t>(nn + 1);
+    b->LogNorm = c.take<double>(nn);
+    b->MeanN = c.take<double>(nn * D);
+    b->CovN = c.take<double>(nn * D * D);
+}
+
+// sgp_predict: the points, their means and an explicit mu_v (Q entries, unpadded)
+struct PredictScratch { double *Xs, *Mean, *Mu; };
+static inline void layout_predict(Carver& c, int64_t ns, int D, int dout, size_t mu_count, PredictScratch* b) {
+    b->Xs = c.take<double>((size_t)ns * D);
+    b->Mean = c.take<double>((size_t)ns * dout);
+    b->Mu = c.take<double>(mu_count);
+}

@@ -8,6 +8,7 @@
 // sequence's first kernel mirrors on the device.
 #include "../../include/sgp_hip.h"
 #include "sgp_kernels.hip.h"
+#include "point_scratch.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1066,15 +1067,26 @@ extern "C" int sgp_set_noise(sgp_handle* h, const double* W, double E_log_w) {
     return 0;
 }
 
-// upload a Q x Q host matrix into a padded Qp x Qp device buffer (pad = identity)
-static int upload_padded(sgp_handle* h, const double* src, double* dst) {
-    const size_t Q = h->Q, Qp = h->Qp;
-    std::vector<double> tmp(Qp * Qp, 0.0);
-    for (size_t j = 0; j < Qp; ++j) {
-        if (j < Q) memcpy(&tmp[j * Qp], &src[j * Q], Q * sizeof(double));
-        else tmp[j * Qp + j] = 1.0;
+// an n x n column-major host matrix padded to np x np (pad = identity)
+static std::vector<double> pad_square(const double* src, size_t n, size_t np) {
+    std::vector<double> tmp(np * np, 0.0);
+    for (size_t j = 0; j < np; ++j) {
+        if (j < n) memcpy(&tmp[j * np], &src[j * n], n * sizeof(double));
+        else tmp[j * np + j] = 1.0;
     }
-    HIPCHK(h, hipMemcpy(dst, tmp.data(), Qp * Qp * sizeof(double), hipMemcpyHostToDevice));
+    return tmp;
+}
+
+// upload a Q x Q host matrix into a padded Qp x Qp device buffer (pad = identity), a Q-vector into a Qp one (pad = 0)
+static int upload_padded(sgp_handle* h, const double* src, double* dst) {
+    const std::vector<double> tmp = pad_square(src, h->Q, h->Qp);
+    HIPCHK(h, hipMemcpy(dst, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+static int upload_padded_vec(sgp_handle* h, const double* src, double* dst) {
+    std::vector<double> v(h->Qp, 0.0);
+    memcpy(v.data(), src, sizeof(double) * h->Q);
+    HIPCHK(h, hipMemcpy(dst, v.data(), sizeof(double) * h->Qp, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1839,6 +1851,15 @@ static int sync_checked(sgp_handle* h) {
     return check_sync_status(h);
 }
 
+// Whether the last sweep's q(v) may be handed out or used (the caller has waited): no stream hand-off gave up and both of its
+// factorisations went through.  sgp_get_posterior and the point-batch calls on the resident q(v) refuse through this one check.
+static int last_sweep_status(sgp_handle* h, const char* name_kuu, const char* name_lambda) {
+    if (int src = check_sync_status(h)) return src;
+    int info[2];
+    HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
+    return factor_status(h, info[0], name_kuu, info[1], name_lambda, true);
+}
+
 static int download_square(sgp_handle* h, const double* dsrc, int ld, int n, double* dst) {
     HIPCHK(h, hipMemcpy2D(dst, sizeof(double) * n, dsrc, sizeof(double) * ld, sizeof(double) * n, n, hipMemcpyDeviceToHost));
     return 0;
@@ -1852,13 +1873,12 @@ extern "C" int sgp_set_posterior(sgp_handle* h, const double* mu_v, const double
     if (int qrc = quiesce(h)) return qrc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t Q = h->Q, Qp = h->Qp;
-    std::vector<double> m(Qp, 0.0), ut(Qp * Qp, 0.0);
-    memcpy(m.data(), mu_v, Q * sizeof(double));
+    std::vector<double> ut(Qp * Qp, 0.0);
     for (size_t k = 0; k < Qp; ++k) {
         if (k >= Q) { ut[k * Qp + k] = 1.0; continue; }
         for (size_t j = k; j < Q; ++j) ut[k * Qp + j] = Uv[k + j * Q];      // column k of Uv^T = row k of Uv (upper part)
     }
-    HIPCHK(h, hipMemcpy(h->dMu, m.data(), Qp * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = upload_padded_vec(h, mu_v, h->dMu)) return rc;
     HIPCHK(h, hipMemcpy(h->dUvT, ut.data(), Qp * Qp * sizeof(double), hipMemcpyHostToDevice));
     h->swept = true;
     stats_drop(h, STATS_QV);                   // q(v) no longer belongs to the statistics on the device
@@ -1881,11 +1901,9 @@ extern "C" int sgp_get_scalars(sgp_handle* h, double* out) {
 extern "C" int sgp_get_posterior(sgp_handle* h, double* mu_v, double* Sigma_v, double* Uv) {
     if (!h) return SGP_ERR_ARG;
     if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_get_posterior: no finished sweep");
-    int rc = sync_checked(h);
+    int rc = sync_all(h);
     if (rc) return rc;
-    int info[4];
-    HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
-    if (int frc = factor_status(h, info[0], "K_uu", info[1], "Lambda", true)) return frc;
+    if (int frc = last_sweep_status(h, "K_uu", "Lambda")) return frc;
     const int Q = h->Q, Qp = h->Qp;
     if (mu_v) HIPCHK(h, hipMemcpy(mu_v, h->dMu, sizeof(double) * Q, hipMemcpyDeviceToHost));
     if (Sigma_v) { rc = download_square(h, h->dSigma, Qp, Q, Sigma_v); if (rc) return rc; }
@@ -2119,29 +2137,153 @@ static void launch_predict(const sgp_handle* h, hipStream_t s, const double* Xus
     }
 }
 
+// ---- what the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message) share ----
+static int refuse(sgp_handle* h, const char* name, const char* why) {
+    return fail(h, SGP_ERR_ARG, (std::string(name) + ": " + why).c_str());
+}
+static int refuse_unset(sgp_handle* h, const char* name) {
+    return h->have_inducing && h->have_kernel ? 0 : refuse(h, name, "set_inducing and set_kernel first");
+}
+static int refuse_training(sgp_handle* h, const char* name) {
+    return h->training ? refuse(h, name, "a device-paced training run is open (sgp_train_end first)") : 0;
+}
+
+// the refusals of a call that needs q(v) with its covariance: the explicit (mu_v, Sigma_v) or the last sweep's
+static int point_call_ready(sgp_handle* h, const char* name, const double* mu_v, const double* Sigma_v) {
+    if (!mu_v != !Sigma_v) return refuse(h, name, "pass both mu_v and Sigma_v, or neither");
+    if (int rc = refuse_unset(h, name)) return rc;
+    if (int rc = refuse_training(h, name)) return rc;
+    if (!mu_v && !h->swept) return refuse(h, name, "no posterior in the handle and mu_v / Sigma_v are NULL");
+    if (!mu_v && h->posterior_set) return refuse(h, name, "sgp_set_posterior gave no Sigma_v: pass mu_v and Sigma_v, or sweep first");
+    return 0;
+}
+
+// ... and its wait: everything enqueued is through, and the last sweep's q(v), where the call uses it, is what sgp_get_posterior
+// would hand out
+static int point_call_wait(sgp_handle* h, const double* mu_v) {
+    if (int wrc = sync_all(h)) return wrc;
+    return mu_v ? 0 : last_sweep_status(h, "K_uu (last sweep)", "Lambda (last sweep)");
+}
+
+// q(v): the explicit one uploaded (mu_v zero-padded into dMuX, Sigma_v padded with the identity into dSigX), or the last sweep's in
+// place (dSigma: what sgp_get_posterior returns -- not dWl, which sgp_set_prior(form 0) reuses; leading dimension Qp either way)
+static int resolve_qv(sgp_handle* h, const double* mu_v, const double* Sigma_v, double* dMuX, double* dSigX, const double** dMu,
+                      const double** dSig) {
+    *dMu = h->dMu;
+    *dSig = h->dSigma;
+    if (!mu_v) return 0;
+    if (int rc = upload_padded_vec(h, mu_v, dMuX)) return rc;
+    if (int rc = upload_padded(h, Sigma_v, dSigX)) return rc;
+    *dMu = dMuX;
+    *dSig = dSigX;
+    return 0;
+}
+
+// points per chunk of the M-wide panel: a multiple of 64, sized to the scratch budget (or SGP_PREDICT_CHUNK), at most the call's
+constexpr int64_t PREDICT_CHUNK_DOUBLES = int64_t(1) << 25;     // scratch of one chunk: 256 MB
+static int64_t point_chunk(const sgp_handle* h, int64_t per_point, int64_t count) {
+    const int64_t chunk = h->env_predict_chunk > 0 ? h->env_predict_chunk : std::max<int64_t>(TB, PREDICT_CHUNK_DOUBLES / per_point);
+    return std::min<int64_t>((chunk + TB - 1) / TB * TB, (count + TB - 1) / TB * TB);
+}
+
+static PointShape point_shape(const sgp_handle* h, int64_t per_point, int64_t n, int64_t n_nodes) {
+    return PointShape{h->Mp, h->Qp, h->T, h->D, h->dout, POTRF_SCRATCH, point_chunk(h, per_point, n), n, n_nodes};
+}
+
+// the call scratch for what pass 1 of a layout function summed, and the carver rewound onto it for pass 2
+static int carve_call_scratch(sgp_handle* h, Carver* c) {
+    double* base = nullptr;
+    if (int crc = call_scratch(h, c->used, &base)) return crc;
+    *c = Carver{base};
+    return 0;
+}
+
+// "Factor at the current kernel", first half: the factorisations' scratch and status words cleared, the current parameters into
+// the K_uu chain's mirror (as sgp_predict), K_uu at them.  The caller may enqueue what forms its second matrix behind it.
+static_assert(2 * POTRF_SCRATCH % Carver::ALIGN == 0, "the status words must lie directly behind the factorisations' scratch");
+static int factor_begin(sgp_handle* h, hipStream_t s, const PanelScratch& b) {
+    HIPCHK(h, hipMemsetAsync(b.Pscr, 0, sizeof(double) * (2 * POTRF_SCRATCH + Carver::ALIGN), s));
+    mirror_current_params(h, s);
+    by_family(h->family, [&](auto F) {
+        hipLaunchKernelGGL(k_gram_uu<decltype(F)::value>, dim3(h->T, h->T), dim3(256), 0, s, h->dXusK, b.Kuu, h->dParamsK, h->M, h->Mp,
+                           h->D);
+    });
+    return 0;
+}
+
+// ... second half: K_uu -> L_K with W_K = L_K^-1, the caller's second matrix (leading dimension ld, Tn tiles, n_valid rows) -> its
+// factor in place; waits and returns the status of the two as the ABI reports it
+static int factor_finish(sgp_handle* h, hipStream_t s, const PanelScratch& b, double* second, int ld, int Tn, int n_valid,
+                         const char* second_name) {
+    launch_potrf(b.Kuu, h->Mp, h->T, b.Info + 0, h->M, b.Pscr, s, b.Wk);
+    launch_potrf(second, ld, Tn, b.Info + 1, n_valid, b.Pscr + POTRF_SCRATCH, s);
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    int info[2];
+    HIPCHK(h, hipMemcpy(info, b.Info, sizeof info, hipMemcpyDeviceToHost));
+    return factor_status(h, info[0], "K_uu (current kernel)", info[1], second_name);
+}
+
+// One chunk of nc points at dXs through the panel: the d_out means k' mu^(d) (sgp_predict's kernel on the same mirror, so bitwise
+// sgp_predict's), K(Xu, X) (d_out = 0: no targets, no B partial -- k_gram_uf's K tile alone, in its summation order), then
+// |W_K k|^2 -> Pa and |second' k|^2 -> Pb: k_quadform_fused as sgp_w_stats runs it, with `second` where that passes Uv' (its
+// k . mu rows go to Kmu, unused).
+static void panel_pass(sgp_handle* h, hipStream_t s, const PanelScratch& b, const double* dXs, const double* dMu, int64_t nc,
+                       const double* second) {
+    launch_predict(h, s, h->dXusK, h->dParamsK, dXs, dMu, b.MeanC, nc);
+    launch_gram_uf(h, s, h->dXusK, dXs, nullptr, b.Kc, nullptr, h->dParamsK, nc, 0, nullptr, nullptr);
+    hipLaunchKernelGGL(k_quadform_fused, dim3((unsigned)((nc + TB - 1) / TB), 2 * h->T), dim3(256), 0, s, (const double*)b.Wk, second,
+                       (const double*)b.Kc, dMu, b.Pa, b.Pb, b.Kmu, h->Mp, h->T, nc);
+}
+
+// the symmetrised inverse of the d_out x d_out column-major W by Gauss-Jordan with partial pivoting; false when W is singular
+static bool invert_outmat(const double* W, int dout, OutMat* out) {
+    if (dout == 1) { out->v[0] = 1.0 / W[0]; return true; }
+    double a[MAXO][2 * MAXO];
+    for (int i = 0; i < dout; ++i)
+        for (int j = 0; j < dout; ++j) { a[i][j] = W[j * dout + i]; a[i][dout + j] = (i == j) ? 1.0 : 0.0; }
+    for (int c = 0; c < dout; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < dout; ++r) if (fabs(a[r][c]) > fabs(a[piv][c])) piv = r;
+        if (!(a[piv][c] != 0.0)) return false;
+        for (int j = 0; j < 2 * dout; ++j) std::swap(a[c][j], a[piv][j]);
+        const double inv = 1.0 / a[c][c];
+        for (int j = 0; j < 2 * dout; ++j) a[c][j] *= inv;
+        for (int r = 0; r < dout; ++r)
+            if (r != c && a[r][c] != 0.0) {
+                const double f = a[r][c];
+                for (int j = 0; j < 2 * dout; ++j) a[r][j] -= f * a[c][j];
+            }
+    }
+    for (int i = 0; i < dout; ++i)
+        for (int j = 0; j < dout; ++j) out->v[j * dout + i] = 0.5 * (a[i][dout + j] + a[j][dout + i]);
+    return true;
+}
+
 extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, double* mean) {
     if (!h || !Xstar || !mean || ns < 0) return fail(h, SGP_ERR_ARG, "sgp_predict: bad argument");
-    if (!h->have_inducing || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_predict: set_inducing and set_kernel first");
+    if (int rc = refuse_unset(h, "sgp_predict")) return rc;
     if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_predict: no posterior in the handle and mu_v is NULL");
-    if (h->training) return fail(h, SGP_ERR_ARG, "sgp_predict: a device-paced training run is open (sgp_train_end first)");
+    if (int rc = refuse_training(h, "sgp_predict")) return rc;
     if (ns == 0) return 0;
     if (int wrc = sync_all(h)) return wrc;
     hipStream_t s = h->own;
-    double *dXs = nullptr, *dMean = nullptr, *dMuTmp = nullptr;
-    if (int crc = call_scratch(h, (size_t)ns * (h->D + h->dout) + (mu_v ? (size_t)h->Q : 0), &dXs)) return crc;
-    dMean = dXs + (size_t)ns * h->D;
-    HIPCHK(h, hipMemcpy(dXs, Xstar, sizeof(double) * ns * h->D, hipMemcpyHostToDevice));
+    Carver c;
+    PredictScratch b;
+    layout_predict(c, ns, h->D, h->dout, mu_v ? h->Q : 0, &b);
+    if (int crc = carve_call_scratch(h, &c)) return crc;
+    layout_predict(c, ns, h->D, h->dout, mu_v ? h->Q : 0, &b);
+    HIPCHK(h, hipMemcpy(b.Xs, Xstar, sizeof(double) * ns * h->D, hipMemcpyHostToDevice));
     const double* dMu = h->dMu;
     if (mu_v) {
-        dMuTmp = dMean + (size_t)ns * h->dout;
-        HIPCHK(h, hipMemcpy(dMuTmp, mu_v, sizeof(double) * h->Q, hipMemcpyHostToDevice));
-        dMu = dMuTmp;
+        HIPCHK(h, hipMemcpy(b.Mu, mu_v, sizeof(double) * h->Q, hipMemcpyHostToDevice));
+        dMu = b.Mu;
     }
     mirror_current_params(h, s);
-    launch_predict(h, s, h->dXusK, h->dParamsK, dXs, dMu, dMean, ns);
+    launch_predict(h, s, h->dXusK, h->dParamsK, b.Xs, dMu, b.Mean, ns);
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpy(mean, dMean, sizeof(double) * ns * h->dout, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(mean, b.Mean, sizeof(double) * ns * h->dout, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2149,142 +2291,62 @@ extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const
 // parameters in call scratch -- K_uu, W_K = L_K^-1, the factor of Sigma_v -- and nothing the sweep keeps is written (dKuu, dWk, dKinv,
 // dSaccK, dWl, the log-det slot and dInfo stay what SGP_FLAG_REUSE_STATS and sgp_theta_objective expect); only the parameter mirror
 // dXusK / dParamsK is rewritten, as sgp_predict does.  The test points go through in chunks, so that the scratch stays bounded.
-constexpr int64_t PREDICT_CHUNK_DOUBLES = int64_t(1) << 25;     // scratch of one chunk: 256 MB
-
 extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
                                int32_t flags, double* mean, double* var) {
     if (!h || ns < 0 || (ns > 0 && (!Xstar || !mean || !var))) return fail(h, SGP_ERR_ARG, "sgp_predict_var: bad argument");
     if (flags & ~SGP_PREDICT_NOISE) return fail(h, SGP_ERR_ARG, "sgp_predict_var: unknown flags");
-    if (!mu_v != !Sigma_v) return fail(h, SGP_ERR_ARG, "sgp_predict_var: pass both mu_v and Sigma_v, or neither");
-    if (!h->have_inducing || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_predict_var: set_inducing and set_kernel first");
-    if (h->training) return fail(h, SGP_ERR_ARG, "sgp_predict_var: a device-paced training run is open (sgp_train_end first)");
-    if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_predict_var: no posterior in the handle and mu_v / Sigma_v are NULL");
-    if (!mu_v && h->posterior_set)
-        return fail(h, SGP_ERR_ARG, "sgp_predict_var: sgp_set_posterior gave no Sigma_v: pass mu_v and Sigma_v, or sweep first");
+    if (int rc = point_call_ready(h, "sgp_predict_var", mu_v, Sigma_v)) return rc;
     if (ns == 0) return 0;
-    if (int wrc = sync_all(h)) return wrc;
-    if (!mu_v) {
-        // the last sweep's q(v), refused exactly when sgp_get_posterior refuses it
-        if (int src = check_sync_status(h)) return src;
-        int info[2];
-        HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
-        if (int frc = factor_status(h, info[0], "K_uu (last sweep)", info[1], "Lambda (last sweep)", true)) return frc;
-    }
+    if (int wrc = point_call_wait(h, mu_v)) return wrc;
     hipStream_t s = h->own;
-    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T, TQ = h->TQ;
-    // chunk of test points: a multiple of 64, sized to the scratch budget (or SGP_PREDICT_CHUNK)
-    const int64_t per_point = (int64_t)Mp + 4 * T + 4 + D + dout + dout * dout;
-    int64_t chunk = h->env_predict_chunk > 0 ? h->env_predict_chunk : std::max<int64_t>(TB, PREDICT_CHUNK_DOUBLES / per_point);
-    chunk = std::min<int64_t>((chunk + TB - 1) / TB * TB, (ns + TB - 1) / TB * TB);
-    // scratch (doubles; every piece a multiple of 64, so that the 16-byte loads of the tiles stay aligned):
-    //   K_uu | W_K (Mp^2 each) | L_S (Qp^2) | chunk: K(Xu, X*) (Mp), pa, pb (2 T each), kmu (4), X* (D), mean (d_out), var (d_out^2)
-    //   | mu_v (Qp) | two factorisations' scratch | status words
-    const size_t fixed = 2 * (size_t)Mp * Mp + (size_t)Qp * Qp;
-    const size_t total = fixed + (size_t)(chunk * per_point) + Qp + 2 * POTRF_SCRATCH + 64;
-    double* base = nullptr;
-    if (int crc = call_scratch(h, total, &base)) return crc;
-    double* dKuuS = base;
-    double* dWkS = dKuuS + (size_t)Mp * Mp;
-    double* dLS = dWkS + (size_t)Mp * Mp;
-    double* dKc = dLS + (size_t)Qp * Qp;
-    double* dPa = dKc + (size_t)chunk * Mp;
-    double* dPb = dPa + (size_t)chunk * 2 * T;
-    double* dKmu = dPb + (size_t)chunk * 2 * T;
-    double* dXs = dKmu + (size_t)chunk * 4;
-    double* dMeanC = dXs + (size_t)chunk * D;
-    double* dVarC = dMeanC + (size_t)chunk * dout;
-    double* dMuX = dVarC + (size_t)chunk * dout * dout;
-    double* dPscr = dMuX + Qp;
-    int* dInfoS = reinterpret_cast<int*>(dPscr + 2 * POTRF_SCRATCH);
-    // q(v): the explicit one uploaded (Sigma_v padded with the identity), or the last sweep's mean in place and its Sigma_v
-    // (dSigma, what sgp_get_posterior returns -- not dWl, which sgp_set_prior(form 0) reuses) copied
-    const double* dMu = h->dMu;
-    if (mu_v) {
-        std::vector<double> m(Qp, 0.0);
-        memcpy(m.data(), mu_v, sizeof(double) * Q);
-        HIPCHK(h, hipMemcpy(dMuX, m.data(), sizeof(double) * Qp, hipMemcpyHostToDevice));
-        if (int rc = upload_padded(h, Sigma_v, dLS)) return rc;
-        dMu = dMuX;
-    } else {
-        hipLaunchKernelGGL(k_pad_square, dim3((unsigned)(((size_t)Qp * Qp + 255) / 256)), dim3(256), 0, s, (const double*)h->dSigma, Qp,
-                           dLS, Q, Qp);
-    }
-    HIPCHK(h, hipMemsetAsync(dPscr, 0, sizeof(double) * (2 * POTRF_SCRATCH + 64), s));
-    // the current parameters into the K_uu chain's mirror (as sgp_predict), K_uu at them and its inverse factor, Sigma_v's factor
-    mirror_current_params(h, s);
-    by_family(h->family, [&](auto F) {
-        hipLaunchKernelGGL(k_gram_uu<decltype(F)::value>, dim3(T, T), dim3(256), 0, s, h->dXusK, dKuuS, h->dParamsK, M, Mp, D);
-    });
-    launch_potrf(dKuuS, Mp, T, dInfoS + 0, M, dPscr, s, dWkS);
-    launch_potrf(dLS, Qp, TQ, dInfoS + 1, Q, dPscr + POTRF_SCRATCH, s);
-    HIPCHK(h, hipStreamSynchronize(s));
-    HIPCHK(h, hipGetLastError());
-    int info[2];
-    HIPCHK(h, hipMemcpy(info, dInfoS, sizeof info, hipMemcpyDeviceToHost));
-    if (int frc = factor_status(h, info[0], "K_uu (current kernel)", info[1], "Sigma_v")) return frc;
-    // the observation noise W^-1 (of the last sgp_set_noise), added in the finishing kernel: 0 without the flag
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T;
+    const PointShape shape = point_shape(h, (int64_t)Mp + 4 * T + 4 + D + dout + dout * dout, ns, 0);
+    const int64_t chunk = shape.chunk;
+    Carver c;
+    PredictVarScratch b;
+    layout_predict_var(c, shape, &b);
+    if (int crc = carve_call_scratch(h, &c)) return crc;
+    layout_predict_var(c, shape, &b);
+    // the last sweep's Sigma_v is copied: its factor is formed in place
+    const double *dMu, *dSig;
+    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.LS, &dMu, &dSig)) return rc;
+    if (!mu_v) hipLaunchKernelGGL(k_pad_square, dim3((unsigned)(((size_t)Qp * Qp + 255) / 256)), dim3(256), 0, s, dSig, Qp, b.LS, Q, Qp);
+    if (int rc = factor_begin(h, s, b)) return rc;
+    if (int frc = factor_finish(h, s, b, b.LS, Qp, h->TQ, Q, "Sigma_v")) return frc;
+    // the observation noise W^-1 (of the last sgp_set_noise, column-major), added in the finishing kernel: 0 without the flag
     OutMat noise;
     memset(&noise, 0, sizeof noise);
-    if (flags & SGP_PREDICT_NOISE) {
-        if (dout == 1) noise.v[0] = 1.0 / h->hParams->W[0];
-        else {
-            // Gauss-Jordan with partial pivoting on the d_out x d_out mean of q(W) (column-major, as sgp_set_noise stores it)
-            double a[MAXO][2 * MAXO];
-            for (int i = 0; i < dout; ++i)
-                for (int j = 0; j < dout; ++j) { a[i][j] = h->hParams->W[j * dout + i]; a[i][dout + j] = (i == j) ? 1.0 : 0.0; }
-            for (int c = 0; c < dout; ++c) {
-                int piv = c;
-                for (int r = c + 1; r < dout; ++r) if (fabs(a[r][c]) > fabs(a[piv][c])) piv = r;
-                if (!(a[piv][c] != 0.0)) return fail(h, SGP_ERR_ARG, "sgp_predict_var: the noise matrix of sgp_set_noise is singular");
-                for (int j = 0; j < 2 * dout; ++j) std::swap(a[c][j], a[piv][j]);
-                const double inv = 1.0 / a[c][c];
-                for (int j = 0; j < 2 * dout; ++j) a[c][j] *= inv;
-                for (int r = 0; r < dout; ++r)
-                    if (r != c && a[r][c] != 0.0) {
-                        const double f = a[r][c];
-                        for (int j = 0; j < 2 * dout; ++j) a[r][j] -= f * a[c][j];
-                    }
-            }
-            for (int i = 0; i < dout; ++i)
-                for (int j = 0; j < dout; ++j) noise.v[j * dout + i] = 0.5 * (a[i][dout + j] + a[j][dout + i]);
-        }
-    }
+    if ((flags & SGP_PREDICT_NOISE) && !invert_outmat(h->hParams->W, dout, &noise))
+        return fail(h, SGP_ERR_ARG, "sgp_predict_var: the noise matrix of sgp_set_noise is singular");
     for (int64_t s0 = 0; s0 < ns; s0 += chunk) {
         const int64_t nc = std::min<int64_t>(chunk, ns - s0);
-        const unsigned nblk = (unsigned)((nc + TB - 1) / TB);
-        HIPCHK(h, hipMemcpyAsync(dXs, Xstar + (size_t)s0 * D, sizeof(double) * nc * D, hipMemcpyHostToDevice, s));
-        // the mean: sgp_predict's kernel on the same mirror, so it is bitwise sgp_predict's
-        launch_predict(h, s, h->dXusK, h->dParamsK, dXs, dMu, dMeanC, nc);
-        // K(Xu, X*) (d_out = 0: no targets, no B partial -- k_gram_uf's K tile alone, in its summation order)
-        launch_gram_uf(h, s, h->dXusK, dXs, nullptr, dKc, nullptr, h->dParamsK, nc, 0, nullptr, nullptr);
-        // |W_K k*|^2 -> pa and, for d_out = 1, |L_S' k*|^2 -> pb: k_quadform_fused as sgp_w_stats runs it, with L_S where that
-        // passes Uv' (its k . mu rows go to kmu, unused).  MultiSGP needs cross terms instead of the second form: the launch then
-        // repeats W_K there (its pb is not read) and k_predvar_multi forms them.
-        hipLaunchKernelGGL(k_quadform_fused, dim3(nblk, 2 * T), dim3(256), 0, s, (const double*)dWkS, dout == 1 ? (const double*)dLS : dWkS,
-                           (const double*)dKc, dMu, dPa, dPb, dKmu, Mp, T, nc);
+        HIPCHK(h, hipMemcpyAsync(b.Xs, Xstar + (size_t)s0 * D, sizeof(double) * nc * D, hipMemcpyHostToDevice, s));
+        // MultiSGP needs cross terms instead of the second form: the pass then repeats W_K there (its Pb is not read) and
+        // k_predvar_multi forms them
+        panel_pass(h, s, b, b.Xs, dMu, nc, dout == 1 ? b.LS : b.Wk);
         if (dout == 1)
-            hipLaunchKernelGGL(k_predvar_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)dPa,
-                               (const double*)dPb, dVarC, (const Params*)h->dParamsK, noise.v[0], T, nc);
+            hipLaunchKernelGGL(k_predvar_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)b.Pa,
+                               (const double*)b.Pb, b.VarC, (const Params*)h->dParamsK, noise.v[0], T, nc);
         else
             by_dout(dout, [&](auto DO) {
-                hipLaunchKernelGGL(k_predvar_multi<decltype(DO)::value>, dim3(nblk), dim3(256), 0, s, (const double*)dLS, (const double*)dKc,
-                                   (const double*)dPa, dVarC, (const Params*)h->dParamsK, noise, M, Mp, Q, Qp, T, nc);
+                hipLaunchKernelGGL(k_predvar_multi<decltype(DO)::value>, dim3((unsigned)((nc + TB - 1) / TB)), dim3(256), 0, s,
+                                   (const double*)b.LS, (const double*)b.Kc, (const double*)b.Pa, b.VarC, (const Params*)h->dParamsK,
+                                   noise, M, Mp, Q, Qp, T, nc);
             });
         HIPCHK(h, hipGetLastError());
         // mean chunk: [d_out][nc] on the device -> rows s0 .. of the ns x d_out column-major output; var chunk: contiguous
-        HIPCHK(h, hipMemcpy2DAsync(mean + s0, sizeof(double) * ns, dMeanC, sizeof(double) * nc, sizeof(double) * nc, dout,
+        HIPCHK(h, hipMemcpy2DAsync(mean + s0, sizeof(double) * ns, b.MeanC, sizeof(double) * nc, sizeof(double) * nc, dout,
                                    hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(var + (size_t)s0 * dout * dout, dVarC, sizeof(double) * nc * dout * dout, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(var + (size_t)s0 * dout * dout, b.VarC, sizeof(double) * nc * dout * dout, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));             // (the next chunk's upload reuses the scratch; pageable host memory)
     }
     return 0;
 }
 
-// The :in log-messages of many nodes and their moment-matched marginals (include/sgp_hip.h).  Modelled on sgp_predict_var: blocking,
-// K_uu, W_K = L_K^-1, S and its factor formed at the CURRENT kernel parameters in call scratch, nothing the sweep keeps written, the
-// M-wide panel K(Xu, X) chunked under the same knob.  Launches: [pad Sigma_v] k_form_S_in, k_prep_xu, k_gram_uu, the two
-// factorisations; per chunk k_predict, k_gram_uf, k_quadform_fused, k_in_point_finish; k_in_moments once behind the last chunk,
-// over the logpdf and the points of ALL chunks (a node may straddle chunks).
+// The :in log-messages of many nodes and their moment-matched marginals (include/sgp_hip.h).  As sgp_predict_var: blocking, K_uu,
+// W_K = L_K^-1, S and its factor formed at the CURRENT kernel parameters in call scratch, nothing the sweep keeps written, the
+// M-wide panel chunked under the same knob.  k_in_moments runs once behind the last chunk, over the logpdf and the points of ALL
+// chunks (a node may straddle chunks).
 extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes,
                               const double* y_mean, const double* weights, const double* mu_v, const double* Sigma_v,
                               double* logpdf, double* log_norm, double* mean, double* cov) {
@@ -2293,12 +2355,7 @@ extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const i
     if (!X || !node_start || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_in_message: null X, node_start or y_mean");
     if (weights && (!log_norm || !mean || !cov))
         return fail(h, SGP_ERR_ARG, "sgp_in_message: weights given without log_norm, mean and cov");
-    if (!mu_v != !Sigma_v) return fail(h, SGP_ERR_ARG, "sgp_in_message: pass both mu_v and Sigma_v, or neither");
-    if (!h->have_inducing || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_in_message: set_inducing and set_kernel first");
-    if (h->training) return fail(h, SGP_ERR_ARG, "sgp_in_message: a device-paced training run is open (sgp_train_end first)");
-    if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_in_message: no posterior in the handle and mu_v / Sigma_v are NULL");
-    if (!mu_v && h->posterior_set)
-        return fail(h, SGP_ERR_ARG, "sgp_in_message: sgp_set_posterior gave no Sigma_v: pass mu_v and Sigma_v, or sweep first");
+    if (int rc = point_call_ready(h, "sgp_in_message", mu_v, Sigma_v)) return rc;
     if (n_nodes < 1 || n_nodes > n || node_start[0] != 0 || node_start[n_nodes] != n)
         return fail(h, SGP_ERR_ARG, "sgp_in_message: node_start must run from 0 to n");
     for (int64_t t = 0; t < n_nodes; ++t)
@@ -2307,16 +2364,9 @@ extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const i
         for (int64_t p = 0; p < n; ++p)
             if (!(weights[p] >= 0.0) || !std::isfinite(weights[p]))
                 return fail(h, SGP_ERR_ARG, "sgp_in_message: weights must be finite and non-negative");
-    if (int wrc = sync_all(h)) return wrc;
-    if (!mu_v) {
-        // the last sweep's q(v), refused exactly when sgp_get_posterior refuses it
-        if (int src = check_sync_status(h)) return src;
-        int info[2];
-        HIPCHK(h, hipMemcpy(info, h->dInfo, sizeof info, hipMemcpyDeviceToHost));
-        if (int frc = factor_status(h, info[0], "K_uu (last sweep)", info[1], "Lambda (last sweep)", true)) return frc;
-    }
+    if (int wrc = point_call_wait(h, mu_v)) return wrc;
     hipStream_t s = h->own;
-    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T;
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Qp = h->Qp, T = h->T;
     // W = mean(q_W) of the last sgp_set_noise ([w_bar] for d_out = 1), tr(W) and the nodes' rows y_t' W
     OutMat W;
     memset(&W, 0, sizeof W);
@@ -2333,99 +2383,44 @@ extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const i
         }
         for (int64_t p = node_start[t]; p < node_start[t + 1]; ++p) node_of[(size_t)p] = t;
     }
-    // chunk of points: a multiple of 64, sized to the scratch budget (or SGP_PREDICT_CHUNK), as sgp_predict_var
-    const int64_t per_point = (int64_t)Mp + 4 * T + 4 + dout;
-    int64_t chunk = h->env_predict_chunk > 0 ? h->env_predict_chunk : std::max<int64_t>(TB, PREDICT_CHUNK_DOUBLES / per_point);
-    chunk = std::min<int64_t>((chunk + TB - 1) / TB * TB, (n + TB - 1) / TB * TB);
-    // scratch (doubles; the pieces the tiles' 16-byte loads read come first, every one a multiple of 64):
-    //   K_uu | W_K | S -> L_S (Mp^2 each) | Sigma_v padded (Qp^2) | chunk: K(Xu, X) (Mp), pa, pb (2 T each), kmu (4), means (d_out)
-    //   | mu_v (Qp) | two factorisations' scratch | status words | all points: X (D), logpdf, weights, g, node (1 each)
-    //   | rows y' W (n_nodes d_out) | node_start (n_nodes + 1) | log_norm, mean, cov (n_nodes (1 + D + D^2))
     const size_t nn = (size_t)n_nodes;
-    const size_t fixed = 3 * (size_t)Mp * Mp + (size_t)Qp * Qp;
-    const size_t total = fixed + (size_t)(chunk * per_point) + Qp + 2 * POTRF_SCRATCH + 64 + (size_t)n * (D + 4) + nn * dout + (nn + 1) +
-                         nn * (1 + (size_t)D + (size_t)D * D);
-    double* base = nullptr;
-    if (int crc = call_scratch(h, total, &base)) return crc;
-    double* dKuuS = base;
-    double* dWkS = dKuuS + (size_t)Mp * Mp;
-    double* dSS = dWkS + (size_t)Mp * Mp;
-    double* dSigP = dSS + (size_t)Mp * Mp;
-    double* dKc = dSigP + (size_t)Qp * Qp;
-    double* dPa = dKc + (size_t)chunk * Mp;
-    double* dPb = dPa + (size_t)chunk * 2 * T;
-    double* dKmu = dPb + (size_t)chunk * 2 * T;
-    double* dMeanC = dKmu + (size_t)chunk * 4;
-    double* dMuX = dMeanC + (size_t)chunk * dout;
-    double* dPscr = dMuX + Qp;
-    int* dInfoS = reinterpret_cast<int*>(dPscr + 2 * POTRF_SCRATCH);
-    double* dXall = dPscr + 2 * POTRF_SCRATCH + 64;
-    double* dLp = dXall + (size_t)n * D;
-    double* dWt = dLp + n;
-    double* dG = dWt + n;
-    int64_t* dNode = reinterpret_cast<int64_t*>(dG + n);
-    double* dYw = dG + 2 * (size_t)n;
-    int64_t* dStart = reinterpret_cast<int64_t*>(dYw + nn * dout);
-    double* dLogNorm = dYw + nn * dout + (nn + 1);
-    double* dMeanN = dLogNorm + nn;
-    double* dCovN = dMeanN + nn * D;
-    // q(v): the explicit one uploaded (Sigma_v padded with the identity), or the last sweep's in place (dSigma: what
-    // sgp_get_posterior returns; leading dimension Qp either way)
-    const double* dMu = h->dMu;
-    const double* dSig = h->dSigma;
-    if (mu_v) {
-        std::vector<double> m(Qp, 0.0);
-        memcpy(m.data(), mu_v, sizeof(double) * Q);
-        HIPCHK(h, hipMemcpy(dMuX, m.data(), sizeof(double) * Qp, hipMemcpyHostToDevice));
-        if (int rc = upload_padded(h, Sigma_v, dSigP)) return rc;
-        dMu = dMuX;
-        dSig = dSigP;
-    }
-    HIPCHK(h, hipMemcpy(dXall, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dNode, node_of.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dYw, yw.data(), sizeof(double) * nn * dout, hipMemcpyHostToDevice));
+    const PointShape shape = point_shape(h, (int64_t)Mp + 4 * T + 4 + dout, n, n_nodes);
+    const int64_t chunk = shape.chunk;
+    Carver c;
+    InMessageScratch b;
+    layout_in_message(c, shape, &b);
+    if (int crc = carve_call_scratch(h, &c)) return crc;
+    layout_in_message(c, shape, &b);
+    const double *dMu, *dSig;
+    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.SigP, &dMu, &dSig)) return rc;
+    HIPCHK(h, hipMemcpy(b.Xall, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Node, node_of.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Yw, yw.data(), sizeof(double) * nn * dout, hipMemcpyHostToDevice));
     if (weights) {
-        HIPCHK(h, hipMemcpy(dWt, weights, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(dStart, node_start, sizeof(int64_t) * (nn + 1), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(b.Wt, weights, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(b.Start, node_start, sizeof(int64_t) * (nn + 1), hipMemcpyHostToDevice));
     }
-    HIPCHK(h, hipMemsetAsync(dPscr, 0, sizeof(double) * (2 * POTRF_SCRATCH + 64), s));
-    // the current parameters into the K_uu chain's mirror (as sgp_predict), K_uu at them and its inverse factor; S and its factor
-    mirror_current_params(h, s);
-    by_family(h->family, [&](auto F) {
-        hipLaunchKernelGGL(k_gram_uu<decltype(F)::value>, dim3(T, T), dim3(256), 0, s, h->dXusK, dKuuS, h->dParamsK, M, Mp, D);
-    });
-    hipLaunchKernelGGL(k_form_S_in, dim3((unsigned)(((size_t)Mp * Mp + 255) / 256)), dim3(256), 0, s, dSig, Qp, dMu, W, dSS, M, Mp, dout);
-    launch_potrf(dKuuS, Mp, T, dInfoS + 0, M, dPscr, s, dWkS);
-    launch_potrf(dSS, Mp, T, dInfoS + 1, M, dPscr + POTRF_SCRATCH, s);
-    HIPCHK(h, hipStreamSynchronize(s));
-    HIPCHK(h, hipGetLastError());
-    int info[2];
-    HIPCHK(h, hipMemcpy(info, dInfoS, sizeof info, hipMemcpyDeviceToHost));
-    if (int frc = factor_status(h, info[0], "K_uu (current kernel)", info[1], "S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)')")) return frc;
+    if (int rc = factor_begin(h, s, b)) return rc;
+    hipLaunchKernelGGL(k_form_S_in, dim3((unsigned)(((size_t)Mp * Mp + 255) / 256)), dim3(256), 0, s, dSig, Qp, dMu, W, b.SS, M, Mp, dout);
+    if (int frc = factor_finish(h, s, b, b.SS, Mp, T, M, "S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)')")) return frc;
     for (int64_t s0 = 0; s0 < n; s0 += chunk) {
         const int64_t nc = std::min<int64_t>(chunk, n - s0);
-        const unsigned nblk = (unsigned)((nc + TB - 1) / TB);
-        const double* dXs = dXall + (size_t)s0 * D;
-        // the d_out means k' mu^(d) (sgp_predict's kernel), K(Xu, X) of the chunk, |W_K k|^2 -> pa and |L_S' k|^2 -> pb
-        launch_predict(h, s, h->dXusK, h->dParamsK, dXs, dMu, dMeanC, nc);
-        launch_gram_uf(h, s, h->dXusK, dXs, nullptr, dKc, nullptr, h->dParamsK, nc, 0, nullptr, nullptr);
-        hipLaunchKernelGGL(k_quadform_fused, dim3(nblk, 2 * T), dim3(256), 0, s, (const double*)dWkS, (const double*)dSS,
-                           (const double*)dKc, dMu, dPa, dPb, dKmu, Mp, T, nc);
-        hipLaunchKernelGGL(k_in_point_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)dPa, (const double*)dPb,
-                           (const double*)dMeanC, (const double*)dYw, (const int64_t*)(dNode + s0), dLp + s0,
+        panel_pass(h, s, b, b.Xall + (size_t)s0 * D, dMu, nc, b.SS);
+        hipLaunchKernelGGL(k_in_point_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)b.Pa, (const double*)b.Pb,
+                           (const double*)b.MeanC, (const double*)b.Yw, (const int64_t*)(b.Node + s0), b.Lp + s0,
                            (const Params*)h->dParamsK, 0.5 * trW, T, nc, dout);
         HIPCHK(h, hipGetLastError());
     }
     if (weights)
-        hipLaunchKernelGGL(k_in_moments, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, s, (const double*)dLp, (const double*)dXall,
-                           (const double*)dWt, (const int64_t*)dStart, dG, dLogNorm, dMeanN, dCovN, D, n_nodes);
+        hipLaunchKernelGGL(k_in_moments, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, s, (const double*)b.Lp, (const double*)b.Xall,
+                           (const double*)b.Wt, (const int64_t*)b.Start, b.G, b.LogNorm, b.MeanN, b.CovN, D, n_nodes);
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
-    if (logpdf) HIPCHK(h, hipMemcpy(logpdf, dLp, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (logpdf) HIPCHK(h, hipMemcpy(logpdf, b.Lp, sizeof(double) * n, hipMemcpyDeviceToHost));
     if (weights) {
-        HIPCHK(h, hipMemcpy(log_norm, dLogNorm, sizeof(double) * nn, hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(mean, dMeanN, sizeof(double) * nn * D, hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(cov, dCovN, sizeof(double) * nn * D * D, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(log_norm, b.LogNorm, sizeof(double) * nn, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(mean, b.MeanN, sizeof(double) * nn * D, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(cov, b.CovN, sizeof(double) * nn * D * D, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -2895,11 +2890,7 @@ static int dense_common(int32_t device, const double* A, int32_t n, double* out,
     if (rc) return rc;
     sgp_handle* h = nullptr;
     const int np = round_up(n, TB), Tn = np / TB;
-    std::vector<double> tmp((size_t)np * np, 0.0);
-    for (int j = 0; j < np; ++j) {
-        if (j < n) memcpy(&tmp[(size_t)j * np], &A[(size_t)j * n], sizeof(double) * n);
-        else tmp[(size_t)j * np + j] = 1.0;
-    }
+    const std::vector<double> tmp = pad_square(A, n, np);
     const size_t mat = sizeof(double) * np * np;
     DevBuf bA, bInfo, bScr, bW, bC;
     HIPCHK(h, bA.alloc(mat));

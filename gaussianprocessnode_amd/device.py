@@ -264,16 +264,21 @@ class SGPDevice:
         self._check(self._lib.sgp_predict(self._h, ptr(Xs), ns, ptr(mu), ptr(out)), "sgp_predict")
         return out[0] if self.d_out == 1 else out.T.copy()
 
+    def _qv_args(self, what: str, mu_v, Sigma_v):
+        """An explicit q(v) as the ABI takes it -- mu_v (Q,), Sigma_v Q x Q column-major -- or (None, None): the handle's own."""
+        if (mu_v is None) != (Sigma_v is None):
+            raise ValueError(f"{what}: pass both mu_v and Sigma_v, or neither")
+        if mu_v is None:
+            return None, None
+        return as_f64(np.reshape(mu_v, (self.Q,))), as_f64(np.asarray(Sigma_v, dtype=np.float64).reshape(self.Q, self.Q).T)
+
     def predict_var(self, Xstar, mu_v=None, Sigma_v=None, noise: bool = False):
         """Predictive mean and (co)variance of the latent f at Xstar (sgp_predict_var), at the current kernel: (mean, var) with
         mean (ns,) and var (ns,) for d_out = 1, mean (ns, d_out) and var (ns, d_out, d_out) otherwise.  q(v) is the last sweep's
         (mu_v = Sigma_v = None) or the one given; noise=True adds W^-1 of the last `set_noise`."""
         Xs = as_f64(np.reshape(Xstar, (-1, self.D)))
         ns = Xs.shape[0]
-        if (mu_v is None) != (Sigma_v is None):
-            raise ValueError("predict_var: pass both mu_v and Sigma_v, or neither")
-        mu = None if mu_v is None else as_f64(np.reshape(mu_v, (self.Q,)))
-        S = None if Sigma_v is None else as_f64(np.asarray(Sigma_v, dtype=np.float64).reshape(self.Q, self.Q).T)   # column-major
+        mu, S = self._qv_args("predict_var", mu_v, Sigma_v)
         mean = np.empty((self.d_out, ns))
         var = np.empty(ns) if self.d_out == 1 else np.empty((ns, self.d_out, self.d_out))
         flags = _lib.SGP_PREDICT_NOISE if noise else 0
@@ -292,11 +297,8 @@ class SGPDevice:
         n_nodes = start.size - 1
         if n_nodes < 0:
             raise ValueError("in_message: node_start needs n_nodes + 1 entries")
-        if (mu_v is None) != (Sigma_v is None):
-            raise ValueError("in_message: pass both mu_v and Sigma_v, or neither")
+        mu, S = self._qv_args("in_message", mu_v, Sigma_v)
         y_cm = as_f64(np.asarray(y_mean, dtype=np.float64).reshape(n_nodes, self.d_out).T)      # column-major n_nodes x d_out
-        mu = None if mu_v is None else as_f64(np.reshape(mu_v, (self.Q,)))
-        S = None if Sigma_v is None else as_f64(np.asarray(Sigma_v, dtype=np.float64).reshape(self.Q, self.Q).T)   # column-major
         logpdf = np.empty(n)
         w = log_norm = mean = cov = None
         if weights is not None:

@@ -238,33 +238,15 @@ def marginal_in_batch(q_outs, lefts, q_v, q_w, q_theta: PointMass, meta: MultiSG
     decided on the host from the returned closure values) gets its left message back, as the reference returns it; False
     returns the shifted moments there too.  Returns a list of MvNormalMeanCovariance (or left messages)."""
     from .cubature import srcubature
-    from .unisgp import reference_moments_are_nan
-    q_outs, lefts = list(q_outs), list(lefts)
-    if len(q_outs) != len(lefts):
-        raise ValueError("marginal_in_batch: one left message per node")
-    if not lefts:
-        return []
-    W = _mean_W(q_w)
-    d_out = W.shape[0]
+    from .unisgp import _marginal_in_batch
     rule = srcubature()
-    pw = [rule.points_weights(*left.mean_cov()) for left in lefts]
-    X = np.concatenate([np.atleast_2d(np.asarray(p, dtype=np.float64)) for p, _ in pw])
-    wts = np.concatenate([np.asarray(w, dtype=np.float64) for _, w in pw])
-    start = np.concatenate([[0], np.cumsum([len(w) for _, w in pw])]).astype(np.int64)
-    Y = np.stack([np.asarray(q.mean(), dtype=np.float64).ravel() for q in q_outs])
-    eng = _engine(meta, 1, d_out)
-    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
-    eng.set_noise(W)
-    mu_v, Sigma_v = q_v.mean_cov()
-    lp, _, mean, cov = eng.in_message(X, start, Y, wts, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64))
-    out = []
-    for t, left in enumerate(lefts):
-        if reference_fallback and reference_moments_are_nan(lp[start[t]:start[t + 1]]):
-            out.append(left)
-        else:
-            out.append(MvNormalMeanCovariance(np.array(mean[t], dtype=np.float64), np.array(cov[t], dtype=np.float64)))
-    return out
+    return _marginal_in_batch(
+        q_outs, lefts, q_v, q_theta, meta, reference_fallback,
+        points_weights_of=lambda left: rule.points_weights(*left.mean_cov()),
+        y_of=lambda q: q.mean(),
+        engine_of=lambda: _engine(meta, 1, _mean_W(q_w).shape[0]),
+        set_noise=lambda eng: eng.set_noise(_mean_W(q_w)),
+        make_marginal=lambda mean, cov: MvNormalMeanCovariance(np.array(mean, dtype=np.float64), np.array(cov, dtype=np.float64)))
 
 
 def prod_logpdf(left, right, reference_fallback: bool = True):

@@ -485,6 +485,32 @@ def shifted_moments(pts, wts, logpdf):
     return a + math.log(Z), mean, (d * g[:, None]).T @ d / Z
 
 
+def _marginal_in_batch(q_outs, lefts, q_v, q_theta, meta, reference_fallback, *, points_weights_of, y_of, engine_of, set_noise,
+                       make_marginal):
+    """What `unisgp.marginal_in_batch` and `multisgp.marginal_in_batch` share: the cubature points of every left message
+    (points_weights_of(left) -> (points, weights)) and the rows y_of(q_out) go to `SGPDevice.in_message` of engine_of() in one
+    call, at the kernel of q_theta, the noise set_noise(engine) installs and the explicit q_v; node t gets
+    make_marginal(mean_t, cov_t), or its left message back under the reference's NaN fallback."""
+    q_outs, lefts = list(q_outs), list(lefts)
+    if len(q_outs) != len(lefts):
+        raise ValueError("marginal_in_batch: one left message per node")
+    if not lefts:
+        return []
+    pw = [points_weights_of(left) for left in lefts]
+    X = np.concatenate([np.asarray(p, dtype=np.float64).reshape(len(w), -1) for p, w in pw])
+    wts = np.concatenate([np.asarray(w, dtype=np.float64) for _, w in pw])
+    start = np.concatenate([[0], np.cumsum([len(w) for _, w in pw])]).astype(np.int64)
+    y = np.stack([np.asarray(y_of(q), dtype=np.float64).ravel() for q in q_outs])
+    eng = engine_of()
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    set_noise(eng)
+    mu_v, Sigma_v = q_v.mean_cov()
+    lp, _, mean, cov = eng.in_message(X, start, y, wts, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64))
+    return [left if reference_fallback and reference_moments_are_nan(lp[start[t]:start[t + 1]]) else make_marginal(mean[t], cov[t])
+            for t, left in enumerate(lefts)]
+
+
 def marginal_in_batch(q_outs, lefts, q_v, q_w, q_theta, meta: UniSGPMeta, reference_fallback: bool = True):
     """q(x_t) of T UniSGP nodes in ONE device call: `prod_logpdf(lefts[t], rule_in(q_outs[t], ...))` for every t
     (GPnode/UniSGPnode.jl:39-46 over :107-122).  The ghcubature(21) points of every left message go to `SGPDevice.in_message`
@@ -495,27 +521,11 @@ def marginal_in_batch(q_outs, lefts, q_v, q_w, q_theta, meta: UniSGPMeta, refere
     from .cubature import ghcubature
     if meta.Xu.shape[1] != 1:
         raise ValueError("unisgp.marginal_in_batch: the Gauss-Hermite product needs a one-dimensional input")
-    q_outs, lefts = list(q_outs), list(lefts)
-    if len(q_outs) != len(lefts):
-        raise ValueError("marginal_in_batch: one left message per node")
-    if not lefts:
-        return []
     rule = ghcubature(21)
-    pw = [rule.points_weights(left.mean(), left.var()) for left in lefts]
-    X = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1, 1) for p, _ in pw])
-    wts = np.concatenate([np.asarray(w, dtype=np.float64) for _, w in pw])
-    start = np.concatenate([[0], np.cumsum([len(w) for _, w in pw])]).astype(np.int64)
-    y = np.array([[float(q.mean())] for q in q_outs])
-    eng = _engine(meta, 1)
-    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
-    eng.set_noise([[_mean_w(q_w)]], _elog_w(q_w))
-    mu_v, Sigma_v = q_v.mean_cov()
-    lp, _, mean, cov = eng.in_message(X, start, y, wts, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64))
-    out = []
-    for t, left in enumerate(lefts):
-        if reference_fallback and reference_moments_are_nan(lp[start[t]:start[t + 1]]):
-            out.append(left)
-        else:
-            out.append(NormalMeanVariance(float(np.ravel(mean[t])[0]), float(np.ravel(cov[t])[0]) + 1e-6))
-    return out
+    return _marginal_in_batch(
+        q_outs, lefts, q_v, q_theta, meta, reference_fallback,
+        points_weights_of=lambda left: rule.points_weights(left.mean(), left.var()),
+        y_of=lambda q: [float(q.mean())],
+        engine_of=lambda: _engine(meta, 1),
+        set_noise=lambda eng: eng.set_noise([[_mean_w(q_w)]], _elog_w(q_w)),
+        make_marginal=lambda mean, cov: NormalMeanVariance(float(np.ravel(mean)[0]), float(np.ravel(cov)[0]) + 1e-6))

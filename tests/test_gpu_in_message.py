@@ -261,3 +261,35 @@ def test_marginal_in_batch_matches_the_rule_in_closures(G):
         meta.engine.close()
         if getattr(meta, "_aux_engine", None) is not None:
             meta._aux_engine.close()
+
+
+def test_predict_var_and_in_message_share_the_call_scratch_cleanly(G, monkeypatch):
+    """predict_var, in_message, predict_var on ONE handle: the two calls lay the same call scratch out differently, every piece
+    rounded up to 64 doubles, so at sizes that are no multiple of 64 (M = 40: Mp != M, Q = 80: Qp != Q, 150 points, 7 uneven
+    nodes) an overlap of two pieces or stale data of the other call's layout would show.  Bitwise: predict_var before and after
+    the in_message call, and in_message against a fresh handle."""
+    monkeypatch.setenv("SGP_PREDICT_CHUNK", "64")                         # 150 points = 2 full chunks and 22
+    M, D, d_out, n = 40, 3, 2, 150
+    rng = np.random.default_rng(24)
+    c = dict(M=M, D=D, d_out=d_out, Xu=rng.uniform(-1.8, 1.8, (M, D)), sigma2=0.9, ell=np.array([1.1, 0.8, 1.3]), jitter=1e-6,
+             family="se", W=np.array([[2.0, 0.3], [0.3, 1.5]]))
+    sizes = [1, 40, 23, 2, 64, 7, 13]
+    assert sum(sizes) == n
+    start = np.concatenate([[0], np.cumsum(sizes)])
+    X = rng.uniform(-1.8, 1.8, (n, D))
+    w = rng.uniform(0.1, 1.0, n)
+    Y = rng.normal(size=(len(sizes), d_out))
+    mu = rng.normal(size=M * d_out)
+    A = rng.normal(size=(M * d_out, M * d_out))
+    Sig = A @ A.T / (M * d_out) + 0.1 * np.eye(M * d_out)
+    with device_for(G, c) as dev:
+        first = dev.predict_var(X, mu, Sig, noise=True)
+        msg = dev.in_message(X, start, Y, w, mu, Sig)
+        second = dev.predict_var(X, mu, Sig, noise=True)
+    with device_for(G, c) as dev:
+        fresh = dev.in_message(X, start, Y, w, mu, Sig)
+    assert all(np.isfinite(a).all() for a in first + msg)
+    for a, b in zip(first, second):
+        assert np.array_equal(a, b)
+    for a, b in zip(msg, fresh):
+        assert np.array_equal(a, b)

@@ -2361,9 +2361,15 @@ extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const i
     for (int64_t t = 0; t < n_nodes; ++t)
         if (node_start[t + 1] <= node_start[t]) return fail(h, SGP_ERR_ARG, "sgp_in_message: node_start must increase (no empty node)");
     if (weights)
-        for (int64_t p = 0; p < n; ++p)
-            if (!(weights[p] >= 0.0) || !std::isfinite(weights[p]))
-                return fail(h, SGP_ERR_ARG, "sgp_in_message: weights must be finite and non-negative");
+        for (int64_t t = 0; t < n_nodes; ++t) {
+            bool positive = false;
+            for (int64_t p = node_start[t]; p < node_start[t + 1]; ++p) {
+                if (!(weights[p] >= 0.0) || !std::isfinite(weights[p]))
+                    return fail(h, SGP_ERR_ARG, "sgp_in_message: weights must be finite and non-negative");
+                positive = positive || weights[p] > 0.0;
+            }
+            if (!positive) return fail(h, SGP_ERR_ARG, "sgp_in_message: the weights of a node sum to 0 (its moments do not exist)");
+        }
     if (int wrc = point_call_wait(h, mu_v)) return wrc;
     hipStream_t s = h->own;
     const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Qp = h->Qp, T = h->T;

@@ -3240,7 +3240,8 @@ __global__ void __launch_bounds__(256) k_in_point_finish(const double* __restric
     logpdf[n] = (lin - half_trW * (P->sigma2 - a)) - 0.5 * b;
 }
 
-// Moments of one node's weighted points under exp(logpdf), shifted by the node's largest logpdf a:  g_s = w_s exp(logpdf_s - a),
+// Moments of one node's weighted points under exp(logpdf), shifted by a, the largest logpdf among the node's points of positive
+// weight (a zero-weight point takes no part; the host refuses a node without a positive weight):  g_s = w_s exp(logpdf_s - a),
 //   log_norm = a + log sum g,  mean = sum g x / sum g,  cov = sum g (x - mean)(x - mean)' / sum g  (about the new mean).
 // One wavefront per node (four nodes per workgroup): lane l sums the points l, l + 64, .. of its node in order, the 64 partial
 // sums meet in an xor butterfly -- every lane ends with the same bits, and a repeated call with them again.  No atomics.
@@ -3259,11 +3260,12 @@ __global__ void __launch_bounds__(256) k_in_moments(const double* __restrict__ l
         return v;
     };
     double a = -__builtin_inf();
-    for (int64_t s = s0 + lane; s < s1; s += 64) a = fmax(a, lp[s]);
+    for (int64_t s = s0 + lane; s < s1; s += 64)
+        if (w[s] > 0.0) a = fmax(a, lp[s]);
     for (int o = 32; o > 0; o >>= 1) a = fmax(a, __shfl_xor(a, o));
     double z = 0.0;
     for (int64_t s = s0 + lane; s < s1; s += 64) {
-        const double gs = w[s] * exp(lp[s] - a);
+        const double gs = w[s] > 0.0 ? w[s] * exp(lp[s] - a) : 0.0;     // (a zero-weight point may lie above a: 0 * inf)
         g[s] = gs;
         z += gs;
     }

@@ -473,12 +473,15 @@ def reference_moments_are_nan(logpdf) -> bool:
 
 
 def shifted_moments(pts, wts, logpdf):
-    """(log_norm, mean, cov) of the weighted points under exp(logpdf), shifted by the largest logpdf (what sgp_in_message
-    computes on the device): g = w exp(logpdf - a), mean = sum g x / sum g, cov about that mean."""
+    """(log_norm, mean, cov) of the weighted points under exp(logpdf), shifted by the largest logpdf among the points of
+    positive weight (what sgp_in_message computes on the device): g = w exp(logpdf - a), mean = sum g x / sum g, cov about that
+    mean; a point of weight 0 takes no part."""
     pts = np.asarray(pts, dtype=np.float64).reshape(len(wts), -1)
     lp = np.asarray(logpdf, dtype=np.float64)
-    a = float(lp.max())
-    g = np.asarray(wts, dtype=np.float64) * np.exp(lp - a)
+    w = np.asarray(wts, dtype=np.float64)
+    a = float(lp[w > 0].max()) if np.any(w > 0) else float(lp.max())
+    with np.errstate(over="ignore", invalid="ignore"):
+        g = np.where(w > 0, w * np.exp(lp - a), 0.0)
     Z = float(g.sum())
     mean = (g @ pts) / Z
     d = pts - mean

@@ -270,13 +270,15 @@ int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double
  *     logpdf_p = -1/2 tr(W) (sigma2 - |L_K^-1 k|^2) + sum_d (y_t' W)_d k' mu_v^(d) - 1/2 k' S k,
  *     S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)'),   k' S k = |L_S' k|^2 with S = L_S L_S'
  * (both quadratic forms through factors, as sgp_w_stats and sgp_predict_var take them).  weights (n cubature weights; NULL: no
- * moments) turns every node's points into the moments of N(x) exp(logpdf(x)), shifted by a = max_s logpdf_s of the node:
+ * moments) turns every node's points into the moments of N(x) exp(logpdf(x)), shifted by a = max logpdf_s over the node's points
+ * of positive weight (a point of weight 0 takes no part in the moments or in the shift, however large its logpdf):
  *     g_s = w_s exp(logpdf_s - a),  log_norm = a + log sum g,  mean = sum g x / sum g,  cov = sum g (x - mean)(x - mean)' / sum g
  * -- approximate_meancov of the reference's products, which exponentiates unshifted and returns NaN where exp overflows or
  * every term underflows; the shifted sums are finite there.  Outputs: logpdf [n] (may be NULL), log_norm [n_nodes], mean
  * D x n_nodes, cov D x D x n_nodes (every block exactly symmetric); the last three are required exactly when weights is given.
  * Posterior: mu_v and Sigma_v both given, or both NULL for the last finished sweep's q(v) -- the rules of sgp_predict_var.
- * SGP_ERR_ARG: node_start not as above (an empty node included), negative or non-finite weights, weights without the three moment
+ * SGP_ERR_ARG: node_start not as above (an empty node included), negative or non-finite weights, a node whose weights sum to 0
+ * (its moments do not exist; weights of 0 beside a positive one are accepted), weights without the three moment
  * outputs, the posterior cases sgp_predict_var refuses, an open sgp_train_* run.  A K_uu (at the current kernel) or S that is not
  * positive definite returns its failing leading minor k > 0.  n = 0 returns 0, nothing done.
  * Blocking.  Everything is formed in call scratch and the points go through in chunks, as in sgp_predict_var: nothing the sweep

@@ -199,6 +199,11 @@ def test_statuses(G):
             wb = np.array(w)
             wb[7] = v
             assert raw(dev, X, st, Y, wb, mu, Sig) == ERR_ARG, v
+        wb = np.array(w)
+        wb[st[2]:st[3]] = 0.0                                             # a node whose weights sum to 0: no moments
+        assert raw(dev, X, st, Y, wb, mu, Sig) == ERR_ARG
+        wb[st[2]] = 0.25                                                  # (one positive weight beside zeros is fine)
+        assert raw(dev, X, st, Y, wb, mu, Sig) == 0
         for missing in range(1, 4):                                       # weights without one of log_norm, mean, cov
             outs = [True] * 4
             outs[missing] = False

@@ -1,4 +1,4 @@
-// Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message).  Plain C++, no HIP: the
+// Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad).  Plain C++, no HIP: the
 // layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
 #pragma once
 
@@ -85,6 +85,38 @@ static inline void layout_in_message(Carver& c, const PointShape& p, InMessageSc
     b->LogNorm = c.take<double>(nn);
     b->MeanN = c.take<double>(nn * D);
     b->CovN = c.take<double>(nn * D * D);
+}
+
+// sgp_in_message_grad: sgp_in_message's factors and logpdf, the matrix A = tr(W) K_uu^-1 - S, and one chunk of the (1 + D)-column
+// panels P = [k | J_1 .. J_D] and U = A P with the chunk's outputs
+struct InMessageGradScratch : PanelScratch {
+    double* SS;                     // S -> its factor (the logpdf's second form)
+    double* SigP;                   // an explicit Sigma_v padded with the identity
+    double* A;                      // a copy of S taken before it is factored -> A, zero on the padding
+    double* Kinv;                   // W_K' W_K
+    double *Xall, *Lp;              // all points: X, logpdf
+    int64_t* Node;                  // all points: the node of each
+    double* Yw;                     // per node: the row y_t' W
+    double *Pn, *Un;                // per chunk: P and U, [point][1 + D][Mp]
+    double* Qc;                     // per chunk: q = s_t + A k and the weights of the z z' terms, [point][2][Mp]
+    double *GradC, *HessC;          // per chunk: the gradients [point][D] and Hessians [point][D][D]
+};
+static inline void layout_in_message_grad(Carver& c, const PointShape& p, InMessageGradScratch* b) {
+    const size_t n = (size_t)p.n, nn = (size_t)p.n_nodes, D = (size_t)p.D, ch = (size_t)p.chunk;
+    layout_panel(c, p, b);
+    b->SS = c.take<double>((size_t)p.Mp * p.Mp);
+    b->SigP = c.take<double>((size_t)p.Qp * p.Qp);
+    b->A = c.take<double>((size_t)p.Mp * p.Mp);
+    b->Kinv = c.take<double>((size_t)p.Mp * p.Mp);
+    b->Xall = c.take<double>(n * D);
+    b->Lp = c.take<double>(n);
+    b->Node = c.take<int64_t>(n);
+    b->Yw = c.take<double>(nn * p.dout);
+    b->Pn = c.take<double>(ch * (1 + D) * p.Mp);
+    b->Un = c.take<double>(ch * (1 + D) * p.Mp);
+    b->Qc = c.take<double>(ch * 2 * p.Mp);
+    b->GradC = c.take<double>(ch * D);
+    b->HessC = c.take<double>(ch * D * D);
 }
 
 // sgp_predict: the points, their means and an explicit mu_v (Q entries, unpadded)

@@ -2431,6 +2431,93 @@ extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const i
     return 0;
 }
 
+// The :in log-messages' gradients and Hessians with respect to the input (include/sgp_hip.h).  A third client of the point-batch
+// pipeline: sgp_in_message's factors, S and logpdf (the same factor_begin / factor_finish / panel_pass / k_in_point_finish on the
+// same inputs, so logpdf is bitwise sgp_in_message's), then A = tr(W) W_K' W_K - S from a copy of S taken before its factorisation,
+// and per chunk the panel P = [k | J], U = A P on the matrix cores and the per-point finish.  Everything in call scratch.
+extern "C" int sgp_in_message_grad(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes,
+                                   const double* y_mean, const double* mu_v, const double* Sigma_v, double* logpdf, double* grad,
+                                   double* hess) {
+    if (!h || n < 0 || n_nodes < 0) return fail(h, SGP_ERR_ARG, "sgp_in_message_grad: bad argument");
+    if (n == 0) return 0;
+    if (!X || !node_start || !y_mean || !grad) return fail(h, SGP_ERR_ARG, "sgp_in_message_grad: null X, node_start, y_mean or grad");
+    if (int rc = point_call_ready(h, "sgp_in_message_grad", mu_v, Sigma_v)) return rc;
+    if (h->family == SGP_KERNEL_MATERN12)
+        return fail(h, SGP_ERR_ARG, "sgp_in_message_grad: the Matern-1/2 kernel has no gradient at the inducing inputs");
+    if (n_nodes < 1 || n_nodes > n || node_start[0] != 0 || node_start[n_nodes] != n)
+        return fail(h, SGP_ERR_ARG, "sgp_in_message_grad: node_start must run from 0 to n");
+    for (int64_t t = 0; t < n_nodes; ++t)
+        if (node_start[t + 1] <= node_start[t])
+            return fail(h, SGP_ERR_ARG, "sgp_in_message_grad: node_start must increase (no empty node)");
+    if (int wrc = point_call_wait(h, mu_v)) return wrc;
+    hipStream_t s = h->own;
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Qp = h->Qp, T = h->T;
+    OutMat W;
+    memset(&W, 0, sizeof W);
+    double trW = 0.0;
+    for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
+    for (int i = 0; i < dout; ++i) trW += W.v[i * dout + i];
+    std::vector<double> yw((size_t)n_nodes * dout);
+    std::vector<int64_t> node_of((size_t)n);
+    for (int64_t t = 0; t < n_nodes; ++t) {
+        for (int d = 0; d < dout; ++d) {
+            double v = 0.0;
+            for (int e = 0; e < dout; ++e) v = fma(y_mean[t + e * n_nodes], W.v[e + d * dout], v);
+            yw[(size_t)t * dout + d] = v;
+        }
+        for (int64_t p = node_start[t]; p < node_start[t + 1]; ++p) node_of[(size_t)p] = t;
+    }
+    // per point of a chunk: the M-wide panel's share as in sgp_in_message, the columns of P and U, q and the z z' weights, the outputs
+    const int64_t per_point = (int64_t)Mp + 4 * T + 4 + dout + (int64_t)(2 * (1 + D) + 2) * Mp + D + D * D;
+    const PointShape shape = point_shape(h, per_point, n, n_nodes);
+    const int64_t chunk = shape.chunk;
+    Carver c;
+    InMessageGradScratch b;
+    layout_in_message_grad(c, shape, &b);
+    if (int crc = carve_call_scratch(h, &c)) return crc;
+    layout_in_message_grad(c, shape, &b);
+    const double *dMu, *dSig;
+    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.SigP, &dMu, &dSig)) return rc;
+    HIPCHK(h, hipMemcpy(b.Xall, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Node, node_of.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Yw, yw.data(), sizeof(double) * (size_t)n_nodes * dout, hipMemcpyHostToDevice));
+    const unsigned sq_blocks = (unsigned)(((size_t)Mp * Mp + 255) / 256);
+    if (int rc = factor_begin(h, s, b)) return rc;
+    hipLaunchKernelGGL(k_form_S_in, dim3(sq_blocks), dim3(256), 0, s, dSig, Qp, dMu, W, b.SS, M, Mp, dout);
+    HIPCHK(h, hipMemcpyAsync(b.A, b.SS, sizeof(double) * Mp * Mp, hipMemcpyDeviceToDevice, s));     // (S, before its factor replaces it)
+    if (int frc = factor_finish(h, s, b, b.SS, Mp, T, M, "S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)')")) return frc;
+    launch_ata(b.Wk, b.Kinv, Mp, T, s);
+    hipLaunchKernelGGL(k_in_form_A, dim3(sq_blocks), dim3(256), 0, s, (const double*)b.Kinv, (const double*)b.A, b.A, trW, M, Mp);
+    for (int64_t s0 = 0; s0 < n; s0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, n - s0), ncols = nc * (D + 1);
+        const double* dXs = b.Xall + (size_t)s0 * D;
+        if (logpdf) {
+            panel_pass(h, s, b, dXs, dMu, nc, b.SS);
+            hipLaunchKernelGGL(k_in_point_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)b.Pa,
+                               (const double*)b.Pb, (const double*)b.MeanC, (const double*)b.Yw, (const int64_t*)(b.Node + s0), b.Lp + s0,
+                               (const Params*)h->dParamsK, 0.5 * trW, T, nc, dout);
+        }
+        by_family(h->family, [&](auto F) {
+            constexpr int FAM = decltype(F)::value;
+            hipLaunchKernelGGL(k_in_grad_panel<FAM>, dim3((unsigned)((nc + 15) / 16), T), dim3(256), 0, s, (const double*)h->dXu, dXs,
+                               b.Pn, (const Params*)h->dParamsK, M, Mp, D, nc);
+            hipLaunchKernelGGL(k_in_grad_gemm, dim3((unsigned)((ncols + TB - 1) / TB), T), dim3(256), 0, s, (const double*)b.A,
+                               (const double*)b.Pn, b.Un, Mp, T, ncols);
+            hipLaunchKernelGGL(k_in_grad_finish<FAM>, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, (const double*)b.Pn,
+                               (const double*)b.Un, (const double*)h->dXu, dXs, dMu, (const double*)b.Yw,
+                               (const int64_t*)(b.Node + s0), b.Qc, b.GradC, hess ? b.HessC : nullptr, (const Params*)h->dParamsK, M, Mp, D,
+                               dout, nc);
+        });
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(grad + (size_t)s0 * D, b.GradC, sizeof(double) * nc * D, hipMemcpyDeviceToHost, s));
+        if (hess) HIPCHK(h, hipMemcpyAsync(hess + (size_t)s0 * D * D, b.HessC, sizeof(double) * nc * D * D, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));             // (the next chunk reuses the scratch; pageable host memory)
+    }
+    HIPCHK(h, hipGetLastError());
+    if (logpdf) HIPCHK(h, hipMemcpy(logpdf, b.Lp, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // F(theta) = -sum_n [ -w/2 k_nn + w/2 |L^-1 k_n|^2 - w/2 |Uv k_n|^2 + w y_n mu_v'k_n ]  (derivative_helper.jl:23-39)
 //          = w/2 [ s_kk - tr(Kuu^-1 Psi2) + tr(R Psi2) ] - w b'mu_v
 // evaluated at the CURRENT kernel parameters with q(v) (mu_v, R = Sigma_v + mu mu') held fixed at the last finished

@@ -3295,6 +3295,221 @@ __global__ void __launch_bounds__(256) k_in_moments(const double* __restrict__ l
         }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Input-message gradients and Hessians (sgp_in_message_grad): the Laplace form of @rule MultiSGP(:in), GPnode/MultiSGPnode.jl:210-236,
+// differentiates the closure above with ForwardDiff / Zygote; here analytically.  With k = K(Xu, x), A = tr(W) K_uu^-1 - S:
+//   logpdf = -1/2 tr(W) sigma2 + s_t' k + 1/2 k' A k,   q = s_t + A k,   grad = J' q,   hess = J' A J + sum_m q_m grad^2 k_m,
+//   k_m = sigma2 g(s_m),  s_m = sum_d ((x_d - u_md) / ell_d)^2,  z_md = (x_d - u_md) / ell_d^2,
+//   J_md = 2 sigma2 g'(s_m) z_md,   grad^2 k_m = sigma2 [4 g''(s_m) z_m z_m' + 2 g'(s_m) diag(1 / ell^2)].
+// Four kernels per chunk of points: k_in_grad_panel writes P = [k | J_1 .. J_D] (Mp rows, 1 + D columns per point, rows >= M zero),
+// k_in_grad_gemm forms U = A P on the matrix cores, k_in_grad_finish takes the dot products, one wavefront per point.  A is formed
+// once per call by k_in_form_A, zero on the padding (so neither P's nor A's padding can leak: both are zero).
+// ------------------------------------------------------------------------------------------------
+// kappa = g, g' and g'' of a family at s (Matern-1/2 has no gradient at the inducing inputs: the host refuses it).  At r = 0 the
+// Matern-3/2 g'' is infinite and multiplies z z' = 0: 0 is returned, the limit of the product.
+template <int FAM>
+__device__ __forceinline__ void fam_g012(double s, double& g0, double& g1, double& g2) {
+    if constexpr (FAM == 0) { const double e = exp(-0.5 * s); g0 = e; g1 = -0.5 * e; g2 = 0.25 * e; }
+    else if constexpr (FAM == 2) {
+        const double r = sqrt(s), a = FAM_SQRT3 * r, e = exp(-a);
+        g0 = (1.0 + a) * e; g1 = -1.5 * e; g2 = r > 0.0 ? (0.75 * FAM_SQRT3) * e / r : 0.0;
+    } else if constexpr (FAM == 3) {
+        const double a = FAM_SQRT5 * sqrt(s), e = exp(-a);
+        g0 = fma(5.0 / 3.0, s, 1.0 + a) * e; g1 = -(5.0 / 6.0) * (1.0 + a) * e; g2 = (25.0 / 12.0) * e;
+    } else { g0 = g1 = g2 = 0.0; }
+}
+
+// A = tr(W) Kinv - S on the leading M x M block, 0 elsewhere (Kinv and S both carry the identity there).  Kinv (k_gemm32's
+// mirrored product) and S (k_form_S_in) are exactly symmetric, so A is.  S and A may be the same buffer.
+__global__ void __launch_bounds__(256) k_in_form_A(const double* Kinv, const double* S, double* A, double trW, int M, int Mp) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)Mp * Mp) return;
+    const int i = (int)(e % Mp), j = (int)(e / Mp);
+    A[e] = (i < M && j < M) ? fma(trW, Kinv[e], -S[e]) : 0.0;
+}
+
+// P of N points: Pn[(n (1 + D) + c) Mp + m], c = 0: k_m, c = 1 + d: J_md.  The differences are taken from the UNSCALED inducing
+// inputs Xu (M x D, a row per inducing input) and scaled afterwards, t_d = (x_d - u_md) / ell_d: k_gram_uf subtracts the scaled
+// coordinates, which is good enough for the squared distance but leaves x_d - u_md, which J is proportional to, with the relative
+// error eps (|x_d| + |u_md|) / |x_d - u_md|.  k and J here are values and derivatives of one function.  Thread = row m of a 64-row
+// tile (blockIdx.y) with its D coordinates in registers, wave = 4 of the workgroup's 16 points, whose coordinates are wave-uniform
+// loads.  Isotropic and ARD lengthscales alike: P->inv_ell has D entries.
+template <int FAM>
+__global__ void __launch_bounds__(256) k_in_grad_panel(const double* __restrict__ Xu, const double* __restrict__ X,
+                                                       double* __restrict__ Pn, const Params* __restrict__ P, int M, int Mp, int D,
+                                                       int64_t N) {
+    const int m = blockIdx.y * TB + (threadIdx.x & 63);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    double u[MAXD];
+    const bool live = m < M;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) u[d] = (d < D && live) ? Xu[(size_t)m * D + d] : 0.0;
+    const double s2 = P->sigma2;
+    for (int q = 0; q < 4; ++q) {
+        const int64_t n = (int64_t)blockIdx.x * 16 + wave * 4 + q;
+        if (n >= N) return;                                            // (wave-uniform)
+        const double* x = X + (size_t)n * D;
+        double t[MAXD], s = 0.0;
+#pragma unroll
+        for (int d = 0; d < MAXD; ++d) {
+            t[d] = 0.0;
+            if (d < D) { t[d] = (x[d] - u[d]) * P->inv_ell[d]; s = fma(t[d], t[d], s); }
+        }
+        double g0, g1, g2;
+        fam_g012<FAM>(s, g0, g1, g2);
+        double* col = Pn + (size_t)n * (D + 1) * Mp + m;
+        col[0] = live ? s2 * g0 : 0.0;
+        const double c = 2.0 * s2 * g1;                                // J_md = 2 sigma2 g' z_md,  z_md = t_d / ell_d
+#pragma unroll
+        for (int d = 0; d < MAXD; ++d)
+            if (d < D) col[(size_t)(d + 1) * Mp] = live ? c * (t[d] * P->inv_ell[d]) : 0.0;
+    }
+}
+
+// U = A P: workgroup (column block blockIdx.x, row tile I = blockIdx.y) forms the 64 x 64 tile U[I, 64 columns] = sum_k A[I, k] P[k,
+// columns] over the T tile columns of the symmetric A (ld x ld, ld = T 64) with v_mfma_f64_16x16x4_f64, k in ascending order.  The A
+// tile is staged [kk][i] with stride PS as it arrives (A's columns are contiguous along i), the P tile [column][kk] with stride
+// KMS (P's columns are contiguous along kk) -- k_quadform_fused's first-factor staging and operand reads; the next tile pair is
+// fetched into registers while the matrix cores work on the current one.  Columns beyond ncols are read clamped, zeroed, and not
+// stored.  A column's result does not depend on which block or chunk it lies in: the contraction order is fixed per entry.
+__global__ void __launch_bounds__(256, 2) k_in_grad_gemm(const double* __restrict__ A, const double* __restrict__ Pn,
+                                                        double* __restrict__ Un, int ld, int T, int64_t ncols) {
+    __shared__ __attribute__((aligned(16))) double lds[TB * PS + TB * KMS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int I = blockIdx.y;
+    const int64_t c0 = (int64_t)blockIdx.x * TB;
+    double* As = lds;
+    double* Bs = lds + TB * PS;
+    Acc4 acc;
+    acc_zero(acc);
+    double2 ra[4][2], rb[4][2];
+    auto gload = [&](int k) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int t = tid + 256 * u, hi = t >> 4, lo4 = (t & 15) * 4;
+            const double* sa = A + (size_t)(k * TB + hi) * ld + I * TB + lo4;          // A[I*64 + lo4 .., k*64 + hi]
+            ra[u][0] = *reinterpret_cast<const double2*>(sa);
+            ra[u][1] = *reinterpret_cast<const double2*>(sa + 2);
+            const int64_t col = c0 + hi;
+            const double* sb = Pn + (size_t)(col < ncols ? col : ncols - 1) * ld + k * TB + lo4;
+            rb[u][0] = *reinterpret_cast<const double2*>(sb);
+            rb[u][1] = *reinterpret_cast<const double2*>(sb + 2);
+            if (col >= ncols) { rb[u][0] = make_double2(0.0, 0.0); rb[u][1] = make_double2(0.0, 0.0); }
+        }
+    };
+    auto lstore = [&]() {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int t = tid + 256 * u, hi = t >> 4, lo4 = (t & 15) * 4;
+            double* da = As + hi * PS + lo4;                                             // As[kk = hi][i = lo4 ..]
+            *reinterpret_cast<double2*>(da) = ra[u][0];
+            *reinterpret_cast<double2*>(da + 2) = ra[u][1];
+            double* db = Bs + hi * KMS + lo4;                                            // Bs[column = hi][kk = lo4 ..]
+            *reinterpret_cast<double2*>(db) = rb[u][0];
+            *reinterpret_cast<double2*>(db + 2) = rb[u][1];
+        }
+    };
+    gload(0);
+    const int li = lane & 15, lk = lane >> 4;
+    const int r0 = wr * 32 + li, r1 = r0 + 16, j0 = wc * 32 + li, j1 = j0 + 16;
+#pragma unroll 1
+    for (int k = 0; k < T; ++k) {
+        __syncthreads();                              // the previous tile pair has been consumed
+        lstore();
+        __syncthreads();
+        if (k + 1 < T) gload(k + 1);
+        const double* ap = As + lk * PS;
+        const double* bp = Bs + lk;
+#pragma unroll 4
+        for (int kk = 0; kk < TB; kk += 4) {
+            const double a0 = ap[r0], a1 = ap[r1];
+            const double b0 = bp[j0 * KMS], b1 = bp[j1 * KMS];
+            acc.t[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc.t[0][0], 0, 0, 0);
+            acc.t[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc.t[0][1], 0, 0, 0);
+            acc.t[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc.t[1][0], 0, 0, 0);
+            acc.t[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc.t[1][1], 0, 0, 0);
+            ap += 4 * PS;
+            bp += 4;
+        }
+    }
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj) {
+        const int64_t col = c0 + acc_col(lane, wc, tj);
+        if (col >= ncols) continue;
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Un[(size_t)col * ld + I * TB + acc_row(lane, wr, ti, r)] = acc.t[ti][tj][r];
+    }
+}
+
+// grad and hess of N points from their columns of P and U.  One wavefront per point (four per workgroup), lane l the rows l, l + 64,
+// .. < M in order, the 64 partial sums met in an xor butterfly: a fixed order whatever the chunk.  Pass 1 forms, per row m,
+// q_m = s_t[m] + U_0[m] (s_t[m] = sum_d yw[t][d] mu^(d)_m on the fly) and w_m = 4 sigma2 g''(s_m) q_m into qc (a lane reads back only
+// what it wrote), and sums c = 2 sigma2 sum_m g'(s_m) q_m.  Pass 2: grad_d = sum_m q_m J_md; for d <= e
+//   hess_de = sum_m (J_md U_e[m] + w_m z_md z_me) + delta_de c / ell_d^2,
+// the z recomputed from x, Xu and ell as k_in_grad_panel takes them; written at (d, e) and (e, d): exactly symmetric.  hess may be null.
+template <int FAM>
+__global__ void __launch_bounds__(256) k_in_grad_finish(const double* __restrict__ Pn, const double* __restrict__ Un,
+                                                        const double* __restrict__ Xu, const double* __restrict__ X,
+                                                        const double* __restrict__ mu, const double* __restrict__ yw,
+                                                        const int64_t* __restrict__ node, double* qc, double* __restrict__ grad,
+                                                        double* __restrict__ hess, const Params* __restrict__ P, int M, int Mp, int D,
+                                                        int dout, int64_t N) {
+    const int lane = threadIdx.x & 63;
+    const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    auto wave_sum = [](double v) {
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        return v;
+    };
+    const double* Pk = Pn + (size_t)n * (D + 1) * Mp;
+    const double* Uk = Un + (size_t)n * (D + 1) * Mp;
+    const double* x = X + (size_t)n * D;
+    const double* row = yw + (size_t)node[n] * dout;
+    double* qv = qc + (size_t)n * 2 * Mp;
+    double* wv = qv + Mp;
+    const double s2 = P->sigma2;
+    double c = 0.0;
+    for (int m = lane; m < M; m += 64) {
+        double st = 0.0;
+        for (int d = 0; d < dout; ++d) st = fma(row[d], mu[(size_t)d * M + m], st);
+        const double q = st + Uk[m];
+        double s = 0.0;
+        for (int d = 0; d < D; ++d) { const double t = (x[d] - Xu[(size_t)m * D + d]) * P->inv_ell[d]; s = fma(t, t, s); }
+        double g0, g1, g2;
+        fam_g012<FAM>(s, g0, g1, g2);
+        qv[m] = q;
+        wv[m] = 4.0 * s2 * g2 * q;
+        c = fma(2.0 * s2 * g1, q, c);
+    }
+    c = wave_sum(c);
+    for (int d = 0; d < D; ++d) {
+        const double* Jd = Pk + (size_t)(d + 1) * Mp;
+        double g = 0.0;
+        for (int m = lane; m < M; m += 64) g = fma(qv[m], Jd[m], g);
+        g = wave_sum(g);
+        if (lane == 0) grad[(size_t)n * D + d] = g;
+        if (!hess) continue;
+        const double ied = P->inv_ell[d] * P->inv_ell[d], xd = x[d];
+        for (int e = d; e < D; ++e) {
+            const double* Ue = Uk + (size_t)(e + 1) * Mp;
+            const double iee = P->inv_ell[e] * P->inv_ell[e], xe = x[e];
+            double hv = 0.0;
+            for (int m = lane; m < M; m += 64) {
+                const double zd = (xd - Xu[(size_t)m * D + d]) * ied, ze = (xe - Xu[(size_t)m * D + e]) * iee;
+                hv = fma(Jd[m], Ue[m], fma(wv[m] * zd, ze, hv));
+            }
+            hv = wave_sum(hv);
+            if (d == e) hv = fma(c, ied, hv);
+            if (lane == 0) {
+                hess[((size_t)n * D + e) * D + d] = hv;
+                hess[((size_t)n * D + d) * D + e] = hv;
+            }
+        }
+    }
+}
+
 // transpose-copy of a square column-major matrix (Uv = L_R^T on the way out)
 __global__ void __launch_bounds__(256) k_transpose(const double* __restrict__ A, double* __restrict__ At, int ld) {
     __shared__ double tile[TB * (TB + 1)];

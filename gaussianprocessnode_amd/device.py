@@ -309,6 +309,26 @@ class SGPDevice:
                     "sgp_in_message")
         return logpdf if weights is None else (logpdf, log_norm, mean, cov)
 
+    def in_message_grad(self, X, node_start, y_mean, mu_v=None, Sigma_v=None, hessian: bool = True):
+        """The :in log-messages of many nodes with their gradients and Hessians with respect to the input (sgp_in_message_grad),
+        analytic, at the current kernel and the last `set_noise`.  X, node_start, y_mean and q(v) as in `in_message`.  Returns
+        (logpdf (n,), grad (n, D), hess (n, D, D) or None without `hessian`); logpdf is bitwise `in_message`'s, every Hessian
+        exactly symmetric.  The Matern-1/2 family is refused."""
+        Xs = as_f64(np.reshape(X, (-1, self.D)))
+        n = Xs.shape[0]
+        start = np.ascontiguousarray(np.asarray(node_start, dtype=np.int64).reshape(-1))
+        n_nodes = start.size - 1
+        if n_nodes < 0:
+            raise ValueError("in_message_grad: node_start needs n_nodes + 1 entries")
+        mu, S = self._qv_args("in_message_grad", mu_v, Sigma_v)
+        y_cm = as_f64(np.asarray(y_mean, dtype=np.float64).reshape(n_nodes, self.d_out).T)      # column-major n_nodes x d_out
+        logpdf, grad = np.empty(n), np.empty((n, self.D))
+        hess = np.empty((n, self.D, self.D)) if hessian else None
+        self._check(self._lib.sgp_in_message_grad(self._h, ptr(Xs), n, start.ctypes.data_as(C.POINTER(C.c_int64)), n_nodes,
+                                                  ptr(y_cm), ptr(mu), ptr(S), ptr(logpdf), ptr(grad), ptr(hess)),
+                    "sgp_in_message_grad")
+        return logpdf, grad, hess
+
     def set_posterior(self, mu_v, Uv):
         """Install an external q(v) (mean and Uv = chol(Sigma_v + mu mu').U) for the per-point outputs (`w_stats`)."""
         mu = as_f64(np.reshape(mu_v, (self.Q,)))

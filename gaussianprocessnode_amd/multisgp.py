@@ -299,6 +299,84 @@ def rule_in_laplace(q_out, q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMet
     return MvNormalWeightedMeanPrecision(W_z @ m_z, W_z)                                # :235
 
 
+def damped_newton_batch(evaluate, x0, iterations: int = 20, gtol: float = 1e-6):
+    """Minimise f_t = -logpdf_t for T independent nodes together.  evaluate(X (T, D)) -> (logpdf (T,), grad (T, D), hess
+    (T, D, D)) of logpdf, one point per node (one device call).  From x0, every round steps each unfinished node by
+    (H + lambda_t I) delta = -g for f (H = -hess, g = -grad), lambda_t >= 0 raised until the matrix is positive definite; the
+    trial point is accepted only if f decreased, otherwise lambda_t grows and the node retries in the next round.  A node is
+    finished when |g|_inf <= thr_t = gtol max(1, |g(x0)|_inf).  At most iterations + 1 calls of `evaluate`.  Returns x (T, D), f, g,
+    H at the last accepted points, thr (T,), converged (T,), rounds (T,): the calls each node took a step in."""
+    x = np.array(x0, dtype=np.float64)
+    T, D = x.shape
+    lp, gr, he = evaluate(x)
+    f, g, H = -np.asarray(lp, dtype=np.float64), -np.asarray(gr, dtype=np.float64), -np.asarray(he, dtype=np.float64)
+    thr = gtol * np.maximum(1.0, np.max(np.abs(g), axis=1))
+    lam = np.zeros(T)
+    rounds = np.zeros(T, dtype=np.int64)
+    done = np.max(np.abs(g), axis=1) <= thr
+    for _ in range(iterations):
+        if done.all():
+            break
+        trial = x.copy()
+        for t in np.flatnonzero(~done):
+            w, V = np.linalg.eigh(H[t])
+            scale = max(float(np.max(np.abs(w))), 1e-300)
+            if w[0] <= 1e-8 * scale:                  # not positive definite: the most negative direction is flipped, w_0 + lambda = |w_0|
+                lam[t] = max(lam[t], 2.0 * abs(float(w[0])) + 1e-3 * scale)
+            trial[t] = x[t] - V @ ((V.T @ g[t]) / (w + lam[t]))
+        lp, gr, he = evaluate(trial)
+        for t in np.flatnonzero(~done):
+            rounds[t] += 1
+            if np.isfinite(lp[t]) and -lp[t] < f[t]:
+                x[t], f[t], g[t], H[t] = trial[t], -lp[t], -gr[t], -he[t]
+                lam[t] *= 0.25
+                done[t] = np.max(np.abs(g[t])) <= thr[t]
+            else:
+                lam[t] = max(4.0 * lam[t], 1e-3 * max(float(np.max(np.abs(np.diag(H[t])))), 1e-300))
+    return x, f, g, H, thr, done, rounds
+
+
+def rule_in_laplace_batch(q_outs, q_ins, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, iterations: int = 20,
+                          gtol: float = 1e-6):
+    """The Laplace form of @rule MultiSGP(:in) (GPnode/MultiSGPnode.jl:210-236) for T nodes together: the batched replacement of
+    a loop over `rule_in_laplace`.  Every node's negative closure is minimised from mean(q_in) by the damped Newton iteration of
+    `damped_newton_batch`, whose every round is ONE `SGPDevice.in_message_grad` call with one point per node (closure value,
+    analytic gradient and Hessian; the D x D systems are solved on the host): at most iterations + 1 device calls in all,
+    against hundreds of K_uu chains for the finite differences of the per-node form.  Returns (marginals, records):
+    marginals[t] = MvNormalWeightedMeanPrecision(W_z m_z, W_z) with W_z the analytic Hessian of the negative closure at m_z,
+    records[t] = dict(converged, rounds, grad_inf, threshold, proper, mode = m_z).  A node whose W_z is not positive definite is returned as
+    the reference would return it (the improper precision), with proper = False; a node that has not met its threshold after
+    `iterations` rounds is returned where it stands, with converged = False."""
+    q_outs, q_ins = list(q_outs), list(q_ins)
+    if len(q_outs) != len(q_ins):
+        raise ValueError("rule_in_laplace_batch: one q_in per node")
+    if not q_ins:
+        return [], []
+    W = _mean_W(q_w)
+    D_in = np.asarray(meta.Xu).shape[1]
+    x0 = np.stack([np.asarray(q.mean(), dtype=np.float64).ravel() for q in q_ins]).reshape(len(q_ins), D_in)
+    y = np.stack([np.asarray(q.mean(), dtype=np.float64).ravel() for q in q_outs])
+    eng = _engine(meta, 1, W.shape[0])
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    eng.set_noise(W)
+    mu_v, Sigma_v = q_v.mean_cov()
+    mu_v, Sigma_v = np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64)
+    start = np.arange(len(q_ins) + 1, dtype=np.int64)
+    x, _, g, H, thr, done, rounds = damped_newton_batch(lambda X: eng.in_message_grad(X, start, y, mu_v, Sigma_v), x0, iterations, gtol)
+    marginals, records = [], []
+    for t in range(len(q_ins)):
+        try:
+            np.linalg.cholesky(H[t])
+            proper = True
+        except np.linalg.LinAlgError:
+            proper = False
+        marginals.append(MvNormalWeightedMeanPrecision(H[t] @ x[t], H[t].copy()))        # :235
+        records.append(dict(converged=bool(done[t]), rounds=int(rounds[t]), grad_inf=float(np.max(np.abs(g[t]))),
+                            threshold=float(thr[t]), proper=proper, mode=x[t].copy()))
+    return marginals, records
+
+
 def _second_moment_contraction(q_out, q_v, W, M):
     """s = sum_d mu_v^(d) (mu_y' W)_d and S = sum_ij W_ij Rv_blk[i][j] -- what the :in and :theta closures keep of q(v)."""
     mu_y = np.asarray(q_out.mean(), dtype=np.float64).ravel()

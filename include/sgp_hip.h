@@ -288,6 +288,32 @@ int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const int64_t* nod
                    const double* weights, const double* mu_v, const double* Sigma_v, double* logpdf, double* log_norm,
                    double* mean, double* cov);
 
+/* sgp_in_message_grad: the :in log-messages of many nodes with their gradients and Hessians with respect to the input -- what the
+ * Laplace form of @rule MultiSGP(:in) (GPnode/MultiSGPnode.jl:210-236) takes from ForwardDiff / Zygote of the closure
+ * (GPnode/MultiSGPnode.jl:162-208), here analytic and for the points of all nodes in one call.  X, node_start, y_mean, W, the kernel
+ * (current parameters, family, jitter) and q(v) are sgp_in_message's.  For point p of node t, k = K(Xu, x_p),
+ * s_t = sum_d mu_v^(d) (y_t' W)_d, S as in sgp_in_message and A = tr(W) (K_uu + jitter I)^-1 - S:
+ *     logpdf_p = -1/2 tr(W) sigma2 + s_t' k + 1/2 k' A k        (bitwise the value sgp_in_message returns: the same kernels on the
+ *                                                                 same inputs, both quadratic forms through factors)
+ *     q        = s_t + A k
+ *     grad_p   = J' q,                      J = dk/dx  (M x D)
+ *     hess_p   = J' A J + sum_m q_m grad^2 k_m          (D x D, stored exactly symmetric)
+ * with k_m = sigma2 g(s_m), s_m = sum_d ((x_d - u_md) / ell_d)^2, r = sqrt(s), z_md = (x_d - u_md) / ell_d^2:
+ *     J_md = 2 sigma2 g'(s_m) z_md,    grad^2 k_m = sigma2 [4 g''(s_m) z_m z_m' + 2 g'(s_m) diag(1 / ell^2)]
+ *     SE          g' = -1/2 exp(-s/2)                            g'' = 1/4 exp(-s/2)
+ *     Matern-5/2  g' = -5/6 (1 + sqrt5 r) exp(-sqrt5 r)          g'' = 25/12 exp(-sqrt5 r)
+ *     Matern-3/2  g' = -3/2 exp(-sqrt3 r)                        g'' = 3 sqrt3 / 4 exp(-sqrt3 r) / r   (g'' z z' = 0 at r = 0, its limit)
+ * Outputs: logpdf [n] (may be NULL), grad D x n, hess D x D x n (may be NULL), column-major.
+ * SGP_ERR_ARG: what sgp_in_message refuses (node_start, the posterior cases, an open sgp_train_* run), a null grad, and
+ * SGP_KERNEL_MATERN12 (a kink at every inducing input: no gradient there).  A K_uu (at the current kernel) or S that is not
+ * positive definite returns its failing leading minor k > 0.  n = 0 returns 0, nothing done.
+ * Blocking.  Everything is formed in call scratch and the points go through in chunks (SGP_PREDICT_CHUNK), as in sgp_in_message:
+ * nothing the sweep keeps is written (sgp_sweep_kind and the theta objective are unaffected).  U = A [k | J] runs on the FP64
+ * matrix cores; all sums are in a fixed order, one wavefront per point, no atomics: repeated calls agree bitwise, and so do calls
+ * that differ in the chunk size. */
+int sgp_in_message_grad(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes, const double* y_mean,
+                        const double* mu_v, const double* Sigma_v, double* logpdf, double* grad, double* hess);
+
 /* sgp_wait: returns when everything this handle has enqueued -- on its own streams or the caller's -- has finished: what a caller
  * does between `infer` calls when it wants the sweep to be over but none of its results yet.  The library's streams are polled
  * (hipStreamQuery, up to ~2 ms, then the blocking call): a blocking hipDeviceSynchronize may put the thread to sleep until an

@@ -178,6 +178,25 @@ function in_message(h::Handle, X::Matrix{Float64}, node_start::Vector{Int64}, y_
     return moments ? (logpdf, log_norm, m, C) : logpdf
 end
 
+# the :in log-messages with their analytic gradients and Hessians with respect to the input (include/sgp_hip.h,
+# sgp_in_message_grad): what the Laplace form of @rule MultiSGP(:in) (GPnode/MultiSGPnode.jl:210-236) takes from ForwardDiff /
+# Zygote, for the points of all nodes in one call.  X, node_start, y_mean, μ_v, Σ_v as in `in_message`; returns (logpdf n,
+# grad D × n, hess D × D × n or nothing).  Written blind like the rest of this file, never executed: only the ccall signature is
+# stated here, no rule dispatches on it yet (gaussianprocessnode_amd/multisgp.py, rule_in_laplace_batch, is the tested host loop).
+function in_message_grad(h::Handle, X::Matrix{Float64}, node_start::Vector{Int64}, y_mean::Matrix{Float64}, μ_v = nothing,
+                         Σ_v = nothing; hessian = true)
+    n = size(X, 2); n_nodes = length(node_start) - 1
+    logpdf = zeros(n); grad = zeros(h.d, n)
+    hess = hessian ? zeros(h.d, h.d, n) : nothing
+    μp = μ_v === nothing ? C_NULL : Vector{Float64}(μ_v)
+    Σp = Σ_v === nothing ? C_NULL : Matrix{Float64}(Σ_v)
+    check(ccall((:sgp_in_message_grad, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}),
+                h.ptr, X, n, node_start, n_nodes, y_mean, μp, Σp, logpdf, grad, hessian ? hess : C_NULL), h.ptr)
+    return logpdf, grad, hess
+end
+
 # q(v) installed from outside for the per-point outputs (include/sgp_hip.h, sgp_set_posterior): mean and the upper factor
 # Uv = chol(Σ_v + μ μ').U, column-major Q × Q -- a Julia Matrix as it is
 set_posterior!(h::Handle, μ_v::Vector{Float64}, Uv::Matrix{Float64}) =

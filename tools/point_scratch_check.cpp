@@ -1,7 +1,7 @@
 // Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over a grid of shapes, the
-// pieces that layout_predict_var and layout_in_message hand out are pairwise disjoint at the sizes their consumers need (stated
-// here independently of the layout functions), every piece starts a multiple of Carver::ALIGN doubles from the base, and the
-// last piece ends at the total of the sizing pass.  No GPU:
+// pieces that layout_predict_var, layout_in_message and layout_in_message_grad hand out are pairwise disjoint at the sizes their
+// consumers need (stated here independently of the layout functions), every piece starts a multiple of Carver::ALIGN doubles from
+// the base, and the last piece ends at the total of the sizing pass.  No GPU:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o tools/point_scratch_check tools/point_scratch_check.cpp
 //   (or any C++17 compiler with -fsanitize=address,undefined) && tools/point_scratch_check
 #include "../gaussianprocessnode_amd/csrc/point_scratch.h"
@@ -97,6 +97,35 @@ void check_shape(const PointShape& s, double* base, size_t capacity, size_t* lar
             check(s, base, total, c.used, p);
         }
     }
+    {
+        Carver c;
+        InMessageGradScratch b;
+        layout_in_message_grad(c, s, &b);
+        const size_t total = c.used;
+        *largest = std::max(*largest, total);
+        if (base && total <= capacity) {
+            c = Carver{base};
+            layout_in_message_grad(c, s, &b);
+            std::vector<Piece> p = panel_pieces(s, b);
+            const size_t d = sizeof(double), n = (size_t)s.n, nn = (size_t)s.n_nodes, D = (size_t)s.D, ch = (size_t)s.chunk, Mp = s.Mp;
+            p.push_back({"SS", b.SS, Mp * Mp * d});
+            p.push_back({"SigP", b.SigP, (size_t)s.Qp * s.Qp * d});
+            p.push_back({"A", b.A, Mp * Mp * d});
+            p.push_back({"Kinv", b.Kinv, Mp * Mp * d});
+            p.push_back({"Xall", b.Xall, n * D * d});
+            p.push_back({"Lp", b.Lp, n * d});
+            p.push_back({"Node", b.Node, n * sizeof(int64_t)});
+            p.push_back({"Yw", b.Yw, nn * s.dout * d});
+            // the panel GEMM reads whole columns of P and writes whole columns of U: (1 + D) columns of Mp per point
+            p.push_back({"Pn", b.Pn, ch * (1 + D) * Mp * d});
+            p.push_back({"Un", b.Un, ch * (1 + D) * Mp * d});
+            p.push_back({"Qc", b.Qc, ch * 2 * Mp * d});
+            p.push_back({"GradC", b.GradC, ch * D * d});
+            p.push_back({"HessC", b.HessC, ch * D * D * d});
+            if ((const char*)b.Info != (const char*)b.Pscr + 2 * (size_t)POTRF_SCRATCH * d) fail(s, "Info is not directly behind Pscr", "");
+            check(s, base, total, c.used, p);
+        }
+    }
 }
 
 // every shape of the grid: pass 0 finds the largest total, pass 1 checks over one allocation of that size
@@ -126,6 +155,6 @@ int main() {
     size_t again = 0;
     const long shapes = sweep(base, largest, &again);
     std::free(base);
-    std::printf("%ld shapes x 2 layouts, largest total %zu doubles: %ld failure(s)\n", shapes, largest, failures);
+    std::printf("%ld shapes x 3 layouts, largest total %zu doubles: %ld failure(s)\n", shapes, largest, failures);
     return failures ? 1 : 0;
 }

@@ -1396,9 +1396,9 @@ static double* mirror_for(const sgp_handle* h) {
 
 // the TRACE_BLOCKS shares of tr(K_uu^-1 Psi2) into dTrace and of tr(R Psi2) behind them, in their own launches (MultiSGP's sweep, the
 // objective at a new theta; the UniSGP sweep takes both from the Sigma launch's epilogue)
-static void launch_traces(sgp_handle* h, hipStream_t s) {
+static void launch_traces(sgp_handle* h, hipStream_t s, const double* Rv = nullptr) {
     hipLaunchKernelGGL(k_trace_kinv, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dKinv, h->dTrace, h->M, h->Mp);
-    hipLaunchKernelGGL(k_trace_R, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, h->dR, h->dTrace + TRACE_BLOCKS, h->M, h->Mp, h->dout,
+    hipLaunchKernelGGL(k_trace_R, dim3(TRACE_BLOCKS), dim3(256), 0, s, h->dStats, Rv ? Rv : h->dR, h->dTrace + TRACE_BLOCKS, h->M, h->Mp, h->dout,
                        h->Qp, (int64_t*)nullptr);
 }
 
@@ -2543,6 +2543,23 @@ static size_t theta_multi_doubles(const sgp_handle* h) {
     return 2 * (size_t)h->Qp * h->Qp + (size_t)h->dout * (size_t)std::max<int64_t>(h->n_max, 1) + (size_t)h->dout * h->Mp + h->Mp;
 }
 
+// R_v of the theta objective on `s`, UniSGP and MultiSGP alike -- the last sweep's dR, or, when sgp_set_posterior came later,
+// Uv^T Uv of the installed q(v) formed at the head of the objective's scratch (dUvT holds Uv^T, identity-padded like the sweep's
+// own R_v; the pad rows / columns are not read).  Formed once per sgp_theta_objective; value and gradient both take it from
+// here: the installed mean with the last sweep's R_v is no q(v) at all.
+static int theta_Rv(sgp_handle* h, hipStream_t s, const double** Rv) {
+    *Rv = h->dR;
+    if (!h->posterior_set) return 0;
+    if (!h->dThetaMulti)
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dThetaMulti), sizeof(double) * theta_multi_doubles(h)));
+    double* dRs = h->dThetaMulti;
+    double* dUv = dRs + (size_t)h->Qp * h->Qp;
+    hipLaunchKernelGGL(k_transpose, dim3(h->TQ, h->TQ), dim3(256), 0, s, (const double*)h->dUvT, dUv, h->Qp);
+    launch_gemm(h->dUvT, dUv, dRs, h->Qp, h->TQ, s);
+    *Rv = dRs;
+    return 0;
+}
+
 // tr(W) of the current mean(q_W), summed in the same order wherever it is used
 static double theta_trace_W(const sgp_handle* h) {
     double t = 0.0;
@@ -2550,9 +2567,12 @@ static double theta_trace_W(const sgp_handle* h) {
     return t;
 }
 
-static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
+// `Rv`: UniSGP's R_v when the caller has formed it already (theta_objective_eval); nullptr: taken from theta_Rv here
+static int enqueue_theta_grad(sgp_handle* h, hipStream_t s, const double* Rv = nullptr) {
     const int Mp = h->Mp, T = h->T;
     if (int arc = alloc_theta_grad(h)) return arc;
+    if (!Rv && h->dout == 1)
+        if (int rrc = theta_Rv(h, s, &Rv)) return rrc;       // (before the side stream's launches: an early return leaves no hand-off open)
     double* dG = h->dGradM;
     double* dT1 = dG + (size_t)Mp * Mp;
     double* dH = dT1 + (size_t)Mp * Mp;
@@ -2580,7 +2600,7 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s) {
     });
     if (split) hipLaunchKernelGGL(k_join_set, dim3(1), dim3(64), 0, su, h->dJoin + WORD_GRAD, ++h->grad_epoch);
     const bool multi = h->dout > 1;
-    if (!multi) hipLaunchKernelGGL(k_form_G, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, h->dR, h->dKinv, dG, cnt);
+    if (!multi) hipLaunchKernelGGL(k_form_G, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, Rv, h->dKinv, dG, cnt);
     if (h->n > 0) {
         // (MultiSGP: G (= S - tr(W) K_uu^-1), omega W y and the padded mean columns were formed by enqueue_theta_multi_value)
         const double* yw = h->dYw;
@@ -2630,7 +2650,7 @@ static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s) {
     if (int arc = alloc_theta_grad(h)) return arc;
     if (!h->dThetaMulti)
         HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dThetaMulti), sizeof(double) * theta_multi_doubles(h)));
-    const int M = h->M, Mp = h->Mp, Qp = h->Qp, TQ = h->TQ, dout = h->dout;
+    const int M = h->M, Mp = h->Mp, Qp = h->Qp, dout = h->dout;
     const size_t nmax = (size_t)std::max<int64_t>(h->n_max, 1);
     double* dRs = h->dThetaMulti;
     double* dUv = dRs + (size_t)Qp * Qp;
@@ -2640,11 +2660,7 @@ static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s) {
     OutMat W{};
     for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
     const double* R = h->dR;
-    if (h->posterior_set) {     // R_v = Uv^T Uv: dUvT holds Uv^T (identity-padded); the pad rows / columns are not read
-        hipLaunchKernelGGL(k_transpose, dim3(TQ, TQ), dim3(256), 0, s, (const double*)h->dUvT, dUv, Qp);
-        launch_gemm(h->dUvT, dUv, dRs, Qp, TQ, s);
-        R = dRs;
-    }
+    if (int rrc = theta_Rv(h, s, &R)) return rrc;
     const int64_t nprep = std::max<int64_t>(h->n, Mp);
     hipLaunchKernelGGL(k_theta_multi_prep, dim3((unsigned)((nprep + 255) / 256)), dim3(256), 0, s, (const double*)h->dYw,
                        (const double*)h->dMu, W, cw, mup, h->n, M, Mp, dout);
@@ -2698,10 +2714,13 @@ static int theta_objective_multi(sgp_handle* h, hipStream_t s, bool fresh, doubl
     return 0;
 }
 
-static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value) {
+static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value, const double** Rv_out) {
     if (int erc = enqueue_restats(h, s)) return erc;
     const int M = h->M, Mp = h->Mp, Q = h->Q, Qp = h->Qp;
-    launch_traces(h, s);
+    const double* Rv = h->dR;
+    if (int rrc = theta_Rv(h, s, &Rv)) return rrc;
+    *Rv_out = Rv;
+    launch_traces(h, s, Rv);
     hipLaunchKernelGGL(k_scalars, dim3(1), dim3(256), 0, s, h->dStats, (const double*)h->dTrace, (int)TRACE_BLOCKS,
                        (const double*)(h->dTrace + TRACE_BLOCKS), (int)TRACE_BLOCKS, h->dMu, h->dKuu, h->dLam, h->dInfo, h->dParams,
                        h->dOut2, h->dWishart, M, Mp, h->dout, Q, Qp, Qp - Q, (int64_t*)nullptr, (int64_t*)nullptr,
@@ -2736,6 +2755,7 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
     const double wscale = fresh ? h->hParams->W[0] / h->stats.w0 : 1.0;
     if (h->dout > 1) return theta_objective_multi(h, s, fresh, value, grad);
     int rc = 0;
+    const double* Rv = nullptr;
     if (fresh) {
         double out[SGP_R_COUNT], sc[SGP_S_COUNT];
         HIPCHK(h, hipMemcpy(out, h->dOut, sizeof out, hipMemcpyDeviceToHost));
@@ -2744,10 +2764,10 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
         *value = 0.5 * h->hParams->W[0] * (out[SGP_R_SUM_I1] + out[SGP_R_SUM_I2] - sc[SGP_S_YY]);
         if (!grad) return 0;
     } else {
-        rc = theta_objective_eval(h, s, value);
+        rc = theta_objective_eval(h, s, value, &Rv);
         if (rc || !grad) return rc;
     }
-    if (int grc = enqueue_theta_grad(h, s)) return grc;
+    if (int grc = enqueue_theta_grad(h, s, Rv)) return grc;
     HIPCHK(h, wait_stream(s));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy(grad, h->dGrad, sizeof(double) * (1 + h->n_ell), hipMemcpyDeviceToHost));

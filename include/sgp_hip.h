@@ -326,7 +326,8 @@ int sgp_wait(sgp_handle* h);
  * point weights omega_p of sgp_set_data, Psi2 = sum_p omega_p k_p k_p', B = sum_p omega_p k_p y_p', s_w = sum_p omega_p:
  *   d_out = 1 (UniSGP): neg_log_backwardmess_fast (helper_functions/derivative_helper.jl:23-39; grad_llh_new! :59-63)
  *       f = w/2 [ sigma2 s_w - tr(Kinv Psi2) + tr(R_v Psi2) ] - w mu_v' B,     q(v) = the last finished sweep's, as the
- *       notebooks use it (experiments/regression_kin40k.ipynb:212-221), w = the last sgp_set_noise;
+ *       notebooks use it (experiments/regression_kin40k.ipynb:212-221) -- or mu_v and Uv'Uv of sgp_set_posterior when that came
+ *       later, in value and gradient alike --, w = the last sgp_set_noise;
  *   d_out = 2..4 (MultiSGP): neg_log_backwardmess_multi (derivative_helper.jl:92-106; grad_llh_multi! :108-115)
  *       f = 1/2 tr(W) (sigma2 s_w - tr(Kinv Psi2)) + 1/2 tr(S Psi2) - sum_de W_de mu^(d)' B_e,   S = sum_ij W_ij R_v^(ij),
  *       with W = the last sgp_set_noise (a mean(q_W) set after the sweep is used), mu_v = [mu^(1); ..] and R_v = Sigma_v +

@@ -113,6 +113,7 @@ struct SweepPlan {
 //   sgp_set_posterior                           drops q(v) (a foreign one; the statistics are untouched)
 //   sgp_theta_objective at another theta/data   drops reuse and q(v); swept_local (the statistics are the NEW theta's)
 //   sgp_train_end                               drops reuse and q(v); swept_local = false (theta moved on the device)
+//   sgp_theta_descend                           drops reuse and q(v); swept_local = false (the statistics are the last EVALUATED theta's)
 //   next_kind (once per record)                 checked, or drops reuse: its sweep ended without K_uu factored / with a wait given up
 struct StatsRecord {
     double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};   // the kernel values they were formed at ...
@@ -2568,7 +2569,9 @@ static double theta_trace_W(const sgp_handle* h) {
 }
 
 // `Rv`: UniSGP's R_v when the caller has formed it already (theta_objective_eval); nullptr: taken from theta_Rv here
-static int enqueue_theta_grad(sgp_handle* h, hipStream_t s, const double* Rv = nullptr) {
+// `one_stream`: both halves on `s` even when it is the library's own stream (sgp_theta_descend: the next step's re-evaluation
+// overwrites what the K_uu half reads, and only stream order stands between them)
+static int enqueue_theta_grad(sgp_handle* h, hipStream_t s, const double* Rv = nullptr, bool one_stream = false) {
     const int Mp = h->Mp, T = h->T;
     if (int arc = alloc_theta_grad(h)) return arc;
     if (!Rv && h->dout == 1)
@@ -2586,7 +2589,7 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s, const double* Rv = n
     // derivatives) and the K_uu half (H = K_uu^-1 Psi2 K_uu^-1 against dK_uu).  On the library's own streams they run side
     // by side -- the K_uu half on the side stream, which idles between two sweeps -- and meet in the finishing kernel through
     // a device word (an event would cost the main stream ~6 us, see sgp_sweep_finish).
-    const bool split = s == h->own;
+    const bool split = s == h->own && !one_stream;
     h->mirror_epoch = -1;                      // (the gradient's hand-offs report into the same status word)
     hipStream_t su = split ? h->side : s;
     if (split)
@@ -2646,7 +2649,8 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s, const double* Rv = n
 // omega W y and the padded mean columns, G = S - tr(W) K_uu^-1 with the column shares of tr(G Psi2), and the fixed-order value.
 // W is the CURRENT mean(q_W) (a sgp_set_noise since the sweep is honoured), passed by value; sigma2 and ell are read from the
 // main stream's mirror, which holds the current values on both paths (fresh: the sweep's, equal to them; re-evaluated: mirrored).
-static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s) {
+// `R`: R_v when the caller has formed it already (sgp_theta_descend: once per call); nullptr: taken from theta_Rv here
+static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s, const double* R = nullptr) {
     if (int arc = alloc_theta_grad(h)) return arc;
     if (!h->dThetaMulti)
         HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dThetaMulti), sizeof(double) * theta_multi_doubles(h)));
@@ -2659,8 +2663,8 @@ static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s) {
     double* part = mup + (size_t)dout * Mp;
     OutMat W{};
     for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
-    const double* R = h->dR;
-    if (int rrc = theta_Rv(h, s, &R)) return rrc;
+    if (!R)
+        if (int rrc = theta_Rv(h, s, &R)) return rrc;
     const int64_t nprep = std::max<int64_t>(h->n, Mp);
     hipLaunchKernelGGL(k_theta_multi_prep, dim3((unsigned)((nprep + 255) / 256)), dim3(256), 0, s, (const double*)h->dYw,
                        (const double*)h->dMu, W, cw, mup, h->n, M, Mp, dout);
@@ -2714,17 +2718,24 @@ static int theta_objective_multi(sgp_handle* h, hipStream_t s, bool fresh, doubl
     return 0;
 }
 
-static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value, const double** Rv_out) {
-    if (int erc = enqueue_restats(h, s)) return erc;
+// UniSGP: the traces against the resident statistics and k_scalars' sums into dOut2 (sum I1, sum I2, the K_uu status), from which
+// the value is finished as 0.5 w (sum I1 + sum I2 - S_YY) -- by the host (theta_objective_eval) or by k_descend_step
+static void enqueue_theta_uni_sums(sgp_handle* h, hipStream_t s, const double* Rv) {
     const int M = h->M, Mp = h->Mp, Q = h->Q, Qp = h->Qp;
-    const double* Rv = h->dR;
-    if (int rrc = theta_Rv(h, s, &Rv)) return rrc;
-    *Rv_out = Rv;
     launch_traces(h, s, Rv);
     hipLaunchKernelGGL(k_scalars, dim3(1), dim3(256), 0, s, h->dStats, (const double*)h->dTrace, (int)TRACE_BLOCKS,
                        (const double*)(h->dTrace + TRACE_BLOCKS), (int)TRACE_BLOCKS, h->dMu, h->dKuu, h->dLam, h->dInfo, h->dParams,
                        h->dOut2, h->dWishart, M, Mp, h->dout, Q, Qp, Qp - Q, (int64_t*)nullptr, (int64_t*)nullptr,
                        (int64_t*)nullptr, (long long*)nullptr, 0LL, (const double*)nullptr, 0, (const double*)nullptr, 0, (double*)nullptr);
+}
+
+static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value, const double** Rv_out) {
+    if (int erc = enqueue_restats(h, s)) return erc;
+    const int Mp = h->Mp;
+    const double* Rv = h->dR;
+    if (int rrc = theta_Rv(h, s, &Rv)) return rrc;
+    *Rv_out = Rv;
+    enqueue_theta_uni_sums(h, s, Rv);
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     double out[SGP_R_COUNT], sc[SGP_S_COUNT];
@@ -2955,6 +2966,115 @@ extern "C" int sgp_train_end(sgp_handle* h, double* theta_raw, int64_t* counts) 
     h->swept_local = false;
     if (theta_raw) for (int i = 0; i <= h->n_ell; ++i) theta_raw[i] = st.theta[i];
     if (counts) { counts[0] = (int64_t)st.steps; counts[1] = (int64_t)st.rejected; }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Device-paced kernel-parameter descent at a held posterior: phase 2 of the pendulum's `PerformInference`
+// (experiments/Pendulum_Wishart_2d.ipynb cell 16: 100 times grad_llh_multi! + Flux.Optimise.update!(AdaMax, theta, grad) with
+// q(x), q(v) and q(W) held), and the same loop for UniSGP.  Per step, all on the library's own stream: the re-evaluation of
+// sgp_theta_objective at theta_k (enqueue_restats: K_uu chain, K_uf, Psi2, B), the value, the gradient with BOTH halves on this
+// stream, and k_descend_step (value out, AdaMax, softplus(theta_k+1) written where the next step's k_prep_xu reads it).  Stream
+// order is the whole ordering argument: step k + 1's re-evaluation overwrites K_uu^-1 and the statistics that step k's gradient
+// reads, and it sits behind that gradient on the same stream.  No device-word wait is enqueued.  The host waits once.
+// ------------------------------------------------------------------------------------------------
+extern "C" int sgp_theta_descend(sgp_handle* h, double* theta_raw, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2,
+                                 double eps, double* opt_state, double* values, int64_t* counts) {
+    if (!h || !theta_raw) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: null argument");
+    if (h->training) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: a device-paced training run is open (sgp_train_end first)");
+    if (n_ell != 1 && n_ell != h->D) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: n_ell must be 1 or D");
+    if (steps < 0) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: steps must be >= 0");
+    if (!(eta > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return fail(h, SGP_ERR_ARG, "sgp_theta_descend: eta > 0 and beta1, beta2 in [0, 1) required");
+    if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: needs a finished sweep or sgp_set_posterior (q(v))");
+    if (!h->have_data || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: data and kernel must be set");
+    if (h->allreduce) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: data-sharded descent is not supported (remove the hook)");
+    const int np = 1 + n_ell;
+    if (opt_state) {
+        // (a power is beta^t, t >= 1: inside (0, 1), or exactly 0 for a beta of 0)
+        const double b[2] = {beta1, beta2};
+        for (int i = 0; i < 2; ++i) {
+            const double pw = opt_state[2 * np + i];
+            if (!(pw < 1.0) || !(pw > 0.0 || (pw == 0.0 && b[i] == 0.0)))
+                return fail(h, SGP_ERR_ARG, "sgp_theta_descend: the running powers of beta in opt_state must lie in (0, 1)");
+        }
+    }
+    if (counts) counts[0] = counts[1] = 0;
+    if (steps == 0) return 0;
+    if (int wrc = sync_checked(h)) return wrc;
+    hipStream_t s = h->own;
+    if (!h->dTrain) {
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
+    }
+    if (int arc = alloc_theta_grad(h)) return arc;
+    DevBuf dvals;
+    HIPCHK(h, dvals.alloc(sizeof(double) * (size_t)steps));
+    std::vector<double> vals((size_t)steps, std::numeric_limits<double>::quiet_NaN());
+    HIPCHK(h, hipMemcpy(dvals.p, vals.data(), sizeof(double) * (size_t)steps, hipMemcpyHostToDevice));
+    TrainState st;
+    memset(&st, 0, sizeof st);
+    for (int i = 0; i < np; ++i) {
+        st.theta[i] = theta_raw[i];
+        if (opt_state) { st.m[i] = opt_state[i]; st.u[i] = opt_state[np + i]; }
+    }
+    st.bp[0] = opt_state ? opt_state[2 * np] : beta1;
+    st.bp[1] = opt_state ? opt_state[2 * np + 1] : beta2;
+    st.eta = eta; st.beta1 = beta1; st.beta2 = beta2; st.eps = eps;
+    HIPCHK(h, hipMemcpy(h->dTrain, &st, sizeof st, hipMemcpyHostToDevice));
+    // noise, E[log w], the prior and the jitter stay what the setters left; sigma2 and the lengthscales come from theta on the device
+    HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
+    h->n_ell = n_ell;
+    h->params_src = h->dTrainParams;
+    h->in_flight = true;
+    const bool multi = h->dout > 1;
+    int rc = 0;
+    hipLaunchKernelGGL(k_train_adamax, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)nullptr, (const double*)nullptr,
+                       h->dTrainParams, h->D, n_ell, 0, (const int*)nullptr, (const Params*)nullptr, (const double*)nullptr);
+    const double* Rv = h->dR;
+    rc = theta_Rv(h, s, &Rv);                                 // R_v: once per call, q(v) is held
+    const double* scal = h->dStats + (size_t)h->Mp * h->Mp + (size_t)h->Mp * h->dout;
+    for (int k = 0; k < steps && !rc; ++k) {
+        h->params_gen++;                                       // theta moved: k_prep_xu mirrors the parameters again
+        rc = enqueue_restats(h, s);
+        if (!rc) {
+            if (multi) rc = enqueue_theta_multi_value(h, s, Rv);
+            else enqueue_theta_uni_sums(h, s, Rv);
+        }
+        if (!rc) rc = enqueue_theta_grad(h, s, Rv, true);
+        if (!rc)
+            hipLaunchKernelGGL(k_descend_step, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)h->dGrad, (const double*)h->dOut2, scal,
+                               (const Params*)h->dParams, (const int*)h->dInfo, (const int*)(h->dInfo + 3), dvals.as<double>(), k,
+                               h->dTrainParams, h->D, n_ell, multi ? 1 : 0);
+    }
+    // whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path
+    const hipError_t werr = wait_stream(s);
+    const hipError_t lerr = hipGetLastError();
+    h->params_src = h->hParams;
+    h->in_flight = false;
+    h->params_gen++;
+    stats_drop(h, STATS_REUSE | STATS_QV);                     // the resident statistics belong to the last evaluated theta
+    h->swept_local = false;
+    if (rc) return rc;
+    HIPCHK(h, werr);
+    HIPCHK(h, lerr);
+    HIPCHK(h, hipMemcpy(&st, h->dTrain, sizeof st, hipMemcpyDeviceToHost));
+    Params P;
+    HIPCHK(h, hipMemcpy(&P, h->dTrainParams, sizeof P, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(vals.data(), dvals.p, sizeof(double) * (size_t)steps, hipMemcpyDeviceToHost));
+    // the handle's kernel is softplus(theta_out), as the device formed it (as after sgp_train_end)
+    h->hParams->sigma2 = P.sigma2;
+    for (int d = 0; d < h->D; ++d) h->hParams->inv_ell[d] = P.inv_ell[d];
+    for (int i = 0; i < np; ++i) {
+        theta_raw[i] = st.theta[i];
+        if (opt_state) { opt_state[i] = st.m[i]; opt_state[np + i] = st.u[i]; }
+    }
+    if (opt_state) { opt_state[2 * np] = st.bp[0]; opt_state[2 * np + 1] = st.bp[1]; }
+    if (values) for (int k = 0; k < steps; ++k) values[k] = vals[(size_t)k];
+    if (counts) { counts[0] = (int64_t)st.steps; counts[1] = st.stop > 0.0 ? (int64_t)st.stop : 0; }
+    if (int src = check_sync_status(h)) return src;
+    if (st.stop != 0.0)
+        return factor_status(h, (int)st.stop, ("sgp_theta_descend, step " + std::to_string((int64_t)st.steps) + ": K_uu").c_str());
     return 0;
 }
 

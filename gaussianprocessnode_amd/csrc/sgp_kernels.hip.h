@@ -3958,9 +3958,34 @@ struct TrainState {
     // (experiments/classification_banana.ipynb cell 9: `shape, rate = params(qw)`)
     double ga, gb;
     double kind;                // 0 Gaussian likelihood with a fixed w (regression), 1 Probit with a Gamma q(w)
+    double stop;                // sgp_theta_descend: 0 running; the K_uu status word (> 0 the failing minor) or -1 (a device-word
+                                // wait gave up) of the step at which the descent stopped.  Latched: later steps change nothing
 };
 
 __device__ __forceinline__ double softplus_dev(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
+
+// The one owner of the optimiser arithmetic (k_train_adamax, k_descend_step).  Flux's AdaMax on the raw parameters with the chain
+// rule through softplus (d softplus = sigmoid): m = b1 m + (1 - b1) g; u = max(b2 u, |g|); theta -= eta / (1 - b1^t) m / (u + eps);
+// `gscale` rescales the gradient (a Probit run's new mean(q_w); 1 otherwise).
+__device__ __forceinline__ void adamax_step(TrainState* __restrict__ st, const double* __restrict__ grad, double gscale, int n_ell) {
+    for (int i = 0; i <= n_ell; ++i) {
+        const double th = st->theta[i];
+        const double g = gscale * grad[i] / (1.0 + exp(-th));
+        const double m = st->beta1 * st->m[i] + (1.0 - st->beta1) * g;
+        const double u = fmax(st->beta2 * st->u[i], fabs(g));
+        st->m[i] = m;
+        st->u[i] = u;
+        st->theta[i] = th - (st->eta / (1.0 - st->bp[0])) * m / (u + st->eps);
+    }
+    st->bp[0] *= st->beta1;
+    st->bp[1] *= st->beta2;
+    st->steps += 1.0;
+}
+// ... and of the map theta -> kernel parameters, written where k_prep_xu reads them
+__device__ __forceinline__ void write_kernel_params(const TrainState* __restrict__ st, Params* __restrict__ src, int D, int n_ell) {
+    src->sigma2 = softplus_dev(st->theta[0]);
+    for (int d = 0; d < D; ++d) src->inv_ell[d] = 1.0 / softplus_dev(st->theta[1 + (n_ell == 1 ? 0 : d)]);
+}
 
 // Classification minibatch (experiments/classification_banana.ipynb cell 7: `f[i] ~ UniSGP(x[i], v, w, theta); y[i] ~ Probit(f[i])`):
 // q(f_i) = the moment-matched product of the UniSGP :out message N(mz_i, 1 / mean(q_w)) (GPnode/UniSGPnode.jl:96-104; mz = k_i' mu_v
@@ -4030,25 +4055,35 @@ __global__ void k_train_adamax(TrainState* __restrict__ st, const double* __rest
             if (probit) { src->W[0] = st->ga / st->gb; src->E_logw = log(st->ga / st->gb); }
             return;
         }
-        if (ok) {
-            for (int i = 0; i <= n_ell; ++i) {
-                const double th = st->theta[i];
-                const double g = gscale * grad[i] / (1.0 + exp(-th));
-                const double m = st->beta1 * st->m[i] + (1.0 - st->beta1) * g;
-                const double u = fmax(st->beta2 * st->u[i], fabs(g));
-                st->m[i] = m;
-                st->u[i] = u;
-                st->theta[i] = th - (st->eta / (1.0 - st->bp[0])) * m / (u + st->eps);
-            }
-            st->bp[0] *= st->beta1;
-            st->bp[1] *= st->beta2;
-            st->steps += 1.0;
-        } else
+        if (ok)
+            adamax_step(st, grad, gscale, n_ell);
+        else
             st->rejected += 1.0;
     }
-    src->sigma2 = softplus_dev(st->theta[0]);
-    for (int d = 0; d < D; ++d) src->inv_ell[d] = 1.0 / softplus_dev(st->theta[1 + (n_ell == 1 ? 0 : d)]);
+    write_kernel_params(st, src, D, n_ell);
     if (probit) { src->W[0] = st->ga / st->gb; src->E_logw = log(st->ga / st->gb); }
+}
+
+// One step of sgp_theta_descend (one wave, lane 0 works): the objective at theta_k and its gradient are in place -- d_out = 1: the
+// value is finished here from k_scalars' sums as the host finishes it in sgp_theta_objective, 0.5 w (sum I1 + sum I2 - S_YY);
+// d_out > 1: k_theta_value_multi left it at grad[GRAD_SLOTS].  A nonzero K_uu status word (`info_kuu`: the failing minor, or a
+// twin-workgroup wait given up) or hand-off status word (`sync_status`) stops the descent: latched in st->stop, and from then on
+// every step leaves theta, the moments, the powers, values[] (NaN from the host) and the kernel parameters as they are.
+// Otherwise values[k] = f(theta_k), the AdaMax step, and softplus(theta_k+1) written where the next step's k_prep_xu reads it.
+__global__ void k_descend_step(TrainState* __restrict__ st, const double* __restrict__ grad, const double* __restrict__ out,
+                               const double* __restrict__ stats_scal, const Params* __restrict__ P, const int* __restrict__ info_kuu,
+                               const int* __restrict__ sync_status, double* __restrict__ values, int k, Params* __restrict__ src,
+                               int D, int n_ell, int multi) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (st->stop != 0.0) return;
+    const int info = *info_kuu, late = *sync_status;
+    if (info != 0 || late != 0) {
+        st->stop = info != 0 ? (double)info : -1.0;
+        return;
+    }
+    values[k] = multi ? grad[GRAD_SLOTS] : 0.5 * P->W[0] * (out[0] + out[1] - stats_scal[0]);   // SGP_R_SUM_I1, _I2, SGP_S_YY
+    adamax_step(st, grad, 1.0, n_ell);
+    write_kernel_params(st, src, D, n_ell);
 }
 
 }  // namespace sgp

@@ -393,6 +393,37 @@ class SGPDevice:
         self._check(self._lib.sgp_train_end(self._h, ptr(th), counts), "sgp_train_end")
         return th, int(counts[0]), int(counts[1])
 
+    def theta_descend(self, theta, steps: int, *, eta: float = 1e-3, beta=(0.9, 0.999), eps: float = 1e-8, state=None):
+        """`steps` AdaMax steps on the raw (pre-softplus) kernel parameters `theta` (sigma2 first) with q(v), data and noise held,
+        paced by the device (sgp_theta_descend): per step the objective of `theta_objective` is re-evaluated at softplus(theta),
+        the host waits once.  `state`: the optimiser state [m | u | beta1^t, beta2^t] of an earlier call (None: zero moments).
+        Returns (theta, values, steps_taken, state) -- values[k] the objective at step k's theta.  Raises LinAlgError naming the
+        minor and the step when K_uu was not positive definite at some theta_k (the handle's kernel is then softplus(theta_k));
+        the exception carries what the call returned: `minor`, `theta`, `values` (NaN from that step on), `steps_taken`, `state`."""
+        th = np.array(theta, dtype=np.float64).reshape(-1)
+        n_ell = th.size - 1
+        steps = int(steps)
+        if state is None:
+            st = np.concatenate([np.zeros(2 * th.size), np.asarray(beta, dtype=np.float64)])
+        else:
+            st = np.array(state, dtype=np.float64).reshape(-1)
+            if st.size != 2 * th.size + 2:
+                raise ValueError(f"theta_descend: state needs 2 (1 + n_ell) + 2 = {2 * th.size + 2} entries, got {st.size}")
+        values = np.empty(max(steps, 0))
+        counts = (C.c_int64 * 2)()
+        rc = self._lib.sgp_theta_descend(self._h, ptr(th), n_ell, steps, float(eta), float(beta[0]), float(beta[1]), float(eps),
+                                         ptr(st), ptr(values), counts)
+        if rc > 0:
+            self._n_ell = n_ell
+            err = np.linalg.LinAlgError(f"theta_descend: K_uu is not positive definite at step {int(counts[0])} "
+                                        f"(leading minor {rc}); theta and the optimiser state are those of that step")
+            err.minor, err.theta, err.values, err.steps_taken, err.state = rc, th, values, int(counts[0]), st
+            raise err
+        self._check(rc, "sgp_theta_descend")
+        if steps > 0:
+            self._n_ell = n_ell
+        return th, values, int(counts[0]), st
+
     def time_kernel(self, which: int, iters: int = 20, stream: int = 0) -> float:
         """Average launch duration (microseconds, HIP events) of the Gram or streaming-SYRK kernel."""
         v = C.c_double()

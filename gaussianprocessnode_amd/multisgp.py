@@ -427,17 +427,14 @@ def rule_theta(q_out, q_in, q_v, q_w, meta: MultiSGPMeta):
 # ------------------------------------------------------------------------------------------------
 # the hyper-parameter objective: neg_log_backwardmess_multi / grad_llh_multi! (helper_functions/derivative_helper.jl:92-115)
 # ------------------------------------------------------------------------------------------------
-def theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta):
-    """Load the objective's inputs on `meta.engine` once and return `evaluate(theta) -> (value, grad)`, value and gradient of
-    neg_log_backwardmess_multi at the raw theta that `meta.kernel` maps (derivative_helper.jl:92-106).
+def load_theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta):
+    """Load the inputs of neg_log_backwardmess_multi on `meta.engine` -- what `theta_objective_multi` evaluates and
+    `train.optimize_theta_multi(device_paced=True)` descends on -- and return (engine, D_in).
 
     The points are meta.method's cubature points of every q_in (a PointMass input is its own point), each node's target
     y_data[i] repeated over its points (the reference passes y_data = mean.(qx)); W = mean(q_w); q(v) is installed with
     `set_posterior` (mu_v and chol(Sigma_v + mu mu').U, factored on the device), so the device forms S = sum_ij W_ij Rv[i][j]
-    and the linear term itself.  K_uu^-1 is taken at meta.jitter (the reference adds 1e-12 I).  Each call of `evaluate` is one
-    `set_kernel` and one `sgp_theta_objective`: value and analytic gradient w.r.t. (sigma2, ell...), then the chain rule
-    through softplus (d softplus / dx = sigmoid) when meta.kernel has softplus_params set.  A kernel callable without
-    `softplus_params` is taken to map theta to (theta[0], theta[1:]) unchanged."""
+    and the linear term itself.  The kernel family is meta.kernel's; the kernel values are the caller's to set."""
     from .device import potrf
     W = _mean_W(q_w)
     d_out = W.shape[0]
@@ -463,6 +460,19 @@ def theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta)
     sign, logdet = np.linalg.slogdet(W)
     eng.set_noise(W, float(logdet))
     eng.set_posterior(mu_v, Uv)
+    return eng, D_in
+
+
+def theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta):
+    """Load the objective's inputs on `meta.engine` once (`load_theta_objective_multi`) and return `evaluate(theta) -> (value,
+    grad)`, value and gradient of neg_log_backwardmess_multi at the raw theta that `meta.kernel` maps
+    (derivative_helper.jl:92-106).
+
+    K_uu^-1 is taken at meta.jitter (the reference adds 1e-12 I).  Each call of `evaluate` is one
+    `set_kernel` and one `sgp_theta_objective`: value and analytic gradient w.r.t. (sigma2, ell...), then the chain rule
+    through softplus (d softplus / dx = sigmoid) when meta.kernel has softplus_params set.  A kernel callable without
+    `softplus_params` is taken to map theta to (theta[0], theta[1:]) unchanged."""
+    eng, D_in = load_theta_objective_multi(y_data, q_ins, q_v, q_w, meta)
     softplus_params = bool(getattr(meta.kernel, "softplus_params", False))
     family = kernel_family(meta.kernel)
 

@@ -31,6 +31,22 @@ class AdaMax:
         x -= delta
         return x
 
+    def get_state(self, x: np.ndarray) -> np.ndarray:
+        """The state kept for the array `x` as sgp_theta_descend lays it out, [m | u | beta1^t, beta2^t] (zero moments and the
+        powers (beta1, beta2) for an array that has taken no step)."""
+        st = self._state.get(id(x))
+        if st is None:
+            return np.concatenate([np.zeros(2 * x.size), np.array(self.beta, dtype=float)])
+        return np.concatenate([np.ravel(st["m"]), np.ravel(st["u"]), np.ravel(st["bp"])]).astype(np.float64)
+
+    def set_state(self, x: np.ndarray, flat) -> None:
+        """Install a state in that layout as the state of `x`: the next `update(x, ...)` continues from it."""
+        flat = np.asarray(flat, dtype=np.float64).reshape(-1)
+        n = x.size
+        if flat.size != 2 * n + 2:
+            raise ValueError(f"AdaMax.set_state: {2 * n + 2} entries expected for {n} parameters, got {flat.size}")
+        self._state[id(x)] = dict(m=flat[:n].reshape(x.shape).copy(), u=flat[n:2 * n].reshape(x.shape).copy(), bp=flat[2 * n:].copy())
+
 
 def sigmoid(x):
     return 1.0 / (1.0 + np.exp(-np.asarray(x, dtype=np.float64)))
@@ -264,17 +280,55 @@ def _perform_inference_classification_device(theta, xtrain, ytrain, Xu, engine, 
     return MvNormalMeanCovariance(mu, Sigma), (a, b), np.asarray(theta)
 
 
-def optimize_theta_multi(theta, y_data, q_ins, q_v, q_w, meta, *, steps: int = 100, optimizer=None, grad_fn=None):
+def _descend(theta, engine, steps, opt):
+    """`steps` device-paced AdaMax steps on `engine` (SGPDevice.theta_descend) with `opt`'s state for `theta` carried in and
+    out; theta is updated in place."""
+    th, _, _, state = engine.theta_descend(theta, steps, eta=opt.eta, beta=opt.beta, eps=opt.eps, state=opt.get_state(theta))
+    theta[...] = th.reshape(theta.shape)
+    opt.set_state(theta, state)
+    return theta
+
+
+def optimize_theta_multi(theta, y_data, q_ins, q_v, q_w, meta, *, steps: int = 100, optimizer=None, grad_fn=None,
+                         device_paced: bool = False):
     """The inner loop of the pendulum's `PerformInference` (experiments/Pendulum_Wishart_2d.ipynb, cell 16): `steps` times
     grad_llh_multi! at the current theta with q(x), q(v) and q(W) held, then Flux.Optimise.update!(AdaMax, theta, grad).
     theta (raw, as meta.kernel maps it) is updated in place and returned.  The objective's inputs go to the device once; each
     step is one set_kernel and one sgp_theta_objective (multisgp.theta_objective_multi).  `grad_fn(theta) -> (value, grad)`
-    replaces the device objective (a host restatement, for comparisons).  The optimiser runs on the host."""
-    from .multisgp import theta_objective_multi
+    replaces the device objective (a host restatement, for comparisons).  The optimiser runs on the host.
+
+    device_paced=True: the same inputs are loaded the same way, then ONE sgp_theta_descend call takes all the steps on the
+    device -- softplus map, objective, gradient and AdaMax -- and the host waits once.  The optimiser's moments for `theta` are
+    read from and written back to `optimizer`, so successive calls continue one optimiser, host-paced or device-paced in any
+    mix.  It needs meta.kernel.softplus_params (the device maps theta through softplus): ValueError otherwise."""
+    from .multisgp import load_theta_objective_multi, theta_objective_multi
     theta = np.asarray(theta, dtype=np.float64)
     opt = optimizer if optimizer is not None else AdaMax()
+    if device_paced:
+        if grad_fn is not None:
+            raise ValueError("optimize_theta_multi: device_paced=True evaluates the device objective; it takes no grad_fn")
+        if not bool(getattr(meta.kernel, "softplus_params", False)):
+            raise ValueError("optimize_theta_multi: device_paced=True maps theta through softplus on the device; "
+                             "meta.kernel must have softplus_params set")
+        from .meta import kernel_family
+        eng, D_in = load_theta_objective_multi(y_data, q_ins, q_v, q_w, meta)
+        if theta.ndim != 1 or theta.size - 1 not in (1, D_in):
+            raise ValueError(f"optimize_theta_multi: theta must be (sigma2, 1 or {D_in} lengthscales), got {theta.size} entries")
+        sigma2, ell = meta.kernel(theta)
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))     # jitter and family of the descent
+        return _descend(theta, eng, int(steps), opt)
     evaluate = grad_fn if grad_fn is not None else theta_objective_multi(y_data, q_ins, q_v, q_w, meta)
     for _ in range(int(steps)):
         _, g = evaluate(theta)
         opt.update(theta, np.asarray(g, dtype=np.float64))
     return theta
+
+
+def optimize_theta(theta, engine, *, steps: int = 100, optimizer=None):
+    """The UniSGP form of the same loop: `steps` device-paced AdaMax steps on neg_log_backwardmess_fast over an `engine`
+    (SGPDevice) that has data, noise, a kernel (its family and jitter are kept; its values are replaced by softplus(theta)) and
+    a swept q(v), all held.  theta (raw, pre-softplus, sigma2 first) is updated in place and returned; `optimizer`'s moments
+    for it are carried in and out as in `optimize_theta_multi`."""
+    theta = np.asarray(theta, dtype=np.float64)
+    opt = optimizer if optimizer is not None else AdaMax()
+    return _descend(theta, engine, int(steps), opt)

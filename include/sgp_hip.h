@@ -378,6 +378,48 @@ int sgp_train_likelihood(sgp_handle* h, int32_t kind, double shape, double rate)
 int sgp_train_get_gamma(sgp_handle* h, double* shape_rate /* 2 */);
 int sgp_train_end(sgp_handle* h, double* theta_raw, int64_t* counts /* 2 */);
 
+/* ---- device-paced kernel-parameter descent at a held posterior ---------------------------------------------------------
+ * Phase 2 of the state-space experiment's `PerformInference` (experiments/Pendulum_Wishart_2d.ipynb cell 16): after
+ * infer(iterations = 10), 100 steps of grad_llh_multi! + Flux.Optimise.update!(AdaMax, theta, grad) with q(x), q(v) and q(W) held --
+ * and the same loop over neg_log_backwardmess_fast for a UniSGP handle.  sgp_train_* cannot express it (it sweeps every step and
+ * is UniSGP only); host-paced it is one sgp_set_kernel + sgp_theta_objective + optimiser update per step, each with its waits.
+ *
+ * theta_raw[1 + n_ell] (in / out): the raw (pre-softplus) parameters, sigma2 first, as in sgp_train_begin.  For k = 0 .. steps - 1,
+ * on the device, the host only enqueueing:
+ *   1. the kernel parameters become softplus(theta_k); family and jitter are those of the last sgp_set_kernel /
+ *      sgp_set_kernel_family;
+ *   2. the K_uu chain and the local statistics (K_uf, Psi2, B) are re-evaluated at theta_k;
+ *   3. the objective sgp_theta_objective documents (d_out = 1: neg_log_backwardmess_fast; d_out = 2..4:
+ *      neg_log_backwardmess_multi) and its gradient are evaluated with the current data, point weights and output covariance sum,
+ *      the current sgp_set_noise, and q(v) of the last finished sweep -- or of sgp_set_posterior when that came later.  All of
+ *      these are held for the whole call; R_v is formed once per call;
+ *   4. values[k] = f(theta_k)   (values: steps entries, may be NULL);
+ *   5. theta_k+1 = AdaMax(theta_k, grad f o sigmoid(theta_k)) with (eta, beta1, beta2, eps), the arithmetic of sgp_train_step.
+ * The call blocks once, at the end.  Everything runs on one stream, in stream order; no device-word wait is enqueued.
+ *
+ * opt_state (2 (1 + n_ell) + 2 doubles, in / out, may be NULL): [m (1 + n_ell) | u (1 + n_ell) | beta1^t, beta2^t], the AdaMax
+ * moments and running powers.  NULL starts from zero moments with the powers (beta1, beta2) and returns no state; a given state is
+ * continued and written back, so that consecutive calls continue one optimiser (the reference creates its Flux.AdaMax() once,
+ * outside the epoch loop).  Powers outside (0, 1) are SGP_ERR_ARG (0 is accepted for a beta of 0).
+ *
+ * A K_uu that is not positive definite at some theta_k stops the descent there: theta, the moments and the powers stay those of
+ * step k bitwise, values[k .. steps - 1] are NaN, the launches already enqueued run but change nothing the caller sees, theta_raw
+ * receives theta_k and the call returns the failing leading minor (> 0).  counts (2, may be NULL): counts[0] = optimiser steps
+ * taken, counts[1] = the failing minor or 0.  A bounded stream hand-off that gave up is SGP_ERR_HIP, as everywhere else.
+ *
+ * Afterwards the handle's kernel is softplus(theta_out), as after sgp_train_end; q(v), data, noise and prior are untouched.  The
+ * resident statistics belong to the last EVALUATED theta, not to q(v)'s sweep: the next sgp_sweep is SGP_SWEEP_FULL and a
+ * following sgp_theta_objective re-evaluates at theta_out.
+ *
+ * SGP_ERR_ARG: null h or theta_raw; n_ell not 1 or D; steps < 0; eta <= 0 or a beta outside [0, 1); no q(v) (no finished sweep
+ * and no sgp_set_posterior); no data or no kernel; an open sgp_train_* run; an installed all-reduce hook, for any d_out
+ * (data-sharded descent is not supported).  steps = 0 returns 0 with nothing changed.
+ * All sums are in a fixed order: two identical calls agree bitwise in theta, values and state. */
+int sgp_theta_descend(sgp_handle* h, double* theta_raw /* 1 + n_ell, in/out */, int32_t n_ell, int32_t steps,
+                      double eta, double beta1, double beta2, double eps,
+                      double* opt_state /* 2 (1 + n_ell) + 2, in/out, may be NULL */,
+                      double* values /* steps, may be NULL */, int64_t* counts /* 2, may be NULL */);
+
 /* ---- building blocks exposed for tests / other callers (host pointers, blocking) ------------
  * K = sigma2 * exp(-0.5 |(a-b)/ell|^2): kernelmatrix(kernel(theta), A, B) of KernelFunctions.jl as called at
  * GPnode/UniSGPnode.jl:102,153; A is D x na, B is D x nb, K is na x nb column-major. */

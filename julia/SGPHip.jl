@@ -502,6 +502,23 @@ function train!(meta::HipSGPMeta, X::Matrix{Float64}, y::Vector{Float64}, θ::Ve
     return θout
 end
 
+# ---- phase 2 of the pendulum's PerformInference (experiments/Pendulum_Wishart_2d.ipynb cell 16) on the device: `steps` times
+# grad_llh_multi! (grad_llh_new! on a UniSGP handle) + Flux.Optimise.update!(AdaMax, θ, grad) at the held q(v), data and noise
+# (sgp_theta_descend).  θ: the raw (pre-softplus) parameters of kernel_gp, updated in place.  `state` = [m | u | β1^t, β2^t]
+# (2 length(θ) + 2 entries) carries the optimiser from call to call, as the notebook's single Flux.AdaMax() does; `nothing` starts
+# from zero moments and returns none.  Returns (θ, values, steps_taken); PosDefException(k) when K_uu failed at some θ_k (θ and
+# `state` are then those of that step).
+function theta_descend!(meta::HipSGPMeta, θ::Vector{Float64}, steps::Integer; η = 1e-3, β = (0.9, 0.999), ϵ = 1e-8,
+                        state::Union{Nothing, Vector{Float64}} = nothing)
+    h = meta.handle
+    state === nothing || length(state) == 2 * length(θ) + 2 || throw(ArgumentError("theta_descend!: state needs 2 length(θ) + 2 entries"))
+    values = fill(NaN, max(steps, 0)); counts = zeros(Int64, 2)
+    check(ccall((:sgp_theta_descend, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Float64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, θ, length(θ) - 1, steps, η, β[1], β[2], ϵ, state === nothing ? C_NULL : state, values, counts), h.ptr)
+    return θ, values, Int(counts[1])
+end
+
 # The classification loop (experiments/classification_banana.ipynb cell 9: `y[i] ~ Probit(f[i])`, q(w) = GammaShapeRate carried
 # over the minibatches, q(v) never reset): labels 0 / 1 in y; returns (θ, shape, rate).  sgp_train_likelihood turns the run
 # opened by sgp_train_begin into this loop -- forward message, Probit moment matching, Gamma update and AdaMax on the device.

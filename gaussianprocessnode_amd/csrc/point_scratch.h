@@ -1,5 +1,6 @@
-// Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad).  Plain C++, no HIP: the
-// layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
+// Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
+// sgp_out_message).  Plain C++, no HIP: the layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp
+// and tools/out_message_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -117,6 +118,26 @@ static inline void layout_in_message_grad(Carver& c, const PointShape& p, InMess
     b->Qc = c.take<double>(ch * 2 * p.Mp);
     b->GradC = c.take<double>(ch * D);
     b->HessC = c.take<double>(ch * D * D);
+}
+
+// sgp_out_message: all points and their d_out means ([d_out][n], what sgp_predict would return for them), one chunk of k_predict's
+// output ([d_out][chunk points]), the cubature weights, node_start, the node sums ([d_out][n_nodes]) and an explicit mu_v (unpadded)
+struct OutMessageScratch {
+    double *Xall, *PointMean, *Wt;  // all points: X, the means, the weights
+    double* MeanC;                  // per chunk: the d_out means, [d_out][nc]
+    int64_t* Start;                 // node_start (n_nodes + 1)
+    double* MeanN;                  // per node: the weighted sums
+    double* Mu;                     // an explicit mu_v
+};
+static inline void layout_out_message(Carver& c, const PointShape& p, size_t mu_count, OutMessageScratch* b) {
+    const size_t n = (size_t)p.n, nn = (size_t)p.n_nodes;
+    b->Xall = c.take<double>(n * p.D);
+    b->PointMean = c.take<double>(n * p.dout);
+    b->Wt = c.take<double>(n);
+    b->MeanC = c.take<double>((size_t)p.chunk * p.dout);
+    b->Start = c.take<int64_t>(nn + 1);
+    b->MeanN = c.take<double>(nn * p.dout);
+    b->Mu = c.take<double>(mu_count);
 }
 
 // sgp_predict: the points, their means and an explicit mu_v (Q entries, unpadded)

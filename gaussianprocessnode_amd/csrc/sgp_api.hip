@@ -2519,6 +2519,63 @@ extern "C" int sgp_in_message_grad(sgp_handle* h, const double* X, int64_t n, co
     return 0;
 }
 
+// The :out messages of many nodes with uncertain inputs (include/sgp_hip.h): the forward counterpart of sgp_in_message.  The mean
+// needs neither factor, so there is no factor_begin / factor_finish and no M-wide panel: per chunk it is sgp_predict's kernel on
+// sgp_predict's parameter mirror (bitwise its values), gathered into the [d_out][n] array of all points; k_out_message_finish runs
+// once behind the last chunk over that array (a node may straddle chunks).  Everything in call scratch; only the parameter mirror
+// dXusK / dParamsK is rewritten, as sgp_predict does.
+extern "C" int sgp_out_message(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes,
+                               const double* weights, const double* mu_v, double* mean, double* point_mean) {
+    if (!h || n < 0 || n_nodes < 0) return fail(h, SGP_ERR_ARG, "sgp_out_message: bad argument");
+    if (n == 0) return 0;
+    if (!X || !node_start) return fail(h, SGP_ERR_ARG, "sgp_out_message: null X or node_start");
+    if (!mean) return fail(h, SGP_ERR_ARG, "sgp_out_message: null mean");
+    if (int rc = refuse_unset(h, "sgp_out_message")) return rc;
+    if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_out_message: no posterior in the handle and mu_v is NULL");
+    if (int rc = refuse_training(h, "sgp_out_message")) return rc;
+    if (n_nodes < 1 || n_nodes > n || node_start[0] != 0 || node_start[n_nodes] != n)
+        return fail(h, SGP_ERR_ARG, "sgp_out_message: node_start must run from 0 to n");
+    for (int64_t t = 0; t < n_nodes; ++t)
+        if (node_start[t + 1] <= node_start[t]) return fail(h, SGP_ERR_ARG, "sgp_out_message: node_start must increase (no empty node)");
+    if (weights)
+        for (int64_t p = 0; p < n; ++p)
+            if (!std::isfinite(weights[p])) return fail(h, SGP_ERR_ARG, "sgp_out_message: weights must be finite");
+    if (int wrc = sync_all(h)) return wrc;
+    hipStream_t s = h->own;
+    const int D = h->D, dout = h->dout;
+    const size_t nn = (size_t)n_nodes;
+    const PointShape shape = point_shape(h, dout, n, n_nodes);
+    const int64_t chunk = shape.chunk;
+    Carver c;
+    OutMessageScratch b;
+    layout_out_message(c, shape, mu_v ? h->Q : 0, &b);
+    if (int crc = carve_call_scratch(h, &c)) return crc;
+    layout_out_message(c, shape, mu_v ? h->Q : 0, &b);
+    HIPCHK(h, hipMemcpy(b.Xall, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Start, node_start, sizeof(int64_t) * (nn + 1), hipMemcpyHostToDevice));
+    if (weights) HIPCHK(h, hipMemcpy(b.Wt, weights, sizeof(double) * n, hipMemcpyHostToDevice));
+    const double* dMu = h->dMu;
+    if (mu_v) {
+        HIPCHK(h, hipMemcpy(b.Mu, mu_v, sizeof(double) * h->Q, hipMemcpyHostToDevice));
+        dMu = b.Mu;
+    }
+    mirror_current_params(h, s);
+    for (int64_t s0 = 0; s0 < n; s0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, n - s0);
+        launch_predict(h, s, h->dXusK, h->dParamsK, b.Xall + (size_t)s0 * D, dMu, b.MeanC, nc);
+        // mean chunk: [d_out][nc] -> points s0 .. of the [d_out][n] array of all points
+        HIPCHK(h, hipMemcpy2DAsync(b.PointMean + s0, sizeof(double) * n, b.MeanC, sizeof(double) * nc, sizeof(double) * nc, dout,
+                                   hipMemcpyDeviceToDevice, s));
+    }
+    hipLaunchKernelGGL(k_out_message_finish, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, s, (const double*)b.PointMean,
+                       weights ? (const double*)b.Wt : (const double*)nullptr, (const int64_t*)b.Start, b.MeanN, n, n_nodes, dout);
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpy(mean, b.MeanN, sizeof(double) * nn * dout, hipMemcpyDeviceToHost));
+    if (point_mean) HIPCHK(h, hipMemcpy(point_mean, b.PointMean, sizeof(double) * n * dout, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // F(theta) = -sum_n [ -w/2 k_nn + w/2 |L^-1 k_n|^2 - w/2 |Uv k_n|^2 + w y_n mu_v'k_n ]  (derivative_helper.jl:23-39)
 //          = w/2 [ s_kk - tr(Kuu^-1 Psi2) + tr(R Psi2) ] - w b'mu_v
 // evaluated at the CURRENT kernel parameters with q(v) (mu_v, R = Sigma_v + mu mu') held fixed at the last finished

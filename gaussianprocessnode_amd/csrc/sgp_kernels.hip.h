@@ -3296,6 +3296,30 @@ __global__ void __launch_bounds__(256) k_in_moments(const double* __restrict__ l
 }
 
 // ------------------------------------------------------------------------------------------------
+// Output messages (sgp_out_message): mean[t, d] = sum_{p in node t} w_p pm[p, d], the weighted node sums of k_predict's per-point
+// means -- Psi1' mu_v^(d) of @rule MultiSGP(:out), GPnode/MultiSGPnode.jl:90-120, with Psi1 = sum_s w_s k(Xu, x_s).
+// pm: [d_out][N] (all points of the call), w: N weights or null (every weight 1: fma(1, x, acc) is acc + x, so null and explicit
+// ones give the same bits), mean: [d_out][n_nodes].  One wavefront per node (four nodes per workgroup), as k_in_moments: lane l
+// sums the points l, l + 64, .. of its node in order, the 64 partial sums meet in an xor butterfly -- every lane ends with the same
+// bits, whatever the chunking that produced pm.  No atomics.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_out_message_finish(const double* __restrict__ pm, const double* __restrict__ w,
+                                                            const int64_t* __restrict__ node_start, double* __restrict__ mean,
+                                                            int64_t N, int64_t n_nodes, int dout) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t t = (int64_t)blockIdx.x * 4 + wave;
+    const bool live = t < n_nodes;
+    const int64_t s0 = live ? node_start[t] : 0, s1 = live ? node_start[t + 1] : 0;
+    for (int d = 0; d < dout; ++d) {
+        const double* col = pm + (size_t)d * N;
+        double acc = 0.0;
+        for (int64_t s = s0 + lane; s < s1; s += 64) acc = fma(w ? w[s] : 1.0, col[s], acc);
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (live && lane == 0) mean[(size_t)d * n_nodes + t] = acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Input-message gradients and Hessians (sgp_in_message_grad): the Laplace form of @rule MultiSGP(:in), GPnode/MultiSGPnode.jl:210-236,
 // differentiates the closure above with ForwardDiff / Zygote; here analytically.  With k = K(Xu, x), A = tr(W) K_uu^-1 - S:
 //   logpdf = -1/2 tr(W) sigma2 + s_t' k + 1/2 k' A k,   q = s_t + A k,   grad = J' q,   hess = J' A J + sum_m q_m grad^2 k_m,

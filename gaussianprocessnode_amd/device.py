@@ -329,6 +329,25 @@ class SGPDevice:
                     "sgp_in_message_grad")
         return logpdf, grad, hess
 
+    def out_message(self, X, node_start, weights=None, mu_v=None, want_points: bool = False):
+        """The :out message means of many nodes in one call (sgp_out_message), at the current kernel.  X (n, D): the points of all
+        nodes; node t owns X[node_start[t]:node_start[t + 1]]; weights (n,): the cubature weights (None: every weight 1); mu_v: the
+        one given or (None) the handle's current posterior mean.  Returns mean (n_nodes, d_out), mean[t, d] = sum_p w_p k_p'
+        mu_v^(d) over node t's points -- or (mean, point_mean (n, d_out)) with `want_points`, point_mean bitwise `predict(X, mu_v)`."""
+        Xs = as_f64(np.reshape(X, (-1, self.D)))
+        n = Xs.shape[0]
+        start = np.ascontiguousarray(np.asarray(node_start, dtype=np.int64).reshape(-1))
+        n_nodes = start.size - 1
+        if n_nodes < 0:
+            raise ValueError("out_message: node_start needs n_nodes + 1 entries")
+        w = None if weights is None else as_f64(np.reshape(weights, (n,)))
+        mu = None if mu_v is None else as_f64(np.reshape(mu_v, (self.Q,)))
+        mean = np.empty((self.d_out, n_nodes))
+        points = np.empty((self.d_out, n)) if want_points else None
+        self._check(self._lib.sgp_out_message(self._h, ptr(Xs), n, start.ctypes.data_as(C.POINTER(C.c_int64)), n_nodes, ptr(w),
+                                              ptr(mu), ptr(mean), ptr(points)), "sgp_out_message")
+        return (mean.T.copy(), points.T.copy()) if want_points else mean.T.copy()
+
     def set_posterior(self, mu_v, Uv):
         """Install an external q(v) (mean and Uv = chol(Sigma_v + mu mu').U) for the per-point outputs (`w_stats`)."""
         mu = as_f64(np.reshape(mu_v, (self.Q,)))

@@ -133,6 +133,32 @@ def rule_out(q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta) -> MvNormal
     return MvNormalMeanPrecision(w @ f, W)
 
 
+def rule_out_batch(q_ins, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta):
+    """`rule_out(q_ins[t], q_v, q_w, q_theta, meta)` for every t in ONE device call (GPnode/MultiSGPnode.jl:90-120): the forward
+    messages a GP-SSM needs from all its time steps in every VMP iteration.  A PointMass input is one point of weight 1, a
+    Gaussian one meta.method's cubature points; all of them go to `SGPDevice.out_message` with the explicit mean(q_v), and the
+    device returns the node sums Psi1' mu_v^(d).  Returns a list of MvNormalMeanPrecision(mean_t, mean(q_w)).  The values are
+    those of the `rule_out` loop up to the order of the node sums (the device's lanes and tree against the host's dot product)."""
+    q_ins = list(q_ins)
+    if not q_ins:
+        return []
+    W = _mean_W(q_w)
+    pts, wts = [], []
+    for q_in in q_ins:
+        if isinstance(q_in, PointMass):
+            p, w = np.atleast_2d(np.asarray(q_in.mean(), dtype=np.float64)), np.ones(1)
+        else:
+            p, w = meta.method.points_weights(*q_in.mean_cov())
+        pts.append(np.asarray(p, dtype=np.float64).reshape(len(w), -1))
+        wts.append(np.asarray(w, dtype=np.float64))
+    start = np.concatenate([[0], np.cumsum([len(w) for w in wts])]).astype(np.int64)
+    eng = _engine(meta, 1, W.shape[0])
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    mean = eng.out_message(np.concatenate(pts), start, np.concatenate(wts), np.asarray(q_v.mean(), dtype=np.float64))
+    return [MvNormalMeanPrecision(mean[t].copy(), W) for t in range(len(q_ins))]
+
+
 def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, noise: bool = True):
     """Predictive means and covariances of the d_out latent outputs (noise=False) or of the observation (noise=True: +
     mean(q_w)^-1) at kernel(q_theta) and the explicit q_v (sgp_predict_var).  Test inputs (ns, D) give means (ns, d_out) and

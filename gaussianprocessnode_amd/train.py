@@ -332,3 +332,153 @@ def optimize_theta(theta, engine, *, steps: int = 100, optimizer=None):
     theta = np.asarray(theta, dtype=np.float64)
     opt = optimizer if optimizer is not None else AdaMax()
     return _descend(theta, engine, int(steps), opt)
+
+
+# ------------------------------------------------------------------------------------------------
+# the GP state-space model: `pendulum_GP` of experiments/Pendulum_Wishart_2d.ipynb (cells 12-16)
+# ------------------------------------------------------------------------------------------------
+def wishart_mean_logdet(nu: float, invscale) -> float:
+    """E[logdet W] of WishartFast(nu, invscale): sum_i digamma((nu + 1 - i) / 2) + d log 2 - logdet(invscale)."""
+    from scipy.special import digamma
+    invscale = np.atleast_2d(np.asarray(invscale, dtype=np.float64))
+    d = invscale.shape[0]
+    return float(sum(digamma(0.5 * (nu - i)) for i in range(d)) + d * np.log(2.0) - np.linalg.slogdet(invscale)[1])
+
+
+def _gauss_kl(m, S, m0, S0) -> float:
+    """KL(N(m, S) || N(m0, S0))."""
+    d = len(m)
+    S0inv = np.linalg.inv(S0)
+    dm = m - m0
+    return float(0.5 * (np.trace(S0inv @ S) + dm @ S0inv @ dm - d + np.linalg.slogdet(S0)[1] - np.linalg.slogdet(S)[1]))
+
+
+def _wishart_kl(nu, invS, nu0, invS0) -> float:
+    """KL(Wishart(nu, invS^-1) || Wishart(nu0, invS0^-1)), both given by their inverse scales."""
+    from scipy.special import multigammaln
+    d = invS.shape[0]
+    V = np.linalg.inv(invS)
+    return float(0.5 * nu0 * (np.linalg.slogdet(invS)[1] - np.linalg.slogdet(invS0)[1]) + 0.5 * nu * (np.trace(invS0 @ V) - d)
+                 + multigammaln(0.5 * nu0, d) - multigammaln(0.5 * nu, d)
+                 + 0.5 * (nu - nu0) * (wishart_mean_logdet(nu, invS) - d * np.log(2.0) + np.linalg.slogdet(invS)[1]))
+
+
+def gpssm_host_energy(y, Pobs, q_x, q_v, q_w, x0_prior, v_prior_var, w_prior) -> float:
+    """The host's share of the GP-SSM free energy: the observation factors' average energies, KL(q(x_0) || prior), minus the
+    entropies of q(x_1..T), KL(q(v) || N(0, v_prior_var I)) and KL(q(W) || prior).  The MultiSGP factors' average energies
+    (`multisgp.average_energy_summed`) complete it."""
+    y = np.asarray(y, dtype=np.float64)
+    d = y.shape[1]
+    Pinv = np.linalg.inv(Pobs)
+    ldP = float(np.linalg.slogdet(Pobs)[1])
+    total = _gauss_kl(q_x[0].m, q_x[0].S, np.asarray(x0_prior[0], dtype=np.float64), np.asarray(x0_prior[1], dtype=np.float64))
+    for t in range(1, len(q_x)):
+        r = y[t - 1] - q_x[t].m
+        total += 0.5 * (d * np.log(2.0 * np.pi) + ldP + r @ Pinv @ r + np.trace(Pinv @ q_x[t].S))
+        total -= 0.5 * (d * (1.0 + np.log(2.0 * np.pi)) + np.linalg.slogdet(q_x[t].S)[1])
+    mu, Sig = q_v.mean_cov()
+    Q = len(mu)
+    total += 0.5 * ((np.trace(Sig) + mu @ mu) / v_prior_var - Q + Q * np.log(v_prior_var) - np.linalg.slogdet(Sig)[1])
+    total += _wishart_kl(q_w.nu, q_w.invS, float(w_prior[0]), np.asarray(w_prior[1], dtype=np.float64))
+    return float(total)
+
+
+def gpssm_initial_marginals(T: int, d: int, Q: int, x0_prior, v_prior_var: float, w_prior):
+    """The notebook's `@initialization` (cell 14): q(x_t) = N(0, 50 I) for t = 1..T, q(v) = N(0, v_prior_var I), q(W) = the prior.
+    x_prev (x_0) is not named there: q(x_0) starts at its prior."""
+    from .distributions import WishartFast
+    q_x = [MvNormalMeanCovariance(np.array(x0_prior[0], dtype=np.float64), np.array(x0_prior[1], dtype=np.float64))]
+    q_x += [MvNormalMeanCovariance(np.zeros(d), 50.0 * np.eye(d)) for _ in range(T)]
+    return q_x, MvNormalMeanCovariance(np.zeros(Q), v_prior_var * np.eye(Q)), WishartFast(float(w_prior[0]), np.array(w_prior[1], dtype=np.float64))
+
+
+def _proper_gaussian(q, floor: float = 1e-10):
+    """q itself when cov(q) has a Cholesky factor; otherwise the same mean with the covariance's eigenvalues raised to
+    floor * max(1, largest).  A moment-matched covariance whose closure values single out one cubature point is singular to
+    rounding, and the next step takes its cubature points through a Cholesky factor; ReactiveMP factors such a matrix with a
+    forced-positive Cholesky (`cholsqrt`), which has the same purpose and not the same values."""
+    try:
+        np.linalg.cholesky(q.S)
+        return q
+    except np.linalg.LinAlgError:
+        w, V = np.linalg.eigh(0.5 * (q.S + q.S.T))
+        w = np.maximum(w, floor * max(1.0, float(w[-1])))
+        return MvNormalMeanCovariance(q.m, (V * w) @ V.T)
+
+
+def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, iterations=10, init=None, free_energy=False,
+              rule_out_fn=None):
+    """The inner `infer(...)` of the pendulum GP-SSM (experiments/Pendulum_Wishart_2d.ipynb cells 12-16):
+        x_0 ~ N(m0, P0);   x_t ~ MultiSGP(x_{t-1}, v, W, theta);   y_t ~ N(x_t, P),   t = 1..T,
+        v ~ N(0, v_prior_var I),   W ~ Wishart(nu0, invscale^-1),   mean field q(x_0) .. q(x_T) q(v) q(W).
+    theta is raw, as meta.kernel maps it; y is (T, d); x0_prior = (m0, P0); w_prior = (nu0, inverse scale), default (100, I).
+    The marginals start at the notebook's `@initialization` (`gpssm_initial_marginals`), or at init = (q_x, q_v, q_W).
+
+    Every iteration is a fixed Jacobi schedule: each step's messages are computed from the marginals the previous step left.
+      1. the forward messages out_t = MultiSGP(:out) at q(x_{t-1}), t = 1..T: `multisgp.rule_out_batch`, ONE device call;
+      2. left_t = out_t x N(y_t, P) for t >= 1 (a d x d Gaussian product on the host), left_0 = N(m0, P0);
+      3. q(x_t), t = 0..T-1 = left_t x the :in message of node t + 1, whose closure uses q_out = q(x_{t+1}) of the previous
+         iteration: `multisgp.marginal_in_batch`, ONE device call (with the reference's NaN fallback; a covariance that is singular to
+         rounding has its eigenvalues floored, `_proper_gaussian`); q(x_T) = left_T;
+      4. q(v): `multisgp.sweep` over all nodes with the new q(x), one sweep;
+      5. q(W) = Wishart(nu0 + T, prior + sum_t (I1_t + I2_t)): `multisgp.rule_w_summed`.
+    free_energy: after step 4, at (new q(x), new q(v), the q(W) of steps 1-4), the free energy is the MultiSGP factors' average
+    energies from the sweep (`multisgp.average_energy_summed`) plus the Gaussian and Wishart terms of `gpssm_host_energy`.
+    What stays on the host per iteration: the cubature points of 2 T Gaussians, T products of d x d Gaussians, the NaN test.
+
+    This is a schedule of the same messages; ReactiveMP's reactive update order is NOT claimed to be reproduced, and no fixture
+    pins it: the notebook's data come from Julia's MersenneTwister(124), so its q(x) cannot be regenerated here.
+
+    rule_out_fn(q_ins, q_v, q_w, q_theta, meta) replaces step 1's batch function (timing comparisons against the per-node loop).
+    Returns (q_x [T + 1], q_v, q_W, free energies [iterations] or [])."""
+    from . import multisgp as MS
+    from .distributions import MvNormalWeightedMeanPrecision, PointMass
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 2:
+        raise ValueError("vmp_gpssm: y must be (T, d)")
+    T, d = y.shape
+    Pobs = np.asarray(P, dtype=np.float64).reshape(d, d)
+    Pinv = np.linalg.inv(Pobs)
+    m0, P0 = np.asarray(x0_prior[0], dtype=np.float64), np.asarray(x0_prior[1], dtype=np.float64)
+    w_prior = (100.0, np.eye(d)) if w_prior is None else (float(w_prior[0]), np.asarray(w_prior[1], dtype=np.float64))
+    Q = d * np.asarray(meta.Xu).shape[0]
+    q_theta = PointMass(np.asarray(theta, dtype=np.float64))
+    q_x, q_v, q_w = init if init is not None else gpssm_initial_marginals(T, d, Q, (m0, P0), v_prior_var, w_prior)
+    q_x = list(q_x)
+    v_prior = MvNormalWeightedMeanPrecision(np.zeros(Q), np.eye(Q) / v_prior_var)
+    rule_out_fn = rule_out_fn or MS.rule_out_batch
+    fe = []
+    for _ in range(int(iterations)):
+        W = q_w.mean()
+        outs = rule_out_fn(q_x[:-1], q_v, q_w, q_theta, meta)                                   # 1
+        S = np.linalg.inv(W + Pinv)                                                             # 2 (every out_t carries precision W)
+        S = 0.5 * (S + S.T)
+        lefts = [MvNormalMeanCovariance(m0, P0)] + [MvNormalMeanCovariance(S @ (W @ outs[t].m + Pinv @ y[t]), S) for t in range(T)]
+        q_x = [_proper_gaussian(q) for q in MS.marginal_in_batch(q_x[1:], lefts[:-1], q_v, q_w, q_theta, meta)] + [lefts[-1]]  # 3
+        q_v = MS.sweep(meta, q_x[1:], q_x[:-1], q_w, q_theta, v_prior, E_logdet_W=wishart_mean_logdet(q_w.nu, q_w.invS))   # 4
+        if free_energy:
+            fe.append(MS.average_energy_summed(meta) + gpssm_host_energy(y, Pobs, q_x, q_v, q_w, (m0, P0), v_prior_var, w_prior))
+        q_w = MS.rule_w_summed(meta, w_prior[0], w_prior[1], T)                                 # 5
+    return q_x, q_v, q_w, fe
+
+
+def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iterations=10, theta_steps=100, device_paced=True,
+                            v_prior_var=50.0, w_prior=None, optimizer=None, free_energy=True):
+    """`PerformInference` of experiments/Pendulum_Wishart_2d.ipynb cell 16.  Per epoch: `vmp_gpssm` from the initialisation at
+    the current theta (step 1), then `optimize_theta_multi` -- theta_steps AdaMax steps on neg_log_backwardmess_multi -- at the held
+    q(x), q(v), q(W), with the targets mean(q(x_t)) and the inputs q(x_{t-1}), t = 1..T, as the notebook passes them (step 2).
+    One optimiser is carried across the epochs (the notebook creates its Flux.AdaMax() once): `optimizer`, or a fresh AdaMax;
+    device_paced passes its state through sgp_theta_descend's opt_state.  theta (raw) is updated in place.
+    Returns (theta, free energies [epochs] (the last iteration's of every epoch, or []), (q_x, q_v, q_W) of the last epoch)."""
+    theta = np.array(theta, dtype=np.float64)
+    opt = optimizer if optimizer is not None else AdaMax()
+    fe_values, post = [], None
+    for _ in range(int(epochs)):
+        q_x, q_v, q_w, fe = vmp_gpssm(theta, y, meta, P=P, x0_prior=x0_prior, v_prior_var=v_prior_var, w_prior=w_prior,
+                                      iterations=vmp_iterations, free_energy=free_energy)
+        if fe:
+            fe_values.append(fe[-1])
+        y_data = np.stack([q.m for q in q_x[1:]])
+        optimize_theta_multi(theta, y_data, q_x[:-1], q_v, q_w, meta, steps=theta_steps, optimizer=opt, device_paced=device_paced)
+        post = (q_x, q_v, q_w)
+    return theta, fe_values, post

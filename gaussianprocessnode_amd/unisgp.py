@@ -301,6 +301,31 @@ def rule_out(q_in, q_v, q_w, q_theta, meta: UniSGPMeta) -> NormalMeanPrecision:
     return NormalMeanPrecision(float(m), _mean_w(q_w))
 
 
+def rule_out_batch(q_ins, q_v, q_w, q_theta, meta: UniSGPMeta):
+    """`rule_out(q_ins[t], q_v, q_w, q_theta, meta)` for every t in ONE device call (`SGPDevice.out_message`): a PointMass input
+    is one point of weight 1, a Gaussian one meta.method's cubature points (GPnode/UniSGPnode.jl:85-93).  Returns a list of
+    NormalMeanPrecision(mean_t, mean(q_w)); the values are those of the `rule_out` loop up to the order of the node sums."""
+    q_ins = list(q_ins)
+    if not q_ins:
+        return []
+    D = np.asarray(meta.Xu).shape[1]
+    pts, wts = [], []
+    for q_in in q_ins:
+        if _is_pointmass(q_in):
+            p, w = np.asarray(q_in.mean(), dtype=np.float64).reshape(1, D), np.ones(1)
+        else:
+            p, w = meta.method.points_weights(q_in.mean(), q_in.var())
+        pts.append(np.asarray(p, dtype=np.float64).reshape(len(w), D))
+        wts.append(np.asarray(w, dtype=np.float64))
+    start = np.concatenate([[0], np.cumsum([len(w) for w in wts])]).astype(np.int64)
+    eng = _engine(meta, 1)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    mean = eng.out_message(np.concatenate(pts), start, np.concatenate(wts), np.asarray(q_v.mean(), dtype=np.float64))
+    w_bar = _mean_w(q_w)
+    return [NormalMeanPrecision(float(mean[t, 0]), w_bar) for t in range(len(q_ins))]
+
+
 def predict(Xstar, q_v, q_theta, meta: UniSGPMeta) -> np.ndarray:
     """Batched `@call_rule UniSGP(:out)` (the 30 000-call loop of experiments/regression_kin40k.ipynb:288-304)."""
     Xstar = np.asarray(Xstar, dtype=np.float64)

@@ -158,7 +158,7 @@ int sgp_sweep(sgp_handle* h, void* stream);                 /* local + [all-redu
  *                      all-reduce hook: ONE call, of the exchange buffer's tail [B | scalars], count = Mp d_out + SGP_S_COUNT +
  *                      d_out^2 on every rank), then phase 2;
  *   SGP_SWEEP_REUSED   otherwise (sgp_set_noise, sgp_set_prior, sgp_carry_posterior, sgp_set_posterior, sgp_w_stats, sgp_predict,
- *                      sgp_predict_var, sgp_in_message):
+ *                      sgp_predict_var, sgp_in_message, sgp_out_message):
  *                      phase 2 alone over the resident statistics; no K_uu chain, no hook call.
  * The results of TARGETS and REUSED sweeps are bitwise those of a full sweep.  sgp_sweep_local / sgp_sweep_finish keep their
  * meaning (a full local phase, phase 2).
@@ -313,6 +313,28 @@ int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const int64_t* nod
  * that differ in the chunk size. */
 int sgp_in_message_grad(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes, const double* y_mean,
                         const double* mu_v, const double* Sigma_v, double* logpdf, double* grad, double* hess);
+
+/* sgp_out_message: the :out messages of many nodes with uncertain inputs in one call -- @rule MultiSGP(:out)
+ * (GPnode/MultiSGPnode.jl:90-120) / UniSGP(:out) with a Gaussian input (GPnode/UniSGPnode.jl:85-93): the mean Psi1' mu_v^(d) with
+ * Psi1 = sum_s omega_s k(Xu, x_s) over the node's cubature points (approximate_kernel_expectation!).  X is D x n and node t owns the
+ * points [node_start[t], node_start[t + 1]) as in sgp_in_message (n_nodes + 1 entries, 0 = node_start[0] < ... < node_start[n_nodes]
+ * = n); weights are the n cubature weights omega (NULL: every weight 1); mu_v (host, d_out*M, output-major) or NULL for the handle's
+ * current posterior, exactly as sgp_predict resolves it.  With k_p = K(Xu, x_p) at the CURRENT kernel (the last sgp_set_kernel, its
+ * family):
+ *     point_mean[p, d] = k_p' mu_v^(d)                              (n x d_out column-major, may be NULL; bitwise what sgp_predict
+ *                                                                    returns for the same X and mu_v)
+ *     mean[t, d]       = sum_{p in node t} omega_p point_mean[p, d]   (n_nodes x d_out column-major, required)
+ * The precision the rule attaches, mean(q_W), is the caller's and takes no part.
+ * A linear functional needs no positive weights: any finite weight is accepted -- negative, zero, a node whose weights sum to 0.
+ * SGP_ERR_ARG: node_start not as above (an empty node included), a non-finite weight, a null mean, everything sgp_predict refuses
+ * (no inducing inputs or kernel, NULL mu_v without a posterior in the handle), an open sgp_train_* run.  n = 0 returns 0, nothing
+ * done.  The call factorises nothing: it never returns k > 0.
+ * Blocking.  The points go through sgp_predict's kernel in chunks (SGP_PREDICT_CHUNK) in call scratch, and nothing the sweep keeps is
+ * written (sgp_sweep_kind and the theta objective are unaffected).  The node sums run behind the last chunk over the points of all
+ * chunks (a node may straddle chunks), one wavefront per node: lane l sums the points l, l + 64, .. of its node in order, the 64
+ * partial sums meet in a fixed tree, no atomics.  Repeated calls agree bitwise, and so do calls that differ in the chunk size. */
+int sgp_out_message(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes, const double* weights,
+                    const double* mu_v, double* mean, double* point_mean);
 
 /* sgp_wait: returns when everything this handle has enqueued -- on its own streams or the caller's -- has finished: what a caller
  * does between `infer` calls when it wants the sweep to be over but none of its results yet.  The library's streams are polled

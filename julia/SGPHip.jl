@@ -197,6 +197,23 @@ function in_message_grad(h::Handle, X::Matrix{Float64}, node_start::Vector{Int64
     return logpdf, grad, hess
 end
 
+# the :out message means of many nodes in one call (include/sgp_hip.h, sgp_out_message): X is D × n, node t owns the columns
+# node_start[t] + 1 : node_start[t + 1] (0-based offsets, n_nodes + 1 entries); weights === nothing: every weight 1; μ_v === nothing:
+# the handle's current posterior mean.  Returns mean n_nodes × d_out, or (mean, point_mean n × d_out) with points = true.  Written
+# blind like the rest of this file, never executed: only the ccall signature is stated here, no rule dispatches on it yet
+# (gaussianprocessnode_amd/multisgp.py, rule_out_batch, is the tested host function).
+function out_message!(h::Handle, X::Matrix{Float64}, node_start::Vector{Int64}, weights = nothing, μ_v = nothing; points = false)
+    n = size(X, 2); n_nodes = length(node_start) - 1
+    mean = zeros(n_nodes, h.d_out)
+    point_mean = points ? zeros(n, h.d_out) : nothing
+    μp = μ_v === nothing ? C_NULL : Vector{Float64}(μ_v)
+    check(ccall((:sgp_out_message, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, X, n, node_start, n_nodes, weights === nothing ? C_NULL : Vector{Float64}(weights), μp, mean,
+                points ? point_mean : C_NULL), h.ptr)
+    return points ? (mean, point_mean) : mean
+end
+
 # q(v) installed from outside for the per-point outputs (include/sgp_hip.h, sgp_set_posterior): mean and the upper factor
 # Uv = chol(Σ_v + μ μ').U, column-major Q × Q -- a Julia Matrix as it is
 set_posterior!(h::Handle, μ_v::Vector{Float64}, Uv::Matrix{Float64}) =

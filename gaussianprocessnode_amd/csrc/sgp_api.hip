@@ -1277,7 +1277,7 @@ static void enqueue_local(sgp_handle* h, hipStream_t s, bool pack) {
     hipLaunchKernelGGL(k_assemble, dim3(T, T + 1, assemble_z(ga)), dim3(256), 0, s, h->dSlabs, h->dBpart, h->dDataScal,
                        pack ? h->dPack : h->dStats, Mp, T, ga, h->n > 0 ? h->nblk : 0, h->dout,
                        SGP_S_COUNT + h->dout * h->dout, 1, h->dStamps + STAMP_STRIDE * SGP_T_LOCAL, h->dInfo + 1, (long long*)nullptr, 0LL,
-                       pack ? 1 : 0, h->dBred);
+                       pack ? 1 : 0, h->dBred, h->has_omega ? 1 : 0);
 }
 
 // The statistics of an overlapped sweep (see plan_overlap): the same kernels, the SYRK and the assembly once per tile-row group.
@@ -1320,7 +1320,7 @@ static int enqueue_stats_overlapped(sgp_handle* h, const SweepPlan& p) {
                            h->dDataScal, sharded ? h->dPack : h->dStats, Mp, T, G.geom, h->nblk, h->dout,
                            SGP_S_COUNT + h->dout * h->dout, g == 0 ? 1 : 0, h->dStamps + STAMP_STRIDE * SGP_T_LOCAL,
                            g == 0 ? h->dInfo + 1 : (int*)nullptr, g == 0 ? h->dJoin + WORD_ASM0 : (long long*)nullptr, h->stat_epoch,
-                           sharded ? 1 : 0, h->dBred);
+                           sharded ? 1 : 0, h->dBred, h->has_omega ? 1 : 0);
         if (sharded) {
             if (int xrc = exchange_stats(h, s, G.geom.tile0, G.geom.ntiles, g == 0)) return xrc;
             if (G.masked && hipEventRecord(h->evGroup[g], s) != hipSuccess) return fail(h, SGP_ERR_HIP, "hipEventRecord failed (statistics group)");

@@ -938,7 +938,7 @@ __global__ void __launch_bounds__(256) k_assemble(const double* __restrict__ sla
                                                   int Mp, int T, SyrkGeom g, int nblk, int d_out,
                                                   int nscal, int do_b, int64_t* stamps, int* __restrict__ info_reset,
                                                   long long* start_word, long long start_value, int packed,
-                                                  double* __restrict__ bscratch) {
+                                                  double* __restrict__ bscratch, int sym_diag) {
     // grid (rows, T + do_b, 4 or 16): blocks (x, y < T, z) sum rows [64 z / grid.z, ...) of the slab tile (I, J) = (row_lo + x, y),
     // I >= J -- four entries per thread and 48 loads in flight (grid.z = 4: few chunks) or one entry per thread (grid.z = 16: many
     // chunks), see below -- and write both mirror images.
@@ -947,6 +947,10 @@ __global__ void __launch_bounds__(256) k_assemble(const double* __restrict__ sla
     // packed (data-sharded sweeps): `stats` is the exchange buffer [lower tiles, row-major triangle, 64 x 64 column-major each |
     // B | scalars] -- what the ranks sum-all-reduce (1.18 MB at M = 512 instead of the 2.10 MB of the full symmetric matrix);
     // k_unpack_stats expands the reduced buffer into the layout the rest of the sweep reads.
+    // sym_diag (weighted points): the SYRK forms entry (i, j) of a DIAGONAL tile as sum_n K_i (omega K_j) and (j, i) as sum_n K_j
+    // (omega K_i), which round differently; of such a tile only the threads on and below the diagonal then store, each to (i, j) and
+    // to (j, i), so that Psi2 is exactly symmetric.  The loads and sums are the same either way; without weights the two entries are
+    // the same products and the stores stay as they are.
     // NO LDS on purpose: in the overlapped sweep this kernel runs while the NEXT group's SYRK already holds every byte of LDS on
     // its CUs; a block that needs none fits beside those workgroups.  (Adjacent LANES down a column -- 32-byte runs both ways -- made
     // the loads irregular across the wave and the kernel twice as slow in round 3, 15 instead of 7.7 us; the layout below keeps the
@@ -990,7 +994,15 @@ __global__ void __launch_bounds__(256) k_assemble(const double* __restrict__ sla
             for (int u = 0; u < 4; ++u) s += v[u];
         }
         for (; c < nchunks; ++c) s += base[(size_t)c * cstride];
-        if (packed) stats[(size_t)(I * (I + 1) / 2 + J) * (TB * TB) + j * TB + z * 4 + il] = s;
+        if (sym_diag && I == J) {                            // (uniform)
+            double* tile = packed ? stats + (size_t)(I * (I + 1) / 2 + J) * (TB * TB) : stats + (size_t)(J * TB) * Mp + I * TB;
+            const size_t ld = packed ? TB : Mp;
+            const int row = z * 4 + il;
+            if (row >= j) {
+                tile[(size_t)j * ld + row] = s;
+                tile[(size_t)row * ld + j] = s;
+            }
+        } else if (packed) stats[(size_t)(I * (I + 1) / 2 + J) * (TB * TB) + j * TB + z * 4 + il] = s;
         else {
             stats[(size_t)(J * TB + j) * Mp + I * TB + z * 4 + il] = s;
             if (I != J) stats[(size_t)(I * TB + z * 4 + il) * Mp + J * TB + j] = s;
@@ -1033,13 +1045,26 @@ __global__ void __launch_bounds__(256) k_assemble(const double* __restrict__ sla
         for (; c < nchunks; ++c)
 #pragma unroll
             for (int r = 0; r < 4; ++r) s[r] += base[(size_t)c * cstride + r * TB];
-        double* col = packed ? stats + (size_t)(I * (I + 1) / 2 + J) * (TB * TB) + (size_t)j * TB + 4 * zr
-                             : stats + (size_t)(J * TB + j) * Mp + I * TB + 4 * zr;
-        *reinterpret_cast<double2*>(col) = make_double2(s[0], s[1]);
-        *reinterpret_cast<double2*>(col + 2) = make_double2(s[2], s[3]);
-        if (!packed && I != J)
+        if (sym_diag && I == J) {                            // (uniform)
+            double* tile = packed ? stats + (size_t)(I * (I + 1) / 2 + J) * (TB * TB) : stats + (size_t)(J * TB) * Mp + I * TB;
+            const size_t ld = packed ? TB : Mp;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) stats[(size_t)(I * TB + 4 * zr + r) * Mp + J * TB + j] = s[r];
+            for (int r = 0; r < 4; ++r) {
+                const int row = 4 * zr + r;
+                if (row >= j) {
+                    tile[(size_t)j * ld + row] = s[r];
+                    tile[(size_t)row * ld + j] = s[r];
+                }
+            }
+        } else {
+            double* col = packed ? stats + (size_t)(I * (I + 1) / 2 + J) * (TB * TB) + (size_t)j * TB + 4 * zr
+                                 : stats + (size_t)(J * TB + j) * Mp + I * TB + 4 * zr;
+            *reinterpret_cast<double2*>(col) = make_double2(s[0], s[1]);
+            *reinterpret_cast<double2*>(col + 2) = make_double2(s[2], s[3]);
+            if (!packed && I != J)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) stats[(size_t)(I * TB + 4 * zr + r) * Mp + J * TB + j] = s[r];
+        }
     }
     // B = sum of the per-block partials (sum_b_pairs), by the blocks of the extra grid row.  (Two ways of taking this off the path in
     // front of the Lambda chain were built and measured in round 4 -- B summed on the masked stream ahead of this launch, and B

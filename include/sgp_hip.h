@@ -212,7 +212,8 @@ int sgp_get_posterior(sgp_handle* h, double* mu_v, double* Sigma_v, double* Uv);
 /* (sgp_get_scalars waits for the handle's work, polled, and then reads a pinned block the sweep's last kernel wrote the scalars and the
  * hand-off status to -- no device-to-host copy behind the wait; SGP_NO_ZERO_COPY=1 restores the copies) */
 int sgp_get_scalars(sgp_handle* h, double* out /* SGP_R_COUNT */);
-/* sgp_get_stats: the reduced statistics (tests, theta-gradient): Psi2 M x M, B M x d_out, scalars SGP_S_COUNT */
+/* sgp_get_stats: the reduced statistics (tests, theta-gradient): Psi2 M x M (exactly symmetric, with point weights too), B M x d_out,
+ * scalars SGP_S_COUNT */
 int sgp_get_stats(sgp_handle* h, double* Psi2, double* B, double* scalars);
 /* sgp_get_kuu_chol: meta.KuuL (helper_functions/gp_helperfunction.jl:39), lower, M x M */
 int sgp_get_kuu_chol(sgp_handle* h, double* KuuL);

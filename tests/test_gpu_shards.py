@@ -113,66 +113,40 @@ def test_ranks_agree_on_the_overlap_plan_with_an_empty_shard(G, n_max):
 
 
 def _sharded_run(G, world, N, M, D, n_max, w=200.0, seed=41):
-    """One sharded sweep and theta objective, simulated: pass 1 captures every rank's pieces (local statistics), pass 2 sweeps every
-    rank with a hook that adds the other ranks' pieces -- what a sum-all-reduce leaves in the buffer -- so that every rank holds the
-    whole posterior; then the 33-double gradient payloads the same way.  Returns the ranks' hook call sizes and rank 0's results."""
-    torch = pytest.importorskip("torch")
-    from gaussianprocessnode_amd.distributed import device_tensor
+    """One sharded sweep and theta objective, simulated (tests/sharded_ref.py, `simulate`): pass 1 captures every rank's pieces (local
+    statistics), pass 2 sweeps every rank with a hook that adds the other ranks' pieces -- what a sum-all-reduce leaves in the
+    buffer -- so that every rank holds the whole posterior; then the 33-double gradient payloads the same way.  Returns the ranks'
+    hook call sizes and rank 0's results."""
+    pytest.importorskip("torch")
+    from tests.sharded_ref import simulate
     rng = np.random.default_rng(seed)
     X = rng.uniform(-1.745, 1.745, (N, D))
     Xu = (X if N >= M else rng.uniform(-1.745, 1.745, (M, D)))[:M].copy()
     y = np.sin(X.sum(axis=1)) + 0.1 * rng.normal(size=N)
     s2, ell = 0.9, np.linspace(1.5, 3.0, D)
-    devs = []
-    for r in range(world):
+    plans = [None] * world
+
+    def make(r):
         lo, hi = shard_bounds(N, world, r)
         d = G.SGPDevice(n_max, M, D)
         d.set_inducing(Xu); d.set_data(X[lo:hi], y[lo:hi]); d.set_kernel(s2, ell, 0.0)
         d.set_prior_isotropic(50.0); d.set_noise([[w]])
-        devs.append(d)
+        return d
 
-    def capturing(store, calls):
-        def hook(ptr, n, stream):
-            calls.append(n)
-            with torch.cuda.stream(torch.cuda.ExternalStream(stream)):
-                store.append(device_tensor(ptr, n).clone())
-        return hook
+    def apply(r, d, op, second):
+        if op == "sweep":
+            d.sweep()
+            if not second:
+                plans[r] = contract(d.overlap_plan())
+            return dict(post=d.posterior(), stats=d.stats(), scalars=d.scalars()) if second else None
+        val, grad = d.theta_objective(want_grad=True)
+        return dict(val=val, grad=grad)
 
-    def adding(others, calls):
-        def hook(ptr, n, stream):
-            k = len(calls)
-            calls.append(n)
-            with torch.cuda.stream(torch.cuda.ExternalStream(stream)):
-                t = device_tensor(ptr, n)
-                for o in others:
-                    assert o[k].numel() == n
-                    t.add_(o[k])
-        return hook
-    try:
-        pieces, calls1 = [[] for _ in devs], [[] for _ in devs]
-        for r, d in enumerate(devs):
-            d.set_allreduce(capturing(pieces[r], calls1[r]))
-            d.sweep()
-        torch.cuda.synchronize()
-        plans = [contract(d.overlap_plan()) for d in devs]
-        calls2 = [[] for _ in devs]
-        for r, d in enumerate(devs):
-            d.set_allreduce(adding([pieces[q] for q in range(world) if q != r], calls2[r]))
-            d.sweep()
-        torch.cuda.synchronize()
-        posts = [d.posterior() for d in devs]
-        gpieces, gcalls = [[] for _ in devs], [[] for _ in devs]
-        for r, d in enumerate(devs[1:], 1):
-            d.set_allreduce(capturing(gpieces[r], gcalls[r]))
-            d.theta_objective(want_grad=True)
-        torch.cuda.synchronize()
-        devs[0].set_allreduce(adding(gpieces[1:], gcalls[0]))
-        val, grad = devs[0].theta_objective(want_grad=True)
-        out = dict(plans=plans, calls1=calls1, calls2=calls2, gcalls=gcalls, posts=posts, val=val, grad=grad,
-                   stats=devs[0].stats(), scalars=devs[0].scalars())
-    finally:
-        for d in devs:
-            d.close()
+    swept, objective = simulate(world, make, ["sweep", "objective"], apply)
+    first = swept["results"][0]
+    out = dict(plans=plans, calls1=swept["captured"], calls2=swept["calls"], gcalls=objective["calls"],
+               posts=[r["post"] for r in swept["results"]], val=objective["results"][0]["val"],
+               grad=objective["results"][0]["grad"], stats=first["stats"], scalars=first["scalars"])
     return out, (X, Xu, y, s2, ell, w)
 
 

@@ -105,33 +105,39 @@ def full_ell(ell, D):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the d_out = 1 objective (helper_functions/derivative_helper.jl:23-39) and its analytic gradient
 # ---------------------------------------------------------------------------------------------------------------------------
-def theta_objective(family, sigma2, ell, Xu, X, y, mu, Sigma, w, jitter):
-    """f = w/2 [sigma2 n - tr(Kinv Psi2) + tr(R Psi2)] - w mu' K_uf y,  R = Sigma + mu mu', Kinv = (K_uu + jitter I)^-1."""
+def theta_objective(family, sigma2, ell, Xu, X, y, mu, Sigma, w, jitter, omega=None):
+    """f = w/2 [sigma2 n - tr(Kinv Psi2) + tr(R Psi2)] - w mu' K_uf y,  R = Sigma + mu mu', Kinv = (K_uu + jitter I)^-1.
+    `omega`: the point weights of sgp_set_data (include/sgp_hip.h, sgp_theta_objective) -- Psi2 = K_uf diag(omega) K_uf', the
+    targets omega .* y and s_w = sum omega in place of n; None is every weight 1."""
     M, D = Xu.shape
     ell = full_ell(ell, D)
+    om = np.ones(len(y)) if omega is None else np.asarray(omega, dtype=np.float64)
     Kinv = np.linalg.inv(kernelmatrix(family, sigma2, ell, Xu, Xu) + jitter * np.eye(M))
     Kuf = kernelmatrix(family, sigma2, ell, Xu, X)
-    Psi2 = Kuf @ Kuf.T
+    Psi2 = (Kuf * om) @ Kuf.T
     R = Sigma + np.outer(mu, mu)
-    return 0.5 * w * (sigma2 * len(y) - np.sum(Kinv * Psi2) + np.sum(R * Psi2)) - w * float(mu @ (Kuf @ y))
+    return 0.5 * w * (sigma2 * om.sum() - np.sum(Kinv * Psi2) + np.sum(R * Psi2)) - w * float(mu @ (Kuf @ (om * y)))
 
 
-def theta_grad(family, sigma2, ell, n_ell, Xu, X, y, mu, Sigma, w, jitter, bound=False, one_dim=False):
+def theta_grad(family, sigma2, ell, n_ell, Xu, X, y, mu, Sigma, w, jitter, bound=False, one_dim=False, omega=None):
     """d f / d (sigma2, ell_1 .. ell_n_ell).  With dk = the derivative of a kernel value,
         df = w [ sum_pn dK_uf o ((R - Kinv) K_uf - mu y') + 1/2 sum H o dK_uu + 1/2 n dsigma2 ],   H = Kinv Psi2 Kinv,
         dk / dsigma2 = k / sigma2 (the jitter is no part of dK_uu),   dk / dell_d = -2 sigma2 kappa'(s) (a_d - b_d)^2 / ell_d^3.
-    n_ell = 1: the single lengthscale's derivative is the sum over the dimensions (`one_dim`: the fault that takes dimension 0)."""
+    n_ell = 1: the single lengthscale's derivative is the sum over the dimensions (`one_dim`: the fault that takes dimension 0).
+    `omega` (None: every weight 1): point p's terms -- its column of dK_uf o (..), of Psi2 and of the bound -- carry omega_p, and
+    s_w = sum omega stands for n (`theta_objective`); integer weights are repeated points."""
     M, D = Xu.shape
-    n = len(y)
+    om = np.ones(len(y)) if omega is None else np.asarray(omega, dtype=np.float64)
+    n = om.sum() if omega is not None else len(y)
     ell = full_ell(ell, D)
     s_uu, s_uf = sq_dist(ell, Xu, Xu), sq_dist(ell, Xu, X)
     Kuu, Kuf = sigma2 * kappa(family, s_uu), sigma2 * kappa(family, s_uf)
     Kj = Kuu + jitter * np.eye(M)
     Kinv = np.linalg.inv(Kj)
     R = Sigma + np.outer(mu, mu)
-    Psi2 = Kuf @ Kuf.T
+    Psi2 = (Kuf * om) @ Kuf.T
     H = Kinv @ Psi2 @ Kinv
-    A = (R - Kinv) @ Kuf - np.outer(mu, y)
+    A = ((R - Kinv) @ Kuf - np.outer(mu, y)) * om
     dsu, dsf = -2.0 * sigma2 * dkappa_ds(family, s_uu), -2.0 * sigma2 * dkappa_ds(family, s_uf)
     d_uf = [Kuf / sigma2] + [dsf * (Xu[:, k:k + 1] - X[None, :, k]) ** 2 / ell[k] ** 3 for k in range(D)]
     d_uu = [Kuu / sigma2] + [dsu * (Xu[:, k:k + 1] - Xu[None, :, k]) ** 2 / ell[k] ** 3 for k in range(D)]
@@ -142,7 +148,7 @@ def theta_grad(family, sigma2, ell, n_ell, Xu, X, y, mu, Sigma, w, jitter, bound
     if not bound:
         return g
     cond = float(np.linalg.cond(Kj))
-    AK, AR = np.abs(Kinv) @ np.abs(Kuf), np.abs(R) @ np.abs(Kuf) + np.outer(np.abs(mu), np.abs(y))
+    AK, AR = (np.abs(Kinv) @ np.abs(Kuf)) * om, (np.abs(R) @ np.abs(Kuf) + np.outer(np.abs(mu), np.abs(y))) * om
     b = np.array([cond * (np.sum(np.abs(f) * AK) + 0.5 * np.sum(np.abs(H) * np.abs(u))) + np.sum(np.abs(f) * AR)
                   for f, u in zip(d_uf, d_uu)])
     b[0] += 0.5 * n

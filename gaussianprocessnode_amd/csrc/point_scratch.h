@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
-// sgp_out_message).  Plain C++, no HIP: the layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp
-// and tools/out_message_scratch_check.cpp.
+// sgp_out_message).  Plain C++, no HIP: all five layouts are checked on the host over a grid of shapes by
+// tools/point_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -29,7 +29,7 @@ struct PointShape {
     int64_t chunk, n, n_nodes;      // points per chunk (a multiple of 64), points and nodes of the call
 };
 
-// what sgp_predict_var and sgp_in_message share: the factors at the current kernel and one chunk of the M-wide panel
+// what sgp_predict_var and the two :in calls share: the factors at the current kernel and one chunk of the M-wide panel
 struct PanelScratch {
     double *Kuu, *Wk;               // K_uu -> L_K, and W_K = L_K^-1
     double *Kc, *Pa, *Pb, *Kmu;     // per chunk: K(Xu, X), the two quadratic forms' partials, k . mu rows
@@ -62,26 +62,36 @@ static inline void layout_predict_var(Carver& c, const PointShape& p, PredictVar
     b->VarC = c.take<double>((size_t)p.chunk * p.dout * p.dout);
 }
 
-struct InMessageScratch : PanelScratch {
+// what sgp_in_message and sgp_in_message_grad share: the panel, S and its factor, an explicit Sigma_v and what the logpdf of all
+// points needs
+struct InScratch : PanelScratch {
     double* SS;                     // S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)') -> its factor
     double* SigP;                   // an explicit Sigma_v padded with the identity
-    double *Xall, *Lp, *Wt, *G;     // all points: X, logpdf, cubature weights, k_in_moments' shifted weights
+    double *Xall, *Lp;              // all points: X, logpdf
     int64_t* Node;                  // all points: the node of each
     double* Yw;                     // per node: the row y_t' W
+};
+static inline void layout_in(Carver& c, const PointShape& p, InScratch* b) {
+    const size_t n = (size_t)p.n;
+    layout_panel(c, p, b);
+    b->SS = c.take<double>((size_t)p.Mp * p.Mp);
+    b->SigP = c.take<double>((size_t)p.Qp * p.Qp);
+    b->Xall = c.take<double>(n * p.D);
+    b->Lp = c.take<double>(n);
+    b->Node = c.take<int64_t>(n);
+    b->Yw = c.take<double>((size_t)p.n_nodes * p.dout);
+}
+
+struct InMessageScratch : InScratch {
+    double *Wt, *G;                 // all points: cubature weights, k_in_moments' shifted weights
     int64_t* Start;                 // node_start (n_nodes + 1)
     double *LogNorm, *MeanN, *CovN; // per node: the moments
 };
 static inline void layout_in_message(Carver& c, const PointShape& p, InMessageScratch* b) {
     const size_t n = (size_t)p.n, nn = (size_t)p.n_nodes, D = (size_t)p.D;
-    layout_panel(c, p, b);
-    b->SS = c.take<double>((size_t)p.Mp * p.Mp);
-    b->SigP = c.take<double>((size_t)p.Qp * p.Qp);
-    b->Xall = c.take<double>(n * D);
-    b->Lp = c.take<double>(n);
+    layout_in(c, p, b);
     b->Wt = c.take<double>(n);
     b->G = c.take<double>(n);
-    b->Node = c.take<int64_t>(n);
-    b->Yw = c.take<double>(nn * p.dout);
     b->Start = c.take<int64_t>(nn + 1);
     b->LogNorm = c.take<double>(nn);
     b->MeanN = c.take<double>(nn * D);
@@ -90,29 +100,18 @@ static inline void layout_in_message(Carver& c, const PointShape& p, InMessageSc
 
 // sgp_in_message_grad: sgp_in_message's factors and logpdf, the matrix A = tr(W) K_uu^-1 - S, and one chunk of the (1 + D)-column
 // panels P = [k | J_1 .. J_D] and U = A P with the chunk's outputs
-struct InMessageGradScratch : PanelScratch {
-    double* SS;                     // S -> its factor (the logpdf's second form)
-    double* SigP;                   // an explicit Sigma_v padded with the identity
+struct InMessageGradScratch : InScratch {
     double* A;                      // a copy of S taken before it is factored -> A, zero on the padding
     double* Kinv;                   // W_K' W_K
-    double *Xall, *Lp;              // all points: X, logpdf
-    int64_t* Node;                  // all points: the node of each
-    double* Yw;                     // per node: the row y_t' W
     double *Pn, *Un;                // per chunk: P and U, [point][1 + D][Mp]
     double* Qc;                     // per chunk: q = s_t + A k and the weights of the z z' terms, [point][2][Mp]
     double *GradC, *HessC;          // per chunk: the gradients [point][D] and Hessians [point][D][D]
 };
 static inline void layout_in_message_grad(Carver& c, const PointShape& p, InMessageGradScratch* b) {
-    const size_t n = (size_t)p.n, nn = (size_t)p.n_nodes, D = (size_t)p.D, ch = (size_t)p.chunk;
-    layout_panel(c, p, b);
-    b->SS = c.take<double>((size_t)p.Mp * p.Mp);
-    b->SigP = c.take<double>((size_t)p.Qp * p.Qp);
+    const size_t D = (size_t)p.D, ch = (size_t)p.chunk;
+    layout_in(c, p, b);
     b->A = c.take<double>((size_t)p.Mp * p.Mp);
     b->Kinv = c.take<double>((size_t)p.Mp * p.Mp);
-    b->Xall = c.take<double>(n * D);
-    b->Lp = c.take<double>(n);
-    b->Node = c.take<int64_t>(n);
-    b->Yw = c.take<double>(nn * p.dout);
     b->Pn = c.take<double>(ch * (1 + D) * p.Mp);
     b->Un = c.take<double>(ch * (1 + D) * p.Mp);
     b->Qc = c.take<double>(ch * 2 * p.Mp);

@@ -2138,7 +2138,8 @@ static void launch_predict(const sgp_handle* h, hipStream_t s, const double* Xus
     }
 }
 
-// ---- what the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message) share ----
+// ---- what the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad, sgp_out_message)
+// ---- share
 static int refuse(sgp_handle* h, const char* name, const char* why) {
     return fail(h, SGP_ERR_ARG, (std::string(name) + ": " + why).c_str());
 }
@@ -2156,6 +2157,22 @@ static int point_call_ready(sgp_handle* h, const char* name, const double* mu_v,
     if (int rc = refuse_training(h, name)) return rc;
     if (!mu_v && !h->swept) return refuse(h, name, "no posterior in the handle and mu_v / Sigma_v are NULL");
     if (!mu_v && h->posterior_set) return refuse(h, name, "sgp_set_posterior gave no Sigma_v: pass mu_v and Sigma_v, or sweep first");
+    return 0;
+}
+
+// ... and of a call that needs the mean of q(v) alone (sgp_predict, sgp_out_message): the explicit mu_v or the handle's
+static int mean_call_ready(sgp_handle* h, const char* name, const double* mu_v) {
+    if (int rc = refuse_unset(h, name)) return rc;
+    if (!mu_v && !h->swept) return refuse(h, name, "no posterior in the handle and mu_v is NULL");
+    return refuse_training(h, name);
+}
+
+// the partition of the node-batch calls: node t owns the points node_start[t] .. node_start[t + 1] of 0 .. n, and none is empty
+static int node_partition_ready(sgp_handle* h, const char* name, int64_t n, const int64_t* node_start, int64_t n_nodes) {
+    if (n_nodes < 1 || n_nodes > n || node_start[0] != 0 || node_start[n_nodes] != n)
+        return refuse(h, name, "node_start must run from 0 to n");
+    for (int64_t t = 0; t < n_nodes; ++t)
+        if (node_start[t + 1] <= node_start[t]) return refuse(h, name, "node_start must increase (no empty node)");
     return 0;
 }
 
@@ -2180,6 +2197,15 @@ static int resolve_qv(sgp_handle* h, const double* mu_v, const double* Sigma_v, 
     return 0;
 }
 
+// the mean of q(v) for the mean-only calls: the explicit one uploaded as it is (Q entries, unpadded) into dMuX, or the handle's
+static int resolve_mu(sgp_handle* h, const double* mu_v, double* dMuX, const double** dMu) {
+    *dMu = h->dMu;
+    if (!mu_v) return 0;
+    HIPCHK(h, hipMemcpy(dMuX, mu_v, sizeof(double) * h->Q, hipMemcpyHostToDevice));
+    *dMu = dMuX;
+    return 0;
+}
+
 // points per chunk of the M-wide panel: a multiple of 64, sized to the scratch budget (or SGP_PREDICT_CHUNK), at most the call's
 constexpr int64_t PREDICT_CHUNK_DOUBLES = int64_t(1) << 25;     // scratch of one chunk: 256 MB
 static int64_t point_chunk(const sgp_handle* h, int64_t per_point, int64_t count) {
@@ -2191,13 +2217,43 @@ static PointShape point_shape(const sgp_handle* h, int64_t per_point, int64_t n,
     return PointShape{h->Mp, h->Qp, h->T, h->D, h->dout, POTRF_SCRATCH, point_chunk(h, per_point, n), n, n_nodes};
 }
 
-// the call scratch for what pass 1 of a layout function summed, and the carver rewound onto it for pass 2
-static int carve_call_scratch(sgp_handle* h, Carver* c) {
+// The two passes of a layout function (point_scratch.h) from one spelling of its arguments: `layout(carver)` over a null base sums
+// the sizes, the call scratch is made that large, and the same `layout` over it hands out the pointers.
+template <class Layout>
+static int carve_call_scratch(sgp_handle* h, Layout&& layout) {
+    Carver c;
+    layout(c);
     double* base = nullptr;
-    if (int crc = call_scratch(h, c->used, &base)) return crc;
-    *c = Carver{base};
+    if (int crc = call_scratch(h, c.used, &base)) return crc;
+    c = Carver{base};
+    layout(c);
     return 0;
 }
+
+// mean(q_W) of the last sgp_set_noise ([w_bar] for d_out = 1) as the :in calls and the MultiSGP theta objective take it: the matrix
+// by value for the kernels, tr(W) summed over d = 0 .. d_out - 1 wherever it is used, and for the node calls the rows y_t' W
+// (n_nodes x d_out, node-major; y_mean column-major n_nodes x d_out) with the node of every point
+struct MeanW {
+    OutMat W;
+    double trace = 0.0;
+    std::vector<double> yw;
+    std::vector<int64_t> node_of;
+    explicit MeanW(const sgp_handle* h, const double* y_mean = nullptr, int64_t n = 0, const int64_t* node_start = nullptr,
+                   int64_t n_nodes = 0) : yw((size_t)n_nodes * h->dout), node_of((size_t)n) {
+        const int dout = h->dout;
+        memset(&W, 0, sizeof W);
+        for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
+        for (int d = 0; d < dout; ++d) trace += W.v[d + d * dout];
+        for (int64_t t = 0; t < n_nodes; ++t) {
+            for (int d = 0; d < dout; ++d) {
+                double v = 0.0;
+                for (int e = 0; e < dout; ++e) v = fma(y_mean[t + e * n_nodes], W.v[e + d * dout], v);
+                yw[(size_t)t * dout + d] = v;
+            }
+            for (int64_t p = node_start[t]; p < node_start[t + 1]; ++p) node_of[(size_t)p] = t;
+        }
+    }
+};
 
 // "Factor at the current kernel", first half: the factorisations' scratch and status words cleared, the current parameters into
 // the K_uu chain's mirror (as sgp_predict), K_uu at them.  The caller may enqueue what forms its second matrix behind it.
@@ -2263,23 +2319,15 @@ static bool invert_outmat(const double* W, int dout, OutMat* out) {
 
 extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, double* mean) {
     if (!h || !Xstar || !mean || ns < 0) return fail(h, SGP_ERR_ARG, "sgp_predict: bad argument");
-    if (int rc = refuse_unset(h, "sgp_predict")) return rc;
-    if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_predict: no posterior in the handle and mu_v is NULL");
-    if (int rc = refuse_training(h, "sgp_predict")) return rc;
+    if (int rc = mean_call_ready(h, "sgp_predict", mu_v)) return rc;
     if (ns == 0) return 0;
     if (int wrc = sync_all(h)) return wrc;
     hipStream_t s = h->own;
-    Carver c;
     PredictScratch b;
-    layout_predict(c, ns, h->D, h->dout, mu_v ? h->Q : 0, &b);
-    if (int crc = carve_call_scratch(h, &c)) return crc;
-    layout_predict(c, ns, h->D, h->dout, mu_v ? h->Q : 0, &b);
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_predict(c, ns, h->D, h->dout, mu_v ? h->Q : 0, &b); })) return crc;
     HIPCHK(h, hipMemcpy(b.Xs, Xstar, sizeof(double) * ns * h->D, hipMemcpyHostToDevice));
-    const double* dMu = h->dMu;
-    if (mu_v) {
-        HIPCHK(h, hipMemcpy(b.Mu, mu_v, sizeof(double) * h->Q, hipMemcpyHostToDevice));
-        dMu = b.Mu;
-    }
+    const double* dMu;
+    if (int rc = resolve_mu(h, mu_v, b.Mu, &dMu)) return rc;
     mirror_current_params(h, s);
     launch_predict(h, s, h->dXusK, h->dParamsK, b.Xs, dMu, b.Mean, ns);
     HIPCHK(h, hipStreamSynchronize(s));
@@ -2303,11 +2351,8 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
     const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T;
     const PointShape shape = point_shape(h, (int64_t)Mp + 4 * T + 4 + D + dout + dout * dout, ns, 0);
     const int64_t chunk = shape.chunk;
-    Carver c;
     PredictVarScratch b;
-    layout_predict_var(c, shape, &b);
-    if (int crc = carve_call_scratch(h, &c)) return crc;
-    layout_predict_var(c, shape, &b);
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_predict_var(c, shape, &b); })) return crc;
     // the last sweep's Sigma_v is copied: its factor is formed in place
     const double *dMu, *dSig;
     if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.LS, &dMu, &dSig)) return rc;
@@ -2344,6 +2389,33 @@ extern "C" int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, c
     return 0;
 }
 
+// What sgp_in_message and sgp_in_message_grad run before their chunks: q(v) resolved, the points, their nodes and the rows y_t' W
+// uploaded, then "factor at the current kernel" with S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)') as the second matrix.
+// `between()` enqueues what the caller wants behind the kernel that forms S and in front of the one that factors it in place.
+template <class Between>
+static int in_prologue(sgp_handle* h, hipStream_t s, const InScratch& b, const MeanW& w, const double* X, int64_t n, int64_t n_nodes,
+                       const double* mu_v, const double* Sigma_v, const double** dMu, Between&& between) {
+    const int M = h->M, Mp = h->Mp, dout = h->dout;
+    const double* dSig;
+    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.SigP, dMu, &dSig)) return rc;
+    HIPCHK(h, hipMemcpy(b.Xall, X, sizeof(double) * n * h->D, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Node, w.node_of.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Yw, w.yw.data(), sizeof(double) * (size_t)n_nodes * dout, hipMemcpyHostToDevice));
+    if (int rc = factor_begin(h, s, b)) return rc;
+    hipLaunchKernelGGL(k_form_S_in, dim3((unsigned)(((size_t)Mp * Mp + 255) / 256)), dim3(256), 0, s, dSig, h->Qp, *dMu, w.W, b.SS, M, Mp,
+                       dout);
+    HIPCHK(h, between());
+    return factor_finish(h, s, b, b.SS, Mp, h->T, M, "S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)')");
+}
+
+// the logpdf of the nc points from s0 on: one chunk through the panel, then the per-point finish into Lp
+static void in_logpdf_chunk(sgp_handle* h, hipStream_t s, const InScratch& b, const double* dMu, double trW, int64_t s0, int64_t nc) {
+    panel_pass(h, s, b, b.Xall + (size_t)s0 * h->D, dMu, nc, b.SS);
+    hipLaunchKernelGGL(k_in_point_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)b.Pa, (const double*)b.Pb,
+                       (const double*)b.MeanC, (const double*)b.Yw, (const int64_t*)(b.Node + s0), b.Lp + s0,
+                       (const Params*)h->dParamsK, 0.5 * trW, h->T, nc, h->dout);
+}
+
 // The :in log-messages of many nodes and their moment-matched marginals (include/sgp_hip.h).  As sgp_predict_var: blocking, K_uu,
 // W_K = L_K^-1, S and its factor formed at the CURRENT kernel parameters in call scratch, nothing the sweep keeps written, the
 // M-wide panel chunked under the same knob.  k_in_moments runs once behind the last chunk, over the logpdf and the points of ALL
@@ -2357,10 +2429,7 @@ extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const i
     if (weights && (!log_norm || !mean || !cov))
         return fail(h, SGP_ERR_ARG, "sgp_in_message: weights given without log_norm, mean and cov");
     if (int rc = point_call_ready(h, "sgp_in_message", mu_v, Sigma_v)) return rc;
-    if (n_nodes < 1 || n_nodes > n || node_start[0] != 0 || node_start[n_nodes] != n)
-        return fail(h, SGP_ERR_ARG, "sgp_in_message: node_start must run from 0 to n");
-    for (int64_t t = 0; t < n_nodes; ++t)
-        if (node_start[t + 1] <= node_start[t]) return fail(h, SGP_ERR_ARG, "sgp_in_message: node_start must increase (no empty node)");
+    if (int rc = node_partition_ready(h, "sgp_in_message", n, node_start, n_nodes)) return rc;
     if (weights)
         for (int64_t t = 0; t < n_nodes; ++t) {
             bool positive = false;
@@ -2373,49 +2442,20 @@ extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const i
         }
     if (int wrc = point_call_wait(h, mu_v)) return wrc;
     hipStream_t s = h->own;
-    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Qp = h->Qp, T = h->T;
-    // W = mean(q_W) of the last sgp_set_noise ([w_bar] for d_out = 1), tr(W) and the nodes' rows y_t' W
-    OutMat W;
-    memset(&W, 0, sizeof W);
-    double trW = 0.0;
-    for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
-    for (int i = 0; i < dout; ++i) trW += W.v[i * dout + i];
-    std::vector<double> yw((size_t)n_nodes * dout);
-    std::vector<int64_t> node_of((size_t)n);
-    for (int64_t t = 0; t < n_nodes; ++t) {
-        for (int d = 0; d < dout; ++d) {
-            double v = 0.0;
-            for (int e = 0; e < dout; ++e) v = fma(y_mean[t + e * n_nodes], W.v[e + d * dout], v);
-            yw[(size_t)t * dout + d] = v;
-        }
-        for (int64_t p = node_start[t]; p < node_start[t + 1]; ++p) node_of[(size_t)p] = t;
-    }
+    const int D = h->D;
     const size_t nn = (size_t)n_nodes;
-    const PointShape shape = point_shape(h, (int64_t)Mp + 4 * T + 4 + dout, n, n_nodes);
-    const int64_t chunk = shape.chunk;
-    Carver c;
+    const MeanW w(h, y_mean, n, node_start, n_nodes);
+    const PointShape shape = point_shape(h, (int64_t)h->Mp + 4 * h->T + 4 + h->dout, n, n_nodes);
     InMessageScratch b;
-    layout_in_message(c, shape, &b);
-    if (int crc = carve_call_scratch(h, &c)) return crc;
-    layout_in_message(c, shape, &b);
-    const double *dMu, *dSig;
-    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.SigP, &dMu, &dSig)) return rc;
-    HIPCHK(h, hipMemcpy(b.Xall, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(b.Node, node_of.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(b.Yw, yw.data(), sizeof(double) * nn * dout, hipMemcpyHostToDevice));
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_in_message(c, shape, &b); })) return crc;
     if (weights) {
         HIPCHK(h, hipMemcpy(b.Wt, weights, sizeof(double) * n, hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(b.Start, node_start, sizeof(int64_t) * (nn + 1), hipMemcpyHostToDevice));
     }
-    if (int rc = factor_begin(h, s, b)) return rc;
-    hipLaunchKernelGGL(k_form_S_in, dim3((unsigned)(((size_t)Mp * Mp + 255) / 256)), dim3(256), 0, s, dSig, Qp, dMu, W, b.SS, M, Mp, dout);
-    if (int frc = factor_finish(h, s, b, b.SS, Mp, T, M, "S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)')")) return frc;
-    for (int64_t s0 = 0; s0 < n; s0 += chunk) {
-        const int64_t nc = std::min<int64_t>(chunk, n - s0);
-        panel_pass(h, s, b, b.Xall + (size_t)s0 * D, dMu, nc, b.SS);
-        hipLaunchKernelGGL(k_in_point_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)b.Pa, (const double*)b.Pb,
-                           (const double*)b.MeanC, (const double*)b.Yw, (const int64_t*)(b.Node + s0), b.Lp + s0,
-                           (const Params*)h->dParamsK, 0.5 * trW, T, nc, dout);
+    const double* dMu;
+    if (int rc = in_prologue(h, s, b, w, X, n, n_nodes, mu_v, Sigma_v, &dMu, [] { return hipSuccess; })) return rc;
+    for (int64_t s0 = 0; s0 < n; s0 += shape.chunk) {
+        in_logpdf_chunk(h, s, b, dMu, w.trace, s0, std::min<int64_t>(shape.chunk, n - s0));
         HIPCHK(h, hipGetLastError());
     }
     if (weights)
@@ -2432,10 +2472,10 @@ extern "C" int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const i
     return 0;
 }
 
-// The :in log-messages' gradients and Hessians with respect to the input (include/sgp_hip.h).  A third client of the point-batch
-// pipeline: sgp_in_message's factors, S and logpdf (the same factor_begin / factor_finish / panel_pass / k_in_point_finish on the
-// same inputs, so logpdf is bitwise sgp_in_message's), then A = tr(W) W_K' W_K - S from a copy of S taken before its factorisation,
-// and per chunk the panel P = [k | J], U = A P on the matrix cores and the per-point finish.  Everything in call scratch.
+// The :in log-messages' gradients and Hessians with respect to the input (include/sgp_hip.h).  sgp_in_message's prologue and logpdf
+// chunk on the same inputs (so logpdf is bitwise sgp_in_message's), then A = tr(W) W_K' W_K - S from a copy of S taken before its
+// factorisation, and per chunk the panel P = [k | J], U = A P on the matrix cores and the per-point finish.  Everything in call
+// scratch.
 extern "C" int sgp_in_message_grad(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes,
                                    const double* y_mean, const double* mu_v, const double* Sigma_v, double* logpdf, double* grad,
                                    double* hess) {
@@ -2445,59 +2485,26 @@ extern "C" int sgp_in_message_grad(sgp_handle* h, const double* X, int64_t n, co
     if (int rc = point_call_ready(h, "sgp_in_message_grad", mu_v, Sigma_v)) return rc;
     if (h->family == SGP_KERNEL_MATERN12)
         return fail(h, SGP_ERR_ARG, "sgp_in_message_grad: the Matern-1/2 kernel has no gradient at the inducing inputs");
-    if (n_nodes < 1 || n_nodes > n || node_start[0] != 0 || node_start[n_nodes] != n)
-        return fail(h, SGP_ERR_ARG, "sgp_in_message_grad: node_start must run from 0 to n");
-    for (int64_t t = 0; t < n_nodes; ++t)
-        if (node_start[t + 1] <= node_start[t])
-            return fail(h, SGP_ERR_ARG, "sgp_in_message_grad: node_start must increase (no empty node)");
+    if (int rc = node_partition_ready(h, "sgp_in_message_grad", n, node_start, n_nodes)) return rc;
     if (int wrc = point_call_wait(h, mu_v)) return wrc;
     hipStream_t s = h->own;
-    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Qp = h->Qp, T = h->T;
-    OutMat W;
-    memset(&W, 0, sizeof W);
-    double trW = 0.0;
-    for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
-    for (int i = 0; i < dout; ++i) trW += W.v[i * dout + i];
-    std::vector<double> yw((size_t)n_nodes * dout);
-    std::vector<int64_t> node_of((size_t)n);
-    for (int64_t t = 0; t < n_nodes; ++t) {
-        for (int d = 0; d < dout; ++d) {
-            double v = 0.0;
-            for (int e = 0; e < dout; ++e) v = fma(y_mean[t + e * n_nodes], W.v[e + d * dout], v);
-            yw[(size_t)t * dout + d] = v;
-        }
-        for (int64_t p = node_start[t]; p < node_start[t + 1]; ++p) node_of[(size_t)p] = t;
-    }
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, T = h->T;
+    const MeanW w(h, y_mean, n, node_start, n_nodes);
     // per point of a chunk: the M-wide panel's share as in sgp_in_message, the columns of P and U, q and the z z' weights, the outputs
     const int64_t per_point = (int64_t)Mp + 4 * T + 4 + dout + (int64_t)(2 * (1 + D) + 2) * Mp + D + D * D;
     const PointShape shape = point_shape(h, per_point, n, n_nodes);
-    const int64_t chunk = shape.chunk;
-    Carver c;
     InMessageGradScratch b;
-    layout_in_message_grad(c, shape, &b);
-    if (int crc = carve_call_scratch(h, &c)) return crc;
-    layout_in_message_grad(c, shape, &b);
-    const double *dMu, *dSig;
-    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.SigP, &dMu, &dSig)) return rc;
-    HIPCHK(h, hipMemcpy(b.Xall, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(b.Node, node_of.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(b.Yw, yw.data(), sizeof(double) * (size_t)n_nodes * dout, hipMemcpyHostToDevice));
-    const unsigned sq_blocks = (unsigned)(((size_t)Mp * Mp + 255) / 256);
-    if (int rc = factor_begin(h, s, b)) return rc;
-    hipLaunchKernelGGL(k_form_S_in, dim3(sq_blocks), dim3(256), 0, s, dSig, Qp, dMu, W, b.SS, M, Mp, dout);
-    HIPCHK(h, hipMemcpyAsync(b.A, b.SS, sizeof(double) * Mp * Mp, hipMemcpyDeviceToDevice, s));     // (S, before its factor replaces it)
-    if (int frc = factor_finish(h, s, b, b.SS, Mp, T, M, "S = sum_ij W_ij (Sigma_v^(ij) + mu^(i) mu^(j)')")) return frc;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_in_message_grad(c, shape, &b); })) return crc;
+    const double* dMu;
+    auto copy_S = [&] { return hipMemcpyAsync(b.A, b.SS, sizeof(double) * Mp * Mp, hipMemcpyDeviceToDevice, s); };   // (before its factor)
+    if (int rc = in_prologue(h, s, b, w, X, n, n_nodes, mu_v, Sigma_v, &dMu, copy_S)) return rc;
     launch_ata(b.Wk, b.Kinv, Mp, T, s);
-    hipLaunchKernelGGL(k_in_form_A, dim3(sq_blocks), dim3(256), 0, s, (const double*)b.Kinv, (const double*)b.A, b.A, trW, M, Mp);
-    for (int64_t s0 = 0; s0 < n; s0 += chunk) {
-        const int64_t nc = std::min<int64_t>(chunk, n - s0), ncols = nc * (D + 1);
+    hipLaunchKernelGGL(k_in_form_A, dim3((unsigned)(((size_t)Mp * Mp + 255) / 256)), dim3(256), 0, s, (const double*)b.Kinv,
+                       (const double*)b.A, b.A, w.trace, M, Mp);
+    for (int64_t s0 = 0; s0 < n; s0 += shape.chunk) {
+        const int64_t nc = std::min<int64_t>(shape.chunk, n - s0), ncols = nc * (D + 1);
         const double* dXs = b.Xall + (size_t)s0 * D;
-        if (logpdf) {
-            panel_pass(h, s, b, dXs, dMu, nc, b.SS);
-            hipLaunchKernelGGL(k_in_point_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)b.Pa,
-                               (const double*)b.Pb, (const double*)b.MeanC, (const double*)b.Yw, (const int64_t*)(b.Node + s0), b.Lp + s0,
-                               (const Params*)h->dParamsK, 0.5 * trW, T, nc, dout);
-        }
+        if (logpdf) in_logpdf_chunk(h, s, b, dMu, w.trace, s0, nc);
         by_family(h->family, [&](auto F) {
             constexpr int FAM = decltype(F)::value;
             hipLaunchKernelGGL(k_in_grad_panel<FAM>, dim3((unsigned)((nc + 15) / 16), T), dim3(256), 0, s, (const double*)h->dXu, dXs,
@@ -2530,13 +2537,8 @@ extern "C" int sgp_out_message(sgp_handle* h, const double* X, int64_t n, const 
     if (n == 0) return 0;
     if (!X || !node_start) return fail(h, SGP_ERR_ARG, "sgp_out_message: null X or node_start");
     if (!mean) return fail(h, SGP_ERR_ARG, "sgp_out_message: null mean");
-    if (int rc = refuse_unset(h, "sgp_out_message")) return rc;
-    if (!mu_v && !h->swept) return fail(h, SGP_ERR_ARG, "sgp_out_message: no posterior in the handle and mu_v is NULL");
-    if (int rc = refuse_training(h, "sgp_out_message")) return rc;
-    if (n_nodes < 1 || n_nodes > n || node_start[0] != 0 || node_start[n_nodes] != n)
-        return fail(h, SGP_ERR_ARG, "sgp_out_message: node_start must run from 0 to n");
-    for (int64_t t = 0; t < n_nodes; ++t)
-        if (node_start[t + 1] <= node_start[t]) return fail(h, SGP_ERR_ARG, "sgp_out_message: node_start must increase (no empty node)");
+    if (int rc = mean_call_ready(h, "sgp_out_message", mu_v)) return rc;
+    if (int rc = node_partition_ready(h, "sgp_out_message", n, node_start, n_nodes)) return rc;
     if (weights)
         for (int64_t p = 0; p < n; ++p)
             if (!std::isfinite(weights[p])) return fail(h, SGP_ERR_ARG, "sgp_out_message: weights must be finite");
@@ -2545,23 +2547,16 @@ extern "C" int sgp_out_message(sgp_handle* h, const double* X, int64_t n, const 
     const int D = h->D, dout = h->dout;
     const size_t nn = (size_t)n_nodes;
     const PointShape shape = point_shape(h, dout, n, n_nodes);
-    const int64_t chunk = shape.chunk;
-    Carver c;
     OutMessageScratch b;
-    layout_out_message(c, shape, mu_v ? h->Q : 0, &b);
-    if (int crc = carve_call_scratch(h, &c)) return crc;
-    layout_out_message(c, shape, mu_v ? h->Q : 0, &b);
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_out_message(c, shape, mu_v ? h->Q : 0, &b); })) return crc;
     HIPCHK(h, hipMemcpy(b.Xall, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(b.Start, node_start, sizeof(int64_t) * (nn + 1), hipMemcpyHostToDevice));
     if (weights) HIPCHK(h, hipMemcpy(b.Wt, weights, sizeof(double) * n, hipMemcpyHostToDevice));
-    const double* dMu = h->dMu;
-    if (mu_v) {
-        HIPCHK(h, hipMemcpy(b.Mu, mu_v, sizeof(double) * h->Q, hipMemcpyHostToDevice));
-        dMu = b.Mu;
-    }
+    const double* dMu;
+    if (int rc = resolve_mu(h, mu_v, b.Mu, &dMu)) return rc;
     mirror_current_params(h, s);
-    for (int64_t s0 = 0; s0 < n; s0 += chunk) {
-        const int64_t nc = std::min<int64_t>(chunk, n - s0);
+    for (int64_t s0 = 0; s0 < n; s0 += shape.chunk) {
+        const int64_t nc = std::min<int64_t>(shape.chunk, n - s0);
         launch_predict(h, s, h->dXusK, h->dParamsK, b.Xall + (size_t)s0 * D, dMu, b.MeanC, nc);
         // mean chunk: [d_out][nc] -> points s0 .. of the [d_out][n] array of all points
         HIPCHK(h, hipMemcpy2DAsync(b.PointMean + s0, sizeof(double) * n, b.MeanC, sizeof(double) * nc, sizeof(double) * nc, dout,
@@ -2616,13 +2611,6 @@ static int theta_Rv(sgp_handle* h, hipStream_t s, const double** Rv) {
     launch_gemm(h->dUvT, dUv, dRs, h->Qp, h->TQ, s);
     *Rv = dRs;
     return 0;
-}
-
-// tr(W) of the current mean(q_W), summed in the same order wherever it is used
-static double theta_trace_W(const sgp_handle* h) {
-    double t = 0.0;
-    for (int d = 0; d < h->dout; ++d) t += h->hParams->W[d + d * h->dout];
-    return t;
 }
 
 // `Rv`: UniSGP's R_v when the caller has formed it already (theta_objective_eval); nullptr: taken from theta_Rv here
@@ -2694,7 +2682,7 @@ static int enqueue_theta_grad(sgp_handle* h, hipStream_t s, const double* Rv = n
         hipLaunchKernelGGL(k_theta_grad_finish<decltype(MULTI)::value>, dim3(1), dim3(256), 0, s, uf_src, uf_blocks, part_uu, T * T,
                            h->dStats + (size_t)Mp * Mp + (size_t)Mp * h->dout, h->dParams, h->dGrad, h->D, h->n_ell,
                            split ? (const long long*)(h->dJoin + WORD_GRAD) : (const long long*)nullptr, h->grad_epoch, h->spin_limit,
-                           h->dInfo + 3, multi ? theta_trace_W(h) : 0.0);
+                           h->dInfo + 3, multi ? MeanW(h).trace : 0.0);
     };
     if (multi) finish(std::true_type{});
     else finish(std::false_type{});
@@ -2718,18 +2706,16 @@ static int enqueue_theta_multi_value(sgp_handle* h, hipStream_t s, const double*
     double* cw = dUv + (size_t)Qp * Qp;
     double* mup = cw + (size_t)dout * nmax;
     double* part = mup + (size_t)dout * Mp;
-    OutMat W{};
-    for (int i = 0; i < dout * dout; ++i) W.v[i] = h->hParams->W[i];
+    const MeanW w(h);
     if (!R)
         if (int rrc = theta_Rv(h, s, &R)) return rrc;
     const int64_t nprep = std::max<int64_t>(h->n, Mp);
     hipLaunchKernelGGL(k_theta_multi_prep, dim3((unsigned)((nprep + 255) / 256)), dim3(256), 0, s, (const double*)h->dYw,
-                       (const double*)h->dMu, W, cw, mup, h->n, M, Mp, dout);
-    const double trW = theta_trace_W(h);
+                       (const double*)h->dMu, w.W, cw, mup, h->n, M, Mp, dout);
     hipLaunchKernelGGL(k_form_G_multi, dim3(Mp), dim3(256), 0, s, R, Qp, (const double*)h->dKinv, (const double*)h->dStats,
-                       W, trW, h->dGradM, part, M, Mp, dout);
+                       w.W, w.trace, h->dGradM, part, M, Mp, dout);
     hipLaunchKernelGGL(k_theta_value_multi, dim3(1), dim3(256), 0, s, (const double*)part, (const double*)h->dStats,
-                       (const double*)mup, (const Params*)h->dParams, W, trW, h->dGrad + GRAD_SLOTS, Mp, dout);
+                       (const double*)mup, (const Params*)h->dParams, w.W, w.trace, h->dGrad + GRAD_SLOTS, Mp, dout);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

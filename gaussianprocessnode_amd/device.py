@@ -285,20 +285,27 @@ class SGPDevice:
         self._check(self._lib.sgp_predict_var(self._h, ptr(Xs), ns, ptr(mu), ptr(S), flags, ptr(mean), ptr(var)), "sgp_predict_var")
         return (mean[0], var) if self.d_out == 1 else (mean.T.copy(), var)
 
+    def _node_points(self, what: str, X, node_start):
+        """The points of a node-batch call as the ABI takes them: (X (n, D) contiguous, n, node_start as int64, n_nodes)."""
+        Xs = as_f64(np.reshape(X, (-1, self.D)))
+        start = np.ascontiguousarray(np.asarray(node_start, dtype=np.int64).reshape(-1))
+        if start.size < 1:
+            raise ValueError(f"{what}: node_start needs n_nodes + 1 entries")
+        return Xs, Xs.shape[0], start, start.size - 1
+
+    def _node_targets(self, y_mean, n_nodes: int):
+        """mean(q_out) per node, (n_nodes, d_out), as the column-major n_nodes x d_out matrix the ABI takes."""
+        return as_f64(np.asarray(y_mean, dtype=np.float64).reshape(n_nodes, self.d_out).T)
+
     def in_message(self, X, node_start, y_mean, weights=None, mu_v=None, Sigma_v=None):
         """The :in log-messages of many nodes in one call (sgp_in_message), at the current kernel and the last `set_noise`.
         X (n, D): the points of all nodes; node t owns X[node_start[t]:node_start[t + 1]] (n_nodes + 1 entries, 0 .. n);
         y_mean (n_nodes, d_out): mean(q_out) per node.  q(v) is the last sweep's (mu_v = Sigma_v = None) or the one given.
         Returns logpdf (n,) without `weights`; with the n cubature weights (logpdf, log_norm (n_nodes,), mean (n_nodes, D),
         cov (n_nodes, D, D)): per node the moments of N(x) exp(logpdf(x)), shifted by the node's largest logpdf."""
-        Xs = as_f64(np.reshape(X, (-1, self.D)))
-        n = Xs.shape[0]
-        start = np.ascontiguousarray(np.asarray(node_start, dtype=np.int64).reshape(-1))
-        n_nodes = start.size - 1
-        if n_nodes < 0:
-            raise ValueError("in_message: node_start needs n_nodes + 1 entries")
+        Xs, n, start, n_nodes = self._node_points("in_message", X, node_start)
         mu, S = self._qv_args("in_message", mu_v, Sigma_v)
-        y_cm = as_f64(np.asarray(y_mean, dtype=np.float64).reshape(n_nodes, self.d_out).T)      # column-major n_nodes x d_out
+        y_cm = self._node_targets(y_mean, n_nodes)
         logpdf = np.empty(n)
         w = log_norm = mean = cov = None
         if weights is not None:
@@ -314,14 +321,9 @@ class SGPDevice:
         analytic, at the current kernel and the last `set_noise`.  X, node_start, y_mean and q(v) as in `in_message`.  Returns
         (logpdf (n,), grad (n, D), hess (n, D, D) or None without `hessian`); logpdf is bitwise `in_message`'s, every Hessian
         exactly symmetric.  The Matern-1/2 family is refused."""
-        Xs = as_f64(np.reshape(X, (-1, self.D)))
-        n = Xs.shape[0]
-        start = np.ascontiguousarray(np.asarray(node_start, dtype=np.int64).reshape(-1))
-        n_nodes = start.size - 1
-        if n_nodes < 0:
-            raise ValueError("in_message_grad: node_start needs n_nodes + 1 entries")
+        Xs, n, start, n_nodes = self._node_points("in_message_grad", X, node_start)
         mu, S = self._qv_args("in_message_grad", mu_v, Sigma_v)
-        y_cm = as_f64(np.asarray(y_mean, dtype=np.float64).reshape(n_nodes, self.d_out).T)      # column-major n_nodes x d_out
+        y_cm = self._node_targets(y_mean, n_nodes)
         logpdf, grad = np.empty(n), np.empty((n, self.D))
         hess = np.empty((n, self.D, self.D)) if hessian else None
         self._check(self._lib.sgp_in_message_grad(self._h, ptr(Xs), n, start.ctypes.data_as(C.POINTER(C.c_int64)), n_nodes,
@@ -334,12 +336,7 @@ class SGPDevice:
         nodes; node t owns X[node_start[t]:node_start[t + 1]]; weights (n,): the cubature weights (None: every weight 1); mu_v: the
         one given or (None) the handle's current posterior mean.  Returns mean (n_nodes, d_out), mean[t, d] = sum_p w_p k_p'
         mu_v^(d) over node t's points -- or (mean, point_mean (n, d_out)) with `want_points`, point_mean bitwise `predict(X, mu_v)`."""
-        Xs = as_f64(np.reshape(X, (-1, self.D)))
-        n = Xs.shape[0]
-        start = np.ascontiguousarray(np.asarray(node_start, dtype=np.int64).reshape(-1))
-        n_nodes = start.size - 1
-        if n_nodes < 0:
-            raise ValueError("out_message: node_start needs n_nodes + 1 entries")
+        Xs, n, start, n_nodes = self._node_points("out_message", X, node_start)
         w = None if weights is None else as_f64(np.reshape(weights, (n,)))
         mu = None if mu_v is None else as_f64(np.reshape(mu_v, (self.Q,)))
         mean = np.empty((self.d_out, n_nodes))

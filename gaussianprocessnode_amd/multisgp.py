@@ -139,24 +139,14 @@ def rule_out_batch(q_ins, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta):
     Gaussian one meta.method's cubature points; all of them go to `SGPDevice.out_message` with the explicit mean(q_v), and the
     device returns the node sums Psi1' mu_v^(d).  Returns a list of MvNormalMeanPrecision(mean_t, mean(q_w)).  The values are
     those of the `rule_out` loop up to the order of the node sums (the device's lanes and tree against the host's dot product)."""
-    q_ins = list(q_ins)
-    if not q_ins:
-        return []
+    from .unisgp import _rule_out_batch
     W = _mean_W(q_w)
-    pts, wts = [], []
-    for q_in in q_ins:
-        if isinstance(q_in, PointMass):
-            p, w = np.atleast_2d(np.asarray(q_in.mean(), dtype=np.float64)), np.ones(1)
-        else:
-            p, w = meta.method.points_weights(*q_in.mean_cov())
-        pts.append(np.asarray(p, dtype=np.float64).reshape(len(w), -1))
-        wts.append(np.asarray(w, dtype=np.float64))
-    start = np.concatenate([[0], np.cumsum([len(w) for w in wts])]).astype(np.int64)
-    eng = _engine(meta, 1, W.shape[0])
-    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
-    mean = eng.out_message(np.concatenate(pts), start, np.concatenate(wts), np.asarray(q_v.mean(), dtype=np.float64))
-    return [MvNormalMeanPrecision(mean[t].copy(), W) for t in range(len(q_ins))]
+    return _rule_out_batch(
+        q_ins, q_v, q_theta, meta,
+        points_weights_of=lambda q_in: ((q_in.mean(), np.ones(1)) if isinstance(q_in, PointMass)
+                                        else meta.method.points_weights(*q_in.mean_cov())),
+        engine_of=lambda: _engine(meta, 1, W.shape[0]),
+        make_message=lambda mean: MvNormalMeanPrecision(mean.copy(), W))
 
 
 def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, noise: bool = True):

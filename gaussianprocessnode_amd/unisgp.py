@@ -301,29 +301,35 @@ def rule_out(q_in, q_v, q_w, q_theta, meta: UniSGPMeta) -> NormalMeanPrecision:
     return NormalMeanPrecision(float(m), _mean_w(q_w))
 
 
+def _rule_out_batch(q_ins, q_v, q_theta, meta, *, points_weights_of, engine_of, make_message):
+    """What `unisgp.rule_out_batch` and `multisgp.rule_out_batch` share: the points and weights of every input
+    (points_weights_of(q_in) -> (points, weights)) go to `SGPDevice.out_message` of engine_of() in one call, at the kernel of
+    q_theta and the explicit mean(q_v); node t gets make_message(mean_t), mean_t the d_out node sums."""
+    q_ins = list(q_ins)
+    if not q_ins:
+        return []
+    pw = [points_weights_of(q_in) for q_in in q_ins]
+    X = np.concatenate([np.asarray(p, dtype=np.float64).reshape(len(w), -1) for p, w in pw])
+    wts = np.concatenate([np.asarray(w, dtype=np.float64) for _, w in pw])
+    start = np.concatenate([[0], np.cumsum([len(w) for _, w in pw])]).astype(np.int64)
+    eng = engine_of()
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    mean = eng.out_message(X, start, wts, np.asarray(q_v.mean(), dtype=np.float64))
+    return [make_message(mean[t]) for t in range(len(q_ins))]
+
+
 def rule_out_batch(q_ins, q_v, q_w, q_theta, meta: UniSGPMeta):
     """`rule_out(q_ins[t], q_v, q_w, q_theta, meta)` for every t in ONE device call (`SGPDevice.out_message`): a PointMass input
     is one point of weight 1, a Gaussian one meta.method's cubature points (GPnode/UniSGPnode.jl:85-93).  Returns a list of
     NormalMeanPrecision(mean_t, mean(q_w)); the values are those of the `rule_out` loop up to the order of the node sums."""
-    q_ins = list(q_ins)
-    if not q_ins:
-        return []
-    D = np.asarray(meta.Xu).shape[1]
-    pts, wts = [], []
-    for q_in in q_ins:
-        if _is_pointmass(q_in):
-            p, w = np.asarray(q_in.mean(), dtype=np.float64).reshape(1, D), np.ones(1)
-        else:
-            p, w = meta.method.points_weights(q_in.mean(), q_in.var())
-        pts.append(np.asarray(p, dtype=np.float64).reshape(len(w), D))
-        wts.append(np.asarray(w, dtype=np.float64))
-    start = np.concatenate([[0], np.cumsum([len(w) for w in wts])]).astype(np.int64)
-    eng = _engine(meta, 1)
-    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
-    mean = eng.out_message(np.concatenate(pts), start, np.concatenate(wts), np.asarray(q_v.mean(), dtype=np.float64))
     w_bar = _mean_w(q_w)
-    return [NormalMeanPrecision(float(mean[t, 0]), w_bar) for t in range(len(q_ins))]
+    return _rule_out_batch(
+        q_ins, q_v, q_theta, meta,
+        points_weights_of=lambda q_in: ((q_in.mean(), np.ones(1)) if _is_pointmass(q_in)
+                                        else meta.method.points_weights(q_in.mean(), q_in.var())),
+        engine_of=lambda: _engine(meta, 1),
+        make_message=lambda mean: NormalMeanPrecision(float(mean[0]), w_bar))
 
 
 def predict(Xstar, q_v, q_theta, meta: UniSGPMeta) -> np.ndarray:

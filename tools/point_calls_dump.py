@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Write every output array of `predict`, `predict_var` and `in_message` for a fixed list of small cases, and the status code and
-`sgp_last_error` string of the refusals that bad arguments and non-PD matrices provoke, to one .npz -- the bitwise A/B of a
-change to the host side of these calls: run it on both libraries (SGP_LIB_VARIANT selects a variant library) and compare with
+"""Write every output array of `predict`, `predict_var`, `in_message`, `in_message_grad` and `out_message` for a fixed list of small
+cases, and the status code and `sgp_last_error` string of the refusals that bad arguments and non-PD matrices provoke, to one .npz
+-- the bitwise A/B of a change to the host side of these calls: run it on both libraries (SGP_LIB_VARIANT selects a variant
+library) and compare with
     python tools/point_calls_dump.py --compare A.npz B.npz
-Cases: d_out 1, 2, 4; the explicit and the last sweep's q(v); noise on and off; weights present and absent; SGP_PREDICT_CHUNK
-unset and 64; SE and Matern-3/2.  M <= 64, n <= 300.
+Cases: d_out 1, 2, 4; D 1, 2, 3, 5; M 33, 40, 48 (padded) and 64 (not); the explicit and the last sweep's q(v); noise on and off;
+weights present and absent; the Hessian on and off and a NULL logpdf; SGP_PREDICT_CHUNK unset and 64 (n = 65 leaves a ragged chunk
+of one point; every case with n > 64 has a node that straddles point 64); SE and Matern-3/2.  M <= 64, n <= 300.
     python tools/point_calls_dump.py OUT.npz"""
 import ctypes as C
 import os
@@ -15,7 +17,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 # (d_out, M, D, n, family)
-CASES = [(1, 40, 1, 150, "se"), (1, 64, 3, 300, "matern32"), (2, 40, 3, 150, "se"), (2, 48, 2, 65, "matern32"), (4, 33, 5, 130, "se")]
+CASES = [(1, 40, 1, 150, "se"), (1, 64, 3, 300, "matern32"), (2, 40, 3, 150, "se"), (2, 48, 2, 65, "matern32"), (4, 33, 5, 130, "se"),
+         (1, 64, 3, 65, "se")]
 
 
 def model(d_out, M, D, n, seed):
@@ -26,6 +29,7 @@ def model(d_out, M, D, n, seed):
     sizes = []
     while sum(sizes) < n:                                                  # uneven nodes of 1 .. 40 points
         sizes.append(int(min(rng.integers(1, 41), n - sum(sizes))))
+    assert n <= 64 or any(a < 64 < b for a, b in zip(np.cumsum([0] + sizes), np.cumsum(sizes))), "no node straddles point 64"
     return dict(Xu=rng.uniform(-1.8, 1.8, (M, D)), ell=rng.uniform(0.8, 1.5, D), X=rng.uniform(-1.8, 1.8, (n, D)),
                 Xtrain=rng.uniform(-1.8, 1.8, (300, D)), ytrain=rng.normal(size=(300, d_out)), w=rng.uniform(0.1, 1.0, n),
                 start=np.concatenate([[0], np.cumsum(sizes)]), Y=rng.normal(size=(len(sizes), d_out)),
@@ -63,7 +67,25 @@ def outputs(G, out):
                         put(f"{qv}_predict_var_noise{int(noise)}", dev.predict_var(m["X"], *args, noise=noise))
                     put(f"{qv}_in_message_weights", dev.in_message(m["X"], m["start"], m["Y"], m["w"], *args))
                     put(f"{qv}_in_message_plain", dev.in_message(m["X"], m["start"], m["Y"], None, *args))
+                    for hessian in (True, False):
+                        put(f"{qv}_in_message_grad_hessian{int(hessian)}",
+                            dev.in_message_grad(m["X"], m["start"], m["Y"], *args, hessian=hessian)[:2 + hessian])
+                    put(f"{qv}_in_message_grad_no_logpdf", grad_without_logpdf(dev, m, *args))
+                    put(f"{qv}_out_message_weights", dev.out_message(m["X"], m["start"], m["w"], args[0], want_points=True))
+                    put(f"{qv}_out_message_plain", dev.out_message(m["X"], m["start"], None, args[0]))
     os.environ.pop("SGP_PREDICT_CHUNK", None)
+
+
+def grad_without_logpdf(dev, m, mu_v, Sigma_v):
+    """(grad, hess) of sgp_in_message_grad called with logpdf = NULL: the C entry point itself, which then skips the logpdf pass."""
+    from gaussianprocessnode_amd._lib import as_f64, ptr
+    n, D = m["X"].shape
+    start = np.ascontiguousarray(m["start"], dtype=np.int64)
+    X, Y, (mu, SigT) = as_f64(m["X"]), as_f64(m["Y"].T), dev._qv_args("in_message_grad", mu_v, Sigma_v)
+    grad, hess = np.empty((n, D)), np.empty((n, D, D))
+    assert 0 == dev._lib.sgp_in_message_grad(dev._h, ptr(X), n, start.ctypes.data_as(C.POINTER(C.c_int64)), len(start) - 1, ptr(Y),
+                                             ptr(mu), ptr(SigT), None, ptr(grad), ptr(hess))
+    return grad, hess
 
 
 def refusals(G, out):
@@ -99,6 +121,21 @@ def refusals(G, out):
         bufs = [ptr(x) if k else None for x, k in zip((lp, ln, mn, cv), outs)]
         record("in_message " + what, dev._lib.sgp_in_message(dev._h, ptr(Xp), n, sp, nn, ptr(Y), ptr(wts), ptr(a), ptr(b), *bufs), dev)
 
+    gr, hs, om, pm = np.empty(n * D), np.empty(n * D * D), np.empty(n * d_out), np.empty(n * d_out)
+
+    def ig(dev, what, start, a, b, Xp=X, grad=gr):
+        keep, sp, nn = st(start)
+        record("in_message_grad " + what,
+               dev._lib.sgp_in_message_grad(dev._h, ptr(Xp), n, sp, nn, ptr(Y), ptr(a), ptr(b), ptr(lp), ptr(grad), ptr(hs)), dev)
+
+    def ou(dev, what, start, wts, a, Xp=X, mean_out=om):
+        keep, sp, nn = st(start)
+        record("out_message " + what, dev._lib.sgp_out_message(dev._h, ptr(Xp), n, sp, nn, ptr(wts), ptr(a), ptr(mean_out), ptr(pm)), dev)
+
+    def node_calls(dev, what, start, a, b, **kw):
+        ig(dev, what, start, a, b, **kw)
+        ou(dev, what, start, w, a, **kw)
+
     def pr(dev, what, a, Xp=X, ns=n):
         record("predict " + what, dev._lib.sgp_predict(dev._h, ptr(Xp), ns, ptr(a), ptr(mean)), dev)
 
@@ -107,6 +144,7 @@ def refusals(G, out):
         pr(dev, "unset", mu)
         pv(dev, "unset", mu, SigT)
         im(dev, "unset", start, w, mu, SigT)
+        node_calls(dev, "unset", start, mu, SigT)
     with device(G, d_out, M, D, family, m) as dev:
         pr(dev, "ok", mu)
         pr(dev, "null X", mu, Xp=None)
@@ -135,6 +173,26 @@ def refusals(G, out):
         im(dev, "no posterior", start, w, None, None)
         im(dev, "non-PD S", start, w, mu, badT)
         im(dev, "ok after a refusal", start, w, mu, SigT)
+        node_calls(dev, "ok", start, mu, SigT)
+        node_calls(dev, "null X", start, mu, SigT, Xp=None)
+        node_calls(dev, "not from 0", [1] + list(start[1:]), mu, SigT)
+        node_calls(dev, "not to n", list(start[:-1]) + [start[-1] - 1], mu, SigT)
+        node_calls(dev, "empty node", [0, 5, 5] + list(start[2:]), mu, SigT)
+        node_calls(dev, "no nodes", [0], mu, SigT)
+        node_calls(dev, "no posterior", start, None, None)
+        ig(dev, "null grad", start, mu, SigT, grad=None)
+        ig(dev, "mu only", start, mu, None)
+        ig(dev, "Sigma only", start, None, SigT)
+        ig(dev, "non-PD S", start, mu, badT)
+        ou(dev, "null mean", start, w, mu, mean_out=None)
+        for v in (np.nan, np.inf):
+            wb = np.array(w)
+            wb[7] = v
+            ou(dev, f"weight {v}", start, wb, mu)
+        dev.set_kernel(0.9, m["ell"], 1e-6, family="matern12")
+        ig(dev, "Matern-1/2", start, mu, SigT)
+        dev.set_kernel(0.9, m["ell"], 1e-6, family=family)
+        node_calls(dev, "ok after a refusal", start, mu, SigT)
         dev.set_noise(np.zeros((d_out, d_out)))
         pv(dev, "singular noise", mu, SigT, flags=1)
         dev.set_noise(m["W"])
@@ -147,6 +205,7 @@ def refusals(G, out):
         pr(dev, "after set_posterior", None)
         pv(dev, "after set_posterior", None, None)
         im(dev, "after set_posterior", start, w, None, None)
+        node_calls(dev, "after set_posterior", start, None, None)
     out["refusals"] = np.array(got)
 
 

@@ -1,7 +1,9 @@
-// Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over a grid of shapes, the
-// pieces that layout_predict_var, layout_in_message and layout_in_message_grad hand out are pairwise disjoint at the sizes their
-// consumers need (stated here independently of the layout functions), every piece starts a multiple of Carver::ALIGN doubles from
-// the base, and the last piece ends at the total of the sizing pass.  No GPU:
+// Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over grids of shapes, the
+// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad and layout_out_message hand out are
+// pairwise disjoint at the sizes their consumers need (stated here independently of the layout functions), every piece starts a
+// multiple of Carver::ALIGN doubles from the base, pass 2 hands out the total pass 1 summed and the last piece ends there.  The
+// panel layouts are checked over one allocation of the grid's largest total; the two mean-only layouts get an allocation of
+// exactly their total per shape and every piece is written end to end, so that the sanitizer sees a write past it.  No GPU:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o tools/point_scratch_check tools/point_scratch_check.cpp
 //   (or any C++17 compiler with -fsanitize=address,undefined) && tools/point_scratch_check
 #include "../gaussianprocessnode_amd/csrc/point_scratch.h"
@@ -9,127 +11,109 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 namespace {
 constexpr int TB = 64, POTRF_SCRATCH = 3 * TB * TB + 64 + 64;      // as csrc/sgp_kernels.hip.h
+constexpr size_t d = sizeof(double);
 
-struct Piece { const char* name; const void* p; size_t bytes; };
+struct Piece { const char* name; void* p; size_t bytes; };
 long failures = 0;
 
-void fail(const PointShape& s, const char* what, const char* a, const char* b = "") {
+void fail(const char* layout, const PointShape& s, size_t mu, const char* what, const char* a, const char* b = "") {
     if (++failures <= 20)
-        std::fprintf(stderr, "Mp %d Qp %d D %d d_out %d chunk %lld n %lld nodes %lld: %s %s %s\n", s.Mp, s.Qp, s.D, s.dout,
-                     (long long)s.chunk, (long long)s.n, (long long)s.n_nodes, what, a, b);
+        std::fprintf(stderr, "%s Mp %d Qp %d D %d d_out %d chunk %lld n %lld nodes %lld mu %zu: %s %s %s\n", layout, s.Mp, s.Qp, s.D,
+                     s.dout, (long long)s.chunk, (long long)s.n, (long long)s.n_nodes, mu, what, a, b);
 }
 
-void check(const PointShape& s, const double* base, size_t total, size_t used, std::vector<Piece> pieces) {
+// One layout at one shape: `layout(carver)` runs as the library runs it, over a null base and then over `base` (of `capacity`
+// doubles; a null base only sums), and returns the pieces at the sizes their consumers need.  `exact`: the second pass runs over
+// an allocation of exactly the total instead, and every piece is written.  Returns the total of pass 1.
+template <class Layout>
+size_t check(const char* name, const PointShape& s, size_t mu, double* base, size_t capacity, bool exact, Layout&& layout) {
+    auto bad = [&](const char* what, const char* a, const char* b = "") { fail(name, s, mu, what, a, b); };
+    Carver c;
+    layout(c);
+    const size_t total = c.used;
+    std::vector<double> own;
+    if (exact) {
+        own.resize(total);
+        base = own.data();
+    } else if (!base || total > capacity) {
+        return total;
+    }
+    c = Carver{base};
+    std::vector<Piece> pieces = layout(c);
+    if (c.used != total) bad("pass 2 handed out another total than pass 1 summed", "");
+    if (exact)
+        for (const Piece& p : pieces) std::memset(p.p, 0x5a, p.bytes);
     const char* lo = reinterpret_cast<const char*>(base);
-    if (used != total) fail(s, "pass 2 handed out another total than pass 1 summed", "");
+    const size_t unit = Carver::ALIGN * d;
     std::sort(pieces.begin(), pieces.end(), [](const Piece& a, const Piece& b) { return a.p < b.p; });
     for (size_t i = 0; i < pieces.size(); ++i) {
         const char* p = static_cast<const char*>(pieces[i].p);
-        if (p < lo || (size_t)(p - lo) % (Carver::ALIGN * sizeof(double)) != 0) fail(s, "misaligned:", pieces[i].name);
-        const char* end = p + pieces[i].bytes;
-        const char* next = i + 1 < pieces.size() ? static_cast<const char*>(pieces[i + 1].p) : lo + total * sizeof(double);
-        if (end > next) fail(s, "overlap:", pieces[i].name, i + 1 < pieces.size() ? pieces[i + 1].name : "(end of the allocation)");
+        if (p < lo || (size_t)(p - lo) % unit != 0) bad("misaligned:", pieces[i].name);
+        const char* next = i + 1 < pieces.size() ? static_cast<const char*>(pieces[i + 1].p) : lo + total * d;
+        if (p + pieces[i].bytes > next) bad("overlap:", pieces[i].name, i + 1 < pieces.size() ? pieces[i + 1].name : "(the end)");
     }
     // the last piece, rounded as the carver rounds it, ends at the total
     const Piece& last = pieces.back();
-    const size_t unit = Carver::ALIGN * sizeof(double);
-    const size_t end = (size_t)(static_cast<const char*>(last.p) - lo) + (last.bytes + unit - 1) / unit * unit;
-    if (end != total * sizeof(double)) fail(s, "the last piece does not end at the total:", last.name);
+    if ((size_t)(static_cast<const char*>(last.p) - lo) + (last.bytes + unit - 1) / unit * unit != total * d)
+        bad("the last piece does not end at the total:", last.name);
+    return total;
 }
 
 // the sizes the consumers need (DESIGN.md "Prediction" and section 6c), in bytes
 std::vector<Piece> panel_pieces(const PointShape& s, const PanelScratch& b) {
-    const size_t d = sizeof(double), Mp = s.Mp, ch = (size_t)s.chunk;
+    const size_t Mp = s.Mp, ch = (size_t)s.chunk;
+    if (b.Pscr && (const char*)b.Info != (const char*)(b.Pscr + 2 * POTRF_SCRATCH)) fail("panel", s, 0, "Info is not directly behind Pscr", "");
     return {{"Kuu", b.Kuu, Mp * Mp * d}, {"Wk", b.Wk, Mp * Mp * d}, {"Kc", b.Kc, ch * Mp * d}, {"Pa", b.Pa, ch * 2 * s.T * d},
             {"Pb", b.Pb, ch * 2 * s.T * d}, {"Kmu", b.Kmu, ch * 4 * d}, {"MeanC", b.MeanC, ch * s.dout * d},
             {"MuX", b.MuX, (size_t)s.Qp * d},
-            // one memset clears the factorisations' scratch and 64 doubles of status words behind it
+            // one memset clears the factorisations' scratch and 64 doubles of status words directly behind it
             {"Pscr", b.Pscr, 2 * (size_t)POTRF_SCRATCH * d}, {"Info", b.Info, 64 * d}};
 }
-
-void check_shape(const PointShape& s, double* base, size_t capacity, size_t* largest) {
-    {
-        Carver c;
-        PredictVarScratch b;
-        layout_predict_var(c, s, &b);
-        const size_t total = c.used;
-        *largest = std::max(*largest, total);
-        if (base && total <= capacity) {
-            c = Carver{base};
-            layout_predict_var(c, s, &b);
-            std::vector<Piece> p = panel_pieces(s, b);
-            const size_t d = sizeof(double), ch = (size_t)s.chunk;
-            p.push_back({"LS", b.LS, (size_t)s.Qp * s.Qp * d});
-            p.push_back({"Xs", b.Xs, ch * s.D * d});
-            p.push_back({"VarC", b.VarC, ch * s.dout * s.dout * d});
-            if ((const char*)b.Info != (const char*)b.Pscr + 2 * (size_t)POTRF_SCRATCH * d) fail(s, "Info is not directly behind Pscr", "");
-            check(s, base, total, c.used, p);
-        }
-    }
-    {
-        Carver c;
-        InMessageScratch b;
-        layout_in_message(c, s, &b);
-        const size_t total = c.used;
-        *largest = std::max(*largest, total);
-        if (base && total <= capacity) {
-            c = Carver{base};
-            layout_in_message(c, s, &b);
-            std::vector<Piece> p = panel_pieces(s, b);
-            const size_t d = sizeof(double), n = (size_t)s.n, nn = (size_t)s.n_nodes, D = (size_t)s.D;
-            p.push_back({"SS", b.SS, (size_t)s.Mp * s.Mp * d});
-            p.push_back({"SigP", b.SigP, (size_t)s.Qp * s.Qp * d});
-            p.push_back({"Xall", b.Xall, n * D * d});
-            p.push_back({"Lp", b.Lp, n * d});
-            p.push_back({"Wt", b.Wt, n * d});
-            p.push_back({"G", b.G, n * d});
-            p.push_back({"Node", b.Node, n * sizeof(int64_t)});
-            p.push_back({"Yw", b.Yw, nn * s.dout * d});
-            p.push_back({"Start", b.Start, (nn + 1) * sizeof(int64_t)});
-            p.push_back({"LogNorm", b.LogNorm, nn * d});
-            p.push_back({"MeanN", b.MeanN, nn * D * d});
-            p.push_back({"CovN", b.CovN, nn * D * D * d});
-            if ((const char*)b.Info != (const char*)b.Pscr + 2 * (size_t)POTRF_SCRATCH * d) fail(s, "Info is not directly behind Pscr", "");
-            check(s, base, total, c.used, p);
-        }
-    }
-    {
-        Carver c;
-        InMessageGradScratch b;
-        layout_in_message_grad(c, s, &b);
-        const size_t total = c.used;
-        *largest = std::max(*largest, total);
-        if (base && total <= capacity) {
-            c = Carver{base};
-            layout_in_message_grad(c, s, &b);
-            std::vector<Piece> p = panel_pieces(s, b);
-            const size_t d = sizeof(double), n = (size_t)s.n, nn = (size_t)s.n_nodes, D = (size_t)s.D, ch = (size_t)s.chunk, Mp = s.Mp;
-            p.push_back({"SS", b.SS, Mp * Mp * d});
-            p.push_back({"SigP", b.SigP, (size_t)s.Qp * s.Qp * d});
-            p.push_back({"A", b.A, Mp * Mp * d});
-            p.push_back({"Kinv", b.Kinv, Mp * Mp * d});
-            p.push_back({"Xall", b.Xall, n * D * d});
-            p.push_back({"Lp", b.Lp, n * d});
-            p.push_back({"Node", b.Node, n * sizeof(int64_t)});
-            p.push_back({"Yw", b.Yw, nn * s.dout * d});
-            // the panel GEMM reads whole columns of P and writes whole columns of U: (1 + D) columns of Mp per point
-            p.push_back({"Pn", b.Pn, ch * (1 + D) * Mp * d});
-            p.push_back({"Un", b.Un, ch * (1 + D) * Mp * d});
-            p.push_back({"Qc", b.Qc, ch * 2 * Mp * d});
-            p.push_back({"GradC", b.GradC, ch * D * d});
-            p.push_back({"HessC", b.HessC, ch * D * D * d});
-            if ((const char*)b.Info != (const char*)b.Pscr + 2 * (size_t)POTRF_SCRATCH * d) fail(s, "Info is not directly behind Pscr", "");
-            check(s, base, total, c.used, p);
-        }
-    }
+std::vector<Piece> in_pieces(const PointShape& s, const InScratch& b) {
+    const size_t n = (size_t)s.n, Mp = s.Mp;
+    std::vector<Piece> p = panel_pieces(s, b);
+    p.insert(p.end(), {{"SS", b.SS, Mp * Mp * d}, {"SigP", b.SigP, (size_t)s.Qp * s.Qp * d}, {"Xall", b.Xall, n * s.D * d},
+                       {"Lp", b.Lp, n * d}, {"Node", b.Node, n * sizeof(int64_t)}, {"Yw", b.Yw, (size_t)s.n_nodes * s.dout * d}});
+    return p;
 }
 
-// every shape of the grid: pass 0 finds the largest total, pass 1 checks over one allocation of that size
-long sweep(double* base, size_t capacity, size_t* largest) {
+// the three panel layouts at one shape
+void check_panel_shape(const PointShape& s, double* base, size_t capacity, size_t* largest) {
+    const size_t n = (size_t)s.n, nn = (size_t)s.n_nodes, D = (size_t)s.D, ch = (size_t)s.chunk, Mp = s.Mp;
+    *largest = std::max(*largest, check("predict_var", s, 0, base, capacity, false, [&](Carver& c) {
+        PredictVarScratch b;
+        layout_predict_var(c, s, &b);
+        std::vector<Piece> p = panel_pieces(s, b);
+        p.insert(p.end(), {{"LS", b.LS, (size_t)s.Qp * s.Qp * d}, {"Xs", b.Xs, ch * D * d}, {"VarC", b.VarC, ch * s.dout * s.dout * d}});
+        return p;
+    }));
+    *largest = std::max(*largest, check("in_message", s, 0, base, capacity, false, [&](Carver& c) {
+        InMessageScratch b;
+        layout_in_message(c, s, &b);
+        std::vector<Piece> p = in_pieces(s, b);
+        p.insert(p.end(), {{"Wt", b.Wt, n * d}, {"G", b.G, n * d}, {"Start", b.Start, (nn + 1) * sizeof(int64_t)},
+                           {"LogNorm", b.LogNorm, nn * d}, {"MeanN", b.MeanN, nn * D * d}, {"CovN", b.CovN, nn * D * D * d}});
+        return p;
+    }));
+    *largest = std::max(*largest, check("in_message_grad", s, 0, base, capacity, false, [&](Carver& c) {
+        InMessageGradScratch b;
+        layout_in_message_grad(c, s, &b);
+        std::vector<Piece> p = in_pieces(s, b);
+        // the panel GEMM reads whole columns of P and writes whole columns of U: (1 + D) columns of Mp per point
+        p.insert(p.end(), {{"A", b.A, Mp * Mp * d}, {"Kinv", b.Kinv, Mp * Mp * d}, {"Pn", b.Pn, ch * (1 + D) * Mp * d},
+                           {"Un", b.Un, ch * (1 + D) * Mp * d}, {"Qc", b.Qc, ch * 2 * Mp * d}, {"GradC", b.GradC, ch * D * d},
+                           {"HessC", b.HessC, ch * D * D * d}});
+        return p;
+    }));
+}
+
+// every shape of the panel grid: pass 0 finds the largest total, pass 1 checks over one allocation of that size
+long panel_sweep(double* base, size_t capacity, size_t* largest) {
     long shapes = 0;
     const int64_t ns[] = {1, 63, 64, 65, 1000};
     for (int M = 1; M <= 130; ++M)
@@ -140,21 +124,56 @@ long sweep(double* base, size_t capacity, size_t* largest) {
                         for (int64_t chunk : {(int64_t)TB, (n + TB - 1) / TB * TB}) {      // SGP_PREDICT_CHUNK=64, and one chunk
                             const int Mp = (M + TB - 1) / TB * TB, Qp = (M * dout + TB - 1) / TB * TB;
                             const PointShape s{Mp, Qp, Mp / TB, D, dout, POTRF_SCRATCH, std::min(chunk, (n + TB - 1) / TB * TB), n, nodes};
-                            check_shape(s, base, capacity, largest);
+                            check_panel_shape(s, base, capacity, largest);
                             ++shapes;
                         }
+    return shapes;
+}
+
+// the two mean-only layouts over their grid, each shape in an allocation of its own
+long mean_only_sweep() {
+    long shapes = 0;
+    for (int D : {1, 2, 5, 32})
+        for (int dout = 1; dout <= 4; ++dout)
+            for (int64_t n : {1, 5, 63, 64, 65, 158, 1500})
+                for (size_t mu : {(size_t)0, (size_t)dout * 48, (size_t)dout * 130}) {
+                    const PointShape ps{0, 0, 0, D, dout, 0, 0, n, 0};
+                    check("predict", ps, mu, nullptr, 0, true, [&](Carver& c) {
+                        PredictScratch b;
+                        layout_predict(c, n, D, dout, mu, &b);
+                        return std::vector<Piece>{{"Xs", b.Xs, n * D * d}, {"Mean", b.Mean, n * dout * d}, {"Mu", b.Mu, mu * d}};
+                    });
+                    ++shapes;
+                    for (int64_t nodes : {(int64_t)1, (int64_t)3, n})
+                        for (int64_t chunk : {(int64_t)64, (int64_t)128, (n + 63) / 64 * 64}) {
+                            if (nodes > n) continue;
+                            const PointShape s{0, 0, 0, D, dout, 0, chunk, n, nodes};
+                            check("out_message", s, mu, nullptr, 0, true, [&](Carver& c) {
+                                OutMessageScratch b;
+                                layout_out_message(c, s, mu, &b);
+                                return std::vector<Piece>{
+                                    {"Xall", b.Xall, (size_t)n * D * d}, {"PointMean", b.PointMean, (size_t)n * dout * d},
+                                    {"Wt", b.Wt, (size_t)n * d}, {"MeanC", b.MeanC, (size_t)chunk * dout * d},
+                                    {"Start", b.Start, (size_t)(nodes + 1) * sizeof(int64_t)}, {"MeanN", b.MeanN, (size_t)nodes * dout * d},
+                                    {"Mu", b.Mu, mu * d}};
+                            });
+                            ++shapes;
+                        }
+                }
     return shapes;
 }
 }  // namespace
 
 int main() {
     size_t largest = 0;
-    sweep(nullptr, 0, &largest);
-    double* base = static_cast<double*>(std::aligned_alloc(Carver::ALIGN * sizeof(double), largest * sizeof(double)));
+    panel_sweep(nullptr, 0, &largest);
+    double* base = static_cast<double*>(std::aligned_alloc(Carver::ALIGN * d, largest * d));
     if (!base) { std::fprintf(stderr, "allocation of %zu doubles failed\n", largest); return 2; }
     size_t again = 0;
-    const long shapes = sweep(base, largest, &again);
+    const long panel = panel_sweep(base, largest, &again);
     std::free(base);
-    std::printf("%ld shapes x 3 layouts, largest total %zu doubles: %ld failure(s)\n", shapes, largest, failures);
+    const long mean_only = mean_only_sweep();
+    std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes: %ld failure(s)\n", panel, largest,
+                mean_only, failures);
     return failures ? 1 : 0;
 }

@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
-// sgp_out_message).  Plain C++, no HIP: all five layouts are checked on the host over a grid of shapes by
-// tools/point_scratch_check.cpp.
+// sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi).  Plain C++, no HIP: all six layouts are checked on the host over a grid
+// of shapes by tools/point_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -137,6 +137,36 @@ static inline void layout_out_message(Carver& c, const PointShape& p, size_t mu_
     b->Start = c.take<int64_t>(nn + 1);
     b->MeanN = c.take<double>(nn * p.dout);
     b->Mu = c.take<double>(mu_count);
+}
+
+// sgp_psi_stats and sgp_sweep_local_psi (p.n = p.n_nodes = the nodes, p.chunk nodes per chunk): the inputs of all nodes, one status
+// word per node, Psi1 and the :out means of all nodes where wanted, one chunk of g ([node][D][Mp]) with the chunk's weights, the range
+// accumulators of Psi2 (acc_tiles 64 x 64 tiles), Psi2 itself (Mp x Mp) where the call returns it, an explicit mu_v and the targets
+struct PsiScratch {
+    double *Mean, *Cov, *Wt;        // all nodes: means D x T, covariances D x D x T, node weights
+    int* Bad;                       // all nodes: 1 where a factorisation failed
+    double *Psi1, *OutMean;         // all nodes: [T][M], [d_out][T]
+    double *G2, *Cw;                // per chunk
+    double *Acc, *Psi2;
+    double* Bs;                     // B = sum_t Psi1_t y_t' ([d_out][Mp]) of the exact sweep: y_count > 0
+    double *Mu, *Y;                 // an explicit mu_v (unpadded); the targets T x d_out
+};
+static inline void layout_psi(Carver& c, const PointShape& p, int M, bool has_cov, bool want_psi1, size_t acc_tiles, bool want_psi2,
+                              size_t mu_count, size_t y_count, PsiScratch* b) {
+    const size_t n = (size_t)p.n, D = (size_t)p.D;
+    b->Mean = c.take<double>(n * D);
+    b->Cov = c.take<double>(has_cov ? n * D * D : 0);
+    b->Wt = c.take<double>(n);
+    b->Bad = c.take<int>(n);
+    b->Psi1 = c.take<double>(want_psi1 ? n * M : 0);
+    b->OutMean = c.take<double>(n * p.dout);
+    b->G2 = c.take<double>(acc_tiles ? (size_t)p.chunk * D * p.Mp : 0);
+    b->Cw = c.take<double>((size_t)p.chunk);
+    b->Acc = c.take<double>(acc_tiles * 64 * 64);
+    b->Psi2 = c.take<double>(want_psi2 ? (size_t)p.Mp * p.Mp : 0);
+    b->Mu = c.take<double>(mu_count);
+    b->Y = c.take<double>(y_count);
+    b->Bs = c.take<double>(y_count ? (size_t)p.Mp * p.dout : 0);
 }
 
 // sgp_predict: the points, their means and an explicit mu_v (Q entries, unpadded)

@@ -115,6 +115,7 @@ struct SweepPlan {
 //   sgp_train_end                               drops reuse and q(v); swept_local = false (theta moved on the device)
 //   sgp_theta_descend                           drops reuse and q(v); swept_local = false (the statistics are the last EVALUATED theta's)
 //   next_kind (once per record)                 checked, or drops reuse: its sweep ended without K_uu factored / with a wait given up
+//   sgp_sweep_local_psi                         fills the record, drops reuse, exact_psi; data_gen++; have_data = false (sgp_set_data clears exact_psi)
 struct StatsRecord {
     double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};   // the kernel values they were formed at ...
     int32_t family = SGP_KERNEL_SE;                           // ... and the family
@@ -124,6 +125,8 @@ struct StatsRecord {
     bool reusable = false;         // formed by a whole sgp_sweep outside a training run, and nothing has touched them since
     bool checked = false;          // ... and that sweep was seen to end with K_uu factored and no bounded wait given up
     bool targets = false;          // new targets since (B and the data scalars are to be formed again)
+    bool exact_psi = false;        // they are the closed-form Psi-statistics of Gaussian inputs (sgp_sweep_local_psi): no resident
+                                   // points, no K_uf -- until the next sgp_set_data
 };
 enum : unsigned { STATS_REUSE = 1u, STATS_QV = 2u };          // what stats_drop drops
 
@@ -261,6 +264,7 @@ static void stats_drop(sgp_handle* h, unsigned what) {
 }
 static void stats_targets(sgp_handle* h, bool pending) { h->stats.targets = pending; }
 static void stats_checked(sgp_handle* h, bool ok) { if (ok) h->stats.checked = true; else h->stats.reusable = false; }
+static void stats_exact_psi(sgp_handle* h, bool on) { h->stats.exact_psi = on; }
 // are the handle's current kernel values and family those of the record?  (values: sgp_set_kernel at the same theta keeps them.)
 // Both readers also need the library's own buffer or a hook: a caller-bound buffer without one may have been reduced outside.
 static bool kernel_matches(const sgp_handle* h) {
@@ -293,6 +297,13 @@ static int fail(sgp_handle* h, int code, const char* msg) {
 // (a bounded wait for a twin workgroup gave up); else the failing leading minor of the first failed matrix, with the message
 // naming it.  `reversed`: the second matrix is Lambda, factored from its last row upwards -- its minor is reported in natural
 // order (needs the handle).
+// the calls that need resident points or K_uf, after sgp_sweep_local_psi
+static int refuse_exact_psi(sgp_handle* h, const char* name) {
+    if (!h->stats.exact_psi) return 0;
+    return fail(h, SGP_ERR_ARG, (std::string(name) + ": the resident statistics are exact Psi-statistics (sgp_sweep_local_psi): there are no "
+                                 "resident points or K_uf until the next sgp_set_data").c_str());
+}
+
 static int factor_status(sgp_handle* h, int info_a, const char* name_a, int info_b = 0, const char* name_b = nullptr,
                          bool reversed = false) {
     if (info_a < 0 || info_b < 0)
@@ -982,6 +993,7 @@ extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean
     h->has_omega = pt_weight != nullptr;
     h->has_yv = y_var != nullptr;
     h->have_data = true;
+    stats_exact_psi(h, false);
     if (int rc = set_point_count(h, n)) return rc;
     h->swept = h->swept_local = false;
     return 0;
@@ -992,6 +1004,7 @@ extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean
 extern "C" int sgp_set_targets(sgp_handle* h, const double* y_mean, const double* y_var) {
     if (!h || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_set_targets: null argument");
     if (int qrc = quiesce(h)) return qrc;
+    if (int prc = refuse_exact_psi(h, "sgp_set_targets")) return prc;
     if (!h->have_data) return fail(h, SGP_ERR_ARG, "sgp_set_targets: call sgp_set_data first");
     if (y_var && h->dout != 1) return fail(h, SGP_ERR_ARG, "sgp_set_targets: y_var is only defined for d_out = 1");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1018,7 +1031,7 @@ extern "C" int sgp_set_targets(sgp_handle* h, const double* y_mean, const double
 extern "C" int sgp_set_output_cov_sum(sgp_handle* h, const double* S) {
     if (!h || !S) return fail(h, SGP_ERR_ARG, "sgp_set_output_cov_sum: null argument");
     if (int qrc = quiesce(h)) return qrc;
-    if (!h->have_data) return fail(h, SGP_ERR_ARG, "sgp_set_output_cov_sum: call sgp_set_data first");
+    if (!h->have_data && !h->stats.exact_psi) return fail(h, SGP_ERR_ARG, "sgp_set_output_cov_sum: call sgp_set_data first");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int dd = h->dout * h->dout;
     std::vector<double> ryy(dd);
@@ -1029,6 +1042,10 @@ extern "C" int sgp_set_output_cov_sum(sgp_handle* h, const double* S) {
         double syy = h->ryy_data[0] + S[0];
         HIPCHK(h, hipMemcpy(h->dDataScal + SGP_S_YY, &syy, sizeof(double), hipMemcpyHostToDevice));
     }
+    // (behind sgp_sweep_local_psi the local phase has already copied the data scalars into the statistics: they follow)
+    if (h->stats.exact_psi)
+        HIPCHK(h, hipMemcpy(h->dStats + (size_t)h->Mp * h->Mp + (size_t)h->Mp * h->dout, h->dDataScal,
+                            sizeof(double) * (SGP_S_COUNT + dd), hipMemcpyDeviceToDevice));
     stats_targets(h, true);                    // (and no data_gen++: see the table above StatsRecord)
     return 0;
 }
@@ -1460,9 +1477,9 @@ struct DevBuf {
 }  // namespace
 
 
-static int check_ready(sgp_handle* h) {
+static int check_ready(sgp_handle* h, bool need_data = true) {
     if (!h) return SGP_ERR_ARG;
-    if (!h->have_inducing || !h->have_data || !h->have_kernel)
+    if (!h->have_inducing || (need_data && !h->have_data) || !h->have_kernel)
         return fail(h, SGP_ERR_ARG, "sweep: set_inducing, set_data and set_kernel must be called first");
     return 0;
 }
@@ -1515,8 +1532,8 @@ static SweepPlan sweep_plan(const sgp_handle* h, void* stream, bool whole) {
 
 // the first half of a full sweep; `whole`: of sgp_sweep (sweep_plan), whose K_uu chain's steps may also go out alternately with the
 // Lambda chain's
-static int sweep_local_impl(sgp_handle* h, void* stream, bool whole) {
-    int rc = check_ready(h);
+static int sweep_local_impl(sgp_handle* h, void* stream, bool whole, bool need_data = true) {
+    int rc = check_ready(h, need_data);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     SweepPlan p = sweep_plan(h, stream, whole);
@@ -2076,6 +2093,7 @@ extern "C" int sgp_overlap_plan(const sgp_handle* h, int32_t* ngroups, int32_t* 
 // ------------------------------------------------------------------------------------------------
 extern "C" int sgp_w_stats(sgp_handle* h, double* I1, double* I2, void* stream) {
     if (!h) return SGP_ERR_ARG;
+    if (int prc = refuse_exact_psi(h, "sgp_w_stats")) return prc;
     if (!(h->cfg.flags & SGP_FLAG_KEEP_KUF)) return fail(h, SGP_ERR_ARG, "sgp_w_stats: create the handle with SGP_FLAG_KEEP_KUF");
     if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_w_stats: no finished sweep");
     if (h->dout != 1) return fail(h, SGP_ERR_ARG, "sgp_w_stats: d_out must be 1");
@@ -2571,6 +2589,197 @@ extern "C" int sgp_out_message(sgp_handle* h, const double* X, int64_t n, const 
     return 0;
 }
 
+// ---- closed-form SE Psi-statistics of Gaussian inputs (include/sgp_hip.h: sgp_psi_stats, sgp_sweep_local_psi) ----
+// The node ranges of k_psi2_accumulate: a function of the call's node count and the tile count alone -- the chunking takes no part,
+// so the sums do not depend on it.  About 1024 workgroups where there are that many ranges of PSI_RANGE_MIN nodes.
+static void psi_ranges(int64_t T, int ntiles, int* nranges, int64_t* range_len) {
+    const int64_t want = std::min<int64_t>((T + PSI_RANGE_MIN - 1) / PSI_RANGE_MIN, std::max(1, 1024 / ntiles));
+    *range_len = (T + want - 1) / want;
+    *nranges = (int)((T + *range_len - 1) / *range_len);
+}
+
+static PsiKern psi_kern(const sgp_handle* h) {
+    PsiKern kp;
+    memset(&kp, 0, sizeof kp);
+    kp.sigma2 = h->hParams->sigma2;
+    for (int d = 0; d < h->D; ++d) kp.ell[d] = 1.0 / h->hParams->inv_ell[d];
+    return kp;
+}
+
+// what both calls refuse, and the inputs every kernel below relies on being finite
+static int psi_inputs_ready(sgp_handle* h, const char* name, const double* mean, const double* cov, int64_t T) {
+    if (int rc = refuse_unset(h, name)) return rc;
+    if (int rc = refuse_training(h, name)) return rc;
+    if (h->family != SGP_KERNEL_SE) return refuse(h, name, "the closed form exists for SGP_KERNEL_SE only");
+    const size_t D = (size_t)h->D;
+    for (size_t i = 0; i < (size_t)T * D; ++i)
+        if (!std::isfinite(mean[i])) return refuse(h, name, "mean must be finite");
+    if (cov)
+        for (size_t i = 0; i < (size_t)T * D * D; ++i)
+            if (!std::isfinite(cov[i])) return refuse(h, name, "cov must be finite");
+    return 0;
+}
+
+// The nodes through the kernels, on `s`: per chunk k_psi_prep and, with Psi2 wanted, k_psi2_accumulate over the ranges the chunk
+// meets; behind the last chunk k_psi2_finish into `psi2_out` (Mp x Mp).  The inputs are in b (Mean, Cov, Wt, Mu as uploaded).
+static int psi_enqueue(sgp_handle* h, hipStream_t s, const PsiScratch& b, const PointShape& shape, bool has_cov, bool has_w,
+                       const double* dMu, bool want_psi1, bool want_out, double* psi2_out, int64_t* stamps) {
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, ntiles = h->ntiles;
+    const int64_t T = shape.n;
+    const PsiKern kp = psi_kern(h);
+    int nranges = 0;
+    int64_t range_len = 0;
+    psi_ranges(T, ntiles, &nranges, &range_len);
+    if (psi2_out) HIPCHK(h, hipMemsetAsync(b.Acc, 0, sizeof(double) * (size_t)nranges * ntiles * TB * TB, s));
+    for (int64_t t0 = 0; t0 < T; t0 += shape.chunk) {
+        const int64_t nc = std::min<int64_t>(shape.chunk, T - t0);
+        auto prep = [&](auto DCAP) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi_prep<decltype(DCAP)::value>), dim3((unsigned)nc), dim3(64), 0, s,
+                               (const double*)h->dXu, (const double*)(b.Mean + (size_t)t0 * D),
+                               has_cov ? (const double*)(b.Cov + (size_t)t0 * D * D) : (const double*)nullptr,
+                               has_w ? (const double*)(b.Wt + t0) : (const double*)nullptr, kp, psi2_out ? b.G2 : (double*)nullptr,
+                               psi2_out ? b.Cw : (double*)nullptr, want_psi1 ? b.Psi1 + (size_t)t0 * M : (double*)nullptr, dMu,
+                               want_out ? b.OutMean + t0 : (double*)nullptr, T, b.Bad + t0, M, Mp, D, dout);
+        };
+        if (D <= 8) prep(std::integral_constant<int, 8>{});
+        else prep(std::integral_constant<int, MAXD>{});
+        if (psi2_out) {
+            const int r0 = (int)(t0 / range_len), r1 = (int)((t0 + nc - 1) / range_len);
+            hipLaunchKernelGGL(k_psi2_accumulate, dim3(ntiles, r1 - r0 + 1), dim3(256), 0, s, (const double*)b.G2, (const double*)b.Cw,
+                               b.Acc, t0, nc, range_len, r0, ntiles, Mp, D);
+        }
+    }
+    if (psi2_out)
+        hipLaunchKernelGGL(k_psi2_finish, dim3(ntiles), dim3(256), 0, s, (const double*)b.Acc, (const double*)h->dXu, kp, psi2_out,
+                           nranges, ntiles, M, Mp, D, stamps);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// the first node whose Lambda + S_t or Lambda + 2 S_t did not factor, as the status t + 1 (0: none); `s` has been waited for
+static int psi_status(sgp_handle* h, const char* name, const PsiScratch& b, int64_t T) {
+    std::vector<int> bad((size_t)T);
+    HIPCHK(h, hipMemcpy(bad.data(), b.Bad, sizeof(int) * (size_t)T, hipMemcpyDeviceToHost));
+    for (int64_t t = 0; t < T; ++t)
+        if (bad[(size_t)t]) {
+            if (t + 1 > std::numeric_limits<int>::max()) return refuse(h, name, "Lambda + S is not positive definite at a node beyond the status range");
+            return fail(h, (int)(t + 1), (std::string(name) + ": Lambda + S or Lambda + 2 S is not positive definite at node " +
+                                         std::to_string(t) + " (cov must be positive semi-definite)").c_str());
+        }
+    return 0;
+}
+
+static PointShape psi_shape(const sgp_handle* h, int64_t T) { return point_shape(h, (int64_t)h->D * h->Mp + 1, T, T); }
+
+static int psi_upload(sgp_handle* h, const PsiScratch& b, const double* mean, const double* cov, const double* w, int64_t T) {
+    const size_t D = (size_t)h->D;
+    HIPCHK(h, hipMemcpy(b.Mean, mean, sizeof(double) * (size_t)T * D, hipMemcpyHostToDevice));
+    if (cov) HIPCHK(h, hipMemcpy(b.Cov, cov, sizeof(double) * (size_t)T * D * D, hipMemcpyHostToDevice));
+    if (w) HIPCHK(h, hipMemcpy(b.Wt, w, sizeof(double) * (size_t)T, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// Psi1, the weighted sum of Psi2 and the :out means of many Gaussian inputs in closed form (include/sgp_hip.h).  Everything in call
+// scratch; K_uu is not touched and nothing the sweep keeps is written.
+extern "C" int sgp_psi_stats(sgp_handle* h, const double* mean, const double* cov, int64_t n_nodes, const double* node_weight,
+                             const double* mu_v, double* psi1, double* psi2, double* out_mean) {
+    const char* name = "sgp_psi_stats";
+    if (!h || n_nodes < 0) return fail(h, SGP_ERR_ARG, "sgp_psi_stats: bad argument");
+    if (!psi1 && !psi2 && !out_mean) return refuse(h, name, "psi1, psi2 and out_mean are all NULL");
+    if (n_nodes == 0) return 0;
+    if (!mean) return refuse(h, name, "null mean");
+    if (int rc = psi_inputs_ready(h, name, mean, cov, n_nodes)) return rc;
+    if (out_mean && !mu_v && !h->swept) return refuse(h, name, "no posterior in the handle and mu_v is NULL");
+    if (psi2 && node_weight)
+        for (int64_t t = 0; t < n_nodes; ++t)
+            if (!std::isfinite(node_weight[t]) || node_weight[t] < 0.0) return refuse(h, name, "node_weight must be finite and >= 0");
+    if (int wrc = sync_all(h)) return wrc;
+    hipStream_t s = h->own;
+    const int M = h->M, Mp = h->Mp, dout = h->dout;
+    const int64_t T = n_nodes;
+    const PointShape shape = psi_shape(h, T);
+    int nranges = 0;
+    int64_t range_len = 0;
+    psi_ranges(T, h->ntiles, &nranges, &range_len);
+    const bool has_w = psi2 && node_weight;
+    PsiScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) {
+            layout_psi(c, shape, M, cov != nullptr, psi1 != nullptr, psi2 ? (size_t)nranges * h->ntiles : 0, psi2 != nullptr,
+                       out_mean && mu_v ? h->Q : 0, 0, &b);
+        }))
+        return crc;
+    if (int rc = psi_upload(h, b, mean, cov, has_w ? node_weight : nullptr, T)) return rc;
+    const double* dMu = nullptr;
+    if (out_mean)
+        if (int rc = resolve_mu(h, mu_v, b.Mu, &dMu)) return rc;
+    if (int rc = psi_enqueue(h, s, b, shape, cov != nullptr, has_w, dMu, psi1 != nullptr, out_mean != nullptr, psi2 ? b.Psi2 : nullptr,
+                             nullptr))
+        return rc;
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    if (int rc = psi_status(h, name, b, T)) return rc;
+    if (psi1) HIPCHK(h, hipMemcpy(psi1, b.Psi1, sizeof(double) * (size_t)T * M, hipMemcpyDeviceToHost));
+    if (psi2)
+        HIPCHK(h, hipMemcpy2D(psi2, sizeof(double) * M, b.Psi2, sizeof(double) * Mp, sizeof(double) * M, M, hipMemcpyDeviceToHost));
+    if (out_mean) HIPCHK(h, hipMemcpy(out_mean, b.OutMean, sizeof(double) * (size_t)T * dout, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The local phase of a sweep over the exact statistics (include/sgp_hip.h).  First the statistics, in call scratch, and the wait that
+// reports an indefinite node: until they have succeeded nothing of the handle's state is touched.  Then the handle is put into the
+// state of a handle without points (set_point_count(0): no gate, no SYRK geometry in use), so that sweep_local_impl enqueues the
+// K_uu chain and the empty local phase -- k_prep_xu, which opens the phase stamps, and k_assemble, which zeroes [Psi2 | B], copies
+// the data scalars and clears the Lambda chain's status word -- exactly as for an empty shard; two copies behind them on the same
+// stream put Psi2 and B over the zeros.  The data scalars are form_targets' of T unweighted points.
+extern "C" int sgp_sweep_local_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, const double* y_var,
+                                   int64_t n_nodes, void* stream) {
+    const char* name = "sgp_sweep_local_psi";
+    if (!h || !mean || !y_mean || n_nodes < 1) return fail(h, SGP_ERR_ARG, "sgp_sweep_local_psi: bad argument");
+    if (h->allreduce) return refuse(h, name, "an all-reduce hook is installed (data-sharded exact statistics are not supported)");
+    if (y_var && h->dout != 1) return refuse(h, name, "y_var is only defined for d_out = 1");
+    if (int rc = psi_inputs_ready(h, name, mean, cov, n_nodes)) return rc;
+    if (int qrc = quiesce(h)) return qrc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int M = h->M, Mp = h->Mp, dout = h->dout;
+    const int64_t T = n_nodes;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
+    const PointShape shape = psi_shape(h, T);
+    int nranges = 0;
+    int64_t range_len = 0;
+    psi_ranges(T, h->ntiles, &nranges, &range_len);
+    PsiScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) {
+            layout_psi(c, shape, M, cov != nullptr, true, (size_t)nranges * h->ntiles, true, 0, (size_t)T * dout, &b);
+        }))
+        return crc;
+    if (int rc = psi_upload(h, b, mean, cov, nullptr, T)) return rc;
+    // (unweighted nodes: form_targets' weighted targets are y_mean itself)
+    HIPCHK(h, hipMemcpy(b.Y, y_mean, sizeof(double) * (size_t)T * dout, hipMemcpyHostToDevice));
+    if (int rc = psi_enqueue(h, s, b, shape, cov != nullptr, false, nullptr, true, false, b.Psi2, nullptr)) return rc;
+    hipLaunchKernelGGL(k_psi_b, dim3((unsigned)((Mp * dout + 255) / 256)), dim3(256), 0, s, (const double*)b.Psi1, (const double*)b.Y,
+                       b.Bs, T, M, Mp, dout);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (int rc = psi_status(h, name, b, T)) return rc;
+    // the statistics exist: the handle's data are gone, the data scalars become these nodes', and no points are resident
+    h->data_gen++;
+    stats_drop(h, STATS_REUSE);
+    h->have_data = false;
+    h->swept = h->swept_local = false;
+    h->has_omega = h->has_yv = false;
+    std::vector<double> yw, scal;
+    form_targets(h, y_mean, y_var, nullptr, T, (double)T, yw, scal);
+    HIPCHK(h, hipMemcpy(h->dDataScal, scal.data(), sizeof(double) * scal.size(), hipMemcpyHostToDevice));
+    h->n_nodes = scal[SGP_S_N];
+    if (int rc = set_point_count(h, 0)) return rc;
+    if (int rc = sweep_local_impl(h, stream, false, false)) return rc;
+    stats_drop(h, STATS_REUSE);
+    HIPCHK(h, hipMemcpyAsync(h->dStats, b.Psi2, sizeof(double) * (size_t)Mp * Mp, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->dStats + (size_t)Mp * Mp, b.Bs, sizeof(double) * (size_t)Mp * dout, hipMemcpyDeviceToDevice, s));
+    stats_exact_psi(h, true);
+    return 0;
+}
+
 // F(theta) = -sum_n [ -w/2 k_nn + w/2 |L^-1 k_n|^2 - w/2 |Uv k_n|^2 + w y_n mu_v'k_n ]  (derivative_helper.jl:23-39)
 //          = w/2 [ s_kk - tr(Kuu^-1 Psi2) + tr(R Psi2) ] - w b'mu_v
 // evaluated at the CURRENT kernel parameters with q(v) (mu_v, R = Sigma_v + mu mu') held fixed at the last finished
@@ -2791,6 +3000,7 @@ static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value, con
 
 extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
     if (!h || !value) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: null argument");
+    if (int prc = refuse_exact_psi(h, "sgp_theta_objective")) return prc;
     if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: needs a finished sweep or sgp_set_posterior (q(v))");
     if (!h->have_data || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: data and kernel must be set");
     if (h->training) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: a device-paced training run is open (sgp_train_end first)");
@@ -3024,6 +3234,7 @@ extern "C" int sgp_train_end(sgp_handle* h, double* theta_raw, int64_t* counts) 
 extern "C" int sgp_theta_descend(sgp_handle* h, double* theta_raw, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2,
                                  double eps, double* opt_state, double* values, int64_t* counts) {
     if (!h || !theta_raw) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: null argument");
+    if (int prc = refuse_exact_psi(h, "sgp_theta_descend")) return prc;
     if (h->training) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: a device-paced training run is open (sgp_train_end first)");
     if (n_ell != 1 && n_ell != h->D) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: n_ell must be 1 or D");
     if (steps < 0) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: steps must be >= 0");

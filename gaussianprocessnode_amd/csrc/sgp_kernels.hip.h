@@ -4135,4 +4135,239 @@ __global__ void k_descend_step(TrainState* __restrict__ st, const double* __rest
     write_kernel_params(st, src, D, n_ell);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Closed-form SE Psi-statistics of Gaussian inputs x_t ~ N(m_t, S_t) (sgp_psi_stats, sgp_sweep_local_psi; DESIGN.md "Exact
+// Psi-statistics").  With Lambda = diag(ell^2), Lambda + c S_t = C C' (c = 1 for Psi1, 2 for Psi2) and g_tm = C^-1 (m_t - z_m):
+//   Psi1_t[m]    = sigma2 prod_d(ell_d / C_dd) exp(-1/2 |g_tm|^2)                                      (c = 1)
+//   Psi2_t[m,m'] = sigma2^2 exp(-1/4 sum_d (z_md - z_m'd)^2 / ell_d^2) prod_d(ell_d / C_dd) exp(-1/4 |g_tm + g_tm'|^2)   (c = 2)
+// Every exponent is <= 0 and every ratio ell_d / C_dd <= 1 for a positive semi-definite S_t: nothing can overflow.
+// The SE parameters travel by value (the setters wait for work in flight before they change them).
+// ------------------------------------------------------------------------------------------------
+struct PsiKern {
+    double sigma2;
+    double ell[MAXD];           // the lengthscale of every dimension (an isotropic one expanded)
+};
+constexpr int PSI_LD = MAXD + 1;            // row stride of a D x D factor in LDS
+constexpr int PSI_RANGE_MIN = 8;            // fewest nodes of a range of k_psi2_accumulate (host: psi_ranges)
+
+// the lower Cholesky factor of Lambda + c S in A (LDS, one wave): lane i owns row i.  The reciprocals of the diagonal go to rinv,
+// *bad becomes 1 when a pivot is not positive.  Only the lower triangle of S is read.
+__device__ __forceinline__ void psi_factor(double* A, double* rinv, int* bad, const double* __restrict__ S, const PsiKern& kp,
+                                           double c, int D, int lane) {
+    if (lane < D)
+        for (int j = 0; j <= lane; ++j)
+            A[lane * PSI_LD + j] = (S ? c * S[(size_t)j * D + lane] : 0.0) + (j == lane ? kp.ell[lane] * kp.ell[lane] : 0.0);
+    __syncthreads();
+    for (int k = 0; k < D; ++k) {
+        const double piv = A[k * PSI_LD + k];
+        if (!(piv > 0.0)) {                                   // (uniform: every lane reads the same word)
+            if (lane == 0) *bad = 1;
+            break;
+        }
+        const double r = 1.0 / sqrt(piv);
+        __syncthreads();
+        if (lane == k) { A[k * PSI_LD + k] = piv * r; rinv[k] = r; }
+        if (lane > k && lane < D) A[lane * PSI_LD + k] *= r;
+        __syncthreads();
+        if (lane > k && lane < D) {
+            const double lik = A[lane * PSI_LD + k];
+            for (int j = k + 1; j <= lane; ++j) A[lane * PSI_LD + j] = fma(-lik, A[j * PSI_LD + k], A[lane * PSI_LD + j]);
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+}
+
+// g = C^-1 diff by forward substitution, the factor read from LDS (every lane the same word: a broadcast); |g|^2 returned
+template <int DCAP>
+__device__ __forceinline__ double psi_solve(double (&g)[DCAP], const double (&diff)[DCAP], const double* A, const double* rinv, int D) {
+    double q = 0.0;
+#pragma unroll
+    for (int i = 0; i < DCAP; ++i) {
+        g[i] = 0.0;
+        if (i < D) {
+            double s = diff[i];
+#pragma unroll
+            for (int j = 0; j < i; ++j) s = fma(-A[i * PSI_LD + j], g[j], s);
+            g[i] = s * rinv[i];
+            q = fma(g[i], g[i], q);
+        }
+    }
+    return q;
+}
+
+// Per node (one wavefront each; grid = the nodes of this chunk): the two factors, the two determinant factors, g of both for every
+// inducing input, Psi1 and, where wanted, the :out mean Psi1' mu^(o).
+//   mean D x nc, cov D x D x nc or null (S = 0), w nc node weights or null (1): pointers at the chunk's first node
+//   G2   [nc][D][Mp]   g of Lambda + 2 S, rows m >= M zero                                  (null: no Psi2 wanted)
+//   cw   [nc]          w_t prod_d(ell_d / C_dd) of Lambda + 2 S                               (with G2)
+//   psi1 [nc][M]       (null: not wanted);   out_mean [d_out][ld_out] at column t (null: not wanted), mu [d_out][M]
+//   bad  [nc]          1 where a factorisation failed (the node's outputs are then not written)
+template <int DCAP>
+__global__ void __launch_bounds__(64) k_psi_prep(const double* __restrict__ Xu, const double* __restrict__ mean,
+                                                 const double* __restrict__ cov, const double* __restrict__ w, PsiKern kp,
+                                                 double* __restrict__ G2, double* __restrict__ cw, double* __restrict__ psi1,
+                                                 const double* __restrict__ mu, double* __restrict__ out_mean, int64_t ld_out,
+                                                 int* __restrict__ bad, int M, int Mp, int D, int d_out) {
+    __shared__ double A1[MAXD * PSI_LD], A2[MAXD * PSI_LD], r1[MAXD], r2[MAXD], mt[MAXD];
+    __shared__ int failed;
+    const int lane = threadIdx.x;
+    const int64_t t = blockIdx.x;
+    if (lane == 0) failed = 0;
+    if (lane < D) mt[lane] = mean[(size_t)t * D + lane];
+    __syncthreads();
+    const double* S = cov ? cov + (size_t)t * D * D : nullptr;
+    psi_factor(A1, r1, &failed, S, kp, 1.0, D, lane);
+    psi_factor(A2, r2, &failed, S, kp, 2.0, D, lane);
+    if (failed) {                                             // (uniform)
+        if (lane == 0) bad[t] = 1;
+        return;
+    }
+    double det1 = 1.0, det2 = 1.0;                            // prod_d ell_d / C_dd, in the order d = 0, 1, ..
+    for (int d = 0; d < D; ++d) { det1 *= kp.ell[d] * r1[d]; det2 *= kp.ell[d] * r2[d]; }
+    if (lane == 0) {
+        bad[t] = 0;
+        if (cw) cw[t] = (w ? w[t] : 1.0) * det2;
+    }
+    double om[MAXO];
+#pragma unroll
+    for (int o = 0; o < MAXO; ++o) om[o] = 0.0;
+    for (int m = lane; m < Mp; m += 64) {
+        double diff[DCAP], g[DCAP];
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d) diff[d] = (d < D && m < M) ? mt[d] - Xu[(size_t)m * D + d] : 0.0;
+        const double q1 = psi_solve<DCAP>(g, diff, A1, r1, D);
+        const double p1 = kp.sigma2 * det1 * exp(-0.5 * q1);
+        if (m < M) {
+            if (psi1) psi1[(size_t)t * M + m] = p1;
+            if (out_mean)
+#pragma unroll
+                for (int o = 0; o < MAXO; ++o)
+                    if (o < d_out) om[o] = fma(p1, mu[(size_t)o * M + m], om[o]);
+        }
+        if (G2) {
+            psi_solve<DCAP>(g, diff, A2, r2, D);
+#pragma unroll
+            for (int d = 0; d < DCAP; ++d)
+                if (d < D) G2[((size_t)t * D + d) * Mp + m] = g[d];
+        }
+    }
+    if (out_mean)
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o)
+            if (o < d_out) {                                  // (uniform) lane l summed m = l, l + 64, .. in order; xor butterfly
+                double v = om[o];
+                for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+                if (lane == 0) out_mean[(size_t)o * ld_out + t] = v;
+            }
+}
+
+// Psi2 partial sums.  The node axis 0 .. T of the CALL is cut into `nranges` contiguous ranges of `range_len` nodes -- a function of
+// T and M alone (host: psi_ranges), never of the chunking -- and workgroup (lower tile, range) adds its range's nodes IN ORDER to
+// the range's own 64 x 64 accumulator tile acc[range][tile][j][i]: a chunk that ends inside a range leaves the tile in memory and the
+// next chunk's launch picks it up, so every accumulator sees the same additions in the same order whatever the chunk size.
+// Thread (ti, tj) of the 16 x 16 owns the entries (ti + 16 a, tj + 16 b); g of the tile's row and column inducing inputs is staged
+// in LDS, PSI_STAGE / D nodes per block.  t0, nc: the chunk's first node and node count; G2 / cw are the chunk's.  r0: first range
+// of this launch (grid.y covers the ranges that meet the chunk).
+constexpr int PSI_STAGE = 32;               // LDS rows (node x dimension) per stage
+__global__ void __launch_bounds__(256) k_psi2_accumulate(const double* __restrict__ G2, const double* __restrict__ cw,
+                                                         double* __restrict__ acc, int64_t t0, int64_t nc, int64_t range_len,
+                                                         int r0, int ntiles, int Mp, int D) {
+    __shared__ double gi[PSI_STAGE * TB], gj[PSI_STAGE * TB], cs[PSI_STAGE];
+    const int tid = threadIdx.x, ti = tid & 15, tj = tid >> 4;       // (ti fastest: the tile's loads and stores run along its columns)
+    int I, J;
+    tile_from_index((int)blockIdx.x, I, J);
+    const int r = r0 + (int)blockIdx.y;
+    const int64_t lo = r * range_len > t0 ? r * range_len : t0;
+    const int64_t hi = (r + 1) * range_len < t0 + nc ? (r + 1) * range_len : t0 + nc;
+    if (lo >= hi) return;                                     // (uniform)
+    double* tile = acc + ((size_t)r * ntiles + blockIdx.x) * (TB * TB);
+    double a[4][4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) a[x][y] = tile[(size_t)(tj + 16 * y) * TB + ti + 16 * x];
+    const int per = PSI_STAGE / D;                            // nodes per stage (D <= 32: at least one)
+    for (int64_t tb = lo; tb < hi; tb += per) {
+        const int nn = (int)(hi - tb < per ? hi - tb : per);
+        __syncthreads();
+        for (int e = tid; e < nn * D * TB; e += 256) {
+            const int q = e >> 6, i = e & 63;
+            const double* row = G2 + ((size_t)(tb - t0) * D + q) * Mp;
+            gi[q * TB + i] = row[I * TB + i];
+            gj[q * TB + i] = row[J * TB + i];
+        }
+        if (tid < nn) cs[tid] = cw[tb - t0 + tid];
+        __syncthreads();
+        for (int n = 0; n < nn; ++n) {
+            double s[4][4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) s[x][y] = 0.0;
+            for (int d = 0; d < D; ++d) {
+                const double* pi = gi + (n * D + d) * TB;
+                const double* pj = gj + (n * D + d) * TB;
+                double vi[4], vj[4];
+#pragma unroll
+                for (int x = 0; x < 4; ++x) { vi[x] = pi[ti + 16 * x]; vj[x] = pj[tj + 16 * x]; }
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+#pragma unroll
+                    for (int y = 0; y < 4; ++y) { const double u = vi[x] + vj[y]; s[x][y] = fma(u, u, s[x][y]); }
+            }
+            const double c = cs[n];
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) a[x][y] = fma(c, exp(-0.25 * s[x][y]), a[x][y]);
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) tile[(size_t)(tj + 16 * y) * TB + ti + 16 * x] = a[x][y];
+}
+
+// Psi2 = the ranges' accumulators summed in the order 0, 1, .. times the node-independent factor sigma2^2 exp(-1/4 |z_m - z_m'|^2 /
+// ell^2), written to both mirror images of a lower tile (out: Mp x Mp column-major; rows and columns >= M are set to zero).  A
+// diagonal tile's entries (i, j) and (j, i) are the same sums of the same numbers -- u + v and (a - b)^2 do not depend on the order of
+// their operands -- so Psi2 is exactly symmetric.  grid = lower tiles.  stamps, when given, is the sweep's phase stamp to close.
+__global__ void __launch_bounds__(256) k_psi2_finish(const double* __restrict__ acc, const double* __restrict__ Xu, PsiKern kp,
+                                                     double* __restrict__ out, int nranges, int ntiles, int M, int Mp, int D,
+                                                     int64_t* stamps) {
+    int I, J;
+    tile_from_index((int)blockIdx.x, I, J);
+    for (int e = threadIdx.x; e < TB * TB; e += 256) {
+        const int j = e >> 6, i = e & 63, gi = I * TB + i, gj = J * TB + j;
+        double v = 0.0;
+        if (gi < M && gj < M) {
+            double s = 0.0;
+            for (int r = 0; r < nranges; ++r) s += acc[((size_t)r * ntiles + blockIdx.x) * (TB * TB) + e];
+            double q = 0.0;
+            for (int d = 0; d < D; ++d) {
+                const double u = (Xu[(size_t)gi * D + d] - Xu[(size_t)gj * D + d]) / kp.ell[d];
+                q = fma(u, u, q);
+            }
+            v = kp.sigma2 * kp.sigma2 * exp(-0.25 * q) * s;
+        }
+        out[(size_t)gj * Mp + gi] = v;
+        if (I != J) out[(size_t)gi * Mp + gj] = v;
+    }
+    stamp_exit(stamps);
+}
+
+// B = sum_t Psi1_t y_t' of the exact local phase (B: [d_out][Mp], y: T x d_out column-major, psi1: [T][M]): one thread per
+// (inducing input, output), the nodes in the order 0, 1, .. T - 1; rows >= M are set to zero.
+__global__ void __launch_bounds__(256) k_psi_b(const double* __restrict__ psi1, const double* __restrict__ y, double* __restrict__ B,
+                                               int64_t T, int M, int Mp, int d_out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= Mp * d_out) return;
+    const int m = e % Mp, o = e / Mp;
+    double s = 0.0;
+    if (m < M)
+        for (int64_t t = 0; t < T; ++t) s = fma(psi1[(size_t)t * M + m], y[(size_t)o * T + t], s);
+    B[(size_t)o * Mp + m] = s;
+}
+
 }  // namespace sgp

@@ -35,6 +35,37 @@ class SphericalRadialCubature:
         return np.stack(pts), w
 
 
+class ExactSE:
+    """Marker method with no points: the Psi-statistics of a Gaussian input are taken in closed form on the device
+    (`SGPDevice.psi_stats` / `sweep_local_psi`), which exists for the SE / ARD kernel only.  `multisgp.sweep`, `rule_v`,
+    `rule_out` / `rule_out_batch` and UniSGP's uncertain-input `:v` / `:out` pair dispatch on it; the `:in` closure and its
+    products stay on cubature points (they are not expectations of the kernel under q(x_in))."""
+
+    def points_weights(self, m, P):
+        raise TypeError("ExactSE has no cubature points: the rules that accept it use the closed-form Psi-statistics")
+
+
+def is_exact(method) -> bool:
+    return isinstance(method, ExactSE)
+
+
+def gaussian_inputs(q_ins, D: int):
+    """Means (T, D) and covariances (T, D, D) of a list of inputs for the closed-form calls; a PointMass input has S = 0."""
+    means, covs = np.zeros((len(q_ins), D)), np.zeros((len(q_ins), D, D))
+    for t, q in enumerate(q_ins):
+        means[t] = np.asarray(q.mean(), dtype=np.float64).ravel()
+        if type(q).__name__ == "PointMass":
+            continue
+        P = np.asarray(q.mean_cov()[1] if hasattr(q, "mean_cov") else q.var(), dtype=np.float64)
+        covs[t] = P.reshape(D, D) if P.size == D * D else np.diag(np.broadcast_to(P.ravel(), (D,)))
+    return means, covs
+
+
+def require_se(kernel_family_name: str) -> None:
+    if str(kernel_family_name).lower() != "se":
+        raise ValueError(f"ExactSE: the closed-form Psi-statistics exist for the SE kernel only, not {kernel_family_name!r}")
+
+
 def ghcubature(p: int) -> GaussHermiteCubature:
     return GaussHermiteCubature(p)
 

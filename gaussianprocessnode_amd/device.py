@@ -345,6 +345,43 @@ class SGPDevice:
                                               ptr(mu), ptr(mean), ptr(points)), "sgp_out_message")
         return (mean.T.copy(), points.T.copy()) if want_points else mean.T.copy()
 
+    def _node_gaussians(self, what: str, mean, cov):
+        """Gaussian inputs as the ABI takes them: means (T, D) contiguous, covariances (T, D, D) (symmetric: row- and column-major
+        blocks coincide) or None for S_t = 0."""
+        m = as_f64(np.reshape(mean, (-1, self.D)))
+        T = m.shape[0]
+        S = None if cov is None else as_f64(np.reshape(cov, (T, self.D, self.D)))
+        return m, S, T
+
+    def psi_stats(self, mean, cov=None, node_weight=None, mu_v=None, want_psi1: bool = True, want_psi2: bool = True,
+                  want_out: bool = False):
+        """The closed-form SE Psi-statistics of T Gaussian inputs N(mean[t], cov[t]) (sgp_psi_stats), at the current kernel.
+        mean (T, D); cov (T, D, D) positive semi-definite or None (all zero); node_weight (T,) or None (all 1).  Returns the
+        tuple (psi1 (T, M), psi2 (M, M) = sum_t w_t Psi2_t, out_mean (T, d_out) = Psi1_t' mu_v^(d)) with None for what was not
+        asked for; mu_v: the one given or (None) the handle's current posterior mean.  A covariance that is not positive
+        semi-definite at node t raises PosDefException with info = t + 1."""
+        m, S, T = self._node_gaussians("psi_stats", mean, cov)
+        w = None if node_weight is None else as_f64(np.reshape(node_weight, (T,)))
+        mu = None if mu_v is None else as_f64(np.reshape(mu_v, (self.Q,)))
+        psi1 = np.empty((T, self.M)) if want_psi1 else None
+        psi2 = np.empty((self.M, self.M)) if want_psi2 else None
+        out = np.empty((self.d_out, T)) if want_out else None
+        self._check(self._lib.sgp_psi_stats(self._h, ptr(m), ptr(S), T, ptr(w), ptr(mu), ptr(psi1), ptr(psi2), ptr(out)),
+                    "sgp_psi_stats")
+        return psi1, psi2, (None if out is None else out.T.copy())
+
+    def sweep_local_psi(self, mean, cov, y_mean, y_var=None, stream: int = 0):
+        """The local phase of a sweep over the exact statistics of T Gaussian inputs (sgp_sweep_local_psi): mean (T, D), cov
+        (T, D, D) or None, y_mean (T, d_out) (or (T,) for d_out = 1), y_var (T,) or None.  `set_output_cov_sum` may follow, then
+        `sweep_finish`.  The handle holds no data afterwards (`set_data` before the next `sweep`)."""
+        m, S, T = self._node_gaussians("sweep_local_psi", mean, cov)
+        y_cm = self._node_targets(y_mean, T)
+        yv = None if y_var is None else as_f64(np.reshape(y_var, (T,)))
+        self._resident_inputs = None
+        self._check(self._lib.sgp_sweep_local_psi(self._h, ptr(m), ptr(S), ptr(y_cm), ptr(yv), T, C.c_void_p(stream)),
+                    "sgp_sweep_local_psi")
+        self.n = 0
+
     def set_posterior(self, mu_v, Uv):
         """Install an external q(v) (mean and Uv = chol(Sigma_v + mu mu').U) for the per-point outputs (`w_stats`)."""
         mu = as_f64(np.reshape(mu_v, (self.Q,)))

@@ -24,6 +24,7 @@ import numpy as np
 
 from .distributions import (MvNormalMeanCovariance, MvNormalMeanPrecision, MvNormalWeightedMeanPrecision, PointMass,
                             WishartFast)
+from .cubature import gaussian_inputs, is_exact, require_se
 from .meta import MultiSGPMeta, kernel_family, set_engine_kernel
 from .unisgp import load_batch
 
@@ -79,14 +80,20 @@ def sweep(meta: MultiSGPMeta, q_outs: Sequence, q_ins: Sequence, q_w, q_theta: P
     """One VMP update of q(v) from all steps' `:v` messages (GPnode/MultiSGPnode.jl:290-328) folded with the prior.
     Returns the marginal MvNormalMeanCovariance; the Wishart statistics and the energy are then available through
     `rule_w_summed` / `average_energy_summed`."""
-    pts, wts, ys, cov_sum = _expand(meta, q_ins, q_outs)
     W = _mean_W(q_w)
     d_out = W.shape[0]
-    eng = _engine(meta, len(wts), d_out)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    load_batch(eng, pts, ys, None, wts, n_nodes=len(q_ins))
-    if cov_sum is not None:
-        eng.set_output_cov_sum(cov_sum)
+    exact = is_exact(meta.method)
+    if exact:
+        # the statistics in closed form (SGPDevice.sweep_local_psi): the setters first, the local phase reads them
+        require_se(kernel_family(meta.kernel))
+        eng = _engine(meta, 1, d_out)
+    else:
+        pts, wts, ys, cov_sum = _expand(meta, q_ins, q_outs)
+        eng = _engine(meta, len(wts), d_out)
+        load_batch(eng, pts, ys, None, wts, n_nodes=len(q_ins))
+        if cov_sum is not None:
+            eng.set_output_cov_sum(cov_sum)
     set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     if E_logdet_W is None:
         E_logdet_W = q_w.mean_logdet() if hasattr(q_w, "mean_logdet") else float(np.linalg.slogdet(W)[1])
@@ -99,9 +106,28 @@ def sweep(meta: MultiSGPMeta, q_outs: Sequence, q_ins: Sequence, q_w, q_theta: P
         eng.set_prior_precision(prior.W @ prior.m, prior.W)
     else:
         raise TypeError(f"unsupported prior type {type(prior).__name__}")
-    eng.sweep()
+    if exact:
+        means, covs = gaussian_inputs(q_ins, np.asarray(meta.Xu).shape[1])
+        Y = np.stack([np.asarray(q.mean(), dtype=np.float64).ravel() for q in q_outs])
+        eng.sweep_local_psi(means, covs, Y)
+        out_covs = [c for c in map(_cov_of, q_outs) if c is not None]
+        if out_covs:
+            eng.set_output_cov_sum(sum(out_covs))
+        eng.sweep_finish()
+    else:
+        eng.sweep()
     mu, Sigma, _ = eng.posterior(want_uv=False)
     return MvNormalMeanCovariance(mu, Sigma)
+
+
+def _exact_out_means(q_ins, q_v, q_theta, meta, eng):
+    """Psi1_t' mu_v^(d) of every input in closed form (SGPDevice.psi_stats), (T, d_out)."""
+    require_se(kernel_family(meta.kernel))
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    means, covs = gaussian_inputs(q_ins, np.asarray(meta.Xu).shape[1])
+    return eng.psi_stats(means, covs, None, np.asarray(q_v.mean(), dtype=np.float64), want_psi1=False, want_psi2=False,
+                         want_out=True)[2]
 
 
 def rule_w_summed(meta: MultiSGPMeta, prior_nu: float, prior_invscale, n_nodes: int) -> WishartFast:
@@ -120,6 +146,8 @@ def rule_out(q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta) -> MvNormal
     """@rule MultiSGP(:out) (GPnode/MultiSGPnode.jl:90-120): mean_d = Psi1 . mu_v^(d), precision mean(q_w)."""
     W = _mean_W(q_w)
     d_out = W.shape[0]
+    if is_exact(meta.method):
+        return MvNormalMeanPrecision(_exact_out_means([q_in], q_v, q_theta, meta, _engine(meta, 1, d_out))[0], W)
     if isinstance(q_in, PointMass):
         p, w = np.atleast_2d(np.asarray(q_in.mean(), dtype=np.float64)), np.ones(1)
     else:
@@ -141,6 +169,12 @@ def rule_out_batch(q_ins, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta):
     those of the `rule_out` loop up to the order of the node sums (the device's lanes and tree against the host's dot product)."""
     from .unisgp import _rule_out_batch
     W = _mean_W(q_w)
+    if is_exact(meta.method):
+        q_ins = list(q_ins)
+        if not q_ins:
+            return []
+        mean = _exact_out_means(q_ins, q_v, q_theta, meta, _engine(meta, 1, W.shape[0]))
+        return [MvNormalMeanPrecision(mean[t].copy(), W) for t in range(len(q_ins))]
     return _rule_out_batch(
         q_ins, q_v, q_theta, meta,
         points_weights_of=lambda q_in: ((q_in.mean(), np.ones(1)) if isinstance(q_in, PointMass)
@@ -178,15 +212,22 @@ def rule_v(q_out, q_in, q_w, q_theta: PointMass, meta: MultiSGPMeta) -> MvNormal
     """@rule MultiSGP(:v) for ONE step (GPnode/MultiSGPnode.jl:290-328): the message itself, xi = vcat(Psi1 (mu_y' W)_d),
     Lambda = kron(W, Psi2), with Psi1 / Psi2 from the device statistics of that step."""
     W = _mean_W(q_w)
-    pts, wts, ys, _ = _expand(meta, [q_in], [q_out])
     d_out = W.shape[0]
-    eng = _engine(meta, len(wts), d_out)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    load_batch(eng, pts, np.ones((len(wts), d_out)), None, wts, n_nodes=1)
-    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
-    eng.sweep_local()
-    Psi2, B, _ = eng.stats()
-    Psi1 = B[:, 0]
+    if is_exact(meta.method):
+        require_se(kernel_family(meta.kernel))
+        eng = _engine(meta, 1, d_out)
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+        psi1, Psi2, _ = eng.psi_stats(*gaussian_inputs([q_in], np.asarray(meta.Xu).shape[1]))
+        Psi1 = psi1[0]
+    else:
+        pts, wts, ys, _ = _expand(meta, [q_in], [q_out])
+        eng = _engine(meta, len(wts), d_out)
+        load_batch(eng, pts, np.ones((len(wts), d_out)), None, wts, n_nodes=1)
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+        eng.sweep_local()
+        Psi2, B, _ = eng.stats()
+        Psi1 = B[:, 0]
     row = np.asarray(q_out.mean(), dtype=np.float64).ravel() @ W                      # :307
     xi = np.concatenate([Psi1 * row[d] for d in range(d_out)])
     return MvNormalWeightedMeanPrecision(xi, np.kron(W, Psi2))                         # :306

@@ -407,7 +407,7 @@ def _proper_gaussian(q, floor: float = 1e-10):
 
 
 def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, iterations=10, init=None, free_energy=False,
-              rule_out_fn=None):
+              rule_out_fn=None, psi="cubature"):
     """The inner `infer(...)` of the pendulum GP-SSM (experiments/Pendulum_Wishart_2d.ipynb cells 12-16):
         x_0 ~ N(m0, P0);   x_t ~ MultiSGP(x_{t-1}, v, W, theta);   y_t ~ N(x_t, P),   t = 1..T,
         v ~ N(0, v_prior_var I),   W ~ Wishart(nu0, invscale^-1),   mean field q(x_0) .. q(x_T) q(v) q(W).
@@ -429,6 +429,9 @@ def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, it
     This is a schedule of the same messages; ReactiveMP's reactive update order is NOT claimed to be reproduced, and no fixture
     pins it: the notebook's data come from Julia's MersenneTwister(124), so its q(x) cannot be regenerated here.
 
+    psi: "cubature" (default) takes the Psi-statistics of steps 1 and 4 over meta.method's cubature points; "exact" takes them in
+    closed form (`cubature.ExactSE`: `SGPDevice.psi_stats` for step 1, `sweep_local_psi` for step 4; SE kernel only).  Steps 2, 3
+    and 5 are the same either way: the :in closure of step 3 is no expectation of the kernel and stays on cubature points.
     rule_out_fn(q_ins, q_v, q_w, q_theta, meta) replaces step 1's batch function (timing comparisons against the per-node loop).
     Returns (q_x [T + 1], q_v, q_W, free energies [iterations] or [])."""
     from . import multisgp as MS
@@ -447,8 +450,32 @@ def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, it
     q_x = list(q_x)
     v_prior = MvNormalWeightedMeanPrecision(np.zeros(Q), np.eye(Q) / v_prior_var)
     rule_out_fn = rule_out_fn or MS.rule_out_batch
+    if psi not in ("cubature", "exact"):
+        raise ValueError(f"vmp_gpssm: psi must be 'cubature' or 'exact', got {psi!r}")
+
+    run_meta = meta
+    if psi == "exact":
+        # one meta for the whole run whose method is the marker: steps 1 and 4 dispatch on it, step 3 names its own cubature rule.
+        # It shares the caller's engine and hands back the one it ends with.
+        import dataclasses
+        from .cubature import ExactSE
+        run_meta = dataclasses.replace(meta, method=ExactSE())
+    try:
+        return _vmp_gpssm_loop(run_meta, y, q_x, q_v, q_w, q_theta, v_prior, rule_out_fn, int(iterations), free_energy,
+                               (m0, P0), Pobs, Pinv, v_prior_var, w_prior)
+    finally:
+        meta.engine = run_meta.engine
+
+
+def _vmp_gpssm_loop(meta, y, q_x, q_v, q_w, q_theta, v_prior, rule_out_fn, iterations, free_energy, x0_prior, Pobs, Pinv,
+                    v_prior_var, w_prior):
+    """The iterations of `vmp_gpssm` (its docstring numbers the steps) on the meta whose method says how steps 1 and 4 take their
+    Psi-statistics."""
+    from . import multisgp as MS
+    T = len(y)
+    m0, P0 = x0_prior
     fe = []
-    for _ in range(int(iterations)):
+    for _ in range(iterations):
         W = q_w.mean()
         outs = rule_out_fn(q_x[:-1], q_v, q_w, q_theta, meta)                                   # 1
         S = np.linalg.inv(W + Pinv)                                                             # 2 (every out_t carries precision W)
@@ -463,7 +490,7 @@ def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, it
 
 
 def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iterations=10, theta_steps=100, device_paced=True,
-                            v_prior_var=50.0, w_prior=None, optimizer=None, free_energy=True):
+                            v_prior_var=50.0, w_prior=None, optimizer=None, free_energy=True, psi="cubature"):
     """`PerformInference` of experiments/Pendulum_Wishart_2d.ipynb cell 16.  Per epoch: `vmp_gpssm` from the initialisation at
     the current theta (step 1), then `optimize_theta_multi` -- theta_steps AdaMax steps on neg_log_backwardmess_multi -- at the held
     q(x), q(v), q(W), with the targets mean(q(x_t)) and the inputs q(x_{t-1}), t = 1..T, as the notebook passes them (step 2).
@@ -475,7 +502,7 @@ def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iteratio
     fe_values, post = [], None
     for _ in range(int(epochs)):
         q_x, q_v, q_w, fe = vmp_gpssm(theta, y, meta, P=P, x0_prior=x0_prior, v_prior_var=v_prior_var, w_prior=w_prior,
-                                      iterations=vmp_iterations, free_energy=free_energy)
+                                      iterations=vmp_iterations, free_energy=free_energy, psi=psi)
         if fe:
             fe_values.append(fe[-1])
         y_data = np.stack([q.m for q in q_x[1:]])

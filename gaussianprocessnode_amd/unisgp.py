@@ -25,6 +25,7 @@ import numpy as np
 
 from .distributions import (GammaShapeRate, MvNormalMeanCovariance, MvNormalMeanPrecision,
                             MvNormalWeightedMeanPrecision, NormalMeanPrecision, NormalMeanVariance, PointMass)
+from .cubature import gaussian_inputs, is_exact, require_se
 from .meta import UniSGPMeta, kernel_family, set_engine_kernel
 
 LOG2PI = math.log(2.0 * math.pi)
@@ -112,8 +113,13 @@ def rule_v(q_out, q_in, q_w, q_theta, meta: UniSGPMeta) -> BufferUniSGP:
         # statistics over the cubature points with their weights; the rule also adds 1e-8 I to every Psi2 (:135)
         if meta.method is None:
             raise ValueError("UniSGP(:v) with an uncertain input needs meta.method (a cubature rule)")
-        pts, wts = meta.method.points_weights(q_in.mean(), q_in.var())
-        x = (np.asarray(pts, dtype=np.float64), np.asarray(wts, dtype=np.float64))
+        if is_exact(meta.method):
+            # closed-form statistics: the node keeps its Gaussian, `prod` hands all of them to SGPDevice.sweep_local_psi
+            require_se(kernel_family(meta.kernel))
+            x = gaussian_inputs([q_in], meta.Xu.shape[1])
+        else:
+            pts, wts = meta.method.points_weights(q_in.mean(), q_in.var())
+            x = (np.asarray(pts, dtype=np.float64), np.asarray(wts, dtype=np.float64))
         meta._batch["uncertain"] = True
     else:
         x = np.atleast_1d(np.asarray(q_in.mean(), dtype=np.float64))
@@ -152,7 +158,14 @@ def prod(left, right: BufferUniSGP):
     # ---- the N-th message: one device sweep for the whole batch
     uncertain = bool(meta._batch.get("uncertain"))
     extra_precision = 0.0
-    if uncertain:
+    exact = uncertain and is_exact(meta.method)
+    if exact:
+        X = np.concatenate([p[0][0] for p in meta._pending])               # the means (N, D) ...
+        covs = np.concatenate([p[0][1] for p in meta._pending])            # ... and covariances (N, D, D)
+        y = np.array([p[1] for p in meta._pending])
+        vy = wts = None
+        extra_precision = 1e-8 * meta._batch["w"] * meta.N
+    elif uncertain:
         X = np.concatenate([p[0][0] for p in meta._pending])
         wts = np.concatenate([p[0][1] for p in meta._pending])
         y = np.concatenate([np.full(len(p[0][1]), p[1]) for p in meta._pending])
@@ -165,7 +178,8 @@ def prod(left, right: BufferUniSGP):
         wts = None
     eng = _engine(meta, len(y))
     sigma2, ell = meta.kernel(meta._batch["theta"])
-    load_batch(eng, X, y, vy, wts, n_nodes=meta.N)
+    if not exact:
+        load_batch(eng, X, y, vy, wts, n_nodes=meta.N)
     set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
     eng.set_noise([[meta._batch["w"]]], meta._batch["E_logw"])
     prior = meta._prior
@@ -185,7 +199,11 @@ def prod(left, right: BufferUniSGP):
         eng.set_prior_precision(prior.W @ prior.m, prior.W)
     else:
         raise TypeError(f"unsupported prior type {type(prior).__name__}")
-    eng.sweep()
+    if exact:
+        eng.sweep_local_psi(X, covs, y)
+        eng.sweep_finish()
+    else:
+        eng.sweep()
     mu_v, Sigma_v, Uv = eng.posterior()            # raises PosDefException like cholesky() in the reference
     meta.Uv = Uv                                   # :69
     meta.KuuL = eng.kuu_chol()
@@ -237,6 +255,9 @@ def _node_I(q_out, q_in, mu_v, Uv, theta, meta: UniSGPMeta, jitter_psi2: float, 
     like the reference (GPnode/UniSGPnode.jl:186-190)."""
     if meta.method is None:
         raise ValueError("an uncertain input needs meta.method (a cubature rule)")
+    if is_exact(meta.method):
+        raise NotImplementedError("ExactSE covers UniSGP's uncertain-input :v / :out pair; the per-node :w rule and energy need a "
+                                  "cubature rule (the summed forms, rule_w_summed, read the sweep's scalars and work with either)")
     pts, wts = meta.method.points_weights(q_in.mean(), q_in.var())
     wts = np.asarray(wts, dtype=np.float64)
     mu_y = float(q_out.mean())
@@ -292,6 +313,8 @@ def rule_w_summed(meta: UniSGPMeta, prior: GammaShapeRate) -> GammaShapeRate:
 # :out  (GPnode/UniSGPnode.jl:96-104)
 # ------------------------------------------------------------------------------------------------
 def rule_out(q_in, q_v, q_w, q_theta, meta: UniSGPMeta) -> NormalMeanPrecision:
+    if not _is_pointmass(q_in) and is_exact(meta.method):
+        return NormalMeanPrecision(float(_exact_out_means([q_in], q_v, q_theta, meta)[0, 0]), _mean_w(q_w))
     if not _is_pointmass(q_in):
         # GPnode/UniSGPnode.jl:85-93: Psi1 = sum_s omega_s K(Xu, x_s), mean = Psi1 . mu_v
         pts, wts = meta.method.points_weights(q_in.mean(), q_in.var())
@@ -299,6 +322,17 @@ def rule_out(q_in, q_v, q_w, q_theta, meta: UniSGPMeta) -> NormalMeanPrecision:
         return NormalMeanPrecision(float(np.dot(wts, f)), _mean_w(q_w))
     m = predict(np.atleast_2d(np.asarray(q_in.mean(), dtype=np.float64)), q_v, q_theta, meta)[0]
     return NormalMeanPrecision(float(m), _mean_w(q_w))
+
+
+def _exact_out_means(q_ins, q_v, q_theta, meta: UniSGPMeta):
+    """Psi1_t . mu_v of every input in closed form (SGPDevice.psi_stats), (T, 1); a PointMass input has S = 0."""
+    require_se(kernel_family(meta.kernel))
+    eng = _engine(meta, 1)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    means, covs = gaussian_inputs(q_ins, meta.Xu.shape[1])
+    return eng.psi_stats(means, covs, None, np.asarray(q_v.mean(), dtype=np.float64), want_psi1=False, want_psi2=False,
+                         want_out=True)[2]
 
 
 def _rule_out_batch(q_ins, q_v, q_theta, meta, *, points_weights_of, engine_of, make_message):
@@ -324,6 +358,10 @@ def rule_out_batch(q_ins, q_v, q_w, q_theta, meta: UniSGPMeta):
     is one point of weight 1, a Gaussian one meta.method's cubature points (GPnode/UniSGPnode.jl:85-93).  Returns a list of
     NormalMeanPrecision(mean_t, mean(q_w)); the values are those of the `rule_out` loop up to the order of the node sums."""
     w_bar = _mean_w(q_w)
+    if is_exact(meta.method):
+        q_ins = list(q_ins)
+        mean = _exact_out_means(q_ins, q_v, q_theta, meta) if q_ins else []
+        return [NormalMeanPrecision(float(mean[t, 0]), w_bar) for t in range(len(q_ins))]
     return _rule_out_batch(
         q_ins, q_v, q_theta, meta,
         points_weights_of=lambda q_in: ((q_in.mean(), np.ones(1)) if _is_pointmass(q_in)

@@ -152,13 +152,13 @@ int sgp_sweep(sgp_handle* h, void* stream);                 /* local + [all-redu
 /* What a sgp_sweep does on a handle created with SGP_FLAG_REUSE_STATS (both FULL, always, without the flag):
  *   SGP_SWEEP_FULL     the whole sweep above: after sgp_set_data, sgp_set_inducing, a changed kernel value (sigma2, a lengthscale,
  *                      the jitter, the kernel family), sgp_theta_objective at another theta, sgp_train_*, sgp_time_kernel, sgp_bind_stats,
- *                      sgp_set_allreduce / sgp_use_rccl, a direct sgp_sweep_local, or a full sweep whose K_uu factorisation failed or
+ *                      sgp_set_allreduce / sgp_use_rccl, a direct sgp_sweep_local or sgp_sweep_local_psi, or a full sweep whose K_uu factorisation failed or
  *                      whose stream hand-off gave up;
  *   SGP_SWEEP_TARGETS  after sgp_set_targets or sgp_set_output_cov_sum: B and the data scalars from the resident K_uf (with an
  *                      all-reduce hook: ONE call, of the exchange buffer's tail [B | scalars], count = Mp d_out + SGP_S_COUNT +
  *                      d_out^2 on every rank), then phase 2;
  *   SGP_SWEEP_REUSED   otherwise (sgp_set_noise, sgp_set_prior, sgp_carry_posterior, sgp_set_posterior, sgp_w_stats, sgp_predict,
- *                      sgp_predict_var, sgp_in_message, sgp_out_message):
+ *                      sgp_predict_var, sgp_in_message, sgp_out_message, sgp_psi_stats):
  *                      phase 2 alone over the resident statistics; no K_uu chain, no hook call.
  * The results of TARGETS and REUSED sweeps are bitwise those of a full sweep.  sgp_sweep_local / sgp_sweep_finish keep their
  * meaning (a full local phase, phase 2).
@@ -336,6 +336,55 @@ int sgp_in_message_grad(sgp_handle* h, const double* X, int64_t n, const int64_t
  * partial sums meet in a fixed tree, no atomics.  Repeated calls agree bitwise, and so do calls that differ in the chunk size. */
 int sgp_out_message(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes, const double* weights,
                     const double* mu_v, double* mean, double* point_mean);
+
+/* sgp_psi_stats: the Psi-statistics of many Gaussian inputs x_t ~ N(m_t, S_t) in CLOSED FORM -- what the rules of MultiSGP
+ * (GPnode/MultiSGPnode.jl:11-35, approximate_kernel_expectation!) and of UniSGP with a Gaussian input (GPnode/UniSGPnode.jl:11-33)
+ * approximate with cubature points.  SGP_KERNEL_SE only.  With Lambda = diag(ell^2) (an isotropic ell expanded) and z_m the m-th
+ * inducing input, at the CURRENT kernel (the last sgp_set_kernel):
+ *     Psi1_t[m]     = sigma2 |I + Lambda^-1 S_t|^-1/2 exp(-1/2 (m_t - z_m)' (Lambda + S_t)^-1 (m_t - z_m))
+ *     Psi2_t[m, m'] = sigma2^2 |I + 2 Lambda^-1 S_t|^-1/2 exp(-1/4 (z_m - z_m')' Lambda^-1 (z_m - z_m')
+ *                                                           - (m_t - zb)' (Lambda + 2 S_t)^-1 (m_t - zb)),   zb = (z_m + z_m') / 2
+ * evaluated through the Cholesky factors Lambda + c S_t = C C' (c = 1, 2): with g_tm = C^-1 (m_t - z_m) the quadratic forms are
+ * |g_tm|^2 and 1/4 |g_tm + g_tm'|^2 and the determinant factor is prod_d ell_d / C_dd; every exponent is <= 0.
+ * mean is D x n_nodes (one node per column, as the points of sgp_predict); cov is D x D x n_nodes, every block symmetric positive
+ * SEMI-definite (its lower triangle is read; the zero matrix is legal), or NULL: every S_t = 0.  Outputs, any of them may be NULL:
+ *     psi1      M x n_nodes column-major, psi1[m + M t] = Psi1_t[m]
+ *     psi2      M x M, sum_t w_t Psi2_t with w = node_weight (n_nodes entries; NULL: every weight 1), exactly symmetric
+ *     out_mean  n_nodes x d_out column-major, out_mean[t, d] = Psi1_t' mu_v^(d): the :out message means; mu_v (host, d_out*M,
+ *               output-major) or NULL for the handle's current posterior, exactly as sgp_predict resolves it
+ * SGP_ERR_ARG: a family other than SGP_KERNEL_SE; no inducing inputs or kernel; a non-finite mean or cov; a non-finite or negative
+ * node_weight where psi2 is wanted; NULL mu_v without a posterior in the handle where out_mean is wanted; psi1, psi2 and out_mean all
+ * NULL; an open sgp_train_* run.  A node t whose Lambda + S_t or Lambda + 2 S_t is not positive definite (S_t was not positive
+ * semi-definite): the return value is t + 1 > 0 and sgp_last_error names the node (the first such node).  n_nodes = 0 returns 0,
+ * nothing done.  K_uu is never formed or factorised.
+ * Blocking.  Everything is formed in call scratch and the nodes go through in chunks (SGP_PREDICT_CHUNK), as in sgp_out_message:
+ * nothing the sweep keeps is written (sgp_sweep_kind and the theta objective are unaffected).  One wavefront per node forms the two
+ * factors, g and Psi1; Psi2 is summed over 64 x 64 tiles of the lower triangle and mirrored on store.  The node axis is cut into
+ * ranges that depend on n_nodes and M alone; a range's nodes are added in order, the ranges' sums are added in order, no atomics:
+ * repeated calls agree bitwise, and so do calls that differ in the chunk size. */
+int sgp_psi_stats(sgp_handle* h, const double* mean /* D x T */, const double* cov /* D x D x T, NULL = all zero */,
+                  int64_t n_nodes, const double* node_weight /* T or NULL = 1 */, const double* mu_v /* Q or NULL */,
+                  double* psi1 /* M x T, may be NULL */, double* psi2 /* M x M = sum_t w_t Psi2_t, may be NULL */,
+                  double* out_mean /* T x d_out = Psi1_t' mu_v^(d), may be NULL */);
+
+/* sgp_sweep_local_psi: the local phase of a sweep whose statistics are the exact ones of sgp_psi_stats -- what a direct
+ * sgp_sweep_local does, in the plain order, for n_nodes nodes with inputs x_t ~ N(m_t, S_t) and targets y_t: the K_uu chain, and the
+ * packed statistics [Psi2 | B | scalars (+ Ryy)] with Psi2 = sum_t Psi2_t, B = sum_t Psi1_t y_t', S_W = S_N = n_nodes and S_YY / Ryy
+ * formed from y_mean (n_nodes x d_out column-major) and y_var (n_nodes or NULL; d_out = 1 only) by the host code of sgp_set_data.
+ * mean and cov as in sgp_psi_stats.  sgp_set_output_cov_sum may follow; then sgp_sweep_finish, unchanged: sgp_get_posterior,
+ * sgp_get_scalars, sgp_get_stats, sgp_get_wishart_invscale and sgp_carry_posterior give what they give after any sweep.
+ * The call first forms the statistics in call scratch on `stream` and waits for them (it reports an indefinite node); only then
+ * does it touch the handle: the K_uu chain and the copies into the statistics buffer are enqueued and the call returns.  A call
+ * that fails -- a refusal, an indefinite node, an allocation -- leaves the handle's data, statistics and q(v) as they were.  Every
+ * exact sweep is a full one.
+ * Afterwards the resident statistics are exact-Psi statistics and the handle holds NO data, until the next sgp_set_data: the calls
+ * that need resident points or K_uf -- sgp_w_stats, sgp_theta_objective, sgp_theta_descend, sgp_set_targets -- return SGP_ERR_ARG
+ * with a message that says so, sgp_sweep asks for sgp_set_data, and the sgp_sweep after that sgp_set_data is a full sweep.
+ * SGP_ERR_ARG: what sgp_psi_stats refuses of the kernel, the inputs and the handle's state; n_nodes < 1; y_var with d_out > 1; an
+ * installed all-reduce hook (data-sharded exact statistics are not supported).  An indefinite node t returns t + 1 as in
+ * sgp_psi_stats. */
+int sgp_sweep_local_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean /* T x d_out */,
+                        const double* y_var /* T or NULL, d_out = 1 */, int64_t n_nodes, void* stream);
 
 /* sgp_wait: returns when everything this handle has enqueued -- on its own streams or the caller's -- has finished: what a caller
  * does between `infer` calls when it wants the sweep to be over but none of its results yet.  The library's streams are polled

@@ -214,6 +214,27 @@ function out_message!(h::Handle, X::Matrix{Float64}, node_start::Vector{Int64}, 
     return points ? (mean, point_mean) : mean
 end
 
+# the closed-form SE Psi-statistics of Gaussian inputs (include/sgp_hip.h, sgp_psi_stats): m is D × T, S is D × D × T or nothing
+# (every S_t = 0), w === nothing: every node weight 1, μ_v === nothing: the handle's current posterior mean.  Returns (Ψ1 M × T,
+# Ψ2 M × M = Σ_t w_t Ψ2_t, out_mean T × d_out).  Written blind like the rest of this file, never executed; a node whose S_t is not
+# positive semi-definite comes back as status t + 1, which `check` rethrows as PosDefException(t + 1).
+function psi_stats!(h::Handle, m::Matrix{Float64}, S = nothing, w = nothing, μ_v = nothing)
+    T = size(m, 2)
+    Ψ1 = zeros(h.m, T); Ψ2 = zeros(h.m, h.m); out = zeros(T, h.d_out)
+    check(ccall((:sgp_psi_stats, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, m, S === nothing ? C_NULL : Array{Float64,3}(S), T, w === nothing ? C_NULL : Vector{Float64}(w),
+                μ_v === nothing ? C_NULL : Vector{Float64}(μ_v), Ψ1, Ψ2, out), h.ptr)
+    return Ψ1, Ψ2, out
+end
+# the local phase of a sweep over those exact statistics (sgp_sweep_local_psi): y is T × d_out, y_var T or nothing; sweep_finish!
+# follows.  The handle holds no data afterwards (set_data! before the next sweep!).
+sweep_local_psi!(h::Handle, m::Matrix{Float64}, S, y::Matrix{Float64}, y_var = nothing; stream = C_NULL) =
+    check(ccall((:sgp_sweep_local_psi, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                h.ptr, m, S === nothing ? C_NULL : Array{Float64,3}(S), y, y_var === nothing ? C_NULL : Vector{Float64}(y_var),
+                size(m, 2), stream), h.ptr)
+
 # q(v) installed from outside for the per-point outputs (include/sgp_hip.h, sgp_set_posterior): mean and the upper factor
 # Uv = chol(Σ_v + μ μ').U, column-major Q × Q -- a Julia Matrix as it is
 set_posterior!(h::Handle, μ_v::Vector{Float64}, Uv::Matrix{Float64}) =

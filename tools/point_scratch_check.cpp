@@ -1,8 +1,8 @@
 // Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over grids of shapes, the
-// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad and layout_out_message hand out are
+// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message and layout_psi hand out are
 // pairwise disjoint at the sizes their consumers need (stated here independently of the layout functions), every piece starts a
 // multiple of Carver::ALIGN doubles from the base, pass 2 hands out the total pass 1 summed and the last piece ends there.  The
-// panel layouts are checked over one allocation of the grid's largest total; the two mean-only layouts get an allocation of
+// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts and layout_psi get an allocation of
 // exactly their total per shape and every piece is written end to end, so that the sanitizer sees a write past it.  No GPU:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o tools/point_scratch_check tools/point_scratch_check.cpp
 //   (or any C++17 compiler with -fsanitize=address,undefined) && tools/point_scratch_check
@@ -162,6 +162,42 @@ long mean_only_sweep() {
                 }
     return shapes;
 }
+
+// sgp_psi_stats / sgp_sweep_local_psi over their grid, each shape in an allocation of its own: the outputs wanted or not, the
+// accumulator tiles of psi_ranges (about 1024 / lower tiles, at least 8 nodes each), with and without mu_v and targets
+long psi_sweep() {
+    long shapes = 0;
+    for (int M : {1, 48, 65, 130})
+        for (int D : {1, 2, 5, 32})
+            for (int dout : {1, 2, 4})
+                for (int64_t n : {1, 63, 65, 300, 1400})
+                    for (int64_t chunk : {(int64_t)64, (n + 63) / 64 * 64})
+                        for (int opt = 0; opt < 8; ++opt) {
+                            const bool cov = opt & 1, psi1 = opt & 2, psi2 = opt & 4, sweep = opt == 7;
+                            const int Mp = (M + TB - 1) / TB * TB, T = Mp / TB, ntiles = T * (T + 1) / 2;
+                            const int64_t want = std::min<int64_t>((n + 7) / 8, std::max(1, 1024 / ntiles)), len = (n + want - 1) / want;
+                            const size_t acc = psi2 ? (size_t)((n + len - 1) / len) * ntiles : 0;
+                            const size_t mu = (opt & 2) && !sweep ? (size_t)dout * M : 0, y = sweep ? (size_t)n * dout : 0;
+                            const PointShape s{Mp, 0, T, D, dout, 0, std::min(chunk, (n + 63) / 64 * 64), n, n};
+                            check("psi", s, mu, nullptr, 0, true, [&](Carver& c) {
+                                PsiScratch b;
+                                layout_psi(c, s, M, cov, psi1, acc, psi2, mu, y, &b);
+                                const size_t nn = (size_t)n, ch = (size_t)s.chunk;
+                                const std::vector<Piece> all = {
+                                    {"Mean", b.Mean, nn * D * d}, {"Cov", b.Cov, cov ? nn * D * D * d : 0}, {"Wt", b.Wt, nn * d},
+                                    {"Bad", b.Bad, nn * sizeof(int)}, {"Psi1", b.Psi1, psi1 ? nn * M * d : 0},
+                                    {"OutMean", b.OutMean, nn * dout * d}, {"G2", b.G2, acc ? ch * D * Mp * d : 0}, {"Cw", b.Cw, ch * d},
+                                    {"Acc", b.Acc, acc * TB * TB * d}, {"Psi2", b.Psi2, psi2 ? (size_t)Mp * Mp * d : 0}, {"Mu", b.Mu, mu * d},
+                                    {"Y", b.Y, y * d}, {"Bs", b.Bs, y ? (size_t)Mp * dout * d : 0}};
+                                std::vector<Piece> p;
+                                for (const Piece& q : all)
+                                    if (q.bytes) p.push_back(q);                  // (a piece that is not wanted has no extent)
+                                return p;
+                            });
+                            ++shapes;
+                        }
+    return shapes;
+}
 }  // namespace
 
 int main() {
@@ -173,7 +209,8 @@ int main() {
     const long panel = panel_sweep(base, largest, &again);
     std::free(base);
     const long mean_only = mean_only_sweep();
-    std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes: %ld failure(s)\n", panel, largest,
-                mean_only, failures);
+    const long psi = psi_sweep();
+    std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes, %ld psi shapes: %ld failure(s)\n", panel,
+                largest, mean_only, psi, failures);
     return failures ? 1 : 0;
 }

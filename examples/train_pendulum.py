@@ -54,7 +54,7 @@ def inducing_inputs():
     return np.stack([xu1, xu2], axis=1)
 
 
-def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cubature"):
+def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cubature", theta_psi="cubature"):
     from gaussianprocessnode_amd.cubature import srcubature
     from gaussianprocessnode_amd.meta import SMSE, MultiSGPMeta, SEARDKernel, softplus
     from gaussianprocessnode_amd.train import perform_inference_gpssm, vmp_gpssm
@@ -68,7 +68,7 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
     try:
         t0 = time.perf_counter()
         theta, fe, _ = perform_inference_gpssm(theta0, y, meta, P=P, x0_prior=x0_prior, epochs=epochs, device_paced=device_paced,
-                                                psi=psi)
+                                                psi=psi, theta_psi=theta_psi)
         t_train = time.perf_counter() - t0
         t0 = time.perf_counter()
         q_x, _, q_w, fe_smooth = vmp_gpssm(theta, y, meta, P=P, x0_prior=x0_prior, iterations=30, free_energy=True, psi=psi)
@@ -79,7 +79,7 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
     est = np.stack([q.m for q in q_x[1:]])
     return {
         "experiment": "pendulum GP-SSM PerformInference (experiments/Pendulum_Wishart_2d.ipynb)",
-        "epochs": epochs, "nodes": nodes, "M": int(len(Xu)), "pacing": "device" if device_paced else "host", "seed": seed, "psi": psi,
+        "epochs": epochs, "nodes": nodes, "M": int(len(Xu)), "pacing": "device" if device_paced else "host", "seed": seed, "psi": psi, "theta_psi": theta_psi,
         "train_seconds": t_train, "smoothing_seconds": t_smooth,
         "smse": [SMSE(x_true[:, k], est[:, k]) for k in range(2)],
         "smse_observations": [SMSE(x_true[:, k], y[:, k]) for k in range(2)],
@@ -99,5 +99,7 @@ if __name__ == "__main__":
     ap.add_argument("--host-paced", action="store_true", help="set_kernel + sgp_theta_objective + AdaMax in NumPy per theta step")
     ap.add_argument("--psi", choices=("cubature", "exact"), default="cubature",
                     help="Psi-statistics of the :out and :v steps: srcubature points, or the SE closed form (sgp_psi_stats)")
+    ap.add_argument("--theta-psi", choices=("cubature", "exact"), default="cubature",
+                    help="statistics of the theta phase: srcubature points, or the SE closed form (sgp_theta_descend_psi)")
     args = ap.parse_args()
-    print(json.dumps(run(args.epochs, args.nodes, args.seed, not args.host_paced, psi=args.psi)))
+    print(json.dumps(run(args.epochs, args.nodes, args.seed, not args.host_paced, psi=args.psi, theta_psi=args.theta_psi)))

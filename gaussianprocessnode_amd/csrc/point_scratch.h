@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
-// sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi).  Plain C++, no HIP: all six layouts are checked on the host over a grid
-// of shapes by tools/point_scratch_check.cpp.
+// sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi).  Plain C++, no HIP: all
+// layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -167,6 +167,57 @@ static inline void layout_psi(Carver& c, const PointShape& p, int M, bool has_co
     b->Mu = c.take<double>(mu_count);
     b->Y = c.take<double>(y_count);
     b->Bs = c.take<double>(y_count ? (size_t)p.Mp * p.dout : 0);
+}
+
+// sgp_theta_objective_psi and sgp_theta_descend_psi (p.n = p.n_nodes = the nodes, p.chunk nodes per chunk): the inputs, status words
+// and Psi1 sums of all nodes ([node][slots]); one chunk of g and h ([node][D][Mp]), of the per-dimension scalars ([node][D]) and of the
+// determinant factors; the range accumulators of Psi2 (acc_tiles 64 x 64 tiles) and of the per-thread sums (acc_tiles x D x 256); the
+// tiles' contractions ([lower tile][tile_slots]); the K_uu chain at the kernel under evaluation (K_uu -> L_K, W_K, K_uu^-1), G, its
+// unused column shares, Psi2, K_uu^-1 Psi2, H and the K_uu half's block sums ([T x T][slots]); value and gradient (2 x slots), the node
+// status word, the descent's values, and one factorisation's scratch with its status word
+struct PsiThetaScratch {
+    double *Mean, *Cov, *Y;
+    int* Bad;
+    double* Lin;
+    double *G2, *H2, *E2, *Cw;
+    double *Acc, *Wd, *TilePart;
+    double *Kuu, *Wk, *Kinv, *G, *Gpart, *Psi2, *T1, *H, *PartUU;
+    double* Out;
+    int* Status;
+    double* Vals;
+    double* Pscr;
+    int* Info;
+};
+static inline void layout_psi_theta(Carver& c, const PointShape& p, bool has_cov, size_t acc_tiles, size_t slots, size_t tile_slots,
+                                    size_t steps, PsiThetaScratch* b) {
+    const size_t n = (size_t)p.n, D = (size_t)p.D, ch = (size_t)p.chunk, mm = (size_t)p.Mp * p.Mp;
+    const size_t ntiles = (size_t)p.T * (p.T + 1) / 2;
+    b->Mean = c.take<double>(n * D);
+    b->Cov = c.take<double>(has_cov ? n * D * D : 0);
+    b->Y = c.take<double>(n * p.dout);
+    b->Bad = c.take<int>(n);
+    b->Lin = c.take<double>(n * slots);
+    b->G2 = c.take<double>(ch * D * p.Mp);
+    b->H2 = c.take<double>(ch * D * p.Mp);
+    b->E2 = c.take<double>(ch * D);
+    b->Cw = c.take<double>(ch);
+    b->Acc = c.take<double>(acc_tiles * 64 * 64);
+    b->Wd = c.take<double>(acc_tiles * D * 256);
+    b->TilePart = c.take<double>(ntiles * tile_slots);
+    b->Kuu = c.take<double>(mm);
+    b->Wk = c.take<double>(mm);
+    b->Kinv = c.take<double>(mm);
+    b->G = c.take<double>(mm);
+    b->Gpart = c.take<double>((size_t)p.Mp);
+    b->Psi2 = c.take<double>(mm);
+    b->T1 = c.take<double>(mm);
+    b->H = c.take<double>(mm);
+    b->PartUU = c.take<double>((size_t)p.T * p.T * slots);
+    b->Out = c.take<double>(2 * slots);
+    b->Status = c.take<int>(1);
+    b->Vals = c.take<double>(steps);
+    b->Pscr = c.take<double>((size_t)p.potrf_scratch);
+    b->Info = c.take<int>(1);
 }
 
 // sgp_predict: the points, their means and an explicit mu_v (Q entries, unpadded)

@@ -116,6 +116,9 @@ struct SweepPlan {
 //   sgp_theta_descend                           drops reuse and q(v); swept_local = false (the statistics are the last EVALUATED theta's)
 //   next_kind (once per record)                 checked, or drops reuse: its sweep ended without K_uu factored / with a wait given up
 //   sgp_sweep_local_psi                         fills the record, drops reuse, exact_psi; data_gen++; have_data = false (sgp_set_data clears exact_psi)
+//   sgp_theta_objective_psi                     nothing: everything it forms is in call scratch
+//   sgp_theta_descend_psi                       nothing: the kernel moved (hParams, params_gen++), nothing resident was rewritten, and
+//                                               kernel_matches, which compares values, turns the resident statistics down
 struct StatsRecord {
     double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};   // the kernel values they were formed at ...
     int32_t family = SGP_KERNEL_SE;                           // ... and the family
@@ -3329,6 +3332,230 @@ extern "C" int sgp_theta_descend(sgp_handle* h, double* theta_raw, int32_t n_ell
     if (int src = check_sync_status(h)) return src;
     if (st.stop != 0.0)
         return factor_status(h, (int)st.stop, ("sgp_theta_descend, step " + std::to_string((int64_t)st.steps) + ": K_uu").c_str());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The kernel-parameter objective over the exact Psi-statistics of Gaussian inputs, its analytic gradient and the device-paced
+// descent on it (include/sgp_hip.h: sgp_theta_objective_psi, sgp_theta_descend_psi; kernels: k_psi_theta_* in sgp_kernels.hip.h).
+// What they form lives in call scratch -- the K_uu chain at the kernel under evaluation too -- so nothing the sweep keeps is written.
+// Outside call scratch they touch what sgp_theta_objective and sgp_theta_descend touch as well: the K_uu chain's parameter mirror
+// (dXusK / dParamsK, rewritten as sgp_predict rewrites it); dThetaMulti, where theta_Rv forms R_v when sgp_set_posterior came last
+// (allocated on first use); and, the descent only, the optimiser state and parameter block dTrain / dTrainParams (allocated on first
+// use) -- an open sgp_train_* run owns those two, so psi_theta_ready, which refuses one, runs before anything is written to them.
+// ------------------------------------------------------------------------------------------------
+static PointShape psi_theta_shape(const sgp_handle* h, int64_t T) {
+    return point_shape(h, 2 * (int64_t)h->D * h->Mp + h->D + 1, T, T);
+}
+
+// what both calls refuse, and the inputs every kernel below relies on being finite
+static int psi_theta_ready(sgp_handle* h, const char* name, const double* mean, const double* cov, const double* y_mean, int64_t T) {
+    if (int rc = psi_inputs_ready(h, name, mean, cov, T)) return rc;
+    for (size_t i = 0; i < (size_t)T * h->dout; ++i)
+        if (!std::isfinite(y_mean[i])) return refuse(h, name, "y_mean must be finite");
+    if (!h->swept) return refuse(h, name, "needs a finished sweep or sgp_set_posterior (q(v))");
+    if (h->allreduce) return refuse(h, name, "an all-reduce hook is installed (data-sharded exact statistics are not supported)");
+    return 0;
+}
+
+static int psi_theta_carve(sgp_handle* h, const PointShape& shape, bool has_cov, size_t steps, PsiThetaScratch* b) {
+    int nranges = 0;
+    int64_t range_len = 0;
+    psi_ranges(shape.n, h->ntiles, &nranges, &range_len);
+    return carve_call_scratch(h, [&](Carver& c) {
+        layout_psi_theta(c, shape, has_cov, (size_t)nranges * h->ntiles, GRAD_SLOTS, PSI_TP_SLOTS, steps, b);
+    });
+}
+
+static int psi_theta_upload(sgp_handle* h, const PsiThetaScratch& b, const double* mean, const double* cov, const double* y_mean,
+                            int64_t T) {
+    const size_t D = (size_t)h->D;
+    HIPCHK(h, hipMemcpy(b.Mean, mean, sizeof(double) * (size_t)T * D, hipMemcpyHostToDevice));
+    if (cov) HIPCHK(h, hipMemcpy(b.Cov, cov, sizeof(double) * (size_t)T * D * D, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Y, y_mean, sizeof(double) * (size_t)T * h->dout, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// One evaluation on `s` at the kernel parameters in `src` (the pinned host block, or the descent's device block): the K_uu chain, G,
+// the nodes chunk by chunk, the tiles' contractions, the K_uu half and the fixed-order finish into b.Out (gradient, value at
+// GRAD_SLOTS) and b.Status.  Rv: R_v of the held q(v) (theta_Rv), w: the held mean(q_W).
+static int psi_theta_enqueue(sgp_handle* h, hipStream_t s, const PsiThetaScratch& b, const PointShape& shape, bool has_cov,
+                             const Params* src, const double* Rv, const MeanW& w, int n_ell) {
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Tn = h->T, ntiles = h->ntiles;
+    const int64_t T = shape.n;
+    int nranges = 0;
+    int64_t range_len = 0;
+    psi_ranges(T, ntiles, &nranges, &range_len);
+    const size_t acc_tiles = (size_t)nranges * ntiles;
+    HIPCHK(h, hipMemsetAsync(b.Pscr, 0, sizeof(double) * POTRF_SCRATCH, s));
+    HIPCHK(h, hipMemsetAsync(b.Info, 0, sizeof(int), s));
+    HIPCHK(h, hipMemsetAsync(b.Acc, 0, sizeof(double) * acc_tiles * TB * TB, s));
+    HIPCHK(h, hipMemsetAsync(b.Wd, 0, sizeof(double) * acc_tiles * D * 256, s));
+    launch_prep_xu(h, s, h->dXusK, src, h->dParamsK);
+    hipLaunchKernelGGL(k_gram_uu<SGP_KERNEL_SE>, dim3(Tn, Tn), dim3(256), 0, s, h->dXusK, b.Kuu, h->dParamsK, M, Mp, D);
+    launch_potrf(b.Kuu, Mp, Tn, b.Info, M, b.Pscr, s, b.Wk);
+    launch_ata(b.Wk, b.Kinv, Mp, Tn, s);
+    // (k_form_G_multi also sums column shares of tr(G Psi2) against its Psi2 argument: not used here, any Mp x Mp matrix will do)
+    hipLaunchKernelGGL(k_form_G_multi, dim3(Mp), dim3(256), 0, s, Rv, h->Qp, (const double*)b.Kinv, (const double*)b.Kinv, w.W, w.trace,
+                       b.G, b.Gpart, M, Mp, dout);
+    for (int64_t t0 = 0; t0 < T; t0 += shape.chunk) {
+        const int64_t nc = std::min<int64_t>(shape.chunk, T - t0);
+        const int r0 = (int)(t0 / range_len), r1 = (int)((t0 + nc - 1) / range_len);
+        auto launch = [&](auto DCAP) {
+            constexpr int DC = decltype(DCAP)::value;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi_theta_prep<DC>), dim3((unsigned)nc), dim3(64), 0, s, (const double*)h->dXu,
+                               (const double*)b.Mean, has_cov ? (const double*)b.Cov : (const double*)nullptr, (const double*)b.Y, T, t0,
+                               (const double*)h->dMu, w.W, (const Params*)h->dParamsK, b.G2, b.H2, b.E2, b.Cw, b.Lin, b.Bad, M, Mp, D, dout);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi2_theta_accumulate<DC>), dim3(ntiles, r1 - r0 + 1), dim3(256), 0, s,
+                               (const double*)b.G2, (const double*)b.H2, (const double*)b.E2, (const double*)b.Cw, (const double*)b.G,
+                               (const double*)h->dXusK, (const Params*)h->dParamsK, b.Acc, b.Wd, t0, nc, range_len, r0, ntiles, Mp, D);
+        };
+        if (D <= 8) launch(std::integral_constant<int, 8>{});
+        else launch(std::integral_constant<int, MAXD>{});
+    }
+    hipLaunchKernelGGL(k_psi2_theta_finish, dim3(ntiles), dim3(256), 0, s, (const double*)b.Acc, (const double*)b.Wd, (const double*)b.G,
+                       (const double*)h->dXusK, (const Params*)h->dParamsK, b.Psi2, b.TilePart, nranges, ntiles, M, Mp, D);
+    launch_gemm(b.Kinv, b.Psi2, b.T1, Mp, Tn, s);
+    launch_gemm(b.T1, b.Kinv, b.H, Mp, Tn, s);
+    hipLaunchKernelGGL(k_theta_grad_uu<SGP_KERNEL_SE>, dim3(Tn, Tn), dim3(256), 0, s, (const double*)b.H, (const double*)h->dXusK,
+                       (const Params*)h->dParamsK, b.PartUU, M, Mp, D);
+    hipLaunchKernelGGL(k_psi_theta_finish, dim3(1), dim3(256), 0, s, (const double*)b.TilePart, ntiles, (const double*)b.Lin, T,
+                       (const double*)b.PartUU, Tn * Tn, (const int*)b.Bad, (const Params*)h->dParamsK, w.trace, b.Out, b.Status, D, n_ell);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// the status of one evaluation as the ABI reports it: the indefinite node first, then K_uu
+static int psi_theta_status(sgp_handle* h, const std::string& name, int node, int info_kuu) {
+    if (node > 0)
+        return fail(h, node, (name + ": Lambda + S or Lambda + 2 S is not positive definite at node " + std::to_string(node - 1) +
+                              " (cov must be positive semi-definite)").c_str());
+    return factor_status(h, info_kuu, (name + ": K_uu").c_str());
+}
+
+extern "C" int sgp_theta_objective_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
+                                       double* value, double* grad, int64_t* info) {
+    const char* name = "sgp_theta_objective_psi";
+    if (!h || !mean || !y_mean || !value) return fail(h, SGP_ERR_ARG, "sgp_theta_objective_psi: null argument");
+    if (info) info[0] = info[1] = 0;
+    if (n_nodes < 1) return refuse(h, name, "n_nodes must be >= 1");
+    if (int rc = psi_theta_ready(h, name, mean, cov, y_mean, n_nodes)) return rc;
+    if (int wrc = sync_checked(h)) return wrc;
+    hipStream_t s = h->own;
+    const PointShape shape = psi_theta_shape(h, n_nodes);
+    PsiThetaScratch b;
+    if (int crc = psi_theta_carve(h, shape, cov != nullptr, 0, &b)) return crc;
+    if (int rc = psi_theta_upload(h, b, mean, cov, y_mean, n_nodes)) return rc;
+    const MeanW w(h);
+    const double* Rv = h->dR;
+    if (int rrc = theta_Rv(h, s, &Rv)) return rrc;
+    if (int rc = psi_theta_enqueue(h, s, b, shape, cov != nullptr, h->hParams, Rv, w, h->n_ell)) return rc;
+    HIPCHK(h, wait_stream(s));
+    HIPCHK(h, hipGetLastError());
+    int node = 0, kuu = 0;
+    HIPCHK(h, hipMemcpy(&node, b.Status, sizeof node, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&kuu, b.Info, sizeof kuu, hipMemcpyDeviceToHost));
+    if (info) { info[0] = kuu > 0 ? kuu : 0; info[1] = node; }
+    if (int rc = psi_theta_status(h, name, node, kuu)) return rc;
+    double res[GRAD_SLOTS + 1];
+    HIPCHK(h, hipMemcpy(res, b.Out, sizeof res, hipMemcpyDeviceToHost));
+    *value = res[GRAD_SLOTS];
+    if (grad)
+        for (int i = 0; i <= h->n_ell; ++i) grad[i] = res[i];
+    return 0;
+}
+
+// sgp_theta_descend with the objective above: per step, all on the library's own stream, one evaluation at theta_k and
+// k_descend_step_psi (value out, AdaMax, softplus(theta_k+1) written where the next step's k_prep_xu reads it).  The inputs are
+// uploaded and R_v is formed once per call.  The host enqueues and waits once.
+extern "C" int sgp_theta_descend_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
+                                     double* theta_raw, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2, double eps,
+                                     double* opt_state, double* values, int64_t* counts) {
+    const char* name = "sgp_theta_descend_psi";
+    if (!h || !theta_raw) return fail(h, SGP_ERR_ARG, "sgp_theta_descend_psi: null argument");
+    if (n_ell != 1 && n_ell != h->D) return refuse(h, name, "n_ell must be 1 or D");
+    if (steps < 0) return refuse(h, name, "steps must be >= 0");
+    if (!(eta > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return refuse(h, name, "eta > 0 and beta1, beta2 in [0, 1) required");
+    const int np = 1 + n_ell;
+    if (opt_state) {
+        // (a power is beta^t, t >= 1: inside (0, 1), or exactly 0 for a beta of 0)
+        const double bt[2] = {beta1, beta2};
+        for (int i = 0; i < 2; ++i) {
+            const double pw = opt_state[2 * np + i];
+            if (!(pw < 1.0) || !(pw > 0.0 || (pw == 0.0 && bt[i] == 0.0)))
+                return refuse(h, name, "the running powers of beta in opt_state must lie in (0, 1)");
+        }
+    }
+    for (int i = 0; i < np; ++i)
+        if (!std::isfinite(theta_raw[i])) return refuse(h, name, "theta_raw must be finite");
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    if (steps == 0) return 0;
+    if (!mean || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_theta_descend_psi: null argument");
+    if (n_nodes < 1) return refuse(h, name, "n_nodes must be >= 1");
+    if (int rc = psi_theta_ready(h, name, mean, cov, y_mean, n_nodes)) return rc;      // (refuses an open run: dTrain below is its state)
+    if (int wrc = sync_checked(h)) return wrc;
+    hipStream_t s = h->own;
+    if (!h->dTrain) {
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
+    }
+    const PointShape shape = psi_theta_shape(h, n_nodes);
+    PsiThetaScratch b;
+    if (int crc = psi_theta_carve(h, shape, cov != nullptr, (size_t)steps, &b)) return crc;
+    if (int rc = psi_theta_upload(h, b, mean, cov, y_mean, n_nodes)) return rc;
+    std::vector<double> vals((size_t)steps, std::numeric_limits<double>::quiet_NaN());
+    HIPCHK(h, hipMemcpy(b.Vals, vals.data(), sizeof(double) * (size_t)steps, hipMemcpyHostToDevice));
+    TrainState st;
+    memset(&st, 0, sizeof st);
+    for (int i = 0; i < np; ++i) {
+        st.theta[i] = theta_raw[i];
+        if (opt_state) { st.m[i] = opt_state[i]; st.u[i] = opt_state[np + i]; }
+    }
+    st.bp[0] = opt_state ? opt_state[2 * np] : beta1;
+    st.bp[1] = opt_state ? opt_state[2 * np + 1] : beta2;
+    st.eta = eta; st.beta1 = beta1; st.beta2 = beta2; st.eps = eps;
+    HIPCHK(h, hipMemcpy(h->dTrain, &st, sizeof st, hipMemcpyHostToDevice));
+    // noise, E[log w], the prior and the jitter stay what the setters left; sigma2 and the lengthscales come from theta on the device
+    HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
+    h->in_flight = true;
+    const MeanW w(h);
+    hipLaunchKernelGGL(k_train_adamax, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)nullptr, (const double*)nullptr,
+                       h->dTrainParams, h->D, n_ell, 0, (const int*)nullptr, (const Params*)nullptr, (const double*)nullptr);
+    const double* Rv = h->dR;
+    int rc = theta_Rv(h, s, &Rv);                             // R_v: once per call, q(v) is held
+    for (int k = 0; k < steps && !rc; ++k) {
+        rc = psi_theta_enqueue(h, s, b, shape, cov != nullptr, h->dTrainParams, Rv, w, n_ell);
+        if (!rc)
+            hipLaunchKernelGGL(k_descend_step_psi, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)b.Out, (const int*)b.Info,
+                               (const int*)b.Status, b.Vals, k, h->dTrainParams, h->D, n_ell);
+    }
+    // whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path
+    const hipError_t werr = wait_stream(s);
+    const hipError_t lerr = hipGetLastError();
+    h->in_flight = false;
+    if (rc) return rc;
+    HIPCHK(h, werr);
+    HIPCHK(h, lerr);
+    HIPCHK(h, hipMemcpy(&st, h->dTrain, sizeof st, hipMemcpyDeviceToHost));
+    Params P;
+    HIPCHK(h, hipMemcpy(&P, h->dTrainParams, sizeof P, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(vals.data(), b.Vals, sizeof(double) * (size_t)steps, hipMemcpyDeviceToHost));
+    // the handle's kernel is softplus(theta_out), as the device formed it (as after sgp_theta_descend)
+    h->hParams->sigma2 = P.sigma2;
+    for (int d = 0; d < h->D; ++d) h->hParams->inv_ell[d] = P.inv_ell[d];
+    h->n_ell = n_ell;
+    h->params_gen++;
+    for (int i = 0; i < np; ++i) {
+        theta_raw[i] = st.theta[i];
+        if (opt_state) { opt_state[i] = st.m[i]; opt_state[np + i] = st.u[i]; }
+    }
+    if (opt_state) { opt_state[2 * np] = st.bp[0]; opt_state[2 * np + 1] = st.bp[1]; }
+    if (values) for (int k = 0; k < steps; ++k) values[k] = vals[(size_t)k];
+    const int node = st.stop <= -2.0 ? (int)(-st.stop - 1.0) : 0;
+    const int kuu = st.stop <= -2.0 ? 0 : (int)st.stop;
+    if (counts) { counts[0] = (int64_t)st.steps; counts[1] = kuu > 0 ? kuu : 0; counts[2] = node; }
+    if (st.stop != 0.0) return psi_theta_status(h, std::string(name) + ", step " + std::to_string((int64_t)st.steps), node, kuu);
     return 0;
 }
 

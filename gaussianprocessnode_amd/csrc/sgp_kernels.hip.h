@@ -4370,4 +4370,388 @@ __global__ void __launch_bounds__(256) k_psi_b(const double* __restrict__ psi1, 
     B[(size_t)o * Mp + m] = s;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The kernel-parameter objective over the exact Psi-statistics, its analytic gradient and the descent on it
+// (sgp_theta_objective_psi, sgp_theta_descend_psi).  With q(v) and W held, G = S - tr(W) K_uu^-1 and
+// s_t = sum_d mu^(d) (W y_t)_d:
+//   f  = 1/2 tr(W) sigma2 T + 1/2 tr(G Psi2) - sum_t s_t' Psi1_t
+//   dlog Psi1_t[m]   / dell_d = 1/ell_d - ell_d (P_1)_dd + ell_d (h1_tm,d)^2                                         P_c = (Lambda + c S_t)^-1
+//   dlog Psi2_t[m,m']/ dell_d = 1/ell_d - ell_d (P_2)_dd + 1/2 (z_md - z_m'd)^2 / ell_d^3 + 1/2 ell_d (h2_tm,d + h2_tm',d)^2,   h = P_c (m_t - z_m)
+// With Lambda + c S = C C' and g = C^-1 a: h = C^-T g, (P_c)_dd = the squared norm of column d of C^-1.  Unlike the kernels above these
+// read sigma2 and 1 / ell from the device parameter block, which k_descend_step_psi moves.  No atomics; every sum has a fixed order.
+// ------------------------------------------------------------------------------------------------
+constexpr int PSI_TP_SLOTS = 1 + 2 * MAXD;  // per lower tile: tr(G Psi2) | [d] sum G Psi2 (dz_d / ell_d)^2 | [d] the node-dependent sums
+
+// psi_factor with the lengthscales in LDS (`ell`), then C^-1 into Ci (lane j owns column j) and e[d] = 1/ell_d - ell_d (P_c)_dd
+__device__ __forceinline__ void psi_factor_inv(double* A, double* Ci, double* rinv, double* e, int* bad, const double* __restrict__ S,
+                                               const double* ell, double c, int D, int lane) {
+    if (lane < D)
+        for (int j = 0; j <= lane; ++j)
+            A[lane * PSI_LD + j] = (S ? c * S[(size_t)j * D + lane] : 0.0) + (j == lane ? ell[lane] * ell[lane] : 0.0);
+    __syncthreads();
+    bool ok = true;
+    for (int k = 0; k < D; ++k) {
+        const double piv = A[k * PSI_LD + k];
+        if (!(piv > 0.0)) {                                   // (uniform: every lane reads the same word)
+            if (lane == 0) *bad = 1;
+            ok = false;
+            break;
+        }
+        const double r = 1.0 / sqrt(piv);
+        __syncthreads();
+        if (lane == k) { A[k * PSI_LD + k] = piv * r; rinv[k] = r; }
+        if (lane > k && lane < D) A[lane * PSI_LD + k] *= r;
+        __syncthreads();
+        if (lane > k && lane < D) {
+            const double lik = A[lane * PSI_LD + k];
+            for (int j = k + 1; j <= lane; ++j) A[lane * PSI_LD + j] = fma(-lik, A[j * PSI_LD + k], A[lane * PSI_LD + j]);
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    if (ok && lane < D) {                                     // column `lane` of C^-1 by forward substitution; the lane reads back its own words
+        double p = rinv[lane] * rinv[lane];
+        Ci[lane * PSI_LD + lane] = rinv[lane];
+        for (int i = lane + 1; i < D; ++i) {
+            double s = 0.0;
+            for (int k = lane; k < i; ++k) s = fma(A[i * PSI_LD + k], Ci[k * PSI_LD + lane], s);
+            const double x = -s * rinv[i];
+            Ci[i * PSI_LD + lane] = x;
+            p = fma(x, x, p);
+        }
+        e[lane] = 1.0 / ell[lane] - ell[lane] * p;
+    }
+    __syncthreads();
+}
+
+// h_d = (C^-T g)_d from C^-1 in LDS (every lane the same word); d is a compile-time constant at every call
+template <int DCAP>
+__device__ __forceinline__ double psi_back(const double (&g)[DCAP], const double* Ci, int D, int d) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < DCAP; ++i)
+        if (i >= d && i < D) s = fma(Ci[i * PSI_LD + d], g[i], s);
+    return s;
+}
+
+// Per node (one wavefront each; grid = the nodes of this chunk, t0 = its first node): both factors and their inverses; for the Psi2 half
+// g and h of Lambda + 2 S ([node of the chunk][D][Mp], rows m >= M zero), E2 [node of the chunk][D] = 1/ell_d - ell_d (P_2)_dd and
+// cw = prod_d(ell_d / C_dd); the whole Psi1 half into lin [node of the call][GRAD_SLOTS]: slot 0 = sum_m s_t[m] Psi1_t[m], slot 1 + d =
+// sum_m s_t[m] Psi1_t[m] (1/ell_d - ell_d (P_1)_dd + ell_d h1_d^2), lane l summing m = l, l + 64, .. in order, then the xor butterfly.
+// mean, cov, y (T x d_out column-major), bad are the call's; mu [d_out][M]; W = mean(q_W) by value.
+template <int DCAP>
+__global__ void __launch_bounds__(64) k_psi_theta_prep(const double* __restrict__ Xu, const double* __restrict__ mean,
+                                                       const double* __restrict__ cov, const double* __restrict__ y, int64_t T, int64_t t0,
+                                                       const double* __restrict__ mu, OutMat W, const Params* __restrict__ P,
+                                                       double* __restrict__ G2, double* __restrict__ H2, double* __restrict__ E2,
+                                                       double* __restrict__ cw, double* __restrict__ lin, int* __restrict__ bad,
+                                                       int M, int Mp, int D, int d_out) {
+    __shared__ double A1[MAXD * PSI_LD], A2[MAXD * PSI_LD], C1[MAXD * PSI_LD], C2[MAXD * PSI_LD];
+    __shared__ double r1[MAXD], r2[MAXD], e1[MAXD], e2[MAXD], mt[MAXD], ell[MAXD];
+    __shared__ int failed;
+    const int lane = threadIdx.x;
+    const int64_t tc = blockIdx.x, t = t0 + tc;
+    if (lane == 0) failed = 0;
+    if (lane < D) { mt[lane] = mean[(size_t)t * D + lane]; ell[lane] = 1.0 / P->inv_ell[lane]; }
+    __syncthreads();
+    const double* S = cov ? cov + (size_t)t * D * D : nullptr;
+    psi_factor_inv(A1, C1, r1, e1, &failed, S, ell, 1.0, D, lane);
+    psi_factor_inv(A2, C2, r2, e2, &failed, S, ell, 2.0, D, lane);
+    if (failed) {                                             // (uniform)
+        // the node is reported through bad[]; it writes zeros -- weight, scalars, g, h and its Psi1 sums -- so that the kernels behind
+        // read nothing uninitialised and the node adds nothing (value and gradient are then those of the other nodes: not returned)
+        if (lane == 0) { bad[t] = 1; cw[tc] = 0.0; }
+        if (lane < D) E2[(size_t)tc * D + lane] = 0.0;
+        if (lane <= D) lin[(size_t)t * (MAXD + 1) + lane] = 0.0;
+        for (int e = lane; e < D * Mp; e += 64) {
+            G2[(size_t)tc * D * Mp + e] = 0.0;
+            H2[(size_t)tc * D * Mp + e] = 0.0;
+        }
+        return;
+    }
+    double det1 = 1.0, det2 = 1.0;                            // prod_d ell_d / C_dd, in the order d = 0, 1, ..
+    for (int d = 0; d < D; ++d) { det1 *= ell[d] * r1[d]; det2 *= ell[d] * r2[d]; }
+    if (lane == 0) { bad[t] = 0; cw[tc] = det2; }
+    if (lane < D) E2[(size_t)tc * D + lane] = e2[lane];
+    double wy[MAXO];                                          // (W y_t)_o
+#pragma unroll
+    for (int o = 0; o < MAXO; ++o) {
+        wy[o] = 0.0;
+        if (o < d_out)
+            for (int e = 0; e < d_out; ++e) wy[o] = fma(W.v[o + e * d_out], y[(size_t)e * T + t], wy[o]);
+    }
+    const double s2 = P->sigma2;
+    double l0 = 0.0, ld[DCAP];
+#pragma unroll
+    for (int d = 0; d < DCAP; ++d) ld[d] = 0.0;
+    for (int m = lane; m < Mp; m += 64) {
+        // (the factors are re-read from LDS for every m: hoisted out of this loop they would need 2 D (D + 1) registers)
+        asm volatile("" ::: "memory");
+        double diff[DCAP], g[DCAP];
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d) diff[d] = (d < D && m < M) ? mt[d] - Xu[(size_t)m * D + d] : 0.0;
+        const double q1 = psi_solve<DCAP>(g, diff, A1, r1, D);
+        if (m < M) {
+            double st = 0.0;
+#pragma unroll
+            for (int o = 0; o < MAXO; ++o)
+                if (o < d_out) st = fma(mu[(size_t)o * M + m], wy[o], st);
+            const double sp = st * (s2 * det1 * exp(-0.5 * q1));
+            l0 += sp;
+#pragma unroll
+            for (int d = 0; d < DCAP; ++d)
+                if (d < D) {
+                    const double hv = psi_back<DCAP>(g, C1, D, d);
+                    ld[d] = fma(sp, fma(ell[d] * hv, hv, e1[d]), ld[d]);
+                }
+        }
+        psi_solve<DCAP>(g, diff, A2, r2, D);
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d)
+            if (d < D) {
+                G2[((size_t)tc * D + d) * Mp + m] = g[d];
+                H2[((size_t)tc * D + d) * Mp + m] = psi_back<DCAP>(g, C2, D, d);
+            }
+    }
+    for (int s = 32; s > 0; s >>= 1) l0 += __shfl_xor(l0, s);
+    if (lane == 0) lin[(size_t)t * (MAXD + 1)] = l0;
+#pragma unroll
+    for (int d = 0; d < DCAP; ++d)
+        if (d < D) {                                          // (uniform)
+            double v = ld[d];
+            for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+            if (lane == 0) lin[(size_t)t * (MAXD + 1) + 1 + d] = v;
+        }
+}
+
+// The Psi2 half: k_psi2_accumulate's decomposition (lower 64 x 64 tiles x node ranges, a range's nodes added IN ORDER, partials left in
+// memory across chunks) with, beside the accumulator tile, D running sums per THREAD over its 4 x 4 entries:
+//   wd[range][tile][d][thread] = sum_t sum_entries omega_ijt [ (1/ell_d - ell_d (P_2)_dd) + 1/2 ell_d (h_id + h_jd)^2 ],
+//   omega_ijt = G_ij exp(-1/4 |z_i - z_j|^2 / ell^2) c_t exp(-1/4 |g_i + g_j|^2)        (sigma2^2 is applied by k_psi_theta_finish)
+// in a second pass over d behind a node's exponentials, so that only D sums, not 16 D, live across nodes.  Templated on the D cap: the
+// sums stay in registers.  Xus: the scaled inducing inputs [d][Mp] (k_prep_xu); Gm: G (Mp x Mp, symmetric, zero outside M x M).
+template <int DCAP>
+__global__ void __launch_bounds__(256) k_psi2_theta_accumulate(const double* __restrict__ G2, const double* __restrict__ H2,
+                                                               const double* __restrict__ E2, const double* __restrict__ cw,
+                                                               const double* __restrict__ Gm, const double* __restrict__ Xus,
+                                                               const Params* __restrict__ P, double* __restrict__ acc,
+                                                               double* __restrict__ wd, int64_t t0, int64_t nc, int64_t range_len,
+                                                               int r0, int ntiles, int Mp, int D) {
+    constexpr int ROWS = DCAP <= 8 ? 16 : 32;                 // LDS rows (node x dimension) per stage and array
+    __shared__ double gi[ROWS * TB], gj[ROWS * TB], hi[ROWS * TB], hj[ROWS * TB];
+    const int tid = threadIdx.x, ti = tid & 15, tj = tid >> 4;
+    int I, J;
+    tile_from_index((int)blockIdx.x, I, J);
+    const int r = r0 + (int)blockIdx.y;
+    const int64_t lo = r * range_len > t0 ? r * range_len : t0;
+    const int64_t hi_t = (r + 1) * range_len < t0 + nc ? (r + 1) * range_len : t0 + nc;
+    if (lo >= hi_t) return;                                   // (uniform)
+    double* tile = acc + ((size_t)r * ntiles + blockIdx.x) * (TB * TB);
+    double* wdp = wd + ((size_t)r * ntiles + blockIdx.x) * D * 256 + tid;
+    double a[4][4], gf[4][4], w[DCAP];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) {
+            const int i = I * TB + ti + 16 * x, j = J * TB + tj + 16 * y;
+            a[x][y] = tile[(size_t)(tj + 16 * y) * TB + ti + 16 * x];
+            double q = 0.0;
+            for (int d = 0; d < D; ++d) { const double u = Xus[(size_t)d * Mp + i] - Xus[(size_t)d * Mp + j]; q = fma(u, u, q); }
+            gf[x][y] = Gm[(size_t)j * Mp + i] * exp(-0.25 * q);
+        }
+#pragma unroll
+    for (int d = 0; d < DCAP; ++d) w[d] = d < D ? wdp[(size_t)d * 256] : 0.0;
+    const int per = ROWS / D;                                 // nodes per stage (D <= ROWS: at least one)
+    for (int64_t tb = lo; tb < hi_t; tb += per) {
+        const int nn = (int)(hi_t - tb < per ? hi_t - tb : per);
+        __syncthreads();
+        for (int e = tid; e < nn * D * TB; e += 256) {
+            const int q = e >> 6, i = e & 63;
+            const size_t row = ((size_t)(tb - t0) * D + q) * Mp;
+            gi[q * TB + i] = G2[row + I * TB + i];
+            gj[q * TB + i] = G2[row + J * TB + i];
+            hi[q * TB + i] = H2[row + I * TB + i];
+            hj[q * TB + i] = H2[row + J * TB + i];
+        }
+        __syncthreads();
+        for (int n = 0; n < nn; ++n) {
+            double s[4][4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) s[x][y] = 0.0;
+            for (int d = 0; d < D; ++d) {
+                const double* pi = gi + (n * D + d) * TB;
+                const double* pj = gj + (n * D + d) * TB;
+                double vi[4], vj[4];
+#pragma unroll
+                for (int x = 0; x < 4; ++x) { vi[x] = pi[ti + 16 * x]; vj[x] = pj[tj + 16 * x]; }
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+#pragma unroll
+                    for (int y = 0; y < 4; ++y) { const double u = vi[x] + vj[y]; s[x][y] = fma(u, u, s[x][y]); }
+            }
+            const double c = cw[tb - t0 + n];
+            const double* en = E2 + (size_t)(tb - t0 + n) * D;
+            double so = 0.0;
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) {
+                    const double ev = c * exp(-0.25 * s[x][y]);
+                    a[x][y] += ev;
+                    s[x][y] = gf[x][y] * ev;                  // omega
+                    so += s[x][y];
+                }
+#pragma unroll
+            for (int d = 0; d < DCAP; ++d)
+                if (d < D) {                                  // (uniform)
+                    const double* pi = hi + (n * D + d) * TB;
+                    const double* pj = hj + (n * D + d) * TB;
+                    double vi[4], vj[4];
+#pragma unroll
+                    for (int x = 0; x < 4; ++x) { vi[x] = pi[ti + 16 * x]; vj[x] = pj[tj + 16 * x]; }
+                    double q = 0.0;
+#pragma unroll
+                    for (int x = 0; x < 4; ++x)
+#pragma unroll
+                        for (int y = 0; y < 4; ++y) { const double u = vi[x] + vj[y]; q = fma(s[x][y], u * u, q); }
+                    w[d] = fma(en[d], so, w[d]);
+                    w[d] = fma(0.5 / P->inv_ell[d], q, w[d]);
+                }
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) tile[(size_t)(tj + 16 * y) * TB + ti + 16 * x] = a[x][y];
+#pragma unroll
+    for (int d = 0; d < DCAP; ++d)
+        if (d < D) wdp[(size_t)d * 256] = w[d];
+}
+
+// Per lower tile: Psi2 = the ranges' accumulators summed in the order 0, 1, .. times sigma2^2 exp(-1/4 |z_m - z_m'|^2 / ell^2), written to
+// both mirror images (out: Mp x Mp, zero outside M x M: what the K_uu half multiplies), and the tile's contractions with G into
+// tp[tile][PSI_TP_SLOTS]: slot 0 = sum G Psi2, slot 1 + d = sum G Psi2 ((z_md - z_m'd) / ell_d)^2 (the node-independent term of
+// dPsi2 / dell_d, contracted once from the finished Psi2), slot 1 + MAXD + d = the ranges' wd sums, ranges in order, then the workgroup.
+__global__ void __launch_bounds__(256) k_psi2_theta_finish(const double* __restrict__ acc, const double* __restrict__ wd,
+                                                           const double* __restrict__ Gm, const double* __restrict__ Xus,
+                                                           const Params* __restrict__ P, double* __restrict__ out,
+                                                           double* __restrict__ tp, int nranges, int ntiles, int M, int Mp, int D) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    int I, J;
+    tile_from_index((int)blockIdx.x, I, J);
+    const double s4 = P->sigma2 * P->sigma2;
+    double gv[16];
+    double t0 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int e = tid + 256 * k, j = e >> 6, i = e & 63, gi = I * TB + i, gj = J * TB + j;
+        double v = 0.0, g = 0.0;
+        if (gi < M && gj < M) {
+            double s = 0.0;
+            for (int r = 0; r < nranges; ++r) s += acc[((size_t)r * ntiles + blockIdx.x) * (TB * TB) + e];
+            double q = 0.0;
+            for (int d = 0; d < D; ++d) { const double u = Xus[(size_t)d * Mp + gi] - Xus[(size_t)d * Mp + gj]; q = fma(u, u, q); }
+            v = s4 * exp(-0.25 * q) * s;
+            g = Gm[(size_t)gj * Mp + gi] * v;
+        }
+        out[(size_t)gj * Mp + gi] = v;
+        if (I != J) out[(size_t)gi * Mp + gj] = v;
+        gv[k] = g;
+        t0 += g;
+    }
+    double* o = tp + (size_t)blockIdx.x * PSI_TP_SLOTS;
+    t0 = block_sum(t0, red);
+    if (tid == 0) o[0] = t0;
+    for (int d = 0; d < D; ++d) {
+        double v = 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int e = tid + 256 * k, j = e >> 6, i = e & 63;
+            const double u = Xus[(size_t)d * Mp + I * TB + i] - Xus[(size_t)d * Mp + J * TB + j];
+            v = fma(gv[k], u * u, v);
+        }
+        v = block_sum(v, red);
+        if (tid == 0) o[1 + d] = v;
+        double ws = 0.0;
+        for (int r = 0; r < nranges; ++r) ws += wd[(((size_t)r * ntiles + blockIdx.x) * D + d) * 256 + tid];
+        ws = block_sum(ws, red);
+        if (tid == 0) o[1 + MAXD + d] = ws;
+    }
+}
+
+// One workgroup: every partial summed in a fixed order -- the tiles (a diagonal tile once, an off-diagonal tile twice), the nodes'
+// Psi1 sums, the K_uu half's blocks (k_theta_grad_uu on H = K_uu^-1 Psi2 K_uu^-1) -- the factors 1/2, tr(W), 2 / sigma2 and
+// 1 / sigma2, and out[0 .. n_ell] = the gradient, out[GRAD_SLOTS] = the value: where k_descend_step_psi reads them.  status[0] = the
+// first node whose factorisation failed, + 1 (0: none).
+__global__ void __launch_bounds__(256) k_psi_theta_finish(const double* __restrict__ tp, int ntiles, const double* __restrict__ lin,
+                                                          int64_t T, const double* __restrict__ part_uu, int n_uu,
+                                                          const int* __restrict__ bad, const Params* __restrict__ P, double trW,
+                                                          double* __restrict__ out, int* __restrict__ status, int D, int n_ell) {
+    __shared__ double red[4];
+    __shared__ double totT[PSI_TP_SLOTS], totL[GRAD_SLOTS], totK[GRAD_SLOTS];
+    __shared__ long long firstbad[4];
+    const int tid = threadIdx.x;
+    long long fb = 0x7fffffffffffffffLL;
+    for (int64_t t = tid; t < T; t += 256)
+        if (bad[t] && t + 1 < fb) fb = t + 1;
+    for (int o = 32; o > 0; o >>= 1) { const long long v = __shfl_xor(fb, o); fb = v < fb ? v : fb; }
+    if ((tid & 63) == 0) firstbad[tid >> 6] = fb;
+    for (int sl = 0; sl < PSI_TP_SLOTS; ++sl) {
+        const int d = sl == 0 ? 0 : (sl - 1) % MAXD;
+        if (d >= D) continue;                                 // (uniform)
+        double v = 0.0;
+        for (int b = tid; b < ntiles; b += 256) {
+            int I, J;
+            tile_from_index(b, I, J);
+            v += (I == J ? 1.0 : 2.0) * tp[(size_t)b * PSI_TP_SLOTS + sl];
+        }
+        v = block_sum(v, red);
+        if (tid == 0) totT[sl] = v;
+    }
+    for (int sl = 0; sl <= D; ++sl) {
+        double v = 0.0;
+        for (int64_t t = tid; t < T; t += 256) v += lin[(size_t)t * GRAD_SLOTS + sl];
+        v = block_sum(v, red);
+        double k = 0.0;
+        for (int b = tid; b < n_uu; b += 256) k += part_uu[(size_t)b * GRAD_SLOTS + sl];
+        k = block_sum(k, red);
+        if (tid == 0) { totL[sl] = v; totK[sl] = k; }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    long long f = firstbad[0];
+    for (int wv = 1; wv < 4; ++wv) f = firstbad[wv] < f ? firstbad[wv] : f;
+    status[0] = f == 0x7fffffffffffffffLL ? 0 : (f > 0x7fffffffLL ? 0x7fffffff : (int)f);
+    const double s2 = P->sigma2, s4 = s2 * s2, n = (double)T;
+    out[GRAD_SLOTS] = 0.5 * (trW * s2 * n + totT[0]) - totL[0];
+    out[0] = (totT[0] - totL[0] + 0.5 * trW * totK[0]) / s2 + 0.5 * trW * n;
+    double gsum = 0.0;
+    for (int d = 0; d < D; ++d) {
+        const double il = P->inv_ell[d];
+        const double g = 0.5 * (s4 * totT[1 + MAXD + d] + 0.5 * totT[1 + d] * il) - totL[1 + d] + 0.5 * trW * totK[1 + d] * il;
+        if (n_ell == 1) gsum += g;
+        else out[1 + d] = g;
+    }
+    if (n_ell == 1) out[1] = gsum;
+}
+
+// k_descend_step for sgp_theta_descend_psi: value and gradient are where k_psi_theta_finish left them.  An indefinite node (checked
+// first) or a nonzero K_uu status word stops the descent, latched in st->stop as -(1 + node + 1) resp. the failing minor (-1: a
+// twin-workgroup wait given up); from then on every step leaves theta, the moments, the powers, values[] and the parameters alone.
+__global__ void k_descend_step_psi(TrainState* __restrict__ st, const double* __restrict__ grad, const int* __restrict__ info_kuu,
+                                   const int* __restrict__ node_status, double* __restrict__ values, int k, Params* __restrict__ src,
+                                   int D, int n_ell) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (st->stop != 0.0) return;
+    const int node = *node_status, info = *info_kuu;
+    if (node != 0) { st->stop = -1.0 - (double)node; return; }
+    if (info != 0) { st->stop = info > 0 ? (double)info : -1.0; return; }
+    values[k] = grad[GRAD_SLOTS];
+    adamax_step(st, grad, 1.0, n_ell);
+    write_kernel_params(st, src, D, n_ell);
+}
+
 }  // namespace sgp

@@ -477,6 +477,63 @@ class SGPDevice:
             self._n_ell = n_ell
         return th, values, int(counts[0]), st
 
+    def theta_objective_psi(self, mean, cov, y_mean, want_grad: bool = False):
+        """The hyper-parameter objective over the exact Psi-statistics of T Gaussian inputs N(mean[t], cov[t]) at the current kernel
+        (sgp_theta_objective_psi; SE only): `theta_objective` with the cubature sums replaced by exact expectations.  mean (T, D),
+        cov (T, D, D) or None, y_mean (T, d_out) (or (T,) for d_out = 1); q(v) the last finished sweep's or `set_posterior`'s, W the
+        last `set_noise`.  Needs no resident data and changes nothing the sweep keeps.  Returns the value, or (value, gradient
+        w.r.t. (sigma2, ell...)).  A covariance that is not positive semi-definite at node t raises PosDefException with
+        info = t + 1; a K_uu that is not positive definite raises PosDefException with the failing minor, as `theta_objective`."""
+        m, S, T = self._node_gaussians("theta_objective_psi", mean, cov)
+        y_cm = self._node_targets(y_mean, T)
+        have = getattr(self, "_n_ell", None)
+        if want_grad and have is None:
+            raise ValueError("theta_objective_psi: call set_kernel first")
+        v = C.c_double()
+        g = np.empty(1 + have) if want_grad else None
+        info = (C.c_int64 * 2)()
+        self._check(self._lib.sgp_theta_objective_psi(self._h, ptr(m), ptr(S), ptr(y_cm), T, C.cast(C.byref(v), C.POINTER(C.c_double)),
+                                                      ptr(g), info), "sgp_theta_objective_psi")
+        return (v.value, g) if want_grad else v.value
+
+    def theta_descend_psi(self, mean, cov, y_mean, theta, steps: int, *, eta: float = 1e-3, beta=(0.9, 0.999), eps: float = 1e-8,
+                          state=None):
+        """`theta_descend` on the objective of `theta_objective_psi` (sgp_theta_descend_psi): `steps` device-paced AdaMax steps on the
+        raw parameters `theta` with q(v), the Gaussian inputs, the targets and the noise held.  Returns (theta, values, steps_taken,
+        state).  An indefinite covariance at node t raises PosDefException with info = t + 1; a K_uu that is not positive definite
+        at some theta_k raises LinAlgError as `theta_descend` does.  Either exception carries `theta`, `values` (NaN from that step
+        on), `steps_taken`, `state`, and `minor` / `node`."""
+        m, S, T = self._node_gaussians("theta_descend_psi", mean, cov)
+        y_cm = self._node_targets(y_mean, T)
+        th = np.array(theta, dtype=np.float64).reshape(-1)
+        n_ell = th.size - 1
+        steps = int(steps)
+        if state is None:
+            st = np.concatenate([np.zeros(2 * th.size), np.asarray(beta, dtype=np.float64)])
+        else:
+            st = np.array(state, dtype=np.float64).reshape(-1)
+            if st.size != 2 * th.size + 2:
+                raise ValueError(f"theta_descend_psi: state needs 2 (1 + n_ell) + 2 = {2 * th.size + 2} entries, got {st.size}")
+        values = np.empty(max(steps, 0))
+        counts = (C.c_int64 * 3)()
+        rc = self._lib.sgp_theta_descend_psi(self._h, ptr(m), ptr(S), ptr(y_cm), T, ptr(th), n_ell, steps, float(eta), float(beta[0]),
+                                             float(beta[1]), float(eps), ptr(st), ptr(values), counts)
+        if rc > 0:
+            self._n_ell = n_ell
+            if int(counts[2]) > 0:
+                msg = self._lib.sgp_last_error(self._h)
+                err = _lib.PosDefException(rc, f"theta_descend_psi {msg.decode() if msg else ''}")
+            else:
+                err = np.linalg.LinAlgError(f"theta_descend_psi: K_uu is not positive definite at step {int(counts[0])} "
+                                            f"(leading minor {rc}); theta and the optimiser state are those of that step")
+            err.minor, err.node = int(counts[1]), int(counts[2])
+            err.theta, err.values, err.steps_taken, err.state = th, values, int(counts[0]), st
+            raise err
+        self._check(rc, "sgp_theta_descend_psi")
+        if steps > 0:
+            self._n_ell = n_ell
+        return th, values, int(counts[0]), st
+
     def time_kernel(self, which: int, iters: int = 20, stream: int = 0) -> float:
         """Average launch duration (microseconds, HIP events) of the Gram or streaming-SYRK kernel."""
         v = C.c_double()

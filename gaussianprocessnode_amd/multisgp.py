@@ -484,15 +484,25 @@ def rule_theta(q_out, q_in, q_v, q_w, meta: MultiSGPMeta):
 # ------------------------------------------------------------------------------------------------
 # the hyper-parameter objective: neg_log_backwardmess_multi / grad_llh_multi! (helper_functions/derivative_helper.jl:92-115)
 # ------------------------------------------------------------------------------------------------
-def load_theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta):
+def _check_psi(psi, what):
+    if psi not in ("cubature", "exact"):
+        raise ValueError(f"{what}: psi must be 'cubature' or 'exact', got {psi!r}")
+
+
+def load_theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta, psi: str = "cubature"):
     """Load the inputs of neg_log_backwardmess_multi on `meta.engine` -- what `theta_objective_multi` evaluates and
     `train.optimize_theta_multi(device_paced=True)` descends on -- and return (engine, D_in).
+
+    psi="exact": the objective over the closed-form Psi-statistics of the Gaussian inputs (SE kernel only; SGPDevice.
+    theta_objective_psi / theta_descend_psi).  No points are formed or loaded: only W and q(v) are installed as below; the inputs
+    those calls take come from `exact_theta_inputs`.
 
     The points are meta.method's cubature points of every q_in (a PointMass input is its own point), each node's target
     y_data[i] repeated over its points (the reference passes y_data = mean.(qx)); W = mean(q_w); q(v) is installed with
     `set_posterior` (mu_v and chol(Sigma_v + mu mu').U, factored on the device), so the device forms S = sum_ij W_ij Rv[i][j]
     and the linear term itself.  The kernel family is meta.kernel's; the kernel values are the caller's to set."""
     from .device import potrf
+    _check_psi(psi, "theta_objective_multi")
     W = _mean_W(q_w)
     d_out = W.shape[0]
     if d_out < 2:
@@ -503,24 +513,38 @@ def load_theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGP
         Y = Y[None, :]
     if Y.ndim != 2 or Y.shape != (len(q_ins), d_out):
         raise ValueError(f"theta_objective_multi: y_data must be {len(q_ins)} x {d_out} (one target per node), got {Y.shape}")
-    if meta.method is None and not all(isinstance(q, PointMass) for q in q_ins):
-        raise ValueError("theta_objective_multi: uncertain inputs need meta.method (a cubature rule)")
-    pts, wts, ys, _ = _expand(meta, q_ins, [PointMass(y) for y in Y])
     M, D_in = np.asarray(meta.Xu).shape
+    if psi == "exact":
+        from .cubature import require_se
+        require_se(kernel_family(meta.kernel))
+    elif meta.method is None and not all(isinstance(q, PointMass) for q in q_ins):
+        raise ValueError("theta_objective_multi: uncertain inputs need meta.method (a cubature rule)")
+    else:
+        pts, wts, ys, _ = _expand(meta, q_ins, [PointMass(y) for y in Y])
     mu_v, Sigma_v = q_v.mean_cov()
     mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
     if mu_v.shape != (d_out * M,):
         raise ValueError(f"theta_objective_multi: q_v must have d_out * M = {d_out * M} entries, got {mu_v.size}")
     Uv = potrf(np.asarray(Sigma_v, dtype=np.float64) + np.outer(mu_v, mu_v), meta.device).T
-    eng = _engine(meta, len(wts), d_out)
-    load_batch(eng, pts, ys, None, wts, n_nodes=len(q_ins))
+    eng = _engine(meta, len(q_ins) if psi == "exact" else len(wts), d_out)
+    if psi != "exact":
+        load_batch(eng, pts, ys, None, wts, n_nodes=len(q_ins))
     sign, logdet = np.linalg.slogdet(W)
     eng.set_noise(W, float(logdet))
     eng.set_posterior(mu_v, Uv)
     return eng, D_in
 
 
-def theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta):
+def exact_theta_inputs(y_data, q_ins: Sequence, meta: MultiSGPMeta):
+    """(means (T, D), covs (T, D, D), Y (T, d_out)): the Gaussian inputs and targets as SGPDevice.theta_objective_psi and
+    theta_descend_psi take them (a PointMass input has S = 0), for an engine loaded by `load_theta_objective_multi(psi="exact")`."""
+    from .cubature import gaussian_inputs
+    q_ins = list(q_ins)
+    means, covs = gaussian_inputs(q_ins, np.asarray(meta.Xu).shape[1])
+    return means, covs, np.asarray(y_data, dtype=np.float64).reshape(len(q_ins), -1)
+
+
+def theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta, psi: str = "cubature"):
     """Load the objective's inputs on `meta.engine` once (`load_theta_objective_multi`) and return `evaluate(theta) -> (value,
     grad)`, value and gradient of neg_log_backwardmess_multi at the raw theta that `meta.kernel` maps
     (derivative_helper.jl:92-106).
@@ -528,8 +552,12 @@ def theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta)
     K_uu^-1 is taken at meta.jitter (the reference adds 1e-12 I).  Each call of `evaluate` is one
     `set_kernel` and one `sgp_theta_objective`: value and analytic gradient w.r.t. (sigma2, ell...), then the chain rule
     through softplus (d softplus / dx = sigmoid) when meta.kernel has softplus_params set.  A kernel callable without
-    `softplus_params` is taken to map theta to (theta[0], theta[1:]) unchanged."""
-    eng, D_in = load_theta_objective_multi(y_data, q_ins, q_v, q_w, meta)
+    `softplus_params` is taken to map theta to (theta[0], theta[1:]) unchanged.
+
+    psi="exact": the same objective over the closed-form Psi-statistics of the Gaussian inputs (`load_theta_objective_multi`);
+    each call is one `set_kernel` and one `sgp_theta_objective_psi`."""
+    eng, D_in = load_theta_objective_multi(y_data, q_ins, q_v, q_w, meta, psi)
+    exact = exact_theta_inputs(y_data, q_ins, meta) if psi == "exact" else None
     softplus_params = bool(getattr(meta.kernel, "softplus_params", False))
     family = kernel_family(meta.kernel)
 
@@ -540,7 +568,10 @@ def theta_objective_multi(y_data, q_ins: Sequence, q_v, q_w, meta: MultiSGPMeta)
         if th.size != 1 + ell.size or ell.size not in (1, D_in):
             raise ValueError(f"theta_objective_multi: theta must be (sigma2, 1 or {D_in} lengthscales), got {th.size} entries")
         set_engine_kernel(eng, sigma2, ell, meta.jitter, family)
-        value, grad = eng.theta_objective(want_grad=True, n_ell=ell.size)
+        if exact is not None:                                                       # (psi="exact": sgp_theta_objective_psi)
+            value, grad = eng.theta_objective_psi(*exact, want_grad=True)
+        else:
+            value, grad = eng.theta_objective(want_grad=True, n_ell=ell.size)
         grad = np.asarray(grad, dtype=np.float64)
         if softplus_params:
             grad = grad / (1.0 + np.exp(-th))                                       # d softplus(x) / dx = sigmoid(x)

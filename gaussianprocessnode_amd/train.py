@@ -280,17 +280,21 @@ def _perform_inference_classification_device(theta, xtrain, ytrain, Xu, engine, 
     return MvNormalMeanCovariance(mu, Sigma), (a, b), np.asarray(theta)
 
 
-def _descend(theta, engine, steps, opt):
-    """`steps` device-paced AdaMax steps on `engine` (SGPDevice.theta_descend) with `opt`'s state for `theta` carried in and
-    out; theta is updated in place."""
-    th, _, _, state = engine.theta_descend(theta, steps, eta=opt.eta, beta=opt.beta, eps=opt.eps, state=opt.get_state(theta))
+def _descend(theta, engine, steps, opt, exact=None):
+    """`steps` device-paced AdaMax steps on `engine` (SGPDevice.theta_descend; `exact` = (means, covs, Y): theta_descend_psi on the
+    exact statistics of those Gaussian inputs) with `opt`'s state for `theta` carried in and out; theta is updated in place."""
+    kw = dict(eta=opt.eta, beta=opt.beta, eps=opt.eps, state=opt.get_state(theta))
+    if exact is not None:
+        th, _, _, state = engine.theta_descend_psi(*exact, theta, steps, **kw)
+    else:
+        th, _, _, state = engine.theta_descend(theta, steps, **kw)
     theta[...] = th.reshape(theta.shape)
     opt.set_state(theta, state)
     return theta
 
 
 def optimize_theta_multi(theta, y_data, q_ins, q_v, q_w, meta, *, steps: int = 100, optimizer=None, grad_fn=None,
-                         device_paced: bool = False):
+                         device_paced: bool = False, psi: str = "cubature"):
     """The inner loop of the pendulum's `PerformInference` (experiments/Pendulum_Wishart_2d.ipynb, cell 16): `steps` times
     grad_llh_multi! at the current theta with q(x), q(v) and q(W) held, then Flux.Optimise.update!(AdaMax, theta, grad).
     theta (raw, as meta.kernel maps it) is updated in place and returned.  The objective's inputs go to the device once; each
@@ -300,8 +304,11 @@ def optimize_theta_multi(theta, y_data, q_ins, q_v, q_w, meta, *, steps: int = 1
     device_paced=True: the same inputs are loaded the same way, then ONE sgp_theta_descend call takes all the steps on the
     device -- softplus map, objective, gradient and AdaMax -- and the host waits once.  The optimiser's moments for `theta` are
     read from and written back to `optimizer`, so successive calls continue one optimiser, host-paced or device-paced in any
-    mix.  It needs meta.kernel.softplus_params (the device maps theta through softplus): ValueError otherwise."""
-    from .multisgp import load_theta_objective_multi, theta_objective_multi
+    mix.  It needs meta.kernel.softplus_params (the device maps theta through softplus): ValueError otherwise.
+
+    psi="exact": the objective over the closed-form Psi-statistics of the Gaussian inputs q_ins instead of their cubature points
+    (SE kernel only): sgp_theta_objective_psi host-paced, sgp_theta_descend_psi device-paced."""
+    from .multisgp import exact_theta_inputs, load_theta_objective_multi, theta_objective_multi
     theta = np.asarray(theta, dtype=np.float64)
     opt = optimizer if optimizer is not None else AdaMax()
     if device_paced:
@@ -311,13 +318,13 @@ def optimize_theta_multi(theta, y_data, q_ins, q_v, q_w, meta, *, steps: int = 1
             raise ValueError("optimize_theta_multi: device_paced=True maps theta through softplus on the device; "
                              "meta.kernel must have softplus_params set")
         from .meta import kernel_family
-        eng, D_in = load_theta_objective_multi(y_data, q_ins, q_v, q_w, meta)
+        eng, D_in = load_theta_objective_multi(y_data, q_ins, q_v, q_w, meta, psi)
         if theta.ndim != 1 or theta.size - 1 not in (1, D_in):
             raise ValueError(f"optimize_theta_multi: theta must be (sigma2, 1 or {D_in} lengthscales), got {theta.size} entries")
         sigma2, ell = meta.kernel(theta)
         set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))     # jitter and family of the descent
-        return _descend(theta, eng, int(steps), opt)
-    evaluate = grad_fn if grad_fn is not None else theta_objective_multi(y_data, q_ins, q_v, q_w, meta)
+        return _descend(theta, eng, int(steps), opt, exact_theta_inputs(y_data, q_ins, meta) if psi == "exact" else None)
+    evaluate = grad_fn if grad_fn is not None else theta_objective_multi(y_data, q_ins, q_v, q_w, meta, psi)
     for _ in range(int(steps)):
         _, g = evaluate(theta)
         opt.update(theta, np.asarray(g, dtype=np.float64))
@@ -490,12 +497,15 @@ def _vmp_gpssm_loop(meta, y, q_x, q_v, q_w, q_theta, v_prior, rule_out_fn, itera
 
 
 def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iterations=10, theta_steps=100, device_paced=True,
-                            v_prior_var=50.0, w_prior=None, optimizer=None, free_energy=True, psi="cubature"):
+                            v_prior_var=50.0, w_prior=None, optimizer=None, free_energy=True, psi="cubature",
+                            theta_psi="cubature"):
     """`PerformInference` of experiments/Pendulum_Wishart_2d.ipynb cell 16.  Per epoch: `vmp_gpssm` from the initialisation at
     the current theta (step 1), then `optimize_theta_multi` -- theta_steps AdaMax steps on neg_log_backwardmess_multi -- at the held
     q(x), q(v), q(W), with the targets mean(q(x_t)) and the inputs q(x_{t-1}), t = 1..T, as the notebook passes them (step 2).
     One optimiser is carried across the epochs (the notebook creates its Flux.AdaMax() once): `optimizer`, or a fresh AdaMax;
     device_paced passes its state through sgp_theta_descend's opt_state.  theta (raw) is updated in place.
+    theta_psi="exact": step 2 descends on the objective over the exact Psi-statistics of q(x_{t-1}) (`optimize_theta_multi(psi=
+    "exact")`) -- with psi="exact" the objective the sweeps of step 1 minimise; the default loads the cubature points as before.
     Returns (theta, free energies [epochs] (the last iteration's of every epoch, or []), (q_x, q_v, q_W) of the last epoch)."""
     theta = np.array(theta, dtype=np.float64)
     opt = optimizer if optimizer is not None else AdaMax()
@@ -506,6 +516,7 @@ def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iteratio
         if fe:
             fe_values.append(fe[-1])
         y_data = np.stack([q.m for q in q_x[1:]])
-        optimize_theta_multi(theta, y_data, q_x[:-1], q_v, q_w, meta, steps=theta_steps, optimizer=opt, device_paced=device_paced)
+        optimize_theta_multi(theta, y_data, q_x[:-1], q_v, q_w, meta, steps=theta_steps, optimizer=opt, device_paced=device_paced,
+                             psi=theta_psi)
         post = (q_x, q_v, q_w)
     return theta, fe_values, post

@@ -492,6 +492,45 @@ int sgp_theta_descend(sgp_handle* h, double* theta_raw /* 1 + n_ell, in/out */, 
                       double* opt_state /* 2 (1 + n_ell) + 2, in/out, may be NULL */,
                       double* values /* steps, may be NULL */, int64_t* counts /* 2, may be NULL */);
 
+/* ---- the kernel-parameter objective over exact Psi-statistics, its gradient and the descent on it ----
+ * The objective of sgp_theta_objective with the sums over cubature points replaced by exact expectations under the Gaussian
+ * inputs x_t ~ N(m_t, S_t) (SGP_KERNEL_SE only), for d_out = 1 .. 4.  With Psi1_t and Psi2 = sum_t Psi2_t as above, q(v) and
+ * W = mean(q_W) held, mu = [mu^(1) .. mu^(d_out)], S_q = sum_ij W_ij R_v^(ij), G = S_q - tr(W) (K_uu + jitter I)^-1 and
+ * s_t = sum_d mu^(d) (W y_t)_d:
+ *     f(theta) = 1/2 tr(W) sigma2 T + 1/2 tr(G Psi2) - sum_t s_t' Psi1_t
+ * (neg_log_backwardmess_multi; d_out = 1: neg_log_backwardmess_fast).  grad[1 + n_ell] = df / d(sigma2, ell), analytic, n_ell as of the
+ * last sgp_set_kernel (one shared lengthscale: the sum over the dimensions).
+ *
+ * The inputs are passed explicitly, laid out as sgp_sweep_local_psi takes them (mean D x T, cov D x D x T or NULL for S = 0, y_mean
+ * T x d_out column-major); no resident data are needed, and the calls work whether or not the resident statistics are exact ones.
+ * q(v) is the last finished sweep's, or sgp_set_posterior's when that came later; W is the last sgp_set_noise.  Statistics, K_uu
+ * chain, G and gradient are formed in call scratch at the kernel under evaluation: the resident statistics, K_uu chain, q(v),
+ * sgp_sweep_kind and what the other calls refuse are unchanged.  Outside call scratch the calls use what sgp_theta_objective and
+ * sgp_theta_descend use: the prediction calls' parameter mirror, the buffer R_v is formed in after sgp_set_posterior, and (the
+ * descent) the optimiser state and parameter block of the device-paced calls, all allocated on first use.  All sums run in a fixed order without atomics: identical calls agree bitwise, also under different
+ * SGP_PREDICT_CHUNK.
+ *
+ * sgp_theta_objective_psi evaluates at the current kernel and blocks.  info (2, may be NULL) = [the failing leading minor of K_uu or 0,
+ * the first node whose Lambda + S_t or Lambda + 2 S_t is not positive definite, + 1, or 0]; the return value is the positive entry
+ * (the node check comes first) and sgp_last_error names which of the two failed.
+ *
+ * sgp_theta_descend_psi is sgp_theta_descend on this objective: theta_raw, n_ell, steps, the AdaMax constants, opt_state and values
+ * as there; per step one evaluation at softplus(theta_k) and the optimiser step on the device; the host enqueues and waits once.
+ * Either failure stops the descent there: theta, the moments and the powers stay those of that step bitwise, values from that step
+ * on are NaN, and counts (3, may be NULL) = [steps taken, the failing K_uu minor or 0, the first indefinite node + 1 or 0].
+ * Afterwards the handle's kernel is softplus(theta_out).
+ *
+ * SGP_ERR_ARG: a kernel family other than SGP_KERNEL_SE; no inducing inputs, no kernel or no q(v); non-finite mean, cov or y_mean;
+ * n_nodes < 1 (the descent with steps = 0 returns 0 with nothing changed); an open sgp_train_* run; an installed all-reduce hook;
+ * for the descent also the argument checks of sgp_theta_descend. */
+int sgp_theta_objective_psi(sgp_handle* h, const double* mean /* D x T */, const double* cov /* D x D x T or NULL */,
+                            const double* y_mean /* T x d_out */, int64_t n_nodes, double* value,
+                            double* grad /* 1 + n_ell, may be NULL */, int64_t* info /* 2, may be NULL */);
+int sgp_theta_descend_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
+                          double* theta_raw /* 1 + n_ell, in/out */, int32_t n_ell, int32_t steps, double eta, double beta1,
+                          double beta2, double eps, double* opt_state /* 2 (1 + n_ell) + 2, in/out, may be NULL */,
+                          double* values /* steps, may be NULL */, int64_t* counts /* 3, may be NULL */);
+
 /* ---- building blocks exposed for tests / other callers (host pointers, blocking) ------------
  * K = sigma2 * exp(-0.5 |(a-b)/ell|^2): kernelmatrix(kernel(theta), A, B) of KernelFunctions.jl as called at
  * GPnode/UniSGPnode.jl:102,153; A is D x na, B is D x nb, K is na x nb column-major. */

@@ -557,6 +557,31 @@ function theta_descend!(meta::HipSGPMeta, Î¸::Vector{Float64}, steps::Integer; Î
     return Î¸, values, Int(counts[1])
 end
 
+# ---- the same objective and descent over the exact Psi-statistics of Gaussian inputs x_t ~ N(m_t, S_t) (SE kernel only;
+# sgp_theta_objective_psi, sgp_theta_descend_psi): m is D Ã— T, S is D Ã— D Ã— T or nothing (S = 0), y is T Ã— d_out.  No resident data are
+# needed; q(v) and W are the handle's.  theta_objective_psi returns (value, gradient w.r.t. (ÏƒÂ², â„“...)); theta_descend_psi! is
+# theta_descend! on it.  PosDefException(t + 1) names an indefinite node, PosDefException(k) a K_uu that failed.
+function theta_objective_psi(h::Handle, m::Matrix{Float64}, S, y::Matrix{Float64}, n_ell::Integer)
+    T = size(m, 2); value = Ref{Float64}(0.0); grad = zeros(1 + n_ell); info = zeros(Int64, 2)
+    check(ccall((:sgp_theta_objective_psi, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, m, S === nothing ? C_NULL : S, y, T, value, grad, info), h.ptr)
+    return value[], grad
+end
+
+function theta_descend_psi!(meta::HipSGPMeta, m::Matrix{Float64}, S, y::Matrix{Float64}, Î¸::Vector{Float64}, steps::Integer;
+                            Î· = 1e-3, Î² = (0.9, 0.999), Ïµ = 1e-8, state::Union{Nothing, Vector{Float64}} = nothing)
+    h = meta.handle
+    state === nothing || length(state) == 2 * length(Î¸) + 2 || throw(ArgumentError("theta_descend_psi!: state needs 2 length(Î¸) + 2 entries"))
+    values = fill(NaN, max(steps, 0)); counts = zeros(Int64, 3)
+    check(ccall((:sgp_theta_descend_psi, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Int32, Int32, Float64, Float64, Float64,
+                 Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, m, S === nothing ? C_NULL : S, y, size(m, 2), Î¸, length(Î¸) - 1, steps, Î·, Î²[1], Î²[2], Ïµ,
+                state === nothing ? C_NULL : state, values, counts), h.ptr)
+    return Î¸, values, Int(counts[1])
+end
+
 # The classification loop (experiments/classification_banana.ipynb cell 9: `y[i] ~ Probit(f[i])`, q(w) = GammaShapeRate carried
 # over the minibatches, q(v) never reset): labels 0 / 1 in y; returns (Î¸, shape, rate).  sgp_train_likelihood turns the run
 # opened by sgp_train_begin into this loop -- forward message, Probit moment matching, Gamma update and AdaMax on the device.

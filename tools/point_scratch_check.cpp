@@ -1,8 +1,8 @@
 // Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over grids of shapes, the
-// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message and layout_psi hand out are
+// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi and layout_psi_theta hand out are
 // pairwise disjoint at the sizes their consumers need (stated here independently of the layout functions), every piece starts a
 // multiple of Carver::ALIGN doubles from the base, pass 2 hands out the total pass 1 summed and the last piece ends there.  The
-// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts and layout_psi get an allocation of
+// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi and layout_psi_theta get an allocation of
 // exactly their total per shape and every piece is written end to end, so that the sanitizer sees a write past it.  No GPU:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o tools/point_scratch_check tools/point_scratch_check.cpp
 //   (or any C++17 compiler with -fsanitize=address,undefined) && tools/point_scratch_check
@@ -198,6 +198,46 @@ long psi_sweep() {
                         }
     return shapes;
 }
+// sgp_theta_objective_psi / sgp_theta_descend_psi over their grid, each shape in an allocation of its own: with and without covariances,
+// the accumulator tiles of psi_ranges, no steps (the objective) and 100 (the descent)
+long psi_theta_sweep() {
+    long shapes = 0;
+    const size_t slots = 33, tile_slots = 65;                 // GRAD_SLOTS, PSI_TP_SLOTS
+    for (int M : {1, 65, 130})
+        for (int D : {1, 5, 32})
+            for (int dout : {1, 4})
+                for (int64_t n : {1, 65, 300})
+                    for (int64_t chunk : {(int64_t)64, (n + 63) / 64 * 64})
+                        for (int opt = 0; opt < 4; ++opt) {
+                            const bool cov = opt & 1;
+                            const size_t steps = (opt & 2) ? 100 : 0;
+                            const int Mp = (M + TB - 1) / TB * TB, T = Mp / TB, ntiles = T * (T + 1) / 2;
+                            const int64_t want = std::min<int64_t>((n + 7) / 8, std::max(1, 1024 / ntiles)), len = (n + want - 1) / want;
+                            const size_t acc = (size_t)((n + len - 1) / len) * ntiles;
+                            const PointShape s{Mp, 0, T, D, dout, POTRF_SCRATCH, std::min(chunk, (n + 63) / 64 * 64), n, n};
+                            check("psi_theta", s, 0, nullptr, 0, true, [&](Carver& c) {
+                                PsiThetaScratch b;
+                                layout_psi_theta(c, s, cov, acc, slots, tile_slots, steps, &b);
+                                const size_t nn = (size_t)n, ch = (size_t)s.chunk, mm = (size_t)Mp * Mp * d;
+                                const std::vector<Piece> all = {
+                                    {"Mean", b.Mean, nn * D * d}, {"Cov", b.Cov, cov ? nn * D * D * d : 0}, {"Y", b.Y, nn * dout * d},
+                                    {"Bad", b.Bad, nn * sizeof(int)}, {"Lin", b.Lin, nn * slots * d}, {"G2", b.G2, ch * D * Mp * d},
+                                    {"H2", b.H2, ch * D * Mp * d}, {"E2", b.E2, ch * D * d}, {"Cw", b.Cw, ch * d},
+                                    {"Acc", b.Acc, acc * TB * TB * d}, {"Wd", b.Wd, acc * D * 256 * d},
+                                    {"TilePart", b.TilePart, (size_t)ntiles * tile_slots * d}, {"Kuu", b.Kuu, mm}, {"Wk", b.Wk, mm},
+                                    {"Kinv", b.Kinv, mm}, {"G", b.G, mm}, {"Gpart", b.Gpart, (size_t)Mp * d}, {"Psi2", b.Psi2, mm},
+                                    {"T1", b.T1, mm}, {"H", b.H, mm}, {"PartUU", b.PartUU, (size_t)T * T * slots * d},
+                                    {"Out", b.Out, 2 * slots * d}, {"Status", b.Status, sizeof(int)}, {"Vals", b.Vals, steps * d},
+                                    {"Pscr", b.Pscr, (size_t)POTRF_SCRATCH * d}, {"Info", b.Info, sizeof(int)}};
+                                std::vector<Piece> p;
+                                for (const Piece& q : all)
+                                    if (q.bytes) p.push_back(q);                  // (a piece that is not wanted has no extent)
+                                return p;
+                            });
+                            ++shapes;
+                        }
+    return shapes;
+}
 }  // namespace
 
 int main() {
@@ -210,7 +250,8 @@ int main() {
     std::free(base);
     const long mean_only = mean_only_sweep();
     const long psi = psi_sweep();
-    std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes, %ld psi shapes: %ld failure(s)\n", panel,
-                largest, mean_only, psi, failures);
+    const long psi_theta = psi_theta_sweep();
+    std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes, %ld psi shapes, %ld psi-theta shapes: "
+                "%ld failure(s)\n", panel, largest, mean_only, psi, psi_theta, failures);
     return failures ? 1 : 0;
 }

@@ -54,7 +54,8 @@ def inducing_inputs():
     return np.stack([xu1, xu2], axis=1)
 
 
-def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cubature", theta_psi="cubature"):
+def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cubature", theta_psi="cubature",
+        in_psi="cubature"):
     from gaussianprocessnode_amd.cubature import srcubature
     from gaussianprocessnode_amd.meta import SMSE, MultiSGPMeta, SEARDKernel, softplus
     from gaussianprocessnode_amd.train import perform_inference_gpssm, vmp_gpssm
@@ -68,10 +69,11 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
     try:
         t0 = time.perf_counter()
         theta, fe, _ = perform_inference_gpssm(theta0, y, meta, P=P, x0_prior=x0_prior, epochs=epochs, device_paced=device_paced,
-                                                psi=psi, theta_psi=theta_psi)
+                                                psi=psi, theta_psi=theta_psi, in_psi=in_psi)
         t_train = time.perf_counter() - t0
         t0 = time.perf_counter()
-        q_x, _, q_w, fe_smooth = vmp_gpssm(theta, y, meta, P=P, x0_prior=x0_prior, iterations=30, free_energy=True, psi=psi)
+        q_x, _, q_w, fe_smooth = vmp_gpssm(theta, y, meta, P=P, x0_prior=x0_prior, iterations=30, free_energy=True, psi=psi,
+                                           in_psi=in_psi)
         t_smooth = time.perf_counter() - t0
     finally:
         if meta.engine is not None:
@@ -80,11 +82,13 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
     return {
         "experiment": "pendulum GP-SSM PerformInference (experiments/Pendulum_Wishart_2d.ipynb)",
         "epochs": epochs, "nodes": nodes, "M": int(len(Xu)), "pacing": "device" if device_paced else "host", "seed": seed, "psi": psi, "theta_psi": theta_psi,
+        "in_psi": in_psi,
         "train_seconds": t_train, "smoothing_seconds": t_smooth,
         "smse": [SMSE(x_true[:, k], est[:, k]) for k in range(2)],
         "smse_observations": [SMSE(x_true[:, k], y[:, k]) for k in range(2)],
         "theta_softplus": [float(v) for v in softplus(theta)],
         "free_energy_last_epoch": fe[-1] if fe else None, "free_energy_smoothing": fe_smooth[-1],
+        "free_energy_epochs": [float(v) for v in fe],
         "mean_W": np.asarray(q_w.mean()).tolist(),
         "reference": {"train_seconds": 1615.249575, "smoothing_seconds": 15.0, "smse": [0.005454764265443909, 0.0010773936260490339],
                       "note": "other data (Julia's MersenneTwister(124)), hardware unstated"},
@@ -101,5 +105,9 @@ if __name__ == "__main__":
                     help="Psi-statistics of the :out and :v steps: srcubature points, or the SE closed form (sgp_psi_stats)")
     ap.add_argument("--theta-psi", choices=("cubature", "exact"), default="cubature",
                     help="statistics of the theta phase: srcubature points, or the SE closed form (sgp_theta_descend_psi)")
+    ap.add_argument("--in-psi", choices=("cubature", "exact"), default="cubature",
+                    help="the q(x) update: moments over srcubature points of the :in closure, or natural-gradient steps on the SE closed "
+                         "form (sgp_psi_in_grad)")
     args = ap.parse_args()
-    print(json.dumps(run(args.epochs, args.nodes, args.seed, not args.host_paced, psi=args.psi, theta_psi=args.theta_psi)))
+    print(json.dumps(run(args.epochs, args.nodes, args.seed, not args.host_paced, psi=args.psi, theta_psi=args.theta_psi,
+                         in_psi=args.in_psi)))

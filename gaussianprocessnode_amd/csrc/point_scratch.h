@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
-// sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi).  Plain C++, no HIP: all
-// layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
+// sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad).  Plain C++,
+// no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -216,6 +216,42 @@ static inline void layout_psi_theta(Carver& c, const PointShape& p, bool has_cov
     b->Out = c.take<double>(2 * slots);
     b->Status = c.take<int>(1);
     b->Vals = c.take<double>(steps);
+    b->Pscr = c.take<double>((size_t)p.potrf_scratch);
+    b->Info = c.take<int>(1);
+}
+
+// sgp_psi_in_grad (p.n = p.n_nodes = the nodes, p.chunk nodes per chunk): the inputs, status words and results of all nodes (energy,
+// gamma [node][D], Gamma [node][D][D]); one chunk of g ([D][Mp][chunk]), of the per-node records ([rec_slots][chunk]) and of the
+// slices' running sums ([slice][sum_slots][chunk]); the weights E and the K_uu chain at the current kernel (K_uu -> L_K, W_K,
+// K_uu^-1), G and its unused column shares; one factorisation's scratch with its status word
+struct PsiInScratch {
+    double *Mean, *Cov, *Y;
+    int* Bad;
+    double *Energy, *GradMean, *GradCov;
+    double *G2, *Rec, *Part;
+    double *E, *Kuu, *Wk, *Kinv, *G, *Gpart;
+    double* Pscr;
+    int* Info;
+};
+static inline void layout_psi_in(Carver& c, const PointShape& p, bool has_cov, bool want_cov, size_t nslices, size_t sum_slots,
+                                 size_t rec_slots, PsiInScratch* b) {
+    const size_t n = (size_t)p.n, D = (size_t)p.D, ch = (size_t)p.chunk, mm = (size_t)p.Mp * p.Mp;
+    b->Mean = c.take<double>(n * D);
+    b->Cov = c.take<double>(has_cov ? n * D * D : 0);
+    b->Y = c.take<double>(n * p.dout);
+    b->Bad = c.take<int>(n);
+    b->Energy = c.take<double>(n);
+    b->GradMean = c.take<double>(n * D);
+    b->GradCov = c.take<double>(want_cov ? n * D * D : 0);
+    b->G2 = c.take<double>(ch * D * p.Mp);
+    b->Rec = c.take<double>(ch * rec_slots);
+    b->Part = c.take<double>(ch * nslices * sum_slots);
+    b->E = c.take<double>(mm);
+    b->Kuu = c.take<double>(mm);
+    b->Wk = c.take<double>(mm);
+    b->Kinv = c.take<double>(mm);
+    b->G = c.take<double>(mm);
+    b->Gpart = c.take<double>((size_t)p.Mp);
     b->Pscr = c.take<double>((size_t)p.potrf_scratch);
     b->Info = c.take<int>(1);
 }

@@ -117,6 +117,7 @@ struct SweepPlan {
 //   next_kind (once per record)                 checked, or drops reuse: its sweep ended without K_uu factored / with a wait given up
 //   sgp_sweep_local_psi                         fills the record, drops reuse, exact_psi; data_gen++; have_data = false (sgp_set_data clears exact_psi)
 //   sgp_theta_objective_psi                     nothing: everything it forms is in call scratch
+//   sgp_psi_in_grad                             nothing: everything it forms is in call scratch
 //   sgp_theta_descend_psi                       nothing: the kernel moved (hParams, params_gen++), nothing resident was rewritten, and
 //                                               kernel_matches, which compares values, turns the resident statistics down
 struct StatsRecord {
@@ -3556,6 +3557,117 @@ extern "C" int sgp_theta_descend_psi(sgp_handle* h, const double* mean, const do
     const int kuu = st.stop <= -2.0 ? 0 : (int)st.stop;
     if (counts) { counts[0] = (int64_t)st.steps; counts[1] = kuu > 0 ? kuu : 0; counts[2] = node; }
     if (st.stop != 0.0) return psi_theta_status(h, std::string(name) + ", step " + std::to_string((int64_t)st.steps), node, kuu);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The exact-Psi input messages (include/sgp_hip.h: sgp_psi_in_grad; kernels: k_psi_in_* / k_psi2_in_accumulate in
+// sgp_kernels.hip.h).  Everything it forms lives in call scratch, the K_uu chain at the current kernel too; outside it
+// the call touches what sgp_theta_objective_psi touches: the K_uu chain's parameter mirror (dXusK / dParamsK) and dThetaMulti, where
+// theta_Rv forms R_v when sgp_set_posterior came last.
+// ------------------------------------------------------------------------------------------------
+// The slices of k_psi2_in_accumulate's lower triangle: a function of the call's node count and M alone -- the chunking takes no
+// part, so the sums do not depend on it.  About 1024 workgroups where the triangle has that many work units.
+static int psi_in_slices(int64_t T, int M) {
+    const int64_t blocks = (T + PSI_IN_NODES - 1) / PSI_IN_NODES, units = (M + PSI_IN_ROWS - 1) / PSI_IN_ROWS;
+    return (int)std::min<int64_t>(units, std::max<int64_t>(1, 1024 / blocks));
+}
+
+static PointShape psi_in_shape(const sgp_handle* h, int64_t T) {
+    return point_shape(h, (int64_t)h->D * h->Mp + (int64_t)psi_in_slices(T, h->M) * psi_in_sums(h->D) + psi_in_rec(h->D), T, T);
+}
+
+// One evaluation on `s`: the K_uu chain at the current kernel, G, the weights E, then per chunk the nodes' records and g, the
+// slices' sums and the finish into b.Energy / b.GradMean / b.GradCov.  Rv: R_v of the held q(v) (theta_Rv), w: the held mean(q_W).
+template <int D>
+static int psi_in_enqueue(sgp_handle* h, hipStream_t s, const PsiInScratch& b, const PointShape& shape, bool has_cov, bool want_energy,
+                          bool want_cov, const double* Rv, const MeanW& w) {
+    const int M = h->M, Mp = h->Mp, dout = h->dout, Tn = h->T;
+    const int64_t T = shape.n, chunk = shape.chunk;
+    const int nslices = psi_in_slices(T, M);
+    HIPCHK(h, hipMemsetAsync(b.Pscr, 0, sizeof(double) * POTRF_SCRATCH, s));
+    HIPCHK(h, hipMemsetAsync(b.Info, 0, sizeof(int), s));
+    launch_prep_xu(h, s, h->dXusK, h->hParams, h->dParamsK);
+    hipLaunchKernelGGL(k_gram_uu<SGP_KERNEL_SE>, dim3(Tn, Tn), dim3(256), 0, s, h->dXusK, b.Kuu, h->dParamsK, M, Mp, D);
+    launch_potrf(b.Kuu, Mp, Tn, b.Info, M, b.Pscr, s, b.Wk);
+    launch_ata(b.Wk, b.Kinv, Mp, Tn, s);
+    // (k_form_G_multi also sums column shares of tr(G Psi2) against its Psi2 argument: not used here, any Mp x Mp matrix will do)
+    hipLaunchKernelGGL(k_form_G_multi, dim3(Mp), dim3(256), 0, s, Rv, h->Qp, (const double*)b.Kinv, (const double*)b.Kinv, w.W, w.trace,
+                       b.G, b.Gpart, M, Mp, dout);
+    hipLaunchKernelGGL(k_psi_in_weights, dim3(Mp), dim3(256), 0, s, (const double*)b.G, (const double*)h->dXusK,
+                       (const Params*)h->dParamsK, b.E, M, Mp, D);
+    for (int64_t t0 = 0; t0 < T; t0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, T - t0);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi_in_prep<PSI_IN_MAXD>), dim3((unsigned)nc), dim3(64), 0, s, (const double*)h->dXu,
+                           (const double*)b.Mean, has_cov ? (const double*)b.Cov : (const double*)nullptr, (const double*)b.Y, T, t0,
+                           (const double*)h->dMu, w.W, (const Params*)h->dParamsK, b.G2, b.Rec, b.Bad, chunk, M, Mp, D, dout);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi2_in_accumulate<D>),
+                           dim3((unsigned)((nc + PSI_IN_NODES - 1) / PSI_IN_NODES), (unsigned)nslices), dim3(PSI_IN_NODES), 0, s,
+                           (const double*)b.G2, (const double*)b.E, b.Part, nc, chunk, nslices, M, Mp);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi_in_finish<D>), dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, s, (const double*)b.Part,
+                           (const double*)b.Rec, t0, nc, chunk, nslices, want_energy ? b.Energy : (double*)nullptr, b.GradMean,
+                           want_cov ? b.GradCov : (double*)nullptr);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+extern "C" int sgp_psi_in_grad(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
+                               double* energy, double* grad_mean, double* grad_cov, int64_t* info) {
+    const char* name = "sgp_psi_in_grad";
+    if (!h || !mean || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_psi_in_grad: null argument");
+    if (info) info[0] = info[1] = 0;
+    if (!grad_mean) return refuse(h, name, "grad_mean must not be NULL");
+    if (n_nodes < 1) return refuse(h, name, "n_nodes must be >= 1");
+    if (h->D > PSI_IN_MAXD) return refuse(h, name, "D > 8 is not supported (the per-node sums are kept in registers)");
+    if (int rc = psi_theta_ready(h, name, mean, cov, y_mean, n_nodes)) return rc;
+    if (int wrc = sync_checked(h)) return wrc;
+    hipStream_t s = h->own;
+    const PointShape shape = psi_in_shape(h, n_nodes);
+    const size_t T = (size_t)n_nodes, D = (size_t)h->D;
+    PsiInScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) {
+            layout_psi_in(c, shape, cov != nullptr, grad_cov != nullptr, (size_t)psi_in_slices(n_nodes, h->M), (size_t)psi_in_sums(h->D),
+                          (size_t)psi_in_rec(h->D), &b);
+        }))
+        return crc;
+    HIPCHK(h, hipMemcpy(b.Mean, mean, sizeof(double) * T * D, hipMemcpyHostToDevice));
+    if (cov) HIPCHK(h, hipMemcpy(b.Cov, cov, sizeof(double) * T * D * D, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Y, y_mean, sizeof(double) * T * h->dout, hipMemcpyHostToDevice));
+    const MeanW w(h);
+    const double* Rv = h->dR;
+    if (int rrc = theta_Rv(h, s, &Rv)) return rrc;
+    int rc = 0;
+    auto run = [&](auto DD) {
+        rc = psi_in_enqueue<decltype(DD)::value>(h, s, b, shape, cov != nullptr, energy != nullptr, grad_cov != nullptr, Rv, w);
+    };
+    switch (h->D) {
+        case 1: run(std::integral_constant<int, 1>{}); break;
+        case 2: run(std::integral_constant<int, 2>{}); break;
+        case 3: run(std::integral_constant<int, 3>{}); break;
+        case 4: run(std::integral_constant<int, 4>{}); break;
+        case 5: run(std::integral_constant<int, 5>{}); break;
+        case 6: run(std::integral_constant<int, 6>{}); break;
+        case 7: run(std::integral_constant<int, 7>{}); break;
+        default: run(std::integral_constant<int, 8>{}); break;
+    }
+    // whatever was enqueued reads the call's buffers: wait before anything else, also on an error path
+    const hipError_t werr = wait_stream(s);
+    if (rc) return rc;
+    HIPCHK(h, werr);
+    HIPCHK(h, hipGetLastError());
+    int kuu = 0;
+    HIPCHK(h, hipMemcpy(&kuu, b.Info, sizeof kuu, hipMemcpyDeviceToHost));
+    std::vector<int> bad(T);
+    HIPCHK(h, hipMemcpy(bad.data(), b.Bad, sizeof(int) * T, hipMemcpyDeviceToHost));
+    int node = 0;
+    for (size_t t = 0; t < T && !node; ++t)
+        if (bad[t]) node = t + 1 > (size_t)std::numeric_limits<int>::max() ? std::numeric_limits<int>::max() : (int)(t + 1);
+    if (info) { info[0] = kuu > 0 ? kuu : 0; info[1] = node; }
+    if (int src = psi_theta_status(h, name, node, kuu)) return src;
+    if (energy) HIPCHK(h, hipMemcpy(energy, b.Energy, sizeof(double) * T, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(grad_mean, b.GradMean, sizeof(double) * T * D, hipMemcpyDeviceToHost));
+    if (grad_cov) HIPCHK(h, hipMemcpy(grad_cov, b.GradCov, sizeof(double) * T * D * D, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -4754,4 +4754,300 @@ __global__ void k_descend_step_psi(TrainState* __restrict__ st, const double* __
     write_kernel_params(st, src, D, n_ell);
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// The exact-Psi input messages (sgp_psi_in_grad): per node t with input x_t ~ N(m_t, S_t) the part of its average
+// energy that depends on the input and its derivatives with respect to m_t and S_t,
+//   U_t     = 1/2 A_t - a1_t
+//   gamma_t = -1/2 b_t + b1_t
+//   Gamma_t = -1/2 A_t P_2 + 1/4 C_t + 1/2 a1_t P_1 - 1/2 C1_t                                     P_c = (Lambda + c S_t)^-1
+//   A_t, b_t, C_t    = sum_ij G_ij Psi2_t[i,j] (1, u_ij, u_ij u_ij'),   u_ij = h2_ti + h2_tj,   h^(c)_tm = P_c (m_t - z_m)
+//   a1_t, b1_t, C1_t = sum_m s_t[m] Psi1_t[m] (1, h1_tm, h1_tm h1_tm')
+// With Lambda + c S = C C', L = C^-1 and g = L (m_t - z): h = L' g and P_c = L' L, so every sum is taken over g -- v_ij = g_i + g_j --
+// and carried into h once per node: b = L' sum w v, C = L' (sum w v v') L.  Only g of Lambda + 2 S travels between the kernels.
+// D <= PSI_IN_MAXD; the sums are packed [1 | D | D (D + 1) / 2 (lower, row-major)].  No atomics; every sum has a fixed order.
+// ------------------------------------------------------------------------------------------------
+constexpr int PSI_IN_MAXD = 8;
+constexpr int PSI_IN_ROWS = 8;              // rows of the lower triangle per work unit of k_psi2_in_accumulate (host: psi_in_slices)
+constexpr int PSI_IN_NODES = 256;           // nodes per workgroup of k_psi2_in_accumulate
+__host__ __device__ constexpr int psi_in_packed(int D) { return D * (D + 1) / 2; }
+__host__ __device__ constexpr int psi_in_sums(int D) { return 1 + D + psi_in_packed(D); }           // running sums per node
+__host__ __device__ constexpr int psi_in_rec(int D) { return 2 + D + 3 * psi_in_packed(D); }        // record per node
+
+// Per node (one wavefront each; grid = the nodes of this chunk, t0 = its first node), a sibling of k_psi_theta_prep: both factors and
+// their inverses in LDS; g of Lambda + 2 S for every inducing input as G2 [D][Mp][chunk] (node fastest: what k_psi2_in_accumulate's
+// lanes read side by side; rows m >= M zero); and the node's record rec [psi_in_rec(D)][chunk]:
+//   c_t = prod_d(ell_d / C_dd) of Lambda + 2 S | a1 | sum_m s Psi1 g1 (D) | sum_m s Psi1 g1 g1' (packed) | L_1 (packed) | L_2 (packed)
+// the Psi1 sums with lane l summing m = l, l + 64, .. in order, then the xor butterfly.  A node whose factorisation fails sets
+// bad[t] and writes zeros for all of it.  mean, cov, y (T x d_out column-major), bad are the call's; mu [d_out][M]; W by value.
+template <int DCAP>
+__global__ void __launch_bounds__(64) k_psi_in_prep(const double* __restrict__ Xu, const double* __restrict__ mean,
+                                                    const double* __restrict__ cov, const double* __restrict__ y, int64_t T, int64_t t0,
+                                                    const double* __restrict__ mu, OutMat W, const Params* __restrict__ P,
+                                                    double* __restrict__ G2, double* __restrict__ rec, int* __restrict__ bad,
+                                                    int64_t chunk, int M, int Mp, int D, int d_out) {
+    static_assert(DCAP <= PSI_IN_MAXD, "the packed sums are sized for D <= PSI_IN_MAXD");
+    __shared__ double A1[MAXD * PSI_LD], A2[MAXD * PSI_LD], C1[MAXD * PSI_LD], C2[MAXD * PSI_LD];
+    __shared__ double r1[MAXD], r2[MAXD], e1[MAXD], e2[MAXD], mt[MAXD], ell[MAXD];
+    __shared__ int failed;
+    const int lane = threadIdx.x;
+    const int64_t tc = blockIdx.x, t = t0 + tc;
+    const int pk = psi_in_packed(D), nrec = psi_in_rec(D);
+    if (lane == 0) failed = 0;
+    if (lane < D) { mt[lane] = mean[(size_t)t * D + lane]; ell[lane] = 1.0 / P->inv_ell[lane]; }
+    __syncthreads();
+    const double* S = cov ? cov + (size_t)t * D * D : nullptr;
+    psi_factor_inv(A1, C1, r1, e1, &failed, S, ell, 1.0, D, lane);
+    psi_factor_inv(A2, C2, r2, e2, &failed, S, ell, 2.0, D, lane);
+    if (failed) {                                             // (uniform)
+        if (lane == 0) bad[t] = 1;
+        for (int k = lane; k < nrec; k += 64) rec[(size_t)k * chunk + tc] = 0.0;
+        for (int e = lane; e < D * Mp; e += 64) G2[(size_t)e * chunk + tc] = 0.0;
+        return;
+    }
+    double det1 = 1.0, det2 = 1.0;                            // prod_d ell_d / C_dd, in the order d = 0, 1, ..
+    for (int d = 0; d < D; ++d) { det1 *= ell[d] * r1[d]; det2 *= ell[d] * r2[d]; }
+    double wy[MAXO];                                          // (W y_t)_o
+#pragma unroll
+    for (int o = 0; o < MAXO; ++o) {
+        wy[o] = 0.0;
+        if (o < d_out)
+            for (int e = 0; e < d_out; ++e) wy[o] = fma(W.v[o + e * d_out], y[(size_t)e * T + t], wy[o]);
+    }
+    const double s2 = P->sigma2;
+    double l0 = 0.0, lb[DCAP], lc[psi_in_packed(DCAP)];
+#pragma unroll
+    for (int d = 0; d < DCAP; ++d) lb[d] = 0.0;
+#pragma unroll
+    for (int k = 0; k < psi_in_packed(DCAP); ++k) lc[k] = 0.0;
+    for (int m = lane; m < Mp; m += 64) {
+        asm volatile("" ::: "memory");                        // (the factors are re-read from LDS for every m, as in k_psi_theta_prep)
+        double diff[DCAP], g[DCAP];
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d) diff[d] = (d < D && m < M) ? mt[d] - Xu[(size_t)m * D + d] : 0.0;
+        const double q1 = psi_solve<DCAP>(g, diff, A1, r1, D);
+        if (m < M) {
+            double st = 0.0;
+#pragma unroll
+            for (int o = 0; o < MAXO; ++o)
+                if (o < d_out) st = fma(mu[(size_t)o * M + m], wy[o], st);
+            const double sp = st * (s2 * det1 * exp(-0.5 * q1));
+            l0 += sp;
+#pragma unroll
+            for (int i = 0; i < DCAP; ++i) {                  // (g is zero beyond D: the sums there stay zero and are not written)
+                const double wv = sp * g[i];
+                lb[i] += wv;
+#pragma unroll
+                for (int j = 0; j <= i; ++j) lc[i * (i + 1) / 2 + j] = fma(wv, g[j], lc[i * (i + 1) / 2 + j]);
+            }
+        }
+        psi_solve<DCAP>(g, diff, A2, r2, D);
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d)
+            if (d < D) G2[((size_t)d * Mp + m) * chunk + tc] = g[d];
+    }
+    for (int s = 32; s > 0; s >>= 1) l0 += __shfl_xor(l0, s);
+#pragma unroll
+    for (int d = 0; d < DCAP; ++d)
+        if (d < D) {                                          // (uniform)
+            double v = lb[d];
+            for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+            if (lane == 0) rec[(size_t)(2 + d) * chunk + tc] = v;
+        }
+#pragma unroll
+    for (int k = 0; k < psi_in_packed(DCAP); ++k)
+        if (k < pk) {                                         // (uniform; packed row-major: the first D (D + 1) / 2 entries are D's own)
+            double v = lc[k];
+            for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+            if (lane == 0) rec[(size_t)(2 + D + k) * chunk + tc] = v;
+        }
+    if (lane == 0) { bad[t] = 0; rec[tc] = det2; rec[(size_t)chunk + tc] = l0; }
+    if (lane < D)                                             // lane j owns column j of both inverses
+        for (int i = lane; i < D; ++i) {
+            rec[(size_t)(2 + D + pk + i * (i + 1) / 2 + lane) * chunk + tc] = C1[i * PSI_LD + lane];
+            rec[(size_t)(2 + D + 2 * pk + i * (i + 1) / 2 + lane) * chunk + tc] = C2[i * PSI_LD + lane];
+        }
+}
+
+// Once per call: E_ij = sigma2^2 G_ij exp(-1/4 sum_d (z_id - z_jd)^2 / ell_d^2) on the lower triangle i >= j of the M x M block
+// (E [j][Mp] column-major, zero elsewhere), the node-independent factor of G_ij Psi2_t[i,j].  Xus: the scaled inducing inputs [d][Mp]
+// (k_prep_xu); Gm: G (Mp x Mp).  grid = Mp columns.
+__global__ void __launch_bounds__(256) k_psi_in_weights(const double* __restrict__ Gm, const double* __restrict__ Xus,
+                                                        const Params* __restrict__ P, double* __restrict__ E, int M, int Mp, int D) {
+    const int j = blockIdx.x;
+    const double s4 = P->sigma2 * P->sigma2;
+    for (int i = threadIdx.x; i < Mp; i += 256) {
+        double v = 0.0;
+        if (i >= j && i < M && j < M) {
+            double q = 0.0;
+            for (int d = 0; d < D; ++d) { const double u = Xus[(size_t)d * Mp + i] - Xus[(size_t)d * Mp + j]; q = fma(u, u, q); }
+            v = s4 * Gm[(size_t)j * Mp + i] * exp(-0.25 * q);
+        }
+        E[(size_t)j * Mp + i] = v;
+    }
+}
+
+// The hot path, O(T M^2 D^2): the sums over the M x M entries PER NODE.  Lane = node: workgroup (x, y) owns the PSI_IN_NODES nodes
+// from 256 x of the chunk and slice y of the lower triangle -- the work units (PSI_IN_ROWS rows i with their columns j <= i) y,
+// y + nslices, .. in order, rows and columns ascending.  A thread keeps its node's psi_in_sums(D) running sums in registers:
+//   w = E_ij (2 for j < i) exp(-1/4 |g_i + g_j|^2):   sum w | sum w v | sum w v v' (packed),   v = g_i + g_j
+// (c_t and the step into h are applied by k_psi_in_finish).  E of a unit's rows and 64 columns is staged in LDS with the factor 2 in
+// it and read as a broadcast; g_i stays in registers over the run of j; g_j is one coalesced load per dimension.  No cross-lane sum.
+// part [slice][psi_in_sums(D)][chunk]: written, never added to, so the result does not depend on the chunking.  nc: the chunk's nodes.
+template <int D>
+__global__ void __launch_bounds__(PSI_IN_NODES) k_psi2_in_accumulate(const double* __restrict__ G2, const double* __restrict__ E,
+                                                                     double* __restrict__ part, int64_t nc, int64_t chunk, int nslices,
+                                                                     int M, int Mp) {
+    constexpr int NS = psi_in_sums(D), R = PSI_IN_ROWS;
+    __shared__ double Es[R * TB];
+    const int tid = threadIdx.x, slice = blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * PSI_IN_NODES + tid;
+    const bool active = n < nc;
+    const double* gp = G2 + (active ? n : 0);
+    const size_t dstride = (size_t)Mp * chunk;
+    const int nunits = (M + R - 1) / R;
+    double acc[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) acc[k] = 0.0;
+    for (int u = slice; u < nunits; u += nslices) {
+        const int i0 = u * R, i1 = i0 + R < M ? i0 + R : M;   // rows i0 .. i1 - 1
+        for (int j0 = 0; j0 < i1; j0 += TB) {
+            __syncthreads();
+            for (int e = tid; e < R * TB; e += PSI_IN_NODES) {
+                const int i = i0 + (e >> 6), j = j0 + (e & 63);
+                Es[e] = (i < i1 && j <= i) ? (j < i ? 2.0 : 1.0) * E[(size_t)j * Mp + i] : 0.0;
+            }
+            __syncthreads();
+            if (!active) continue;
+            for (int i = i0; i < i1; ++i) {
+                const int jn = i - j0 + 1 < TB ? i - j0 + 1 : TB;      // columns j0 .. j0 + jn - 1 (none when j0 > i)
+                if (jn <= 0) continue;
+                double gi[D], gj[D];
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    gi[d] = gp[d * dstride + (size_t)i * chunk];
+                    gj[d] = gp[d * dstride + (size_t)j0 * chunk];
+                }
+                const double* es = Es + (i - i0) * TB;
+                for (int jj = 0; jj < jn; ++jj) {
+                    double v[D];
+                    double q = 0.0;
+#pragma unroll
+                    for (int d = 0; d < D; ++d) { v[d] = gi[d] + gj[d]; q = fma(v[d], v[d], q); }
+                    if (jj + 1 < jn) {                        // (uniform) the next column's g, under this one's arithmetic
+#pragma unroll
+                        for (int d = 0; d < D; ++d) gj[d] = gp[d * dstride + (size_t)(j0 + jj + 1) * chunk];
+                    }
+                    const double w = es[jj] * exp(-0.25 * q);
+                    acc[0] += w;
+#pragma unroll
+                    for (int a = 0; a < D; ++a) {
+                        const double wv = w * v[a];
+                        acc[1 + a] += wv;
+#pragma unroll
+                        for (int b = 0; b <= a; ++b) acc[1 + D + a * (a + 1) / 2 + b] = fma(wv, v[b], acc[1 + D + a * (a + 1) / 2 + b]);
+                    }
+                }
+            }
+        }
+    }
+    if (active)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) part[((size_t)slice * NS + k) * chunk + n] = acc[k];
+}
+
+// X (lower triangle, packed) += L' N L for a lower-triangular L and a symmetric N, both packed: column b of N L first, then the rows
+// a >= b of column b of X.  Every index is a compile-time constant.
+template <int D>
+__device__ __forceinline__ void psi_in_congruence(double (&X)[psi_in_packed(D)], const double (&L)[psi_in_packed(D)],
+                                                  const double (&N)[psi_in_packed(D)]) {
+#pragma unroll
+    for (int b = 0; b < D; ++b) {
+        double yb[D];                                         // (N L)[i][b] = sum_{j >= b} N_ij L_jb
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = b; j < D; ++j) s = fma(i >= j ? N[i * (i + 1) / 2 + j] : N[j * (j + 1) / 2 + i], L[j * (j + 1) / 2 + b], s);
+            yb[i] = s;
+        }
+#pragma unroll
+        for (int a = b; a < D; ++a) {
+            double s = 0.0;
+#pragma unroll
+            for (int i = a; i < D; ++i) s = fma(L[i * (i + 1) / 2 + a], yb[i], s);
+            X[a * (a + 1) / 2 + b] += s;
+        }
+    }
+}
+
+// Per node (thread = node of the chunk): the slices' sums added in the order 0, 1, .., c_t and the step from g into h, the Psi1 half
+// from the node's record, and the results: energy[t] = U_t (null: not wanted), gmean [t][D] = gamma_t, gcov [t][D][D] = Gamma_t
+// (null: not wanted), its lower triangle computed and stored to both mirror images.  A failed node's record is zero: it writes zeros.
+template <int D>
+__global__ void __launch_bounds__(64) k_psi_in_finish(const double* __restrict__ part, const double* __restrict__ rec, int64_t t0,
+                                                      int64_t nc, int64_t chunk, int nslices, double* __restrict__ energy,
+                                                      double* __restrict__ gmean, double* __restrict__ gcov) {
+    constexpr int NS = psi_in_sums(D), PK = psi_in_packed(D);
+    const int64_t n = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (n >= nc) return;
+    const int64_t t = t0 + n;
+    auto R = [&](int k) { return rec[(size_t)k * chunk + n]; };
+    double X[PK], gam[D];
+    {   // the Psi2 half: N = c_t (-1/2 (sum w) I + 1/4 sum w v v'),   gamma = -1/2 c_t L_2' sum w v
+        double acc[NS], L[PK], N[PK];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            double s = 0.0;
+            for (int sl = 0; sl < nslices; ++sl) s += part[((size_t)sl * NS + k) * chunk + n];
+            acc[k] = s;
+        }
+        const double c = R(0);
+#pragma unroll
+        for (int k = 0; k < PK; ++k) { L[k] = R(2 + D + 2 * PK + k); X[k] = 0.0; }
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b <= a; ++b)
+                N[a * (a + 1) / 2 + b] = c * (0.25 * acc[1 + D + a * (a + 1) / 2 + b] - (a == b ? 0.5 * acc[0] : 0.0));
+        psi_in_congruence<D>(X, L, N);
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            double s = 0.0;
+#pragma unroll
+            for (int i = a; i < D; ++i) s = fma(L[i * (i + 1) / 2 + a], acc[1 + i], s);
+            gam[a] = -0.5 * c * s;
+        }
+        if (energy) energy[t] = 0.5 * c * acc[0] - R(1);
+    }
+    {   // the Psi1 half: N = 1/2 a1 I - 1/2 sum s Psi1 g1 g1',   gamma += L_1' sum s Psi1 g1
+        double L[PK], N[PK];
+        const double a1 = R(1);
+#pragma unroll
+        for (int k = 0; k < PK; ++k) L[k] = R(2 + D + PK + k);
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b <= a; ++b) N[a * (a + 1) / 2 + b] = (a == b ? 0.5 * a1 : 0.0) - 0.5 * R(2 + D + a * (a + 1) / 2 + b);
+        psi_in_congruence<D>(X, L, N);
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            double s = 0.0;
+#pragma unroll
+            for (int i = a; i < D; ++i) s = fma(L[i * (i + 1) / 2 + a], R(2 + i), s);
+            gam[a] += s;
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a) gmean[(size_t)t * D + a] = gam[a];
+    if (gcov)
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b <= a; ++b) {
+                gcov[((size_t)t * D + b) * D + a] = X[a * (a + 1) / 2 + b];
+                gcov[((size_t)t * D + a) * D + b] = X[a * (a + 1) / 2 + b];
+            }
+}
+
 }  // namespace sgp

@@ -534,6 +534,24 @@ class SGPDevice:
             self._n_ell = n_ell
         return th, values, int(counts[0]), st
 
+    def psi_in_grad(self, mean, cov, y_mean, want_energy: bool = True, want_cov: bool = True):
+        """The exact-Psi input messages of T nodes with Gaussian inputs N(mean[t], cov[t]) at the current kernel (sgp_psi_in_grad; SE
+        only, D <= 8): U_t = 1/2 tr(G Psi2_t) - s_t' Psi1_t, the part of node t's average energy that depends on its input, with
+        gamma_t = dU_t / dm_t and Gamma_t = dU_t / dS_t (symmetric: dU = <Gamma, dS>).  mean (T, D), cov (T, D, D) or None, y_mean
+        (T, d_out); q(v) the last finished sweep's or `set_posterior`'s, W the last `set_noise`.  Needs no resident data and changes
+        nothing the sweep keeps.  Returns (U (T,) or None, gamma (T, D), Gamma (T, D, D) or None).  A covariance that is not positive
+        semi-definite at node t raises PosDefException with info = t + 1; a K_uu that is not positive definite raises
+        PosDefException with the failing minor."""
+        m, S, T = self._node_gaussians("psi_in_grad", mean, cov)
+        y_cm = self._node_targets(y_mean, T)
+        U = np.empty(T) if want_energy else None
+        gamma = np.empty((T, self.D))
+        Gamma = np.empty((T, self.D, self.D)) if want_cov else None
+        info = (C.c_int64 * 2)()
+        self._check(self._lib.sgp_psi_in_grad(self._h, ptr(m), ptr(S), ptr(y_cm), T, ptr(U), ptr(gamma), ptr(Gamma), info),
+                    "sgp_psi_in_grad")
+        return U, gamma, Gamma
+
     def time_kernel(self, which: int, iters: int = 20, stream: int = 0) -> float:
         """Average launch duration (microseconds, HIP events) of the Gram or streaming-SYRK kernel."""
         v = C.c_double()

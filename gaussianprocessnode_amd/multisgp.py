@@ -434,6 +434,107 @@ def rule_in_laplace_batch(q_outs, q_ins, q_v, q_w, q_theta: PointMass, meta: Mul
     return marginals, records
 
 
+def natural_gradient_in(evaluate, left_m, left_S, m, S, iterations: int = 1, halvings: int = 8):
+    """Natural-gradient steps of T independent Gaussians q_t = N(m_t, S_t) on L_t(q) = KL(q || N(left_m_t, left_S_t)) + U_t(q).
+    evaluate(idx, m (n, D), S (n, D, D)) -> (U (n,), gamma = dU/dm (n, D), Gamma = dU/dS (n, D, D)) of the nodes `idx`, one call.
+    With Sl = left_S the stationary point has precision Sl^-1 + 2 Gamma and weighted mean Sl^-1 ml + 2 Gamma m - gamma, so from the
+    current q the step is (Lambda, xi) <- (1 - rho)(Lambda, xi) + rho (Lambda*, xi*), from rho = 1; rho is halved per node until
+    Lambda is positive definite (decided on the host) and L_t has not risen (one `evaluate` of all the nodes still trying per
+    round).  A node that has used `halvings` halvings keeps its current q.  Returns (m, S, records) with records = dict(before,
+    after (T,): L_t at the start and at the end, rho (T,): the last accepted step length or 0, halved (T,): halvings taken)."""
+    m, S = np.array(m, dtype=np.float64), np.array(S, dtype=np.float64)
+    left_m, left_S = np.asarray(left_m, dtype=np.float64), np.asarray(left_S, dtype=np.float64)
+    T, D = m.shape
+    Sl_inv = np.linalg.inv(left_S)
+    Sl_inv = 0.5 * (Sl_inv + Sl_inv.transpose(0, 2, 1))
+    ld_left = np.linalg.slogdet(left_S)[1]
+
+    def free(idx, mm, SS, U):
+        dm = mm - left_m[idx]
+        kl = 0.5 * (np.einsum("tab,tba->t", Sl_inv[idx], SS) + np.einsum("ta,tab,tb->t", dm, Sl_inv[idx], dm) - D + ld_left[idx]
+                    - np.linalg.slogdet(SS)[1])
+        return kl + U
+
+    everyone = np.arange(T)
+    U, gam, Gam = (np.array(a, dtype=np.float64) for a in evaluate(everyone, m, S))
+    L = free(everyone, m, S, U)
+    before = L.copy()
+    rho_taken, halved = np.zeros(T), np.zeros(T, dtype=np.int64)
+    for _ in range(int(iterations)):
+        Lam0 = np.linalg.inv(S)
+        xi0 = np.einsum("tab,tb->ta", Lam0, m)
+        Lam1 = Sl_inv + 2.0 * Gam
+        xi1 = np.einsum("tab,tb->ta", Sl_inv, left_m) + 2.0 * np.einsum("tab,tb->ta", Gam, m) - gam
+        rho, used = np.ones(T), np.zeros(T, dtype=np.int64)
+        pending = everyone
+        while pending.size:
+            idx, tm, tS = [], [], []
+            for t in pending:
+                while used[t] <= halvings:
+                    Lam = (1.0 - rho[t]) * Lam0[t] + rho[t] * Lam1[t]
+                    Lam = 0.5 * (Lam + Lam.T)
+                    try:
+                        np.linalg.cholesky(Lam)
+                        break
+                    except np.linalg.LinAlgError:
+                        rho[t] *= 0.5
+                        used[t] += 1
+                if used[t] > halvings:
+                    continue
+                St = np.linalg.inv(Lam)
+                St = 0.5 * (St + St.T)
+                idx.append(t)
+                tS.append(St)
+                tm.append(St @ ((1.0 - rho[t]) * xi0[t] + rho[t] * xi1[t]))
+            if not idx:
+                break
+            idx, tm, tS = np.array(idx), np.array(tm), np.array(tS)
+            U2, g2, G2 = (np.asarray(a, dtype=np.float64) for a in evaluate(idx, tm, tS))
+            L2 = free(idx, tm, tS, U2)
+            ok = np.isfinite(L2) & (L2 <= L[idx])
+            acc = idx[ok]
+            m[acc], S[acc], U[acc], gam[acc], Gam[acc], L[acc] = tm[ok], tS[ok], U2[ok], g2[ok], G2[ok], L2[ok]
+            rho_taken[acc] = rho[acc]
+            pending = idx[~ok]
+            rho[pending] *= 0.5
+            used[pending] += 1
+        halved += np.minimum(used, halvings)
+    return m, S, dict(before=before, after=L, rho=rho_taken, halved=halved)
+
+
+def marginal_in_exact_batch(q_outs, lefts, q_ins, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, iterations: int = 1,
+                            halvings: int = 8):
+    """q(x_t) of T MultiSGP nodes on the closed-form objective (SE kernel only): from q_ins[t] = N(m, S), `iterations`
+    natural-gradient steps (`natural_gradient_in`) on L_t(q) = KL(q || lefts[t]) + U_t(q), U_t the part of the node's average energy
+    that depends on its input -- the expectation under q of what `marginal_in_batch` evaluates at cubature points, with the targets
+    mean(q_outs[t]).  Every evaluation round is ONE `SGPDevice.psi_in_grad` call over the nodes still trying.  q(v) is installed
+    with `set_posterior` and W = mean(q_w) with `set_noise`, as `load_theta_objective_multi(psi="exact")` installs them.  L_t does
+    not rise at any node; simultaneous updates of all nodes do not make the global free energy monotone.  Returns (marginals
+    [MvNormalMeanCovariance], records of `natural_gradient_in`)."""
+    from .device import potrf
+    q_outs, lefts, q_ins = list(q_outs), list(lefts), list(q_ins)
+    if not (len(q_outs) == len(lefts) == len(q_ins)):
+        raise ValueError("marginal_in_exact_batch: one q_out, one left message and one q_in per node")
+    require_se(kernel_family(meta.kernel))
+    if not q_ins:
+        return [], dict(before=np.zeros(0), after=np.zeros(0), rho=np.zeros(0), halved=np.zeros(0, dtype=np.int64))
+    W = _mean_W(q_w)
+    M, D_in = np.asarray(meta.Xu).shape
+    y = np.stack([np.asarray(q.mean(), dtype=np.float64).ravel() for q in q_outs])
+    mu_v, Sigma_v = q_v.mean_cov()
+    mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
+    Uv = potrf(np.asarray(Sigma_v, dtype=np.float64) + np.outer(mu_v, mu_v), meta.device).T
+    eng = _engine(meta, len(q_ins), W.shape[0])
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    eng.set_noise(W, float(np.linalg.slogdet(W)[1]))
+    eng.set_posterior(mu_v, Uv)
+    m0, S0 = gaussian_inputs(q_ins, D_in)
+    lm, lS = gaussian_inputs(lefts, D_in)
+    m, S, rec = natural_gradient_in(lambda idx, mm, SS: eng.psi_in_grad(mm, SS, y[idx]), lm, lS, m0, S0, iterations, halvings)
+    return [MvNormalMeanCovariance(m[t].copy(), S[t].copy()) for t in range(len(q_ins))], rec
+
+
 def _second_moment_contraction(q_out, q_v, W, M):
     """s = sum_d mu_v^(d) (mu_y' W)_d and S = sum_ij W_ij Rv_blk[i][j] -- what the :in and :theta closures keep of q(v)."""
     mu_y = np.asarray(q_out.mean(), dtype=np.float64).ravel()

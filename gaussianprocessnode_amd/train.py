@@ -414,7 +414,7 @@ def _proper_gaussian(q, floor: float = 1e-10):
 
 
 def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, iterations=10, init=None, free_energy=False,
-              rule_out_fn=None, psi="cubature"):
+              rule_out_fn=None, psi="cubature", in_psi="cubature"):
     """The inner `infer(...)` of the pendulum GP-SSM (experiments/Pendulum_Wishart_2d.ipynb cells 12-16):
         x_0 ~ N(m0, P0);   x_t ~ MultiSGP(x_{t-1}, v, W, theta);   y_t ~ N(x_t, P),   t = 1..T,
         v ~ N(0, v_prior_var I),   W ~ Wishart(nu0, invscale^-1),   mean field q(x_0) .. q(x_T) q(v) q(W).
@@ -439,6 +439,10 @@ def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, it
     psi: "cubature" (default) takes the Psi-statistics of steps 1 and 4 over meta.method's cubature points; "exact" takes them in
     closed form (`cubature.ExactSE`: `SGPDevice.psi_stats` for step 1, `sweep_local_psi` for step 4; SE kernel only).  Steps 2, 3
     and 5 are the same either way: the :in closure of step 3 is no expectation of the kernel and stays on cubature points.
+    in_psi: "cubature" (default) is step 3 as above; "exact" (SE kernel only) replaces it by one natural-gradient step of every
+    q(x_t), t = 0..T-1, from the previous iteration's q(x_t), on L_t(q) = KL(q || left_t) + U_{t+1}(q) with U the closed-form energy of
+    node t + 1 in its input (`multisgp.marginal_in_exact_batch`, `SGPDevice.psi_in_grad`): the functional psi="exact" sweeps on.  L_t
+    does not rise at any node; the simultaneous update of all nodes does not make the global free energy monotone.
     rule_out_fn(q_ins, q_v, q_w, q_theta, meta) replaces step 1's batch function (timing comparisons against the per-node loop).
     Returns (q_x [T + 1], q_v, q_W, free energies [iterations] or [])."""
     from . import multisgp as MS
@@ -459,6 +463,12 @@ def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, it
     rule_out_fn = rule_out_fn or MS.rule_out_batch
     if psi not in ("cubature", "exact"):
         raise ValueError(f"vmp_gpssm: psi must be 'cubature' or 'exact', got {psi!r}")
+    if in_psi not in ("cubature", "exact"):
+        raise ValueError(f"vmp_gpssm: in_psi must be 'cubature' or 'exact', got {in_psi!r}")
+    if in_psi == "exact":
+        from .cubature import require_se
+        from .meta import kernel_family
+        require_se(kernel_family(meta.kernel))
 
     run_meta = meta
     if psi == "exact":
@@ -469,15 +479,15 @@ def vmp_gpssm(theta, y, meta, *, P, x0_prior, v_prior_var=50.0, w_prior=None, it
         run_meta = dataclasses.replace(meta, method=ExactSE())
     try:
         return _vmp_gpssm_loop(run_meta, y, q_x, q_v, q_w, q_theta, v_prior, rule_out_fn, int(iterations), free_energy,
-                               (m0, P0), Pobs, Pinv, v_prior_var, w_prior)
+                               (m0, P0), Pobs, Pinv, v_prior_var, w_prior, in_psi)
     finally:
         meta.engine = run_meta.engine
 
 
 def _vmp_gpssm_loop(meta, y, q_x, q_v, q_w, q_theta, v_prior, rule_out_fn, iterations, free_energy, x0_prior, Pobs, Pinv,
-                    v_prior_var, w_prior):
+                    v_prior_var, w_prior, in_psi="cubature"):
     """The iterations of `vmp_gpssm` (its docstring numbers the steps) on the meta whose method says how steps 1 and 4 take their
-    Psi-statistics."""
+    Psi-statistics; in_psi says how step 3 updates q(x)."""
     from . import multisgp as MS
     T = len(y)
     m0, P0 = x0_prior
@@ -488,7 +498,10 @@ def _vmp_gpssm_loop(meta, y, q_x, q_v, q_w, q_theta, v_prior, rule_out_fn, itera
         S = np.linalg.inv(W + Pinv)                                                             # 2 (every out_t carries precision W)
         S = 0.5 * (S + S.T)
         lefts = [MvNormalMeanCovariance(m0, P0)] + [MvNormalMeanCovariance(S @ (W @ outs[t].m + Pinv @ y[t]), S) for t in range(T)]
-        q_x = [_proper_gaussian(q) for q in MS.marginal_in_batch(q_x[1:], lefts[:-1], q_v, q_w, q_theta, meta)] + [lefts[-1]]  # 3
+        if in_psi == "exact":                                                                   # 3
+            q_x = MS.marginal_in_exact_batch(q_x[1:], lefts[:-1], q_x[:-1], q_v, q_w, q_theta, meta)[0] + [lefts[-1]]
+        else:
+            q_x = [_proper_gaussian(q) for q in MS.marginal_in_batch(q_x[1:], lefts[:-1], q_v, q_w, q_theta, meta)] + [lefts[-1]]
         q_v = MS.sweep(meta, q_x[1:], q_x[:-1], q_w, q_theta, v_prior, E_logdet_W=wishart_mean_logdet(q_w.nu, q_w.invS))   # 4
         if free_energy:
             fe.append(MS.average_energy_summed(meta) + gpssm_host_energy(y, Pobs, q_x, q_v, q_w, (m0, P0), v_prior_var, w_prior))
@@ -498,7 +511,7 @@ def _vmp_gpssm_loop(meta, y, q_x, q_v, q_w, q_theta, v_prior, rule_out_fn, itera
 
 def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iterations=10, theta_steps=100, device_paced=True,
                             v_prior_var=50.0, w_prior=None, optimizer=None, free_energy=True, psi="cubature",
-                            theta_psi="cubature"):
+                            theta_psi="cubature", in_psi="cubature"):
     """`PerformInference` of experiments/Pendulum_Wishart_2d.ipynb cell 16.  Per epoch: `vmp_gpssm` from the initialisation at
     the current theta (step 1), then `optimize_theta_multi` -- theta_steps AdaMax steps on neg_log_backwardmess_multi -- at the held
     q(x), q(v), q(W), with the targets mean(q(x_t)) and the inputs q(x_{t-1}), t = 1..T, as the notebook passes them (step 2).
@@ -512,7 +525,7 @@ def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iteratio
     fe_values, post = [], None
     for _ in range(int(epochs)):
         q_x, q_v, q_w, fe = vmp_gpssm(theta, y, meta, P=P, x0_prior=x0_prior, v_prior_var=v_prior_var, w_prior=w_prior,
-                                      iterations=vmp_iterations, free_energy=free_energy, psi=psi)
+                                      iterations=vmp_iterations, free_energy=free_energy, psi=psi, in_psi=in_psi)
         if fe:
             fe_values.append(fe[-1])
         y_data = np.stack([q.m for q in q_x[1:]])

@@ -531,6 +531,34 @@ int sgp_theta_descend_psi(sgp_handle* h, const double* mean, const double* cov, 
                           double beta2, double eps, double* opt_state /* 2 (1 + n_ell) + 2, in/out, may be NULL */,
                           double* values /* steps, may be NULL */, int64_t* counts /* 3, may be NULL */);
 
+/* ---- exact-Psi input messages: a node's energy and its derivatives in the mean and covariance of its Gaussian input ----
+ * With q(v), W, G and s_t as for sgp_theta_objective_psi (SGP_KERNEL_SE only, d_out = 1 .. 4, D <= 8) and x_t ~ N(m_t, S_t), the part of
+ * node t's average energy that depends on its input is
+ *     U_t(m_t, S_t) = 1/2 tr(G Psi2_t) - s_t' Psi1_t            (sgp_theta_objective_psi's value is 1/2 tr(W) sigma2 T + sum_t U_t)
+ * and, with P_c = (Lambda + c S_t)^-1, h^(c)_tm = P_c (m_t - z_m), u_ij = h^(2)_ti + h^(2)_tj,
+ *     A_t, b_t, C_t = sum_ij G_ij Psi2_t[i,j] (1, u_ij, u_ij u_ij'),   a1_t, b1_t, C1_t = sum_m s_t[m] Psi1_t[m] (1, h^(1)_tm, h^(1)_tm h^(1)_tm'):
+ *     energy[t]    = U_t = 1/2 A_t - a1_t
+ *     grad_mean[t] = dU_t / dm_t = -1/2 b_t + b1_t                                            (D)
+ *     grad_cov[t]  = dU_t / dS_t = -1/2 A_t P_2 + 1/4 C_t + 1/2 a1_t P_1 - 1/2 C1_t           (D x D, exactly symmetric)
+ * grad_cov is the symmetric matrix with dU = <grad_cov, dS> for symmetric dS.  At S_t = 0 these are -logpdf - 1/2 tr(W) sigma2, -grad and
+ * -1/2 hess of sgp_in_message_grad at the point m_t.  A natural-gradient step of q(x_t) on KL(q || left) + U_t has the precision
+ * left^-1 + 2 grad_cov as its target (Python: multisgp.marginal_in_exact_batch).
+ *
+ * Inputs as sgp_theta_objective_psi takes them (mean D x T, cov D x D x T or NULL for S = 0, y_mean T x d_out column-major); q(v) is the
+ * last finished sweep's, or sgp_set_posterior's when that came later; W is the last sgp_set_noise.  Blocking; everything is formed in
+ * call scratch at the current kernel: the resident statistics, K_uu chain, q(v), sgp_sweep_kind and what the other calls refuse are
+ * unchanged, and outside call scratch the call touches only what sgp_theta_objective_psi touches.  All sums run in a fixed order
+ * without atomics: identical calls agree bitwise, also under different SGP_PREDICT_CHUNK.
+ *
+ * info (2, may be NULL) = [the failing leading minor of K_uu or 0, the first node whose Lambda + S_t or Lambda + 2 S_t is not positive
+ * definite, + 1, or 0]; the return value is the positive entry (the node check comes first) and sgp_last_error names which failed.
+ *
+ * SGP_ERR_ARG: everything sgp_theta_objective_psi refuses; a NULL grad_mean; D > 8 (the per-node sums live in registers: 1 + D +
+ * D (D + 1) / 2 of them). */
+int sgp_psi_in_grad(sgp_handle* h, const double* mean /* D x T */, const double* cov /* D x D x T or NULL */,
+                    const double* y_mean /* T x d_out */, int64_t n_nodes, double* energy /* T, may be NULL */,
+                    double* grad_mean /* D x T */, double* grad_cov /* D x D x T, may be NULL */, int64_t* info /* 2, may be NULL */);
+
 /* ---- building blocks exposed for tests / other callers (host pointers, blocking) ------------
  * K = sigma2 * exp(-0.5 |(a-b)/ell|^2): kernelmatrix(kernel(theta), A, B) of KernelFunctions.jl as called at
  * GPnode/UniSGPnode.jl:102,153; A is D x na, B is D x nb, K is na x nb column-major. */

@@ -582,6 +582,18 @@ function theta_descend_psi!(meta::HipSGPMeta, m::Matrix{Float64}, S, y::Matrix{F
     return θ, values, Int(counts[1])
 end
 
+# ---- the exact-Psi input messages (sgp_psi_in_grad; SE kernel only, D <= 8): per node t with input x_t ~ N(m_t, S_t) the part U_t of its
+# average energy that depends on the input, γ_t = ∂U_t/∂m_t and Γ_t = ∂U_t/∂S_t (symmetric).  m is D × T, S is D × D × T or nothing
+# (S = 0), y is T × d_out; q(v) and W are the handle's.  Returns (U, γ (D × T), Γ (D × D × T)).  PosDefException(t + 1) names an
+# indefinite node, PosDefException(k) a K_uu that failed.
+function psi_in_grad(h::Handle, m::Matrix{Float64}, S, y::Matrix{Float64})
+    D, T = size(m); U = zeros(T); γ = zeros(D, T); Γ = zeros(D, D, T); info = zeros(Int64, 2)
+    check(ccall((:sgp_psi_in_grad, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, m, S === nothing ? C_NULL : S, y, T, U, γ, Γ, info), h.ptr)
+    return U, γ, Γ
+end
+
 # The classification loop (experiments/classification_banana.ipynb cell 9: `y[i] ~ Probit(f[i])`, q(w) = GammaShapeRate carried
 # over the minibatches, q(v) never reset): labels 0 / 1 in y; returns (θ, shape, rate).  sgp_train_likelihood turns the run
 # opened by sgp_train_begin into this loop -- forward message, Probit moment matching, Gamma update and AdaMax on the device.

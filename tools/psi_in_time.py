@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Time one exact-Psi input-message call (sgp_psi_in_grad: energy, gamma, Gamma of every node) against the cubature route for the same
+nodes -- the srcubature points of the T Gaussians formed on the host, then one sgp_in_message_grad on them (closure value, gradient and
+Hessian per point) -- and against sgp_theta_objective_psi at the same shape as a yardstick for the kernel pair.  Random nodes on a
+random inducing set; the three alternate `--reps` times after a warm-up of each, host clock around each blocking call.  One JSON line
+per shape.
+    python tools/psi_in_time.py [--reps 9] [--shapes 300,48,2,2 20000,256,4,3]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _bind  # noqa: E402,F401  (NUMA node of the GPU first)
+import numpy as np  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gaussianprocessnode_amd import SGPDevice  # noqa: E402
+from gaussianprocessnode_amd.cubature import srcubature  # noqa: E402
+
+
+def spread(ts):
+    return dict(median_s=statistics.median(ts), min_s=min(ts), max_s=max(ts))
+
+
+def shape(T, M, D, d_out, reps):
+    rng = np.random.default_rng(0)
+    Xu = rng.uniform(-2.0, 2.0, (M, D))
+    mean = rng.uniform(-2.0, 2.0, (T, D))
+    A = rng.normal(size=(T, D, D)) * 0.2
+    cov = A @ A.transpose(0, 2, 1) + 1e-3 * np.eye(D)
+    Y = rng.normal(size=(T, d_out))
+    mu = 0.1 * rng.normal(size=d_out * M)
+    Sig = 0.01 * np.eye(d_out * M)
+    rule = srcubature()
+
+    with SGPDevice(8, M, D, d_out=d_out) as dev:
+        dev.set_inducing(Xu)
+        dev.set_kernel(1.0, np.full(D, 1.5), 1e-6)
+        dev.set_noise(10.0 * np.eye(d_out))
+        dev.set_posterior(mu, np.linalg.cholesky(Sig + np.outer(mu, mu)).T)
+
+        def exact():
+            return dev.psi_in_grad(mean, cov, Y)
+
+        def points():
+            pts = [rule.points_weights(mean[t], cov[t])[0] for t in range(T)]
+            start = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64)
+            return np.concatenate(pts), start
+
+        def cubature(timing=None):
+            t0 = time.perf_counter()
+            X, start = points()
+            t1 = time.perf_counter()
+            out = dev.in_message_grad(X, start, Y, mu, Sig)
+            if timing is not None:
+                timing.append((t1 - t0, time.perf_counter() - t1))
+            return out
+
+        def yardstick():
+            return dev.theta_objective_psi(mean, cov, Y, want_grad=True)
+
+        routes = dict(psi_in_grad=exact, cubature_route=cubature, theta_objective_psi=yardstick)
+        for f in routes.values():
+            f()
+        ts = {k: [] for k in routes}
+        parts = []
+        for _ in range(reps):
+            for k, f in routes.items():
+                t0 = time.perf_counter()
+                f(parts) if k == "cubature_route" else f()
+                ts[k].append(time.perf_counter() - t0)
+        n_points = int(points()[1][-1])
+    out = dict(T=T, M=M, D=D, d_out=d_out, reps=reps, cubature_points=n_points, **{k: spread(v) for k, v in ts.items()})
+    out["cubature_route_host_points"] = spread([p[0] for p in parts])
+    out["cubature_route_in_message_grad"] = spread([p[1] for p in parts])
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--shapes", nargs="*", default=["300,48,2,2", "20000,256,4,3"], help="T,M,D,d_out")
+    a = ap.parse_args()
+    for s in a.shapes:
+        T, M, D, d_out = (int(v) for v in s.split(","))
+        print(json.dumps(shape(T, M, D, d_out, a.reps)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -55,10 +55,11 @@ def inducing_inputs():
 
 
 def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cubature", theta_psi="cubature",
-        in_psi="cubature"):
+        in_psi="cubature", forecast=0):
     from gaussianprocessnode_amd.cubature import srcubature
     from gaussianprocessnode_amd.meta import SMSE, MultiSGPMeta, SEARDKernel, softplus
-    from gaussianprocessnode_amd.train import perform_inference_gpssm, vmp_gpssm
+    from gaussianprocessnode_amd.distributions import PointMass
+    from gaussianprocessnode_amd.train import forecast_gpssm, perform_inference_gpssm, vmp_gpssm
 
     states, obs, P = generate(N, seed)
     x_true, y = states[:nodes], obs[:nodes]
@@ -72,12 +73,20 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
                                                 psi=psi, theta_psi=theta_psi, in_psi=in_psi)
         t_train = time.perf_counter() - t0
         t0 = time.perf_counter()
-        q_x, _, q_w, fe_smooth = vmp_gpssm(theta, y, meta, P=P, x0_prior=x0_prior, iterations=30, free_energy=True, psi=psi,
+        q_x, q_v, q_w, fe_smooth = vmp_gpssm(theta, y, meta, P=P, x0_prior=x0_prior, iterations=30, free_energy=True, psi=psi,
                                            in_psi=in_psi)
         t_smooth = time.perf_counter() - t0
+        roll = None
+        if forecast > 0:                                      # where will the state be in k steps: closed form, no cubature points
+            f_mean, f_cov = forecast_gpssm(q_x[-1], forecast, q_v, q_w, PointMass(theta), meta)
+            roll = {"mean": f_mean[:, 0].tolist(), "std": np.sqrt(np.einsum("kii->ki", f_cov[:, 0])).tolist()}
     finally:
-        if meta.engine is not None:
-            meta.engine.close()
+        for eng in (meta.engine, getattr(meta, "_aux_engine_out", None)):
+            if eng is not None:
+                eng.close()
+    if roll is not None:
+        for k, (mk, sk) in enumerate(zip(roll["mean"], roll["std"])):
+            print(f"forecast step {k + 1}: mean {np.round(mk, 4).tolist()} std {np.round(sk, 4).tolist()}")
     est = np.stack([q.m for q in q_x[1:]])
     return {
         "experiment": "pendulum GP-SSM PerformInference (experiments/Pendulum_Wishart_2d.ipynb)",
@@ -90,6 +99,7 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
         "free_energy_last_epoch": fe[-1] if fe else None, "free_energy_smoothing": fe_smooth[-1],
         "free_energy_epochs": [float(v) for v in fe],
         "mean_W": np.asarray(q_w.mean()).tolist(),
+        "forecast": roll,
         "reference": {"train_seconds": 1615.249575, "smoothing_seconds": 15.0, "smse": [0.005454764265443909, 0.0010773936260490339],
                       "note": "other data (Julia's MersenneTwister(124)), hardware unstated"},
     }
@@ -108,6 +118,9 @@ if __name__ == "__main__":
     ap.add_argument("--in-psi", choices=("cubature", "exact"), default="cubature",
                     help="the q(x) update: moments over srcubature points of the :in closure, or natural-gradient steps on the SE closed "
                          "form (sgp_psi_in_grad)")
+    ap.add_argument("--forecast", type=int, default=0, metavar="K",
+                    help="after smoothing, roll q(x_T) out K steps in closed form (sgp_psi_predict) and print the per-step means and "
+                         "standard deviations")
     args = ap.parse_args()
     print(json.dumps(run(args.epochs, args.nodes, args.seed, not args.host_paced, psi=args.psi, theta_psi=args.theta_psi,
-                         in_psi=args.in_psi)))
+                         in_psi=args.in_psi, forecast=args.forecast)))

@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
-// sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad).  Plain C++,
-// no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
+// sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad,
+// sgp_psi_predict).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -252,6 +252,39 @@ static inline void layout_psi_in(Carver& c, const PointShape& p, bool has_cov, b
     b->Kinv = c.take<double>(mm);
     b->G = c.take<double>(mm);
     b->Gpart = c.take<double>((size_t)p.Mp);
+    b->Pscr = c.take<double>((size_t)p.potrf_scratch);
+    b->Info = c.take<int>(1);
+}
+
+// sgp_psi_predict (p.n = p.n_nodes = the nodes, p.chunk nodes per chunk): the inputs, status words and results of all nodes (means
+// [d_out][node], C_f [node][d_out][d_out], cross [node][d_out][D]); one chunk of g ([D][Mp][chunk]), of c_t and of the slices' running
+// sums ([slice][sums][chunk]); the `sums` weight matrices E and the K_uu chain at the current kernel (K_uu -> L_K, W_K, K_uu^-1); one
+// factorisation's scratch with its status word
+struct PsiPredictScratch {
+    double *Mean, *Cov;
+    int* Bad;
+    double *OutMean, *OutCov, *Cross;
+    double *G2, *Ct, *Part;
+    double *E, *Kuu, *Wk, *Kinv;
+    double* Pscr;
+    int* Info;
+};
+static inline void layout_psi_predict(Carver& c, const PointShape& p, bool has_cov, bool want_cov, bool want_cross, size_t nslices,
+                                      size_t sums, PsiPredictScratch* b) {
+    const size_t n = (size_t)p.n, D = (size_t)p.D, ch = (size_t)p.chunk, mm = (size_t)p.Mp * p.Mp;
+    b->Mean = c.take<double>(n * D);
+    b->Cov = c.take<double>(has_cov ? n * D * D : 0);
+    b->Bad = c.take<int>(n);
+    b->OutMean = c.take<double>(n * p.dout);
+    b->OutCov = c.take<double>(want_cov ? n * p.dout * p.dout : 0);
+    b->Cross = c.take<double>(want_cross ? n * p.dout * D : 0);
+    b->G2 = c.take<double>(ch * D * p.Mp);
+    b->Ct = c.take<double>(ch);
+    b->Part = c.take<double>(ch * nslices * sums);
+    b->E = c.take<double>(sums * mm);
+    b->Kuu = c.take<double>(mm);
+    b->Wk = c.take<double>(mm);
+    b->Kinv = c.take<double>(mm);
     b->Pscr = c.take<double>((size_t)p.potrf_scratch);
     b->Info = c.take<int>(1);
 }

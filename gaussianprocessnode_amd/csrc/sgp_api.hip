@@ -118,6 +118,7 @@ struct SweepPlan {
 //   sgp_sweep_local_psi                         fills the record, drops reuse, exact_psi; data_gen++; have_data = false (sgp_set_data clears exact_psi)
 //   sgp_theta_objective_psi                     nothing: everything it forms is in call scratch
 //   sgp_psi_in_grad                             nothing: everything it forms is in call scratch
+//   sgp_psi_predict                             nothing: everything it forms is in call scratch
 //   sgp_theta_descend_psi                       nothing: the kernel moved (hParams, params_gen++), nothing resident was rewritten, and
 //                                               kernel_matches, which compares values, turns the resident statistics down
 struct StatsRecord {
@@ -3352,10 +3353,23 @@ static PointShape psi_theta_shape(const sgp_handle* h, int64_t T) {
 // what both calls refuse, and the inputs every kernel below relies on being finite
 static int psi_theta_ready(sgp_handle* h, const char* name, const double* mean, const double* cov, const double* y_mean, int64_t T) {
     if (int rc = psi_inputs_ready(h, name, mean, cov, T)) return rc;
-    for (size_t i = 0; i < (size_t)T * h->dout; ++i)
+    for (size_t i = 0; y_mean && i < (size_t)T * h->dout; ++i)    // (sgp_psi_predict has no targets)
         if (!std::isfinite(y_mean[i])) return refuse(h, name, "y_mean must be finite");
     if (!h->swept) return refuse(h, name, "needs a finished sweep or sgp_set_posterior (q(v))");
     if (h->allreduce) return refuse(h, name, "an all-reduce hook is installed (data-sharded exact statistics are not supported)");
+    return 0;
+}
+
+// The K_uu chain at the kernel parameters in `src` into call scratch, on `s`: the parameters into the chain's mirror (k_prep_xu), K_uu,
+// its factor in place with W_K = L_K^-1, and K_uu^-1 = W_K' W_K.  info: the factorisation's status word, pscr: its scratch.
+static int psi_kuu_chain(sgp_handle* h, hipStream_t s, const Params* src, double* Kuu, double* Wk, double* Kinv, double* pscr,
+                         int* info) {
+    HIPCHK(h, hipMemsetAsync(pscr, 0, sizeof(double) * POTRF_SCRATCH, s));
+    HIPCHK(h, hipMemsetAsync(info, 0, sizeof(int), s));
+    launch_prep_xu(h, s, h->dXusK, src, h->dParamsK);
+    hipLaunchKernelGGL(k_gram_uu<SGP_KERNEL_SE>, dim3(h->T, h->T), dim3(256), 0, s, h->dXusK, Kuu, h->dParamsK, h->M, h->Mp, h->D);
+    launch_potrf(Kuu, h->Mp, h->T, info, h->M, pscr, s, Wk);
+    launch_ata(Wk, Kinv, h->Mp, h->T, s);
     return 0;
 }
 
@@ -3388,14 +3402,9 @@ static int psi_theta_enqueue(sgp_handle* h, hipStream_t s, const PsiThetaScratch
     int64_t range_len = 0;
     psi_ranges(T, ntiles, &nranges, &range_len);
     const size_t acc_tiles = (size_t)nranges * ntiles;
-    HIPCHK(h, hipMemsetAsync(b.Pscr, 0, sizeof(double) * POTRF_SCRATCH, s));
-    HIPCHK(h, hipMemsetAsync(b.Info, 0, sizeof(int), s));
     HIPCHK(h, hipMemsetAsync(b.Acc, 0, sizeof(double) * acc_tiles * TB * TB, s));
     HIPCHK(h, hipMemsetAsync(b.Wd, 0, sizeof(double) * acc_tiles * D * 256, s));
-    launch_prep_xu(h, s, h->dXusK, src, h->dParamsK);
-    hipLaunchKernelGGL(k_gram_uu<SGP_KERNEL_SE>, dim3(Tn, Tn), dim3(256), 0, s, h->dXusK, b.Kuu, h->dParamsK, M, Mp, D);
-    launch_potrf(b.Kuu, Mp, Tn, b.Info, M, b.Pscr, s, b.Wk);
-    launch_ata(b.Wk, b.Kinv, Mp, Tn, s);
+    if (int rc = psi_kuu_chain(h, s, src, b.Kuu, b.Wk, b.Kinv, b.Pscr, b.Info)) return rc;
     // (k_form_G_multi also sums column shares of tr(G Psi2) against its Psi2 argument: not used here, any Mp x Mp matrix will do)
     hipLaunchKernelGGL(k_form_G_multi, dim3(Mp), dim3(256), 0, s, Rv, h->Qp, (const double*)b.Kinv, (const double*)b.Kinv, w.W, w.trace,
                        b.G, b.Gpart, M, Mp, dout);
@@ -3582,15 +3591,10 @@ static PointShape psi_in_shape(const sgp_handle* h, int64_t T) {
 template <int D>
 static int psi_in_enqueue(sgp_handle* h, hipStream_t s, const PsiInScratch& b, const PointShape& shape, bool has_cov, bool want_energy,
                           bool want_cov, const double* Rv, const MeanW& w) {
-    const int M = h->M, Mp = h->Mp, dout = h->dout, Tn = h->T;
+    const int M = h->M, Mp = h->Mp, dout = h->dout;
     const int64_t T = shape.n, chunk = shape.chunk;
     const int nslices = psi_in_slices(T, M);
-    HIPCHK(h, hipMemsetAsync(b.Pscr, 0, sizeof(double) * POTRF_SCRATCH, s));
-    HIPCHK(h, hipMemsetAsync(b.Info, 0, sizeof(int), s));
-    launch_prep_xu(h, s, h->dXusK, h->hParams, h->dParamsK);
-    hipLaunchKernelGGL(k_gram_uu<SGP_KERNEL_SE>, dim3(Tn, Tn), dim3(256), 0, s, h->dXusK, b.Kuu, h->dParamsK, M, Mp, D);
-    launch_potrf(b.Kuu, Mp, Tn, b.Info, M, b.Pscr, s, b.Wk);
-    launch_ata(b.Wk, b.Kinv, Mp, Tn, s);
+    if (int rc = psi_kuu_chain(h, s, h->hParams, b.Kuu, b.Wk, b.Kinv, b.Pscr, b.Info)) return rc;
     // (k_form_G_multi also sums column shares of tr(G Psi2) against its Psi2 argument: not used here, any Mp x Mp matrix will do)
     hipLaunchKernelGGL(k_form_G_multi, dim3(Mp), dim3(256), 0, s, Rv, h->Qp, (const double*)b.Kinv, (const double*)b.Kinv, w.W, w.trace,
                        b.G, b.Gpart, M, Mp, dout);
@@ -3668,6 +3672,124 @@ extern "C" int sgp_psi_in_grad(sgp_handle* h, const double* mean, const double* 
     if (energy) HIPCHK(h, hipMemcpy(energy, b.Energy, sizeof(double) * T, hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(grad_mean, b.GradMean, sizeof(double) * T * D, hipMemcpyDeviceToHost));
     if (grad_cov) HIPCHK(h, hipMemcpy(grad_cov, b.GradCov, sizeof(double) * T * D * D, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Closed-form prediction at Gaussian inputs (include/sgp_hip.h: sgp_psi_predict; kernels: k_psi_pred_* / k_psi2_pred_accumulate in
+// sgp_kernels.hip.h).  As sgp_psi_in_grad: everything in call scratch, the K_uu chain at the current kernel too; outside
+// it the call touches the K_uu chain's parameter mirror and dThetaMulti (theta_Rv).
+// ------------------------------------------------------------------------------------------------
+static PointShape psi_predict_shape(const sgp_handle* h, int64_t T) {
+    return point_shape(h, (int64_t)h->D * h->Mp + (int64_t)psi_in_slices(T, h->M) * psi_pred_sums(h->dout) + 1, T, T);
+}
+
+// true when the d_out x d_out column-major W is symmetric positive definite (its Cholesky factorisation runs through)
+static bool outmat_posdef(const double* W, int dout) {
+    double L[MAXO][MAXO];
+    for (int i = 0; i < dout; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double s = W[j * dout + i];
+            for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+            if (i == j) {
+                if (!(s > 0.0) || !std::isfinite(s)) return false;
+                L[i][i] = sqrt(s);
+            } else {
+                L[i][j] = s / L[j][j];
+            }
+        }
+    return true;
+}
+
+// One evaluation on `s`: the K_uu chain at the current kernel, the weights E, then per chunk the nodes' g, c_t, means and cross terms,
+// the slices' sums and the finish into b.OutCov.  Rv: R_v of the held q(v) (theta_Rv); noise: W^-1 or zero.
+template <int DCAP>
+static int psi_predict_enqueue(sgp_handle* h, hipStream_t s, const PsiPredictScratch& b, const PointShape& shape, bool has_cov,
+                               bool want_cov, bool want_cross, const double* Rv, const OutMat& noise) {
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout;
+    const int64_t T = shape.n, chunk = shape.chunk;
+    const int nslices = psi_in_slices(T, M), K = psi_pred_sums(dout);
+    const PsiKern kp = psi_kern(h);
+    if (want_cov) {
+        if (int rc = psi_kuu_chain(h, s, h->hParams, b.Kuu, b.Wk, b.Kinv, b.Pscr, b.Info)) return rc;
+        hipLaunchKernelGGL(k_psi_pred_weights, dim3(Mp, K), dim3(256), 0, s, (const double*)b.Kinv, Rv, h->Qp, (const double*)h->dXusK,
+                           (const Params*)h->dParamsK, b.E, M, Mp, D);
+    } else {
+        HIPCHK(h, hipMemsetAsync(b.Info, 0, sizeof(int), s));
+    }
+    for (int64_t t0 = 0; t0 < T; t0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, T - t0);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi_pred_prep<DCAP>), dim3((unsigned)nc), dim3(64), 0, s, (const double*)h->dXu,
+                           (const double*)b.Mean, has_cov ? (const double*)b.Cov : (const double*)nullptr, T, t0, (const double*)h->dMu,
+                           kp, b.G2, b.Ct, b.OutMean, want_cross ? b.Cross : (double*)nullptr, b.Bad, chunk, M, Mp, D, dout);
+        if (!want_cov) continue;
+        const dim3 grid((unsigned)((nc + PSI_IN_NODES - 1) / PSI_IN_NODES), (unsigned)nslices);
+        auto run = [&](auto DO) {
+            constexpr int DOUT = decltype(DO)::value;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi2_pred_accumulate<DCAP, psi_pred_sums(DOUT)>), grid, dim3(PSI_IN_NODES), 0, s,
+                               (const double*)b.G2, (const double*)b.E, b.Part, nc, chunk, nslices, M, Mp, D);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi_pred_finish<DOUT>), dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, s,
+                               (const double*)b.Part, (const double*)b.Ct, (const double*)b.OutMean, (const Params*)h->dParamsK, noise, T,
+                               t0, nc, chunk, nslices, b.OutCov);
+        };
+        if (dout == 1) run(std::integral_constant<int, 1>{});
+        else by_dout(dout, run);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+extern "C" int sgp_psi_predict(sgp_handle* h, const double* mean, const double* cov, int64_t n_nodes, int32_t flags, double* out_mean,
+                               double* out_cov, double* cross, int64_t* info) {
+    const char* name = "sgp_psi_predict";
+    if (!h) return fail(h, SGP_ERR_ARG, "sgp_psi_predict: null handle");
+    if (info) info[0] = info[1] = 0;
+    if (n_nodes < 0) return refuse(h, name, "n_nodes must be >= 0");
+    if (!out_mean) return refuse(h, name, "out_mean must not be NULL");
+    if (flags & ~SGP_PREDICT_NOISE) return refuse(h, name, "unknown flags");
+    if (n_nodes == 0) return 0;
+    if (!mean) return refuse(h, name, "null mean");
+    if (int rc = psi_theta_ready(h, name, mean, cov, nullptr, n_nodes)) return rc;
+    OutMat noise;
+    memset(&noise, 0, sizeof noise);
+    if (flags & SGP_PREDICT_NOISE) {
+        if (!outmat_posdef(h->hParams->W, h->dout) || !invert_outmat(h->hParams->W, h->dout, &noise))
+            return refuse(h, name, "the noise matrix of sgp_set_noise is not positive definite");
+    }
+    if (int wrc = sync_checked(h)) return wrc;
+    hipStream_t s = h->own;
+    const PointShape shape = psi_predict_shape(h, n_nodes);
+    const size_t T = (size_t)n_nodes, D = (size_t)h->D, dout = (size_t)h->dout;
+    PsiPredictScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) {
+            layout_psi_predict(c, shape, cov != nullptr, out_cov != nullptr, cross != nullptr, (size_t)psi_in_slices(n_nodes, h->M),
+                               (size_t)psi_pred_sums(h->dout), &b);
+        }))
+        return crc;
+    HIPCHK(h, hipMemcpy(b.Mean, mean, sizeof(double) * T * D, hipMemcpyHostToDevice));
+    if (cov) HIPCHK(h, hipMemcpy(b.Cov, cov, sizeof(double) * T * D * D, hipMemcpyHostToDevice));
+    const double* Rv = h->dR;
+    if (out_cov)
+        if (int rrc = theta_Rv(h, s, &Rv)) return rrc;
+    const int rc = h->D <= 8 ? psi_predict_enqueue<8>(h, s, b, shape, cov != nullptr, out_cov != nullptr, cross != nullptr, Rv, noise)
+                             : psi_predict_enqueue<MAXD>(h, s, b, shape, cov != nullptr, out_cov != nullptr, cross != nullptr, Rv, noise);
+    // whatever was enqueued reads the call's buffers: wait before anything else, also on an error path
+    const hipError_t werr = wait_stream(s);
+    if (rc) return rc;
+    HIPCHK(h, werr);
+    HIPCHK(h, hipGetLastError());
+    int kuu = 0;
+    HIPCHK(h, hipMemcpy(&kuu, b.Info, sizeof kuu, hipMemcpyDeviceToHost));
+    std::vector<int> bad(T);
+    HIPCHK(h, hipMemcpy(bad.data(), b.Bad, sizeof(int) * T, hipMemcpyDeviceToHost));
+    int node = 0;
+    for (size_t t = 0; t < T && !node; ++t)
+        if (bad[t]) node = t + 1 > (size_t)std::numeric_limits<int>::max() ? std::numeric_limits<int>::max() : (int)(t + 1);
+    if (info) { info[0] = kuu > 0 ? kuu : 0; info[1] = node; }
+    if (int src = psi_theta_status(h, name, node, kuu)) return src;
+    HIPCHK(h, hipMemcpy(out_mean, b.OutMean, sizeof(double) * T * dout, hipMemcpyDeviceToHost));
+    if (out_cov) HIPCHK(h, hipMemcpy(out_cov, b.OutCov, sizeof(double) * T * dout * dout, hipMemcpyDeviceToHost));
+    if (cross) HIPCHK(h, hipMemcpy(cross, b.Cross, sizeof(double) * T * dout * D, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -5050,4 +5050,248 @@ __global__ void __launch_bounds__(64) k_psi_in_finish(const double* __restrict__
             }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Closed-form prediction at Gaussian inputs (sgp_psi_predict): per node t with input x_t ~ N(m_t, S_t) and outputs i, j
+//   mean[t,i]      = Psi1_t' mu^(i)
+//   C_f[t][i][j]   = delta_ij (sigma2 - tr(Kinv Psi2_t)) + tr(R^(ij) Psi2_t) - mean[t,i] mean[t,j]            (+ W^-1 under the flag)
+//   cross[t][:, i] = Cov[x_t, f_i] = -S_t L_1' sum_m mu^(i)_m Psi1_t[m] g1_tm
+// in the factors of 6f: Lambda + c S = C C', L = C^-1, g = L (m_t - z).  The K = 1 + d_out (d_out + 1) / 2 contractions of Psi2_t --
+// Kinv first, then the symmetric parts of R^(ij) for the lower triangle j <= i, row-major -- share k_psi2_in_accumulate's decomposition
+// and one exp per entry.  Nothing is kept per D^2, so D goes up to MAXD.  No atomics; every sum has a fixed order.
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int psi_pred_sums(int d_out) { return 1 + d_out * (d_out + 1) / 2; }
+
+// Per node (one wavefront each; grid = the nodes of this chunk, t0 = its first node), a sibling of k_psi_in_prep with both factors in
+// LDS: g of Lambda + 2 S for every inducing input as G2 [D][Mp][chunk] (node fastest, rows m >= M zero), ct [chunk] = prod_d(ell_d /
+// C_dd) of Lambda + 2 S, and the :out means exactly as k_psi_prep forms them (same parameters by value, lane l sums m = l, l + 64, ..
+// in order, then the xor butterfly): out_mean [d_out][T] at column t.  With cross wanted ([T][d_out][D]): per output u = sum_m mu_m
+// Psi1[m] g1_m in the same lane order (one pass over m per output, so that D sums live in registers, not d_out D), h = C_1^-T u by back
+// substitution and cross = -S_t h from the lower triangle of S_t; exactly zero without a covariance.  A node whose factorisation
+// fails sets bad[t] and writes zeros.  At DCAP = 32 the factors are re-read from LDS for every m, as in k_psi_theta_prep.
+template <int DCAP>
+__global__ void __launch_bounds__(64) k_psi_pred_prep(const double* __restrict__ Xu, const double* __restrict__ mean,
+                                                      const double* __restrict__ cov, int64_t T, int64_t t0,
+                                                      const double* __restrict__ mu, PsiKern kp, double* __restrict__ G2,
+                                                      double* __restrict__ ct, double* __restrict__ out_mean,
+                                                      double* __restrict__ cross, int* __restrict__ bad, int64_t chunk, int M, int Mp,
+                                                      int D, int d_out) {
+    __shared__ double A1[MAXD * PSI_LD], A2[MAXD * PSI_LD], r1[MAXD], r2[MAXD], mt[MAXD], us[MAXD], hs[MAXD];
+    __shared__ int failed;
+    const int lane = threadIdx.x;
+    const int64_t tc = blockIdx.x, t = t0 + tc;
+    if (lane == 0) failed = 0;
+    if (lane < D) mt[lane] = mean[(size_t)t * D + lane];
+    __syncthreads();
+    const double* S = cov ? cov + (size_t)t * D * D : nullptr;
+    psi_factor(A1, r1, &failed, S, kp, 1.0, D, lane);
+    psi_factor(A2, r2, &failed, S, kp, 2.0, D, lane);
+    if (failed) {                                             // (uniform)
+        if (lane == 0) { bad[t] = 1; ct[tc] = 0.0; }
+        if (lane < d_out) out_mean[(size_t)lane * T + t] = 0.0;
+        if (cross)
+            for (int e = lane; e < d_out * D; e += 64) cross[(size_t)t * d_out * D + e] = 0.0;
+        for (int e = lane; e < D * Mp; e += 64) G2[(size_t)e * chunk + tc] = 0.0;
+        return;
+    }
+    double det1 = 1.0, det2 = 1.0;                            // prod_d ell_d / C_dd, in the order d = 0, 1, ..
+    for (int d = 0; d < D; ++d) { det1 *= kp.ell[d] * r1[d]; det2 *= kp.ell[d] * r2[d]; }
+    if (lane == 0) { bad[t] = 0; ct[tc] = det2; }
+    double om[MAXO];
+#pragma unroll
+    for (int o = 0; o < MAXO; ++o) om[o] = 0.0;
+    for (int m = lane; m < Mp; m += 64) {
+        if (DCAP > 8) asm volatile("" ::: "memory");
+        double diff[DCAP], g[DCAP];
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d) diff[d] = (d < D && m < M) ? mt[d] - Xu[(size_t)m * D + d] : 0.0;
+        const double q1 = psi_solve<DCAP>(g, diff, A1, r1, D);
+        const double p1 = kp.sigma2 * det1 * exp(-0.5 * q1);
+        if (m < M) {
+#pragma unroll
+            for (int o = 0; o < MAXO; ++o)
+                if (o < d_out) om[o] = fma(p1, mu[(size_t)o * M + m], om[o]);
+        }
+        psi_solve<DCAP>(g, diff, A2, r2, D);
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d)
+            if (d < D) G2[((size_t)d * Mp + m) * chunk + tc] = g[d];
+    }
+#pragma unroll
+    for (int o = 0; o < MAXO; ++o)
+        if (o < d_out) {                                      // (uniform) lane l summed m = l, l + 64, .. in order; xor butterfly
+            double v = om[o];
+            for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+            if (lane == 0) out_mean[(size_t)o * T + t] = v;
+        }
+    if (!cross) return;
+    if (!S) {                                                 // S = 0: the input and f are uncorrelated
+        for (int e = lane; e < d_out * D; e += 64) cross[(size_t)t * d_out * D + e] = 0.0;
+        return;
+    }
+    for (int o = 0; o < d_out; ++o) {
+        double lu[DCAP];
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d) lu[d] = 0.0;
+        for (int m = lane; m < M; m += 64) {
+            if (DCAP > 8) asm volatile("" ::: "memory");
+            double diff[DCAP], g[DCAP];
+#pragma unroll
+            for (int d = 0; d < DCAP; ++d) diff[d] = d < D ? mt[d] - Xu[(size_t)m * D + d] : 0.0;
+            const double q1 = psi_solve<DCAP>(g, diff, A1, r1, D);
+            const double wv = mu[(size_t)o * M + m] * (kp.sigma2 * det1 * exp(-0.5 * q1));
+#pragma unroll
+            for (int d = 0; d < DCAP; ++d) lu[d] = fma(wv, g[d], lu[d]);     // (g is zero beyond D)
+        }
+        __syncthreads();                                      // (the previous output's us / hs have been read)
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d)
+            if (d < D) {                                      // (uniform)
+                double v = lu[d];
+                for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+                if (lane == 0) us[d] = v;
+            }
+        __syncthreads();
+        if (lane == 0)                                        // h = C_1^-T u, rows D - 1 .. 0
+            for (int i = D - 1; i >= 0; --i) {
+                double s = us[i];
+                for (int j = i + 1; j < D; ++j) s = fma(-A1[j * PSI_LD + i], hs[j], s);
+                hs[i] = s * r1[i];
+            }
+        __syncthreads();
+        if (lane < D) {                                       // row `lane` of -S h; S (r, c), r >= c, is at S[c D + r]
+            double s = 0.0;
+            for (int e = 0; e < D; ++e) s = fma(-(e <= lane ? S[(size_t)e * D + lane] : S[(size_t)lane * D + e]), hs[e], s);
+            cross[((size_t)t * d_out + o) * D + lane] = s;
+        }
+    }
+}
+
+// Once per call: the K = psi_pred_sums(d_out) weight matrices E^(k)_ab = sigma2^2 Q^(k)_ab exp(-1/4 sum_d (z_ad - z_bd)^2 / ell_d^2) on
+// the lower triangle a >= b of the M x M block (E [k][b][Mp] column-major, zero elsewhere): Q^(0) = Kinv and, for outputs j <= i,
+// Q^(1 + i (i + 1) / 2 + j) = 1/2 (R^(ij) + R^(ij)'), R^(ij) the block of R (Qp x Qp) at rows i M, columns j M.  Xus: the scaled
+// inducing inputs [d][Mp] (k_prep_xu).  grid = (Mp columns, K).
+__global__ void __launch_bounds__(256) k_psi_pred_weights(const double* __restrict__ Kinv, const double* __restrict__ R, int Qp,
+                                                          const double* __restrict__ Xus, const Params* __restrict__ P,
+                                                          double* __restrict__ E, int M, int Mp, int D) {
+    const int b = blockIdx.x, k = blockIdx.y;
+    int oi = 0, oj = 0;                                       // k - 1 = oi (oi + 1) / 2 + oj
+    if (k > 0) {
+        int r = k - 1;
+        while (r > oi) { r -= oi + 1; ++oi; }
+        oj = r;
+    }
+    const double s4 = P->sigma2 * P->sigma2;
+    double* Ek = E + (size_t)k * Mp * Mp;
+    for (int a = threadIdx.x; a < Mp; a += 256) {
+        double v = 0.0;
+        if (a >= b && a < M && b < M) {
+            double q = 0.0;
+            for (int d = 0; d < D; ++d) { const double u = Xus[(size_t)d * Mp + a] - Xus[(size_t)d * Mp + b]; q = fma(u, u, q); }
+            const double w = k == 0 ? Kinv[(size_t)b * Mp + a]
+                                    : 0.5 * (R[(size_t)(oj * M + b) * Qp + oi * M + a] + R[(size_t)(oj * M + a) * Qp + oi * M + b]);
+            v = s4 * w * exp(-0.25 * q);
+        }
+        Ek[(size_t)b * Mp + a] = v;
+    }
+}
+
+// The hot path, O(T M^2 (D + K)): k_psi2_in_accumulate's decomposition -- lane = node, workgroup (x, y) owns the PSI_IN_NODES nodes
+// from 256 x of the chunk and slice y of the lower triangle (the work units of PSI_IN_ROWS rows y, y + nslices, .. in order, rows and
+// columns ascending) -- with K running sums per thread:  acc[k] += E^(k)_ij (2 for j < i) exp(-1/4 |g_i + g_j|^2), one exp shared by
+// the K sums (c_t is applied by k_psi_pred_finish).  The K weight rows of a unit and 64 columns are staged in LDS with the factor 2 in
+// them and read as broadcasts; g_i stays in registers over the run of j; g_j is loaded one column ahead.  No cross-lane sum.
+// part [slice][K][chunk]: written, never added to, so the result does not depend on the chunking.  nc: the chunk's nodes.
+template <int DCAP, int K>
+__global__ void __launch_bounds__(PSI_IN_NODES) k_psi2_pred_accumulate(const double* __restrict__ G2, const double* __restrict__ E,
+                                                                       double* __restrict__ part, int64_t nc, int64_t chunk,
+                                                                       int nslices, int M, int Mp, int D) {
+    constexpr int R = PSI_IN_ROWS;
+    __shared__ double Es[K * R * TB];
+    const int tid = threadIdx.x, slice = blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * PSI_IN_NODES + tid;
+    const bool active = n < nc;
+    const double* gp = G2 + (active ? n : 0);
+    const size_t dstride = (size_t)Mp * chunk, mm = (size_t)Mp * Mp;
+    const int nunits = (M + R - 1) / R;
+    double acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    for (int u = slice; u < nunits; u += nslices) {
+        const int i0 = u * R, i1 = i0 + R < M ? i0 + R : M;   // rows i0 .. i1 - 1
+        for (int j0 = 0; j0 < i1; j0 += TB) {
+            __syncthreads();
+            for (int e = tid; e < K * R * TB; e += PSI_IN_NODES) {
+                const int k = e / (R * TB), r = e % (R * TB), i = i0 + (r >> 6), j = j0 + (r & 63);
+                Es[e] = (i < i1 && j <= i) ? (j < i ? 2.0 : 1.0) * E[k * mm + (size_t)j * Mp + i] : 0.0;
+            }
+            __syncthreads();
+            if (!active) continue;
+            for (int i = i0; i < i1; ++i) {
+                const int jn = i - j0 + 1 < TB ? i - j0 + 1 : TB;      // columns j0 .. j0 + jn - 1 (none when j0 > i)
+                if (jn <= 0) continue;
+                double gi[DCAP], gj[DCAP];
+#pragma unroll
+                for (int d = 0; d < DCAP; ++d) {
+                    gi[d] = gj[d] = 0.0;
+                    if (d < D) {                              // (uniform)
+                        gi[d] = gp[d * dstride + (size_t)i * chunk];
+                        gj[d] = gp[d * dstride + (size_t)j0 * chunk];
+                    }
+                }
+                const double* es = Es + (i - i0) * TB;
+                for (int jj = 0; jj < jn; ++jj) {
+                    double q = 0.0;
+#pragma unroll
+                    for (int d = 0; d < DCAP; ++d)
+                        if (d < D) { const double v = gi[d] + gj[d]; q = fma(v, v, q); }
+                    if (jj + 1 < jn) {                        // (uniform) the next column's g, under this one's arithmetic
+#pragma unroll
+                        for (int d = 0; d < DCAP; ++d)
+                            if (d < D) gj[d] = gp[d * dstride + (size_t)(j0 + jj + 1) * chunk];
+                    }
+                    const double ex = exp(-0.25 * q);
+#pragma unroll
+                    for (int k = 0; k < K; ++k) acc[k] = fma(es[k * R * TB + jj], ex, acc[k]);
+                }
+            }
+        }
+    }
+    if (active)
+#pragma unroll
+        for (int k = 0; k < K; ++k) part[((size_t)slice * K + k) * chunk + n] = acc[k];
+}
+
+// Per node (thread = node of the chunk): the slices' sums added in the order 0, 1, .., c_t applied, and
+//   C_f[i][j] = delta_ij (sigma2 - c_t sum^(0)) + c_t sum^(ij) - mean_i mean_j + noise_ij
+// for the lower triangle, stored to both mirror images (out_cov [T][DO][DO]; [T] for DO = 1).  out_mean [DO][T] as k_psi_pred_prep
+// left it; noise: W^-1 by value (column-major DO x DO, symmetric), zero without SGP_PREDICT_NOISE.
+template <int DO>
+__global__ void __launch_bounds__(64) k_psi_pred_finish(const double* __restrict__ part, const double* __restrict__ ct,
+                                                        const double* __restrict__ out_mean, const Params* __restrict__ P, OutMat noise,
+                                                        int64_t T, int64_t t0, int64_t nc, int64_t chunk, int nslices,
+                                                        double* __restrict__ out_cov) {
+    constexpr int K = psi_pred_sums(DO);
+    const int64_t n = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (n >= nc) return;
+    const int64_t t = t0 + n;
+    double acc[K], mn[DO];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double s = 0.0;
+        for (int sl = 0; sl < nslices; ++sl) s += part[((size_t)sl * K + k) * chunk + n];
+        acc[k] = s;
+    }
+#pragma unroll
+    for (int o = 0; o < DO; ++o) mn[o] = out_mean[(size_t)o * T + t];
+    const double c = ct[n], base = P->sigma2 - c * acc[0];
+#pragma unroll
+    for (int i = 0; i < DO; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            const double v = ((i == j ? base : 0.0) + c * acc[1 + i * (i + 1) / 2 + j]) - mn[i] * mn[j] + noise.v[i + j * DO];
+            out_cov[((size_t)t * DO + j) * DO + i] = v;
+            out_cov[((size_t)t * DO + i) * DO + j] = v;
+        }
+}
+
 }  // namespace sgp

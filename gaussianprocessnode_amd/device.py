@@ -552,6 +552,24 @@ class SGPDevice:
                     "sgp_psi_in_grad")
         return U, gamma, Gamma
 
+    def psi_predict(self, mean, cov=None, noise: bool = False, want_cov: bool = True, want_cross: bool = False):
+        """Closed-form prediction at T Gaussian inputs N(mean[t], cov[t]) at the current kernel (sgp_psi_predict; SE only, D <= 32):
+        the mean and covariance of f(x_t) with x_t and v both integrated out, and Cov[x_t, f(x_t)].  mean (T, D), cov (T, D, D)
+        positive semi-definite or None (all zero); q(v) the last finished sweep's or `set_posterior`'s; noise=True adds W^-1 of the last
+        `set_noise`.  Needs no resident data and changes nothing the sweep keeps.  Returns (mean (T, d_out), bitwise `psi_stats`'
+        out_mean; cov (T,) for d_out = 1, (T, d_out, d_out) otherwise, or None; cross (T, D, d_out) or None).  A covariance that is
+        not positive semi-definite at node t raises PosDefException with info = t + 1; a K_uu that is not positive definite raises
+        PosDefException with the failing minor."""
+        m, S, T = self._node_gaussians("psi_predict", mean, cov)
+        out = np.empty((self.d_out, T))
+        var = (np.empty(T) if self.d_out == 1 else np.empty((T, self.d_out, self.d_out))) if want_cov else None
+        cross = np.empty((T, self.d_out, self.D)) if want_cross else None
+        info = (C.c_int64 * 2)()
+        flags = _lib.SGP_PREDICT_NOISE if noise else 0
+        self._check(self._lib.sgp_psi_predict(self._h, ptr(m), ptr(S), T, flags, ptr(out), ptr(var), ptr(cross), info),
+                    "sgp_psi_predict")
+        return out.T.copy(), var, (None if cross is None else cross.transpose(0, 2, 1).copy())
+
     def time_kernel(self, which: int, iters: int = 20, stream: int = 0) -> float:
         """Average launch duration (microseconds, HIP events) of the Gram or streaming-SYRK kernel."""
         v = C.c_double()

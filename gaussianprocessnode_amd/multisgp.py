@@ -183,15 +183,56 @@ def rule_out_batch(q_ins, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta):
         make_message=lambda mean: MvNormalMeanPrecision(mean.copy(), W))
 
 
-def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, noise: bool = True):
+def exact_predict_inputs(x, D: int):
+    """The inputs of `predictive(psi="exact")` as (means (T, D), covs (T, D, D) or None, single): a Gaussian or PointMass is one
+    node (single: the caller returns one mean and covariance), a plain array its rows with S = 0, a list one node per entry."""
+    def is_dist(q):
+        return not isinstance(q, (np.ndarray, list, tuple, float, int)) and hasattr(q, "mean")
+    if is_dist(x):
+        means, covs = gaussian_inputs([x], D)
+        return means, covs, True
+    if isinstance(x, (list, tuple)) and len(x) and all(is_dist(q) for q in x):
+        means, covs = gaussian_inputs(list(x), D)
+        return means, covs, False
+    return np.asarray(x, dtype=np.float64).reshape(-1, D), None, False
+
+
+def exact_predictive(eng, x, q_v, D: int, noise: bool, device: int):
+    """ONE `SGPDevice.psi_predict` call over the inputs of `exact_predict_inputs` with the explicit q_v installed through
+    `set_posterior`, as `marginal_in_exact_batch` installs it; kernel and noise are already the engine's.  Returns (mean (T, d_out),
+    cov as the device returns it, single)."""
+    from .device import potrf
+    means, covs, single = exact_predict_inputs(x, D)
+    mu_v, Sigma_v = q_v.mean_cov()
+    mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
+    Uv = potrf(np.asarray(Sigma_v, dtype=np.float64) + np.outer(mu_v, mu_v), device).T
+    eng.set_posterior(mu_v, Uv)
+    m, C, _ = eng.psi_predict(means, covs, noise=noise)
+    return m, C, single
+
+
+def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, noise: bool = True, psi: str = "cubature"):
     """Predictive means and covariances of the d_out latent outputs (noise=False) or of the observation (noise=True: +
     mean(q_w)^-1) at kernel(q_theta) and the explicit q_v (sgp_predict_var).  Test inputs (ns, D) give means (ns, d_out) and
     covariances (ns, d_out, d_out); a PointMass or an uncertain input q(x*) gives one mean (d_out,) and covariance (d_out,
-    d_out) -- the latter by one device call over meta.method's cubature points and the law of total variance in matrix form."""
+    d_out) -- the latter by one device call over meta.method's cubature points and the law of total variance in matrix form.
+    psi="exact" (SE kernel only) takes a Gaussian, a PointMass, a plain array or a list of inputs through ONE closed-form
+    `SGPDevice.psi_predict` call instead -- no cubature points; a list gives stacked means (T, d_out) and covariances."""
     from .unisgp import _test_points, combine_total_variance
+    _check_psi(psi, "predictive")
     W = _mean_W(q_w)
     d_out = W.shape[0]
     D = np.asarray(meta.Xu).shape[1]
+    if psi == "exact":
+        require_se(kernel_family(meta.kernel))
+        eng = _aux_engine_out(meta, d_out)
+        sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+        if noise:
+            eng.set_noise(W)
+        m, C, single = exact_predictive(eng, Xstar_or_q_in, q_v, D, noise, meta.device)
+        C = np.asarray(C, dtype=np.float64).reshape(-1, d_out, d_out)
+        return (m[0], C[0]) if single else (m, C)
     X, wts = _test_points(Xstar_or_q_in, meta.method, D)
     eng = _engine(meta, 1, d_out)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
@@ -246,6 +287,22 @@ def _aux_engine(meta: MultiSGPMeta, n: int):
         eng = SGPDevice(max(n, 64), M, D, 1, device=meta.device, keep_kuf=True)
         eng.set_inducing(Xu)
         meta._aux_engine = eng
+    return eng
+
+
+def _aux_engine_out(meta: MultiSGPMeta, d_out: int):
+    """A d_out-output device object without data for the closed-form prediction: `set_posterior` replaces its q(v), so it is not
+    the engine that holds the last swept sequence."""
+    Xu = np.asarray(meta.Xu, dtype=np.float64)
+    M, D = Xu.shape
+    eng = getattr(meta, "_aux_engine_out", None)
+    if eng is None or eng.d_out != d_out:
+        from .device import SGPDevice
+        if eng is not None:
+            eng.close()
+        eng = SGPDevice(1, M, D, d_out, device=meta.device)
+        eng.set_inducing(Xu)
+        meta._aux_engine_out = eng
     return eng
 
 

@@ -533,3 +533,38 @@ def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iteratio
                              psi=theta_psi)
         post = (q_x, q_v, q_w)
     return theta, fe_values, post
+
+
+def forecast_gpssm(q_x, steps, q_v, q_w, q_theta, meta, noise=True):
+    """Roll the GP-SSM transition x_{k+1} ~ MultiSGP(x_k, v, W, theta) forward from q_x -- one Gaussian, or a list of B of them (a
+    batch of trajectories) -- in closed form (SE kernel only; d_out must equal D).  Each step is ONE `SGPDevice.psi_predict` call over
+    the B current Gaussians: Gaussian in, moment-matched Gaussian out, x_{k+1} ~ N(mean, C_f + mean(q_W)^-1) (noise=False leaves the
+    process noise out: the latent f alone).  No cubature points are formed.  q(v) is installed through `set_posterior` on the
+    auxiliary engine once.  Returns (means (steps, B, D), covariances (steps, B, D, D))."""
+    from . import multisgp as MS
+    from .cubature import gaussian_inputs, require_se
+    from .device import potrf
+    from .meta import kernel_family, set_engine_kernel
+    require_se(kernel_family(meta.kernel))
+    q0 = list(q_x) if isinstance(q_x, (list, tuple)) else [q_x]
+    D = np.asarray(meta.Xu).shape[1]
+    W = MS._mean_W(q_w)
+    if W.shape[0] != D:
+        raise ValueError(f"forecast_gpssm: the transition maps D = {D} inputs to d_out = {W.shape[0]} outputs; a rollout needs d_out = D")
+    steps = int(steps)
+    m, S = gaussian_inputs(q0, D)
+    means, covs = np.empty((steps, len(q0), D)), np.empty((steps, len(q0), D, D))
+    if not q0 or steps < 1:
+        return means, covs
+    eng = MS._aux_engine_out(meta, D)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    eng.set_noise(W)
+    mu_v, Sigma_v = q_v.mean_cov()
+    mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
+    eng.set_posterior(mu_v, potrf(np.asarray(Sigma_v, dtype=np.float64) + np.outer(mu_v, mu_v), meta.device).T)
+    for k in range(steps):
+        m, S, _ = eng.psi_predict(m, S, noise=noise)
+        S = np.asarray(S, dtype=np.float64).reshape(len(q0), D, D)
+        means[k], covs[k] = m, S
+    return means, covs

@@ -407,13 +407,27 @@ def combine_total_variance(wts, m, var):
     return mean, second - np.outer(mean, mean)
 
 
-def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool = True):
+def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool = True, psi: str = "cubature"):
     """Predictive mean and variance of the latent f (noise=False) or of the observation y (noise=True: + 1 / mean(q_w)) at
     kernel(q_theta) and the explicit q_v (`q_v.mean_cov()` goes to the device, sgp_predict_var).  Test inputs (ns, D) give
     per-point arrays (ns,), (ns,); a PointMass or an uncertain input q(x*) gives two floats -- the latter by one device call over
     meta.method's cubature points and the law of total variance on the host.  `rule_out` is unchanged (the reference's
-    message carries precision mean(q_w) only)."""
+    message carries precision mean(q_w) only).  psi="exact" (SE kernel only) takes a Gaussian, a PointMass, a plain array or a
+    list of inputs through ONE closed-form `SGPDevice.psi_predict` call on the auxiliary engine instead -- no cubature points; a
+    list gives per-input arrays (T,), (T,)."""
     D = meta.Xu.shape[1]
+    if psi not in ("cubature", "exact"):
+        raise ValueError(f"predictive: psi must be 'cubature' or 'exact', got {psi!r}")
+    if psi == "exact":
+        from .multisgp import exact_predictive
+        require_se(kernel_family(meta.kernel))
+        eng = _aux_engine(meta, 1)
+        sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+        if noise:
+            eng.set_noise([[_mean_w(q_w)]], _elog_w(q_w))
+        m, v, single = exact_predictive(eng, Xstar_or_q_in, q_v, D, noise, meta.device)
+        return (float(m[0, 0]), float(v[0])) if single else (m[:, 0].copy(), v)
     X, wts = _test_points(Xstar_or_q_in, meta.method, D)
     eng = _engine(meta, 1)
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))

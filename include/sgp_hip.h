@@ -559,6 +559,33 @@ int sgp_psi_in_grad(sgp_handle* h, const double* mean /* D x T */, const double*
                     const double* y_mean /* T x d_out */, int64_t n_nodes, double* energy /* T, may be NULL */,
                     double* grad_mean /* D x T */, double* grad_cov /* D x D x T, may be NULL */, int64_t* info /* 2, may be NULL */);
 
+/* ---- closed-form prediction at Gaussian inputs: Gaussian in, moment-matched Gaussian out ----
+ * With q(v) = N(mu, Sigma_v), R^(ij) = Sigma_v^(ij) + mu^(i) mu^(j)', Kinv = (K_uu + jitter I)^-1 and x_t ~ N(m_t, S_t) (SGP_KERNEL_SE only,
+ * d_out = 1 .. 4, D = 1 .. 32), the first two moments of f(x_t) with x_t and v both integrated out, and its covariance with the input:
+ *     out_mean[t, i] = Psi1_t' mu^(i)                                              (bitwise sgp_psi_stats' out_mean)
+ *     out_cov[t][i][j] = delta_ij (sigma2 - tr(Kinv Psi2_t)) + tr(R^(ij) Psi2_t) - out_mean[t,i] out_mean[t,j]      (exactly symmetric)
+ *     cross[t][:, i] = Cov[x_t, f_i] = S_t P_1 sum_m mu^(i)_m Psi1_t[m] (z_m - m_t),    P_1 = (Lambda + S_t)^-1
+ * SGP_PREDICT_NOISE adds W^-1 (of the last sgp_set_noise) to out_cov, as sgp_predict_var does.  At S_t = 0 mean and covariance are
+ * sgp_predict_var's at the point m_t and cross = 0 (exactly 0 when cov is NULL).
+ *
+ * mean D x T, cov D x D x T (lower triangles read) or NULL for S = 0, all finite; q(v) is the last finished sweep's, or
+ * sgp_set_posterior's when that came later.  Blocking; everything is formed in call scratch at the current kernel, the nodes in chunks
+ * (SGP_PREDICT_CHUNK): the resident statistics, K_uu chain, q(v) and sgp_sweep_kind are unchanged, and outside call scratch the call
+ * touches only what sgp_theta_objective_psi touches.  All sums run in a fixed order without atomics: identical calls agree bitwise, also
+ * under different SGP_PREDICT_CHUNK.  n_nodes = 0 returns 0 with nothing done.
+ *
+ * info (2, may be NULL) = [the failing leading minor of K_uu or 0 (K_uu is only factored when out_cov is wanted), the first node whose
+ * Lambda + S_t or Lambda + 2 S_t is not positive definite, + 1, or 0]; the return value is the positive entry (the node check comes
+ * first) and sgp_last_error names which failed.
+ *
+ * SGP_ERR_ARG: everything sgp_theta_objective_psi refuses (family, no inducing inputs / kernel / q(v), non-finite inputs, an open
+ * sgp_train_* run, an installed all-reduce hook); a NULL out_mean; unknown flag bits; SGP_PREDICT_NOISE with a W that is not positive
+ * definite. */
+int sgp_psi_predict(sgp_handle* h, const double* mean /* D x T */, const double* cov /* D x D x T or NULL */, int64_t n_nodes,
+                    int32_t flags /* 0 | SGP_PREDICT_NOISE */, double* out_mean /* T x d_out column-major, required */,
+                    double* out_cov /* [T] for d_out = 1, else [T][d_out][d_out]; may be NULL */,
+                    double* cross /* [T][d_out][D], i.e. D x d_out x T column-major; may be NULL */, int64_t* info /* 2, may be NULL */);
+
 /* ---- building blocks exposed for tests / other callers (host pointers, blocking) ------------
  * K = sigma2 * exp(-0.5 |(a-b)/ell|^2): kernelmatrix(kernel(theta), A, B) of KernelFunctions.jl as called at
  * GPnode/UniSGPnode.jl:102,153; A is D x na, B is D x nb, K is na x nb column-major. */

@@ -594,6 +594,19 @@ function psi_in_grad(h::Handle, m::Matrix{Float64}, S, y::Matrix{Float64})
     return U, γ, Γ
 end
 
+# ---- closed-form prediction at Gaussian inputs (sgp_psi_predict; SE kernel only, D <= 32): per node t with input x_t ~ N(m_t, S_t) the
+# mean and covariance of f(x_t) with x_t and v both integrated out, and Cov[x_t, f(x_t)].  m is D × T, S is D × D × T or nothing
+# (S = 0); q(v) and W are the handle's; noise = true adds W⁻¹.  Returns (mean (T × d_out), C_f (d_out × d_out × T; a vector of T for
+# d_out = 1), cross (D × d_out × T)).  PosDefException(t + 1) names an indefinite node, PosDefException(k) a K_uu that failed.
+function psi_predict(h::Handle, m::Matrix{Float64}, S, d_out::Integer; noise::Bool = false)
+    D, T = size(m); μ = zeros(T, d_out); info = zeros(Int64, 2)
+    C = d_out == 1 ? zeros(T) : zeros(d_out, d_out, T); X = zeros(D, d_out, T)
+    check(ccall((:sgp_psi_predict, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, m, S === nothing ? C_NULL : S, T, noise ? Int32(1) : Int32(0), μ, C, X, info), h.ptr)
+    return μ, C, X
+end
+
 # The classification loop (experiments/classification_banana.ipynb cell 9: `y[i] ~ Probit(f[i])`, q(w) = GammaShapeRate carried
 # over the minibatches, q(v) never reset): labels 0 / 1 in y; returns (θ, shape, rate).  sgp_train_likelihood turns the run
 # opened by sgp_train_begin into this loop -- forward message, Probit moment matching, Gamma update and AdaMax on the device.

@@ -1,8 +1,8 @@
 // Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over grids of shapes, the
-// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta and layout_psi_in hand out are
+// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in and layout_psi_predict hand out are
 // pairwise disjoint at the sizes their consumers need (stated here independently of the layout functions), every piece starts a
 // multiple of Carver::ALIGN doubles from the base, pass 2 hands out the total pass 1 summed and the last piece ends there.  The
-// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta and layout_psi_in get an allocation of
+// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta, layout_psi_in and layout_psi_predict get an allocation of
 // exactly their total per shape and every piece is written end to end, so that the sanitizer sees a write past it.  No GPU:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o tools/point_scratch_check tools/point_scratch_check.cpp
 //   (or any C++17 compiler with -fsanitize=address,undefined) && tools/point_scratch_check
@@ -274,6 +274,41 @@ long psi_in_sweep() {
                         }
     return shapes;
 }
+// sgp_psi_predict over its grid (D up to 32), each shape in an allocation of its own: with and without input covariances, with and
+// without C_f and cross, the slice count of psi_in_slices and 1 + d_out (d_out + 1) / 2 sums
+long psi_predict_sweep() {
+    long shapes = 0;
+    for (int M : {1, 48, 65, 130})
+        for (int D : {1, 2, 5, 8, 9, 32})
+            for (int dout : {1, 2, 3, 4})
+                for (int64_t n : {1, 65, 257, 300})
+                    for (int64_t chunk : {(int64_t)64, (n + 63) / 64 * 64})
+                        for (int opt = 0; opt < 8; ++opt) {
+                            const bool cov = opt & 1, want = opt & 2, wcross = opt & 4;
+                            const int Mp = (M + TB - 1) / TB * TB, T = Mp / TB;
+                            const size_t sums = 1 + (size_t)dout * (dout + 1) / 2;
+                            const size_t slices = (size_t)std::min<int64_t>((M + 7) / 8, std::max<int64_t>(1, 1024 / ((n + 255) / 256)));
+                            const PointShape s{Mp, 0, T, D, dout, POTRF_SCRATCH, std::min(chunk, (n + 63) / 64 * 64), n, n};
+                            check("psi_predict", s, 0, nullptr, 0, true, [&](Carver& c) {
+                                PsiPredictScratch b;
+                                layout_psi_predict(c, s, cov, want, wcross, slices, sums, &b);
+                                const size_t nn = (size_t)n, ch = (size_t)s.chunk, mm = (size_t)Mp * Mp * d;
+                                const std::vector<Piece> all = {
+                                    {"Mean", b.Mean, nn * D * d}, {"Cov", b.Cov, cov ? nn * D * D * d : 0}, {"Bad", b.Bad, nn * sizeof(int)},
+                                    {"OutMean", b.OutMean, nn * dout * d}, {"OutCov", b.OutCov, want ? nn * dout * dout * d : 0},
+                                    {"Cross", b.Cross, wcross ? nn * dout * D * d : 0}, {"G2", b.G2, ch * D * Mp * d},
+                                    {"Ct", b.Ct, ch * d}, {"Part", b.Part, ch * slices * sums * d}, {"E", b.E, sums * mm},
+                                    {"Kuu", b.Kuu, mm}, {"Wk", b.Wk, mm}, {"Kinv", b.Kinv, mm},
+                                    {"Pscr", b.Pscr, (size_t)POTRF_SCRATCH * d}, {"Info", b.Info, sizeof(int)}};
+                                std::vector<Piece> p;
+                                for (const Piece& q : all)
+                                    if (q.bytes) p.push_back(q);                  // (a piece that is not wanted has no extent)
+                                return p;
+                            });
+                            ++shapes;
+                        }
+    return shapes;
+}
 }  // namespace
 
 int main() {
@@ -288,7 +323,9 @@ int main() {
     const long psi = psi_sweep();
     const long psi_theta = psi_theta_sweep();
     const long psi_in = psi_in_sweep();
+    const long psi_predict = psi_predict_sweep();
     std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes, %ld psi shapes, %ld psi-theta shapes, "
-                "%ld psi-in shapes: %ld failure(s)\n", panel, largest, mean_only, psi, psi_theta, psi_in, failures);
+                "%ld psi-in shapes, %ld psi-predict shapes: %ld failure(s)\n", panel, largest, mean_only, psi, psi_theta, psi_in,
+                psi_predict, failures);
     return failures ? 1 : 0;
 }

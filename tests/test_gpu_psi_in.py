@@ -45,17 +45,26 @@ def G():
     return g
 
 
+# (M, D): lengthscale over sqrt(D) where the default would leave K_uu ill conditioned (it stays below 1e5)
+SCALES = {(65, 1): 0.06, (130, 2): 0.2, (64, 2): 0.3, (128, 2): 0.15, (17, 1): 0.2}
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
+    return problem(name, CASES[name], 900 + sorted(CASES).index(name))
+
+
+def problem(name, spec, seed, subset=None):
     """The inputs of a case and the reference's U, gamma, Gamma (computed once; arrays not to be written to), built as
-    tests/test_gpu_psi_theta.py builds its cases: q(v) is one VMP update from an isotropic prior over the exact statistics."""
-    d_out, M, D, T, shared, cov = CASES[name]
-    rng = np.random.default_rng(900 + sorted(CASES).index(name))
+    tests/test_gpu_psi_theta.py builds its cases: q(v) is one VMP update from an isotropic prior over the exact statistics.
+    subset: the nodes q(v) is fitted to and the reference is evaluated at (an index array; default: all of them)."""
+    d_out, M, D, T, shared, cov = spec
+    rng = np.random.default_rng(seed)
     if (M, D) == (48, 2):
         Xu, ell, lo, hi = DR.pendulum_grid(), np.array([0.4, 1.0]), np.array([-1.3, -3.7]), np.array([1.3, 3.7])
     else:
         Xu = np.stack([rng.permutation(np.linspace(-1.7, 1.7, M)) for _ in range(D)], axis=1)
-        scale = {(65, 1): 0.06, (130, 2): 0.2}.get((M, D), 0.45) * np.sqrt(D)     # (K_uu stays well conditioned: below 1e5)
+        scale = SCALES.get((M, D), 0.45) * np.sqrt(D)
         ell = np.full(D, scale) if shared else scale * np.linspace(0.9, 1.1, D)
         lo, hi = np.full(D, -1.7), np.full(D, 1.7)
     mean = rng.uniform(lo, hi, (T, D))
@@ -72,13 +81,15 @@ def case(name):
     Y = np.sin(mean @ rng.normal(size=(D, d_out)) / np.sqrt(D) * 2.0) + 0.05 * rng.normal(size=(T, d_out))
     A = rng.normal(size=(d_out, d_out))
     W = 20.0 * (A @ A.T / d_out + np.eye(d_out))
-    psi1, psi2 = PR.psi_stats(Xu, SIGMA2, ell, mean, S)
+    sel = slice(None) if subset is None else subset
+    S_sel = None if S is None else S[sel]
+    psi1, psi2 = PR.psi_stats(Xu, SIGMA2, ell, mean[sel], S_sel)
     Sig = np.linalg.inv(np.kron(W, psi2) + np.eye(d_out * M) / 50.0)
     Sig = 0.5 * (Sig + Sig.T)
-    mu = Sig @ ((psi1.T @ Y) @ W.T).T.ravel()
+    mu = Sig @ ((psi1.T @ Y[sel]) @ W.T).T.ravel()
     Rv = Sig + np.outer(mu, mu)
     ell_arg = ell[:1] if shared else ell
-    U, gamma, Gamma = R.evaluate(SIGMA2, ell_arg, mean, S, Y, Rv, mu, W, Xu, JITTER)
+    U, gamma, Gamma = R.evaluate(SIGMA2, ell_arg, mean[sel], S_sel, Y[sel], Rv, mu, W, Xu, JITTER)
     return dict(name=name, d_out=d_out, M=M, D=D, T=T, ell=ell_arg, mean=mean, S=S, Y=Y, W=W, Xu=Xu, mu=mu, Sig=Sig, Rv=Rv, jitter=JITTER,
                 U=U, gamma=gamma, Gamma=Gamma)
 

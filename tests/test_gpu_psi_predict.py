@@ -48,19 +48,28 @@ def G():
     return g
 
 
+# (M, D): lengthscale over sqrt(D) where the default would leave K_uu ill conditioned (it stays below 1e5)
+SCALES = {(65, 1): 0.06, (130, 2): 0.2, (64, 2): 0.3, (128, 2): 0.15, (17, 1): 0.2}
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
-    """The inputs of a case and the reference's results (computed once; arrays not to be written to), built as
-    tests/test_gpu_psi_in.py builds its cases: q(v) is one VMP update from an isotropic prior over the exact statistics.  The three
-    cov_* cases share one seed, so that they differ in the covariances alone."""
-    d_out, M, D, T, shared, cov = CASES[name]
+    """The three cov_* cases share one seed, so that they differ in the covariances alone."""
     seed_name = "cov_null" if name.startswith("cov_") else name
-    rng = np.random.default_rng(1700 + sorted(CASES).index(seed_name))
+    return problem(name, CASES[name], 1700 + sorted(CASES).index(seed_name))
+
+
+def problem(name, spec, seed, subset=None):
+    """The inputs of a case and the reference's results (computed once; arrays not to be written to), built as
+    tests/test_gpu_psi_in.py builds its cases: q(v) is one VMP update from an isotropic prior over the exact statistics.
+    subset: the nodes q(v) is fitted to and the reference is evaluated at (an index array; default: all of them)."""
+    d_out, M, D, T, shared, cov = spec
+    rng = np.random.default_rng(seed)
     if (M, D) == (48, 2):
         Xu, ell, lo, hi = DR.pendulum_grid(), np.array([0.4, 1.0]), np.array([-1.3, -3.7]), np.array([1.3, 3.7])
     else:
         Xu = np.stack([rng.permutation(np.linspace(-1.7, 1.7, M)) for _ in range(D)], axis=1)
-        scale = {(65, 1): 0.06, (130, 2): 0.2}.get((M, D), 0.45) * np.sqrt(D)     # (K_uu stays well conditioned: below 1e5)
+        scale = SCALES.get((M, D), 0.45) * np.sqrt(D)
         ell = np.full(D, scale) if shared else scale * np.linspace(0.9, 1.1, D)
         lo, hi = np.full(D, -1.7), np.full(D, 1.7)
     mean = rng.uniform(lo, hi, (T, D))
@@ -71,13 +80,14 @@ def case(name):
     Y = np.sin(mean @ rng.normal(size=(D, d_out)) / np.sqrt(D) * 2.0) + 0.05 * rng.normal(size=(T, d_out))
     B = rng.normal(size=(d_out, d_out))
     W = 20.0 * (B @ B.T / d_out + np.eye(d_out))
-    psi1, psi2 = PR.psi_stats(Xu, SIGMA2, ell, mean, S_full)          # (q(v) from the full covariances in every cov_* case)
+    sel = slice(None) if subset is None else subset
+    psi1, psi2 = PR.psi_stats(Xu, SIGMA2, ell, mean[sel], S_full[sel])   # (q(v) from the full covariances in every cov_* case)
     Sig = np.linalg.inv(np.kron(W, psi2) + np.eye(d_out * M) / 50.0)
     Sig = 0.5 * (Sig + Sig.T)
-    mu = Sig @ ((psi1.T @ Y) @ W.T).T.ravel()
+    mu = Sig @ ((psi1.T @ Y[sel]) @ W.T).T.ravel()
     Rv = Sig + np.outer(mu, mu)
     ell_arg = ell[:1] if shared else ell
-    out, Cf, cross, mag, cmag = R.predict(SIGMA2, ell_arg, mean, S, Rv, mu, Xu, d_out, JITTER)
+    out, Cf, cross, mag, cmag = R.predict(SIGMA2, ell_arg, mean[sel], None if S is None else S[sel], Rv, mu, Xu, d_out, JITTER)
     return dict(name=name, d_out=d_out, M=M, D=D, T=T, ell=ell_arg, mean=mean, S=S, W=W, Xu=Xu, mu=mu, Sig=Sig, Rv=Rv,
                 out=out, Cf=Cf, cross=cross, mag=mag, cmag=cmag)
 
@@ -102,10 +112,10 @@ def full(C_f, d_out):
 
 
 def error_over_bound(Cf, cross, Cf_ref, cross_ref, mag, cmag):
-    ec = float(np.max(np.abs(Cf - Cf_ref) / (VALUE_RTOL * mag)))
-    safe = np.where(cmag > 0, cmag, 1.0)
-    ex = float(np.max(np.where(cmag > 0, np.abs(cross - cross_ref) / (VALUE_RTOL * safe), np.where(cross == cross_ref, 0.0, np.inf))))
-    return ec, ex
+    def over(got, ref, mag):                 # where the magnitude is exactly zero (nothing to cancel) equality is demanded
+        safe = np.where(mag > 0, mag, 1.0)
+        return float(np.max(np.where(mag > 0, np.abs(got - ref) / (VALUE_RTOL * safe), np.where(got == ref, 0.0, np.inf))))
+    return over(Cf, Cf_ref, mag), over(cross, cross_ref, cmag)
 
 
 def assert_close(label, Cf, cross, c, ref=None):

@@ -27,10 +27,10 @@ def rel_max(a, b):
     return float(np.max(np.abs(np.asarray(a) - np.asarray(b))) / max(np.max(np.abs(b)), 1e-300))
 
 
-def problem(M, D, T, seed, ard=True, cov="full", d_out=1):
+def problem(M, D, T, seed, ard=True, cov="full", d_out=1, ell_scale=1.0):
     rng = np.random.default_rng(seed)
     Xu = rng.uniform(-2.0, 2.0, (M, D))
-    ell = np.linspace(0.9, 1.6, D) * np.sqrt(D) if ard else np.array([1.3 * np.sqrt(D)])
+    ell = (np.linspace(0.9, 1.6, D) * np.sqrt(D) if ard else np.array([1.3 * np.sqrt(D)])) * ell_scale
     mean = rng.uniform(-2.0, 2.0, (T, D))
     if cov == "full":                                   # eigenvalues up to ~ell^2
         A = rng.normal(size=(T, D, D)) * 0.7
@@ -54,8 +54,9 @@ def device(G, Xu, ell, d_out=1, sigma2=0.8):
     return dev
 
 
-def check(G, M, D, T, seed, ard=True, cov="full", d_out=1, weights=False):
-    Xu, ell, mean, S, mu = problem(M, D, T, seed, ard, cov, d_out)
+def check(G, M, D, T, seed, ard=True, cov="full", d_out=1, weights=False, ell_scale=1.0):
+    """one case against the restatement, with every property this suite asserts; returns the device's psi1, psi2 and :out means"""
+    Xu, ell, mean, S, mu = problem(M, D, T, seed, ard, cov, d_out, ell_scale)
     w = None
     if weights:
         w = np.random.default_rng(seed + 1).uniform(0.0, 2.0, T)
@@ -72,6 +73,7 @@ def check(G, M, D, T, seed, ard=True, cov="full", d_out=1, weights=False):
     for a, b in zip((psi1, psi2, out), again):
         assert np.array_equal(a, b)
     assert e1 < TOL and e2 < TOL and eo < TOL, (e1, e2, eo)
+    return psi1, psi2, out
 
 
 @pytest.mark.parametrize("M", [1, 48, 65, 130])

@@ -36,6 +36,10 @@ CASES = {
 }
 
 
+# (M, D): lengthscale over sqrt(D) where the default would leave K_uu ill conditioned (it stays below 1e5)
+SCALES = {(65, 1): 0.06, (130, 2): 0.2, (64, 2): 0.3}
+
+
 @pytest.fixture(scope="module")
 def G():
     import gaussianprocessnode_amd as g
@@ -44,15 +48,19 @@ def G():
 
 @functools.lru_cache(maxsize=None)
 def case(name):
+    return problem(name, CASES[name], 500 + sorted(CASES).index(name))
+
+
+def problem(name, spec, seed):
     """The inputs of a case and the reference's value and gradient (computed once; arrays not to be written to).  q(v) is one VMP
     update from an isotropic prior over the exact statistics, so that the terms of the objective have their usual sizes."""
-    d_out, M, D, T, shared, cov, jitter = CASES[name]
-    rng = np.random.default_rng(500 + sorted(CASES).index(name))
+    d_out, M, D, T, shared, cov, jitter = spec
+    rng = np.random.default_rng(seed)
     if (M, D) == (48, 2):
         Xu, ell, lo, hi = DR.pendulum_grid(), np.array([0.4, 1.0]), np.array([-1.3, -3.7]), np.array([1.3, 3.7])
     else:
         Xu = np.stack([rng.permutation(np.linspace(-1.7, 1.7, M)) for _ in range(D)], axis=1)
-        scale = {(65, 1): 0.06, (130, 2): 0.2}.get((M, D), 0.45) * np.sqrt(D)     # (K_uu stays well conditioned: below 1e5)
+        scale = SCALES.get((M, D), 0.45) * np.sqrt(D)
         ell = np.full(D, scale) if shared else scale * np.linspace(0.9, 1.1, D)
         lo, hi = np.full(D, -1.7), np.full(D, 1.7)
     mean = rng.uniform(lo, hi, (T, D))

@@ -30,10 +30,14 @@ def G():
 
 @functools.lru_cache(maxsize=None)
 def case(name):
+    return problem(name, CASES[name], 900 + sorted(CASES).index(name))
+
+
+def problem(name, spec, seed):
     """The inputs of a case and the NumPy loop's theta and values (once; arrays not to be written to).  q(v): one VMP update over the
     exact statistics at theta0 from an isotropic prior."""
-    d_out, M, D, T, jitter, steps, eta = CASES[name]
-    rng = np.random.default_rng(900 + sorted(CASES).index(name))
+    d_out, M, D, T, jitter, steps, eta = spec
+    rng = np.random.default_rng(seed)
     if name == "pendulum":                                           # tests/theta_descend_ref.pendulum(60), inputs taken as Gaussians
         means, covs, Y = DR.pendulum(T)
         covs = np.stack(covs)
@@ -92,7 +96,12 @@ def rel(a, b):
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_device_paced_matches_the_host_paced_loop_and_the_restatement(G, name):
-    c = case(name)
+    compare(G, case(name))
+
+
+def compare(G, c):
+    """the device-paced descent of a case against the host-paced loop and the NumPy loop, with the bounds of this suite"""
+    name = c["name"]
     with device(G, c) as dev:
         f0 = dev.theta_objective_psi(c["means"], c["covs"], c["Y"])
         theta, values, taken, state = descend(dev, c)

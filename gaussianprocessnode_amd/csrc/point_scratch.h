@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
 // sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad,
-// sgp_psi_predict).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
+// sgp_psi_predict, sgp_theta_objective_xu).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -287,6 +287,16 @@ static inline void layout_psi_predict(Carver& c, const PointShape& p, bool has_c
     b->Kinv = c.take<double>(mm);
     b->Pscr = c.take<double>((size_t)p.potrf_scratch);
     b->Info = c.take<int>(1);
+}
+
+// sgp_theta_objective_xu (p.n = the resident points; no chunking): the data half's partials ([range][tile row][D][64]), the K_uu
+// half's ([J][I][D][64]) and the gradient (M x D)
+struct XuGradScratch { double *PartUF, *PartUU, *Grad; };
+static inline void layout_xu_grad(Carver& c, const PointShape& p, int M, size_t nranges, XuGradScratch* b) {
+    const size_t tile = (size_t)p.D * 64;
+    b->PartUF = c.take<double>(nranges * p.T * tile);
+    b->PartUU = c.take<double>((size_t)p.T * p.T * tile);
+    b->Grad = c.take<double>((size_t)M * p.D);
 }
 
 // sgp_predict: the points, their means and an explicit mu_v (Q entries, unpadded)

@@ -3003,14 +3003,15 @@ static int theta_objective_eval(sgp_handle* h, hipStream_t s, double* value, con
     return 0;
 }
 
-extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
-    if (!h || !value) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: null argument");
-    if (int prc = refuse_exact_psi(h, "sgp_theta_objective")) return prc;
-    if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: needs a finished sweep or sgp_set_posterior (q(v))");
-    if (!h->have_data || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: data and kernel must be set");
-    if (h->training) return fail(h, SGP_ERR_ARG, "sgp_theta_objective: a device-paced training run is open (sgp_train_end first)");
+// sgp_theta_objective, and the front half of sgp_theta_objective_xu under its own name (`name`: the refusals' prefix)
+static int theta_objective_call(sgp_handle* h, const char* name, double* value, double* grad) {
+    if (!h || !value) return refuse(h, name, "null argument");
+    if (int prc = refuse_exact_psi(h, name)) return prc;
+    if (!h->swept) return refuse(h, name, "needs a finished sweep or sgp_set_posterior (q(v))");
+    if (!h->have_data || !h->have_kernel) return refuse(h, name, "data and kernel must be set");
+    if (int trc = refuse_training(h, name)) return trc;
     if (h->dout > 1 && h->allreduce)
-        return fail(h, SGP_ERR_ARG, "sgp_theta_objective: data-sharded MultiSGP theta objectives are not supported (remove the hook)");
+        return refuse(h, name, "data-sharded MultiSGP theta objectives are not supported (remove the hook)");
     if (int wrc = sync_checked(h)) return wrc;
     hipStream_t s = h->own;
     // Same theta, data and noise as the sweep that produced q(v) -- the notebooks' call pattern
@@ -3041,6 +3042,75 @@ extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy(grad, h->dGrad, sizeof(double) * (1 + h->n_ell), hipMemcpyDeviceToHost));
     for (int i = 0; i <= h->n_ell; ++i) grad[i] *= wscale;
+    return 0;
+}
+
+extern "C" int sgp_theta_objective(sgp_handle* h, double* value, double* grad) {
+    return theta_objective_call(h, "sgp_theta_objective", value, grad);
+}
+
+// ---- the same objective's gradient in the inducing inputs (include/sgp_hip.h: sgp_theta_objective_xu; k_xu_grad_* in
+// ---- sgp_kernels.hip.h) ----
+// The point-block ranges of k_xu_grad_uf: a function of the resident point count and the tile count alone, so the sums depend on
+// nothing else.  About 256 workgroups (the kernel's LDS lets one share a CU) where there are that many point blocks; scratch is
+// ranges x Mp x D doubles whatever N.
+static void xu_ranges(int64_t n, int T, int* nranges, int* range_len) {
+    const int64_t nblk = (n + TB - 1) / TB;
+    const int64_t want = std::max<int64_t>(1, std::min<int64_t>(nblk, std::max(1, 256 / T)));
+    *range_len = (int)((nblk + want - 1) / want);
+    *nranges = (int)((nblk + *range_len - 1) / *range_len);
+}
+
+// sgp_theta_objective with its gradient runs first, unchanged: value and grad are its own, and it leaves G (d_out > 1: with the
+// padded mean columns and omega W y in dThetaMulti) and H in dGradM, K_uf, the scaled inducing inputs and the parameter mirror at the
+// current theta on both of its paths.  The new kernels read those behind it; what they write is call scratch.
+extern "C" int sgp_theta_objective_xu(sgp_handle* h, double* value, double* grad, double* grad_xu) {
+    const char* name = "sgp_theta_objective_xu";
+    if (h && value && !grad_xu) return refuse(h, name, "grad_xu is NULL (sgp_theta_objective returns value and theta gradient alone)");
+    if (h && h->allreduce) return refuse(h, name, "data-sharded inducing-input gradients are not supported (remove the hook)");
+    double gtheta[GRAD_SLOTS];
+    if (int rc = theta_objective_call(h, name, value, gtheta)) return rc;
+    if (grad)
+        for (int i = 0; i <= h->n_ell; ++i) grad[i] = gtheta[i];
+    const int Mp = h->Mp, T = h->T, D = h->D;
+    hipStream_t s = h->own;
+    if (h->side) HIPCHK(h, hipStreamSynchronize(h->side));     // (the K_uu half's H came from there; its join is a bounded wait)
+    int nranges = 0, range_len = 1;
+    if (h->n > 0) xu_ranges(h->n, T, &nranges, &range_len);
+    const PointShape shape = point_shape(h, 1, h->n, h->n);
+    XuGradScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_xu_grad(c, shape, h->M, (size_t)nranges, &b); })) return crc;
+    const double* dG = h->dGradM;
+    const double* dH = h->dGradM + 2 * (size_t)Mp * Mp;
+    const bool multi = h->dout > 1;
+    by_family(h->family, [&](auto F) {
+        hipLaunchKernelGGL(k_xu_grad_uu<decltype(F)::value>, dim3(T, T), dim3(256), 0, s, dH, (const double*)h->dXus,
+                           (const Params*)h->dParams, b.PartUU, h->M, Mp, D);
+    });
+    if (nranges > 0) {
+        const double* yw = h->dYw;
+        const double* mu = h->dMu;
+        if (multi) {                                           // (as enqueue_theta_grad: formed by enqueue_theta_multi_value)
+            yw = h->dThetaMulti + 2 * (size_t)h->Qp * h->Qp;
+            mu = yw + (size_t)h->dout * (size_t)std::max<int64_t>(h->n_max, 1);
+        }
+        auto launch = [&](auto DO) {
+            by_family(h->family, [&](auto F) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_xu_grad_uf<decltype(F)::value, decltype(DO)::value>), dim3(nranges, T), dim3(256),
+                                   0, s, dG, (const double*)h->dKuf, (const double*)h->dX, (const double*)h->dXus, yw, omega_of(h), mu,
+                                   (const Params*)h->dParams, b.PartUF, Mp, T, D, h->n, h->nblk, range_len);
+            });
+        };
+        if (multi) by_dout(h->dout, launch);
+        else launch(std::integral_constant<int, 1>{});
+    }
+    const double w = h->hParams->W[0];
+    hipLaunchKernelGGL(k_xu_grad_finish, dim3((unsigned)((h->M * D + 255) / 256)), dim3(256), 0, s, (const double*)b.PartUF, nranges,
+                       (const double*)b.PartUU, (const Params*)h->dParams, multi ? 1.0 : w, multi ? MeanW(h).trace : w, b.Grad,
+                       h->M, T, D);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, wait_stream(s));
+    HIPCHK(h, hipMemcpy(grad_xu, b.Grad, sizeof(double) * (size_t)h->M * D, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -3977,6 +3977,193 @@ __global__ void __launch_bounds__(256) k_theta_grad_finish(const double* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// Analytic gradient of the same objective in the inducing inputs (sgp_theta_objective_xu).  With G, H and Z' as above and
+// A_mn = omega_n (G k_n)_m - sum_d mu^(d)_m (omega_n W y_n)_d (k_theta_grad_uf's c / 2), dk(a, b)/db_d = sigma2 phi (a_d - b_d) / ell_d^2:
+//   df/dz_md = [ sum_n A_mn sigma2 phi(z_m, x_n) (x_nd - z_md) + tr(W) sum_m' H_mm' sigma2 phi(z_m, z_m') (z_m'd - z_md) ] / ell_d^2
+// (UniSGP: both halves times w instead; H carries no 1/2 here: z_m moves row and column m of K_uu; the diagonal sigma2 + jitter
+// does not depend on Z).  The per-entry quantities are those of k_theta_grad_uf / k_theta_grad_uu, summed per inducing row and
+// dimension instead of per dimension, always with the DIRECT difference of the scaled coordinates (the expanded form
+// Z' X - rowsum(Z') z cancels where |x - z| << |x|).
+// k_xu_grad_uf: grid (ranges, T).  A workgroup owns tile row I and one range of point blocks (host: xu_ranges, a function of N and M
+//   alone), walks it in order -- per block the 64 x 64 tile of G K_uf on the matrix cores, then the epilogue -- and keeps the running
+//   [64 rows][D] sums in LDS (16 KB per column half at D = 32; in registers they would be 8 rows x D per lane).  Per (row, d): the
+//   lane's two columns, the 16 lanes of a row set by __shfl_xor 1, 2, 4, 8, the blocks of the range in order, and at the end the
+//   two column halves (waves wc = 0, 1); one partial [D][64] per (range, I).  No atomics.
+// k_xu_grad_uu: grid T x T, k_theta_grad_uu's tiling; per (row, d) the thread's 16 columns in order, then the four column
+//   quarters; one partial [D][64] per (J, I).
+// k_xu_grad_finish: per (m, d) the ranges in order, then the J tiles in order, the factors and 1 / ell_d; out is M x D row-major.
+// ------------------------------------------------------------------------------------------------
+template <int FAM, int DO = 1>
+__global__ void __launch_bounds__(256) k_xu_grad_uf(const double* __restrict__ G, const double* __restrict__ Kuf,
+                                                    const double* __restrict__ X, const double* __restrict__ Xus,
+                                                    const double* __restrict__ Yw, const double* __restrict__ omega,
+                                                    const double* __restrict__ mu, const Params* __restrict__ P,
+                                                    double* __restrict__ partial, int Mp, int T, int D, int64_t N,
+                                                    int nblk, int range_len) {
+    __shared__ __attribute__((aligned(16))) double lds[2 * TB * PS];
+    __shared__ double us[MAXD * TB];
+    __shared__ double sums[2][MAXD * TB];
+    __shared__ double ys[TB], om[TB], mus[TB];
+    __shared__ double cws[DO > 1 ? DO * TB : 1], mum[DO > 1 ? DO * TB : 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int I = blockIdx.y;
+    const int b0 = blockIdx.x * range_len, b1 = min(nblk, b0 + range_len);
+    double* As = lds;
+    double* Bs = lds + TB * PS;
+    double* xs = lds;                                              // (over the A panel, between a block's product and the next one's)
+    for (int t = tid; t < D * TB; t += 256) {
+        us[t] = Xus[(size_t)(t / TB) * Mp + I * TB + t % TB];
+        sums[0][t] = 0.0;
+        sums[1][t] = 0.0;
+    }
+    if (tid < TB) {
+        mus[tid] = mu[I * TB + tid];
+        if constexpr (DO > 1) {
+#pragma unroll
+            for (int d = 0; d < DO; ++d) mum[d * TB + tid] = mu[(size_t)d * Mp + I * TB + tid];
+        }
+    }
+    const double s2 = P->sigma2;
+    for (int b = b0; b < b1; ++b) {
+        const int64_t n0 = (int64_t)b * TB;
+        Acc4 acc;
+        acc_zero(acc);
+        for (int k = 0; k < T; ++k) {
+            __syncthreads();
+            load_panel_n(As, G, Mp, I * TB, k * TB, TB, tid);          // As[kk][i] = G[I*64 + i, k*64 + kk]  (G symmetric)
+            for (int t = tid; t < TB * 16; t += 256) {                 // Bs[j][kk] = Kuf[k*64 + kk, n0 + j]  (as k_theta_grad_uf)
+                int j = t >> 4, g = t & 15;
+                int64_t n = n0 + j;
+                double2 v0 = make_double2(0.0, 0.0), v1 = v0;
+                if (n < N) {
+                    const double* src = Kuf + (size_t)n * Mp + k * TB + g * 4;
+                    v0 = *reinterpret_cast<const double2*>(src);
+                    v1 = *reinterpret_cast<const double2*>(src + 2);
+                }
+                double* dst = Bs + j * KMS + g * 4;
+                *reinterpret_cast<double2*>(dst) = v0;
+                *reinterpret_cast<double2*>(dst + 2) = v1;
+            }
+            __syncthreads();
+            tile_mma_bk(acc, As, Bs, TB, lane, wr, wc);
+        }
+        __syncthreads();
+        for (int t = tid; t < D * TB; t += 256) {
+            int p = t / D, d = t % D;
+            int64_t n = n0 + p;
+            xs[d * TB + p] = (n < N) ? X[(size_t)n * D + d] * P->inv_ell[d] : 0.0;
+        }
+        if (tid < TB) {
+            int64_t n = n0 + tid;
+            ys[tid] = (n < N) ? Yw[n] : 0.0;
+            om[tid] = (n < N) ? (omega ? omega[n] : 1.0) : 0.0;
+            if constexpr (DO > 1) {
+#pragma unroll
+                for (int d = 0; d < DO; ++d) cws[d * TB + tid] = (n < N) ? Yw[(size_t)d * N + n] : 0.0;
+            }
+        }
+        __syncthreads();
+        double z[2][2][4];                                         // A_mn sigma2 phi_mn: exactly zero at padded rows and past N
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int tj = 0; tj < 2; ++tj) {
+                const int col = acc_col(lane, wc, tj);
+                const int64_t n = n0 + col;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = acc_row(lane, wr, ti, r);
+                    const double kv = (n < N) ? Kuf[(size_t)n * Mp + I * TB + row] : 0.0;
+                    const double c = om[col] * acc.t[ti][tj][r] - grad_lin<DO>(ys, mus, cws, mum, col, row);
+                    if constexpr (FAM == 0) {
+                        z[ti][tj][r] = c * kv;
+                    } else {
+                        double s = 0.0;
+                        for (int d = 0; d < D; ++d) { const double t = xs[d * TB + col] - us[d * TB + row]; s = fma(t, t, s); }
+                        double kap, phi;
+                        fam_kappa_phi<FAM>(s, kap, phi);
+                        z[ti][tj][r] = kv != 0.0 ? c * (s2 * phi) : 0.0;    // (the guard of k_theta_grad_uf)
+                    }
+                }
+            }
+        for (int d = 0; d < D; ++d) {
+            const double x0 = xs[d * TB + acc_col(lane, wc, 0)], x1 = xs[d * TB + acc_col(lane, wc, 1)];
+#pragma unroll
+            for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = acc_row(lane, wr, ti, r);
+                    const double u = us[d * TB + row];
+                    double e = fma(z[ti][1][r], x1 - u, z[ti][0][r] * (x0 - u));
+                    for (int o = 1; o < 16; o <<= 1) e += __shfl_xor(e, o);
+                    if ((lane & 15) == 0) sums[wc][d * TB + row] += e;     // (this wave alone owns rows wr*32 .. +31 of half wc)
+                }
+        }
+    }
+    __syncthreads();
+    double* out = partial + ((size_t)blockIdx.x * T + I) * D * TB;
+    for (int t = tid; t < D * TB; t += 256) out[t] = sums[0][t] + sums[1][t];
+}
+
+template <int FAM>
+__global__ void __launch_bounds__(256) k_xu_grad_uu(const double* __restrict__ H, const double* __restrict__ Xus,
+                                                    const Params* __restrict__ P, double* __restrict__ partial,
+                                                    int M, int Mp, int D) {
+    __shared__ double ui[MAXD * TB];
+    __shared__ double uj[MAXD * TB];
+    __shared__ double red[4][TB];
+    const int tid = threadIdx.x;
+    const int I = blockIdx.x * TB, J = blockIdx.y * TB;
+    for (int t = tid; t < D * TB; t += 256) {
+        const int d = t / TB, r = t % TB;
+        ui[t] = Xus[(size_t)d * Mp + I + r];
+        uj[t] = Xus[(size_t)d * Mp + J + r];
+    }
+    __syncthreads();
+    const int r = tid & 63, q = tid >> 6, c0 = q * 16;
+    const double s2 = P->sigma2;
+    double hp[16];                                                 // H sigma2 phi, zero outside M x M
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        double d2 = 0.0;
+        for (int d = 0; d < D; ++d) {
+            const double t = ui[d * TB + r] - uj[d * TB + c0 + e];
+            d2 = fma(t, t, d2);
+        }
+        const bool in = (I + r < M) && (J + c0 + e < M);
+        const double h = H[(size_t)(J + c0 + e) * Mp + I + r];
+        double kap, phi;
+        fam_kappa_phi<FAM>(d2, kap, phi);
+        hp[e] = in ? h * (s2 * phi) : 0.0;
+    }
+    double* out = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * D * TB;
+    for (int d = 0; d < D; ++d) {
+        const double a = ui[d * TB + r];
+        double v = 0.0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v = fma(hp[e], uj[d * TB + c0 + e] - a, v);
+        red[q][r] = v;
+        __syncthreads();
+        if (q == 0) out[d * TB + r] = (red[0][r] + red[1][r]) + (red[2][r] + red[3][r]);
+        __syncthreads();
+    }
+}
+
+// scale_uf, scale_uu: w and w (UniSGP), 1 and tr(W) (MultiSGP: G carries W already)
+__global__ void __launch_bounds__(256) k_xu_grad_finish(const double* __restrict__ part_uf, int nranges,
+                                                        const double* __restrict__ part_uu, const Params* __restrict__ P,
+                                                        double scale_uf, double scale_uu, double* __restrict__ out,
+                                                        int M, int T, int D) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= M * D) return;
+    const int m = e / D, d = e % D, I = m / TB, r = m % TB;
+    double a = 0.0, b = 0.0;
+    for (int g = 0; g < nranges; ++g) a += part_uf[(((size_t)g * T + I) * D + d) * TB + r];
+    for (int J = 0; J < T; ++J) b += part_uu[(((size_t)J * T + I) * D + d) * TB + r];
+    out[e] = fma(scale_uf, a, scale_uu * b) * P->inv_ell[d];
+}
+
+// ------------------------------------------------------------------------------------------------
 // Device-paced minibatch training (sgp_train_* in sgp_api.hip): the host only enqueues; the data window's scalars, the
 // softplus map theta -> kernel parameters and the optimiser step are tiny kernels between the sweep's own.
 // ------------------------------------------------------------------------------------------------

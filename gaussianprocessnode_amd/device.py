@@ -406,6 +406,21 @@ class SGPDevice:
         self._check(self._lib.sgp_theta_objective(self._h, C.cast(C.byref(v), C.POINTER(C.c_double)), ptr(g)), "sgp_theta_objective")
         return (v.value, g) if want_grad else v.value
 
+    def theta_objective_xu(self, want_grad: bool = False):
+        """`theta_objective` and, behind it, the analytic gradient of the same objective in the inducing inputs at the resident
+        `set_inducing` and the current kernel (sgp_theta_objective_xu): (value, grad_xu) or, with want_grad, (value, grad,
+        grad_xu).  value and grad are bitwise `theta_objective`'s; grad_xu is (M, D), laid out as `set_inducing` takes Xu.  q(v)
+        is held: moving z_m reinterprets v_m as the function value at the new location."""
+        v = C.c_double()
+        have = getattr(self, "_n_ell", None)
+        if have is None:
+            raise ValueError("theta_objective_xu: call set_kernel first")
+        g = np.empty(1 + have) if want_grad else None
+        gxu = np.empty((self.M, self.D))
+        self._check(self._lib.sgp_theta_objective_xu(self._h, C.cast(C.byref(v), C.POINTER(C.c_double)), ptr(g), ptr(gxu)),
+                    "sgp_theta_objective_xu")
+        return (v.value, g, gxu) if want_grad else (v.value, gxu)
+
     # -- device-paced minibatch training (sgp_train_*) -----------------------------------------------------------------
     def train_begin(self, X, y, theta_raw, *, jitter: float = 0.0, eta: float = 1e-3, beta=(0.9, 0.999), eps: float = 1e-8,
                     likelihood=None, gamma=(0.01, 0.01)):

@@ -341,6 +341,51 @@ def optimize_theta(theta, engine, *, steps: int = 100, optimizer=None):
     return _descend(theta, engine, int(steps), opt)
 
 
+def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=None, learn_theta: bool = True, jitter: float = 0.0):
+    """`steps` host-paced AdaMax steps on the objective of `theta_objective` in the inducing inputs -- on [theta | vec Xu] together,
+    or on Xu alone with learn_theta=False -- over an `engine` (SGPDevice) that has data, noise and a kernel family, with q(v) held
+    for the whole call.  theta is raw (pre-softplus, sigma2 first, 1 or D lengthscales); Xu is (M, D); q_v is (mu_v, Uv) as
+    `set_posterior` takes them, or a distribution with `mean_cov()` (Uv = chol(Sigma_v + mu mu').U is then formed here).
+
+    Per step: set_kernel(softplus(theta), jitter), set_inducing(Xu), one `theta_objective_xu` (value, d/d(sigma2, ell), d/dXu),
+    the chain rule through softplus for theta, one optimiser update of the joint vector.  `set_inducing` withdraws the handle's
+    finished-sweep mark, and with it the q(v) the objective would use (sgp_theta_objective then refuses), so q_v is installed
+    again with `set_posterior` after every `set_inducing`.  Returns (theta, Xu, values): new arrays, values[k] the objective at
+    step k's parameters; the engine is left at the LAST EVALUATED parameters, one update behind the returned ones.
+
+    With q(v) held, moving z_m reinterprets v_m as the function value at the new location: the objective is a function of Xu only
+    through that reading, and q(v) is no longer the posterior of any sweep once Xu has moved.  The intended use is alternation --
+    a few steps here, then sweeps at the new Xu to refit q(v).  The reference never moves Xu; there is no counterpart of this
+    loop in it."""
+    theta = np.array(theta, dtype=np.float64).reshape(-1)
+    Xu = np.array(Xu, dtype=np.float64)
+    if Xu.ndim != 2:
+        raise ValueError(f"optimize_inducing: Xu must be (M, D), got shape {Xu.shape}")
+    M, D = Xu.shape
+    if theta.size - 1 not in (1, D):
+        raise ValueError(f"optimize_inducing: theta must be (sigma2, 1 or {D} lengthscales), got {theta.size} entries")
+    if hasattr(q_v, "mean_cov"):
+        mu_v, Sigma_v = q_v.mean_cov()
+        mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
+        Uv = np.linalg.cholesky(np.asarray(Sigma_v, dtype=np.float64) + np.outer(mu_v, mu_v)).T
+    else:
+        mu_v, Uv = q_v
+    opt = optimizer if optimizer is not None else AdaMax()
+    nt = theta.size if learn_theta else 0
+    x = np.concatenate([theta[:nt], Xu.ravel()])
+    values = np.empty(max(int(steps), 0))
+    for k in range(int(steps)):
+        th = x[:nt] if learn_theta else theta
+        p = softplus(th)
+        engine.set_kernel(float(p[0]), p[1:], jitter)
+        engine.set_inducing(x[nt:].reshape(M, D))
+        engine.set_posterior(mu_v, Uv)
+        values[k], g, gxu = engine.theta_objective_xu(want_grad=True)
+        grad = np.concatenate([(np.asarray(g) * sigmoid(th))[:nt], np.asarray(gxu, dtype=np.float64).ravel()])
+        opt.update(x, grad)
+    return (x[:nt].copy() if learn_theta else theta), x[nt:].reshape(M, D).copy(), values
+
+
 # ------------------------------------------------------------------------------------------------
 # the GP state-space model: `pendulum_GP` of experiments/Pendulum_Wishart_2d.ipynb (cells 12-16)
 # ------------------------------------------------------------------------------------------------

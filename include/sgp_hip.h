@@ -410,6 +410,20 @@ int sgp_wait(sgp_handle* h);
  * sgp_set_posterior, and while a sgp_train_* run is open.  Sums are in a fixed order: repeated calls agree bitwise. */
 int sgp_theta_objective(sgp_handle* h, double* value, double* grad);
 
+/* sgp_theta_objective_xu: sgp_theta_objective and, behind it, the analytic gradient of the same f in the inducing inputs, at the
+ * resident Xu (sgp_set_inducing) and the current kernel.  With G = S - tr(W) Kinv, H = Kinv Psi2 Kinv (no 1/2: z_m moves row and
+ * column m of K_uu), A_mp = omega_p (G k_p)_m - sum_d mu^(d)_m (omega_p W y_p)_d and dk(a, b)/db_d = sigma2 phi(a, b) (a_d - b_d) /
+ * ell_d^2 (phi per family as for the ell gradient; Matern-1/2: 0 at coincident points):
+ *   df/dz_md = [ sum_p A_mp sigma2 phi(z_m, x_p) (x_pd - z_md) + tr(W) sum_m' H_mm' sigma2 phi(z_m, z_m') (z_m'd - z_md) ] / ell_d^2
+ * (d_out = 1: S = w R_v, tr(W) = w, the linear term w y_p mu_m).  value and grad (1 + n_ell, may be NULL) are bitwise what
+ * sgp_theta_objective returns from the same handle state -- fresh or re-evaluated by the same rules, a later sgp_set_posterior wins
+ * -- and the handle is left exactly as sgp_theta_objective leaves it; grad_xu is M x D, laid out as sgp_set_inducing's Xu.  All
+ * sums run in a fixed order that depends on (N, M, D) alone, without atomics: identical calls agree bitwise.  q(v) is held: moving
+ * z_m reinterprets v_m as the function value at the new location.  The exact-Psi objective has no such call.
+ * SGP_ERR_ARG: everything sgp_theta_objective refuses; a NULL grad_xu; an all-reduce hook installed (any d_out). */
+int sgp_theta_objective_xu(sgp_handle* h, double* value, double* grad /* 1 + n_ell, may be NULL */,
+                           double* grad_xu /* M x D */);
+
 /* ---- device-paced minibatch training: `PerformInference` of experiments/regression_kin40k.ipynb:196-230 ---------------
  * The reference's loop is, per minibatch, infer(iterations = 1) (:205-211), q(v) carried over as the next prior (:212),
  * grad_llh_new! at that q(v) (:214-221) and Flux.Optimise.update!(AdaMax, theta, grad) (:222) with

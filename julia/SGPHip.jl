@@ -34,7 +34,7 @@ import ReactiveMP: @rule, @average_energy, @call_rule, GenericProd, PointMass, M
                    mean_var, AverageEnergy, ContinuousUnivariateLogPdf, ContinuousMultivariateLogPdf, UnspecifiedDomain
 import ..UniSGP, ..UniSGPMeta, ..MultiSGP, ..MultiSGPMeta, ..WishartFast, ..approximate_kernel_expectation!
 
-export HipSGPMeta, HipMultiSGPMeta, predict, predictive, theta_objective, carry_posterior!, multisgp_sweep!
+export HipSGPMeta, HipMultiSGPMeta, predict, predictive, theta_objective, theta_objective_xu, carry_posterior!, multisgp_sweep!
 
 const LIB = get(ENV, "SGP_HIP_LIB", "libsgp_hip.so")
 
@@ -514,6 +514,14 @@ function theta_objective(meta::HipSGPMeta, nparams::Int)
     f = Ref{Float64}(0.0); g = zeros(nparams)
     check(ccall((:sgp_theta_objective, LIB), Cint, (Ptr{Cvoid}, Ref{Float64}, Ptr{Float64}), meta.handle.ptr, f, g), meta.handle.ptr)
     return f[], g
+end
+# The same value and gradient and, behind them, dF/dXu at the resident inducing inputs (sgp_theta_objective_xu): D × M, the
+# layout of the handle's Xu.  q(v) is held: moving z_m reinterprets v_m as the function value at the new location.
+function theta_objective_xu(meta::HipSGPMeta, nparams::Int)
+    h = meta.handle
+    f = Ref{Float64}(0.0); g = zeros(nparams); gxu = zeros(h.d, h.m)
+    check(ccall((:sgp_theta_objective_xu, LIB), Cint, (Ptr{Cvoid}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}), h.ptr, f, g, gxu), h.ptr)
+    return f[], g, gxu
 end
 
 # ---- minibatch loops (experiments/regression_kin40k.ipynb:205-212): prior <- posterior without leaving the device --

@@ -1,8 +1,8 @@
 // Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over grids of shapes, the
-// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in and layout_psi_predict hand out are
+// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict and layout_xu_grad hand out are
 // pairwise disjoint at the sizes their consumers need (stated here independently of the layout functions), every piece starts a
 // multiple of Carver::ALIGN doubles from the base, pass 2 hands out the total pass 1 summed and the last piece ends there.  The
-// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta, layout_psi_in and layout_psi_predict get an allocation of
+// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict and layout_xu_grad get an allocation of
 // exactly their total per shape and every piece is written end to end, so that the sanitizer sees a write past it.  No GPU:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o tools/point_scratch_check tools/point_scratch_check.cpp
 //   (or any C++17 compiler with -fsanitize=address,undefined) && tools/point_scratch_check
@@ -309,6 +309,31 @@ long psi_predict_sweep() {
                         }
     return shapes;
 }
+// sgp_theta_objective_xu over its grid, each shape in an allocation of its own: the range count of xu_ranges (none without points)
+long xu_grad_sweep() {
+    long shapes = 0;
+    for (int M : {1, 17, 65, 130, 600})
+        for (int D : {1, 3, 8, 32})
+            for (int64_t n : {(int64_t)0, (int64_t)1, (int64_t)65, (int64_t)8193, (int64_t)100000}) {
+                const int Mp = (M + TB - 1) / TB * TB, T = Mp / TB;
+                const int64_t nblk = (n + TB - 1) / TB, want = std::max<int64_t>(1, std::min<int64_t>(nblk, std::max(1, 256 / T)));
+                const int64_t len = std::max<int64_t>(1, (nblk + want - 1) / want);
+                const size_t ranges = (size_t)((nblk + len - 1) / len);
+                const PointShape s{Mp, 0, T, D, 1, POTRF_SCRATCH, 64, n, n};
+                check("xu_grad", s, 0, nullptr, 0, true, [&](Carver& c) {
+                    XuGradScratch b;
+                    layout_xu_grad(c, s, M, ranges, &b);
+                    const std::vector<Piece> all = {{"PartUF", b.PartUF, ranges * Mp * D * d}, {"PartUU", b.PartUU, (size_t)T * Mp * D * d},
+                                                    {"Grad", b.Grad, (size_t)M * D * d}};
+                    std::vector<Piece> p;
+                    for (const Piece& q : all)
+                        if (q.bytes) p.push_back(q);                  // (a piece that is not wanted has no extent)
+                    return p;
+                });
+                ++shapes;
+            }
+    return shapes;
+}
 }  // namespace
 
 int main() {
@@ -324,8 +349,9 @@ int main() {
     const long psi_theta = psi_theta_sweep();
     const long psi_in = psi_in_sweep();
     const long psi_predict = psi_predict_sweep();
+    const long xu_grad = xu_grad_sweep();
     std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes, %ld psi shapes, %ld psi-theta shapes, "
-                "%ld psi-in shapes, %ld psi-predict shapes: %ld failure(s)\n", panel, largest, mean_only, psi, psi_theta, psi_in,
-                psi_predict, failures);
+                "%ld psi-in shapes, %ld psi-predict shapes, %ld xu-grad shapes: %ld failure(s)\n", panel, largest, mean_only, psi,
+                psi_theta, psi_in, psi_predict, xu_grad, failures);
     return failures ? 1 : 0;
 }

@@ -84,6 +84,7 @@ struct StatGroup {
     int ntiles;            // their lower tiles
     SyrkGeom geom;         // split of the point axis (one resident round of workgroups on the group's CUs)
     int form_step;
+    bool early;            // added by the trailing workgroups of step form_step - 1 (LAM_FORM_EARLY; model_overlap_end decides)
     bool masked;           // runs on statM
     size_t slab_off;       // doubles into dSlabs
 };
@@ -211,6 +212,7 @@ struct sgp_handle {
     int64_t env_predict_chunk = 0; // SGP_PREDICT_CHUNK: test points per chunk of sgp_predict_var (default: sized to a scratch budget)
     bool posterior_set = false;    // sgp_set_posterior installed mu_v and Uv only: dSigma is not that q(v)'s covariance until the next sweep
     bool syrk_wide = false;        // the resident problem's SYRK launches are k_syrk_direct (set_point_count)
+    int env_early_form = -1;       // SGP_EARLY_FORM: 1 / 0 every masked group is / none is added one step early; default: the planner's model per group
     std::vector<int> env_overlap_cols;   // SGP_OVERLAP_COLS: group boundaries (tile columns of P Lambda P), e.g. "3" or "2,4"
     int nblk = 0, ntiles = 0, num_cus = 256;
     SyrkGeom geom{};               // the plain sweep's single SYRK launch over all tile rows (set_point_count)
@@ -449,7 +451,8 @@ static void launch_syrk(const SyrkGeom& g, hipStream_t s, const double* Kuf, con
 // reading it from A.  Sacc (may be nullptr; needs Winv): collects Sigma = W^T W row by row during the steps
 // (sigma_row_tile); pass the same buffer to launch_ata, which then only adds the last block row.
 // step_wait (may be nullptr): step_wait[j] != nullptr makes the stream wait for that event in front of step j (data-sharded
-// overlapped sweeps: the group of tile columns that step j forms has come back from its all-reduce, see enqueue_stats_overlapped).
+// overlapped sweeps: the group of tile columns that step j's trailing workgroups add has come back from its all-reduce, see
+// enqueue_stats_overlapped).
 // (a sequence object: launch_potrf runs it to the end; the interleaved enqueue of a sweep's two chains -- enqueue_chains_interleaved --
 // alternates between two of them)
 struct PotrfSeq {
@@ -627,11 +630,12 @@ extern "C" int sgp_create(const sgp_config* cfg, sgp_handle** out) {
     ALLOC(h->dXusK, Mp * h->D);
     {
         // Test hooks, read once (not per sweep).  Each forces a path the product already takes in some configuration, so that the
-        // tests can compare it with the others: SGP_OVERLAP / SGP_OVERLAP_COLS (the overlapped sweep and its groups), SGP_SPIN_LIMIT
+        // tests can compare it with the others: SGP_OVERLAP / SGP_OVERLAP_COLS / SGP_EARLY_FORM (the overlapped sweep, its groups, where they are added), SGP_SPIN_LIMIT
         // (a short bounded wait), SGP_INTERLEAVE (the chain-after-chain host order), SGP_NO_ZERO_COPY (results copied back),
         // SGP_PREDICT_CHUNK (sgp_predict_var in small chunks).
         if (const char* lim = getenv("SGP_SPIN_LIMIT")) h->spin_limit = std::max(1, atoi(lim));
         if (const char* ov = getenv("SGP_OVERLAP")) h->env_overlap = atoi(ov);
+        if (const char* ef = getenv("SGP_EARLY_FORM")) h->env_early_form = atoi(ef) != 0;
         if (const char* zc = getenv("SGP_NO_ZERO_COPY")) h->env_no_zero_copy = atoi(zc) != 0;
         if (const char* ni = getenv("SGP_INTERLEAVE")) h->env_interleave = atoi(ni) != 0;
         if (const char* pc = getenv("SGP_PREDICT_CHUNK")) h->env_predict_chunk = std::max(1LL, atoll(pc));
@@ -778,7 +782,8 @@ extern "C" int sgp_set_inducing(sgp_handle* h, const double* Xu) {
 //     (N = 10 000, M = 512; sweeps/s on one box): plain order 3750; cuts {3} 3896, {2} 3832-3950, {2,4} 3925, {1,3} 3656,
 //     {2,3,5} 3790, {1,2,4} 3528 -- the model ranks them the same way.  When no plan beats the plain order by 5 us the plain
 //     order stays (huge N: the masked groups' lost CUs cost more than the chain's early start saves).
-static double model_overlap_end(const sgp_handle* h, int64_t n, bool wide, const int* cuts, int ncuts, double* classic_end) {
+static double model_overlap_end(const sgp_handle* h, int64_t n, bool wide, const int* cuts, int ncuts, double* classic_end,
+                                bool* early_out = nullptr) {
     const int T = h->T;
     // one SYRK launch = one resident round: its duration follows the points per chunk (k_syrk_stream: 0.18 us per point at four
     // workgroups per CU, + ~5 us of launch ramp and tail; k_syrk_direct: 0.029 us per point -- eight waves share the chunk, two to a
@@ -796,7 +801,8 @@ static double model_overlap_end(const sgp_handle* h, int64_t n, bool wide, const
     // {2} 216.3, {4} 224.9, {2,5} 213.2, {3,6} 221.5, {2,4} 215.5 -- profiles/r04_ab_log.txt [17]; residuals of this model
     // +-1.3 us): in the kernel's own duration (7.5 + 0.029 us per point; syrk_us above is what HIP events see) group 0's assembly
     // and its two boundaries are 11.5 us, the masked stream's first SYRK starts 8 us behind group 0's, a masked group is usable
-    // 5 us behind its SYRK, and a step that forms a group costs 5 us more than one that does not.
+    // 5 us behind its SYRK.  (Both fits priced a forming step, 2.5 / 5 us on the chain: the groups have since moved off the chain's
+    // critical workgroups, see below.)
     const bool dk = wide;
     const double asm0 = dk ? 11.5 : 8.0, asmm = dk ? 5.0 : 11.0, step = 17.0, margin = dk ? 0.0 : 4.0, forming = dk ? 5.0 : 2.5;
     const double mstart = dk ? 8.0 : 2.0, launch = dk ? 5.5 : 0.0;   // (launch: what syrk_us counts beyond the kernel's own duration)
@@ -810,12 +816,30 @@ static double model_overlap_end(const sgp_handle* h, int64_t n, bool wide, const
         t += syrk_us(T - c1, c1 - c0, h->stat_cus_masked) - launch + asmm;
         for (int c = c0; c < c1; ++c) ready[c] = t;
     }
+    // A masked group is formed by its form step f -- the panel and diagonal workgroups poll and load in front of their pivots,
+    // `forming` us on the chain -- or EARLY, by the trailing workgroups of step f - 1 (k_potrf_step, late_form): they have their own
+    // update done `lead` us into the launch and need `add` us for the group (in-kernel exits at T: 5.5 - 6 us without, 7.6 - 8.1 us
+    // with a group that is there; profiles/r05_early_formation.txt), so step f - 1 keeps its length and step f loses `forming`.
+    // Only a group that is there by then is taken early: one that is not holds step f - 1's launch open until it has arrived, is
+    // read past the L2 and added -- measured with every group early: T {2,5} step 1 20.6 instead of 16.6 us; C2 {1} (f = 1: step 0's
+    // trailing workgroups poll beside group 0's tail and group 1's SYRK) 130.1 against 125.8 us per sweep, C3 {4} 357.1 against 354.7.
+    const double lead = 6.0, add = 2.5;
+    bool early[LAM_MAX_COLS] = {false};
     double end = ready[0];
     for (int j = 0; j < T; ++j) {
+        double start = end;
         bool forms = false;
-        for (int g = 0; g < ncuts; ++g) forms = forms || cuts[g] == j;
-        end = std::max(end, ready[j] + (j >= cuts[0] ? margin : 0.0)) + step + (forms ? forming : 0.0);
+        for (int g = 0; g < ncuts && g < LAM_MAX_COLS; ++g)
+            if (cuts[g] == j && !early[g]) { start = std::max(start, ready[j] + margin); forms = true; }
+        end = start + step + (forms ? forming : 0.0);
+        for (int g = 0; g < ncuts && g < LAM_MAX_COLS; ++g)
+            if (cuts[g] == j + 1) {
+                early[g] = h->env_early_form >= 0 ? h->env_early_form != 0 : ready[j + 1] + margin <= start + lead;
+                if (early[g]) end = std::max(end, std::max(start + lead, ready[j + 1] + margin) + add);
+            }
     }
+    if (early_out)
+        for (int g = 0; g < ncuts && g < LAM_MAX_COLS; ++g) early_out[g] = early[g];
     return end;
 }
 
@@ -838,8 +862,8 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
     for (int c : h->env_overlap_cols) if (c > 0 && c < T && (cuts.empty() || c > cuts.back())) cuts.push_back(c);
     if (cuts.empty()) {
         double classic = 0.0, best = 1e300;
-        int cand[2];
-        // One or two cuts.  (Round 3 settled on ONE: with its 16 us steps the chain reached a third group's columns before that group
+        int cand[3];
+        // One to three cuts.  (Round 3 settled on ONE: with its 16 us steps the chain reached a third group's columns before that group
         // was there.  With k_syrk_direct a masked group's launch is a quarter shorter and {2,5} beats {3} at T, 213.2 against 216.3 us.)
         // Among plans the model cannot tell apart (< 0.3 us) the later second cut wins: the measured order at T.
         for (int a = 1; a < T; ++a) {
@@ -862,6 +886,18 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
                 if (m1 > 45.0 || m2 > 45.0) continue;
                 const double e2 = model_overlap_end(h, np, wide, cand, 2, &classic);
                 if (e2 < best - 0.3) { best = e2; cuts.assign(cand, cand + 2); }
+                // Four groups, under the same bound on the masked launches, from eight tile columns on: with the groups added off the
+                // chain's critical workgroups a further group costs the chain nothing, and smaller masked groups are there earlier --
+                // {2,4,6} beats {2,5} at T, 208.9 against 210.8 us per sweep (profiles/r05_early_formation.txt)
+                if (T < 8) continue;
+                for (int c = T - 1; c > b; --c) {
+                    cand[2] = c;
+                    const double n2 = 13.0 + 0.029 * syrk_geometry(T - c, c - b, h->stat_cus_masked, np, true).chunk;
+                    const double n3 = 13.0 + 0.029 * syrk_geometry(0, T - c, h->stat_cus_masked, np, true).chunk;
+                    if (n2 > 45.0 || n3 > 45.0) continue;
+                    const double e3 = model_overlap_end(h, np, wide, cand, 3, &classic);
+                    if (e3 < best - 0.3) { best = e3; cuts.assign(cand, cand + 3); }
+                }
             }
         }
         // (the plain order stays unless the model sees a gain: 5 us with the LDS-staged SYRK's constants; 1 us with k_syrk_direct's --
@@ -869,6 +905,8 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
         if (h->env_overlap != 1 && best > classic - (wide ? 1.0 : 5.0)) return;
     }
     if ((int)cuts.size() + 1 > LAM_MAX_GROUPS) return;
+    bool early[LAM_MAX_COLS] = {false};
+    (void)model_overlap_end(h, np, wide, cuts.data(), (int)cuts.size(), nullptr, early);
     size_t off = 0;
     int c0 = 0;
     for (size_t g = 0; g <= cuts.size(); ++g) {
@@ -879,6 +917,7 @@ static void plan_overlap(sgp_handle* h, int64_t n) {
         G.nrows = G.c1 - G.c0;
         G.masked = g > 0;
         G.form_step = G.c0;
+        G.early = g > 0 && early[g - 1];
         // (the 16-wave kernel for the masked groups as well: with the 256-thread kernel there the sweep was 1 % slower, profiles/r04_ab_log.txt [9])
         G.geom = syrk_geometry(G.row_lo, G.nrows, G.masked ? h->stat_cus_masked : h->num_cus, n, h->syrk_wide);
         G.ntiles = G.geom.ntiles;
@@ -1308,13 +1347,13 @@ static void enqueue_local(sgp_handle* h, hipStream_t s, bool pack) {
 // factorisation chains run on.  No events: statM's first kernel waits for the word the first block of group 0's k_assemble
 // sets (group 0's SYRK has drained), a k_join_set behind each masked group's k_assemble writes the sweep's number into the
 // group's word (the kernel boundary in front of it makes the statistics visible device-wide), and the chain step that forms the
-// group polls that word.
+// group -- or, early, the trailing workgroups of the step in front of it -- polls that word.
 static int exchange_stats(sgp_handle* h, hipStream_t s, int tile0, int ntile, bool with_tail);
 // Data-sharded (an all-reduce hook is installed; round 4): the same schedule with ONE reduce per group, on the group's own stream --
 // k_assemble writes the group's lower tiles into the exchange buffer, the hook sums that piece over the ranks (group 0's piece
 // also carries B and the scalars: the last tile rows of Psi2 sit next to the buffer's tail), k_unpack_stats expands it.  Group 0's
 // reduce is in front of the chain in plain stream order; a masked group's is published by an EVENT recorded behind its unpack, and
-// the sweep's stream waits for it in front of the chain step that forms the group (launch_potrf's step_wait) -- not by a device
+// the sweep's stream waits for it in front of the chain step that adds the group (launch_potrf's step_wait) -- not by a device
 // word: words are waited for with a bounded spin, and a collective that builds its rings or waits for a straggler rank may take
 // longer than that.  The chain therefore starts after (statistics of group 0 -> reduce of 0.6 MB) instead of (all statistics ->
 // reduce of 1.18 MB), and the second reduce runs beside it.  Every rank calls the hook in the same order (group 0, 1, ...).
@@ -1369,20 +1408,21 @@ static void enqueue_finish1(sgp_handle* h, hipStream_t s, const SweepPlan& p) {
     hipEvent_t step_wait[LAM_MAX_COLS] = {nullptr};
     bool any_wait = false;
     if (p.overlapped) {
-        // the statistics arrive group by group while the chain runs (enqueue_stats_overlapped): step G.form_step forms group G.
+        // the statistics arrive group by group while the chain runs (enqueue_stats_overlapped): step G.form_step forms group G, or
+        // (G.early) the trailing workgroups of the step in FRONT of it add it (k_potrf_step, late_form).
         // Group 0 was summed on this very stream: nothing to wait for.  (A step 0 resident from the start of the sweep and
         // waiting for its statistics itself was measured too: on T + 1 CUs it keeps group 0's SYRK from its full single round,
         // 54 instead of 35 us.)
-        // (data-sharded: the masked groups arrive through events the stream waits for in front of their forming step -- nothing
-        // for the kernel to poll, every column is "in stream order")
+        // (data-sharded: the masked groups arrive through events the stream waits for in front of the launch that reads them,
+        // step form_step or, early, form_step - 1 -- nothing for the kernel to poll, every column is "in stream order")
         form.col_words = h->dJoin + WORD_GROUP0;
         form.col_need = h->stat_epoch;
         for (int g = 0; g < h->ngroups; ++g) {
             for (int c = h->grp[g].c0; c < h->grp[g].c1; ++c) {
-                form.form_step[c] = (unsigned char)h->grp[g].form_step;
+                form.form_step[c] = (unsigned char)(h->grp[g].form_step | (h->grp[g].early ? LAM_FORM_EARLY : 0));
                 form.col_group[c] = (h->grp[g].masked && !p.pack && !p.resident) ? (unsigned char)g : (unsigned char)0xff;
             }
-            if (h->grp[g].masked && p.pack && !p.resident) { step_wait[h->grp[g].form_step] = h->evGroup[g]; any_wait = true; }
+            if (h->grp[g].masked && p.pack && !p.resident) { step_wait[h->grp[g].form_step - (h->grp[g].early ? 1 : 0)] = h->evGroup[g]; any_wait = true; }
         }
     }
     // mu = Sigma xi = P W'^T W' P xi as two triangular mat-vecs, both riding along with the factorisation: t = W' P xi block by

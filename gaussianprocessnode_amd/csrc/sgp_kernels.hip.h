@@ -1548,12 +1548,14 @@ __device__ __forceinline__ void tile_g2r(TileRegs& t, const double* __restrict__
 // HBM) sits in front of the chain.  stats == nullptr: the matrix is already in A.
 // Overlapped sweep (sgp_api.hip, sweep_overlapped): the statistics arrive in GROUPS of tile columns of P Lambda P (= tile rows of
 // Psi2, last rows first) while the factorisation is already running.  Tile column c is formed -- added into the matrix -- by the
-// workgroups of step form_step[c] <= c, which first wait (bounded) until col_words[col_group[c]] >= col_need (the sweep's number,
-// written by a k_join_set behind the group's k_assemble);
+// workgroups of step f = form_step[c] <= c or, with LAM_FORM_EARLY set in form_step[c] (f >= 1), by the trailing-update workgroups
+// of step f - 1 behind their own update, so that the column is complete when step f starts; either way they first wait (bounded)
+// until col_words[col_group[c]] >= col_need (the sweep's number, written by a k_join_set behind the group's k_assemble);
 // until then the tile in A holds only the (negative) rank-64 updates that steps 1 .. collected for it.  col_words == nullptr:
 // the statistics are complete before step 0, which forms every tile (form_step all zero).
 constexpr int LAM_MAX_GROUPS = 8;
 constexpr int LAM_MAX_COLS = 64;            // CU_MAXQ / TB
+constexpr int LAM_FORM_EARLY = 0x80;        // flag in form_step[c]: the column is added one step early (k_potrf_step, late_form)
 struct LamForm {
     const double* stats;
     const double* Lambda0;
@@ -1656,6 +1658,15 @@ __device__ __forceinline__ void tile_s2g(const double* S, double* __restrict__ A
     for (int u = 0; u < 8; ++u) {
         const int e = (threadIdx.x & 255) + 256 * u, c = e >> 5, r = (e & 31) * 2;
         *reinterpret_cast<double2*>(A + (size_t)(col0 + c) * ld + row0 + r) = v[u];
+    }
+}
+// A = S + t, t in tile_g2r's register layout (a trailing tile that takes its share of Lambda in on the way out, see k_potrf_step)
+__device__ __forceinline__ void tile_s2g_add(const double* S, const TileRegs& t, double* __restrict__ A, size_t ld, int row0, int col0) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int e = (threadIdx.x & 255) + 256 * u, c = e >> 5, r = (e & 31) * 2;
+        *reinterpret_cast<double2*>(A + (size_t)(col0 + c) * ld + row0 + r) =
+            make_double2(S[r * LT + c] + t.v[2 * u], S[(r + 1) * LT + c] + t.v[2 * u + 1]);
     }
 }
 // the same for the transposed tile: A(r, c) = S[c][r]
@@ -2145,9 +2156,18 @@ __global__ void __launch_bounds__(PSTEP_THREADS) k_potrf_step(double* __restrict
     if (xgroup && !(panel && (a != 0 || diag_inv))) return;
     // What this workgroup's tile column starts from (see LamForm): formed here (do_form), already in A (load_old), or neither yet
     const bool lam = form.stats != nullptr;
-    const int fstep = lam ? (int)form.form_step[j + b] : -1;
-    const bool do_form = lam && fstep == j;
-    const bool load_old = !lam || fstep < j || j >= 2;
+    const int fword = lam ? (int)form.form_step[j + b] : 0;
+    const int fstep = lam ? (fword & (LAM_FORM_EARLY - 1)) : -1;
+    const bool early = (fword & LAM_FORM_EARLY) != 0;                   // (never with fstep == 0)
+    // A tile column with form step f is formed by the workgroups of step f that own its tiles -- for column f itself the panel
+    // and diagonal workgroups, which every later step waits for: a poll and a dependent load in front of their 64 pivots.  EARLY
+    // (the planner's choice per group, LAM_FORM_EARLY): the column is complete WHEN step f starts: the trailing workgroups of
+    // step f - 1 add Lambda's tile behind their own rank-64 update (late_form) -- they leave after 5 - 8 us of a 15 us launch.
+    // The sums are the same, term by term: (what steps < f collected) + Lambda's tile, then step f's own update.  f = 1: step 0
+    // has no update to apply and nothing to add to, it stores Lambda's tile as group 0's columns do (do_form).
+    const bool do_form = lam && (early ? (j == 0 && fstep == 1) : fstep == j);
+    const bool late_form = lam && early && j >= 1 && fstep == j + 1;    // (b >= 1: always a trailing tile)
+    const bool load_old = !lam || j >= 2 || (early ? (j == 1 && fstep == 1) : fstep < j);
     const bool xi_duty = lam && j == 0 && blockIdx.x == gridDim.x - 1;     // (step 0 has no extra workgroups)
     if (!lam && j == 0 && !panel) return;       // step 0 of a matrix that is already in A: no update to apply to the trailing tiles
     bool bypass = false;
@@ -2365,6 +2385,16 @@ __global__ void __launch_bounds__(PSTEP_THREADS) k_potrf_step(double* __restrict
     __syncthreads();
     tile_sub_acc(X, accX, lane, wr, wc);
     __syncthreads();
+    if (late_form) {
+        // the next step's group: polled HERE, behind the update, by a workgroup nobody waits for.  A late group holds this
+        // workgroup (bounded, SYNC_LATE_COLUMN) and is then read past the L2; the tile reaches memory once, complete -- nobody else
+        // reads this column during the launch (the ride-along roles read finished columns of L, W and t only).
+        bool late = false;
+        if (form.col_words && form.col_group[j + b] != 0xff) late = wait_stat_group(form, form.col_group[j + b]);
+        tile_form_r(rX, form, ld, i0, k0, late);
+        tile_s2g_add(X, rX, A, ld, i0, k0);
+        return;
+    }
     tile_s2g(X, A, ld, i0, k0);
 }
 

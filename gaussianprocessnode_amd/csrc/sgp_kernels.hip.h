@@ -1168,7 +1168,7 @@ __global__ void __launch_bounds__(256) k_form_lambda(const double* __restrict__ 
 //   (A_ik -= L_i,j-1 L_k,j-1^T on the matrix cores).  Blocks of the first trailing column (b = 0) then
 //   continue with step j without leaving the kernel: each of them ALSO factors the diagonal tile A_jj itself in
 //   LDS (redundant compute instead of an inter-block hand-off; its rank-64 update arrives as a tile formed by
-//   the previous launch, see syrk_slice) and solves X L_jj^T = A_ij for its own tile; the block on the
+//   the previous launch, see syrk_slice_load) and solves X L_jj^T = A_ij for its own tile; the block on the
 //   diagonal writes L_jj (and, with Winv, L_jj^-1).
 // Thread layout of the sequential parts: the triangular solves give 4 adjacent lanes (q = tid & 3) one row
 // r = tid >> 2, lane q keeping the row's entries c = q (mod 4) in registers (no reductions; the quad exchanges
@@ -1287,11 +1287,15 @@ __device__ __forceinline__ void potf2_tile(double* S, double* Dp, double* rinv, 
 #pragma unroll 1
     for (int cb = 0; cb < 4; ++cb) {
         if (cb > 0 && wave > cb) {                          // (the pivot wave's own block is already up to date, see (3))
+            double so[4];                                   // (read in front of the products: see trsm_update)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) so[r] = S[(r0 + lk + 4 * r) * LT + 16 * cb + li];
+            __builtin_amdgcn_sched_barrier(0);
             d4 acc[4];
             mma_left_n(acc, S + (r0 + li) * LT + lk /* A[i][k] = L[r0 + i][k] */, S + (16 * cb + li) * LT + lk /* B[k][j] = L[16 cb + j][k] */, cb);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                S[(r0 + lk + 4 * r) * LT + 16 * cb + li] -= (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+                S[(r0 + lk + 4 * r) * LT + 16 * cb + li] = so[r] - ((acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]));
         }
         if (wave == cb) {
             // Pivot-phase coordinates: lane = 16 pq + pr holds row pr, columns 4 i + pq -- of the FULL symmetric block, so
@@ -1407,11 +1411,17 @@ __device__ __forceinline__ void trsm_update(double* X, const double* S, int rb, 
     const int lane = threadIdx.x & 63;
     const int r0 = 16 * rb;
     const int li = lane & 15, lk = lane >> 4;
+    // the block's own entries are read with the operands, in front of the products: left behind them they were four
+    // read - wait - subtract - write rounds, one LDS latency each, at the end of every update
+    double xo[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) xo[r] = X[(r0 + lk + 4 * r) * LT + 16 * cb + li];
+    __builtin_amdgcn_sched_barrier(0);
     d4 acc[4];
     mma_left_n(acc, X + (r0 + li) * LT + lk, S + (16 * cb + li) * LT + lk, cb);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-        X[(r0 + lk + 4 * r) * LT + 16 * cb + li] -= (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+        X[(r0 + lk + 4 * r) * LT + 16 * cb + li] = xo[r] - ((acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]));
 }
 __device__ __forceinline__ void trsm_solve(double* X, const double* Dp, const double* rinv, int rb, int cb) {
     const int lane = threadIdx.x & 63;
@@ -1436,15 +1446,19 @@ __device__ __forceinline__ void trsm_interval(double* X, const double* S, const 
 // K-slice c (columns 16 c .. 16 c + 15 of the solved tile X) of the lower 16 x 16 tile (R, C) of X X^T, formed transposed
 // (A operand = the column tile) so that the stores run along Dn's columns (Dn: 64 x 64, column-major, ld 64; the next step
 // subtracts it from its diagonal tile instead of recomputing the product in front of its factorisation)
-__device__ __forceinline__ void syrk_slice(d4& g, const double* X, int R, int C, int c) {
+// In two halves, so that the caller can put the reads of everything it is about to multiply in front of the first product
+// (k_potrf_step: written as one function the compiler sank the reads back, two in front of every two products of the
+// dependent chain, and the wave sat out an LDS latency four times per slice).
+struct SyrkOps { double a[4], b[4]; };
+__device__ __forceinline__ void syrk_slice_load(SyrkOps& o, const double* X, int R, int C, int c) {
     const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
     const double* pa = X + (16 * C + li) * LT + 16 * c + lk;
     const double* pb = X + (16 * R + li) * LT + 16 * c + lk;
-    double av[4], bv[4];
 #pragma unroll
-    for (int k4 = 0; k4 < 4; ++k4) { av[k4] = pa[4 * k4]; bv[k4] = pb[4 * k4]; }
-#pragma unroll
-    for (int k4 = 0; k4 < 4; ++k4) g = __builtin_amdgcn_mfma_f64_16x16x4f64(av[k4], bv[k4], g, 0, 0, 0);
+    for (int k4 = 0; k4 < 4; ++k4) { o.a[k4] = pa[4 * k4]; o.b[k4] = pb[4 * k4]; }
+}
+__device__ __forceinline__ void syrk_slice_mma(d4& g, const SyrkOps& o, int k4) {
+    g = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[k4], o.b[k4], g, 0, 0, 0);
 }
 __device__ __forceinline__ void syrk_store(const d4& g, double* __restrict__ Dn, int R, int C) {
     const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
@@ -2183,7 +2197,7 @@ __global__ void __launch_bounds__(PSTEP_THREADS) k_potrf_step(double* __restrict
     }
     // scratch: tile 0 parks L_jj; tiles 1 and 2 (alternating with the step's parity: a late workgroup of step j + 1 may
     // still read one while step j + 1's owner of tile (j + 2, j + 1) writes the other) carry the next diagonal tile's
-    // update L_{j+1,j} L_{j+1,j}^T from the workgroup that solved L_{j+1,j} to the next launch (syrk_slice / syrk_store)
+    // update L_{j+1,j} L_{j+1,j}^T from the workgroup that solved L_{j+1,j} to the next launch (syrk_slice_load / syrk_store)
     double* Dn_out = scratch + (size_t)(1 + (j & 1)) * TB * TB;
     const double* Dn_in = scratch + (size_t)(2 - (j & 1)) * TB * TB;
     // (the diagonal block moves the previous step's L_{j-1,j-1} from `scratch` into place: see move_prev below)
@@ -2225,25 +2239,48 @@ __global__ void __launch_bounds__(PSTEP_THREADS) k_potrf_step(double* __restrict
             // 16 x 16 tiles belongs to workgroup t mod (1 + twins)): K-slice c once column block c of X is final in all rows.
             const bool has_solve = (a != 0) || diag_inv;
             const int ntwf = 1 + potrf_twins(Tn, j);
-            int fcount = 0, fR[3], fC[3];
-            d4 fg[3];
+            // (a block below the diagonal always has its twins, so a wave has two tiles at most: ten over 2 x 3 waves)
+            static_assert(10 <= 2 * 2 * (1 + POTRF_TWINS), "two tiles of X X^T per wave must cover the ten lower tiles");
+            int fcount = 0, fR[2], fC[2];
+            d4 fg[2];
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
+            for (int q = 0; q < 2; ++q) {
                 fg[q] = (d4){0.0, 0.0, 0.0, 0.0};
                 fR[q] = fC[q] = 0;
                 const int t = tw + ntwf * ((wave - 1) + 2 * q);      // the q-th tile of wave 1 / wave 2
                 if (a == 1 && (wave == 1 || wave == 2) && t < 10) { tile_from_index(t, fR[q], fC[q]); fcount = q + 1; }
             }
-            auto fsyrk = [&](int c) {
+            fcount = __builtin_amdgcn_readfirstlane(fcount);         // (the same in every lane of a wave: a scalar branch, no exec mask)
+            // K-slices c0 .. c0 + NC - 1 of the wave's tiles.  The operands of ALL of them are read first (a tile without work reads
+            // tile (0, 0): in bounds, unused), then the products run with nothing to wait for but the reads' own latency, once: the
+            // two tiles' dependent chains alternate, the order per accumulator is k4 = 0 .. 3 of slice c0, c0 + 1, .. as before.
+            auto fsyrk = [&](auto ncv, int c0) {
+                constexpr int NC = decltype(ncv)::value;
+                if (fcount == 0) return;
+                SyrkOps o[NC][2];
 #pragma unroll
-                for (int q = 0; q < 3; ++q)
-                    if (q < fcount) syrk_slice(fg[q], X, fR[q], fC[q], c);
+                for (int s = 0; s < NC; ++s)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) syrk_slice_load(o[s][q], X, fR[q], fC[q], c0 + s);
+                __builtin_amdgcn_sched_barrier(0);                   // (the reads stay in front of the products: see syrk_direct_stream)
+                if (fcount == 2) {
+#pragma unroll
+                    for (int s = 0; s < NC; ++s)
+#pragma unroll
+                        for (int k4 = 0; k4 < 4; ++k4) { syrk_slice_mma(fg[0], o[s][0], k4); syrk_slice_mma(fg[1], o[s][1], k4); }
+                } else {
+#pragma unroll
+                    for (int s = 0; s < NC; ++s)
+#pragma unroll
+                        for (int k4 = 0; k4 < 4; ++k4) syrk_slice_mma(fg[0], o[s][0], k4);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             };
             auto idle = [&](int iv) {
                 if (!has_solve) return;
                 if (wave == 0 && iv >= 4 && iv <= 6) trsm_interval(X, S, dprep, rinv, iv == 4 ? 2 : 3, iv - 4);
-                if (iv == 6) { fsyrk(0); fsyrk(1); }
-                else if (iv == 7) fsyrk(2);
+                if (iv == 6) fsyrk(std::integral_constant<int, 2>{}, 0);
+                else if (iv == 7) fsyrk(std::integral_constant<int, 1>{}, 2);
             };
             potf2_tile(S, dprep, rinv, info, j0, n_valid, idle);
             STEP_TRACE(3);
@@ -2253,9 +2290,9 @@ __global__ void __launch_bounds__(PSTEP_THREADS) k_potrf_step(double* __restrict
                 if (lane == 0) scratch[POTRF_LOGDET + j] = lg;
             }
             if (fcount > 0) {
-                fsyrk(3);
+                fsyrk(std::integral_constant<int, 1>{}, 3);
 #pragma unroll
-                for (int q = 0; q < 3; ++q)
+                for (int q = 0; q < 2; ++q)
                     if (q < fcount) syrk_store(fg[q], Dn_out, fR[q], fC[q]);
             }
             if (a == 0) {
@@ -2305,29 +2342,49 @@ __global__ void __launch_bounds__(PSTEP_THREADS) k_potrf_step(double* __restrict
         //   I4 run 2                                    -> wave 2 idle        I5 phase 2 (wave 3), I6 run 3 -> wave 3 idle
         // and the work moves: the tile's own rank-64 update (four K-slices per wave, I0 .. I3) and the sixteen 16 x 16 blocks of
         // the triangular solve (I4 .. I7; X is in LDS, so any wave can take any row block) go where a SIMD is free.
+        // What the products cost here (step trace, T): 35 ns each in a run of four independent accumulators, whether their
+        // operands are read directly in front of them or a k-step ahead -- the pipe's rate; the runs were never waiting for LDS.
+        // So the schedule is a packing problem in units of 0.56 us (a K-slice): see the table below.
         {
             // K-slices of the own update per wave and interval, a nibble each (immediates: a table in memory costs a scalar-cache
-            // miss per interval): wave 0: 0 2 2 0, wave 1: 3 0 0 1, waves 2 and 3: 2 0 2 0
-            const unsigned nslice = (wave == 0) ? 0x0220u : (wave == 1) ? 0x1003u : 0x0202u;
+            // miss per interval): wave 0: 0 1 2 1, wave 1: 3 0 0 1, waves 2 and 3: 3 0 1 0.  Fitted to the step trace: a slice
+            // (16 products) takes 0.56 us wherever it runs, so an interval carries what fits beside its factoring work -- I0 (the
+            // first pivot run, 2.1 us) three slices, I1 and I3 (phases, 0.85 us) one, I2 (a pivot run, 1.25 us) two on wave 0 and
+            // one on waves 2 and 3.  With wave 0: 0 2 2 0 and waves 2, 3: 2 0 2 0, I1 lasted 1.2 and I2 1.45 us.
+            const unsigned nslice = (wave == 0) ? 0x1210u : (wave == 1) ? 0x1003u : 0x0103u;
             int done = 0;
 #pragma unroll 1
             for (int it = 0; it < 4; ++it) {
                 if (below && j > 0) {
-                    const int n = (nslice >> (4 * it)) & 15;
-                    for (int q = 0; q < n; ++q) {
-                        const int sl = done++;
+                    const int n = __builtin_amdgcn_readfirstlane((nslice >> (4 * it)) & 15);     // (per wave: a scalar loop)
+                    if (n > 0) {
+                        // The interval's slices are one run of 4 n k-steps down the panels (a slice is 16 rows, a k-step 4).  The
+                        // operands are read a k-step AHEAD, into a second set of registers: the four products of step k wait for
+                        // reads that were issued in front of the products of step k - 1, not for reads directly in front of them.
+                        // The last step of the run reads its own rows again (nothing behind the panels may be read).
+                        // (Measured: a slice takes 0.56 us either way -- 35 ns per product, the matrix pipe's own rate.  With the
+                        // reads directly in front, the four independent products of the step before were still in the pipe while
+                        // the reads returned.  What this form saves is the exec-masked loop around the run.)
                         const int li = lane & 15, lk = lane >> 4;
-                        const double* ap = P0 + (16 * sl + lk) * PS + wr * 32 + li;
-                        const double* bp = P1 + (16 * sl + lk) * PS + wc * 32 + li;
+                        const double* ap = P0 + (16 * done + lk) * PS + wr * 32 + li;
+                        const double* bp = P1 + (16 * done + lk) * PS + wc * 32 + li;
+                        double a0 = ap[0], a1 = ap[16], b0 = bp[0], b1 = bp[16];
+                        for (int q = 0; q < n; ++q) {
 #pragma unroll
-                        for (int k4 = 0; k4 < 4; ++k4) {
-                            const double a0 = ap[0], a1 = ap[16], b0 = bp[0], b1 = bp[16];
-                            accX.t[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, accX.t[0][0], 0, 0, 0);
-                            accX.t[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, accX.t[0][1], 0, 0, 0);
-                            accX.t[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, accX.t[1][0], 0, 0, 0);
-                            accX.t[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, accX.t[1][1], 0, 0, 0);
-                            ap += 4 * PS; bp += 4 * PS;
+                            for (int k4 = 0; k4 < 4; ++k4) {
+                                const int adv = (k4 < 3 || q + 1 < n) ? 4 * PS : 0;
+                                ap += adv; bp += adv;
+                                const double na0 = ap[0], na1 = ap[16], nb0 = bp[0], nb1 = bp[16];
+                                __builtin_amdgcn_sched_barrier(0);   // (reads and products stay in the order written: see syrk_direct_stream)
+                                accX.t[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, accX.t[0][0], 0, 0, 0);
+                                accX.t[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, accX.t[0][1], 0, 0, 0);
+                                accX.t[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, accX.t[1][0], 0, 0, 0);
+                                accX.t[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, accX.t[1][1], 0, 0, 0);
+                                __builtin_amdgcn_sched_barrier(0);
+                                a0 = na0; a1 = na1; b0 = nb0; b1 = nb1;
+                            }
                         }
+                        done += n;
                     }
                     if (done == 4) { tile_sub_acc(X, accX, lane, wr, wc); done = 5; }
                 }

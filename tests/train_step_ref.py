@@ -406,6 +406,8 @@ PROBIT = {
     "g1e-4": ((1e-4, 1.0), [(0, 200, True, False), (200, 200, True, False), (0, 63, False, False)]),
     "g1_moments": ((1.0, 1.0), [(3, 255, False, False)]),
     "g1e-4_moments": ((1e-4, 1.0), [(0, 256, False, False)]),
+    # (tests/test_gpu_sharded_train.py: over three ranks the first window is 1 / 1 / 0 points -- an empty rank on a learning step)
+    "g1_empty": ((1.0, 1.0), [(0, 2, True, False), (2, 200, True, False)]),
 }
 
 

@@ -15,8 +15,12 @@ from oracle import sgp_oracle as O
 from tests import multi_theta_ref as R
 from tests.test_envelope_host import (EPS, LIMIT, MULTI_DIN, MULTI_ELL, MULTI_JIT, MULTI_RAGGED, MULTI_S2, UNI_D, UNI_ELL,
                                       UNI_JIT, UNI_PRIOR, UNI_S2, UNI_W, multi_reference, relF, uni_inputs, uni_reference)
+from tests.test_envelope_host import spd_cond
 from tests.test_gpu_parity import kuu_tol, post_tol
 from tests.test_gpu_reuse_stats import assert_bitwise, snapshot
+from tests.test_gpu_xu_grad import COND_MAX
+from tests.xu_grad_coverage import geometry as xu_geometry
+from tests.xu_grad_ref import analytic_grad_xu
 
 pytestmark = pytest.mark.gpu
 
@@ -288,6 +292,7 @@ def test_unisgp_theta_objective_at_the_limit(G):
         mu0, _, Uv0 = dev.posterior()
         dev.set_kernel(p0[0], p0[1:], UNI_JIT)
         val, grad = dev.theta_objective(want_grad=True, n_ell=1)
+        xu_val, xu_grad, gxu = dev.theta_objective_xu(want_grad=True)
 
         def f_dev(p):
             dev.set_kernel(p[0], p[1:], UNI_JIT)
@@ -301,6 +306,15 @@ def test_unisgp_theta_objective_at_the_limit(G):
     np.testing.assert_allclose(grad, g_ref, rtol=5e-5, atol=1e-6 * np.abs(g_ref).max())
     print(f"theta M=4032: value rel err {abs(val - ref) / abs(ref):.2g}, gradient rel err "
           f"{np.abs(grad - g_ref).max() / np.abs(g_ref).max():.2g}")
+    # the gradient in the inducing inputs behind it: T = 63, four ranges of 12, 12, 12 and 11 point blocks
+    assert xu_geometry(N, M)[:5] == (63, 47, 12, 4, 11)
+    assert xu_val == val and np.array_equal(xu_grad, grad) and gxu.shape == (M, UNI_D) and np.all(np.isfinite(gxu))
+    cond = spd_cond(O.kernelmatrix(p0[0], np.full(UNI_D, p0[1]), Xu) + UNI_JIT * np.eye(M))
+    assert cond < COND_MAX, cond                                   # so the bound of tests/test_gpu_xu_grad.py holds here as well
+    x_ref = analytic_grad_xu(p0[0], p0[1:], X, np.ones(N), y, Uv0.T @ Uv0, mu0, [[UNI_W]], Xu, UNI_JIT)
+    print(f"theta_objective_xu M=4032: cond(K_uu) {cond:.3g}, grad_xu error / bound = "
+          f"{(np.abs(gxu - x_ref) / (1e-6 * np.abs(x_ref) + 1e-9 * np.abs(x_ref).max())).max():.3g}")
+    np.testing.assert_allclose(gxu, x_ref, rtol=1e-6, atol=1e-9 * np.abs(x_ref).max())
 
 
 def test_multisgp_theta_objective_at_the_limit(G):
@@ -316,6 +330,7 @@ def test_multisgp_theta_objective_at_the_limit(G):
         mu, Sig, _ = dev.posterior(want_uv=False)
         dev.set_kernel(p0[0], p0[1:], MULTI_JIT)
         val, grad = dev.theta_objective(want_grad=True)
+        xu_val, xu_grad, gxu = dev.theta_objective_xu(want_grad=True)
     Rv = Sig + np.outer(mu, mu)
     fo = lambda p: R.batched_objective(p[0], p[1:], X, om, Yp, Rv, mu, f["W"], f["Xu"], MULTI_JIT)
     ref = fo(p0)
@@ -326,6 +341,13 @@ def test_multisgp_theta_objective_at_the_limit(G):
     np.testing.assert_allclose(grad, g_fd, rtol=5e-5, atol=1e-6 * np.abs(g_fd).max())
     print(f"theta (4, 1008): value rel err {abs(val - ref) / abs(ref):.2g}, gradient rel err "
           f"{np.abs(grad - g_an).max() / np.abs(g_an).max():.2g}")
+    # the gradient in the inducing inputs behind it: T = 16 with four outputs, 15 ranges of 4 point blocks
+    assert xu_geometry(len(X), M)[:5] == (16, 60, 4, 15, 4)
+    assert xu_val == val and np.array_equal(xu_grad, grad) and gxu.shape == (M, MULTI_DIN) and np.all(np.isfinite(gxu))
+    x_ref = analytic_grad_xu(p0[0], p0[1:], X, om, Yp, Rv, mu, f["W"], f["Xu"], MULTI_JIT)
+    print(f"theta_objective_xu (4, 1008): grad_xu error / bound = "
+          f"{(np.abs(gxu - x_ref) / (1e-6 * np.abs(x_ref) + 1e-9 * np.abs(x_ref).max())).max():.3g}")
+    np.testing.assert_allclose(gxu, x_ref, rtol=1e-6, atol=1e-9 * np.abs(x_ref).max())
 
 
 def test_reused_and_targets_sweeps_at_the_limit(G):

@@ -51,7 +51,7 @@ CASES = {
     "f": dict(M=48, D=2, d_out=2, nodes=7, cub="sr", jitter=1e-8, seed=6, family="matern32"),
 }
 SIGMA2 = 0.8
-ELL = {1: (0.25, 0.25), 2: (0.7, 0.9), 3: (0.9, 1.3), 5: (1.8, 2.6)}     # lengthscales per input dimension: linspace(lo, hi, D)
+ELL = {1: (0.25, 0.25), 2: (0.7, 0.9), 3: (0.9, 1.3), 4: (1.1, 1.7), 5: (1.8, 2.6)}     # per input dimension: linspace(lo, hi, D)
 
 
 @contextlib.contextmanager

@@ -46,9 +46,13 @@ def test_cases_match_the_reference(G, name):
         ones = dev.out_message(c["X"], c["start"], np.ones(len(c["X"])), c["mu_v"])
         unweighted = dev.out_message(c["X"], c["start"], None, c["mu_v"])
     ratio = worst(np.abs(mean - mean_ref), tol)
-    print(f"case {name}: worst |mean - reference| / tol {ratio:.3g}")
+    K = np.abs(R.kernel(c["family"], c["sigma2"], c["ell"], c["Xu"], c["X"]))             # M x n
+    point_tol = 50 * R.EPS * K.T @ np.abs(c["mu_v"]).reshape(c["d_out"], c["M"]).T          # tol's summand: 50 eps |k_s|'|mu_v^(d)|
+    point_ratio = worst(np.abs(point - point_ref), point_tol)
+    print(f"case {name}: worst |mean - reference| / tol {ratio:.3g}, per point {point_ratio:.3g}")
     assert mean.shape == mean_ref.shape and np.isfinite(mean).all() and np.isfinite(point).all()
     assert ratio <= 1.0
+    assert point.shape == point_ref.shape and point_ratio <= 1.0
     assert np.array_equal(point, predicted)                                # bitwise sgp_predict's values
     assert np.array_equal(mean, again[0]) and np.array_equal(point, again[1])        # repeated calls agree bitwise
     assert np.array_equal(ones, unweighted)

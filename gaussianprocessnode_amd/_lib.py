@@ -35,7 +35,7 @@ EXPORTS = [
     "sgp_predict_var", "sgp_set_kernel_family", "sgp_kernelmatrix_family", "sgp_in_message", "sgp_in_message_grad",
     "sgp_theta_descend", "sgp_out_message", "sgp_psi_stats", "sgp_sweep_local_psi",
     "sgp_theta_objective_psi", "sgp_theta_descend_psi", "sgp_psi_in_grad", "sgp_psi_predict",
-    "sgp_theta_objective_xu",
+    "sgp_theta_objective_xu", "sgp_theta_objective_psi_xu",
 ]
 # kernel families (SGP_KERNEL_* of include/sgp_hip.h), by the names the Python layer accepts
 SGP_KERNEL_SE, SGP_KERNEL_MATERN12, SGP_KERNEL_MATERN32, SGP_KERNEL_MATERN52 = 0, 1, 2, 3
@@ -158,6 +158,7 @@ def load(build_if_missing: bool = True, variant=None):
     lib.sgp_theta_descend.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, dp, dp,
                                       C.POINTER(C.c_int64)]
     lib.sgp_theta_objective_psi.argtypes = [vp, dp, dp, dp, C.c_int64, dp, dp, C.POINTER(C.c_int64)]
+    lib.sgp_theta_objective_psi_xu.argtypes = [vp, dp, dp, dp, C.c_int64, dp, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_psi_in_grad.argtypes = [vp, dp, dp, dp, C.c_int64, dp, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_psi_predict.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_theta_descend_psi.argtypes = [vp, dp, dp, dp, C.c_int64, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,

@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
 // sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad,
-// sgp_psi_predict, sgp_theta_objective_xu).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
+// sgp_psi_predict, sgp_theta_objective_xu, sgp_theta_objective_psi_xu).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -218,6 +218,26 @@ static inline void layout_psi_theta(Carver& c, const PointShape& p, bool has_cov
     b->Vals = c.take<double>(steps);
     b->Pscr = c.take<double>((size_t)p.potrf_scratch);
     b->Info = c.take<int>(1);
+}
+
+// sgp_theta_objective_psi_xu: sgp_theta_objective_psi's pieces (no steps) and, behind them, what the second pass adds: one chunk of
+// the Psi1 half's rows ([node][D][Mp]) and their range sums ([range][D][Mp]); the node part's row partials ([range][lower tile][wave]
+// [D][64]) and column partials ([range][lower tile][D][64]); the K_uu half's partials ([J][I][D][64]) and the gradient (M x D)
+struct PsiThetaXuScratch : PsiThetaScratch {
+    double *P1, *Part1;
+    double *RowPart, *ColPart;
+    double *PartXU, *GradXu;
+};
+static inline void layout_psi_theta_xu(Carver& c, const PointShape& p, int M, bool has_cov, size_t nranges, size_t slots,
+                                       size_t tile_slots, PsiThetaXuScratch* b) {
+    const size_t D = (size_t)p.D, ntiles = (size_t)p.T * (p.T + 1) / 2, acc_tiles = nranges * ntiles;
+    layout_psi_theta(c, p, has_cov, acc_tiles, slots, tile_slots, 0, b);
+    b->P1 = c.take<double>((size_t)p.chunk * D * p.Mp);
+    b->Part1 = c.take<double>(nranges * D * p.Mp);
+    b->RowPart = c.take<double>(acc_tiles * 4 * D * 64);
+    b->ColPart = c.take<double>(acc_tiles * D * 64);
+    b->PartXU = c.take<double>((size_t)p.T * p.T * D * 64);
+    b->GradXu = c.take<double>((size_t)M * D);
 }
 
 // sgp_psi_in_grad (p.n = p.n_nodes = the nodes, p.chunk nodes per chunk): the inputs, status words and results of all nodes (energy,

@@ -118,6 +118,7 @@ struct SweepPlan {
 //   next_kind (once per record)                 checked, or drops reuse: its sweep ended without K_uu factored / with a wait given up
 //   sgp_sweep_local_psi                         fills the record, drops reuse, exact_psi; data_gen++; have_data = false (sgp_set_data clears exact_psi)
 //   sgp_theta_objective_psi                     nothing: everything it forms is in call scratch
+//   sgp_theta_objective_psi_xu                  nothing: everything it forms is in call scratch
 //   sgp_psi_in_grad                             nothing: everything it forms is in call scratch
 //   sgp_psi_predict                             nothing: everything it forms is in call scratch
 //   sgp_theta_descend_psi                       nothing: the kernel moved (hParams, params_gen++), nothing resident was rewritten, and
@@ -3553,18 +3554,31 @@ static int psi_theta_status(sgp_handle* h, const std::string& name, int node, in
     return factor_status(h, info_kuu, (name + ": K_uu").c_str());
 }
 
-extern "C" int sgp_theta_objective_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
-                                       double* value, double* grad, int64_t* info) {
-    const char* name = "sgp_theta_objective_psi";
-    if (!h || !mean || !y_mean || !value) return fail(h, SGP_ERR_ARG, "sgp_theta_objective_psi: null argument");
+// sgp_theta_objective_psi, and sgp_theta_objective_psi_xu under its own name (`name`: the refusals' prefix; grad_xu non-null: its
+// second pass behind the same evaluation, over the larger layout of the same pieces).
+static int psi_xu_enqueue(sgp_handle* h, hipStream_t s, const PsiThetaXuScratch& b, const PointShape& shape, bool has_cov, const MeanW& w);
+static int theta_objective_psi_call(sgp_handle* h, const char* name, const double* mean, const double* cov, const double* y_mean,
+                                    int64_t n_nodes, double* value, double* grad, int64_t* info, double* grad_xu, bool want_xu) {
+    if (!h || !mean || !y_mean || !value) return refuse(h, name, "null argument");
     if (info) info[0] = info[1] = 0;
+    if (want_xu && !grad_xu)
+        return refuse(h, name, "grad_xu is NULL (sgp_theta_objective_psi returns value and theta gradient alone)");
     if (n_nodes < 1) return refuse(h, name, "n_nodes must be >= 1");
     if (int rc = psi_theta_ready(h, name, mean, cov, y_mean, n_nodes)) return rc;
     if (int wrc = sync_checked(h)) return wrc;
     hipStream_t s = h->own;
-    const PointShape shape = psi_theta_shape(h, n_nodes);
-    PsiThetaScratch b;
-    if (int crc = psi_theta_carve(h, shape, cov != nullptr, 0, &b)) return crc;
+    const PointShape shape = want_xu ? point_shape(h, 3 * (int64_t)h->D * h->Mp + h->D + 1, n_nodes, n_nodes) : psi_theta_shape(h, n_nodes);
+    PsiThetaXuScratch b;
+    if (want_xu) {
+        int nranges = 0;
+        int64_t range_len = 0;
+        psi_ranges(shape.n, h->ntiles, &nranges, &range_len);
+        if (int crc = carve_call_scratch(h, [&](Carver& c) {
+                layout_psi_theta_xu(c, shape, h->M, cov != nullptr, (size_t)nranges, GRAD_SLOTS, PSI_TP_SLOTS, &b);
+            })) return crc;
+    } else if (int crc = psi_theta_carve(h, shape, cov != nullptr, 0, &b)) {
+        return crc;
+    }
     if (int rc = psi_theta_upload(h, b, mean, cov, y_mean, n_nodes)) return rc;
     const MeanW w(h);
     const double* Rv = h->dR;
@@ -3579,10 +3593,68 @@ extern "C" int sgp_theta_objective_psi(sgp_handle* h, const double* mean, const 
     if (int rc = psi_theta_status(h, name, node, kuu)) return rc;
     double res[GRAD_SLOTS + 1];
     HIPCHK(h, hipMemcpy(res, b.Out, sizeof res, hipMemcpyDeviceToHost));
+    if (want_xu) {
+        // every node and K_uu factored: the second pass over the nodes, reading G, H, Psi2 and the chain's mirror where the first left them
+        if (int rc = psi_xu_enqueue(h, s, b, shape, cov != nullptr, w)) return rc;
+        HIPCHK(h, wait_stream(s));
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpy(grad_xu, b.GradXu, sizeof(double) * (size_t)h->M * h->D, hipMemcpyDeviceToHost));
+    }
     *value = res[GRAD_SLOTS];
     if (grad)
         for (int i = 0; i <= h->n_ell; ++i) grad[i] = res[i];
     return 0;
+}
+
+extern "C" int sgp_theta_objective_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
+                                       double* value, double* grad, int64_t* info) {
+    return theta_objective_psi_call(h, "sgp_theta_objective_psi", mean, cov, y_mean, n_nodes, value, grad, info, nullptr, false);
+}
+
+// ---- the same objective's gradient in the inducing inputs (include/sgp_hip.h: sgp_theta_objective_psi_xu; k_psi_xu_* / k_psi1_xu_* /
+// ---- k_psi2_xu_* in sgp_kernels.hip.h) ----
+// The second pass, on `s` behind a finished and successful psi_theta_enqueue over the same scratch: per chunk the nodes' g, h and Psi1
+// rows again (the first pass kept one chunk of them), the Psi1 half's and the node part's range sums over psi_ranges' ranges -- a
+// function of T and M alone, partials left in memory across chunks -- then the K_uu half on H and the fixed-order finish into b.GradXu.
+static int psi_xu_enqueue(sgp_handle* h, hipStream_t s, const PsiThetaXuScratch& b, const PointShape& shape, bool has_cov, const MeanW& w) {
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Tn = h->T, ntiles = h->ntiles;
+    const int64_t T = shape.n;
+    int nranges = 0;
+    int64_t range_len = 0;
+    psi_ranges(T, ntiles, &nranges, &range_len);
+    const size_t acc_tiles = (size_t)nranges * ntiles;
+    HIPCHK(h, hipMemsetAsync(b.Part1, 0, sizeof(double) * (size_t)nranges * D * Mp, s));
+    HIPCHK(h, hipMemsetAsync(b.RowPart, 0, sizeof(double) * acc_tiles * 4 * D * TB, s));
+    HIPCHK(h, hipMemsetAsync(b.ColPart, 0, sizeof(double) * acc_tiles * D * TB, s));
+    for (int64_t t0 = 0; t0 < T; t0 += shape.chunk) {
+        const int64_t nc = std::min<int64_t>(shape.chunk, T - t0);
+        const int r0 = (int)(t0 / range_len), r1 = (int)((t0 + nc - 1) / range_len);
+        auto launch = [&](auto DCAP) {
+            constexpr int DC = decltype(DCAP)::value;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi_xu_prep<DC>), dim3((unsigned)nc), dim3(64), 0, s, (const double*)h->dXu,
+                               (const double*)b.Mean, has_cov ? (const double*)b.Cov : (const double*)nullptr, (const double*)b.Y, T, t0,
+                               (const double*)h->dMu, w.W, (const Params*)h->dParamsK, b.G2, b.H2, b.Cw, b.P1, M, Mp, D, dout);
+            hipLaunchKernelGGL(k_psi1_xu_accumulate, dim3((unsigned)((D * Mp + 255) / 256), r1 - r0 + 1), dim3(256), 0, s,
+                               (const double*)b.P1, b.Part1, t0, nc, range_len, r0, Mp, D);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psi2_xu_accumulate<DC>), dim3(ntiles, r1 - r0 + 1), dim3(256), 0, s,
+                               (const double*)b.G2, (const double*)b.H2, (const double*)b.Cw, (const double*)b.G,
+                               (const double*)h->dXusK, b.RowPart, b.ColPart, t0, nc, range_len, r0, ntiles, Mp, D);
+        };
+        if (D <= 8) launch(std::integral_constant<int, 8>{});
+        else launch(std::integral_constant<int, MAXD>{});
+    }
+    hipLaunchKernelGGL(k_xu_grad_uu<SGP_KERNEL_SE>, dim3(Tn, Tn), dim3(256), 0, s, (const double*)b.H, (const double*)h->dXusK,
+                       (const Params*)h->dParamsK, b.PartXU, M, Mp, D);
+    hipLaunchKernelGGL(k_psi_xu_finish, dim3((unsigned)((M * D + 255) / 256)), dim3(256), 0, s, (const double*)b.Part1,
+                       (const double*)b.RowPart, (const double*)b.ColPart, nranges, ntiles, (const double*)b.G, (const double*)b.Psi2,
+                       (const double*)h->dXusK, (const double*)b.PartXU, (const Params*)h->dParamsK, w.trace, b.GradXu, M, Mp, Tn, D);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+extern "C" int sgp_theta_objective_psi_xu(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
+                                          double* value, double* grad, double* grad_xu, int64_t* info) {
+    return theta_objective_psi_call(h, "sgp_theta_objective_psi_xu", mean, cov, y_mean, n_nodes, value, grad, info, grad_xu, true);
 }
 
 // sgp_theta_descend with the objective above: per step, all on the library's own stream, one evaluation at theta_k and

@@ -5012,6 +5012,260 @@ __global__ void __launch_bounds__(256) k_psi_theta_finish(const double* __restri
     if (n_ell == 1) out[1] = gsum;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same objective's gradient in the inducing inputs (sgp_theta_objective_psi_xu): a second pass over the nodes behind
+// the objective's own, which has left G, H, the summed Psi2 and the K_uu chain's mirror in call scratch.  With h(c)_tm = P_c (m_t - z_m):
+//   df/dz_md = - sum_t s_t[m] Psi1_t[m] h(1)_tm,d + 1/2 sum_t sum_j G_mj Psi2_t[m,j] (h(2)_tm,d + h(2)_tj,d)
+//              - 1/2 sum_j G_mj Psi2[m,j] (z_md - z_jd) / ell_d^2 + tr(W) sum_j H_mj K_uu[m,j] (z_jd - z_md) / ell_d^2
+// (the last term is k_xu_grad_uu<SE> on H).  No atomics; every sum has an order that (T, M, D) fix.
+// ------------------------------------------------------------------------------------------------
+// k_psi_theta_prep without the theta sums: g and h of Lambda + 2 S and cw as there, and the Psi1 half's rows
+//   P1 [node of the chunk][D][Mp] = s_t[m] Psi1_t[m] h(1)_tm,d, rows m >= M zero.
+// A node whose factorisation fails (the objective's pass has reported it: the host does not come here) writes zeros.
+template <int DCAP>
+__global__ void __launch_bounds__(64) k_psi_xu_prep(const double* __restrict__ Xu, const double* __restrict__ mean,
+                                                    const double* __restrict__ cov, const double* __restrict__ y, int64_t T, int64_t t0,
+                                                    const double* __restrict__ mu, OutMat W, const Params* __restrict__ P,
+                                                    double* __restrict__ G2, double* __restrict__ H2, double* __restrict__ cw,
+                                                    double* __restrict__ P1, int M, int Mp, int D, int d_out) {
+    __shared__ double A1[MAXD * PSI_LD], A2[MAXD * PSI_LD], C1[MAXD * PSI_LD], C2[MAXD * PSI_LD];
+    __shared__ double r1[MAXD], r2[MAXD], e1[MAXD], e2[MAXD], mt[MAXD], ell[MAXD];
+    __shared__ int failed;
+    const int lane = threadIdx.x;
+    const int64_t tc = blockIdx.x, t = t0 + tc;
+    if (lane == 0) failed = 0;
+    if (lane < D) { mt[lane] = mean[(size_t)t * D + lane]; ell[lane] = 1.0 / P->inv_ell[lane]; }
+    __syncthreads();
+    const double* S = cov ? cov + (size_t)t * D * D : nullptr;
+    psi_factor_inv(A1, C1, r1, e1, &failed, S, ell, 1.0, D, lane);
+    psi_factor_inv(A2, C2, r2, e2, &failed, S, ell, 2.0, D, lane);
+    if (failed) {                                             // (uniform)
+        if (lane == 0) cw[tc] = 0.0;
+        for (int e = lane; e < D * Mp; e += 64) {
+            G2[(size_t)tc * D * Mp + e] = 0.0;
+            H2[(size_t)tc * D * Mp + e] = 0.0;
+            P1[(size_t)tc * D * Mp + e] = 0.0;
+        }
+        return;
+    }
+    double det1 = 1.0, det2 = 1.0;                            // prod_d ell_d / C_dd, in the order d = 0, 1, ..
+    for (int d = 0; d < D; ++d) { det1 *= ell[d] * r1[d]; det2 *= ell[d] * r2[d]; }
+    if (lane == 0) cw[tc] = det2;
+    double wy[MAXO];                                          // (W y_t)_o
+#pragma unroll
+    for (int o = 0; o < MAXO; ++o) {
+        wy[o] = 0.0;
+        if (o < d_out)
+            for (int e = 0; e < d_out; ++e) wy[o] = fma(W.v[o + e * d_out], y[(size_t)e * T + t], wy[o]);
+    }
+    const double s2 = P->sigma2;
+    for (int m = lane; m < Mp; m += 64) {
+        asm volatile("" ::: "memory");                        // (as k_psi_theta_prep: the factors are re-read from LDS for every m)
+        double diff[DCAP], g[DCAP];
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d) diff[d] = (d < D && m < M) ? mt[d] - Xu[(size_t)m * D + d] : 0.0;
+        const double q1 = psi_solve<DCAP>(g, diff, A1, r1, D);
+        double sp = 0.0;
+        if (m < M) {
+            double st = 0.0;
+#pragma unroll
+            for (int o = 0; o < MAXO; ++o)
+                if (o < d_out) st = fma(mu[(size_t)o * M + m], wy[o], st);
+            sp = st * (s2 * det1 * exp(-0.5 * q1));
+        }
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d)
+            if (d < D) P1[((size_t)tc * D + d) * Mp + m] = sp * psi_back<DCAP>(g, C1, D, d);
+        psi_solve<DCAP>(g, diff, A2, r2, D);
+#pragma unroll
+        for (int d = 0; d < DCAP; ++d)
+            if (d < D) {
+                G2[((size_t)tc * D + d) * Mp + m] = g[d];
+                H2[((size_t)tc * D + d) * Mp + m] = psi_back<DCAP>(g, C2, D, d);
+            }
+    }
+}
+
+// The Psi1 half's column sums over nodes: part1[range][d][m] += P1[node][d][m], the nodes of the range that this chunk holds IN ORDER
+// (k_psi2_accumulate's ranges; a chunk that ends inside a range leaves the sum in memory for the next chunk's launch).  Grid
+// (ceil(D Mp / 256), the ranges the chunk meets).
+__global__ void __launch_bounds__(256) k_psi1_xu_accumulate(const double* __restrict__ P1, double* __restrict__ part1, int64_t t0,
+                                                            int64_t nc, int64_t range_len, int r0, int Mp, int D) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= D * Mp) return;
+    const int r = r0 + (int)blockIdx.y;
+    const int64_t lo = r * range_len > t0 ? r * range_len : t0;
+    const int64_t hi_t = (r + 1) * range_len < t0 + nc ? (r + 1) * range_len : t0 + nc;
+    if (lo >= hi_t) return;
+    double* o = part1 + (size_t)r * D * Mp + e;
+    double v = *o;
+    for (int64_t t = lo; t < hi_t; ++t) v += P1[(size_t)(t - t0) * D * Mp + e];
+    *o = v;
+}
+
+// The node part of the Psi2 half: k_psi2_theta_accumulate's decomposition, staging and omega (the same expressions), but the sums
+// are per ROW and per COLUMN of the tile:
+//   rowp[range][tile][wave][d][i] += sum_{j of the wave} omega_ijt (h_id + h_jd),   colp[range][tile][d][j] += sum_i omega_ijt (h_id + h_jd)
+// (the column sums feed the rows of tile row J: off-diagonal tiles only; a diagonal tile holds both mirror images already).  The running
+// sums live in LDS, [4 waves + 1][D][64] doubles -- in registers a thread's 4 rows + 4 columns would be 8 D values.  Per node and d a
+// thread folds its 4 x 4 entries into 4 row and 4 column values; the 16 threads of a column (16 adjacent lanes) and the 4 of a row
+// that share a wave reduce them by a halving butterfly (each step hands half of the values to the partner, so 4 values cost 5 resp.
+// 3 exchanges), which leaves every value with ONE owner lane that adds it to its own LDS word: no two lanes write a word, and a word
+// sees its nodes in order.  The four waves' row sums stay apart down to memory (k_psi_xu_finish adds them), so that a range cut by
+// the chunking adds in the same order as one that is not.
+template <int DCAP>
+__global__ void __launch_bounds__(256) k_psi2_xu_accumulate(const double* __restrict__ G2, const double* __restrict__ H2,
+                                                            const double* __restrict__ cw, const double* __restrict__ Gm,
+                                                            const double* __restrict__ Xus, double* __restrict__ rowp,
+                                                            double* __restrict__ colp, int64_t t0, int64_t nc, int64_t range_len,
+                                                            int r0, int ntiles, int Mp, int D) {
+    constexpr int ROWS = DCAP <= 8 ? 16 : 32;                 // LDS rows (node x dimension) per stage and array
+    __shared__ double gi[ROWS * TB], gj[ROWS * TB], hi[ROWS * TB], hj[ROWS * TB];
+    __shared__ double rs[4 * DCAP * TB], cs[DCAP * TB];
+    const int tid = threadIdx.x, ti = tid & 15, tj = tid >> 4, lane = tid & 63, wave = tid >> 6;
+    int I, J;
+    tile_from_index((int)blockIdx.x, I, J);
+    const int r = r0 + (int)blockIdx.y;
+    const int64_t lo = r * range_len > t0 ? r * range_len : t0;
+    const int64_t hi_t = (r + 1) * range_len < t0 + nc ? (r + 1) * range_len : t0 + nc;
+    if (lo >= hi_t) return;                                   // (uniform)
+    const bool offdiag = I != J;                              // (uniform)
+    double* rp = rowp + ((size_t)r * ntiles + blockIdx.x) * 4 * D * TB;
+    double* cp = colp + ((size_t)r * ntiles + blockIdx.x) * D * TB;
+    for (int e = tid; e < 4 * D * TB; e += 256) rs[e] = rp[e];
+    for (int e = tid; e < D * TB; e += 256) cs[e] = cp[e];
+    double gf[4][4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) {
+            const int i = I * TB + ti + 16 * x, j = J * TB + tj + 16 * y;
+            double q = 0.0;
+            for (int d = 0; d < D; ++d) { const double u = Xus[(size_t)d * Mp + i] - Xus[(size_t)d * Mp + j]; q = fma(u, u, q); }
+            gf[x][y] = Gm[(size_t)j * Mp + i] * exp(-0.25 * q);
+        }
+    // the lane's words: after the butterflies it holds row ti + 16 (2 b4 + b5) of its wave and, lanes ti < 4, column tj + 16 (2 b0 + b1)
+    const bool b0 = lane & 1, b1 = lane & 2, b4 = lane & 16, b5 = lane & 32;
+    double* myrow = rs + (size_t)wave * D * TB + ti + 16 * (2 * (int)b4 + (int)b5);
+    double* mycol = cs + tj + 16 * (2 * (int)b0 + (int)b1);
+    const bool colowner = ti < 4;
+    const int per = ROWS / D;                                 // nodes per stage (D <= ROWS: at least one)
+    for (int64_t tb = lo; tb < hi_t; tb += per) {
+        const int nn = (int)(hi_t - tb < per ? hi_t - tb : per);
+        __syncthreads();
+        for (int e = tid; e < nn * D * TB; e += 256) {
+            const int q = e >> 6, i = e & 63;
+            const size_t row = ((size_t)(tb - t0) * D + q) * Mp;
+            gi[q * TB + i] = G2[row + I * TB + i];
+            gj[q * TB + i] = G2[row + J * TB + i];
+            hi[q * TB + i] = H2[row + I * TB + i];
+            hj[q * TB + i] = H2[row + J * TB + i];
+        }
+        __syncthreads();
+        for (int n = 0; n < nn; ++n) {
+            double s[4][4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) s[x][y] = 0.0;
+            for (int d = 0; d < D; ++d) {
+                const double* pi = gi + (n * D + d) * TB;
+                const double* pj = gj + (n * D + d) * TB;
+                double vi[4], vj[4];
+#pragma unroll
+                for (int x = 0; x < 4; ++x) { vi[x] = pi[ti + 16 * x]; vj[x] = pj[tj + 16 * x]; }
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+#pragma unroll
+                    for (int y = 0; y < 4; ++y) { const double u = vi[x] + vj[y]; s[x][y] = fma(u, u, s[x][y]); }
+            }
+            const double c = cw[tb - t0 + n];
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) s[x][y] = gf[x][y] * (c * exp(-0.25 * s[x][y]));     // omega
+            for (int d = 0; d < D; ++d) {
+                const double* pi = hi + (n * D + d) * TB;
+                const double* pj = hj + (n * D + d) * TB;
+                double vi[4], vj[4], rr[4], cc[4];
+#pragma unroll
+                for (int x = 0; x < 4; ++x) { vi[x] = pi[ti + 16 * x]; vj[x] = pj[tj + 16 * x]; rr[x] = 0.0; cc[x] = 0.0; }
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+#pragma unroll
+                    for (int y = 0; y < 4; ++y) {
+                        const double p = s[x][y] * (vi[x] + vj[y]);
+                        rr[x] += p;
+                        cc[y] += p;
+                    }
+                {   // rows: the 4 lanes ti, ti + 16, ti + 32, ti + 48 of this wave
+                    double ka = b4 ? rr[2] : rr[0], kb = b4 ? rr[3] : rr[1];
+                    ka += __shfl_xor(b4 ? rr[0] : rr[2], 16);
+                    kb += __shfl_xor(b4 ? rr[1] : rr[3], 16);
+                    double k = b5 ? kb : ka;
+                    k += __shfl_xor(b5 ? ka : kb, 32);
+                    myrow[d * TB] += k;
+                }
+                if (offdiag) {   // columns: the 16 lanes ti = 0 .. 15 of this tj
+                    double ka = b0 ? cc[2] : cc[0], kb = b0 ? cc[3] : cc[1];
+                    ka += __shfl_xor(b0 ? cc[0] : cc[2], 1);
+                    kb += __shfl_xor(b0 ? cc[1] : cc[3], 1);
+                    double k = b1 ? kb : ka;
+                    k += __shfl_xor(b1 ? ka : kb, 2);
+                    k += __shfl_xor(k, 4);
+                    k += __shfl_xor(k, 8);
+                    if (colowner) mycol[d * TB] += k;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 4 * D * TB; e += 256) rp[e] = rs[e];
+    if (offdiag)
+        for (int e = tid; e < D * TB; e += 256) cp[e] = cs[e];
+}
+
+// Per (m, d), m fastest: the Psi1 half's ranges in order; the node part -- per tile of the row the ranges in order (the four waves of
+// one as (0 + 1) + (2 + 3)), the row's own tiles J = 0 .. I, then the column sums of the tiles (I', I), I' = I + 1 .. -- ; the
+// node-independent term against the summed Psi2, j = 0 .. M - 1; the K_uu half's tiles J = 0 .. T - 1 (k_xu_grad_uu<SE> on H); then
+// the factors -1, sigma2^2 / 2, -1/2 and tr(W), the latter two with 1 / ell_d.  out is M x D row-major.
+__global__ void __launch_bounds__(256) k_psi_xu_finish(const double* __restrict__ part1, const double* __restrict__ rowp,
+                                                       const double* __restrict__ colp, int nranges, int ntiles,
+                                                       const double* __restrict__ Gm, const double* __restrict__ psi2,
+                                                       const double* __restrict__ Xus, const double* __restrict__ part_uu,
+                                                       const Params* __restrict__ P, double trW, double* __restrict__ out,
+                                                       int M, int Mp, int T, int D) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= M * D) return;
+    const int m = e % M, d = e / M, I = m / TB, rw = m % TB;
+    double lin = 0.0;
+    for (int r = 0; r < nranges; ++r) lin += part1[((size_t)r * D + d) * Mp + m];
+    double node = 0.0;
+    for (int J = 0; J <= I; ++J) {
+        const int tile = I * (I + 1) / 2 + J;
+        double v = 0.0;
+        for (int r = 0; r < nranges; ++r) {
+            const double* p = rowp + (((size_t)r * ntiles + tile) * 4 * D + d) * TB + rw;
+            v += (p[0] + p[(size_t)D * TB]) + (p[(size_t)2 * D * TB] + p[(size_t)3 * D * TB]);
+        }
+        node += v;
+    }
+    for (int I2 = I + 1; I2 < T; ++I2) {
+        const int tile = I2 * (I2 + 1) / 2 + I;
+        double v = 0.0;
+        for (int r = 0; r < nranges; ++r) v += colp[(((size_t)r * ntiles + tile) * D + d) * TB + rw];
+        node += v;
+    }
+    const double zm = Xus[(size_t)d * Mp + m];
+    double fix = 0.0;
+    for (int j = 0; j < M; ++j)
+        fix = fma(Gm[(size_t)j * Mp + m] * psi2[(size_t)j * Mp + m], zm - Xus[(size_t)d * Mp + j], fix);
+    double uu = 0.0;
+    for (int J = 0; J < T; ++J) uu += part_uu[(((size_t)J * T + I) * D + d) * TB + rw];
+    const double s4 = P->sigma2 * P->sigma2;
+    out[(size_t)m * D + d] = 0.5 * s4 * node - lin + (trW * uu - 0.5 * fix) * P->inv_ell[d];
+}
+
 // k_descend_step for sgp_theta_descend_psi: value and gradient are where k_psi_theta_finish left them.  An indefinite node (checked
 // first) or a nonzero K_uu status word stops the descent, latched in st->stop as -(1 + node + 1) resp. the failing minor (-1: a
 // twin-workgroup wait given up); from then on every step leaves theta, the moments, the powers, values[] and the parameters alone.

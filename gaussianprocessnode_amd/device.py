@@ -141,12 +141,20 @@ class SGPDevice:
         self._n_ell = int(ell.size)          # the C side writes 1 + n_ell gradient entries (sgp_theta_objective)
         if fam is not None:
             self._check(self._lib.sgp_set_kernel_family(self._h, fam), "sgp_set_kernel_family")
+            self._family = int(fam)
 
     def set_kernel_family(self, family) -> None:
         """Kernel family of every later sweep, prediction and theta objective: a name ("se", "matern12", "matern32",
         "matern52") or an SGP_KERNEL_* id.  Ids outside 0..3 and a change inside a training run raise SGPError."""
         fam = family if isinstance(family, (int, np.integer)) else _lib.family_id(family)
         self._check(self._lib.sgp_set_kernel_family(self._h, int(fam)), "sgp_set_kernel_family")
+        self._family = int(fam)
+
+    @property
+    def kernel_family(self) -> str:
+        """The name of the kernel family last set through this object ("se" on a new handle)."""
+        fam = getattr(self, "_family", _lib.SGP_KERNEL_SE)
+        return next(name for name, i in _lib.KERNEL_FAMILIES.items() if i == fam)
 
     def set_prior_meancov(self, mu0, Sigma0):
         mu0 = as_f64(np.reshape(mu0, (self.Q,)))
@@ -510,6 +518,25 @@ class SGPDevice:
         self._check(self._lib.sgp_theta_objective_psi(self._h, ptr(m), ptr(S), ptr(y_cm), T, C.cast(C.byref(v), C.POINTER(C.c_double)),
                                                       ptr(g), info), "sgp_theta_objective_psi")
         return (v.value, g) if want_grad else v.value
+
+    def theta_objective_psi_xu(self, mean, cov, y_mean, want_grad: bool = False):
+        """`theta_objective_psi` and, behind it, the analytic gradient of the same objective in the inducing inputs at the resident
+        `set_inducing` and the current kernel (sgp_theta_objective_psi_xu): (value, grad_xu) or, with want_grad, (value, grad,
+        grad_xu).  value and grad are bitwise `theta_objective_psi`'s; grad_xu is (M, D), laid out as `set_inducing` takes Xu.  q(v),
+        W and the Gaussian inputs are held.  Arguments and exceptions as `theta_objective_psi`."""
+        m, S, T = self._node_gaussians("theta_objective_psi_xu", mean, cov)
+        y_cm = self._node_targets(y_mean, T)
+        have = getattr(self, "_n_ell", None)
+        if want_grad and have is None:
+            raise ValueError("theta_objective_psi_xu: call set_kernel first")
+        v = C.c_double()
+        g = np.empty(1 + have) if want_grad else None
+        gxu = np.empty((self.M, self.D))
+        info = (C.c_int64 * 2)()
+        self._check(self._lib.sgp_theta_objective_psi_xu(self._h, ptr(m), ptr(S), ptr(y_cm), T,
+                                                         C.cast(C.byref(v), C.POINTER(C.c_double)), ptr(g), ptr(gxu), info),
+                    "sgp_theta_objective_psi_xu")
+        return (v.value, g, gxu) if want_grad else (v.value, gxu)
 
     def theta_descend_psi(self, mean, cov, y_mean, theta, steps: int, *, eta: float = 1e-3, beta=(0.9, 0.999), eps: float = 1e-8,
                           state=None):

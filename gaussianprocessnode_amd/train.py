@@ -341,7 +341,8 @@ def optimize_theta(theta, engine, *, steps: int = 100, optimizer=None):
     return _descend(theta, engine, int(steps), opt)
 
 
-def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=None, learn_theta: bool = True, jitter: float = 0.0):
+def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=None, learn_theta: bool = True, jitter: float = 0.0,
+                      psi: str = "cubature", inputs=None):
     """`steps` host-paced AdaMax steps on the objective of `theta_objective` in the inducing inputs -- on [theta | vec Xu] together,
     or on Xu alone with learn_theta=False -- over an `engine` (SGPDevice) that has data, noise and a kernel family, with q(v) held
     for the whole call.  theta is raw (pre-softplus, sigma2 first, 1 or D lengthscales); Xu is (M, D); q_v is (mu_v, Uv) as
@@ -356,7 +357,17 @@ def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=Non
     With q(v) held, moving z_m reinterprets v_m as the function value at the new location: the objective is a function of Xu only
     through that reading, and q(v) is no longer the posterior of any sweep once Xu has moved.  The intended use is alternation --
     a few steps here, then sweeps at the new Xu to refit q(v).  The reference never moves Xu; there is no counterpart of this
-    loop in it."""
+    loop in it.
+
+    psi="exact" with inputs=(mean, cov, y_mean) as `theta_objective_psi` takes them: the same loop on the objective over the exact
+    Psi-statistics of the Gaussian inputs (SE kernel only), one `theta_objective_psi_xu` per step; no resident data are needed."""
+    if psi not in ("cubature", "exact"):
+        raise ValueError(f"optimize_inducing: psi must be 'cubature' or 'exact', got {psi!r}")
+    if psi == "exact":
+        if inputs is None:
+            raise ValueError("optimize_inducing: psi='exact' needs inputs=(mean, cov, y_mean)")
+        if getattr(engine, "kernel_family", "se") != "se":
+            raise ValueError("optimize_inducing: psi='exact' exists for the SE kernel only")
     theta = np.array(theta, dtype=np.float64).reshape(-1)
     Xu = np.array(Xu, dtype=np.float64)
     if Xu.ndim != 2:
@@ -380,7 +391,10 @@ def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=Non
         engine.set_kernel(float(p[0]), p[1:], jitter)
         engine.set_inducing(x[nt:].reshape(M, D))
         engine.set_posterior(mu_v, Uv)
-        values[k], g, gxu = engine.theta_objective_xu(want_grad=True)
+        if psi == "exact":
+            values[k], g, gxu = engine.theta_objective_psi_xu(*inputs, want_grad=True)
+        else:
+            values[k], g, gxu = engine.theta_objective_xu(want_grad=True)
         grad = np.concatenate([(np.asarray(g) * sigmoid(th))[:nt], np.asarray(gxu, dtype=np.float64).ravel()])
         opt.update(x, grad)
     return (x[:nt].copy() if learn_theta else theta), x[nt:].reshape(M, D).copy(), values

@@ -545,6 +545,29 @@ int sgp_theta_descend_psi(sgp_handle* h, const double* mean, const double* cov, 
                           double beta2, double eps, double* opt_state /* 2 (1 + n_ell) + 2, in/out, may be NULL */,
                           double* values /* steps, may be NULL */, int64_t* counts /* 3, may be NULL */);
 
+/* sgp_theta_objective_psi_xu: sgp_theta_objective_psi with its gradient and, behind it, the analytic gradient of the same f in the
+ * inducing inputs, with q(v), W, theta and the Gaussian inputs held.  With P_c = (Lambda + c S_t)^-1, Lambda = diag(ell^2),
+ * h(c)_tm = P_c (m_t - z_m), H = Kinv Psi2 Kinv and Kinv = (K_uu + jitter I)^-1:
+ *     df/dz_md = - sum_t s_t[m] Psi1_t[m] h(1)_tm,d
+ *                + 1/2 sum_t sum_j G_mj Psi2_t[m,j] (h(2)_tm,d + h(2)_tj,d)
+ *                - 1/2 sum_j G_mj Psi2[m,j] (z_md - z_jd) / ell_d^2
+ *                + tr(W) sum_j H_mj K_uu[m,j] (z_jd - z_md) / ell_d^2
+ * (the diagonal sigma2 + jitter of K_uu does not depend on Z).  At S_t = 0 for all t this is sgp_theta_objective_xu's grad_xu with
+ * the means as data points.
+ *
+ * The objective runs first, through sgp_theta_objective_psi's own code: value and grad (1 + n_ell, may be NULL) are bitwise that
+ * call's, info and the positive return values are its own.  grad_xu is then formed in a second pass over the nodes from what the
+ * first left in call scratch (G, H, the summed Psi2, the K_uu chain): M x D, laid out as sgp_set_inducing takes Xu.  d_out = 1 .. 4,
+ * D <= 32, one shared or D lengthscales, cov NULL / zero / rank-deficient / full, as there.  A failed call -- an indefinite node or
+ * K_uu minor included -- leaves grad_xu unwritten; the handle's state afterwards is what sgp_theta_objective_psi leaves.  No atomics;
+ * every sum runs in an order that (T, M, D) fix: identical calls agree bitwise, also under different SGP_PREDICT_CHUNK.
+ *
+ * SGP_ERR_ARG: everything sgp_theta_objective_psi refuses; a NULL grad_xu. */
+int sgp_theta_objective_psi_xu(sgp_handle* h, const double* mean /* D x T */, const double* cov /* D x D x T or NULL */,
+                               const double* y_mean /* T x d_out */, int64_t n_nodes, double* value,
+                               double* grad /* 1 + n_ell, may be NULL */, double* grad_xu /* M x D as sgp_set_inducing takes Xu */,
+                               int64_t* info /* 2, may be NULL */);
+
 /* ---- exact-Psi input messages: a node's energy and its derivatives in the mean and covariance of its Gaussian input ----
  * With q(v), W, G and s_t as for sgp_theta_objective_psi (SGP_KERNEL_SE only, d_out = 1 .. 4, D <= 8) and x_t ~ N(m_t, S_t), the part of
  * node t's average energy that depends on its input is

@@ -34,7 +34,7 @@ import ReactiveMP: @rule, @average_energy, @call_rule, GenericProd, PointMass, M
                    mean_var, AverageEnergy, ContinuousUnivariateLogPdf, ContinuousMultivariateLogPdf, UnspecifiedDomain
 import ..UniSGP, ..UniSGPMeta, ..MultiSGP, ..MultiSGPMeta, ..WishartFast, ..approximate_kernel_expectation!
 
-export HipSGPMeta, HipMultiSGPMeta, predict, predictive, theta_objective, theta_objective_xu, carry_posterior!, multisgp_sweep!
+export HipSGPMeta, HipMultiSGPMeta, predict, predictive, theta_objective, theta_objective_xu, theta_objective_psi_xu, carry_posterior!, multisgp_sweep!
 
 const LIB = get(ENV, "SGP_HIP_LIB", "libsgp_hip.so")
 
@@ -575,6 +575,16 @@ function theta_objective_psi(h::Handle, m::Matrix{Float64}, S, y::Matrix{Float64
                 (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
                 h.ptr, m, S === nothing ? C_NULL : S, y, T, value, grad, info), h.ptr)
     return value[], grad
+end
+
+# The same value and gradient and, behind them, dF/dXu at the resident inducing inputs (sgp_theta_objective_psi_xu): D × M, the
+# column-major image of the M × D row-major array the ABI writes.  q(v), W, θ and the Gaussian inputs are held.
+function theta_objective_psi_xu(h::Handle, m::Matrix{Float64}, S, y::Matrix{Float64}, n_ell::Integer, M::Integer)
+    D, T = size(m); value = Ref{Float64}(0.0); grad = zeros(1 + n_ell); gxu = zeros(D, M); info = zeros(Int64, 2)
+    check(ccall((:sgp_theta_objective_psi_xu, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, m, S === nothing ? C_NULL : S, y, T, value, grad, gxu, info), h.ptr)
+    return value[], grad, gxu
 end
 
 function theta_descend_psi!(meta::HipSGPMeta, m::Matrix{Float64}, S, y::Matrix{Float64}, θ::Vector{Float64}, steps::Integer;

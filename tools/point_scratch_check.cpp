@@ -1,8 +1,8 @@
 // Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over grids of shapes, the
-// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict and layout_xu_grad hand out are
+// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad and layout_psi_theta_xu hand out are
 // pairwise disjoint at the sizes their consumers need (stated here independently of the layout functions), every piece starts a
 // multiple of Carver::ALIGN doubles from the base, pass 2 hands out the total pass 1 summed and the last piece ends there.  The
-// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict and layout_xu_grad get an allocation of
+// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad and layout_psi_theta_xu get an allocation of
 // exactly their total per shape and every piece is written end to end, so that the sanitizer sees a write past it.  No GPU:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o tools/point_scratch_check tools/point_scratch_check.cpp
 //   (or any C++17 compiler with -fsanitize=address,undefined) && tools/point_scratch_check
@@ -334,6 +334,50 @@ long xu_grad_sweep() {
             }
     return shapes;
 }
+// sgp_theta_objective_psi_xu over its grid, each shape in an allocation of its own: sgp_theta_objective_psi's pieces (no steps) and the
+// second pass's, with and without covariances, the range count of psi_ranges
+long psi_theta_xu_sweep() {
+    long shapes = 0;
+    const size_t slots = 33, tile_slots = 65;                 // GRAD_SLOTS, PSI_TP_SLOTS
+    for (int M : {1, 48, 65, 130})
+        for (int D : {1, 2, 5, 8, 9, 32})
+            for (int dout : {1, 4})
+                for (int64_t n : {1, 63, 65, 300})
+                    for (int64_t chunk : {(int64_t)64, (n + 63) / 64 * 64})
+                        for (int opt = 0; opt < 2; ++opt) {
+                            const bool cov = opt & 1;
+                            const int Mp = (M + TB - 1) / TB * TB, T = Mp / TB, ntiles = T * (T + 1) / 2;
+                            const int64_t want = std::min<int64_t>((n + 7) / 8, std::max(1, 1024 / ntiles)), len = (n + want - 1) / want;
+                            const size_t ranges = (size_t)((n + len - 1) / len), acc = ranges * ntiles;
+                            const PointShape s{Mp, 0, T, D, dout, POTRF_SCRATCH, std::min(chunk, (n + 63) / 64 * 64), n, n};
+                            check("psi_theta_xu", s, 0, nullptr, 0, true, [&](Carver& c) {
+                                PsiThetaXuScratch b;
+                                layout_psi_theta_xu(c, s, M, cov, ranges, slots, tile_slots, &b);
+                                const size_t nn = (size_t)n, ch = (size_t)s.chunk, mm = (size_t)Mp * Mp * d;
+                                const std::vector<Piece> all = {
+                                    {"Mean", b.Mean, nn * D * d}, {"Cov", b.Cov, cov ? nn * D * D * d : 0}, {"Y", b.Y, nn * dout * d},
+                                    {"Bad", b.Bad, nn * sizeof(int)}, {"Lin", b.Lin, nn * slots * d}, {"G2", b.G2, ch * D * Mp * d},
+                                    {"H2", b.H2, ch * D * Mp * d}, {"E2", b.E2, ch * D * d}, {"Cw", b.Cw, ch * d},
+                                    {"Acc", b.Acc, acc * TB * TB * d}, {"Wd", b.Wd, acc * D * 256 * d},
+                                    {"TilePart", b.TilePart, (size_t)ntiles * tile_slots * d}, {"Kuu", b.Kuu, mm}, {"Wk", b.Wk, mm},
+                                    {"Kinv", b.Kinv, mm}, {"G", b.G, mm}, {"Gpart", b.Gpart, (size_t)Mp * d}, {"Psi2", b.Psi2, mm},
+                                    {"T1", b.T1, mm}, {"H", b.H, mm}, {"PartUU", b.PartUU, (size_t)T * T * slots * d},
+                                    {"Out", b.Out, 2 * slots * d}, {"Status", b.Status, sizeof(int)},
+                                    {"Pscr", b.Pscr, (size_t)POTRF_SCRATCH * d}, {"Info", b.Info, sizeof(int)},
+                                    // the second pass: a chunk of Psi1 rows, the range sums, the (tile, range) partials of the four waves'
+                                    // rows and of the columns, k_xu_grad_uu's T x T partials and the gradient
+                                    {"P1", b.P1, ch * D * Mp * d}, {"Part1", b.Part1, ranges * D * Mp * d},
+                                    {"RowPart", b.RowPart, acc * 4 * D * TB * d}, {"ColPart", b.ColPart, acc * D * TB * d},
+                                    {"PartXU", b.PartXU, (size_t)T * T * D * TB * d}, {"GradXu", b.GradXu, (size_t)M * D * d}};
+                                std::vector<Piece> p;
+                                for (const Piece& q : all)
+                                    if (q.bytes) p.push_back(q);                  // (a piece that is not wanted has no extent)
+                                return p;
+                            });
+                            ++shapes;
+                        }
+    return shapes;
+}
 }  // namespace
 
 int main() {
@@ -350,8 +394,9 @@ int main() {
     const long psi_in = psi_in_sweep();
     const long psi_predict = psi_predict_sweep();
     const long xu_grad = xu_grad_sweep();
+    const long psi_theta_xu = psi_theta_xu_sweep();
     std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes, %ld psi shapes, %ld psi-theta shapes, "
-                "%ld psi-in shapes, %ld psi-predict shapes, %ld xu-grad shapes: %ld failure(s)\n", panel, largest, mean_only, psi,
-                psi_theta, psi_in, psi_predict, xu_grad, failures);
+                "%ld psi-in shapes, %ld psi-predict shapes, %ld xu-grad shapes, %ld psi-theta-xu shapes: %ld failure(s)\n", panel, largest,
+                mean_only, psi, psi_theta, psi_in, psi_predict, xu_grad, psi_theta_xu, failures);
     return failures ? 1 : 0;
 }

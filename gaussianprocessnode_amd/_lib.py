@@ -35,7 +35,7 @@ EXPORTS = [
     "sgp_predict_var", "sgp_set_kernel_family", "sgp_kernelmatrix_family", "sgp_in_message", "sgp_in_message_grad",
     "sgp_theta_descend", "sgp_out_message", "sgp_psi_stats", "sgp_sweep_local_psi",
     "sgp_theta_objective_psi", "sgp_theta_descend_psi", "sgp_psi_in_grad", "sgp_psi_predict",
-    "sgp_theta_objective_xu", "sgp_theta_objective_psi_xu",
+    "sgp_theta_objective_xu", "sgp_theta_objective_psi_xu", "sgp_inducing_descend", "sgp_inducing_descend_psi",
 ]
 # kernel families (SGP_KERNEL_* of include/sgp_hip.h), by the names the Python layer accepts
 SGP_KERNEL_SE, SGP_KERNEL_MATERN12, SGP_KERNEL_MATERN32, SGP_KERNEL_MATERN52 = 0, 1, 2, 3
@@ -55,6 +55,7 @@ def family_id(family) -> int:
 SGP_TIME_GROUP0 = 100
 SGP_TIME_QUADFORM = 120
 SGP_PREDICT_NOISE = 1         # sgp_predict_var: add the observation noise W^-1
+SGP_DESCEND_THETA, SGP_DESCEND_XU = 1, 2      # sgp_inducing_descend[_psi]: what the optimised vector holds
 
 
 class SGPError(RuntimeError):
@@ -163,6 +164,10 @@ def load(build_if_missing: bool = True, variant=None):
     lib.sgp_psi_predict.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_theta_descend_psi.argtypes = [vp, dp, dp, dp, C.c_int64, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
                                           C.c_double, dp, dp, C.POINTER(C.c_int64)]
+    lib.sgp_inducing_descend.argtypes = [vp, dp, C.c_int32, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         dp, dp, C.POINTER(C.c_int64)]
+    lib.sgp_inducing_descend_psi.argtypes = [vp, dp, dp, dp, C.c_int64, dp, C.c_int32, dp, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                             C.c_double, C.c_double, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_get_step_trace.argtypes = [C.POINTER(C.c_int64)]
     lib.sgp_measure_clocks.argtypes = [C.c_int32, dp]
     lib.sgp_overlap_plan.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

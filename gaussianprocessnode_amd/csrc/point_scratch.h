@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
 // sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad,
-// sgp_psi_predict, sgp_theta_objective_xu, sgp_theta_objective_psi_xu).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
+// sgp_psi_predict, sgp_theta_objective_xu, sgp_theta_objective_psi_xu, sgp_inducing_descend, sgp_inducing_descend_psi).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
 #pragma once
 
 #include <cstddef>
@@ -317,6 +317,29 @@ static inline void layout_xu_grad(Carver& c, const PointShape& p, int M, size_t 
     b->PartUF = c.take<double>(nranges * p.T * tile);
     b->PartUU = c.take<double>((size_t)p.T * p.T * tile);
     b->Grad = c.take<double>((size_t)M * p.D);
+}
+
+// what the two inducing-input descents add behind their objective's layout: the AdaMax moments of the M x D inducing coordinates
+// ([m | u], 2 M D), the words the scalar optimiser launch publishes for the elementwise one (`pub`), and the values of the steps
+struct InducingStepScratch { double *Mom, *Pub, *Vals; };
+static inline void layout_inducing_step(Carver& c, int M, int D, size_t pub, size_t steps, InducingStepScratch* b) {
+    b->Mom = c.take<double>(2 * (size_t)M * D);
+    b->Pub = c.take<double>(pub);
+    b->Vals = c.take<double>(steps);
+}
+// sgp_inducing_descend: sgp_theta_objective_xu's pieces and the optimiser's
+struct InducingDescendScratch { XuGradScratch g; InducingStepScratch o; };
+static inline void layout_inducing_descend(Carver& c, const PointShape& p, int M, size_t nranges, size_t pub, size_t steps,
+                                           InducingDescendScratch* b) {
+    layout_xu_grad(c, p, M, nranges, &b->g);
+    layout_inducing_step(c, M, p.D, pub, steps, &b->o);
+}
+// sgp_inducing_descend_psi: sgp_theta_objective_psi_xu's pieces and the optimiser's
+struct PsiInducingDescendScratch { PsiThetaXuScratch g; InducingStepScratch o; };
+static inline void layout_psi_inducing_descend(Carver& c, const PointShape& p, int M, bool has_cov, size_t nranges, size_t slots,
+                                               size_t tile_slots, size_t pub, size_t steps, PsiInducingDescendScratch* b) {
+    layout_psi_theta_xu(c, p, M, has_cov, nranges, slots, tile_slots, &b->g);
+    layout_inducing_step(c, M, p.D, pub, steps, &b->o);
 }
 
 // sgp_predict: the points, their means and an explicit mu_v (Q entries, unpadded)

@@ -123,6 +123,10 @@ struct SweepPlan {
 //   sgp_psi_predict                             nothing: everything it forms is in call scratch
 //   sgp_theta_descend_psi                       nothing: the kernel moved (hParams, params_gen++), nothing resident was rewritten, and
 //                                               kernel_matches, which compares values, turns the resident statistics down
+//   sgp_inducing_descend                        drops reuse and q(v); swept_local = false; data_gen++ (the statistics are the last
+//                                               EVALUATED (theta, Xu)'s; the inducing inputs moved, as after sgp_set_inducing)
+//   sgp_inducing_descend_psi                    drops reuse; data_gen++ (nothing resident was rewritten, but the inducing inputs moved: the
+//                                               statistics on the device are those of the OLD Xu -- stale, though sgp_get_stats still hands them out)
 struct StatsRecord {
     double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};   // the kernel values they were formed at ...
     int32_t family = SGP_KERNEL_SE;                           // ... and the family
@@ -3102,25 +3106,11 @@ static void xu_ranges(int64_t n, int T, int* nranges, int* range_len) {
     *nranges = (int)((nblk + *range_len - 1) / *range_len);
 }
 
-// sgp_theta_objective with its gradient runs first, unchanged: value and grad are its own, and it leaves G (d_out > 1: with the
-// padded mean columns and omega W y in dThetaMulti) and H in dGradM, K_uf, the scaled inducing inputs and the parameter mirror at the
-// current theta on both of its paths.  The new kernels read those behind it; what they write is call scratch.
-extern "C" int sgp_theta_objective_xu(sgp_handle* h, double* value, double* grad, double* grad_xu) {
-    const char* name = "sgp_theta_objective_xu";
-    if (h && value && !grad_xu) return refuse(h, name, "grad_xu is NULL (sgp_theta_objective returns value and theta gradient alone)");
-    if (h && h->allreduce) return refuse(h, name, "data-sharded inducing-input gradients are not supported (remove the hook)");
-    double gtheta[GRAD_SLOTS];
-    if (int rc = theta_objective_call(h, name, value, gtheta)) return rc;
-    if (grad)
-        for (int i = 0; i <= h->n_ell; ++i) grad[i] = gtheta[i];
+// The three launches behind a theta gradient on `s` (the caller orders them behind BOTH of its halves): the K_uu half on H, the data half
+// over xu_ranges' ranges, and the fixed-order finish into b.Grad.  They read G (d_out > 1: with the padded mean columns and omega W y in
+// dThetaMulti) and H in dGradM, K_uf, the scaled inducing inputs and the parameter mirror; what they write is call scratch.
+static void enqueue_xu_grad(sgp_handle* h, hipStream_t s, const XuGradScratch& b, int nranges, int range_len) {
     const int Mp = h->Mp, T = h->T, D = h->D;
-    hipStream_t s = h->own;
-    if (h->side) HIPCHK(h, hipStreamSynchronize(h->side));     // (the K_uu half's H came from there; its join is a bounded wait)
-    int nranges = 0, range_len = 1;
-    if (h->n > 0) xu_ranges(h->n, T, &nranges, &range_len);
-    const PointShape shape = point_shape(h, 1, h->n, h->n);
-    XuGradScratch b;
-    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_xu_grad(c, shape, h->M, (size_t)nranges, &b); })) return crc;
     const double* dG = h->dGradM;
     const double* dH = h->dGradM + 2 * (size_t)Mp * Mp;
     const bool multi = h->dout > 1;
@@ -3149,9 +3139,29 @@ extern "C" int sgp_theta_objective_xu(sgp_handle* h, double* value, double* grad
     hipLaunchKernelGGL(k_xu_grad_finish, dim3((unsigned)((h->M * D + 255) / 256)), dim3(256), 0, s, (const double*)b.PartUF, nranges,
                        (const double*)b.PartUU, (const Params*)h->dParams, multi ? 1.0 : w, multi ? MeanW(h).trace : w, b.Grad,
                        h->M, T, D);
+}
+
+// sgp_theta_objective with its gradient runs first, unchanged: value and grad are its own, and it leaves G and H in dGradM, K_uf, the
+// scaled inducing inputs and the parameter mirror at the current theta on both of its paths.  enqueue_xu_grad reads those behind it.
+extern "C" int sgp_theta_objective_xu(sgp_handle* h, double* value, double* grad, double* grad_xu) {
+    const char* name = "sgp_theta_objective_xu";
+    if (h && value && !grad_xu) return refuse(h, name, "grad_xu is NULL (sgp_theta_objective returns value and theta gradient alone)");
+    if (h && h->allreduce) return refuse(h, name, "data-sharded inducing-input gradients are not supported (remove the hook)");
+    double gtheta[GRAD_SLOTS];
+    if (int rc = theta_objective_call(h, name, value, gtheta)) return rc;
+    if (grad)
+        for (int i = 0; i <= h->n_ell; ++i) grad[i] = gtheta[i];
+    hipStream_t s = h->own;
+    if (h->side) HIPCHK(h, hipStreamSynchronize(h->side));     // (the K_uu half's H came from there; its join is a bounded wait)
+    int nranges = 0, range_len = 1;
+    if (h->n > 0) xu_ranges(h->n, h->T, &nranges, &range_len);
+    const PointShape shape = point_shape(h, 1, h->n, h->n);
+    XuGradScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_xu_grad(c, shape, h->M, (size_t)nranges, &b); })) return crc;
+    enqueue_xu_grad(h, s, b, nranges, range_len);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, wait_stream(s));
-    HIPCHK(h, hipMemcpy(grad_xu, b.Grad, sizeof(double) * (size_t)h->M * D, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(grad_xu, b.Grad, sizeof(double) * (size_t)h->M * h->D, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -3744,6 +3754,254 @@ extern "C" int sgp_theta_descend_psi(sgp_handle* h, const double* mean, const do
     }
     if (opt_state) { opt_state[2 * np] = st.bp[0]; opt_state[2 * np + 1] = st.bp[1]; }
     if (values) for (int k = 0; k < steps; ++k) values[k] = vals[(size_t)k];
+    const int node = st.stop <= -2.0 ? (int)(-st.stop - 1.0) : 0;
+    const int kuu = st.stop <= -2.0 ? 0 : (int)st.stop;
+    if (counts) { counts[0] = (int64_t)st.steps; counts[1] = kuu > 0 ? kuu : 0; counts[2] = node; }
+    if (st.stop != 0.0) return psi_theta_status(h, std::string(name) + ", step " + std::to_string((int64_t)st.steps), node, kuu);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Device-paced AdaMax descent in the inducing inputs at a held q(v) (include/sgp_hip.h: sgp_inducing_descend,
+// sgp_inducing_descend_psi): sgp_theta_descend / sgp_theta_descend_psi with the gradient in Xu behind each step's theta
+// gradient and the optimiser on x = [theta_raw | vec Xu] (or vec Xu alone).  Stream order is again the whole ordering argument: the
+// elementwise optimiser launch writes dXu behind the last kernel that read it or its scaled copies at step k, and step k + 1's
+// k_prep_xu launches (the K_uu chain's and the main stream's, both re-run because params_gen moves; the Psi path's chain and its node
+// kernels, which read dXu itself) sit behind that write.  The host enqueues and waits once.
+// ------------------------------------------------------------------------------------------------
+struct InducingRun {
+    int nt = 0, nx = 0, np = 0;     // optimised theta entries (0: theta held), inducing coordinates, their sum
+    int ntheta = 0;                 // 1 + n_ell
+    bool learn = false;
+};
+
+// what both calls check before anything is touched
+static int inducing_descend_args(sgp_handle* h, const char* name, const double* theta_raw, int32_t n_ell, const double* Xu, int32_t flags,
+                                 int32_t steps, double eta, double beta1, double beta2, const double* opt_state, InducingRun* r) {
+    if (!h || !theta_raw) return refuse(h, name, "null argument");
+    if (!Xu) return refuse(h, name, "Xu is NULL");
+    if (!(flags & SGP_DESCEND_XU) || (flags & ~(SGP_DESCEND_THETA | SGP_DESCEND_XU)))
+        return refuse(h, name, "flags must contain SGP_DESCEND_XU and nothing but SGP_DESCEND_THETA beside it (theta alone: sgp_theta_descend)");
+    if (n_ell != 1 && n_ell != h->D) return refuse(h, name, "n_ell must be 1 or D");
+    if (steps < 0) return refuse(h, name, "steps must be >= 0");
+    if (!(eta > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return refuse(h, name, "eta > 0 and beta1, beta2 in [0, 1) required");
+    r->learn = (flags & SGP_DESCEND_THETA) != 0;
+    r->ntheta = 1 + n_ell;
+    r->nt = r->learn ? r->ntheta : 0;
+    r->nx = h->M * h->D;
+    r->np = r->nt + r->nx;
+    if (opt_state) {
+        // (a power is beta^t, t >= 1: inside (0, 1), or exactly 0 for a beta of 0)
+        const double bt[2] = {beta1, beta2};
+        for (int i = 0; i < 2; ++i) {
+            const double pw = opt_state[2 * (size_t)r->np + i];
+            if (!(pw < 1.0) || !(pw > 0.0 || (pw == 0.0 && bt[i] == 0.0)))
+                return refuse(h, name, "the running powers of beta in opt_state must lie in (0, 1)");
+        }
+    }
+    for (int i = 0; i < r->ntheta; ++i)
+        if (!std::isfinite(theta_raw[i])) return refuse(h, name, "theta_raw must be finite");
+    for (int i = 0; i < r->nx; ++i)
+        if (!std::isfinite(Xu[i])) return refuse(h, name, "Xu must be finite");
+    if (h->allreduce) return refuse(h, name, "data-sharded descent is not supported (remove the hook)");
+    return 0;
+}
+
+// The run's state onto the device (the caller has waited for the handle): theta and its moments into dTrain, the kernel block, Xu into
+// dXu, the inducing coordinates' moments, a cleared publish block and NaN values into call scratch; then softplus(theta_0) where the
+// first k_prep_xu reads it.
+static int inducing_descend_begin(sgp_handle* h, hipStream_t s, const InducingRun& r, const InducingStepScratch& o, const double* theta_raw,
+                                  const double* Xu, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2, double eps,
+                                  const double* opt_state) {
+    TrainState st;
+    memset(&st, 0, sizeof st);
+    for (int i = 0; i < r.ntheta; ++i) {
+        st.theta[i] = theta_raw[i];
+        if (opt_state && r.learn) { st.m[i] = opt_state[i]; st.u[i] = opt_state[r.np + i]; }
+    }
+    st.bp[0] = opt_state ? opt_state[2 * (size_t)r.np] : beta1;
+    st.bp[1] = opt_state ? opt_state[2 * (size_t)r.np + 1] : beta2;
+    st.eta = eta; st.beta1 = beta1; st.beta2 = beta2; st.eps = eps;
+    HIPCHK(h, hipMemcpy(h->dTrain, &st, sizeof st, hipMemcpyHostToDevice));
+    // noise, E[log w], the prior and the jitter stay what the setters left; sigma2 and the lengthscales come from theta on the device
+    HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->dXu, Xu, sizeof(double) * (size_t)r.nx, hipMemcpyHostToDevice));
+    h->have_inducing = true;
+    if (opt_state) {
+        HIPCHK(h, hipMemcpy(o.Mom, opt_state + r.nt, sizeof(double) * (size_t)r.nx, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(o.Mom + r.nx, opt_state + r.np + r.nt, sizeof(double) * (size_t)r.nx, hipMemcpyHostToDevice));
+    } else {
+        HIPCHK(h, hipMemsetAsync(o.Mom, 0, sizeof(double) * 2 * (size_t)r.nx, s));     // (on `s`: in front of the kernels by stream order)
+    }
+    HIPCHK(h, hipMemsetAsync(o.Pub, 0, sizeof(double) * INDUCING_PUB, s));
+    const std::vector<double> nan((size_t)steps, std::numeric_limits<double>::quiet_NaN());
+    HIPCHK(h, hipMemcpy(o.Vals, nan.data(), sizeof(double) * (size_t)steps, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_train_adamax, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)nullptr, (const double*)nullptr,
+                       h->dTrainParams, h->D, n_ell, 0, (const int*)nullptr, (const Params*)nullptr, (const double*)nullptr);
+    return 0;
+}
+
+static void launch_inducing_step_xu(sgp_handle* h, hipStream_t s, const InducingRun& r, const InducingStepScratch& o, const double* grad_xu,
+                                    double beta1, double beta2, double eps) {
+    hipLaunchKernelGGL(k_inducing_step_xu, dim3((unsigned)((r.nx + 255) / 256)), dim3(256), 0, s, (const double*)o.Pub, grad_xu, h->dXu, o.Mom,
+                       r.nx, beta1, beta2, eps);
+}
+
+// The run's results back (the caller has waited for the stream): the handle's kernel is softplus(theta_out) as the device formed it,
+// its inducing inputs are what dXu holds; theta, Xu, the state in AdaMax.get_state's layout for the joint vector, and the values
+static int inducing_descend_end(sgp_handle* h, const InducingRun& r, const InducingStepScratch& o, double* theta_raw, double* Xu,
+                                int32_t steps, double* opt_state, double* values, TrainState* st) {
+    HIPCHK(h, hipMemcpy(st, h->dTrain, sizeof *st, hipMemcpyDeviceToHost));
+    Params P;
+    HIPCHK(h, hipMemcpy(&P, h->dTrainParams, sizeof P, hipMemcpyDeviceToHost));
+    h->hParams->sigma2 = P.sigma2;
+    for (int d = 0; d < h->D; ++d) h->hParams->inv_ell[d] = P.inv_ell[d];
+    HIPCHK(h, hipMemcpy(Xu, h->dXu, sizeof(double) * (size_t)r.nx, hipMemcpyDeviceToHost));
+    for (int i = 0; i < r.ntheta; ++i) theta_raw[i] = st->theta[i];
+    if (opt_state) {
+        for (int i = 0; i < r.nt; ++i) { opt_state[i] = st->m[i]; opt_state[r.np + i] = st->u[i]; }
+        HIPCHK(h, hipMemcpy(opt_state + r.nt, o.Mom, sizeof(double) * (size_t)r.nx, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(opt_state + r.np + r.nt, o.Mom + r.nx, sizeof(double) * (size_t)r.nx, hipMemcpyDeviceToHost));
+        opt_state[2 * (size_t)r.np] = st->bp[0];
+        opt_state[2 * (size_t)r.np + 1] = st->bp[1];
+    }
+    if (values) HIPCHK(h, hipMemcpy(values, o.Vals, sizeof(double) * (size_t)steps, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Per step on the library's own stream: the re-evaluation of sgp_theta_objective at (softplus(theta_k), Xu_k) -- enqueue_restats; both
+// k_prep_xu launches read dXu, so the K_uu chain's mirror and the main stream's follow the moved inducing inputs --, the value, the theta
+// gradient with both halves on this stream, enqueue_xu_grad behind it (no side-stream wait: nothing ran there), k_inducing_step and
+// k_inducing_step_xu.
+extern "C" int sgp_inducing_descend(sgp_handle* h, double* theta_raw, int32_t n_ell, double* Xu, int32_t flags, int32_t steps, double eta,
+                                    double beta1, double beta2, double eps, double* opt_state, double* values, int64_t* counts) {
+    const char* name = "sgp_inducing_descend";
+    InducingRun r;
+    if (int rc = inducing_descend_args(h, name, theta_raw, n_ell, Xu, flags, steps, eta, beta1, beta2, opt_state, &r)) return rc;
+    if (int prc = refuse_exact_psi(h, name)) return prc;
+    if (int trc = refuse_training(h, name)) return trc;
+    if (!h->swept) return refuse(h, name, "needs a finished sweep or sgp_set_posterior (q(v))");
+    if (!h->have_data || !h->have_kernel) return refuse(h, name, "data and kernel must be set");
+    if (counts) counts[0] = counts[1] = 0;
+    if (steps == 0) return 0;
+    if (int wrc = sync_checked(h)) return wrc;
+    hipStream_t s = h->own;
+    if (!h->dTrain) {
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
+    }
+    if (int arc = alloc_theta_grad(h)) return arc;
+    int nranges = 0, range_len = 1;
+    if (h->n > 0) xu_ranges(h->n, h->T, &nranges, &range_len);
+    const PointShape shape = point_shape(h, 1, h->n, h->n);
+    InducingDescendScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) {
+            layout_inducing_descend(c, shape, h->M, (size_t)nranges, INDUCING_PUB, (size_t)steps, &b);
+        })) return crc;
+    if (int brc = inducing_descend_begin(h, s, r, b.o, theta_raw, Xu, n_ell, steps, eta, beta1, beta2, eps, opt_state)) return brc;
+    h->n_ell = n_ell;
+    h->params_src = h->dTrainParams;
+    h->in_flight = true;
+    const bool multi = h->dout > 1;
+    const double* Rv = h->dR;
+    int rc = theta_Rv(h, s, &Rv);                             // R_v: once per call, q(v) is held
+    const double* scal = h->dStats + (size_t)h->Mp * h->Mp + (size_t)h->Mp * h->dout;
+    for (int k = 0; k < steps && !rc; ++k) {
+        h->params_gen++;                                       // theta and Xu moved: k_prep_xu mirrors them again
+        rc = enqueue_restats(h, s);
+        if (!rc) {
+            if (multi) rc = enqueue_theta_multi_value(h, s, Rv);
+            else enqueue_theta_uni_sums(h, s, Rv);
+        }
+        if (!rc) rc = enqueue_theta_grad(h, s, Rv, true);
+        if (!rc) {
+            enqueue_xu_grad(h, s, b.g, nranges, range_len);
+            hipLaunchKernelGGL(k_inducing_step, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)h->dGrad, (const double*)h->dOut2, scal,
+                               (const Params*)h->dParams, (const int*)h->dInfo, (const int*)(h->dInfo + 3), b.o.Vals, k, h->dTrainParams,
+                               h->D, n_ell, multi ? 1 : 0, r.learn ? 1 : 0, b.o.Pub);
+            launch_inducing_step_xu(h, s, r, b.o, b.g.Grad, beta1, beta2, eps);
+        }
+    }
+    // whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path
+    const hipError_t werr = wait_stream(s);
+    const hipError_t lerr = hipGetLastError();
+    h->params_src = h->hParams;
+    h->in_flight = false;
+    h->params_gen++;
+    h->data_gen++;                                             // the inducing inputs moved, as after sgp_set_inducing
+    stats_drop(h, STATS_REUSE | STATS_QV);                     // the resident statistics belong to the last evaluated (theta, Xu)
+    h->swept_local = false;
+    if (rc) return rc;
+    HIPCHK(h, werr);
+    HIPCHK(h, lerr);
+    TrainState st;
+    if (int erc = inducing_descend_end(h, r, b.o, theta_raw, Xu, steps, opt_state, values, &st)) return erc;
+    if (counts) { counts[0] = (int64_t)st.steps; counts[1] = st.stop > 0.0 ? (int64_t)st.stop : 0; }
+    if (int src = check_sync_status(h)) return src;
+    if (st.stop != 0.0)
+        return factor_status(h, (int)st.stop, (std::string(name) + ", step " + std::to_string((int64_t)st.steps) + ": K_uu").c_str());
+    return 0;
+}
+
+// Per step on the library's own stream: psi_theta_enqueue at the descent's device parameter block and psi_xu_enqueue behind it, as
+// theta_objective_psi_call chains them -- without the host's look at the status words in between: a failed evaluation's second pass
+// works on whatever the first left (a failed node writes zeros, the shapes fix every index) and k_inducing_step_psi discards it --, then
+// the two optimiser launches.  Everything but dXu, the optimiser state and the chain's mirror stays in call scratch.
+extern "C" int sgp_inducing_descend_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
+                                        double* theta_raw, int32_t n_ell, double* Xu, int32_t flags, int32_t steps, double eta,
+                                        double beta1, double beta2, double eps, double* opt_state, double* values, int64_t* counts) {
+    const char* name = "sgp_inducing_descend_psi";
+    InducingRun r;
+    if (int rc = inducing_descend_args(h, name, theta_raw, n_ell, Xu, flags, steps, eta, beta1, beta2, opt_state, &r)) return rc;
+    if (!mean || !y_mean) return refuse(h, name, "null argument");
+    if (n_nodes < 1) return refuse(h, name, "n_nodes must be >= 1");
+    if (int rc = psi_theta_ready(h, name, mean, cov, y_mean, n_nodes)) return rc;      // (refuses an open run: dTrain below is its state)
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    if (steps == 0) return 0;                                  // (behind every refusal, as in sgp_inducing_descend)
+    if (int wrc = sync_checked(h)) return wrc;
+    hipStream_t s = h->own;
+    if (!h->dTrain) {
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
+    }
+    const bool has_cov = cov != nullptr;
+    const PointShape shape = point_shape(h, 3 * (int64_t)h->D * h->Mp + h->D + 1, n_nodes, n_nodes);
+    int nranges = 0;
+    int64_t range_len = 0;
+    psi_ranges(shape.n, h->ntiles, &nranges, &range_len);
+    PsiInducingDescendScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) {
+            layout_psi_inducing_descend(c, shape, h->M, has_cov, (size_t)nranges, GRAD_SLOTS, PSI_TP_SLOTS, INDUCING_PUB, (size_t)steps, &b);
+        })) return crc;
+    if (int rc = psi_theta_upload(h, b.g, mean, cov, y_mean, n_nodes)) return rc;
+    if (int brc = inducing_descend_begin(h, s, r, b.o, theta_raw, Xu, n_ell, steps, eta, beta1, beta2, eps, opt_state)) return brc;
+    h->in_flight = true;
+    const MeanW w(h);
+    const double* Rv = h->dR;
+    int rc = theta_Rv(h, s, &Rv);                             // R_v: once per call, q(v) is held
+    for (int k = 0; k < steps && !rc; ++k) {
+        rc = psi_theta_enqueue(h, s, b.g, shape, has_cov, h->dTrainParams, Rv, w, n_ell);
+        if (!rc) rc = psi_xu_enqueue(h, s, b.g, shape, has_cov, w);
+        if (!rc) {
+            hipLaunchKernelGGL(k_inducing_step_psi, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)b.g.Out, (const int*)b.g.Info,
+                               (const int*)b.g.Status, b.o.Vals, k, h->dTrainParams, h->D, n_ell, r.learn ? 1 : 0, b.o.Pub);
+            launch_inducing_step_xu(h, s, r, b.o, b.g.GradXu, beta1, beta2, eps);
+        }
+    }
+    // whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path
+    const hipError_t werr = wait_stream(s);
+    const hipError_t lerr = hipGetLastError();
+    h->in_flight = false;
+    h->params_gen++;
+    h->data_gen++;                                             // the inducing inputs moved, as after sgp_set_inducing: the statistics on
+    stats_drop(h, STATS_REUSE);                                // the device (not written here) are no longer those of the handle's Xu
+    if (rc) return rc;
+    HIPCHK(h, werr);
+    HIPCHK(h, lerr);
+    TrainState st;
+    if (int erc = inducing_descend_end(h, r, b.o, theta_raw, Xu, steps, opt_state, values, &st)) return erc;
+    h->n_ell = n_ell;
     const int node = st.stop <= -2.0 ? (int)(-st.stop - 1.0) : 0;
     const int kuu = st.stop <= -2.0 ? 0 : (int)st.stop;
     if (counts) { counts[0] = (int64_t)st.steps; counts[1] = kuu > 0 ? kuu : 0; counts[2] = node; }

@@ -5282,6 +5282,77 @@ __global__ void k_descend_step_psi(TrainState* __restrict__ st, const double* __
     write_kernel_params(st, src, D, n_ell);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The optimiser step of sgp_inducing_descend / sgp_inducing_descend_psi: AdaMax on x = [theta_raw | vec Xu] in two
+// launches.  The scalar launch (one wave, lane 0 works) is k_descend_step / k_descend_step_psi with two additions: with
+// `learn_theta` = 0 theta, its moments and the kernel parameters stay and only the running powers and the step count advance; and it
+// PUBLISHES what the elementwise launch behind it needs -- pub[0] = 1 when this step is taken, 0 when the descent has stopped (now
+// or earlier); pub[1] = eta / (1 - beta1^t) with the power as it stood BEFORE this step.  k_inducing_step_xu runs behind it on the
+// same stream, reads those two words and nothing else of the optimiser's state, and updates the M D inducing coordinates in place:
+// every thread sees the same stop decision and the same step size because both were written by an earlier launch.  No atomics;
+// one thread per coordinate, so identical calls agree bitwise.
+// ------------------------------------------------------------------------------------------------
+constexpr int INDUCING_PUB = 2;             // doubles the scalar launch publishes
+__device__ __forceinline__ void inducing_scalar_step(TrainState* __restrict__ st, const double* __restrict__ grad, int learn_theta,
+                                                     double* __restrict__ pub, Params* __restrict__ src, int D, int n_ell) {
+    pub[0] = 1.0;
+    pub[1] = st->eta / (1.0 - st->bp[0]);
+    if (learn_theta) {
+        adamax_step(st, grad, 1.0, n_ell);
+        write_kernel_params(st, src, D, n_ell);
+    } else {
+        st->bp[0] *= st->beta1;
+        st->bp[1] *= st->beta2;
+        st->steps += 1.0;
+    }
+}
+
+// point objective: the value and the stop conditions of k_descend_step
+__global__ void k_inducing_step(TrainState* __restrict__ st, const double* __restrict__ grad, const double* __restrict__ out,
+                                const double* __restrict__ stats_scal, const Params* __restrict__ P, const int* __restrict__ info_kuu,
+                                const int* __restrict__ sync_status, double* __restrict__ values, int k, Params* __restrict__ src,
+                                int D, int n_ell, int multi, int learn_theta, double* __restrict__ pub) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    pub[0] = 0.0;
+    if (st->stop != 0.0) return;
+    const int info = *info_kuu, late = *sync_status;
+    if (info != 0 || late != 0) {
+        st->stop = info != 0 ? (double)info : -1.0;
+        return;
+    }
+    values[k] = multi ? grad[GRAD_SLOTS] : 0.5 * P->W[0] * (out[0] + out[1] - stats_scal[0]);   // SGP_R_SUM_I1, _I2, SGP_S_YY
+    inducing_scalar_step(st, grad, learn_theta, pub, src, D, n_ell);
+}
+
+// exact-Psi objective: the value and the stop conditions of k_descend_step_psi
+__global__ void k_inducing_step_psi(TrainState* __restrict__ st, const double* __restrict__ grad, const int* __restrict__ info_kuu,
+                                    const int* __restrict__ node_status, double* __restrict__ values, int k, Params* __restrict__ src,
+                                    int D, int n_ell, int learn_theta, double* __restrict__ pub) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    pub[0] = 0.0;
+    if (st->stop != 0.0) return;
+    const int node = *node_status, info = *info_kuu;
+    if (node != 0) { st->stop = -1.0 - (double)node; return; }
+    if (info != 0) { st->stop = info > 0 ? (double)info : -1.0; return; }
+    values[k] = grad[GRAD_SLOTS];
+    inducing_scalar_step(st, grad, learn_theta, pub, src, D, n_ell);
+}
+
+// The elementwise half: Xu (M x D, as sgp_set_inducing takes it) moves by the raw gradient `grad_xu`; mom = [m (count) | u (count)].
+// grid = ceil(count / 256).
+__global__ void __launch_bounds__(256) k_inducing_step_xu(const double* __restrict__ pub, const double* __restrict__ grad_xu,
+                                                          double* __restrict__ Xu, double* __restrict__ mom, int count, double beta1,
+                                                          double beta2, double eps) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count || pub[0] == 0.0) return;
+    const double g = grad_xu[i];
+    const double m = beta1 * mom[i] + (1.0 - beta1) * g;
+    const double u = fmax(beta2 * mom[count + i], fabs(g));
+    mom[i] = m;
+    mom[count + i] = u;
+    Xu[i] = Xu[i] - pub[1] * m / (u + eps);
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // The exact-Psi input messages (sgp_psi_in_grad): per node t with input x_t ~ N(m_t, S_t) the part of its average

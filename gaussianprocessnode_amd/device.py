@@ -576,6 +576,68 @@ class SGPDevice:
             self._n_ell = n_ell
         return th, values, int(counts[0]), st
 
+    # -- device-paced descent in the inducing inputs (sgp_inducing_descend, sgp_inducing_descend_psi) ---------------------------
+    def _inducing_args(self, what: str, theta, Xu, steps, learn_theta: bool, beta, state):
+        th = np.array(theta, dtype=np.float64).reshape(-1)
+        Z = np.array(np.reshape(Xu, (self.M, self.D)), dtype=np.float64, order="C")
+        P = (th.size if learn_theta else 0) + Z.size
+        if state is None:
+            st = np.concatenate([np.zeros(2 * P), np.asarray(beta, dtype=np.float64)])
+        else:
+            st = np.array(state, dtype=np.float64).reshape(-1)
+            if st.size != 2 * P + 2:
+                raise ValueError(f"{what}: state needs 2 P + 2 = {2 * P + 2} entries for P = {P} optimised parameters, got {st.size}")
+        flags = _lib.SGP_DESCEND_XU | (_lib.SGP_DESCEND_THETA if learn_theta else 0)
+        return th, Z, st, flags, np.empty(max(int(steps), 0))
+
+    def _inducing_result(self, what: str, rc: int, counts, th, Z, values, st, steps: int, psi: bool):
+        if rc > 0:
+            self._n_ell = th.size - 1
+            node = int(counts[2]) if psi else 0
+            if node > 0:
+                msg = self._lib.sgp_last_error(self._h)
+                err = _lib.PosDefException(rc, f"{what} {msg.decode() if msg else ''}")
+            else:
+                err = np.linalg.LinAlgError(f"{what}: K_uu is not positive definite at step {int(counts[0])} (leading minor {rc}); "
+                                            f"theta, Xu and the optimiser state are those of that step")
+            err.minor, err.node = int(counts[1]), node
+            err.theta, err.Xu, err.values, err.steps_taken, err.state = th, Z, values, int(counts[0]), st
+            raise err
+        self._check(rc, what)
+        if steps > 0:
+            self._n_ell = th.size - 1
+        return th, Z, values, int(counts[0]), st
+
+    def inducing_descend(self, theta, Xu, steps: int, *, learn_theta: bool = True, eta: float = 1e-3, beta=(0.9, 0.999),
+                         eps: float = 1e-8, state=None):
+        """`steps` AdaMax steps on [theta | vec Xu] -- theta raw (pre-softplus, sigma2 first), Xu (M, D) -- or, learn_theta=False, on
+        Xu alone with the kernel held at softplus(theta), paced by the device (sgp_inducing_descend): per step the objective of
+        `theta_objective_xu` is re-evaluated at (softplus(theta), Xu) with q(v), data and noise held; the host waits once.  `state`:
+        the optimiser state [m | u | beta1^t, beta2^t] of the joint vector (`train.AdaMax.get_state`'s layout; None: zero moments).
+        Returns (theta, Xu, values, steps_taken, state) -- values[k] the objective at step k's parameters.  Afterwards the handle's
+        kernel is softplus(theta) and its inducing inputs are Xu, both as returned; q(v) stays installed.  A K_uu that is not
+        positive definite at some step raises LinAlgError as `theta_descend` does, carrying `minor`, `theta`, `Xu`, `values` (NaN
+        from that step on), `steps_taken`, `state`."""
+        th, Z, st, flags, values = self._inducing_args("inducing_descend", theta, Xu, steps, learn_theta, beta, state)
+        counts = (C.c_int64 * 2)()
+        rc = self._lib.sgp_inducing_descend(self._h, ptr(th), th.size - 1, ptr(Z), flags, int(steps), float(eta), float(beta[0]),
+                                            float(beta[1]), float(eps), ptr(st), ptr(values), counts)
+        return self._inducing_result("inducing_descend", rc, counts, th, Z, values, st, int(steps), False)
+
+    def inducing_descend_psi(self, mean, cov, y_mean, theta, Xu, steps: int, *, learn_theta: bool = True, eta: float = 1e-3,
+                             beta=(0.9, 0.999), eps: float = 1e-8, state=None):
+        """`inducing_descend` on the objective of `theta_objective_psi_xu` (sgp_inducing_descend_psi; SE only): the Gaussian inputs,
+        the targets, q(v) and the noise are held.  Returns (theta, Xu, values, steps_taken, state).  An indefinite covariance at
+        node t raises PosDefException with info = t + 1, a K_uu that is not positive definite LinAlgError; either carries `theta`,
+        `Xu`, `values`, `steps_taken`, `state`, `minor` and `node`."""
+        m, S, T = self._node_gaussians("inducing_descend_psi", mean, cov)
+        y_cm = self._node_targets(y_mean, T)
+        th, Z, st, flags, values = self._inducing_args("inducing_descend_psi", theta, Xu, steps, learn_theta, beta, state)
+        counts = (C.c_int64 * 3)()
+        rc = self._lib.sgp_inducing_descend_psi(self._h, ptr(m), ptr(S), ptr(y_cm), T, ptr(th), th.size - 1, ptr(Z), flags, int(steps),
+                                                float(eta), float(beta[0]), float(beta[1]), float(eps), ptr(st), ptr(values), counts)
+        return self._inducing_result("inducing_descend_psi", rc, counts, th, Z, values, st, int(steps), True)
+
     def psi_in_grad(self, mean, cov, y_mean, want_energy: bool = True, want_cov: bool = True):
         """The exact-Psi input messages of T nodes with Gaussian inputs N(mean[t], cov[t]) at the current kernel (sgp_psi_in_grad; SE
         only, D <= 8): U_t = 1/2 tr(G Psi2_t) - s_t' Psi1_t, the part of node t's average energy that depends on its input, with

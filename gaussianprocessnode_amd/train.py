@@ -21,6 +21,7 @@ class AdaMax:
     beta: tuple = (0.9, 0.999)
     eps: float = 1e-8
     _state: dict = field(default_factory=dict, repr=False)
+    _named: dict = field(default_factory=dict, repr=False)
 
     def update(self, x: np.ndarray, grad: np.ndarray) -> np.ndarray:
         st = self._state.setdefault(id(x), dict(m=np.zeros_like(x), u=np.zeros_like(x), bp=np.array(self.beta, dtype=float)))
@@ -46,6 +47,21 @@ class AdaMax:
         if flat.size != 2 * n + 2:
             raise ValueError(f"AdaMax.set_state: {2 * n + 2} entries expected for {n} parameters, got {flat.size}")
         self._state[id(x)] = dict(m=flat[:n].reshape(x.shape).copy(), u=flat[n:2 * n].reshape(x.shape).copy(), bp=flat[2 * n:].copy())
+
+    def get_named_state(self, key, n: int) -> np.ndarray:
+        """The state kept under the name `key` for a vector of `n` parameters, in `get_state`'s layout (fresh -- zero moments, the
+        powers (beta1, beta2) -- when none is kept).  Unlike `get_state` it does not depend on which array object holds the
+        parameters.  A kept state of another size is an error, never a silent restart."""
+        flat = self._named.get(key)
+        if flat is None:
+            return np.concatenate([np.zeros(2 * n), np.array(self.beta, dtype=float)])
+        if flat.size != 2 * n + 2:
+            raise ValueError(f"AdaMax: the state kept under {key!r} is for {(flat.size - 2) // 2} parameters, not {n}: "
+                             f"use a fresh optimizer for another problem")
+        return flat.copy()
+
+    def set_named_state(self, key, flat) -> None:
+        self._named[key] = np.array(flat, dtype=np.float64).reshape(-1)
 
 
 def sigmoid(x):
@@ -341,8 +357,11 @@ def optimize_theta(theta, engine, *, steps: int = 100, optimizer=None):
     return _descend(theta, engine, int(steps), opt)
 
 
+INDUCING_STATE = "optimize_inducing"      # the name `optimize_inducing(device_paced=True)` keeps its joint state under (AdaMax.get_named_state)
+
+
 def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=None, learn_theta: bool = True, jitter: float = 0.0,
-                      psi: str = "cubature", inputs=None):
+                      psi: str = "cubature", inputs=None, device_paced: bool = False):
     """`steps` host-paced AdaMax steps on the objective of `theta_objective` in the inducing inputs -- on [theta | vec Xu] together,
     or on Xu alone with learn_theta=False -- over an `engine` (SGPDevice) that has data, noise and a kernel family, with q(v) held
     for the whole call.  theta is raw (pre-softplus, sigma2 first, 1 or D lengthscales); Xu is (M, D); q_v is (mu_v, Uv) as
@@ -360,7 +379,17 @@ def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=Non
     loop in it.
 
     psi="exact" with inputs=(mean, cov, y_mean) as `theta_objective_psi` takes them: the same loop on the objective over the exact
-    Psi-statistics of the Gaussian inputs (SE kernel only), one `theta_objective_psi_xu` per step; no resident data are needed."""
+    Psi-statistics of the Gaussian inputs (SE kernel only), one `theta_objective_psi_xu` per step; no resident data are needed.
+
+    device_paced=True: set_kernel, set_inducing and set_posterior run ONCE, then one `inducing_descend` (psi="exact":
+    `inducing_descend_psi`) call takes all the steps on the device and the host waits once.  The same (theta, Xu, values) come
+    back (new arrays), but the engine ends AT the returned parameters, whereas the host-paced engine ends one update behind them.
+    The optimiser's state for the joint vector x = [theta | vec Xu] (vec Xu with learn_theta=False) is read from and written back
+    to `optimizer` under the name INDUCING_STATE (`optimizer.get_named_state(INDUCING_STATE, x.size)`), so successive device-paced
+    calls with one optimizer continue one optimiser whatever array objects carry theta and Xu; an optimizer that holds such a
+    state for another number of parameters raises ValueError.  To continue on the host, install it for the joint array:
+    `optimizer.set_state(x, optimizer.get_named_state(INDUCING_STATE, x.size))`; to hand host-paced moments to the device,
+    `optimizer.set_named_state(INDUCING_STATE, optimizer.get_state(x))`."""
     if psi not in ("cubature", "exact"):
         raise ValueError(f"optimize_inducing: psi must be 'cubature' or 'exact', got {psi!r}")
     if psi == "exact":
@@ -384,6 +413,18 @@ def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=Non
     opt = optimizer if optimizer is not None else AdaMax()
     nt = theta.size if learn_theta else 0
     x = np.concatenate([theta[:nt], Xu.ravel()])
+    if device_paced:
+        kw = dict(learn_theta=learn_theta, eta=opt.eta, beta=opt.beta, eps=opt.eps, state=opt.get_named_state(INDUCING_STATE, x.size))
+        p = softplus(theta)
+        engine.set_kernel(float(p[0]), p[1:], jitter)
+        engine.set_inducing(Xu)
+        engine.set_posterior(mu_v, Uv)
+        if psi == "exact":
+            th, Z, values, _, state = engine.inducing_descend_psi(*inputs, theta, Xu, int(steps), **kw)
+        else:
+            th, Z, values, _, state = engine.inducing_descend(theta, Xu, int(steps), **kw)
+        opt.set_named_state(INDUCING_STATE, state)
+        return (np.array(th, dtype=np.float64).reshape(-1) if learn_theta else theta), np.array(Z, dtype=np.float64).reshape(M, D), values
     values = np.empty(max(int(steps), 0))
     for k in range(int(steps)):
         th = x[:nt] if learn_theta else theta

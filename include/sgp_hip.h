@@ -568,6 +568,39 @@ int sgp_theta_objective_psi_xu(sgp_handle* h, const double* mean /* D x T */, co
                                double* grad /* 1 + n_ell, may be NULL */, double* grad_xu /* M x D as sgp_set_inducing takes Xu */,
                                int64_t* info /* 2, may be NULL */);
 
+/* ---- device-paced AdaMax descent in the inducing inputs at a held q(v) ----
+ * sgp_inducing_descend is sgp_theta_descend, and sgp_inducing_descend_psi is sgp_theta_descend_psi, on the vector
+ *     x = [theta_raw | vec Xu]   (flags = SGP_DESCEND_THETA | SGP_DESCEND_XU, P = 1 + n_ell + M D)   or
+ *     x = vec Xu                 (flags = SGP_DESCEND_XU: theta held at softplus(theta_raw), P = M D)
+ * with Xu (M x D, as sgp_set_inducing takes it) in/out.  Per step k, on the library's own stream with no host wait: the objective and
+ * its theta gradient at (softplus(theta_k), Xu_k) as those calls form them, the gradient in Xu as sgp_theta_objective_xu /
+ * sgp_theta_objective_psi_xu form it, values[k] = f(theta_k, Xu_k), and one AdaMax step -- theta entries through the softplus chain
+ * rule, Xu entries raw.  opt_state = [m (P) | u (P) | beta1^t, beta2^t] for the joint vector (NULL: zero moments, powers beta): host-
+ * and device-paced steps continue one optimiser in any mix.  No atomics, fixed orders: identical calls agree bitwise, and k steps then
+ * steps - k through opt_state equal one call.
+ *
+ * A K_uu that is not positive definite (or, _psi, an indefinite node) at step k stops the descent as in sgp_theta_descend[_psi]: theta,
+ * Xu, the moments and the powers stay those of step k, values[k ..] are NaN, the call returns the positive status; counts as there
+ * (2 resp. 3 entries).
+ *
+ * Afterwards the handle's kernel is softplus(theta_out) and its inducing inputs are Xu_out; q(v), data, noise and prior are untouched and
+ * q(v) stays usable (sgp_theta_objective[_xu] evaluates at (theta_out, Xu_out) without a sgp_set_posterior).  The next sgp_sweep is
+ * SGP_SWEEP_FULL.  sgp_inducing_descend drops the resident statistics as sgp_theta_descend does; the _psi call writes none of them:
+ * what sgp_get_stats / sgp_sweep_finish then read are the statistics of the OLD inducing inputs -- stale, and no longer reusable.
+ * After a negative return the handle's inducing inputs are undefined: upload them again.
+ *
+ * SGP_ERR_ARG: everything sgp_theta_descend resp. sgp_theta_descend_psi refuses; flags without SGP_DESCEND_XU or with unknown bits; a
+ * NULL Xu; a non-finite Xu or theta_raw; an installed all-reduce hook.  steps == 0 returns 0 with nothing changed, behind every refusal. */
+enum { SGP_DESCEND_THETA = 1, SGP_DESCEND_XU = 2 };
+int sgp_inducing_descend(sgp_handle* h, double* theta_raw /* 1 + n_ell, in/out */, int32_t n_ell,
+                         double* Xu /* M x D as sgp_set_inducing takes it, in/out */, int32_t flags, int32_t steps, double eta,
+                         double beta1, double beta2, double eps, double* opt_state /* 2 P + 2, in/out, may be NULL */,
+                         double* values /* steps, may be NULL */, int64_t* counts /* 2, may be NULL */);
+int sgp_inducing_descend_psi(sgp_handle* h, const double* mean /* D x T */, const double* cov /* D x D x T or NULL */,
+                             const double* y_mean /* T x d_out */, int64_t n_nodes, double* theta_raw, int32_t n_ell, double* Xu,
+                             int32_t flags, int32_t steps, double eta, double beta1, double beta2, double eps, double* opt_state,
+                             double* values, int64_t* counts /* 3, may be NULL */);
+
 /* ---- exact-Psi input messages: a node's energy and its derivatives in the mean and covariance of its Gaussian input ----
  * With q(v), W, G and s_t as for sgp_theta_objective_psi (SGP_KERNEL_SE only, d_out = 1 .. 4, D <= 8) and x_t ~ N(m_t, S_t), the part of
  * node t's average energy that depends on its input is

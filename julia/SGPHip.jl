@@ -34,7 +34,7 @@ import ReactiveMP: @rule, @average_energy, @call_rule, GenericProd, PointMass, M
                    mean_var, AverageEnergy, ContinuousUnivariateLogPdf, ContinuousMultivariateLogPdf, UnspecifiedDomain
 import ..UniSGP, ..UniSGPMeta, ..MultiSGP, ..MultiSGPMeta, ..WishartFast, ..approximate_kernel_expectation!
 
-export HipSGPMeta, HipMultiSGPMeta, predict, predictive, theta_objective, theta_objective_xu, theta_objective_psi_xu, carry_posterior!, multisgp_sweep!
+export HipSGPMeta, HipMultiSGPMeta, predict, predictive, theta_objective, theta_objective_xu, theta_objective_psi_xu, inducing_descend!, inducing_descend_psi!, carry_posterior!, multisgp_sweep!
 
 const LIB = get(ENV, "SGP_HIP_LIB", "libsgp_hip.so")
 
@@ -598,6 +598,39 @@ function theta_descend_psi!(meta::HipSGPMeta, m::Matrix{Float64}, S, y::Matrix{F
                 h.ptr, m, S === nothing ? C_NULL : S, y, size(m, 2), θ, length(θ) - 1, steps, η, β[1], β[2], ϵ,
                 state === nothing ? C_NULL : state, values, counts), h.ptr)
     return θ, values, Int(counts[1])
+end
+
+# Device-paced AdaMax in the inducing inputs at a held q(v) (sgp_inducing_descend, sgp_inducing_descend_psi): on [θ | vec Xu], or on
+# Xu alone with learn_theta = false.  Xu is D × M (column m is inducing point m: the memory layout sgp_set_inducing takes); θ and Xu are
+# updated in place.  state: [m | u | β1^t, β2^t] of the joint vector, 2 P + 2 entries with P = (learn_theta ? length(θ) : 0) + D M.
+# Returns (θ, Xu, values, steps taken); afterwards the handle's kernel is softplus(θ) and its inducing inputs are Xu.
+function inducing_descend!(meta::HipSGPMeta, θ::Vector{Float64}, Xu::Matrix{Float64}, steps::Integer; learn_theta::Bool = true,
+                           η = 1e-3, β = (0.9, 0.999), ϵ = 1e-8, state::Union{Nothing, Vector{Float64}} = nothing)
+    h = meta.handle
+    P = (learn_theta ? length(θ) : 0) + length(Xu)
+    state === nothing || length(state) == 2 * P + 2 || throw(ArgumentError("inducing_descend!: state needs 2 P + 2 entries"))
+    values = fill(NaN, max(steps, 0)); counts = zeros(Int64, 2)
+    check(ccall((:sgp_inducing_descend, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Int32, Float64, Float64, Float64, Float64, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Int64}),
+                h.ptr, θ, length(θ) - 1, Xu, learn_theta ? 3 : 2, steps, η, β[1], β[2], ϵ, state === nothing ? C_NULL : state, values,
+                counts), h.ptr)
+    return θ, Xu, values, Int(counts[1])
+end
+
+function inducing_descend_psi!(meta::HipSGPMeta, m::Matrix{Float64}, S, y::Matrix{Float64}, θ::Vector{Float64}, Xu::Matrix{Float64},
+                               steps::Integer; learn_theta::Bool = true, η = 1e-3, β = (0.9, 0.999), ϵ = 1e-8,
+                               state::Union{Nothing, Vector{Float64}} = nothing)
+    h = meta.handle
+    P = (learn_theta ? length(θ) : 0) + length(Xu)
+    state === nothing || length(state) == 2 * P + 2 || throw(ArgumentError("inducing_descend_psi!: state needs 2 P + 2 entries"))
+    values = fill(NaN, max(steps, 0)); counts = zeros(Int64, 3)
+    check(ccall((:sgp_inducing_descend_psi, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Int32, Float64,
+                 Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, m, S === nothing ? C_NULL : S, y, size(m, 2), θ, length(θ) - 1, Xu, learn_theta ? 3 : 2, steps, η, β[1], β[2], ϵ,
+                state === nothing ? C_NULL : state, values, counts), h.ptr)
+    return θ, Xu, values, Int(counts[1])
 end
 
 # ---- the exact-Psi input messages (sgp_psi_in_grad; SE kernel only, D <= 8): per node t with input x_t ~ N(m_t, S_t) the part U_t of its

@@ -1,8 +1,8 @@
 // Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over grids of shapes, the
-// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad and layout_psi_theta_xu hand out are
+// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad, layout_psi_theta_xu, layout_inducing_descend and layout_psi_inducing_descend hand out are
 // pairwise disjoint at the sizes their consumers need (stated here independently of the layout functions), every piece starts a
 // multiple of Carver::ALIGN doubles from the base, pass 2 hands out the total pass 1 summed and the last piece ends there.  The
-// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad and layout_psi_theta_xu get an allocation of
+// panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad, layout_psi_theta_xu and the two inducing-descent layouts get an allocation of
 // exactly their total per shape and every piece is written end to end, so that the sanitizer sees a write past it.  No GPU:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o tools/point_scratch_check tools/point_scratch_check.cpp
 //   (or any C++17 compiler with -fsanitize=address,undefined) && tools/point_scratch_check
@@ -378,6 +378,72 @@ long psi_theta_xu_sweep() {
                         }
     return shapes;
 }
+// sgp_inducing_descend and sgp_inducing_descend_psi over their grids, each shape in an allocation of its own: the objective's pieces
+// (as the two sweeps above state them) and the optimiser's -- the inducing coordinates' two moments, the two published words and the
+// values of the steps
+long inducing_descend_sweep() {
+    long shapes = 0;
+    const size_t slots = 33, tile_slots = 65, pub = 2;        // GRAD_SLOTS, PSI_TP_SLOTS, INDUCING_PUB
+    for (int M : {1, 20, 65, 130, 600})
+        for (int D : {1, 2, 5, 12, 32})
+            for (size_t steps : {(size_t)1, (size_t)15, (size_t)1000}) {
+                const int Mp = (M + TB - 1) / TB * TB, T = Mp / TB, ntiles = T * (T + 1) / 2;
+                for (int64_t n : {(int64_t)0, (int64_t)150, (int64_t)8193, (int64_t)100000}) {
+                    const int64_t nblk = (n + TB - 1) / TB, want = std::max<int64_t>(1, std::min<int64_t>(nblk, std::max(1, 256 / T)));
+                    const int64_t len = std::max<int64_t>(1, (nblk + want - 1) / want);
+                    const size_t ranges = (size_t)((nblk + len - 1) / len);
+                    const PointShape s{Mp, 0, T, D, 1, POTRF_SCRATCH, 64, n, n};
+                    check("inducing_descend", s, 0, nullptr, 0, true, [&](Carver& c) {
+                        InducingDescendScratch b;
+                        layout_inducing_descend(c, s, M, ranges, pub, steps, &b);
+                        const std::vector<Piece> all = {{"PartUF", b.g.PartUF, ranges * Mp * D * d}, {"PartUU", b.g.PartUU, (size_t)T * Mp * D * d},
+                                                        {"Grad", b.g.Grad, (size_t)M * D * d}, {"Mom", b.o.Mom, 2 * (size_t)M * D * d},
+                                                        {"Pub", b.o.Pub, pub * d}, {"Vals", b.o.Vals, steps * d}};
+                        std::vector<Piece> p;
+                        for (const Piece& q : all)
+                            if (q.bytes) p.push_back(q);
+                        return p;
+                    });
+                    ++shapes;
+                }
+                if (M > 130) continue;
+                for (int dout : {1, 3})
+                    for (int64_t n : {1, 60, 300})
+                        for (int64_t chunk : {(int64_t)64, (n + 63) / 64 * 64})
+                            for (int opt = 0; opt < 2; ++opt) {
+                                const bool cov = opt & 1;
+                                const int64_t want = std::min<int64_t>((n + 7) / 8, std::max(1, 1024 / ntiles)), len = (n + want - 1) / want;
+                                const size_t ranges = (size_t)((n + len - 1) / len), acc = ranges * ntiles;
+                                const PointShape s{Mp, 0, T, D, dout, POTRF_SCRATCH, std::min(chunk, (n + 63) / 64 * 64), n, n};
+                                check("psi_inducing_descend", s, 0, nullptr, 0, true, [&](Carver& c) {
+                                    PsiInducingDescendScratch bb;
+                                    layout_psi_inducing_descend(c, s, M, cov, ranges, slots, tile_slots, pub, steps, &bb);
+                                    const PsiThetaXuScratch& b = bb.g;
+                                    const size_t nn = (size_t)n, ch = (size_t)s.chunk, mm = (size_t)Mp * Mp * d;
+                                    const std::vector<Piece> all = {
+                                        {"Mean", b.Mean, nn * D * d}, {"Cov", b.Cov, cov ? nn * D * D * d : 0}, {"Y", b.Y, nn * dout * d},
+                                        {"Bad", b.Bad, nn * sizeof(int)}, {"Lin", b.Lin, nn * slots * d}, {"G2", b.G2, ch * D * Mp * d},
+                                        {"H2", b.H2, ch * D * Mp * d}, {"E2", b.E2, ch * D * d}, {"Cw", b.Cw, ch * d},
+                                        {"Acc", b.Acc, acc * TB * TB * d}, {"Wd", b.Wd, acc * D * 256 * d},
+                                        {"TilePart", b.TilePart, (size_t)ntiles * tile_slots * d}, {"Kuu", b.Kuu, mm}, {"Wk", b.Wk, mm},
+                                        {"Kinv", b.Kinv, mm}, {"G", b.G, mm}, {"Gpart", b.Gpart, (size_t)Mp * d}, {"Psi2", b.Psi2, mm},
+                                        {"T1", b.T1, mm}, {"H", b.H, mm}, {"PartUU", b.PartUU, (size_t)T * T * slots * d},
+                                        {"Out", b.Out, 2 * slots * d}, {"Status", b.Status, sizeof(int)},
+                                        {"Pscr", b.Pscr, (size_t)POTRF_SCRATCH * d}, {"Info", b.Info, sizeof(int)},
+                                        {"P1", b.P1, ch * D * Mp * d}, {"Part1", b.Part1, ranges * D * Mp * d},
+                                        {"RowPart", b.RowPart, acc * 4 * D * TB * d}, {"ColPart", b.ColPart, acc * D * TB * d},
+                                        {"PartXU", b.PartXU, (size_t)T * T * D * TB * d}, {"GradXu", b.GradXu, (size_t)M * D * d},
+                                        {"Mom", bb.o.Mom, 2 * (size_t)M * D * d}, {"Pub", bb.o.Pub, pub * d}, {"Vals", bb.o.Vals, steps * d}};
+                                    std::vector<Piece> p;
+                                    for (const Piece& q : all)
+                                        if (q.bytes) p.push_back(q);
+                                    return p;
+                                });
+                                ++shapes;
+                            }
+            }
+    return shapes;
+}
 }  // namespace
 
 int main() {
@@ -395,8 +461,9 @@ int main() {
     const long psi_predict = psi_predict_sweep();
     const long xu_grad = xu_grad_sweep();
     const long psi_theta_xu = psi_theta_xu_sweep();
+    const long inducing = inducing_descend_sweep();
     std::printf("%ld shapes x 3 panel layouts (largest total %zu doubles), %ld mean-only shapes, %ld psi shapes, %ld psi-theta shapes, "
-                "%ld psi-in shapes, %ld psi-predict shapes, %ld xu-grad shapes, %ld psi-theta-xu shapes: %ld failure(s)\n", panel, largest,
-                mean_only, psi, psi_theta, psi_in, psi_predict, xu_grad, psi_theta_xu, failures);
+                "%ld psi-in shapes, %ld psi-predict shapes, %ld xu-grad shapes, %ld psi-theta-xu shapes, %ld inducing-descend shapes: %ld failure(s)\n",
+                panel, largest, mean_only, psi, psi_theta, psi_in, psi_predict, xu_grad, psi_theta_xu, inducing, failures);
     return failures ? 1 : 0;
 }

@@ -105,7 +105,9 @@ struct SweepPlan {
 // dStats), the K_uu chain's outputs (dKuu, dWk, dKinv, dSaccK, the log-det in dScratch + POTRF_LOGDET) and q(v).  Written only by the
 // stats_* helpers, read by sgp_theta_objective's fresh path and planned_kind (kernel_matches + what is theirs).  Entry point -> effect:
 //   sgp_set_inducing, sgp_set_data              drop reuse; data_gen++ (new inputs: the objective re-forms the statistics too)
-//   sgp_set_targets / sgp_set_output_cov_sum    targets pending; data_gen++ / data_gen stays as it always has (not settled here)
+//   sgp_set_targets                             targets pending; data_gen++ (B and S_YY feed the objective: it re-forms the statistics)
+//   sgp_set_output_cov_sum                      targets pending; data_gen stays: the objective does not depend on the sum (d_out > 1: it has
+//                                               no y'y term; d_out = 1: the sum enters S_YY and sum I2 alike and cancels), its fresh path stays valid
 //   sgp_set_kernel, sgp_set_kernel_family       nothing: kernel_matches compares values, the same theta set again keeps the statistics
 //   sgp_bind_stats, sgp_set_allreduce/use_rccl  drop reuse (another buffer; this rank's share or the ranks' sum)
 //   sgp_sweep_local                             fills the record, drops reuse (the caller may change the statistics between the halves)
@@ -127,6 +129,8 @@ struct SweepPlan {
 //                                               EVALUATED (theta, Xu)'s; the inducing inputs moved, as after sgp_set_inducing)
 //   sgp_inducing_descend_psi                    drops reuse; data_gen++ (nothing resident was rewritten, but the inducing inputs moved: the
 //                                               statistics on the device are those of the OLD Xu -- stale, though sgp_get_stats still hands them out)
+// A new entry point gets a row here and an entry in MUTATORS / READERS of tests/call_sequence_ref.py, which drives every row in front
+// of every reader (tests/test_gpu_call_sequences.py) and holds the ledger of the exported names (tests/test_call_sequences_host.py).
 struct StatsRecord {
     double sigma2 = 0.0, jitter = 0.0, inv_ell[MAXD] = {0};   // the kernel values they were formed at ...
     int32_t family = SGP_KERNEL_SE;                           // ... and the family

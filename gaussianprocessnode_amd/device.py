@@ -461,6 +461,7 @@ class SGPDevice:
         the isotropic prior of `set_prior_isotropic` back first (the per-epoch reset of the notebooks)."""
         self._check(self._lib.sgp_train_step(self._h, int(offset), int(n), (1 if learn else 0) | (2 if reset_prior else 0)),
                     "sgp_train_step")
+        self.n = int(n)                       # the resident points are the window's now: `w_stats` sizes its outputs by them
 
     def train_end(self):
         """Wait for the queued steps; returns (theta_raw, optimiser steps taken, minibatches skipped)."""

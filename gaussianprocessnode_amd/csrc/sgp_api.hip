@@ -99,7 +99,15 @@ struct SweepPlan {
     bool join_word = false;        // F2 waits on dJoin[WORD_JOIN] inside k_gemm32 instead of on evSide
     bool kuu_interleaved = false;  // the K_uu chain's steps go out alternately with the Lambda chain's (enqueue_finish1)
     bool resident = false;         // the statistics are resident (sweep_resident): an overlapped sweep's column layout, nothing to wait for
+    bool stats_first = false;      // the data-sized kernels were enqueued in front of the K_uu chain (host order only)
+    bool gate_side = false;        // the K_uu chain waits for the SYRK's resident round (the handle's gate_side when the plan was made)
 };
+// the plan as sgp_sweep_plan reports it (SGP_PLAN_* of include/sgp_hip.h)
+static int32_t plan_bits_of(const SweepPlan& p) {
+    return (p.overlapped ? SGP_PLAN_OVERLAPPED : 0) | (p.pack ? SGP_PLAN_PACK : 0) | (p.events ? SGP_PLAN_EVENTS : 0) |
+           (p.join_word ? SGP_PLAN_JOIN_WORD : 0) | (p.kuu_interleaved ? SGP_PLAN_KUU_INTERLEAVED : 0) |
+           (p.stats_first ? SGP_PLAN_STATS_FIRST : 0) | (p.gate_side ? SGP_PLAN_GATE_SIDE : 0) | (p.resident ? SGP_PLAN_RESIDENT : 0);
+}
 
 // What the statistics now on the device belong to: K_uf, the Psi2 / B partials and the assembled statistics (dKuf, dBpart, dSlabs,
 // dStats), the K_uu chain's outputs (dKuu, dWk, dKinv, dSaccK, the log-det in dScratch + POTRF_LOGDET) and q(v).  Written only by the
@@ -156,6 +164,8 @@ struct sgp_handle {
     bool in_flight = false;        // a sweep may still be executing (its streams are non-blocking)
     bool sync_reported = false;    // a getter has reported dInfo[3] (check_sync_status): the next sweep clears it
     hipStream_t last_stream = nullptr;   // the stream the last sweep's tail was enqueued on (sgp_sweep_finish): what stream order covers
+    hipStream_t tail_stream = nullptr;   // the stream the handle's last asynchronous work went to (order_behind); nullptr: the library's own
+    hipEvent_t evOrder = nullptr;        // orders work on one stream behind the handle's earlier work on another (order_behind)
     uint64_t data_gen = 0;         // bumped by set_data / set_inducing / set_targets; recorded by the sweep (stats.data_gen)
     int32_t family = SGP_KERNEL_SE;   // kernel family (sgp_set_kernel_family)
     int n_ell = 1;
@@ -188,6 +198,7 @@ struct sgp_handle {
     long long* dJoin = nullptr;    // device-side join word of the two streams (see UvArgs::join)
     long long join_epoch = 0;
     SweepPlan plan;                // of the last sweep (sweep_local_impl), read by sgp_sweep_finish
+    int32_t plan_bits = 0;         // the same as sgp_sweep_plan reports it: recorded when the plan was made, never recomputed
     bool gate_side = false;        // the K_uu chain waits for the SYRK's resident round (dJoin[2]); the SYRK grid then uses all CUs
     long long grad_epoch = 0;      // dJoin[3]: the K_uu half of the theta gradient is complete (enqueue_theta_grad)
     long long done_epoch = 0;      // dJoin[1]: the last value a sweep's final kernel was told to write (see k_scalars)
@@ -382,6 +393,23 @@ static int sync_all(sgp_handle* h) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, drain_device(h));
     h->in_flight = false;
+    h->tail_stream = nullptr;
+    return 0;
+}
+
+// Work about to be enqueued on `s` reads or overwrites what the handle's earlier asynchronous work touches.  On the same stream,
+// stream order covers that.  On another one -- a sweep on a caller's stream behind one on the library's or the reverse,
+// sgp_sweep_finish on another stream than sgp_sweep_local, sgp_carry_posterior on another stream than its sweep -- nothing did: `s`
+// (and the side stream, whose first kernel would otherwise spin on the done word for as long as the other stream is held up) now
+// waits for an event recorded behind everything the earlier stream holds.  Never on the path of a caller that stays on one stream.
+static int order_behind(sgp_handle* h, hipStream_t s) {
+    hipStream_t tail = h->tail_stream ? h->tail_stream : h->own;
+    if (h->in_flight && tail != s) {
+        HIPCHK(h, hipEventRecord(h->evOrder, tail));
+        HIPCHK(h, hipStreamWaitEvent(s, h->evOrder, 0));
+        if (s != h->side) HIPCHK(h, hipStreamWaitEvent(h->side, h->evOrder, 0));
+    }
+    h->tail_stream = s;
     return 0;
 }
 
@@ -692,7 +720,8 @@ extern "C" int sgp_create(const sgp_config* cfg, sgp_handle** out) {
     if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess ||
         create_low_priority_stream(&h->side) != hipSuccess ||
         hipEventCreateWithFlags(&h->evSide, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->evDone, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&h->evDone, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&h->evOrder, hipEventDisableTiming) != hipSuccess) {
         g_create_error = "stream/event creation failed";
         sgp_destroy(h);
         return SGP_ERR_HIP;
@@ -758,6 +787,7 @@ extern "C" int sgp_destroy(sgp_handle* h) {
     if (h->hMirror) hipHostFree(h->hMirror);
     if (h->evSide) hipEventDestroy(h->evSide);
     if (h->evDone) hipEventDestroy(h->evDone);
+    if (h->evOrder) hipEventDestroy(h->evOrder);
     for (hipEvent_t e : h->evGroup) if (e) hipEventDestroy(e);
     if (h->own) hipStreamDestroy(h->own);
     if (h->side) hipStreamDestroy(h->side);
@@ -1213,6 +1243,7 @@ extern "C" int sgp_carry_posterior(sgp_handle* h, void* stream) {
         return fail(h, SGP_ERR_ARG, "sgp_carry_posterior: call it right after a finished sweep (before sgp_theta_objective)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
+    if (int orc = order_behind(h, s)) return orc;             // (the sweep whose statistics it reads may sit on another stream)
     // in place: Lambda0 += W (x) Psi2, xi0 += vec(B W), entry by entry (no scratch, no copies)
     hipLaunchKernelGGL(k_form_lambda, dim3(h->TQ, h->TQ), dim3(256), 0, s, h->dStats, h->dLambda0, h->dXi0, h->dLambda0, h->dXi0,
                        h->dParams, h->M, h->Mp, h->dout, h->Q, h->Qp, h->prior_form, 0, (int64_t*)nullptr, (int*)nullptr);
@@ -1591,6 +1622,7 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool whole, bool need_d
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     SweepPlan p = sweep_plan(h, stream, whole);
+    if (int orc = order_behind(h, p.stream)) return orc;
     if (int brc = sweep_begin(h)) return brc;
     // The K_uu chain depends on theta and Xu only: it starts on the (low-priority) side stream as soon as the previous
     // sweep has finished with its outputs, runs beside the data-sized kernels, the all-reduce and the Lambda chain, and is
@@ -1619,7 +1651,10 @@ static int sweep_local_impl(sgp_handle* h, void* stream, bool whole, bool need_d
     // (one-shot sgp_sweep on the library's streams: only the K_uu chain's first two kernels go out here, its steps are enqueued
     // alternately with the Lambda chain's by sgp_sweep_finish -- see enqueue_finish1)
     p.kuu_interleaved = whole && h->env_interleave && stats_first && !p.events;
+    p.stats_first = stats_first;
+    p.gate_side = h->gate_side;
     h->plan = p;
+    h->plan_bits = plan_bits_of(p);
     auto enqueue_stats = [&]() -> int {
         if (p.overlapped) {
             if (int orc = enqueue_stats_overlapped(h, p)) return orc;
@@ -1653,9 +1688,14 @@ extern "C" int sgp_sweep_finish(sgp_handle* h, void* stream) {
     if (!h->swept_local) return fail(h, SGP_ERR_ARG, "sgp_sweep_finish: call sgp_sweep_local first");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->own;
-    const SweepPlan p = h->plan;
+    SweepPlan p = h->plan;
     // (a repeated sgp_sweep_finish runs F1 and F2 alone: the statistics are complete and the K_uu chain has gone out)
     h->plan.overlapped = h->plan.kuu_interleaved = false;
+    // Another stream than sgp_sweep_local's: F1 reads the statistics that one holds (and whatever the caller enqueued behind them
+    // there: its own reduce), so `s` waits for it; and a caller's stream may be held up for longer than a bounded spin, so the next
+    // sweep's K_uu chain is told through evDone as well, whatever the local half planned.
+    if (int orc = order_behind(h, s)) return orc;
+    if (s != h->own) p.events = true;
     h->in_flight = true;
     enqueue_finish1(h, s, p);
     HIPCHK(h, hipGetLastError());
@@ -1714,8 +1754,11 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     SweepPlan p = sweep_plan(h, stream, true);
     p.resident = true;
     hipStream_t s = p.stream;
+    if (int orc = order_behind(h, s)) return orc;
     if (int brc = sweep_begin(h)) return brc;
+    p.gate_side = h->gate_side;
     h->plan = p;
+    h->plan_bits = plan_bits_of(p);
     h->plan.overlapped = false;                              // (as after sgp_sweep_finish: a repeated finish runs F1 and F2 alone)
     prep_main(h, s, true, h->dInfo + 1);
     if (targets) {
@@ -1759,6 +1802,13 @@ extern "C" int sgp_sweep(sgp_handle* h, void* stream) {
     if (rc) return rc;
     h->last_kind = SGP_SWEEP_FULL;
     if ((h->cfg.flags & SGP_FLAG_REUSE_STATS) && !h->training) stats_reusable(h);   // this sweep formed the statistics of the resident inputs
+    return 0;
+}
+
+// the plan the last sgp_sweep / sgp_sweep_local / sgp_sweep_local_psi made (SGP_PLAN_*): what was recorded then, nothing recomputed
+extern "C" int sgp_sweep_plan(const sgp_handle* h, int32_t* bits) {
+    if (!h || !bits) return SGP_ERR_ARG;
+    *bits = h->plan_bits;
     return 0;
 }
 

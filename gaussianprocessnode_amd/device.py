@@ -259,9 +259,9 @@ class SGPDevice:
         self._check(self._lib.sgp_get_wishart_invscale(self._h, ptr(S)), "sgp_get_wishart_invscale")
         return S.T.copy()
 
-    def w_stats(self):
+    def w_stats(self, stream: int = 0):
         I1, I2 = np.empty(self.n), np.empty(self.n)
-        self._check(self._lib.sgp_w_stats(self._h, ptr(I1), ptr(I2), None), "sgp_w_stats")
+        self._check(self._lib.sgp_w_stats(self._h, ptr(I1), ptr(I2), C.c_void_p(stream)), "sgp_w_stats")
         return I1, I2
 
     def predict(self, Xstar, mu_v=None):
@@ -690,6 +690,13 @@ class SGPDevice:
         self._check(self._lib.sgp_overlap_plan(self._h, C.byref(n), info), "sgp_overlap_plan")
         keys = ("col_begin", "col_end", "tiles", "chunks", "points_per_chunk", "masked", "cus", "form_step")
         return [dict(zip(keys, info[8 * g:8 * g + 8])) for g in range(n.value)]
+
+    def sweep_plan(self):
+        """How the last `sweep` / `sweep_local` made its launches meet (sgp_sweep_plan): the set of the names of `_lib.PLAN_BITS`
+        that were on when the library planned it -- recorded then, not recomputed."""
+        bits = C.c_int32()
+        self._check(self._lib.sgp_sweep_plan(self._h, C.byref(bits)), "sgp_sweep_plan")
+        return frozenset(name for name, b in _lib.PLAN_BITS.items() if bits.value & b)
 
     def time_group(self, g: int, iters: int = 20) -> float:
         """Average duration (microseconds, HIP events on the group's own stream) of the SYRK launch of statistics group g."""

@@ -724,6 +724,26 @@ int sgp_time_kernel(sgp_handle* h, int32_t which, int32_t iters, void* stream, d
  * between) then does not have its Lambda chain wait for the host to get through the other chain's 14 launches; once the host is a
  * sweep ahead the order makes no difference (SGP_INTERLEAVE=0: chain after chain).  Same kernels, same results either way. */
 int sgp_overlap_plan(const sgp_handle* h, int32_t* ngroups, int32_t* info /* 8 per group, up to 8 groups; may be NULL */);
+/* sgp_sweep_plan: how the launches of the LAST sgp_sweep / sgp_sweep_local / sgp_sweep_local_psi were made to meet, as the library
+ * recorded it when it planned that sweep (0 before the first one).  Read-only; nothing is recomputed.  Bits:
+ *   OVERLAPPED       the statistics went out in tile-row groups beside the Lambda chain (sgp_overlap_plan)
+ *   PACK             they went to the exchange buffer (an all-reduce hook is installed)
+ *   EVENTS           the sweep's streams meet through events as well as device words: a hook is installed, or `stream` was a caller's
+ *   JOIN_WORD        the Sigma launch polls a device word for the K_uu chain instead of waiting for an event: d_out = 1, no EVENTS,
+ *                    TQ (TQ + 1) / 2 * 4 + TQ^2 <= CUs - 40 workgroups, and this handle is the only one alive in the process
+ *   KUU_INTERLEAVED  the K_uu chain's and the Lambda chain's launches were enqueued alternately: a whole sgp_sweep, STATS_FIRST, no EVENTS
+ *   STATS_FIRST      the data-sized kernels were enqueued in front of the K_uu chain: GATE_SIDE, resident points, no hook
+ *   GATE_SIDE        the K_uu chain waits for the SYRK's resident round: points x lower tiles >= 10 000
+ *   RESIDENT         a sweep over the resident statistics (SGP_SWEEP_TARGETS / SGP_SWEEP_REUSED): no K_uu chain, nothing to join
+ * Streams.  A handle may change streams between calls: a sweep, sgp_sweep_finish or sgp_carry_posterior on another stream than the
+ * handle's last asynchronous call is ordered behind that call by the library (an event wait; none when the stream stays the same).
+ * In particular sgp_sweep_local and sgp_sweep_finish may be given different streams, NULL included: the finish is ordered behind
+ * everything the local half's stream held when sgp_sweep_finish was called -- the caller's own reduce on that stream too.  Work the
+ * caller enqueues on a THIRD stream is the caller's to order.  A caller's stream must stay alive until the work the library put on
+ * it has finished (sgp_wait, or any getter). */
+enum { SGP_PLAN_OVERLAPPED = 1, SGP_PLAN_PACK = 2, SGP_PLAN_EVENTS = 4, SGP_PLAN_JOIN_WORD = 8, SGP_PLAN_KUU_INTERLEAVED = 16,
+       SGP_PLAN_STATS_FIRST = 32, SGP_PLAN_GATE_SIDE = 64, SGP_PLAN_RESIDENT = 128 };
+int sgp_sweep_plan(const sgp_handle* h, int32_t* bits);
 
 #ifdef __cplusplus
 }

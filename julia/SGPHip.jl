@@ -109,6 +109,13 @@ function sweep_kind(h::Handle)
     check(ccall((:sgp_sweep_kind, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), h.ptr, nxt, last), h.ptr)
     return (Int(nxt[]), Int(last[]))
 end
+# the plan of the last sweep as a bit mask (include/sgp_hip.h, sgp_sweep_plan): 1 overlapped, 2 pack, 4 events, 8 join_word,
+# 16 kuu_interleaved, 32 stats_first, 64 gate_side, 128 resident
+function sweep_plan(h::Handle)
+    bits = Ref{Int32}(0)
+    check(ccall((:sgp_sweep_plan, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), h.ptr, bits), h.ptr)
+    return Int(bits[])
+end
 sweep_local!(h::Handle) = check(ccall((:sgp_sweep_local, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), h.ptr, C_NULL), h.ptr)
 wait!(h::Handle) = check(ccall((:sgp_wait, LIB), Cint, (Ptr{Cvoid},), h.ptr), h.ptr)      # polled drain of the handle's streams
 

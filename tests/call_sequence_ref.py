@@ -523,6 +523,7 @@ ENTRY_POINTS = {
         "sgp_train_get_gamma")},
     **{n: NO_STATE for n in (
         "sgp_abi_version", "sgp_create", "sgp_destroy", "sgp_last_error", "sgp_wait", "sgp_stats_layout", "sgp_overlap_plan",
+        "sgp_sweep_plan",              # (reads the bits the last sweep recorded: tests/test_gpu_sweep_plans.py)
         "sgp_kernelmatrix", "sgp_kernelmatrix_family", "sgp_potrf", "sgp_potri", "sgp_measure_sclk_mhz", "sgp_measure_clocks",
         "sgp_get_timestamps", "sgp_get_phase_totals", "sgp_get_chain_trace", "sgp_get_step_trace", "sgp_get_sweep_trace")},
 }

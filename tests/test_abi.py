@@ -30,6 +30,13 @@ def test_library_builds_loads_and_exports_every_symbol():
     assert lib.sgp_abi_version() == 1
 
 
+def test_sweep_plan_refuses_null_arguments_without_a_device():
+    from gaussianprocessnode_amd import _lib
+    lib = _lib.load()
+    bits = ctypes.c_int32(-1)
+    assert lib.sgp_sweep_plan(None, ctypes.byref(bits)) == -1 and bits.value == -1      # SGP_ERR_ARG, nothing written
+
+
 def test_library_is_gfx950_only():
     from gaussianprocessnode_amd import _build
     blob = open(_build.build(), "rb").read()

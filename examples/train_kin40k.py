@@ -6,7 +6,10 @@ The reference reports SMSE 0.08343114079545057 after "approx 3h30min" (:239).  D
 committed golden fixtures (tests/golden/kin40k_data.npz, kin40k_fixture.npz: the reference's own `Xu`), so the run
 differs from the reference's only in floating-point order.  Prints one JSON line.
 
-    python examples/train_kin40k.py [--epochs 500] [--batch 500]
+    python examples/train_kin40k.py [--epochs 500] [--batch 500] [--select-inducing]
+
+--select-inducing starts from the M inducing inputs that greedy conditional-variance selection (train.select_inducing) picks among
+the training inputs at theta_init instead of the fixture's, and adds "xu_init" and the selection's final trace / trace[0] to the line.
 """
 import argparse
 import json
@@ -29,11 +32,12 @@ def main():
     ap.add_argument("--batch", type=int, default=500)
     ap.add_argument("--eta", type=float, default=1e-3)
     ap.add_argument("--host-paced", action="store_true", help="setters + sgp_theta_objective + numpy AdaMax per minibatch")
+    ap.add_argument("--select-inducing", action="store_true", help="start from the greedy selection among xtrain at theta_init")
     args = ap.parse_args()
 
     import gaussianprocessnode_amd as G
     from gaussianprocessnode_amd.meta import SMSE, softplus
-    from gaussianprocessnode_amd.train import AdaMax, perform_inference
+    from gaussianprocessnode_amd.train import AdaMax, perform_inference, select_inducing
 
     gold = os.path.join(ROOT, "tests", "golden")
     data = np.load(os.path.join(gold, "kin40k_data.npz"))
@@ -45,7 +49,12 @@ def main():
     w_val = 1e4
 
     t_create = time.perf_counter()
+    extra = {}
     with G.SGPDevice(args.batch, M, D) as eng:
+        if args.select_inducing:
+            Xu, _, trace = select_inducing(xtrain, M, theta_init, eng)
+            extra = {"xu_init": "greedy selection (train.select_inducing) among xtrain at theta_init",
+                     "select_trace_ratio": float(trace[-1] / trace[0])}
         t0 = time.perf_counter()
         qv, theta = perform_inference(theta_init, xtrain, ytrain, Xu, eng, batch_size=args.batch, epochs=args.epochs,
                                       w_val=w_val, optimizer=AdaMax(eta=args.eta), device_paced=not args.host_paced)
@@ -64,6 +73,7 @@ def main():
         "theta_softplus": [float(v) for v in p],
         "reference": {"smse_test": 0.08343114079545057, "wall": "approx 3h30min (notebook comment, :239)",
                       "theta_softplus": [float(v) for v in softplus(fix["theta_opt"])]},
+        **extra,
     }))
 
 

@@ -355,16 +355,22 @@ static hipError_t create_low_priority_stream(hipStream_t* s) {
 // synchronisation of hipMemcpy with the legacy default stream does not cover them.
 // per-call device scratch: a training loop calls sgp_predict / sgp_w_stats every minibatch, hipMalloc + hipFree per call
 // was ~0.1 ms each
-static int call_scratch(sgp_handle* h, size_t count, double** out) {
+// (call_scratch_try: the allocation's own status, for a caller that reports a scratch that does not fit as SGP_ERR_NOMEM)
+static hipError_t call_scratch_try(sgp_handle* h, size_t count, double** out) {
     if (count > h->call_capacity) {
         if (h->dCall) hipFree(h->dCall);
         h->dCall = nullptr;
         h->call_capacity = 0;
         const size_t want = count + count / 2;
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dCall), sizeof(double) * want));
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->dCall), sizeof(double) * want);
+        if (e != hipSuccess) { h->dCall = nullptr; return e; }
         h->call_capacity = want;
     }
     *out = h->dCall;
+    return hipSuccess;
+}
+static int call_scratch(sgp_handle* h, size_t count, double** out) {
+    HIPCHK(h, call_scratch_try(h, count, out));
     return 0;
 }
 
@@ -2455,6 +2461,87 @@ extern "C" int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy(mean, b.Mean, sizeof(double) * ns * h->dout, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Greedy inducing-input selection (include/sgp_hip.h; kernels and data layout: k_select_step in sgp_kernels.hip.h).  Everything is in
+// call scratch and nothing of the handle is written: it has no row in the table above StatsRecord (its class in the ledger of exported
+// names, a reader, is entered by tests/select_inducing_ref.py).  The init launch, the m_sel + 1
+// step launches (the last one only finishes step m_sel - 1) and, above SEL_RED_MAX workgroups, a reduce launch behind every step all
+// go to the library's stream at once; a stop turns the rest into no-ops on the device, and the host waits once at the end.
+extern "C" int sgp_select_inducing(sgp_handle* h, const double* X, int64_t n, int32_t m_sel, double tol, double min_var, int64_t* idx,
+                                   double* trace, int32_t* count) {
+    const char* name = "sgp_select_inducing";
+    if (!h || !X || !idx) return fail(h, SGP_ERR_ARG, "sgp_select_inducing: null h, X or idx");
+    if (int rc = refuse_training(h, name)) return rc;
+    if (!h->have_kernel) return refuse(h, name, "set_kernel first");
+    if (n < 1) return refuse(h, name, "need n >= 1 candidates");
+    if (m_sel < 1 || m_sel > n || m_sel > SEL_MAX) return refuse(h, name, "m_sel must lie in 1 .. min(n, 4032)");
+    if (!(tol >= 0.0) || !(min_var >= 0.0)) return refuse(h, name, "tol and min_var must be >= 0");
+    const int D = h->D;
+    // the whole scratch in doubles: X as given | Xs | d | C | two sets of partials and the reduced one | idx | trace | state
+    const int64_t G = (n + SEL_TILE - 1) / SEL_TILE;
+    if (n > (int64_t(1) << 40) / m_sel || G > INT32_MAX)
+        return fail(h, SGP_ERR_NOMEM, "sgp_select_inducing: the 8 m_sel n-byte factor does not fit in device memory");
+    for (int64_t e = 0; e < n * D; ++e)
+        if (!std::isfinite(X[e])) return refuse(h, name, "X must be finite");
+    const auto up8 = [](size_t c) { return (c + 7) / 8 * 8; };
+    const size_t nX = up8((size_t)n * D), nD = up8((size_t)n), nC = (size_t)m_sel * n, nP = up8((size_t)G);
+    const size_t total = 2 * nX + nD + up8(nC) + 3 * (2 * nP + 8) + up8((size_t)m_sel) + up8((size_t)m_sel + 1) + 8;
+    if (int wrc = sync_all(h)) return wrc;
+    double* base = nullptr;
+    if (call_scratch_try(h, total, &base) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, SGP_ERR_NOMEM, "sgp_select_inducing: the 8 m_sel n-byte factor does not fit in device memory");
+    }
+    const auto take = [&](size_t c) { double* q = base; base += c; return q; };
+    double* dXraw = take(nX);
+    SelArgs a{};
+    a.Xs = take(nX);
+    a.dres = take(nD);
+    a.C = take(up8(nC));
+    SelPartials set[3];                                  // [0], [1]: the steps' own, alternating; [2]: the reduced one
+    for (int k = 0; k < 3; ++k) {
+        const size_t c = k < 2 ? nP : 8;
+        set[k].pmax = take(c);
+        set[k].pidx = reinterpret_cast<long long*>(take(c));
+        set[k].psum = take(c);
+    }
+    a.idx = reinterpret_cast<long long*>(take(up8((size_t)m_sel)));
+    a.trace = take(up8((size_t)m_sel + 1));
+    a.state = reinterpret_cast<SelState*>(take(8));
+    a.n = n;
+    a.D = D;
+    a.m_sel = m_sel;
+    a.sigma2 = h->hParams->sigma2;
+    a.tol = tol;
+    a.stop_var = min_var * a.sigma2;
+    SelScale sc{};
+    for (int d = 0; d < D; ++d) sc.inv_ell[d] = h->hParams->inv_ell[d];
+    const bool reduce = G > SEL_RED_MAX;
+    hipStream_t s = h->own;
+    HIPCHK(h, hipMemcpy(dXraw, X, sizeof(double) * n * D, hipMemcpyHostToDevice));
+    a.in = set[reduce ? 2 : 0];
+    a.np_in = 1;
+    hipLaunchKernelGGL(k_select_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double*)dXraw, sc, a);
+    for (int j = 0; j <= m_sel; ++j) {
+        a.in = set[reduce ? 2 : (j & 1)];
+        a.np_in = (reduce || j == 0) ? 1 : (int)G;
+        a.out = set[reduce ? 0 : ((j + 1) & 1)];
+        const unsigned grid = j < m_sel ? (unsigned)G : 1u;
+        by_family(h->family, [&](auto F) {
+            hipLaunchKernelGGL(k_select_step<decltype(F)::value>, dim3(grid), dim3(SEL_TILE * SEL_WAVES), 0, s, a, j);
+        });
+        if (reduce && j < m_sel)
+            hipLaunchKernelGGL(k_select_reduce, dim3(1), dim3(256), 0, s, set[0], (int)G, set[2], (const SelState*)a.state);
+    }
+    HIPCHK(h, wait_stream(s));
+    HIPCHK(h, hipGetLastError());
+    SelState st{};
+    HIPCHK(h, hipMemcpy(&st, a.state, sizeof st, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(idx, a.idx, sizeof(int64_t) * m_sel, hipMemcpyDeviceToHost));
+    if (trace) HIPCHK(h, hipMemcpy(trace, a.trace, sizeof(double) * ((size_t)m_sel + 1), hipMemcpyDeviceToHost));
+    if (count) *count = st.count;
     return 0;
 }
 

@@ -5893,4 +5893,191 @@ __global__ void __launch_bounds__(64) k_psi_pred_finish(const double* __restrict
         }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Greedy inducing-input selection (sgp_select_inducing): partial pivoted Cholesky of K_ff over n candidates.
+//   Xs [D][n]      the candidates scaled by 1 / ell (coordinate-major: a step's sweep over the candidates is coalesced)
+//   dres [n]       the residual variances d_i
+//   C [m_sel][n]   the factor, step-major: row l is c_l
+//   partials       per workgroup (max d, lowest index holding it, sum d) as three arrays [np]: pmax, pidx (int64), psum
+// One launch per step: every workgroup finishes the PREVIOUS step's argmax and trace from that step's partials (the same code on the
+// same values in the same order in every workgroup, so they agree bitwise), workgroup 0 records them, then the workgroup forms c_j for
+// its SEL_TILE candidates, updates d and writes this step's partial.  The partials alternate between two sets, so no workgroup
+// overwrites what a slower one of the same launch still reads.  Above SEL_RED_MAX workgroups a one-workgroup k_select_reduce
+// launch in between folds them into one partial.  A stop sets state->stop: every later launch returns at once.
+// Per-point order (a function of j alone): wave w of the workgroup sums l = w, w + SEL_WAVES, ... < j in ascending order by fused
+// multiply-adds from 0, and the four sums are added as (s_0 + s_1) + (s_2 + s_3).
+// ------------------------------------------------------------------------------------------------
+constexpr int SEL_TILE = 64;        // candidates per workgroup: one per lane
+constexpr int SEL_WAVES = 4;        // waves per workgroup: the l range of the tile is dealt to them round-robin
+constexpr int SEL_MAX = 4032;       // most picks of one call (the pivot's column lives in LDS)
+constexpr int SEL_RED_MAX = 512;    // most partials the step kernel reduces itself (two per thread)
+
+struct SelState {
+    double trace0;                  // n sigma2
+    int32_t stop;                   // a stop rule has fired: the remaining launches do nothing
+    int32_t count;                  // picks made
+};
+struct SelPartials {
+    double* pmax;
+    long long* pidx;
+    double* psum;
+};
+struct SelArgs {
+    double* Xs;
+    double* dres;
+    double* C;
+    SelPartials in, out;
+    int np_in;                      // partials of the previous step (1 behind k_select_init or k_select_reduce)
+    int64_t n;
+    int D, m_sel;
+    double sigma2, tol, stop_var;   // stop_var = min_var sigma2
+    long long* idx;
+    double* trace;
+    SelState* state;
+};
+struct SelScale { double inv_ell[MAXD]; };
+
+// X (point-major, as the host gives it) -> Xs; d_i = sigma2; idx = -1, trace = NaN; the "partial" of step -1: max sigma2 at index 0,
+// sum n sigma2
+__global__ void __launch_bounds__(256) k_select_init(const double* __restrict__ X, SelScale sc, SelArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < a.n) {
+        for (int d = 0; d < a.D; ++d) a.Xs[(size_t)d * a.n + i] = X[(size_t)i * a.D + d] * sc.inv_ell[d];
+        a.dres[i] = a.sigma2;
+    }
+    if (blockIdx.x == 0) {
+        for (int e = threadIdx.x; e <= a.m_sel; e += 256) {
+            if (e < a.m_sel) a.idx[e] = -1;
+            a.trace[e] = __builtin_nan("");
+        }
+        if (threadIdx.x == 0) {
+            a.in.pmax[0] = a.sigma2;
+            a.in.pidx[0] = 0;
+            a.in.psum[0] = (double)a.n * a.sigma2;
+            a.state->trace0 = (double)a.n * a.sigma2;
+            a.state->stop = 0;
+            a.state->count = 0;
+        }
+    }
+}
+
+// (value, index) pairs: the larger value, the lower index among equal values
+__device__ __forceinline__ void sel_better(double& v, long long& ix, double ov, long long oi) {
+    if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+}
+// the np partials folded by the 256 threads of a workgroup, in a fixed order: thread t takes t, t + 256, ... ascending, a butterfly
+// within each wave, the waves in order.  Every thread returns the same three values.  red: 3 SEL_WAVES doubles of LDS.
+__device__ __forceinline__ void sel_fold(const SelPartials& p, int np, double* red, double& best, long long& bidx, double& sum) {
+    best = -__builtin_inf();
+    bidx = 0x7fffffffffffffffLL;
+    sum = 0.0;
+    for (int e = threadIdx.x; e < np; e += 256) {
+        sel_better(best, bidx, p.pmax[e], p.pidx[e]);
+        sum += p.psum[e];
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(best, o);
+        const long long oi = __shfl_xor(bidx, o);
+        sel_better(best, bidx, ov, oi);
+        sum += __shfl_xor(sum, o);
+    }
+    long long* redi = reinterpret_cast<long long*>(red + SEL_WAVES);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = best;
+        redi[threadIdx.x >> 6] = bidx;
+        red[2 * SEL_WAVES + (threadIdx.x >> 6)] = sum;
+    }
+    __syncthreads();
+    best = red[0];
+    bidx = redi[0];
+    sum = red[2 * SEL_WAVES];
+    for (int w = 1; w < SEL_WAVES; ++w) {
+        sel_better(best, bidx, red[w], redi[w]);
+        sum += red[2 * SEL_WAVES + w];
+    }
+}
+
+// the stop word as the whole workgroup sees it (one read, so that no thread leaves a barrier behind).  In the launch where a rule
+// fires, workgroup 0 writes the word while other workgroups of that launch may still read it, unsynchronised: a workgroup that sees it
+// set returns here, one that does not evaluates the same rule on the same partials and returns there -- the same uniform return
+__device__ __forceinline__ bool sel_stopped(const SelState* state, int* flag) {
+    if (threadIdx.x == 0) *flag = state->stop;
+    __syncthreads();
+    return *flag != 0;
+}
+
+__global__ void __launch_bounds__(256) k_select_reduce(SelPartials in, int np, SelPartials out, const SelState* state) {
+    __shared__ double red[3 * SEL_WAVES];
+    __shared__ int flag;
+    if (sel_stopped(state, &flag)) return;
+    double best, sum;
+    long long bidx;
+    sel_fold(in, np, red, best, bidx, sum);
+    if (threadIdx.x == 0) { out.pmax[0] = best; out.pidx[0] = bidx; out.psum[0] = sum; }
+}
+
+// step j (j = m_sel: only the finish of step m_sel - 1, one workgroup)
+template <int FAM>
+__global__ void __launch_bounds__(SEL_TILE * SEL_WAVES) k_select_step(SelArgs a, int j) {
+    __shared__ double cp[SEL_MAX];                      // the pivot's column C[0 .. j, p]
+    __shared__ double part[SEL_WAVES][SEL_TILE];
+    __shared__ double xp[MAXD];
+    __shared__ double red[3 * SEL_WAVES];
+    __shared__ int flag;
+    if (sel_stopped(a.state, &flag)) return;
+    double dp, tr;
+    long long p;
+    sel_fold(a.in, a.np_in, red, dp, p, tr);
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (first) a.trace[j] = tr;
+    // (the same in every thread of the launch; written so that a pick always has a positive, finite-or-larger d_p and a valid index)
+    if (j == a.m_sel || tr <= a.tol * a.state->trace0 || !(dp > a.stop_var) || p < 0 || p >= a.n) {
+        if (first) { a.state->count = j; if (j < a.m_sel) a.state->stop = 1; }
+        return;
+    }
+    if (first) a.idx[j] = p;
+    const int64_t n = a.n;
+    for (int l = threadIdx.x; l < j; l += SEL_TILE * SEL_WAVES) cp[l] = a.C[(size_t)l * n + p];
+    if ((int)threadIdx.x < a.D) xp[threadIdx.x] = a.Xs[(size_t)threadIdx.x * n + p];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t i = (int64_t)blockIdx.x * SEL_TILE + lane;
+    const bool valid = i < n;
+    const double* Ci = a.C + (valid ? i : n - 1);
+    double acc = 0.0;
+    int l = w;
+    for (; l + 3 * SEL_WAVES < j; l += 4 * SEL_WAVES) {           // four loads in flight, added in ascending l
+        const double c0 = Ci[(size_t)l * n], c1 = Ci[(size_t)(l + SEL_WAVES) * n], c2 = Ci[(size_t)(l + 2 * SEL_WAVES) * n],
+                     c3 = Ci[(size_t)(l + 3 * SEL_WAVES) * n];
+        acc = fma(c0, cp[l], acc);
+        acc = fma(c1, cp[l + SEL_WAVES], acc);
+        acc = fma(c2, cp[l + 2 * SEL_WAVES], acc);
+        acc = fma(c3, cp[l + 3 * SEL_WAVES], acc);
+    }
+    for (; l < j; l += SEL_WAVES) acc = fma(Ci[(size_t)l * n], cp[l], acc);
+    part[w][lane] = acc;
+    __syncthreads();
+    if (w != 0) return;
+    double dnew = -__builtin_inf(), dsum = 0.0;
+    if (valid) {
+        const double dot = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+        double s = 0.0;
+        for (int d = 0; d < a.D; ++d) { const double t = a.Xs[(size_t)d * n + i] - xp[d]; s = fma(t, t, s); }
+        const double c = (a.sigma2 * fam_kappa<FAM>(s) - dot) / sqrt(dp);
+        dnew = (i == p) ? 0.0 : a.dres[i] - c * c;
+        a.C[(size_t)j * n + i] = c;
+        a.dres[i] = dnew;
+        dsum = dnew;
+    }
+    long long ix = i;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(dnew, o);
+        const long long oi = __shfl_xor(ix, o);
+        sel_better(dnew, ix, ov, oi);
+        dsum += __shfl_xor(dsum, o);
+    }
+    if (lane == 0) { a.out.pmax[blockIdx.x] = dnew; a.out.pidx[blockIdx.x] = ix; a.out.psum[blockIdx.x] = dsum; }
+}
+
 }  // namespace sgp

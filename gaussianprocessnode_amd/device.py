@@ -272,6 +272,21 @@ class SGPDevice:
         self._check(self._lib.sgp_predict(self._h, ptr(Xs), ns, ptr(mu), ptr(out)), "sgp_predict")
         return out[0] if self.d_out == 1 else out.T.copy()
 
+    def select_inducing(self, X, m: int, *, tol: float = 0.0, min_var: float = 1e-12):
+        """Greedy conditional-variance selection of up to `m` of the candidates X (n, D) at the current kernel
+        (sgp_select_inducing: partial pivoted Cholesky of K_ff): (idx[:count], trace[:count + 1]), trace[j] = tr(K_ff - Q_ff) of
+        the first j picks.  It stops early once trace[j] <= tol trace[0] or no candidate's residual variance exceeds min_var sigma2.
+        Nothing of the handle changes: install the result with set_inducing(X[idx])."""
+        X = as_f64(np.reshape(X, (-1, self.D)))
+        n, m = X.shape[0], int(m)
+        idx = np.full(max(m, 1), -1, dtype=np.int64)
+        trace = np.full(max(m, 1) + 1, np.nan)
+        count = C.c_int32(0)
+        self._check(self._lib.sgp_select_inducing(self._h, ptr(X), n, m, float(tol), float(min_var),
+                                                  idx.ctypes.data_as(C.POINTER(C.c_int64)), ptr(trace), C.byref(count)),
+                    "sgp_select_inducing")
+        return idx[:count.value].copy(), trace[:count.value + 1].copy()
+
     def _qv_args(self, what: str, mu_v, Sigma_v):
         """An explicit q(v) as the ABI takes it -- mu_v (Q,), Sigma_v Q x Q column-major -- or (None, None): the handle's own."""
         if (mu_v is None) != (Sigma_v is None):

@@ -441,6 +441,36 @@ def optimize_inducing(theta, Xu, engine, *, q_v, steps: int = 100, optimizer=Non
     return (x[:nt].copy() if learn_theta else theta), x[nt:].reshape(M, D).copy(), values
 
 
+def select_inducing(X, m, theta, engine, *, family="se", tol=0.0, min_var=1e-12, install=True):
+    """A starting Xu for `engine` (SGPDevice): the `m` candidates among the rows of X (n, D) that greedy conditional-variance
+    selection picks at the kernel of raw theta (pre-softplus, sigma2 first, 1 or D lengthscales) -- `engine.select_inducing`, the
+    partial pivoted Cholesky factorisation of K_ff.  The kernel is set as `optimize_inducing` sets it, set_kernel(softplus(theta))
+    with `family` and jitter 0 (the selection uses no jitter; the caller's next set_kernel brings its own); with install=True the
+    picks are installed with set_inducing(X[idx]).  Targets, q(v) and the resident data play no part.
+
+    Returns (Xu, idx, trace): Xu = X[idx] (m, D), trace[j] = tr(K_ff - Q_ff) of the first j picks (trace[0] = n sigma2).  The
+    engine takes exactly engine.M inducing inputs: m != engine.M, or a selection that a stop rule (tol, min_var: duplicates and
+    candidates inside the span of the picks are never taken) ended short of m, raises ValueError and installs nothing."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError(f"select_inducing: X must be (n, D), got shape {X.shape}")
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+    if theta.size - 1 not in (1, X.shape[1]):
+        raise ValueError(f"select_inducing: theta must be (sigma2, 1 or {X.shape[1]} lengthscales), got {theta.size} entries")
+    if int(m) != engine.M:
+        raise ValueError(f"select_inducing: the engine holds M = {engine.M} inducing inputs, m = {m} were asked for")
+    p = softplus(theta)
+    engine.set_kernel(float(p[0]), p[1:], 0.0, family=family)
+    idx, trace = engine.select_inducing(X, int(m), tol=tol, min_var=min_var)
+    if len(idx) != engine.M:
+        raise ValueError(f"select_inducing: the selection stopped after {len(idx)} of {engine.M} picks (tol = {tol}, min_var = "
+                         f"{min_var}; residual trace {trace[-1]:.3e} of {trace[0]:.3e}): use a smaller engine or looser stop rules")
+    Xu = X[idx].copy()
+    if install:
+        engine.set_inducing(Xu)
+    return Xu, idx, trace
+
+
 # ------------------------------------------------------------------------------------------------
 # the GP state-space model: `pendulum_GP` of experiments/Pendulum_Wishart_2d.ipynb (cells 12-16)
 # ------------------------------------------------------------------------------------------------

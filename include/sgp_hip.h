@@ -656,6 +656,31 @@ int sgp_psi_predict(sgp_handle* h, const double* mean /* D x T */, const double*
                     double* out_cov /* [T] for d_out = 1, else [T][d_out][d_out]; may be NULL */,
                     double* cross /* [T][d_out][D], i.e. D x d_out x T column-major; may be NULL */, int64_t* info /* 2, may be NULL */);
 
+/* Greedy inducing-input selection: a partial pivoted Cholesky factorisation of K_ff over the n candidate points X (the columns of the
+ * D x n matrix), at the handle's current kernel -- family, sigma2, ell; the jitter is not used.  It needs no targets and no q(v), and
+ * works on UniSGP, MultiSGP and GP-SSM handles alike.  With d_i = sigma2 for every i and trace[0] = n sigma2, step j = 0 .. m_sel - 1
+ *     p_j     = the LOWEST index among the candidates whose stored d_i equals max_i d_i (compared exactly as doubles; idx[0] = 0 always)
+ *     c_j[i]  = (k(x_i, x_{p_j}) - sum_{l < j} c_l[i] c_l[p_j]) / sqrt(d_{p_j})
+ *     d_i    <- d_i - c_j[i]^2,   d_{p_j} <- 0 exactly;      idx[j] = p_j,   trace[j + 1] = sum_i d_i = tr(K_ff - Q_ff) of the picks so far
+ * (sgp_get_scalars' SGP_R_SUM_I1 of unweighted data X after sgp_set_inducing(X[:, idx[0 .. j]]), as a function of the number of picks).
+ * The call stops before step j when trace[j] <= tol trace[0], or when max_i d_i <= min_var sigma2: candidates inside the span of the
+ * picked ones, duplicates included, are never picked.  *count = the number of picks made; idx[j] = -1 for j >= count and trace[j + 1] =
+ * NaN.  An early stop returns 0.
+ *
+ * Blocking; everything lives in call scratch (8 n (m_sel + 2 D + 1) bytes -- the factor, the candidates as given and scaled, d -- and
+ * the partials; allocated with half as much again and, like every call's scratch, kept by the handle until sgp_destroy).  The handle's Xu, the resident data and
+ * statistics, the K_uu chain, q(v), sgp_sweep_kind and what every other call refuses are unchanged: installing the result is the
+ * caller's sgp_set_inducing(X[:, idx]).  An installed all-reduce hook is neither called nor a reason to refuse: the selection is local
+ * to the candidates given.  The sum over l runs in one fixed order that depends on j alone (l = w, w + 4, w + 8, ... by fused
+ * multiply-adds for w = 0 .. 3, then (s_0 + s_1) + (s_2 + s_3)), the squared distance as in every kernel of the library (over d
+ * ascending, on inputs scaled by 1 / ell once), and the argmax and the trace are reduced in fixed orders without atomics: identical
+ * calls agree bitwise in idx and trace, and idx does not depend on which workgroup owns a point.
+ *
+ * SGP_ERR_ARG: a NULL h, X or idx; no kernel set; n < 1; m_sel < 1, m_sel > n or m_sel > 4032; non-finite X; tol or min_var negative or
+ * NaN; an open sgp_train_* run.  SGP_ERR_NOMEM: the 8 m_sel n-byte factor does not fit. */
+int sgp_select_inducing(sgp_handle* h, const double* X /* D x n, host */, int64_t n, int32_t m_sel, double tol, double min_var,
+                        int64_t* idx /* m_sel */, double* trace /* m_sel + 1, may be NULL */, int32_t* count /* may be NULL */);
+
 /* ---- building blocks exposed for tests / other callers (host pointers, blocking) ------------
  * K = sigma2 * exp(-0.5 |(a-b)/ell|^2): kernelmatrix(kernel(theta), A, B) of KernelFunctions.jl as called at
  * GPnode/UniSGPnode.jl:102,153; A is D x na, B is D x nb, K is na x nb column-major. */

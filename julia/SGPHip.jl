@@ -34,7 +34,7 @@ import ReactiveMP: @rule, @average_energy, @call_rule, GenericProd, PointMass, M
                    mean_var, AverageEnergy, ContinuousUnivariateLogPdf, ContinuousMultivariateLogPdf, UnspecifiedDomain
 import ..UniSGP, ..UniSGPMeta, ..MultiSGP, ..MultiSGPMeta, ..WishartFast, ..approximate_kernel_expectation!
 
-export HipSGPMeta, HipMultiSGPMeta, predict, predictive, theta_objective, theta_objective_xu, theta_objective_psi_xu, inducing_descend!, inducing_descend_psi!, carry_posterior!, multisgp_sweep!
+export HipSGPMeta, HipMultiSGPMeta, predict, predictive, theta_objective, theta_objective_xu, theta_objective_psi_xu, inducing_descend!, inducing_descend_psi!, select_inducing, carry_posterior!, multisgp_sweep!
 
 const LIB = get(ENV, "SGP_HIP_LIB", "libsgp_hip.so")
 
@@ -529,6 +529,20 @@ function theta_objective_xu(meta::HipSGPMeta, nparams::Int)
     f = Ref{Float64}(0.0); g = zeros(nparams); gxu = zeros(h.d, h.m)
     check(ccall((:sgp_theta_objective_xu, LIB), Cint, (Ptr{Cvoid}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}), h.ptr, f, g, gxu), h.ptr)
     return f[], g, gxu
+end
+
+# Greedy inducing-input selection (include/sgp_hip.h, sgp_select_inducing): up to m of the columns of X (D × n) at the handle's
+# current kernel, by partial pivoted Cholesky of K_ff.  Returns (idx, trace): idx the picks in order, 1-based (columns of X), trace[j + 1]
+# = tr(K_ff - Q_ff) of the first j picks; both cut at the number of picks made (tol, min_var stop early).  Nothing of the handle changes:
+# X[:, idx] is the Xu to create the next Handle with (or to pass to sgp_set_inducing on this one).
+function select_inducing(meta, X::Matrix{Float64}, m::Integer; tol::Float64 = 0.0,     # meta: HipSGPMeta or HipMultiSGPMeta
+                         min_var::Float64 = 1e-12)
+    h = meta.handle
+    idx = fill(Int64(-1), max(m, 1)); trace = fill(NaN, max(m, 1) + 1); count = Ref{Int32}(0)
+    check(ccall((:sgp_select_inducing, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32, Float64, Float64, Ptr{Int64}, Ptr{Float64}, Ref{Int32}),
+                h.ptr, X, size(X, 2), Int32(m), tol, min_var, idx, trace, count), h.ptr)
+    return idx[1:count[]] .+ 1, trace[1:count[]+1]
 end
 
 # ---- minibatch loops (experiments/regression_kin40k.ipynb:205-212): prior <- posterior without leaving the device --

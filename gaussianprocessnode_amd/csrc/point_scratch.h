@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
 // sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad,
-// sgp_psi_predict, sgp_theta_objective_xu, sgp_theta_objective_psi_xu, sgp_inducing_descend, sgp_inducing_descend_psi).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp.
+// sgp_psi_predict, sgp_theta_objective_xu, sgp_theta_objective_psi_xu, sgp_inducing_descend, sgp_inducing_descend_psi, sgp_predict_joint, sgp_sample_f).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp (layout_joint: tools/joint_scratch_check.cpp).
 #pragma once
 
 #include <cstddef>
@@ -60,6 +60,39 @@ static inline void layout_predict_var(Carver& c, const PointShape& p, PredictVar
     b->LS = c.take<double>((size_t)p.Qp * p.Qp);
     b->Xs = c.take<double>((size_t)p.chunk * p.D);
     b->VarC = c.take<double>((size_t)p.chunk * p.dout * p.dout);
+}
+
+// sgp_predict_joint and sgp_sample_f (p.n = the test points, p.chunk points per chunk of K(Xu, X*)): the panel's pieces, Sigma_v's
+// factor, all points and their means, the panels Z = W_K K_u* and U_i = L_S[iM:(i+1)M, :]' K_u* of ALL points (nsp = p.n rounded up
+// to 64 columns each), the covariance padded to a multiple of 64 (rows = d_out p.n) and, for n_samples > 0, a third factorisation's
+// scratch (its log-det slots: one per tile row, at least the 64 of potrf_scratch) and status word, the normals and the samples
+struct JointScratch : PanelScratch {
+    double* LS;                     // Sigma_v padded with the identity -> its factor L_S
+    double *Xall, *MeanAll;         // all points: X* ([point][D]) and the means ([d_out][point] = vec(mean))
+    double *Z, *U;                  // all points: [nsp][Mp] and [d_out][nsp][Qp]
+    double* Cov;                    // [rows_pad][rows_pad], column-major -> its factor L_C
+    double* Cscr;                   // the third factorisation's scratch ...
+    int* Cinfo;                     // ... and its status word
+    double *Eps, *Samples;          // [rows][n_samples] each
+};
+static inline size_t joint_rows_pad(const PointShape& p) { return ((size_t)p.n * p.dout + 63) / 64 * 64; }
+static inline size_t joint_cscr_count(const PointShape& p) {
+    const size_t tiles = joint_rows_pad(p) / 64;
+    return (size_t)p.potrf_scratch + (tiles > 64 ? tiles - 64 : 0);
+}
+static inline void layout_joint(Carver& c, const PointShape& p, size_t n_samples, JointScratch* b) {
+    const size_t n = (size_t)p.n, nsp = (n + 63) / 64 * 64, rows = n * p.dout, rp = joint_rows_pad(p);
+    layout_panel(c, p, b);
+    b->LS = c.take<double>((size_t)p.Qp * p.Qp);
+    b->Xall = c.take<double>(n * p.D);
+    b->MeanAll = c.take<double>(rows);
+    b->Z = c.take<double>(nsp * p.Mp);
+    b->U = c.take<double>((size_t)p.dout * nsp * p.Qp);
+    b->Cov = c.take<double>(rp * rp);
+    b->Cscr = c.take<double>(n_samples ? joint_cscr_count(p) : 0);
+    b->Cinfo = c.take<int>(n_samples ? 1 : 0);
+    b->Eps = c.take<double>(rows * n_samples);
+    b->Samples = c.take<double>(rows * n_samples);
 }
 
 // what sgp_in_message and sgp_in_message_grad share: the panel, S and its factor, an explicit Sigma_v and what the logpdf of all

@@ -4375,6 +4375,127 @@ extern "C" int sgp_psi_predict(sgp_handle* h, const double* mean, const double* 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Joint predictive covariance and posterior function samples (include/sgp_hip.h; kernels: k_joint_panel, k_joint_cov, k_tri_apply in
+// sgp_kernels.hip.h).  As sgp_predict_var: blocking, K_uu, W_K = L_K^-1 and the factor of Sigma_v formed at the CURRENT kernel
+// parameters in call scratch, nothing the sweep keeps written (only the parameter mirror dXusK / dParamsK, as sgp_predict), K(Xu, X*)
+// chunked under the same knob.  The means are ONE k_predict launch over all points, as sgp_predict's.  Neither call has a row in the
+// table above StatsRecord: both are readers.
+// ------------------------------------------------------------------------------------------------
+static bool all_finite(const double* v, size_t count) {
+    for (size_t e = 0; e < count; ++e)
+        if (!std::isfinite(v[e])) return false;
+    return true;
+}
+
+// n_samples == 0: sgp_predict_joint (cov out); else sgp_sample_f (samples and info out)
+static int joint_common(sgp_handle* h, const char* name, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
+                        int32_t flags, double sample_jitter, const double* eps, int64_t n_samples, double* mean, double* cov,
+                        double* samples, int64_t* info) {
+    const bool sampling = n_samples > 0;
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T, TQ = h->TQ;
+    if (ns * dout > SGP_JOINT_MAX_ROWS) return refuse(h, name, "ns * d_out exceeds SGP_JOINT_MAX_ROWS (8192)");
+    if (!all_finite(Xstar, (size_t)ns * D)) return refuse(h, name, "Xstar must be finite");
+    const int R = (int)(ns * dout);
+    if (sampling) {
+        if (!std::isfinite(sample_jitter) || sample_jitter < 0.0) return refuse(h, name, "sample_jitter must be finite and >= 0");
+        if (!all_finite(eps, (size_t)R * n_samples)) return refuse(h, name, "eps must be finite");
+    }
+    OutMat noise;
+    memset(&noise, 0, sizeof noise);
+    if ((flags & SGP_PREDICT_NOISE) && (!outmat_posdef(h->hParams->W, dout) || !invert_outmat(h->hParams->W, dout, &noise)))
+        return refuse(h, name, "the noise matrix of sgp_set_noise is not positive definite");
+    if (int wrc = point_call_wait(h, mu_v)) return wrc;
+    hipStream_t s = h->own;
+    const PointShape shape = point_shape(h, (int64_t)Mp + 4 * T + 4 + dout, ns, 0);
+    const int64_t chunk = shape.chunk, nsp = (ns + TB - 1) / TB * TB;
+    const int nb = (int)(nsp / TB), Rp = (int)joint_rows_pad(shape), TR = Rp / TB;
+    JointScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_joint(c, shape, (size_t)n_samples, &b); })) return crc;
+    // the last sweep's Sigma_v is copied: its factor is formed in place
+    const double *dMu, *dSig;
+    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.LS, &dMu, &dSig)) return rc;
+    if (!mu_v) hipLaunchKernelGGL(k_pad_square, dim3((unsigned)(((size_t)Qp * Qp + 255) / 256)), dim3(256), 0, s, dSig, Qp, b.LS, Q, Qp);
+    HIPCHK(h, hipMemcpy(b.Xall, Xstar, sizeof(double) * ns * D, hipMemcpyHostToDevice));
+    if (sampling) HIPCHK(h, hipMemcpy(b.Eps, eps, sizeof(double) * R * n_samples, hipMemcpyHostToDevice));
+    if (int rc = factor_begin(h, s, b)) return rc;
+    if (info) info[0] = info[1] = info[2] = 0;
+    if (int frc = factor_finish(h, s, b, b.LS, Qp, TQ, Q, "Sigma_v")) {
+        int two[2] = {0, 0};
+        if (info && frc > 0 && hipMemcpy(two, b.Info, sizeof two, hipMemcpyDeviceToHost) == hipSuccess) {
+            info[0] = two[0] > 0 ? two[0] : 0;
+            info[1] = two[1] > 0 ? two[1] : 0;
+        }
+        return frc;
+    }
+    // the panel columns of the ragged last point block and, for the factorisation, the covariance's padding start as zeros
+    HIPCHK(h, hipMemsetAsync(b.Z, 0, sizeof(double) * (size_t)nsp * Mp, s));
+    HIPCHK(h, hipMemsetAsync(b.U, 0, sizeof(double) * (size_t)dout * nsp * Qp, s));
+    if (sampling) HIPCHK(h, hipMemsetAsync(b.Cov, 0, sizeof(double) * (size_t)Rp * Rp, s));
+    launch_predict(h, s, h->dXusK, h->dParamsK, b.Xall, dMu, b.MeanAll, ns);
+    for (int64_t s0 = 0; s0 < ns; s0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, ns - s0);
+        launch_gram_uf(h, s, h->dXusK, b.Xall + (size_t)s0 * D, nullptr, b.Kc, nullptr, h->dParamsK, nc, 0, nullptr, nullptr);
+        hipLaunchKernelGGL(k_joint_panel, dim3((unsigned)((nc + TB - 1) / TB), T + dout * TQ), dim3(256), 0, s, (const double*)b.Wk,
+                           (const double*)b.LS, (const double*)b.Kc, b.Z, b.U, M, Mp, Qp, T, TQ, nc, s0, nsp);
+    }
+    const int nbt = dout * nb;
+    by_family(h->family, [&](auto F) {
+        hipLaunchKernelGGL(k_joint_cov<decltype(F)::value>, dim3((unsigned)(nbt * (nbt + 1) / 2)), dim3(256), 0, s, (const double*)b.Z,
+                           (const double*)b.U, (const double*)b.Xall, b.Cov, (const Params*)h->dParamsK, noise, M, Mp, Qp, T, D, dout,
+                           ns, nsp, nb, (int64_t)Rp);
+    });
+    if (!sampling) {
+        HIPCHK(h, hipStreamSynchronize(s));
+        HIPCHK(h, hipGetLastError());
+        if (mean) HIPCHK(h, hipMemcpy(mean, b.MeanAll, sizeof(double) * R, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy2D(cov, sizeof(double) * R, b.Cov, sizeof(double) * Rp, sizeof(double) * R, R, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    // cov + sample_jitter I, padded with the identity -> L_C in place (the dense factorisation of sgp_potrf), then mean + L_C eps
+    const size_t cscr = joint_cscr_count(shape);
+    HIPCHK(h, hipMemsetAsync(b.Cscr, 0, sizeof(double) * ((cscr + Carver::ALIGN - 1) / Carver::ALIGN * Carver::ALIGN + Carver::ALIGN), s));
+    hipLaunchKernelGGL(k_joint_diag, dim3((unsigned)((Rp + 255) / 256)), dim3(256), 0, s, b.Cov, (int64_t)Rp, R, Rp, sample_jitter);
+    launch_potrf(b.Cov, Rp, TR, b.Cinfo, R, b.Cscr, s);
+    hipLaunchKernelGGL(k_tri_apply, dim3((unsigned)TR, (unsigned)((n_samples + TB - 1) / TB)), dim3(256), 0, s, (const double*)b.Cov,
+                       (int64_t)Rp, (const double*)b.Eps, (const double*)b.MeanAll, b.Samples, R, n_samples);
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    int cinfo = 0;
+    HIPCHK(h, hipMemcpy(&cinfo, b.Cinfo, sizeof cinfo, hipMemcpyDeviceToHost));
+    if (info) info[2] = cinfo > 0 ? cinfo : 0;
+    if (int src = factor_status(h, cinfo, "cov + sample_jitter I")) return src;
+    if (mean) HIPCHK(h, hipMemcpy(mean, b.MeanAll, sizeof(double) * R, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(samples, b.Samples, sizeof(double) * R * n_samples, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int sgp_predict_joint(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
+                                 int32_t flags, double* mean, double* cov) {
+    const char* name = "sgp_predict_joint";
+    if (!h || ns < 0) return fail(h, SGP_ERR_ARG, "sgp_predict_joint: bad argument");
+    if (flags & ~SGP_PREDICT_NOISE) return fail(h, SGP_ERR_ARG, "sgp_predict_joint: unknown flags");
+    if (int rc = point_call_ready(h, name, mu_v, Sigma_v)) return rc;
+    if (ns == 0) return 0;
+    if (!Xstar) return refuse(h, name, "null Xstar");
+    if (!cov) return refuse(h, name, "null cov");
+    return joint_common(h, name, Xstar, ns, mu_v, Sigma_v, flags, 0.0, nullptr, 0, mean, cov, nullptr, nullptr);
+}
+
+extern "C" int sgp_sample_f(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v, int32_t flags,
+                            double sample_jitter, const double* eps, int64_t n_samples, double* mean, double* samples,
+                            int64_t* info) {
+    const char* name = "sgp_sample_f";
+    if (!h || ns < 0) return fail(h, SGP_ERR_ARG, "sgp_sample_f: bad argument");
+    if (flags & ~SGP_PREDICT_NOISE) return fail(h, SGP_ERR_ARG, "sgp_sample_f: unknown flags");
+    if (int rc = point_call_ready(h, name, mu_v, Sigma_v)) return rc;
+    if (ns == 0) return 0;
+    if (!Xstar) return refuse(h, name, "null Xstar");
+    if (!samples || !eps) return refuse(h, name, "null samples or eps");
+    if (n_samples < 1) return refuse(h, name, "need n_samples >= 1");
+    return joint_common(h, name, Xstar, ns, mu_v, Sigma_v, flags, sample_jitter, eps, n_samples, mean, nullptr, samples, info);
+}
+
+// ------------------------------------------------------------------------------------------------
 // stand-alone building blocks (host in / host out, blocking)
 // ------------------------------------------------------------------------------------------------
 extern "C" int sgp_kernelmatrix(int32_t device, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,

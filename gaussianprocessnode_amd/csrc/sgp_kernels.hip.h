@@ -6080,4 +6080,220 @@ __global__ void __launch_bounds__(SEL_TILE * SEL_WAVES) k_select_step(SelArgs a,
     if (lane == 0) { a.out.pmax[blockIdx.x] = dnew; a.out.pidx[blockIdx.x] = ix; a.out.psum[blockIdx.x] = dsum; }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Joint predictive covariance and posterior function samples (sgp_predict_joint, sgp_sample_f).  With k_s = K(Xu, x_s),
+// z_s = L_K^-1 k_s, Sigma_v = L_S L_S' and u_is = (L_S[iM:(i+1)M, :])' k_s (a Q-vector whose entries from (i + 1) M on are zero),
+// row r = i ns + s of the covariance is output i at test point s and
+//   cov[(j,s),(i,s')] = delta_ij (k(x_s, x_s') - z_s . z_s') + u_js . u_is'    (+ delta_ss' (W^-1)_ji with the noise flag)
+// k_joint_panel keeps Z = W_K K_u* and the d_out panels U_i of all test points, chunk by chunk; k_joint_cov forms the lower 64 x 64
+// tiles from them and stores each with its mirror; k_joint_diag pads and shifts the diagonal for the factorisation; k_tri_apply
+// multiplies the factor into the caller's normals.  Every entry's sums run in an order fixed by (ns, M, d_out): no atomics, and a
+// point's panel columns do not depend on the chunk it came in.
+// ------------------------------------------------------------------------------------------------
+// one 64 x 64 MFMA tile product with k_quadform_fused's operand reads: A as [kk][row] with stride PS (ak = PS, ar = 1) or as
+// [row][kk] with stride KMS (ak = 1, ar = KMS); B as [column][kk] with stride KMS
+__device__ __forceinline__ void joint_mma(Acc4& acc, const double* As, const double* Bs, int ak, int ar, int lane, int wr, int wc) {
+    const int li = lane & 15, lk = lane >> 4;
+    const int r0 = wr * 32 + li, r1 = r0 + 16, c0 = wc * 32 + li, c1 = c0 + 16;
+    const double* ap = As + lk * ak;
+    const double* bp = Bs + lk;
+#pragma unroll 4
+    for (int kk = 0; kk < TB; kk += 4) {
+        const double a0 = ap[r0 * ar], a1 = ap[r1 * ar];
+        const double b0 = bp[c0 * KMS], b1 = bp[c1 * KMS];
+        acc.t[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc.t[0][0], 0, 0, 0);
+        acc.t[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc.t[0][1], 0, 0, 0);
+        acc.t[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc.t[1][0], 0, 0, 0);
+        acc.t[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc.t[1][1], 0, 0, 0);
+        ap += 4 * ak;
+        bp += 4;
+    }
+}
+
+// The panels of one chunk of nc points (columns s0 .. of the call's panels; Kc: the chunk's K(Xu, X*), [point][Mp], zero from row M
+// on).  Workgroup (point block blockIdx.x, item y): y < T forms rows 64 y .. of Z = W_K K (W_K lower: tile columns k <= y, the
+// diagonal tile masked to its lower part); item T + i TQ + I forms rows 64 I .. of U_i = L_i' K, L_i = L_S[iM:(i+1)M, :] -- the
+// entries of L_S above its diagonal (what the factorisation leaves of Sigma_v there) are masked on the way into LDS, and the tile
+// columns that lie wholly above it are skipped.  The contraction runs over m in ascending tiles of 64 either way.
+//   Z : [nsp][Mp];  U : [d_out][nsp][Qp]  (a point's column contiguous, as K_uf's)
+__global__ void __launch_bounds__(256, 2) k_joint_panel(const double* __restrict__ Wk, const double* __restrict__ LS,
+                                                       const double* __restrict__ Kc, double* __restrict__ Z, double* __restrict__ U,
+                                                       int M, int Mp, int Qp, int T, int TQ, int64_t nc, int64_t s0, int64_t nsp) {
+    __shared__ __attribute__((aligned(16))) double lds[TB * PS + TB * KMS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int y = blockIdx.y;
+    const bool umode = y >= T;
+    const int i = umode ? (y - T) / TQ : 0, I = umode ? (y - T) % TQ : y;
+    const int64_t n0 = (int64_t)blockIdx.x * TB;
+    double* As = lds;
+    double* Bs = lds + TB * PS;
+    Acc4 acc;
+    acc_zero(acc);
+    // U_i: row q = 64 I + r of the tile takes L_S[iM + m, q] for q <= iM + m, so the first tile column with an entry is the one of
+    // m = 64 I - iM
+    const int k_begin = umode ? (I * TB - i * M > 0 ? (I * TB - i * M) / TB : 0) : 0;
+    const int k_end = umode ? T - 1 : I;
+#pragma unroll 1
+    for (int kt = k_begin; kt <= k_end; ++kt) {
+        __syncthreads();                              // the previous tile pair has been consumed
+        for (int e = tid; e < TB * TB; e += 256) {
+            const int lo = e & 63, hi = e >> 6;
+            if (umode) {                              // As[row = hi][kk = lo] = L_S[iM + m, q]: contiguous along m
+                const int m = kt * TB + lo, q = I * TB + hi, row = i * M + m;
+                As[hi * KMS + lo] = (m < M && q <= row) ? LS[(size_t)q * Qp + row] : 0.0;
+            } else {                                  // As[kk = hi][row = lo] = W_K[rr, m]: contiguous along rr
+                const int m = kt * TB + hi, rr = I * TB + lo;
+                As[hi * PS + lo] = (m < M && m <= rr) ? Wk[(size_t)m * Mp + rr] : 0.0;
+            }
+            const int64_t n = n0 + hi;                // Bs[point = hi][kk = lo] = K[m, n]
+            Bs[hi * KMS + lo] = (n < nc) ? Kc[(size_t)n * Mp + kt * TB + lo] : 0.0;
+        }
+        __syncthreads();
+        joint_mma(acc, As, Bs, umode ? 1 : PS, umode ? KMS : 1, lane, wr, wc);
+    }
+    double* out = umode ? U + ((size_t)i * nsp + s0) * Qp : Z + (size_t)s0 * Mp;
+    const int ldo = umode ? Qp : Mp;
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj) {
+        const int64_t n = n0 + acc_col(lane, wc, tj);
+        if (n >= nc) continue;
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out[(size_t)n * ldo + I * TB + acc_row(lane, wr, ti, r)] = acc.t[ti][tj][r];
+    }
+}
+
+// One workgroup per lower 64 x 64 tile of the block grid whose block index is (output, point block): row block (j, a), column
+// block (i, b), j > i with any (a, b) or j == i with a >= b -- every output pair i <= j and point-block pair of the lower half.
+// The tile accumulates U_j[:, a]' U_i[:, b] over the min(i, j) + 1 = i + 1 outputs' worth of rows that U_i has and, for i == j,
+// Z[:, a]' Z[:, b] in a second accumulator; it then evaluates k(x_s, x_s') from the inputs scaled by 1 / ell once (d ascending, the
+// direct-difference sum of every family), subtracts ONCE -- (k - z.z) + u.u, as sigma2 - |z|^2 is formed per point --, adds the noise
+// where s == s', and stores the entry and its mirror: the matrix is exactly symmetric (of a diagonal tile only the lower half is
+// taken).  Points from ns on (the ragged last block) are not stored; their panel columns are zero.  The coordinates share the LDS
+// of the panels.
+//   X : [ns][D] unscaled;  C : column-major, leading dimension ldc >= d_out ns
+template <int FAM>
+__global__ void __launch_bounds__(256, 2) k_joint_cov(const double* __restrict__ Z, const double* __restrict__ U,
+                                                     const double* __restrict__ X, double* __restrict__ C,
+                                                     const Params* __restrict__ P, OutMat noise, int M, int Mp, int Qp, int T, int D,
+                                                     int dout, int64_t ns, int64_t nsp, int nb, int64_t ldc) {
+    __shared__ __attribute__((aligned(16))) double lds[2 * TB * PS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    int rb, cb;
+    tile_from_index(blockIdx.x, rb, cb);
+    const int j = rb / nb, a = rb % nb, i = cb / nb, b = cb % nb;
+    double* As = lds;
+    double* Bs = lds + TB * PS;
+    Acc4 form, zz;
+    acc_zero(form);
+    acc_zero(zz);
+    const int nq = ((i + 1) * M + TB - 1) / TB;       // U_i is zero from row (i + 1) M on
+    const double* Uj = U + (size_t)j * nsp * Qp;
+    const double* Ui = U + (size_t)i * nsp * Qp;
+#pragma unroll 1
+    for (int kt = 0; kt < nq; ++kt) {
+        __syncthreads();
+        load_panel_t(As, Uj, (size_t)Qp, kt * TB, a * TB, TB, tid);
+        load_panel_t(Bs, Ui, (size_t)Qp, kt * TB, b * TB, TB, tid);
+        __syncthreads();
+        tile_mma(form, As, Bs, TB, lane, wr, wc);
+    }
+    const bool same = i == j;
+    if (same) {
+#pragma unroll 1
+        for (int kt = 0; kt < T; ++kt) {
+            __syncthreads();
+            load_panel_t(As, Z, (size_t)Mp, kt * TB, a * TB, TB, tid);
+            load_panel_t(Bs, Z, (size_t)Mp, kt * TB, b * TB, TB, tid);
+            __syncthreads();
+            tile_mma(zz, As, Bs, TB, lane, wr, wc);
+        }
+        __syncthreads();                              // the panels are through: their LDS takes the scaled coordinates [d][point]
+        for (int t = tid; t < D * TB; t += 256) {
+            const int p = t / D, d = t % D;
+            const int64_t sa = (int64_t)a * TB + p, sb = (int64_t)b * TB + p;
+            As[d * TB + p] = (sa < ns) ? X[(size_t)sa * D + d] * P->inv_ell[d] : 0.0;
+            Bs[d * TB + p] = (sb < ns) ? X[(size_t)sb * D + d] * P->inv_ell[d] : 0.0;
+        }
+        __syncthreads();
+    }
+    const double s2 = P->sigma2;
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj) {
+        const int col = acc_col(lane, wc, tj);
+        const int64_t sb = (int64_t)b * TB + col;
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = acc_row(lane, wr, ti, r);
+                const int64_t sa = (int64_t)a * TB + row;
+                if (sa >= ns || sb >= ns || (rb == cb && col > row)) continue;
+                double v = form.t[ti][tj][r];
+                if (same) {
+                    double d2 = 0.0;
+                    for (int d = 0; d < D; ++d) { const double t = As[d * TB + row] - Bs[d * TB + col]; d2 = fma(t, t, d2); }
+                    v = (s2 * fam_kappa<FAM>(d2) - zz.t[ti][tj][r]) + v;
+                }
+                if (sa == sb) v += noise.v[i * dout + j];
+                const size_t gr = (size_t)j * ns + sa, gc = (size_t)i * ns + sb;
+                C[gc * ldc + gr] = v;
+                C[gr * ldc + gc] = v;
+            }
+    }
+}
+
+// the diagonal of the n_pad x n_pad matrix C before its factorisation: + shift on the n valid entries, 1 on the padding (whose
+// off-diagonal entries the caller has cleared)
+__global__ void __launch_bounds__(256) k_joint_diag(double* __restrict__ C, int64_t ldc, int n, int n_pad, double shift) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_pad) return;
+    double* p = C + (size_t)r * ldc + r;
+    *p = (r < n) ? *p + shift : 1.0;
+}
+
+// samples[:, k] = mean + L eps[:, k] with the lower-triangular L (n x n in an ld-strided matrix whose strictly upper part holds
+// anything: it is never read -- tile columns above the row tile are not visited, the diagonal tile is masked on the way into LDS).
+// Workgroup (row tile, 64 samples), the long row tiles first; the tile columns 0 .. I are contracted in ascending order.
+//   eps, samples : n x n_samples column-major;  mean : n
+__global__ void __launch_bounds__(256, 2) k_tri_apply(const double* __restrict__ L, int64_t ld, const double* __restrict__ eps,
+                                                     const double* __restrict__ mean, double* __restrict__ samples, int n,
+                                                     int64_t n_samples) {
+    __shared__ __attribute__((aligned(16))) double lds[TB * PS + TB * KMS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int I = gridDim.x - 1 - blockIdx.x;
+    const int64_t j0 = (int64_t)blockIdx.y * TB;
+    double* As = lds;
+    double* Bs = lds + TB * PS;
+    Acc4 acc;
+    acc_zero(acc);
+#pragma unroll 1
+    for (int ct = 0; ct <= I; ++ct) {
+        __syncthreads();
+        for (int e = tid; e < TB * TB; e += 256) {
+            const int lo = e & 63, hi = e >> 6;
+            const int row = I * TB + lo, c = ct * TB + hi;            // As[kk = hi][row = lo] = L[row, c]
+            As[hi * PS + lo] = (c <= row && row < n) ? L[(size_t)c * ld + row] : 0.0;
+            const int ce = ct * TB + lo;                              // Bs[sample = hi][kk = lo] = eps[ce, j0 + hi]
+            const int64_t smp = j0 + hi;
+            Bs[hi * KMS + lo] = (ce < n && smp < n_samples) ? eps[(size_t)smp * n + ce] : 0.0;
+        }
+        __syncthreads();
+        joint_mma(acc, As, Bs, PS, 1, lane, wr, wc);
+    }
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj) {
+        const int64_t smp = j0 + acc_col(lane, wc, tj);
+        if (smp >= n_samples) continue;
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = I * TB + acc_row(lane, wr, ti, r);
+                if (row < n) samples[(size_t)smp * n + row] = mean[row] + acc.t[ti][tj][r];
+            }
+    }
+}
+
 }  // namespace sgp

@@ -308,6 +308,45 @@ class SGPDevice:
         self._check(self._lib.sgp_predict_var(self._h, ptr(Xs), ns, ptr(mu), ptr(S), flags, ptr(mean), ptr(var)), "sgp_predict_var")
         return (mean[0], var) if self.d_out == 1 else (mean.T.copy(), var)
 
+    def predict_joint(self, Xstar, mu_v=None, Sigma_v=None, noise: bool = False):
+        """Predictive mean and JOINT covariance of the latent f over all of Xstar (sgp_predict_joint), at the current kernel:
+        (mean, cov) with mean (ns,) for d_out = 1 and (ns, d_out) otherwise, cov (R, R), R = ns * d_out, exactly symmetric; row
+        i * ns + s is output i at point s (`mean.T.reshape(-1)`).  q(v) is the last sweep's (mu_v = Sigma_v = None) or the one
+        given; noise=True adds W^-1 of the last `set_noise` where the two points are the same one."""
+        Xs = as_f64(np.reshape(Xstar, (-1, self.D)))
+        ns = Xs.shape[0]
+        mu, S = self._qv_args("predict_joint", mu_v, Sigma_v)
+        mean = np.empty((self.d_out, ns))
+        cov = np.empty((ns * self.d_out, ns * self.d_out))
+        flags = _lib.SGP_PREDICT_NOISE if noise else 0
+        self._check(self._lib.sgp_predict_joint(self._h, ptr(Xs), ns, ptr(mu), ptr(S), flags, ptr(mean), ptr(cov)),
+                    "sgp_predict_joint")
+        return (mean[0] if self.d_out == 1 else mean.T.copy()), cov
+
+    def sample_f(self, Xstar, eps, sample_jitter: float = 0.0, mu_v=None, Sigma_v=None, noise: bool = False):
+        """Posterior function samples at Xstar (sgp_sample_f): (mean, samples) with samples[:, k] = vec(mean) + L_C eps[:, k],
+        L_C L_C' = cov + sample_jitter I, cov and the row order as `predict_joint`.  eps (R, n_samples) holds the caller's standard
+        normals (the library has no random state); samples has its shape.  A cov + sample_jitter I, K_uu or Sigma_v that is not
+        positive definite raises PosDefException with the failing minor."""
+        Xs = as_f64(np.reshape(Xstar, (-1, self.D)))
+        ns = Xs.shape[0]
+        R = ns * self.d_out
+        e = np.asarray(eps, dtype=np.float64)
+        if e.ndim == 1:
+            e = e.reshape(R, 1)
+        if e.ndim != 2 or e.shape[0] != R:
+            raise ValueError(f"sample_f: eps must be (ns * d_out, n_samples) = ({R}, n_samples), got {e.shape}")
+        n_samples = e.shape[1]
+        e_cm = as_f64(e.T)                                     # column-major R x n_samples
+        mu, S = self._qv_args("sample_f", mu_v, Sigma_v)
+        mean = np.empty((self.d_out, ns))
+        out = np.empty((n_samples, R))
+        info = (C.c_int64 * 3)()
+        flags = _lib.SGP_PREDICT_NOISE if noise else 0
+        self._check(self._lib.sgp_sample_f(self._h, ptr(Xs), ns, ptr(mu), ptr(S), flags, float(sample_jitter), ptr(e_cm), n_samples,
+                                           ptr(mean), ptr(out), info), "sgp_sample_f")
+        return (mean[0] if self.d_out == 1 else mean.T.copy()), out.T.copy()
+
     def _node_points(self, what: str, X, node_start):
         """The points of a node-batch call as the ABI takes them: (X (n, D) contiguous, n, node_start as int64, n_nodes)."""
         Xs = as_f64(np.reshape(X, (-1, self.D)))

@@ -211,18 +211,31 @@ def exact_predictive(eng, x, q_v, D: int, noise: bool, device: int):
     return m, C, single
 
 
-def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, noise: bool = True, psi: str = "cubature"):
+def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, noise: bool = True, psi: str = "cubature",
+               joint: bool = False):
     """Predictive means and covariances of the d_out latent outputs (noise=False) or of the observation (noise=True: +
     mean(q_w)^-1) at kernel(q_theta) and the explicit q_v (sgp_predict_var).  Test inputs (ns, D) give means (ns, d_out) and
     covariances (ns, d_out, d_out); a PointMass or an uncertain input q(x*) gives one mean (d_out,) and covariance (d_out,
     d_out) -- the latter by one device call over meta.method's cubature points and the law of total variance in matrix form.
     psi="exact" (SE kernel only) takes a Gaussian, a PointMass, a plain array or a list of inputs through ONE closed-form
-    `SGPDevice.psi_predict` call instead -- no cubature points; a list gives stacked means (T, d_out) and covariances."""
-    from .unisgp import _test_points, combine_total_variance
+    `SGPDevice.psi_predict` call instead -- no cubature points; a list gives stacked means (T, d_out) and covariances.
+    joint=True (point inputs (ns, D) only) returns the means (ns, d_out) and the JOINT (ns d_out, ns d_out) covariance over all
+    test points instead (`SGPDevice.predict_joint`: row i ns + s is output i at point s)."""
+    from .unisgp import _test_points, combine_total_variance, joint_points
     _check_psi(psi, "predictive")
     W = _mean_W(q_w)
     d_out = W.shape[0]
     D = np.asarray(meta.Xu).shape[1]
+    if joint:
+        X = joint_points(Xstar_or_q_in, psi, D)
+        eng = _engine(meta, 1, d_out)
+        sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+        if noise:
+            eng.set_noise(W)
+        mu_v, Sigma_v = q_v.mean_cov()
+        m, C = eng.predict_joint(X, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64), noise=noise)
+        return np.asarray(m, dtype=np.float64).reshape(-1, d_out), C
     if psi == "exact":
         require_se(kernel_family(meta.kernel))
         eng = _aux_engine_out(meta, d_out)

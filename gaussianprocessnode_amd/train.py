@@ -665,6 +665,40 @@ def perform_inference_gpssm(theta, y, meta, *, P, x0_prior, epochs, vmp_iteratio
     return theta, fe_values, post
 
 
+def sample_posterior(meta, Xstar, n_samples, rng, *, q_v, q_theta, q_w=None, noise=False, sample_jitter=None):
+    """Whole functions from the posterior: n_samples joint draws of the latent f (noise=True: of the observation, + mean(q_w)^-1 per
+    point) at the test inputs Xstar (ns, D), at kernel(q_theta) and the explicit q_v -- ONE `SGPDevice.sample_f` call on meta's
+    engine (UniSGPMeta or MultiSGPMeta).  The standard normals come from `rng` (a numpy.random.Generator): the library holds no
+    random state, so a seeded generator reproduces the draws bitwise.  sample_jitter (default 1e-9 sigma2) is added to the joint
+    covariance's diagonal before it is factored; nearly coincident test points need more.  Returns (mean (ns, d_out), samples
+    (n_samples, ns, d_out)); ns * d_out is limited to SGP_JOINT_MAX_ROWS = 8192."""
+    from . import multisgp as MS
+    from . import unisgp as US
+    from .meta import kernel_family, set_engine_kernel
+    Xu = np.asarray(meta.Xu)
+    M, D = Xu.shape
+    X = np.asarray(Xstar, dtype=np.float64).reshape(-1, D)
+    ns, n_samples = X.shape[0], int(n_samples)
+    mu_v, Sigma_v = q_v.mean_cov()
+    mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
+    d_out = mu_v.size // M
+    multi = isinstance(meta, MS.MultiSGPMeta)
+    eng = MS._engine(meta, 1, d_out) if multi else US._engine(meta, 1)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+    if noise:
+        if q_w is None:
+            raise ValueError("sample_posterior: noise=True needs q_w")
+        if multi:
+            eng.set_noise(MS._mean_W(q_w))
+        else:
+            eng.set_noise([[US._mean_w(q_w)]], US._elog_w(q_w))
+    eps = rng.standard_normal((ns * d_out, n_samples))
+    jit = 1e-9 * float(sigma2) if sample_jitter is None else float(sample_jitter)
+    mean, smp = eng.sample_f(X, eps, jit, mu_v, np.asarray(Sigma_v, dtype=np.float64), noise=noise)
+    return np.asarray(mean).reshape(ns, d_out), smp.T.reshape(n_samples, d_out, ns).transpose(0, 2, 1).copy()
+
+
 def forecast_gpssm(q_x, steps, q_v, q_w, q_theta, meta, noise=True):
     """Roll the GP-SSM transition x_{k+1} ~ MultiSGP(x_k, v, W, theta) forward from q_x -- one Gaussian, or a list of B of them (a
     batch of trajectories) -- in closed form (SE kernel only; d_out must equal D).  Each step is ONE `SGPDevice.psi_predict` call over

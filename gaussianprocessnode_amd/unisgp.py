@@ -407,17 +407,38 @@ def combine_total_variance(wts, m, var):
     return mean, second - np.outer(mean, mean)
 
 
-def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool = True, psi: str = "cubature"):
+def joint_points(Xstar, psi: str, D: int):
+    """The test inputs of predictive(..., joint=True): a plain (ns, D) array -- joint covariances at Gaussian inputs are not
+    covered (their per-point counterpart is psi="exact")."""
+    if psi != "cubature":
+        raise ValueError("predictive: joint=True takes point inputs (ns, D) only (psi must be 'cubature')")
+    try:
+        return np.asarray(Xstar, dtype=np.float64).reshape(-1, D)
+    except (TypeError, ValueError):
+        raise ValueError("predictive: joint=True takes point inputs (ns, D) only") from None
+
+
+def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool = True, psi: str = "cubature", joint: bool = False):
     """Predictive mean and variance of the latent f (noise=False) or of the observation y (noise=True: + 1 / mean(q_w)) at
     kernel(q_theta) and the explicit q_v (`q_v.mean_cov()` goes to the device, sgp_predict_var).  Test inputs (ns, D) give
     per-point arrays (ns,), (ns,); a PointMass or an uncertain input q(x*) gives two floats -- the latter by one device call over
     meta.method's cubature points and the law of total variance on the host.  `rule_out` is unchanged (the reference's
     message carries precision mean(q_w) only).  psi="exact" (SE kernel only) takes a Gaussian, a PointMass, a plain array or a
     list of inputs through ONE closed-form `SGPDevice.psi_predict` call on the auxiliary engine instead -- no cubature points; a
-    list gives per-input arrays (T,), (T,)."""
+    list gives per-input arrays (T,), (T,).  joint=True (point inputs (ns, D) only) returns the mean (ns,) and the JOINT (ns, ns)
+    covariance over all test points instead (`SGPDevice.predict_joint`; the noise enters its diagonal)."""
     D = meta.Xu.shape[1]
     if psi not in ("cubature", "exact"):
         raise ValueError(f"predictive: psi must be 'cubature' or 'exact', got {psi!r}")
+    if joint:
+        X = joint_points(Xstar_or_q_in, psi, D)
+        eng = _engine(meta, 1)
+        sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+        if noise:
+            eng.set_noise([[_mean_w(q_w)]], _elog_w(q_w))
+        mu_v, Sigma_v = q_v.mean_cov()
+        return eng.predict_joint(X, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64), noise=noise)
     if psi == "exact":
         from .multisgp import exact_predictive
         require_se(kernel_family(meta.kernel))

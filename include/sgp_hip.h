@@ -261,6 +261,34 @@ int sgp_predict(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu
 int sgp_predict_var(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
                     int32_t flags, double* mean, double* var);
 
+/* sgp_predict_joint: the predictive mean and the JOINT covariance of the latent f over all test points.  Row r = i*ns + s is output
+ * i at test point s (the order of `mean`).  With k_s = k(Xu, x_s), z_s = L_K^-1 k_s and q(v) = N(mu_v, Sigma_v):
+ *     cov[(i,s),(j,s')] = delta_ij (k(x_s, x_s') - z_s . z_s') + k_s' Sigma_v^(ij) k_s'   (+ delta_ss' (W^-1)_ij with SGP_PREDICT_NOISE)
+ * at the CURRENT kernel (family, sigma2, ell, jitter), every family, d_out 1..4, D 1..32.  cov is R x R column-major, R = ns*d_out,
+ * a full, exactly symmetric matrix (the lower 64 x 64 tiles are computed and mirrored on store).  mean (ns x d_out, may be NULL) is
+ * bitwise what sgp_predict returns.  The diagonal blocks cov[(.,s),(.,s)] are sgp_predict_var's values UP TO ROUNDING, not bitwise:
+ * here k(x_s, x_s') - z_s . z_s' is one subtraction of a matrix-core sum, there sigma2 minus the partial sums of |z|^2, and the
+ * Sigma_v forms are contracted in different orders.
+ * sgp_sample_f: forms the same cov, adds sample_jitter to its diagonal, factors it (cov + sample_jitter I = L_C L_C', the dense
+ * factorisation of sgp_potrf, lower) and returns samples[:, k] = vec(mean) + L_C eps[:, k] for the caller's standard normals eps
+ * (R x n_samples, column-major; samples alike).  The library holds no random state: identical calls agree bitwise.  The strictly
+ * upper part of L_C is never read: eps = e_j returns column j of L_C added to the mean, rows < j the mean itself.  info (3 entries,
+ * may be NULL): the failing leading minor (0: none) of K_uu, of Sigma_v and of cov + sample_jitter I; the return value is the first
+ * positive one and sgp_last_error names the matrix.
+ * Both calls follow sgp_predict_var: blocking; everything in call scratch, nothing the sweep keeps written (sgp_sweep_kind, the
+ * theta objective and the resident statistics are unaffected); the same posterior rules and refusals; unknown flags SGP_ERR_ARG;
+ * ns = 0 returns 0 with nothing done; an installed all-reduce hook is neither called nor a reason to refuse; K(Xu, X*) goes through
+ * in chunks, and every sum runs in an order fixed by (ns, M, d_out): results do not depend on the chunk size.  Also refused with
+ * SGP_ERR_ARG: a NULL Xstar or cov; a NULL samples or eps; n_samples < 1; ns*d_out > SGP_JOINT_MAX_ROWS; a non-finite Xstar, eps or
+ * sample_jitter, or a negative sample_jitter; SGP_PREDICT_NOISE with a W that is not positive definite (as sgp_psi_predict). */
+#define SGP_JOINT_MAX_ROWS 8192     /* ns * d_out; 512 MiB of covariance */
+int sgp_predict_joint(sgp_handle* h, const double* Xstar /* D x ns, host */, int64_t ns, const double* mu_v, const double* Sigma_v,
+                      int32_t flags /* 0 | SGP_PREDICT_NOISE */, double* mean /* ns x d_out, may be NULL */,
+                      double* cov /* R x R column-major, R = ns d_out */);
+int sgp_sample_f(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v, int32_t flags,
+                 double sample_jitter, const double* eps /* R x n_samples, host, standard normals */, int64_t n_samples,
+                 double* mean /* ns x d_out, may be NULL */, double* samples /* R x n_samples */, int64_t* info /* 3, may be NULL */);
+
 /* sgp_in_message: the :in log-messages of many nodes in one call and, with cubature weights, the moment-matched marginals of the
  * Gaussian x log-pdf products -- @rule MultiSGP(:in) (GPnode/MultiSGPnode.jl:162-208) / UniSGP(:in) (GPnode/UniSGPnode.jl:107-122)
  * and ReactiveMP.prod(GenericProd, Gaussian, Continuous*LogPdf) (GPnode/MultiSGPnode.jl:37-44, GPnode/UniSGPnode.jl:39-54).

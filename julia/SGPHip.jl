@@ -164,6 +164,40 @@ function predict_var(h::Handle, Xstar::Matrix{Float64}, μ_v = nothing, Σ_v = n
     return mean, var
 end
 
+# predictive mean and JOINT covariance over all test points (include/sgp_hip.h, sgp_predict_joint), call for call with the Python
+# layer's SGPDevice.predict_joint: cov is R × R, R = ns d_out, exactly symmetric; row i ns + s (0-based) is output i at point s,
+# the order of vec(mean).  Like the rest of this file it has never been executed: only the ccall signature is stated here.
+function predict_joint(h::Handle, Xstar::Matrix{Float64}, μ_v = nothing, Σ_v = nothing; noise::Bool = false)
+    ns = size(Xstar, 2)
+    R = ns * h.d_out
+    mean = zeros(ns, h.d_out)
+    cov = zeros(R, R)
+    μp = μ_v === nothing ? C_NULL : Vector{Float64}(μ_v)
+    Σp = Σ_v === nothing ? C_NULL : Matrix{Float64}(Σ_v)
+    check(ccall((:sgp_predict_joint, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, Xstar, ns, μp, Σp, Int32(noise ? 1 : 0), mean, cov), h.ptr)
+    return mean, cov
+end
+
+# posterior function samples (sgp_sample_f), call for call with SGPDevice.sample_f: samples[:, k] = vec(mean) + L_C eps[:, k] with
+# L_C L_C' = cov + sample_jitter I and the caller's standard normals eps (R × n_samples; the library holds no random state)
+function sample_f(h::Handle, Xstar::Matrix{Float64}, eps::Matrix{Float64}, μ_v = nothing, Σ_v = nothing; sample_jitter::Float64 = 0.0,
+                  noise::Bool = false)
+    ns = size(Xstar, 2)
+    R = ns * h.d_out
+    size(eps, 1) == R || error("sample_f: eps must have ns * d_out = $R rows")
+    n_samples = size(eps, 2)
+    mean = zeros(ns, h.d_out)
+    samples = zeros(R, n_samples)
+    info = zeros(Int64, 3)
+    μp = μ_v === nothing ? C_NULL : Vector{Float64}(μ_v)
+    Σp = Σ_v === nothing ? C_NULL : Matrix{Float64}(Σ_v)
+    check(ccall((:sgp_sample_f, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Int64,
+                                            Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, Xstar, ns, μp, Σp, Int32(noise ? 1 : 0), sample_jitter, eps, n_samples, mean, samples, info), h.ptr)
+    return mean, samples
+end
+
 # the :in log-messages of many nodes and their moment-matched marginals in one call (include/sgp_hip.h, sgp_in_message): X is
 # D × n, node t owns the columns node_start[t] + 1 : node_start[t + 1] (0-based offsets, n_nodes + 1 entries), y_mean is
 # n_nodes × d_out; weights === nothing returns the closure values alone, else (logpdf, log_norm, mean D × n_nodes,

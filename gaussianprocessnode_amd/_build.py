@@ -17,7 +17,7 @@ LIB = os.path.join(CSRC, "libsgp_hip.so")
 VARIANTS = {"trace": ("libsgp_hip_trace.so", ["-DSGP_SWEEP_TRACE", "-DSGP_STEP_TRACE"])}
 SOURCES = [os.path.join(CSRC, "sgp_api.hip")]
 HEADERS = [os.path.join(CSRC, "sgp_kernels.hip.h"), os.path.join(CSRC, "point_scratch.h"),
-           os.path.join(os.path.dirname(HERE), "include", "sgp_hip.h")]
+           os.path.join(CSRC, "descent_state.h"), os.path.join(os.path.dirname(HERE), "include", "sgp_hip.h")]
 
 
 def _hipcc() -> str:

@@ -3313,6 +3313,14 @@ extern "C" int sgp_theta_objective_xu(sgp_handle* h, double* value, double* grad
 // read from where the optimiser kernel wrote them.  The host never waits inside the loop; factorisation failures are
 // counted on the device (the step is then skipped) and reported by sgp_train_end.
 // ------------------------------------------------------------------------------------------------
+// the optimiser state and the parameter block the optimiser kernels write, allocated on first use (the descents share them)
+static int descent_device_state(sgp_handle* h) {
+    if (h->dTrain) return 0;
+    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
+    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
+    return 0;
+}
+
 extern "C" int sgp_train_begin(sgp_handle* h, const double* X, const double* y, int64_t n_total, const double* theta_raw,
                                int32_t n_ell, double jitter, double eta, double beta1, double beta2, double eps) {
     if (!h || !X || !y || !theta_raw) return fail(h, SGP_ERR_ARG, "sgp_train_begin: null argument");
@@ -3335,10 +3343,7 @@ extern "C" int sgp_train_begin(sgp_handle* h, const double* X, const double* y, 
         HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainY), sizeof(double) * (size_t)n_total));
         h->train_N = n_total;
     }
-    if (!h->dTrain) {
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
-    }
+    if (int drc = descent_device_state(h)) return drc;
     HIPCHK(h, hipMemcpy(h->dTrainX, X, sizeof(double) * (size_t)n_total * h->D, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->dTrainY, y, sizeof(double) * (size_t)n_total, hipMemcpyHostToDevice));
     TrainState st;
@@ -3486,116 +3491,6 @@ extern "C" int sgp_train_end(sgp_handle* h, double* theta_raw, int64_t* counts) 
     h->swept_local = false;
     if (theta_raw) for (int i = 0; i <= h->n_ell; ++i) theta_raw[i] = st.theta[i];
     if (counts) { counts[0] = (int64_t)st.steps; counts[1] = (int64_t)st.rejected; }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Device-paced kernel-parameter descent at a held posterior: phase 2 of the pendulum's `PerformInference`
-// (experiments/Pendulum_Wishart_2d.ipynb cell 16: 100 times grad_llh_multi! + Flux.Optimise.update!(AdaMax, theta, grad) with
-// q(x), q(v) and q(W) held), and the same loop for UniSGP.  Per step, all on the library's own stream: the re-evaluation of
-// sgp_theta_objective at theta_k (enqueue_restats: K_uu chain, K_uf, Psi2, B), the value, the gradient with BOTH halves on this
-// stream, and k_descend_step (value out, AdaMax, softplus(theta_k+1) written where the next step's k_prep_xu reads it).  Stream
-// order is the whole ordering argument: step k + 1's re-evaluation overwrites K_uu^-1 and the statistics that step k's gradient
-// reads, and it sits behind that gradient on the same stream.  No device-word wait is enqueued.  The host waits once.
-// ------------------------------------------------------------------------------------------------
-extern "C" int sgp_theta_descend(sgp_handle* h, double* theta_raw, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2,
-                                 double eps, double* opt_state, double* values, int64_t* counts) {
-    if (!h || !theta_raw) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: null argument");
-    if (int prc = refuse_exact_psi(h, "sgp_theta_descend")) return prc;
-    if (h->training) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: a device-paced training run is open (sgp_train_end first)");
-    if (n_ell != 1 && n_ell != h->D) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: n_ell must be 1 or D");
-    if (steps < 0) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: steps must be >= 0");
-    if (!(eta > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
-        return fail(h, SGP_ERR_ARG, "sgp_theta_descend: eta > 0 and beta1, beta2 in [0, 1) required");
-    if (!h->swept) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: needs a finished sweep or sgp_set_posterior (q(v))");
-    if (!h->have_data || !h->have_kernel) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: data and kernel must be set");
-    if (h->allreduce) return fail(h, SGP_ERR_ARG, "sgp_theta_descend: data-sharded descent is not supported (remove the hook)");
-    const int np = 1 + n_ell;
-    if (opt_state) {
-        // (a power is beta^t, t >= 1: inside (0, 1), or exactly 0 for a beta of 0)
-        const double b[2] = {beta1, beta2};
-        for (int i = 0; i < 2; ++i) {
-            const double pw = opt_state[2 * np + i];
-            if (!(pw < 1.0) || !(pw > 0.0 || (pw == 0.0 && b[i] == 0.0)))
-                return fail(h, SGP_ERR_ARG, "sgp_theta_descend: the running powers of beta in opt_state must lie in (0, 1)");
-        }
-    }
-    if (counts) counts[0] = counts[1] = 0;
-    if (steps == 0) return 0;
-    if (int wrc = sync_checked(h)) return wrc;
-    hipStream_t s = h->own;
-    if (!h->dTrain) {
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
-    }
-    if (int arc = alloc_theta_grad(h)) return arc;
-    DevBuf dvals;
-    HIPCHK(h, dvals.alloc(sizeof(double) * (size_t)steps));
-    std::vector<double> vals((size_t)steps, std::numeric_limits<double>::quiet_NaN());
-    HIPCHK(h, hipMemcpy(dvals.p, vals.data(), sizeof(double) * (size_t)steps, hipMemcpyHostToDevice));
-    TrainState st;
-    memset(&st, 0, sizeof st);
-    for (int i = 0; i < np; ++i) {
-        st.theta[i] = theta_raw[i];
-        if (opt_state) { st.m[i] = opt_state[i]; st.u[i] = opt_state[np + i]; }
-    }
-    st.bp[0] = opt_state ? opt_state[2 * np] : beta1;
-    st.bp[1] = opt_state ? opt_state[2 * np + 1] : beta2;
-    st.eta = eta; st.beta1 = beta1; st.beta2 = beta2; st.eps = eps;
-    HIPCHK(h, hipMemcpy(h->dTrain, &st, sizeof st, hipMemcpyHostToDevice));
-    // noise, E[log w], the prior and the jitter stay what the setters left; sigma2 and the lengthscales come from theta on the device
-    HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
-    h->n_ell = n_ell;
-    h->params_src = h->dTrainParams;
-    h->in_flight = true;
-    const bool multi = h->dout > 1;
-    int rc = 0;
-    hipLaunchKernelGGL(k_train_adamax, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)nullptr, (const double*)nullptr,
-                       h->dTrainParams, h->D, n_ell, 0, (const int*)nullptr, (const Params*)nullptr, (const double*)nullptr);
-    const double* Rv = h->dR;
-    rc = theta_Rv(h, s, &Rv);                                 // R_v: once per call, q(v) is held
-    const double* scal = h->dStats + (size_t)h->Mp * h->Mp + (size_t)h->Mp * h->dout;
-    for (int k = 0; k < steps && !rc; ++k) {
-        h->params_gen++;                                       // theta moved: k_prep_xu mirrors the parameters again
-        rc = enqueue_restats(h, s);
-        if (!rc) {
-            if (multi) rc = enqueue_theta_multi_value(h, s, Rv);
-            else enqueue_theta_uni_sums(h, s, Rv);
-        }
-        if (!rc) rc = enqueue_theta_grad(h, s, Rv, true);
-        if (!rc)
-            hipLaunchKernelGGL(k_descend_step, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)h->dGrad, (const double*)h->dOut2, scal,
-                               (const Params*)h->dParams, (const int*)h->dInfo, (const int*)(h->dInfo + 3), dvals.as<double>(), k,
-                               h->dTrainParams, h->D, n_ell, multi ? 1 : 0);
-    }
-    // whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path
-    const hipError_t werr = wait_stream(s);
-    const hipError_t lerr = hipGetLastError();
-    h->params_src = h->hParams;
-    h->in_flight = false;
-    h->params_gen++;
-    stats_drop(h, STATS_REUSE | STATS_QV);                     // the resident statistics belong to the last evaluated theta
-    h->swept_local = false;
-    if (rc) return rc;
-    HIPCHK(h, werr);
-    HIPCHK(h, lerr);
-    HIPCHK(h, hipMemcpy(&st, h->dTrain, sizeof st, hipMemcpyDeviceToHost));
-    Params P;
-    HIPCHK(h, hipMemcpy(&P, h->dTrainParams, sizeof P, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(vals.data(), dvals.p, sizeof(double) * (size_t)steps, hipMemcpyDeviceToHost));
-    // the handle's kernel is softplus(theta_out), as the device formed it (as after sgp_train_end)
-    h->hParams->sigma2 = P.sigma2;
-    for (int d = 0; d < h->D; ++d) h->hParams->inv_ell[d] = P.inv_ell[d];
-    for (int i = 0; i < np; ++i) {
-        theta_raw[i] = st.theta[i];
-        if (opt_state) { opt_state[i] = st.m[i]; opt_state[np + i] = st.u[i]; }
-    }
-    if (opt_state) { opt_state[2 * np] = st.bp[0]; opt_state[2 * np + 1] = st.bp[1]; }
-    if (values) for (int k = 0; k < steps; ++k) values[k] = vals[(size_t)k];
-    if (counts) { counts[0] = (int64_t)st.steps; counts[1] = st.stop > 0.0 ? (int64_t)st.stop : 0; }
-    if (int src = check_sync_status(h)) return src;
-    if (st.stop != 0.0)
-        return factor_status(h, (int)st.stop, ("sgp_theta_descend, step " + std::to_string((int64_t)st.steps) + ": K_uu").c_str());
     return 0;
 }
 
@@ -3808,230 +3703,271 @@ extern "C" int sgp_theta_objective_psi_xu(sgp_handle* h, const double* mean, con
     return theta_objective_psi_call(h, "sgp_theta_objective_psi_xu", mean, cov, y_mean, n_nodes, value, grad, info, grad_xu, true);
 }
 
-// sgp_theta_descend with the objective above: per step, all on the library's own stream, one evaluation at theta_k and
-// k_descend_step_psi (value out, AdaMax, softplus(theta_k+1) written where the next step's k_prep_xu reads it).  The inputs are
-// uploaded and R_v is formed once per call.  The host enqueues and waits once.
-extern "C" int sgp_theta_descend_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
-                                     double* theta_raw, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2, double eps,
-                                     double* opt_state, double* values, int64_t* counts) {
-    const char* name = "sgp_theta_descend_psi";
-    if (!h || !theta_raw) return fail(h, SGP_ERR_ARG, "sgp_theta_descend_psi: null argument");
-    if (n_ell != 1 && n_ell != h->D) return refuse(h, name, "n_ell must be 1 or D");
-    if (steps < 0) return refuse(h, name, "steps must be >= 0");
-    if (!(eta > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+// ------------------------------------------------------------------------------------------------
+// The device-paced AdaMax descents at a held q(v) (include/sgp_hip.h):
+//     sgp_theta_descend          point (cubature) objective    x = theta_raw
+//     sgp_theta_descend_psi      exact-Psi objective           x = theta_raw
+//     sgp_inducing_descend       point objective               x = [theta_raw | vec Xu], or vec Xu
+//     sgp_inducing_descend_psi   exact-Psi objective           x = [theta_raw | vec Xu], or vec Xu
+// Phase 2 of the pendulum's `PerformInference` (experiments/Pendulum_Wishart_2d.ipynb cell 16: 100 times grad_llh_multi! +
+// Flux.Optimise.update!(AdaMax, theta, grad) with q(x), q(v) and q(W) held), the same loop for UniSGP, and both with the inducing
+// inputs in the optimised vector.  One program (descent_run) with one part that differs, the step each entry point enqueues: one
+// evaluation of its objective at (softplus(theta_k), Xu_k) with the gradient, then the optimiser -- the scalar launch (value out,
+// AdaMax on theta, softplus(theta_k+1) written where the next step's k_prep_xu reads it) and, where Xu is optimised, the elementwise
+// launch on dXu behind it.  Everything runs on the library's own stream and stream order is the whole ordering argument: step k + 1's
+// evaluation overwrites what step k's gradient reads (K_uu^-1, the statistics, the scaled copies of Xu) and sits behind that gradient
+// and behind the optimiser's writes.  No device-word wait is enqueued.  The host enqueues and waits once.
+// ------------------------------------------------------------------------------------------------
+struct DescentRun {
+    const char* name;               // the entry point: the prefix of every message
+    // What differs between the entry points on purpose.
+    // psi: the exact-Psi pair.  Its evaluations live in call scratch and take dTrainParams as an argument, so the handle's parameter
+    //   source stays, params_gen moves once (afterwards: the handle's kernel changed), n_ell is written after a run that came back,
+    //   the resident statistics are not written (moved inducing inputs only end their reuse), no sweep hand-off is involved
+    //   (no check_sync_status) and counts has a third entry, the indefinite node.  The point pair re-forms the resident statistics per
+    //   step from dTrainParams: params_src is switched for the loop, params_gen moves per step (k_prep_xu mirrors again) and afterwards,
+    //   n_ell is written before the loop, and the statistics end as those of the last evaluated point, q(v)'s no longer.
+    bool psi;
+    // any_theta: sgp_theta_descend alone does not refuse a non-finite theta_raw (the other three do); kept as it was found
+    bool any_theta;
+    // the caller's arguments (Xu: NULL in a theta-only run)
+    double* theta_raw;
+    int32_t n_ell;
+    double* Xu;
+    int32_t steps;
+    double eta, beta1, beta2, eps;
+    double *opt_state, *values;
+    int64_t* counts;
+    DescentLayout l;                // the optimised vector (descent_state.h).  nx = 0, a theta-only run: no Xu upload, no Mom, no Pub
+    double *Mom = nullptr, *Pub = nullptr, *Vals = nullptr;     // device: the moments of Xu, the published words, the values
+    void zero_counts() const {
+        for (int i = 0; counts && i < (psi ? 3 : 2); ++i) counts[i] = 0;
+    }
+};
+
+// what needs no handle state: checked before anything is touched.  `inducing`: Xu is in the optimised vector, `flags` says what else is
+static int descent_args(sgp_handle* h, DescentRun& r, bool inducing, int32_t flags) {
+    const char* name = r.name;
+    if (!h || !r.theta_raw) return refuse(h, name, "null argument");
+    if (inducing && !r.Xu) return refuse(h, name, "Xu is NULL");
+    if (inducing && (!(flags & SGP_DESCEND_XU) || (flags & ~(SGP_DESCEND_THETA | SGP_DESCEND_XU))))
+        return refuse(h, name, "flags must contain SGP_DESCEND_XU and nothing but SGP_DESCEND_THETA beside it (theta alone: sgp_theta_descend)");
+    if (r.n_ell != 1 && r.n_ell != h->D) return refuse(h, name, "n_ell must be 1 or D");
+    if (r.steps < 0) return refuse(h, name, "steps must be >= 0");
+    if (!(r.eta > 0.0) || !(r.beta1 >= 0.0 && r.beta1 < 1.0) || !(r.beta2 >= 0.0 && r.beta2 < 1.0))
         return refuse(h, name, "eta > 0 and beta1, beta2 in [0, 1) required");
-    const int np = 1 + n_ell;
-    if (opt_state) {
-        // (a power is beta^t, t >= 1: inside (0, 1), or exactly 0 for a beta of 0)
-        const double bt[2] = {beta1, beta2};
-        for (int i = 0; i < 2; ++i) {
-            const double pw = opt_state[2 * np + i];
-            if (!(pw < 1.0) || !(pw > 0.0 || (pw == 0.0 && bt[i] == 0.0)))
-                return refuse(h, name, "the running powers of beta in opt_state must lie in (0, 1)");
-        }
-    }
-    for (int i = 0; i < np; ++i)
-        if (!std::isfinite(theta_raw[i])) return refuse(h, name, "theta_raw must be finite");
-    if (counts) counts[0] = counts[1] = counts[2] = 0;
-    if (steps == 0) return 0;
-    if (!mean || !y_mean) return fail(h, SGP_ERR_ARG, "sgp_theta_descend_psi: null argument");
+    r.l = descent_layout(r.n_ell, !inducing || (flags & SGP_DESCEND_THETA) != 0, inducing ? h->M * h->D : 0);
+    if (r.opt_state && !descent_powers_ok(r.l, r.opt_state, r.beta1, r.beta2))
+        return refuse(h, name, "the running powers of beta in opt_state must lie in (0, 1)");
+    for (int i = 0; !r.any_theta && i < r.l.ntheta; ++i)
+        if (!std::isfinite(r.theta_raw[i])) return refuse(h, name, "theta_raw must be finite");
+    for (int i = 0; i < r.l.nx; ++i)
+        if (!std::isfinite(r.Xu[i])) return refuse(h, name, "Xu must be finite");
+    return 0;
+}
+
+// the handle state the two pairs refuse (the exact-Psi pair's psi_theta_ready also refuses an open training run: dTrain is its state)
+static int descent_point_ready(sgp_handle* h, const char* name) {
+    if (int prc = refuse_exact_psi(h, name)) return prc;
+    if (int trc = refuse_training(h, name)) return trc;
+    if (!h->swept) return refuse(h, name, "needs a finished sweep or sgp_set_posterior (q(v))");
+    if (!h->have_data || !h->have_kernel) return refuse(h, name, "data and kernel must be set");
+    if (h->allreduce) return refuse(h, name, "data-sharded descent is not supported (remove the hook)");
+    return 0;
+}
+static int descent_psi_ready(sgp_handle* h, const char* name, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes) {
+    if (!mean || !y_mean) return refuse(h, name, "null argument");
     if (n_nodes < 1) return refuse(h, name, "n_nodes must be >= 1");
-    if (int rc = psi_theta_ready(h, name, mean, cov, y_mean, n_nodes)) return rc;      // (refuses an open run: dTrain below is its state)
-    if (int wrc = sync_checked(h)) return wrc;
-    hipStream_t s = h->own;
-    if (!h->dTrain) {
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
-    }
-    const PointShape shape = psi_theta_shape(h, n_nodes);
-    PsiThetaScratch b;
-    if (int crc = psi_theta_carve(h, shape, cov != nullptr, (size_t)steps, &b)) return crc;
-    if (int rc = psi_theta_upload(h, b, mean, cov, y_mean, n_nodes)) return rc;
-    std::vector<double> vals((size_t)steps, std::numeric_limits<double>::quiet_NaN());
-    HIPCHK(h, hipMemcpy(b.Vals, vals.data(), sizeof(double) * (size_t)steps, hipMemcpyHostToDevice));
+    return psi_theta_ready(h, name, mean, cov, y_mean, n_nodes);
+}
+
+// The run's state onto the device (the caller has waited for the handle): theta and its moments into dTrain, the kernel block, NaN
+// values; with Xu in the vector, Xu into dXu, its moments and a cleared publish block; then softplus(theta_0) where the first
+// k_prep_xu reads it.
+static int descent_begin(sgp_handle* h, hipStream_t s, const DescentRun& r) {
+    const size_t nx = (size_t)r.l.nx;
     TrainState st;
-    memset(&st, 0, sizeof st);
-    for (int i = 0; i < np; ++i) {
-        st.theta[i] = theta_raw[i];
-        if (opt_state) { st.m[i] = opt_state[i]; st.u[i] = opt_state[np + i]; }
-    }
-    st.bp[0] = opt_state ? opt_state[2 * np] : beta1;
-    st.bp[1] = opt_state ? opt_state[2 * np + 1] : beta2;
-    st.eta = eta; st.beta1 = beta1; st.beta2 = beta2; st.eps = eps;
+    descent_pack(r.l, r.theta_raw, r.opt_state, r.eta, r.beta1, r.beta2, r.eps, &st);
     HIPCHK(h, hipMemcpy(h->dTrain, &st, sizeof st, hipMemcpyHostToDevice));
     // noise, E[log w], the prior and the jitter stay what the setters left; sigma2 and the lengthscales come from theta on the device
     HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
-    h->in_flight = true;
-    const MeanW w(h);
-    hipLaunchKernelGGL(k_train_adamax, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)nullptr, (const double*)nullptr,
-                       h->dTrainParams, h->D, n_ell, 0, (const int*)nullptr, (const Params*)nullptr, (const double*)nullptr);
-    const double* Rv = h->dR;
-    int rc = theta_Rv(h, s, &Rv);                             // R_v: once per call, q(v) is held
-    for (int k = 0; k < steps && !rc; ++k) {
-        rc = psi_theta_enqueue(h, s, b, shape, cov != nullptr, h->dTrainParams, Rv, w, n_ell);
-        if (!rc)
-            hipLaunchKernelGGL(k_descend_step_psi, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)b.Out, (const int*)b.Info,
-                               (const int*)b.Status, b.Vals, k, h->dTrainParams, h->D, n_ell);
+    if (nx) {
+        HIPCHK(h, hipMemcpy(h->dXu, r.Xu, sizeof(double) * nx, hipMemcpyHostToDevice));
+        h->have_inducing = true;
+        if (r.opt_state) {
+            HIPCHK(h, hipMemcpy(r.Mom, descent_state_mx(r.l, r.opt_state), sizeof(double) * nx, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(r.Mom + nx, descent_state_ux(r.l, r.opt_state), sizeof(double) * nx, hipMemcpyHostToDevice));
+        } else {
+            HIPCHK(h, hipMemsetAsync(r.Mom, 0, sizeof(double) * 2 * nx, s));   // (on `s`: in front of the kernels by stream order)
+        }
+        HIPCHK(h, hipMemsetAsync(r.Pub, 0, sizeof(double) * INDUCING_PUB, s));
     }
-    // whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path
+    const std::vector<double> nan((size_t)r.steps, std::numeric_limits<double>::quiet_NaN());
+    HIPCHK(h, hipMemcpy(r.Vals, nan.data(), sizeof(double) * (size_t)r.steps, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_train_adamax, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)nullptr, (const double*)nullptr,
+                       h->dTrainParams, h->D, r.n_ell, 0, (const int*)nullptr, (const Params*)nullptr, (const double*)nullptr);
+    return 0;
+}
+
+// Whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path.  `rc`: the
+// enqueueing status, reported first; then the wait's; then a launch's.
+static int descent_wait(sgp_handle* h, hipStream_t s, int rc) {
     const hipError_t werr = wait_stream(s);
     const hipError_t lerr = hipGetLastError();
     h->in_flight = false;
     if (rc) return rc;
     HIPCHK(h, werr);
     HIPCHK(h, lerr);
-    HIPCHK(h, hipMemcpy(&st, h->dTrain, sizeof st, hipMemcpyDeviceToHost));
-    Params P;
-    HIPCHK(h, hipMemcpy(&P, h->dTrainParams, sizeof P, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(vals.data(), b.Vals, sizeof(double) * (size_t)steps, hipMemcpyDeviceToHost));
-    // the handle's kernel is softplus(theta_out), as the device formed it (as after sgp_theta_descend)
-    h->hParams->sigma2 = P.sigma2;
-    for (int d = 0; d < h->D; ++d) h->hParams->inv_ell[d] = P.inv_ell[d];
-    h->n_ell = n_ell;
-    h->params_gen++;
-    for (int i = 0; i < np; ++i) {
-        theta_raw[i] = st.theta[i];
-        if (opt_state) { opt_state[i] = st.m[i]; opt_state[np + i] = st.u[i]; }
-    }
-    if (opt_state) { opt_state[2 * np] = st.bp[0]; opt_state[2 * np + 1] = st.bp[1]; }
-    if (values) for (int k = 0; k < steps; ++k) values[k] = vals[(size_t)k];
-    const int node = st.stop <= -2.0 ? (int)(-st.stop - 1.0) : 0;
-    const int kuu = st.stop <= -2.0 ? 0 : (int)st.stop;
-    if (counts) { counts[0] = (int64_t)st.steps; counts[1] = kuu > 0 ? kuu : 0; counts[2] = node; }
-    if (st.stop != 0.0) return psi_theta_status(h, std::string(name) + ", step " + std::to_string((int64_t)st.steps), node, kuu);
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Device-paced AdaMax descent in the inducing inputs at a held q(v) (include/sgp_hip.h: sgp_inducing_descend,
-// sgp_inducing_descend_psi): sgp_theta_descend / sgp_theta_descend_psi with the gradient in Xu behind each step's theta
-// gradient and the optimiser on x = [theta_raw | vec Xu] (or vec Xu alone).  Stream order is again the whole ordering argument: the
-// elementwise optimiser launch writes dXu behind the last kernel that read it or its scaled copies at step k, and step k + 1's
-// k_prep_xu launches (the K_uu chain's and the main stream's, both re-run because params_gen moves; the Psi path's chain and its node
-// kernels, which read dXu itself) sit behind that write.  The host enqueues and waits once.
-// ------------------------------------------------------------------------------------------------
-struct InducingRun {
-    int nt = 0, nx = 0, np = 0;     // optimised theta entries (0: theta held), inducing coordinates, their sum
-    int ntheta = 0;                 // 1 + n_ell
-    bool learn = false;
-};
-
-// what both calls check before anything is touched
-static int inducing_descend_args(sgp_handle* h, const char* name, const double* theta_raw, int32_t n_ell, const double* Xu, int32_t flags,
-                                 int32_t steps, double eta, double beta1, double beta2, const double* opt_state, InducingRun* r) {
-    if (!h || !theta_raw) return refuse(h, name, "null argument");
-    if (!Xu) return refuse(h, name, "Xu is NULL");
-    if (!(flags & SGP_DESCEND_XU) || (flags & ~(SGP_DESCEND_THETA | SGP_DESCEND_XU)))
-        return refuse(h, name, "flags must contain SGP_DESCEND_XU and nothing but SGP_DESCEND_THETA beside it (theta alone: sgp_theta_descend)");
-    if (n_ell != 1 && n_ell != h->D) return refuse(h, name, "n_ell must be 1 or D");
-    if (steps < 0) return refuse(h, name, "steps must be >= 0");
-    if (!(eta > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
-        return refuse(h, name, "eta > 0 and beta1, beta2 in [0, 1) required");
-    r->learn = (flags & SGP_DESCEND_THETA) != 0;
-    r->ntheta = 1 + n_ell;
-    r->nt = r->learn ? r->ntheta : 0;
-    r->nx = h->M * h->D;
-    r->np = r->nt + r->nx;
-    if (opt_state) {
-        // (a power is beta^t, t >= 1: inside (0, 1), or exactly 0 for a beta of 0)
-        const double bt[2] = {beta1, beta2};
-        for (int i = 0; i < 2; ++i) {
-            const double pw = opt_state[2 * (size_t)r->np + i];
-            if (!(pw < 1.0) || !(pw > 0.0 || (pw == 0.0 && bt[i] == 0.0)))
-                return refuse(h, name, "the running powers of beta in opt_state must lie in (0, 1)");
-        }
-    }
-    for (int i = 0; i < r->ntheta; ++i)
-        if (!std::isfinite(theta_raw[i])) return refuse(h, name, "theta_raw must be finite");
-    for (int i = 0; i < r->nx; ++i)
-        if (!std::isfinite(Xu[i])) return refuse(h, name, "Xu must be finite");
-    if (h->allreduce) return refuse(h, name, "data-sharded descent is not supported (remove the hook)");
-    return 0;
-}
-
-// The run's state onto the device (the caller has waited for the handle): theta and its moments into dTrain, the kernel block, Xu into
-// dXu, the inducing coordinates' moments, a cleared publish block and NaN values into call scratch; then softplus(theta_0) where the
-// first k_prep_xu reads it.
-static int inducing_descend_begin(sgp_handle* h, hipStream_t s, const InducingRun& r, const InducingStepScratch& o, const double* theta_raw,
-                                  const double* Xu, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2, double eps,
-                                  const double* opt_state) {
-    TrainState st;
-    memset(&st, 0, sizeof st);
-    for (int i = 0; i < r.ntheta; ++i) {
-        st.theta[i] = theta_raw[i];
-        if (opt_state && r.learn) { st.m[i] = opt_state[i]; st.u[i] = opt_state[r.np + i]; }
-    }
-    st.bp[0] = opt_state ? opt_state[2 * (size_t)r.np] : beta1;
-    st.bp[1] = opt_state ? opt_state[2 * (size_t)r.np + 1] : beta2;
-    st.eta = eta; st.beta1 = beta1; st.beta2 = beta2; st.eps = eps;
-    HIPCHK(h, hipMemcpy(h->dTrain, &st, sizeof st, hipMemcpyHostToDevice));
-    // noise, E[log w], the prior and the jitter stay what the setters left; sigma2 and the lengthscales come from theta on the device
-    HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->dXu, Xu, sizeof(double) * (size_t)r.nx, hipMemcpyHostToDevice));
-    h->have_inducing = true;
-    if (opt_state) {
-        HIPCHK(h, hipMemcpy(o.Mom, opt_state + r.nt, sizeof(double) * (size_t)r.nx, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(o.Mom + r.nx, opt_state + r.np + r.nt, sizeof(double) * (size_t)r.nx, hipMemcpyHostToDevice));
-    } else {
-        HIPCHK(h, hipMemsetAsync(o.Mom, 0, sizeof(double) * 2 * (size_t)r.nx, s));     // (on `s`: in front of the kernels by stream order)
-    }
-    HIPCHK(h, hipMemsetAsync(o.Pub, 0, sizeof(double) * INDUCING_PUB, s));
-    const std::vector<double> nan((size_t)steps, std::numeric_limits<double>::quiet_NaN());
-    HIPCHK(h, hipMemcpy(o.Vals, nan.data(), sizeof(double) * (size_t)steps, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_train_adamax, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)nullptr, (const double*)nullptr,
-                       h->dTrainParams, h->D, n_ell, 0, (const int*)nullptr, (const Params*)nullptr, (const double*)nullptr);
-    return 0;
-}
-
-static void launch_inducing_step_xu(sgp_handle* h, hipStream_t s, const InducingRun& r, const InducingStepScratch& o, const double* grad_xu,
-                                    double beta1, double beta2, double eps) {
-    hipLaunchKernelGGL(k_inducing_step_xu, dim3((unsigned)((r.nx + 255) / 256)), dim3(256), 0, s, (const double*)o.Pub, grad_xu, h->dXu, o.Mom,
-                       r.nx, beta1, beta2, eps);
-}
-
-// The run's results back (the caller has waited for the stream): the handle's kernel is softplus(theta_out) as the device formed it,
-// its inducing inputs are what dXu holds; theta, Xu, the state in AdaMax.get_state's layout for the joint vector, and the values
-static int inducing_descend_end(sgp_handle* h, const InducingRun& r, const InducingStepScratch& o, double* theta_raw, double* Xu,
-                                int32_t steps, double* opt_state, double* values, TrainState* st) {
+// The run's results back (the caller has waited for the stream): the handle's kernel is softplus(theta_out) as the device formed it
+// (as after sgp_train_end), its inducing inputs are what dXu holds; theta, Xu, the state in AdaMax.get_state's layout, and the values
+static int descent_end(sgp_handle* h, const DescentRun& r, TrainState* st) {
+    const size_t nx = (size_t)r.l.nx;
     HIPCHK(h, hipMemcpy(st, h->dTrain, sizeof *st, hipMemcpyDeviceToHost));
     Params P;
     HIPCHK(h, hipMemcpy(&P, h->dTrainParams, sizeof P, hipMemcpyDeviceToHost));
     h->hParams->sigma2 = P.sigma2;
     for (int d = 0; d < h->D; ++d) h->hParams->inv_ell[d] = P.inv_ell[d];
-    HIPCHK(h, hipMemcpy(Xu, h->dXu, sizeof(double) * (size_t)r.nx, hipMemcpyDeviceToHost));
-    for (int i = 0; i < r.ntheta; ++i) theta_raw[i] = st->theta[i];
-    if (opt_state) {
-        for (int i = 0; i < r.nt; ++i) { opt_state[i] = st->m[i]; opt_state[r.np + i] = st->u[i]; }
-        HIPCHK(h, hipMemcpy(opt_state + r.nt, o.Mom, sizeof(double) * (size_t)r.nx, hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(opt_state + r.np + r.nt, o.Mom + r.nx, sizeof(double) * (size_t)r.nx, hipMemcpyDeviceToHost));
-        opt_state[2 * (size_t)r.np] = st->bp[0];
-        opt_state[2 * (size_t)r.np + 1] = st->bp[1];
+    if (nx) HIPCHK(h, hipMemcpy(r.Xu, h->dXu, sizeof(double) * nx, hipMemcpyDeviceToHost));
+    descent_unpack(r.l, *st, r.theta_raw, r.opt_state);
+    if (nx && r.opt_state) {
+        HIPCHK(h, hipMemcpy(descent_state_mx(r.l, r.opt_state), r.Mom, sizeof(double) * nx, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(descent_state_ux(r.l, r.opt_state), r.Mom + nx, sizeof(double) * nx, hipMemcpyDeviceToHost));
     }
-    if (values) HIPCHK(h, hipMemcpy(values, o.Vals, sizeof(double) * (size_t)steps, hipMemcpyDeviceToHost));
+    if (r.values) HIPCHK(h, hipMemcpy(r.values, r.Vals, sizeof(double) * (size_t)r.steps, hipMemcpyDeviceToHost));
     return 0;
 }
 
-// Per step on the library's own stream: the re-evaluation of sgp_theta_objective at (softplus(theta_k), Xu_k) -- enqueue_restats; both
-// k_prep_xu launches read dXu, so the K_uu chain's mirror and the main stream's follow the moved inducing inputs --, the value, the theta
-// gradient with both halves on this stream, enqueue_xu_grad behind it (no side-stream wait: nothing ran there), k_inducing_step and
-// k_inducing_step_xu.
-extern "C" int sgp_inducing_descend(sgp_handle* h, double* theta_raw, int32_t n_ell, double* Xu, int32_t flags, int32_t steps, double eta,
-                                    double beta1, double beta2, double eps, double* opt_state, double* values, int64_t* counts) {
-    const char* name = "sgp_inducing_descend";
-    InducingRun r;
-    if (int rc = inducing_descend_args(h, name, theta_raw, n_ell, Xu, flags, steps, eta, beta1, beta2, opt_state, &r)) return rc;
-    if (int prc = refuse_exact_psi(h, name)) return prc;
-    if (int trc = refuse_training(h, name)) return trc;
-    if (!h->swept) return refuse(h, name, "needs a finished sweep or sgp_set_posterior (q(v))");
-    if (!h->have_data || !h->have_kernel) return refuse(h, name, "data and kernel must be set");
-    if (counts) counts[0] = counts[1] = 0;
+// st.stop as the ABI reports it (TrainState): counts = steps taken, K_uu's failing minor and, the exact-Psi pair, the indefinite node;
+// the status names the step
+static int descent_status(sgp_handle* h, const DescentRun& r, const TrainState& st) {
+    const bool at_node = r.psi && st.stop <= -2.0;
+    const int node = at_node ? (int)(-st.stop - 1.0) : 0;
+    const int kuu = at_node ? 0 : (int)st.stop;
+    if (r.counts) {
+        r.counts[0] = (int64_t)st.steps;
+        r.counts[1] = kuu > 0 ? kuu : 0;
+        if (r.psi) r.counts[2] = node;
+    }
+    if (!r.psi)
+        if (int src = check_sync_status(h)) return src;
+    if (st.stop == 0.0) return 0;
+    const std::string at = std::string(r.name) + ", step " + std::to_string((int64_t)st.steps);
+    return r.psi ? psi_theta_status(h, at, node, kuu) : factor_status(h, kuu, (at + ": K_uu").c_str());
+}
+
+// The run: the caller has checked, waited for the handle (sync_checked), made sure of the device state and carved its buffers.
+// `step(s, k, Rv)` enqueues step k -- the evaluation, then the optimiser -- and returns a status; a nonzero one ends the enqueueing.
+template <class Step>
+static int descent_run(sgp_handle* h, const DescentRun& r, Step&& step) {
+    hipStream_t s = h->own;
+    if (int brc = descent_begin(h, s, r)) return brc;
+    if (!r.psi) {
+        h->n_ell = r.n_ell;
+        h->params_src = h->dTrainParams;
+    }
+    h->in_flight = true;
+    const double* Rv = h->dR;
+    int rc = theta_Rv(h, s, &Rv);                             // R_v: once per call, q(v) is held
+    for (int k = 0; k < r.steps && !rc; ++k) {
+        if (!r.psi) h->params_gen++;                           // theta and Xu moved: k_prep_xu mirrors them again
+        rc = step(s, k, Rv);
+    }
+    rc = descent_wait(h, s, rc);
+    // what the handle holds now, on every path: a HIP failure invalidates what a finished run does
+    h->params_gen++;
+    if (r.l.nx) h->data_gen++;                                 // the inducing inputs moved, as after sgp_set_inducing
+    if (!r.psi) {
+        h->params_src = h->hParams;
+        stats_drop(h, STATS_REUSE | STATS_QV);                 // the resident statistics belong to the last evaluated (theta, Xu)
+        h->swept_local = false;
+    } else if (r.l.nx) {
+        stats_drop(h, STATS_REUSE);                            // (not written here, but no longer those of the handle's Xu)
+    }
+    if (rc) return rc;
+    TrainState st;
+    if (int erc = descent_end(h, r, &st)) return erc;
+    if (r.psi) h->n_ell = r.n_ell;
+    return descent_status(h, r, st);
+}
+
+// The point pair's evaluation: sgp_theta_objective at the device's (theta_k, Xu_k) -- enqueue_restats (K_uu chain, K_uf, Psi2, B; both
+// k_prep_xu launches read dXu and the parameter source, so the chain's mirror and the main stream's follow what moved), the value,
+// and the theta gradient with BOTH halves on this stream
+static int descent_point_eval(sgp_handle* h, hipStream_t s, const double* Rv) {
+    if (int rc = enqueue_restats(h, s)) return rc;
+    if (h->dout == 1) enqueue_theta_uni_sums(h, s, Rv);
+    else if (int rc = enqueue_theta_multi_value(h, s, Rv)) return rc;
+    return enqueue_theta_grad(h, s, Rv, true);
+}
+static const double* stats_scalars(const sgp_handle* h) { return h->dStats + (size_t)h->Mp * h->Mp + (size_t)h->Mp * h->dout; }
+
+static void launch_inducing_step_xu(sgp_handle* h, hipStream_t s, const DescentRun& r, const double* grad_xu) {
+    hipLaunchKernelGGL(k_inducing_step_xu, dim3((unsigned)((r.l.nx + 255) / 256)), dim3(256), 0, s, (const double*)r.Pub, grad_xu, h->dXu,
+                       r.Mom, r.l.nx, r.beta1, r.beta2, r.eps);
+}
+
+extern "C" int sgp_theta_descend(sgp_handle* h, double* theta_raw, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2,
+                                 double eps, double* opt_state, double* values, int64_t* counts) {
+    DescentRun r{"sgp_theta_descend", false, true, theta_raw, n_ell, nullptr, steps, eta, beta1, beta2, eps, opt_state, values, counts};
+    if (int rc = descent_args(h, r, false, 0)) return rc;
+    if (int rc = descent_point_ready(h, r.name)) return rc;
+    r.zero_counts();
     if (steps == 0) return 0;
     if (int wrc = sync_checked(h)) return wrc;
-    hipStream_t s = h->own;
-    if (!h->dTrain) {
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
-    }
+    if (int drc = descent_device_state(h)) return drc;
+    if (int arc = alloc_theta_grad(h)) return arc;
+    DevBuf dvals;                                              // (the call carves no scratch: a buffer of its own, as it always had)
+    HIPCHK(h, dvals.alloc(sizeof(double) * (size_t)steps));
+    r.Vals = dvals.as<double>();
+    const int multi = h->dout > 1 ? 1 : 0;
+    return descent_run(h, r, [&](hipStream_t s, int k, const double* Rv) {
+        if (int rc = descent_point_eval(h, s, Rv)) return rc;
+        hipLaunchKernelGGL(k_descend_step, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)h->dGrad, (const double*)h->dOut2,
+                           stats_scalars(h), (const Params*)h->dParams, (const int*)h->dInfo, (const int*)(h->dInfo + 3), r.Vals, k,
+                           h->dTrainParams, h->D, n_ell, multi);
+        return 0;
+    });
+}
+
+// (steps = 0 returns before the inputs are looked at; the other three answer it behind every refusal)
+extern "C" int sgp_theta_descend_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
+                                     double* theta_raw, int32_t n_ell, int32_t steps, double eta, double beta1, double beta2, double eps,
+                                     double* opt_state, double* values, int64_t* counts) {
+    DescentRun r{"sgp_theta_descend_psi", true, false, theta_raw, n_ell, nullptr, steps, eta, beta1, beta2, eps, opt_state, values, counts};
+    if (int rc = descent_args(h, r, false, 0)) return rc;
+    r.zero_counts();
+    if (steps == 0) return 0;
+    if (int rc = descent_psi_ready(h, r.name, mean, cov, y_mean, n_nodes)) return rc;
+    if (int wrc = sync_checked(h)) return wrc;
+    if (int drc = descent_device_state(h)) return drc;
+    const bool has_cov = cov != nullptr;
+    const PointShape shape = psi_theta_shape(h, n_nodes);
+    PsiThetaScratch b;
+    if (int crc = psi_theta_carve(h, shape, has_cov, (size_t)steps, &b)) return crc;
+    if (int rc = psi_theta_upload(h, b, mean, cov, y_mean, n_nodes)) return rc;
+    r.Vals = b.Vals;
+    const MeanW w(h);
+    return descent_run(h, r, [&](hipStream_t s, int k, const double* Rv) {
+        if (int rc = psi_theta_enqueue(h, s, b, shape, has_cov, h->dTrainParams, Rv, w, n_ell)) return rc;
+        hipLaunchKernelGGL(k_descend_step_psi, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)b.Out, (const int*)b.Info,
+                           (const int*)b.Status, r.Vals, k, h->dTrainParams, h->D, n_ell);
+        return 0;
+    });
+}
+
+// The point step with enqueue_xu_grad behind the theta gradient (no side-stream wait: nothing ran there), then both optimiser launches
+extern "C" int sgp_inducing_descend(sgp_handle* h, double* theta_raw, int32_t n_ell, double* Xu, int32_t flags, int32_t steps, double eta,
+                                    double beta1, double beta2, double eps, double* opt_state, double* values, int64_t* counts) {
+    DescentRun r{"sgp_inducing_descend", false, false, theta_raw, n_ell, Xu, steps, eta, beta1, beta2, eps, opt_state, values, counts};
+    if (int rc = descent_args(h, r, true, flags)) return rc;
+    if (int rc = descent_point_ready(h, r.name)) return rc;
+    r.zero_counts();
+    if (steps == 0) return 0;
+    if (int wrc = sync_checked(h)) return wrc;
+    if (int drc = descent_device_state(h)) return drc;
     if (int arc = alloc_theta_grad(h)) return arc;
     int nranges = 0, range_len = 1;
     if (h->n > 0) xu_ranges(h->n, h->T, &nranges, &range_len);
@@ -4040,72 +3976,34 @@ extern "C" int sgp_inducing_descend(sgp_handle* h, double* theta_raw, int32_t n_
     if (int crc = carve_call_scratch(h, [&](Carver& c) {
             layout_inducing_descend(c, shape, h->M, (size_t)nranges, INDUCING_PUB, (size_t)steps, &b);
         })) return crc;
-    if (int brc = inducing_descend_begin(h, s, r, b.o, theta_raw, Xu, n_ell, steps, eta, beta1, beta2, eps, opt_state)) return brc;
-    h->n_ell = n_ell;
-    h->params_src = h->dTrainParams;
-    h->in_flight = true;
-    const bool multi = h->dout > 1;
-    const double* Rv = h->dR;
-    int rc = theta_Rv(h, s, &Rv);                             // R_v: once per call, q(v) is held
-    const double* scal = h->dStats + (size_t)h->Mp * h->Mp + (size_t)h->Mp * h->dout;
-    for (int k = 0; k < steps && !rc; ++k) {
-        h->params_gen++;                                       // theta and Xu moved: k_prep_xu mirrors them again
-        rc = enqueue_restats(h, s);
-        if (!rc) {
-            if (multi) rc = enqueue_theta_multi_value(h, s, Rv);
-            else enqueue_theta_uni_sums(h, s, Rv);
-        }
-        if (!rc) rc = enqueue_theta_grad(h, s, Rv, true);
-        if (!rc) {
-            enqueue_xu_grad(h, s, b.g, nranges, range_len);
-            hipLaunchKernelGGL(k_inducing_step, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)h->dGrad, (const double*)h->dOut2, scal,
-                               (const Params*)h->dParams, (const int*)h->dInfo, (const int*)(h->dInfo + 3), b.o.Vals, k, h->dTrainParams,
-                               h->D, n_ell, multi ? 1 : 0, r.learn ? 1 : 0, b.o.Pub);
-            launch_inducing_step_xu(h, s, r, b.o, b.g.Grad, beta1, beta2, eps);
-        }
-    }
-    // whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path
-    const hipError_t werr = wait_stream(s);
-    const hipError_t lerr = hipGetLastError();
-    h->params_src = h->hParams;
-    h->in_flight = false;
-    h->params_gen++;
-    h->data_gen++;                                             // the inducing inputs moved, as after sgp_set_inducing
-    stats_drop(h, STATS_REUSE | STATS_QV);                     // the resident statistics belong to the last evaluated (theta, Xu)
-    h->swept_local = false;
-    if (rc) return rc;
-    HIPCHK(h, werr);
-    HIPCHK(h, lerr);
-    TrainState st;
-    if (int erc = inducing_descend_end(h, r, b.o, theta_raw, Xu, steps, opt_state, values, &st)) return erc;
-    if (counts) { counts[0] = (int64_t)st.steps; counts[1] = st.stop > 0.0 ? (int64_t)st.stop : 0; }
-    if (int src = check_sync_status(h)) return src;
-    if (st.stop != 0.0)
-        return factor_status(h, (int)st.stop, (std::string(name) + ", step " + std::to_string((int64_t)st.steps) + ": K_uu").c_str());
-    return 0;
+    r.Mom = b.o.Mom; r.Pub = b.o.Pub; r.Vals = b.o.Vals;
+    const int multi = h->dout > 1 ? 1 : 0;
+    return descent_run(h, r, [&](hipStream_t s, int k, const double* Rv) {
+        if (int rc = descent_point_eval(h, s, Rv)) return rc;
+        enqueue_xu_grad(h, s, b.g, nranges, range_len);
+        hipLaunchKernelGGL(k_inducing_step, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)h->dGrad, (const double*)h->dOut2,
+                           stats_scalars(h), (const Params*)h->dParams, (const int*)h->dInfo, (const int*)(h->dInfo + 3), r.Vals, k,
+                           h->dTrainParams, h->D, n_ell, multi, r.l.learn ? 1 : 0, r.Pub);
+        launch_inducing_step_xu(h, s, r, b.g.Grad);
+        return 0;
+    });
 }
 
-// Per step on the library's own stream: psi_theta_enqueue at the descent's device parameter block and psi_xu_enqueue behind it, as
-// theta_objective_psi_call chains them -- without the host's look at the status words in between: a failed evaluation's second pass
-// works on whatever the first left (a failed node writes zeros, the shapes fix every index) and k_inducing_step_psi discards it --, then
-// the two optimiser launches.  Everything but dXu, the optimiser state and the chain's mirror stays in call scratch.
+// psi_theta_enqueue at the descent's device parameter block and psi_xu_enqueue behind it, as theta_objective_psi_call chains them --
+// without the host's look at the status words in between: a failed evaluation's second pass works on whatever the first left (a failed
+// node writes zeros, the shapes fix every index) and k_inducing_step_psi discards it --, then both optimiser launches.  Everything but
+// dXu, the optimiser state and the chain's mirror stays in call scratch.
 extern "C" int sgp_inducing_descend_psi(sgp_handle* h, const double* mean, const double* cov, const double* y_mean, int64_t n_nodes,
                                         double* theta_raw, int32_t n_ell, double* Xu, int32_t flags, int32_t steps, double eta,
                                         double beta1, double beta2, double eps, double* opt_state, double* values, int64_t* counts) {
-    const char* name = "sgp_inducing_descend_psi";
-    InducingRun r;
-    if (int rc = inducing_descend_args(h, name, theta_raw, n_ell, Xu, flags, steps, eta, beta1, beta2, opt_state, &r)) return rc;
-    if (!mean || !y_mean) return refuse(h, name, "null argument");
-    if (n_nodes < 1) return refuse(h, name, "n_nodes must be >= 1");
-    if (int rc = psi_theta_ready(h, name, mean, cov, y_mean, n_nodes)) return rc;      // (refuses an open run: dTrain below is its state)
-    if (counts) counts[0] = counts[1] = counts[2] = 0;
-    if (steps == 0) return 0;                                  // (behind every refusal, as in sgp_inducing_descend)
+    DescentRun r{"sgp_inducing_descend_psi", true, false, theta_raw, n_ell, Xu, steps, eta, beta1, beta2, eps, opt_state, values, counts};
+    if (int rc = descent_args(h, r, true, flags)) return rc;
+    if (h->allreduce) return refuse(h, r.name, "data-sharded descent is not supported (remove the hook)");
+    if (int rc = descent_psi_ready(h, r.name, mean, cov, y_mean, n_nodes)) return rc;
+    r.zero_counts();
+    if (steps == 0) return 0;
     if (int wrc = sync_checked(h)) return wrc;
-    hipStream_t s = h->own;
-    if (!h->dTrain) {
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrain), sizeof(TrainState)));
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->dTrainParams), sizeof(Params)));
-    }
+    if (int drc = descent_device_state(h)) return drc;
     const bool has_cov = cov != nullptr;
     const PointShape shape = point_shape(h, 3 * (int64_t)h->D * h->Mp + h->D + 1, n_nodes, n_nodes);
     int nranges = 0;
@@ -4116,38 +4014,16 @@ extern "C" int sgp_inducing_descend_psi(sgp_handle* h, const double* mean, const
             layout_psi_inducing_descend(c, shape, h->M, has_cov, (size_t)nranges, GRAD_SLOTS, PSI_TP_SLOTS, INDUCING_PUB, (size_t)steps, &b);
         })) return crc;
     if (int rc = psi_theta_upload(h, b.g, mean, cov, y_mean, n_nodes)) return rc;
-    if (int brc = inducing_descend_begin(h, s, r, b.o, theta_raw, Xu, n_ell, steps, eta, beta1, beta2, eps, opt_state)) return brc;
-    h->in_flight = true;
+    r.Mom = b.o.Mom; r.Pub = b.o.Pub; r.Vals = b.o.Vals;
     const MeanW w(h);
-    const double* Rv = h->dR;
-    int rc = theta_Rv(h, s, &Rv);                             // R_v: once per call, q(v) is held
-    for (int k = 0; k < steps && !rc; ++k) {
-        rc = psi_theta_enqueue(h, s, b.g, shape, has_cov, h->dTrainParams, Rv, w, n_ell);
-        if (!rc) rc = psi_xu_enqueue(h, s, b.g, shape, has_cov, w);
-        if (!rc) {
-            hipLaunchKernelGGL(k_inducing_step_psi, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)b.g.Out, (const int*)b.g.Info,
-                               (const int*)b.g.Status, b.o.Vals, k, h->dTrainParams, h->D, n_ell, r.learn ? 1 : 0, b.o.Pub);
-            launch_inducing_step_xu(h, s, r, b.o, b.g.GradXu, beta1, beta2, eps);
-        }
-    }
-    // whatever was enqueued reads dTrainParams and the call's buffers: wait before anything else, also on an error path
-    const hipError_t werr = wait_stream(s);
-    const hipError_t lerr = hipGetLastError();
-    h->in_flight = false;
-    h->params_gen++;
-    h->data_gen++;                                             // the inducing inputs moved, as after sgp_set_inducing: the statistics on
-    stats_drop(h, STATS_REUSE);                                // the device (not written here) are no longer those of the handle's Xu
-    if (rc) return rc;
-    HIPCHK(h, werr);
-    HIPCHK(h, lerr);
-    TrainState st;
-    if (int erc = inducing_descend_end(h, r, b.o, theta_raw, Xu, steps, opt_state, values, &st)) return erc;
-    h->n_ell = n_ell;
-    const int node = st.stop <= -2.0 ? (int)(-st.stop - 1.0) : 0;
-    const int kuu = st.stop <= -2.0 ? 0 : (int)st.stop;
-    if (counts) { counts[0] = (int64_t)st.steps; counts[1] = kuu > 0 ? kuu : 0; counts[2] = node; }
-    if (st.stop != 0.0) return psi_theta_status(h, std::string(name) + ", step " + std::to_string((int64_t)st.steps), node, kuu);
-    return 0;
+    return descent_run(h, r, [&](hipStream_t s, int k, const double* Rv) {
+        if (int rc = psi_theta_enqueue(h, s, b.g, shape, has_cov, h->dTrainParams, Rv, w, n_ell)) return rc;
+        if (int rc = psi_xu_enqueue(h, s, b.g, shape, has_cov, w)) return rc;
+        hipLaunchKernelGGL(k_inducing_step_psi, dim3(1), dim3(64), 0, s, h->dTrain, (const double*)b.g.Out, (const int*)b.g.Info,
+                           (const int*)b.g.Status, r.Vals, k, h->dTrainParams, h->D, n_ell, r.l.learn ? 1 : 0, r.Pub);
+        launch_inducing_step_xu(h, s, r, b.g.GradXu);
+        return 0;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

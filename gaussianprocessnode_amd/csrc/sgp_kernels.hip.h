@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <utility>
+#include "descent_state.h"      // TrainState
 
 namespace sgp {
 
@@ -4270,24 +4271,12 @@ __global__ void __launch_bounds__(256) k_train_window(const double* __restrict__
     }
 }
 
-struct TrainState {
-    double theta[MAXD + 1];     // raw (pre-softplus) parameters: sigma2 first, then the lengthscale(s)
-    double m[MAXD + 1];         // AdaMax first moment
-    double u[MAXD + 1];         // AdaMax infinity-norm accumulator
-    double bp[2];               // running powers of beta
-    double eta, beta1, beta2, eps;
-    double steps, rejected;     // optimiser steps taken / minibatches whose factorisations failed (theta left alone)
-    // classification (SGP_LIKELIHOOD_PROBIT): q(w) = Gamma(ga, gb), carried over the minibatches and never reset
-    // (experiments/classification_banana.ipynb cell 9: `shape, rate = params(qw)`)
-    double ga, gb;
-    double kind;                // 0 Gaussian likelihood with a fixed w (regression), 1 Probit with a Gamma q(w)
-    double stop;                // sgp_theta_descend: 0 running; the K_uu status word (> 0 the failing minor) or -1 (a device-word
-                                // wait gave up) of the step at which the descent stopped.  Latched: later steps change nothing
-};
+static_assert(THETA_SLOTS == MAXD + 1, "TrainState (descent_state.h) holds one raw parameter per input dimension and sigma2");
 
 __device__ __forceinline__ double softplus_dev(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
 
-// The one owner of the optimiser arithmetic (k_train_adamax, k_descend_step).  Flux's AdaMax on the raw parameters with the chain
+// The one owner of the optimiser arithmetic (k_train_adamax, k_descend_step, k_descend_step_psi and, through inducing_scalar_step,
+// k_inducing_step and k_inducing_step_psi).  Flux's AdaMax on the raw parameters with the chain
 // rule through softplus (d softplus = sigmoid): m = b1 m + (1 - b1) g; u = max(b2 u, |g|); theta -= eta / (1 - b1^t) m / (u + eps);
 // `gscale` rescales the gradient (a Probit run's new mean(q_w); 1 otherwise).
 __device__ __forceinline__ void adamax_step(TrainState* __restrict__ st, const double* __restrict__ grad, double gscale, int n_ell) {
@@ -4393,18 +4382,26 @@ __global__ void k_train_adamax(TrainState* __restrict__ st, const double* __rest
 // twin-workgroup wait given up) or hand-off status word (`sync_status`) stops the descent: latched in st->stop, and from then on
 // every step leaves theta, the moments, the powers, values[] (NaN from the host) and the kernel parameters as they are.
 // Otherwise values[k] = f(theta_k), the AdaMax step, and softplus(theta_k+1) written where the next step's k_prep_xu reads it.
+// The latch and the value line, shared with k_inducing_step: false when the descent has stopped, now or earlier.
+__device__ __forceinline__ bool descend_latch(TrainState* __restrict__ st, const double* __restrict__ grad, const double* __restrict__ out,
+                                              const double* __restrict__ stats_scal, const Params* __restrict__ P,
+                                              const int* __restrict__ info_kuu, const int* __restrict__ sync_status,
+                                              double* __restrict__ values, int k, int multi) {
+    if (st->stop != 0.0) return false;
+    const int info = *info_kuu, late = *sync_status;
+    if (info != 0 || late != 0) {
+        st->stop = info != 0 ? (double)info : -1.0;
+        return false;
+    }
+    values[k] = multi ? grad[GRAD_SLOTS] : 0.5 * P->W[0] * (out[0] + out[1] - stats_scal[0]);   // SGP_R_SUM_I1, _I2, SGP_S_YY
+    return true;
+}
 __global__ void k_descend_step(TrainState* __restrict__ st, const double* __restrict__ grad, const double* __restrict__ out,
                                const double* __restrict__ stats_scal, const Params* __restrict__ P, const int* __restrict__ info_kuu,
                                const int* __restrict__ sync_status, double* __restrict__ values, int k, Params* __restrict__ src,
                                int D, int n_ell, int multi) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (st->stop != 0.0) return;
-    const int info = *info_kuu, late = *sync_status;
-    if (info != 0 || late != 0) {
-        st->stop = info != 0 ? (double)info : -1.0;
-        return;
-    }
-    values[k] = multi ? grad[GRAD_SLOTS] : 0.5 * P->W[0] * (out[0] + out[1] - stats_scal[0]);   // SGP_R_SUM_I1, _I2, SGP_S_YY
+    if (!descend_latch(st, grad, out, stats_scal, P, info_kuu, sync_status, values, k, multi)) return;
     adamax_step(st, grad, 1.0, n_ell);
     write_kernel_params(st, src, D, n_ell);
 }
@@ -5269,15 +5266,22 @@ __global__ void __launch_bounds__(256) k_psi_xu_finish(const double* __restrict_
 // k_descend_step for sgp_theta_descend_psi: value and gradient are where k_psi_theta_finish left them.  An indefinite node (checked
 // first) or a nonzero K_uu status word stops the descent, latched in st->stop as -(1 + node + 1) resp. the failing minor (-1: a
 // twin-workgroup wait given up); from then on every step leaves theta, the moments, the powers, values[] and the parameters alone.
+// The latch and the value line, shared with k_inducing_step_psi: false when the descent has stopped, now or earlier.
+__device__ __forceinline__ bool descend_latch_psi(TrainState* __restrict__ st, const double* __restrict__ grad,
+                                                  const int* __restrict__ info_kuu, const int* __restrict__ node_status,
+                                                  double* __restrict__ values, int k) {
+    if (st->stop != 0.0) return false;
+    const int node = *node_status, info = *info_kuu;
+    if (node != 0) { st->stop = -1.0 - (double)node; return false; }
+    if (info != 0) { st->stop = info > 0 ? (double)info : -1.0; return false; }
+    values[k] = grad[GRAD_SLOTS];
+    return true;
+}
 __global__ void k_descend_step_psi(TrainState* __restrict__ st, const double* __restrict__ grad, const int* __restrict__ info_kuu,
                                    const int* __restrict__ node_status, double* __restrict__ values, int k, Params* __restrict__ src,
                                    int D, int n_ell) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (st->stop != 0.0) return;
-    const int node = *node_status, info = *info_kuu;
-    if (node != 0) { st->stop = -1.0 - (double)node; return; }
-    if (info != 0) { st->stop = info > 0 ? (double)info : -1.0; return; }
-    values[k] = grad[GRAD_SLOTS];
+    if (!descend_latch_psi(st, grad, info_kuu, node_status, values, k)) return;
     adamax_step(st, grad, 1.0, n_ell);
     write_kernel_params(st, src, D, n_ell);
 }
@@ -5314,13 +5318,7 @@ __global__ void k_inducing_step(TrainState* __restrict__ st, const double* __res
                                 int D, int n_ell, int multi, int learn_theta, double* __restrict__ pub) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     pub[0] = 0.0;
-    if (st->stop != 0.0) return;
-    const int info = *info_kuu, late = *sync_status;
-    if (info != 0 || late != 0) {
-        st->stop = info != 0 ? (double)info : -1.0;
-        return;
-    }
-    values[k] = multi ? grad[GRAD_SLOTS] : 0.5 * P->W[0] * (out[0] + out[1] - stats_scal[0]);   // SGP_R_SUM_I1, _I2, SGP_S_YY
+    if (!descend_latch(st, grad, out, stats_scal, P, info_kuu, sync_status, values, k, multi)) return;
     inducing_scalar_step(st, grad, learn_theta, pub, src, D, n_ell);
 }
 
@@ -5330,11 +5328,7 @@ __global__ void k_inducing_step_psi(TrainState* __restrict__ st, const double* _
                                     int D, int n_ell, int learn_theta, double* __restrict__ pub) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     pub[0] = 0.0;
-    if (st->stop != 0.0) return;
-    const int node = *node_status, info = *info_kuu;
-    if (node != 0) { st->stop = -1.0 - (double)node; return; }
-    if (info != 0) { st->stop = info > 0 ? (double)info : -1.0; return; }
-    values[k] = grad[GRAD_SLOTS];
+    if (!descend_latch_psi(st, grad, info_kuu, node_status, values, k)) return;
     inducing_scalar_step(st, grad, learn_theta, pub, src, D, n_ell);
 }
 

@@ -531,29 +531,12 @@ class SGPDevice:
         Returns (theta, values, steps_taken, state) -- values[k] the objective at step k's theta.  Raises LinAlgError naming the
         minor and the step when K_uu was not positive definite at some theta_k (the handle's kernel is then softplus(theta_k));
         the exception carries what the call returned: `minor`, `theta`, `values` (NaN from that step on), `steps_taken`, `state`."""
-        th = np.array(theta, dtype=np.float64).reshape(-1)
-        n_ell = th.size - 1
-        steps = int(steps)
-        if state is None:
-            st = np.concatenate([np.zeros(2 * th.size), np.asarray(beta, dtype=np.float64)])
-        else:
-            st = np.array(state, dtype=np.float64).reshape(-1)
-            if st.size != 2 * th.size + 2:
-                raise ValueError(f"theta_descend: state needs 2 (1 + n_ell) + 2 = {2 * th.size + 2} entries, got {st.size}")
-        values = np.empty(max(steps, 0))
+        th, _, st, _, values = self._descent_args("theta_descend", theta, None, steps, True, beta, state)
         counts = (C.c_int64 * 2)()
-        rc = self._lib.sgp_theta_descend(self._h, ptr(th), n_ell, steps, float(eta), float(beta[0]), float(beta[1]), float(eps),
-                                         ptr(st), ptr(values), counts)
-        if rc > 0:
-            self._n_ell = n_ell
-            err = np.linalg.LinAlgError(f"theta_descend: K_uu is not positive definite at step {int(counts[0])} "
-                                        f"(leading minor {rc}); theta and the optimiser state are those of that step")
-            err.minor, err.theta, err.values, err.steps_taken, err.state = rc, th, values, int(counts[0]), st
-            raise err
-        self._check(rc, "sgp_theta_descend")
-        if steps > 0:
-            self._n_ell = n_ell
-        return th, values, int(counts[0]), st
+        rc = self._lib.sgp_theta_descend(self._h, ptr(th), th.size - 1, int(steps), float(eta), float(beta[0]), float(beta[1]),
+                                         float(eps), ptr(st), ptr(values), counts)
+        th, _, values, taken, st = self._descent_result("theta_descend", rc, counts, th, None, values, st, int(steps), False)
+        return th, values, taken, st
 
     def theta_objective_psi(self, mean, cov, y_mean, want_grad: bool = False):
         """The hyper-parameter objective over the exact Psi-statistics of T Gaussian inputs N(mean[t], cov[t]) at the current kernel
@@ -602,50 +585,30 @@ class SGPDevice:
         on), `steps_taken`, `state`, and `minor` / `node`."""
         m, S, T = self._node_gaussians("theta_descend_psi", mean, cov)
         y_cm = self._node_targets(y_mean, T)
-        th = np.array(theta, dtype=np.float64).reshape(-1)
-        n_ell = th.size - 1
-        steps = int(steps)
-        if state is None:
-            st = np.concatenate([np.zeros(2 * th.size), np.asarray(beta, dtype=np.float64)])
-        else:
-            st = np.array(state, dtype=np.float64).reshape(-1)
-            if st.size != 2 * th.size + 2:
-                raise ValueError(f"theta_descend_psi: state needs 2 (1 + n_ell) + 2 = {2 * th.size + 2} entries, got {st.size}")
-        values = np.empty(max(steps, 0))
+        th, _, st, _, values = self._descent_args("theta_descend_psi", theta, None, steps, True, beta, state)
         counts = (C.c_int64 * 3)()
-        rc = self._lib.sgp_theta_descend_psi(self._h, ptr(m), ptr(S), ptr(y_cm), T, ptr(th), n_ell, steps, float(eta), float(beta[0]),
-                                             float(beta[1]), float(eps), ptr(st), ptr(values), counts)
-        if rc > 0:
-            self._n_ell = n_ell
-            if int(counts[2]) > 0:
-                msg = self._lib.sgp_last_error(self._h)
-                err = _lib.PosDefException(rc, f"theta_descend_psi {msg.decode() if msg else ''}")
-            else:
-                err = np.linalg.LinAlgError(f"theta_descend_psi: K_uu is not positive definite at step {int(counts[0])} "
-                                            f"(leading minor {rc}); theta and the optimiser state are those of that step")
-            err.minor, err.node = int(counts[1]), int(counts[2])
-            err.theta, err.values, err.steps_taken, err.state = th, values, int(counts[0]), st
-            raise err
-        self._check(rc, "sgp_theta_descend_psi")
-        if steps > 0:
-            self._n_ell = n_ell
-        return th, values, int(counts[0]), st
+        rc = self._lib.sgp_theta_descend_psi(self._h, ptr(m), ptr(S), ptr(y_cm), T, ptr(th), th.size - 1, int(steps), float(eta),
+                                             float(beta[0]), float(beta[1]), float(eps), ptr(st), ptr(values), counts)
+        th, _, values, taken, st = self._descent_result("theta_descend_psi", rc, counts, th, None, values, st, int(steps), True)
+        return th, values, taken, st
 
-    # -- device-paced descent in the inducing inputs (sgp_inducing_descend, sgp_inducing_descend_psi) ---------------------------
-    def _inducing_args(self, what: str, theta, Xu, steps, learn_theta: bool, beta, state):
+    # -- what the four device-paced descents share; Xu is None in the theta-only ones ------------------------------------------
+    def _descent_args(self, what: str, theta, Xu, steps, learn_theta: bool, beta, state):
         th = np.array(theta, dtype=np.float64).reshape(-1)
-        Z = np.array(np.reshape(Xu, (self.M, self.D)), dtype=np.float64, order="C")
-        P = (th.size if learn_theta else 0) + Z.size
+        Z = None if Xu is None else np.array(np.reshape(Xu, (self.M, self.D)), dtype=np.float64, order="C")
+        P = (th.size if learn_theta else 0) + (0 if Z is None else Z.size)
         if state is None:
             st = np.concatenate([np.zeros(2 * P), np.asarray(beta, dtype=np.float64)])
         else:
             st = np.array(state, dtype=np.float64).reshape(-1)
             if st.size != 2 * P + 2:
-                raise ValueError(f"{what}: state needs 2 P + 2 = {2 * P + 2} entries for P = {P} optimised parameters, got {st.size}")
+                need = (f"2 (1 + n_ell) + 2 = {2 * P + 2} entries" if Z is None else
+                        f"2 P + 2 = {2 * P + 2} entries for P = {P} optimised parameters")
+                raise ValueError(f"{what}: state needs {need}, got {st.size}")
         flags = _lib.SGP_DESCEND_XU | (_lib.SGP_DESCEND_THETA if learn_theta else 0)
         return th, Z, st, flags, np.empty(max(int(steps), 0))
 
-    def _inducing_result(self, what: str, rc: int, counts, th, Z, values, st, steps: int, psi: bool):
+    def _descent_result(self, what: str, rc: int, counts, th, Z, values, st, steps: int, psi: bool):
         if rc > 0:
             self._n_ell = th.size - 1
             node = int(counts[2]) if psi else 0
@@ -654,14 +617,18 @@ class SGPDevice:
                 err = _lib.PosDefException(rc, f"{what} {msg.decode() if msg else ''}")
             else:
                 err = np.linalg.LinAlgError(f"{what}: K_uu is not positive definite at step {int(counts[0])} (leading minor {rc}); "
-                                            f"theta, Xu and the optimiser state are those of that step")
+                                            f"{'theta' if Z is None else 'theta, Xu'} and the optimiser state are those of that step")
             err.minor, err.node = int(counts[1]), node
-            err.theta, err.Xu, err.values, err.steps_taken, err.state = th, Z, values, int(counts[0]), st
+            err.theta, err.values, err.steps_taken, err.state = th, values, int(counts[0]), st
+            if Z is not None:
+                err.Xu = Z
             raise err
-        self._check(rc, what)
+        self._check(rc, what if Z is not None else "sgp_" + what)     # (the refusals' prefixes as each pair has always had them)
         if steps > 0:
             self._n_ell = th.size - 1
         return th, Z, values, int(counts[0]), st
+
+    # -- device-paced descent in the inducing inputs (sgp_inducing_descend, sgp_inducing_descend_psi) ---------------------------
 
     def inducing_descend(self, theta, Xu, steps: int, *, learn_theta: bool = True, eta: float = 1e-3, beta=(0.9, 0.999),
                          eps: float = 1e-8, state=None):
@@ -673,11 +640,11 @@ class SGPDevice:
         kernel is softplus(theta) and its inducing inputs are Xu, both as returned; q(v) stays installed.  A K_uu that is not
         positive definite at some step raises LinAlgError as `theta_descend` does, carrying `minor`, `theta`, `Xu`, `values` (NaN
         from that step on), `steps_taken`, `state`."""
-        th, Z, st, flags, values = self._inducing_args("inducing_descend", theta, Xu, steps, learn_theta, beta, state)
+        th, Z, st, flags, values = self._descent_args("inducing_descend", theta, Xu, steps, learn_theta, beta, state)
         counts = (C.c_int64 * 2)()
         rc = self._lib.sgp_inducing_descend(self._h, ptr(th), th.size - 1, ptr(Z), flags, int(steps), float(eta), float(beta[0]),
                                             float(beta[1]), float(eps), ptr(st), ptr(values), counts)
-        return self._inducing_result("inducing_descend", rc, counts, th, Z, values, st, int(steps), False)
+        return self._descent_result("inducing_descend", rc, counts, th, Z, values, st, int(steps), False)
 
     def inducing_descend_psi(self, mean, cov, y_mean, theta, Xu, steps: int, *, learn_theta: bool = True, eta: float = 1e-3,
                              beta=(0.9, 0.999), eps: float = 1e-8, state=None):
@@ -687,11 +654,11 @@ class SGPDevice:
         `Xu`, `values`, `steps_taken`, `state`, `minor` and `node`."""
         m, S, T = self._node_gaussians("inducing_descend_psi", mean, cov)
         y_cm = self._node_targets(y_mean, T)
-        th, Z, st, flags, values = self._inducing_args("inducing_descend_psi", theta, Xu, steps, learn_theta, beta, state)
+        th, Z, st, flags, values = self._descent_args("inducing_descend_psi", theta, Xu, steps, learn_theta, beta, state)
         counts = (C.c_int64 * 3)()
         rc = self._lib.sgp_inducing_descend_psi(self._h, ptr(m), ptr(S), ptr(y_cm), T, ptr(th), th.size - 1, ptr(Z), flags, int(steps),
                                                 float(eta), float(beta[0]), float(beta[1]), float(eps), ptr(st), ptr(values), counts)
-        return self._inducing_result("inducing_descend_psi", rc, counts, th, Z, values, st, int(steps), True)
+        return self._descent_result("inducing_descend_psi", rc, counts, th, Z, values, st, int(steps), True)
 
     def psi_in_grad(self, mean, cov, y_mean, want_energy: bool = True, want_cov: bool = True):
         """The exact-Psi input messages of T nodes with Gaussian inputs N(mean[t], cov[t]) at the current kernel (sgp_psi_in_grad; SE

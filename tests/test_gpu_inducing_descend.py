@@ -193,6 +193,53 @@ def test_state_afterwards(G):
     assert np.abs(Z - c["Xu"]).max() > 1e-3
 
 
+@pytest.mark.parametrize("op", ["theta_descend_3", "theta_descend_psi_3", "inducing_descend_3", "inducing_descend_psi_3"])
+def test_all_four_descents_leave_the_handle_at_what_they_return(G, op):
+    """The four descents share one teardown: after three steps of each, on a handle whose next sweep would have reused its statistics,
+    that sweep is what tests/call_sequence_ref.py says for the call, and the next objective -- q(v) still the sweep's, no setter in
+    between -- is that of a fresh handle given the returned theta and Xu, to the bound of test_state_afterwards (RTOL: the host's
+    softplus is not the device's to the last bit).  Point pair: shape a; exact-Psi pair: shape e, its means as the resident points."""
+    from tests import call_sequence_ref as CR
+    psi, inducing = "psi" in op, op.startswith("inducing")
+    c = IR.case("e" if psi else "a")
+    X, Y = (c["mean"], c["Y"]) if psi else (c["X"], c["Y"][:, 0])
+    gauss = (c["mean"], c["S"], c["Y"]) if psi else ()
+
+    def handle(Xu, theta):
+        dev = G.SGPDevice(len(X), c["M"], c["D"], c["d_out"], reuse_stats=True)
+        dev.set_inducing(Xu)
+        dev.set_data(X, Y)
+        p = IR.softplus(theta)
+        dev.set_kernel(float(p[0]), p[1:], c["jitter"], family=c["family"])
+        dev.set_prior_isotropic(50.0)
+        dev.set_noise(c["W"], float(np.linalg.slogdet(c["W"])[1]))
+        return dev
+
+    def objective(dev):
+        return dev.theta_objective_psi(*gauss) if psi else dev.theta_objective()
+    with handle(c["Xu"], c["theta0"]) as dev:
+        dev.sweep()
+        dev.sweep()
+        assert dev.sweep_kind()[0] == CR.REUSED
+        mu, _, Uv = dev.posterior()
+        if inducing:
+            call = functools.partial(dev.inducing_descend_psi, *gauss) if psi else dev.inducing_descend
+            th, Z, vals, taken, _ = call(c["theta0"], c["Xu"], 3, **KW)
+        else:
+            call = functools.partial(dev.theta_descend_psi, *gauss) if psi else dev.theta_descend
+            th, vals, taken, _ = call(c["theta0"], 3, **KW)
+            Z = c["Xu"]
+        assert taken == 3 and np.isfinite(vals).all()
+        assert dev.sweep_kind()[0] == CR.MUTATORS[op].kind == CR.FULL
+        v = objective(dev)
+    with handle(Z, th) as fresh:
+        fresh.set_posterior(mu, Uv)
+        v0 = objective(fresh)
+    print(f"{op}: next objective {v:.12e}, fresh handle {v0:.12e}, rel {abs(v / v0 - 1):.2e}")
+    np.testing.assert_allclose(v, v0, rtol=RTOL)
+    assert (np.abs(Z - c["Xu"]).max() > 1e-3) == inducing and np.abs(th - c["theta0"]).max() > 1e-3
+
+
 def test_refusals(G):
     from gaussianprocessnode_amd._lib import ptr
     c = IR.case("a")

@@ -36,7 +36,7 @@ EXPORTS = [
     "sgp_theta_descend", "sgp_out_message", "sgp_psi_stats", "sgp_sweep_local_psi",
     "sgp_theta_objective_psi", "sgp_theta_descend_psi", "sgp_psi_in_grad", "sgp_psi_predict",
     "sgp_theta_objective_xu", "sgp_theta_objective_psi_xu", "sgp_inducing_descend", "sgp_inducing_descend_psi",
-    "sgp_sweep_plan", "sgp_select_inducing", "sgp_predict_joint", "sgp_sample_f",
+    "sgp_sweep_plan", "sgp_select_inducing", "sgp_predict_joint", "sgp_sample_f", "sgp_vmp_run",
 ]
 # sgp_sweep_plan's bits (SGP_PLAN_* of include/sgp_hip.h), by name
 PLAN_BITS = {"overlapped": 1, "pack": 2, "events": 4, "join_word": 8, "kuu_interleaved": 16, "stats_first": 32, "gate_side": 64,
@@ -61,6 +61,8 @@ SGP_TIME_QUADFORM = 120
 SGP_PREDICT_NOISE = 1         # sgp_predict_var: add the observation noise W^-1
 SGP_JOINT_MAX_ROWS = 8192     # sgp_predict_joint / sgp_sample_f: ns * d_out
 SGP_DESCEND_THETA, SGP_DESCEND_XU = 1, 2      # sgp_inducing_descend[_psi]: what the optimised vector holds
+SGP_VMP_GAUSSIAN, SGP_VMP_PROBIT = 0, 1       # sgp_vmp_run: likelihood
+SGP_VMP_HOLD_W = 1                            # sgp_vmp_run: flags
 
 
 class SGPError(RuntimeError):
@@ -177,6 +179,7 @@ def load(build_if_missing: bool = True, variant=None):
                                              C.c_double, C.c_double, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_select_inducing.argtypes = [vp, dp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int64), dp,
                                         C.POINTER(C.c_int32)]
+    lib.sgp_vmp_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_get_step_trace.argtypes = [C.POINTER(C.c_int64)]
     lib.sgp_measure_clocks.argtypes = [C.c_int32, dp]
     lib.sgp_overlap_plan.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -292,6 +292,8 @@ static void stats_drop(sgp_handle* h, unsigned what) {
 static void stats_targets(sgp_handle* h, bool pending) { h->stats.targets = pending; }
 static void stats_checked(sgp_handle* h, bool ok) { if (ok) h->stats.checked = true; else h->stats.reusable = false; }
 static void stats_exact_psi(sgp_handle* h, bool on) { h->stats.exact_psi = on; }
+// the sweep that produced q(v) ran at a noise the device chose (sgp_vmp_run): the record follows it
+static void stats_swept_at(sgp_handle* h, double w0) { h->stats.w0 = w0; }
 // are the handle's current kernel values and family those of the record?  (values: sgp_set_kernel at the same theta keeps them.)
 // Both readers also need the library's own buffer or a hook: a caller-bound buffer without one may have been reduced outside.
 static bool kernel_matches(const sgp_handle* h) {
@@ -4024,6 +4026,166 @@ extern "C" int sgp_inducing_descend_psi(sgp_handle* h, const double* mean, const
         launch_inducing_step_xu(h, s, r, b.g.GradXu);
         return 0;
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Device-paced VMP iterations with the free energy (include/sgp_hip.h: sgp_vmp_run; kernels: k_probit_points, k_vmp_kl, k_vmp_close;
+// DESIGN.md 6m).  Per iteration the sweep's own launches -- the full sweep first, then the sweeps over the resident statistics -- with
+// the three kernels between them, all on the library's own stream in stream order; the noise travels through dTrainParams, where
+// k_vmp_close writes it and every sweep's k_prep_xu reads it (params_src, as in the descents).  The descents' driver (descent_run) is
+// built around theta and the AdaMax state and does not fit; its pieces that do -- sync_checked, descent_device_state, descent_wait --
+// are used.  A stopped run's remaining launches still execute: the latch keeps the three kernels from writing, and the sweeps re-form
+// bitwise the q(v) they find (same statistics, same targets, same noise).
+// ------------------------------------------------------------------------------------------------
+static bool finite_positive(double v) { return std::isfinite(v) && v > 0.0; }
+
+extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int32_t iterations, const double* gamma_prior,
+                           double* gamma, const double* mu_init, double tol, double* values, double* terms, int64_t* counts) {
+    const char* name = "sgp_vmp_run";
+    if (!h) return fail(h, SGP_ERR_ARG, "sgp_vmp_run: null handle");
+    if (likelihood != SGP_VMP_GAUSSIAN && likelihood != SGP_VMP_PROBIT) return refuse(h, name, "unknown likelihood");
+    if (flags & ~SGP_VMP_HOLD_W) return refuse(h, name, "unknown flags");
+    if (iterations < 0) return refuse(h, name, "iterations must be >= 0");
+    const bool hold = (flags & SGP_VMP_HOLD_W) != 0, probit = likelihood == SGP_VMP_PROBIT;
+    if (!hold) {
+        if (!gamma_prior || !gamma) return refuse(h, name, "gamma_prior and gamma are required without SGP_VMP_HOLD_W");
+        if (!finite_positive(gamma_prior[0]) || !finite_positive(gamma_prior[1])) return refuse(h, name, "gamma_prior must be positive and finite");
+        if (!finite_positive(gamma[0]) || !finite_positive(gamma[1])) return refuse(h, name, "gamma must be positive and finite");
+    }
+    if (!(tol >= 0.0)) return refuse(h, name, "tol must be >= 0");
+    for (int i = 0; mu_init && i < h->Q; ++i)
+        if (!std::isfinite(mu_init[i])) return refuse(h, name, "mu_init must be finite");
+    if (h->dout != 1) return refuse(h, name, "UniSGP handles only (d_out = 1)");
+    if (int prc = refuse_exact_psi(h, name)) return prc;
+    if (h->training) return refuse(h, name, "a device-paced training run is open (sgp_train_end first)");
+    if (!h->have_inducing || !h->have_kernel || !h->have_data || h->n < 1)
+        return refuse(h, name, "set_inducing, set_kernel and set_data (at least one point) first");
+    if (h->has_yv || h->has_omega) return refuse(h, name, "the resident data must have been set without y_var and without pt_weight");
+    if (h->allreduce) return refuse(h, name, "data-sharded runs are not supported (remove the hook)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int64_t n = h->n;
+    if (probit) {
+        if (int wrc = sync_all(h)) return wrc;
+        std::vector<double> lab((size_t)n);
+        HIPCHK(h, hipMemcpy(lab.data(), h->dY, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; ++i)
+            if (lab[i] != 0.0 && lab[i] != 1.0) return refuse(h, name, "Probit labels must be 0 or 1 (the resident y_mean of sgp_set_data)");
+    }
+    if (counts) counts[0] = counts[1] = 0;
+    if (iterations == 0) return 0;
+    if (int wrc = sync_checked(h)) return wrc;
+    if (int drc = descent_device_state(h)) return drc;
+
+    // call scratch: [state | values | terms | mu0 | k_vmp_kl's pairs | (Probit) mu_init, mz, labels, k_probit_points' pairs]; the first
+    // four go up in one copy and the first three come back in one
+    const int Q = h->Q, Qp = h->Qp, form = h->prior_form;
+    const int nkl = form == 2 ? (Q + 255) / 256 : std::min(Q, 256);
+    const int npp = probit ? (int)((n + PROBIT_RANGE - 1) / PROBIT_RANGE) : 0;
+    const size_t it = (size_t)iterations;
+    size_t need = VMP_STATE + 5 * it + 2 * (size_t)nkl + (size_t)Qp;
+    if (probit) need += (size_t)Qp + 2 * (size_t)n + 2 * (size_t)npp;
+    double* base = nullptr;
+    if (int crc = call_scratch(h, need, &base)) return crc;
+    double *dSt = base, *dVals = dSt + VMP_STATE, *dTerms = dVals + it, *dMu0 = dTerms + 4 * it, *dKl = dMu0 + Qp;
+    double *dMuInit = dKl + 2 * nkl, *dMz = dMuInit + Qp, *dLab = dMz + n, *dPp = dLab + n;
+    {
+        std::vector<double> init(VMP_STATE + 5 * it + (size_t)Qp, std::numeric_limits<double>::quiet_NaN());
+        for (int i = 0; i < VMP_STATE; ++i) init[i] = 0.0;
+        for (int i = 0; i < Qp; ++i) init[VMP_STATE + 5 * it + i] = 0.0;
+        if (!hold) { init[VMP_A] = gamma[0]; init[VMP_B] = gamma[1]; }
+        init[VMP_ELOGW] = h->hParams->E_logw;
+        HIPCHK(h, hipMemcpy(dSt, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
+    }
+    if (probit) {
+        std::vector<double> m0((size_t)Qp, 0.0);
+        if (mu_init) memcpy(m0.data(), mu_init, sizeof(double) * (size_t)Q);
+        HIPCHK(h, hipMemcpy(dMuInit, m0.data(), sizeof(double) * (size_t)Qp, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(dLab, h->dY, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice));
+    }
+    HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
+
+    hipStream_t s = h->own;
+    h->params_src = h->dTrainParams;
+    h->params_gen++;
+    h->in_flight = true;
+    const double* ld0 = nullptr;
+    int nld0 = 0;
+    if (form != 2) {
+        // log|Lambda0| and mu0 = Lambda0^-1 xi0, once per call: one factorisation of a copy of Lambda0 with the step kernel, in the
+        // buffers sgp_set_prior(form 0) factors Sigma0 in (every sweep rewrites dTmp, dWl and dSigma before it reads them)
+        HIPCHK(h, hipMemcpyAsync(h->dTmp, h->dLambda0, sizeof(double) * (size_t)Qp * Qp, hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemsetAsync(h->dInfo + 2, 0, sizeof(int), s));
+        launch_potrf(h->dTmp, Qp, h->TQ, h->dInfo + 2, Q, h->dScratch + 2 * POTRF_SCRATCH, s, h->dWl);
+        launch_ata(h->dWl, h->dSigma, Qp, h->TQ, s);
+        hipLaunchKernelGGL(k_symv, dim3((Qp + 3) / 4), dim3(256), 0, s, (const double*)h->dSigma, (const double*)h->dXi0, dMu0, Qp, Qp);
+        ld0 = h->dScratch + 2 * POTRF_SCRATCH + POTRF_LOGDET;
+        nld0 = h->TQ;
+    }
+    VmpClose c;
+    memset(&c, 0, sizeof c);
+    c.out = h->dOut; c.info = h->dInfo; c.stats_scal = stats_scalars(h); c.swept = h->dParams; c.src = h->dTrainParams;
+    c.ppart = dPp; c.npp = npp; c.klpart = dKl; c.nkl = nkl; c.ld0 = ld0; c.nld0 = nld0; c.data_scal = h->dDataScal;
+    c.st = dSt; c.values = dVals; c.terms = dTerms;
+    c.a0 = hold ? 1.0 : gamma_prior[0]; c.b0 = hold ? 1.0 : gamma_prior[1]; c.tol = tol;
+    c.M = Q; c.hold = hold ? 1 : 0; c.probit = probit ? 1 : 0; c.form = form;
+    if (!hold) hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_INIT);
+    int rc = 0;
+    for (int k = 0; k < iterations && !rc; ++k) {
+        if (probit) {
+            // q(f): the forward message from the previous mean (mu_init first) at the resident X, then the moments, written as
+            // sgp_set_targets would leave them
+            if (k == 0) prep_main(h, s, false);
+            launch_predict(h, s, h->dXus, h->dParams, h->dX, k == 0 ? dMuInit : h->dMu, dMz, n);
+            hipLaunchKernelGGL(k_probit_points, dim3(npp), dim3(256), 0, s, (const double*)dLab, (const double*)dMz, n,
+                               (const Params*)h->dTrainParams, (const double*)dSt, h->dY, h->dYw, h->dYv, dPp);
+            hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_REDUCE);
+            h->has_yv = true;
+            h->data_gen++;
+        }
+        if (k == 0) {
+            rc = sweep_local_impl(h, nullptr, true);
+            if (!rc) rc = sgp_sweep_finish(h, nullptr);
+            if (!rc) {
+                h->last_kind = SGP_SWEEP_FULL;
+                if (h->cfg.flags & SGP_FLAG_REUSE_STATS) stats_reusable(h);
+            }
+        } else {
+            rc = sweep_resident(h, nullptr, probit);
+        }
+        if (rc) break;
+        hipLaunchKernelGGL(k_vmp_kl, dim3(nkl), dim3(256), 0, s, (const double*)h->dLambda0, (const double*)h->dSigma,
+                           (const double*)h->dMu, (const double*)dMu0, (const Params*)h->dParams, Q, Qp, form, dKl);
+        c.k = k;
+        hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_CLOSE);
+    }
+    rc = descent_wait(h, s, rc);
+    h->params_src = h->hParams;
+    h->params_gen++;
+    if (rc) { stats_drop(h, STATS_REUSE | STATS_QV); return rc; }
+
+    std::vector<double> back(VMP_STATE + 5 * it);
+    HIPCHK(h, hipMemcpy(back.data(), dSt, sizeof(double) * back.size(), hipMemcpyDeviceToHost));
+    const double* st = back.data();
+    if (values) memcpy(values, st + VMP_STATE, sizeof(double) * it);
+    if (terms) memcpy(terms, st + VMP_STATE + it, sizeof(double) * 4 * it);
+    const int done = (int)st[VMP_DONE], stop = (int)st[VMP_STOP];
+    if (done > 0) {
+        if (!hold) {
+            h->hParams->W[0] = st[VMP_A] / st[VMP_B];
+            h->hParams->E_logw = st[VMP_ELOGW];
+            gamma[0] = st[VMP_A]; gamma[1] = st[VMP_B];
+        }
+        stats_swept_at(h, st[VMP_W_SWEPT]);
+    }
+    if (h->cfg.flags & SGP_FLAG_REUSE_STATS) stats_checked(h, st[VMP_INFO_KUU] == 0.0 && st[VMP_INFO_SYNC] == 0.0);
+    if (counts) { counts[0] = done; counts[1] = stop == 1 ? 1 : 0; }
+    if (stop != 2) return 0;
+    const std::string at = std::string(name) + ", iteration " + std::to_string(done);
+    int frc = check_sync_status(h);
+    if (!frc) frc = factor_status(h, (int)st[VMP_INFO_PRIOR], (at + ": the prior precision").c_str());
+    if (!frc) frc = factor_status(h, (int)st[VMP_INFO_KUU], (at + ": K_uu").c_str(), (int)st[VMP_INFO_LAMBDA], (at + ": Lambda").c_str(), true);
+    if (counts && frc > 0) counts[1] = -frc;
+    return frc;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -4307,6 +4307,18 @@ __device__ __forceinline__ void write_kernel_params(const TrainState* __restrict
 // r through erfcx for g < 0 (phi / Phi = sqrt(2 / pi) / erfcx(-g / sqrt 2): no cancellation, no underflow in the tail).
 // Writes the window's data as the sweep reads it -- mean (twice: y and omega y), variance -- and its data scalars
 // (sum mean^2 + var, n, n: what sgp_set_data computes on the host).  One workgroup, fixed summation order.
+// The per-point arithmetic, shared by k_probit_window and k_probit_points: (mf, vf) from the label, the forward mean m, vz and
+// q = 1 / sqrt(1 + vz); g is handed back for the callers that go on to log Phi(g).
+__device__ __forceinline__ void probit_point(double label, double m, double vz, double q, double& mf, double& vf, double& g) {
+    const double sgn = 2.0 * label - 1.0;
+    g = sgn * m * q;
+    double r;
+    if (g < 0.0) r = 0.79788456080286535588 / erfcx(-g * 0.70710678118654752440);
+    else r = exp(-0.5 * g * g) * 0.39894228040143267794 / (0.5 * erfc(-g * 0.70710678118654752440));
+    mf = m + sgn * vz * r * q;
+    vf = vz - vz * vz / (1.0 + vz) * r * (g + r);
+}
+
 __global__ void __launch_bounds__(256) k_probit_window(const double* __restrict__ label, const double* __restrict__ mz, int64_t n,
                                                        const TrainState* __restrict__ st, double* __restrict__ ymean,
                                                        double* __restrict__ yw, double* __restrict__ yvar, double* __restrict__ scal,
@@ -4315,13 +4327,8 @@ __global__ void __launch_bounds__(256) k_probit_window(const double* __restrict_
     const double vz = st->gb / st->ga, q = 1.0 / sqrt(1.0 + vz);
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) {
-        const double sgn = 2.0 * label[i] - 1.0, m = mz[i];
-        const double g = sgn * m * q;
-        double r;
-        if (g < 0.0) r = 0.79788456080286535588 / erfcx(-g * 0.70710678118654752440);
-        else r = exp(-0.5 * g * g) * 0.39894228040143267794 / (0.5 * erfc(-g * 0.70710678118654752440));
-        const double mf = m + sgn * vz * r * q;
-        const double vf = vz - vz * vz / (1.0 + vz) * r * (g + r);
+        double mf, vf, g;
+        probit_point(label[i], mz[i], vz, q, mf, vf, g);
         ymean[i] = mf;
         yw[i] = mf;
         yvar[i] = vf;
@@ -4404,6 +4411,187 @@ __global__ void k_descend_step(TrainState* __restrict__ st, const double* __rest
     if (!descend_latch(st, grad, out, stats_scal, P, info_kuu, sync_status, values, k, multi)) return;
     adamax_step(st, grad, 1.0, n_ell);
     write_kernel_params(st, src, D, n_ell);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Device-paced VMP iterations with the free energy (sgp_vmp_run in sgp_api.hip).  Between the sweeps' own kernels:
+// k_probit_points (Probit: q(f) of all resident points and the factors' share of the free energy), k_vmp_kl (the two data-dependent
+// sums of KL(q(v) || p(v))) and k_vmp_close (the Gamma step, the noise of the next iteration, the free energy, the latch).
+// The run's state is VMP_STATE doubles in call scratch; st[VMP_STOP] != 0 is the latch: every kernel below returns at once and the
+// sweeps that are still enqueued re-form, from unchanged targets and unchanged noise, bitwise the q(v) they find.
+// ------------------------------------------------------------------------------------------------
+enum { VMP_A = 0, VMP_B = 1,          // q(w) = Gamma(a, b) after the last completed iteration
+       VMP_FPREV = 2,                 // the free energy of the last completed iteration
+       VMP_DONE = 3,                  // iterations completed
+       VMP_STOP = 4,                  // 0 running, 1 converged by tol, 2 a factorisation failed or a stream hand-off gave up
+       VMP_INFO_KUU = 5, VMP_INFO_LAMBDA = 6, VMP_INFO_SYNC = 7, VMP_INFO_PRIOR = 8,     // the status words found when it stopped
+       VMP_W_SWEPT = 9,               // mean(q_w) the last completed iteration's sweep ran at
+       VMP_ELOGW = 10,                // E[log w] of q(w) = Gamma(a, b)
+       VMP_LIK = 11,                  // Probit: the factors' share, left by the reduce stage for the closing stage
+       VMP_STATE = 16 };
+enum { VMP_STAGE_REDUCE = 0, VMP_STAGE_CLOSE = 1, VMP_STAGE_INIT = 2 };
+constexpr int PROBIT_RANGE = 256;     // points per workgroup of k_probit_points: fixed, so that the ranges depend on N alone
+
+// digamma: the recurrence psi(x) = psi(x + 1) - 1 / x up to x >= 10, then the asymptotic series through x^-14 (the first term left
+// out, 3617 / (8160 x^16), is below 5e-17 there)
+__device__ __forceinline__ double digamma_dev(double x) {
+    double r = 0.0;
+    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
+    const double i = 1.0 / x, i2 = i * i;
+    const double s = i2 * (1.0 / 12.0 - i2 * (1.0 / 120.0 - i2 * (1.0 / 252.0 - i2 * (1.0 / 240.0 - i2 * (1.0 / 132.0 - i2 * (691.0 / 32760.0 - i2 * (1.0 / 12.0)))))));
+    return r + log(x) - 0.5 * i - s;
+}
+
+// log Phi(g), through erfcx for g < 0 as the ratio phi / Phi is
+__device__ __forceinline__ double log_ndtr_dev(double g) {
+    if (g < 0.0) return log(0.5 * erfcx(-g * 0.70710678118654752440)) - 0.5 * g * g;
+    return log(0.5 * erfc(-g * 0.70710678118654752440));
+}
+
+// q(f_i) of the resident points i = 0 .. n - 1 for `f_i ~ N(mz_i, vz), y_i ~ Probit(f_i)`, vz = 1 / mean(q_w) read from `src` (where
+// the closing stage wrote it): mf (twice: y and omega y) and vf as the sweep reads them, and per workgroup the pair
+// (sum mf^2 + vf, sum lik_i) with lik_i = -1/2 log(2 pi vz) - ((mf - mz)^2 + vf) / (2 vz) - log Phi(g): E_q[log q(f) - log Phi(s f)]
+// under the tilted q(f).  Workgroup b owns the points [256 b, 256 b + 256).
+__global__ void __launch_bounds__(256) k_probit_points(const double* __restrict__ label, const double* __restrict__ mz, int64_t n,
+                                                       const Params* __restrict__ src, const double* __restrict__ st,
+                                                       double* __restrict__ ymean, double* __restrict__ yw, double* __restrict__ yvar,
+                                                       double* __restrict__ part) {
+    __shared__ double red[4];
+    if (st[VMP_STOP] != 0.0) return;                            // (uniform)
+    const double vz = 1.0 / src->W[0], q = 1.0 / sqrt(1.0 + vz);
+    const int64_t i = (int64_t)blockIdx.x * PROBIT_RANGE + threadIdx.x;
+    double syy = 0.0, lik = 0.0;
+    if (i < n) {
+        const double m = mz[i];
+        double mf, vf, g;
+        probit_point(label[i], m, vz, q, mf, vf, g);
+        ymean[i] = mf;
+        yw[i] = mf;
+        yvar[i] = vf;
+        syy = mf * mf + vf;
+        const double dm = mf - m;
+        lik = -0.5 * log(6.2831853071795864769 * vz) - (dm * dm + vf) / (2.0 * vz) - log_ndtr_dev(g);
+    }
+    syy = block_sum(syy, red);
+    lik = block_sum(lik, red);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = syy; part[2 * blockIdx.x + 1] = lik; }
+}
+
+// The data-dependent sums of KL(q(v) || p(v)): part[2 b] = block b's share of tr(Lambda0 Sigma_v), part[2 b + 1] of
+// (mu - mu0)' Lambda0 (mu - mu0).  form 2 (Lambda0 = iso I, mu0 = 0): a pass over the diagonal, 256 entries per block;
+// otherwise block b takes the columns b, b + G, .. of the device-resident Lambda0 (Q x Q in ld x ld).
+__global__ void __launch_bounds__(256) k_vmp_kl(const double* __restrict__ L0, const double* __restrict__ Sigma,
+                                                const double* __restrict__ mu, const double* __restrict__ mu0,
+                                                const Params* __restrict__ P, int Q, int ld, int form, double* __restrict__ part) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    double tr = 0.0, qd = 0.0;
+    if (form == 2) {
+        const double iso = P->prior_iso;
+        for (int e = blockIdx.x * 256 + tid; e < Q; e += gridDim.x * 256) {
+            tr += iso * Sigma[(size_t)e * ld + e];
+            qd = fma(iso * mu[e], mu[e], qd);
+        }
+    } else {
+        for (int j = blockIdx.x; j < Q; j += gridDim.x) {
+            const double dj = mu[j] - mu0[j];
+            for (int i = tid; i < Q; i += 256) {
+                const double l = L0[(size_t)j * ld + i];
+                tr = fma(l, Sigma[(size_t)j * ld + i], tr);
+                qd = fma(l * (mu[i] - mu0[i]), dj, qd);
+            }
+        }
+    }
+    tr = block_sum(tr, red);
+    qd = block_sum(qd, red);
+    if (tid == 0) { part[2 * blockIdx.x] = tr; part[2 * blockIdx.x + 1] = qd; }
+}
+
+struct VmpClose {
+    const double* out;          // the sweep's scalars (k_scalars)
+    const int* info;            // the status words: K_uu, Lambda, prior, stream hand-off
+    const double* stats_scal;   // the statistics' scalars (SGP_S_N: the number of factor nodes)
+    const Params* swept;        // the parameters the sweep ran at
+    Params* src;                // where the next iteration's k_prep_xu reads the noise
+    const double* ppart; int npp;    // k_probit_points' pairs
+    const double* klpart; int nkl;   // k_vmp_kl's pairs
+    const double* ld0; int nld0;     // per-step sums of log L_cc of Lambda0's factor (form 2: none)
+    double* data_scal;          // the data scalars the sweep's assembly reads (the reduce stage writes sum mf^2 + vf there)
+    double* st;
+    double* values; double* terms;
+    double a0, b0, tol;
+    int k, M, hold, probit, form;
+};
+
+// One workgroup, three roles.  INIT: the noise of iteration 0 from q(w) = Gamma(a, b).  REDUCE (Probit, in front of the sweep): the
+// workgroups' pairs in a fixed order; sum mf^2 + vf into the data scalars (S_YY and the Ryy slot, as sgp_set_targets leaves them),
+// the factors' share into the state.  CLOSE (behind the sweep, iteration k): the status words; the Gamma step from the sweep's sums;
+// the four terms and their sum at (q(f), q(v), the NEW q(w)); the stop rule; the noise of the next iteration, unless the run stops.
+// It writes nothing the sweep's own kernels write -- the scalars' pinned mirror in particular stays k_scalars' alone.
+__global__ void __launch_bounds__(256) k_vmp_close(VmpClose c, int stage) {
+    __shared__ double red[4];
+    double* st = c.st;
+    const int tid = threadIdx.x;
+    if (stage == VMP_STAGE_INIT) {
+        if (tid == 0) {
+            const double a = st[VMP_A], b = st[VMP_B], el = digamma_dev(a) - log(b);
+            c.src->W[0] = a / b;
+            c.src->E_logw = el;
+            st[VMP_ELOGW] = el;
+        }
+        return;
+    }
+    if (st[VMP_STOP] != 0.0) return;                            // (uniform)
+    if (stage == VMP_STAGE_REDUCE) {
+        double syy = 0.0, lik = 0.0;
+        for (int b = tid; b < c.npp; b += 256) { syy += c.ppart[2 * b]; lik += c.ppart[2 * b + 1]; }
+        syy = block_sum(syy, red);
+        lik = block_sum(lik, red);
+        if (tid == 0) {
+            c.data_scal[SGP_S_YY] = syy;
+            c.data_scal[SGP_S_COUNT] = syy;                    // Ryy[0] of d_out = 1, behind the scalar slots
+            st[VMP_LIK] = lik;
+        }
+        return;
+    }
+    double tr = 0.0, qd = 0.0, ld = 0.0;
+    for (int b = tid; b < c.nkl; b += 256) { tr += c.klpart[2 * b]; qd += c.klpart[2 * b + 1]; }
+    for (int e = tid; e < c.nld0; e += 256) ld += c.ld0[e];
+    tr = block_sum(tr, red);
+    qd = block_sum(qd, red);
+    ld = 2.0 * block_sum(ld, red);
+    if (tid != 0) return;
+    const int i_kuu = (int)c.out[SGP_R_INFO_KUU], i_lam = (int)c.out[SGP_R_INFO_LAMBDA];
+    const int i_prior = c.form == 2 ? 0 : c.info[2], i_sync = c.info[3];     // (dInfo: K_uu, Lambda, prior, stream hand-off)
+    if (i_kuu != 0 || i_lam != 0 || i_prior != 0 || i_sync != 0) {
+        st[VMP_STOP] = 2.0;
+        st[VMP_INFO_KUU] = (double)i_kuu; st[VMP_INFO_LAMBDA] = (double)i_lam;
+        st[VMP_INFO_PRIOR] = (double)i_prior; st[VMP_INFO_SYNC] = (double)i_sync;
+        return;
+    }
+    const double LOG2PI = 1.8378770664093454835606594728112;
+    const double n = c.stats_scal[SGP_S_N], S = c.out[SGP_R_SUM_I1] + c.out[SGP_R_SUM_I2], w_swept = c.swept->W[0];
+    double a = st[VMP_A], b = st[VMP_B], wbar = w_swept, elog = c.swept->E_logw, t3 = 0.0;
+    if (!c.hold) {
+        a = c.a0 + 0.5 * n;
+        b = c.b0 + 0.5 * S;
+        wbar = a / b;
+        const double psi = digamma_dev(a);
+        elog = psi - log(b);
+        t3 = (a - c.a0) * psi - lgamma(a) + lgamma(c.a0) + c.a0 * (log(b) - log(c.b0)) + a * (c.b0 - b) / b;
+    }
+    const double ld0 = c.form == 2 ? (double)c.M * log(c.swept->prior_iso) : ld;
+    const double t0 = 0.5 * (wbar * S - n * elog + n * LOG2PI);
+    const double t1 = c.probit ? st[VMP_LIK] : 0.0;
+    const double t2 = 0.5 * (tr + qd - (double)c.M - ld0 + c.out[SGP_R_LOGDET_LAMBDA]);
+    const double F = ((t0 + t1) + t2) + t3;
+    c.terms[4 * c.k] = t0; c.terms[4 * c.k + 1] = t1; c.terms[4 * c.k + 2] = t2; c.terms[4 * c.k + 3] = t3;
+    c.values[c.k] = F;
+    const bool conv = c.k >= 1 && c.tol > 0.0 && fabs(F - st[VMP_FPREV]) <= c.tol * fabs(F);
+    st[VMP_A] = a; st[VMP_B] = b; st[VMP_FPREV] = F; st[VMP_DONE] = (double)(c.k + 1);
+    st[VMP_W_SWEPT] = w_swept; st[VMP_ELOGW] = elog;
+    if (conv) { st[VMP_STOP] = 1.0; return; }
+    if (!c.hold) { c.src->W[0] = wbar; c.src->E_logw = elog; }
 }
 
 // ------------------------------------------------------------------------------------------------

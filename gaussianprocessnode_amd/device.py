@@ -538,6 +538,41 @@ class SGPDevice:
         th, _, values, taken, st = self._descent_result("theta_descend", rc, counts, th, None, values, st, int(steps), False)
         return th, values, taken, st
 
+    def vmp_run(self, iterations: int, *, likelihood: str = "gaussian", gamma_prior=None, gamma=None, mu_init=None,
+                tol: float = 0.0, hold_w: bool = False):
+        """`iterations` VMP iterations over the resident data with the free energy of each, paced by the device (sgp_vmp_run):
+        `infer(iterations = K, free_energy = true)`.  likelihood "gaussian" (y are targets) or "probit" (y are labels in {0, 1});
+        gamma_prior = (shape0, rate0) and gamma = (shape, rate) of q(w) entering the run (default: the prior), unless hold_w keeps
+        the last `set_noise`; mu_init: the mean the first Probit forward message uses (None: 0).  Returns (values, terms, gamma,
+        iterations_done, converged): values[k] the free energy after iteration k (NaN beyond a stop), terms (iterations, 4) its
+        parts [node energy, Probit factors, KL(q(v)), KL(q(w))], gamma the final (shape, rate) or None with hold_w.  A K_uu or
+        Lambda that is not positive definite raises LinAlgError naming the minor and the iteration; the exception carries
+        `minor`, `values`, `terms`, `gamma`, `iterations_done`, `counts`."""
+        kinds = {"gaussian": _lib.SGP_VMP_GAUSSIAN, "probit": _lib.SGP_VMP_PROBIT}
+        if likelihood not in kinds:
+            raise ValueError(f"vmp_run: unknown likelihood {likelihood!r}: expected one of {sorted(kinds)}")
+        K = int(iterations)
+        g0 = g = None
+        if not hold_w:
+            if gamma_prior is None:
+                raise ValueError("vmp_run: gamma_prior = (shape0, rate0) is required without hold_w")
+            g0 = as_f64(gamma_prior, (2,))
+            g = as_f64(g0 if gamma is None else gamma, (2,)).copy()
+        mu0 = None if mu_init is None else as_f64(mu_init, (self.M,))
+        values = np.full(max(K, 0), np.nan)
+        terms = np.full((max(K, 0), 4), np.nan)
+        counts = (C.c_int64 * 2)()
+        rc = self._lib.sgp_vmp_run(self._h, kinds[likelihood], _lib.SGP_VMP_HOLD_W if hold_w else 0, K, ptr(g0), ptr(g), ptr(mu0),
+                                   float(tol), ptr(values), ptr(terms), counts)
+        if rc > 0:
+            msg = self._lib.sgp_last_error(self._h)
+            err = np.linalg.LinAlgError(f"sgp_vmp_run: {msg.decode() if msg else ''} (leading minor {rc})")
+            err.minor, err.values, err.terms, err.gamma, err.iterations_done = rc, values, terms, g, int(counts[0])
+            err.counts = (int(counts[0]), int(counts[1]))       # counts[1] = -minor
+            raise err
+        self._check(rc, "sgp_vmp_run")
+        return values, terms, g, int(counts[0]), bool(counts[1] == 1)
+
     def theta_objective_psi(self, mean, cov, y_mean, want_grad: bool = False):
         """The hyper-parameter objective over the exact Psi-statistics of T Gaussian inputs N(mean[t], cov[t]) at the current kernel
         (sgp_theta_objective_psi; SE only): `theta_objective` with the cubature sums replaced by exact expectations.  mean (T, D),

@@ -162,8 +162,29 @@ def probit_marginal(y, mz, vz):
     return mz + s * vz * r / np.sqrt(1.0 + vz), vz - vz * vz / (1.0 + vz) * r * (g + r)
 
 
+def _host_free_energy(engine, sc, prior_var, shape, rate, a, b, N, lik=0.0):
+    """The free energy of sgp_vmp_run (include/sgp_hip.h) after one host-paced iteration, by the same formulas in NumPy: the node
+    energy at the NEW q(w) = Gamma(a, b), the Probit factors' share `lik`, KL(q(v) || N(0, prior_var I)) and KL(q(w) || p(w))."""
+    from scipy.special import digamma, gammaln
+    mu, Sigma, _ = engine.posterior(want_uv=False)
+    M, S = mu.size, sc.sum_I1 + sc.sum_I2
+    elog = digamma(a) - np.log(b)
+    t0 = 0.5 * ((a / b) * S - N * elog + N * np.log(2.0 * np.pi))
+    t2 = 0.5 * (np.trace(Sigma) / prior_var + mu @ mu / prior_var - M + M * np.log(prior_var) + sc.logdet_lambda)
+    t3 = (a - shape) * digamma(a) - gammaln(a) + gammaln(shape) + shape * (np.log(b) - np.log(rate)) + a * (rate - b) / b
+    return ((t0 + lik) + t2) + t3
+
+
+def _vmp_device(engine, likelihood, iterations, shape, rate, free_energy):
+    """The iteration loop as one sgp_vmp_run; returns what the host-paced loops return (and the trace)."""
+    values, _, gamma, _, _ = engine.vmp_run(iterations, likelihood=likelihood, gamma_prior=(shape, rate))
+    mu, Sigma, _ = engine.posterior(want_uv=False)
+    out = (MvNormalMeanCovariance(mu, Sigma), (float(gamma[0]), float(gamma[1])))
+    return out + (values,) if free_energy else out
+
+
 def vmp_regression(p, xtrain, ytrain, Xu, engine, *, iterations=7, prior_var=50.0, shape=1e-2, rate=1e-2, jitter=1e-8,
-                   family="se"):
+                   family="se", device_paced=False, free_energy=False):
     """The inner `infer(...)` of experiments/GPT_regression.ipynb's `my_free_energy` (cell 9; model cell 6:
     `v ~ MvNormal(0, 50 I); w ~ Gamma(1e-2, 1e-2); y[i] ~ UniSGP(x[i], v, w, theta)`, mean field q(v) q(w), q(w) initialised
     at its prior, 7 iterations) at the kernel parameters p = (sigma2, lengthscale...) -- BASELINE config 1.  Per iteration:
@@ -177,17 +198,24 @@ def vmp_regression(p, xtrain, ytrain, Xu, engine, *, iterations=7, prior_var=50.
     set_engine_kernel(engine, float(p[0]), p[1:], jitter, family)
     engine.set_prior_isotropic(prior_var)
     engine.set_data(xtrain, np.asarray(ytrain, dtype=np.float64))
+    if device_paced:                                   # the loop below as one sgp_vmp_run: the host waits once
+        return _vmp_device(engine, "gaussian", iterations, shape, rate, free_energy)
+    trace = []
     for _ in range(iterations):
         engine.set_noise([[a / b]])
         engine.sweep()
         sc = engine.scalars()
         a, b = shape + 0.5 * len(ytrain), rate + 0.5 * (sc.sum_I1 + sc.sum_I2)
+        if free_energy:
+            trace.append(_host_free_energy(engine, sc, prior_var, shape, rate, a, b, len(ytrain)))
     mu, Sigma, _ = engine.posterior(want_uv=False)
+    if free_energy:
+        return MvNormalMeanCovariance(mu, Sigma), (a, b), np.array(trace)
     return MvNormalMeanCovariance(mu, Sigma), (a, b)
 
 
 def vmp_classification(p, xtrain, ytrain, Xu, engine, *, iterations=30, prior_var=50.0, shape=1e-2, rate=1e-2, jitter=0.0,
-                       family="se"):
+                       family="se", device_paced=False, free_energy=False):
     """The inner `infer(...)` of experiments/GPT_classification.ipynb's `my_free_energy` (cell 9; model cell 7:
     `f[i] ~ UniSGP(x[i], v, w, theta); y[i] ~ Probit(f[i])`, mean field q(f) q(v) q(w), q(v) and q(w) initialised at their
     priors, 30 iterations, K_uu without jitter).  Per iteration: q(f_i) from the :out message N(k_i' mu_v, 1 / mean(q_w))
@@ -202,9 +230,14 @@ def vmp_classification(p, xtrain, ytrain, Xu, engine, *, iterations=30, prior_va
     set_engine_kernel(engine, float(p[0]), p[1:], jitter, family)
     engine.set_prior_isotropic(prior_var)
     reuse = getattr(engine, "reuse_stats", False)
+    if device_paced:                                   # the loop below as one sgp_vmp_run: the host waits once
+        engine.set_data(xtrain, ytrain)
+        return _vmp_device(engine, "probit", iterations, shape, rate, free_energy)
+    trace = []
     for it in range(iterations):
         w = a / b
-        mf, vf = probit_marginal(ytrain, engine.predict(xtrain, mu), 1.0 / w)
+        mz = engine.predict(xtrain, mu)
+        mf, vf = probit_marginal(ytrain, mz, 1.0 / w)
         if it > 0 and reuse:
             engine.set_targets(mf, vf)         # x is fixed: only q(f) moves (the sweep then reuses K_uf, Psi2 and the K_uu chain)
         else:
@@ -214,7 +247,14 @@ def vmp_classification(p, xtrain, ytrain, Xu, engine, *, iterations=30, prior_va
         sc = engine.scalars()
         a, b = shape + 0.5 * len(ytrain), rate + 0.5 * (sc.sum_I1 + sc.sum_I2)
         mu = engine.posterior(want_cov=False, want_uv=False)[0]
+        if free_energy:
+            from scipy.special import log_ndtr
+            g = (2.0 * ytrain - 1.0) * mz / np.sqrt(1.0 + 1.0 / w)
+            lik = np.sum(-0.5 * np.log(2.0 * np.pi / w) - 0.5 * w * ((mf - mz) ** 2 + vf) - log_ndtr(g))
+            trace.append(_host_free_energy(engine, sc, prior_var, shape, rate, a, b, len(ytrain), lik))
     mu, Sigma, _ = engine.posterior(want_uv=False)
+    if free_energy:
+        return MvNormalMeanCovariance(mu, Sigma), (a, b), np.array(trace)
     return MvNormalMeanCovariance(mu, Sigma), (a, b)
 
 

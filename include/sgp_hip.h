@@ -629,6 +629,55 @@ int sgp_inducing_descend_psi(sgp_handle* h, const double* mean /* D x T */, cons
                              int32_t flags, int32_t steps, double eta, double beta1, double beta2, double eps, double* opt_state,
                              double* values, int64_t* counts /* 3, may be NULL */);
 
+/* ---- device-paced VMP iterations with the free energy: `infer(model, data, iterations = K, free_energy = true)` ----
+ * The inner call of every notebook's `my_free_energy` (experiments/GPT_regression.ipynb: 7 iterations, GPT_classification.ipynb: 30,
+ * GPLVM.ipynb: 6) for a UniSGP handle: K coordinate updates of q(f) (Probit only), q(v) and q(w) over the RESIDENT data of the last
+ * sgp_set_data (given without y_var and without pt_weight; SGP_VMP_GAUSSIAN: y_mean are the targets, SGP_VMP_PROBIT: labels in
+ * {0, 1}), at the Xu, kernel (any family), jitter and prior the setters left, all held for the whole call.  The host only enqueues,
+ * on the library's own stream, and waits once at the end.  With (a, b) = q(w) entering iteration k and w = a / b (SGP_VMP_HOLD_W: w
+ * and E[log w] of the last sgp_set_noise, never changed; gamma_prior and gamma are ignored and may be NULL):
+ *   1. Probit: q(f_i) from the forward message N(k_i' mu_v, 1 / w) -- mu_v = mu_init (NULL: 0) at k = 0, the previous iteration's
+ *      mean afterwards -- and the label, the moments of sgp_train_step's classification runs, written as the sweep's targets and
+ *      variances with the data scalars, as sgp_set_targets would leave them; and lik = sum_i [-1/2 log(2 pi / w)
+ *      - w ((mf_i - mz_i)^2 + vf_i) / 2 - log Phi(g_i)], the factors' energy minus the entropy of the tilted q(f_i);
+ *   2. q(v): iteration 0 is a full sweep, later ones run over the resident statistics (Gaussian: what SGP_SWEEP_REUSED does, Probit:
+ *      what SGP_SWEEP_TARGETS does) -- K_uf and Psi2 are formed once per call -- on every handle, with or without
+ *      SGP_FLAG_REUSE_STATS (phase 2 over resident statistics needs no allocation of its own);
+ *   3. q(w) <- Gamma(shape0 + N / 2, rate0 + (sum I1 + sum I2) / 2), N = the number of factor nodes; E[log w] = psi(a) - log b;
+ *   4. terms[4 k ..] = { 1/2 [w (sum I1 + sum I2) - N E[log w] + N log 2 pi] at the NEW q(w);  lik (0 for Gaussian);
+ *      KL(q(v) || p(v)) = 1/2 [tr(Lambda0 Sigma_v) + (mu_v - mu0)' Lambda0 (mu_v - mu0) - M - log|Lambda0| + log|Lambda|];
+ *      KL(q(w) || p(w)) = (a - a0) psi(a) - lgamma(a) + lgamma(a0) + a0 (log b - log b0) + a (b0 - b) / b  (0 with HOLD_W) },
+ *      values[k] = their sum, added in that order.  log|Lambda0| and mu0 are formed once per call: -M log s for the isotropic
+ *      prior; otherwise from one factorisation of the resident Lambda0 (sgp_set_prior keeps form 0 as a precision too);
+ *   5. if k >= 1, tol > 0 and |F_k - F_{k-1}| <= tol |F_k| the run has converged: the later iterations change nothing, and
+ *      values / terms beyond k stay NaN.
+ * A K_uu, Lambda or prior precision that is not positive definite at iteration k stops the run the same way: q(w) stays the one that
+ * entered k, values[k ..] are NaN and the call returns the failing leading minor.  With a dense prior (forms 0, 1) the call factors a
+ * copy of Lambda0 before iteration 0 in buffers every sweep rewrites -- the factor scratch, the q(v) covariance and the prior's status
+ * word among them: after a run that stopped at iteration 0 the covariance buffer holds Lambda0^-1 and SGP_R_INFO_PRIOR the status of
+ * Lambda0's factor (not Sigma0's); the getters refuse through the status words, as after any failed sweep.
+ * Host waits: the call waits for the handle's earlier work before it starts, like every setter, and blocks once at the end.  A Probit
+ * run also downloads the n resident labels first to check them (8 n bytes, blocking): the refusal has to come before anything is
+ * changed, and behind it iterations = 0 still returns 0.
+ * counts (2, may be NULL): iterations completed; 0, 1 = converged by tol, or minus the failing minor.  gamma receives (a, b).
+ * Afterwards the handle is what the host-paced sequence leaves: the getters give the last completed iteration's sweep, the noise is
+ * mean(q(w)) with E[log w] = psi(a) - log b (as if by sgp_set_noise after that sweep), Probit: the resident targets are the last
+ * q(f) -- NOT labels any more: a second Probit run needs sgp_set_data again --, sgp_sweep_kind's `last` is FULL after one
+ * iteration, else REUSED (Gaussian) or TARGETS (Probit), and on a SGP_FLAG_REUSE_STATS handle the statistics stay reusable.
+ * All sums run in fixed orders without atomics: identical calls agree bitwise, and K iterations agree bitwise with k then K - k
+ * through gamma and mu_init = the first call's mean (tol = 0; Probit: with the labels set again in between).
+ * SGP_ERR_ARG: d_out > 1; no data (or none of n >= 1), kernel or inducing inputs (a handle always has a prior: N(0, I) until
+ * sgp_set_prior); data set with y_var or pt_weight; exact-Psi statistics resident; a Probit label outside {0, 1}; iterations < 0;
+ * unknown flags or likelihood; non-positive or non-finite gamma / gamma_prior entries (without HOLD_W); a negative or NaN tol; a
+ * non-finite mu_init; an open sgp_train_* run; an installed all-reduce hook.  iterations = 0 returns 0 with nothing changed, behind
+ * every refusal. */
+enum { SGP_VMP_GAUSSIAN = 0, SGP_VMP_PROBIT = 1 };
+enum { SGP_VMP_HOLD_W = 1 };
+int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int32_t iterations,
+                const double* gamma_prior /* 2: shape0, rate0 */, double* gamma /* 2, in/out: q(w) shape, rate */,
+                const double* mu_init /* M, may be NULL = 0 */, double tol, double* values /* iterations, may be NULL */,
+                double* terms /* 4 x iterations column-major, may be NULL */, int64_t* counts /* 2, may be NULL */);
+
 /* ---- exact-Psi input messages: a node's energy and its derivatives in the mean and covariance of its Gaussian input ----
  * With q(v), W, G and s_t as for sgp_theta_objective_psi (SGP_KERNEL_SE only, d_out = 1 .. 4, D <= 8) and x_t ~ N(m_t, S_t), the part of
  * node t's average energy that depends on its input is

@@ -620,6 +620,24 @@ function theta_descend!(meta::HipSGPMeta, Î¸::Vector{Float64}, steps::Integer; Î
     return Î¸, values, Int(counts[1])
 end
 
+# ---- device-paced VMP iterations with the free energy (sgp_vmp_run): `infer(iterations = K, free_energy = true)` over the resident
+# data.  likelihood 0 Gaussian, 1 Probit (labels in {0, 1}); Î³0 = (shape0, rate0), Î³ = q(w) entering the run (in/out; nothing with
+# hold_w = true, which keeps the last set_noise); Î¼_init the mean of the first Probit forward message (nothing: 0).  Returns
+# (values, terms, Î³, iterations_done, converged); PosDefException(k) when K_uu or Î› failed (values from that iteration on are NaN).
+function vmp_run!(meta::HipSGPMeta, iterations::Integer; likelihood::Integer = 0, Î³0 = nothing, Î³ = nothing, Î¼_init = nothing,
+                  tol = 0.0, hold_w::Bool = false)
+    h = meta.handle
+    hold_w || Î³0 !== nothing || throw(ArgumentError("vmp_run!: Î³0 = (shape0, rate0) is required without hold_w"))
+    g0 = hold_w ? nothing : Float64[Î³0[1], Î³0[2]]
+    g = hold_w ? nothing : (Î³ === nothing ? copy(g0) : Float64[Î³[1], Î³[2]])
+    values = fill(NaN, max(iterations, 0)); terms = fill(NaN, 4, max(iterations, 0)); counts = zeros(Int64, 2)
+    check(ccall((:sgp_vmp_run, LIB), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, likelihood, hold_w ? 1 : 0, iterations, g0 === nothing ? C_NULL : g0, g === nothing ? C_NULL : g,
+                Î¼_init === nothing ? C_NULL : Î¼_init, tol, values, terms, counts), h.ptr)
+    return values, terms, g, Int(counts[1]), counts[2] == 1
+end
+
 # ---- the same objective and descent over the exact Psi-statistics of Gaussian inputs x_t ~ N(m_t, S_t) (SE kernel only;
 # sgp_theta_objective_psi, sgp_theta_descend_psi): m is D Ã— T, S is D Ã— D Ã— T or nothing (S = 0), y is T Ã— d_out.  No resident data are
 # needed; q(v) and W are the handle's.  theta_objective_psi returns (value, gradient w.r.t. (ÏƒÂ², â„“...)); theta_descend_psi! is

@@ -137,6 +137,14 @@ static int32_t plan_bits_of(const SweepPlan& p) {
 //                                               EVALUATED (theta, Xu)'s; the inducing inputs moved, as after sgp_set_inducing)
 //   sgp_inducing_descend_psi                    drops reuse; data_gen++ (nothing resident was rewritten, but the inducing inputs moved: the
 //                                               statistics on the device are those of the OLD Xu -- stale, though sgp_get_stats still hands them out)
+//   sgp_vmp_run                                 per iteration what its sweep does: the first fills the record as a full sgp_sweep (reusable on a
+//                                               REUSE_STATS handle, checked and targets cleared), the later ones run over the resident statistics
+//                                               and fill it again (targets cleared); Probit: data_gen++ per iteration, has_yv, the resident targets
+//                                               and data scalars become q(f)'s.  Behind the run: w0 = the noise the last completed sweep ran at
+//                                               (stats_swept_at), the noise in force = mean(q(w)); checked from the run's own K_uu and hand-off
+//                                               words, or reuse dropped; q(v) is the last completed sweep's.  A failed enqueue or wait drops reuse
+//                                               and q(v); a factorisation that failed on the device drops reuse when it was K_uu's and leaves
+//                                               q(v) to the status words (the getters refuse).  iterations = 0 changes nothing.
 // A new entry point gets a row here and an entry in MUTATORS / READERS of tests/call_sequence_ref.py, which drives every row in front
 // of every reader (tests/test_gpu_call_sequences.py) and holds the ledger of the exported names (tests/test_call_sequences_host.py).
 struct StatsRecord {

@@ -104,6 +104,17 @@ def kuu_cond(P, theta, family, Xu=None):
 SETTERS = ("inducing", "data", "targets", "cov_sum", "kernel", "family", "prior", "noise")    # the order `build` applies them in
 
 
+class Noise:
+    """a noise precision with the E[log w] it was set with (sgp_set_noise's second argument; a bare matrix: its default, log w)"""
+
+    def __init__(self, W, E_logw):
+        self.W, self.E_logw = np.atleast_2d(np.asarray(W, dtype=np.float64)), float(E_logw)
+
+
+def noise_matrix(value):
+    return value.W if isinstance(value, Noise) else np.asarray(value)
+
+
 class Shadow:
     """The handle's normal form.  `cur`: the setter values in force; `at`: those of the last sweep; `kind`: "sweep", "psi"
     (sweep_local_psi + sweep_finish), None (no sweep: nothing on the handle can be compared but a sweep) ; `post`: what has changed
@@ -196,7 +207,7 @@ def apply_set(dev, name, value):
         else:
             dev.set_prior_precision(value[1], value[2])
     elif name == "noise":
-        dev.set_noise(value)
+        dev.set_noise(value.W, value.E_logw) if isinstance(value, Noise) else dev.set_noise(value)
     else:
         raise KeyError(name)
 
@@ -255,10 +266,14 @@ class Op:
     needs first where the call leaves the handle without data."""
 
     def __init__(self, run, model=None, kind=REUSED, rows=(), problems=PROBLEMS, nothing=False, restore=None, model_restore=None,
-                 out=None):
+                 out=None, prepare=None, last=None):
         self.run, self.model, self.kind, self.rows, self.problems = run, model, kind, tuple(rows), tuple(problems)
         self.out = out or _flat                               # (readers) the arrays of a result that are compared
         self.nothing, self.restore, self.model_restore = nothing, restore, model_restore
+        # prepare(dev, P): what `run` itself does first where the call refuses the problem's state as it stands (a `nothing` call is
+        # then held to the state behind prepare + the call's own part, `run` without it being run(dev, P, prepared=True));
+        # last: sgp_sweep_kind's `last` behind the call on EVERY handle where the header documents one (None: a sgp_sweep's)
+        self.prepare, self.last = prepare, last
 
 
 def _setter(name, key):
@@ -398,7 +413,7 @@ def _m_inducing(psi, steps):
 def _m_carry(m, P, r, d):
     """prior <- posterior in natural form, from the statistics the handle hands out: Lambda0 += W (x) Psi2, xi0 += vec(B W)"""
     Psi2, B, _ = d.stats()
-    W, Q = np.asarray(m.cur["noise"]), P["d_out"] * P["M"]
+    W, Q = noise_matrix(m.cur["noise"]), P["d_out"] * P["M"]
     prior = m.cur["prior"]
     L0, xi0 = (np.eye(Q) / prior[1], np.zeros(Q)) if prior[0] == "iso" else (prior[2], prior[1])
     m.set("prior", ("precision", xi0 + (B.reshape(P["M"], P["d_out"]) @ W).T.ravel(), L0 + np.kron(W, Psi2)), device=True)
@@ -413,6 +428,106 @@ def _set_posterior(d, P):
     mu2, Uv2 = 0.9 * mu, 1.1 * Uv
     d.set_posterior(mu2, Uv2)
     return mu2, Uv2
+
+
+# ---- sgp_vmp_run (d_out = 1 only: `uni`) ---------------------------------------------------------------------------------------
+# The call refuses data with point variances, which `uni` carries: every entry first sets (X, Y) alone, and the model records that.
+# Kinds by hand from the header: "on a SGP_FLAG_REUSE_STATS handle the statistics stay reusable" -> REUSED; `last` "is FULL after one
+# iteration, else REUSED (Gaussian) or TARGETS (Probit)" on every handle.  The host equivalent of a run is the host-paced sequence the
+# header names: the last completed iteration's setters (Probit: its q(f) as targets and variances; the noise that entered it with
+# E[log w] = psi(a) - log b), one sweep, then set_noise(mean(q(w)), psi(a) - log b).  The noise that entered the last iteration is
+# known because the run is made in two calls through `gamma`, documented to equal the single call bitwise.
+VMP_PRIOR_G = (1e-2, 1e-2)
+
+
+def _vmp_data(P, targets=None, variances=None):
+    return (P["X"], P["Y"] if targets is None else targets, variances, None, None)
+
+
+def _vmp_prepare(d, P):
+    apply_set(d, "data", _vmp_data(P))
+
+
+def _gamma_noise(g):
+    from scipy.special import digamma
+    a, b = float(g[0]), float(g[1])
+    return Noise([[a / b]], digamma(a) - math.log(b))
+
+
+def _vmp_run_0(d, P, prepared=False):
+    if not prepared:
+        _vmp_prepare(d, P)
+        d.sweep()
+    return d.vmp_run(0, gamma_prior=VMP_PRIOR_G)
+
+
+def _m_vmp_run_0(m, P, r, d):
+    m.set("data", _vmp_data(P))
+    m.swept()
+
+
+def _vmp_hold(d, P):
+    _vmp_prepare(d, P)
+    return d.vmp_run(3, hold_w=True)
+
+
+def _vmp_gauss(d, P):
+    _vmp_prepare(d, P)
+    _, _, g2, done, _ = d.vmp_run(2, gamma_prior=VMP_PRIOR_G)
+    _, _, g3, done2, _ = d.vmp_run(1, gamma_prior=VMP_PRIOR_G, gamma=g2)
+    assert (done, done2) == (2, 1)
+    return g2, g3
+
+
+def _m_vmp(m, P, r, d):
+    """r = (q(w) that entered the last completed iteration, the final q(w)[, the targets and variances of that iteration])"""
+    m.set("data", _vmp_data(P, *r[2:4]), device=len(r) > 2)
+    m.set("noise", _gamma_noise(r[0]), device=True)           # (the device's digamma is not SciPy's to the last bit)
+    m.swept()
+    m.set("noise", _gamma_noise(r[1]), device=True)
+
+
+def vmp_labels(P):
+    return (P["Y"] > 0).astype(np.float64)
+
+
+def _vmp_probit(d, P):
+    from scipy.special import log_ndtr
+    from tests import vmp_ref
+    lab = vmp_labels(P)
+    apply_set(d, "data", _vmp_data(P, lab))
+    _, _, g2, done, _ = d.vmp_run(2, likelihood="probit", gamma_prior=VMP_PRIOR_G)
+    mu2 = d.posterior(want_cov=False, want_uv=False)[0]
+    apply_set(d, "data", _vmp_data(P, lab))                    # the resident targets are q(f) now: the labels again
+    _, _, g3, done2, _ = d.vmp_run(1, likelihood="probit", gamma_prior=VMP_PRIOR_G, gamma=g2, mu_init=mu2)
+    assert (done, done2) == (2, 1)
+    # the last iteration's q(f) in NumPy, from the reference kernel and the mean that entered it
+    s2, ell, _ = P["theta1"]
+    mz = vmp_ref.kernel(P["Xu"], P["X"], s2, ell).T @ mu2
+    mf, vf, _ = vmp_ref.probit_moments(lab, mz, float(g2[1]) / float(g2[0]), log_ndtr)
+    return g2, g3, mf, vf
+
+
+@functools.lru_cache(maxsize=None)
+def vmp_tol_stop(pname="uni"):
+    """(tol, k): a tol between the restatement's relative decrements at iterations k - 1 and k, so that the run stops after k + 1"""
+    from tests import vmp_ref
+    P = problem(pname)
+    s2, ell, jit = P["theta1"]
+    v = vmp_ref.vmp_run_ref(P["X"], P["Y"], P["Xu"], s2, ell, jit, P["prior"], 7, gamma_prior=VMP_PRIOR_G)["values"]
+    dec = np.abs(np.diff(v)) / np.abs(v[1:])
+    k = 3
+    assert dec[k - 1] < dec[k - 2] / 4, ("the trace does not separate the two decrements", dec)
+    return float(np.sqrt(dec[k - 1] * dec[k - 2])), k
+
+
+def _vmp_tol_stop(d, P):
+    tol, k = vmp_tol_stop(P["name"])
+    _vmp_prepare(d, P)
+    _, _, g_in, _, _ = d.vmp_run(k, gamma_prior=VMP_PRIOR_G)   # q(w) entering iteration k (the run below repeats these bitwise)
+    values, _, g, done, conv = d.vmp_run(7, gamma_prior=VMP_PRIOR_G, tol=tol)
+    assert (done, conv) == (k + 1, True) and np.isnan(values[k + 1:]).all(), (done, conv, values)
+    return g_in, g
 
 
 MUTATORS = {
@@ -452,7 +567,12 @@ MUTATORS = {
                                          rows=["sgp_inducing_descend_psi"]),
     "sweep_local_psi+finish": Op(_psi_sweep, _m_psi_sweep, kind=FULL, rows=["sgp_sweep_local_psi"], restore=_restore_data,
                                  model_restore=_m_restore_data),
+    "vmp_run_hold_3": Op(_vmp_hold, _m_vmp_run_0, kind=REUSED, rows=["sgp_vmp_run"], problems=["uni"], last=REUSED),
+    "vmp_run_gauss_3": Op(_vmp_gauss, _m_vmp, kind=REUSED, rows=["sgp_vmp_run"], problems=["uni"], last=FULL),
+    "vmp_run_probit_3": Op(_vmp_probit, _m_vmp, kind=REUSED, rows=["sgp_vmp_run"], problems=["uni"], last=FULL),
+    "vmp_run_tol_stop": Op(_vmp_tol_stop, _m_vmp, kind=REUSED, rows=["sgp_vmp_run"], problems=["uni"], last=REUSED),
     # the calls that claim to change nothing
+    "vmp_run_0": Op(_vmp_run_0, _m_vmp_run_0, kind=REUSED, rows=["sgp_vmp_run"], problems=["uni"], nothing=True, prepare=_vmp_prepare),
     "psi_stats": Op(lambda d, P: d.psi_stats(P["mean"], P["cov"], want_out=True), nothing=True),
     "theta_objective_psi": Op(lambda d, P: d.theta_objective_psi(*_psi(P), want_grad=True), nothing=True,
                               rows=["sgp_theta_objective_psi"]),
@@ -514,7 +634,7 @@ ENTRY_POINTS = {
         "sgp_use_rccl",                # (the set_allreduce row: it installs the hook; driving it needs a communicator)
         "sgp_time_kernel", "sgp_train_begin", "sgp_train_step", "sgp_train_end", "sgp_train_likelihood", "sgp_set_posterior",
         "sgp_carry_posterior", "sgp_theta_descend", "sgp_theta_descend_psi", "sgp_inducing_descend", "sgp_inducing_descend_psi",
-        "sgp_sweep_local_psi")},
+        "sgp_sweep_local_psi", "sgp_vmp_run")},
     **{n: READER for n in (
         "sgp_get_posterior", "sgp_get_scalars", "sgp_get_stats", "sgp_get_kuu_chol", "sgp_get_wishart_invscale", "sgp_sweep_kind",
         "sgp_w_stats", "sgp_predict", "sgp_predict_var", "sgp_in_message", "sgp_in_message_grad", "sgp_out_message",

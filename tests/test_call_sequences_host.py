@@ -42,8 +42,15 @@ def test_every_row_of_the_comment_table_has_a_mutator_entry():
                  "inducing_descend_psi_0", "inducing_descend_psi_3", "inducing_descend_psi_3_xu_only", "train_run", "set_posterior",
                  "carry_posterior", "set_targets", "set_output_cov_sum", "sweep_local_psi+finish", "psi_stats", "theta_objective_psi",
                  "theta_objective_psi_xu", "psi_in_grad", "psi_predict", "predict", "predict_var", "w_stats", "in_message",
-                 "in_message_grad", "out_message"):
+                 "in_message_grad", "out_message", "vmp_run_0", "vmp_run_hold_3", "vmp_run_gauss_3", "vmp_run_probit_3",
+                 "vmp_run_tol_stop"):
         assert name in CR.MUTATORS, name
+    for name, op in CR.MUTATORS.items():                      # sgp_vmp_run refuses d_out > 1
+        if "sgp_vmp_run" in op.rows:
+            assert op.problems == ("uni",) and op.kind == CR.REUSED, name
+    assert {n: CR.MUTATORS[n].last for n in CR.MUTATORS if CR.MUTATORS[n].last is not None} == {
+        "vmp_run_hold_3": CR.REUSED, "vmp_run_gauss_3": CR.FULL, "vmp_run_probit_3": CR.FULL, "vmp_run_tol_stop": CR.REUSED}
+    assert CR.ENTRY_POINTS["sgp_vmp_run"] == CR.MUTATOR
     assert CR.MUTATORS["set_output_cov_sum"].problems == ("multi",) and CR.MUTATORS["train_run"].problems == ("uni",)
     assert all(op.kind == CR.REUSED for op in CR.MUTATORS.values() if op.nothing)
 
@@ -180,6 +187,28 @@ def test_the_normal_form_of_a_ten_call_history():
     assert m.device_set                                        # (q(v) is still that sweep's)
     m.swept()
     assert not m.device_set
+    # a noise with its E[log w] (what sgp_vmp_run leaves: psi(a) - log b, not set_noise's default log w) travels as one value; one
+    # that came back from the device flags the history like a device-set kernel
+    class Recorder:
+        def set_noise(self, W, E_logw=None):
+            self.noise = (np.asarray(W), E_logw)
+    n1, n2 = CR._gamma_noise((3.0, 2.0)), CR._gamma_noise((5.0, 2.0))
+    assert n1.W.shape == (1, 1) and n1.W[0, 0] == 1.5 and abs(n1.E_logw - (0.9227843350984671 - np.log(2.0))) < 1e-15   # psi(3) = 3/2 - gamma
+    assert n1.E_logw < np.log(1.5) and CR.noise_matrix(n1) is n1.W and CR.noise_matrix(P["W"]).shape == P["W"].shape
+    m.set("noise", n1, device=True)
+    m.swept()
+    m.set("noise", n2, device=True)
+    nf = m.normal_form()
+    assert m.device_set and [o[:2] for o in nf[-3:]] == [("set", "noise"), ("sweep",), ("set", "noise")]
+    assert nf[-3][2] is n1 and nf[-1][2] is n2
+    rec = Recorder()
+    CR.apply_set(rec, "noise", nf[-1][2])
+    assert rec.noise[0][0, 0] == 2.5 and rec.noise[1] == n2.E_logw
+    CR.apply_set(rec, "noise", P["W"])
+    assert rec.noise[0] is P["W"] and rec.noise[1] is None
+    m.set("noise", P["W"])
+    m.swept()
+    assert not m.device_set
     # the exact-Psi sweep leaves the handle without data
     m.swept("psi", (P["mean"], P["cov"], P["Yn"]))
     assert m.cur["data"] is None and m.normal_form()[-1][0] == "psi_sweep"
@@ -204,3 +233,11 @@ def test_kuu_is_well_conditioned_at_every_theta_of_the_tables(name):
         np.testing.assert_allclose(np.einsum("tp,tpi->ti", w, pts), P["mean"], rtol=1e-12, atol=1e-14)
         dev = pts - P["mean"][:, None, :]
         np.testing.assert_allclose(np.einsum("tp,tpi,tpj->tij", w, dev, dev), P["cov"], rtol=1e-10, atol=1e-14)
+
+
+def test_the_tol_of_vmp_run_tol_stop_separates_two_decrements_of_the_restatement():
+    tol, k = CR.vmp_tol_stop("uni")
+    assert k == 3 and 0.0 < tol < 1.0
+    P = CR.problem("uni")
+    lab = CR.vmp_labels(P)
+    assert set(np.unique(lab)) == {0.0, 1.0} and 0.3 < lab.mean() < 0.7

@@ -156,7 +156,9 @@ def test_next_sweep_kind_after(G, mname, pname):
         a, b, model, refused = prepared(G, P, mname, stack)
         assert refused is None, refused
         assert a.sweep_kind()[0] == mut.kind, (mname, a.sweep_kind(), mut.kind)
-        assert b.sweep_kind() == (CR.FULL, CR.FULL)
+        assert b.sweep_kind() == (CR.FULL, CR.FULL if mut.last is None else mut.last)
+        if mut.last is not None:                               # (a call that sweeps on its own documents its `last` for every handle)
+            assert a.sweep_kind()[1] == mut.last, (mname, a.sweep_kind(), mut.last)
         if mut.restore:                                        # (the call leaves the handle without data)
             assert a.sweep_kind()[0] == CR.FULL
             mut.restore(a, P)
@@ -192,10 +194,88 @@ def test_nothing_calls_change_nothing(G, pname):
         for mname, mut in CR.MUTATORS.items():
             if not mut.nothing or pname not in mut.problems:
                 continue
-            mut.run(a, P)
+            if mut.prepare:                                    # the call refuses the problem's state as it stands: behind what it needs
+                mut.prepare(a, P)                              # and a sweep, it and every later call are held to THAT state
+                a.sweep()
+                before, kinds = snapshot(a), a.sweep_kind()
+                mut.run(a, P, prepared=True)
+            else:
+                mut.run(a, P)
             after = snapshot(a)
             assert all(before[k].tobytes() == after[k].tobytes() for k in before), mname
             assert a.sweep_kind() == kinds == (CR.REUSED, CR.FULL), mname
+
+
+def _answer(G, name, dev, P):
+    """a reader's arrays, or what it raised (a failed factorisation is reported by the getters as LinAlgError, PosDefException or
+    SGPError: the class and the text are compared)"""
+    try:
+        if name == "sweep":
+            dev.sweep()
+            return snapshot(dev), None
+        return flat(name, CR.READERS[name].run(dev, P)), None
+    except (G.SGPError, np.linalg.LinAlgError, ArithmeticError, ValueError) as e:
+        return None, (type(e).__name__, str(e))
+
+
+def failure_problem():
+    """the `toy` case of tests/test_gpu_vmp_run.py (its test_failure_stop_and_recovery: two coincident inducing inputs and no jitter make
+    K_uu fail at minor 6) with what the readers of this grid ask for"""
+    from tests import test_gpu_vmp_run as V
+    T = V.problem("toy")
+    rng = np.random.default_rng(103)
+    N, M, D = T["N"], T["M"], T["D"]
+    Xu = T["Xu"].copy()
+    Xu[5] = Xu[2]
+    theta = (T["s2"], T["ell"], T["jitter"])
+    return dict(name="toy", d_out=1, D=D, M=M, N=N, X=T["X"], Y=T["y"], vy=None, wts=None, n_nodes=None, Xu=T["Xu"], Xu_bad=Xu,
+                Xu2=CR._grid_xu(rng, M, D), W=np.array([[20.0]]), prior=T["prior"], theta1=theta, theta_bad=(T["s2"], T["ell"], 0.0),
+                raw2=CR.invsoftplus(np.concatenate([[1.1 * T["s2"]], 0.9 * T["ell"]])), Xq=rng.uniform(-1.7, 1.7, (37, D)),
+                qstart=np.array([0, 5, 6, 20, 37]), Yq=rng.normal(size=(4, 1)), wq=rng.uniform(0.2, 1.0, 37))
+
+
+def test_failed_vmp_run_leaves_no_q_v(G):
+    """A run whose K_uu is not positive definite (a status, not a fault) returns the failing minor at iteration 0.  The statistics its
+    sweep formed are not reusable, and no reader hands out on the SGP_FLAG_REUSE_STATS handle anything the plain handle does not: the
+    same arrays or the same refusal."""
+    import contextlib
+    P = failure_problem()
+    cells = []
+    for rname, reader in CR.READERS.items():
+        with contextlib.ExitStack() as stack:
+            a, b = stack.enter_context(handle(G, P, True)), stack.enter_context(handle(G, P))
+            CR.start([a, b], P)
+            assert a.sweep_kind()[0] == CR.REUSED
+            for d in (a, b):
+                d.set_inducing(P["Xu_bad"])
+                d.set_kernel(*P["theta_bad"])
+                with pytest.raises(np.linalg.LinAlgError) as e:
+                    d.vmp_run(4, gamma_prior=CR.VMP_PRIOR_G)
+                assert e.value.minor == 6 and e.value.iterations_done == 0 and np.isnan(e.value.values).all()
+                assert e.value.counts == (0, -6)
+            assert a.sweep_kind()[0] == CR.FULL and b.sweep_kind()[0] == CR.FULL
+            ra, fa = _answer(G, rname, a, P)
+            rb, fb = _answer(G, rname, b, P)
+            assert fa == fb, f"failed vmp_run -> {rname}: A {fa} but B {fb}"
+            if fa is None:                                     # (bytes: a reader that does not look at the status words -- w_stats, after any
+                # failed sweep -- hands out the NaN of the failed factor, on both handles alike)
+                assert all(ra[k].tobytes() == rb[k].tobytes() for k in ra), f"failed vmp_run -> {rname}: A and B differ"
+                finite = all(np.isfinite(ra[k]).all() for k in ra)
+            cells.append((rname, ("same-answer" if finite else "same-answer non-finite") if fa is None else f"same-refusal {fa[0]}"))
+    for rname, cell in cells:
+        print(f"CELL vmp_run_failed {rname} toy {cell}")
+
+
+def test_a_second_probit_run_needs_set_data(G):
+    """behind a Probit run the resident targets are q(f) with its variances, no labels: the header asks for sgp_set_data first"""
+    P = CR.problem("uni")
+    with handle(G, P, True) as a:
+        CR.start([a], P)
+        CR.MUTATORS["vmp_run_probit_3"].run(a, P)
+        with pytest.raises(G.SGPError, match="the resident data must have been set without y_var"):
+            a.vmp_run(1, likelihood="probit", gamma_prior=CR.VMP_PRIOR_G)
+        a.set_data(P["X"], CR.vmp_labels(P))
+        assert a.vmp_run(1, likelihood="probit", gamma_prior=CR.VMP_PRIOR_G)[3] == 1
 
 
 def test_stale_statistics_are_only_handed_out_where_documented(G):

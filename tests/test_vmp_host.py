@@ -1,5 +1,6 @@
 """sgp_vmp_run's NumPy restatement (tests/vmp_ref.py) without a GPU: against itself in extended precision, the monotone decrease of
-the free energy, the closed-form Probit term against Gauss-Hermite quadrature, and the seeded mutants."""
+the free energy, the closed-form Probit term against Gauss-Hermite quadrature, the seeded mutants, and for the branch cases of
+tests/test_gpu_vmp_run.py their conditioning and the one mutant per branch that their tolerances must see."""
 import numpy as np
 import pytest
 from scipy import special
@@ -48,7 +49,7 @@ def test_probit_term_against_gauss_hermite():
                 assert abs(quad - closed) <= 1e-6 * max(1.0, abs(closed)), (vz, g, yl, quad, closed)
 
 
-@pytest.mark.parametrize("mutant", R.MUTANTS)
+@pytest.mark.parametrize("mutant", R.FORMULA_MUTANTS)
 def test_mutants_miss_the_tolerances(mutant):
     """each seeded fault moves the free energy by far more than 10 x (floor, 50 eps sensitivity)"""
     N, M, D = 300, 70, 3
@@ -60,3 +61,71 @@ def test_mutants_miss_the_tolerances(mutant):
     factor = np.abs(m["values"] - a["values"]).max() / tol
     print(f"mutant {mutant}: misses the tolerance by a factor {factor:.3g}")
     assert factor > 100
+
+
+# ---- the branch cases of tests/test_gpu_vmp_run.py ------------------------------------------------------------------------------
+def test_matern_kernels_against_their_closed_forms_in_one_dimension():
+    """kappa(r) of include/sgp_hip.h at r = |x - z| / ell, typed out once more for scalars"""
+    x, z, ell, s2 = np.array([[0.3]]), np.array([[-1.1]]), 0.7, 0.8
+    r = 1.4 / 0.7
+    assert R.kernel(x, z, s2, ell, "matern12")[0, 0] == pytest.approx(s2 * np.exp(-r), rel=1e-15)
+    assert R.kernel(x, z, s2, ell, "matern32")[0, 0] == pytest.approx(s2 * (1 + 3 ** 0.5 * r) * np.exp(-3 ** 0.5 * r), rel=1e-15)
+    for fam in ("matern12", "matern32", "matern52", "se"):
+        assert R.kernel(x, x, s2, ell, fam)[0, 0] == s2
+
+
+def test_kuu_is_well_conditioned_in_every_branch_case():
+    from tests import test_gpu_vmp_run as G
+    for name in list(G.BRANCH_CASES) + ["tails"]:
+        P = G.tails_problem(10)[0] if name == "tails" else G.problem(name)
+        c = np.linalg.cond(R.kernel(P["Xu"], P["Xu"], P["s2"], P["ell"], P["family"]) + P["jitter"] * np.eye(P["M"]))
+        print(f"vmp_run {name}: cond(K_uu + jitter I) {c:.3e}")
+        assert c < 1e8
+        if name in ("d5", "dmax"):                            # lengthscales proportional to sqrt(D) keep K_uu away from the identity
+            K = R.kernel(P["Xu"], P["Xu"], 1.0, P["ell"])
+            assert 0.01 < np.median(K[np.triu_indices(P["M"], 1)]) < 0.05 and c < 200
+
+
+# mutant -> (the case that reaches its branch, iterations).  The digamma mutant is held at n1 (a = 0.51, ten recurrence steps): at
+# n19 (a = 9.51, one step) the series without the step is already right to 1e-16 -- its first omitted term is 3617 / (8160 a^16) --
+# so no tolerance can see the step there; n19 / n20 hold the threshold itself.
+BRANCH_OF = {"kl_iso_tail": ("kl_iso_257", 7), "kl_dense_tail": ("kl_dense_300", 7), "reduce_tail": ("reduce_65537", 1),
+             "digamma_no_recurrence": ("n1", 7), "log_ndtr_naive": ("tails", 2)}
+
+
+@pytest.mark.parametrize("mutant", R.BRANCH_MUTANTS)
+def test_branch_mutants_are_seen_at_their_case_and_nowhere_below_it(mutant):
+    """At the case that reaches the branch the fault moves a compared quantity beyond that case's tolerance -- the very tolerance
+    tests/test_gpu_vmp_run.py holds the device to --, and at `ard` it changes no bit: the cases below the thresholds could not see it."""
+    from tests import test_gpu_vmp_run as G
+    if R.mpmath is None:
+        print("vmp_ref: mpmath is missing -- the extended run's psi, lgamma and log Phi are SciPy's float64 ones")
+    name, K = BRANCH_OF[mutant]
+    assert set(BRANCH_OF) == set(R.BRANCH_MUTANTS)
+    if name == "tails":
+        P = G.tails_problem(10)[0]
+        kw = dict(likelihood="probit", gamma_prior=G.PRIOR_G, gamma=G.TAILS_GAMMA, mu_init=P["mu_init"])
+        ref, tol = G.tails_reference(10, K)
+    else:
+        P = G.problem(name)
+        kw = dict(likelihood=P["lik"], gamma_prior=P["g0"], hold_w=P["hold"], family=P["family"])
+        ref, tol = G.reference(name, K)
+    m = R.vmp_run_ref(P["X"], P["y"], P["Xu"], P["s2"], P["ell"], P["jitter"], P["prior"], K, mutant=mutant, **kw)
+    # every quantity test_against_the_restatement compares, by its own tolerance (psi(a) cancels in the SUM of the terms: only the
+    # node's term and KL(q(w)) can see a digamma fault)
+    with np.errstate(invalid="ignore"):
+        ratios = {q: np.abs(m[q] - ref[q]).max() / tol[q] for q in ("values", "mu", "Sigma")}
+        for j in range(4):
+            if tol["terms"][j] > 0:
+                ratios[f"terms{j}"] = np.abs(m["terms"][:, j] - ref["terms"][:, j]).max() / tol["terms"][j]
+    ratios = {q: (v if np.isfinite(v) else np.inf) for q, v in ratios.items()}
+    q, factor = max(ratios.items(), key=lambda kv: kv[1])
+    print(f"mutant {mutant} at {name} (K = {K}): deviation / tolerance {factor:.3g} ({q}; of the free energy {ratios['values']:.3g})")
+    assert factor > 1.0
+    A = G.problem("ard")
+    kw = dict(likelihood=A["lik"], gamma_prior=A["g0"], hold_w=A["hold"], family=A["family"])
+    args = (A["X"], A["y"], A["Xu"], A["s2"], A["ell"], A["jitter"], A["prior"], 7)
+    plain, mut = R.vmp_run_ref(*args, **kw), R.vmp_run_ref(*args, mutant=mutant, **kw)
+    for q in ("values", "terms", "mu", "Sigma"):
+        assert np.array_equal(plain[q], mut[q]), q
+    assert plain["gamma"] == mut["gamma"]

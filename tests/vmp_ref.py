@@ -19,7 +19,13 @@ except ImportError:                                          # pragma: no cover
 from scipy import special
 
 LOG2PI = np.log(2.0 * np.pi)
-MUTANTS = ("elogw_pointmass", "energy_old_qw", "drop_M", "logdet0_sign", "last_block_lik", "vz_new_w")
+FORMULA_MUTANTS = ("elogw_pointmass", "energy_old_qw", "drop_M", "logdet0_sign", "last_block_lik", "vz_new_w")
+# one fault per branch of the three kernels that only a shape beyond the first workgroup (or the first pass, or the asymptotic range)
+# reaches; each is invisible, bitwise, at the shapes below those thresholds (tests/test_vmp_host.py)
+BRANCH_MUTANTS = ("kl_iso_tail", "kl_dense_tail", "reduce_tail", "digamma_no_recurrence", "log_ndtr_naive")
+MUTANTS = FORMULA_MUTANTS + BRANCH_MUTANTS
+KL_BLOCK = 256                                               # entries per workgroup (isotropic prior) / rows per pass (dense) of k_vmp_kl
+REDUCE_PASS = 256 * 256                                      # points behind one pass of the reduce stage: 256 pairs of 256 points
 
 
 def make_toy(N, M, D, seed, probit=False):
@@ -38,6 +44,10 @@ def kernel(A, B, s2, ell, family="se"):
     if family == "se":
         return s2 * np.exp(-s / 2)
     r = np.sqrt(s)
+    if family == "matern12":
+        return s2 * np.exp(-r)
+    if family == "matern32":
+        return s2 * (1 + np.sqrt(A.dtype.type(3)) * r) * np.exp(-np.sqrt(A.dtype.type(3)) * r)
     if family == "matern52":
         return s2 * (1 + np.sqrt(A.dtype.type(5)) * r + 5 * s / 3) * np.exp(-np.sqrt(A.dtype.type(5)) * r)
     raise ValueError(family)
@@ -81,6 +91,19 @@ def _special(dtype):
     f = lambda fn: (lambda x: np.vectorize(lambda v: np.longdouble(str(fn(mpmath.mpf(float(v)) if not isinstance(v, np.longdouble)
                                                                       else mpmath.mpf(str(v))))), otypes=[np.longdouble])(x))
     return f(mpmath.digamma), f(mpmath.loggamma), f(lambda g: mpmath.log(mpmath.ncdf(g)))
+
+
+def digamma_asymptotic(x):
+    """log x - 1 / (2 x) - sum_k B_2k / (2 k x^2k) through x^-14, with no recurrence in front of it (the mutant "digamma_no_recurrence")"""
+    i2 = 1 / (x * x)
+    s = i2 * (1 / 12 - i2 * (1 / 120 - i2 * (1 / 252 - i2 * (1 / 240 - i2 * (1 / 132 - i2 * (691 / 32760 - i2 / 12))))))
+    return np.log(x) - 0.5 / x - s
+
+
+def log_ndtr_naive(g):
+    """log Phi(g) as log(erfc(-g / sqrt 2) / 2) in both tails (the mutant "log_ndtr_naive": -inf below g = -38.5)"""
+    with np.errstate(divide="ignore"):
+        return np.log(0.5 * special.erfc(-np.asarray(g, dtype=np.float64) / np.sqrt(2.0)))
 
 
 def probit_moments(y, mz, vz, log_ndtr):
@@ -138,12 +161,15 @@ def vmp_run_ref(X, y, Xu, s2, ell, jitter, prior, iterations, *, likelihood="gau
             vz = 1 / wd
             mz = Kuf.T @ mu
             mf, vf, g = probit_moments(y, mz, vz, log_ndtr)
-            li = probit_lik(mz, vz, mf, vf, g, log_ndtr)
+            li = probit_lik(mz, vz, mf, vf, g, log_ndtr_naive if mutant == "log_ndtr_naive" else log_ndtr)
             if mutant == "last_block_lik":
                 li = li[:(N - 1) // 256 * 256] if N > 256 else li[:0]
+            sq = mf * mf + vf
+            if mutant == "reduce_tail" and N > REDUCE_PASS:      # the pairs of the second pass never arrive
+                li, sq = li[:REDUCE_PASS], sq[:REDUCE_PASS]
             lik = li.sum()
             moments = (mz, mf, vf, g)
-            tgt, syy = mf, (mf * mf + vf).sum()
+            tgt, syy = mf, sq.sum()
         else:
             tgt, syy = y, (y * y).sum()
         P2 = Psi2 * (1 + t(displace))
@@ -157,7 +183,7 @@ def vmp_run_ref(X, y, Xu, s2, ell, jitter, prior, iterations, *, likelihood="gau
         t3 = t(0)
         if hold_w is None:
             a, b = a0 + t(N) / 2, b0 + S / 2
-            psi = digamma(a)
+            psi = digamma_asymptotic(a) if mutant == "digamma_no_recurrence" and a < 10 else digamma(a)
             w, elog = a / b, (np.log(a / b) if mutant == "elogw_pointmass" else psi - np.log(b))
             t3 = (a - a0) * psi - gammaln(a) + gammaln(a0) + a0 * (np.log(b) - np.log(b0)) + a * (b0 - b) / b
         if probit and mutant == "vz_new_w":
@@ -165,7 +191,11 @@ def vmp_run_ref(X, y, Xu, s2, ell, jitter, prior, iterations, *, likelihood="gau
         we, ee = (w_old, elog_old) if mutant == "energy_old_qw" else (w, elog)
         t0 = 0.5 * (we * S - N * ee + N * t(LOG2PI))
         d = mu - mu0
-        t2 = 0.5 * (np.sum(L0 * Sigma) + d @ L0 @ d - (0 if mutant == "drop_M" else M) - ld0 + ldL)
+        L0k = L0
+        if M > KL_BLOCK and mutant == ("kl_iso_tail" if prior[0] == "iso" else "kl_dense_tail"):
+            L0k = L0.copy()                                  # the diagonal entries resp. the rows of Lambda0 from 256 on never arrive
+            L0k[KL_BLOCK:, :] = 0
+        t2 = 0.5 * (np.sum(L0k * Sigma) + d @ L0k @ d - (0 if mutant == "drop_M" else M) - ld0 + ldL)
         terms.append([t0, lik, t2, t3])
         values.append(((t0 + lik) + t2) + t3)
         mus.append(mu.copy())
@@ -175,8 +205,8 @@ def vmp_run_ref(X, y, Xu, s2, ell, jitter, prior, iterations, *, likelihood="gau
 # ---- the ledger of exported names --------------------------------------------------------------------------------------------
 # tests/call_sequence_ref.ENTRY_POINTS classifies every exported sgp_* name (tests/test_call_sequences_host.py holds it to the header).
 # sgp_vmp_run sweeps: it rewrites q(v), the noise and, for Probit, the resident targets, so it is a mutator; what it leaves is held to
-# the host-paced sequence by tests/test_gpu_vmp_run.py (test_state_afterwards, test_state_equals_the_host_paced_sequence).  Its entry
-# is made here, in the module both vmp suites import, and so is present whenever the suite is collected.
+# the host-paced sequence by tests/test_gpu_vmp_run.py (test_state_afterwards, test_state_equals_the_host_paced_sequence) and by the
+# vmp_run_* entries of the call grid.  ENTRY_POINTS names it itself now; the registration below is kept and changes nothing.
 def register_entry_point():
     from tests import call_sequence_ref as CR
     CR.ENTRY_POINTS.setdefault("sgp_vmp_run", CR.MUTATOR)

@@ -17,7 +17,7 @@ SGP_FLAG_KEEP_KUF = 2
 SGP_FLAG_GRAPH = 4             # no-op: graph replay was measured slower and removed (DESIGN.md "Launch mode")
 SGP_FLAG_PERSISTENT_CHAIN = 8
 SGP_FLAG_REUSE_STATS = 16      # sgp_sweep reuses the resident statistics where the setters left them valid (sgp_sweep_kind)
-SGP_SWEEP_FULL, SGP_SWEEP_TARGETS, SGP_SWEEP_REUSED = 0, 1, 2
+SGP_SWEEP_FULL, SGP_SWEEP_TARGETS, SGP_SWEEP_REUSED, SGP_SWEEP_REWEIGHTED = 0, 1, 2, 3
 SGP_S_YY, SGP_S_W, SGP_S_N, SGP_S_COUNT = 0, 1, 2, 8
 (SGP_R_SUM_I1, SGP_R_SUM_I2, SGP_R_ENERGY, SGP_R_INFO_KUU, SGP_R_INFO_LAMBDA, SGP_R_INFO_PRIOR,
  SGP_R_LOGDET_KUU, SGP_R_LOGDET_LAMBDA, SGP_R_COUNT) = range(9)
@@ -37,6 +37,7 @@ EXPORTS = [
     "sgp_theta_objective_psi", "sgp_theta_descend_psi", "sgp_psi_in_grad", "sgp_psi_predict",
     "sgp_theta_objective_xu", "sgp_theta_objective_psi_xu", "sgp_inducing_descend", "sgp_inducing_descend_psi",
     "sgp_sweep_plan", "sgp_select_inducing", "sgp_predict_joint", "sgp_sample_f", "sgp_vmp_run",
+    "sgp_vmp_run_t",
 ]
 # sgp_sweep_plan's bits (SGP_PLAN_* of include/sgp_hip.h), by name
 PLAN_BITS = {"overlapped": 1, "pack": 2, "events": 4, "join_word": 8, "kuu_interleaved": 16, "stats_first": 32, "gate_side": 64,
@@ -62,7 +63,7 @@ SGP_PREDICT_NOISE = 1         # sgp_predict_var: add the observation noise W^-1
 SGP_JOINT_MAX_ROWS = 8192     # sgp_predict_joint / sgp_sample_f: ns * d_out
 SGP_DESCEND_THETA, SGP_DESCEND_XU = 1, 2      # sgp_inducing_descend[_psi]: what the optimised vector holds
 SGP_VMP_GAUSSIAN, SGP_VMP_PROBIT = 0, 1       # sgp_vmp_run: likelihood
-SGP_VMP_HOLD_W = 1                            # sgp_vmp_run: flags
+SGP_VMP_HOLD_W = 1                            # sgp_vmp_run, sgp_vmp_run_t: flags
 
 
 class SGPError(RuntimeError):
@@ -180,6 +181,7 @@ def load(build_if_missing: bool = True, variant=None):
     lib.sgp_select_inducing.argtypes = [vp, dp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int64), dp,
                                         C.POINTER(C.c_int32)]
     lib.sgp_vmp_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_int64)]
+    lib.sgp_vmp_run_t.argtypes = [vp, C.c_double, dp, C.c_int32, C.c_int32, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_get_step_trace.argtypes = [C.POINTER(C.c_int64)]
     lib.sgp_measure_clocks.argtypes = [C.c_int32, dp]
     lib.sgp_overlap_plan.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

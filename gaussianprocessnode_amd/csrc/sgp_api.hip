@@ -145,6 +145,10 @@ static int32_t plan_bits_of(const SweepPlan& p) {
 //                                               words, or reuse dropped; q(v) is the last completed sweep's.  A failed enqueue or wait drops reuse
 //                                               and q(v); a factorisation that failed on the device drops reuse when it was K_uu's and leaves
 //                                               q(v) to the status words (the getters refuse).  iterations = 0 changes nothing.
+//                                               The Student-t run (the _t export) does the same with the point weights moving: data_gen++
+//                                               per iteration, has_omega and omega_vmp_t (the weights are the run's, not a caller's), the
+//                                               resident weights, weighted targets and data scalars become those of the last sweep; its later
+//                                               sweeps re-form Psi2 and B from the resident K_uf (sweep_reweighted) and fill the record again.
 // A new entry point gets a row here and an entry in MUTATORS / READERS of tests/call_sequence_ref.py, which drives every row in front
 // of every reader (tests/test_gpu_call_sequences.py) and holds the ledger of the exported names (tests/test_call_sequences_host.py).
 struct StatsRecord {
@@ -167,6 +171,7 @@ struct sgp_handle {
     int64_t n = 0, n_max = 0;
     double n_nodes = 0;
     bool has_omega = false, has_yv = false, have_data = false, have_kernel = false, have_inducing = false;
+    bool omega_vmp_t = false;      // the resident point weights are those sgp_vmp_run_t left (alpha / beta_i), not a caller's pt_weight
     int prior_form = 2;            // 1 dense precision, 2 isotropic
     bool swept_local = false, swept = false;
     bool in_flight = false;        // a sweep may still be executing (its streams are non-blocking)
@@ -1090,6 +1095,7 @@ extern "C" int sgp_set_data(sgp_handle* h, const double* X, const double* y_mean
     h->n = n;
     h->n_nodes = scal[SGP_S_N];
     h->has_omega = pt_weight != nullptr;
+    h->omega_vmp_t = false;
     h->has_yv = y_var != nullptr;
     h->have_data = true;
     stats_exact_psi(h, false);
@@ -1379,14 +1385,31 @@ static void prep_main(sgp_handle* h, hipStream_t s, bool always, int* info_reset
 }
 static void force_prep_main(sgp_handle* h) { h->main_prep_gen = 0; }   // (phase stamps were opened that no closing kernel folds)
 
+// The plain order's statistics from the resident K_uf, one owner per launch (the full sweep and the objective's re-evaluation through
+// enqueue_local, the re-weighted sweep of sgp_vmp_run_t through enqueue_reweighted, sgp_time_kernel).
+// Psi2's slabs at the resident weights: ONE SYRK launch over all tile rows.  `sweep`: a sweep's launch -- stamped, and it opens the
+// K_uu chain's gate where that chain waits for it (`gated`); sgp_time_kernel's launches do neither
+static void launch_syrk_plain(sgp_handle* h, hipStream_t s, bool sweep, bool gated) {
+    long long* gate = sweep && gated && h->gate_side ? h->dJoin + WORD_GATE : nullptr;
+    launch_syrk(h->geom, s, h->dKuf, omega_of(h), h->dSlabs, h->Mp, h->n, sweep ? h->dStamps + STAMP_STRIDE * SGP_T_SYRK : (int64_t*)nullptr,
+                gate, h->gate_epoch);
+}
+// B's partials from the resident K_uf and the resident weighted targets, in k_gram_uf's partition and order
+static void launch_bpart_kuf(sgp_handle* h, hipStream_t s) {
+    hipLaunchKernelGGL(k_bpart_kuf, dim3(h->nblk, (h->Mp + BPK_ROWS - 1) / BPK_ROWS), dim3(64), 0, s, (const double*)h->dKuf,
+                       (const double*)h->dYw, h->dBpart, h->Mp, h->n, h->dout);
+}
+
 // `pack`: the statistics go to the exchange buffer (exchange_stats follows)
-static void enqueue_local(sgp_handle* h, hipStream_t s, bool pack) {
+static void enqueue_local(sgp_handle* h, hipStream_t s, bool pack, bool resident_kuf = false) {
     const int Mp = h->Mp, T = h->T;
-    prep_main(h, s, h->n <= 0);
+    prep_main(h, s, h->n <= 0 || resident_kuf, resident_kuf ? h->dInfo + 1 : nullptr);
     if (h->n > 0) {
-        launch_gram(h, s, true);
-        long long* gate = h->gate_side ? h->dJoin + WORD_GATE : nullptr;
-        launch_syrk(h->geom, s, h->dKuf, omega_of(h), h->dSlabs, Mp, h->n, h->dStamps + STAMP_STRIDE * SGP_T_SYRK, gate, h->gate_epoch);
+        // (resident_kuf: the inputs, Xu and the kernel are those K_uf was formed at and only the weights moved -- no Gram kernel, no
+        // K_uu chain to open a gate for; B's partials come from K_uf, bitwise the Gram kernel's)
+        if (resident_kuf) launch_bpart_kuf(h, s);
+        else launch_gram(h, s, true);
+        launch_syrk_plain(h, s, true, !resident_kuf);
     }
     SyrkGeom ga = h->geom;
     if (h->n <= 0) { ga = syrk_geometry(0, T, h->num_cus, 0); }       // no data: zero chunks, the statistics are zero
@@ -1779,9 +1802,7 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     prep_main(h, s, true, h->dInfo + 1);
     if (targets) {
         const int Mp = h->Mp, T = h->T;
-        if (h->n > 0)
-            hipLaunchKernelGGL(k_bpart_kuf, dim3(h->nblk, (Mp + BPK_ROWS - 1) / BPK_ROWS), dim3(64), 0, s, (const double*)h->dKuf,
-                               (const double*)h->dYw, h->dBpart, Mp, h->n, h->dout);
+        if (h->n > 0) launch_bpart_kuf(h, s);
         double* B = p.pack ? h->dPack + (size_t)h->ntiles * TB * TB : h->dStats + (size_t)Mp * Mp;
         hipLaunchKernelGGL(k_assemble_b, dim3(T * h->dout), dim3(256), 0, s, (const double*)h->dBpart, (const double*)h->dDataScal, B,
                            Mp, T, h->n > 0 ? h->nblk : 0, h->dout, SGP_S_COUNT + h->dout * h->dout,
@@ -1797,6 +1818,31 @@ static int sweep_resident(sgp_handle* h, void* stream, bool targets) {
     if (int crc = sweep_close(h, s, p, false)) return crc;
     stats_targets(h, false);
     h->last_kind = targets ? SGP_SWEEP_TARGETS : SGP_SWEEP_REUSED;
+    return 0;
+}
+
+// A re-weighted sweep (sgp_vmp_run_t from its second iteration on): the point weights, the weighted targets and the data scalars
+// moved on the device, X, Xu and the kernel did not.  Psi2 and B are formed again from the resident K_uf (enqueue_local, resident_kuf),
+// then phase 2; the K_uu chain's outputs stay.  Plain order on the library's own stream, as the full sweep in front of it in that call
+// (sweep_local_impl with whole = false): one SYRK launch, every tile column of Lambda formed at step 0 -- the sums of iteration k do
+// not depend on whether a call reached it as its first sweep or a later one.
+static int sweep_reweighted(sgp_handle* h) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    SweepPlan p = sweep_plan(h, nullptr, false);
+    p.resident = true;
+    hipStream_t s = p.stream;
+    if (int orc = order_behind(h, s)) return orc;
+    if (int brc = sweep_begin(h)) return brc;
+    h->plan = p;
+    h->plan_bits = plan_bits_of(p);
+    enqueue_local(h, s, false, true);
+    HIPCHK(h, hipGetLastError());
+    stats_formed(h);
+    enqueue_finish1(h, s, p);
+    HIPCHK(h, hipGetLastError());
+    if (int crc = sweep_close(h, s, p, false)) return crc;
+    stats_targets(h, false);
+    h->last_kind = SGP_SWEEP_REWEIGHTED;
     return 0;
 }
 
@@ -2176,7 +2222,7 @@ extern "C" int sgp_time_kernel(sgp_handle* h, int32_t which, int32_t iters, void
         else if (which == SGP_T_GRAM)
             launch_gram(h, s, false);
         else
-            launch_syrk(h->geom, s, h->dKuf, omega_of(h), h->dSlabs, h->Mp, h->n, (int64_t*)nullptr, (long long*)nullptr, 0LL);
+            launch_syrk_plain(h, s, false, false);
     };
     if (!G && qmode < 0 && which != SGP_T_GRAM && which != SGP_T_SYRK)
         return fail(h, SGP_ERR_ARG, "sgp_time_kernel: which must be SGP_T_GRAM, SGP_T_SYRK or SGP_TIME_GROUP0 + g");
@@ -2967,7 +3013,7 @@ extern "C" int sgp_sweep_local_psi(sgp_handle* h, const double* mean, const doub
     stats_drop(h, STATS_REUSE);
     h->have_data = false;
     h->swept = h->swept_local = false;
-    h->has_omega = h->has_yv = false;
+    h->has_omega = h->has_yv = h->omega_vmp_t = false;
     std::vector<double> yw, scal;
     form_targets(h, y_mean, y_var, nullptr, T, (double)T, yw, scal);
     HIPCHK(h, hipMemcpy(h->dDataScal, scal.data(), sizeof(double) * scal.size(), hipMemcpyHostToDevice));
@@ -3436,7 +3482,7 @@ extern "C" int sgp_train_step(sgp_handle* h, int64_t offset, int64_t n, int32_t 
     double *ownX = h->dX, *ownYw = h->dYw, *ownY = h->dY;
     h->dX = h->dTrainX + (size_t)offset * h->D;
     if (!h->train_probit) h->dYw = h->dY = h->dTrainY + offset;      // (classification: the window's q(f) goes to the handle's own buffers)
-    h->has_omega = false;
+    h->has_omega = h->omega_vmp_t = false;
     h->has_yv = h->train_probit;
     h->have_data = true;
     h->n_nodes = (double)n;
@@ -4047,27 +4093,104 @@ extern "C" int sgp_inducing_descend_psi(sgp_handle* h, const double* mean, const
 // ------------------------------------------------------------------------------------------------
 static bool finite_positive(double v) { return std::isfinite(v) && v > 0.0; }
 
-extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int32_t iterations, const double* gamma_prior,
-                           double* gamma, const double* mu_init, double tol, double* values, double* terms, int64_t* counts) {
-    const char* name = "sgp_vmp_run";
-    if (!h) return fail(h, SGP_ERR_ARG, "sgp_vmp_run: null handle");
-    if (likelihood != SGP_VMP_GAUSSIAN && likelihood != SGP_VMP_PROBIT) return refuse(h, name, "unknown likelihood");
+// What both runs hand to k_vmp_close; with a dense prior also log|Lambda0| and mu0 = Lambda0^-1 xi0, enqueued once per call: one
+// factorisation of a copy of Lambda0 with the step kernel, in the buffers sgp_set_prior(form 0) factors Sigma0 in (every sweep
+// rewrites dTmp, dWl and dSigma before it reads them).  dSt: [state | values | terms] of `it` iterations.
+static int vmp_close_args(sgp_handle* h, hipStream_t s, VmpClose* c, double* dSt, size_t it, double* dMu0, const double* dKl, int nkl,
+                          const double* dPp, int npp, bool hold, const double* gamma_prior, double tol) {
+    const int Q = h->Q, Qp = h->Qp, form = h->prior_form;
+    const double* ld0 = nullptr;
+    int nld0 = 0;
+    if (form != 2) {
+        HIPCHK(h, hipMemcpyAsync(h->dTmp, h->dLambda0, sizeof(double) * (size_t)Qp * Qp, hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemsetAsync(h->dInfo + 2, 0, sizeof(int), s));
+        launch_potrf(h->dTmp, Qp, h->TQ, h->dInfo + 2, Q, h->dScratch + 2 * POTRF_SCRATCH, s, h->dWl);
+        launch_ata(h->dWl, h->dSigma, Qp, h->TQ, s);
+        hipLaunchKernelGGL(k_symv, dim3((Qp + 3) / 4), dim3(256), 0, s, (const double*)h->dSigma, (const double*)h->dXi0, dMu0, Qp, Qp);
+        ld0 = h->dScratch + 2 * POTRF_SCRATCH + POTRF_LOGDET;
+        nld0 = h->TQ;
+    }
+    memset(c, 0, sizeof *c);
+    c->out = h->dOut; c->info = h->dInfo; c->stats_scal = stats_scalars(h); c->swept = h->dParams; c->src = h->dTrainParams;
+    c->ppart = dPp; c->npp = npp; c->klpart = dKl; c->nkl = nkl; c->ld0 = ld0; c->nld0 = nld0; c->data_scal = h->dDataScal;
+    c->st = dSt; c->values = dSt + VMP_STATE; c->terms = dSt + VMP_STATE + it;
+    c->a0 = hold ? 1.0 : gamma_prior[0]; c->b0 = hold ? 1.0 : gamma_prior[1]; c->tol = tol;
+    c->M = Q; c->hold = hold ? 1 : 0; c->form = form;
+    return 0;
+}
+
+// A run's results, after the wait: [state | values | terms] back in one copy, q(w) and the noise the last completed iteration left,
+// the record of the resident statistics, counts, and the status of a run that a factorisation stopped
+static int vmp_results(sgp_handle* h, const char* name, const double* dSt, size_t it, bool hold, double* gamma, double* values,
+                       double* terms, int64_t* counts) {
+    std::vector<double> back(VMP_STATE + 5 * it);
+    HIPCHK(h, hipMemcpy(back.data(), dSt, sizeof(double) * back.size(), hipMemcpyDeviceToHost));
+    const double* st = back.data();
+    if (values) memcpy(values, st + VMP_STATE, sizeof(double) * it);
+    if (terms) memcpy(terms, st + VMP_STATE + it, sizeof(double) * 4 * it);
+    const int done = (int)st[VMP_DONE], stop = (int)st[VMP_STOP];
+    if (done > 0) {
+        if (!hold) {
+            h->hParams->W[0] = st[VMP_A] / st[VMP_B];
+            h->hParams->E_logw = st[VMP_ELOGW];
+            gamma[0] = st[VMP_A]; gamma[1] = st[VMP_B];
+        }
+        stats_swept_at(h, st[VMP_W_SWEPT]);
+    }
+    if (h->cfg.flags & SGP_FLAG_REUSE_STATS) stats_checked(h, st[VMP_INFO_KUU] == 0.0 && st[VMP_INFO_SYNC] == 0.0);
+    if (counts) { counts[0] = done; counts[1] = stop == 1 ? 1 : 0; }
+    if (stop != 2) return 0;
+    const std::string at = std::string(name) + ", iteration " + std::to_string(done);
+    int frc = check_sync_status(h);
+    if (!frc) frc = factor_status(h, (int)st[VMP_INFO_PRIOR], (at + ": the prior precision").c_str());
+    if (!frc) frc = factor_status(h, (int)st[VMP_INFO_KUU], (at + ": K_uu").c_str(), (int)st[VMP_INFO_LAMBDA], (at + ": Lambda").c_str(), true);
+    if (counts && frc > 0) counts[1] = -frc;
+    return frc;
+}
+
+// the first iteration's sweep of either run: a full sweep; `whole`: as sgp_sweep plans it (sweep_plan), else in the plain order
+static int vmp_full_sweep(sgp_handle* h, bool whole) {
+    int rc = sweep_local_impl(h, nullptr, whole);
+    if (!rc) rc = sgp_sweep_finish(h, nullptr);
+    if (!rc) {
+        h->last_kind = SGP_SWEEP_FULL;
+        if (h->cfg.flags & SGP_FLAG_REUSE_STATS) stats_reusable(h);
+    }
+    return rc;
+}
+
+// the refusals sgp_vmp_run and sgp_vmp_run_t share: the call's own arguments, then what the handle must be
+static int vmp_check_args(sgp_handle* h, const char* name, int32_t flags, int32_t iterations, const double* gamma_prior,
+                          const double* gamma, double tol) {
     if (flags & ~SGP_VMP_HOLD_W) return refuse(h, name, "unknown flags");
     if (iterations < 0) return refuse(h, name, "iterations must be >= 0");
-    const bool hold = (flags & SGP_VMP_HOLD_W) != 0, probit = likelihood == SGP_VMP_PROBIT;
-    if (!hold) {
+    if (!(flags & SGP_VMP_HOLD_W)) {
         if (!gamma_prior || !gamma) return refuse(h, name, "gamma_prior and gamma are required without SGP_VMP_HOLD_W");
         if (!finite_positive(gamma_prior[0]) || !finite_positive(gamma_prior[1])) return refuse(h, name, "gamma_prior must be positive and finite");
         if (!finite_positive(gamma[0]) || !finite_positive(gamma[1])) return refuse(h, name, "gamma must be positive and finite");
     }
     if (!(tol >= 0.0)) return refuse(h, name, "tol must be >= 0");
-    for (int i = 0; mu_init && i < h->Q; ++i)
-        if (!std::isfinite(mu_init[i])) return refuse(h, name, "mu_init must be finite");
+    return 0;
+}
+static int vmp_check_handle(sgp_handle* h, const char* name) {
     if (h->dout != 1) return refuse(h, name, "UniSGP handles only (d_out = 1)");
     if (int prc = refuse_exact_psi(h, name)) return prc;
     if (h->training) return refuse(h, name, "a device-paced training run is open (sgp_train_end first)");
     if (!h->have_inducing || !h->have_kernel || !h->have_data || h->n < 1)
         return refuse(h, name, "set_inducing, set_kernel and set_data (at least one point) first");
+    return 0;
+}
+
+extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int32_t iterations, const double* gamma_prior,
+                           double* gamma, const double* mu_init, double tol, double* values, double* terms, int64_t* counts) {
+    const char* name = "sgp_vmp_run";
+    if (!h) return fail(h, SGP_ERR_ARG, "sgp_vmp_run: null handle");
+    if (likelihood != SGP_VMP_GAUSSIAN && likelihood != SGP_VMP_PROBIT) return refuse(h, name, "unknown likelihood");
+    if (int arc = vmp_check_args(h, name, flags, iterations, gamma_prior, gamma, tol)) return arc;
+    const bool hold = (flags & SGP_VMP_HOLD_W) != 0, probit = likelihood == SGP_VMP_PROBIT;
+    for (int i = 0; mu_init && i < h->Q; ++i)
+        if (!std::isfinite(mu_init[i])) return refuse(h, name, "mu_init must be finite");
+    if (int hrc = vmp_check_handle(h, name)) return hrc;
     if (h->has_yv || h->has_omega) return refuse(h, name, "the resident data must have been set without y_var and without pt_weight");
     if (h->allreduce) return refuse(h, name, "data-sharded runs are not supported (remove the hook)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -4094,7 +4217,7 @@ extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int
     if (probit) need += (size_t)Qp + 2 * (size_t)n + 2 * (size_t)npp;
     double* base = nullptr;
     if (int crc = call_scratch(h, need, &base)) return crc;
-    double *dSt = base, *dVals = dSt + VMP_STATE, *dTerms = dVals + it, *dMu0 = dTerms + 4 * it, *dKl = dMu0 + Qp;
+    double *dSt = base, *dMu0 = dSt + VMP_STATE + 5 * it, *dKl = dMu0 + Qp;
     double *dMuInit = dKl + 2 * nkl, *dMz = dMuInit + Qp, *dLab = dMz + n, *dPp = dLab + n;
     {
         std::vector<double> init(VMP_STATE + 5 * it + (size_t)Qp, std::numeric_limits<double>::quiet_NaN());
@@ -4116,26 +4239,9 @@ extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int
     h->params_src = h->dTrainParams;
     h->params_gen++;
     h->in_flight = true;
-    const double* ld0 = nullptr;
-    int nld0 = 0;
-    if (form != 2) {
-        // log|Lambda0| and mu0 = Lambda0^-1 xi0, once per call: one factorisation of a copy of Lambda0 with the step kernel, in the
-        // buffers sgp_set_prior(form 0) factors Sigma0 in (every sweep rewrites dTmp, dWl and dSigma before it reads them)
-        HIPCHK(h, hipMemcpyAsync(h->dTmp, h->dLambda0, sizeof(double) * (size_t)Qp * Qp, hipMemcpyDeviceToDevice, s));
-        HIPCHK(h, hipMemsetAsync(h->dInfo + 2, 0, sizeof(int), s));
-        launch_potrf(h->dTmp, Qp, h->TQ, h->dInfo + 2, Q, h->dScratch + 2 * POTRF_SCRATCH, s, h->dWl);
-        launch_ata(h->dWl, h->dSigma, Qp, h->TQ, s);
-        hipLaunchKernelGGL(k_symv, dim3((Qp + 3) / 4), dim3(256), 0, s, (const double*)h->dSigma, (const double*)h->dXi0, dMu0, Qp, Qp);
-        ld0 = h->dScratch + 2 * POTRF_SCRATCH + POTRF_LOGDET;
-        nld0 = h->TQ;
-    }
     VmpClose c;
-    memset(&c, 0, sizeof c);
-    c.out = h->dOut; c.info = h->dInfo; c.stats_scal = stats_scalars(h); c.swept = h->dParams; c.src = h->dTrainParams;
-    c.ppart = dPp; c.npp = npp; c.klpart = dKl; c.nkl = nkl; c.ld0 = ld0; c.nld0 = nld0; c.data_scal = h->dDataScal;
-    c.st = dSt; c.values = dVals; c.terms = dTerms;
-    c.a0 = hold ? 1.0 : gamma_prior[0]; c.b0 = hold ? 1.0 : gamma_prior[1]; c.tol = tol;
-    c.M = Q; c.hold = hold ? 1 : 0; c.probit = probit ? 1 : 0; c.form = form;
+    if (int prc = vmp_close_args(h, s, &c, dSt, it, dMu0, dKl, nkl, dPp, npp, hold, gamma_prior, tol)) return prc;
+    c.probit = probit ? 1 : 0;
     if (!hold) hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_INIT);
     int rc = 0;
     for (int k = 0; k < iterations && !rc; ++k) {
@@ -4150,16 +4256,7 @@ extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int
             h->has_yv = true;
             h->data_gen++;
         }
-        if (k == 0) {
-            rc = sweep_local_impl(h, nullptr, true);
-            if (!rc) rc = sgp_sweep_finish(h, nullptr);
-            if (!rc) {
-                h->last_kind = SGP_SWEEP_FULL;
-                if (h->cfg.flags & SGP_FLAG_REUSE_STATS) stats_reusable(h);
-            }
-        } else {
-            rc = sweep_resident(h, nullptr, probit);
-        }
+        rc = k == 0 ? vmp_full_sweep(h, true) : sweep_resident(h, nullptr, probit);
         if (rc) break;
         hipLaunchKernelGGL(k_vmp_kl, dim3(nkl), dim3(256), 0, s, (const double*)h->dLambda0, (const double*)h->dSigma,
                            (const double*)h->dMu, (const double*)dMu0, (const Params*)h->dParams, Q, Qp, form, dKl);
@@ -4171,29 +4268,113 @@ extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int
     h->params_gen++;
     if (rc) { stats_drop(h, STATS_REUSE | STATS_QV); return rc; }
 
-    std::vector<double> back(VMP_STATE + 5 * it);
-    HIPCHK(h, hipMemcpy(back.data(), dSt, sizeof(double) * back.size(), hipMemcpyDeviceToHost));
-    const double* st = back.data();
-    if (values) memcpy(values, st + VMP_STATE, sizeof(double) * it);
-    if (terms) memcpy(terms, st + VMP_STATE + it, sizeof(double) * 4 * it);
-    const int done = (int)st[VMP_DONE], stop = (int)st[VMP_STOP];
-    if (done > 0) {
-        if (!hold) {
-            h->hParams->W[0] = st[VMP_A] / st[VMP_B];
-            h->hParams->E_logw = st[VMP_ELOGW];
-            gamma[0] = st[VMP_A]; gamma[1] = st[VMP_B];
-        }
-        stats_swept_at(h, st[VMP_W_SWEPT]);
+    return vmp_results(h, name, dSt, it, hold, gamma, values, terms, counts);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Student-t regression, device-paced (include/sgp_hip.h: sgp_vmp_run_t; kernels: k_t_points and the T_* stages of k_vmp_close;
+// DESIGN.md 6n).  sgp_vmp_run's frame with the point weights omega_i = alpha / beta_i moving every iteration: per iteration the
+// weights and the data scalars (k_t_points, stage T_WEIGHTS), the sweep -- full first, re-weighted over the resident K_uf afterwards,
+// both in the plain order --, k_vmp_kl, the q(w) stage, k_quadform_fused at the new q(v), the rates (k_t_points) and the closing stage.
+// ------------------------------------------------------------------------------------------------
+// psi(x) in extended precision (the recurrence up to x >= 20, then the asymptotic series through x^-14): the call's constants are
+// differences of numbers of the size of lgamma(nu / 2), formed once on the host so that they carry none of its rounding
+static long double digamma_ext(long double x) {
+    long double r = 0.0L;
+    while (x < 20.0L) { r -= 1.0L / x; x += 1.0L; }
+    const long double i = 1.0L / x, i2 = i * i;
+    const long double s = i2 * (1.0L / 12 - i2 * (1.0L / 120 - i2 * (1.0L / 252 - i2 * (1.0L / 240 - i2 * (1.0L / 132 - i2 * (691.0L / 32760 - i2 / 12))))));
+    return r + logl(x) - 0.5L * i - s;
+}
+
+extern "C" int sgp_vmp_run_t(sgp_handle* h, double nu, double* tau_rate, int32_t flags, int32_t iterations, const double* gamma_prior,
+                             double* gamma, double tol, double* values, double* terms, int64_t* counts) {
+    const char* name = "sgp_vmp_run_t";
+    if (!h) return fail(h, SGP_ERR_ARG, "sgp_vmp_run_t: null handle");
+    if (int arc = vmp_check_args(h, name, flags, iterations, gamma_prior, gamma, tol)) return arc;
+    const bool hold = (flags & SGP_VMP_HOLD_W) != 0;
+    if (!finite_positive(nu)) return refuse(h, name, "nu must be positive and finite");
+    if (int hrc = vmp_check_handle(h, name)) return hrc;
+    if (!(h->cfg.flags & SGP_FLAG_KEEP_KUF))
+        return refuse(h, name, "create the handle with SGP_FLAG_KEEP_KUF (the per-point partial buffers of the rates exist only with it)");
+    if (h->has_yv) return refuse(h, name, "the resident data must have been set without y_var");
+    if (h->has_omega && !h->omega_vmp_t)
+        return refuse(h, name, "the resident data carry the caller's pt_weight, which the run would overwrite (sgp_set_data without them)");
+    if (h->allreduce) return refuse(h, name, "data-sharded runs are not supported (remove the hook)");
+    const int64_t n = h->n;
+    for (int64_t i = 0; tau_rate && i < n; ++i)
+        if (!finite_positive(tau_rate[i])) return refuse(h, name, "tau_rate must be positive and finite");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (counts) counts[0] = counts[1] = 0;
+    if (iterations == 0) return 0;
+    if (int wrc = sync_checked(h)) return wrc;
+    if (int drc = descent_device_state(h)) return drc;
+
+    // call scratch: [state | values | terms | mu0 | rates | k_vmp_kl's pairs | k_t_points' triples]; the first five go up in one copy
+    const int Q = h->Q, Qp = h->Qp, form = h->prior_form;
+    const int nkl = form == 2 ? (Q + 255) / 256 : std::min(Q, 256);
+    const int npp = (int)((n + PROBIT_RANGE - 1) / PROBIT_RANGE);
+    const size_t it = (size_t)iterations;
+    const double alpha = 0.5 * (nu + 1.0), half_nu = 0.5 * nu;
+    double* base = nullptr;
+    if (int crc = call_scratch(h, VMP_STATE + 5 * it + (size_t)Qp + (size_t)n + 2 * (size_t)nkl + T_PART * (size_t)npp, &base)) return crc;
+    double *dSt = base, *dMu0 = dSt + VMP_STATE + 5 * it, *dBeta = dMu0 + Qp, *dKl = dBeta + n, *dPp = dKl + 2 * nkl;
+    {
+        std::vector<double> init(VMP_STATE + 5 * it + (size_t)Qp + (size_t)n, std::numeric_limits<double>::quiet_NaN());
+        for (int i = 0; i < VMP_STATE; ++i) init[i] = 0.0;
+        for (int i = 0; i < Qp; ++i) init[VMP_STATE + 5 * it + i] = 0.0;
+        double* beta0 = init.data() + VMP_STATE + 5 * it + Qp;
+        for (int64_t i = 0; i < n; ++i) beta0[i] = tau_rate ? tau_rate[i] : alpha;
+        if (!hold) { init[VMP_A] = gamma[0]; init[VMP_B] = gamma[1]; }
+        init[VMP_ELOGW] = h->hParams->E_logw;
+        HIPCHK(h, hipMemcpy(dSt, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
     }
-    if (h->cfg.flags & SGP_FLAG_REUSE_STATS) stats_checked(h, st[VMP_INFO_KUU] == 0.0 && st[VMP_INFO_SYNC] == 0.0);
-    if (counts) { counts[0] = done; counts[1] = stop == 1 ? 1 : 0; }
-    if (stop != 2) return 0;
-    const std::string at = std::string(name) + ", iteration " + std::to_string(done);
-    int frc = check_sync_status(h);
-    if (!frc) frc = factor_status(h, (int)st[VMP_INFO_PRIOR], (at + ": the prior precision").c_str());
-    if (!frc) frc = factor_status(h, (int)st[VMP_INFO_KUU], (at + ": K_uu").c_str(), (int)st[VMP_INFO_LAMBDA], (at + ": Lambda").c_str(), true);
-    if (counts && frc > 0) counts[1] = -frc;
-    return frc;
+    HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
+
+    hipStream_t s = h->own;
+    h->params_src = h->dTrainParams;
+    h->params_gen++;
+    h->in_flight = true;
+    VmpClose c;
+    if (int prc = vmp_close_args(h, s, &c, dSt, it, dMu0, dKl, nkl, dPp, npp, hold, gamma_prior, tol)) return prc;
+    {
+        const long double psi = digamma_ext((long double)alpha);
+        c.t_points = (double)n;
+        c.t_psi = (double)psi;
+        c.t_kl0 = (double)(0.5L * psi - lgammal((long double)alpha) + lgammal((long double)half_nu));
+    }
+    if (!hold) hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_INIT);
+    // from here on the resident data are weighted, by weights that are this call's
+    h->has_omega = h->omega_vmp_t = true;
+    auto points = [&](int mode) {
+        hipLaunchKernelGGL(k_t_points, dim3(npp), dim3(256), 0, s, mode, (const double*)h->dPa, (const double*)h->dPb,
+                           (const double*)h->dKmu, (const double*)h->dY, h->T, n, (const Params*)h->dParams, (const double*)dSt, alpha,
+                           half_nu, dBeta, h->dOmega, h->dYw, dPp);
+    };
+    int rc = 0;
+    for (int k = 0; k < iterations && !rc; ++k) {
+        points(T_MODE_WEIGHTS);
+        hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_T_WEIGHTS);
+        h->data_gen++;
+        rc = k == 0 ? vmp_full_sweep(h, false) : sweep_reweighted(h);
+        if (rc) break;
+        hipLaunchKernelGGL(k_vmp_kl, dim3(nkl), dim3(256), 0, s, (const double*)h->dLambda0, (const double*)h->dSigma,
+                           (const double*)h->dMu, (const double*)dMu0, (const Params*)h->dParams, Q, Qp, form, dKl);
+        c.k = k;
+        hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_T_QW);
+        launch_quadform(h, s);
+        points(T_MODE_POINTS);
+        hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_T_CLOSE);
+    }
+    rc = descent_wait(h, s, rc);
+    h->params_src = h->hParams;
+    h->params_gen++;
+    if (rc) { stats_drop(h, STATS_REUSE | STATS_QV); return rc; }
+
+    // (the host's record of sum omega y^2, which sgp_set_output_cov_sum adds to, follows the device's)
+    HIPCHK(h, hipMemcpy(h->ryy_data, h->dDataScal + SGP_S_YY, sizeof(double), hipMemcpyDeviceToHost));
+    if (tau_rate) HIPCHK(h, hipMemcpy(tau_rate, dBeta, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    return vmp_results(h, name, dSt, it, hold, gamma, values, terms, counts);
 }
 
 // ------------------------------------------------------------------------------------------------

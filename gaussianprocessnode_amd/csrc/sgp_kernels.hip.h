@@ -3188,18 +3188,25 @@ __global__ void __launch_bounds__(256, 2) k_quadform_fused(const double* __restr
 }
 
 // I1_n = sigma2 - sum_r pa[r][n] ;  I2_n = y^2 + v - 2 y (k_n . mu) + sum_r pb[r][n]      (fixed summation order)
+// point n's pair from k_quadform_fused's partial rows, shared by k_w_point_finish and k_t_points
+__device__ __forceinline__ void w_point(const double* __restrict__ pa, const double* __restrict__ pb, const double* __restrict__ kmu,
+                                        double yy, double v, double sigma2, int T, int64_t N, int64_t n, double& i1, double& i2) {
+    double a = 0.0, b = 0.0;
+    for (int r = 0; r < 2 * T; ++r) { a += pa[(size_t)r * N + n]; b += pb[(size_t)r * N + n]; }
+    const double km = (kmu[n] + kmu[(size_t)N + n]) + (kmu[(size_t)2 * N + n] + kmu[(size_t)3 * N + n]);
+    i1 = sigma2 - a;
+    i2 = yy * yy + v - 2.0 * yy * km + b;
+}
 __global__ void __launch_bounds__(256) k_w_point_finish(const double* __restrict__ pa, const double* __restrict__ pb,
                                                         const double* __restrict__ kmu, const double* __restrict__ y,
                                                         const double* __restrict__ yv, double* __restrict__ I1,
                                                         double* __restrict__ I2, const Params* __restrict__ P, int T, int64_t N) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
-    double a = 0.0, b = 0.0;
-    for (int r = 0; r < 2 * T; ++r) { a += pa[(size_t)r * N + n]; b += pb[(size_t)r * N + n]; }
-    const double km = (kmu[n] + kmu[(size_t)N + n]) + (kmu[(size_t)2 * N + n] + kmu[(size_t)3 * N + n]);
-    const double yy = y[n], v = yv ? yv[n] : 0.0;
-    I1[n] = P->sigma2 - a;
-    I2[n] = yy * yy + v - 2.0 * yy * km + b;
+    double i1, i2;
+    w_point(pa, pb, kmu, y[n], yv ? yv[n] : 0.0, P->sigma2, T, N, n, i1, i2);
+    I1[n] = i1;
+    I2[n] = i2;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4428,8 +4435,12 @@ enum { VMP_A = 0, VMP_B = 1,          // q(w) = Gamma(a, b) after the last compl
        VMP_W_SWEPT = 9,               // mean(q_w) the last completed iteration's sweep ran at
        VMP_ELOGW = 10,                // E[log w] of q(w) = Gamma(a, b)
        VMP_LIK = 11,                  // Probit: the factors' share, left by the reduce stage for the closing stage
-       VMP_STATE = 16 };
-enum { VMP_STAGE_REDUCE = 0, VMP_STAGE_CLOSE = 1, VMP_STAGE_INIT = 2 };
+       // Student-t (sgp_vmp_run_t): what the q(w) stage of iteration k leaves for k_t_points and the closing stage -- the NEW q(w),
+       // its mean and E[log w], and the two KL terms; committed to the slots above by the closing stage
+       VMP_T_A = 12, VMP_T_B = 13, VMP_T_W = 14, VMP_T_ELOGW = 15, VMP_T_KLV = 16, VMP_T_KLW = 17,
+       VMP_STATE = 24 };
+enum { VMP_STAGE_REDUCE = 0, VMP_STAGE_CLOSE = 1, VMP_STAGE_INIT = 2,
+       VMP_STAGE_T_WEIGHTS = 3, VMP_STAGE_T_QW = 4, VMP_STAGE_T_CLOSE = 5 };      // Student-t: see k_t_points
 constexpr int PROBIT_RANGE = 256;     // points per workgroup of k_probit_points: fixed, so that the ranges depend on N alone
 
 // digamma: the recurrence psi(x) = psi(x + 1) - 1 / x up to x >= 10, then the asymptotic series through x^-14 (the first term left
@@ -4507,6 +4518,52 @@ __global__ void __launch_bounds__(256) k_vmp_kl(const double* __restrict__ L0, c
     if (tid == 0) { part[2 * blockIdx.x] = tr; part[2 * blockIdx.x + 1] = qd; }
 }
 
+// Student-t regression (sgp_vmp_run_t): `y_i ~ N(f_i, 1 / (w tau_i)), tau_i ~ Gamma(nu / 2, nu / 2)` with
+// q(tau_i) = Gamma(alpha, beta_i), alpha = (nu + 1) / 2.  One point per thread, workgroup b owns the points [256 b, 256 b + 256) and
+// leaves T_PART sums in a fixed order, as k_probit_points does.  Two modes:
+//   T_MODE_WEIGHTS (in front of iteration k's sweep): the sweep's point weights from the rates that enter k, omega_i = alpha / beta_i
+//     -> omega, omega_i y_i -> yw; sums { omega, omega y^2, 0 } (the data scalars S_W and S_YY: stage T_WEIGHTS).
+//   T_MODE_POINTS (behind k_quadform_fused at the new q(v), and behind the q(w) stage): r_i = I1_i + I2_i (w_point),
+//     beta_i <- nu / 2 + w r_i / 2 at the NEW mean(q_w) = st[VMP_T_W]; sums { (alpha / beta_i) r_i, log beta_i, kl_i } with
+//     kl_i = (nu / 2) log(beta_i / (nu / 2)) + alpha (nu / 2 - beta_i) / beta_i, the part of KL(Gamma(alpha, beta_i) || Gamma(nu / 2,
+//     nu / 2)) that depends on the point -- the logarithm through log1p(w r_i / nu): at a large nu the two halves cancel to
+//     O((w r)^2 / nu), and log(beta) - log(nu / 2) would leave nu / 2 roundings of a logarithm of ~17 in it.
+// The weights are written in front of the sweep that reads them and not by the pass that forms the rates: a run that stops by tol at
+// iteration k has formed the rates of k + 1 already, and the sweeps still enqueued must find the weights of sweep k.
+enum { T_MODE_WEIGHTS = 0, T_MODE_POINTS = 1, T_PART = 3 };
+__global__ void __launch_bounds__(256) k_t_points(int mode, const double* __restrict__ pa, const double* __restrict__ pb,
+                                                  const double* __restrict__ kmu, const double* __restrict__ y, int T, int64_t n,
+                                                  const Params* __restrict__ P, const double* __restrict__ st, double alpha,
+                                                  double half_nu, double* __restrict__ beta, double* __restrict__ omega,
+                                                  double* __restrict__ yw, double* __restrict__ part) {
+    __shared__ double red[4];
+    if (st[VMP_STOP] != 0.0) return;                            // (uniform)
+    const int64_t i = (int64_t)blockIdx.x * PROBIT_RANGE + threadIdx.x;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    if (i < n) {
+        const double yy = y[i];
+        if (mode == T_MODE_WEIGHTS) {
+            const double om = alpha / beta[i], oy = om * yy;
+            omega[i] = om;
+            yw[i] = oy;
+            s0 = om;
+            s1 = oy * yy;
+        } else {
+            double i1, i2;
+            w_point(pa, pb, kmu, yy, 0.0, P->sigma2, T, n, i, i1, i2);
+            const double r = i1 + i2, hw = 0.5 * (st[VMP_T_W] * r), be = half_nu + hw;
+            beta[i] = be;
+            s0 = (alpha / be) * r;
+            s1 = log(be);
+            s2 = half_nu * log1p(hw / half_nu) - alpha * (hw / be);
+        }
+    }
+    s0 = block_sum(s0, red);
+    s1 = block_sum(s1, red);
+    s2 = block_sum(s2, red);
+    if (threadIdx.x == 0) { part[T_PART * blockIdx.x] = s0; part[T_PART * blockIdx.x + 1] = s1; part[T_PART * blockIdx.x + 2] = s2; }
+}
+
 struct VmpClose {
     const double* out;          // the sweep's scalars (k_scalars)
     const int* info;            // the status words: K_uu, Lambda, prior, stream hand-off
@@ -4521,6 +4578,10 @@ struct VmpClose {
     double* values; double* terms;
     double a0, b0, tol;
     int k, M, hold, probit, form;
+    // Student-t (stages T_*): k_t_points' triples (ppart, npp), the number of points, and the constants of the call, formed once on
+    // the host in extended precision: psi(alpha), and kl0 = psi(alpha) / 2 - lgamma(alpha) + lgamma(nu / 2), the part of every
+    // point's KL that depends on nu alone
+    double t_points, t_psi, t_kl0;
 };
 
 // One workgroup, three roles.  INIT: the noise of iteration 0 from q(w) = Gamma(a, b).  REDUCE (Probit, in front of the sweep): the
@@ -4528,6 +4589,11 @@ struct VmpClose {
 // the factors' share into the state.  CLOSE (behind the sweep, iteration k): the status words; the Gamma step from the sweep's sums;
 // the four terms and their sum at (q(f), q(v), the NEW q(w)); the stop rule; the noise of the next iteration, unless the run stops.
 // It writes nothing the sweep's own kernels write -- the scalars' pinned mirror in particular stays k_scalars' alone.
+// Student-t (sgp_vmp_run_t) closes an iteration in two stages with k_t_points between them, because the rates need the NEW mean(q_w)
+// and the free energy the new rates.  T_WEIGHTS (in front of the sweep): k_t_points' sums of omega and omega y^2 into the data scalars.
+// T_QW (behind the sweep): CLOSE up to the Gamma step and the two KL terms, left in the VMP_T_* slots -- nothing is committed.
+// T_CLOSE (behind k_t_points): term 0 from sum_i (alpha / beta_i) r_i at the new rates, lik = sum_i [KL(q(tau_i) || p(tau_i)) - 1/2
+// (psi(alpha) - log beta_i)], the sum, the stop rule, and the commit.
 __global__ void __launch_bounds__(256) k_vmp_close(VmpClose c, int stage) {
     __shared__ double red[4];
     double* st = c.st;
@@ -4552,6 +4618,34 @@ __global__ void __launch_bounds__(256) k_vmp_close(VmpClose c, int stage) {
             c.data_scal[SGP_S_COUNT] = syy;                    // Ryy[0] of d_out = 1, behind the scalar slots
             st[VMP_LIK] = lik;
         }
+        return;
+    }
+    if (stage == VMP_STAGE_T_WEIGHTS || stage == VMP_STAGE_T_CLOSE) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int b = tid; b < c.npp; b += 256) { s0 += c.ppart[T_PART * b]; s1 += c.ppart[T_PART * b + 1]; s2 += c.ppart[T_PART * b + 2]; }
+        s0 = block_sum(s0, red);
+        s1 = block_sum(s1, red);
+        s2 = block_sum(s2, red);
+        if (tid != 0) return;
+        if (stage == VMP_STAGE_T_WEIGHTS) {
+            c.data_scal[SGP_S_W] = s0;
+            c.data_scal[SGP_S_YY] = s1;
+            c.data_scal[SGP_S_COUNT] = s1;                     // Ryy[0] of d_out = 1, behind the scalar slots
+            return;
+        }
+        const double LOG2PI = 1.8378770664093454835606594728112;
+        const double n = c.stats_scal[SGP_S_N], wbar = st[VMP_T_W], elog = st[VMP_T_ELOGW];
+        const double t0 = 0.5 * (wbar * s0 - n * elog + n * LOG2PI);
+        const double t1 = (c.t_points * c.t_kl0 + s2) - 0.5 * (c.t_points * c.t_psi - s1);
+        const double t2 = st[VMP_T_KLV], t3 = st[VMP_T_KLW];
+        const double F = ((t0 + t1) + t2) + t3;
+        c.terms[4 * c.k] = t0; c.terms[4 * c.k + 1] = t1; c.terms[4 * c.k + 2] = t2; c.terms[4 * c.k + 3] = t3;
+        c.values[c.k] = F;
+        const bool conv = c.k >= 1 && c.tol > 0.0 && fabs(F - st[VMP_FPREV]) <= c.tol * fabs(F);
+        st[VMP_A] = st[VMP_T_A]; st[VMP_B] = st[VMP_T_B]; st[VMP_FPREV] = F; st[VMP_DONE] = (double)(c.k + 1);
+        st[VMP_W_SWEPT] = c.swept->W[0]; st[VMP_ELOGW] = elog;
+        if (conv) { st[VMP_STOP] = 1.0; return; }
+        if (!c.hold) { c.src->W[0] = wbar; c.src->E_logw = elog; }
         return;
     }
     double tr = 0.0, qd = 0.0, ld = 0.0;
@@ -4581,6 +4675,12 @@ __global__ void __launch_bounds__(256) k_vmp_close(VmpClose c, int stage) {
         t3 = (a - c.a0) * psi - lgamma(a) + lgamma(c.a0) + c.a0 * (log(b) - log(c.b0)) + a * (c.b0 - b) / b;
     }
     const double ld0 = c.form == 2 ? (double)c.M * log(c.swept->prior_iso) : ld;
+    if (stage == VMP_STAGE_T_QW) {
+        st[VMP_T_A] = a; st[VMP_T_B] = b; st[VMP_T_W] = wbar; st[VMP_T_ELOGW] = elog;
+        st[VMP_T_KLV] = 0.5 * (tr + qd - (double)c.M - ld0 + c.out[SGP_R_LOGDET_LAMBDA]);
+        st[VMP_T_KLW] = t3;
+        return;
+    }
     const double t0 = 0.5 * (wbar * S - n * elog + n * LOG2PI);
     const double t1 = c.probit ? st[VMP_LIK] : 0.0;
     const double t2 = 0.5 * (tr + qd - (double)c.M - ld0 + c.out[SGP_R_LOGDET_LAMBDA]);

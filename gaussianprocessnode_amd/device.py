@@ -573,6 +573,37 @@ class SGPDevice:
         self._check(rc, "sgp_vmp_run")
         return values, terms, g, int(counts[0]), bool(counts[1] == 1)
 
+    def vmp_run_t(self, iterations: int, nu: float, *, tau_rate=None, gamma_prior=None, gamma=None, tol: float = 0.0,
+                  hold_w: bool = False):
+        """`iterations` VMP iterations of Student-t regression over the resident data, paced by the device (sgp_vmp_run_t):
+        `y_i ~ N(f_i, 1 / (w tau_i)), tau_i ~ Gamma(nu / 2, nu / 2)` with q(tau_i) = Gamma((nu + 1) / 2, beta_i).  Needs keep_kuf.
+        tau_rate: the rates beta_i entering the run (None: (nu + 1) / 2, i.e. unit weights); gamma_prior, gamma, tol and hold_w as
+        in `vmp_run`.  Returns (values, terms, gamma, tau_rate, iterations_done, converged): terms (iterations, 4) = [node energy
+        at the new weights, sum_i KL(q(tau_i) || p(tau_i)) - E[log tau_i] / 2, KL(q(v)), KL(q(w))], tau_rate the final rates (a
+        copy; those given are not changed).  Failures raise as in `vmp_run`; the exception also carries `tau_rate`."""
+        K = int(iterations)
+        g0 = g = None
+        if not hold_w:
+            if gamma_prior is None:
+                raise ValueError("vmp_run_t: gamma_prior = (shape0, rate0) is required without hold_w")
+            g0 = as_f64(gamma_prior, (2,))
+            g = as_f64(g0 if gamma is None else gamma, (2,)).copy()
+        beta = (np.full(self.n, 0.5 * (float(nu) + 1.0)) if tau_rate is None else as_f64(tau_rate, (self.n,)).copy())
+        values = np.full(max(K, 0), np.nan)
+        terms = np.full((max(K, 0), 4), np.nan)
+        counts = (C.c_int64 * 2)()
+        rc = self._lib.sgp_vmp_run_t(self._h, float(nu), ptr(beta), _lib.SGP_VMP_HOLD_W if hold_w else 0, K, ptr(g0), ptr(g),
+                                     float(tol), ptr(values), ptr(terms), counts)
+        if rc > 0:
+            msg = self._lib.sgp_last_error(self._h)
+            err = np.linalg.LinAlgError(f"sgp_vmp_run_t: {msg.decode() if msg else ''} (leading minor {rc})")
+            err.minor, err.values, err.terms, err.gamma, err.iterations_done = rc, values, terms, g, int(counts[0])
+            err.tau_rate = beta
+            err.counts = (int(counts[0]), int(counts[1]))       # counts[1] = -minor
+            raise err
+        self._check(rc, "sgp_vmp_run_t")
+        return values, terms, g, beta, int(counts[0]), bool(counts[1] == 1)
+
     def theta_objective_psi(self, mean, cov, y_mean, want_grad: bool = False):
         """The hyper-parameter objective over the exact Psi-statistics of T Gaussian inputs N(mean[t], cov[t]) at the current kernel
         (sgp_theta_objective_psi; SE only): `theta_objective` with the cubature sums replaced by exact expectations.  mean (T, D),

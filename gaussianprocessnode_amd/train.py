@@ -6,6 +6,7 @@ minibatch's posterior as prior (:205-212), then one optimiser step on the kernel
 (:213-222, `grad_llh_new!` + `Flux.Optimise.update!`).  Host logic only -- the numbers come from the engine (C ABI)."""
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -183,13 +184,51 @@ def _vmp_device(engine, likelihood, iterations, shape, rate, free_energy):
     return out + (values,) if free_energy else out
 
 
+def _vmp_regression_t(engine, xtrain, ytrain, nu, iterations, prior_var, shape, rate, device_paced, free_energy):
+    """vmp_regression's loop for the Student-t likelihood `y_i ~ N(f_i, 1 / (w tau_i)), tau_i ~ Gamma(nu / 2, nu / 2)` with
+    q(tau_i) = Gamma((nu + 1) / 2, beta_i) (include/sgp_hip.h, sgp_vmp_run_t).  Device-paced: one sgp_vmp_run_t.  Host-paced, per
+    iteration and from existing calls alone: the data again with the point weights omega_i = alpha / beta_i, one sweep for q(v), q(w)
+    from its sums, r_i = I1_i + I2_i from w_stats, and beta_i = nu / 2 + mean(q_w) r_i / 2."""
+    from scipy.special import digamma, gammaln
+    N, alpha, hn = len(ytrain), 0.5 * (nu + 1.0), 0.5 * nu
+    if device_paced:
+        values, _, gamma, beta, _, _ = engine.vmp_run_t(iterations, nu, gamma_prior=(shape, rate))
+        a, b = float(gamma[0]), float(gamma[1])
+        trace = values
+    else:
+        a, b, beta, trace = float(shape), float(rate), np.full(N, alpha), []
+        for _ in range(iterations):
+            engine.set_data(xtrain, ytrain, weights=alpha / beta)
+            engine.set_noise([[a / b]])
+            engine.sweep()
+            sc = engine.scalars()
+            a, b = shape + 0.5 * N, rate + 0.5 * (sc.sum_I1 + sc.sum_I2)
+            I1, I2 = engine.w_stats()
+            r = I1 + I2
+            beta = hn + 0.5 * (a / b) * r
+            if free_energy:
+                S = np.sum(alpha / beta * r)
+                kl = ((alpha - hn) * digamma(alpha) - gammaln(alpha) + gammaln(hn) + hn * (np.log(beta) - np.log(hn))
+                      + alpha * (hn - beta) / beta)
+                lik = np.sum(kl - 0.5 * (digamma(alpha) - np.log(beta)))
+                # (the node energy at the NEW weights: their sum stands where the sweep's own sums do for the Gaussian likelihood)
+                trace.append(_host_free_energy(engine, dataclasses.replace(sc, sum_I1=S, sum_I2=0.0), prior_var, shape, rate, a, b,
+                                               N, lik))
+        trace = np.array(trace)
+    mu, Sigma, _ = engine.posterior(want_uv=False)
+    out = (MvNormalMeanCovariance(mu, Sigma), (a, b), beta)
+    return out + (trace,) if free_energy else out
+
+
 def vmp_regression(p, xtrain, ytrain, Xu, engine, *, iterations=7, prior_var=50.0, shape=1e-2, rate=1e-2, jitter=1e-8,
-                   family="se", device_paced=False, free_energy=False):
+                   family="se", device_paced=False, free_energy=False, student_t=None):
     """The inner `infer(...)` of experiments/GPT_regression.ipynb's `my_free_energy` (cell 9; model cell 6:
     `v ~ MvNormal(0, 50 I); w ~ Gamma(1e-2, 1e-2); y[i] ~ UniSGP(x[i], v, w, theta)`, mean field q(v) q(w), q(w) initialised
     at its prior, 7 iterations) at the kernel parameters p = (sigma2, lengthscale...) -- BASELINE config 1.  Per iteration:
     one sweep for q(v) at mean(q_w), then q(w) = Gamma(shape + N/2, rate + (sum I1 + sum I2)/2) from that q(v)
-    (GPnode/UniSGPnode.jl:56-73,196-238).  Returns (q_v, (shape, rate))."""
+    (GPnode/UniSGPnode.jl:56-73,196-238).  Returns (q_v, (shape, rate)).
+    student_t = nu replaces the Gaussian likelihood by Student-t with nu degrees of freedom, as a Gamma scale mixture with one
+    q(tau_i) per point (robust to displaced targets; the engine needs keep_kuf).  Returns (q_v, (shape, rate), tau_rate)."""
     xtrain = np.asarray(xtrain, dtype=np.float64).reshape(len(ytrain), -1)
     Xu = np.asarray(Xu, dtype=np.float64).reshape(-1, xtrain.shape[1])
     p = np.asarray(p, dtype=np.float64)
@@ -198,6 +237,9 @@ def vmp_regression(p, xtrain, ytrain, Xu, engine, *, iterations=7, prior_var=50.
     set_engine_kernel(engine, float(p[0]), p[1:], jitter, family)
     engine.set_prior_isotropic(prior_var)
     engine.set_data(xtrain, np.asarray(ytrain, dtype=np.float64))
+    if student_t is not None:
+        return _vmp_regression_t(engine, xtrain, np.asarray(ytrain, dtype=np.float64), float(student_t), iterations, prior_var,
+                                 float(shape), float(rate), device_paced, free_energy)
     if device_paced:                                   # the loop below as one sgp_vmp_run: the host waits once
         return _vmp_device(engine, "gaussian", iterations, shape, rate, free_energy)
     trace = []

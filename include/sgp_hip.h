@@ -164,7 +164,9 @@ int sgp_sweep(sgp_handle* h, void* stream);                 /* local + [all-redu
  * meaning (a full local phase, phase 2).
  * sgp_sweep_kind: next = what the next sgp_sweep will do (it may wait, once, for the last full sweep to finish and checks its
  * status), last = what the last completed sgp_sweep did.  Either pointer may be NULL. */
-enum { SGP_SWEEP_FULL = 0, SGP_SWEEP_TARGETS = 1, SGP_SWEEP_REUSED = 2 };
+/* SGP_SWEEP_REWEIGHTED is only ever a `last`: the sweeps of sgp_vmp_run_t behind its first, which form Psi2 and B again from the
+ * resident K_uf at point weights that moved on the device, then phase 2.  sgp_sweep never does one. */
+enum { SGP_SWEEP_FULL = 0, SGP_SWEEP_TARGETS = 1, SGP_SWEEP_REUSED = 2, SGP_SWEEP_REWEIGHTED = 3 };
 int sgp_sweep_kind(const sgp_handle* h, int32_t* next, int32_t* last);
 
 /* ---- multi-GPU: the one exchange step of a sweep --------------------------------------------
@@ -677,6 +679,36 @@ int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int32_t iterat
                 const double* gamma_prior /* 2: shape0, rate0 */, double* gamma /* 2, in/out: q(w) shape, rate */,
                 const double* mu_init /* M, may be NULL = 0 */, double tol, double* values /* iterations, may be NULL */,
                 double* terms /* 4 x iterations column-major, may be NULL */, int64_t* counts /* 2, may be NULL */);
+
+/* ---- device-paced VMP iterations of Student-t (robust) regression ----
+ * sgp_vmp_run for `y_i ~ N(f_i, 1 / (w tau_i)), tau_i ~ Gamma(nu / 2, nu / 2), f_i ~ UniSGP(x_i, v, ., theta)` with the mean-field
+ * q(v) q(w) prod_i q(tau_i), q(tau_i) = Gamma(alpha, beta_i), alpha = (nu + 1) / 2: the Gaussian likelihood's scale mixture, under
+ * which one displaced target lowers its own weight instead of raising everybody's noise.  The handle needs SGP_FLAG_KEEP_KUF.  With the
+ * rates beta_i and (a, b) = q(w) entering iteration k (SGP_VMP_HOLD_W as in sgp_vmp_run):
+ *   1. q(v): a sweep over the resident data at the point weights omega_i = alpha / beta_i -- iteration 0 a full sweep, later ones
+ *      re-weighted: omega, omega .* y and the data scalars (S_YY = sum omega y^2, S_W = sum omega; S_N stays sgp_set_data's) are
+ *      rewritten on the device, Psi2 and B formed again from the resident K_uf, then phase 2; K_uf and the K_uu chain are formed once
+ *      per call.  Every sweep of the call runs in the plain order (one SYRK launch, no statistics groups);
+ *   2. q(w) <- Gamma(shape0 + N / 2, rate0 + (sum I1 + sum I2) / 2) from that sweep's (omega-weighted) sums, as in sgp_vmp_run;
+ *   3. q(tau): with r_i = I1_i + I2_i of sgp_w_stats at the new q(v) and the NEW w = a / b:  beta_i <- nu / 2 + w r_i / 2;
+ *   4. terms[4 k ..] = { 1/2 [w sum_i (alpha / beta_i) r_i - N E[log w] + N log 2 pi] at the new rates;
+ *      lik = sum_i [KL(Gamma(alpha, beta_i) || Gamma(nu / 2, nu / 2)) - 1/2 (psi(alpha) - log beta_i)], the Gamma KL as below;
+ *      KL(q(v) || p(v)); KL(q(w) || p(w)), both as in sgp_vmp_run }, values[k] = their sum in that order;
+ *   5. the tol stop and the failure stop of sgp_vmp_run.  A run that converged at iteration k returns the rates and q(w) that k formed;
+ *      one that a factorisation stopped at k returns those that entered k.
+ * tau_rate (n, may be NULL): the rates, in and out; NULL starts from beta_i = alpha (omega = 1) and returns none.  With tol = 0, k
+ * iterations followed by K - k through tau_rate and gamma equal K iterations bitwise; identical calls agree bitwise.
+ * Afterwards the handle is what the host-paced sequence (sgp_w_stats, new weights through sgp_set_data, sgp_sweep) leaves: the
+ * resident point weights, weighted targets and data scalars are those of the last sweep, the noise is mean(q(w)), the getters give
+ * the last completed iteration's sweep, sgp_sweep_kind's `last` is FULL after one iteration and SGP_SWEEP_REWEIGHTED after more, and
+ * on a SGP_FLAG_REUSE_STATS handle the statistics stay reusable.  A second run continues on the weights the first left; any other
+ * weighted data are refused, so that a caller's pt_weight is never overwritten.
+ * SGP_ERR_ARG: everything sgp_vmp_run refuses (mu_init and likelihood apart); a handle without SGP_FLAG_KEEP_KUF; nu or a tau_rate
+ * entry that is not positive and finite; data set with y_var; data set with pt_weight, unless an earlier sgp_vmp_run_t left them.
+ * iterations = 0 returns 0 with nothing changed, behind every refusal. */
+int sgp_vmp_run_t(sgp_handle* h, double nu, double* tau_rate /* n, in/out, may be NULL */, int32_t flags, int32_t iterations,
+                  const double* gamma_prior /* 2 */, double* gamma /* 2, in/out */, double tol, double* values /* iterations, may be NULL */,
+                  double* terms /* 4 x iterations column-major, may be NULL */, int64_t* counts /* 2, may be NULL */);
 
 /* ---- exact-Psi input messages: a node's energy and its derivatives in the mean and covariance of its Gaussian input ----
  * With q(v), W, G and s_t as for sgp_theta_objective_psi (SGP_KERNEL_SE only, d_out = 1 .. 4, D <= 8) and x_t ~ N(m_t, S_t), the part of

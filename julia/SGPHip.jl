@@ -46,7 +46,7 @@ struct SGPConfig
 end
 const SGP_FLAG_KEEP_KUF = Int32(2)
 const SGP_FLAG_REUSE_STATS = Int32(16)
-const SGP_SWEEP_FULL, SGP_SWEEP_TARGETS, SGP_SWEEP_REUSED = 0, 1, 2
+const SGP_SWEEP_FULL, SGP_SWEEP_TARGETS, SGP_SWEEP_REUSED, SGP_SWEEP_REWEIGHTED = 0, 1, 2, 3
 const SGP_KERNEL_SE, SGP_KERNEL_MATERN12, SGP_KERNEL_MATERN32, SGP_KERNEL_MATERN52 = Int32(0), Int32(1), Int32(2), Int32(3)
 
 # the kernel family (include/sgp_hip.h, SGP_KERNEL_*) of a `kernel_family` argument: a name (:se, :matern12, :matern32,
@@ -636,6 +636,22 @@ function vmp_run!(meta::HipSGPMeta, iterations::Integer; likelihood::Integer = 0
                 h.ptr, likelihood, hold_w ? 1 : 0, iterations, g0 === nothing ? C_NULL : g0, g === nothing ? C_NULL : g,
                 μ_init === nothing ? C_NULL : μ_init, tol, values, terms, counts), h.ptr)
     return values, terms, g, Int(counts[1]), counts[2] == 1
+end
+
+# ---- device-paced VMP iterations of Student-t regression (sgp_vmp_run_t): y_i ~ N(f_i, 1 / (w τ_i)), τ_i ~ Gamma(ν/2, ν/2).  The handle
+# needs SGP_FLAG_KEEP_KUF.  β: the rates of q(τ_i) entering the run (in/out; nothing: (ν + 1) / 2, none returned); γ0, γ, tol, hold_w as
+# in vmp_run!.  Returns (values, terms, γ, β, iterations_done, converged).
+function vmp_run_t!(meta::HipSGPMeta, iterations::Integer, ν::Real; β = nothing, γ0 = nothing, γ = nothing, tol = 0.0, hold_w::Bool = false)
+    h = meta.handle
+    hold_w || γ0 !== nothing || throw(ArgumentError("vmp_run_t!: γ0 = (shape0, rate0) is required without hold_w"))
+    g0 = hold_w ? nothing : Float64[γ0[1], γ0[2]]
+    g = hold_w ? nothing : (γ === nothing ? copy(g0) : Float64[γ[1], γ[2]])
+    values = fill(NaN, max(iterations, 0)); terms = fill(NaN, 4, max(iterations, 0)); counts = zeros(Int64, 2)
+    check(ccall((:sgp_vmp_run_t, LIB), Cint,
+                (Ptr{Cvoid}, Float64, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, ν, β === nothing ? C_NULL : β, hold_w ? 1 : 0, iterations, g0 === nothing ? C_NULL : g0, g === nothing ? C_NULL : g,
+                tol, values, terms, counts), h.ptr)
+    return values, terms, g, β, Int(counts[1]), counts[2] == 1
 end
 
 # ---- the same objective and descent over the exact Psi-statistics of Gaussian inputs x_t ~ N(m_t, S_t) (SE kernel only;

@@ -149,6 +149,9 @@ static int32_t plan_bits_of(const SweepPlan& p) {
 //                                               per iteration, has_omega and omega_vmp_t (the weights are the run's, not a caller's), the
 //                                               resident weights, weighted targets and data scalars become those of the last sweep; its later
 //                                               sweeps re-form Psi2 and B from the resident K_uf (sweep_reweighted) and fill the record again.
+//                                               The MultiSGP run with Wishart noise (the _w export) is the Gaussian run on a handle with
+//                                               d_out > 1: the same sweeps, the same record; the noise in force behind it is mean(q(W)) with
+//                                               E[logdet W], and w0 is W[0] of the noise the last completed sweep ran at.
 // A new entry point gets a row here and an entry in MUTATORS / READERS of tests/call_sequence_ref.py, which drives every row in front
 // of every reader (tests/test_gpu_call_sequences.py) and holds the ledger of the exported names (tests/test_call_sequences_host.py).
 struct StatsRecord {
@@ -4095,9 +4098,10 @@ static bool finite_positive(double v) { return std::isfinite(v) && v > 0.0; }
 
 // What both runs hand to k_vmp_close; with a dense prior also log|Lambda0| and mu0 = Lambda0^-1 xi0, enqueued once per call: one
 // factorisation of a copy of Lambda0 with the step kernel, in the buffers sgp_set_prior(form 0) factors Sigma0 in (every sweep
-// rewrites dTmp, dWl and dSigma before it reads them).  dSt: [state | values | terms] of `it` iterations.
+// rewrites dTmp, dWl and dSigma before it reads them).  dSt: [state (nst) | values | terms] of `it` iterations.  The prior of q(w)
+// is the caller's to fill in (a0, b0; sgp_vmp_run_w keeps its Wishart prior in the state block).
 static int vmp_close_args(sgp_handle* h, hipStream_t s, VmpClose* c, double* dSt, size_t it, double* dMu0, const double* dKl, int nkl,
-                          const double* dPp, int npp, bool hold, const double* gamma_prior, double tol) {
+                          const double* dPp, int npp, bool hold, double tol, int nst = VMP_STATE) {
     const int Q = h->Q, Qp = h->Qp, form = h->prior_form;
     const double* ld0 = nullptr;
     int nld0 = 0;
@@ -4113,28 +4117,26 @@ static int vmp_close_args(sgp_handle* h, hipStream_t s, VmpClose* c, double* dSt
     memset(c, 0, sizeof *c);
     c->out = h->dOut; c->info = h->dInfo; c->stats_scal = stats_scalars(h); c->swept = h->dParams; c->src = h->dTrainParams;
     c->ppart = dPp; c->npp = npp; c->klpart = dKl; c->nkl = nkl; c->ld0 = ld0; c->nld0 = nld0; c->data_scal = h->dDataScal;
-    c->st = dSt; c->values = dSt + VMP_STATE; c->terms = dSt + VMP_STATE + it;
-    c->a0 = hold ? 1.0 : gamma_prior[0]; c->b0 = hold ? 1.0 : gamma_prior[1]; c->tol = tol;
+    c->st = dSt; c->values = dSt + nst; c->terms = dSt + nst + it;
+    c->a0 = c->b0 = 1.0; c->tol = tol;
     c->M = Q; c->hold = hold ? 1 : 0; c->form = form;
     return 0;
 }
 
-// A run's results, after the wait: [state | values | terms] back in one copy, q(w) and the noise the last completed iteration left,
-// the record of the resident statistics, counts, and the status of a run that a factorisation stopped
-static int vmp_results(sgp_handle* h, const char* name, const double* dSt, size_t it, bool hold, double* gamma, double* values,
-                       double* terms, int64_t* counts) {
-    std::vector<double> back(VMP_STATE + 5 * it);
+// A run's results, after the wait: [state (nst) | values | terms] back in one copy, q(w) and the noise the last completed iteration
+// left -- commit(st), which knows the run's q(w): Gamma(a, b) or Wishart(nu, R) --, the record of the resident statistics, counts,
+// and the status of a run that a factorisation stopped; w_info >= 0: the state slot of the Wishart inverse scale's failing minor
+template <class Commit>
+static int vmp_results(sgp_handle* h, const char* name, const double* dSt, size_t nst, size_t it, bool hold, Commit commit,
+                       double* values, double* terms, int64_t* counts, int w_info = -1) {
+    std::vector<double> back(nst + 5 * it);
     HIPCHK(h, hipMemcpy(back.data(), dSt, sizeof(double) * back.size(), hipMemcpyDeviceToHost));
     const double* st = back.data();
-    if (values) memcpy(values, st + VMP_STATE, sizeof(double) * it);
-    if (terms) memcpy(terms, st + VMP_STATE + it, sizeof(double) * 4 * it);
+    if (values) memcpy(values, st + nst, sizeof(double) * it);
+    if (terms) memcpy(terms, st + nst + it, sizeof(double) * 4 * it);
     const int done = (int)st[VMP_DONE], stop = (int)st[VMP_STOP];
     if (done > 0) {
-        if (!hold) {
-            h->hParams->W[0] = st[VMP_A] / st[VMP_B];
-            h->hParams->E_logw = st[VMP_ELOGW];
-            gamma[0] = st[VMP_A]; gamma[1] = st[VMP_B];
-        }
+        if (!hold) commit(st);
         stats_swept_at(h, st[VMP_W_SWEPT]);
     }
     if (h->cfg.flags & SGP_FLAG_REUSE_STATS) stats_checked(h, st[VMP_INFO_KUU] == 0.0 && st[VMP_INFO_SYNC] == 0.0);
@@ -4144,11 +4146,12 @@ static int vmp_results(sgp_handle* h, const char* name, const double* dSt, size_
     int frc = check_sync_status(h);
     if (!frc) frc = factor_status(h, (int)st[VMP_INFO_PRIOR], (at + ": the prior precision").c_str());
     if (!frc) frc = factor_status(h, (int)st[VMP_INFO_KUU], (at + ": K_uu").c_str(), (int)st[VMP_INFO_LAMBDA], (at + ": Lambda").c_str(), true);
+    if (!frc && w_info >= 0) frc = factor_status(h, (int)st[w_info], (at + ": the Wishart inverse scale R0 + S").c_str());
     if (counts && frc > 0) counts[1] = -frc;
     return frc;
 }
 
-// the first iteration's sweep of either run: a full sweep; `whole`: as sgp_sweep plans it (sweep_plan), else in the plain order
+// the first iteration's sweep of every run: a full sweep; `whole`: as sgp_sweep plans it (sweep_plan), else in the plain order
 static int vmp_full_sweep(sgp_handle* h, bool whole) {
     int rc = sweep_local_impl(h, nullptr, whole);
     if (!rc) rc = sgp_sweep_finish(h, nullptr);
@@ -4159,21 +4162,49 @@ static int vmp_full_sweep(sgp_handle* h, bool whole) {
     return rc;
 }
 
-// the refusals sgp_vmp_run and sgp_vmp_run_t share: the call's own arguments, then what the handle must be
-static int vmp_check_args(sgp_handle* h, const char* name, int32_t flags, int32_t iterations, const double* gamma_prior,
-                          const double* gamma, double tol) {
+// The refusals the three runs share, each rule in one place.  The call's own arguments: the flags and the iteration count, q(w)
+// (vmp_check_gamma: the Gamma runs; vmp_check_wishart, below wishart_scale_fault: sgp_vmp_run_w), tol -- asked in that order --, then
+// what the handle must be (vmp_check_handle; `multi`: a MultiSGP handle, else a UniSGP one), what the resident data must be
+// (vmp_check_data) and that no hook is installed (vmp_check_unsharded).
+static int vmp_check_call(sgp_handle* h, const char* name, int32_t flags, int32_t iterations) {
     if (flags & ~SGP_VMP_HOLD_W) return refuse(h, name, "unknown flags");
     if (iterations < 0) return refuse(h, name, "iterations must be >= 0");
-    if (!(flags & SGP_VMP_HOLD_W)) {
-        if (!gamma_prior || !gamma) return refuse(h, name, "gamma_prior and gamma are required without SGP_VMP_HOLD_W");
-        if (!finite_positive(gamma_prior[0]) || !finite_positive(gamma_prior[1])) return refuse(h, name, "gamma_prior must be positive and finite");
-        if (!finite_positive(gamma[0]) || !finite_positive(gamma[1])) return refuse(h, name, "gamma must be positive and finite");
-    }
-    if (!(tol >= 0.0)) return refuse(h, name, "tol must be >= 0");
     return 0;
 }
-static int vmp_check_handle(sgp_handle* h, const char* name) {
-    if (h->dout != 1) return refuse(h, name, "UniSGP handles only (d_out = 1)");
+static int vmp_check_gamma(sgp_handle* h, const char* name, int32_t flags, const double* gamma_prior, const double* gamma) {
+    if (flags & SGP_VMP_HOLD_W) return 0;
+    if (!gamma_prior || !gamma) return refuse(h, name, "gamma_prior and gamma are required without SGP_VMP_HOLD_W");
+    if (!finite_positive(gamma_prior[0]) || !finite_positive(gamma_prior[1])) return refuse(h, name, "gamma_prior must be positive and finite");
+    if (!finite_positive(gamma[0]) || !finite_positive(gamma[1])) return refuse(h, name, "gamma must be positive and finite");
+    return 0;
+}
+static int vmp_check_tol(sgp_handle* h, const char* name, double tol) {
+    return tol >= 0.0 ? 0 : refuse(h, name, "tol must be >= 0");
+}
+static int vmp_check_args(sgp_handle* h, const char* name, int32_t flags, int32_t iterations, const double* gamma_prior,
+                          const double* gamma, double tol) {
+    if (int rc = vmp_check_call(h, name, flags, iterations)) return rc;
+    if (int rc = vmp_check_gamma(h, name, flags, gamma_prior, gamma)) return rc;
+    return vmp_check_tol(h, name, tol);
+}
+// the resident data: never with y_var; with the caller's pt_weight only where the run leaves the weights alone (`weights_ok`)
+static int vmp_check_data(sgp_handle* h, const char* name, bool weights_ok) {
+    if (!h->has_yv && (weights_ok || !h->has_omega)) return 0;
+    return refuse(h, name, weights_ok ? "the resident data must have been set without y_var"
+                                      : "the resident data must have been set without y_var and without pt_weight");
+}
+static int vmp_check_unsharded(sgp_handle* h, const char* name) {
+    return h->allreduce ? refuse(h, name, "data-sharded runs are not supported (remove the hook)") : 0;
+}
+// q(w) of the Gamma runs as the last completed iteration left it, and the noise that follows from it (vmp_results' commit)
+static void vmp_commit_gamma(sgp_handle* h, const double* st, double* gamma) {
+    h->hParams->W[0] = st[VMP_A] / st[VMP_B];
+    h->hParams->E_logw = st[VMP_ELOGW];
+    gamma[0] = st[VMP_A]; gamma[1] = st[VMP_B];
+}
+static int vmp_check_handle(sgp_handle* h, const char* name, bool multi = false) {
+    if (!multi && h->dout != 1) return refuse(h, name, "UniSGP handles only (d_out = 1)");
+    if (multi && h->dout < 2) return refuse(h, name, "MultiSGP handles only (d_out = 2 .. 4; sgp_vmp_run is the UniSGP run)");
     if (int prc = refuse_exact_psi(h, name)) return prc;
     if (h->training) return refuse(h, name, "a device-paced training run is open (sgp_train_end first)");
     if (!h->have_inducing || !h->have_kernel || !h->have_data || h->n < 1)
@@ -4191,8 +4222,8 @@ extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int
     for (int i = 0; mu_init && i < h->Q; ++i)
         if (!std::isfinite(mu_init[i])) return refuse(h, name, "mu_init must be finite");
     if (int hrc = vmp_check_handle(h, name)) return hrc;
-    if (h->has_yv || h->has_omega) return refuse(h, name, "the resident data must have been set without y_var and without pt_weight");
-    if (h->allreduce) return refuse(h, name, "data-sharded runs are not supported (remove the hook)");
+    if (int drc = vmp_check_data(h, name, false)) return drc;
+    if (int arc = vmp_check_unsharded(h, name)) return arc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int64_t n = h->n;
     if (probit) {
@@ -4240,7 +4271,8 @@ extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int
     h->params_gen++;
     h->in_flight = true;
     VmpClose c;
-    if (int prc = vmp_close_args(h, s, &c, dSt, it, dMu0, dKl, nkl, dPp, npp, hold, gamma_prior, tol)) return prc;
+    if (int prc = vmp_close_args(h, s, &c, dSt, it, dMu0, dKl, nkl, dPp, npp, hold, tol)) return prc;
+    if (!hold) { c.a0 = gamma_prior[0]; c.b0 = gamma_prior[1]; }
     c.probit = probit ? 1 : 0;
     if (!hold) hipLaunchKernelGGL(k_vmp_close, dim3(1), dim3(256), 0, s, c, (int)VMP_STAGE_INIT);
     int rc = 0;
@@ -4268,7 +4300,7 @@ extern "C" int sgp_vmp_run(sgp_handle* h, int32_t likelihood, int32_t flags, int
     h->params_gen++;
     if (rc) { stats_drop(h, STATS_REUSE | STATS_QV); return rc; }
 
-    return vmp_results(h, name, dSt, it, hold, gamma, values, terms, counts);
+    return vmp_results(h, name, dSt, VMP_STATE, it, hold, [&](const double* st) { vmp_commit_gamma(h, st, gamma); }, values, terms, counts);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4297,10 +4329,10 @@ extern "C" int sgp_vmp_run_t(sgp_handle* h, double nu, double* tau_rate, int32_t
     if (int hrc = vmp_check_handle(h, name)) return hrc;
     if (!(h->cfg.flags & SGP_FLAG_KEEP_KUF))
         return refuse(h, name, "create the handle with SGP_FLAG_KEEP_KUF (the per-point partial buffers of the rates exist only with it)");
-    if (h->has_yv) return refuse(h, name, "the resident data must have been set without y_var");
+    if (int yrc = vmp_check_data(h, name, true)) return yrc;
     if (h->has_omega && !h->omega_vmp_t)
         return refuse(h, name, "the resident data carry the caller's pt_weight, which the run would overwrite (sgp_set_data without them)");
-    if (h->allreduce) return refuse(h, name, "data-sharded runs are not supported (remove the hook)");
+    if (int arc = vmp_check_unsharded(h, name)) return arc;
     const int64_t n = h->n;
     for (int64_t i = 0; tau_rate && i < n; ++i)
         if (!finite_positive(tau_rate[i])) return refuse(h, name, "tau_rate must be positive and finite");
@@ -4336,7 +4368,8 @@ extern "C" int sgp_vmp_run_t(sgp_handle* h, double nu, double* tau_rate, int32_t
     h->params_gen++;
     h->in_flight = true;
     VmpClose c;
-    if (int prc = vmp_close_args(h, s, &c, dSt, it, dMu0, dKl, nkl, dPp, npp, hold, gamma_prior, tol)) return prc;
+    if (int prc = vmp_close_args(h, s, &c, dSt, it, dMu0, dKl, nkl, dPp, npp, hold, tol)) return prc;
+    if (!hold) { c.a0 = gamma_prior[0]; c.b0 = gamma_prior[1]; }
     {
         const long double psi = digamma_ext((long double)alpha);
         c.t_points = (double)n;
@@ -4374,7 +4407,130 @@ extern "C" int sgp_vmp_run_t(sgp_handle* h, double nu, double* tau_rate, int32_t
     // (the host's record of sum omega y^2, which sgp_set_output_cov_sum adds to, follows the device's)
     HIPCHK(h, hipMemcpy(h->ryy_data, h->dDataScal + SGP_S_YY, sizeof(double), hipMemcpyDeviceToHost));
     if (tau_rate) HIPCHK(h, hipMemcpy(tau_rate, dBeta, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    return vmp_results(h, name, dSt, it, hold, gamma, values, terms, counts);
+    return vmp_results(h, name, dSt, VMP_STATE, it, hold, [&](const double* st) { vmp_commit_gamma(h, st, gamma); }, values, terms, counts);
+}
+
+// ------------------------------------------------------------------------------------------------
+// MultiSGP with Wishart noise, device-paced (include/sgp_hip.h: sgp_vmp_run_w; kernels: k_vmp_kl and k_vmp_close_w).
+// sgp_vmp_run's Gaussian frame on a handle with d_out = 2 .. 4: per iteration the sweep -- full first, over the resident statistics
+// afterwards --, k_vmp_kl and the Wishart closing stage, which writes W_bar and E[logdet W] of the next sweep into dTrainParams.
+// ------------------------------------------------------------------------------------------------
+// A d x d column-major host matrix as q(W)'s inverse scale: finite, symmetric to rounding -- |A_ij - A_ji| <= 1e-9 sqrt(A_ii A_jj):
+// the sweep's own S carries a few roundings of sums that cancel in it -- and positive definite.  *logdet (may be NULL) receives log|A|.
+static const char* wishart_scale_fault(const double* A, int d, double* logdet) {
+    for (int i = 0; i < d * d; ++i)
+        if (!std::isfinite(A[i])) return "has a non-finite entry";
+    for (int j = 0; j < d; ++j)
+        for (int i = j + 1; i < d; ++i)
+            if (!(std::fabs(A[i + j * d] - A[j + i * d]) <= 1e-9 * std::sqrt(std::fabs(A[i + i * d] * A[j + j * d])))) return "is not symmetric";
+    long double L[MAXO][MAXO] = {{0}}, ld = 0.0L;
+    for (int j = 0; j < d; ++j) {
+        long double dj = A[j + j * d];
+        for (int k = 0; k < j; ++k) dj -= L[j][k] * L[j][k];
+        if (!(dj > 0.0L)) return "is not positive definite";
+        L[j][j] = sqrtl(dj);
+        ld += logl(L[j][j]);
+        for (int i = j + 1; i < d; ++i) {
+            long double v = A[i + j * d];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    if (logdet) *logdet = (double)(2.0L * ld);
+    return nullptr;
+}
+
+// q(W) of sgp_vmp_run_w, d = d_out >= 2: the prior and the entering (nu, R), each 1 + d * d; *ld_r0 receives log|R0|
+static int vmp_check_wishart(sgp_handle* h, const char* name, int32_t flags, const double* wishart_prior, const double* wishart,
+                             double* ld_r0) {
+    if (flags & SGP_VMP_HOLD_W) return 0;
+    const int d = h->dout;
+    if (!wishart_prior || !wishart) return refuse(h, name, "wishart_prior and wishart are required without SGP_VMP_HOLD_W");
+    for (const double* q : {wishart_prior, wishart}) {
+        const std::string what = q == wishart_prior ? "wishart_prior" : "wishart";
+        if (!std::isfinite(q[0]) || !(q[0] > (double)(d - 1)))
+            return refuse(h, name, (what + ": the degrees of freedom must be finite and > d - 1").c_str());
+        if (const char* fault = wishart_scale_fault(q + 1, d, q == wishart_prior ? ld_r0 : nullptr))
+            return refuse(h, name, (what + ": the inverse scale " + fault).c_str());
+    }
+    return 0;
+}
+
+extern "C" int sgp_vmp_run_w(sgp_handle* h, int32_t flags, int32_t iterations, const double* wishart_prior, double* wishart, double tol,
+                             double* values, double* terms, int64_t* counts) {
+    const char* name = "sgp_vmp_run_w";
+    if (!h) return fail(h, SGP_ERR_ARG, "sgp_vmp_run_w: null handle");
+    if (int arc = vmp_check_call(h, name, flags, iterations)) return arc;
+    const bool hold = (flags & SGP_VMP_HOLD_W) != 0;
+    const int d = h->dout;
+    if (d < 2) return vmp_check_handle(h, name, true);           // (q(W) below is read as d x d)
+    double ld_r0 = 0.0;
+    if (int qrc = vmp_check_wishart(h, name, flags, wishart_prior, wishart, &ld_r0)) return qrc;
+    if (int trc = vmp_check_tol(h, name, tol)) return trc;
+    if (int hrc = vmp_check_handle(h, name, true)) return hrc;
+    if (int yrc = vmp_check_data(h, name, true)) return yrc;
+    if (int src = vmp_check_unsharded(h, name)) return src;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (counts) counts[0] = counts[1] = 0;
+    if (iterations == 0) return 0;
+    if (int wrc = sync_checked(h)) return wrc;
+    if (int drc = descent_device_state(h)) return drc;
+
+    // call scratch: [state | values | terms | mu0 | k_vmp_kl's pairs]; the first four go up in one copy, the first three come back in one
+    const int Q = h->Q, Qp = h->Qp, form = h->prior_form;
+    const int nkl = form == 2 ? (Q + 255) / 256 : std::min(Q, 256);
+    const size_t it = (size_t)iterations;
+    double* base = nullptr;
+    if (int crc = call_scratch(h, VMP_W_STATE + 5 * it + (size_t)Qp + 2 * (size_t)nkl, &base)) return crc;
+    double *dSt = base, *dMu0 = dSt + VMP_W_STATE + 5 * it, *dKl = dMu0 + Qp;
+    {
+        std::vector<double> init(VMP_W_STATE + 5 * it + (size_t)Qp, std::numeric_limits<double>::quiet_NaN());
+        for (int i = 0; i < VMP_W_STATE; ++i) init[i] = 0.0;
+        for (int i = 0; i < Qp; ++i) init[VMP_W_STATE + 5 * it + i] = 0.0;
+        if (!hold) {
+            long double lg0 = 0.0L;
+            for (int i = 0; i < d; ++i) lg0 += lgammal(0.5L * ((long double)wishart_prior[0] - i));
+            init[VMP_W_NU] = wishart[0];
+            init[VMP_W_NU0] = wishart_prior[0]; init[VMP_W_LDR0] = ld_r0; init[VMP_W_LG0] = (double)lg0;
+            for (int i = 0; i < d * d; ++i) { init[VMP_W_R + i] = wishart[1 + i]; init[VMP_W_R0 + i] = wishart_prior[1 + i]; }
+        }
+        init[VMP_ELOGW] = h->hParams->E_logw;
+        HIPCHK(h, hipMemcpy(dSt, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, hipMemcpy(h->dTrainParams, h->hParams, sizeof(Params), hipMemcpyHostToDevice));
+
+    hipStream_t s = h->own;
+    h->params_src = h->dTrainParams;
+    h->params_gen++;
+    h->in_flight = true;
+    VmpClose c;
+    if (int prc = vmp_close_args(h, s, &c, dSt, it, dMu0, dKl, nkl, nullptr, 0, hold, tol, VMP_W_STATE)) return prc;
+    auto close = [&](int stage) {
+        by_dout(d, [&](auto DO) {
+            hipLaunchKernelGGL(k_vmp_close_w<decltype(DO)::value>, dim3(1), dim3(256), 0, s, c, (const double*)h->dWishart, stage);
+        });
+    };
+    if (!hold) close(VMP_STAGE_INIT);
+    int rc = 0;
+    for (int k = 0; k < iterations && !rc; ++k) {
+        rc = k == 0 ? vmp_full_sweep(h, true) : sweep_resident(h, nullptr, false);
+        if (rc) break;
+        hipLaunchKernelGGL(k_vmp_kl, dim3(nkl), dim3(256), 0, s, (const double*)h->dLambda0, (const double*)h->dSigma,
+                           (const double*)h->dMu, (const double*)dMu0, (const Params*)h->dParams, Q, Qp, form, dKl);
+        c.k = k;
+        close(VMP_STAGE_CLOSE);
+    }
+    rc = descent_wait(h, s, rc);
+    h->params_src = h->hParams;
+    h->params_gen++;
+    if (rc) { stats_drop(h, STATS_REUSE | STATS_QV); return rc; }
+
+    auto commit = [&](const double* st) {
+        for (int i = 0; i < d * d; ++i) { h->hParams->W[i] = st[VMP_W_WBAR + i]; wishart[1 + i] = st[VMP_W_R + i]; }
+        h->hParams->E_logw = st[VMP_ELOGW];
+        wishart[0] = st[VMP_W_NU];
+    };
+    return vmp_results(h, name, dSt, VMP_W_STATE, it, hold, commit, values, terms, counts, VMP_W_INFO);
 }
 
 // ------------------------------------------------------------------------------------------------

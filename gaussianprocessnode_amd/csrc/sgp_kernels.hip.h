@@ -4695,6 +4695,196 @@ __global__ void __launch_bounds__(256) k_vmp_close(VmpClose c, int stage) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The Wishart closing step of the MultiSGP run (sgp_vmp_run_w in sgp_api.hip): k_vmp_close's CLOSE and INIT with
+// q(W) = Wishart(nu, R^-1), R the DO x DO inverse scale, in the place of q(w) = Gamma(a, b).  The run's state is VMP_W_STATE doubles:
+// the slots above (VMP_A, VMP_B, VMP_LIK and the VMP_T_* stay unused) and, behind them, q(W), the noise that follows from it and the
+// prior.  `wishart` is S = sum_t (I1_t + I2_t) of the sweep (k_scalars).
+// The matrices are DO x DO column-major with stride DO, as Params::W and k_scalars' `wishart` are.
+// ------------------------------------------------------------------------------------------------
+enum { VMP_W_NU = VMP_STATE,                        // q(W) = (nu, R) after the last completed iteration
+       VMP_W_INFO = VMP_STATE + 1,                  // the failing leading minor of R0 + S when that stopped the run
+       // the prior, constant over the call: nu0, and log|R0| and sum_i lgamma((nu0 - i) / 2) as the host formed them once
+       VMP_W_NU0 = VMP_STATE + 2, VMP_W_LDR0 = VMP_STATE + 3, VMP_W_LG0 = VMP_STATE + 4,
+       VMP_W_R = VMP_STATE + 8,                     // R, MAXO * MAXO slots
+       VMP_W_WBAR = VMP_W_R + MAXO * MAXO,          // mean(q_W) = nu R^-1, exactly symmetric, MAXO * MAXO slots
+       VMP_W_R0 = VMP_W_WBAR + MAXO * MAXO,         // the prior's inverse scale, MAXO * MAXO slots
+       VMP_W_STATE = VMP_W_R0 + MAXO * MAXO };
+static_assert(VMP_W_STATE == 80, "the layout of sgp_vmp_run_w's state block");
+
+// Everything below works on DO x DO matrices held by ONE lane.  DO is a template parameter and every loop is unrolled, so that every
+// index into the local arrays is a constant and the arrays live in registers.  The arithmetic is not contracted: the INIT stage of one
+// call and the CLOSE stage of the call in front of it form W_bar from the same (nu, R) and must give the same doubles.
+//
+// A = L L' (the lower triangle of A is read), Inv = A^-1 with Inv[i,j] and Inv[j,i] the same double, logdet = log|A|.  Returns 0, or
+// the order of the first leading minor that is not positive (then Inv and logdet are not formed).
+template <int DO>
+__device__ __forceinline__ int spd_inverse_small(const double (&A)[DO * DO], double (&Inv)[DO * DO], double& logdet) {
+#pragma clang fp contract(off)
+    double L[DO * DO], Li[DO * DO];
+    int bad = 0;
+    double ld = 0.0;
+#pragma unroll
+    for (int j = 0; j < DO; ++j) {
+        double d = A[j + j * DO];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[j + k * DO] * L[j + k * DO];
+        if (!(d > 0.0) && bad == 0) bad = j + 1;
+        const double ljj = sqrt(d);
+        L[j + j * DO] = ljj;
+        ld += log(ljj);
+#pragma unroll
+        for (int i = j + 1; i < DO; ++i) {
+            double v = A[i + j * DO];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= L[i + k * DO] * L[j + k * DO];
+            L[i + j * DO] = v / ljj;
+        }
+    }
+    if (bad) return bad;
+    // Li = L^-1 (lower), column by column
+#pragma unroll
+    for (int j = 0; j < DO; ++j) {
+        Li[j + j * DO] = 1.0 / L[j + j * DO];
+#pragma unroll
+        for (int i = j + 1; i < DO; ++i) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = j; k < i; ++k) v += L[i + k * DO] * Li[k + j * DO];
+            Li[i + j * DO] = -v / L[i + i * DO];
+        }
+    }
+    // A^-1 = Li' Li: the lower triangle, mirrored
+#pragma unroll
+    for (int j = 0; j < DO; ++j)
+#pragma unroll
+        for (int i = j; i < DO; ++i) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = i; k < DO; ++k) v += Li[k + i * DO] * Li[k + j * DO];
+            Inv[i + j * DO] = v;
+            Inv[j + i * DO] = v;
+        }
+    logdet = 2.0 * ld;
+    return 0;
+}
+
+// sum_i psi((nu - i) / 2) and sum_i lgamma((nu - i) / 2), i = 0 .. d - 1 (no array behind them: the loops stay loops)
+__device__ __forceinline__ double wishart_psi_sum(double nu, int d) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+#pragma nounroll
+    for (int i = 0; i < d; ++i) s += digamma_dev(0.5 * (nu - (double)i));
+    return s;
+}
+__device__ __forceinline__ double wishart_lgamma_sum(double nu, int d) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+#pragma nounroll
+    for (int i = 0; i < d; ++i) s += lgamma(0.5 * (nu - (double)i));
+    return s;
+}
+
+// One workgroup.  INIT: the noise of iteration 0 from q(W) = (nu, R) in the state block: W_bar = nu R^-1 and
+// E[logdet W] = sum_i psi((nu - i) / 2) + DO log 2 - log|R| into the parameter block `src` and the state.  (The host has checked that R
+// is positive definite.)  CLOSE (behind the sweep and k_vmp_kl, iteration k), in this order: k_vmp_kl's pairs and the prior's
+// log-determinant in a fixed order; the status words; S, N; R = R0 + S, its factor, R^-1 and log|R|; the four terms and the value at
+// (q(v), the NEW q(W)); the stop rule and the commit; the noise of the next iteration, unless the run stops.  It writes nothing the
+// sweep's own kernels write.
+template <int DO>
+__global__ void __launch_bounds__(256) k_vmp_close_w(VmpClose c, const double* __restrict__ wishart, int stage) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    double* st = c.st;
+    const int tid = threadIdx.x;
+    constexpr double LOG2 = 0.69314718055994530941723212145818;
+    if (stage == VMP_STAGE_INIT) {
+        if (tid != 0) return;
+        double R[DO * DO], Ri[DO * DO], ldr = 0.0;
+#pragma unroll
+        for (int e = 0; e < DO * DO; ++e) R[e] = st[VMP_W_R + e];
+        const double nu = st[VMP_W_NU];
+        spd_inverse_small<DO>(R, Ri, ldr);
+        const double el = (wishart_psi_sum(nu, DO) + (double)DO * LOG2) - ldr;
+#pragma unroll
+        for (int e = 0; e < DO * DO; ++e) {
+            const double wb = nu * Ri[e];
+            c.src->W[e] = wb;
+            st[VMP_W_WBAR + e] = wb;
+        }
+        c.src->E_logw = el;
+        st[VMP_ELOGW] = el;
+        return;
+    }
+    if (st[VMP_STOP] != 0.0) return;                            // (uniform)
+    double tr = 0.0, qd = 0.0, ld = 0.0;
+    for (int b = tid; b < c.nkl; b += 256) { tr += c.klpart[2 * b]; qd += c.klpart[2 * b + 1]; }
+    for (int e = tid; e < c.nld0; e += 256) ld += c.ld0[e];
+    tr = block_sum(tr, red);
+    qd = block_sum(qd, red);
+    ld = 2.0 * block_sum(ld, red);
+    if (tid != 0) return;
+    const int i_kuu = (int)c.out[SGP_R_INFO_KUU], i_lam = (int)c.out[SGP_R_INFO_LAMBDA];
+    const int i_prior = c.form == 2 ? 0 : c.info[2], i_sync = c.info[3];     // (dInfo: K_uu, Lambda, prior, stream hand-off)
+    if (i_kuu != 0 || i_lam != 0 || i_prior != 0 || i_sync != 0) {
+        st[VMP_STOP] = 2.0;
+        st[VMP_INFO_KUU] = (double)i_kuu; st[VMP_INFO_LAMBDA] = (double)i_lam;
+        st[VMP_INFO_PRIOR] = (double)i_prior; st[VMP_INFO_SYNC] = (double)i_sync;
+        return;
+    }
+    const double LOG2PI = 1.8378770664093454835606594728112;
+    const double n = c.stats_scal[SGP_S_N];
+    double S[DO * DO], Wb[DO * DO], R[DO * DO];
+#pragma unroll
+    for (int e = 0; e < DO * DO; ++e) { S[e] = wishart[e]; Wb[e] = c.swept->W[e]; R[e] = 0.0; }
+    double nu = 0.0, elog = c.swept->E_logw, t3 = 0.0;
+    if (!c.hold) {
+        double Ri[DO * DO], R0[DO * DO], ldr = 0.0;
+        const double nu0 = st[VMP_W_NU0];
+#pragma unroll
+        for (int e = 0; e < DO * DO; ++e) { R0[e] = st[VMP_W_R0 + e]; R[e] = R0[e] + S[e]; }
+        const int minor = spd_inverse_small<DO>(R, Ri, ldr);
+        if (minor != 0) {
+            st[VMP_STOP] = 2.0;
+            st[VMP_W_INFO] = (double)minor;
+            return;
+        }
+        nu = nu0 + n;
+        const double psis = wishart_psi_sum(nu, DO);
+        elog = (psis + (double)DO * LOG2) - ldr;
+        double tr0 = 0.0;                                        // tr(R0 R^-1)
+#pragma unroll
+        for (int e = 0; e < DO * DO; ++e) { Wb[e] = nu * Ri[e]; tr0 += R0[e] * Ri[e]; }
+        // lnGamma_d(nu0 / 2) - lnGamma_d(nu / 2): the DO (DO - 1) / 4 log(pi) cancel
+        const double lmg = st[VMP_W_LG0] - wishart_lgamma_sum(nu, DO);
+        t3 = (((0.5 * nu0 * (ldr - st[VMP_W_LDR0]) + 0.5 * nu * (tr0 - (double)DO)) + lmg) + 0.5 * (nu - nu0) * psis);
+    }
+    double trws = 0.0;                                           // tr(W_bar S), W_bar symmetric
+#pragma unroll
+    for (int e = 0; e < DO * DO; ++e) trws += Wb[e] * S[e];
+    const double ld0 = c.form == 2 ? (double)c.M * log(c.swept->prior_iso) : ld;
+    const double t0 = 0.5 * ((trws - n * elog) + n * ((double)DO * LOG2PI));
+    const double t1 = 0.0;
+    const double t2 = 0.5 * (tr + qd - (double)c.M - ld0 + c.out[SGP_R_LOGDET_LAMBDA]);
+    const double F = ((t0 + t1) + t2) + t3;
+    c.terms[4 * c.k] = t0; c.terms[4 * c.k + 1] = t1; c.terms[4 * c.k + 2] = t2; c.terms[4 * c.k + 3] = t3;
+    c.values[c.k] = F;
+    const bool conv = c.k >= 1 && c.tol > 0.0 && fabs(F - st[VMP_FPREV]) <= c.tol * fabs(F);
+    st[VMP_FPREV] = F; st[VMP_DONE] = (double)(c.k + 1);
+    st[VMP_W_SWEPT] = c.swept->W[0]; st[VMP_ELOGW] = elog;
+    if (!c.hold) {
+        st[VMP_W_NU] = nu;
+#pragma unroll
+        for (int e = 0; e < DO * DO; ++e) { st[VMP_W_R + e] = R[e]; st[VMP_W_WBAR + e] = Wb[e]; }
+    }
+    if (conv) { st[VMP_STOP] = 1.0; return; }
+    if (!c.hold) {
+#pragma unroll
+        for (int e = 0; e < DO * DO; ++e) c.src->W[e] = Wb[e];
+        c.src->E_logw = elog;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Closed-form SE Psi-statistics of Gaussian inputs x_t ~ N(m_t, S_t) (sgp_psi_stats, sgp_sweep_local_psi; DESIGN.md "Exact
 // Psi-statistics").  With Lambda = diag(ell^2), Lambda + c S_t = C C' (c = 1 for Psi1, 2 for Psi2) and g_tm = C^-1 (m_t - z_m):
 //   Psi1_t[m]    = sigma2 prod_d(ell_d / C_dd) exp(-1/2 |g_tm|^2)                                      (c = 1)

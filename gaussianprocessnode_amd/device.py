@@ -604,6 +604,45 @@ class SGPDevice:
         self._check(rc, "sgp_vmp_run_t")
         return values, terms, g, beta, int(counts[0]), bool(counts[1] == 1)
 
+    def vmp_run_w(self, iterations: int, wishart_prior=None, wishart=None, hold_w: bool = False, tol: float = 0.0):
+        """`iterations` VMP iterations of `y_t ~ MultiSGP(x_t, v, W, theta), W ~ Wishart` over the resident data (points, optional
+        weights / n_nodes, optional output covariance sum) with the free energy of each, paced by the device (sgp_vmp_run_w;
+        d_out = 2 .. 4).  wishart_prior = (nu0, R0) and wishart = (nu, R) or a WishartFast -- q(W) entering the run, default the
+        prior --, R the d x d inverse scale, unless hold_w keeps the last `set_noise`.  Returns (values, terms, WishartFast,
+        iterations_done, converged): terms (iterations, 4) = [node energy at the new q(W), 0, KL(q(v)), KL(q(W))]; the
+        WishartFast is the final q(W), None with hold_w.  A K_uu, Lambda or R0 + S that is not positive definite raises
+        LinAlgError as `vmp_run` does; the exception carries `minor`, `values`, `terms`, `wishart`, `iterations_done`, `counts`."""
+        from .distributions import WishartFast
+        K, d = int(iterations), self.d_out
+
+        def pack(q, what):
+            nu, R = (q.nu, q.invS) if isinstance(q, WishartFast) else q
+            R = np.asarray(R, dtype=np.float64)
+            if R.shape != (d, d):
+                raise ValueError(f"vmp_run_w: {what}: the inverse scale must be ({d}, {d}), got {R.shape}")
+            return as_f64(np.concatenate([[float(nu)], R.T.ravel()]))      # column-major
+
+        p0 = q = None
+        if not hold_w:
+            if wishart_prior is None:
+                raise ValueError("vmp_run_w: wishart_prior = (nu0, R0) is required without hold_w")
+            p0 = pack(wishart_prior, "wishart_prior")
+            q = p0.copy() if wishart is None else pack(wishart, "wishart").copy()
+        values = np.full(max(K, 0), np.nan)
+        terms = np.full((max(K, 0), _lib.SGP_VMP_W_TERMS), np.nan)
+        counts = (C.c_int64 * 2)()
+        rc = self._lib.sgp_vmp_run_w(self._h, _lib.SGP_VMP_HOLD_W if hold_w else 0, K, ptr(p0), ptr(q), float(tol), ptr(values),
+                                     ptr(terms), counts)
+        q_w = None if q is None else WishartFast(float(q[0]), q[1:].reshape(d, d).T.copy())
+        if rc > 0:
+            msg = self._lib.sgp_last_error(self._h)
+            err = np.linalg.LinAlgError(f"sgp_vmp_run_w: {msg.decode() if msg else ''} (leading minor {rc})")
+            err.minor, err.values, err.terms, err.wishart, err.iterations_done = rc, values, terms, q_w, int(counts[0])
+            err.counts = (int(counts[0]), int(counts[1]))       # counts[1] = -minor
+            raise err
+        self._check(rc, "sgp_vmp_run_w")
+        return values, terms, q_w, int(counts[0]), bool(counts[1] == 1)
+
     def theta_objective_psi(self, mean, cov, y_mean, want_grad: bool = False):
         """The hyper-parameter objective over the exact Psi-statistics of T Gaussian inputs N(mean[t], cov[t]) at the current kernel
         (sgp_theta_objective_psi; SE only): `theta_objective` with the cubature sums replaced by exact expectations.  mean (T, D),

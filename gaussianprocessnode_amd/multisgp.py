@@ -76,15 +76,14 @@ def _expand(meta: MultiSGPMeta, q_ins: Sequence, q_outs: Sequence):
     return np.concatenate(pts), np.concatenate(wts), np.concatenate(ys), cov_sum
 
 
-def sweep(meta: MultiSGPMeta, q_outs: Sequence, q_ins: Sequence, q_w, q_theta: PointMass, prior, E_logdet_W=None):
-    """One VMP update of q(v) from all steps' `:v` messages (GPnode/MultiSGPnode.jl:290-328) folded with the prior.
-    Returns the marginal MvNormalMeanCovariance; the Wishart statistics and the energy are then available through
-    `rule_w_summed` / `average_energy_summed`."""
+def load(meta: MultiSGPMeta, q_outs: Sequence, q_ins: Sequence, q_w, q_theta: PointMass, prior, E_logdet_W=None):
+    """What `sweep` puts on the engine in front of its sweep: the steps' cubature points as weighted data with the output
+    covariance sum (not with exact Psi-statistics, whose local phase takes the inputs itself), the kernel, the noise and the
+    prior.  Returns the engine."""
     W = _mean_W(q_w)
     d_out = W.shape[0]
     sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
-    exact = is_exact(meta.method)
-    if exact:
+    if is_exact(meta.method):
         # the statistics in closed form (SGPDevice.sweep_local_psi): the setters first, the local phase reads them
         require_se(kernel_family(meta.kernel))
         eng = _engine(meta, 1, d_out)
@@ -106,7 +105,15 @@ def sweep(meta: MultiSGPMeta, q_outs: Sequence, q_ins: Sequence, q_w, q_theta: P
         eng.set_prior_precision(prior.W @ prior.m, prior.W)
     else:
         raise TypeError(f"unsupported prior type {type(prior).__name__}")
-    if exact:
+    return eng
+
+
+def sweep(meta: MultiSGPMeta, q_outs: Sequence, q_ins: Sequence, q_w, q_theta: PointMass, prior, E_logdet_W=None):
+    """One VMP update of q(v) from all steps' `:v` messages (GPnode/MultiSGPnode.jl:290-328) folded with the prior.
+    Returns the marginal MvNormalMeanCovariance; the Wishart statistics and the energy are then available through
+    `rule_w_summed` / `average_energy_summed`."""
+    eng = load(meta, q_outs, q_ins, q_w, q_theta, prior, E_logdet_W)
+    if is_exact(meta.method):
         means, covs = gaussian_inputs(q_ins, np.asarray(meta.Xu).shape[1])
         Y = np.stack([np.asarray(q.mean(), dtype=np.float64).ravel() for q in q_outs])
         eng.sweep_local_psi(means, covs, Y)

@@ -582,6 +582,58 @@ def _wishart_kl(nu, invS, nu0, invS0) -> float:
                  + 0.5 * (nu - nu0) * (wishart_mean_logdet(nu, invS) - d * np.log(2.0) + np.linalg.slogdet(invS)[1]))
 
 
+def vmp_regression_multi(theta, X, Y, meta, *, iterations=10, v_prior_var=50.0, w_prior=None, device_paced=True, free_energy=True,
+                         q_ins=None):
+    """`infer(iterations = K, free_energy = true)` of multi-output regression with a learned full noise precision:
+        y_t ~ MultiSGP(x_t, v, W, theta),   v ~ N(0, v_prior_var I),   W ~ Wishart(nu0, invscale^-1),   mean field q(v) q(W).
+    theta is raw, as meta.kernel maps it; Y is (T, d), d = 2 .. 4; w_prior = (nu0, inverse scale), default (d + 2, I); q(W) starts at
+    its prior.  The inputs are the rows of X as PointMass, or q_ins: Gaussians held fixed, which enter through meta.method's cubature
+    points as weighted data (steps 4-5 of `vmp_gpssm` at a held q(x)).  Per iteration: q(v) from one sweep at mean(q_W) and
+    E[logdet W], then q(W) = Wishart(nu0 + T, prior + sum_t (I1_t + I2_t)); the free energy is the summed average energy at the new
+    q(W) plus KL(q(v) || p(v)) and KL(q(W) || p(W)).
+    device_paced: one `SGPDevice.vmp_run_w` (sgp_vmp_run_w), the host waits once.  Otherwise the host-paced loop of existing calls:
+    `multisgp.sweep`, `multisgp.rule_w_summed`, `multisgp.average_energy_summed` and the KL helpers of this module.
+    Returns (q_v, q_W) or, with free_energy, (q_v, q_W, free energies [iterations])."""
+    from . import multisgp as MS
+    from .distributions import MvNormalWeightedMeanPrecision, PointMass, WishartFast
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim != 2 or not 2 <= Y.shape[1] <= 4:
+        raise ValueError("vmp_regression_multi: Y must be (T, d) with d = 2 .. 4")
+    T, d = Y.shape
+    if q_ins is None:
+        q_ins = [PointMass(x) for x in np.asarray(X, dtype=np.float64).reshape(T, -1)]
+    if len(q_ins) != T:
+        raise ValueError(f"vmp_regression_multi: {len(q_ins)} inputs for {T} targets")
+    q_outs = [PointMass(y) for y in Y]
+    nu0, R0 = (d + 2.0, np.eye(d)) if w_prior is None else (float(w_prior[0]), np.asarray(w_prior[1], dtype=np.float64))
+    Q = d * np.asarray(meta.Xu).shape[0]
+    q_theta = PointMass(np.asarray(theta, dtype=np.float64))
+    v_prior = MvNormalWeightedMeanPrecision(np.zeros(Q), np.eye(Q) / v_prior_var)
+    q_w = WishartFast(nu0, R0)
+    q_v = MvNormalMeanCovariance(np.zeros(Q), v_prior_var * np.eye(Q))   # (iterations = 0: the prior, nothing is swept)
+    if int(iterations) <= 0:
+        return (q_v, q_w, np.zeros(0)) if free_energy else (q_v, q_w)
+    if device_paced:
+        eng = MS.load(meta, q_outs, q_ins, q_w, q_theta, v_prior, E_logdet_W=wishart_mean_logdet(nu0, R0))
+        trace, _, q_w, _, _ = eng.vmp_run_w(int(iterations), wishart_prior=(nu0, R0))
+        mu, Sigma, _ = eng.posterior(want_uv=False)
+        q_v = MvNormalMeanCovariance(mu, Sigma)
+    else:
+        trace = []
+        for _ in range(int(iterations)):
+            W_old, el_old = q_w.mean(), wishart_mean_logdet(q_w.nu, q_w.invS)
+            q_v = MS.sweep(meta, q_outs, q_ins, q_w, q_theta, v_prior, E_logdet_W=el_old)
+            q_w = MS.rule_w_summed(meta, nu0, R0, T)
+            if free_energy:
+                energy_old = MS.average_energy_summed(meta)   # at the q(W) the sweep ran at
+                # the node energy is linear in (W_bar, E[logdet W]): moved to the NEW q(W), where sgp_vmp_run_w evaluates it
+                S = q_w.invS - R0
+                energy = energy_old + 0.5 * (np.sum((q_w.mean() - W_old) * S) - T * (wishart_mean_logdet(q_w.nu, q_w.invS) - el_old))
+                trace.append(energy + _gauss_kl(q_v.m, q_v.S, np.zeros(Q), v_prior_var * np.eye(Q)) + _wishart_kl(q_w.nu, q_w.invS, nu0, R0))
+        trace = np.array(trace)
+    return (q_v, q_w, trace) if free_energy else (q_v, q_w)
+
+
 def gpssm_host_energy(y, Pobs, q_x, q_v, q_w, x0_prior, v_prior_var, w_prior) -> float:
     """The host's share of the GP-SSM free energy: the observation factors' average energies, KL(q(x_0) || prior), minus the
     entropies of q(x_1..T), KL(q(v) || N(0, v_prior_var I)) and KL(q(W) || prior).  The MultiSGP factors' average energies

@@ -710,6 +710,42 @@ int sgp_vmp_run_t(sgp_handle* h, double nu, double* tau_rate /* n, in/out, may b
                   const double* gamma_prior /* 2 */, double* gamma /* 2, in/out */, double tol, double* values /* iterations, may be NULL */,
                   double* terms /* 4 x iterations column-major, may be NULL */, int64_t* counts /* 2, may be NULL */);
 
+/* ---- device-paced VMP iterations of MultiSGP with Wishart noise ----
+ * sgp_vmp_run for the second node, `y_t ~ MultiSGP(x_t, v, W, theta), W ~ Wishart(nu0, R0^-1)` with the mean field q(v) q(W)
+ * (GPnode/MultiSGPnode.jl:290-328, 367-444, 544-632; experiments/Pendulum_Wishart_2d.ipynb: infer(iterations = 10, free_energy =
+ * true)), on a handle with d_out = d in {2, 3, 4}.  It works on the resident data of the last sgp_set_data -- the points, optionally
+ * pt_weight and n_nodes (the cubature points of a held q(x), as multisgp.sweep loads them) and optionally sgp_set_output_cov_sum --
+ * at the Xu, kernel (any family), jitter and prior the setters left.  q(W) = (nu, R) enters iteration k, R the d x d inverse scale
+ * (distributions.WishartFast): W_bar = nu R^-1, E[logdet W] = sum_{i<d} psi((nu - i) / 2) + d log 2 - log|R|.  With SGP_VMP_HOLD_W,
+ * W_bar and E[logdet W] are those of the last sgp_set_noise and never change; wishart_prior and wishart are ignored and may be NULL.
+ *   1. q(v): iteration 0 is a full sweep, later ones run over the resident statistics (what SGP_SWEEP_REUSED does): the statistics
+ *      are formed once per call, on every handle, with or without SGP_FLAG_REUSE_STATS;
+ *   2. q(W) <- (nu0 + N, R0 + S), S = sum_t (I1_t + I2_t) of that sweep (what sgp_get_wishart_invscale returns), N = SGP_S_N, the
+ *      number of factor nodes; the new W_bar (W_bar[i,j] and W_bar[j,i] the same double) and E[logdet W] are the next sweep's noise;
+ *   3. terms[4 k ..] = { 1/2 [tr(W_bar S) - N E[logdet W] + N d log 2 pi] at the NEW q(W), the summed @average_energy;  0 (the
+ *      likelihood slot of sgp_vmp_run's layout);  KL(q(v) || p(v)) as in sgp_vmp_run;  KL(q(W) || p(W)) = 1/2 nu0 (log|R| - log|R0|)
+ *      + 1/2 nu (tr(R0 R^-1) - d) + lnGamma_d(nu0 / 2) - lnGamma_d(nu / 2) + 1/2 (nu - nu0) sum_i psi((nu - i) / 2)  (0 with HOLD_W) },
+ *      values[k] = their sum in that order;
+ *   4. the tol stop and the failure stop of sgp_vmp_run, and one more failure: an R0 + S that is not positive definite to rounding
+ *      stops the run like a failed factorisation -- the call returns the failing leading minor, counts[1] = -minor, values[k ..] are
+ *      NaN and q(W) stays the one that entered k.
+ * Afterwards the handle is what the host-paced sequence (sgp_sweep, sgp_get_wishart_invscale, sgp_set_noise) leaves: the noise is
+ * W_bar with E[logdet W] of the final q(W), the getters give the last completed iteration's sweep, sgp_sweep_kind's `last` is FULL
+ * after one iteration and REUSED after more, on a SGP_FLAG_REUSE_STATS handle the statistics stay reusable, and wishart receives
+ * (nu, R).  All sums run in fixed orders without atomics: identical calls agree bitwise, and with tol = 0 K iterations equal k then
+ * K - k through wishart bitwise.
+ * SGP_ERR_ARG: d_out = 1; no data, kernel or inducing inputs; data set with y_var; exact-Psi statistics resident (sgp_sweep_local_psi:
+ * a run over closed-form statistics is left for a later change); an open sgp_train_* run; an installed all-reduce hook;
+ * iterations < 0; unknown flags; a negative or NaN tol; without HOLD_W: a NULL wishart_prior or wishart, degrees of freedom that are
+ * not finite or not > d - 1, a non-finite entry, an inverse scale that is not symmetric (|A_ij - A_ji| <= 1e-9 sqrt(A_ii A_jj)) or
+ * not positive definite (checked on the host).  iterations = 0 returns 0 with nothing changed, behind every refusal. */
+enum { SGP_VMP_W_TERMS = 4 };
+int sgp_vmp_run_w(sgp_handle* h, int32_t flags /* 0 | SGP_VMP_HOLD_W */, int32_t iterations,
+                  const double* wishart_prior /* 1 + d*d: nu0, inverse scale R0 (d x d column-major) */,
+                  double* wishart /* 1 + d*d, in/out: q(W) = (nu, R) */,
+                  double tol, double* values /* iterations, may be NULL */,
+                  double* terms /* 4 x iterations column-major, may be NULL */, int64_t* counts /* 2, may be NULL */);
+
 /* ---- exact-Psi input messages: a node's energy and its derivatives in the mean and covariance of its Gaussian input ----
  * With q(v), W, G and s_t as for sgp_theta_objective_psi (SGP_KERNEL_SE only, d_out = 1 .. 4, D <= 8) and x_t ~ N(m_t, S_t), the part of
  * node t's average energy that depends on its input is

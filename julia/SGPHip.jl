@@ -961,4 +961,24 @@ function multisgp_sweep!(meta::HipMultiSGPMeta, q_outs, q_ins, q_w, q_θ::PointM
     return MvNormalMeanCovariance(μ, Σ), wishart_invscale(h), scalars(h)[3]
 end
 
+# ---- device-paced VMP iterations of MultiSGP with Wishart noise (sgp_vmp_run_w): y_t ~ MultiSGP(x_t, v, W, θ), W ~ Wishart, on the
+# d_out = 2:4 handle of a HipMultiSGPMeta, over the resident data, kernel and prior (what multisgp_sweep! loaded, for instance).
+# W0 = (ν0, R0) the prior and W = (ν, R) the q(W) entering the run (default the prior), R the d × d inverse scale (WishartFast);
+# nothing with hold_w = true, which keeps the last set_noise.  Returns (values, terms, (ν, R), iterations_done, converged);
+# PosDefException(k) when K_uu, Λ or R0 + S failed.
+function vmp_run_w!(meta::HipMultiSGPMeta, iterations::Integer; W0 = nothing, W = nothing, tol = 0.0, hold_w::Bool = false)
+    h = meta.handle
+    hold_w || W0 !== nothing || throw(ArgumentError("vmp_run_w!: W0 = (ν0, R0) is required without hold_w"))
+    pack(q) = vcat(Float64(q[1]), vec(Matrix{Float64}(q[2])))        # (Julia's matrices are column-major already)
+    p0 = hold_w ? nothing : pack(W0)
+    q = hold_w ? nothing : (W === nothing ? copy(p0) : pack(W))
+    values = fill(NaN, max(iterations, 0)); terms = fill(NaN, 4, max(iterations, 0)); counts = zeros(Int64, 2)
+    check(ccall((:sgp_vmp_run_w, LIB), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, hold_w ? 1 : 0, iterations, p0 === nothing ? C_NULL : p0, q === nothing ? C_NULL : q, tol, values, terms, counts),
+          h.ptr)
+    d = q === nothing ? 0 : isqrt(length(q) - 1)
+    return values, terms, q === nothing ? nothing : (q[1], reshape(q[2:end], d, d)), Int(counts[1]), counts[2] == 1
+end
+
 end # module

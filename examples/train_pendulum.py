@@ -55,11 +55,11 @@ def inducing_inputs():
 
 
 def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cubature", theta_psi="cubature",
-        in_psi="cubature", forecast=0):
+        in_psi="cubature", forecast=0, rollout_paths=0):
     from gaussianprocessnode_amd.cubature import srcubature
     from gaussianprocessnode_amd.meta import SMSE, MultiSGPMeta, SEARDKernel, softplus
     from gaussianprocessnode_amd.distributions import PointMass
-    from gaussianprocessnode_amd.train import forecast_gpssm, perform_inference_gpssm, vmp_gpssm
+    from gaussianprocessnode_amd.train import forecast_gpssm, perform_inference_gpssm, rollout_gpssm_paths, vmp_gpssm
 
     states, obs, P = generate(N, seed)
     x_true, y = states[:nodes], obs[:nodes]
@@ -80,6 +80,12 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
         if forecast > 0:                                      # where will the state be in k steps: closed form, no cubature points
             f_mean, f_cov = forecast_gpssm(q_x[-1], forecast, q_v, q_w, PointMass(theta), meta)
             roll = {"mean": f_mean[:, 0].tolist(), "std": np.sqrt(np.einsum("kii->ki", f_cov[:, 0])).tolist()}
+        paths = None
+        if rollout_paths > 0:                                 # the same horizon along sampled dynamics: one function per path
+            steps = forecast if forecast > 0 else 10
+            traj = rollout_gpssm_paths(q_x[-1], steps, rollout_paths, np.random.default_rng(seed), q_v=q_v, q_w=q_w,
+                                       q_theta=PointMass(theta), meta=meta)
+            paths = {"mean": traj[1:].mean(axis=1).tolist(), "std": traj[1:].std(axis=1).tolist(), "paths": rollout_paths}
     finally:
         for eng in (meta.engine, getattr(meta, "_aux_engine_out", None)):
             if eng is not None:
@@ -87,6 +93,9 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
     if roll is not None:
         for k, (mk, sk) in enumerate(zip(roll["mean"], roll["std"])):
             print(f"forecast step {k + 1}: mean {np.round(mk, 4).tolist()} std {np.round(sk, 4).tolist()}")
+    if paths is not None:
+        for k, (mk, sk) in enumerate(zip(paths["mean"], paths["std"])):
+            print(f"rollout step {k + 1} over {rollout_paths} sampled paths: mean {np.round(mk, 4).tolist()} std {np.round(sk, 4).tolist()}")
     est = np.stack([q.m for q in q_x[1:]])
     return {
         "experiment": "pendulum GP-SSM PerformInference (experiments/Pendulum_Wishart_2d.ipynb)",
@@ -100,6 +109,7 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
         "free_energy_epochs": [float(v) for v in fe],
         "mean_W": np.asarray(q_w.mean()).tolist(),
         "forecast": roll,
+        "rollout_paths": paths,
         "reference": {"train_seconds": 1615.249575, "smoothing_seconds": 15.0, "smse": [0.005454764265443909, 0.0010773936260490339],
                       "note": "other data (Julia's MersenneTwister(124)), hardware unstated"},
     }
@@ -121,6 +131,9 @@ if __name__ == "__main__":
     ap.add_argument("--forecast", type=int, default=0, metavar="K",
                     help="after smoothing, roll q(x_T) out K steps in closed form (sgp_psi_predict) and print the per-step means and "
                          "standard deviations")
+    ap.add_argument("--rollout-paths", type=int, default=0, metavar="K",
+                    help="after smoothing, draw K dynamics functions (pathwise samples, sgp_sample_path) and roll each out from its "
+                         "own draw of q(x_T) over the --forecast horizon (10 steps without it); prints the per-step mean and spread")
     args = ap.parse_args()
     print(json.dumps(run(args.epochs, args.nodes, args.seed, not args.host_paced, psi=args.psi, theta_psi=args.theta_psi,
-                         in_psi=args.in_psi, forecast=args.forecast)))
+                         in_psi=args.in_psi, forecast=args.forecast, rollout_paths=args.rollout_paths)))

@@ -37,7 +37,7 @@ EXPORTS = [
     "sgp_theta_objective_psi", "sgp_theta_descend_psi", "sgp_psi_in_grad", "sgp_psi_predict",
     "sgp_theta_objective_xu", "sgp_theta_objective_psi_xu", "sgp_inducing_descend", "sgp_inducing_descend_psi",
     "sgp_sweep_plan", "sgp_select_inducing", "sgp_predict_joint", "sgp_sample_f", "sgp_vmp_run",
-    "sgp_vmp_run_t", "sgp_vmp_run_w",
+    "sgp_vmp_run_t", "sgp_vmp_run_w", "sgp_sample_path",
 ]
 # sgp_sweep_plan's bits (SGP_PLAN_* of include/sgp_hip.h), by name
 PLAN_BITS = {"overlapped": 1, "pack": 2, "events": 4, "join_word": 8, "kuu_interleaved": 16, "stats_first": 32, "gate_side": 64,
@@ -61,7 +61,9 @@ SGP_TIME_GROUP0 = 100
 SGP_TIME_QUADFORM = 120
 SGP_PREDICT_NOISE = 1         # sgp_predict_var: add the observation noise W^-1
 SGP_JOINT_MAX_ROWS = 8192     # sgp_predict_joint / sgp_sample_f: ns * d_out
-SGP_DESCEND_THETA, SGP_DESCEND_XU = 1, 2      # sgp_inducing_descend[_psi]: what the optimised vector holds
+SGP_PATH_MAX_FEATURES = 16384  # sgp_sample_path: L
+SGP_PATH_MAX_COLUMNS = 2097152  # sgp_sample_path: d_out * n_samples
+SGP_DESCEND_THETA, SGP_DESCEND_XU = 1, 2     # sgp_inducing_descend[_psi]: what the optimised vector holds
 SGP_VMP_GAUSSIAN, SGP_VMP_PROBIT = 0, 1       # sgp_vmp_run: likelihood
 SGP_VMP_HOLD_W = 1                            # sgp_vmp_run, sgp_vmp_run_t, sgp_vmp_run_w: flags
 SGP_VMP_W_TERMS = 4                           # sgp_vmp_run_w: entries of `terms` per iteration
@@ -144,6 +146,8 @@ def load(build_if_missing: bool = True, variant=None):
     lib.sgp_predict_var.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int32, dp, dp]
     lib.sgp_predict_joint.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int32, dp, dp]
     lib.sgp_sample_f.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int32, C.c_double, dp, C.c_int64, dp, dp, C.POINTER(C.c_int64)]
+    lib.sgp_sample_path.argtypes = [vp, dp, C.c_int64, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int64, C.c_int32, dp,
+                                    C.POINTER(C.c_int64)]
     lib.sgp_in_message.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64), C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp]
     lib.sgp_in_message_grad.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64), C.c_int64, dp, dp, dp, dp, dp, dp]
     lib.sgp_out_message.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64), C.c_int64, dp, dp, dp, dp]

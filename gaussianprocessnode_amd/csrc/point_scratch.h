@@ -1,6 +1,6 @@
 // Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
 // sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad,
-// sgp_psi_predict, sgp_theta_objective_xu, sgp_theta_objective_psi_xu, sgp_inducing_descend, sgp_inducing_descend_psi, sgp_predict_joint, sgp_sample_f).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp (layout_joint: tools/joint_scratch_check.cpp).
+// sgp_psi_predict, sgp_theta_objective_xu, sgp_theta_objective_psi_xu, sgp_inducing_descend, sgp_inducing_descend_psi, sgp_predict_joint, sgp_sample_f, sgp_sample_path).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp (layout_joint: tools/joint_scratch_check.cpp; layout_path: tools/path_scratch_check.cpp).
 #pragma once
 
 #include <cstddef>
@@ -93,6 +93,43 @@ static inline void layout_joint(Carver& c, const PointShape& p, size_t n_samples
     b->Cinfo = c.take<int>(n_samples ? 1 : 0);
     b->Eps = c.take<double>(rows * n_samples);
     b->Samples = c.take<double>(rows * n_samples);
+}
+
+// sgp_sample_path (p.n = the test points, p.chunk points per chunk; L features, cols = d_out n_samples sample columns): of the
+// panel's pieces the factors, the explicit mu_v and the two factorisations' scratch with their status words alone (the per-chunk
+// pieces of the panel stay null: no K(Xu, X*) is kept), Sigma_v's factor, the caller's frequencies (a row per feature, padded to DP
+// coordinates), phases, feature weights and normals, the scaled inducing inputs padded alike, the draws v = mu_v + L_S eps_v ([n_samples][Qp]), Phi_u w, W_K Phi_u w and the coefficients C ([cols][Mp] each), and one
+// chunk of points with its result ([cols][chunk]).  Nothing grows with p.n.
+static inline int path_padded_dim(int D) { return (D + 7) / 8 * 8; }     // DP: k_path_eval's coordinate groups (PATH_DG)
+struct PathScratch : PanelScratch {
+    double* LS;                     // Sigma_v padded with the identity -> its factor L_S
+    double *Omega, *Phase;          // [L][DP] (zero from D on), [L]
+    double* XuP;                    // the scaled inducing inputs, [M][DP]
+    double *FeatW, *Eps;            // [cols][L], [n_samples][Q]
+    double* V;                      // [n_samples][Qp]
+    double *Bu, *Y, *C;             // [cols][Mp] each
+    double *Xs, *Out;               // per chunk: X* ([point][D]) and the samples ([cols][chunk])
+};
+static inline void layout_path(Carver& c, const PointShape& p, size_t L, size_t n_samples, PathScratch* b) {
+    const size_t cols = (size_t)p.dout * n_samples, Q = (size_t)p.Qp;
+    b->Kc = b->Pa = b->Pb = b->Kmu = b->MeanC = nullptr;
+    b->Kuu = c.take<double>((size_t)p.Mp * p.Mp);
+    b->Wk = c.take<double>((size_t)p.Mp * p.Mp);
+    b->MuX = c.take<double>(Q);
+    b->Pscr = c.take<double>(2 * (size_t)p.potrf_scratch);
+    b->Info = c.take<int>(2);
+    b->LS = c.take<double>(Q * Q);
+    b->Omega = c.take<double>(L * path_padded_dim(p.D));
+    b->Phase = c.take<double>(L);
+    b->XuP = c.take<double>((size_t)p.Mp * path_padded_dim(p.D));
+    b->FeatW = c.take<double>(cols * L);
+    b->Eps = c.take<double>(n_samples * Q);
+    b->V = c.take<double>(n_samples * Q);
+    b->Bu = c.take<double>(cols * p.Mp);
+    b->Y = c.take<double>(cols * p.Mp);
+    b->C = c.take<double>(cols * p.Mp);
+    b->Xs = c.take<double>((size_t)p.chunk * p.D);
+    b->Out = c.take<double>(cols * (size_t)p.chunk);
 }
 
 // what sgp_in_message and sgp_in_message_grad share: the panel, S and its factor, an explicit Sigma_v and what the logpdf of all

@@ -4960,3 +4960,97 @@ static int dense_common(int32_t device, const double* A, int32_t n, double* out,
 
 extern "C" int sgp_potrf(int32_t device, const double* A, int32_t n, double* L) { return dense_common(device, A, n, L, false); }
 extern "C" int sgp_potri(int32_t device, const double* A, int32_t n, double* Ainv) { return dense_common(device, A, n, Ainv, true); }
+
+// ------------------------------------------------------------------------------------------------
+// Pathwise (Matheron) posterior function samples (include/sgp_hip.h; kernels: k_path_tri, k_path_coef, k_path_eval in
+// sgp_kernels.hip.h).  As sgp_sample_f: blocking, K_uu, W_K = L_K^-1 and the factor of Sigma_v formed at the CURRENT kernel parameters
+// in call scratch, nothing the sweep keeps written (only the parameter mirror dXusK / dParamsK, as sgp_predict), a reader without a
+// row in the table above StatsRecord.  The coefficients of all d_out n_samples sample columns are formed once -- v = mu_v + L_S eps_v,
+// Phi_u w by k_path_eval over the inducing inputs, W_K' (W_K Phi_u w) -- and the test points then go through k_path_eval in chunks,
+// each chunk's result copied out behind it: no piece of the scratch grows with ns.  (Last in this file: the kernels are templates
+// and are emitted where they are first launched, behind everything the other entry points launch.)
+// ------------------------------------------------------------------------------------------------
+template <int FAM>
+static void launch_path_eval(const sgp_handle* h, hipStream_t s, const PathScratch& b, const double* dX, int64_t n, int L, int M,
+                             int64_t J, double* dOut, int64_t ldo, double* dScaled = nullptr) {
+    hipLaunchKernelGGL(k_path_eval<FAM>, dim3((unsigned)((n + TB - 1) / TB), (unsigned)((J + TB - 1) / TB)), dim3(256), 0, s, dX, n,
+                       (const double*)b.Omega, (const double*)b.Phase, (const double*)b.FeatW, L, (const double*)b.XuP,
+                       (const double*)b.C, M, h->Mp, (const Params*)h->dParamsK, h->D, path_padded_dim(h->D), J, dOut, ldo, dScaled);
+}
+static_assert(PATH_DG == 8, "path_padded_dim (point_scratch.h) pads to k_path_eval's coordinate groups");
+
+extern "C" int sgp_sample_path(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
+                               const double* omega, const double* phase, int32_t L, const double* feat_w, const double* eps_v,
+                               int64_t n_samples, int32_t flags, double* samples, int64_t* info) {
+    const char* name = "sgp_sample_path";
+    if (!h || ns < 0) return fail(h, SGP_ERR_ARG, "sgp_sample_path: bad argument");
+    if (flags != 0) return fail(h, SGP_ERR_ARG, "sgp_sample_path: unknown flags");
+    if (int rc = point_call_ready(h, name, mu_v, Sigma_v)) return rc;
+    if (ns == 0) return 0;
+    if (!Xstar || !samples) return refuse(h, name, "null Xstar or samples");
+    if (!omega || !phase || !feat_w || !eps_v) return refuse(h, name, "null omega, phase, feat_w or eps_v");
+    if (L < 1 || L > SGP_PATH_MAX_FEATURES) return refuse(h, name, "L must lie in 1 .. SGP_PATH_MAX_FEATURES (16384)");
+    if (n_samples < 1) return refuse(h, name, "need n_samples >= 1");
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, TQ = h->TQ;
+    if (n_samples > SGP_PATH_MAX_COLUMNS / dout) return refuse(h, name, "d_out * n_samples exceeds SGP_PATH_MAX_COLUMNS (2097152)");
+    const int64_t J = (int64_t)dout * n_samples;
+    if (!all_finite(Xstar, (size_t)ns * D)) return refuse(h, name, "Xstar must be finite");
+    if (!all_finite(omega, (size_t)L * D) || !all_finite(phase, (size_t)L)) return refuse(h, name, "omega and phase must be finite");
+    if (!all_finite(feat_w, (size_t)L * J) || !all_finite(eps_v, (size_t)Q * n_samples))
+        return refuse(h, name, "feat_w and eps_v must be finite");
+    if (int wrc = point_call_wait(h, mu_v)) return wrc;
+    hipStream_t s = h->own;
+    const PointShape shape = point_shape(h, (int64_t)D + J, ns, 0);
+    const int64_t chunk = shape.chunk;
+    PathScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_path(c, shape, (size_t)L, (size_t)n_samples, &b); })) return crc;
+    // the last sweep's Sigma_v is copied: its factor is formed in place
+    const double *dMu, *dSig;
+    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.LS, &dMu, &dSig)) return rc;
+    if (!mu_v) hipLaunchKernelGGL(k_pad_square, dim3((unsigned)(((size_t)Qp * Qp + 255) / 256)), dim3(256), 0, s, dSig, Qp, b.LS, Q, Qp);
+    {   // feature l's D frequencies, zero-padded to DP
+        const int DP = path_padded_dim(D);
+        std::vector<double> om((size_t)L * DP, 0.0);
+        for (int l = 0; l < L; ++l) memcpy(&om[(size_t)l * DP], omega + (size_t)l * D, sizeof(double) * D);
+        HIPCHK(h, hipMemcpy(b.Omega, om.data(), sizeof(double) * om.size(), hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, hipMemcpy(b.Phase, phase, sizeof(double) * L, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.FeatW, feat_w, sizeof(double) * L * J, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(b.Eps, eps_v, sizeof(double) * Q * n_samples, hipMemcpyHostToDevice));
+    if (int rc = factor_begin(h, s, b)) return rc;
+    if (info) info[0] = info[1] = 0;
+    if (int frc = factor_finish(h, s, b, b.LS, Qp, TQ, Q, "Sigma_v")) {
+        int two[2] = {0, 0};
+        if (info && frc > 0 && hipMemcpy(two, b.Info, sizeof two, hipMemcpyDeviceToHost) == hipSuccess) {
+            info[0] = two[0] > 0 ? two[0] : 0;
+            info[1] = two[1] > 0 ? two[1] : 0;
+        }
+        return frc;
+    }
+    // the coefficients: v = mu_v + L_S eps_v; Phi_u w (the inducing inputs through the evaluation kernel, feature part alone);
+    // W_K (Phi_u w); C = v - W_K' (W_K Phi_u w)
+    hipLaunchKernelGGL(k_path_tri<true>, dim3((unsigned)n_samples, (unsigned)((Q + 255) / 256)), dim3(256), 0, s, (const double*)b.LS, Qp, Q,
+                       (const double*)b.Eps, (int64_t)Q, dMu, b.V, (int64_t)Qp);
+    by_family(h->family, [&](auto F) { launch_path_eval<decltype(F)::value>(h, s, b, h->dXu, M, L, 0, J, b.Bu, Mp, b.XuP); });
+    hipLaunchKernelGGL(k_path_tri<false>, dim3((unsigned)J, (unsigned)((M + 255) / 256)), dim3(256), 0, s, (const double*)b.Wk, Mp, M,
+                       (const double*)b.Bu, (int64_t)Mp, (const double*)nullptr, b.Y, (int64_t)Mp);
+    const dim3 coef_grid((unsigned)J, (unsigned)((M + 3) / 4));
+    if (dout == 1)
+        hipLaunchKernelGGL(k_path_coef<false>, coef_grid, dim3(256), 0, s, (const double*)b.Wk, (const double*)b.Y, (const double*)b.V,
+                           b.C, M, Mp, Qp, dout);
+    else
+        hipLaunchKernelGGL(k_path_coef<true>, coef_grid, dim3(256), 0, s, (const double*)b.Wk, (const double*)b.Y, (const double*)b.V,
+                           b.C, M, Mp, Qp, dout);
+    HIPCHK(h, hipGetLastError());
+    for (int64_t s0 = 0; s0 < ns; s0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, ns - s0);
+        HIPCHK(h, hipMemcpyAsync(b.Xs, Xstar + (size_t)s0 * D, sizeof(double) * nc * D, hipMemcpyHostToDevice, s));
+        by_family(h->family, [&](auto F) { launch_path_eval<decltype(F)::value>(h, s, b, b.Xs, nc, L, M, J, b.Out, chunk); });
+        HIPCHK(h, hipGetLastError());
+        // the chunk's [J][chunk] on the device -> rows s0 .. of every column c of the ns x J column-major result
+        HIPCHK(h, hipMemcpy2DAsync(samples + s0, sizeof(double) * ns, b.Out, sizeof(double) * chunk, sizeof(double) * nc, (size_t)J,
+                                   hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));             // (the next chunk's upload reuses the scratch; pageable host memory)
+    }
+    return 0;
+}

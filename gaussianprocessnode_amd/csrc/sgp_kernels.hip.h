@@ -6768,4 +6768,161 @@ __global__ void __launch_bounds__(256, 2) k_tri_apply(const double* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Pathwise (Matheron) posterior function samples (sgp_sample_path).  With the caller's L random Fourier features
+//   phi_l(x) = sqrt(2 sigma2 / L) cos(phase_l + sum_d omega[d, l] x_d / ell_d),
+// feature weights w (L x J, column c = i + d_out j: output i of sample j), a posterior draw v^(j) = mu_v + L_S eps_v[:, j] of the
+// inducing variable and K = K_uu + jitter I = L_K L_K', W_K = L_K^-1, sample column c at a point x is
+//   f_c(x) = sum_l w[l, c] phi_l(x) + k(Xu, x)' C[:, c],    C[:, c] = v_i^(j) - W_K' W_K Phi_u w[:, c],   Phi_u[m, l] = phi_l(Xu_m).
+// k_path_tri applies a lower factor to many columns (L_S to eps_v; W_K to Phi_u w), k_path_coef closes C with W_K', and k_path_eval
+// evaluates f at a block of points: it is also what forms Phi_u w (the inducing inputs as points, no Gram part).  No atomics; every
+// sum runs in an order fixed by (L, M, d_out), and a point's values depend on nothing but the point, so that a sample is a function.
+// ------------------------------------------------------------------------------------------------
+// (All four are templates although two of them need no parameter for speed: a template kernel is emitted where it is first
+// launched, behind every kernel the sweep uses, whose places in the code object therefore stay what they were.)
+// Y[c][r] = (ADD ? add[r] : 0) + sum_{m <= r} F[r, m] X[c][m] for r < n: the lower-triangular F (column-major, leading dimension ld;
+// what lies above its diagonal is never read) times the columns of X, m ascending.  Thread (row r, column c = blockIdx.x): the rows
+// of a column of F are contiguous across a wavefront and X[c][m] is uniform.
+//   X : [columns][ldx];  Y : [columns][ldy]
+template <bool ADD>
+__global__ void __launch_bounds__(256) k_path_tri(const double* __restrict__ F, int ld, int n, const double* __restrict__ X,
+                                                  int64_t ldx, const double* __restrict__ add, double* __restrict__ Y, int64_t ldy) {
+    const int r = blockIdx.y * 256 + threadIdx.x;
+    if (r >= n) return;
+    const double* x = X + (size_t)blockIdx.x * ldx;
+    double acc = 0.0;
+    for (int m = 0; m <= r; ++m) acc = fma(F[(size_t)m * ld + r], x[m], acc);
+    Y[(size_t)blockIdx.x * ldy + r] = ADD ? add[r] + acc : acc;
+}
+
+// C[c][m] = V[j][i M + m] - sum_{r >= m} W_K[r, m] Y[c][r], c = i + d_out j = blockIdx.x: one wavefront per (m, c).  Lane t takes
+// r = m + t, m + t + 64, ... in ascending order and the 64 partial sums meet in a butterfly: an order fixed by M.
+// MULTI = false: d_out = 1, column c is sample c.
+//   Y, C : [J][Mp];  V : [n_samples][Qp]
+template <bool MULTI>
+__global__ void __launch_bounds__(256) k_path_coef(const double* __restrict__ Wk, const double* __restrict__ Y,
+                                                   const double* __restrict__ V, double* __restrict__ C, int M, int Mp, int Qp,
+                                                   int dout) {
+    const int lane = threadIdx.x & 63, m = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;                               // (the whole wavefront)
+    const int64_t c = blockIdx.x;
+    const double* w = Wk + (size_t)m * Mp;
+    const double* y = Y + (size_t)c * Mp;
+    double acc = 0.0;
+    for (int r = m + lane; r < M; r += 64) acc = fma(w[r], y[r], acc);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    const int64_t j = MULTI ? c / dout : c, i = MULTI ? c % dout : 0;
+    if (lane == 0) C[(size_t)c * Mp + m] = V[(size_t)j * Qp + (size_t)i * M + m] - acc;
+}
+
+// Workgroup (block of 64 points blockIdx.x, tile of 64 sample columns blockIdx.y): out[c][p] = f_c(x_p).  Lane t of every wavefront
+// keeps point t of the block in registers, scaled by 1 / ell once.  For the feature chunks of 64 in ascending order the workgroup
+// generates the tile phi[point][kk] into LDS -- wavefront w the features kk = w, w + 4, ..., so omega[:, l] and phase_l are uniform
+// and the cosine is taken once per (point, feature) whatever the number of columns -- beside the tile w[column][kk], and the matrix
+// cores add their product to the accumulator; then the same for the inducing points in chunks of 64 with k(Xu_m, x_p) (the families'
+// direct-difference sum over the scaled coordinates, d ascending) beside C[column][kk]; one store at the end.  The operand tiles
+// are k_joint_panel's ([row][kk] and [point][kk], stride KMS).  Edges: points from n on, features from L on, inducing points from M
+// on and columns from J on enter as zeros and are not stored.  M = 0: the feature part alone (XuP and C are not read).
+// scaled_out (or null): the first column tile also stores its points as it holds them -- scaled (k_prep_xu's product) and zero
+// from D on, [n][DP] -- which is how the pass over the inducing inputs leaves XuP for the passes over the test points.
+// The frequencies and the scaled inducing inputs come one row per feature / inducing point, zero-padded to DP = D rounded up to
+// PATH_DG coordinates, so that the uniform loads go a group at a time and the coordinate loops need no per-coordinate guard: a
+// padded coordinate adds fma(0, 0, t) = t.
+//   X : [n][D] unscaled;  Omega : [L][DP];  Wf : [J][L];  XuP : [M][DP] scaled;  C : [J][Mp];  out : [J][ldo], ldo >= n
+constexpr int PATH_DG = 8;
+static_assert(MAXD % PATH_DG == 0, "the padded coordinate count must not exceed MAXD");
+
+template <int FAM>
+__global__ void __launch_bounds__(256, 2) k_path_eval(const double* __restrict__ X, int64_t n, const double* __restrict__ Omega,
+                                                     const double* __restrict__ Phase, const double* __restrict__ Wf, int L,
+                                                     const double* __restrict__ XuP, const double* __restrict__ C, int M, int Mp,
+                                                     const Params* __restrict__ P, int D, int DP, int64_t J,
+                                                     double* __restrict__ out, int64_t ldo, double* __restrict__ scaled_out) {
+    __shared__ __attribute__((aligned(16))) double lds[2 * TB * KMS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wave >> 1, wc = wave & 1;
+    const int64_t n0 = (int64_t)blockIdx.x * TB, c0 = (int64_t)blockIdx.y * TB;
+    double* As = lds;                                 // [column][kk]
+    double* Bs = lds + TB * KMS;                      // [point][kk]
+    const bool live = n0 + lane < n;
+    if (tid < MAXD) Bs[tid] = P->inv_ell[tid];        // (through LDS: 32 uniform loads at once would take 64 scalar registers)
+    __syncthreads();
+    double x[MAXD];
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) x[d] = (d < D && live) ? X[(size_t)(n0 + lane) * D + d] * Bs[d] : 0.0;
+    if (scaled_out && blockIdx.y == 0 && wave == 0 && live) {
+#pragma unroll
+        for (int d = 0; d < MAXD; ++d)
+            if (d < DP) scaled_out[(size_t)(n0 + lane) * DP + d] = x[d];
+    }
+    const double s2 = P->sigma2, amp = sqrt(2.0 * s2 / (double)L);
+    Acc4 acc;
+    acc_zero(acc);
+#pragma unroll 1
+    for (int l0 = 0; l0 < L; l0 += TB) {
+        __syncthreads();                              // the previous tile pair has been consumed
+        for (int e = tid; e < TB * TB; e += 256) {
+            const int lo = e & 63, hi = e >> 6;
+            As[hi * KMS + lo] = (l0 + lo < L && c0 + hi < J) ? Wf[(size_t)(c0 + hi) * L + l0 + lo] : 0.0;
+        }
+#pragma unroll 1
+        for (int u = 0; u < TB / 4; ++u) {
+            const int kk = wave + 4 * u, l = l0 + kk;
+            double v = 0.0;
+            if (l < L) {
+                const double* om = Omega + (size_t)l * DP;             // (wave-uniform address)
+                double t = Phase[l];
+#pragma unroll
+                for (int d0 = 0; d0 < MAXD; d0 += PATH_DG)
+                    if (d0 < DP) {
+#pragma unroll
+                        for (int d = d0; d < d0 + PATH_DG; ++d) t = fma(om[d], x[d], t);
+                    }
+                v = live ? amp * cos(t) : 0.0;
+            }
+            Bs[lane * KMS + kk] = v;
+        }
+        __syncthreads();
+        joint_mma(acc, As, Bs, 1, KMS, lane, wr, wc);
+    }
+#pragma unroll 1
+    for (int m0 = 0; m0 < M; m0 += TB) {
+        __syncthreads();
+        for (int e = tid; e < TB * TB; e += 256) {
+            const int lo = e & 63, hi = e >> 6;
+            As[hi * KMS + lo] = (m0 + lo < M && c0 + hi < J) ? C[(size_t)(c0 + hi) * Mp + m0 + lo] : 0.0;
+        }
+#pragma unroll 1
+        for (int u = 0; u < TB / 4; ++u) {
+            const int kk = wave + 4 * u, m = m0 + kk;
+            double v = 0.0;
+            if (m < M) {
+                const double* um = XuP + (size_t)m * DP;               // (wave-uniform address)
+                double d2 = 0.0;
+#pragma unroll
+                for (int d0 = 0; d0 < MAXD; d0 += PATH_DG)
+                    if (d0 < DP) {
+#pragma unroll
+                        for (int d = d0; d < d0 + PATH_DG; ++d) { const double t = um[d] - x[d]; d2 = fma(t, t, d2); }
+                    }
+                v = live ? s2 * fam_kappa<FAM>(d2) : 0.0;
+            }
+            Bs[lane * KMS + kk] = v;
+        }
+        __syncthreads();
+        joint_mma(acc, As, Bs, 1, KMS, lane, wr, wc);
+    }
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj) {
+        const int64_t p = n0 + acc_col(lane, wc, tj);
+        if (p >= n) continue;
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t c = c0 + acc_row(lane, wr, ti, r);
+                if (c < J) out[(size_t)c * ldo + p] = acc.t[ti][tj][r];
+            }
+    }
+}
+
 }  // namespace sgp

@@ -347,6 +347,34 @@ class SGPDevice:
                                            ptr(mean), ptr(out), info), "sgp_sample_f")
         return (mean[0] if self.d_out == 1 else mean.T.copy()), out.T.copy()
 
+    def sample_path(self, Xstar, omega, phase, feat_w, eps_v, mu_v=None, Sigma_v=None):
+        """Pathwise (Matheron) posterior function samples at Xstar (sgp_sample_path): (ns, d_out, n_samples).  omega (D, L) and phase
+        (L,) are the random Fourier features of the current kernel on 1 / ell-scaled inputs (`train.path_features`), feat_w (L,
+        d_out, n_samples) and eps_v (Q, n_samples) the caller's standard normals.  The same four arrays give the same functions at
+        any other points, bitwise per point, and ns is not limited.  A K_uu or Sigma_v that is not positive definite raises
+        PosDefException with the failing minor."""
+        Xs = as_f64(np.reshape(Xstar, (-1, self.D)))
+        ns = Xs.shape[0]
+        om = np.asarray(omega, dtype=np.float64)
+        if om.ndim != 2 or om.shape[0] != self.D:
+            raise ValueError(f"sample_path: omega must be (D, L) = ({self.D}, L), got {om.shape}")
+        L = om.shape[1]
+        ph = as_f64(np.reshape(phase, (-1,)), (L,))
+        w = np.asarray(feat_w, dtype=np.float64)
+        if w.ndim == 2 and self.d_out == 1:
+            w = w[:, None, :]
+        if w.ndim != 3 or w.shape[:2] != (L, self.d_out):
+            raise ValueError(f"sample_path: feat_w must be (L, d_out, n_samples) = ({L}, {self.d_out}, n_samples), got {w.shape}")
+        n_samples = w.shape[2]
+        e = as_f64(np.asarray(eps_v, dtype=np.float64), (self.Q, n_samples))
+        mu, S = self._qv_args("sample_path", mu_v, Sigma_v)
+        out = np.empty((n_samples, self.d_out, ns))
+        info = (C.c_int64 * 2)()
+        om_cm, w_cm, e_cm = as_f64(om.T), as_f64(w.transpose(2, 1, 0)), as_f64(e.T)      # column-major D x L, L x d_out x n, Q x n
+        self._check(self._lib.sgp_sample_path(self._h, ptr(Xs), ns, ptr(mu), ptr(S), ptr(om_cm), ptr(ph), L, ptr(w_cm), ptr(e_cm),
+                                              n_samples, 0, ptr(out), info), "sgp_sample_path")
+        return out.transpose(2, 1, 0).copy()
+
     def _node_points(self, what: str, X, node_start):
         """The points of a node-batch call as the ABI takes them: (X (n, D) contiguous, n, node_start as int64, n_nodes)."""
         Xs = as_f64(np.reshape(X, (-1, self.D)))

@@ -833,6 +833,103 @@ def sample_posterior(meta, Xstar, n_samples, rng, *, q_v, q_theta, q_w=None, noi
     return np.asarray(mean).reshape(ns, d_out), smp.T.reshape(n_samples, d_out, ns).transpose(0, 2, 1).copy()
 
 
+MATERN_NU2 = {"matern12": 1, "matern32": 3, "matern52": 5}       # 2 nu of the Matern families
+
+
+def path_features(family, D, L, rng):
+    """Random Fourier features of a kernel family on 1 / ell-scaled inputs, as `SGPDevice.sample_path` takes them: (omega (D, L),
+    phase (L,)), so that E[phi(x)' phi(x')] = k(x, x') for phi_l(x) = sqrt(2 sigma2 / L) cos(phase_l + omega[:, l] . x / ell).  SE:
+    omega[:, l] ~ N(0, I).  Matern-nu: N(0, I) / sqrt(g_l / (2 nu)) with one g_l ~ chi2(2 nu) per feature -- the multivariate
+    Student-t with 2 nu degrees of freedom, the spectral measure of the families as `sgp_set_kernel_family` defines them.  phase ~
+    U[0, 2 pi).  Drawn from `rng` in the order omega's normals, g, phase."""
+    from ._lib import family_id, KERNEL_FAMILIES
+    name = {v: k for k, v in KERNEL_FAMILIES.items()}[family if isinstance(family, (int, np.integer)) else family_id(family)]
+    D, L = int(D), int(L)
+    omega = rng.standard_normal((D, L))
+    if name != "se":
+        nu2 = MATERN_NU2[name]
+        omega = omega / np.sqrt(rng.chisquare(nu2, L) / nu2)
+    return omega, rng.uniform(0.0, 2.0 * np.pi, L)
+
+
+def _path_engine(meta, q_v, q_theta):
+    """(engine at kernel(q_theta), family, mu_v (Q,), Sigma_v (Q, Q), d_out) for the pathwise samplers"""
+    from . import multisgp as MS
+    from . import unisgp as US
+    from .meta import kernel_family, set_engine_kernel
+    M = np.asarray(meta.Xu).shape[0]
+    mu_v, Sigma_v = q_v.mean_cov()
+    mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
+    d_out = mu_v.size // M
+    eng = MS._engine(meta, 1, d_out) if isinstance(meta, MS.MultiSGPMeta) else US._engine(meta, 1)
+    sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+    family = kernel_family(meta.kernel)
+    set_engine_kernel(eng, sigma2, ell, meta.jitter, family)
+    return eng, family, mu_v, np.asarray(Sigma_v, dtype=np.float64), d_out
+
+
+def _noise_factor(meta, q_w, d_out, what):
+    """the lower factor of mean(q_w)^-1 (d_out x d_out)"""
+    from . import multisgp as MS
+    from . import unisgp as US
+    if q_w is None:
+        raise ValueError(f"{what}: noise=True needs q_w")
+    W = MS._mean_W(q_w) if isinstance(meta, MS.MultiSGPMeta) else np.array([[US._mean_w(q_w)]])
+    if W.shape != (d_out, d_out):
+        raise ValueError(f"{what}: mean(q_w) must be {d_out} x {d_out}, got {W.shape}")
+    return np.linalg.cholesky(np.linalg.inv(W))
+
+
+def sample_paths(meta, Xstar, n_samples, rng, *, q_v, q_theta, features=1024, q_w=None, noise=False):
+    """Whole functions from the posterior by pathwise (Matheron) sampling over `features` random Fourier features: n_samples draws
+    of the latent f (noise=True: of the observation, + mean(q_w)^-1 noise per point, added on the host) at the test inputs Xstar
+    (ns, D), at kernel(q_theta) and the explicit q_v -- ONE `SGPDevice.sample_path` call on meta's engine.  Unlike
+    `sample_posterior` the cost is linear in ns and ns is not limited; the prior part of a draw is its random-feature approximation.
+    Everything random comes from `rng`, in the order path_features, feat_w, eps_v, noise: a seeded generator reproduces the draws
+    bitwise.  Returns samples (n_samples, ns, d_out)."""
+    eng, family, mu_v, Sigma_v, d_out = _path_engine(meta, q_v, q_theta)
+    D = np.asarray(meta.Xu).shape[1]
+    X = np.asarray(Xstar, dtype=np.float64).reshape(-1, D)
+    n_samples, L = int(n_samples), int(features)
+    factor = _noise_factor(meta, q_w, d_out, "sample_paths") if noise else None
+    omega, phase = path_features(family, D, L, rng)
+    feat_w = rng.standard_normal((L, d_out, n_samples))
+    eps_v = rng.standard_normal((mu_v.size, n_samples))
+    smp = eng.sample_path(X, omega, phase, feat_w, eps_v, mu_v, Sigma_v).transpose(2, 0, 1).copy()
+    if noise:
+        smp += rng.standard_normal(smp.shape) @ factor.T
+    return smp
+
+
+def rollout_gpssm_paths(q_x0, steps, n_paths, rng, *, q_v, q_w, q_theta, meta, features=1024, noise=True):
+    """Roll the GP-SSM transition forward along sampled dynamics: n_paths functions f^(j) are drawn ONCE (pathwise samples of the
+    posterior over the transition, d_out must equal D), x_0^(j) ~ q_x0 (one Gaussian), and x_{k+1}^(j) = f^(j)(x_k^(j)) (+ mean(q_W)^-1
+    noise with noise=True) -- the same function at every step, which `forecast_gpssm`'s moment matching cannot express.  Each step is
+    ONE `SGPDevice.sample_path` call that evaluates all paths at the n_paths current states; path j takes its own state's value (the
+    diagonal).  Everything random comes from `rng`.  Returns the trajectories (steps + 1, n_paths, D)."""
+    from .cubature import gaussian_inputs
+    eng, family, mu_v, Sigma_v, d_out = _path_engine(meta, q_v, q_theta)
+    D = np.asarray(meta.Xu).shape[1]
+    if d_out != D:
+        raise ValueError(f"rollout_gpssm_paths: the transition maps D = {D} inputs to d_out = {d_out} outputs; a rollout needs d_out = D")
+    steps, n_paths, L = int(steps), int(n_paths), int(features)
+    factor = _noise_factor(meta, q_w, d_out, "rollout_gpssm_paths") if noise else None
+    m0, S0 = gaussian_inputs([q_x0], D)
+    m0, S0 = np.asarray(m0, dtype=np.float64).reshape(D), np.asarray(S0, dtype=np.float64).reshape(D, D)
+    omega, phase = path_features(family, D, L, rng)
+    feat_w = rng.standard_normal((L, d_out, n_paths))
+    eps_v = rng.standard_normal((mu_v.size, n_paths))
+    traj = np.empty((steps + 1, n_paths, D))
+    traj[0] = m0 + rng.standard_normal((n_paths, D)) @ np.linalg.cholesky(S0).T if np.any(S0) else np.broadcast_to(m0, (n_paths, D))
+    own = np.arange(n_paths)
+    for k in range(steps):
+        f = eng.sample_path(traj[k], omega, phase, feat_w, eps_v, mu_v, Sigma_v)         # (state, output, path)
+        traj[k + 1] = f[own, :, own]
+        if noise:
+            traj[k + 1] += rng.standard_normal((n_paths, D)) @ factor.T
+    return traj
+
+
 def forecast_gpssm(q_x, steps, q_v, q_w, q_theta, meta, noise=True):
     """Roll the GP-SSM transition x_{k+1} ~ MultiSGP(x_k, v, W, theta) forward from q_x -- one Gaussian, or a list of B of them (a
     batch of trajectories) -- in closed form (SE kernel only; d_out must equal D).  Each step is ONE `SGPDevice.psi_predict` call over

@@ -291,6 +291,39 @@ int sgp_sample_f(sgp_handle* h, const double* Xstar, int64_t ns, const double* m
                  double sample_jitter, const double* eps /* R x n_samples, host, standard normals */, int64_t n_samples,
                  double* mean /* ns x d_out, may be NULL */, double* samples /* R x n_samples */, int64_t* info /* 3, may be NULL */);
 
+/* sgp_sample_path: posterior function samples by Matheron's rule over the caller's random Fourier features -- a draw is a finite
+ * set of coefficients evaluated at any number of points in time linear in ns, with no joint covariance and no limit on ns other
+ * than memory.  In the library's parametrisation f_i(x) = k(Xu, x)' v_i + e_i(x), e_i ~ GP(0, k - k' K^-1 k), q(v) = N(mu_v,
+ * Sigma_v), at the CURRENT kernel (family, sigma2, ell, jitter) and K = K_uu + jitter I:
+ *     phi_l(x)  = sqrt(2 sigma2 / L) cos(phase_l + sum_d omega[d,l] x_d / ell_d)     (inputs scaled by 1 / ell once; d ascending,
+ *                                                                                    the sum starts from phase_l)
+ *     v^(j)     = mu_v + L_S eps_v[:, j],  Sigma_v = L_S L_S' (the factor sgp_predict_var forms)
+ *     C_ij      = v_i^(j) - K^-1 Phi_u feat_w[:, i, j],  Phi_u[m,l] = phi_l(Xu_m)    (the K_uu chain's factor, all columns at once)
+ *     samples[i*ns + s, j] = sum_l feat_w[l,i,j] phi_l(x_s) + k(Xu, x_s)' C_ij       (features ascending, then inducing points)
+ * omega (D x L, column-major: feature l's D frequencies contiguous) and phase (L) are the caller's draws from the kernel's spectral
+ * measure on 1/ell-scaled inputs and from U[0, 2 pi) -- so the call is the same for every family --, feat_w (L x d_out x n_samples)
+ * and eps_v (Q x n_samples, Q = d_out M) the caller's standard normals: the library holds no random state.  samples is R x n_samples
+ * column-major, R = ns d_out, row i*ns + s output i at point s as sgp_sample_f.  With feat_w = 0 and eps_v = 0 every column is the
+ * predictive mean up to rounding (a matrix-core sum here, sgp_predict's per-point chain there).
+ * Every sum runs in an order fixed by (L, M, d_out), and a point's rows depend on nothing but that point: not on the chunk it came
+ * in (SGP_PREDICT_CHUNK), not on its position and not on which other points the call holds -- bitwise.  A sample is a function:
+ * evaluating it at points that are only known after earlier evaluations (x_{t+1} = f(x_t)) is a sequence of calls with the same
+ * omega, phase, feat_w and eps_v.  Identical calls agree bitwise.
+ * As sgp_sample_f: blocking; everything in call scratch, nothing the sweep keeps written; the posterior rules and refusals of
+ * sgp_predict_var; ns = 0 returns 0 with nothing done; an installed all-reduce hook is neither called nor a reason to refuse.  The
+ * points go through in chunks and each chunk's result is copied out behind it, so the device scratch is bounded by the chunk, L, M
+ * and d_out n_samples.  Also refused with SGP_ERR_ARG, outputs untouched: flags != 0; a NULL Xstar, omega, phase, feat_w, eps_v or
+ * samples; L < 1 or L > SGP_PATH_MAX_FEATURES; n_samples < 1; d_out n_samples > SGP_PATH_MAX_COLUMNS; a non-finite Xstar, omega,
+ * phase, feat_w or eps_v.  info (2 entries, may be NULL): the failing leading minor (0: none) of K_uu and of Sigma_v; the return
+ * value is the first positive one and sgp_last_error names the matrix. */
+#define SGP_PATH_MAX_FEATURES 16384
+#define SGP_PATH_MAX_COLUMNS 2097152    /* d_out * n_samples */
+int sgp_sample_path(sgp_handle* h, const double* Xstar /* D x ns, host */, int64_t ns, const double* mu_v, const double* Sigma_v,
+                    const double* omega /* D x L, host */, const double* phase /* L */, int32_t L,
+                    const double* feat_w /* L x d_out x n_samples, host */, const double* eps_v /* Q x n_samples, host */,
+                    int64_t n_samples, int32_t flags /* must be 0 */, double* samples /* R x n_samples */,
+                    int64_t* info /* 2, may be NULL */);
+
 /* sgp_in_message: the :in log-messages of many nodes in one call and, with cubature weights, the moment-matched marginals of the
  * Gaussian x log-pdf products -- @rule MultiSGP(:in) (GPnode/MultiSGPnode.jl:162-208) / UniSGP(:in) (GPnode/UniSGPnode.jl:107-122)
  * and ReactiveMP.prod(GenericProd, Gaussian, Continuous*LogPdf) (GPnode/MultiSGPnode.jl:37-44, GPnode/UniSGPnode.jl:39-54).

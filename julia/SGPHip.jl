@@ -198,6 +198,27 @@ function sample_f(h::Handle, Xstar::Matrix{Float64}, eps::Matrix{Float64}, μ_v 
     return mean, samples
 end
 
+# pathwise (Matheron) posterior function samples (sgp_sample_path), call for call with SGPDevice.sample_path: ω (D × L) and phase (L)
+# are the random Fourier features of the current kernel on 1/ℓ-scaled inputs, feat_w (L × d_out × n_samples) and eps_v (Q × n_samples)
+# the caller's standard normals.  Returns samples R × n_samples, row (i - 1) ns + s output i at point s; the same four arrays give
+# the same functions at any other points, and ns is not limited.  Like the rest of this file it has never been executed.
+function sample_path(h::Handle, Xstar::Matrix{Float64}, ω::Matrix{Float64}, phase::Vector{Float64}, feat_w::Array{Float64,3},
+                     eps_v::Matrix{Float64}, μ_v = nothing, Σ_v = nothing)
+    ns = size(Xstar, 2)
+    L = size(ω, 2)
+    (length(phase) == L && size(feat_w, 1) == L && size(feat_w, 2) == h.d_out) || error("sample_path: ω, phase and feat_w disagree on L or d_out")
+    n_samples = size(feat_w, 3)
+    size(eps_v, 2) == n_samples || error("sample_path: eps_v must have n_samples = $n_samples columns")
+    samples = zeros(ns * h.d_out, n_samples)
+    info = zeros(Int64, 2)
+    μp = μ_v === nothing ? C_NULL : Vector{Float64}(μ_v)
+    Σp = Σ_v === nothing ? C_NULL : Matrix{Float64}(Σ_v)
+    check(ccall((:sgp_sample_path, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32,
+                                               Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, Xstar, ns, μp, Σp, ω, phase, Int32(L), feat_w, eps_v, n_samples, Int32(0), samples, info), h.ptr)
+    return samples
+end
+
 # the :in log-messages of many nodes and their moment-matched marginals in one call (include/sgp_hip.h, sgp_in_message): X is
 # D × n, node t owns the columns node_start[t] + 1 : node_start[t + 1] (0-based offsets, n_nodes + 1 entries), y_mean is
 # n_nodes × d_out; weights === nothing returns the closure values alone, else (logpdf, log_norm, mean D × n_nodes,

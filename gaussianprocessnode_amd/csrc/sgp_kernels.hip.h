@@ -1189,14 +1189,11 @@ __device__ __forceinline__ double quad_bcast(double v) {
     return __hiloint2double(hi, lo);
 }
 
-// lane N of each 16-lane DPP row to the whole row (row_newbcast)
+// lane N of each 16-lane DPP row to the whole row (row_newbcast), as ONE instruction: the 64-bit DPP move (v_mov_b64_dpp)
+// takes this control and no other
 template <int N>
 __device__ __forceinline__ double row_bcast(double v) {
-    constexpr int ctrl = 0x150 + N;
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, ctrl, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, ctrl, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
+    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + N, 0xf, 0xf, true);
 }
 
 template <typename F, int... Is>
@@ -1309,30 +1306,52 @@ __device__ __forceinline__ void potf2_tile(double* S, double* Dp, double* rinv, 
                 a[i] = (c <= pr) ? S[(r0 + pr) * LT + 16 * cb + c] : S[(r0 + c) * LT + 16 * cb + pr];
                 lo[i] = 0.0;
             }
-            // The loop is bound by what this one wave can issue (~7 cycles per instruction) and by the LDS crossbar
-            // (ds_bpermute: ~75 cycles, DPP: ~14), so everything that can wait does: the column is kept unnormalised (lo),
-            // lane k keeps pivot k, and 1 / sqrt(d), the scaling of the columns and the failure test happen once after the
-            // 16 pivots, for all of them in parallel.  On the dependent chain: pivot -> v_rcp_f64 -> e = 1 - d r ->
-            // w = e + e^2 -> 1 / d = r (1 + w) (to rounding) -> rank-1 update -> next pivot.
+            // The loop is bound by what this one wave can issue (measured: with the crossbar fetch taken off the dependent
+            // chain at the price of three more instructions per pivot, a run took as long as before; it shortened only once
+            // instructions were removed as well), so everything that can wait does, and nothing is done twice: the
+            // column is kept unnormalised (lo), its diagonal IS pivot k (no separate copy), a row broadcast is one 64-bit DPP
+            // move, and 1 / sqrt(d), the scaling of the columns and the failure test happen once after the 16 pivots, for
+            // all of them in parallel.  On the dependent chain: pivot -> v_rcp_f64 -> e = 1 - d r -> w = e + e^2 ->
+            // 1 / d = r (1 + w) (to rounding) -> rank-1 update -> next pivot.
             // A non-positive pivot is reported and NOT patched: what follows it in the factor is NaN / garbage (LAPACK
             // leaves it undefined).  Finished columns and the rows above the pivot receive garbage updates; nothing reads
             // them again.
-            double dsave = 1.0;
+            //
+            // The crossbar round trip (ds_bpermute: ~75 cycles) is off that chain: column k + 1 is fetched BEFORE update k,
+            // under the reciprocal, and the receiving lane applies update k to the fetched number itself.  That repeats,
+            // operand for operand, the FMA its source lane performs in update k -- a[ki1] of lane (kq1, pr) <-
+            // fma(-dinv, x_k[pr] * y, .) with y = row k of DPP row kq1 = A[k][k + 1] = s: x_k[pr] is the same number in every
+            // lane of row pr, s a readlane, dinv uniform -- so the number is bitwise the one read after the update.  The
+            // fetched register holds entry (pr, k + 1) of the FULL block whatever k + 1 is against pr (the (c <= pr)
+            // mirroring happened at the load above; column k + 1 is live, so every lane's copy has had updates 0 .. k - 1).
+            // (Forming pivot k + 1 ahead of update k as well, fma(-dinv, s * s, A[k + 1][k + 1]), was measured and left out:
+            // no interval shortened with it.)
+            const auto col_fetch = [&](double v, int q_src) {     // v of lane (q_src, pr)
+                const int src = 4 * (16 * q_src + pr);
+                return __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(v)),
+                                        __builtin_amdgcn_ds_bpermute(src, __double2loint(v)));
+            };
+            const auto lane_read = [](double v, int l) {
+                return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+            };
+            double x = col_fetch(a[0], 0);                        // A[pr][0]
             static_for<16>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 constexpr int kq = k & 3, ki = k >> 2;
+                constexpr int k1 = (k + 1) & 15, kq1 = k1 & 3, ki1 = k1 >> 2;
                 // A[k][4 i + pq]: register a[i] of lane (pq, k) -- lane k of this lane's own DPP row
                 double y[4];
 #pragma unroll
                 for (int i = ki; i < 4; ++i) y[i] = row_bcast<k>(a[i]);
-                // A[pr][k]: register a[ki] of lane (kq, pr) -- another DPP row, through the LDS crossbar
-                // (v_permlane32_swap + v_permlane16_swap can do this without LDS, but measured slower: 9.0 vs 7.6 us per tile)
-                const int src = 4 * (16 * kq + pr);
-                const double x = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(a[ki])),
-                                                  __builtin_amdgcn_ds_bpermute(src, __double2loint(a[ki])));
-                const double d = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(a[ki]), 16 * kq + k),
-                                                  __builtin_amdgcn_readlane(__double2loint(a[ki]), 16 * kq + k));
-                dsave = (lane == k) ? d : dsave;
+                // A[pr][k + 1] as it stands BEFORE update k: register a[ki1] of lane (kq1, pr) -- another DPP row, through the
+                // LDS crossbar (v_permlane32_swap + v_permlane16_swap can do this without LDS, but measured slower: 9.0 vs
+                // 7.6 us per tile) -- and, wave-uniform, s = A[k][k + 1]
+                double f = 0.0, s = 0.0;
+                if constexpr (k < 15) {
+                    f = col_fetch(a[ki1], kq1);
+                    s = lane_read(a[ki1], 16 * kq1 + k);
+                }
+                const double d = lane_read(a[ki], 16 * kq + k);
                 // 1 / d = r / (1 - e) = r (1 + e + e^2 + ...), e = 1 - d r ~ 2^-25: two terms past r are exact to rounding
                 const double r = __builtin_amdgcn_rcp(d);
                 const double e = fma(-d, r, 1.0);
@@ -1344,16 +1363,22 @@ __device__ __forceinline__ void potf2_tile(double* S, double* Dp, double* rinv, 
                 // With (x / d) y the two triangles drift apart by rounding, the factor is then that of an LU (column part
                 // kept, row part discarded), L L^T = A holds only to cond * eps, and the Schur complements of an
                 // ill-conditioned K_uu (cond 1e9) came out 1e5 times less accurate (measured: 1e-7 instead of 1e-12).
+                const double xk = x;
+                if constexpr (k < 15) x = fma(-dinv, xk * s, f);  // column k + 1 after update k
 #pragma unroll
-                for (int i = ki; i < 4; ++i) a[i] = fma(-dinv, x * y[i], a[i]);
+                for (int i = ki; i < 4; ++i) a[i] = fma(-dinv, xk * y[i], a[i]);
             });
-            const unsigned long long failed = __ballot(lane < 16 && !(dsave > 0.0));
+            // Pivot k is the diagonal entry of the unnormalised column: lo[k / 4] of lane (k % 4, k) is x_k[k] = A[k][k] = d_k
+            const bool diag = pq == (pr & 3);
+            const double dsave = pr < 8 ? (pr < 4 ? lo[0] : lo[1]) : (pr < 12 ? lo[2] : lo[3]);
+            unsigned long long failed = __ballot(diag && !(dsave > 0.0));       // bit 16 (c % 4) + c: column c
+            failed = (failed | (failed >> 16) | (failed >> 32) | (failed >> 48)) & 0xffffull;
             if (failed != 0ull && lane == 0) {
                 const int bad = __builtin_ctzll(failed);
                 if (col_base + 16 * cb + bad < n_valid) atomicCAS(info, 0, col_base + 16 * cb + bad + 1);
             }
             const double ri = rsqrt_nr(dsave);
-            if (lane < 16) rinv[16 * cb + lane] = ri;
+            if (diag) rinv[16 * cb + pr] = ri;
             __builtin_amdgcn_wave_barrier();                  // (same wave: the LDS queue keeps the order; this keeps the compiler's)
             const double rrow = rinv[16 * cb + pr];
 #pragma unroll

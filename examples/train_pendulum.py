@@ -55,7 +55,7 @@ def inducing_inputs():
 
 
 def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cubature", theta_psi="cubature",
-        in_psi="cubature", forecast=0, rollout_paths=0):
+        in_psi="cubature", forecast=0, rollout_paths=0, forecast_method="exact"):
     from gaussianprocessnode_amd.cubature import srcubature
     from gaussianprocessnode_amd.meta import SMSE, MultiSGPMeta, SEARDKernel, softplus
     from gaussianprocessnode_amd.distributions import PointMass
@@ -78,7 +78,7 @@ def run(epochs=150, nodes=300, seed=124, device_paced=True, jitter=1e-8, psi="cu
         t_smooth = time.perf_counter() - t0
         roll = None
         if forecast > 0:                                      # where will the state be in k steps: closed form, no cubature points
-            f_mean, f_cov = forecast_gpssm(q_x[-1], forecast, q_v, q_w, PointMass(theta), meta)
+            f_mean, f_cov = forecast_gpssm(q_x[-1], forecast, q_v, q_w, PointMass(theta), meta, method=forecast_method)
             roll = {"mean": f_mean[:, 0].tolist(), "std": np.sqrt(np.einsum("kii->ki", f_cov[:, 0])).tolist()}
         paths = None
         if rollout_paths > 0:                                 # the same horizon along sampled dynamics: one function per path
@@ -131,9 +131,13 @@ if __name__ == "__main__":
     ap.add_argument("--forecast", type=int, default=0, metavar="K",
                     help="after smoothing, roll q(x_T) out K steps in closed form (sgp_psi_predict) and print the per-step means and "
                          "standard deviations")
+    ap.add_argument("--forecast-method", choices=("exact", "linearize"), default="exact",
+                    help="the --forecast rollout: moment matching in closed form (sgp_psi_predict), or linearised through the "
+                         "Jacobian of the posterior mean (sgp_predict_grad)")
     ap.add_argument("--rollout-paths", type=int, default=0, metavar="K",
                     help="after smoothing, draw K dynamics functions (pathwise samples, sgp_sample_path) and roll each out from its "
                          "own draw of q(x_T) over the --forecast horizon (10 steps without it); prints the per-step mean and spread")
     args = ap.parse_args()
     print(json.dumps(run(args.epochs, args.nodes, args.seed, not args.host_paced, psi=args.psi, theta_psi=args.theta_psi,
-                         in_psi=args.in_psi, forecast=args.forecast, rollout_paths=args.rollout_paths)))
+                         in_psi=args.in_psi, forecast=args.forecast, rollout_paths=args.rollout_paths,
+                         forecast_method=args.forecast_method)))

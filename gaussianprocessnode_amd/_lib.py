@@ -37,7 +37,7 @@ EXPORTS = [
     "sgp_theta_objective_psi", "sgp_theta_descend_psi", "sgp_psi_in_grad", "sgp_psi_predict",
     "sgp_theta_objective_xu", "sgp_theta_objective_psi_xu", "sgp_inducing_descend", "sgp_inducing_descend_psi",
     "sgp_sweep_plan", "sgp_select_inducing", "sgp_predict_joint", "sgp_sample_f", "sgp_vmp_run",
-    "sgp_vmp_run_t", "sgp_vmp_run_w", "sgp_sample_path",
+    "sgp_vmp_run_t", "sgp_vmp_run_w", "sgp_sample_path", "sgp_predict_grad",
 ]
 # sgp_sweep_plan's bits (SGP_PLAN_* of include/sgp_hip.h), by name
 PLAN_BITS = {"overlapped": 1, "pack": 2, "events": 4, "join_word": 8, "kuu_interleaved": 16, "stats_first": 32, "gate_side": 64,
@@ -144,6 +144,7 @@ def load(build_if_missing: bool = True, variant=None):
     lib.sgp_set_posterior.argtypes = [vp, dp, dp]
     lib.sgp_predict.argtypes = [vp, dp, C.c_int64, dp, dp]
     lib.sgp_predict_var.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int32, dp, dp]
+    lib.sgp_predict_grad.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int32, dp, dp, dp, dp, dp]
     lib.sgp_predict_joint.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int32, dp, dp]
     lib.sgp_sample_f.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int32, C.c_double, dp, C.c_int64, dp, dp, C.POINTER(C.c_int64)]
     lib.sgp_sample_path.argtypes = [vp, dp, C.c_int64, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int64, C.c_int32, dp,

@@ -1,4 +1,4 @@
-// Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_in_message, sgp_in_message_grad,
+// Call-scratch layouts of the blocking point-batch calls (sgp_predict, sgp_predict_var, sgp_predict_grad, sgp_in_message, sgp_in_message_grad,
 // sgp_out_message, sgp_psi_stats / sgp_sweep_local_psi, sgp_theta_objective_psi / sgp_theta_descend_psi, sgp_psi_in_grad,
 // sgp_psi_predict, sgp_theta_objective_xu, sgp_theta_objective_psi_xu, sgp_inducing_descend, sgp_inducing_descend_psi, sgp_predict_joint, sgp_sample_f, sgp_sample_path).  Plain C++, no HIP: all layouts are checked on the host over a grid of shapes by tools/point_scratch_check.cpp (layout_joint: tools/joint_scratch_check.cpp; layout_path: tools/path_scratch_check.cpp).
 #pragma once
@@ -60,6 +60,33 @@ static inline void layout_predict_var(Carver& c, const PointShape& p, PredictVar
     b->LS = c.take<double>((size_t)p.Qp * p.Qp);
     b->Xs = c.take<double>((size_t)p.chunk * p.D);
     b->VarC = c.take<double>((size_t)p.chunk * p.dout * p.dout);
+}
+
+// sgp_predict_grad: sgp_predict_var's pieces (LS only where var is wanted: Sigma_v is factored for it alone), Sigma_v as given where
+// the call uploads one, K_uu^-1 and the matrix A_ij of the output pair at work, and one chunk of the (1 + D)-column panels
+// P = [k | J_1 .. J_D] and U = A_ij P (one U for all pairs) with the chunk's derivative outputs
+struct PredictGradScratch : PredictVarScratch {
+    double* SigP;                   // an explicit Sigma_v padded with the identity, read as given
+    double *Kinv, *A;               // W_K' W_K; A_ij = Sigma_v^(ij) - delta_ij K_uu^-1, zero on the padding
+    double *Pn, *Un;                // per chunk: P and U, [point][1 + D][Mp]
+    double *JacC, *VgC, *JcC;       // per chunk: [point][d_out][D], [point][d_out][d_out][D], [point][d_out D][d_out D]
+};
+static inline void layout_predict_grad(Carver& c, const PointShape& p, bool explicit_qv, bool want_var, bool want_vgrad,
+                                       bool want_jcov, PredictGradScratch* b) {
+    const size_t D = (size_t)p.D, ch = (size_t)p.chunk, o = (size_t)p.dout, mm = (size_t)p.Mp * p.Mp;
+    const bool product = want_vgrad || want_jcov;
+    layout_panel(c, p, b);
+    b->LS = c.take<double>(want_var ? (size_t)p.Qp * p.Qp : 0);
+    b->Xs = c.take<double>(ch * D);
+    b->VarC = c.take<double>(want_var ? ch * o * o : 0);
+    b->SigP = c.take<double>(explicit_qv ? (size_t)p.Qp * p.Qp : 0);
+    b->Kinv = c.take<double>(product ? mm : 0);
+    b->A = c.take<double>(product ? mm : 0);
+    b->Pn = c.take<double>(ch * (1 + D) * p.Mp);
+    b->Un = c.take<double>(product ? ch * (1 + D) * p.Mp : 0);
+    b->JacC = c.take<double>(ch * o * D);
+    b->VgC = c.take<double>(want_vgrad ? ch * o * o * D : 0);
+    b->JcC = c.take<double>(want_jcov ? ch * o * D * o * D : 0);
 }
 
 // sgp_predict_joint and sgp_sample_f (p.n = the test points, p.chunk points per chunk of K(Xu, X*)): the panel's pieces, Sigma_v's

@@ -5054,3 +5054,116 @@ extern "C" int sgp_sample_path(sgp_handle* h, const double* Xstar, int64_t ns, c
     }
     return 0;
 }
+
+// Predictive derivatives at test inputs (include/sgp_hip.h; kernels: k_pgrad_form_A / k_pgrad_finish in sgp_kernels.hip.h).  As
+// sgp_predict_var: blocking, everything at the CURRENT kernel in call scratch, nothing the sweep keeps written (only the parameter
+// mirror dXusK / dParamsK, as sgp_predict), chunked under the same knob.  mean and var come from sgp_predict_var's kernels on the same
+// chunk (bitwise its values); Sigma_v is factored for var alone, the derivative outputs read it as given.  Per chunk the panel
+// P = [k | J] is sgp_in_message_grad's; then, one output pair i <= j after the other, A_ij = Sigma_v^(ij) - delta_ij K_uu^-1,
+// U = A_ij P on the matrix cores into the one U buffer, and the finish launch that writes the pair's entries.  jac needs no product
+// and comes out of the first pair's launch.  The call has no row in the table above StatsRecord (its class in the ledger of exported
+// names, a reader, is entered by tests/predict_grad_ref.py).  It stands behind sgp_sample_path, at the end of this file, and both of
+// its kernels are templates: they are emitted behind everything the sweep launches, whose kernels keep their places in the code object.
+extern "C" int sgp_predict_grad(sgp_handle* h, const double* Xstar, int64_t ns, const double* mu_v, const double* Sigma_v,
+                                int32_t flags, double* mean, double* jac, double* var, double* var_grad, double* jac_cov) {
+    const char* name = "sgp_predict_grad";
+    if (!h || ns < 0 || !Xstar || !jac) return fail(h, SGP_ERR_ARG, "sgp_predict_grad: bad argument (null h, Xstar or jac)");
+    if (flags & ~SGP_PREDICT_NOISE) return fail(h, SGP_ERR_ARG, "sgp_predict_grad: unknown flags");
+    if (int rc = point_call_ready(h, name, mu_v, Sigma_v)) return rc;
+    if (h->family == SGP_KERNEL_MATERN12)
+        return fail(h, SGP_ERR_ARG, "sgp_predict_grad: the Matern-1/2 kernel has no gradient at the inducing inputs");
+    if (ns == 0) return 0;
+    const int M = h->M, Mp = h->Mp, D = h->D, dout = h->dout, Q = h->Q, Qp = h->Qp, T = h->T;
+    for (int64_t e = 0; e < ns * D; ++e)
+        if (!std::isfinite(Xstar[e])) return refuse(h, name, "Xstar must be finite");
+    if (int wrc = point_call_wait(h, mu_v)) return wrc;
+    hipStream_t s = h->own;
+    const bool want_var = var != nullptr, want_vg = var_grad != nullptr, want_jc = jac_cov != nullptr, product = want_vg || want_jc;
+    const int64_t R = (int64_t)dout * D;
+    // per point of a chunk: sgp_predict_var's share, the columns of P and U, the outputs
+    const int64_t per_point = (int64_t)Mp + 4 * T + 4 + D + dout + dout * dout + (int64_t)(product ? 2 : 1) * (1 + D) * Mp + R +
+                              (want_vg ? dout * R : 0) + (want_jc ? R * R : 0);
+    const PointShape shape = point_shape(h, per_point, ns, 0);
+    const int64_t chunk = shape.chunk;
+    PredictGradScratch b;
+    if (int crc = carve_call_scratch(h, [&](Carver& c) { layout_predict_grad(c, shape, mu_v != nullptr, want_var, want_vg, want_jc, &b); }))
+        return crc;
+    // Sigma_v as given stays where it is (the handle's, or the upload in SigP); var's factor is formed in a copy of it
+    const double *dMu, *dSig;
+    if (int rc = resolve_qv(h, mu_v, Sigma_v, b.MuX, b.SigP, &dMu, &dSig)) return rc;
+    if (want_var)
+        hipLaunchKernelGGL(k_pad_square, dim3((unsigned)(((size_t)Qp * Qp + 255) / 256)), dim3(256), 0, s, dSig, Qp, b.LS, Q, Qp);
+    if (int rc = factor_begin(h, s, b)) return rc;
+    if (want_var) {
+        if (int frc = factor_finish(h, s, b, b.LS, Qp, h->TQ, Q, "Sigma_v")) return frc;
+    } else {
+        launch_potrf(b.Kuu, Mp, T, b.Info + 0, M, b.Pscr, s, b.Wk);
+        HIPCHK(h, hipStreamSynchronize(s));
+        HIPCHK(h, hipGetLastError());
+        int info = 0;
+        HIPCHK(h, hipMemcpy(&info, b.Info, sizeof info, hipMemcpyDeviceToHost));
+        if (int frc = factor_status(h, info, "K_uu (current kernel)")) return frc;
+    }
+    OutMat noise;
+    memset(&noise, 0, sizeof noise);
+    if (want_var && (flags & SGP_PREDICT_NOISE) && !invert_outmat(h->hParams->W, dout, &noise))
+        return fail(h, SGP_ERR_ARG, "sgp_predict_grad: the noise matrix of sgp_set_noise is singular");
+    if (product) launch_ata(b.Wk, b.Kinv, Mp, T, s);
+    const unsigned mm_blocks = (unsigned)(((size_t)Mp * Mp + 255) / 256);
+    for (int64_t s0 = 0; s0 < ns; s0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, ns - s0), ncols = nc * (D + 1);
+        HIPCHK(h, hipMemcpyAsync(b.Xs, Xstar + (size_t)s0 * D, sizeof(double) * nc * D, hipMemcpyHostToDevice, s));
+        if (want_var) {
+            panel_pass(h, s, b, b.Xs, dMu, nc, dout == 1 ? b.LS : b.Wk);
+            if (dout == 1)
+                hipLaunchKernelGGL(k_predvar_finish, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, (const double*)b.Pa,
+                                   (const double*)b.Pb, b.VarC, (const Params*)h->dParamsK, noise.v[0], T, nc);
+            else
+                by_dout(dout, [&](auto DO) {
+                    hipLaunchKernelGGL(k_predvar_multi<decltype(DO)::value>, dim3((unsigned)((nc + TB - 1) / TB)), dim3(256), 0, s,
+                                       (const double*)b.LS, (const double*)b.Kc, (const double*)b.Pa, b.VarC, (const Params*)h->dParamsK,
+                                       noise, M, Mp, Q, Qp, T, nc);
+                });
+        } else if (mean) {
+            launch_predict(h, s, h->dXusK, h->dParamsK, b.Xs, dMu, b.MeanC, nc);
+        }
+        by_family(h->family, [&](auto F) {
+            constexpr int FAM = decltype(F)::value;
+            hipLaunchKernelGGL(k_in_grad_panel<FAM>, dim3((unsigned)((nc + 15) / 16), T), dim3(256), 0, s, (const double*)h->dXu,
+                               (const double*)b.Xs, b.Pn, (const Params*)h->dParamsK, M, Mp, D, nc);
+            auto finish = [&](int want_jac, int i, int j) {
+                hipLaunchKernelGGL(k_pgrad_finish<FAM>, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, (const double*)b.Pn,
+                                   product ? (const double*)b.Un : nullptr, dMu, b.JacC, want_vg ? b.VgC : nullptr,
+                                   want_jc ? b.JcC : nullptr, (const Params*)h->dParamsK, want_jac, i, j, M, Mp, D, dout, nc);
+            };
+            if (!product) finish(1, 0, 0);
+            else
+                for (int i = 0; i < dout; ++i)
+                    for (int j = i; j < dout; ++j) {
+                        if (i == j)
+                            hipLaunchKernelGGL(k_pgrad_form_A<true>, dim3(mm_blocks), dim3(256), 0, s, dSig, Qp, (const double*)b.Kinv,
+                                               b.A, i, j, M, Mp);
+                        else
+                            hipLaunchKernelGGL(k_pgrad_form_A<false>, dim3(mm_blocks), dim3(256), 0, s, dSig, Qp, (const double*)b.Kinv,
+                                               b.A, i, j, M, Mp);
+                        hipLaunchKernelGGL(k_in_grad_gemm, dim3((unsigned)((ncols + TB - 1) / TB), T), dim3(256), 0, s,
+                                           (const double*)b.A, (const double*)b.Pn, b.Un, Mp, T, ncols);
+                        finish(i == 0 && j == 0, i, j);
+                    }
+        });
+        HIPCHK(h, hipGetLastError());
+        // mean chunk: [d_out][nc] on the device -> rows s0 .. of the ns x d_out column-major output; the others: contiguous per point
+        if (mean)
+            HIPCHK(h, hipMemcpy2DAsync(mean + s0, sizeof(double) * ns, b.MeanC, sizeof(double) * nc, sizeof(double) * nc, dout,
+                                       hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(jac + (size_t)s0 * R, b.JacC, sizeof(double) * nc * R, hipMemcpyDeviceToHost, s));
+        if (want_var)
+            HIPCHK(h, hipMemcpyAsync(var + (size_t)s0 * dout * dout, b.VarC, sizeof(double) * nc * dout * dout, hipMemcpyDeviceToHost, s));
+        if (want_vg)
+            HIPCHK(h, hipMemcpyAsync(var_grad + (size_t)s0 * dout * R, b.VgC, sizeof(double) * nc * dout * R, hipMemcpyDeviceToHost, s));
+        if (want_jc)
+            HIPCHK(h, hipMemcpyAsync(jac_cov + (size_t)s0 * R * R, b.JcC, sizeof(double) * nc * R * R, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));             // (the next chunk's upload reuses the scratch; pageable host memory)
+    }
+    return 0;
+}

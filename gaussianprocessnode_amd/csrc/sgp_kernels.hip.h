@@ -3679,6 +3679,118 @@ __global__ void __launch_bounds__(256) k_in_grad_finish(const double* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Predictive derivatives at test inputs (sgp_predict_grad).  With k = K(Xu, x), J = dk/dx as above, q(v) = N(mu_v, Sigma_v) and,
+// per output pair (i, j), A_ij = Sigma_v^(ij) - delta_ij K_uu^-1:
+//   jac[d][o]            = J_d' mu^(o)                                              (the mean of the derivative process)
+//   var_grad[i][j][d]    = dC_f[i][j] / dx_d = J_d' A_ij k + k' A_ij J_d
+//   jac_cov[(i,d),(j,e)] = delta_ij delta_de c_fam sigma2 / ell_d^2 + J_d' A_ij J_e,   c_fam = -2 g'(0)
+// The panel P = [k | J] is k_in_grad_panel's and U = A_ij P is k_in_grad_gemm's, one pair i <= j after the other into the same U;
+// k_pgrad_form_A forms A_ij and k_pgrad_finish contracts, one wavefront per point.
+// ------------------------------------------------------------------------------------------------
+// A = Sigma_v^(ib, jb) - (ib == jb ? Kinv : 0) on the leading M x M block, 0 elsewhere.  Sig: leading dimension lds, block (ib, jb) at
+// rows ib M, columns jb M, read as stored (a cross block is not symmetric and is not symmetrised).  DIAG: ib == jb.
+template <bool DIAG>
+__global__ void __launch_bounds__(256) k_pgrad_form_A(const double* __restrict__ Sig, int lds, const double* __restrict__ Kinv,
+                                                      double* __restrict__ A, int ib, int jb, int M, int Mp) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)Mp * Mp) return;
+    const int r = (int)(e % Mp), c = (int)(e / Mp);
+    double v = 0.0;
+    if (r < M && c < M) {
+        v = Sig[(size_t)(jb * M + c) * lds + ib * M + r];
+        if constexpr (DIAG) v -= Kinv[e];
+    }
+    A[e] = v;
+}
+
+// The outputs of the pair (ib, jb), ib <= jb, of N points from their columns of P and U = A_ij P.  One wavefront per point (four per
+// workgroup), lane l the rows l, l + 64, .. < M in order, the 64 partial sums met in an xor butterfly: every sum's order is fixed by
+// M alone, whatever the chunk.  The dot products of one J_d with four neighbouring columns of U run side by side (J_d is read once
+// for the four, four independent fma chains); a column past the last is read clamped and its sum dropped.
+//   want_jac (the first pair's launch, which needs no product: Un may then be null with vgrad and jcov): jac[n][o][d] = J_d . mu^(o)
+//   vgrad: [n][dout][dout][D], entry (ib, jb, d) = sum_m (J_d[m] U_0[m] + k[m] U_d[m]), stored at (ib, jb) and (jb, ib)
+//   jcov:  [n] blocks R x R column-major, R = dout D, row ib D + d: J_d . U_e (+ c_fam sigma2 / ell_d^2 at ib == jb, d == e); for
+//          ib == jb only d <= e is formed; every value is stored at its entry and at the transposed one
+// Each output entry is written by exactly one pair's launch.
+template <int FAM>
+__global__ void __launch_bounds__(256) k_pgrad_finish(const double* __restrict__ Pn, const double* __restrict__ Un,
+                                                      const double* __restrict__ mu, double* __restrict__ jac,
+                                                      double* __restrict__ vgrad, double* __restrict__ jcov,
+                                                      const Params* __restrict__ P, int want_jac, int ib, int jb, int M, int Mp, int D,
+                                                      int dout, int64_t N) {
+    const int lane = threadIdx.x & 63;
+    const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;                                                    // (wave-uniform)
+    auto wave_sum = [](double v) {
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        return v;
+    };
+    const double* Pk = Pn + (size_t)n * (D + 1) * Mp;
+    if (want_jac)
+        for (int o = 0; o < dout; ++o) {
+            const double* mo = mu + (size_t)o * M;
+            for (int d = 0; d < D; ++d) {
+                const double* Jd = Pk + (size_t)(d + 1) * Mp;
+                double a = 0.0;
+                for (int m = lane; m < M; m += 64) a = fma(Jd[m], mo[m], a);
+                a = wave_sum(a);
+                if (lane == 0) jac[((size_t)n * dout + o) * D + d] = a;
+            }
+        }
+    if (!vgrad && !jcov) return;
+    const double* Uk = Un + (size_t)n * (D + 1) * Mp;
+    if (vgrad)
+        for (int d = 0; d < D; ++d) {
+            const double* Jd = Pk + (size_t)(d + 1) * Mp;
+            const double* Ud = Uk + (size_t)(d + 1) * Mp;
+            double a = 0.0;
+            for (int m = lane; m < M; m += 64) a = fma(Jd[m], Uk[m], fma(Pk[m], Ud[m], a));
+            a = wave_sum(a);
+            if (lane == 0) {
+                double* vg = vgrad + (size_t)n * dout * dout * D;
+                vg[((size_t)ib * dout + jb) * D + d] = a;
+                vg[((size_t)jb * dout + ib) * D + d] = a;
+            }
+        }
+    if (!jcov) return;
+    double g0, g1, g2;
+    fam_g012<FAM>(0.0, g0, g1, g2);
+    const double prior = -2.0 * g1 * P->sigma2;                            // c_fam sigma2
+    const size_t R = (size_t)dout * D;
+    double* cv = jcov + (size_t)n * R * R;
+    for (int d = 0; d < D; ++d) {
+        const double* Jd = Pk + (size_t)(d + 1) * Mp;
+        const double ied = P->inv_ell[d] * P->inv_ell[d];
+        for (int e0 = (ib == jb ? d : 0); e0 < D; e0 += 4) {
+            const double* u0 = Uk + (size_t)(e0 + 1) * Mp;
+            const double* u1 = Uk + (size_t)(min(e0 + 1, D - 1) + 1) * Mp;
+            const double* u2 = Uk + (size_t)(min(e0 + 2, D - 1) + 1) * Mp;
+            const double* u3 = Uk + (size_t)(min(e0 + 3, D - 1) + 1) * Mp;
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            for (int m = lane; m < M; m += 64) {
+                const double j = Jd[m];
+                a0 = fma(j, u0[m], a0);
+                a1 = fma(j, u1[m], a1);
+                a2 = fma(j, u2[m], a2);
+                a3 = fma(j, u3[m], a3);
+            }
+            a0 = wave_sum(a0);
+            a1 = wave_sum(a1);
+            a2 = wave_sum(a2);
+            a3 = wave_sum(a3);
+            if (lane < 4 && e0 + lane < D) {
+                const int e = e0 + lane;
+                double v = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
+                if (ib == jb && d == e) v = fma(prior, ied, v);
+                const size_t row = (size_t)ib * D + d, col = (size_t)jb * D + e;
+                cv[col * R + row] = v;
+                cv[row * R + col] = v;
+            }
+        }
+    }
+}
+
 // transpose-copy of a square column-major matrix (Uv = L_R^T on the way out)
 __global__ void __launch_bounds__(256) k_transpose(const double* __restrict__ A, double* __restrict__ At, int ld) {
     __shared__ double tile[TB * (TB + 1)];

@@ -308,6 +308,30 @@ class SGPDevice:
         self._check(self._lib.sgp_predict_var(self._h, ptr(Xs), ns, ptr(mu), ptr(S), flags, ptr(mean), ptr(var)), "sgp_predict_var")
         return (mean[0], var) if self.d_out == 1 else (mean.T.copy(), var)
 
+    def predict_grad(self, Xstar, mu_v=None, Sigma_v=None, *, noise: bool = False, var: bool = True, var_grad: bool = True,
+                     jac_cov: bool = False):
+        """Predictive derivatives at Xstar (sgp_predict_grad), at the current kernel: (mean, jac, var, var_grad, jac_cov) with mean
+        (ns, d_out), jac (ns, d_out, D) = d mean / d x, var (ns, d_out, d_out) bitwise `predict_var`'s, var_grad (ns, d_out, d_out, D)
+        = d var / d x and jac_cov (ns, d_out D, d_out D), the covariance of vec(df/dx) with row index i D + d, exactly symmetric;
+        an output not asked for is None.  q(v) is the last sweep's (mu_v = Sigma_v = None) or the one given; noise=True adds W^-1
+        of the last `set_noise` to var.  The Matern-1/2 family is refused."""
+        Xs = np.asarray(Xstar, dtype=np.float64)
+        if Xs.ndim == 1 and self.D == 1:
+            Xs = Xs.reshape(-1, 1)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"predict_grad: Xstar must be (ns, D) = (ns, {self.D}), got {Xs.shape}")
+        Xs = as_f64(Xs)
+        ns, o, D = Xs.shape[0], self.d_out, self.D
+        mu, S = self._qv_args("predict_grad", mu_v, Sigma_v)
+        mean, jac = np.empty((o, ns)), np.empty((ns, o, D))
+        v = np.empty((ns, o, o)) if var else None
+        vg = np.empty((ns, o, o, D)) if var_grad else None
+        jc = np.empty((ns, o * D, o * D)) if jac_cov else None
+        flags = _lib.SGP_PREDICT_NOISE if noise else 0
+        self._check(self._lib.sgp_predict_grad(self._h, ptr(Xs), ns, ptr(mu), ptr(S), flags, ptr(mean), ptr(jac), ptr(v), ptr(vg),
+                                               ptr(jc)), "sgp_predict_grad")
+        return mean.T.copy(), jac, v, vg, jc
+
     def predict_joint(self, Xstar, mu_v=None, Sigma_v=None, noise: bool = False):
         """Predictive mean and JOINT covariance of the latent f over all of Xstar (sgp_predict_joint), at the current kernel:
         (mean, cov) with mean (ns,) for d_out = 1 and (ns, d_out) otherwise, cov (R, R), R = ns * d_out, exactly symmetric; row

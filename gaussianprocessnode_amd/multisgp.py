@@ -219,7 +219,7 @@ def exact_predictive(eng, x, q_v, D: int, noise: bool, device: int):
 
 
 def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, noise: bool = True, psi: str = "cubature",
-               joint: bool = False):
+               joint: bool = False, grad: bool = False):
     """Predictive means and covariances of the d_out latent outputs (noise=False) or of the observation (noise=True: +
     mean(q_w)^-1) at kernel(q_theta) and the explicit q_v (sgp_predict_var).  Test inputs (ns, D) give means (ns, d_out) and
     covariances (ns, d_out, d_out); a PointMass or an uncertain input q(x*) gives one mean (d_out,) and covariance (d_out,
@@ -227,12 +227,26 @@ def predictive(Xstar_or_q_in, q_v, q_w, q_theta: PointMass, meta: MultiSGPMeta, 
     psi="exact" (SE kernel only) takes a Gaussian, a PointMass, a plain array or a list of inputs through ONE closed-form
     `SGPDevice.psi_predict` call instead -- no cubature points; a list gives stacked means (T, d_out) and covariances.
     joint=True (point inputs (ns, D) only) returns the means (ns, d_out) and the JOINT (ns d_out, ns d_out) covariance over all
-    test points instead (`SGPDevice.predict_joint`: row i ns + s is output i at point s)."""
+    test points instead (`SGPDevice.predict_joint`: row i ns + s is output i at point s).  grad=True (point inputs or a PointMass)
+    returns (means (ns, d_out), covariances (ns, d_out, d_out), Jacobians (ns, d_out, D), covariance gradients (ns, d_out, d_out, D)):
+    the prediction with its derivatives with respect to the test input (`SGPDevice.predict_grad`; SE, Matern-3/2, Matern-5/2)."""
     from .unisgp import _test_points, combine_total_variance, joint_points
     _check_psi(psi, "predictive")
     W = _mean_W(q_w)
     d_out = W.shape[0]
     D = np.asarray(meta.Xu).shape[1]
+    if joint and grad:
+        raise ValueError("predictive: pass joint=True or grad=True, not both")
+    if grad:
+        X = joint_points(Xstar_or_q_in, psi, D, "grad")
+        eng = _engine(meta, 1, d_out)
+        sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+        if noise:
+            eng.set_noise(W)
+        mu_v, Sigma_v = q_v.mean_cov()
+        m, jac, var, vg, _ = eng.predict_grad(X, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64), noise=noise)
+        return m, var, jac, vg
     if joint:
         X = joint_points(Xstar_or_q_in, psi, D)
         eng = _engine(meta, 1, d_out)

@@ -930,17 +930,31 @@ def rollout_gpssm_paths(q_x0, steps, n_paths, rng, *, q_v, q_w, q_theta, meta, f
     return traj
 
 
-def forecast_gpssm(q_x, steps, q_v, q_w, q_theta, meta, noise=True):
+def linearize_step(mean, jac, var, S):
+    """One linearised (EKF-style) step through the GP for B Gaussians N(m_b, S_b): `predict_grad`'s mean (B, d_out), jac
+    (B, d_out, D) and var (B, d_out, d_out) at the m_b give (mean, Jac S Jac' + var), every covariance exactly symmetric."""
+    jac = np.asarray(jac, dtype=np.float64)
+    P = np.einsum("bid,bde,bje->bij", jac, np.asarray(S, dtype=np.float64), jac)
+    return np.asarray(mean, dtype=np.float64), 0.5 * (P + P.transpose(0, 2, 1)) + np.asarray(var, dtype=np.float64)
+
+
+def forecast_gpssm(q_x, steps, q_v, q_w, q_theta, meta, noise=True, method="exact"):
     """Roll the GP-SSM transition x_{k+1} ~ MultiSGP(x_k, v, W, theta) forward from q_x -- one Gaussian, or a list of B of them (a
     batch of trajectories) -- in closed form (SE kernel only; d_out must equal D).  Each step is ONE `SGPDevice.psi_predict` call over
     the B current Gaussians: Gaussian in, moment-matched Gaussian out, x_{k+1} ~ N(mean, C_f + mean(q_W)^-1) (noise=False leaves the
     process noise out: the latent f alone).  No cubature points are formed.  q(v) is installed through `set_posterior` on the
-    auxiliary engine once.  Returns (means (steps, B, D), covariances (steps, B, D, D))."""
+    auxiliary engine once.  Returns (means (steps, B, D), covariances (steps, B, D, D)).
+    method="linearize" propagates through the Jacobian of the posterior mean instead (EKF-style), for the SE, Matern-3/2 and
+    Matern-5/2 kernels: each step is ONE `SGPDevice.predict_grad` call over the B current means, m' = mean(m),
+    S' = Jac S Jac' + C_f(m) (+ mean(q_W)^-1 with noise=True), with the explicit q(v)."""
     from . import multisgp as MS
     from .cubature import gaussian_inputs, require_se
     from .device import potrf
     from .meta import kernel_family, set_engine_kernel
-    require_se(kernel_family(meta.kernel))
+    if method not in ("exact", "linearize"):
+        raise ValueError(f"forecast_gpssm: method must be 'exact' or 'linearize', not {method!r}")
+    if method == "exact":
+        require_se(kernel_family(meta.kernel))
     q0 = list(q_x) if isinstance(q_x, (list, tuple)) else [q_x]
     D = np.asarray(meta.Xu).shape[1]
     W = MS._mean_W(q_w)
@@ -957,6 +971,13 @@ def forecast_gpssm(q_x, steps, q_v, q_w, q_theta, meta, noise=True):
     eng.set_noise(W)
     mu_v, Sigma_v = q_v.mean_cov()
     mu_v = np.asarray(mu_v, dtype=np.float64).ravel()
+    if method == "linearize":
+        Sigma_v = np.asarray(Sigma_v, dtype=np.float64)
+        for k in range(steps):
+            mean, jac, var, _, _ = eng.predict_grad(m, mu_v, Sigma_v, noise=noise, var=True, var_grad=False)
+            m, S = linearize_step(mean, jac, var, S)
+            means[k], covs[k] = m, S
+        return means, covs
     eng.set_posterior(mu_v, potrf(np.asarray(Sigma_v, dtype=np.float64) + np.outer(mu_v, mu_v), meta.device).T)
     for k in range(steps):
         m, S, _ = eng.psi_predict(m, S, noise=noise)

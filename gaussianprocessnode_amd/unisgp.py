@@ -407,18 +407,21 @@ def combine_total_variance(wts, m, var):
     return mean, second - np.outer(mean, mean)
 
 
-def joint_points(Xstar, psi: str, D: int):
-    """The test inputs of predictive(..., joint=True): a plain (ns, D) array -- joint covariances at Gaussian inputs are not
-    covered (their per-point counterpart is psi="exact")."""
+def joint_points(Xstar, psi: str, D: int, what: str = "joint"):
+    """The test inputs of predictive(..., joint=True) or (..., grad=True): a plain (ns, D) array (a PointMass gives its point) --
+    joint covariances and derivatives at Gaussian inputs are not covered (their per-point counterpart is psi="exact")."""
     if psi != "cubature":
-        raise ValueError("predictive: joint=True takes point inputs (ns, D) only (psi must be 'cubature')")
+        raise ValueError(f"predictive: {what}=True takes point inputs (ns, D) only (psi must be 'cubature')")
+    if what == "grad" and type(Xstar).__name__ == "PointMass":
+        Xstar = Xstar.mean()
     try:
         return np.asarray(Xstar, dtype=np.float64).reshape(-1, D)
     except (TypeError, ValueError):
-        raise ValueError("predictive: joint=True takes point inputs (ns, D) only") from None
+        raise ValueError(f"predictive: {what}=True takes point inputs (ns, D) only") from None
 
 
-def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool = True, psi: str = "cubature", joint: bool = False):
+def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool = True, psi: str = "cubature", joint: bool = False,
+               grad: bool = False):
     """Predictive mean and variance of the latent f (noise=False) or of the observation y (noise=True: + 1 / mean(q_w)) at
     kernel(q_theta) and the explicit q_v (`q_v.mean_cov()` goes to the device, sgp_predict_var).  Test inputs (ns, D) give
     per-point arrays (ns,), (ns,); a PointMass or an uncertain input q(x*) gives two floats -- the latter by one device call over
@@ -426,10 +429,24 @@ def predictive(Xstar_or_q_in, q_v, q_w, q_theta, meta: UniSGPMeta, noise: bool =
     message carries precision mean(q_w) only).  psi="exact" (SE kernel only) takes a Gaussian, a PointMass, a plain array or a
     list of inputs through ONE closed-form `SGPDevice.psi_predict` call on the auxiliary engine instead -- no cubature points; a
     list gives per-input arrays (T,), (T,).  joint=True (point inputs (ns, D) only) returns the mean (ns,) and the JOINT (ns, ns)
-    covariance over all test points instead (`SGPDevice.predict_joint`; the noise enters its diagonal)."""
+    covariance over all test points instead (`SGPDevice.predict_joint`; the noise enters its diagonal).  grad=True (point inputs
+    or a PointMass) returns (mean (ns,), var (ns,), dmean (ns, D), dvar (ns, D)): the prediction with its derivatives with respect to
+    the test input (`SGPDevice.predict_grad`; SE, Matern-3/2 and Matern-5/2)."""
     D = meta.Xu.shape[1]
     if psi not in ("cubature", "exact"):
         raise ValueError(f"predictive: psi must be 'cubature' or 'exact', got {psi!r}")
+    if joint and grad:
+        raise ValueError("predictive: pass joint=True or grad=True, not both")
+    if grad:
+        X = joint_points(Xstar_or_q_in, psi, D, "grad")
+        eng = _engine(meta, 1)
+        sigma2, ell = meta.kernel(np.atleast_1d(np.asarray(q_theta.mean(), dtype=np.float64)))
+        set_engine_kernel(eng, sigma2, ell, meta.jitter, kernel_family(meta.kernel))
+        if noise:
+            eng.set_noise([[_mean_w(q_w)]], _elog_w(q_w))
+        mu_v, Sigma_v = q_v.mean_cov()
+        m, jac, var, vg, _ = eng.predict_grad(X, np.asarray(mu_v, dtype=np.float64), np.asarray(Sigma_v, dtype=np.float64), noise=noise)
+        return m[:, 0].copy(), var[:, 0, 0].copy(), jac[:, 0, :].copy(), vg[:, 0, 0, :].copy()
     if joint:
         X = joint_points(Xstar_or_q_in, psi, D)
         eng = _engine(meta, 1)

@@ -378,6 +378,41 @@ int sgp_in_message(sgp_handle* h, const double* X, int64_t n, const int64_t* nod
 int sgp_in_message_grad(sgp_handle* h, const double* X, int64_t n, const int64_t* node_start, int64_t n_nodes, const double* y_mean,
                         const double* mu_v, const double* Sigma_v, double* logpdf, double* grad, double* hess);
 
+/* sgp_predict_grad: how the prediction changes when the test input moves -- the Jacobian of the posterior mean, the gradient of
+ * the predictive covariance and the covariance of the derivative process df/dx, at many test inputs in one call.  With k = k(Xu, x),
+ * J = dk/dx (M x D, as sgp_in_message_grad defines it per family), Kinv = (K_uu + jitter I)^-1 and q(v) = N(mu_v, Sigma_v), block
+ * (i, j) of Sigma_v written Sigma^(ij), everything at the CURRENT kernel (family, sigma2, ell, jitter):
+ *     mean[s, o]            = k' mu^(o)                                          (bitwise what sgp_predict returns)
+ *     jac[d, o, s]          = J_d' mu^(o)                                        (also the mean of the derivative process)
+ *     var                   = C_f, bitwise what sgp_predict_var returns for the same arguments and flags
+ *     var_grad[s][i][j][d]  = dC_f[i][j] / dx_d = J_d' A_ij k + k' A_ij J_d,     A_ij = Sigma^(ij) - delta_ij Kinv
+ *                           = J_d' (Sigma^(ij) + Sigma^(ji)) k - 2 delta_ij J_d' Kinv k
+ *     jac_cov[s]((i,d),(j,e)) = delta_ij delta_de c_fam sigma2 / ell_d^2 + J_d' A_ij J_e,   c_fam = -2 g'(0): SE 1, Matern-3/2 3,
+ *                             Matern-5/2 5/3                                     (the covariance of vec(df/dx), row index i D + d)
+ * Layout: Xstar D x ns and mean ns x d_out as sgp_predict; jac D x d_out x ns column-major; var as sgp_predict_var; var_grad D x ns
+ * for d_out = 1 and [ns][d_out][d_out][D] otherwise, entries (i, j) and (j, i) the same double; jac_cov [ns] blocks of
+ * (d_out D) x (d_out D), column-major, every block exactly symmetric (i <= j, and for i = j d <= e, are computed and mirrored on
+ * store).  mean, var, var_grad and jac_cov may each be NULL; an output does not depend on which of the others are asked for.
+ * SGP_PREDICT_NOISE affects var only (the noise does not depend on x).  One linearised (EKF-style) step through the GP is
+ * m' = mean(m), S' = Jac S Jac' + C_f(m).
+ * As sgp_predict_var: blocking; everything in call scratch, nothing the sweep keeps written (sgp_sweep_kind, the resident statistics,
+ * the K_uu chain, q(v) and the theta objective are unaffected); an installed all-reduce hook is neither called nor a reason to
+ * refuse; the same posterior rules and refusals (both of mu_v and Sigma_v or neither, NULL after sgp_set_posterior until the next
+ * sweep, NULL before any sweep, an open sgp_train_* run).  A K_uu that is not positive definite returns its failing leading minor
+ * k > 0; Sigma_v is factored only when var is wanted, and then its failing minor is returned too -- the derivative outputs read
+ * Sigma_v as given (a cross block is read as stored, not symmetrised).  SGP_ERR_ARG, outputs untouched: a NULL h, Xstar or jac;
+ * unknown flag bits; a non-finite Xstar; SGP_KERNEL_MATERN12 (a kink at every inducing input, as sgp_in_message_grad).  ns = 0
+ * returns 0 with nothing done.
+ * The points go through in chunks (SGP_PREDICT_CHUNK) and each chunk's results are copied out behind it, so ns is bounded by host
+ * memory only.  The output pairs i <= j are processed one after another: one product U = A_ij [k | J] on the FP64 matrix cores and
+ * one wavefront-per-point contraction each.  No atomics; every sum runs in an order fixed by (M, D, d_out): a point's results do not
+ * depend on its chunk, its position or the other points, bitwise, and identical calls agree bitwise. */
+int sgp_predict_grad(sgp_handle* h, const double* Xstar /* D x ns, host */, int64_t ns, const double* mu_v, const double* Sigma_v,
+                     int32_t flags /* 0 | SGP_PREDICT_NOISE */, double* mean /* ns x d_out, may be NULL */,
+                     double* jac /* D x d_out x ns column-major, required */, double* var /* as sgp_predict_var, may be NULL */,
+                     double* var_grad /* d_out = 1: D x ns; else [ns][d_out][d_out][D]; may be NULL */,
+                     double* jac_cov /* [ns] blocks (d_out D) x (d_out D) column-major; may be NULL */);
+
 /* sgp_out_message: the :out messages of many nodes with uncertain inputs in one call -- @rule MultiSGP(:out)
  * (GPnode/MultiSGPnode.jl:90-120) / UniSGP(:out) with a Gaussian input (GPnode/UniSGPnode.jl:85-93): the mean Psi1' mu_v^(d) with
  * Psi1 = sum_s omega_s k(Xu, x_s) over the node's cubature points (approximate_kernel_expectation!).  X is D x n and node t owns the

@@ -179,6 +179,29 @@ function predict_joint(h::Handle, Xstar::Matrix{Float64}, μ_v = nothing, Σ_v =
     return mean, cov
 end
 
+# predictive derivatives at test inputs (include/sgp_hip.h, sgp_predict_grad), call for call with the Python layer's
+# SGPDevice.predict_grad: mean ns × d_out, jac D × d_out × ns (∂mean_o/∂x_d), var d_out × d_out × ns, var_grad D × d_out × d_out × ns
+# (∂C_f[i, j]/∂x_d; C_f is symmetric, so the column-major reading of the C layout is the same array) and jac_cov
+# (d_out D) × (d_out D) × ns, the covariance of vec(∂f/∂x) with 0-based row index i D + d, exactly symmetric.  An output that is
+# switched off is `nothing`.  Like the rest of this file it has never been executed: only the ccall signature is stated here.
+function predict_grad(h::Handle, Xstar::Matrix{Float64}, μ_v = nothing, Σ_v = nothing; noise::Bool = false, var::Bool = true,
+                      var_grad::Bool = true, jac_cov::Bool = false)
+    D, ns = size(Xstar)
+    o = h.d_out
+    mean = zeros(ns, o)
+    jac = zeros(D, o, ns)
+    v = var ? zeros(o, o, ns) : nothing
+    vg = var_grad ? zeros(D, o, o, ns) : nothing
+    jc = jac_cov ? zeros(o * D, o * D, ns) : nothing
+    μp = μ_v === nothing ? C_NULL : Vector{Float64}(μ_v)
+    Σp = Σ_v === nothing ? C_NULL : Matrix{Float64}(Σ_v)
+    check(ccall((:sgp_predict_grad, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+                                                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, Xstar, ns, μp, Σp, Int32(noise ? 1 : 0), mean, jac, v === nothing ? C_NULL : v, vg === nothing ? C_NULL : vg,
+                jc === nothing ? C_NULL : jc), h.ptr)
+    return mean, jac, v, vg, jc
+end
+
 # posterior function samples (sgp_sample_f), call for call with SGPDevice.sample_f: samples[:, k] = vec(mean) + L_C eps[:, k] with
 # L_C L_C' = cov + sample_jitter I and the caller's standard normals eps (R × n_samples; the library holds no random state)
 function sample_f(h::Handle, Xstar::Matrix{Float64}, eps::Matrix{Float64}, μ_v = nothing, Σ_v = nothing; sample_jitter::Float64 = 0.0,

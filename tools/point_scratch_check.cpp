@@ -1,5 +1,5 @@
 // Host check of the point-batch calls' scratch layouts (gaussianprocessnode_amd/csrc/point_scratch.h): over grids of shapes, the
-// pieces that layout_predict, layout_predict_var, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad, layout_psi_theta_xu, layout_inducing_descend and layout_psi_inducing_descend hand out are
+// pieces that layout_predict, layout_predict_var, layout_predict_grad, layout_in_message, layout_in_message_grad, layout_out_message, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad, layout_psi_theta_xu, layout_inducing_descend and layout_psi_inducing_descend hand out are
 // pairwise disjoint at the sizes their consumers need (stated here independently of the layout functions), every piece starts a
 // multiple of Carver::ALIGN doubles from the base, pass 2 hands out the total pass 1 summed and the last piece ends there.  The
 // panel layouts are checked over one allocation of the grid's largest total; the mean-only layouts, layout_psi, layout_psi_theta, layout_psi_in, layout_psi_predict, layout_xu_grad, layout_psi_theta_xu and the two inducing-descent layouts get an allocation of
@@ -110,6 +110,24 @@ void check_panel_shape(const PointShape& s, double* base, size_t capacity, size_
                            {"HessC", b.HessC, ch * D * D * d}});
         return p;
     }));
+    // sgp_predict_grad: every combination of an explicit q(v) and the three optional outputs (a piece that is not wanted has no size
+    // and is not listed)
+    for (int mask = 0; mask < 16; ++mask) {
+        const bool ex = mask & 1, var = mask & 2, vg = mask & 4, jc = mask & 8, product = vg || jc;
+        *largest = std::max(*largest, check("predict_grad", s, 0, base, capacity, false, [&](Carver& c) {
+            PredictGradScratch b;
+            layout_predict_grad(c, s, ex, var, vg, jc, &b);
+            const size_t o = (size_t)s.dout, QQ = (size_t)s.Qp * s.Qp;
+            std::vector<Piece> p = panel_pieces(s, b);
+            p.insert(p.end(), {{"Xs", b.Xs, ch * D * d}, {"Pn", b.Pn, ch * (1 + D) * Mp * d}, {"JacC", b.JacC, ch * o * D * d}});
+            if (var) p.insert(p.end(), {{"LS", b.LS, QQ * d}, {"VarC", b.VarC, ch * o * o * d}});
+            if (ex) p.push_back({"SigP", b.SigP, QQ * d});
+            if (product) p.insert(p.end(), {{"Kinv", b.Kinv, Mp * Mp * d}, {"A", b.A, Mp * Mp * d}, {"Un", b.Un, ch * (1 + D) * Mp * d}});
+            if (vg) p.push_back({"VgC", b.VgC, ch * o * o * D * d});
+            if (jc) p.push_back({"JcC", b.JcC, ch * o * D * o * D * d});
+            return p;
+        }));
+    }
 }
 
 // every shape of the panel grid: pass 0 finds the largest total, pass 1 checks over one allocation of that size
